@@ -1,21 +1,26 @@
 #!/usr/bin/env python3
 """bench.py -- chars/sec through forward + BPTT + Adagrad on the BASELINE headline workload.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one training window: slide, forward over S-1 timesteps, loss, BPTT, [RCCL all-reduce of
 the flat gradient block], Adagrad -- everything the reference's i-loop does per iteration
 (OV/lstm_eigen_opt/lstm.cc:186-318).  Workload = BASELINE.json configs[2] (the config the metric is
 quoted on): hidden 512, window 100, batch 64 per GPU, fp32.  The corpus is synthetic (1e6 bytes drawn
-with enwik6's order-0 byte statistics): /root/reference does not exist on the GPU box and the
+with enwik6's order-0 byte statistics): the reference's corpora are not part of this repository and the
 throughput is content-independent.  For N > 1 the driver launches one rank per GPU with
 torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_PORT from the env).  The ranks exchange only
 the RCCL id, barriers and a few doubles, over dp.Rendezvous (plain sockets): the GPU processes do not import
 torch, so the library's HIP runtime and RCCL are the only copies mapped.  The data path is the C-ABI library
 and RCCL inside it.
 
-Prints ONE JSON line on rank 0 (see the task contract), including
+A plain run does what the headline figure needs: set-up, --sustained-seconds of windows to bring the GPU to its
+operating clocks, the W warm-up and the K timed windows from the seeded initial state, and ONE JSON line on rank 0
+(see the task contract).  --dump-outputs DIR writes what the last timed window left behind (see dump_outputs).
+--full adds the measurements that take runs of their own:
+  sustained    : the clock warm-up leg timed as a measurement of its own (at least K windows)
   roofline     : the dominant kernel's algorithmic FLOP per launch / its HIP-event-timed duration
+  kernels_us   : every kernel's HIP-event time, in a profiling pass after the timed windows
   cpu_baseline : the CPU oracle (oracle/, a port of the reference's loop) timed on this host
 """
 import argparse
@@ -38,8 +43,9 @@ METRIC = "chars/sec fwd+BPTT, enwik6 H=512 S=100 B=64, 1/2/4/8 GPU"
 PEAK_FP32_MFMA_TFLOPS = 157.3  # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32 / 16x16x4_f32 dense peak
 
 # BASELINE.json `configs`, by index.  The corpora are synthetic stand-ins of the named file's length (enwik6's order-0
-# byte statistics): /root/reference does not travel to the GPU box, enwik7 is absent even there, and the
-# throughput does not depend on the content.  configs[3] is configs[2] under `--gpus 8` (the driver's run).
+# byte statistics): the reference's corpora are not part of this repository, enwik7 is absent even from the reference
+# (SURVEY 8d), and the throughput does not depend on the content.  configs[3] is configs[2] under `--gpus 8` (the
+# driver's run).
 CONFIGS = {
     0: dict(label="configs[0]: alice29.txt, hidden=128 seq=25 batch=1, fp32 (the `lstm.cc as-is` row)", N=128, S=25, B=1,
             nbytes=152_089, corpus="alice29"),
@@ -130,6 +136,22 @@ def cpu_baseline(N, S, B, text, lr, budget_s=20.0):
     return out
 
 
+MAX_DUMP_BYTES = 60 << 20  # the files of --dump-outputs stay under 64 MB
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: each array as DIR/<name>.npy (float32 / float64).  If together they exceed MAX_DUMP_BYTES, each is
+    cut to a fixed, seeded sample of its flat elements: one element from every run of `step`, in index order."""
+    os.makedirs(d, exist_ok=True)
+    step = -(-sum(a.nbytes for a in arrays.values()) // MAX_DUMP_BYTES)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        if step > 1:
+            k = max(1, a.size // step)
+            a = a.ravel()[np.arange(k) * step + np.random.RandomState(0).randint(0, min(step, a.size), k)]
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -141,8 +163,9 @@ def main():
     ap.add_argument("--seq", type=int, default=None, help="override the config's window length")
     ap.add_argument("--batch", type=int, default=None, help="override: streams per GPU (weak scaling)")
     ap.add_argument("--sustained-seconds", type=float, default=2.0,
-                    help="after the K timed steps, a second timed region of at least this many seconds (0 = skip)")
-    ap.add_argument("--cpu-budget", type=float, default=20.0, help="seconds of CPU work for the cpu_baseline leg")
+                    help="before the warm-up, this many seconds of windows to bring the GPU to its operating clocks; with "
+                         "--full also timed as the `sustained` figure, over at least K windows (0 = skip)")
+    ap.add_argument("--cpu-budget", type=float, default=20.0, help="seconds of CPU work for the cpu_baseline leg (--full)")
     ap.add_argument("--lr", type=float, default=0.01,
                     help="Adagrad step; 0.1 (R/lstm.cc:59) overflows the unshifted softmax at hidden=512 batch=64 "
                          "within ~100 windows unless the class_CUDA warm-up (lr=0 for 50*S windows) is used")
@@ -150,8 +173,12 @@ def main():
     ap.add_argument("--bf16", action="store_true", help="bf16 MFMA in the recurrent products (not the headline dtype)")
     ap.add_argument("--fp32", action="store_true", help="force the fp32 path on a config whose named dtype is bf16 (configs[4]: the "
                                                          "fp32 line beside the bf16 one)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--profile-windows", type=int, default=3)
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline leg")
+    ap.add_argument("--profile-windows", type=int, default=3, help="windows of the --full per-kernel profiling pass")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the `sustained` figure, per-kernel times, the roofline and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -189,10 +216,9 @@ def main():
         args.bf16 = False
         args.flags &= ~128
         L = lstm_hip.Lstm(N, S, B, device=local_rank, flags=args.flags)
-    rng = lstm_hip.MT19937Normal(1)
-    L.set_params(lstm_hip.init_params(rng, N))  # identical on every rank
+    P0 = lstm_hip.init_params(lstm_hip.MT19937Normal(1), N)  # identical on every rank
     srng = lstm_hip.MT19937Normal(1000 + rank)
-    L.set_state(1, srng.randn(N, B, 0.0, 0.1), srng.randn(N, B, 0.0, 0.1))  # becomes column 0 after the first slide
+    h1, c1 = srng.randn(N, B, 0.0, 0.1), srng.randn(N, B, 0.0, 0.1)  # column 1: becomes column 0 after the first slide
     L.set_text(text)
     # Steady state from the first timed window on, whatever --warmup is: the window is uploaded FULL, as S slides from the
     # start cursors c0 would have left it (OV/lstm_eigen_opt/lstm.cc:190-213: target[t] = text[c0+t], x[t] = target[t-1]),
@@ -201,8 +227,18 @@ def main():
     tt = np.arange(S, dtype=np.int64)[:, None]
     ti0 = text[(c0[None, :] + tt) % len(text)].astype(np.int32)
     xi0 = text[(c0[None, :] + tt - 1) % len(text)].astype(np.int32)
-    L.set_window(xi0, ti0)
-    L.set_cursors(((c0 + S) % len(text)).astype(np.uint64))
+
+    def initial_state():
+        """the seeded start of every window sequence: parameters, zero Adagrad memory (as a new handle has it), carry,
+        full window (ring head 0), cursors.  The timed windows start here whatever the clock warm-up ran before them,
+        so the same arguments give the same inputs and outputs on every run."""
+        L.set_params(P0)
+        L.set_params(np.zeros_like(P0), lstm_hip.P_MEM)
+        L.set_state(1, h1, c1)
+        L.set_window(xi0, ti0)
+        L.set_cursors(((c0 + S) % len(text)).astype(np.uint64))
+
+    initial_state()
     L.set_global_batch(world * B)
     if world > 1:
         L.comm_init(rdzv.broadcast(lstm_hip.comm_unique_id() if rank == 0 else None), world, rank)
@@ -211,9 +247,10 @@ def main():
         L.synchronize()
         rdzv.barrier()
 
-    # ---- sustained leg FIRST: >= 2 s of windows.  It is a measurement of its own (the `sustained` key), and it
-    # leaves the GPU at its operating clocks for the contract's region below: W warm-up windows, then exactly K timed ones.
-    # (Timed cold, 25 windows = 20 ms of work run on ramping clocks: 0.83 ms per window against 0.77 sustained.)
+    # ---- clock warm-up FIRST: >= 2 s of windows.  It leaves the GPU at its operating clocks for the contract's
+    # region below: W warm-up windows, then exactly K timed ones, from the initial state again.  (Timed cold, 25 windows =
+    # 20 ms of work run on ramping clocks: 0.83 ms per window against 0.77 sustained.)  With --full the leg runs at least K
+    # windows and is a measurement of its own (the `sustained` key).
     sustained = None
     if args.sustained_seconds > 0:
         barrier()
@@ -221,19 +258,23 @@ def main():
         L.train_windows(20, lr, want_losses=False)  # probe: how many windows make up the requested seconds
         L.synchronize()
         probe = (time.perf_counter() - tp) / 20
-        n_sus = max(args.steps, int(np.ceil(args.sustained_seconds / probe)))
+        n_sus = int(np.ceil(args.sustained_seconds / probe))
+        if args.full:
+            n_sus = max(args.steps, n_sus)
         n_sus = int(rdzv.allgather(n_sus)[0]) if world > 1 else n_sus  # every rank runs rank 0's count
         barrier()
         t1 = time.perf_counter()
-        sl = L.train_windows(n_sus, lr, want_losses=True)
+        sl = L.train_windows(n_sus, lr, want_losses=args.full)
         L.synchronize()
         barrier()
         wall_s = time.perf_counter() - t1
-        if world > 1:
-            wall_s = max(rdzv.allgather(wall_s))
-        sustained = {"steps": n_sus, "seconds": round(wall_s, 3), "ms_per_step": round(wall_s / n_sus * 1e3, 4),
-                     "value": round((S - 1) * B * n_sus * world / wall_s, 1),
-                     "loss_finite": bool(np.all(np.isfinite(sl))), "order": "before the warm-up and the timed steps"}
+        if args.full:
+            if world > 1:
+                wall_s = max(rdzv.allgather(wall_s))
+            sustained = {"steps": n_sus, "seconds": round(wall_s, 3), "ms_per_step": round(wall_s / n_sus * 1e3, 4),
+                         "value": round((S - 1) * B * n_sus * world / wall_s, 1),
+                         "loss_finite": bool(np.all(np.isfinite(sl))), "order": "before the warm-up and the timed steps"}
+        initial_state()
 
     L.train_windows(args.warmup, lr, want_losses=False)
     barrier()
@@ -252,10 +293,17 @@ def main():
     chars = (S - 1) * B * args.steps * world
     value = chars / wall
 
+    # ---- what the last timed window left: its loss (summed over ranks), the parameters and Adagrad memory after its update
+    # (identical on every rank), rank 0's h and c at its last timestep
+    if args.dump_outputs and rank == 0:
+        h_last, c_last = L.get_state(S - 1)
+        dump_outputs(args.dump_outputs, {"loss": np.asarray(losses[-1:], np.float64), "params": L.get_params(),
+                                         "adagrad_mem": L.get_params(lstm_hip.P_MEM), "h": h_last, "c": c_last})
+
     # ---- per-kernel durations, HIP events on the library's own stream (separate short pass) ----
     roofline = None
     kstats = {}
-    if rank == 0 or world > 1:
+    if args.full and (rank == 0 or world > 1):
         L.reset_kernel_stats()
         L.set_profiling(True)
         L.train_windows(args.profile_windows, lr, want_losses=False)
@@ -307,12 +355,13 @@ def main():
                        "gemm": "native"},
             "device_ms_per_step": round(dev_ms / args.steps, 4),
             "loss_first_last": [round(float(losses[0]), 4), round(float(losses[-1]), 4)],
-            "sustained": sustained,
-            "roofline": roofline,
-            "kernels_us": {k: [v[0] // max(args.profile_windows, 1), round(v[1] / v[0] * 1e3, 2)] for k, v in kstats.items()},
         }
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(N, S, B, text, lr, budget_s=args.cpu_budget)
+        if args.full:
+            out["sustained"] = sustained
+            out["roofline"] = roofline
+            out["kernels_us"] = {k: [v[0] // max(args.profile_windows, 1), round(v[1] / v[0] * 1e3, 2)] for k, v in kstats.items()}
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(N, S, B, text, lr, budget_s=args.cpu_budget)
         print(json.dumps(out), flush=True)
     L.close()
     rdzv.barrier()

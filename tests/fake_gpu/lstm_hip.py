@@ -6,6 +6,7 @@ import time
 import numpy as np
 
 STEP_KERNELS = 4
+P_PARAMS, P_GRADS, P_MEM = 0, 1, 2
 FAKE = True
 
 
@@ -30,8 +31,10 @@ class Lstm:
         self.N, self.S, self.B, self.device = N, S, B, device
         self.comm = None
 
-    def set_params(self, p): pass
+    def set_params(self, p, which=P_PARAMS): self.np = p.size
+    def get_params(self, which=P_PARAMS): return np.full(self.np, float(which), np.float32)
     def set_state(self, t, h, c): pass
+    def get_state(self, t): return np.zeros((self.B, self.N), np.float32), np.ones((self.B, self.N), np.float32)
     def set_text(self, t): pass
     def set_cursors(self, pos): assert len(pos) == self.B
     def set_window(self, xi, ti): assert xi.shape == (self.S, self.B) and ti.shape == (self.S, self.B)

@@ -24,6 +24,18 @@ struct lstm_hip_ctx {
 };
 
 static char g_err[256] = "";
+/* 1 once some rank has logged "train_windows HANG": the failing rank waits for it (up to 20 s) so that its peer is
+ * blocked in the "all-reduce" when it dies, as on real hardware, and not still before its call when the job ends */
+static int peer_hangs(void) {
+    const char *path = getenv("LSTM_STUB_LOG");
+    FILE *f = path ? fopen(path, "r") : NULL;
+    if (!f) return 0;
+    char line[256];
+    int found = 0;
+    while (!found && fgets(line, sizeof(line), f)) found = strstr(line, "train_windows HANG") != NULL;
+    fclose(f);
+    return found;
+}
 static void logf_(const struct lstm_hip_ctx *h, const char *fmt, ...) {
     const char *path = getenv("LSTM_STUB_LOG");
     if (!path) return;
@@ -94,6 +106,7 @@ int lstm_hip_train_windows(lstm_hip_t *h, int64_t count, double lr, double *loss
     const char *fr = getenv("LSTM_STUB_FAIL_RANK");
     if (fr && h->calls >= 2) {
         if (atoi(fr) == h->rank) {
+            for (int i = 0; i < 2000 && !peer_hangs(); i++) usleep(10000);
             snprintf(g_err, sizeof(g_err), "stub: injected failure on rank %d", h->rank);
             logf_(h, "train_windows FAIL");
             return LSTM_HIP_ESTATE;

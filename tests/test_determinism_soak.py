@@ -82,3 +82,23 @@ def test_two_live_handles_interleaved_stay_identical():
         L.close()
     assert np.array_equal(np.concatenate(out[0]), np.concatenate(out[1]))
     assert np.array_equal(P[0], P[1])
+
+
+def test_bench_outputs_identical_whatever_the_clock_warmup(tmp_path):
+    """bench.py --dump-outputs: the timed windows start from the seeded initial state, so two runs with the same arguments
+    write bit-identical outputs, and the clock warm-up before them (its length is timed, so it varies) changes nothing."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    got = []
+    for k, warm in enumerate(("0", "0.5")):
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "6", "--warmup", "2",
+                              "--sustained-seconds", warm, "--dump-outputs", str(tmp_path / str(k))],
+                             capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0, out.stderr[-2000:]
+        got.append({f: np.load(tmp_path / str(k) / f) for f in sorted(os.listdir(tmp_path / str(k)))})
+    assert sorted(got[0]) == ["adagrad_mem.npy", "c.npy", "h.npy", "loss.npy", "params.npy"]
+    assert sum(a.nbytes for a in got[0].values()) < 64e6
+    for f, a in got[0].items():
+        assert np.all(np.isfinite(a)) and np.array_equal(a, got[1][f]), f

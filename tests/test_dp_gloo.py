@@ -115,3 +115,51 @@ def test_bench_multi_rank_plumbing_under_torchrun():
     # whole-job aggregate: both ranks' characters over the slowest rank's time
     assert abs(d["value"] - 99 * 64 * 5 * 2 / (d["ms_per_step"] * 5e-3)) / d["value"] < 1e-3
     assert d["loss_first_last"] == [2.0, 2.0]  # sum over ranks of each rank's share
+
+
+def _fake_bench(*argv):
+    import json
+    import subprocess
+    env = dict(os.environ, LSTM_BENCH_FAKE_GPU="1")
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", *argv], capture_output=True,
+                         text=True, env=env, timeout=240)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout
+    return json.loads(lines[0])
+
+
+def test_bench_plain_run_is_lean_and_full_adds_the_rest(tmp_path):
+    """A plain bench.py run prints the headline line only; --full adds the sustained, per-kernel, roofline and CPU figures;
+    --dump-outputs writes the last timed window's outputs as float .npy files (GPU library replaced by tests/fake_gpu)."""
+    d = _fake_bench("--steps", "7", "--warmup", "2", "--sustained-seconds", "0.05", "--dump-outputs", str(tmp_path / "o"))
+    assert d["steps"] == 7 and d["unit"] == "chars/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert abs(d["value"] - 99 * 64 * 7 / (d["ms_per_step"] * 7e-3)) / d["value"] < 1e-3
+    assert d["metric"].startswith("chars/sec fwd+BPTT, enwik6 H=512 S=100 B=64")
+    assert not {"sustained", "roofline", "kernels_us", "cpu_baseline"} & set(d)
+    got = {f: np.load(tmp_path / "o" / f) for f in sorted(os.listdir(tmp_path / "o"))}
+    assert sorted(got) == ["adagrad_mem.npy", "c.npy", "h.npy", "loss.npy", "params.npy"]
+    assert got["loss.npy"].dtype == np.float64 and got["loss.npy"].tolist() == [1.0]
+    assert got["params.npy"].dtype == np.float32 and got["params.npy"].size == 4 * 512 * 768 + 4 * 512 + 256 * 513
+    assert np.all(got["adagrad_mem.npy"] == 2.0) and got["h.npy"].shape == (64, 512)
+
+    f = _fake_bench("--steps", "3", "--warmup", "1", "--sustained-seconds", "0.05", "--full", "--no-cpu-baseline")
+    assert f["sustained"]["steps"] >= 3 and f["roofline"]["kernel"] == "bwd_persistent" and f["kernels_us"]
+    assert "cpu_baseline" not in f
+
+
+def test_bench_dump_outputs_sample_large_arrays(tmp_path, monkeypatch):
+    """Outputs over the size cap are cut to the same fixed sample on every call, within the cap."""
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "MAX_DUMP_BYTES", 4000)
+    arrays = {"a": np.arange(1500, dtype=np.float32), "b": np.arange(300, dtype=np.float64).reshape(30, 10),
+              "loss": np.ones(1)}
+    for k in range(2):
+        bench.dump_outputs(str(tmp_path / str(k)), arrays)
+    sizes = 0
+    for name, a in arrays.items():
+        x, y = np.load(tmp_path / "0" / f"{name}.npy"), np.load(tmp_path / "1" / f"{name}.npy")
+        assert np.array_equal(x, y) and x.dtype == a.dtype and np.isin(x, a).all()
+        sizes += x.nbytes
+    assert sizes <= 4000 and np.load(tmp_path / "0" / "a.npy").size == 500
