@@ -210,6 +210,25 @@ void slide_window(const uint8_t *text, uint64_t len, uint64_t *pos, int32_t *Xr,
                   int32_t *xi, int32_t *ti, float *H, float *C, int S, int B, int N, int stride, int carry_col,
                   hipStream_t st);
 
+// ---- logical <-> padded hidden width (LSTM_HIP_PAD_HIDDEN), at the ABI boundary only.  A buffer is a list of pieces, each a
+//      column-major matrix whose columns are `blocks` row blocks of rows_l (logical) / rows_p (padded) rows: W, U and b have
+//      the four gate blocks, Why and by one block of 256 rows.  Padded: cols_p >= cols_l columns of blocks * rows_p rows.
+//      to_padded: every float of the padded buffer is written, the padding entries as 0; else the logical buffer is gathered
+//      from the padded one.  One launch.
+constexpr int PAD_MAX_PIECES = 5;
+struct PadPiece {
+    size_t off_l, off_p; // float offsets of the piece in the logical / padded buffer
+    int blocks, rows_l, rows_p, cols_l, cols_p;
+};
+struct PadMap {
+    PadPiece piece[PAD_MAX_PIECES]; // in buffer order
+    int n;
+    size_t total_l, total_p;
+};
+PadMap pad_map_params(int N, int Np, int M);              // the flat block [W | U | b | Why | by]
+PadMap pad_map_rows(int blocks, int N, int Np, int cols); // `cols` columns of `blocks` x N rows (h, c: 1; g: 4)
+void pad_copy(const float *src, float *dst, const PadMap &map, bool to_padded, hipStream_t st);
+
 // ---- B = 1 recurrence for the evaluator / sampler (OV/lstm_eigen_class_CUDA/lstm.cc:578-720)
 void eval_bits(const float *P, int N, const uint8_t *text, uint64_t len, double *out_bits_sum, float *scratch,
                hipStream_t st);

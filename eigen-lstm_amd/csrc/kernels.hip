@@ -1475,4 +1475,53 @@ void sample(const float *P, int N, float *hc, const double *u, int count, uint8_
     hipLaunchKernelGGL(k_sample, dim3(1), dim3(1024), lds, st, P, N, hc, u, count, out);
 }
 
+// ------------------------------------------------------------------------------------------------
+// pad_copy: logical <-> padded hidden width (kernels.h).  One thread per DESTINATION float (grid-stride), so every float of
+// the destination is written exactly once and no two threads write the same one.
+__global__ __launch_bounds__(256) void k_pad_copy(const float *__restrict__ src, float *__restrict__ dst, PadMap m, int to_padded) {
+    const size_t n = to_padded ? m.total_p : m.total_l;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        PadPiece p = m.piece[0];
+#pragma unroll
+        for (int s = 1; s < PAD_MAX_PIECES; s++) // (constant indices: the map stays in kernel arguments)
+            if (s < m.n && i >= (to_padded ? m.piece[s].off_p : m.piece[s].off_l)) p = m.piece[s];
+        const int rows = to_padded ? p.rows_p : p.rows_l;           // rows per block on the destination side
+        const size_t k = i - (to_padded ? p.off_p : p.off_l);
+        const size_t col = k / ((size_t)p.blocks * rows);
+        const int rr = (int)(k - col * p.blocks * rows), blk = rr / rows, r = rr - blk * rows;
+        if (to_padded)
+            dst[i] = (col < (size_t)p.cols_l && r < p.rows_l) ? src[p.off_l + col * p.blocks * p.rows_l + (size_t)blk * p.rows_l + r] : 0.0f;
+        else
+            dst[i] = src[p.off_p + col * p.blocks * p.rows_p + (size_t)blk * p.rows_p + r];
+    }
+}
+void pad_copy(const float *src, float *dst, const PadMap &map, bool to_padded, hipStream_t st) {
+    const size_t n = to_padded ? map.total_p : map.total_l;
+    int blocks = (int)((n + 255) / 256);
+    if (blocks > 2048) blocks = 2048;
+    if (blocks < 1) return;
+    hipLaunchKernelGGL(k_pad_copy, dim3(blocks), dim3(256), 0, st, src, dst, map, to_padded ? 1 : 0);
+}
+PadMap pad_map_params(int N, int Np, int M) {
+    const ParamLayout l = ParamLayout::make(N, M), p = ParamLayout::make(Np, M);
+    PadMap m{};
+    m.piece[0] = {l.W, p.W, 4, N, Np, M, M};
+    m.piece[1] = {l.U, p.U, 4, N, Np, N, Np};
+    m.piece[2] = {l.b, p.b, 4, N, Np, 1, 1};
+    m.piece[3] = {l.Why, p.Why, 1, M, M, N, Np};
+    m.piece[4] = {l.by, p.by, 1, M, M, 1, 1};
+    m.n = 5;
+    m.total_l = l.total;
+    m.total_p = p.total;
+    return m;
+}
+PadMap pad_map_rows(int blocks, int N, int Np, int cols) {
+    PadMap m{};
+    m.piece[0] = {0, 0, blocks, N, Np, cols, cols};
+    m.n = 1;
+    m.total_l = (size_t)blocks * N * cols;
+    m.total_p = (size_t)blocks * Np * cols;
+    return m;
+}
+
 } // namespace lstmk

@@ -87,7 +87,10 @@ int rccl_load() {
 } // namespace
 
 struct lstm_hip_ctx {
-    lstm_hip_config cfg{};
+    lstm_hip_config cfg{}; // cfg.N is the internal (padded) width Np; every buffer and launcher uses it
+    int N_log = 0;         // the caller's N (LSTM_HIP_PAD_HIDDEN: may be < cfg.N); the boundary calls convert to and from it
+    float *stage = nullptr; // N_log != cfg.N: logical-width staging buffer of the boundary copies (pad_copy)
+    bool padded() const { return N_log != cfg.N; }
     ParamLayout pl{};
     int T = 0; // (S-1)*B columns in the time-batched matrices
     hipStream_t st = nullptr;
@@ -183,6 +186,11 @@ namespace {
 int launch_status(int id) {
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(LSTM_HIP_EHIP, "launch of %s failed: %s", kKernelNames[id], hipGetErrorString(e));
+    return 0;
+}
+int pad_status() { // the boundary's layout copies (not one of the window's timed kernels)
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(LSTM_HIP_EHIP, "launch of pad_copy failed: %s", hipGetErrorString(e));
     return 0;
 }
 template <class F> int timed(lstm_hip_ctx *h, int id, F &&launch) {
@@ -620,6 +628,24 @@ int do_adagrad(lstm_hip_ctx *h, double lr) {
 
 static int create_body(lstm_hip_ctx *h, const lstm_hip_config *cfg, const hipDeviceProp_t &prop);
 
+namespace {
+// LSTM_HIP_PAD_HIDDEN: the internal width of a logical hidden size N >= 1 (include/lstm_hip.h).  A function of N and the flags
+// only, never of S or B: the evaluator's B = 1 handle, the ranks of a communicator and an explicit Np handle must all agree
+// on the layout.  0: refused.
+int padded_hidden(int N, unsigned flags) {
+    const auto up = [](int n, int k) { return (n + k - 1) / k * k; };
+    if (flags & LSTM_HIP_STEP_KERNELS) return up(N, 16);
+    if (flags & LSTM_HIP_BF16_RECURRENCE) return up(N, 128) <= 1024 ? up(N, 128) : 0;
+    if (N <= 64 || N > 1024) return up(N, 16);
+    if (N % 64 == 0) return N;
+    // only these widths have forms for wide batches (the two-half forms at 256 / 512); a generic width's grid is not
+    // co-resident at B = 1024 and would fall back to the per-step engine (448 against 512 for N = 400)
+    for (int w : {128, 256, 512})
+        if (N <= w) return w;
+    return 1024;
+}
+} // namespace
+
 extern "C" {
 
 const char *lstm_hip_last_error(void) { return g_err; }
@@ -635,11 +661,19 @@ int lstm_hip_device_info(int32_t device, char name[64], int32_t *cus, int32_t *c
     return 0;
 }
 
-int lstm_hip_create(const lstm_hip_config *cfg, lstm_hip_t **out) {
-    if (!cfg || !out) return fail(LSTM_HIP_EINVAL, "null argument");
+int lstm_hip_create(const lstm_hip_config *user_cfg, lstm_hip_t **out) {
+    if (!user_cfg || !out) return fail(LSTM_HIP_EINVAL, "null argument");
     *out = nullptr;
+    lstm_hip_config padded_cfg = *user_cfg; // from here on cfg->N is the internal width
+    const lstm_hip_config *cfg = &padded_cfg;
     if (cfg->M != LSTM_HIP_VOCAB) return fail(LSTM_HIP_EINVAL, "M must be %d (got %d)", LSTM_HIP_VOCAB, cfg->M);
-    if (cfg->N < 16 || cfg->N % 16 != 0) return fail(LSTM_HIP_EINVAL, "N must be a positive multiple of 16 (got %d)", cfg->N);
+    if (cfg->flags & LSTM_HIP_PAD_HIDDEN) {
+        if (cfg->N < 1 || cfg->N > (1 << 24)) return fail(LSTM_HIP_EINVAL, "N must be in [1, 2^24] (got %d)", cfg->N);
+        padded_cfg.N = padded_hidden(user_cfg->N, cfg->flags);
+        if (padded_cfg.N == 0)
+            return fail(LSTM_HIP_EINVAL, "LSTM_HIP_BF16_RECURRENCE needs N <= 1024 (got %d)", user_cfg->N);
+    } else if (cfg->N < 16 || cfg->N % 16 != 0)
+        return fail(LSTM_HIP_EINVAL, "N must be a positive multiple of 16 (got %d)", cfg->N);
     if (cfg->S < 2) return fail(LSTM_HIP_EINVAL, "S must be >= 2 (got %d)", cfg->S);
     if (cfg->B < 1) return fail(LSTM_HIP_EINVAL, "B must be >= 1 (got %d)", cfg->B);
     int ndev = 0;
@@ -664,6 +698,7 @@ int lstm_hip_create(const lstm_hip_config *cfg, lstm_hip_t **out) {
     }
 
     lstm_hip_ctx *h = new lstm_hip_ctx();
+    h->N_log = user_cfg->N;
     const int rc = create_body(h, cfg, prop);
     if (rc != 0) {
         char keep[sizeof(g_err)];
@@ -817,6 +852,8 @@ static int create_body(lstm_hip_ctx *h, const lstm_hip_config *cfg, const hipDev
     if (h->persistent && (cfg->flags & LSTM_HIP_DEBUG_STAMPS) &&
         ((cfg->N == 512 && h->Hx && h->Ubwd4) || (h->fwd_halves16 && h->bwd_scatter16)))
         ALLOC(h->stamps, 4 * S * 16);
+    if (h->padded()) // the largest logical-width copy: the parameter block, or g of one step (4N x B; h0 and c0 for the sampler)
+        ALLOC(h->stage, std::max({ParamLayout::make(h->N_log, cfg->M).total, (size_t)4 * h->N_log * B, (size_t)2 * h->N_log}));
     HIP_TRY(hipDeviceSynchronize());
     return 0;
 }
@@ -831,7 +868,7 @@ int lstm_hip_destroy(lstm_hip_t *h) {
     if (h->st2) (void)hipStreamSynchronize(h->st2);
     if (h->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(h->comm);
     void *bufs[] = {h->P, h->dP, h->mem, h->Ufwd, h->Ubwd, h->Ubwd4, h->Ufwd4, h->Hx, h->DGx, h->H, h->C, h->G, h->DG, h->Y, h->Pr, h->DHy, h->dcnext,
-                    h->colloss, h->dby_part, h->slabs, h->slabs_dU, h->gpart, h->Hb, h->DGb, h->Ufwd16, h->Ubwd16, h->Ubwd6b, h->Ufwd6b, h->Hxb, h->WhyT_b, h->Why_b, h->Ht_b, h->dYt_b, h->DGt_b, h->dYb, h->dw_scratch, h->xi, h->ti, h->Xr, h->Tr, h->head, h->cnt, h->abortp, h->stamps, h->d_loss, h->d_losses, h->text, h->pos};
+                    h->colloss, h->dby_part, h->slabs, h->slabs_dU, h->gpart, h->Hb, h->DGb, h->Ufwd16, h->Ubwd16, h->Ubwd6b, h->Ufwd6b, h->Hxb, h->WhyT_b, h->Why_b, h->Ht_b, h->dYt_b, h->DGt_b, h->dYb, h->dw_scratch, h->xi, h->ti, h->Xr, h->Tr, h->head, h->cnt, h->abortp, h->stamps, h->d_loss, h->d_losses, h->text, h->pos, h->stage};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     if (h->h_losses) (void)hipHostFree(h->h_losses);
@@ -853,6 +890,12 @@ int lstm_hip_set_params(lstm_hip_t *h, int which, const float *host_block) {
     CHECK(h);
     float *dst = block_of(h, which);
     if (!dst || !host_block) return fail(LSTM_HIP_EINVAL, "set_params: bad block id %d or null pointer", which);
+    if (h->padded()) { // logical block -> staging -> padded block, padding entries 0
+        const PadMap m = pad_map_params(h->N_log, h->cfg.N, h->cfg.M);
+        HIP_TRY(hipMemcpyAsync(h->stage, host_block, sizeof(float) * m.total_l, hipMemcpyHostToDevice, h->st));
+        pad_copy(h->stage, dst, m, true, h->st);
+        if (int rc = pad_status()) return rc;
+    } else
     HIP_TRY(hipMemcpyAsync(dst, host_block, sizeof(float) * h->pl.total, hipMemcpyHostToDevice, h->st));
     HIP_TRY(hipStreamSynchronize(h->st));
     if (which == 0) h->packed = h->packed16 = h->packed6b = h->packedf6b = h->why_packed = false;
@@ -862,6 +905,12 @@ int lstm_hip_get_params(lstm_hip_t *h, int which, float *host_block) {
     CHECK(h);
     float *src = block_of(h, which);
     if (!src || !host_block) return fail(LSTM_HIP_EINVAL, "get_params: bad block id %d or null pointer", which);
+    if (h->padded()) {
+        const PadMap m = pad_map_params(h->N_log, h->cfg.N, h->cfg.M);
+        pad_copy(src, h->stage, m, false, h->st);
+        if (int rc = pad_status()) return rc;
+        HIP_TRY(hipMemcpyAsync(host_block, h->stage, sizeof(float) * m.total_l, hipMemcpyDeviceToHost, h->st));
+    } else
     HIP_TRY(hipMemcpyAsync(host_block, src, sizeof(float) * h->pl.total, hipMemcpyDeviceToHost, h->st));
     HIP_TRY(hipStreamSynchronize(h->st));
     return check_abort(h);
@@ -872,6 +921,18 @@ int lstm_hip_set_state(lstm_hip_t *h, int32_t t, const float *h_t, const float *
     CHECK(h);
     if (t < 0 || t >= h->cfg.S) return fail(LSTM_HIP_EINVAL, "set_state: t=%d outside [0,%d)", t, h->cfg.S);
     const size_t n = (size_t)h->cfg.N * h->cfg.B;
+    if (h->padded()) { // N_log x B -> staging -> Np x B (rows N_log.. zero)
+        const PadMap m = pad_map_rows(1, h->N_log, h->cfg.N, h->cfg.B);
+        for (int k = 0; k < 2; k++) {
+            const float *src = k ? c_t : h_t;
+            if (!src) continue;
+            HIP_TRY(hipMemcpyAsync(h->stage, src, sizeof(float) * m.total_l, hipMemcpyHostToDevice, h->st));
+            pad_copy(h->stage, (k ? h->C : h->H) + t * n, m, true, h->st);
+            if (int rc = pad_status()) return rc;
+        }
+        HIP_TRY(hipStreamSynchronize(h->st));
+        return 0;
+    }
     if (h_t) HIP_TRY(hipMemcpyAsync(h->H + t * n, h_t, sizeof(float) * n, hipMemcpyHostToDevice, h->st));
     if (c_t) HIP_TRY(hipMemcpyAsync(h->C + t * n, c_t, sizeof(float) * n, hipMemcpyHostToDevice, h->st));
     HIP_TRY(hipStreamSynchronize(h->st));
@@ -881,6 +942,18 @@ int lstm_hip_get_state(lstm_hip_t *h, int32_t t, float *h_t, float *c_t) {
     CHECK(h);
     if (t < 0 || t >= h->cfg.S) return fail(LSTM_HIP_EINVAL, "get_state: t=%d outside [0,%d)", t, h->cfg.S);
     const size_t n = (size_t)h->cfg.N * h->cfg.B;
+    if (h->padded()) {
+        const PadMap m = pad_map_rows(1, h->N_log, h->cfg.N, h->cfg.B);
+        for (int k = 0; k < 2; k++) {
+            float *dst = k ? c_t : h_t;
+            if (!dst) continue;
+            pad_copy((k ? h->C : h->H) + t * n, h->stage, m, false, h->st);
+            if (int rc = pad_status()) return rc;
+            HIP_TRY(hipMemcpyAsync(dst, h->stage, sizeof(float) * m.total_l, hipMemcpyDeviceToHost, h->st));
+            HIP_TRY(hipStreamSynchronize(h->st)); // (the staging buffer is reused for c)
+        }
+        return 0;
+    }
     if (h_t) HIP_TRY(hipMemcpyAsync(h_t, h->H + t * n, sizeof(float) * n, hipMemcpyDeviceToHost, h->st));
     if (c_t) HIP_TRY(hipMemcpyAsync(c_t, h->C + t * n, sizeof(float) * n, hipMemcpyDeviceToHost, h->st));
     HIP_TRY(hipStreamSynchronize(h->st));
@@ -890,6 +963,12 @@ int lstm_hip_get_activations(lstm_hip_t *h, int32_t t, float *g_t, float *probs_
     CHECK(h);
     if (t < 1 || t >= h->cfg.S) return fail(LSTM_HIP_EINVAL, "get_activations: t=%d outside [1,%d)", t, h->cfg.S);
     const size_t B = h->cfg.B, G4 = 4 * (size_t)h->cfg.N;
+    if (g_t && h->padded()) { // gate blocks [i;o;f;u] of Np rows -> of N_log rows
+        const PadMap m = pad_map_rows(4, h->N_log, h->cfg.N, h->cfg.B);
+        pad_copy(h->G + t * G4 * B, h->stage, m, false, h->st);
+        if (int rc = pad_status()) return rc;
+        HIP_TRY(hipMemcpyAsync(g_t, h->stage, sizeof(float) * m.total_l, hipMemcpyDeviceToHost, h->st));
+    } else
     if (g_t) HIP_TRY(hipMemcpyAsync(g_t, h->G + t * G4 * B, sizeof(float) * G4 * B, hipMemcpyDeviceToHost, h->st));
     if (probs_t) HIP_TRY(hipMemcpyAsync(probs_t, h->Pr + t * 256 * B, sizeof(float) * 256 * B, hipMemcpyDeviceToHost, h->st));
     HIP_TRY(hipStreamSynchronize(h->st));
@@ -1153,7 +1232,7 @@ int lstm_hip_train_windows(lstm_hip_t *h, int64_t count, double learning_rate, d
 static const int AUX_S = 129; // 128 characters per evaluator chunk
 static int ensure_aux_handle(lstm_hip_ctx *h) {
     if (h->eval_h) return 0;
-    lstm_hip_config c = h->cfg;
+    lstm_hip_config c = h->cfg; // (cfg.N is the parent's internal width: a padded parent's aux handle is an unpadded Np one)
     c.S = AUX_S;
     c.B = 1;
     c.flags = (h->cfg.flags & LSTM_HIP_FAST_MATH) | LSTM_HIP_NO_FUSED_GRADS;
@@ -1237,8 +1316,16 @@ int lstm_hip_sample(lstm_hip_t *h, float *h0, float *c0, const double *u, int32_
     HIP_TRY(hipMalloc((void **)&d_hc, sizeof(float) * 2 * N));
     HIP_TRY(hipMalloc((void **)&d_u, sizeof(double) * (count + 1)));
     HIP_TRY(hipMalloc((void **)&d_out, (size_t)count + 1));
-    HIP_TRY(hipMemcpyAsync(d_hc, h0, sizeof(float) * N, hipMemcpyHostToDevice, h->st));
-    HIP_TRY(hipMemcpyAsync(d_hc + N, c0, sizeof(float) * N, hipMemcpyHostToDevice, h->st));
+    const PadMap hc_map = pad_map_rows(1, h->N_log, N, 2); // [h | c] as two columns
+    if (h->padded()) {
+        HIP_TRY(hipMemcpyAsync(h->stage, h0, sizeof(float) * h->N_log, hipMemcpyHostToDevice, h->st));
+        HIP_TRY(hipMemcpyAsync(h->stage + h->N_log, c0, sizeof(float) * h->N_log, hipMemcpyHostToDevice, h->st));
+        pad_copy(h->stage, d_hc, hc_map, true, h->st);
+        if (int rc = pad_status()) return rc;
+    } else {
+        HIP_TRY(hipMemcpyAsync(d_hc, h0, sizeof(float) * N, hipMemcpyHostToDevice, h->st));
+        HIP_TRY(hipMemcpyAsync(d_hc + N, c0, sizeof(float) * N, hipMemcpyHostToDevice, h->st));
+    }
     HIP_TRY(hipMemcpyAsync(d_u, u, sizeof(double) * count, hipMemcpyHostToDevice, h->st));
     if (h->persistent && !(h->cfg.flags & LSTM_HIP_STEP_KERNELS) && count > 0) {
         // Multi-workgroup path: per character one k_sample_head (probabilities + CDF walk, one workgroup) and one
@@ -1268,8 +1355,15 @@ int lstm_hip_sample(lstm_hip_t *h, float *h0, float *c0, const double *u, int32_
         e->fwd_done = false;
     } else
     sample(h->P, N, d_hc, d_u, count, d_out, nullptr, h->st);
-    HIP_TRY(hipMemcpyAsync(h0, d_hc, sizeof(float) * N, hipMemcpyDeviceToHost, h->st));
-    HIP_TRY(hipMemcpyAsync(c0, d_hc + N, sizeof(float) * N, hipMemcpyDeviceToHost, h->st));
+    if (h->padded()) {
+        pad_copy(d_hc, h->stage, hc_map, false, h->st);
+        if (int rc = pad_status()) return rc;
+        HIP_TRY(hipMemcpyAsync(h0, h->stage, sizeof(float) * h->N_log, hipMemcpyDeviceToHost, h->st));
+        HIP_TRY(hipMemcpyAsync(c0, h->stage + h->N_log, sizeof(float) * h->N_log, hipMemcpyDeviceToHost, h->st));
+    } else {
+        HIP_TRY(hipMemcpyAsync(h0, d_hc, sizeof(float) * N, hipMemcpyDeviceToHost, h->st));
+        HIP_TRY(hipMemcpyAsync(c0, d_hc + N, sizeof(float) * N, hipMemcpyDeviceToHost, h->st));
+    }
     HIP_TRY(hipMemcpyAsync(out, d_out, count, hipMemcpyDeviceToHost, h->st));
     HIP_TRY(hipStreamSynchronize(h->st));
     return 0;

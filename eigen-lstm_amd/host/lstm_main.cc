@@ -240,7 +240,8 @@ int run_rank(const Options &o, int rank, int up, int down) {
     if (data.size() <= (size_t)S + 1) die("text too short");
     const size_t length = data.size();
 
-    lstm_hip_config cfg{N, M, S, Bl, rank, o.flags};
+    // the reference takes any hidden size (R/lstm.cc:53): the library pads it internally; every shape here stays N
+    lstm_hip_config cfg{N, M, S, Bl, rank, o.flags | LSTM_HIP_PAD_HIDDEN};
     lstm_hip_t *h = nullptr;
     CK(lstm_hip_create(&cfg, &h));
     if (o.gpus > 1) {

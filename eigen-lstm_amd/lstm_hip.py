@@ -22,6 +22,7 @@ STEP_KERNELS = 4
 DEBUG_STAMPS = 16
 NO_FUSED_GRADS = 64
 BF16_RECURRENCE = 128
+PAD_HIDDEN = 256  # any hidden size >= 1, run at an internal padded width (include/lstm_hip.h); shapes stay logical
 LOSS_ALL_STEPS_BITS, LOSS_LAST_STEP_NATS, LOSS_LAST_STEP_BITS = 0, 1, 2
 UNIQUE_ID_BYTES = 128
 VOCAB = 256

@@ -56,11 +56,21 @@ extern "C" {
                                       instead of accumulating them inside it */
 #define LSTM_HIP_DEBUG_STAMPS 16u    /* diagnostic builds of both recurrences (N = 512, 8-column forms) that record
                                       s_memtime at marked points of every step; see lstm_hip_debug_stamps */
+#define LSTM_HIP_PAD_HIDDEN 256u     /* accept any N >= 1 and run it at an internal width Np >= N whose extra hidden units
+                                      have all-zero rows and columns in W, U, b and Why (exact: such a unit keeps c = h = 0
+                                      and gets zero gradients).  Np depends on N and the flags only:
+                                        fp32, N <= 64 or N > 1024:       N rounded up to 16
+                                        fp32, 64 < N <= 1024, N % 64 = 0: N
+                                        fp32, other 64 < N <= 1024:      the smallest of 128, 256, 512, 1024 >= N
+                                        LSTM_HIP_BF16_RECURRENCE:        N rounded up to 128 (refused above 1024)
+                                        LSTM_HIP_STEP_KERNELS:           N rounded up to 16
+                                      Every call still takes and returns logical-N shapes; only the RCCL all-reduce
+                                      payload is the padded block (lstm_hip_param_count(Np, M) floats). */
 
 typedef struct lstm_hip_ctx lstm_hip_t; /* opaque: cuParameters p,d,m + cuLSTM<S> in one object */
 
 typedef struct lstm_hip_config {
-    int32_t N;       /* hidden size, multiple of 16                       R/lstm.cc:53 */
+    int32_t N;       /* hidden size: a multiple of 16, or any N >= 1 with LSTM_HIP_PAD_HIDDEN   R/lstm.cc:53 */
     int32_t M;       /* vocabulary, must be LSTM_HIP_VOCAB                R/lstm.cc:55 */
     int32_t S;       /* window columns; S-1 timesteps per window, S >= 2  R/lstm.cc:57 */
     int32_t B;       /* concurrent streams on THIS device                 OV/lstm_eigen_opt/lstm.cc:56 */
@@ -74,7 +84,7 @@ typedef struct lstm_hip_config {
 int lstm_hip_create(const lstm_hip_config *cfg, lstm_hip_t **out);
 int lstm_hip_destroy(lstm_hip_t *h);
 const char *lstm_hip_last_error(void);
-/* number of floats in the flat block: 4N*M + 4N*N + 4N + M*N + M */
+/* number of floats in the flat block: 4N*M + 4N*N + 4N + M*N + M (logical N: the size every call below takes) */
 size_t lstm_hip_param_count(int32_t N, int32_t M);
 
 /* ---- copy_parameters_to_device / copy_parameters_to_host, cu_lstm.h:307-325.
@@ -114,7 +124,9 @@ int lstm_hip_backward(lstm_hip_t *h);
 int lstm_hip_adagrad(lstm_hip_t *h, double learning_rate);
 
 /* ---- data-parallel exchange (new; the reference is single-device).  One SUM all-reduce of the
- *      flat gradient block per window over RCCL; every rank then applies the identical Adagrad step. */
+ *      flat gradient block per window over RCCL; every rank then applies the identical Adagrad step.
+ *      With LSTM_HIP_PAD_HIDDEN the payload is the padded block (Np from N and the flags, so every
+ *      rank of a job has the same layout). */
 #define LSTM_HIP_UNIQUE_ID_BYTES 128
 int lstm_hip_comm_unique_id(uint8_t id[LSTM_HIP_UNIQUE_ID_BYTES]);
 int lstm_hip_comm_init(lstm_hip_t *h, const uint8_t id[LSTM_HIP_UNIQUE_ID_BYTES], int32_t nranks, int32_t rank);
