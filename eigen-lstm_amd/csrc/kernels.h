@@ -234,7 +234,24 @@ void eval_bits(const float *P, int N, const uint8_t *text, uint64_t len, double 
                hipStream_t st);
 void sample(const float *P, int N, float *hc /*2N*/, const double *u, int count, uint8_t *out, float *scratch,
             hipStream_t st);
-void sample_head(const float *Why, const float *by, int N, const float *hvec, const double *u, uint8_t *out, int32_t *x_next,
-                 hipStream_t st);
+
+// ---- batched generator (lstm_hip_generate): per step gen_head on the state after t inputs, then fwd_step over all
+// streams with x_next as inputs.  Arrays are [streams] or [count][streams]; H, C, h_out, c_out are [streams][N], N % 16 == 0
+struct GenHeadArgs {
+    const float *Why, *by;
+    const float *H, *C;         // state after t inputs
+    const uint8_t *prompts;     // concatenated prompts (null: none)
+    const uint64_t *off;        // streams + 1 prompt offsets (null: no prompts)
+    const double *u;            // draws [count][streams] (null when mode == 2)
+    uint8_t *out;               // drawn bytes [count][streams]
+    double *bits;               // prompt bits per stream, accumulated (null: not scored)
+    int32_t *x_next;            // the next input of every stream (-1: none)
+    float *h_out, *c_out;       // the state after each stream's last input (null: not kept)
+    int N, streams, count;
+    int mode;                   // 0: temperature 1 (unshifted expf, as the sampler), 1: tempered, 2: greedy
+    float tau;
+};
+void gen_head(const GenHeadArgs &a, long long t, hipStream_t st);
+int gen_head_group(int N, int streams); // streams per workgroup of gen_head
 
 } // namespace lstmk

@@ -1427,48 +1427,162 @@ __global__ __launch_bounds__(1024) void k_sample(const float *__restrict__ P, in
         hc[N + j] = cs[j];
     }
 }
-// One character of the sampler for the multi-workgroup path (lstm_hip_api.cpp: per character this kernel, then one
-// k_fwd_step launch with the sampled byte as input): probabilities from h exactly as b1_output / k_sample compute them,
-// then the sequential float CDF walk of R/lstm.cc:321-338.  The byte goes to out[0] and, as the next input index, to
-// x_next[0].
-__global__ __launch_bounds__(256) void k_sample_head(const float *__restrict__ Why, const float *__restrict__ by, int N,
-                                                     const float *__restrict__ hvec, const double *__restrict__ u,
-                                                     uint8_t *__restrict__ out, int32_t *__restrict__ x_next) {
-    __shared__ float ps[256];
-    __shared__ float hs[1024];
-    const int m = threadIdx.x;
-    for (int k = m; k < N; k += 256) hs[k] = hvec[k];
-    __syncthreads();
-    float y = 0.0f;
-    for (int k0 = 0; k0 < N; k0 += 16) { // 16 loads in flight; the additions stay in k order (as b1_output)
-        float wv[16];
+// ------------------------------------------------------------------------------------------------
+// gen_head: one step of the batched generator (lstm_hip_generate; lstm_hip_sample on the persistent engine is its
+// streams = 1 case).  Per step the host launches this kernel on the state after t inputs, then one k_fwd_step over all
+// streams with the inputs it chose.  Per stream s, with L = its prompt length:
+//   t <  L          input prompt[t]; for t >= 1 (and bits requested) bits[s] += -log2 p(prompt[t]) at temperature 1
+//   L <= t < L + C  byte i = t - L drawn from p (mode 0: expf(z) unshifted, as b1_output; 1: expf((z - max z) / tau);
+//                   2: argmax z, lowest index on ties) by the sequential float CDF walk of R/lstm.cc:321-338 (index 0
+//                   if u passes every edge); it goes to out[i * streams + s] and becomes the next input
+//   t == L + C      the state is the stream's final one: copied to h_out / c_out (the stream idles afterwards, x = -1)
+// Workgroup g owns streams g*SB .. g*SB+SB-1; thread m owns logit m of all of them, so each Why element read serves SB
+// streams (h of the group in LDS, k-major).  Each logit is summed sequentially in k with separate multiply and add
+// (contraction is off in this file), so a stream's bytes do not depend on SB, on its position or on the other streams.
+// ------------------------------------------------------------------------------------------------
+// what stream s does at step t: 0 idle, 1 prompt byte scored, 2 drawn byte, 3 prompt byte not scored; *len = its prompt length
+__device__ __forceinline__ int gen_phase(const GenHeadArgs &a, int s, long long t, long long *len) {
+    *len = a.off ? (long long)(a.off[s + 1] - a.off[s]) : 0;
+    if (t < *len) return (t >= 1 && a.bits) ? 1 : 3;
+    return t - *len < a.count ? 2 : 0;
+}
+template <int SB>
+__global__ __launch_bounds__(256) void k_gen_head(GenHeadArgs a, long long t) {
+    extern __shared__ __attribute__((aligned(16))) float hs[]; // [N][SB]
+    __shared__ float ps[SB][256];
+    __shared__ float s_zmax[SB], s_sum[SB];
+    __shared__ int s_arg[SB];
+    const int m = threadIdx.x, N = a.N, s0 = blockIdx.x * SB;
+    int phase[SB]; // (the same in every thread)
+    bool need = false;
 #pragma unroll
-        for (int i = 0; i < 16; i++) wv[i] = Why[(size_t)(k0 + i) * 256 + m];
-#pragma unroll
-        for (int i = 0; i < 16; i++) y += wv[i] * hs[k0 + i];
+    for (int j = 0; j < SB; j++) {
+        const int s = s0 + j;
+        phase[j] = 0;
+        if (s >= a.streams) continue;
+        long long len;
+        phase[j] = gen_phase(a, s, t, &len);
+        need |= phase[j] == 1 || phase[j] == 2;
+        if (t == len + a.count) { // the state after the stream's last input
+            if (a.h_out)
+                for (int k = m; k < N; k += 256) a.h_out[(size_t)s * N + k] = a.H[(size_t)s * N + k];
+            if (a.c_out)
+                for (int k = m; k < N; k += 256) a.c_out[(size_t)s * N + k] = a.C[(size_t)s * N + k];
+        }
     }
-    ps[m] = expf(y + by[m]);
-    __syncthreads();
-    if (m == 0) {
-        float s = 0.0f;
-        for (int i = 0; i < 256; i++) s += ps[i];
-        const float r = (float)u[0];
-        float cdf = 0.0f;
-        int index = 0;
-        for (int i = 0; i < 256; i++) {
-            cdf += ps[i] / s;
-            if (r < cdf) {
-                index = i;
-                break;
+    if (need) { // (uniform)
+        for (int i = m; i < N * SB; i += 256) {
+            const int k = i / SB, j = i - k * SB;
+            hs[i] = s0 + j < a.streams ? a.H[(size_t)(s0 + j) * N + k] : 0.0f;
+        }
+        __syncthreads();
+        float y[SB];
+#pragma unroll
+        for (int j = 0; j < SB; j++) y[j] = 0.0f;
+        for (int k0 = 0; k0 < N; k0 += 16) { // 16 loads in flight; the additions stay in k order (as b1_output)
+            float wv[16];
+#pragma unroll
+            for (int i = 0; i < 16; i++) wv[i] = a.Why[(size_t)(k0 + i) * 256 + m];
+#pragma unroll
+            for (int i = 0; i < 16; i++)
+#pragma unroll
+                for (int j = 0; j < SB; j++) y[j] += wv[i] * hs[(k0 + i) * SB + j];
+        }
+        const float bym = a.by[m];
+        bool any_max = false;
+#pragma unroll
+        for (int j = 0; j < SB; j++) {
+            y[j] = y[j] + bym; // the logit z
+            ps[j][m] = y[j];
+            any_max |= phase[j] == 2 && a.mode != 0;
+        }
+        if (any_max) { // max z / argmax z of each tempered or greedy stream (every order gives the same max)
+            __syncthreads();
+            long long len;
+            if (m < SB && s0 + m < a.streams && gen_phase(a, s0 + m, t, &len) == 2) {
+                float best = ps[m][0];
+                int arg = 0;
+                for (int i = 1; i < 256; i++)
+                    if (ps[m][i] > best) {
+                        best = ps[m][i];
+                        arg = i;
+                    }
+                s_zmax[m] = best;
+                s_arg[m] = arg;
+            }
+            __syncthreads();
+        }
+#pragma unroll
+        for (int j = 0; j < SB; j++) {
+            if (phase[j] == 1 || (phase[j] == 2 && a.mode == 0)) ps[j][m] = expf(y[j]);
+            else if (phase[j] == 2 && a.mode == 1) ps[j][m] = expf((y[j] - s_zmax[j]) / a.tau);
+        }
+        __syncthreads();
+        long long len;
+        const int pm = m < SB && s0 + m < a.streams ? gen_phase(a, s0 + m, t, &len) : 0;
+        if (pm == 1 || (pm == 2 && a.mode != 2)) {
+            float s = 0.0f;
+            for (int i = 0; i < 256; i++) s += ps[m][i];
+            s_sum[m] = s;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < SB; j++)
+            if (phase[j] == 1 || (phase[j] == 2 && a.mode != 2)) ps[j][m] = ps[j][m] / s_sum[j]; // p, the CDF's terms
+        __syncthreads();
+    }
+    // one owner thread per stream, spread over the four waves
+    const int j = (m & 63) * 4 + (m >> 6);
+    if (j >= SB || s0 + j >= a.streams) return;
+    const int s = s0 + j;
+    long long len;
+    const int ph = gen_phase(a, s, t, &len);
+    int x = -1;
+    if (ph == 1 || ph == 3) {
+        x = a.prompts[a.off[s] + t];
+        if (ph == 1) a.bits[s] += -(double)log2f(ps[j][x]);
+    } else if (ph == 2) {
+        const size_t i = (size_t)(t - len);
+        if (a.mode == 2) x = s_arg[j];
+        else {
+            const float r = (float)a.u[i * a.streams + s];
+            float cdf = 0.0f;
+            x = 0;
+            for (int k = 0; k < 256; k++) {
+                cdf += ps[j][k];
+                if (r < cdf) {
+                    x = k;
+                    break;
+                }
             }
         }
-        out[0] = (uint8_t)index;
-        x_next[0] = index;
+        a.out[i * a.streams + s] = (uint8_t)x;
     }
+    a.x_next[s] = x;
 }
-void sample_head(const float *Why, const float *by, int N, const float *hvec, const double *u, uint8_t *out, int32_t *x_next,
-                 hipStream_t st) {
-    hipLaunchKernelGGL(k_sample_head, dim3(1), dim3(256), 0, st, Why, by, N, hvec, u, out, x_next);
+int gen_head_group(int N, int streams) {
+    int sb = 1; // enough workgroups to cover the chip before Why is shared, and h of the group within 64 KB of LDS
+    while (sb < 16 && streams >= 256 * 2 * sb && (size_t)2 * sb * N <= 16384) sb *= 2;
+    return sb;
+}
+void gen_head(const GenHeadArgs &a, long long t, hipStream_t st) {
+    const int sb = gen_head_group(a.N, a.streams);
+    const size_t lds = (size_t)sb * a.N * sizeof(float);
+    const dim3 grid((a.streams + sb - 1) / sb);
+#define GEN_HEAD_CASE(SB)                                                                                                   \
+    case SB:                                                                                                                \
+        if (lds > 32768)                                                                                                    \
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_gen_head<SB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+        hipLaunchKernelGGL(k_gen_head<SB>, grid, dim3(256), lds, st, a, t);                                                \
+        break;
+    switch (sb) {
+        GEN_HEAD_CASE(1)
+        GEN_HEAD_CASE(2)
+        GEN_HEAD_CASE(4)
+        GEN_HEAD_CASE(8)
+        GEN_HEAD_CASE(16)
+    }
+#undef GEN_HEAD_CASE
 }
 void sample(const float *P, int N, float *hc, const double *u, int count, uint8_t *out, float *, hipStream_t st) {
     const size_t lds = (size_t)(6 * N + 256) * sizeof(float);

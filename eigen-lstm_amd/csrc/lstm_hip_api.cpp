@@ -15,6 +15,8 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cfloat>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -44,11 +46,11 @@ int fail(int code, const char *fmt, ...) {
 
 enum KernelId {
     K_PACK_U, K_FWD_STEP, K_GEMM_Y, K_SOFTMAX, K_LOSS, K_GEMM_DHY, K_BWD_STEP, K_GEMM_DWHY, K_GEMM_DU, K_DW_DB,
-    K_DBY, K_ADAGRAD, K_SLIDE, K_ALLREDUCE, K_FWD_PERSIST, K_BWD_PERSIST, K_COUNT
+    K_DBY, K_ADAGRAD, K_SLIDE, K_ALLREDUCE, K_FWD_PERSIST, K_BWD_PERSIST, K_GEN_HEAD, K_COUNT
 };
 const char *const kKernelNames[K_COUNT] = {
     "pack_U", "fwd_step", "gemm_Y", "softmax_loss_dy", "loss_reduce", "gemm_DHy", "bwd_step", "gemm_dWhy", "gemm_dU",
-    "dW_db", "loss_dby", "adagrad", "slide", "allreduce", "fwd_persistent", "bwd_persistent"};
+    "dW_db", "loss_dby", "adagrad", "slide", "allreduce", "fwd_persistent", "bwd_persistent", "gen_head"};
 
 // ---- RCCL, loaded on first use so single-GPU users never touch it --------------------------
 struct UniqueId {
@@ -160,6 +162,8 @@ struct lstm_hip_ctx {
     uint64_t *pos = nullptr;
     int32_t global_B = 0;
     lstm_hip_ctx *eval_h = nullptr; // internal B = 1 handle used by lstm_hip_eval_bits
+    char *gen_scratch = nullptr;    // lstm_hip_generate's working memory: grows to the largest call, freed with the handle
+    size_t gen_scratch_bytes = 0;
     int stride = 1, carry_col = 1; // window advance per iteration and the column that becomes the carry
     bool fwd_done = false;
     bool dby_done = false;       // dby already produced by the loss launch of this window
@@ -868,7 +872,7 @@ int lstm_hip_destroy(lstm_hip_t *h) {
     if (h->st2) (void)hipStreamSynchronize(h->st2);
     if (h->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(h->comm);
     void *bufs[] = {h->P, h->dP, h->mem, h->Ufwd, h->Ubwd, h->Ubwd4, h->Ufwd4, h->Hx, h->DGx, h->H, h->C, h->G, h->DG, h->Y, h->Pr, h->DHy, h->dcnext,
-                    h->colloss, h->dby_part, h->slabs, h->slabs_dU, h->gpart, h->Hb, h->DGb, h->Ufwd16, h->Ubwd16, h->Ubwd6b, h->Ufwd6b, h->Hxb, h->WhyT_b, h->Why_b, h->Ht_b, h->dYt_b, h->DGt_b, h->dYb, h->dw_scratch, h->xi, h->ti, h->Xr, h->Tr, h->head, h->cnt, h->abortp, h->stamps, h->d_loss, h->d_losses, h->text, h->pos, h->stage};
+                    h->colloss, h->dby_part, h->slabs, h->slabs_dU, h->gpart, h->Hb, h->DGb, h->Ufwd16, h->Ubwd16, h->Ubwd6b, h->Ufwd6b, h->Hxb, h->WhyT_b, h->Why_b, h->Ht_b, h->dYt_b, h->DGt_b, h->dYb, h->dw_scratch, h->xi, h->ti, h->Xr, h->Tr, h->head, h->cnt, h->abortp, h->stamps, h->d_loss, h->d_losses, h->text, h->pos, h->stage, h->gen_scratch};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     if (h->h_losses) (void)hipHostFree(h->h_losses);
@@ -1228,7 +1232,7 @@ int lstm_hip_train_windows(lstm_hip_t *h, int64_t count, double learning_rate, d
 // Where the persistent forward recurrence exists for this hidden size, the text is run through it in
 // chunks on an internal B = 1 handle (the carry moves from the last column of a chunk to column 0 of the
 // next); otherwise by the single-workgroup kernel.
-// internal B = 1 handle behind the evaluator and the sampler (its own copy of the parameters and their fragment images)
+// internal B = 1 handle behind the evaluator (its own copy of the parameters and their fragment images)
 static const int AUX_S = 129; // 128 characters per evaluator chunk
 static int ensure_aux_handle(lstm_hip_ctx *h) {
     if (h->eval_h) return 0;
@@ -1299,6 +1303,12 @@ int lstm_hip_eval_bits(lstm_hip_t *h, const uint8_t *text, size_t len, double *b
 int lstm_hip_sample(lstm_hip_t *h, float *h0, float *c0, const double *u, int32_t count, uint8_t *out) {
     CHECK(h);
     if (!h0 || !c0 || !u || !out || count < 0) return fail(LSTM_HIP_EINVAL, "sample: null pointer or negative count");
+    // Persistent engine: the batched generator with one stream (per character one gen_head and one k_fwd_step launch; the
+    // sampled byte never leaves the device).  (k_sample does the whole 4N x N product in ONE workgroup: 395 us per
+    // character at N = 512.)  Fixed cost per call: one pack_U of the current U (4N^2 floats, about 10 us at N = 512; P
+    // changes under many calls, so the image is not cached) and the uploads; the scratch memory stays with the handle.
+    if (h->persistent && !(h->cfg.flags & LSTM_HIP_STEP_KERNELS) && count > 0)
+        return lstm_hip_generate(h, 1, nullptr, nullptr, h0, c0, 1.0, u, count, out, nullptr, h0, c0);
     const int N = h->cfg.N;
     float *d_hc = nullptr;
     double *d_u = nullptr;
@@ -1327,33 +1337,6 @@ int lstm_hip_sample(lstm_hip_t *h, float *h0, float *c0, const double *u, int32_
         HIP_TRY(hipMemcpyAsync(d_hc + N, c0, sizeof(float) * N, hipMemcpyHostToDevice, h->st));
     }
     HIP_TRY(hipMemcpyAsync(d_u, u, sizeof(double) * count, hipMemcpyHostToDevice, h->st));
-    if (h->persistent && !(h->cfg.flags & LSTM_HIP_STEP_KERNELS) && count > 0) {
-        // Multi-workgroup path: per character one k_sample_head (probabilities + CDF walk, one workgroup) and one
-        // k_fwd_step launch (the recurrent product over N/4 workgroups) on the internal B = 1 handle the evaluator uses;
-        // the sampled byte never leaves the device.  (k_sample does the whole 4N x N product in ONE workgroup:
-        // 395 us per character at N = 512.)
-        HIP_TRY(hipStreamSynchronize(h->st));
-        int rc = ensure_aux_handle(h);
-        if (rc) return rc;
-        lstm_hip_ctx *e = h->eval_h;
-        HIP_TRY(hipMemcpyAsync(e->P, h->P, sizeof(float) * h->pl.total, hipMemcpyDeviceToDevice, e->st));
-        pack_U(e->P + e->pl.U, e->Ufwd, e->Ubwd, N, e->st);
-        e->packed = true;
-        HIP_TRY(hipMemcpyAsync(e->H, d_hc, sizeof(float) * N, hipMemcpyDeviceToDevice, e->st));
-        HIP_TRY(hipMemcpyAsync(e->C, d_hc + N, sizeof(float) * N, hipMemcpyDeviceToDevice, e->st));
-        const bool fast = (h->cfg.flags & LSTM_HIP_FAST_MATH) != 0;
-        int cur = 0;
-        for (int i = 0; i < count; i++) {
-            sample_head(e->P + e->pl.Why, e->P + e->pl.by, N, e->H + (size_t)cur * N, d_u + i, d_out + i, e->xi, e->st);
-            fwd_step(e->Ufwd, e->P + e->pl.W, e->P + e->pl.b, e->H + (size_t)cur * N, e->C + (size_t)cur * N,
-                     e->H + (size_t)(cur ^ 1) * N, e->C + (size_t)(cur ^ 1) * N, e->G, e->xi, N, 1, fast, e->st);
-            cur ^= 1;
-        }
-        HIP_TRY(hipMemcpyAsync(d_hc, e->H + (size_t)cur * N, sizeof(float) * N, hipMemcpyDeviceToDevice, e->st));
-        HIP_TRY(hipMemcpyAsync(d_hc + N, e->C + (size_t)cur * N, sizeof(float) * N, hipMemcpyDeviceToDevice, e->st));
-        HIP_TRY(hipStreamSynchronize(e->st));
-        e->fwd_done = false;
-    } else
     sample(h->P, N, d_hc, d_u, count, d_out, nullptr, h->st);
     if (h->padded()) {
         pad_copy(d_hc, h->stage, hc_map, false, h->st);
@@ -1365,6 +1348,137 @@ int lstm_hip_sample(lstm_hip_t *h, float *h0, float *c0, const double *u, int32_
         HIP_TRY(hipMemcpyAsync(c0, d_hc + N, sizeof(float) * N, hipMemcpyDeviceToHost, h->st));
     }
     HIP_TRY(hipMemcpyAsync(out, d_out, count, hipMemcpyDeviceToHost, h->st));
+    HIP_TRY(hipStreamSynchronize(h->st));
+    return 0;
+}
+
+// Batched, prompted generation and per-text scoring (include/lstm_hip.h).  All streams advance together: per step one
+// gen_head launch (logits, prompt bits, the next input of every stream, final states) and one k_fwd_step over all streams,
+// from the fp32 master parameters P and a fragment image of U made for this call.  Nothing of the training state is
+// read or written except P; everything else lives in one scratch allocation kept on the handle (gen_scratch).
+int lstm_hip_generate(lstm_hip_t *h, int32_t streams, const uint8_t *prompts, const uint64_t *prompt_off, const float *h0,
+                      const float *c0, double temperature, const double *u, int32_t count, uint8_t *out, double *bits,
+                      float *h_out, float *c_out) {
+    CHECK(h);
+    if (streams < 1 || streams > 4096) return fail(LSTM_HIP_EINVAL, "generate: streams must be in [1, 4096] (got %d)", streams);
+    if (count < 0) return fail(LSTM_HIP_EINVAL, "generate: count < 0 (%d)", count);
+    if (!std::isfinite(temperature) || temperature < 0.0)
+        return fail(LSTM_HIP_EINVAL, "generate: temperature must be finite and >= 0 (got %g)", temperature);
+    if (count > 0 && temperature > 0.0 && !u) return fail(LSTM_HIP_EINVAL, "generate: draws u are needed unless temperature is 0");
+    if (count > 0 && !out) return fail(LSTM_HIP_EINVAL, "generate: null out with count > 0");
+    if (prompts && !prompt_off) return fail(LSTM_HIP_EINVAL, "generate: prompts without prompt_off");
+    uint64_t max_len = 0;
+    if (prompt_off) {
+        if (prompt_off[0] != 0) return fail(LSTM_HIP_EINVAL, "generate: prompt_off[0] must be 0 (got %llu)", (unsigned long long)prompt_off[0]);
+        for (int s = 0; s < streams; s++) {
+            if (prompt_off[s + 1] < prompt_off[s])
+                return fail(LSTM_HIP_EINVAL, "generate: prompt_off decreases at stream %d (%llu < %llu)", s,
+                            (unsigned long long)prompt_off[s + 1], (unsigned long long)prompt_off[s]);
+            max_len = std::max<uint64_t>(max_len, prompt_off[s + 1] - prompt_off[s]);
+        }
+        if (prompt_off[streams] > 0 && !prompts) return fail(LSTM_HIP_EINVAL, "generate: prompt_off without prompts");
+    }
+    const int N = h->cfg.N, Nl = h->N_log;
+    if (N > 16384) return fail(LSTM_HIP_EINVAL, "generate: hidden width %d above 16384", N);
+    const uint64_t total = prompt_off ? prompt_off[streams] : 0;
+    const size_t n = (size_t)N * streams, nl = (size_t)Nl * streams, nd = (size_t)count * streams;
+    const bool keep = h_out || c_out;
+
+    // one scratch allocation, 256-byte aligned pieces
+    size_t bytes = 0;
+    auto piece = [&](size_t b) {
+        const size_t o = bytes;
+        bytes += (b + 255) / 256 * 256;
+        return o;
+    };
+    const size_t o_U = piece(sizeof(float) * 4 * (size_t)N * N), o_H = piece(sizeof(float) * 2 * n), o_C = piece(sizeof(float) * 2 * n),
+                 o_G = piece(sizeof(float) * 4 * n), o_ho = piece(keep ? sizeof(float) * 2 * n : 0),
+                 o_st = piece(h->padded() ? sizeof(float) * 2 * nl : 0), o_x = piece(sizeof(int32_t) * streams),
+                 o_off = piece(prompt_off ? sizeof(uint64_t) * (streams + 1) : 0), o_p = piece(total),
+                 o_u = piece(count > 0 && temperature >= (double)FLT_MIN ? sizeof(double) * nd : 0), o_out = piece(nd),
+                 o_bits = piece(sizeof(double) * streams);
+    if (bytes > h->gen_scratch_bytes) { // (kept between calls: hipFree waits for the whole device)
+        HIP_TRY(hipStreamSynchronize(h->st));
+        if (h->gen_scratch) HIP_TRY(hipFree(h->gen_scratch));
+        h->gen_scratch = nullptr;
+        h->gen_scratch_bytes = 0;
+        HIP_TRY(hipMalloc((void **)&h->gen_scratch, bytes));
+        h->gen_scratch_bytes = bytes;
+    }
+    char *base = h->gen_scratch;
+    float4 *Ufwd = reinterpret_cast<float4 *>(base + o_U);
+    float *H = reinterpret_cast<float *>(base + o_H), *Cs = reinterpret_cast<float *>(base + o_C);
+    float *G = reinterpret_cast<float *>(base + o_G), *stage = reinterpret_cast<float *>(base + o_st);
+    float *ho = keep ? reinterpret_cast<float *>(base + o_ho) : nullptr;
+    int32_t *xi = reinterpret_cast<int32_t *>(base + o_x);
+    uint64_t *d_off = prompt_off ? reinterpret_cast<uint64_t *>(base + o_off) : nullptr;
+    uint8_t *d_prompts = total ? reinterpret_cast<uint8_t *>(base + o_p) : nullptr;
+    double *d_u = count > 0 && temperature >= (double)FLT_MIN ? reinterpret_cast<double *>(base + o_u) : nullptr;
+    uint8_t *d_out = reinterpret_cast<uint8_t *>(base + o_out);
+    double *d_bits = reinterpret_cast<double *>(base + o_bits);
+
+    // start state (padding rows zero), inputs
+    const PadMap map = pad_map_rows(1, Nl, N, streams);
+    for (int k = 0; k < 2; k++) {
+        const float *src = k ? c0 : h0;
+        float *dst = k ? Cs : H;
+        if (!src) HIP_TRY(hipMemsetAsync(dst, 0, sizeof(float) * n, h->st));
+        else if (h->padded()) {
+            HIP_TRY(hipMemcpyAsync(stage + k * nl, src, sizeof(float) * nl, hipMemcpyHostToDevice, h->st));
+            pad_copy(stage + k * nl, dst, map, true, h->st);
+            if (int rc = pad_status()) return rc;
+        } else
+            HIP_TRY(hipMemcpyAsync(dst, src, sizeof(float) * n, hipMemcpyHostToDevice, h->st));
+    }
+    if (d_off) HIP_TRY(hipMemcpyAsync(d_off, prompt_off, sizeof(uint64_t) * (streams + 1), hipMemcpyHostToDevice, h->st));
+    if (d_prompts) HIP_TRY(hipMemcpyAsync(d_prompts, prompts, total, hipMemcpyHostToDevice, h->st));
+    if (d_u) HIP_TRY(hipMemcpyAsync(d_u, u, sizeof(double) * nd, hipMemcpyHostToDevice, h->st));
+    HIP_TRY(hipMemsetAsync(d_bits, 0, sizeof(double) * streams, h->st));
+    RUN(K_PACK_U, pack_U(h->P + h->pl.U, Ufwd, nullptr, N, h->st));
+
+    GenHeadArgs a{};
+    a.Why = h->P + h->pl.Why;
+    a.by = h->P + h->pl.by;
+    a.prompts = d_prompts;
+    a.off = d_off;
+    a.u = d_u;
+    a.out = d_out;
+    a.bits = bits ? d_bits : nullptr;
+    a.x_next = xi;
+    a.h_out = ho;
+    a.c_out = ho ? ho + n : nullptr;
+    a.N = N;
+    a.streams = streams;
+    a.count = count;
+    // a temperature below the smallest normal float is the greedy limit (in float it would be 0 or denormal: (z - max z) / tau
+    // would give 0 / 0 at the maximum)
+    a.mode = temperature < (double)FLT_MIN ? 2 : temperature == 1.0 ? 0 : 1;
+    a.tau = (float)temperature;
+    const bool fast = (h->cfg.flags & LSTM_HIP_FAST_MATH) != 0;
+    const long long steps = (long long)max_len + count; // inputs of the longest stream
+    int cur = 0;
+    for (long long t = 0;; t++) {
+        a.H = H + cur * n;
+        a.C = Cs + cur * n;
+        RUN(K_GEN_HEAD, gen_head(a, t, h->st));
+        if (t == steps) break;
+        RUN(K_FWD_STEP, fwd_step(Ufwd, h->P + h->pl.W, h->P + h->pl.b, H + cur * n, Cs + cur * n, H + (cur ^ 1) * n,
+                                 Cs + (cur ^ 1) * n, G, xi, N, streams, fast, h->st));
+        cur ^= 1;
+    }
+
+    if (count > 0) HIP_TRY(hipMemcpyAsync(out, d_out, nd, hipMemcpyDeviceToHost, h->st));
+    if (bits) HIP_TRY(hipMemcpyAsync(bits, d_bits, sizeof(double) * streams, hipMemcpyDeviceToHost, h->st));
+    for (int k = 0; k < 2; k++) {
+        float *dst = k ? c_out : h_out;
+        if (!dst) continue;
+        if (h->padded()) {
+            pad_copy(ho + k * n, stage + k * nl, map, false, h->st);
+            if (int rc = pad_status()) return rc;
+            HIP_TRY(hipMemcpyAsync(dst, stage + k * nl, sizeof(float) * nl, hipMemcpyDeviceToHost, h->st));
+        } else
+            HIP_TRY(hipMemcpyAsync(dst, ho + k * n, sizeof(float) * n, hipMemcpyDeviceToHost, h->st));
+    }
     HIP_TRY(hipStreamSynchronize(h->st));
     return 0;
 }

@@ -1,0 +1,204 @@
+// generate_main.cc -- use a trained model: score files and generate text from a checkpoint, through lstm_hip_generate
+// (include/lstm_hip.h).  The reference's test() and sample() (OV/lstm_eigen_class_CUDA/lstm.cc:578-720, R/lstm.cc:293-356)
+// over many streams at once.  No HIP, no torch here.
+//
+//   lstm_generate --load PREFIX [--score FILE ...] [--count C --streams K --prime TEXT|--prime-file F
+//                 --temperature T --seed S] [--fast-math] [--device D]
+//
+// --load reads the five-file text checkpoint PREFIX_{W,U,Why,b,by}.txt (checkpoint.h); N is the rows of W / 4.
+// --score runs every FILE as one stream from h = c = 0 and prints "FILE: X.XXXXX bits/char (n bytes)" per file (bits over
+// the n - 1 predicted bytes, as lstm_hip_eval_bits) and a total weighted by those bytes.
+// --count prints K samples of C bytes, each continuing from the prompt (--prime / --prime-file, default none) from a zero
+// state; the draws come from SeededRng(S) (rng.h), byte i of stream s taking draw i*K + s, so a seed gives the same text.
+// --temperature 0 is greedy decoding and takes no draws.
+#include "../../include/lstm_hip.h"
+#include "checkpoint.h"
+#include "rng.h"
+
+#include <cerrno>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <algorithm>
+#include <string>
+#include <vector>
+
+namespace {
+
+const char *const kUsage =
+    "usage: lstm_generate --load PREFIX [--score FILE ...] [--count C --streams K --prime TEXT|--prime-file F\n"
+    "                     --temperature T --seed S] [--fast-math] [--device D]\n";
+
+[[noreturn]] void usage(const std::string &m) {
+    fprintf(stderr, "lstm_generate: %s\n%s", m.c_str(), kUsage);
+    exit(2);
+}
+[[noreturn]] void die(const std::string &m) {
+    fprintf(stderr, "lstm_generate: %s\n", m.c_str());
+    exit(1);
+}
+#define CK(call)                                                                \
+    do {                                                                        \
+        int rc_ = (call);                                                       \
+        if (rc_ != 0) die(std::string(#call) + ": " + lstm_hip_last_error());   \
+    } while (0)
+
+bool read_file(const std::string &path, std::vector<uint8_t> &v) {
+    FILE *fp = fopen(path.c_str(), "rb");
+    if (!fp) return false;
+    char buf[1 << 16];
+    while (size_t len = fread(buf, 1, sizeof(buf), fp)) v.insert(v.end(), buf, buf + len);
+    fclose(fp);
+    return true;
+}
+
+// whole-string numbers only: "12x", "" and out-of-range values are usage errors
+long parse_int(const std::string &opt, const std::string &v, long lo, long hi) {
+    char *end = nullptr;
+    errno = 0;
+    const long x = strtol(v.c_str(), &end, 10);
+    if (v.empty() || *end != '\0' || errno != 0 || x < lo || x > hi)
+        usage(opt + " needs an integer in [" + std::to_string(lo) + ", " + std::to_string(hi) + "], got '" + v + "'");
+    return x;
+}
+double parse_double(const std::string &opt, const std::string &v) {
+    char *end = nullptr;
+    const double x = strtod(v.c_str(), &end);
+    if (v.empty() || *end != '\0' || !std::isfinite(x) || x < 0.0) usage(opt + " needs a finite number >= 0, got '" + v + "'");
+    return x;
+}
+
+struct Options {
+    std::string load, prime, prime_file;
+    bool has_prime = false;
+    std::vector<std::string> sampling_opts; // options that only mean something with --count
+    std::vector<std::string> score;
+    long count = -1, streams = 1, device = 0;
+    double temperature = 1.0;
+    uint32_t seed = 1;
+    unsigned flags = 0;
+};
+
+Options parse(int argc, char **argv) {
+    Options o;
+    for (int i = 1; i < argc; i++) {
+        const std::string a = argv[i];
+        auto val = [&]() -> std::string {
+            if (i + 1 >= argc) usage("missing value for " + a);
+            return argv[++i];
+        };
+        if (a == "--load") o.load = val();
+        else if (a == "--score") {
+            o.score.push_back(val());
+            while (i + 1 < argc && std::string(argv[i + 1]).rfind("--", 0) != 0) o.score.push_back(argv[++i]);
+        } else if (a == "--count") o.count = parse_int(a, val(), 0, 1L << 30);
+        else if (a == "--streams") {
+            o.streams = parse_int(a, val(), 1, 4096);
+            o.sampling_opts.push_back(a);
+        }
+        else if (a == "--prime") {
+            o.prime = val();
+            o.has_prime = true;
+            o.sampling_opts.push_back(a);
+        } else if (a == "--prime-file") {
+            o.prime_file = val();
+            o.sampling_opts.push_back(a);
+        } else if (a == "--temperature") {
+            o.temperature = parse_double(a, val());
+            o.sampling_opts.push_back(a);
+        } else if (a == "--seed") {
+            o.seed = (uint32_t)parse_int(a, val(), 0, 0xFFFFFFFFL);
+            o.sampling_opts.push_back(a);
+        }
+        else if (a == "--device") o.device = parse_int(a, val(), 0, 1 << 20);
+        else if (a == "--fast-math") o.flags |= LSTM_HIP_FAST_MATH;
+        else if (a == "-h" || a == "--help") {
+            printf("%s", kUsage);
+            exit(0);
+        } else usage("unknown argument " + a);
+    }
+    if (o.load.empty()) usage("--load PREFIX is required");
+    if (o.score.empty() && o.count < 0) usage("nothing to do: give --score and/or --count");
+    if (o.has_prime && !o.prime_file.empty()) usage("--prime and --prime-file exclude each other");
+    if (o.count < 0 && !o.sampling_opts.empty()) usage(o.sampling_opts[0] + " needs --count");
+    if ((long long)std::max(o.count, 0L) * o.streams > (1LL << 31) - 1) usage("--count x --streams is too large");
+    return o;
+}
+
+} // namespace
+
+int main(int argc, char **argv) {
+    const Options o = parse(argc, argv);
+    const int M = LSTM_HIP_VOCAB;
+    std::string err;
+    const int N = checkpoint::hidden_size(o.load, M, &err);
+    if (N == 0) die(err);
+    std::vector<float> P(lstm_hip_param_count(N, M));
+    const int rc = checkpoint::load_params(o.load, P, N, M, &err);
+    if (rc == 0) die("missing a file of " + o.load + "_{W,U,Why,b,by}.txt");
+    if (rc < 0) die(err);
+    std::vector<std::vector<uint8_t>> texts;
+    for (const std::string &f : o.score) {
+        texts.emplace_back();
+        if (!read_file(f, texts.back())) die("cannot read " + f);
+        if (texts.back().size() < 2) die(f + ": need at least 2 bytes to score");
+    }
+    std::vector<uint8_t> prime(o.prime.begin(), o.prime.end());
+    if (!o.prime_file.empty() && !read_file(o.prime_file, prime)) die("cannot read " + o.prime_file);
+
+    // every hidden size runs (LSTM_HIP_PAD_HIDDEN); S and B of the handle are not used by the generator
+    lstm_hip_config cfg{N, M, 2, 1, (int32_t)o.device, o.flags | LSTM_HIP_PAD_HIDDEN};
+    lstm_hip_t *h = nullptr;
+    CK(lstm_hip_create(&cfg, &h));
+    CK(lstm_hip_set_params(h, 0, P.data()));
+
+    if (!texts.empty()) { // one stream per file, in chunks of at most 4096 files
+        double sum_bits = 0.0, sum_chars = 0.0;
+        for (size_t f0 = 0; f0 < texts.size(); f0 += 4096) {
+            const size_t k = std::min<size_t>(4096, texts.size() - f0);
+            std::vector<uint64_t> off(k + 1, 0);
+            std::vector<uint8_t> all;
+            for (size_t s = 0; s < k; s++) {
+                all.insert(all.end(), texts[f0 + s].begin(), texts[f0 + s].end());
+                off[s + 1] = all.size();
+            }
+            std::vector<double> bits(k);
+            CK(lstm_hip_generate(h, (int32_t)k, all.data(), off.data(), nullptr, nullptr, 1.0, nullptr, 0, nullptr, bits.data(),
+                                 nullptr, nullptr));
+            for (size_t s = 0; s < k; s++) {
+                const size_t n = texts[f0 + s].size();
+                printf("%s: %.5f bits/char (%zu bytes)\n", o.score[f0 + s].c_str(), bits[s] / (double)(n - 1), n);
+                sum_bits += bits[s];
+                sum_chars += (double)(n - 1);
+            }
+        }
+        printf("total: %.5f bits/char (%.0f bytes scored in %zu files)\n", sum_bits / sum_chars, sum_chars, texts.size());
+    }
+
+    if (o.count >= 0) {
+        const int K = (int)o.streams, C = (int)o.count;
+        std::vector<uint64_t> off(K + 1);
+        std::vector<uint8_t> prompts;
+        for (int s = 0; s < K; s++) {
+            prompts.insert(prompts.end(), prime.begin(), prime.end());
+            off[s + 1] = prompts.size();
+        }
+        std::vector<double> u;
+        if (o.temperature > 0.0) {
+            SeededRng rng(o.seed);
+            u.resize((size_t)C * K);
+            for (double &x : u) x = rng.uniform();
+        }
+        std::vector<uint8_t> out((size_t)C * K);
+        CK(lstm_hip_generate(h, K, prompts.data(), off.data(), nullptr, nullptr, o.temperature, u.empty() ? nullptr : u.data(), C,
+                             out.data(), nullptr, nullptr, nullptr));
+        for (int s = 0; s < K; s++) {
+            printf("== sample %d ==\n", s);
+            fwrite(prime.data(), 1, prime.size(), stdout);
+            for (int i = 0; i < C; i++) fputc(out[(size_t)i * K + s], stdout);
+            fputc('\n', stdout);
+        }
+    }
+    CK(lstm_hip_destroy(h));
+    return 0;
+}

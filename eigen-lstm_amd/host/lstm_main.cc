@@ -23,6 +23,7 @@
 // --lr-warmup-windows X applies lr = 0 for the first X windows (the reference's GPU driver uses
 // X = 50*S, OV/lstm_eigen_class_CUDA/lstm.cc:364-367; 0 = the root file's behaviour).
 #include "../../include/lstm_hip.h"
+#include "checkpoint.h"
 #include "matrix_io.h"
 #include "rng.h"
 
@@ -105,47 +106,16 @@ double count_flops(double M, double N, double S, double B) {
            8 * (M * N + M + N * 4 * N + N * 4 * M + N * 4);
 }
 
-// Parameters::save_to_disk / load_from_disk, OV/lstm_eigen_class_CUDA/lstm.h:83-101, io.h:16-74:
-// five text files <prefix>_{W,U,Why,b,by}.txt in the reference's own layout (matrix_io.h): loadable by either program.
-struct Block {
-    const char *name;
-    size_t rows, cols, off;
-};
-std::vector<Block> blocks(int N, int M) {
-    size_t o = 0;
-    std::vector<Block> b;
-    auto add = [&](const char *n, size_t r, size_t c) {
-        b.push_back({n, r, c, o});
-        o += r * c;
-    };
-    add("W", 4 * (size_t)N, M);
-    add("U", 4 * (size_t)N, N);
-    add("b", 4 * (size_t)N, 1);
-    add("Why", M, N);
-    add("by", M, 1);
-    return b;
-}
+// Parameters::save_to_disk / load_from_disk (checkpoint.h), ending the program on an error
 void save_params(const std::string &prefix, const std::vector<float> &P, int N, int M, int digits = 6) {
-    for (const Block &b : blocks(N, M)) {
-        const std::string path = prefix + "_" + b.name + ".txt";
-        if (!matrix_io::write_matrix(path, b.rows, b.cols, [&](size_t r, size_t c) { return P[b.off + c * b.rows + r]; }, digits))
-            die("cannot write " + path);
-    }
+    std::string err;
+    if (!checkpoint::save_params(prefix, P, N, M, digits, &err)) die(err);
 }
 bool load_params(const std::string &prefix, std::vector<float> &P, int N, int M) {
-    for (const Block &b : blocks(N, M)) {
-        const std::string path = prefix + "_" + b.name + ".txt";
-        size_t rows = 0, cols = 0;
-        if (!std::ifstream(path).good()) return false;
-        if (!matrix_io::read_matrix(path, [&](size_t r, size_t c, double v) {
-                if (r < b.rows && c < b.cols) P[b.off + c * b.rows + r] = (float)v;
-            }, &rows, &cols))
-            die(path + ": rows of different lengths");
-        if (rows != b.rows || cols != b.cols)
-            die(path + ": " + std::to_string(rows) + " x " + std::to_string(cols) + ", expected " + std::to_string(b.rows) + " x " +
-                std::to_string(b.cols));
-    }
-    return true;
+    std::string err;
+    const int rc = checkpoint::load_params(prefix, P, N, M, &err);
+    if (rc < 0) die(err);
+    return rc > 0;
 }
 
 // results log, OV/lstm_eigen_class_CUDA/lstm.cc:203-226 + io.h:16-30: the whole 5-column matrix is rewritten after
@@ -260,7 +230,7 @@ int run_rank(const Options &o, int rank, int up, int down) {
     std::vector<float> P(np, 0.0f);
     SeededRng rng(o.seed);
     {
-        auto bl = blocks(N, M);
+        auto bl = checkpoint::blocks(N, M);
         rng.randn(P.data() + bl[0].off, 4 * N, M, 0.0, 0.01);
         rng.randn(P.data() + bl[1].off, 4 * N, N, 0.0, 0.01);
         rng.randn(P.data() + bl[3].off, M, N, 0.0, 0.01);

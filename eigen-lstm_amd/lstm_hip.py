@@ -24,6 +24,7 @@ NO_FUSED_GRADS = 64
 BF16_RECURRENCE = 128
 PAD_HIDDEN = 256  # any hidden size >= 1, run at an internal padded width (include/lstm_hip.h); shapes stay logical
 LOSS_ALL_STEPS_BITS, LOSS_LAST_STEP_NATS, LOSS_LAST_STEP_BITS = 0, 1, 2
+OK, EINVAL, EHIP, ENODEV, ERCCL, ESTATE = 0, -1, -2, -3, -4, -5  # LSTM_HIP_OK, LSTM_HIP_E* return codes
 UNIQUE_ID_BYTES = 128
 VOCAB = 256
 
@@ -49,7 +50,7 @@ SYMBOLS = [
     "lstm_hip_adagrad", "lstm_hip_comm_unique_id", "lstm_hip_comm_init", "lstm_hip_allreduce_grads",
     "lstm_hip_set_text", "lstm_hip_set_cursors", "lstm_hip_get_cursors", "lstm_hip_reset_window",
     "lstm_hip_get_window", "lstm_hip_train_windows", "lstm_hip_set_global_batch", "lstm_hip_set_loss_mode", "lstm_hip_set_stride", "lstm_hip_eval_bits",
-    "lstm_hip_sample", "lstm_hip_synchronize", "lstm_hip_set_profiling", "lstm_hip_kernel_stat_count",
+    "lstm_hip_sample", "lstm_hip_generate", "lstm_hip_synchronize", "lstm_hip_set_profiling", "lstm_hip_kernel_stat_count",
     "lstm_hip_kernel_stat", "lstm_hip_reset_kernel_stats", "lstm_hip_device_info", "lstm_hip_debug_stamps",
 ]
 
@@ -260,6 +261,39 @@ class Lstm:
         _chk(self.lib.lstm_hip_sample(self._h, _ptr(h0), _ptr(c0), _ptr(u, C.c_double), int(u.size),
                                       _ptr(out, C.c_uint8)))
         return out, h0, c0
+
+    def generate(self, prompts=None, count=0, u=None, temperature=1.0, h0=None, c0=None, streams=None, score=False):
+        """lstm_hip_generate: `streams` independent streams, each fed its prompt (bytes or a uint8 array) and then `count`
+        drawn bytes.  u: draws [count, streams] (may be None only at temperature 0); h0, c0: [streams, N] or None (zeros).
+        Returns (out [count, streams] uint8, bits [streams] float64 -- the prompts' summed -log2 p, or None unless
+        score --, h [streams, N], c [streams, N]: the state after each stream's last input)."""
+        if streams is None:
+            streams = len(prompts) if prompts is not None else (np.asarray(h0).shape[0] if h0 is not None else
+                                                                (np.asarray(u).reshape(count, -1).shape[1] if u is not None and count > 0 else 1))
+        streams = int(streams)
+        d_p = d_off = None
+        if prompts is not None:
+            assert len(prompts) == streams, (len(prompts), streams)
+            parts = [np.frombuffer(bytes(p), np.uint8) if isinstance(p, (bytes, bytearray)) else np.asarray(p, np.uint8).ravel()
+                     for p in prompts]
+            off = np.zeros(streams + 1, np.uint64)
+            off[1:] = np.cumsum([q.size for q in parts])
+            d_p = np.ascontiguousarray(np.concatenate(parts) if off[-1] > 0 else np.zeros(1, np.uint8))
+            d_off = off
+        hh = None if h0 is None else _f32(h0).reshape(streams, self.N)
+        cc = None if c0 is None else _f32(c0).reshape(streams, self.N)
+        uu = None if u is None else np.ascontiguousarray(u, dtype=np.float64).reshape(count, streams)
+        out = np.zeros((count, streams), np.uint8)
+        bits = np.zeros(streams, np.float64) if score else None
+        h = np.empty((streams, self.N), np.float32)
+        c = np.empty((streams, self.N), np.float32)
+        _chk(self.lib.lstm_hip_generate(self._h, C.c_int32(streams), _ptr(d_p, C.c_uint8) if d_p is not None else None,
+                                        _ptr(d_off, C.c_uint64) if d_off is not None else None,
+                                        _ptr(hh) if hh is not None else None, _ptr(cc) if cc is not None else None,
+                                        C.c_double(temperature), _ptr(uu, C.c_double) if uu is not None else None,
+                                        C.c_int32(count), _ptr(out, C.c_uint8), _ptr(bits, C.c_double) if score else None,
+                                        _ptr(h), _ptr(c)))
+        return out, bits, h, c
 
     def debug_stamps(self):
         out = np.zeros((4, self.S, 16), np.uint64)  # [fwd wg0, fwd wg1, bwd wg0, bwd wg1][step][slot]

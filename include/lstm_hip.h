@@ -169,6 +169,26 @@ int lstm_hip_set_loss_mode(lstm_hip_t *h, int32_t mode);
  *      bytes from state (h0,c0) (N floats each, in/out) using the caller's uniform draws u[i]. */
 int lstm_hip_eval_bits(lstm_hip_t *h, const uint8_t *text, size_t len, double *bits_per_char);
 int lstm_hip_sample(lstm_hip_t *h, float *h0, float *c0, const double *u, int32_t count, uint8_t *out);
+/* ---- batched, prompted sampling and per-text scoring (the loops of R/lstm.cc:293-356 and
+ *      OV/lstm_eigen_class_CUDA/lstm.cc:578-720 over many independent streams at once).  Per stream s:
+ *        start   state column s of h0 / c0 (N x streams each; NULL = zeros, test()'s reset_std = 0)
+ *        prompt  prompts[prompt_off[s] .. prompt_off[s+1]) fed as inputs (prompts and prompt_off may both be NULL:
+ *                no prompts); bits[s] (may be NULL) = sum over prompt positions j = 1..L-1 of -log2 p(prompt[j]) at
+ *                temperature 1, so bits[s] / (L-1) is the text's lstm_hip_eval_bits from a zero start
+ *        sample  then `count` bytes, byte i drawn from the current h and fed back as the next input (as lstm_hip_sample):
+ *                with z = Why*h + by, temperature 1: p = expf(z) / sum (unshifted); other temperature > 0:
+ *                p ~ expf((z - max z) / temperature); 0 (and any temperature below FLT_MIN, its limit): argmax z,
+ *                lowest index on ties.  The byte is the first m with
+ *                u < cdf[m] (sequential float sum), 0 if none; the draw is u[i*streams + s] (u may be NULL only for
+ *                temperature 0) and the byte goes to out[i*streams + s]
+ *        final   h_out / c_out (N x streams each, may be NULL) receive the state after the stream's last input
+ *      N is the logical N of the handle.  Computed from the fp32 parameters whatever the precision flags
+ *      (LSTM_HIP_FAST_MATH applies); nothing else of the handle is read or changed (gradients, Adagrad memory, window,
+ *      cursors, carry).  LSTM_HIP_EINVAL: streams outside 1..4096, count < 0, offsets not starting at 0 or decreasing,
+ *      temperature negative or not finite, u missing with temperature > 0 and count > 0, out missing with count > 0. */
+int lstm_hip_generate(lstm_hip_t *h, int32_t streams, const uint8_t *prompts, const uint64_t *prompt_off,
+                      const float *h0, const float *c0, double temperature, const double *u, int32_t count,
+                      uint8_t *out, double *bits, float *h_out, float *c_out);
 
 /* ---- measurement.  With profiling on, every kernel launch is bracketed by HIP events on the
  *      handle's stream and per-kernel totals accumulate. */
