@@ -21,6 +21,60 @@ struct ParamLayout {
     }
 };
 
+// ---- which form of each recurrence a handle runs (plan_engine, persistent.hip) ------------------------------------------
+// Decided once per handle at create from the shape, the create flags and the CU count; every launch of the window follows it.
+enum class FwdForm {
+    Step,       // one fwd_step launch per timestep (LSTM_HIP_STEP_KERNELS, or no co-resident persistent grid)
+    Small,      // k_small_fwd: one stream at hidden 64 / 128, the whole recurrence on one CU
+    Persistent, // fwd_persistent: one recurrence on 16x16x4 tiles (k_fwd_persistent / k_fwd_persistent2), image Ufwd
+    Cols8,      // fwd_persistent4: 8-column groups on 4x4x1, image Ufwd4, ring Hx
+    TwoHalf,    // fwd_persistent6: two alternating 4-column halves per group, Ufwd4 in the Ufwd5 layout, ring Hx; column launches
+    Bf16,       // fwd_persistent_bf16: the bf16 one-recurrence forms, image Ufwd16
+    Bf16Halves, // fwd_halves_bf16: the bf16 two-half form, image Ufwd6b, ring Hxb; column launches
+};
+enum class BwdForm {
+    Step,        // one bwd_step launch per timestep
+    Small,       // k_small_bwd (reads the tile image Ubwd)
+    Persistent,  // bwd_persistent on 16-column groups, 16x16x4 tiles, image Ubwd
+    Cols8,       // bwd_persistent on 8-column groups, 4x4x1, image Ubwd4
+    Scatter,     // bwd_scatter: two-half scatter form, Ubwd4 in the Ubwd6 layout, partial-sum ring DGx; column launches
+    Bf16,        // bwd_persistent on the bf16 image Ubwd16 (4-, 8- or 16-column groups)
+    Bf16Scatter, // bwd_scatter_bf16: image Ubwd6b, ring DGx; column launches
+};
+struct EnginePlan {
+    FwdForm fwd = FwdForm::Step;
+    BwdForm bwd = BwdForm::Step;
+    int n_cus = 0;
+    bool fused = false;     // dW / db / dWhy (and Why^T dy) inside the backward recurrence, as per-group partial blocks (gpart)
+    int bwd_cols = 16;      // batch columns per workgroup of bwd_persistent (Persistent, Cols8, Bf16)
+    int gpart_cols = 8;     // batch columns per fused partial block
+    int fwd_cols = 16;      // Bf16 forward: 8- or 16-column groups
+    // the multi-launch forms (TwoHalf, Scatter, Bf16Halves, Bf16Scatter): one launch per `launch_cols` columns of the batch,
+    // `group_cols` (4 or 8) columns per group; a launch of fewer than 8 groups is pinned one group per XCD where *_pin
+    int launch_cols = 0, group_cols = 8;
+    bool fwd_pin = false, bwd_pin = false;
+    int poll_cfg = 0;         // Cols8 / TwoHalf: bits 0-7 s_sleep between polls, 8-15 first delay of the non-gating waves
+    int bwd_cfg = 0;          // Scatter: the kernel's tuning / test bits (LSTM_HIP_BWD_HALVES >> 1)
+    bool bwd_spread = false;  // LSTM_HIP_BWD_SPREAD: keep the dispatch-order workgroup mapping of the backward recurrence
+    bool side_stream = false; // unfused Scatter: the sums that do not feed the recurrence run on the second stream beside it
+    bool direct_dgt = false;  // Bf16Scatter: the recurrence writes the k-contiguous bf16 image of dg for the dU product
+    bool adagrad_quad = false; // Adagrad refreshes the two-half images (Ufwd5 + Ubwd6, or Ufwd6b) with quad transposes
+    bool du_split = false;    // LSTM_HIP_DU_SPLIT (fp32, communicator loop): dU as two column halves, the first reduced early
+    bool stamps = false;      // LSTM_HIP_DEBUG_STAMPS on a shape whose forms carry stamps
+    // live images and rings (sizes in elements; 0: none)
+    size_t hx_floats = 0;        // Hx
+    size_t hxb_halfwords = 0;    // Hxb
+    size_t dgx_floats = 0;       // DGx
+    bool u16 = false;            // Ufwd16 / Ubwd16 (a bf16 one-recurrence form runs)
+    char refusal[192] = "";      // non-empty: the shape cannot run; the reason
+    bool bf16() const { return fwd == FwdForm::Bf16 || fwd == FwdForm::Bf16Halves; }
+    bool persistent() const { return fwd != FwdForm::Step; }
+    bool ufwd4() const { return fwd == FwdForm::Cols8 || fwd == FwdForm::TwoHalf; }
+    bool ubwd4() const { return bwd == BwdForm::Cols8 || bwd == BwdForm::Scatter; }
+    int half_forms() const { return (fwd == FwdForm::TwoHalf ? 1 : 0) | (bwd == BwdForm::Scatter ? 4 : 0); } // layouts of Ufwd4 / Ubwd4
+};
+EnginePlan plan_engine(int N, int B, unsigned flags, int n_cus);
+
 // ---- recurrent weight repack (once per window, after Adagrad) -------------------------------
 // Ufwd[N/4][N/16][64] float4 : MFMA 16x16x4 A-fragments of U for the forward product
 // Ubwd[N/16][N/4][64] float4 : A-fragments of U^T for the backward product
@@ -28,8 +82,6 @@ struct ParamLayout {
 // image of the two-half forward form (k_fwd_persistent6) instead
 void pack_U(const float *U, float4 *Ufwd, float4 *Ubwd, int N, hipStream_t st, float4 *Ubwd4 = nullptr,
             float4 *Ufwd4 = nullptr, int half_forms = 0);
-bool fwd_uses_8col_form(int N, int B, int n_cus); // forward recurrence on 8-column groups (k_fwd_persistent4, Ufwd4 image)
-bool bwd_uses_m4(int N, int cols, bool bf16);     // backward recurrence on v_mfma_f32_4x4x1 (8-column groups, fp32, Ubwd4 image)
 
 // ---- baseline engine: one launch per timestep -----------------------------------------------
 // g = U*h_prev + W[:,x] + b ; gates ; c = tanh(i*u + f*c_prev) ; h = o*c      (R/lstm.cc:176-192)
@@ -42,89 +94,70 @@ void bwd_step(const float4 *Ubwd, const float *DGnext /*null at t=S-1*/, const f
 // ---- default engine: each recurrence of a window as ONE persistent launch (persistent.hip) ----
 // Weights stay in VGPRs; the steps are chained inside the launch.  Hand-off, by form:
 //   8-column forward form and (optionally) the fp32 4x4x1 backward form: data-as-flag through a ring of sentinel-filled
-//     step slots (Hx / DGx; *_ring_floats() floats, filled with 0xFF bytes once and after an abort; ring_base starts at 0
+//     step slots (Hx / DGx; EnginePlan sizes, filled with 0xFF bytes once and after an abort; ring_base starts at 0
 //     and moves by *_ring_advance() after every launch);
 //   every other form: sc1 stores + sharded device-scope counters.  `cnt` must hold persistent_counter_bytes() bytes
 //     (separate regions for fwd and bwd), zeroed once; `epoch` = 1, 2, ... counts the launches that used that region
 //     (counters are cumulative).  The ring forms use the step-0 slots of `cnt` for their XCD placement check.
 // `abortp` is one zeroed word that a timed-out spin sets.  `stamps` (diagnostic builds, N = 512 only): [2][S][16] u64.
+// The multi-launch forms take columns [col0, col0 + cols) of the batch per launch, in groups of `gc` columns; `pin`: a launch
+// of fewer than 8 groups runs pinned, one group per XCD (EnginePlan).
 size_t persistent_counter_bytes(int S, int B);
-bool persistent_supported(int N, int B, int n_cus, bool fused);      // fused: dW/db/DHy/dWhy inside the backward recurrence
-bool persistent_supported_bf16(int N, int B, int n_cus, bool fused); // the bf16 recurrence's own kernels and grids
-int bwd_group_cols_bf16(int N, int B, int n_cus, bool fused);        // 8 where that grid is co-resident, else 16
 void fwd_persistent(const float4 *Ufwd, const float *W, const float *bias, float *H, float *C, float *G,
                     const int32_t *xi, unsigned *cnt, unsigned *abortp, unsigned epoch, int N, int S, int B, bool fast,
                     hipStream_t st);
-size_t fwd_ring_floats(int N, int B);
 int fwd_ring_advance(int ring_base, int S);
 void fwd_persistent4(const float4 *Ufwd4, const float *W, const float *bias, float *H, float *C, float *G, const int32_t *xi,
                      float *Hx, unsigned *cnt, unsigned *abortp, unsigned epoch, int ring_base, int N, int S, int B, bool fast,
                      int poll_cfg, hipStream_t st, unsigned long long *stamps = nullptr);
-// two-half form (N = 512): the same grid and ring, each workgroup's eight columns advanced as two alternating 4-column
-// recurrences; weights in the Ufwd5 image (pack_U / adagrad with half_forms)
-bool fwd_uses_two_half_form(int N, int B, int n_cus);
+// two-half form (N = 512 / 256): the same ring, each group's eight columns advanced as two alternating 4-column recurrences
+// (or one, gc = 4); weights in the Ufwd5 image (pack_U / adagrad with half_forms)
 void fwd_persistent6(const float4 *Ufwd5, const float *W, const float *bias, float *H, float *C, float *G, const int32_t *xi,
                      float *Hx, unsigned *cnt, unsigned *abortp, unsigned epoch, int ring_base, int N, int S, int B, bool fast,
-                     int poll_cfg, hipStream_t st, unsigned long long *stamps = nullptr, int col0 = 0, int cols = 0);
-// columns one launch of the fp32 two-half forms takes; a wider batch (two_half_wide) runs as launches over column ranges
-// [col0, col0 + cols) -- cols = 0: the whole batch
-int two_half_launch_cols(int N, int n_cus);
-int two_half_group_cols(int N, int B, int n_cus);     // forward: 8, or 4 (one half per workgroup) where the batch then fits one launch
-int bwd_scatter_group_cols(int N, int B, int n_cus);  // backward: the same rule; the fused partial blocks are one per group
-bool two_half_wide(int N, int B, int n_cus);
+                     int poll_cfg, int col0, int cols, int gc, bool pin, hipStream_t st, unsigned long long *stamps);
 // two-half (scatter) form of the backward recurrence (N = 512 / 256, 8-column groups): every workgroup advances its eight
 // columns as two alternating 4-column recurrences, multiplies its OWN dg_t into partial sums for all N outputs and scatters
 // them to the owners of the outputs.  Ubwd6 image (pack_U / adagrad with bit 2 of half_forms), partial-sum ring Qx
-// (bwd_ring_floats floats, sentinel-filled like the other rings; ring_base moves by bwds_ring_advance); computes Why^T dy
-// itself; gpart != null: fused mode as below.  cfg: tuning / test bits (16: keep the dispatch-order workgroup mapping).
-bool bwd_scatter_supported(int N, int B, int n_cus, bool fused);
+// (sentinel-filled like the other rings; ring_base moves by bwds_ring_advance); computes Why^T dy itself; gpart != null:
+// fused mode as below.  cfg: tuning / test bits (16: keep the dispatch-order workgroup mapping).
 int bwds_ring_advance(int ring_base, int S);
 void bwd_scatter(const float4 *Ubwd6, float *DG, const float *Why, const float *dY, const float *G, const float *C, const float *H,
                  const int32_t *xi, float *gpart, float *Qx, unsigned *cnt, unsigned *abortp, unsigned epoch, int ring_base, int N,
-                 int S, int B, int cfg, hipStream_t st, unsigned long long *stamps = nullptr, int col0 = 0, int cols = 0);
+                 int S, int B, int cfg, int col0, int cols, int gc, bool pin, hipStream_t st, unsigned long long *stamps);
 // gpart != null (8-column groups only): fused mode.  The recurrence then also produces DHy on the fly from
 // Why and dY (DHy is not read), and leaves per-column-group partial blocks [dW | - | db | dWhy]
-// (bwd_partial_floats(N) floats each) to be folded in group order; H and xi are read as well.
+// (bwd_partial_floats(N) floats each) to be folded in group order; H and xi are read as well.  spread: keep the
+// dispatch-order workgroup mapping (column groups over all XCDs).
 void bwd_persistent(const float4 *Ubwd, float *DG, const float *DHy, const float *G, const float *C, const float *H,
                     const int32_t *xi, float *gpart, const float *Why, const float *dY, unsigned *cnt, unsigned *abortp,
-                    unsigned epoch, int N, int S, int B, int cols, hipStream_t st, unsigned long long *stamps = nullptr,
+                    unsigned epoch, int N, int S, int B, int cols, bool spread, hipStream_t st, unsigned long long *stamps = nullptr,
                     unsigned short *DGb = nullptr);
-size_t bwd_ring_floats(int N, int B);
-int bwd_ring_advance(int ring_base, int S);
 // bf16 recurrence (N % 128 == 0): bf16 fragment images of U (N*N*8 bytes each), h and dg also kept as bf16
 // hand-off copies Hb [S][B][N], DGb [S][B][4N]; bwd_persistent takes the Ubwd16 image as `Ubwd` and DGb != null
 void pack_U_bf16(const float *U, void *Ufwd16, void *Ubwd16, int N, hipStream_t st);
 void fwd_persistent_bf16(const void *Ufwd16, const float *W, const float *bias, float *H, unsigned short *Hb, float *C,
                          float *G, const int32_t *xi, unsigned *cnt, unsigned *abortp, unsigned epoch, int N, int S, int B,
-                         bool fast, hipStream_t st, int n_cus);
-// scatter form of the bf16 backward recurrence (N = 256 / 512 / 1024, 8-column groups co-resident): Ubwd6b image (pack_U6_bf16,
-// N*N*8 bytes), partial-sum ring Qx as in bwd_scatter; reads DHy (a launch of its own in the bf16 path), writes the fp32 DG
-bool bwd_scatter_bf16_supported(int N, int B, int n_cus);
+                         bool fast, int cols, hipStream_t st);
+// scatter form of the bf16 backward recurrence (N = 256 / 512 / 1024): Ubwd6b image (pack_U6_bf16, N*N*8 bytes), partial-sum
+// ring Qx as in bwd_scatter; reads DHy (a launch of its own in the bf16 path), writes the fp32 DG
 void pack_U6_bf16(const float *U, void *Ubwd6b, int N, hipStream_t st);
 // two-half form of the bf16 forward recurrence (k_fwd_halves_bf16): weights image Ufwd6b (N*N*8 bytes), bf16 sentinel ring Hxb
-// (fwd_halves_bf16_ring_halfwords, all ones at rest; slots advance with fwd_ring_advance)
-bool fwd_halves_bf16_supported(int N, int B, int n_cus);
+// (all ones at rest; slots advance with fwd_ring_advance)
 void pack_Ufwd6_bf16(const float *U, void *img, int N, hipStream_t st);
-size_t fwd_halves_bf16_ring_halfwords(int N, int B);
 void fwd_halves_bf16(const void *Ufwd6b, const float *W, const float *bias, float *H, unsigned short *Hb, float *C, float *G,
                      const int32_t *xi, void *Hxb, unsigned *cnt, unsigned *abortp, unsigned epoch, int ring_base, int N, int S,
-                     int B, int col0, int cols, bool fast, int n_cus, hipStream_t st, unsigned long long *stamps);
-int fwd_halves_bf16_launch_cols(int N, int B, int n_cus); // a launch takes this many columns; wider batches run as several launches
-size_t bwd_scatter_bf16_ring_floats(int N, int B, int n_cus);
-int bwd_scatter_bf16_launch_cols(int N, int B, int n_cus);
+                     int B, int col0, int cols, int gc, bool pin, bool fast, hipStream_t st, unsigned long long *stamps);
 int bwd_scatter_bf16_units(int N);
 int bwd_scatter_bf16_ring_advance(int base, int S);
 void bwd_scatter_bf16(const void *Ubwd6b, float *DG, const float *DHy, const float *G, const float *C, float *Qx, unsigned *cnt,
-                      unsigned *abortp, unsigned epoch, int ring_base, int N, int S, int B, int col0, int cols, int n_cus, hipStream_t st,
-                      unsigned long long *stamps, unsigned short *DGt_b = nullptr, int Tpad = 0);
+                      unsigned *abortp, unsigned epoch, int ring_base, int N, int S, int B, int col0, int cols, int gc, bool pin,
+                      hipStream_t st, unsigned long long *stamps, unsigned short *DGt_b = nullptr, int Tpad = 0);
 // one stream, hidden 64 / 128: both recurrences on one CU (k_small_fwd, k_small_bwd); they read U and Why as stored, write H, C,
 // G and DG (the backward one reads U from the Ubwd tile image); the backward one computes Why^T dy itself (no DHy), dW / db / dWhy / dU are the unfused path's launches
-bool small_recurrence_supported(int N, int B);
 void small_fwd(const float *U, const float *W, const float *bias, float *H, float *C, float *G, const int32_t *xi, int N, int S, bool fast,
                hipStream_t st);
 void small_bwd(const float4 *Ubwd, const float *Why, const float *dY, const float *G, const float *C, float *DG, int N, int S, hipStream_t st);
 size_t bwd_partial_floats(int N);
-int bwd_group_cols(int N, int B, int n_cus); // 8 or 16 batch columns per backward workgroup
 
 // ---- time-batched dense products (gemm.hip: fp32 MFMA 32x32x2, operands streamed into registers, K split over the waves
 //      of a workgroup) --------------------------------------------------------------------------
@@ -141,7 +174,6 @@ void gemm_fold(const float *slabs, int splits, int M, int Nn, float *C, int ldc,
 // the split-K product without its fold (slabs densely packed, M*Nn floats each); returns the number of slabs written
 int gemm_slabs(bool TA, bool TB, int M, int Nn, int K, const float *A, int lda, const float *B, int ldb, float *slabs, int splits,
                hipStream_t st);
-void gemm_probe_small_kfast(int M, int Nn, int K, const float *A, int lda, const float *B, int ldb, float *C, int ldc, hipStream_t st);
 // the same by operand layout ("k fast": the contraction index is the contiguous one); gemm / gemm_slabs map onto these
 int gemm_regs_splits(bool a_kfast, bool b_kfast, int M, int Nn, int K, int n_cus);
 int gemm_regs(bool a_kfast, bool b_kfast, int M, int Nn, int K, const float *A, int lda, const float *B, int ldb, float *C, int ldc,
@@ -182,10 +214,6 @@ void dW_sort(const int32_t *xi, int T, int G4, void *scratch, hipStream_t st);
 void dW_sums(const float *DG, int T, int G4, float *dW, float *db, void *scratch, hipStream_t st);
 
 // ---- Adagrad over the flat block (R/lstm.cc:261-272; eps added in double, :25,46-48)
-// When Ufwd/Ubwd are given, the U block also refreshes both MFMA fragment images (fused pack_U).
-// gpart != null: the gradient is still in pieces -- `n_groups` partial blocks [dW | - | db | dWhy] (group_stride floats apart)
-// and, when slabs != null, `n_slabs` split-K slabs of dU; they are summed here in the order the separate folds use and the
-// sums are also stored to dP.  by_off: float offset of dby in the flat block (dby is final in dP).
 // the NEXT window's slide (slide_window's arguments), carried by an Adagrad launch in extra workgroups: inside the window loop
 // the slide of window i+1 needs nothing Adagrad of window i produces and touches nothing it reads
 struct SlideJob {
@@ -196,12 +224,33 @@ struct SlideJob {
     float *H, *C;
     int S, B, N, stride, carry_col;
 };
-void adagrad(float *P, float *dP, float *mem, size_t n, float lr, size_t u_off, int N, float4 *Ufwd, float4 *Ubwd,
-             hipStream_t st, float4 *Ubwd4 = nullptr, float4 *Ufwd4 = nullptr, const float *gpart = nullptr, int n_groups = 0,
-             size_t group_stride = 0, size_t by_off = 0, const float *slabs = nullptr, int n_slabs = 0, size_t slab_stride = 0,
-             int half_forms = 0, void *u6b = nullptr, int u6_uw = 0, unsigned short *why_b = nullptr,
-             unsigned short *whyT_b = nullptr, size_t why_off = 0, const SlideJob *slide = nullptr, void *uf6b = nullptr,
-             int uf6_uw = 0);
+// One Adagrad launch: the update of the flat block P / dP / mem (n floats, U at float offset u_off) and what it carries:
+//  - the live images of U, refreshed from the updated block: fp32 Ufwd / Ubwd (16x16x4 tiles) and Ufwd4 / Ubwd4 in the
+//    layouts half_forms names (pack_U); bf16 u6b (scatter-form backward image, u6_uw units per workgroup) and uf6b (two-half
+//    forward image, quad launches only); Why as bf16 in place order and transposed (why_off: float offset of Why); null: none
+//  - gpart != null: the gradient still in pieces -- n_groups partial blocks [dW | - | db | dWhy] group_stride floats apart and,
+//    when slabs != null, n_slabs split-K slabs of dU slab_stride floats apart; they are summed here in the order the separate
+//    folds use and the sums are also stored to dP (by_off: float offset of dby, final in dP)
+//  - slide: the next window's slide (or null); quad: the two-half images (Ufwd4 + Ubwd4 with half_forms 5, or uf6b) are
+//    written through quad transposes
+struct AdagradJob {
+    float *P, *dP, *mem;
+    size_t n, u_off;
+    int N;
+    float lr;
+    float4 *Ufwd, *Ubwd, *Ubwd4, *Ufwd4;
+    int half_forms;
+    void *u6b, *uf6b;
+    int u6_uw, uf6_uw;
+    unsigned short *why_b, *whyT_b;
+    size_t why_off;
+    const float *gpart, *slabs;
+    int n_groups, n_slabs;
+    size_t group_stride, slab_stride, by_off;
+    const SlideJob *slide;
+    bool quad;
+};
+void adagrad(const AdagradJob &job, hipStream_t st);
 int fwd_halves_bf16_units(int N);
 
 // ---- window builder on the device (OV/lstm_eigen_opt/lstm.cc:190-213): x/target rings + flat copies,

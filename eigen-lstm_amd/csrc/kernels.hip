@@ -1240,32 +1240,28 @@ __global__ __launch_bounds__(256) void k_adagrad(float *__restrict__ P, float *_
         }
     }
 }
-void adagrad(float *P, float *dP, float *mem, size_t n, float lr, size_t u_off, int N, float4 *Ufwd, float4 *Ubwd,
-             hipStream_t st, float4 *Ubwd4, float4 *Ufwd4, const float *gpart, int n_groups, size_t group_stride, size_t by_off,
-             const float *slabs, int n_slabs, size_t slab_stride, int half_forms, void *u6b, int u6_uw,
-             unsigned short *why_b, unsigned short *whyT_b, size_t why_off, const SlideJob *slide, void *uf6b, int uf6_uw) {
-    const size_t n4 = n / 4; // the flat block is a multiple of 4 floats (M = 256, N % 16 == 0)
+void adagrad(const AdagradJob &j, hipStream_t st) {
+    const size_t n4 = j.n / 4; // the flat block is a multiple of 4 floats (M = 256, N % 16 == 0)
     int blocks = (int)((n4 + 255) / 256);
     if (blocks > 2048) blocks = 2048;
     SlideArgs sl{};
     int extra = 0;
-    if (slide != nullptr) {
-        const int nb4 = slide->N * slide->B / 4;
+    if (j.slide != nullptr) {
+        const SlideJob &s = *j.slide;
+        const int nb4 = s.N * s.B / 4;
         int copy_blocks = (nb4 + 255) / 256;
         if (copy_blocks > 128) copy_blocks = 128;
-        sl = SlideArgs{slide->text, slide->len, slide->pos, slide->Xr, slide->Tr, slide->headp, slide->xi, slide->ti, slide->H, slide->C,
-                       slide->S, slide->B, nb4, slide->stride, slide->carry_col};
+        sl = SlideArgs{s.text, s.len, s.pos, s.Xr, s.Tr, s.headp, s.xi, s.ti, s.H, s.C, s.S, s.B, nb4, s.stride, s.carry_col};
         extra = 1 + copy_blocks;
     }
-    const GradFold fold{gpart, n_groups, group_stride, by_off / 4, slabs, n_slabs, slab_stride, reinterpret_cast<uint2 *>(u6b), u6_uw, reinterpret_cast<uint2 *>(uf6b), uf6_uw, why_b, whyT_b, why_off / 4, (size_t)256 * N / 4, sl, blocks};
+    const GradFold fold{j.gpart, j.n_groups, j.group_stride, j.by_off / 4, j.slabs, j.n_slabs, j.slab_stride,
+                        reinterpret_cast<uint2 *>(j.u6b), j.u6_uw, reinterpret_cast<uint2 *>(j.uf6b), j.uf6_uw, j.why_b, j.whyT_b,
+                        j.why_off / 4, (size_t)256 * j.N / 4, sl, blocks};
     blocks += extra;
-    static const bool quad_off = getenv("LSTM_HIP_ADAGRAD_QUAD") && atoi(getenv("LSTM_HIP_ADAGRAD_QUAD")) == 0; // A/B
-    const bool quad = !quad_off && Ufwd == nullptr && Ubwd == nullptr &&
-                      ((Ufwd4 != nullptr && Ubwd4 != nullptr && (half_forms & 1) && (half_forms & 4)) || // fp32 two-half forms
-                       (Ufwd4 == nullptr && Ubwd4 == nullptr && uf6b != nullptr));                          // bf16 two-half forms
-#define ADA_GO(F, S_, Q) \
-    hipLaunchKernelGGL((k_adagrad<F, S_, Q>), dim3(blocks), dim3(256), 0, st, P, dP, mem, n4, lr, u_off / 4, N, Ufwd, Ubwd, Ubwd4, Ufwd4, fold, half_forms)
-    const bool f = gpart != nullptr, sl_ = extra != 0;
+#define ADA_GO(F, S_, Q)                                                                                                      \
+    hipLaunchKernelGGL((k_adagrad<F, S_, Q>), dim3(blocks), dim3(256), 0, st, j.P, j.dP, j.mem, n4, j.lr, j.u_off / 4, j.N, j.Ufwd, \
+                       j.Ubwd, j.Ubwd4, j.Ufwd4, fold, j.half_forms)
+    const bool f = j.gpart != nullptr, sl_ = extra != 0, quad = j.quad;
     if (f && sl_ && quad) ADA_GO(true, true, true);
     else if (f && sl_) ADA_GO(true, true, false);
     else if (f && quad) ADA_GO(true, false, true);

@@ -46,11 +46,15 @@ int fail(int code, const char *fmt, ...) {
 
 enum KernelId {
     K_PACK_U, K_FWD_STEP, K_GEMM_Y, K_SOFTMAX, K_LOSS, K_GEMM_DHY, K_BWD_STEP, K_GEMM_DWHY, K_GEMM_DU, K_DW_DB,
-    K_DBY, K_ADAGRAD, K_SLIDE, K_ALLREDUCE, K_FWD_PERSIST, K_BWD_PERSIST, K_GEN_HEAD, K_COUNT
+    K_DBY, K_ADAGRAD, K_SLIDE, K_ALLREDUCE, K_FWD_PERSIST, K_BWD_PERSIST, K_GEN_HEAD,
+    K_SIDE_SUMS, // dW_sort, the dWhy product and dW_sums on the second stream (never timed: profiling keeps them on `st`)
+    K_DU_HALVES, // the two column halves of the dU product (LSTM_HIP_DU_SPLIT; communicator loop only, never timed)
+    K_COUNT
 };
 const char *const kKernelNames[K_COUNT] = {
     "pack_U", "fwd_step", "gemm_Y", "softmax_loss_dy", "loss_reduce", "gemm_DHy", "bwd_step", "gemm_dWhy", "gemm_dU",
-    "dW_db", "loss_dby", "adagrad", "slide", "allreduce", "fwd_persistent", "bwd_persistent", "gen_head"};
+    "dW_db", "loss_dby", "adagrad", "slide", "allreduce", "fwd_persistent", "bwd_persistent", "gen_head", "side_sums",
+    "gemm_dU_halves"};
 
 // ---- RCCL, loaded on first use so single-GPU users never touch it --------------------------
 struct UniqueId {
@@ -104,17 +108,14 @@ struct lstm_hip_ctx {
     size_t dU_reduced = 0;      // ... and so are this many leading floats of the dU range (its first column half)
     bool early_reduced = false; // [dW] and [db | dWhy | dby] are already being all-reduced on st2 (ev_join marks the end)
     float *slabs_dU = nullptr; // split-K slabs of dU
-    bool bf16 = false;         // LSTM_HIP_BF16_RECURRENCE
+    EnginePlan plan;           // the form of each recurrence and everything derived from it (plan_engine)
     bool packed16 = false;
     unsigned short *Hb = nullptr, *DGb = nullptr; // bf16 hand-off copies of h and dg
-    void *Ufwd16 = nullptr, *Ubwd16 = nullptr;    // bf16 fragment images of U
-    void *Ubwd6b = nullptr;                       // ... and the scatter-form backward's (bwd_scatter16)
-    bool bwd_scatter16 = false;                   // bf16 backward recurrence in its scatter form (k_bwd_scatter_bf16)
-    void *Ufwd6b = nullptr, *Hxb = nullptr;       // two-half bf16 forward form: weights image, bf16 hand-off ring
-    bool fwd_halves16 = false;
-    bool slide_in_adagrad = true;                 // LSTM_HIP_SLIDE_IN_ADAGRAD=0 (per handle): A/B
+    void *Ufwd16 = nullptr, *Ubwd16 = nullptr;    // bf16 fragment images of U (the one-recurrence forms)
+    void *Ubwd6b = nullptr;                       // ... of the scatter-form backward (BwdForm::Bf16Scatter)
+    void *Ufwd6b = nullptr;                       // two-half bf16 forward form: weights image
+    unsigned short *Hxb = nullptr;                // ... and bf16 hand-off ring
     bool carry_slide = false, pre_slid = false;   // window loop: this Adagrad launch carries the next window's slide / it has been done
-    bool small = false;                           // one stream, hidden <= 128: both recurrences on one CU (k_small_fwd / k_small_bwd)
     bool dgt_written = false;                     // the backward recurrence wrote the transposed bf16 image of dg itself
     bool packed6b = false;                        // Ubwd6b is current (written by the Adagrad launch)
     bool packedf6b = false;                       // ... and Ufwd6b
@@ -124,25 +125,15 @@ struct lstm_hip_ctx {
     int Tpad = 0, SBpad = 0;
     bool why_packed = false;
     float *gpart = nullptr;    // per-column-group partial [dW|dU|db|dWhy] blocks of the fused backward recurrence
-    int bwd_cols = 16;         // batch columns per backward-recurrence workgroup (8 or 16)
 
     float *P = nullptr, *dP = nullptr, *mem = nullptr;
-    float4 *Ufwd = nullptr, *Ubwd = nullptr;
-    float4 *Ubwd4 = nullptr; // weight image of the 4x4x1 backward form (kernels.hip, k_pack_U), when bwd_uses_m4
-    float4 *Ufwd4 = nullptr; // ... of the 8-column forward kernel (fwd_uses_8col_form) or, fwd_cols4, of the two-half one
-    int n_cus = 0;           // compute units of the device (grid choices)
-    bool side_stream = true; // LSTM_HIP_NO_SIDE_STREAM=1 (per handle): keep the whole window on one stream
-    int probe_overlap = 0;   // LSTM_HIP_PROBE_OVERLAP=k (per handle, timing probe): k Y-sized products on st2 beside the forward recurrence
-    int bwd_halves = 0;      // != 0: backward recurrence likewise, scatter form (k_bwd_scatter); bits above bit 0: its cfg word
-    int half_forms() const { return fwd_cols4 | (bwd_halves ? 4 : 0); } // which U images are live (kernels.h)
-    int fwd_cols4 = 0;       // 1: forward recurrence as two alternating 4-column halves per workgroup (k_fwd_persistent6)
-    float *Hx = nullptr;     // 8-column forward form: ring of hand-off slots (data-as-flag), sentinel-filled
+    float4 *Ufwd = nullptr, *Ubwd = nullptr; // 16x16x4 tile images of U (fp32)
+    float4 *Ubwd4 = nullptr; // weight image of the 4x4x1 backward forms (kernels.hip, k_pack_U): BwdForm::Cols8 / Scatter
+    float4 *Ufwd4 = nullptr; // ... of the 8-column forward forms: FwdForm::Cols8 / TwoHalf
+    float *Hx = nullptr;     // 8-column forward forms: ring of hand-off slots (data-as-flag), sentinel-filled
     int ring_base = 0;       // slot of step 0 in the next launch
-    float *DGx = nullptr;    // backward recurrence: the same kind of ring for dg
+    float *DGx = nullptr;    // backward scatter forms: the same kind of ring for the partial sums
     int ring_base_b = 0;
-    int gpart_cols = 8;      // columns per fused partial gradient block (4 where the scatter form runs one half per workgroup)
-    size_t DGx_floats = 0;   // size of the backward hand-off ring
-    int poll_cfg = 0;        // LSTM_HIP_FWD_POLL: bits 0-7 s_sleep between polls, 8-15 first delay of the non-gating waves
     bool packed = false;
     float *H = nullptr, *C = nullptr, *G = nullptr, *DG = nullptr, *Y = nullptr, *Pr = nullptr, *DHy = nullptr;
     float *dcnext = nullptr, *colloss = nullptr, *dby_part = nullptr, *slabs = nullptr;
@@ -167,7 +158,6 @@ struct lstm_hip_ctx {
     int stride = 1, carry_col = 1; // window advance per iteration and the column that becomes the carry
     bool fwd_done = false;
     bool dby_done = false;       // dby already produced by the loss launch of this window
-    bool persistent = false;     // default engine; false = one launch per timestep
     unsigned *cnt = nullptr;     // [2][persistent_counter_bytes]: fwd region, bwd region
     unsigned *abortp = nullptr;  // set by a timed-out spin inside a persistent kernel
     size_t cnt_bytes = 0;
@@ -219,15 +209,15 @@ template <class F> int timed(lstm_hip_ctx *h, int id, F &&launch) {
         if (rc_) return rc_;                                       \
     } while (0)
 
-template <class T> int dalloc(T **p, size_t count) {
+template <class T> int dalloc(T **p, size_t count, int fill_byte = 0) {
     HIP_TRY(hipMalloc((void **)p, count * sizeof(T)));
-    HIP_TRY(hipMemset(*p, 0, count * sizeof(T)));
+    HIP_TRY(hipMemset(*p, fill_byte, count * sizeof(T)));
     return 0;
 }
-#define ALLOC(p, n)                  \
-    do {                             \
-        int rc_ = dalloc(&(p), (n)); \
-        if (rc_) return rc_;         \
+#define ALLOC(p, ...)                         \
+    do {                                      \
+        int rc_ = dalloc(&(p), __VA_ARGS__); \
+        if (rc_) return rc_;                  \
     } while (0)
 
 int check(lstm_hip_ctx *h) {
@@ -243,7 +233,8 @@ int check(lstm_hip_ctx *h) {
 
 // after a synchronisation point: did a persistent kernel give up on a hand-off?
 int check_abort(lstm_hip_ctx *h) {
-    if (!h->persistent) return 0;
+    const EnginePlan &p = h->plan;
+    if (!p.persistent()) return 0;
     unsigned flag = 0;
     HIP_TRY(hipMemcpyAsync(&flag, h->abortp, sizeof(unsigned), hipMemcpyDeviceToHost, h->st));
     HIP_TRY(hipStreamSynchronize(h->st));
@@ -251,18 +242,15 @@ int check_abort(lstm_hip_ctx *h) {
         HIP_TRY(hipMemsetAsync(h->abortp, 0, sizeof(unsigned), h->st));
         HIP_TRY(hipMemsetAsync(h->cnt, 0, 2 * h->cnt_bytes, h->st)); // counters are inconsistent after an abort
         h->fwd_epoch = h->bwd_epoch = 0;
-        if (h->Hx) { // and so are the hand-off rings
-            HIP_TRY(hipMemsetAsync(h->Hx, 0xff, sizeof(float) * fwd_ring_floats(h->cfg.N, h->cfg.B), h->st));
-            h->ring_base = 0;
-        }
-        if (h->Hxb) {
-            HIP_TRY(hipMemsetAsync(h->Hxb, 0xff, sizeof(unsigned short) * fwd_halves_bf16_ring_halfwords(h->cfg.N, h->cfg.B), h->st));
-            h->ring_base = 0;
-        }
-        if (h->DGx) {
-            HIP_TRY(hipMemsetAsync(h->DGx, 0xff, sizeof(float) * h->DGx_floats, h->st));
-            h->ring_base_b = 0;
-        }
+        // and so are the hand-off rings
+        if (p.fwd == FwdForm::Cols8 || p.fwd == FwdForm::TwoHalf)
+            HIP_TRY(hipMemsetAsync(h->Hx, 0xff, sizeof(float) * p.hx_floats, h->st));
+        if (p.fwd == FwdForm::Bf16Halves)
+            HIP_TRY(hipMemsetAsync(h->Hxb, 0xff, sizeof(unsigned short) * p.hxb_halfwords, h->st));
+        h->ring_base = 0;
+        if (p.bwd == BwdForm::Scatter || p.bwd == BwdForm::Bf16Scatter)
+            HIP_TRY(hipMemsetAsync(h->DGx, 0xff, sizeof(float) * p.dgx_floats, h->st));
+        h->ring_base_b = 0;
         return fail(LSTM_HIP_ESTATE, "a persistent recurrence kernel timed out waiting for a hand-off (results invalid)");
     }
     return 0;
@@ -278,99 +266,75 @@ const float *loss_src(const lstm_hip_ctx *h) {
 int loss_steps(const lstm_hip_ctx *h) { return loss_last_step(h) ? 1 : h->cfg.S - 1; }
 float loss_scale(const lstm_hip_ctx *h) { return h->loss_mode == LSTM_HIP_LOSS_LAST_STEP_NATS ? 0.693147180559945f : 1.0f; }
 
-int launch_fwd_recurrence(lstm_hip_ctx *h) {
-    const int N = h->cfg.N, B = h->cfg.B, S = h->cfg.S;
-    const bool fast = (h->cfg.flags & LSTM_HIP_FAST_MATH) != 0;
-    if (h->fwd_epoch >= (1u << 26)) { // keep epoch * arrivals inside 32 bits
-        HIP_TRY(hipMemsetAsync(h->cnt, 0, h->cnt_bytes, h->st));
-        h->fwd_epoch = 0;
-    }
-    h->fwd_epoch++;
-    if (h->small) {
-        RUN(K_FWD_PERSIST, small_fwd(h->P + h->pl.U, h->P + h->pl.W, h->P + h->pl.b, h->H, h->C, h->G, h->xi, N, S, fast, h->st));
-        return 0;
-    }
-    if (h->bf16) {
-        if (!h->packed16) {
-            // (the one-recurrence forms' images only where one of them runs)
-            RUN(K_PACK_U, (h->fwd_halves16 && h->bwd_scatter16 ? (void)0 : pack_U_bf16(h->P + h->pl.U, h->Ufwd16, h->Ubwd16, N, h->st),
-                           h->bwd_scatter16 && !h->packed6b ? pack_U6_bf16(h->P + h->pl.U, h->Ubwd6b, N, h->st) : (void)0,
-                           h->fwd_halves16 && !h->packedf6b ? pack_Ufwd6_bf16(h->P + h->pl.U, h->Ufwd6b, N, h->st) : (void)0));
-            h->packed16 = true;
-        }
-        if (h->fwd_halves16) { // as many 8-column groups per launch as are co-resident; the streams are independent
-            const int lc = fwd_halves_bf16_launch_cols(N, B, h->n_cus);
-            for (int c0 = 0; c0 < B; c0 += lc) {
-                if (c0 > 0) h->fwd_epoch++;
-                RUN(K_FWD_PERSIST, fwd_halves_bf16(h->Ufwd6b, h->P + h->pl.W, h->P + h->pl.b, h->H, h->Hb, h->C, h->G, h->xi, h->Hxb,
-                                                   h->cnt, h->abortp, h->fwd_epoch, h->ring_base, N, S, B, c0, B - c0 < lc ? B - c0 : lc,
-                                                   fast, h->n_cus, h->st, h->stamps));
-            }
-            h->ring_base = fwd_ring_advance(h->ring_base, S); // (every column range has made the same S - 1 hand-offs on its part of the ring)
-            return 0;
-        }
-        RUN(K_FWD_PERSIST, fwd_persistent_bf16(h->Ufwd16, h->P + h->pl.W, h->P + h->pl.b, h->H, h->Hb, h->C, h->G, h->xi,
-                                               h->cnt, h->abortp, h->fwd_epoch, N, S, B, fast, h->st, h->n_cus));
-    } else if (h->Hx && h->fwd_cols4) { // as many 8-column groups per launch as are co-resident (one launch unless the batch is wide)
-        const int lc = two_half_launch_cols(N, h->n_cus);
-        for (int c0 = 0; c0 < B; c0 += lc) {
-            if (c0 > 0) h->fwd_epoch++;
-            RUN(K_FWD_PERSIST, fwd_persistent6(h->Ufwd4, h->P + h->pl.W, h->P + h->pl.b, h->H, h->C, h->G, h->xi, h->Hx, h->cnt,
-                                               h->abortp, h->fwd_epoch, h->ring_base, N, S, B, fast, h->poll_cfg, h->st, h->stamps, c0,
-                                               B - c0 < lc ? B - c0 : lc));
-        }
-        h->ring_base = fwd_ring_advance(h->ring_base, S); // (every column has made the same S - 1 hand-offs on its part of the ring)
-    } else if (h->Hx) {
-        RUN(K_FWD_PERSIST, fwd_persistent4(h->Ufwd4, h->P + h->pl.W, h->P + h->pl.b, h->H, h->C, h->G, h->xi, h->Hx, h->cnt,
-                                           h->abortp, h->fwd_epoch, h->ring_base, N, S, B, fast, h->poll_cfg, h->st, h->stamps));
-        h->ring_base = fwd_ring_advance(h->ring_base, S);
-    } else {
-        RUN(K_FWD_PERSIST, fwd_persistent(h->Ufwd, h->P + h->pl.W, h->P + h->pl.b, h->H, h->C, h->G, h->xi, h->cnt, h->abortp,
-                                          h->fwd_epoch, N, S, B, fast, h->st));
-    }
-    return 0;
-}
-
 int do_forward(lstm_hip_ctx *h) {
+    const EnginePlan &p = h->plan;
     const int N = h->cfg.N, B = h->cfg.B, S = h->cfg.S, G4 = 4 * N;
     const bool fast = (h->cfg.flags & LSTM_HIP_FAST_MATH) != 0;
-    if (!h->packed && !h->bf16) { // (the bf16 path packs its own images, launch_fwd_recurrence)
-        RUN(K_PACK_U, pack_U(h->P + h->pl.U, h->Ufwd4 ? nullptr : h->Ufwd, h->Ubwd4 ? nullptr : h->Ubwd, N, h->st, h->Ubwd4,
-                             h->Ufwd4, h->half_forms())); // one image per direction is live
+    float *W = h->P + h->pl.W, *bias = h->P + h->pl.b;
+    if (!h->packed && !p.bf16()) { // (the bf16 path packs its own images below)
+        RUN(K_PACK_U, pack_U(h->P + h->pl.U, p.ufwd4() ? nullptr : h->Ufwd, p.ubwd4() ? nullptr : h->Ubwd, N, h->st, h->Ubwd4,
+                             h->Ufwd4, p.half_forms())); // one image per direction is live
         h->packed = true;
     }
     h->n_dby_parts = softmax_parts(h->T);
-    // Timing probe (LSTM_HIP_PROBE_OVERLAP=1, tools/ab_kernels.py; results unaffected): the Y product of the PREVIOUS window's
-    // H is launched on st2 beside the forward recurrence, into the Pr buffer (overwritten by the softmax later), to measure
-    // what a time-batched product costs the recurrence when both share the chip ("overlap").
-    const int probe_overlap = h->probe_overlap;
-    if (probe_overlap && h->persistent && !h->bf16 && !h->profiling) {
-        HIP_TRY(hipEventRecord(h->ev_fork, h->st));
-        HIP_TRY(hipStreamWaitEvent(h->st2, h->ev_fork, 0));
+    if (p.persistent()) {
+        if (h->fwd_epoch >= (1u << 26)) { // keep epoch * arrivals inside 32 bits
+            HIP_TRY(hipMemsetAsync(h->cnt, 0, h->cnt_bytes, h->st));
+            h->fwd_epoch = 0;
+        }
+        h->fwd_epoch++;
     }
-    if (h->persistent) {
-        int rc = launch_fwd_recurrence(h);
-        if (rc) return rc;
-        if (probe_overlap && !h->bf16 && !h->profiling) {
-            for (int rep = 0; rep < (probe_overlap & 15); rep++) {
-                if (probe_overlap & 16) // 64 x 64 tiles: can share a compute unit with a workgroup of the recurrence
-                    gemm_probe_small_kfast(256, h->T, N, h->P + h->pl.Why, 256, h->H + (size_t)N * B, N, h->Pr + (size_t)256 * B, 256, h->st2);
-                else // the library's 128 x 64 tiles (128 KB of LDS): starts only where a recurrence workgroup has left
-                    gemm(false, false, 256, h->T, N, h->P + h->pl.Why, 256, h->H + (size_t)N * B, N, h->Pr + (size_t)256 * B, 256, 1,
-                         nullptr, h->st2);
-            }
-            HIP_TRY(hipEventRecord(h->ev_join, h->st2));
-            HIP_TRY(hipStreamWaitEvent(h->st, h->ev_join, 0));
-        }
-    } else {
+    if (p.bf16() && !h->packed16) { // (the one-recurrence forms' images only where one of them runs)
+        RUN(K_PACK_U, (p.u16 ? pack_U_bf16(h->P + h->pl.U, h->Ufwd16, h->Ubwd16, N, h->st) : (void)0,
+                       p.bwd == BwdForm::Bf16Scatter && !h->packed6b ? pack_U6_bf16(h->P + h->pl.U, h->Ubwd6b, N, h->st) : (void)0,
+                       p.fwd == FwdForm::Bf16Halves && !h->packedf6b ? pack_Ufwd6_bf16(h->P + h->pl.U, h->Ufwd6b, N, h->st) : (void)0));
+        h->packed16 = true;
+    }
+    switch (p.fwd) {
+    case FwdForm::Step:
         for (int t = 1; t < S; t++) {
-            RUN(K_FWD_STEP, fwd_step(h->Ufwd, h->P + h->pl.W, h->P + h->pl.b, h->H + (size_t)(t - 1) * N * B,
-                                     h->C + (size_t)(t - 1) * N * B, h->H + (size_t)t * N * B, h->C + (size_t)t * N * B,
-                                     h->G + (size_t)t * G4 * B, h->xi + (size_t)t * B, N, B, fast, h->st));
+            RUN(K_FWD_STEP, fwd_step(h->Ufwd, W, bias, h->H + (size_t)(t - 1) * N * B, h->C + (size_t)(t - 1) * N * B,
+                                     h->H + (size_t)t * N * B, h->C + (size_t)t * N * B, h->G + (size_t)t * G4 * B,
+                                     h->xi + (size_t)t * B, N, B, fast, h->st));
         }
+        break;
+    case FwdForm::Small:
+        RUN(K_FWD_PERSIST, small_fwd(h->P + h->pl.U, W, bias, h->H, h->C, h->G, h->xi, N, S, fast, h->st));
+        break;
+    case FwdForm::Persistent:
+        RUN(K_FWD_PERSIST, fwd_persistent(h->Ufwd, W, bias, h->H, h->C, h->G, h->xi, h->cnt, h->abortp, h->fwd_epoch, N, S, B, fast,
+                                          h->st));
+        break;
+    case FwdForm::Cols8:
+        RUN(K_FWD_PERSIST, fwd_persistent4(h->Ufwd4, W, bias, h->H, h->C, h->G, h->xi, h->Hx, h->cnt, h->abortp, h->fwd_epoch,
+                                           h->ring_base, N, S, B, fast, p.poll_cfg, h->st, h->stamps));
+        h->ring_base = fwd_ring_advance(h->ring_base, S);
+        break;
+    case FwdForm::TwoHalf: // as many groups per launch as are co-resident (one launch unless the batch is wide)
+        for (int c0 = 0; c0 < B; c0 += p.launch_cols) {
+            if (c0 > 0) h->fwd_epoch++;
+            RUN(K_FWD_PERSIST, fwd_persistent6(h->Ufwd4, W, bias, h->H, h->C, h->G, h->xi, h->Hx, h->cnt, h->abortp, h->fwd_epoch,
+                                               h->ring_base, N, S, B, fast, p.poll_cfg, c0, std::min(B - c0, p.launch_cols),
+                                               p.group_cols, p.fwd_pin, h->st, h->stamps));
+        }
+        h->ring_base = fwd_ring_advance(h->ring_base, S); // (every column has made the same S - 1 hand-offs on its part of the ring)
+        break;
+    case FwdForm::Bf16:
+        RUN(K_FWD_PERSIST, fwd_persistent_bf16(h->Ufwd16, W, bias, h->H, h->Hb, h->C, h->G, h->xi, h->cnt, h->abortp, h->fwd_epoch,
+                                               N, S, B, fast, p.fwd_cols, h->st));
+        break;
+    case FwdForm::Bf16Halves: // likewise; the streams are independent
+        for (int c0 = 0; c0 < B; c0 += p.launch_cols) {
+            if (c0 > 0) h->fwd_epoch++;
+            RUN(K_FWD_PERSIST, fwd_halves_bf16(h->Ufwd6b, W, bias, h->H, h->Hb, h->C, h->G, h->xi, h->Hxb, h->cnt, h->abortp,
+                                               h->fwd_epoch, h->ring_base, N, S, B, c0, std::min(B - c0, p.launch_cols),
+                                               p.group_cols, p.fwd_pin, fast, h->st, h->stamps));
+        }
+        h->ring_base = fwd_ring_advance(h->ring_base, S);
+        break;
     }
     // Y = Why * H[1..S-1]   (R/lstm.cc:195 for every step at once)
-    if (h->bf16) { // bf16 operands (Why rounded once per update, the recurrence's own bf16 copy of h), fp32 accumulate
+    if (p.bf16()) { // bf16 operands (Why rounded once per update, the recurrence's own bf16 copy of h), fp32 accumulate
         if (!h->why_packed) {
             RUN(K_PACK_U, (transpose_pack_bf16(h->P + h->pl.Why, N, 256, 256, h->WhyT_b, N, h->st),
                            pack_bf16(h->P + h->pl.Why, (size_t)256 * N, h->Why_b, h->st)));
@@ -388,6 +352,7 @@ int do_forward(lstm_hip_ctx *h) {
 }
 
 int do_backward(lstm_hip_ctx *h) {
+    const EnginePlan &p = h->plan;
     const int N = h->cfg.N, B = h->cfg.B, S = h->cfg.S, G4 = 4 * N, T = h->T;
     if (!h->fwd_done) return fail(LSTM_HIP_ESTATE, "backward called before forward");
     float *dY = h->Y + (size_t)256 * B;
@@ -397,82 +362,80 @@ int do_backward(lstm_hip_ctx *h) {
                                h->dP + h->pl.by, h->st, loss_scale(h)));
     h->dby_done = false;
     // fused mode: the backward recurrence produces DHy = Why^T * dY (R/lstm.cc:228) itself and accumulates dW, db, dWhy
-    const bool fused = h->persistent && h->gpart != nullptr && h->bwd_cols == 8;
-    if (h->bf16) { // DHy = Why^T * dY on bf16 operands: both already have the contraction index m contiguous
+    const bool fused = p.fused;
+    if (p.bf16()) { // DHy = Why^T * dY on bf16 operands: both already have the contraction index m contiguous
         RUN(K_GEMM_DHY, (pack_bf16(dY, (size_t)T * 256, h->dYb, h->st),
                          gemm_bf16(N, T, 256, h->Why_b, 256, h->dYb, 256, h->DHy + (size_t)N * B, N, 1, nullptr, h->st)));
-    } else if (!fused && !h->bwd_halves && !h->small) // (the two-half and the single-CU backward forms compute Why^T dy themselves)
+    } else if (!fused && p.bwd != BwdForm::Scatter && p.bwd != BwdForm::Small) // (those compute Why^T dy themselves)
         RUN(K_GEMM_DHY, gemm(true, false, N, T, 256, h->P + h->pl.Why, 256, dY, 256, h->DHy + (size_t)N * B, N, 1, nullptr,
                              h->st));
     // Unfused two-half form, single GPU: the sums that do not feed the recurrence run on st2 beside it -- the column sort of
     // the dW pass and dWhy = dY H^T while the recurrence runs (one workgroup per CU leaves room), the dW / db sums beside
     // the dU product.  (Profiling runs keep everything on `st`, one timed launch after the other.)
-    const bool side = h->bwd_halves && !fused && h->side_stream && !h->comm && !h->profiling;
-    // (Not for the bf16 scatter form, although its pinned launch leaves most of the chip idle -- configs[4]: 64 of 256 CUs.
-    // Measured, kernel trace: of the side stream's launches only the one-workgroup column sort ran beside the recurrence; the
-    // next one started and then sat until the recurrence ended, because its workgroups are dealt to the XCDs in turn and the
-    // two XCDs the recurrence fills have no room for the ones they are dealt.  Window 0.6993 -> 0.6955 ms: dropped.  The
-    // sort alone, queued beside the FORWARD recurrence: 0.7094 against 0.7094.)
+    const bool side = p.side_stream && !h->comm && !h->profiling;
     if (side) {
         HIP_TRY(hipEventRecord(h->ev_fork, h->st));
         HIP_TRY(hipStreamWaitEvent(h->st2, h->ev_fork, 0));
         dW_sort(h->xi + B, T, G4, h->dw_scratch, h->st2);
         gemm(false, true, 256, N, T, dY, 256, h->H + (size_t)N * B, N, h->dP + h->pl.Why, 256, h->splits_dWhy, h->slabs, h->st2);
+        if (int rc = launch_status(K_SIDE_SUMS)) return rc;
     }
     unsigned *cb = h->cnt + h->cnt_bytes / sizeof(unsigned);
-    if (h->persistent) {
+    unsigned long long *stamps_b = h->stamps ? h->stamps + (size_t)2 * S * 16 : nullptr;
+    float *gpart = fused ? h->gpart : nullptr;
+    if (p.persistent()) {
         if (h->bwd_epoch >= (1u << 26)) {
             HIP_TRY(hipMemsetAsync(cb, 0, h->cnt_bytes, h->st));
             h->bwd_epoch = 0;
         }
         h->bwd_epoch++;
-        h->dgt_written = false;
-        if (h->small) {
-            RUN(K_BWD_PERSIST, small_bwd(h->Ubwd, h->P + h->pl.Why, dY, h->G, h->C, h->DG, N, S, h->st));
-        } else if (h->bf16 && h->bwd_scatter16) {
-            const int lc = bwd_scatter_bf16_launch_cols(N, B, h->n_cus); // one launch per co-resident range of columns
-            static const bool no_direct = getenv("LSTM_HIP_NO_DIRECT_DGT") && atoi(getenv("LSTM_HIP_NO_DIRECT_DGT")); // A/B
-            // The recurrence writes the k-contiguous bf16 image of dg for the dU product itself (2-byte stores, off the chain)
-            // where that is cheaper than the transposing pass behind it: measured at N=1024 with 16 streams 0.5776 -> 0.5701 ms
-            // (recurrence +4 us, dU launch -9); with 64 streams the scattered stores cost the recurrence what the pass costs
-            // (N=512: +19 / -18 us) and with 128 more (+76 / -71 us per window), so only for the narrow batches.
-            const bool direct_dgt = !no_direct && N == 1024 && B <= 32;
-            h->dgt_written = direct_dgt;
-            for (int c0 = 0; c0 < B; c0 += lc) {
-                if (c0 > 0) h->bwd_epoch++;
-                RUN(K_BWD_PERSIST, bwd_scatter_bf16(h->Ubwd6b, h->DG, h->DHy, h->G, h->C, h->DGx, cb, h->abortp, h->bwd_epoch,
-                                                    h->ring_base_b, N, S, B, c0, B - c0 < lc ? B - c0 : lc, h->n_cus, h->st,
-                                                    h->stamps ? h->stamps + (size_t)2 * S * 16 : nullptr, direct_dgt ? h->DGt_b : nullptr, h->Tpad));
-            }
-            h->ring_base_b = bwd_scatter_bf16_ring_advance(h->ring_base_b, S); // (every group's region has had its S - 2 publications)
-        } else if (h->bf16) {
-            RUN(K_BWD_PERSIST, bwd_persistent(reinterpret_cast<const float4 *>(h->Ubwd16), h->DG, h->DHy, h->G, h->C, h->H,
-                                              h->xi, fused ? h->gpart : nullptr, h->P + h->pl.Why, dY, cb, h->abortp,
-                                              h->bwd_epoch, N, S, B, h->bwd_cols, h->st, nullptr, h->DGb));
-        } else if (h->bwd_halves) {
-            const int lc = two_half_launch_cols(N, h->n_cus); // one launch per co-resident range of columns; every group of the
-            for (int c0 = 0; c0 < B; c0 += lc) {               // batch has its own ring region and partial gradient block
-                if (c0 > 0) h->bwd_epoch++;
-                RUN(K_BWD_PERSIST, bwd_scatter(h->Ubwd4, h->DG, h->P + h->pl.Why, dY, h->G, h->C, h->H, h->xi, fused ? h->gpart : nullptr,
-                                               h->DGx, cb, h->abortp, h->bwd_epoch, h->ring_base_b, N, S, B, h->bwd_halves >> 1, h->st,
-                                               h->stamps ? h->stamps + (size_t)2 * S * 16 : nullptr, c0, B - c0 < lc ? B - c0 : lc));
-            }
-            h->ring_base_b = bwds_ring_advance(h->ring_base_b, S);
-        } else {
-            RUN(K_BWD_PERSIST, bwd_persistent(h->Ubwd4 ? h->Ubwd4 : h->Ubwd, h->DG, h->DHy, h->G, h->C, h->H, h->xi,
-                                              fused ? h->gpart : nullptr, h->P + h->pl.Why, dY, cb, h->abortp, h->bwd_epoch, N, S,
-                                              B, h->bwd_cols, h->st, h->stamps ? h->stamps + (size_t)2 * S * 16 : nullptr, nullptr));
-        }
-    } else {
+    }
+    h->dgt_written = false;
+    switch (p.bwd) {
+    case BwdForm::Step:
         HIP_TRY(hipMemsetAsync(h->dcnext, 0, sizeof(float) * N * B, h->st)); // R/lstm.cc:216-217
         for (int t = S - 1; t >= 1; t--) {
             RUN(K_BWD_STEP, bwd_step(h->Ubwd, t < S - 1 ? h->DG + (size_t)(t + 1) * G4 * B : nullptr,
                                      h->DHy + (size_t)t * N * B, h->G + (size_t)t * G4 * B, h->C + (size_t)t * N * B,
                                      h->C + (size_t)(t - 1) * N * B, h->dcnext, h->DG + (size_t)t * G4 * B, N, B, h->st));
         }
+        break;
+    case BwdForm::Small:
+        RUN(K_BWD_PERSIST, small_bwd(h->Ubwd, h->P + h->pl.Why, dY, h->G, h->C, h->DG, N, S, h->st));
+        break;
+    case BwdForm::Persistent:
+    case BwdForm::Cols8:
+        RUN(K_BWD_PERSIST, bwd_persistent(p.bwd == BwdForm::Cols8 ? h->Ubwd4 : h->Ubwd, h->DG, h->DHy, h->G, h->C, h->H, h->xi, gpart,
+                                          h->P + h->pl.Why, dY, cb, h->abortp, h->bwd_epoch, N, S, B, p.bwd_cols, p.bwd_spread, h->st,
+                                          stamps_b, nullptr));
+        break;
+    case BwdForm::Scatter: // one launch per co-resident range of columns; every group of the batch has its own ring region
+        for (int c0 = 0; c0 < B; c0 += p.launch_cols) { // and partial gradient block
+            if (c0 > 0) h->bwd_epoch++;
+            RUN(K_BWD_PERSIST, bwd_scatter(h->Ubwd4, h->DG, h->P + h->pl.Why, dY, h->G, h->C, h->H, h->xi, gpart, h->DGx, cb, h->abortp,
+                                           h->bwd_epoch, h->ring_base_b, N, S, B, p.bwd_cfg, c0, std::min(B - c0, p.launch_cols),
+                                           p.group_cols, p.bwd_pin, h->st, stamps_b));
+        }
+        h->ring_base_b = bwds_ring_advance(h->ring_base_b, S);
+        break;
+    case BwdForm::Bf16:
+        RUN(K_BWD_PERSIST, bwd_persistent(reinterpret_cast<const float4 *>(h->Ubwd16), h->DG, h->DHy, h->G, h->C, h->H, h->xi, nullptr,
+                                          h->P + h->pl.Why, dY, cb, h->abortp, h->bwd_epoch, N, S, B, p.bwd_cols, p.bwd_spread, h->st,
+                                          nullptr, h->DGb));
+        break;
+    case BwdForm::Bf16Scatter: // one launch per co-resident range of columns
+        h->dgt_written = p.direct_dgt;
+        for (int c0 = 0; c0 < B; c0 += p.launch_cols) {
+            if (c0 > 0) h->bwd_epoch++;
+            RUN(K_BWD_PERSIST, bwd_scatter_bf16(h->Ubwd6b, h->DG, h->DHy, h->G, h->C, h->DGx, cb, h->abortp, h->bwd_epoch,
+                                                h->ring_base_b, N, S, B, c0, std::min(B - c0, p.launch_cols), p.group_cols,
+                                                p.bwd_pin, h->st, stamps_b, p.direct_dgt ? h->DGt_b : nullptr, h->Tpad));
+        }
+        h->ring_base_b = bwd_scatter_bf16_ring_advance(h->ring_base_b, S); // (every group's region has had its S - 2 publications)
+        break;
     }
     // dWhy = dY * H[1..]^T             R/lstm.cc:226
-    if (h->bf16) {
+    if (p.bf16()) {
         // the contraction runs over the window's columns: k-contiguous bf16 images of dy, h and dg first (zero-padded to
         // Tpad); dy_t pairs with h_t, i.e. column (t-1)*B+b of dY with column t*B+b of H: the h image shifted by B columns
         RUN(K_GEMM_DWHY, (transpose_pack_bf16(dY, T, 256, 256, h->dYt_b, h->Tpad, h->st),
@@ -489,7 +452,7 @@ int do_backward(lstm_hip_ctx *h) {
     if (defer_fold) {
         h->fold_pending = true;
     } else if (fused) { // accumulated per column group inside the recurrence: fold the groups in order
-        const int NGb = (B + h->gpart_cols - 1) / h->gpart_cols;
+        const int NGb = (B + p.gpart_cols - 1) / p.gpart_cols;
         const size_t psz = bwd_partial_floats(N);
         // b and Why are adjacent both in the flat block and in the partial blocks: one fold covers both.  With the early
         // all-reduce below the folds go to st2 with it, so the dU product on `st` does not wait for them.
@@ -507,6 +470,7 @@ int do_backward(lstm_hip_ctx *h) {
         HIP_TRY(hipEventRecord(h->ev_mid, h->st)); // DG is complete
         HIP_TRY(hipStreamWaitEvent(h->st2, h->ev_mid, 0));
         dW_sums(h->DG + (size_t)G4 * B, T, G4, h->dP + h->pl.W, h->dP + h->pl.b, h->dw_scratch, h->st2);
+        if (int rc = launch_status(K_SIDE_SUMS)) return rc;
         HIP_TRY(hipEventRecord(h->ev_join, h->st2));
     } else {
         RUN(K_DW_DB, dW_db(h->DG + (size_t)G4 * B, h->xi + B, T, G4, h->dP + h->pl.W, h->dP + h->pl.b, h->dw_scratch, h->st));
@@ -534,17 +498,18 @@ int do_backward(lstm_hip_ctx *h) {
         // behind the early ranges and beside the second half's product; only the second half is left for `st`.  Off by
         // default: two half-size products cost more than the whole one, about what hiding half of the dU all-reduce can
         // win back (measured with a 1-rank communicator, tools/comm_overhead_probe.py); to be decided on a multi-GPU node.
-        // The switch is read once per process and the path depends on nothing else, so every rank of a job (same
+        // The switch is read at create (plan_engine) and the path depends on nothing else, so every rank of a job (same
         // environment) posts the same sequence of collectives.
         h->dU_reduced = 0;
-        static const bool du_split = getenv("LSTM_HIP_DU_SPLIT") && atoi(getenv("LSTM_HIP_DU_SPLIT")) != 0;
-        if (!h->bf16 && du_split) {
+        if (p.du_split) {
             int n1 = (N / 2) / 64 * 64; // whole 64-column tiles in the first half
             if (n1 == 0) n1 = N / 2;
             gemm(false, true, G4, n1, T, h->DG + (size_t)G4 * B, G4, h->H, N, h->dP + h->pl.U, G4, h->splits_dU, h->slabs_dU, h->st);
+            if (int rc_ = launch_status(K_DU_HALVES)) return rc_;
             HIP_TRY(hipEventRecord(h->ev_mid, h->st));
             gemm(false, true, G4, N - n1, T, h->DG + (size_t)G4 * B, G4, h->H + n1, N, h->dP + h->pl.U + (size_t)G4 * n1, G4,
                  h->splits_dU, h->slabs_dU, h->st);
+            if (int rc_ = launch_status(K_DU_HALVES)) return rc_;
             HIP_TRY(hipStreamWaitEvent(h->st2, h->ev_mid, 0));
             h->dU_reduced = (size_t)G4 * n1;
             rc = g_rccl.AllReduce(h->dP + h->pl.U, h->dP + h->pl.U, h->dU_reduced, 7, 0, h->comm, h->st2);
@@ -557,7 +522,7 @@ int do_backward(lstm_hip_ctx *h) {
         if (h->dU_reduced) return 0; // the product is done
     }
     // dU = DG * H[0..S-2]^T            R/lstm.cc:250
-    if (h->bf16) { // dg_t pairs with h_{t-1}: column (t-1)*B+b of both images
+    if (p.bf16()) { // dg_t pairs with h_{t-1}: column (t-1)*B+b of both images
         h->n_slabs_dU = 0;
         RUN(K_GEMM_DU, (h->dgt_written ? (void)0 : transpose_pack_bf16(h->DG + (size_t)G4 * B, T, G4, G4, h->DGt_b, h->Tpad, h->st),
                         gemm_bf16(G4, N, h->Tpad, h->DGt_b, h->Tpad, h->Ht_b, h->SBpad, h->dP + h->pl.U, G4, h->splits_dU,
@@ -596,41 +561,44 @@ int do_allreduce(lstm_hip_ctx *h) {
 }
 
 int do_adagrad(lstm_hip_ctx *h, double lr) {
-    const SlideJob job{h->text, h->text_len, h->pos, h->Xr, h->Tr, h->head, h->xi, h->ti, h->H, h->C,
-                       h->cfg.S, h->cfg.B, h->cfg.N, h->stride, h->carry_col};
-    const SlideJob *sj = h->carry_slide ? &job : nullptr;
-    if (h->fold_pending) {
-        h->fold_pending = false;
-        const int NGb = (h->cfg.B + h->gpart_cols - 1) / h->gpart_cols;
-        RUN(K_ADAGRAD, adagrad(h->P, h->dP, h->mem, h->pl.total, (float)lr, h->pl.U, h->cfg.N, h->Ufwd4 ? nullptr : h->Ufwd,
-                               h->Ubwd4 ? nullptr : h->Ubwd, h->st, h->Ubwd4, h->Ufwd4, h->gpart, NGb, bwd_partial_floats(h->cfg.N),
-                               h->pl.by, h->n_slabs_dU > 0 ? h->slabs_dU : nullptr, h->n_slabs_dU,
-                               (size_t)4 * h->cfg.N * h->cfg.N, h->half_forms(), nullptr, 0, nullptr, nullptr, 0, sj));
-    } else if (h->bf16) // the fp32 fragment images are not used by the bf16 path (its own are repacked by pack_U_bf16)
-    {   // ... except the scatter-form backward image, whose 8-byte elements are the four rows an Adagrad thread holds
-        RUN(K_ADAGRAD, adagrad(h->P, h->dP, h->mem, h->pl.total, (float)lr, h->pl.U, h->cfg.N, nullptr, nullptr, h->st, nullptr, nullptr,
-                               nullptr, 0, 0, 0, nullptr, 0, 0, 0, h->bwd_scatter16 ? h->Ubwd6b : nullptr,
-                               bwd_scatter_bf16_units(h->cfg.N), h->Why_b, h->WhyT_b, h->pl.Why, sj,
-                               h->fwd_halves16 ? h->Ufwd6b : nullptr, fwd_halves_bf16_units(h->cfg.N)));
-        h->packed6b = h->bwd_scatter16;
-        static const bool quad_off = getenv("LSTM_HIP_ADAGRAD_QUAD") && atoi(getenv("LSTM_HIP_ADAGRAD_QUAD")) == 0; // (A/B switch of adagrad())
-        h->packedf6b = h->fwd_halves16 && !quad_off;
+    const EnginePlan &p = h->plan;
+    const int N = h->cfg.N;
+    const SlideJob slide{h->text, h->text_len, h->pos, h->Xr, h->Tr, h->head, h->xi, h->ti, h->H, h->C,
+                         h->cfg.S, h->cfg.B, N, h->stride, h->carry_col};
+    AdagradJob job{};
+    job.P = h->P, job.dP = h->dP, job.mem = h->mem, job.n = h->pl.total, job.u_off = h->pl.U, job.N = N, job.lr = (float)lr;
+    // The same launch refreshes every live image of U: the fp32 ones in the layouts of the plan's forms; on the bf16 path (whose
+    // one-recurrence images pack_U_bf16 repacks) the two-half images, whose 8-byte elements are the four rows an Adagrad thread
+    // holds, and both bf16 copies of Why.
+    if (!p.bf16()) {
+        job.Ufwd = p.ufwd4() ? nullptr : h->Ufwd, job.Ubwd = p.ubwd4() ? nullptr : h->Ubwd;
+        job.Ufwd4 = h->Ufwd4, job.Ubwd4 = h->Ubwd4, job.half_forms = p.half_forms();
+    } else {
+        job.u6b = h->Ubwd6b, job.u6_uw = bwd_scatter_bf16_units(N), job.uf6b = h->Ufwd6b, job.uf6_uw = fwd_halves_bf16_units(N);
+        job.why_b = h->Why_b, job.whyT_b = h->WhyT_b, job.why_off = h->pl.Why;
     }
-    else
-    RUN(K_ADAGRAD, adagrad(h->P, h->dP, h->mem, h->pl.total, (float)lr, h->pl.U, h->cfg.N, h->Ufwd4 ? nullptr : h->Ufwd,
-                           h->Ubwd4 ? nullptr : h->Ubwd, h->st, h->Ubwd4, h->Ufwd4, nullptr, 0, 0, 0, nullptr, 0, 0, h->half_forms(), nullptr, 0,
-                           nullptr, nullptr, 0, sj));
-    if (sj) h->pre_slid = true;
+    if (h->fold_pending) { // the fused backward pass left the gradient in pieces (single-GPU loop)
+        h->fold_pending = false;
+        job.gpart = h->gpart, job.n_groups = (h->cfg.B + p.gpart_cols - 1) / p.gpart_cols, job.group_stride = bwd_partial_floats(N);
+        job.slabs = h->n_slabs_dU > 0 ? h->slabs_dU : nullptr, job.n_slabs = h->n_slabs_dU, job.slab_stride = (size_t)4 * N * N;
+        job.by_off = h->pl.by;
+    }
+    job.slide = h->carry_slide ? &slide : nullptr;
+    job.quad = p.adagrad_quad;
+    RUN(K_ADAGRAD, adagrad(job, h->st));
+    if (job.slide) h->pre_slid = true;
     h->carry_slide = false;
     h->packed = true; // the fp32 U images were refreshed by the same launch (the bf16 path has none)
     h->packed16 = false;
-    h->why_packed = h->bf16; // (the bf16 path's Adagrad launch has just rewritten both bf16 copies of Why)
+    h->packed6b = p.bwd == BwdForm::Bf16Scatter;
+    h->packedf6b = p.fwd == FwdForm::Bf16Halves && p.adagrad_quad; // (k_adagrad writes that image in its quad form only)
+    h->why_packed = p.bf16(); // (the bf16 path's Adagrad launch has just rewritten both bf16 copies of Why)
     return 0;
 }
 
 } // namespace
 
-static int create_body(lstm_hip_ctx *h, const lstm_hip_config *cfg, const hipDeviceProp_t &prop);
+static int create_body(lstm_hip_ctx *h, const lstm_hip_config *cfg);
 
 namespace {
 // LSTM_HIP_PAD_HIDDEN: the internal width of a logical hidden size N >= 1 (include/lstm_hip.h).  A function of N and the flags
@@ -689,21 +657,13 @@ int lstm_hip_create(const lstm_hip_config *user_cfg, lstm_hip_t **out) {
         return fail(LSTM_HIP_ENODEV, "device %d is %s; this library is built for gfx950 only", cfg->device, prop.gcnArchName);
     HIP_TRY(hipSetDevice(cfg->device));
     // everything that can be refused is refused before the first allocation
-    if (cfg->flags & LSTM_HIP_BF16_RECURRENCE) {
-        if ((cfg->flags & LSTM_HIP_STEP_KERNELS) || cfg->N % 128 != 0 || cfg->N > 1024)
-            return fail(LSTM_HIP_EINVAL, "LSTM_HIP_BF16_RECURRENCE needs the persistent engine and N a multiple of 128, <= 1024 (N=%d, B=%d)", cfg->N, cfg->B);
-        if (cfg->B % 8 != 0)
-            return fail(LSTM_HIP_EINVAL, "LSTM_HIP_BF16_RECURRENCE needs a multiple of 8 streams (16-byte aligned bf16 operand rows); B=%d", cfg->B);
-        // the two-half forms (one workgroup per CU, 8-column groups) or, where a shape has none, the one-recurrence forms
-        if (!(fwd_halves_bf16_supported(cfg->N, cfg->B, prop.multiProcessorCount) && bwd_scatter_bf16_supported(cfg->N, cfg->B, prop.multiProcessorCount)) &&
-            !persistent_supported_bf16(cfg->N, cfg->B, prop.multiProcessorCount, false))
-            return fail(LSTM_HIP_EINVAL, "LSTM_HIP_BF16_RECURRENCE: the bf16 recurrence grids for N=%d, B=%d are not co-resident on %d CUs",
-                        cfg->N, cfg->B, prop.multiProcessorCount);
-    }
+    const EnginePlan plan = plan_engine(cfg->N, cfg->B, cfg->flags, prop.multiProcessorCount);
+    if (plan.refusal[0]) return fail(LSTM_HIP_EINVAL, "%s", plan.refusal);
 
     lstm_hip_ctx *h = new lstm_hip_ctx();
     h->N_log = user_cfg->N;
-    const int rc = create_body(h, cfg, prop);
+    h->plan = plan;
+    const int rc = create_body(h, cfg);
     if (rc != 0) {
         char keep[sizeof(g_err)];
         memcpy(keep, g_err, sizeof(keep)); // destroy must not overwrite the reason
@@ -717,7 +677,7 @@ int lstm_hip_create(const lstm_hip_config *user_cfg, lstm_hip_t **out) {
 
 } // extern "C"
 
-static int create_body(lstm_hip_ctx *h, const lstm_hip_config *cfg, const hipDeviceProp_t &prop) {
+static int create_body(lstm_hip_ctx *h, const lstm_hip_config *cfg) {
     h->cfg = *cfg;
     h->pl = ParamLayout::make(cfg->N, cfg->M);
     const size_t N = cfg->N, B = cfg->B, S = cfg->S, G4 = 4 * N;
@@ -735,11 +695,10 @@ static int create_body(lstm_hip_ctx *h, const lstm_hip_config *cfg, const hipDev
         HIP_TRY(hipEventSynchronize(h->evt1));
         HIP_TRY(hipEventElapsedTime(&ms, h->evt0, h->evt1));
     }
+    const EnginePlan &p = h->plan;
     ALLOC(h->P, h->pl.total);
     ALLOC(h->dP, h->pl.total);
     ALLOC(h->mem, h->pl.total);
-    ALLOC(h->Ufwd, N * N);
-    ALLOC(h->Ubwd, N * N);
     ALLOC(h->H, N * B * S);
     ALLOC(h->C, N * B * S);
     ALLOC(h->G, G4 * B * S);
@@ -750,9 +709,9 @@ static int create_body(lstm_hip_ctx *h, const lstm_hip_config *cfg, const hipDev
     ALLOC(h->dcnext, N * B);
     ALLOC(h->colloss, B * S);
     ALLOC(h->dby_part, (size_t)256 * softmax_parts(h->T));
-    h->splits_dWhy = gemm_pick_splits(false, true, 256, (int)N, h->T, prop.multiProcessorCount);
-    h->splits_dU = gemm_pick_splits(false, true, (int)G4, (int)N, h->T, prop.multiProcessorCount);
-    if (cfg->flags & LSTM_HIP_BF16_RECURRENCE) {
+    h->splits_dWhy = gemm_pick_splits(false, true, 256, (int)N, h->T, p.n_cus);
+    h->splits_dU = gemm_pick_splits(false, true, (int)G4, (int)N, h->T, p.n_cus);
+    if (p.bf16()) {
         h->Tpad = (h->T + 63) / 64 * 64;
         h->SBpad = ((int)B + h->Tpad + 63) / 64 * 64;
         h->splits_dWhy = gemm_bf16_pick_splits(256, (int)N, h->Tpad);
@@ -761,101 +720,48 @@ static int create_body(lstm_hip_ctx *h, const lstm_hip_config *cfg, const hipDev
     ALLOC(h->slabs, (size_t)h->splits_dWhy * 256 * N);
     ALLOC(h->slabs_dU, (size_t)h->splits_dU * G4 * N);
     ALLOC(h->dw_scratch, dW_scratch_bytes(h->T, (int)G4));
-    ALLOC(h->xi, S * B);
-    ALLOC(h->ti, S * B);
-    ALLOC(h->Xr, S * B);
-    ALLOC(h->Tr, S * B);
+    ALLOC(h->xi, S * B, 0xff); // -1: all-zero columns (opt:122,125)
+    ALLOC(h->ti, S * B, 0xff);
+    ALLOC(h->Xr, S * B, 0xff);
+    ALLOC(h->Tr, S * B, 0xff);
     ALLOC(h->head, 1);
-    HIP_TRY(hipMemset(h->xi, 0xff, sizeof(int32_t) * S * B)); // -1: all-zero columns (opt:122,125)
-    HIP_TRY(hipMemset(h->ti, 0xff, sizeof(int32_t) * S * B));
-    HIP_TRY(hipMemset(h->Xr, 0xff, sizeof(int32_t) * S * B));
-    HIP_TRY(hipMemset(h->Tr, 0xff, sizeof(int32_t) * S * B));
     ALLOC(h->d_loss, 1);
     ALLOC(h->pos, B);
     h->cnt_bytes = persistent_counter_bytes((int)S, (int)B);
     ALLOC(h->cnt, 2 * h->cnt_bytes / sizeof(unsigned));
     ALLOC(h->abortp, 4);
-    // bf16 path: every product is a bf16 GEMM of its own, nothing is fused into the recurrence
-    // one stream at hidden <= 128 (the reference's default shape): single-CU recurrences, unfused sums ("0": the multi-CU forms, A/B)
-    const bool small_ok = !(cfg->flags & (LSTM_HIP_STEP_KERNELS | LSTM_HIP_BF16_RECURRENCE)) && small_recurrence_supported(cfg->N, cfg->B) &&
-                          !(getenv("LSTM_HIP_SMALL") && atoi(getenv("LSTM_HIP_SMALL")) == 0);
-    const bool want_fused = !(cfg->flags & (LSTM_HIP_NO_FUSED_GRADS | LSTM_HIP_BF16_RECURRENCE)) && cfg->N <= 512 && !small_ok; // larger N: one workgroup per CU no longer holds
-    h->persistent = !(cfg->flags & LSTM_HIP_STEP_KERNELS) &&                          // the dW table beside the weights
-                    persistent_supported(cfg->N, cfg->B, prop.multiProcessorCount, want_fused);
-    h->n_cus = prop.multiProcessorCount;
-    h->slide_in_adagrad = !(getenv("LSTM_HIP_SLIDE_IN_ADAGRAD") && atoi(getenv("LSTM_HIP_SLIDE_IN_ADAGRAD")) == 0);
-    h->small = h->persistent && small_ok;
-    h->bwd_cols = bwd_group_cols(cfg->N, cfg->B, prop.multiProcessorCount);
-    if (cfg->flags & LSTM_HIP_BF16_RECURRENCE) { // refusals: lstm_hip_create, before anything is allocated
-        h->persistent = true;                    // ... where the bf16 kernels' own grids were checked
-        h->bf16 = true;
-        h->bwd_cols = bwd_group_cols_bf16(cfg->N, cfg->B, prop.multiProcessorCount, false);
+    // what the plan's forms use: weight images, bf16 operand copies, hand-off rings (sentinel-filled), partial blocks
+    if (!p.bf16()) {
+        ALLOC(h->Ufwd, N * N);
+        ALLOC(h->Ubwd, N * N);
+    }
+    if (p.ufwd4()) ALLOC(h->Ufwd4, N * N);
+    if (p.ubwd4()) ALLOC(h->Ubwd4, N * N);
+    if (p.bf16()) {
         ALLOC(h->Hb, S * B * N);
         ALLOC(h->DGb, S * B * G4);
-        HIP_TRY(hipMalloc(&h->Ufwd16, (size_t)8 * N * N));
-        HIP_TRY(hipMalloc(&h->Ubwd16, (size_t)8 * N * N));
         ALLOC(h->WhyT_b, 256 * N);
         ALLOC(h->Why_b, 256 * N);
         ALLOC(h->Ht_b, N * (size_t)h->SBpad);
         ALLOC(h->dYt_b, (size_t)256 * h->Tpad);
         ALLOC(h->DGt_b, G4 * (size_t)h->Tpad);
         ALLOC(h->dYb, (size_t)h->T * 256);
-        // "0": the one-recurrence forms (A/B; per handle) -- where the shape has them
-        const bool older = persistent_supported_bf16(cfg->N, cfg->B, prop.multiProcessorCount, false);
-        const char *bh = getenv("LSTM_HIP_BWD_HALVES");
-        h->bwd_scatter16 = !(older && bh && atoi(bh) == 0) && bwd_scatter_bf16_supported((int)N, (int)B, prop.multiProcessorCount);
-        const char *fh = getenv("LSTM_HIP_FWD_HALVES");
-        h->fwd_halves16 = !(older && fh && atoi(fh) == 0) && fwd_halves_bf16_supported((int)N, (int)B, prop.multiProcessorCount);
-        if (h->fwd_halves16) {
-            HIP_TRY(hipMalloc(&h->Ufwd6b, (size_t)8 * N * N));
-            HIP_TRY(hipMalloc(&h->Hxb, sizeof(unsigned short) * fwd_halves_bf16_ring_halfwords((int)N, (int)B)));
-            HIP_TRY(hipMemset(h->Hxb, 0xff, sizeof(unsigned short) * fwd_halves_bf16_ring_halfwords((int)N, (int)B)));
-        }
-        if (h->bwd_scatter16) {
-            HIP_TRY(hipMalloc(&h->Ubwd6b, (size_t)8 * N * N));
-            h->DGx_floats = bwd_scatter_bf16_ring_floats((int)N, (int)B, prop.multiProcessorCount);
-            ALLOC(h->DGx, h->DGx_floats);
-            HIP_TRY(hipMemset(h->DGx, 0xff, sizeof(float) * h->DGx_floats));
-        }
     }
-    if (h->persistent && bwd_uses_m4((int)N, h->bwd_cols, h->bf16) && !h->small) { // (the single-CU form reads the tile image Ubwd)
-        ALLOC(h->Ubwd4, N * N);
-        const char *bh = getenv("LSTM_HIP_BWD_HALVES");
-        h->side_stream = !(getenv("LSTM_HIP_NO_SIDE_STREAM") && atoi(getenv("LSTM_HIP_NO_SIDE_STREAM")));
-        // two-half (scatter) form wherever it exists; "0" selects the one-recurrence form (A/B), other values carry test /
-        // tuning bits for the kernel (value >> 1 = its cfg word)
-        const int bhv = bh ? atoi(bh) : 1;
-        const bool wide = two_half_wide((int)N, (int)B, prop.multiProcessorCount); // (no one-recurrence form there)
-        h->bwd_halves = bhv == 0 && !wide ? 0 : (bhv | 1) * (int)bwd_scatter_supported((int)N, (int)B, prop.multiProcessorCount, want_fused);
-        if (h->bwd_halves) { // hand-off through a sentinel ring
-            h->DGx_floats = bwd_ring_floats((int)N, (int)B);
-            ALLOC(h->DGx, h->DGx_floats);
-            HIP_TRY(hipMemset(h->DGx, 0xff, sizeof(float) * h->DGx_floats));
-        }
+    if (p.u16) {
+        HIP_TRY(hipMalloc(&h->Ufwd16, (size_t)8 * N * N));
+        HIP_TRY(hipMalloc(&h->Ubwd16, (size_t)8 * N * N));
     }
-    if (h->persistent && !h->bf16 && fwd_uses_8col_form((int)N, (int)B, prop.multiProcessorCount)) {
-        const char *pp = getenv("LSTM_HIP_FWD_HALVES"); // "0": one 8-column recurrence per workgroup (A/B; per handle)
-        h->fwd_cols4 = fwd_uses_two_half_form((int)N, (int)B, prop.multiProcessorCount) &&
-                       (!(pp && atoi(pp) == 0) || two_half_wide((int)N, (int)B, prop.multiProcessorCount));
-        ALLOC(h->Ufwd4, N * N);
-        ALLOC(h->Hx, fwd_ring_floats((int)N, (int)B));
-        HIP_TRY(hipMemset(h->Hx, 0xff, sizeof(float) * fwd_ring_floats((int)N, (int)B)));
-        // tuning knob (flat from 0 to 4 for the one-recurrence form; the two-half form polls without pause)
-        h->poll_cfg = getenv("LSTM_HIP_FWD_POLL") ? atoi(getenv("LSTM_HIP_FWD_POLL")) : (h->fwd_cols4 ? 0 : 1);
-    }
-    if (h->persistent && want_fused && h->bwd_cols == 8)
-    {
-        h->gpart_cols = h->bwd_halves ? bwd_scatter_group_cols((int)N, (int)B, prop.multiProcessorCount) : h->bwd_cols;
-        ALLOC(h->gpart, (size_t)((B + h->gpart_cols - 1) / h->gpart_cols) * bwd_partial_floats(cfg->N));
-    }
-    h->probe_overlap = getenv("LSTM_HIP_PROBE_OVERLAP") ? atoi(getenv("LSTM_HIP_PROBE_OVERLAP")) : 0;
+    if (p.fwd == FwdForm::Bf16Halves) HIP_TRY(hipMalloc(&h->Ufwd6b, (size_t)8 * N * N));
+    if (p.bwd == BwdForm::Bf16Scatter) HIP_TRY(hipMalloc(&h->Ubwd6b, (size_t)8 * N * N));
+    if (p.hx_floats) ALLOC(h->Hx, p.hx_floats, 0xff);
+    if (p.hxb_halfwords) ALLOC(h->Hxb, p.hxb_halfwords, 0xff);
+    if (p.dgx_floats) ALLOC(h->DGx, p.dgx_floats, 0xff);
+    if (p.fused) ALLOC(h->gpart, (size_t)((B + p.gpart_cols - 1) / p.gpart_cols) * bwd_partial_floats(cfg->N));
     HIP_TRY(hipStreamCreateWithFlags(&h->st2, hipStreamNonBlocking));
     HIP_TRY(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&h->ev_mid, hipEventDisableTiming));
-    if (h->persistent && (cfg->flags & LSTM_HIP_DEBUG_STAMPS) &&
-        ((cfg->N == 512 && h->Hx && h->Ubwd4) || (h->fwd_halves16 && h->bwd_scatter16)))
-        ALLOC(h->stamps, 4 * S * 16);
+    if (p.stamps) ALLOC(h->stamps, 4 * S * 16);
     if (h->padded()) // the largest logical-width copy: the parameter block, or g of one step (4N x B; h0 and c0 for the sampler)
         ALLOC(h->stage, std::max({ParamLayout::make(h->N_log, cfg->M).total, (size_t)4 * h->N_log * B, (size_t)2 * h->N_log}));
     HIP_TRY(hipDeviceSynchronize());
@@ -1212,7 +1118,7 @@ int lstm_hip_train_windows(lstm_hip_t *h, int64_t count, double learning_rate, d
         // ... and only for windows of up to 2 048 columns: the slide's one window-building workgroup has 256 threads there
         // instead of 1 024 and outlasts the Adagrad workgroups at the headline shape (6 400 columns: 0.660 -> 0.665 ms, while
         // configs[1] gains 4 us, configs[0] 2, configs[4] 3)
-        h->carry_slide = i + 1 < count && !h->profiling && h->slide_in_adagrad && (int64_t)h->cfg.S * h->cfg.B <= 2048;
+        h->carry_slide = i + 1 < count && !h->profiling && (int64_t)h->cfg.S * h->cfg.B <= 2048;
         if ((rc = do_adagrad(h, learning_rate))) return rc;
     }
     if (elapsed_ms) {
@@ -1247,7 +1153,7 @@ int lstm_hip_eval_bits(lstm_hip_t *h, const uint8_t *text, size_t len, double *b
     CHECK(h);
     if (!text || len < 2 || !bits_per_char) return fail(LSTM_HIP_EINVAL, "eval_bits: need >= 2 bytes and an output pointer");
     const int N = h->cfg.N;
-    if (!h->persistent || (h->cfg.flags & LSTM_HIP_STEP_KERNELS)) {
+    if (!h->plan.persistent()) {
         uint8_t *d_text = nullptr;
         struct Free {
             uint8_t *&p;
@@ -1307,7 +1213,7 @@ int lstm_hip_sample(lstm_hip_t *h, float *h0, float *c0, const double *u, int32_
     // sampled byte never leaves the device).  (k_sample does the whole 4N x N product in ONE workgroup: 395 us per
     // character at N = 512.)  Fixed cost per call: one pack_U of the current U (4N^2 floats, about 10 us at N = 512; P
     // changes under many calls, so the image is not cached) and the uploads; the scratch memory stays with the handle.
-    if (h->persistent && !(h->cfg.flags & LSTM_HIP_STEP_KERNELS) && count > 0)
+    if (h->plan.persistent() && count > 0)
         return lstm_hip_generate(h, 1, nullptr, nullptr, h0, c0, 1.0, u, count, out, nullptr, h0, c0);
     const int N = h->cfg.N;
     float *d_hc = nullptr;

@@ -44,6 +44,7 @@
 // against the occupancy of the device and falls back to the per-step engine otherwise.
 #include <type_traits>
 #include "kernels.h"
+#include "../../include/lstm_hip.h"
 
 #include <cstdlib>
 
@@ -3140,40 +3141,25 @@ constexpr size_t DW_TABLE_BYTES = 257 * 64 * sizeof(float); // dynamic LDS of th
 static bool fwd_second_form(int N) { return N == 128 || N == 256 || N == 512 || N == 1024; }
 // Columns one launch of the fp32 two-half forms takes (N = 256, 512): as many 8-column groups as are co-resident at one
 // workgroup per CU.  A wider batch runs as several launches over column ranges (the streams are independent recurrences).
-// CU count of the current device (the launchers' shape rules must agree with the ones lstm_hip_create applied)
-static int current_device_cus() {
-    static int cached_dev = -1, cached_cus = 0; // (a process drives one device; re-queried if that ever changes)
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) == hipSuccess && dev == cached_dev) return cached_cus;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 256;
-    cached_dev = dev, cached_cus = cus;
-    return cus;
-}
-int two_half_launch_cols(int N, int n_cus) { return 8 * (n_cus / (N / 16)); }
+static int two_half_launch_cols(int N, int n_cus) { return 8 * (n_cus / (N / 16)); }
 // 8 columns per workgroup (two alternating halves), or 4 (one half, twice the workgroups) where the whole batch then still
-// fits one launch -- the forward form only (the fused backward form's side waves are built around eight columns)
-int two_half_group_cols(int N, int B, int n_cus) {
-    static const int force = getenv("LSTM_HIP_FWD_GCOLS") ? atoi(getenv("LSTM_HIP_FWD_GCOLS")) : 0; // A/B: 4 or 8
-    if ((N != 256 && N != 512) || force == 8 || (B + 3) / 4 > n_cus / (N / 16)) return 8;
-    return 4;
-}
-bool two_half_wide(int N, int B, int n_cus) { return (N == 256 || N == 512) && B > two_half_launch_cols(N, n_cus) && n_cus >= N / 16; }
-bool fwd_uses_8col_form(int N, int B, int n_cus) {
+// fits one launch -- both directions (the scatter form's fused partial blocks are then one per 4-column group)
+static int two_half_group_cols(int N, int B, int n_cus) { return (N != 256 && N != 512) || (B + 3) / 4 > n_cus / (N / 16) ? 8 : 4; }
+static bool two_half_wide(int N, int B, int n_cus) { return (N == 256 || N == 512) && B > two_half_launch_cols(N, n_cus) && n_cus >= N / 16; }
+// forward recurrence on 8-column groups (k_fwd_persistent4 / k_fwd_persistent6, Ufwd4 image)
+static bool fwd_uses_8col_form(int N, int B, int n_cus) {
     // (N = 256, 512: any batch -- with one half per workgroup and a pinned launch a single stream is one group of 32 / 16
     // workgroups on one XCD, 1.8 us a step where the second form's 64 workgroups over all XCDs took 3.75; N = 1024 has the
     // 8-column one-recurrence form only, which wants more than one group)
-    static const bool narrow_off = getenv("LSTM_HIP_NARROW_TWO_HALF") && atoi(getenv("LSTM_HIP_NARROW_TWO_HALF")) == 0; // A/B
-    return (N == 256 || N == 512 || N == 1024) && (B > 8 || ((N == 256 || N == 512) && !narrow_off)) &&
-           ((N / 16) * ((B + 7) / 8) <= n_cus || two_half_wide(N, B, n_cus));
+    return (N == 256 || N == 512 || (N == 1024 && B > 8)) && ((N / 16) * ((B + 7) / 8) <= n_cus || two_half_wide(N, B, n_cus));
 }
 // 8-column groups in the backward recurrence when that still fits one workgroup per CU (more CUs pulling fewer bytes
 // each); on v_mfma_f32_4x4x1 for fp32 (N a multiple of 64)
-int bwd_group_cols(int N, int B, int n_cus) { return (N / 16) * ((B + 7) / 8) <= n_cus || two_half_wide(N, B, n_cus) ? 8 : 16; }
-bool bwd_uses_m4(int N, int cols, bool bf16) { return cols == 8 && !bf16 && N % 64 == 0 && N <= 1024; }
+static int bwd_group_cols(int N, int B, int n_cus) { return (N / 16) * ((B + 7) / 8) <= n_cus || two_half_wide(N, B, n_cus) ? 8 : 16; }
 // floats in one column group's partial gradient block [dW | dU | db | dWhy]
 size_t bwd_partial_floats(int N) { return (size_t)4 * N * 256 + (size_t)4 * N * N + (size_t)4 * N + (size_t)256 * N; }
 
-bool bwd_scatter_supported(int N, int B, int n_cus, bool fused);
+static bool bwd_scatter_supported(int N, int B, int n_cus, bool fused);
 // All workgroups of a recurrence wait on each other, so its grid must be co-resident.  The occupancy API is asked about
 // exactly the instantiation that will be launched, with its dynamic LDS; it can over-report by one block per CU
 // (MI355X_MICROARCH.md, residency), so one is taken off wherever more than one is claimed.
@@ -3182,7 +3168,7 @@ static bool grid_fits(size_t grid, int per_cu, int n_cus) {
     if (per_cu > 8) per_cu = 8;
     return per_cu >= 1 && grid <= (size_t)per_cu * n_cus;
 }
-bool persistent_supported(int N, int B, int n_cus, bool fused) {
+static bool persistent_supported(int N, int B, int n_cus, bool fused) {
     if (N % 64 != 0 || N > 1024) return false;
     if (two_half_wide(N, B, n_cus)) // several launches per direction: the two-half forms or nothing
         return (N == 512 ? blocks_per_cu(k_fwd_persistent6<512, false>, FWD4_THREADS) : blocks_per_cu(k_fwd_persistent6<256, false>, FWD4_THREADS)) >= 1 &&
@@ -3247,7 +3233,7 @@ static int bwd_bf16_blocks(int N, int cols, bool fused) {
     }
     return bb;
 }
-int bwd_group_cols_bf16(int N, int B, int n_cus, bool fused) {
+static int bwd_group_cols_bf16(int N, int B, int n_cus, bool fused) {
     // 4-column groups when even 8-column groups would leave half the CUs idle (BASELINE configs[4]: hidden 1024, 16 streams
     // per GPU = 128 workgroups of 8 columns): twice the CUs, each pulling and multiplying half as much per step
     if (!fused && B % 4 == 0 && (size_t)(N / 16) * ((B + 7) / 8) * 2 <= (size_t)n_cus &&
@@ -3256,7 +3242,7 @@ int bwd_group_cols_bf16(int N, int B, int n_cus, bool fused) {
     if (grid_fits((size_t)(N / 16) * ((B + 7) / 8), bwd_bf16_blocks(N, 8, fused), n_cus)) return 8;
     return 16;
 }
-bool persistent_supported_bf16(int N, int B, int n_cus, bool fused) {
+static bool persistent_supported_bf16(int N, int B, int n_cus, bool fused) {
     if (N % 128 != 0 || N > 1024) return false;
     int fb = 0, bb = 0;
     size_t fwd_grid = 0;
@@ -3439,7 +3425,7 @@ __global__ __launch_bounds__(SMALL_BWD_THREADS) void k_small_bwd(const float4 *_
         lds_barrier();
     }
 }
-bool small_recurrence_supported(int N, int B) { return B == 1 && (N == 128 || N == 64); }
+static bool small_recurrence_supported(int N, int B) { return B == 1 && (N == 128 || N == 64); }
 void small_fwd(const float *U, const float *W, const float *bias, float *H, float *C, float *G, const int32_t *xi, int N, int S, bool fast,
                hipStream_t st) {
 #define GO(n)                                                                                                     \
@@ -3485,7 +3471,6 @@ void fwd_persistent(const float4 *Ufwd, const float *W, const float *bias, float
     }
 }
 
-size_t fwd_ring_floats(int N, int B) { return (size_t)HX_RING * N * B; }
 int fwd_ring_advance(int ring_base, int S) { return (ring_base + S - 1) & (HX_RING - 1); }
 void fwd_persistent4(const float4 *Ufwd4, const float *W, const float *bias, float *H, float *C, float *G, const int32_t *xi,
                      float *Hx, unsigned *cnt, unsigned *abortp, unsigned epoch, int ring_base, int N, int S, int B, bool fast,
@@ -3508,14 +3493,11 @@ void fwd_persistent4(const float4 *Ufwd4, const float *W, const float *bias, flo
 }
 
 // two-half form (k_fwd_persistent6): N = 512 or 256 on the grid of the 8-column form
-bool fwd_uses_two_half_form(int N, int B, int n_cus) { return (N == 512 || N == 256) && fwd_uses_8col_form(N, B, n_cus); }
 void fwd_persistent6(const float4 *Ufwd5, const float *W, const float *bias, float *H, float *C, float *G, const int32_t *xi,
                      float *Hx, unsigned *cnt, unsigned *abortp, unsigned epoch, int ring_base, int N, int S, int B, bool fast,
-                     int poll_cfg, hipStream_t st, unsigned long long *stamps, int col0, int cols) {
-    const int GC = two_half_group_cols(N, B, current_device_cus());
-    const int NGh = ((cols > 0 ? cols : B) + GC - 1) / GC; // groups of this launch: columns [col0, col0 + cols)
-    static const bool no_pin = getenv("LSTM_HIP_NO_PIN") && atoi(getenv("LSTM_HIP_NO_PIN")); // A/B
-    const bool pinned = NGh < 8 && !no_pin; // one group per XCD (see the kernel)
+                     int poll_cfg, int col0, int cols, int GC, bool pin, hipStream_t st, unsigned long long *stamps) {
+    const int NGh = (cols + GC - 1) / GC; // groups of this launch: columns [col0, col0 + cols)
+    const bool pinned = pin && NGh < 8;   // one group per XCD (see the kernel)
     poll_cfg = (poll_cfg & 0xffff) | (pinned ? NGh << 16 : 0) | ((col0 / GC) << 20) | (GC == 4 ? 1 << 28 : 0);
     const dim3 grid(N / 16, pinned ? 8 : NGh), block(FWD4_THREADS);
 #define F6_GO(...)                                                                                                            \
@@ -3569,7 +3551,6 @@ void pack_Ufwd6_bf16(const float *U, void *img, int N, hipStream_t st) {
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(k_pack_Ufwd6_bf16, dim3(blocks), dim3(256), 0, st, U, reinterpret_cast<uint2 *>(img), N, fwd_halves_bf16_units(N));
 }
-size_t fwd_halves_bf16_ring_halfwords(int N, int B) { return (size_t)HX_RING * N * B; }
 #define FHB_DISPATCH(GO)                  \
     do {                                  \
         if (N == 1024) GO(1024, 32);      \
@@ -3584,15 +3565,12 @@ size_t fwd_halves_bf16_ring_halfwords(int N, int B) { return (size_t)HX_RING * N
 // (forward / backward / window): N=1024 B=16 259 / 280 us, 0.708 ms -> 212 / 219 us, 0.601 ms; B=32 260 / 286 -> 215 / 223;
 // N=512 B=16 141 / 172 -> 137 / 156; N=256 B=32 134 / 128 -> 128 / 115.  (A batch that would need a second launch with
 // 4-column groups keeps 8: hidden 1024 with 64 streams is one launch of 625 us, not two of 435.)
-int bf16_group_cols(int N, int B, int n_cus) {
-    static const int force = getenv("LSTM_HIP_BF16_GCOLS") ? atoi(getenv("LSTM_HIP_BF16_GCOLS")) : 0; // A/B: 4 or 8
+static int bf16_group_cols(int N, int B, int n_cus) {
     const int fit = n_cus / (N / fwd_halves_bf16_units(N)); // groups of one launch
-    if (force == 8 || B % 4 != 0 || (B + 3) / 4 > fit) return 8;
-    if (force == 4) return 4;
+    if (B % 4 != 0 || (B + 3) / 4 > fit) return 8;
     return BF16_SINGLE_HALF_DEFAULT ? 4 : 8;
 }
-int fwd_halves_bf16_launch_cols(int N, int B, int n_cus) { return bf16_group_cols(N, B, n_cus) * (n_cus / (N / fwd_halves_bf16_units(N))); }
-bool fwd_halves_bf16_supported(int N, int B, int n_cus) {
+static bool fwd_halves_bf16_supported(int N, int B, int n_cus) {
     if (N != 256 && N != 512 && N != 1024) return false;
     if (B % 4 != 0) return false; // 8-byte ring pieces and Hb rows
     if (n_cus / (N / fwd_halves_bf16_units(N)) < 1) return false;
@@ -3606,14 +3584,12 @@ bool fwd_halves_bf16_supported(int N, int B, int n_cus) {
 #undef GO
     return per_cu >= 1;
 }
-// one launch: columns [col0, col0 + cols) of the B, cols <= fwd_halves_bf16_launch_cols; ring_base is that column range's own
+// one launch: columns [col0, col0 + cols) of the B, cols <= EnginePlan::launch_cols; ring_base is that column range's own
 void fwd_halves_bf16(const void *Ufwd6b, const float *W, const float *bias, float *H, unsigned short *Hb, float *C, float *G,
                      const int32_t *xi, void *Hxb, unsigned *cnt, unsigned *abortp, unsigned epoch, int ring_base, int N, int S,
-                     int B, int col0, int cols, bool fast, int n_cus, hipStream_t st, unsigned long long *stamps) {
-    const int GC = bf16_group_cols(N, B, n_cus);
+                     int B, int col0, int cols, int GC, bool pin, bool fast, hipStream_t st, unsigned long long *stamps) {
     const int NB = N / fwd_halves_bf16_units(N), NG = (cols + GC - 1) / GC;
-    static const bool no_pin = getenv("LSTM_HIP_NO_PIN") && atoi(getenv("LSTM_HIP_NO_PIN")); // A/B
-    const int pinned = NG < 8 && 8 * NB <= n_cus && !no_pin;
+    const int pinned = pin && NG < 8;
     const dim3 grid(pinned ? 8 * NB : NB * NG);
     const FwdhbArgs args = {reinterpret_cast<const uint2 *>(Ufwd6b), W, bias, H, Hb, C, G, xi, reinterpret_cast<unsigned *>(Hxb), cnt, abortp,
                             epoch, ring_base, S, B, NG, pinned, col0, GC, stamps};
@@ -3630,10 +3606,10 @@ void fwd_halves_bf16(const void *Ufwd6b, const float *W, const float *bias, floa
 
 void fwd_persistent_bf16(const void *Ufwd16, const float *W, const float *bias, float *H, unsigned short *Hb, float *C,
                          float *G, const int32_t *xi, unsigned *cnt, unsigned *abortp, unsigned epoch, int N, int S, int B,
-                         bool fast, hipStream_t st, int n_cus) {
+                         bool fast, int cols, hipStream_t st) {
     const u32x4 *U16 = reinterpret_cast<const u32x4 *>(Ufwd16);
     if (N % 256 == 0) {
-        if (fwd_bf16_cols(N, B, n_cus) == 8) {
+        if (cols == 8) {
             const dim3 grid8(N / 8, (B + 7) / 8), block2(512);
             switch (N / 256) {
 #define X(k)                                                                                                             \
@@ -3672,16 +3648,9 @@ void fwd_persistent_bf16(const void *Ufwd16, const float *W, const float *bias, 
 
 // ---- backward --------------------------------------------------------------------------------------------------------
 // (one buffer serves whichever form the handle runs: the dg ring of the two-half form or the partial-sum ring of the scatter form)
-size_t bwd_ring_floats(int N, int B) {
+static size_t bwd_ring_floats(int N, int B) {
     const size_t dg = (size_t)HX_RING * 4 * N * B, q = (N == 512 || N == 256) ? bwds_ring_floats(N, B) : 0;
     return dg > q ? dg : q;
-}
-int bwd_ring_advance(int ring_base, int S) { return (ring_base - (S - 1)) & (HX_RING - 1); }
-// columns per group of the fp32 scatter form for this shape (4 = one half per workgroup): the fused partial gradient blocks
-// are one per group
-int bwd_scatter_group_cols(int N, int B, int n_cus) {
-    static const bool force8 = getenv("LSTM_HIP_BWD_GCOLS") && atoi(getenv("LSTM_HIP_BWD_GCOLS")) == 8; // A/B
-    return two_half_group_cols(N, B, n_cus) == 4 && !force8 ? 4 : 8;
 }
 int bwds_ring_advance(int ring_base, int S) {
     if (BWDS_TAGGED) return (ring_base + (S > 2 ? S - 2 : 0)) & 7; // publication number: slot = low two bits, parity = bit 2
@@ -3689,7 +3658,7 @@ int bwds_ring_advance(int ring_base, int S) {
 }
 
 // scatter form of the backward recurrence (k_bwd_scatter): the shapes of the two-half form
-bool bwd_scatter_supported(int N, int B, int n_cus, bool fused) {
+static bool bwd_scatter_supported(int N, int B, int n_cus, bool fused) {
     if ((N != 512 && N != 256) || bwd_group_cols(N, B, n_cus) != 8) return false;
     const int lg = two_half_launch_cols(N, n_cus) / 8, ng = (B + 7) / 8;
     const size_t grid = (size_t)(N / 16) * (ng < lg ? ng : lg); // of one launch
@@ -3704,13 +3673,11 @@ bool bwd_scatter_supported(int N, int B, int n_cus, bool fused) {
 }
 void bwd_scatter(const float4 *Ubwd6, float *DG, const float *Why, const float *dY, const float *G, const float *C, const float *H,
                  const int32_t *xi, float *gpart, float *Qx, unsigned *cnt, unsigned *abortp, unsigned epoch, int ring_base, int N,
-                 int S, int B, int cfg, hipStream_t st, unsigned long long *stamps, int col0, int cols) {
-    // fewer than 8 groups: pinned launch, one group per XCD (see BWDH_COMMON); cfg bit 16 (spread mapping, tests) keeps the plain one
-    const int GC = bwd_scatter_group_cols(N, B, current_device_cus());
-    const int NGh = ((cols > 0 ? cols : B) + GC - 1) / GC; // groups of this launch: columns [col0, col0 + cols)
+                 int S, int B, int cfg, int col0, int cols, int GC, bool pin, hipStream_t st, unsigned long long *stamps) {
+    // fewer than 8 groups: pinned launch, one group per XCD (see BWDH_COMMON); pin is off with cfg bit 16 (spread mapping, tests)
+    const int NGh = (cols + GC - 1) / GC; // groups of this launch: columns [col0, col0 + cols)
     cfg = (cfg & 0xffff) | ((col0 / GC) << 20) | (GC == 4 ? 1 << 28 : 0);
-    static const bool no_pin = getenv("LSTM_HIP_NO_PIN") && atoi(getenv("LSTM_HIP_NO_PIN")); // A/B
-    const bool pinned = NGh < 8 && !(cfg & 16) && !no_pin;
+    const bool pinned = pin && NGh < 8;
     if (pinned) cfg |= NGh << 16;
     const dim3 grid(N / 16, pinned ? 8 : NGh), block(BWDH_THREADS);
     const bool fuse = gpart != nullptr;
@@ -3743,15 +3710,8 @@ void bwd_scatter(const float4 *Ubwd6, float *DG, const float *Why, const float *
 int bwd_scatter_bf16_units(int N) { return N == 1024 ? 32 : 16; }
 // publication number of the next launch's first hand-off (slot = low two bits, parity = bit 2)
 int bwd_scatter_bf16_ring_advance(int base, int S) { return (base + (S > 2 ? S - 2 : 0)) & 7; }
-int bf16_group_cols(int N, int B, int n_cus);
-int bwd_scatter_bf16_launch_cols(int N, int B, int n_cus) { return bf16_group_cols(N, B, n_cus) * (n_cus / (N / bwd_scatter_bf16_units(N))); }
-size_t bwd_scatter_bf16_ring_floats(int N, int B, int n_cus) {
-    (void)n_cus;
-    return bwdsb_ring_floats(N, bwd_scatter_bf16_units(N), B); // a region per column group of the whole batch
-}
-bool bwd_scatter_bf16_supported(int N, int B, int n_cus) {
+static bool bwd_scatter_bf16_supported(int N, int n_cus) {
     if (N != 256 && N != 512 && N != 1024) return false;
-    (void)B;
     if (n_cus / (N / bwd_scatter_bf16_units(N)) < 1) return false;
     int per_cu = 0;
     if (N == 1024) per_cu = blocks_per_cu(k_bwd_scatter_bf16<1024, 32>, BwdsbShape<1024, 32>::THREADS);
@@ -3759,14 +3719,12 @@ bool bwd_scatter_bf16_supported(int N, int B, int n_cus) {
     else per_cu = blocks_per_cu(k_bwd_scatter_bf16<256, 16>, BwdsbShape<256, 16>::THREADS);
     return per_cu >= 1;
 }
-// one launch: columns [col0, col0 + cols) of the B, cols <= bwd_scatter_bf16_launch_cols
+// one launch: columns [col0, col0 + cols) of the B, cols <= EnginePlan::launch_cols
 void bwd_scatter_bf16(const void *Ubwd6b, float *DG, const float *DHy, const float *G, const float *C, float *Qx, unsigned *cnt,
-                      unsigned *abortp, unsigned epoch, int ring_base, int N, int S, int B, int col0, int cols, int n_cus, hipStream_t st,
-                      unsigned long long *stamps, unsigned short *DGt_b, int Tpad) {
-    const int GC = bf16_group_cols(N, B, n_cus);
+                      unsigned *abortp, unsigned epoch, int ring_base, int N, int S, int B, int col0, int cols, int GC, bool pin,
+                      hipStream_t st, unsigned long long *stamps, unsigned short *DGt_b, int Tpad) {
     const int NB = N / bwd_scatter_bf16_units(N), NG = (cols + GC - 1) / GC;
-    static const int spread = getenv("LSTM_HIP_BWD_SPREAD") && atoi(getenv("LSTM_HIP_BWD_SPREAD")) ? 1 : 0;
-    const int pinned = NG < 8 && 8 * NB <= n_cus && !spread;
+    const int pinned = pin && NG < 8;
     const dim3 grid(pinned ? 8 * NB : NB * NG);
     const BwdsbArgs args = {reinterpret_cast<const uint2 *>(Ubwd6b), DG, DHy, G, C, Qx, cnt, abortp, epoch, ring_base, S, B, NG, pinned, col0, GC, DGt_b, Tpad, stamps};
     if (N == 1024 && stamps) hipLaunchKernelGGL((k_bwd_scatter_bf16<1024, 32, true>), grid, dim3(BwdsbShape<1024, 32>::THREADS), 0, st, args);
@@ -3778,13 +3736,12 @@ void bwd_scatter_bf16(const void *Ubwd6b, float *DG, const float *DHy, const flo
 
 void bwd_persistent(const float4 *Ubwd, float *DG, const float *DHy, const float *G, const float *C, const float *H,
                     const int32_t *xi, float *gpart, const float *Why, const float *dY, unsigned *cnt, unsigned *abortp,
-                    unsigned epoch, int N, int S, int B, int cols, hipStream_t st, unsigned long long *stamps,
+                    unsigned epoch, int N, int S, int B, int cols, bool spread_groups, hipStream_t st, unsigned long long *stamps,
                     unsigned short *DGb) {
     const dim3 grid(N / 16, (B + cols - 1) / cols), block(512);
     const bool fuse = gpart != nullptr;
     const size_t lds = fuse ? DW_TABLE_BYTES : 0;
-    // test hook: LSTM_HIP_BWD_SPREAD=1 keeps the dispatch-order workgroup mapping (column groups spread over all XCDs)
-    static const int spread = getenv("LSTM_HIP_BWD_SPREAD") && atoi(getenv("LSTM_HIP_BWD_SPREAD")) ? 1 : 0;
+    const int spread = spread_groups ? 1 : 0; // test hook: keep the dispatch-order workgroup mapping (groups over all XCDs)
 #define BWD_GO(...)                                                                                                    \
     do {                                                                                                               \
         if (fuse) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_bwd_persistent<__VA_ARGS__>),           \
@@ -3806,7 +3763,7 @@ void bwd_persistent(const float4 *Ubwd, float *DG, const float *DHy, const float
         }
         return;
     }
-    if (bwd_uses_m4(N, cols, false)) { // Ubwd is the 4x4x1 image here (the caller packs it when bwd_uses_m4 says so)
+    if (cols == 8) { // Ubwd is the 4x4x1 image here (BwdForm::Cols8)
         if (stamps != nullptr && N == 512) { // diagnostic build of the headline shape
             if (fuse) BWD_GO(16, 8, true, true, false, true);
             else BWD_GO(16, 8, false, true, false, true);
@@ -3833,4 +3790,89 @@ void bwd_persistent(const float4 *Ubwd, float *DG, const float *DHy, const float
 #undef BWD_GO
 }
 
+// ---- the engine plan: which form each recurrence of a handle runs, decided once at create ------------------------------
+// Every rule of the window lives here, next to the occupancy checks it rests on; the launchers and the window code follow the
+// plan.  Environment switches, read here (per handle): LSTM_HIP_FWD_HALVES=0 / LSTM_HIP_BWD_HALVES=0 select the one-recurrence
+// forms where the shape has them (other BWD_HALVES values carry the scatter kernel's test bits, value >> 1),
+// LSTM_HIP_BWD_SPREAD=1 keeps the dispatch-order mapping of the backward recurrence, LSTM_HIP_DU_SPLIT=1.
+static int env_int(const char *name, int dflt) { return getenv(name) ? atoi(getenv(name)) : dflt; }
+EnginePlan plan_engine(int N, int B, unsigned flags, int n_cus) {
+    EnginePlan p;
+    const auto refuse = [&p](const char *fmt, auto... args) {
+        snprintf(p.refusal, sizeof(p.refusal), fmt, args...);
+        return p;
+    };
+    p.n_cus = n_cus;
+    const int fwd_halves = env_int("LSTM_HIP_FWD_HALVES", 1), bwd_halves = env_int("LSTM_HIP_BWD_HALVES", 1);
+    p.bwd_spread = env_int("LSTM_HIP_BWD_SPREAD", 0) != 0;
+    const bool step = (flags & LSTM_HIP_STEP_KERNELS) != 0;
+    if (flags & LSTM_HIP_BF16_RECURRENCE) { // every product is a bf16 GEMM of its own, nothing is fused into the recurrence
+        if (step || N % 128 != 0 || N > 1024)
+            return refuse("LSTM_HIP_BF16_RECURRENCE needs the persistent engine and N a multiple of 128, <= 1024 (N=%d, B=%d)", N, B);
+        if (B % 8 != 0)
+            return refuse("LSTM_HIP_BF16_RECURRENCE needs a multiple of 8 streams (16-byte aligned bf16 operand rows); B=%d", B);
+        // the two-half forms (one workgroup per CU, 8-column groups) or, where a shape has none, the one-recurrence forms
+        const bool halves = fwd_halves_bf16_supported(N, B, n_cus), scatter = bwd_scatter_bf16_supported(N, n_cus);
+        const bool older = persistent_supported_bf16(N, B, n_cus, false);
+        if (!(halves && scatter) && !older)
+            return refuse("LSTM_HIP_BF16_RECURRENCE: the bf16 recurrence grids for N=%d, B=%d are not co-resident on %d CUs", N, B, n_cus);
+        p.fwd = halves && !(older && fwd_halves == 0) ? FwdForm::Bf16Halves : FwdForm::Bf16;
+        p.bwd = scatter && !(older && bwd_halves == 0) ? BwdForm::Bf16Scatter : BwdForm::Bf16;
+        p.fwd_cols = fwd_bf16_cols(N, B, n_cus);
+        p.bwd_cols = bwd_group_cols_bf16(N, B, n_cus, false);
+        // both two-half forms: as many groups per launch as are co-resident at one workgroup per CU (the same units per
+        // workgroup in both directions), pinned where eight groups' workgroups fit
+        const int NB = N / fwd_halves_bf16_units(N);
+        p.group_cols = bf16_group_cols(N, B, n_cus);
+        p.launch_cols = p.group_cols * (n_cus / NB);
+        p.fwd_pin = 8 * NB <= n_cus;
+        p.bwd_pin = p.fwd_pin && !p.bwd_spread;
+        // The recurrence writes the k-contiguous bf16 image of dg for the dU product itself (2-byte stores, off the chain)
+        // where that is cheaper than the transposing pass behind it: measured at N=1024 with 16 streams 0.5776 -> 0.5701 ms
+        // (recurrence +4 us, dU launch -9); with 64 streams the scattered stores cost the recurrence what the pass costs
+        // (N=512: +19 / -18 us) and with 128 more (+76 / -71 us per window), so only for the narrow batches.
+        p.direct_dgt = p.bwd == BwdForm::Bf16Scatter && N == 1024 && B <= 32;
+        p.adagrad_quad = p.fwd == FwdForm::Bf16Halves;
+        p.hxb_halfwords = p.fwd == FwdForm::Bf16Halves ? (size_t)HX_RING * N * B : 0; // bf16 h of every step slot
+        p.dgx_floats = p.bwd == BwdForm::Bf16Scatter ? bwdsb_ring_floats(N, bwd_scatter_bf16_units(N), B) : 0; // a region per group
+        p.u16 = p.fwd == FwdForm::Bf16 || p.bwd == BwdForm::Bf16;
+        p.stamps = (flags & LSTM_HIP_DEBUG_STAMPS) && p.fwd == FwdForm::Bf16Halves && p.bwd == BwdForm::Bf16Scatter;
+        return p;
+    }
+    // one stream at hidden <= 128 (the reference's default shape): single-CU recurrences, unfused sums.  Fused sums up to
+    // N = 512 (larger N: the dW table beside the weights no longer fits one workgroup per CU).
+    const bool small = !step && small_recurrence_supported(N, B);
+    const bool want_fused = !(flags & LSTM_HIP_NO_FUSED_GRADS) && N <= 512 && !small;
+    p.du_split = env_int("LSTM_HIP_DU_SPLIT", 0) != 0;
+    if (step || !persistent_supported(N, B, n_cus, want_fused)) return p;
+    if (small) {
+        p.fwd = FwdForm::Small, p.bwd = BwdForm::Small;
+        return p;
+    }
+    const bool wide = two_half_wide(N, B, n_cus); // several launches per direction: no one-recurrence form there
+    if (!fwd_uses_8col_form(N, B, n_cus)) p.fwd = FwdForm::Persistent;
+    else p.fwd = (N == 512 || N == 256) && (fwd_halves != 0 || wide) ? FwdForm::TwoHalf : FwdForm::Cols8;
+    p.bwd_cols = bwd_group_cols(N, B, n_cus);
+    if (p.bwd_cols != 8) p.bwd = BwdForm::Persistent;
+    else p.bwd = (bwd_halves != 0 || wide) && bwd_scatter_supported(N, B, n_cus, want_fused) ? BwdForm::Scatter : BwdForm::Cols8;
+    p.fused = want_fused && p.bwd_cols == 8;
+    if (p.fwd == FwdForm::TwoHalf || p.bwd == BwdForm::Scatter)
+        p.launch_cols = two_half_launch_cols(N, n_cus), p.group_cols = two_half_group_cols(N, B, n_cus);
+    p.gpart_cols = p.bwd == BwdForm::Scatter ? p.group_cols : p.bwd_cols;
+    p.bwd_cfg = p.bwd == BwdForm::Scatter ? bwd_halves >> 1 : 0;
+    p.fwd_pin = true;
+    p.bwd_pin = !(p.bwd_cfg & 16);
+    p.poll_cfg = p.fwd == FwdForm::Cols8 ? 1 : 0; // (flat from 0 to 4 for the one-recurrence form; the two-half form: no pause)
+    // (Not for the bf16 scatter form, although its pinned launch leaves most of the chip idle -- configs[4]: 64 of 256 CUs.
+    // Measured, kernel trace: of the side stream's launches only the one-workgroup column sort ran beside the recurrence; the
+    // next one started and then sat until the recurrence ended, because its workgroups are dealt to the XCDs in turn and the
+    // two XCDs the recurrence fills have no room for the ones they are dealt.  Window 0.6993 -> 0.6955 ms: dropped.  The
+    // sort alone, queued beside the FORWARD recurrence: 0.7094 against 0.7094.)
+    p.side_stream = p.bwd == BwdForm::Scatter && !p.fused;
+    p.adagrad_quad = p.fwd == FwdForm::TwoHalf && p.bwd == BwdForm::Scatter;
+    p.hx_floats = p.ufwd4() ? (size_t)HX_RING * N * B : 0;
+    p.dgx_floats = p.bwd == BwdForm::Scatter ? bwd_ring_floats(N, B) : 0;
+    p.stamps = (flags & LSTM_HIP_DEBUG_STAMPS) && N == 512 && p.ufwd4() && p.ubwd4();
+    return p;
+}
 } // namespace lstmk
