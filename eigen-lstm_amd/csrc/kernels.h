@@ -192,10 +192,11 @@ void pack_bf16(const float *src, size_t n, unsigned short *dst, hipStream_t st);
 // ---- output layer elementwise: probs = exp(y+by)/sum ; loss ; dy = probs - onehot  (R/lstm.cc:195-207,225)
 // Y is [T cols][256] (column-major 256 x T) and is overwritten by dY; probs written to P.
 // colloss[col] = -log2 p[target] (0 for an empty target); dby_part[wave][256] partial row sums of dY.
+// stable: the max-shifted form of LSTM_HIP_STABLE_SOFTMAX (probs = exp(z - max z)/sum, log-sum-exp surprisal).
 // Processes columns [col0, col1) (col0 a multiple of 8) with global indexing, so a window can be done in time chunks.
 int softmax_parts(int T);
 void softmax_loss_dy(float *Y, float *P, const float *by, const int32_t *ti, float *colloss, float *dby_part, int col0,
-                     int col1, hipStream_t st);
+                     int col1, bool stable, hipStream_t st); // stable: LSTM_HIP_STABLE_SOFTMAX (kernels.hip)
 // window loss as the reference sums it: for each t a float sum over b, / B_global, accumulated in double;
 // when dby != null a second workgroup folds the per-wave partials into dby = rowsum(dY) (R/lstm.cc:227)
 void loss_reduce(const float *colloss, int steps, int B, int B_global, double *out, const float *dby_part, int n_parts,
@@ -279,9 +280,9 @@ PadMap pad_map_rows(int blocks, int N, int Np, int cols); // `cols` columns of `
 void pad_copy(const float *src, float *dst, const PadMap &map, bool to_padded, hipStream_t st);
 
 // ---- B = 1 recurrence for the evaluator / sampler (OV/lstm_eigen_class_CUDA/lstm.cc:578-720)
-void eval_bits(const float *P, int N, const uint8_t *text, uint64_t len, double *out_bits_sum, float *scratch,
+void eval_bits(const float *P, int N, const uint8_t *text, uint64_t len, double *out_bits_sum, float *scratch, bool stable,
                hipStream_t st);
-void sample(const float *P, int N, float *hc /*2N*/, const double *u, int count, uint8_t *out, float *scratch,
+void sample(const float *P, int N, float *hc /*2N*/, const double *u, int count, uint8_t *out, float *scratch, bool stable,
             hipStream_t st);
 
 // ---- batched generator (lstm_hip_generate): per step gen_head on the state after t inputs, then fwd_step over all
@@ -297,10 +298,10 @@ struct GenHeadArgs {
     int32_t *x_next;            // the next input of every stream (-1: none)
     float *h_out, *c_out;       // the state after each stream's last input (null: not kept)
     int N, streams, count;
-    int mode;                   // 0: temperature 1 (unshifted expf, as the sampler), 1: tempered, 2: greedy
+    int mode;                   // 0: temperature 1 (expf as the sampler: unshifted, or shifted when stable), 1: tempered, 2: greedy
     float tau;
 };
-void gen_head(const GenHeadArgs &a, long long t, hipStream_t st);
+void gen_head(const GenHeadArgs &a, long long t, bool stable, hipStream_t st); // stable: LSTM_HIP_STABLE_SOFTMAX
 int gen_head_group(int N, int streams); // streams per workgroup of gen_head
 
 } // namespace lstmk

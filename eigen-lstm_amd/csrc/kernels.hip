@@ -36,6 +36,25 @@ __device__ __forceinline__ float wave_sum(float v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+// max over the 64 lanes, in every lane (exact in any order): four DPP steps within each row of 16 lanes (lane ^ 1, lane ^ 2,
+// then the mirrors within 8 and 16 lanes), lane ^ 16 by a shuffle and lane ^ 32 by v_permlane32_swap (with both operands
+// the same register, the two results hold this lane's value and lane ^ 32's)
+template <int CTRL> __device__ __forceinline__ float max_dpp(float v) {
+    return fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false)));
+}
+__device__ __forceinline__ float wave_max(float v) {
+    v = max_dpp<0xB1>(v);  // quad_perm [1,0,3,2]
+    v = max_dpp<0x4E>(v);  // quad_perm [2,3,0,1]
+    v = max_dpp<0x141>(v); // row_half_mirror
+    v = max_dpp<0x140>(v); // row_mirror
+    v = fmaxf(v, __shfl_xor(v, 16, 64));
+    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+}
+// LSTM_HIP_STABLE_SOFTMAX: -log2 p_t of p = exp(z - zmax) / s in log-sum-exp form (finite where p_t underflows to 0)
+__device__ __forceinline__ float lse_surprisal(float s, float zmax, float zt) {
+    return log2f(s) + (zmax - zt) * 1.44269504088896341f;
+}
 
 // ------------------------------------------------------------------------------------------------
 // pack_U: build the MFMA A-fragment images of U (4N x N) for both recurrences.
@@ -538,8 +557,11 @@ void pack_bf16(const float *src, size_t n, unsigned short *dst, hipStream_t st) 
 //   probs = exp(y + by) / sum  (no max shift)     R/lstm.cc:195-201
 //   surprisal = -log2(probs[target])              R/lstm.cc:204
 //   dy = probs - target                           R/lstm.cc:225
+// STABLE (LSTM_HIP_STABLE_SOFTMAX): with z = y + by and zmax the column's max (wave_max, same lanes),
+//   probs = exp(z - zmax) / sum,  surprisal = log2(sum) + (zmax - z[target]) log2(e); the sum's order is the default's
 // ------------------------------------------------------------------------------------------------
 constexpr int SM_COLS_PER_WAVE = 2;
+template <bool STABLE>
 __global__ __launch_bounds__(256) void k_softmax_loss_dy(float *__restrict__ Y, float *__restrict__ P,
                                                          const float *__restrict__ by, const int32_t *__restrict__ ti,
                                                          float *__restrict__ colloss, float *__restrict__ dby_part,
@@ -555,10 +577,23 @@ __global__ __launch_bounds__(256) void k_softmax_loss_dy(float *__restrict__ Y, 
         float4 *yp = reinterpret_cast<float4 *>(Y + (size_t)col * 256) + l;
         float4 y = *yp;
         float4 e;
-        e.x = expf(y.x + b4.x);
-        e.y = expf(y.y + b4.y);
-        e.z = expf(y.z + b4.z);
-        e.w = expf(y.w + b4.w);
+        float zmax = 0.0f;
+        if constexpr (STABLE) {
+            y.x = y.x + b4.x; // y is z from here on
+            y.y = y.y + b4.y;
+            y.z = y.z + b4.z;
+            y.w = y.w + b4.w;
+            zmax = wave_max(fmaxf(fmaxf(y.x, y.y), fmaxf(y.z, y.w)));
+            e.x = expf(y.x - zmax);
+            e.y = expf(y.y - zmax);
+            e.z = expf(y.z - zmax);
+            e.w = expf(y.w - zmax);
+        } else {
+            e.x = expf(y.x + b4.x);
+            e.y = expf(y.y + b4.y);
+            e.z = expf(y.z + b4.z);
+            e.w = expf(y.w + b4.w);
+        }
         const float s = wave_sum((e.x + e.y) + (e.z + e.w));
         float4 p;
         p.x = e.x / s;
@@ -570,8 +605,13 @@ __global__ __launch_bounds__(256) void k_softmax_loss_dy(float *__restrict__ Y, 
         float4 d = p;
         if (tk >= 0 && (tk >> 2) == l) {
             const int c = tk & 3;
-            const float pt = c == 0 ? p.x : c == 1 ? p.y : c == 2 ? p.z : p.w;
-            colloss[col] = -log2f(pt);
+            if constexpr (STABLE) {
+                const float zt = c == 0 ? y.x : c == 1 ? y.y : c == 2 ? y.z : y.w;
+                colloss[col] = lse_surprisal(s, zmax, zt);
+            } else {
+                const float pt = c == 0 ? p.x : c == 1 ? p.y : c == 2 ? p.z : p.w;
+                colloss[col] = -log2f(pt);
+            }
             if (c == 0) d.x -= 1.0f;
             else if (c == 1) d.y -= 1.0f;
             else if (c == 2) d.z -= 1.0f;
@@ -602,10 +642,13 @@ __global__ __launch_bounds__(256) void k_softmax_loss_dy(float *__restrict__ Y, 
 // softmax_parts(T) rows of 256 floats; rows of waves past col1 are written as zeros.
 int softmax_parts(int T) { return (T + 4 * SM_COLS_PER_WAVE - 1) / (4 * SM_COLS_PER_WAVE) + 4; } // one row per workgroup
 void softmax_loss_dy(float *Y, float *P, const float *by, const int32_t *ti, float *colloss, float *dby_part, int col0,
-                     int col1, hipStream_t st) {
+                     int col1, bool stable, hipStream_t st) {
     const int waves = (col1 - col0 + SM_COLS_PER_WAVE - 1) / SM_COLS_PER_WAVE;
     const int blocks = (waves + 3) / 4;
-    hipLaunchKernelGGL(k_softmax_loss_dy, dim3(blocks), dim3(256), 0, st, Y, P, by, ti, colloss, dby_part, col0, col1);
+    if (stable)
+        hipLaunchKernelGGL(k_softmax_loss_dy<true>, dim3(blocks), dim3(256), 0, st, Y, P, by, ti, colloss, dby_part, col0, col1);
+    else
+        hipLaunchKernelGGL(k_softmax_loss_dy<false>, dim3(blocks), dim3(256), 0, st, Y, P, by, ti, colloss, dby_part, col0, col1);
 }
 
 // dby = rowsum(dY) (R/lstm.cc:227): fold the per-wave partials.  1024 threads = 64 float4 row groups
@@ -1367,6 +1410,28 @@ __device__ float b1_output(const float *__restrict__ Why, const float *__restric
     for (int m = 0; m < 256; m++) s += ps[m];
     return s;
 }
+// LSTM_HIP_STABLE_SOFTMAX form: ps[m] = expf(z_m - zmax); returns the sum; *zmax and, for target >= 0, *zt = z_target
+// (every thread identically)
+__device__ float b1_output_stable(const float *__restrict__ Why, const float *__restrict__ by, int N, const float *hs,
+                                  float *ps, int target, float *zmax, float *zt) {
+    for (int m = threadIdx.x; m < 256; m += blockDim.x) {
+        float y = 0.0f;
+        for (int k = 0; k < N; k++) y += Why[(size_t)k * 256 + m] * hs[k];
+        ps[m] = y + by[m];
+    }
+    __syncthreads();
+    float zm = ps[0];
+    for (int m = 1; m < 256; m++) zm = fmaxf(zm, ps[m]);
+    *zmax = zm;
+    *zt = target >= 0 ? ps[target] : 0.0f;
+    __syncthreads();
+    for (int m = threadIdx.x; m < 256; m += blockDim.x) ps[m] = expf(ps[m] - zm);
+    __syncthreads();
+    float s = 0.0f;
+    for (int m = 0; m < 256; m++) s += ps[m];
+    return s;
+}
+template <bool STABLE>
 __global__ __launch_bounds__(1024) void k_eval_bits(const float *__restrict__ P, int N, const uint8_t *__restrict__ text,
                                                     uint64_t len, double *__restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -1377,16 +1442,25 @@ __global__ __launch_bounds__(1024) void k_eval_bits(const float *__restrict__ P,
     double err = 0.0;
     for (uint64_t ii = 0; ii + 1 < len; ii++) {
         b1_step(P + pl.W, P + pl.U, P + pl.b, N, text[ii], hs, cs, gs);
-        const float s = b1_output(P + pl.Why, P + pl.by, N, hs, ps);
-        err += -(double)log2f(ps[text[ii + 1]] / s);
+        if constexpr (STABLE) {
+            float zmax, zt;
+            const float s = b1_output_stable(P + pl.Why, P + pl.by, N, hs, ps, text[ii + 1], &zmax, &zt);
+            err += (double)lse_surprisal(s, zmax, zt);
+        } else {
+            const float s = b1_output(P + pl.Why, P + pl.by, N, hs, ps);
+            err += -(double)log2f(ps[text[ii + 1]] / s);
+        }
         __syncthreads();
     }
     if (threadIdx.x == 0) out[0] = err;
 }
-void eval_bits(const float *P, int N, const uint8_t *text, uint64_t len, double *out_bits_sum, float *, hipStream_t st) {
+void eval_bits(const float *P, int N, const uint8_t *text, uint64_t len, double *out_bits_sum, float *, bool stable,
+               hipStream_t st) {
     const size_t lds = (size_t)(6 * N + 256) * sizeof(float);
-    hipLaunchKernelGGL(k_eval_bits, dim3(1), dim3(1024), lds, st, P, N, text, len, out_bits_sum);
+    if (stable) hipLaunchKernelGGL(k_eval_bits<true>, dim3(1), dim3(1024), lds, st, P, N, text, len, out_bits_sum);
+    else hipLaunchKernelGGL(k_eval_bits<false>, dim3(1), dim3(1024), lds, st, P, N, text, len, out_bits_sum);
 }
+template <bool STABLE>
 __global__ __launch_bounds__(1024) void k_sample(const float *__restrict__ P, int N, float *__restrict__ hc,
                                                  const double *__restrict__ u, int count, uint8_t *__restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -1399,7 +1473,12 @@ __global__ __launch_bounds__(1024) void k_sample(const float *__restrict__ P, in
     }
     __syncthreads();
     for (int i = 0; i < count; i++) {
-        const float s = b1_output(P + pl.Why, P + pl.by, N, hs, ps);
+        float s;
+        if constexpr (STABLE) {
+            float zmax, zt;
+            s = b1_output_stable(P + pl.Why, P + pl.by, N, hs, ps, -1, &zmax, &zt);
+        } else
+            s = b1_output(P + pl.Why, P + pl.by, N, hs, ps);
         if (threadIdx.x == 0) {
             // cumulative sum, first index with r < cdf (R/lstm.cc:321-338); index 0 if none
             const float r = (float)u[i];
@@ -1428,13 +1507,16 @@ __global__ __launch_bounds__(1024) void k_sample(const float *__restrict__ P, in
 // streams = 1 case).  Per step the host launches this kernel on the state after t inputs, then one k_fwd_step over all
 // streams with the inputs it chose.  Per stream s, with L = its prompt length:
 //   t <  L          input prompt[t]; for t >= 1 (and bits requested) bits[s] += -log2 p(prompt[t]) at temperature 1
-//   L <= t < L + C  byte i = t - L drawn from p (mode 0: expf(z) unshifted, as b1_output; 1: expf((z - max z) / tau);
+//   L <= t < L + C  byte i = t - L drawn from p (mode 0: expf(z) unshifted, as b1_output, or expf(z - max z) when STABLE;
+//                   1: expf((z - max z) / tau);
 //                   2: argmax z, lowest index on ties) by the sequential float CDF walk of R/lstm.cc:321-338 (index 0
 //                   if u passes every edge); it goes to out[i * streams + s] and becomes the next input
 //   t == L + C      the state is the stream's final one: copied to h_out / c_out (the stream idles afterwards, x = -1)
 // Workgroup g owns streams g*SB .. g*SB+SB-1; thread m owns logit m of all of them, so each Why element read serves SB
 // streams (h of the group in LDS, k-major).  Each logit is summed sequentially in k with separate multiply and add
 // (contraction is off in this file), so a stream's bytes do not depend on SB, on its position or on the other streams.
+// STABLE (LSTM_HIP_STABLE_SOFTMAX): scored prompt bytes and mode-0 draws shift by max z too, and a prompt byte scores
+// lse_surprisal (the max and the target's logit are taken by the stream's max thread).
 // ------------------------------------------------------------------------------------------------
 // what stream s does at step t: 0 idle, 1 prompt byte scored, 2 drawn byte, 3 prompt byte not scored; *len = its prompt length
 __device__ __forceinline__ int gen_phase(const GenHeadArgs &a, int s, long long t, long long *len) {
@@ -1442,11 +1524,11 @@ __device__ __forceinline__ int gen_phase(const GenHeadArgs &a, int s, long long 
     if (t < *len) return (t >= 1 && a.bits) ? 1 : 3;
     return t - *len < a.count ? 2 : 0;
 }
-template <int SB>
+template <int SB, bool STABLE>
 __global__ __launch_bounds__(256) void k_gen_head(GenHeadArgs a, long long t) {
     extern __shared__ __attribute__((aligned(16))) float hs[]; // [N][SB]
     __shared__ float ps[SB][256];
-    __shared__ float s_zmax[SB], s_sum[SB];
+    __shared__ float s_zmax[SB], s_sum[SB], s_zt[STABLE ? SB : 1];
     __shared__ int s_arg[SB];
     const int m = threadIdx.x, N = a.N, s0 = blockIdx.x * SB;
     int phase[SB]; // (the same in every thread)
@@ -1491,11 +1573,13 @@ __global__ __launch_bounds__(256) void k_gen_head(GenHeadArgs a, long long t) {
             y[j] = y[j] + bym; // the logit z
             ps[j][m] = y[j];
             any_max |= phase[j] == 2 && a.mode != 0;
+            if constexpr (STABLE) any_max |= phase[j] == 1 || phase[j] == 2;
         }
         if (any_max) { // max z / argmax z of each tempered or greedy stream (every order gives the same max)
             __syncthreads();
             long long len;
-            if (m < SB && s0 + m < a.streams && gen_phase(a, s0 + m, t, &len) == 2) {
+            const int pm = m < SB && s0 + m < a.streams ? gen_phase(a, s0 + m, t, &len) : 0;
+            if (pm == 2 || (STABLE && pm == 1)) {
                 float best = ps[m][0];
                 int arg = 0;
                 for (int i = 1; i < 256; i++)
@@ -1505,12 +1589,14 @@ __global__ __launch_bounds__(256) void k_gen_head(GenHeadArgs a, long long t) {
                     }
                 s_zmax[m] = best;
                 s_arg[m] = arg;
+                if constexpr (STABLE)
+                    if (pm == 1) s_zt[m] = ps[m][a.prompts[a.off[s0 + m] + t]];
             }
             __syncthreads();
         }
 #pragma unroll
         for (int j = 0; j < SB; j++) {
-            if (phase[j] == 1 || (phase[j] == 2 && a.mode == 0)) ps[j][m] = expf(y[j]);
+            if (phase[j] == 1 || (phase[j] == 2 && a.mode == 0)) ps[j][m] = STABLE ? expf(y[j] - s_zmax[j]) : expf(y[j]);
             else if (phase[j] == 2 && a.mode == 1) ps[j][m] = expf((y[j] - s_zmax[j]) / a.tau);
         }
         __syncthreads();
@@ -1536,7 +1622,10 @@ __global__ __launch_bounds__(256) void k_gen_head(GenHeadArgs a, long long t) {
     int x = -1;
     if (ph == 1 || ph == 3) {
         x = a.prompts[a.off[s] + t];
-        if (ph == 1) a.bits[s] += -(double)log2f(ps[j][x]);
+        if (ph == 1) {
+            if constexpr (STABLE) a.bits[s] += (double)lse_surprisal(s_sum[j], s_zmax[j], s_zt[j]);
+            else a.bits[s] += -(double)log2f(ps[j][x]);
+        }
     } else if (ph == 2) {
         const size_t i = (size_t)(t - len);
         if (a.mode == 2) x = s_arg[j];
@@ -1561,15 +1650,15 @@ int gen_head_group(int N, int streams) {
     while (sb < 16 && streams >= 256 * 2 * sb && (size_t)2 * sb * N <= 16384) sb *= 2;
     return sb;
 }
-void gen_head(const GenHeadArgs &a, long long t, hipStream_t st) {
+template <bool STABLE> static void gen_head_launch(const GenHeadArgs &a, long long t, hipStream_t st) {
     const int sb = gen_head_group(a.N, a.streams);
     const size_t lds = (size_t)sb * a.N * sizeof(float);
     const dim3 grid((a.streams + sb - 1) / sb);
 #define GEN_HEAD_CASE(SB)                                                                                                   \
     case SB:                                                                                                                \
         if (lds > 32768)                                                                                                    \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_gen_head<SB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL(k_gen_head<SB>, grid, dim3(256), lds, st, a, t);                                                \
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_gen_head<SB, STABLE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+        hipLaunchKernelGGL((k_gen_head<SB, STABLE>), grid, dim3(256), lds, st, a, t);                                      \
         break;
     switch (sb) {
         GEN_HEAD_CASE(1)
@@ -1580,9 +1669,14 @@ void gen_head(const GenHeadArgs &a, long long t, hipStream_t st) {
     }
 #undef GEN_HEAD_CASE
 }
-void sample(const float *P, int N, float *hc, const double *u, int count, uint8_t *out, float *, hipStream_t st) {
+void gen_head(const GenHeadArgs &a, long long t, bool stable, hipStream_t st) {
+    if (stable) gen_head_launch<true>(a, t, st);
+    else gen_head_launch<false>(a, t, st);
+}
+void sample(const float *P, int N, float *hc, const double *u, int count, uint8_t *out, float *, bool stable, hipStream_t st) {
     const size_t lds = (size_t)(6 * N + 256) * sizeof(float);
-    hipLaunchKernelGGL(k_sample, dim3(1), dim3(1024), lds, st, P, N, hc, u, count, out);
+    if (stable) hipLaunchKernelGGL(k_sample<true>, dim3(1), dim3(1024), lds, st, P, N, hc, u, count, out);
+    else hipLaunchKernelGGL(k_sample<false>, dim3(1), dim3(1024), lds, st, P, N, hc, u, count, out);
 }
 
 // ------------------------------------------------------------------------------------------------

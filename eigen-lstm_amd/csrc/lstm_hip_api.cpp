@@ -346,7 +346,7 @@ int do_forward(lstm_hip_ctx *h) {
     RUN(K_GEMM_Y, gemm(false, false, 256, h->T, N, h->P + h->pl.Why, 256, h->H + (size_t)N * B, N,
                        h->Y + (size_t)256 * B, 256, 1, nullptr, h->st));
     RUN(K_SOFTMAX, softmax_loss_dy(h->Y + (size_t)256 * B, h->Pr + (size_t)256 * B, h->P + h->pl.by, h->ti + B,
-                                   h->colloss, h->dby_part, 0, h->T, h->st));
+                                   h->colloss, h->dby_part, 0, h->T, (h->cfg.flags & LSTM_HIP_STABLE_SOFTMAX) != 0, h->st));
     h->fwd_done = true;
     return 0;
 }
@@ -1145,7 +1145,7 @@ static int ensure_aux_handle(lstm_hip_ctx *h) {
     lstm_hip_config c = h->cfg; // (cfg.N is the parent's internal width: a padded parent's aux handle is an unpadded Np one)
     c.S = AUX_S;
     c.B = 1;
-    c.flags = (h->cfg.flags & LSTM_HIP_FAST_MATH) | LSTM_HIP_NO_FUSED_GRADS;
+    c.flags = (h->cfg.flags & (LSTM_HIP_FAST_MATH | LSTM_HIP_STABLE_SOFTMAX)) | LSTM_HIP_NO_FUSED_GRADS;
     return lstm_hip_create(&c, &h->eval_h);
 }
 
@@ -1163,7 +1163,7 @@ int lstm_hip_eval_bits(lstm_hip_t *h, const uint8_t *text, size_t len, double *b
         } free_text{d_text};
         HIP_TRY(hipMalloc((void **)&d_text, len));
         HIP_TRY(hipMemcpyAsync(d_text, text, len, hipMemcpyHostToDevice, h->st));
-        eval_bits(h->P, N, d_text, len, h->d_loss, nullptr, h->st);
+        eval_bits(h->P, N, d_text, len, h->d_loss, nullptr, (h->cfg.flags & LSTM_HIP_STABLE_SOFTMAX) != 0, h->st);
         double sum = 0.0;
         HIP_TRY(hipMemcpyAsync(&sum, h->d_loss, sizeof(double), hipMemcpyDeviceToHost, h->st));
         HIP_TRY(hipStreamSynchronize(h->st));
@@ -1243,7 +1243,7 @@ int lstm_hip_sample(lstm_hip_t *h, float *h0, float *c0, const double *u, int32_
         HIP_TRY(hipMemcpyAsync(d_hc + N, c0, sizeof(float) * N, hipMemcpyHostToDevice, h->st));
     }
     HIP_TRY(hipMemcpyAsync(d_u, u, sizeof(double) * count, hipMemcpyHostToDevice, h->st));
-    sample(h->P, N, d_hc, d_u, count, d_out, nullptr, h->st);
+    sample(h->P, N, d_hc, d_u, count, d_out, nullptr, (h->cfg.flags & LSTM_HIP_STABLE_SOFTMAX) != 0, h->st);
     if (h->padded()) {
         pad_copy(d_hc, h->stage, hc_map, false, h->st);
         if (int rc = pad_status()) return rc;
@@ -1360,13 +1360,13 @@ int lstm_hip_generate(lstm_hip_t *h, int32_t streams, const uint8_t *prompts, co
     // would give 0 / 0 at the maximum)
     a.mode = temperature < (double)FLT_MIN ? 2 : temperature == 1.0 ? 0 : 1;
     a.tau = (float)temperature;
-    const bool fast = (h->cfg.flags & LSTM_HIP_FAST_MATH) != 0;
+    const bool fast = (h->cfg.flags & LSTM_HIP_FAST_MATH) != 0, stable = (h->cfg.flags & LSTM_HIP_STABLE_SOFTMAX) != 0;
     const long long steps = (long long)max_len + count; // inputs of the longest stream
     int cur = 0;
     for (long long t = 0;; t++) {
         a.H = H + cur * n;
         a.C = Cs + cur * n;
-        RUN(K_GEN_HEAD, gen_head(a, t, h->st));
+        RUN(K_GEN_HEAD, gen_head(a, t, stable, h->st));
         if (t == steps) break;
         RUN(K_FWD_STEP, fwd_step(Ufwd, h->P + h->pl.W, h->P + h->pl.b, H + cur * n, Cs + cur * n, H + (cur ^ 1) * n,
                                  Cs + (cur ^ 1) * n, G, xi, N, streams, fast, h->st));

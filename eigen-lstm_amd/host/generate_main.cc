@@ -3,14 +3,15 @@
 // over many streams at once.  No HIP, no torch here.
 //
 //   lstm_generate --load PREFIX [--score FILE ...] [--count C --streams K --prime TEXT|--prime-file F
-//                 --temperature T --seed S] [--fast-math] [--device D]
+//                 --temperature T --seed S] [--fast-math] [--stable-softmax] [--device D]
 //
 // --load reads the five-file text checkpoint PREFIX_{W,U,Why,b,by}.txt (checkpoint.h); N is the rows of W / 4.
 // --score runs every FILE as one stream from h = c = 0 and prints "FILE: X.XXXXX bits/char (n bytes)" per file (bits over
 // the n - 1 predicted bytes, as lstm_hip_eval_bits) and a total weighted by those bytes.
 // --count prints K samples of C bytes, each continuing from the prompt (--prime / --prime-file, default none) from a zero
 // state; the draws come from SeededRng(S) (rng.h), byte i of stream s taking draw i*K + s, so a seed gives the same text.
-// --temperature 0 is greedy decoding and takes no draws.
+// --temperature 0 is greedy decoding and takes no draws.  --stable-softmax scores and draws at temperature 1 with the
+// max-shifted softmax (LSTM_HIP_STABLE_SOFTMAX), for checkpoints whose logits pass expf's range.
 #include "../../include/lstm_hip.h"
 #include "checkpoint.h"
 #include "rng.h"
@@ -27,7 +28,7 @@ namespace {
 
 const char *const kUsage =
     "usage: lstm_generate --load PREFIX [--score FILE ...] [--count C --streams K --prime TEXT|--prime-file F\n"
-    "                     --temperature T --seed S] [--fast-math] [--device D]\n";
+    "                     --temperature T --seed S] [--fast-math] [--stable-softmax] [--device D]\n";
 
 [[noreturn]] void usage(const std::string &m) {
     fprintf(stderr, "lstm_generate: %s\n%s", m.c_str(), kUsage);
@@ -112,6 +113,7 @@ Options parse(int argc, char **argv) {
         }
         else if (a == "--device") o.device = parse_int(a, val(), 0, 1 << 20);
         else if (a == "--fast-math") o.flags |= LSTM_HIP_FAST_MATH;
+        else if (a == "--stable-softmax") o.flags |= LSTM_HIP_STABLE_SOFTMAX;
         else if (a == "-h" || a == "--help") {
             printf("%s", kUsage);
             exit(0);

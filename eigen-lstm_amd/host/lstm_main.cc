@@ -6,7 +6,7 @@
 //   lstm --data F --hidden N --seq S --batch B --lr LR [--epochs E] [--seed K] [--gpus G]
 //        [--windows W] [--sample C] [--lr-warmup-windows X] [--save PREFIX] [--load PREFIX]
 //        [--eval-file F] [--stride K] [--forget-bias V] [--test-percent F] [--test-every SEC] [--log PREFIX]
-//        [--fast-math] [--step-kernels] [--quiet]
+//        [--fast-math] [--step-kernels] [--stable-softmax] [--quiet]
 //
 // stdout follows the reference: "Read N bytes (file)" (R/lstm.cc:398), the carriage-return progress
 // line (OV/lstm_eigen_opt/lstm.cc:320-331), the epoch summary (R/lstm.cc:284-291: GFLOP uses 2^30,
@@ -174,13 +174,15 @@ Options parse(int argc, char **argv) {
         else if (a == "--test-every") o.test_every = atof(val().c_str());
         else if (a == "--fast-math") o.flags |= LSTM_HIP_FAST_MATH;
         else if (a == "--step-kernels") o.flags |= LSTM_HIP_STEP_KERNELS;
+        else if (a == "--stable-softmax") o.flags |= LSTM_HIP_STABLE_SOFTMAX;
         else if (a == "--last-step-loss") o.last_step_loss = true;
         else if (a == "--last-step-loss-bits") o.last_step_bits = true;
         else if (a == "--quiet") o.quiet = true;
         else if (a == "-h" || a == "--help") {
             printf("usage: lstm <text file> <hidden> <seq> <batch> <lr> [--epochs E --seed K --gpus G --windows W --sample C\n"
                    "            --lr-warmup-windows X --save PREFIX --load PREFIX --eval-file F --stride K --forget-bias V\n"
-                   "            --test-percent F --test-every SEC --log PREFIX --last-step-loss --last-step-loss-bits --fast-math --step-kernels --quiet]\n");
+                   "            --test-percent F --test-every SEC --log PREFIX --last-step-loss --last-step-loss-bits --fast-math --step-kernels\n"
+                   "            --stable-softmax --quiet]\n");
             exit(0);
         } else if (a.rfind("--", 0) == 0) die("unknown option " + a);
         else pos.push_back(a);
@@ -358,8 +360,9 @@ int run_rank(const Options &o, int rank, int up, int down) {
             printf("chars/s through fwd+BPTT = %.1f (%ld windows, %d GPU%s)\n", chars / epoch_time, windows_per_epoch, o.gpus,
                    o.gpus > 1 ? "s" : "");
             if (nan_windows > 0) // the reference skips NaN losses silently; the unshifted softmax (R/lstm.cc:199) overflows when lr is too large
-                printf("!!!! %ld of %ld windows had a NaN loss (skipped in the average): lower --lr or use --lr-warmup-windows\n",
-                       nan_windows, windows_per_epoch);
+                printf("!!!! %ld of %ld windows had a NaN loss (skipped in the average): lower --lr or use --lr-warmup-windows%s\n",
+                       nan_windows, windows_per_epoch,
+                       (o.flags & LSTM_HIP_STABLE_SOFTMAX) ? "" : ". --stable-softmax keeps large logits finite.");
             if (evaldata.size() > 1 || !o.log.empty())
                 test_and_log(epoch_loss / ((double)S * (double)(windows_per_epoch + S)),
                              (flops_per_iteration * windows_per_epoch / std::pow(2.0, 30)) / epoch_time);

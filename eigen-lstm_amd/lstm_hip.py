@@ -23,6 +23,7 @@ DEBUG_STAMPS = 16
 NO_FUSED_GRADS = 64
 BF16_RECURRENCE = 128
 PAD_HIDDEN = 256  # any hidden size >= 1, run at an internal padded width (include/lstm_hip.h); shapes stay logical
+STABLE_SOFTMAX = 512  # max-shifted output layer with log-sum-exp surprisal, for logits past expf's range (include/lstm_hip.h)
 LOSS_ALL_STEPS_BITS, LOSS_LAST_STEP_NATS, LOSS_LAST_STEP_BITS = 0, 1, 2
 OK, EINVAL, EHIP, ENODEV, ERCCL, ESTATE = 0, -1, -2, -3, -4, -5  # LSTM_HIP_OK, LSTM_HIP_E* return codes
 UNIQUE_ID_BYTES = 128

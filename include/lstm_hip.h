@@ -66,6 +66,16 @@ extern "C" {
                                         LSTM_HIP_STEP_KERNELS:           N rounded up to 16
                                       Every call still takes and returns logical-N shapes; only the RCCL all-reduce
                                       payload is the padded block (lstm_hip_param_count(Np, M) floats). */
+#define LSTM_HIP_STABLE_SOFTMAX 512u /* max-shifted output layer, for logits past expf's range (about 88).  Per column
+                                      (one stream at one step), with z = Why*h + by and zmax = max_m z_m:
+                                        p_m = expf(z_m - zmax) / s,  s = sum_m expf(z_m - zmax)
+                                        surprisal = log2f(s) + (zmax - z_target) * log2(e)  (finite where p_target
+                                                    underflows to 0; 0 for an empty target, as without the flag)
+                                      dy = p - onehot, the loss modes, the /B and dby are defined on these as without
+                                      the flag.  Training, lstm_hip_eval_bits, lstm_hip_sample and the temperature-1 draws
+                                      and prompt bits of lstm_hip_generate all use it (tempered and greedy draws are
+                                      unchanged).  Fixed at create; combines with every other flag.  Default: the
+                                      reference's unshifted softmax (R/lstm.cc:195-204). */
 
 typedef struct lstm_hip_ctx lstm_hip_t; /* opaque: cuParameters p,d,m + cuLSTM<S> in one object */
 
@@ -176,7 +186,8 @@ int lstm_hip_sample(lstm_hip_t *h, float *h0, float *c0, const double *u, int32_
  *                no prompts); bits[s] (may be NULL) = sum over prompt positions j = 1..L-1 of -log2 p(prompt[j]) at
  *                temperature 1, so bits[s] / (L-1) is the text's lstm_hip_eval_bits from a zero start
  *        sample  then `count` bytes, byte i drawn from the current h and fed back as the next input (as lstm_hip_sample):
- *                with z = Why*h + by, temperature 1: p = expf(z) / sum (unshifted); other temperature > 0:
+ *                with z = Why*h + by, temperature 1: p = expf(z) / sum (unshifted; max-shifted with
+ *                LSTM_HIP_STABLE_SOFTMAX, which also scores prompts in log-sum-exp form); other temperature > 0:
  *                p ~ expf((z - max z) / temperature); 0 (and any temperature below FLT_MIN, its limit): argmax z,
  *                lowest index on ties.  The byte is the first m with
  *                u < cdf[m] (sequential float sum), 0 if none; the draw is u[i*streams + s] (u may be NULL only for
