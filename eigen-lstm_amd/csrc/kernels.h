@@ -250,8 +250,16 @@ struct AdagradJob {
     size_t group_stride, slab_stride, by_off;
     const SlideJob *slide;
     bool quad;
+    const float *clip; // global-norm clipping: the coefficient grad_norm wrote (the step uses d * coef where coef < 1); null: off
 };
 void adagrad(const AdagradJob &job, hipStream_t st);
+// ---- global gradient norm (lstm_hip_set_grad_clip), before the clipped Adagrad launch: grad_sumsq takes the block of `job`
+// (dP, or the fold pieces job.gpart / job.slabs, which it sums into dP in the order adagrad uses) and writes
+// grad_norm_parts(job.n) double partials of sum d^2 in a fixed order; grad_norm adds them, writes the norm to *norm_out and
+// the float coefficient max_norm / (norm + 1e-6) (1 where it is not below 1) to *coef_out.  Deterministic: no atomics.
+int grad_norm_parts(size_t n);
+void grad_sumsq(const AdagradJob &job, double *part, hipStream_t st);
+void grad_norm(const double *part, int n_parts, double max_norm, double *norm_out, float *coef_out, hipStream_t st);
 int fwd_halves_bf16_units(int N);
 
 // ---- window builder on the device (OV/lstm_eigen_opt/lstm.cc:190-213): x/target rings + flat copies,

@@ -1140,16 +1140,20 @@ template <int CTRL> __device__ __forceinline__ float quad_dpp(float v) {
 // four rows (element (rows 4rg..4rg+3, k = 4*kb4 + lane & 3) instead of consecutive row groups of one k), so that after a 4 x 4
 // transpose across the quad BOTH images are written in 16-byte pieces: Ubwd6 wants four rows of a column, Ufwd5 four values of
 // k of a row.  (Loads and stores of P / dP / mem stay runs of 256 bytes per sixteen lanes.)
-template <bool FOLD, bool SLIDE = false, bool QUAD = false>
+// CLIP (global-norm clipping, lstm_hip_set_grad_clip): the step uses d * coef where the coefficient k_grad_norm left in
+// *clip is below 1 (the summed gradient is in dP by then: k_grad_sumsq did the fold, so FOLD is false with CLIP).
+template <bool FOLD, bool SLIDE = false, bool QUAD = false, bool CLIP = false>
 __global__ __launch_bounds__(256) void k_adagrad(float *__restrict__ P, float *__restrict__ dP,
                                                  float *__restrict__ mem, size_t n4, float lr, size_t u_off4, int N,
                                                  float4 *__restrict__ Ufwd, float4 *__restrict__ Ubwd,
                                                  float4 *__restrict__ Ubwd4, float4 *__restrict__ Ufwd4, GradFold fold,
-                                                 int half_forms) {
+                                                 int half_forms, const float *__restrict__ clip) {
+    static_assert(!(FOLD && CLIP), "with clipping the fold is done by k_grad_sumsq");
     if (SLIDE && (int)blockIdx.x >= fold.ada_blocks) { // the next window's slide: touches nothing this launch reads or writes
         slide_body(fold.slide, (int)blockIdx.x - fold.ada_blocks, (int)gridDim.x - fold.ada_blocks);
         return;
     }
+    const float coef = CLIP ? *clip : 1.0f;
     const size_t stride_ = (size_t)(SLIDE ? fold.ada_blocks : (int)gridDim.x) * blockDim.x;
     const size_t u_n4 = (size_t)N * N; // float4 count of U
     for (size_t i0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i0 < n4; i0 += stride_) {
@@ -1183,6 +1187,12 @@ __global__ __launch_bounds__(256) void k_adagrad(float *__restrict__ P, float *_
             }
         } else {
             d = reinterpret_cast<const float4 *>(dP)[i];
+        }
+        if (CLIP && coef < 1.0f) {
+            d.x *= coef;
+            d.y *= coef;
+            d.z *= coef;
+            d.w *= coef;
         }
         float4 m = reinterpret_cast<float4 *>(mem)[i];
         p.x = adagrad1(p.x, d.x, m.x, lr);
@@ -1301,11 +1311,16 @@ void adagrad(const AdagradJob &j, hipStream_t st) {
                         reinterpret_cast<uint2 *>(j.u6b), j.u6_uw, reinterpret_cast<uint2 *>(j.uf6b), j.uf6_uw, j.why_b, j.whyT_b,
                         j.why_off / 4, (size_t)256 * j.N / 4, sl, blocks};
     blocks += extra;
-#define ADA_GO(F, S_, Q)                                                                                                      \
-    hipLaunchKernelGGL((k_adagrad<F, S_, Q>), dim3(blocks), dim3(256), 0, st, j.P, j.dP, j.mem, n4, j.lr, j.u_off / 4, j.N, j.Ufwd, \
-                       j.Ubwd, j.Ubwd4, j.Ufwd4, fold, j.half_forms)
+#define ADA_GO(F, S_, Q, ...)                                                                                                 \
+    hipLaunchKernelGGL((k_adagrad<F, S_, Q, ##__VA_ARGS__>), dim3(blocks), dim3(256), 0, st, j.P, j.dP, j.mem, n4, j.lr,      \
+                       j.u_off / 4, j.N, j.Ufwd, j.Ubwd, j.Ubwd4, j.Ufwd4, fold, j.half_forms, j.clip)
     const bool f = j.gpart != nullptr, sl_ = extra != 0, quad = j.quad;
-    if (f && sl_ && quad) ADA_GO(true, true, true);
+    if (j.clip != nullptr) { // (never with a fold: k_grad_sumsq has summed the pieces into dP)
+        if (sl_ && quad) ADA_GO(false, true, true, true);
+        else if (sl_) ADA_GO(false, true, false, true);
+        else if (quad) ADA_GO(false, false, true, true);
+        else ADA_GO(false, false, false, true);
+    } else if (f && sl_ && quad) ADA_GO(true, true, true);
     else if (f && sl_) ADA_GO(true, true, false);
     else if (f && quad) ADA_GO(true, false, true);
     else if (f) ADA_GO(true, false, false);
@@ -1314,6 +1329,84 @@ void adagrad(const AdagradJob &j, hipStream_t st) {
     else if (quad) ADA_GO(false, false, true);
     else ADA_GO(false, false, false);
 #undef ADA_GO
+}
+
+// ------------------------------------------------------------------------------------------------
+// Global gradient norm (lstm_hip_set_grad_clip): sum of d^2 over the flat block [dW|dU|db|dWhy|dby] in double, in one fixed
+// order over flat float4 indices: thread t of the fixed grid takes float4s t, t + grid*256, ... (x, y, z, w in turn), the
+// 256 threads of a workgroup are added by a fixed LDS tree, and k_grad_norm adds the workgroup partials in the same way.  The
+// order depends on the block size only, so the fold path, the summed dP and the communicator path give the same bits.
+// With a fold (the fused backward's column-group partial blocks and the dU split-K slabs), the pieces are summed here in
+// exactly the order of k_adagrad<FOLD> (and gemm_fold) and the sums stored to dP, which the Adagrad launch then reads plainly.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double block_sum256(double v, double *red) {
+    red[threadIdx.x] = v;
+#pragma unroll
+    for (int w = 128; w > 0; w >>= 1) {
+        __syncthreads();
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+    }
+    __syncthreads();
+    return red[0];
+}
+__global__ __launch_bounds__(256) void k_grad_sumsq(float *__restrict__ dP, size_t n4, size_t u_off4, size_t u_n4, GradFold fold,
+                                                    double *__restrict__ part) {
+    __shared__ double red[256];
+    double s = 0.0;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
+        float4 d;
+        const bool in_u = i >= u_off4 && i < u_off4 + u_n4;
+        if (fold.gpart != nullptr && i < fold.by_off4 && !(in_u && fold.slabs == nullptr)) {
+            const float *src = in_u ? fold.slabs + 4 * (i - u_off4) : fold.gpart + 4 * i;
+            const size_t stride = in_u ? fold.slab_stride : fold.group_stride;
+            const int n = in_u ? fold.n_slabs : fold.n_groups;
+            d = *reinterpret_cast<const float4 *>(src);
+            for (int z = 1; z < n; z++) {
+                const float4 q = *reinterpret_cast<const float4 *>(src + (size_t)z * stride);
+                d.x += q.x;
+                d.y += q.y;
+                d.z += q.z;
+                d.w += q.w;
+            }
+            reinterpret_cast<float4 *>(dP)[i] = d;
+        } else {
+            d = reinterpret_cast<const float4 *>(dP)[i];
+        }
+        s += (double)d.x * (double)d.x;
+        s += (double)d.y * (double)d.y;
+        s += (double)d.z * (double)d.z;
+        s += (double)d.w * (double)d.w;
+    }
+    s = block_sum256(s, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+// one workgroup: norm = sqrt(sum of the partials) -> *norm_out; coef = max_norm / (norm + 1e-6) in double, narrowed -> *coef_out,
+// and 1 where that is not below 1 (max_norm = +inf) or the norm is not finite (an inf or NaN entry: the step stays unscaled;
+// +inf would otherwise give coef 0 and no step at all)
+__global__ __launch_bounds__(256) void k_grad_norm(const double *__restrict__ part, int n_parts, double max_norm,
+                                                   double *__restrict__ norm_out, float *__restrict__ coef_out) {
+    __shared__ double red[256];
+    double s = 0.0;
+    for (int j = threadIdx.x; j < n_parts; j += blockDim.x) s += part[j];
+    s = block_sum256(s, red);
+    if (threadIdx.x == 0) {
+        const double norm = sqrt(s);
+        const float c = (float)(max_norm / (norm + 1e-6));
+        *norm_out = norm;
+        *coef_out = isfinite(norm) && c < 1.0f ? c : 1.0f;
+    }
+}
+int grad_norm_parts(size_t n) {
+    const size_t blocks = (n / 4 + 255) / 256;
+    return blocks > 1024 ? 1024 : (int)blocks;
+}
+void grad_sumsq(const AdagradJob &j, double *part, hipStream_t st) {
+    const GradFold fold{j.gpart, j.n_groups, j.group_stride, j.by_off / 4, j.slabs, j.n_slabs, j.slab_stride};
+    hipLaunchKernelGGL(k_grad_sumsq, dim3(grad_norm_parts(j.n)), dim3(256), 0, st, j.dP, j.n / 4, j.u_off / 4, (size_t)j.N * j.N,
+                       fold, part);
+}
+void grad_norm(const double *part, int n_parts, double max_norm, double *norm_out, float *coef_out, hipStream_t st) {
+    hipLaunchKernelGGL(k_grad_norm, dim3(1), dim3(256), 0, st, part, n_parts, max_norm, norm_out, coef_out);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -49,12 +49,13 @@ enum KernelId {
     K_DBY, K_ADAGRAD, K_SLIDE, K_ALLREDUCE, K_FWD_PERSIST, K_BWD_PERSIST, K_GEN_HEAD,
     K_SIDE_SUMS, // dW_sort, the dWhy product and dW_sums on the second stream (never timed: profiling keeps them on `st`)
     K_DU_HALVES, // the two column halves of the dU product (LSTM_HIP_DU_SPLIT; communicator loop only, never timed)
+    K_GRAD_SUMSQ, K_GRAD_NORM, // global-norm clipping (lstm_hip_set_grad_clip): partial sums of d^2, then norm and coefficient
     K_COUNT
 };
 const char *const kKernelNames[K_COUNT] = {
     "pack_U", "fwd_step", "gemm_Y", "softmax_loss_dy", "loss_reduce", "gemm_DHy", "bwd_step", "gemm_dWhy", "gemm_dU",
     "dW_db", "loss_dby", "adagrad", "slide", "allreduce", "fwd_persistent", "bwd_persistent", "gen_head", "side_sums",
-    "gemm_dU_halves"};
+    "gemm_dU_halves", "grad_sumsq", "grad_norm"};
 
 // ---- RCCL, loaded on first use so single-GPU users never touch it --------------------------
 struct UniqueId {
@@ -148,6 +149,13 @@ struct lstm_hip_ctx {
                                 // (The runtime's own staging path for a first large pageable copy cost the NEXT 20 windows
                                 // 0.4 ms of device time -- tools/train_windows_probe.py.)
     int64_t losses_cap = 0;
+    // global-norm clipping (lstm_hip_set_grad_clip): max_norm 0 = off
+    double clip_max = 0.0;
+    double *d_norms = nullptr;  // pre-clip norm of every Adagrad step of the current call (the window index of train_windows)
+    double *norm_part = nullptr; // grad_norm_parts(total) workgroup partials of k_grad_sumsq
+    float *clip_coef = nullptr;  // the coefficient of the step under way
+    int64_t norms_cap = 0;       // d_norms holds this many
+    int64_t norms_n = -1;        // steps of the last adagrad / train_windows call that recorded norms; -1: clipping was off
     uint8_t *text = nullptr;
     uint64_t text_len = 0;
     uint64_t *pos = nullptr;
@@ -560,7 +568,8 @@ int do_allreduce(lstm_hip_ctx *h) {
     return 0;
 }
 
-int do_adagrad(lstm_hip_ctx *h, double lr) {
+// norm_idx: the slot of d_norms this step's norm goes to (clipping on only)
+int do_adagrad(lstm_hip_ctx *h, double lr, int64_t norm_idx) {
     const EnginePlan &p = h->plan;
     const int N = h->cfg.N;
     const SlideJob slide{h->text, h->text_len, h->pos, h->Xr, h->Tr, h->head, h->xi, h->ti, h->H, h->C,
@@ -585,6 +594,12 @@ int do_adagrad(lstm_hip_ctx *h, double lr) {
     }
     job.slide = h->carry_slide ? &slide : nullptr;
     job.quad = p.adagrad_quad;
+    if (h->clip_max > 0.0) { // norm of the whole (summed, all-reduced) block first; the fold moves into k_grad_sumsq
+        RUN(K_GRAD_SUMSQ, grad_sumsq(job, h->norm_part, h->st));
+        RUN(K_GRAD_NORM, grad_norm(h->norm_part, grad_norm_parts(job.n), h->clip_max, h->d_norms + norm_idx, h->clip_coef, h->st));
+        job.gpart = nullptr, job.slabs = nullptr;
+        job.clip = h->clip_coef;
+    }
     RUN(K_ADAGRAD, adagrad(job, h->st));
     if (job.slide) h->pre_slid = true;
     h->carry_slide = false;
@@ -782,6 +797,8 @@ int lstm_hip_destroy(lstm_hip_t *h) {
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     if (h->h_losses) (void)hipHostFree(h->h_losses);
+    for (void *p : {(void *)h->d_norms, (void *)h->norm_part, (void *)h->clip_coef})
+        if (p) (void)hipFree(p);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->evt0) (void)hipEventDestroy(h->evt0);
@@ -978,7 +995,45 @@ int lstm_hip_backward(lstm_hip_t *h) {
 }
 int lstm_hip_adagrad(lstm_hip_t *h, double learning_rate) {
     CHECK(h);
-    return do_adagrad(h, learning_rate);
+    h->norms_n = -1;
+    if (int rc = do_adagrad(h, learning_rate, 0)) return rc;
+    if (h->clip_max > 0.0) h->norms_n = 1;
+    return 0;
+}
+
+// global-norm clipping before every Adagrad step (include/lstm_hip.h).  The scratch memory is made on the first use and kept
+// with the handle: d_norms grows with the longest train_windows call (train_windows, outside its loop).
+static int ensure_norms(lstm_hip_ctx *h, int64_t count) {
+    if (count <= h->norms_cap) return 0;
+    const int64_t cap = count < 8192 ? 8192 : count;
+    HIP_TRY(hipStreamSynchronize(h->st));
+    if (h->d_norms) HIP_TRY(hipFree(h->d_norms));
+    h->d_norms = nullptr;
+    h->norms_cap = 0;
+    HIP_TRY(hipMalloc((void **)&h->d_norms, sizeof(double) * cap));
+    h->norms_cap = cap;
+    return 0;
+}
+int lstm_hip_set_grad_clip(lstm_hip_t *h, double max_norm) {
+    CHECK(h);
+    if (std::isnan(max_norm) || max_norm < 0.0)
+        return fail(LSTM_HIP_EINVAL, "set_grad_clip: max_norm must be >= 0 (0 = off, +inf = measure only; got %g)", max_norm);
+    if (max_norm > 0.0) {
+        if (int rc = ensure_norms(h, 1)) return rc;
+        if (!h->norm_part) HIP_TRY(hipMalloc((void **)&h->norm_part, sizeof(double) * grad_norm_parts(h->pl.total)));
+        if (!h->clip_coef) HIP_TRY(hipMalloc((void **)&h->clip_coef, sizeof(float)));
+    }
+    h->clip_max = max_norm;
+    return 0;
+}
+int lstm_hip_get_grad_norms(lstm_hip_t *h, double *norms, int64_t n) {
+    CHECK(h);
+    if (h->norms_n < 0) return fail(LSTM_HIP_ESTATE, "get_grad_norms: clipping was off for the last adagrad / train_windows call");
+    if (n < 0 || n > h->norms_n || (n > 0 && !norms))
+        return fail(LSTM_HIP_EINVAL, "get_grad_norms: n = %lld outside [0, %lld] or null pointer", (long long)n, (long long)h->norms_n);
+    if (n > 0) HIP_TRY(hipMemcpyAsync(norms, h->d_norms, sizeof(double) * n, hipMemcpyDeviceToHost, h->st));
+    HIP_TRY(hipStreamSynchronize(h->st));
+    return 0;
 }
 
 int lstm_hip_comm_unique_id(uint8_t id[LSTM_HIP_UNIQUE_ID_BYTES]) {
@@ -1079,6 +1134,10 @@ int lstm_hip_train_windows(lstm_hip_t *h, int64_t count, double learning_rate, d
         HIP_TRY(hipHostMalloc((void **)&h->h_losses, sizeof(double) * cap, hipHostMallocDefault));
         h->losses_cap = cap;
     }
+    h->norms_n = -1;
+    const bool clip = h->clip_max > 0.0;
+    if (clip)
+        if (int rc = ensure_norms(h, count)) return rc;
     // the handle's own event pair (made and exercised once at create: the first timed record on a stream costs ~0.5 ms of
     // device time, which a 20-window measurement would carry)
     if (elapsed_ms) HIP_TRY(hipEventRecord(h->evt0, h->st));
@@ -1119,7 +1178,7 @@ int lstm_hip_train_windows(lstm_hip_t *h, int64_t count, double learning_rate, d
         // instead of 1 024 and outlasts the Adagrad workgroups at the headline shape (6 400 columns: 0.660 -> 0.665 ms, while
         // configs[1] gains 4 us, configs[0] 2, configs[4] 3)
         h->carry_slide = i + 1 < count && !h->profiling && (int64_t)h->cfg.S * h->cfg.B <= 2048;
-        if ((rc = do_adagrad(h, learning_rate))) return rc;
+        if ((rc = do_adagrad(h, learning_rate, i))) return rc;
     }
     if (elapsed_ms) {
         HIP_TRY(hipEventRecord(h->evt1, h->st));
@@ -1131,6 +1190,7 @@ int lstm_hip_train_windows(lstm_hip_t *h, int64_t count, double learning_rate, d
     HIP_TRY(hipStreamSynchronize(h->st));
     if (losses && count > 0) std::memcpy(losses, h->h_losses, sizeof(double) * count);
     guard.completed = true;
+    if (clip) h->norms_n = count;
     return check_abort(h);
 }
 

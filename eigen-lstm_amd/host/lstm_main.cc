@@ -6,7 +6,7 @@
 //   lstm --data F --hidden N --seq S --batch B --lr LR [--epochs E] [--seed K] [--gpus G]
 //        [--windows W] [--sample C] [--lr-warmup-windows X] [--save PREFIX] [--load PREFIX]
 //        [--eval-file F] [--stride K] [--forget-bias V] [--test-percent F] [--test-every SEC] [--log PREFIX]
-//        [--fast-math] [--step-kernels] [--stable-softmax] [--quiet]
+//        [--fast-math] [--step-kernels] [--stable-softmax] [--clip-norm X] [--quiet]
 //
 // stdout follows the reference: "Read N bytes (file)" (R/lstm.cc:398), the carriage-return progress
 // line (OV/lstm_eigen_opt/lstm.cc:320-331), the epoch summary (R/lstm.cc:284-291: GFLOP uses 2^30,
@@ -22,7 +22,13 @@
 // memory (PREFIX_mem_*.txt) and the stream cursors (PREFIX_cursors.txt), which the reference's checkpoints lack.
 // --lr-warmup-windows X applies lr = 0 for the first X windows (the reference's GPU driver uses
 // X = 50*S, OV/lstm_eigen_class_CUDA/lstm.cc:364-367; 0 = the root file's behaviour).
+// --clip-norm X clips the global gradient norm to X before every Adagrad step (lstm_hip_set_grad_clip; inf = measure only)
+// and adds one line per epoch report: mean and max pre-clip norm and the number of clipped windows.
 #include "../../include/lstm_hip.h"
+
+// referenced weakly: the program still links against a library without them and refuses --clip-norm there
+#pragma weak lstm_hip_set_grad_clip
+#pragma weak lstm_hip_get_grad_norms
 #include "checkpoint.h"
 #include "matrix_io.h"
 #include "rng.h"
@@ -65,6 +71,7 @@ struct Options {
     bool quiet = false;
     bool last_step_loss = false; // report forward_loss of OV/lstm_eigen_class_CUDA/lstm.h:200-221 (last step, nats)
     bool last_step_bits = false; // ... or cuLSTM::calculate_loss, cu_lstm.h:203-215 (last step, bits)
+    double clip_norm = 0.0;      // --clip-norm: 0 = off
 };
 
 [[noreturn]] void die(const std::string &m) {
@@ -175,6 +182,15 @@ Options parse(int argc, char **argv) {
         else if (a == "--fast-math") o.flags |= LSTM_HIP_FAST_MATH;
         else if (a == "--step-kernels") o.flags |= LSTM_HIP_STEP_KERNELS;
         else if (a == "--stable-softmax") o.flags |= LSTM_HIP_STABLE_SOFTMAX;
+        else if (a == "--clip-norm") {
+            const std::string v = val();
+            char *end = nullptr;
+            o.clip_norm = strtod(v.c_str(), &end);
+            if (end == v.c_str() || *end != '\0' || std::isnan(o.clip_norm) || o.clip_norm < 0.0)
+                die("--clip-norm needs a number >= 0 (0: off, inf: measure the norm only), got " + v);
+            if (o.clip_norm > 0.0 && (lstm_hip_set_grad_clip == nullptr || lstm_hip_get_grad_norms == nullptr))
+                die("--clip-norm: the loaded liblstm_hip has no lstm_hip_set_grad_clip / lstm_hip_get_grad_norms");
+        }
         else if (a == "--last-step-loss") o.last_step_loss = true;
         else if (a == "--last-step-loss-bits") o.last_step_bits = true;
         else if (a == "--quiet") o.quiet = true;
@@ -182,7 +198,7 @@ Options parse(int argc, char **argv) {
             printf("usage: lstm <text file> <hidden> <seq> <batch> <lr> [--epochs E --seed K --gpus G --windows W --sample C\n"
                    "            --lr-warmup-windows X --save PREFIX --load PREFIX --eval-file F --stride K --forget-bias V\n"
                    "            --test-percent F --test-every SEC --log PREFIX --last-step-loss --last-step-loss-bits --fast-math --step-kernels\n"
-                   "            --stable-softmax --quiet]\n");
+                   "            --stable-softmax --clip-norm X --quiet]\n");
             exit(0);
         } else if (a.rfind("--", 0) == 0) die("unknown option " + a);
         else pos.push_back(a);
@@ -216,6 +232,7 @@ int run_rank(const Options &o, int rank, int up, int down) {
     lstm_hip_config cfg{N, M, S, Bl, rank, o.flags | LSTM_HIP_PAD_HIDDEN};
     lstm_hip_t *h = nullptr;
     CK(lstm_hip_create(&cfg, &h));
+    if (o.clip_norm > 0.0) CK(lstm_hip_set_grad_clip(h, o.clip_norm)); // (every rank: each steps on the same all-reduced norm)
     if (o.gpus > 1) {
         uint8_t id[LSTM_HIP_UNIQUE_ID_BYTES];
         if (lead) {
@@ -303,7 +320,7 @@ int run_rank(const Options &o, int rank, int up, int down) {
     const long windows_per_epoch = (o.windows > 0) ? o.windows : (long)((length - S + o.stride - 1) / o.stride);
     long done_windows = 0;
     std::vector<float> hs((size_t)N * o.B), cs((size_t)N * o.B);
-    std::vector<double> losses;
+    std::vector<double> losses, norms;
 
     for (long e = 0; e < o.epochs; e++) {
         // epoch start: h[t], c[t] ~ N(0, 0.1) for every t (OV/lstm_eigen_opt/lstm.cc:176-181); drawn for
@@ -315,6 +332,8 @@ int run_rank(const Options &o, int rank, int up, int down) {
         }
         double epoch_loss = 0.0;
         long nan_windows = 0;
+        double norm_sum = 0.0, norm_max = 0.0;
+        long clipped = 0, norm_count = 0;
         const double t0 = now();
         double tf = t0;
         for (long i = 0; i < windows_per_epoch;) {
@@ -326,6 +345,17 @@ int run_rank(const Options &o, int rank, int up, int down) {
             }
             losses.resize(chunk);
             CK(lstm_hip_train_windows(h, chunk, lr, losses.data(), nullptr));
+            if (o.clip_norm > 0.0) {
+                norms.resize(chunk);
+                CK(lstm_hip_get_grad_norms(h, norms.data(), chunk));
+                for (double v : norms) { // (the rule of lstm_hip_set_grad_clip: scaled where the norm is finite and the float
+                                         // coefficient below 1)
+                    norm_sum += v;
+                    norm_max = std::max(norm_max, v);
+                    norm_count++;
+                    if (std::isfinite(v) && (float)(o.clip_norm / (v + 1e-6)) < 1.0f) clipped++;
+                }
+            }
             for (double v : losses) {
                 if (!std::isnan(v)) epoch_loss += v; // NaN guard as OV/lstm_eigen_class_CUDA/lstm.cc:325-326
                 else nan_windows++;
@@ -359,6 +389,9 @@ int run_rank(const Options &o, int rank, int up, int down) {
                    epoch_loss / ((double)S * (double)(windows_per_epoch + S))); // R/lstm.cc:290: loss/(S*length)
             printf("chars/s through fwd+BPTT = %.1f (%ld windows, %d GPU%s)\n", chars / epoch_time, windows_per_epoch, o.gpus,
                    o.gpus > 1 ? "s" : "");
+            if (o.clip_norm > 0.0)
+                printf("grad norm: mean %.4g, max %.4g, clipped %ld of %ld windows (--clip-norm %g)\n",
+                       norm_count ? norm_sum / (double)norm_count : 0.0, norm_max, clipped, norm_count, o.clip_norm);
             if (nan_windows > 0) // the reference skips NaN losses silently; the unshifted softmax (R/lstm.cc:199) overflows when lr is too large
                 printf("!!!! %ld of %ld windows had a NaN loss (skipped in the average): lower --lr or use --lr-warmup-windows%s\n",
                        nan_windows, windows_per_epoch,

@@ -53,6 +53,7 @@ SYMBOLS = [
     "lstm_hip_get_window", "lstm_hip_train_windows", "lstm_hip_set_global_batch", "lstm_hip_set_loss_mode", "lstm_hip_set_stride", "lstm_hip_eval_bits",
     "lstm_hip_sample", "lstm_hip_generate", "lstm_hip_synchronize", "lstm_hip_set_profiling", "lstm_hip_kernel_stat_count",
     "lstm_hip_kernel_stat", "lstm_hip_reset_kernel_stats", "lstm_hip_device_info", "lstm_hip_debug_stamps",
+    "lstm_hip_set_grad_clip", "lstm_hip_get_grad_norms",
 ]
 
 
@@ -200,6 +201,20 @@ class Lstm:
 
     def adagrad(self, lr):
         _chk(self.lib.lstm_hip_adagrad(self._h, C.c_double(lr)))
+        self._steps = 1
+
+    # ---- global-norm gradient clipping (lstm_hip_set_grad_clip) --------------------------------
+    def set_grad_clip(self, max_norm):
+        """0: off; > 0: scale the step's gradient by max_norm / (norm + 1e-6) where that is below 1; inf: measure only."""
+        _chk(self.lib.lstm_hip_set_grad_clip(self._h, C.c_double(max_norm)))
+
+    def grad_norms(self, n=None):
+        """pre-clip norms of the Adagrad steps of the last adagrad (1) / train_windows (count) call, oldest first;
+        n=None: all of them."""
+        k = getattr(self, "_steps", 0) if n is None else int(n)
+        out = np.zeros(k, np.float64)
+        _chk(self.lib.lstm_hip_get_grad_norms(self._h, _ptr(out, C.c_double), C.c_int64(k)))
+        return out
 
     # ---- data-parallel -----------------------------------------------------------------------
     def comm_init(self, unique_id, nranks, rank):
@@ -244,6 +259,7 @@ class Lstm:
         _chk(self.lib.lstm_hip_train_windows(self._h, C.c_int64(count), C.c_double(lr),
                                              _ptr(losses, C.c_double) if want_losses else None,
                                              C.byref(ms) if want_time else None))
+        self._steps = count
         if want_time:
             return losses, ms.value
         return losses

@@ -133,6 +133,23 @@ int lstm_hip_backward(lstm_hip_t *h);
 /* ---- cuda_adagrad, cu_lstm.h:417-432 (R/lstm.cc:261-272): m += d.*d; p -= lr*d./sqrt(m+1e-10) */
 int lstm_hip_adagrad(lstm_hip_t *h, double learning_rate);
 
+/* ---- global-norm gradient clipping before every Adagrad step (lstm_hip_adagrad and each window of lstm_hip_train_windows)
+ *   max_norm == 0      off (the default; nothing is computed, every path is the one without clipping)
+ *   max_norm  > 0      norm = sqrt(sum of d^2 over the whole flat gradient block [dW|dU|db|dWhy|dby]), taken after the
+ *                      all-reduce when there is a communicator; coef = max_norm / (norm + 1e-6) computed in double and
+ *                      narrowed to float; when coef < 1 the step uses d' = d * coef (fp32) in place of d:
+ *                      m += d'^2; p -= lr * d' / sqrt(m + 1e-10).  +INFINITY: measure only, never scale.
+ *                      A non-finite norm is recorded as is and the step is unscaled (it behaves as without clipping).
+ *   negative or NaN    LSTM_HIP_EINVAL
+ * The squares are summed in double in one fixed order over flat-block indices, so the norm depends
+ * only on the values of the summed block: bit-identical across engines' fold and plain paths and across ranks.  A padded
+ * handle (LSTM_HIP_PAD_HIDDEN) sums its padded block, whose padding entries are 0.  The gradient block (lstm_hip_get_params
+ * which=1) keeps the unclipped d.  Per handle, may change between calls, not part of checkpoints. */
+int lstm_hip_set_grad_clip(lstm_hip_t *h, double max_norm);
+/* the pre-clip norms of the Adagrad steps of the last lstm_hip_adagrad (1) or lstm_hip_train_windows (count) call,
+ * oldest first; n <= that number (else LSTM_HIP_EINVAL); LSTM_HIP_ESTATE when clipping was off for that call */
+int lstm_hip_get_grad_norms(lstm_hip_t *h, double *norms, int64_t n);
+
 /* ---- data-parallel exchange (new; the reference is single-device).  One SUM all-reduce of the
  *      flat gradient block per window over RCCL; every rank then applies the identical Adagrad step.
  *      With LSTM_HIP_PAD_HIDDEN the payload is the padded block (Np from N and the flags, so every
