@@ -234,6 +234,17 @@ struct SlideJob {
 //    folds use and the sums are also stored to dP (by_off: float offset of dby, final in dP)
 //  - slide: the next window's slide (or null); quad: the two-half images (Ufwd4 + Ubwd4 with half_forms 5, or uf6b) are
 //    written through quad transposes
+//  - v != null: the update is Adam with decoupled weight decay (lstm_hip_set_optimizer) instead of Adagrad: mem holds the
+//    first moment m, v the second moment, and `adam` the step's scalars, computed in double on the host and narrowed:
+//      p = p * decay; m = m + omb1 * (d - m); v = b2 * v + omb2 * d^2; p = p - step * m / (sqrt(v) / bc2s + eps)
+struct AdamScalars {
+    float decay;     // 1 - lr * weight_decay (1 when weight_decay is 0)
+    float omb1;      // 1 - beta1
+    float b2, omb2;  // beta2, 1 - beta2
+    float step;      // lr / (1 - beta1^t)
+    float bc2s;      // sqrt(1 - beta2^t)
+    float eps;
+};
 struct AdagradJob {
     float *P, *dP, *mem;
     size_t n, u_off;
@@ -251,6 +262,8 @@ struct AdagradJob {
     const SlideJob *slide;
     bool quad;
     const float *clip; // global-norm clipping: the coefficient grad_norm wrote (the step uses d * coef where coef < 1); null: off
+    float *v;          // Adam's second moment (n floats); null: Adagrad
+    AdamScalars adam;
 };
 void adagrad(const AdagradJob &job, hipStream_t st);
 // ---- global gradient norm (lstm_hip_set_grad_clip), before the clipped Adagrad launch: grad_sumsq takes the block of `job`

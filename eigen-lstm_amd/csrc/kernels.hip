@@ -1062,6 +1062,15 @@ __device__ __forceinline__ float adagrad1(float p, float d, float &m, float lr) 
     const float den = sqrtf((float)((double)m + 1e-10));
     return p - lr * (d / den);
 }
+// adam (lstm_hip_set_optimizer, torch.optim.AdamW's single-tensor step): decoupled decay, the moments as lerp / scaled
+// add, the bias corrections folded into the host's per-step scalars (AdamScalars).  m is `mem`.
+__device__ __forceinline__ float adam1(float p, float d, float &m, float &v, const AdamScalars &a) {
+    p = p * a.decay; // (decay = 1 without weight decay: exact)
+    m = m + a.omb1 * (d - m);
+    v = a.b2 * v + a.omb2 * (d * d);
+    const float den = sqrtf(v) / a.bc2s + a.eps;
+    return p - a.step * (m / den);
+}
 // The U block additionally refreshes the two MFMA fragment images (what k_pack_U builds), so the
 // forward of the next window needs no separate repack launch.  A float4 here is 4 consecutive gate
 // rows of one column k of U: one float4 of Ubwd, four scalars of Ufwd.
@@ -1142,12 +1151,15 @@ template <int CTRL> __device__ __forceinline__ float quad_dpp(float v) {
 // k of a row.  (Loads and stores of P / dP / mem stay runs of 256 bytes per sixteen lanes.)
 // CLIP (global-norm clipping, lstm_hip_set_grad_clip): the step uses d * coef where the coefficient k_grad_norm left in
 // *clip is below 1 (the summed gradient is in dP by then: k_grad_sumsq did the fold, so FOLD is false with CLIP).
-template <bool FOLD, bool SLIDE = false, bool QUAD = false, bool CLIP = false>
+// ADAM (lstm_hip_set_optimizer): the step is adam1 with m in `mem` and the second moment in v, at the same (QUAD-remapped)
+// index; everything else -- fold, clip, images, slide -- as for Adagrad.  The Adagrad instantiations never read v or adam.
+template <bool FOLD, bool SLIDE = false, bool QUAD = false, bool CLIP = false, bool ADAM = false>
 __global__ __launch_bounds__(256) void k_adagrad(float *__restrict__ P, float *__restrict__ dP,
                                                  float *__restrict__ mem, size_t n4, float lr, size_t u_off4, int N,
                                                  float4 *__restrict__ Ufwd, float4 *__restrict__ Ubwd,
                                                  float4 *__restrict__ Ubwd4, float4 *__restrict__ Ufwd4, GradFold fold,
-                                                 int half_forms, const float *__restrict__ clip) {
+                                                 int half_forms, const float *__restrict__ clip, float *__restrict__ v,
+                                                 AdamScalars adam) {
     static_assert(!(FOLD && CLIP), "with clipping the fold is done by k_grad_sumsq");
     if (SLIDE && (int)blockIdx.x >= fold.ada_blocks) { // the next window's slide: touches nothing this launch reads or writes
         slide_body(fold.slide, (int)blockIdx.x - fold.ada_blocks, (int)gridDim.x - fold.ada_blocks);
@@ -1195,10 +1207,19 @@ __global__ __launch_bounds__(256) void k_adagrad(float *__restrict__ P, float *_
             d.w *= coef;
         }
         float4 m = reinterpret_cast<float4 *>(mem)[i];
-        p.x = adagrad1(p.x, d.x, m.x, lr);
-        p.y = adagrad1(p.y, d.y, m.y, lr);
-        p.z = adagrad1(p.z, d.z, m.z, lr);
-        p.w = adagrad1(p.w, d.w, m.w, lr);
+        if (ADAM) {
+            float4 s = reinterpret_cast<float4 *>(v)[i];
+            p.x = adam1(p.x, d.x, m.x, s.x, adam);
+            p.y = adam1(p.y, d.y, m.y, s.y, adam);
+            p.z = adam1(p.z, d.z, m.z, s.z, adam);
+            p.w = adam1(p.w, d.w, m.w, s.w, adam);
+            reinterpret_cast<float4 *>(v)[i] = s;
+        } else {
+            p.x = adagrad1(p.x, d.x, m.x, lr);
+            p.y = adagrad1(p.y, d.y, m.y, lr);
+            p.z = adagrad1(p.z, d.z, m.z, lr);
+            p.w = adagrad1(p.w, d.w, m.w, lr);
+        }
         reinterpret_cast<float4 *>(P)[i] = p;
         reinterpret_cast<float4 *>(mem)[i] = m;
         if (fold.why_b != nullptr && i >= fold.why_off4 && i < fold.why_off4 + fold.why_n4) {
@@ -1293,6 +1314,27 @@ __global__ __launch_bounds__(256) void k_adagrad(float *__restrict__ P, float *_
         }
     }
 }
+template <bool ADAM> static void launch_update(const AdagradJob &j, const GradFold &fold, int blocks, bool sl_, hipStream_t st) {
+    const size_t n4 = j.n / 4;
+#define ADA_GO(F, S_, Q, C_)                                                                                                   \
+    hipLaunchKernelGGL((k_adagrad<F, S_, Q, C_, ADAM>), dim3(blocks), dim3(256), 0, st, j.P, j.dP, j.mem, n4, j.lr,         \
+                       j.u_off / 4, j.N, j.Ufwd, j.Ubwd, j.Ubwd4, j.Ufwd4, fold, j.half_forms, j.clip, j.v, j.adam)
+    const bool f = j.gpart != nullptr, quad = j.quad;
+    if (j.clip != nullptr) { // (never with a fold: k_grad_sumsq has summed the pieces into dP)
+        if (sl_ && quad) ADA_GO(false, true, true, true);
+        else if (sl_) ADA_GO(false, true, false, true);
+        else if (quad) ADA_GO(false, false, true, true);
+        else ADA_GO(false, false, false, true);
+    } else if (f && sl_ && quad) ADA_GO(true, true, true, false);
+    else if (f && sl_) ADA_GO(true, true, false, false);
+    else if (f && quad) ADA_GO(true, false, true, false);
+    else if (f) ADA_GO(true, false, false, false);
+    else if (sl_ && quad) ADA_GO(false, true, true, false);
+    else if (sl_) ADA_GO(false, true, false, false);
+    else if (quad) ADA_GO(false, false, true, false);
+    else ADA_GO(false, false, false, false);
+#undef ADA_GO
+}
 void adagrad(const AdagradJob &j, hipStream_t st) {
     const size_t n4 = j.n / 4; // the flat block is a multiple of 4 floats (M = 256, N % 16 == 0)
     int blocks = (int)((n4 + 255) / 256);
@@ -1311,24 +1353,8 @@ void adagrad(const AdagradJob &j, hipStream_t st) {
                         reinterpret_cast<uint2 *>(j.u6b), j.u6_uw, reinterpret_cast<uint2 *>(j.uf6b), j.uf6_uw, j.why_b, j.whyT_b,
                         j.why_off / 4, (size_t)256 * j.N / 4, sl, blocks};
     blocks += extra;
-#define ADA_GO(F, S_, Q, ...)                                                                                                 \
-    hipLaunchKernelGGL((k_adagrad<F, S_, Q, ##__VA_ARGS__>), dim3(blocks), dim3(256), 0, st, j.P, j.dP, j.mem, n4, j.lr,      \
-                       j.u_off / 4, j.N, j.Ufwd, j.Ubwd, j.Ubwd4, j.Ufwd4, fold, j.half_forms, j.clip)
-    const bool f = j.gpart != nullptr, sl_ = extra != 0, quad = j.quad;
-    if (j.clip != nullptr) { // (never with a fold: k_grad_sumsq has summed the pieces into dP)
-        if (sl_ && quad) ADA_GO(false, true, true, true);
-        else if (sl_) ADA_GO(false, true, false, true);
-        else if (quad) ADA_GO(false, false, true, true);
-        else ADA_GO(false, false, false, true);
-    } else if (f && sl_ && quad) ADA_GO(true, true, true);
-    else if (f && sl_) ADA_GO(true, true, false);
-    else if (f && quad) ADA_GO(true, false, true);
-    else if (f) ADA_GO(true, false, false);
-    else if (sl_ && quad) ADA_GO(false, true, true);
-    else if (sl_) ADA_GO(false, true, false);
-    else if (quad) ADA_GO(false, false, true);
-    else ADA_GO(false, false, false);
-#undef ADA_GO
+    if (j.v != nullptr) launch_update<true>(j, fold, blocks, extra != 0, st);
+    else launch_update<false>(j, fold, blocks, extra != 0, st);
 }
 
 // ------------------------------------------------------------------------------------------------

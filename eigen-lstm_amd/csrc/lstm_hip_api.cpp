@@ -50,12 +50,13 @@ enum KernelId {
     K_SIDE_SUMS, // dW_sort, the dWhy product and dW_sums on the second stream (never timed: profiling keeps them on `st`)
     K_DU_HALVES, // the two column halves of the dU product (LSTM_HIP_DU_SPLIT; communicator loop only, never timed)
     K_GRAD_SUMSQ, K_GRAD_NORM, // global-norm clipping (lstm_hip_set_grad_clip): partial sums of d^2, then norm and coefficient
+    K_ADAM,                    // the update launch on a handle set to LSTM_HIP_OPT_ADAM (K_ADAGRAD's launch with the Adam rule)
     K_COUNT
 };
 const char *const kKernelNames[K_COUNT] = {
     "pack_U", "fwd_step", "gemm_Y", "softmax_loss_dy", "loss_reduce", "gemm_DHy", "bwd_step", "gemm_dWhy", "gemm_dU",
     "dW_db", "loss_dby", "adagrad", "slide", "allreduce", "fwd_persistent", "bwd_persistent", "gen_head", "side_sums",
-    "gemm_dU_halves", "grad_sumsq", "grad_norm"};
+    "gemm_dU_halves", "grad_sumsq", "grad_norm", "adam"};
 
 // ---- RCCL, loaded on first use so single-GPU users never touch it --------------------------
 struct UniqueId {
@@ -156,6 +157,11 @@ struct lstm_hip_ctx {
     float *clip_coef = nullptr;  // the coefficient of the step under way
     int64_t norms_cap = 0;       // d_norms holds this many
     int64_t norms_n = -1;        // steps of the last adagrad / train_windows call that recorded norms; -1: clipping was off
+    // the update rule (lstm_hip_set_optimizer): Adagrad, or Adam with m in `mem` and v in adam_v
+    int opt_kind = LSTM_HIP_OPT_ADAGRAD;
+    double beta1 = 0.0, beta2 = 0.0, adam_eps = 0.0, weight_decay = 0.0;
+    int64_t opt_steps = 0;       // updates launched since create / the last change of kind
+    float *adam_v = nullptr;     // Adam's second moment (flat block); allocated when Adam is first selected
     uint8_t *text = nullptr;
     uint64_t text_len = 0;
     uint64_t *pos = nullptr;
@@ -600,7 +606,20 @@ int do_adagrad(lstm_hip_ctx *h, double lr, int64_t norm_idx) {
         job.gpart = nullptr, job.slabs = nullptr;
         job.clip = h->clip_coef;
     }
-    RUN(K_ADAGRAD, adagrad(job, h->st));
+    const bool adam = h->opt_kind == LSTM_HIP_OPT_ADAM;
+    if (adam) { // this step's scalars, in double and narrowed (include/lstm_hip.h); t counts every update of the handle
+        const double t = (double)(h->opt_steps + 1);
+        job.v = h->adam_v;
+        job.adam.decay = h->weight_decay > 0.0 ? (float)(1.0 - lr * h->weight_decay) : 1.0f;
+        job.adam.omb1 = (float)(1.0 - h->beta1);
+        job.adam.b2 = (float)h->beta2;
+        job.adam.omb2 = (float)(1.0 - h->beta2);
+        job.adam.step = (float)(lr / (1.0 - std::pow(h->beta1, t)));
+        job.adam.bc2s = (float)std::sqrt(1.0 - std::pow(h->beta2, t));
+        job.adam.eps = (float)h->adam_eps;
+    }
+    RUN(adam ? K_ADAM : K_ADAGRAD, adagrad(job, h->st));
+    h->opt_steps++;
     if (job.slide) h->pre_slid = true;
     h->carry_slide = false;
     h->packed = true; // the fp32 U images were refreshed by the same launch (the bf16 path has none)
@@ -797,7 +816,7 @@ int lstm_hip_destroy(lstm_hip_t *h) {
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     if (h->h_losses) (void)hipHostFree(h->h_losses);
-    for (void *p : {(void *)h->d_norms, (void *)h->norm_part, (void *)h->clip_coef})
+    for (void *p : {(void *)h->d_norms, (void *)h->norm_part, (void *)h->clip_coef, (void *)h->adam_v})
         if (p) (void)hipFree(p);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -811,10 +830,19 @@ int lstm_hip_destroy(lstm_hip_t *h) {
     return 0;
 }
 
-static float *block_of(lstm_hip_ctx *h, int which) { return which == 0 ? h->P : which == 1 ? h->dP : which == 2 ? h->mem : nullptr; }
+static float *block_of(lstm_hip_ctx *h, int which) {
+    return which == 0 ? h->P : which == 1 ? h->dP : which == 2 ? h->mem : which == 3 ? h->adam_v : nullptr;
+}
+// which = 3 (Adam's second moment) exists only while the handle is on Adam
+static int check_block(lstm_hip_ctx *h, int which, const char *what) {
+    if (which == 3 && h->opt_kind != LSTM_HIP_OPT_ADAM)
+        return fail(LSTM_HIP_ESTATE, "%s: block 3 (Adam's second moment) needs a handle set to LSTM_HIP_OPT_ADAM", what);
+    return 0;
+}
 
 int lstm_hip_set_params(lstm_hip_t *h, int which, const float *host_block) {
     CHECK(h);
+    if (int rc = check_block(h, which, "set_params")) return rc;
     float *dst = block_of(h, which);
     if (!dst || !host_block) return fail(LSTM_HIP_EINVAL, "set_params: bad block id %d or null pointer", which);
     if (h->padded()) { // logical block -> staging -> padded block, padding entries 0
@@ -830,6 +858,7 @@ int lstm_hip_set_params(lstm_hip_t *h, int which, const float *host_block) {
 }
 int lstm_hip_get_params(lstm_hip_t *h, int which, float *host_block) {
     CHECK(h);
+    if (int rc = check_block(h, which, "get_params")) return rc;
     float *src = block_of(h, which);
     if (!src || !host_block) return fail(LSTM_HIP_EINVAL, "get_params: bad block id %d or null pointer", which);
     if (h->padded()) {
@@ -1033,6 +1062,45 @@ int lstm_hip_get_grad_norms(lstm_hip_t *h, double *norms, int64_t n) {
         return fail(LSTM_HIP_EINVAL, "get_grad_norms: n = %lld outside [0, %lld] or null pointer", (long long)n, (long long)h->norms_n);
     if (n > 0) HIP_TRY(hipMemcpyAsync(norms, h->d_norms, sizeof(double) * n, hipMemcpyDeviceToHost, h->st));
     HIP_TRY(hipStreamSynchronize(h->st));
+    return 0;
+}
+
+// the update rule (include/lstm_hip.h).  A new kind starts from zero state: the memory / first moment, the second moment
+// (allocated on the first switch to Adam, kept with the handle) and the step count.
+int lstm_hip_set_optimizer(lstm_hip_t *h, int32_t kind, double beta1, double beta2, double eps, double weight_decay) {
+    CHECK(h);
+    if (kind == LSTM_HIP_OPT_ADAGRAD) {
+        if (beta1 != 0.0 || beta2 != 0.0 || eps != 0.0 || weight_decay != 0.0)
+            return fail(LSTM_HIP_EINVAL, "set_optimizer: LSTM_HIP_OPT_ADAGRAD takes no parameters (all four must be 0)");
+    } else if (kind == LSTM_HIP_OPT_ADAM) {
+        const bool ok = std::isfinite(beta1) && std::isfinite(beta2) && std::isfinite(eps) && std::isfinite(weight_decay) &&
+                        beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps > 0.0 && weight_decay >= 0.0;
+        if (!ok)
+            return fail(LSTM_HIP_EINVAL, "set_optimizer: Adam needs 0 <= beta1, beta2 < 1, eps > 0 and weight_decay >= 0, all finite "
+                                         "(got %g, %g, %g, %g)", beta1, beta2, eps, weight_decay);
+    } else
+        return fail(LSTM_HIP_EINVAL, "set_optimizer: unknown kind %d", kind);
+    if (kind != h->opt_kind) {
+        HIP_TRY(hipStreamSynchronize(h->st));
+        if (kind == LSTM_HIP_OPT_ADAM && !h->adam_v) HIP_TRY(hipMalloc((void **)&h->adam_v, sizeof(float) * h->pl.total));
+        HIP_TRY(hipMemsetAsync(h->mem, 0, sizeof(float) * h->pl.total, h->st));
+        if (h->adam_v) HIP_TRY(hipMemsetAsync(h->adam_v, 0, sizeof(float) * h->pl.total, h->st));
+        HIP_TRY(hipStreamSynchronize(h->st));
+        h->opt_kind = kind;
+        h->opt_steps = 0;
+    }
+    h->beta1 = beta1, h->beta2 = beta2, h->adam_eps = eps, h->weight_decay = weight_decay;
+    return 0;
+}
+int lstm_hip_get_optimizer_steps(lstm_hip_t *h, int64_t *steps) {
+    if (!h || !steps) return fail(LSTM_HIP_EINVAL, "get_optimizer_steps: null argument");
+    *steps = h->opt_steps;
+    return 0;
+}
+int lstm_hip_set_optimizer_steps(lstm_hip_t *h, int64_t steps) {
+    if (!h) return fail(LSTM_HIP_EINVAL, "null handle");
+    if (steps < 0) return fail(LSTM_HIP_EINVAL, "set_optimizer_steps: steps must be >= 0 (got %lld)", (long long)steps);
+    h->opt_steps = steps;
     return 0;
 }
 

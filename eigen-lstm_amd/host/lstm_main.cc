@@ -6,7 +6,8 @@
 //   lstm --data F --hidden N --seq S --batch B --lr LR [--epochs E] [--seed K] [--gpus G]
 //        [--windows W] [--sample C] [--lr-warmup-windows X] [--save PREFIX] [--load PREFIX]
 //        [--eval-file F] [--stride K] [--forget-bias V] [--test-percent F] [--test-every SEC] [--log PREFIX]
-//        [--fast-math] [--step-kernels] [--stable-softmax] [--clip-norm X] [--quiet]
+//        [--fast-math] [--step-kernels] [--stable-softmax] [--clip-norm X] [--optimizer adagrad|adam]
+//        [--adam-betas B1,B2] [--adam-eps E] [--weight-decay W] [--quiet]
 //
 // stdout follows the reference: "Read N bytes (file)" (R/lstm.cc:398), the carriage-return progress
 // line (OV/lstm_eigen_opt/lstm.cc:320-331), the epoch summary (R/lstm.cc:284-291: GFLOP uses 2^30,
@@ -24,11 +25,17 @@
 // X = 50*S, OV/lstm_eigen_class_CUDA/lstm.cc:364-367; 0 = the root file's behaviour).
 // --clip-norm X clips the global gradient norm to X before every Adagrad step (lstm_hip_set_grad_clip; inf = measure only)
 // and adds one line per epoch report: mean and max pre-clip norm and the number of clipped windows.
+// --optimizer adam trains with Adam / AdamW (lstm_hip_set_optimizer; --adam-betas, default 0.9,0.999, --adam-eps, default
+// 1e-8, --weight-decay, default 0) instead of Adagrad.  Its checkpoints carry PREFIX_adam_{m,v}_*.txt and
+// PREFIX_adam_steps.txt in place of the Adagrad memory; each rule loads only its own state.
 #include "../../include/lstm_hip.h"
 
-// referenced weakly: the program still links against a library without them and refuses --clip-norm there
+// referenced weakly: the program still links against a library without them and refuses --clip-norm / --optimizer adam there
 #pragma weak lstm_hip_set_grad_clip
 #pragma weak lstm_hip_get_grad_norms
+#pragma weak lstm_hip_set_optimizer
+#pragma weak lstm_hip_get_optimizer_steps
+#pragma weak lstm_hip_set_optimizer_steps
 #include "checkpoint.h"
 #include "matrix_io.h"
 #include "rng.h"
@@ -72,6 +79,8 @@ struct Options {
     bool last_step_loss = false; // report forward_loss of OV/lstm_eigen_class_CUDA/lstm.h:200-221 (last step, nats)
     bool last_step_bits = false; // ... or cuLSTM::calculate_loss, cu_lstm.h:203-215 (last step, bits)
     double clip_norm = 0.0;      // --clip-norm: 0 = off
+    bool adam = false;           // --optimizer adam
+    double beta1 = 0.9, beta2 = 0.999, adam_eps = 1e-8, weight_decay = 0.0;
 };
 
 [[noreturn]] void die(const std::string &m) {
@@ -151,9 +160,17 @@ bool load_cursors(const std::string &prefix, std::vector<uint64_t> &pos, size_t 
     return true;
 }
 
+double finite_number(const std::string &opt, const std::string &v) {
+    char *end = nullptr;
+    const double x = strtod(v.c_str(), &end);
+    if (end == v.c_str() || *end != '\0' || !std::isfinite(x)) die(opt + " needs a finite number, got " + v);
+    return x;
+}
+
 Options parse(int argc, char **argv) {
     Options o;
     std::vector<std::string> pos;
+    std::string adam_opt; // the last Adam option given (refused without --optimizer adam)
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto val = [&]() -> std::string {
@@ -191,6 +208,27 @@ Options parse(int argc, char **argv) {
             if (o.clip_norm > 0.0 && (lstm_hip_set_grad_clip == nullptr || lstm_hip_get_grad_norms == nullptr))
                 die("--clip-norm: the loaded liblstm_hip has no lstm_hip_set_grad_clip / lstm_hip_get_grad_norms");
         }
+        else if (a == "--optimizer") {
+            const std::string v = val();
+            if (v != "adagrad" && v != "adam") die("--optimizer needs adagrad or adam, got " + v);
+            o.adam = v == "adam";
+        } else if (a == "--adam-betas") {
+            const std::string v = val();
+            const size_t comma = v.find(',');
+            if (comma == std::string::npos) die("--adam-betas needs B1,B2, got " + v);
+            o.beta1 = finite_number(a, v.substr(0, comma));
+            o.beta2 = finite_number(a, v.substr(comma + 1));
+            if (o.beta1 < 0.0 || o.beta1 >= 1.0 || o.beta2 < 0.0 || o.beta2 >= 1.0) die("--adam-betas needs 0 <= B1, B2 < 1, got " + v);
+            adam_opt = a;
+        } else if (a == "--adam-eps") {
+            o.adam_eps = finite_number(a, val());
+            if (o.adam_eps <= 0.0) die("--adam-eps needs a number > 0");
+            adam_opt = a;
+        } else if (a == "--weight-decay") {
+            o.weight_decay = finite_number(a, val());
+            if (o.weight_decay < 0.0) die("--weight-decay needs a number >= 0");
+            adam_opt = a;
+        }
         else if (a == "--last-step-loss") o.last_step_loss = true;
         else if (a == "--last-step-loss-bits") o.last_step_bits = true;
         else if (a == "--quiet") o.quiet = true;
@@ -198,11 +236,17 @@ Options parse(int argc, char **argv) {
             printf("usage: lstm <text file> <hidden> <seq> <batch> <lr> [--epochs E --seed K --gpus G --windows W --sample C\n"
                    "            --lr-warmup-windows X --save PREFIX --load PREFIX --eval-file F --stride K --forget-bias V\n"
                    "            --test-percent F --test-every SEC --log PREFIX --last-step-loss --last-step-loss-bits --fast-math --step-kernels\n"
-                   "            --stable-softmax --clip-norm X --quiet]\n");
+                   "            --stable-softmax --clip-norm X --optimizer adagrad|adam --adam-betas B1,B2 --adam-eps E\n"
+                   "            --weight-decay W --quiet]\n");
             exit(0);
         } else if (a.rfind("--", 0) == 0) die("unknown option " + a);
         else pos.push_back(a);
     }
+    if (!adam_opt.empty() && !o.adam) die(adam_opt + " needs --optimizer adam");
+    if (o.adam && (lstm_hip_set_optimizer == nullptr || lstm_hip_get_optimizer_steps == nullptr ||
+                   lstm_hip_set_optimizer_steps == nullptr))
+        die("--optimizer adam: the loaded liblstm_hip has no lstm_hip_set_optimizer / lstm_hip_get_optimizer_steps / "
+            "lstm_hip_set_optimizer_steps");
     if (pos.size() > 0) o.data = pos[0];
     if (pos.size() > 1) o.N = atoi(pos[1].c_str());
     if (pos.size() > 2) o.S = atoi(pos[2].c_str());
@@ -233,6 +277,8 @@ int run_rank(const Options &o, int rank, int up, int down) {
     lstm_hip_t *h = nullptr;
     CK(lstm_hip_create(&cfg, &h));
     if (o.clip_norm > 0.0) CK(lstm_hip_set_grad_clip(h, o.clip_norm)); // (every rank: each steps on the same all-reduced norm)
+    if (o.adam) // (every rank: the same step with the same t on the all-reduced gradient)
+        CK(lstm_hip_set_optimizer(h, LSTM_HIP_OPT_ADAM, o.beta1, o.beta2, o.adam_eps, o.weight_decay));
     if (o.gpus > 1) {
         uint8_t id[LSTM_HIP_UNIQUE_ID_BYTES];
         if (lead) {
@@ -261,7 +307,17 @@ int run_rank(const Options &o, int rank, int up, int down) {
         } else if (lead) printf("fopen error: (%s_W.txt) -- keeping the random initialisation\n", o.load.c_str());
     }
     CK(lstm_hip_set_params(h, 0, P.data()));
-    if (!o.load.empty()) { // resume: Adagrad memory, when the checkpoint has it
+    if (!o.load.empty() && o.adam) { // resume: Adam's moments and step count, when the checkpoint has them (never _mem_*)
+        std::vector<float> m(np, 0.0f), v(np, 0.0f);
+        long long t = -1;
+        std::ifstream steps(o.load + "_adam_steps.txt");
+        if (steps && (steps >> t) && t >= 0 && load_params(o.load + "_adam_m", m, N, M) && load_params(o.load + "_adam_v", v, N, M)) {
+            CK(lstm_hip_set_params(h, 2, m.data()));
+            CK(lstm_hip_set_params(h, 3, v.data()));
+            CK(lstm_hip_set_optimizer_steps(h, t));
+            if (lead) printf("Loaded Adam state (t = %lld) from %s_adam_{m,v}_{W,U,Why,b,by}.txt\n", t, o.load.c_str());
+        }
+    } else if (!o.load.empty()) { // resume: Adagrad memory, when the checkpoint has it (never _adam_*)
         std::vector<float> mem(np, 0.0f);
         if (std::ifstream(o.load + "_mem_W.txt").good() && load_params(o.load + "_mem", mem, N, M)) {
             CK(lstm_hip_set_params(h, 2, mem.data()));
@@ -417,7 +473,16 @@ int run_rank(const Options &o, int rank, int up, int down) {
                 save_params(o.save, P, N, M);
                 std::vector<float> mem(np);
                 CK(lstm_hip_get_params(h, 2, mem.data()));
-                save_params(o.save + "_mem", mem, N, M, 9);
+                if (o.adam) { // (no _mem_* files: an Adagrad run would take m, which can be negative, as its memory)
+                    save_params(o.save + "_adam_m", mem, N, M, 9);
+                    CK(lstm_hip_get_params(h, 3, mem.data()));
+                    save_params(o.save + "_adam_v", mem, N, M, 9);
+                    int64_t t = 0;
+                    CK(lstm_hip_get_optimizer_steps(h, &t));
+                    std::ofstream f(o.save + "_adam_steps.txt");
+                    if (!(f << (long long)t << "\n")) die("cannot write " + o.save + "_adam_steps.txt");
+                } else
+                    save_params(o.save + "_mem", mem, N, M, 9);
                 std::vector<uint64_t> all(o.B); // every stream has advanced by the same number of bytes
                 const uint64_t span = (uint64_t)(length - S), adv = (uint64_t)done_windows * (uint64_t)o.stride;
                 for (int b = 0; b < o.B; b++) all[b] = (uint64_t)S + ((start_all[b] - S) + adv) % span;
@@ -426,7 +491,8 @@ int run_rank(const Options &o, int rank, int up, int down) {
                 for (int b = 0; b < Bl; b++)
                     if (mine[b] != all[(size_t)rank * Bl + b]) die("cursor bookkeeping out of step with the library");
                 save_cursors(o.save, all);
-                printf("Saved parameters to %s_{W,U,Why,b,by}.txt (+ _mem_*, _cursors)\n", o.save.c_str());
+                printf("Saved parameters to %s_{W,U,Why,b,by}.txt (+ %s, _cursors)\n", o.save.c_str(),
+                       o.adam ? "_adam_m_*, _adam_v_*, _adam_steps" : "_mem_*");
             }
             fflush(stdout);
         }

@@ -30,6 +30,8 @@ UNIQUE_ID_BYTES = 128
 VOCAB = 256
 
 P_PARAMS, P_GRADS, P_MEM = 0, 1, 2
+P_ADAM_V = 3  # Adam's second moment (P_MEM is its first moment on an Adam handle)
+OPT_ADAGRAD, OPT_ADAM = 0, 1  # update rules of lstm_hip_set_optimizer (include/lstm_hip.h)
 
 
 class LstmHipError(RuntimeError):
@@ -53,7 +55,8 @@ SYMBOLS = [
     "lstm_hip_get_window", "lstm_hip_train_windows", "lstm_hip_set_global_batch", "lstm_hip_set_loss_mode", "lstm_hip_set_stride", "lstm_hip_eval_bits",
     "lstm_hip_sample", "lstm_hip_generate", "lstm_hip_synchronize", "lstm_hip_set_profiling", "lstm_hip_kernel_stat_count",
     "lstm_hip_kernel_stat", "lstm_hip_reset_kernel_stats", "lstm_hip_device_info", "lstm_hip_debug_stamps",
-    "lstm_hip_set_grad_clip", "lstm_hip_get_grad_norms",
+    "lstm_hip_set_grad_clip", "lstm_hip_get_grad_norms", "lstm_hip_set_optimizer", "lstm_hip_get_optimizer_steps",
+    "lstm_hip_set_optimizer_steps",
 ]
 
 
@@ -215,6 +218,23 @@ class Lstm:
         out = np.zeros(k, np.float64)
         _chk(self.lib.lstm_hip_get_grad_norms(self._h, _ptr(out, C.c_double), C.c_int64(k)))
         return out
+
+    # ---- the update rule (lstm_hip_set_optimizer) ----------------------------------------------
+    def set_optimizer(self, kind, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0):
+        """OPT_ADAGRAD (the default rule) or OPT_ADAM (AdamW; weight_decay 0: plain Adam).  A new kind zeroes the
+        optimizer state and the step count; the same kind again keeps them."""
+        if kind == OPT_ADAGRAD:
+            beta1 = beta2 = eps = weight_decay = 0.0
+        _chk(self.lib.lstm_hip_set_optimizer(self._h, C.c_int32(kind), C.c_double(beta1), C.c_double(beta2), C.c_double(eps),
+                                             C.c_double(weight_decay)))
+
+    def optimizer_steps(self):
+        out = C.c_int64()
+        _chk(self.lib.lstm_hip_get_optimizer_steps(self._h, C.byref(out)))
+        return out.value
+
+    def set_optimizer_steps(self, t):
+        _chk(self.lib.lstm_hip_set_optimizer_steps(self._h, C.c_int64(t)))
 
     # ---- data-parallel -----------------------------------------------------------------------
     def comm_init(self, unique_id, nranks, rank):

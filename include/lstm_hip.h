@@ -98,7 +98,8 @@ const char *lstm_hip_last_error(void);
 size_t lstm_hip_param_count(int32_t N, int32_t M);
 
 /* ---- copy_parameters_to_device / copy_parameters_to_host, cu_lstm.h:307-325.
- *      `which`: 0 = parameters p, 1 = gradients d, 2 = Adagrad memory m.  Host block layout
+ *      `which`: 0 = parameters p, 1 = gradients d, 2 = Adagrad memory m (Adam: first moment), 3 = Adam's second moment
+ *      (lstm_hip_set_optimizer).  Host block layout
  *      [W (4N x M) | U (4N x N) | b (4N) | Why (M x N) | by (M)], each column-major. */
 int lstm_hip_set_params(lstm_hip_t *h, int which, const float *host_block);
 int lstm_hip_get_params(lstm_hip_t *h, int which, float *host_block);
@@ -149,6 +150,32 @@ int lstm_hip_set_grad_clip(lstm_hip_t *h, double max_norm);
 /* the pre-clip norms of the Adagrad steps of the last lstm_hip_adagrad (1) or lstm_hip_train_windows (count) call,
  * oldest first; n <= that number (else LSTM_HIP_EINVAL); LSTM_HIP_ESTATE when clipping was off for that call */
 int lstm_hip_get_grad_norms(lstm_hip_t *h, double *norms, int64_t n);
+
+/* ---- the update rule of lstm_hip_adagrad and of every window of lstm_hip_train_windows (the name is kept for the seam)
+ *   LSTM_HIP_OPT_ADAGRAD  the default above; beta1, beta2, eps and weight_decay must all be 0
+ *   LSTM_HIP_OPT_ADAM     Adam with decoupled weight decay (torch.optim.AdamW, single-tensor form; weight_decay 0: plain
+ *                         Adam); needs 0 <= beta1 < 1, 0 <= beta2 < 1, eps > 0, weight_decay >= 0, all finite.
+ *                         At step number t (1-based, counted per handle), with d' = d * coef when clipping scales the step:
+ *                           p <- p * (1 - lr*wd)                                 (only when wd > 0)
+ *                           m <- m + (1 - beta1) * (d' - m)
+ *                           v <- beta2 * v + (1 - beta2) * d'^2
+ *                           p <- p - (lr / (1 - beta1^t)) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
+ *                         The per-step scalars (lr / (1 - beta1^t), sqrt(1 - beta2^t), 1 - lr*wd, 1 - beta1, beta2,
+ *                         1 - beta2, eps) are computed in double on the host and narrowed to float; the elementwise work,
+ *                         m and v are fp32.  The decay covers the whole flat block, biases included.  Every step counts,
+ *                         lr = 0 steps included (t advances, m and v are updated).
+ * Anything else is LSTM_HIP_EINVAL.  A new kind zeroes the optimizer state (which = 2, and 3 for Adam) and the step count;
+ * the same kind again keeps both and takes the new numbers (e.g. a new weight decay mid-run).  State blocks of
+ * lstm_hip_set_params / lstm_hip_get_params: which = 2 is Adagrad's memory or Adam's first moment m, which = 3 Adam's
+ * second moment v (LSTM_HIP_ESTATE on a handle that is not on Adam).  A padded handle keeps m and v at the padded width
+ * with zero padding, as the memory.  With a communicator every rank applies the same step, with the same t, to the
+ * all-reduced gradient.  The step counter advances once per update launched, for either kind; in one train_windows call
+ * every window has its own t.  steps >= 0 for set. */
+#define LSTM_HIP_OPT_ADAGRAD 0
+#define LSTM_HIP_OPT_ADAM 1
+int lstm_hip_set_optimizer(lstm_hip_t *h, int32_t kind, double beta1, double beta2, double eps, double weight_decay);
+int lstm_hip_get_optimizer_steps(lstm_hip_t *h, int64_t *steps);
+int lstm_hip_set_optimizer_steps(lstm_hip_t *h, int64_t steps);
 
 /* ---- data-parallel exchange (new; the reference is single-device).  One SUM all-reduce of the
  *      flat gradient block per window over RCCL; every rank then applies the identical Adagrad step.
