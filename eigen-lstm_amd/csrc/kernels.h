@@ -325,4 +325,33 @@ struct GenHeadArgs {
 void gen_head(const GenHeadArgs &a, long long t, bool stable, hipStream_t st); // stable: LSTM_HIP_STABLE_SOFTMAX
 int gen_head_group(int N, int streams); // streams per workgroup of gen_head
 
+// ---- model-driven range coder (lstm_hip_encode / lstm_hip_decode): per step code_head on the state
+// after t inputs (byte t of every stream with more than t bytes is coded), then fwd_step over all streams with x_next.
+// Stream s owns text[text_off[s] .. text_off[s+1]) and code[code_base[s] .. code_base[s+1]): the encoder never writes past
+// the end of its range, the decoder reads 0 there.
+constexpr uint32_t CODER_TOTAL_BITS = 16;   // totals <= 2^16 (the carryless coder's BOT)
+constexpr uint32_t CODER_SCALE = 65024;     // q_m = 1 + (uint32)(p_m * 65024.0f): sum <= 256 + 65025 < 2^16
+constexpr uint32_t CODE_ERR_TOTAL = 1u;     // a frequency total above 2^16 (the quantisation bound broken)
+constexpr uint32_t CODE_ERR_BOUND = 2u;     // a code would pass its stream's range (lstm_hip_code_bound broken)
+struct CoderState {                         // per stream, in device memory between steps
+    uint32_t low, range, code, pad;
+    uint64_t pos;                           // code bytes written (encoder) / read (decoder) so far
+};
+struct CodeHeadArgs {
+    const float *Why, *by;
+    const float *H;             // state after t inputs, [streams][N]
+    const uint64_t *text_off;   // streams + 1
+    uint8_t *text;              // encoder: read; decoder: written
+    uint8_t *code;              // encoder: written; decoder: read
+    const uint64_t *code_base;  // streams + 1: each stream's code range
+    uint64_t *code_len;         // encoder: each stream's code length, written after its flush
+    CoderState *state;          // [streams]
+    double *bits;               // encoder: sum of -log2(freq / total) per stream, accumulated (null: not kept)
+    uint32_t *trace;            // encoder: (cum, freq, total) per coded byte, in text order (null: not kept)
+    int32_t *x_next;            // the next input of every stream (-1: none)
+    uint32_t *err;              // OR of CODE_ERR_*
+    int N, streams, decode;
+};
+void code_head(const CodeHeadArgs &a, long long t, hipStream_t st);
+
 } // namespace lstmk

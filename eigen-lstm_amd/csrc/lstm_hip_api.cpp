@@ -51,12 +51,13 @@ enum KernelId {
     K_DU_HALVES, // the two column halves of the dU product (LSTM_HIP_DU_SPLIT; communicator loop only, never timed)
     K_GRAD_SUMSQ, K_GRAD_NORM, // global-norm clipping (lstm_hip_set_grad_clip): partial sums of d^2, then norm and coefficient
     K_ADAM,                    // the update launch on a handle set to LSTM_HIP_OPT_ADAM (K_ADAGRAD's launch with the Adam rule)
+    K_CODE_HEAD,               // one step of the range coder (lstm_hip_encode / lstm_hip_decode)
     K_COUNT
 };
 const char *const kKernelNames[K_COUNT] = {
     "pack_U", "fwd_step", "gemm_Y", "softmax_loss_dy", "loss_reduce", "gemm_DHy", "bwd_step", "gemm_dWhy", "gemm_dU",
     "dW_db", "loss_dby", "adagrad", "slide", "allreduce", "fwd_persistent", "bwd_persistent", "gen_head", "side_sums",
-    "gemm_dU_halves", "grad_sumsq", "grad_norm", "adam"};
+    "gemm_dU_halves", "grad_sumsq", "grad_norm", "adam", "code_head"};
 
 // ---- RCCL, loaded on first use so single-GPU users never touch it --------------------------
 struct UniqueId {
@@ -1386,6 +1387,19 @@ int lstm_hip_sample(lstm_hip_t *h, float *h0, float *c0, const double *u, int32_
     return 0;
 }
 
+// the generator's and the coder's working memory: one allocation on the handle, grown to the largest call
+static int reserve_gen_scratch(lstm_hip_t *h, size_t bytes) {
+    if (bytes > h->gen_scratch_bytes) { // (kept between calls: hipFree waits for the whole device)
+        HIP_TRY(hipStreamSynchronize(h->st));
+        if (h->gen_scratch) HIP_TRY(hipFree(h->gen_scratch));
+        h->gen_scratch = nullptr;
+        h->gen_scratch_bytes = 0;
+        HIP_TRY(hipMalloc((void **)&h->gen_scratch, bytes));
+        h->gen_scratch_bytes = bytes;
+    }
+    return 0;
+}
+
 // Batched, prompted generation and per-text scoring (include/lstm_hip.h).  All streams advance together: per step one
 // gen_head launch (logits, prompt bits, the next input of every stream, final states) and one k_fwd_step over all streams,
 // from the fp32 master parameters P and a fragment image of U made for this call.  Nothing of the training state is
@@ -1431,14 +1445,7 @@ int lstm_hip_generate(lstm_hip_t *h, int32_t streams, const uint8_t *prompts, co
                  o_off = piece(prompt_off ? sizeof(uint64_t) * (streams + 1) : 0), o_p = piece(total),
                  o_u = piece(count > 0 && temperature >= (double)FLT_MIN ? sizeof(double) * nd : 0), o_out = piece(nd),
                  o_bits = piece(sizeof(double) * streams);
-    if (bytes > h->gen_scratch_bytes) { // (kept between calls: hipFree waits for the whole device)
-        HIP_TRY(hipStreamSynchronize(h->st));
-        if (h->gen_scratch) HIP_TRY(hipFree(h->gen_scratch));
-        h->gen_scratch = nullptr;
-        h->gen_scratch_bytes = 0;
-        HIP_TRY(hipMalloc((void **)&h->gen_scratch, bytes));
-        h->gen_scratch_bytes = bytes;
-    }
+    if (int rc = reserve_gen_scratch(h, bytes)) return rc;
     char *base = h->gen_scratch;
     float4 *Ufwd = reinterpret_cast<float4 *>(base + o_U);
     float *H = reinterpret_cast<float *>(base + o_H), *Cs = reinterpret_cast<float *>(base + o_C);
@@ -1515,6 +1522,156 @@ int lstm_hip_generate(lstm_hip_t *h, int32_t streams, const uint8_t *prompts, co
     }
     HIP_TRY(hipStreamSynchronize(h->st));
     return 0;
+}
+
+// ---- arithmetic coding of bytes with the model (include/lstm_hip.h)
+uint32_t lstm_hip_coder_version(void) { return 1; }
+
+size_t lstm_hip_code_bound(uint64_t len) {
+    if (len == 0) return 0;
+    if (len > (SIZE_MAX - 4) / 3) return SIZE_MAX;
+    return (size_t)(3 * len + 4);
+}
+
+// offsets of `streams` streams: off[0] == 0, never decreasing
+static int check_offsets(const char *what, const char *name, const uint64_t *off, int32_t streams) {
+    if (!off) return fail(LSTM_HIP_EINVAL, "%s: null %s", what, name);
+    if (off[0] != 0) return fail(LSTM_HIP_EINVAL, "%s: %s[0] must be 0 (got %llu)", what, name, (unsigned long long)off[0]);
+    for (int s = 0; s < streams; s++)
+        if (off[s + 1] < off[s])
+            return fail(LSTM_HIP_EINVAL, "%s: %s decreases at stream %d (%llu < %llu)", what, name, s,
+                        (unsigned long long)off[s + 1], (unsigned long long)off[s]);
+    return 0;
+}
+
+// Both directions: per step one code_head launch and one k_fwd_step over all streams (the generator's loop), from the fp32
+// master parameters P and a fragment image of U made for this call, in the handle's generator scratch memory.  Encoder:
+// `text` in, the streams' codes (at lstm_hip_code_bound offsets) out; decoder: `code` at `code_off` in, `text` out.
+static int run_coder(lstm_hip_t *h, bool decode, int32_t streams, const uint64_t *text_off, const uint8_t *text_in,
+                     uint8_t *text_out, const uint8_t *code_in, const uint64_t *code_off_in, uint8_t *code_out,
+                     uint64_t *code_off_out, double *bits, uint32_t *trace) {
+    const int N = h->cfg.N;
+    const uint64_t total = text_off[streams];
+    uint64_t max_len = 0;
+    for (int s = 0; s < streams; s++) max_len = std::max<uint64_t>(max_len, text_off[s + 1] - text_off[s]);
+    std::vector<uint64_t> base(streams + 1, 0); // each stream's code range on the device
+    if (decode) base.assign(code_off_in, code_off_in + streams + 1);
+    else
+        for (int s = 0; s < streams; s++) base[s + 1] = base[s] + lstm_hip_code_bound(text_off[s + 1] - text_off[s]);
+    const uint64_t code_bytes = base[streams];
+    const size_t n = (size_t)N * streams;
+
+    size_t bytes = 0;
+    auto piece = [&](size_t b) {
+        const size_t o = bytes;
+        bytes += (b + 255) / 256 * 256;
+        return o;
+    };
+    const size_t o_U = piece(sizeof(float) * 4 * (size_t)N * N), o_H = piece(sizeof(float) * 2 * n), o_C = piece(sizeof(float) * 2 * n),
+                 o_G = piece(sizeof(float) * 4 * n), o_x = piece(sizeof(int32_t) * streams),
+                 o_toff = piece(sizeof(uint64_t) * (streams + 1)), o_base = piece(sizeof(uint64_t) * (streams + 1)),
+                 o_text = piece(total), o_code = piece(code_bytes), o_st = piece(sizeof(CoderState) * streams),
+                 o_len = piece(sizeof(uint64_t) * streams), o_bits = piece(sizeof(double) * streams),
+                 o_tr = piece(trace ? sizeof(uint32_t) * 3 * total : 0), o_err = piece(sizeof(uint32_t));
+    if (int rc = reserve_gen_scratch(h, bytes)) return rc;
+    char *b0 = h->gen_scratch;
+    float4 *Ufwd = reinterpret_cast<float4 *>(b0 + o_U);
+    float *H = reinterpret_cast<float *>(b0 + o_H), *Cs = reinterpret_cast<float *>(b0 + o_C), *G = reinterpret_cast<float *>(b0 + o_G);
+    CodeHeadArgs a{};
+    a.Why = h->P + h->pl.Why;
+    a.by = h->P + h->pl.by;
+    a.text_off = reinterpret_cast<uint64_t *>(b0 + o_toff);
+    a.text = reinterpret_cast<uint8_t *>(b0 + o_text);
+    a.code = reinterpret_cast<uint8_t *>(b0 + o_code);
+    a.code_base = reinterpret_cast<uint64_t *>(b0 + o_base);
+    a.code_len = reinterpret_cast<uint64_t *>(b0 + o_len);
+    a.state = reinterpret_cast<CoderState *>(b0 + o_st);
+    a.bits = decode ? nullptr : reinterpret_cast<double *>(b0 + o_bits);
+    a.trace = trace && !decode ? reinterpret_cast<uint32_t *>(b0 + o_tr) : nullptr;
+    a.x_next = reinterpret_cast<int32_t *>(b0 + o_x);
+    a.err = reinterpret_cast<uint32_t *>(b0 + o_err);
+    a.N = N;
+    a.streams = streams;
+    a.decode = decode ? 1 : 0;
+
+    HIP_TRY(hipMemsetAsync(H, 0, sizeof(float) * n, h->st)); // every stream starts from h = c = 0 (padding rows too)
+    HIP_TRY(hipMemsetAsync(Cs, 0, sizeof(float) * n, h->st));
+    HIP_TRY(hipMemcpyAsync(const_cast<uint64_t *>(a.text_off), text_off, sizeof(uint64_t) * (streams + 1), hipMemcpyHostToDevice, h->st));
+    HIP_TRY(hipMemcpyAsync(const_cast<uint64_t *>(a.code_base), base.data(), sizeof(uint64_t) * (streams + 1), hipMemcpyHostToDevice, h->st));
+    if (!decode && total) HIP_TRY(hipMemcpyAsync(a.text, text_in, total, hipMemcpyHostToDevice, h->st));
+    if (decode && code_bytes) HIP_TRY(hipMemcpyAsync(a.code, code_in, code_bytes, hipMemcpyHostToDevice, h->st));
+    HIP_TRY(hipMemsetAsync(a.code_len, 0, sizeof(uint64_t) * streams, h->st)); // (empty streams: no code)
+    HIP_TRY(hipMemsetAsync(b0 + o_bits, 0, sizeof(double) * streams, h->st));
+    HIP_TRY(hipMemsetAsync(a.err, 0, sizeof(uint32_t), h->st));
+    if (max_len) RUN(K_PACK_U, pack_U(h->P + h->pl.U, Ufwd, nullptr, N, h->st));
+
+    const bool fast = (h->cfg.flags & LSTM_HIP_FAST_MATH) != 0;
+    int cur = 0;
+    for (long long t = 0; t < (long long)max_len; t++) {
+        a.H = H + cur * n;
+        RUN(K_CODE_HEAD, code_head(a, t, h->st));
+        if (t + 1 == (long long)max_len) break;
+        RUN(K_FWD_STEP, fwd_step(Ufwd, h->P + h->pl.W, h->P + h->pl.b, H + cur * n, Cs + cur * n, H + (cur ^ 1) * n,
+                                 Cs + (cur ^ 1) * n, G, a.x_next, N, streams, fast, h->st));
+        cur ^= 1;
+    }
+
+    uint32_t err = 0;
+    std::vector<uint64_t> len(streams);
+    HIP_TRY(hipMemcpyAsync(&err, a.err, sizeof(uint32_t), hipMemcpyDeviceToHost, h->st));
+    if (decode) {
+        if (total) HIP_TRY(hipMemcpyAsync(text_out, a.text, total, hipMemcpyDeviceToHost, h->st));
+    } else {
+        HIP_TRY(hipMemcpyAsync(len.data(), a.code_len, sizeof(uint64_t) * streams, hipMemcpyDeviceToHost, h->st));
+        if (code_bytes) HIP_TRY(hipMemcpyAsync(code_out, a.code, code_bytes, hipMemcpyDeviceToHost, h->st));
+        if (bits) HIP_TRY(hipMemcpyAsync(bits, a.bits, sizeof(double) * streams, hipMemcpyDeviceToHost, h->st));
+        if (trace && total) HIP_TRY(hipMemcpyAsync(trace, a.trace, sizeof(uint32_t) * 3 * total, hipMemcpyDeviceToHost, h->st));
+    }
+    HIP_TRY(hipStreamSynchronize(h->st));
+    if (err & CODE_ERR_TOTAL) return fail(LSTM_HIP_EINVAL, "%s: a frequency total passed 2^16 (the quantisation bound)", decode ? "decode" : "encode");
+    if (err & CODE_ERR_BOUND) return fail(LSTM_HIP_EINVAL, "%s: a code passed lstm_hip_code_bound", decode ? "decode" : "encode");
+    if (!decode) { // the codes back to back: move each down from its bound-sized range (memmove: ranges overlap in order)
+        code_off_out[0] = 0;
+        for (int s = 0; s < streams; s++) {
+            if (len[s] > base[s + 1] - base[s]) return fail(LSTM_HIP_EINVAL, "encode: stream %d's code passed its bound", s);
+            if (len[s]) memmove(code_out + code_off_out[s], code_out + base[s], len[s]);
+            code_off_out[s + 1] = code_off_out[s] + len[s];
+        }
+    }
+    return 0;
+}
+
+int lstm_hip_encode(lstm_hip_t *h, int32_t streams, const uint8_t *text, const uint64_t *text_off, uint8_t *code,
+                    uint64_t code_cap, uint64_t *code_off, double *bits, uint32_t *trace) {
+    CHECK(h);
+    if (streams < 1 || streams > 4096) return fail(LSTM_HIP_EINVAL, "encode: streams must be in [1, 4096] (got %d)", streams);
+    if (int rc = check_offsets("encode", "text_off", text_off, streams)) return rc;
+    if (!code_off) return fail(LSTM_HIP_EINVAL, "encode: null code_off");
+    if (text_off[streams] > 0 && !text) return fail(LSTM_HIP_EINVAL, "encode: null text with %llu bytes to code", (unsigned long long)text_off[streams]);
+    uint64_t need = 0;
+    for (int s = 0; s < streams; s++) {
+        const size_t b = lstm_hip_code_bound(text_off[s + 1] - text_off[s]);
+        if (b == SIZE_MAX || need > UINT64_MAX - b) return fail(LSTM_HIP_EINVAL, "encode: text too long");
+        need += b;
+    }
+    if (code_cap < need)
+        return fail(LSTM_HIP_EINVAL, "encode: code_cap %llu is below the bound %llu (sum of lstm_hip_code_bound)",
+                    (unsigned long long)code_cap, (unsigned long long)need);
+    if (need > 0 && !code) return fail(LSTM_HIP_EINVAL, "encode: null code");
+    if (h->cfg.N > 16384) return fail(LSTM_HIP_EINVAL, "encode: hidden width %d above 16384", h->cfg.N);
+    return run_coder(h, false, streams, text_off, text, nullptr, nullptr, nullptr, code, code_off, bits, trace);
+}
+
+int lstm_hip_decode(lstm_hip_t *h, int32_t streams, const uint8_t *code, const uint64_t *code_off, const uint64_t *text_off,
+                    uint8_t *text) {
+    CHECK(h);
+    if (streams < 1 || streams > 4096) return fail(LSTM_HIP_EINVAL, "decode: streams must be in [1, 4096] (got %d)", streams);
+    if (int rc = check_offsets("decode", "code_off", code_off, streams)) return rc;
+    if (int rc = check_offsets("decode", "text_off", text_off, streams)) return rc;
+    if (code_off[streams] > 0 && !code) return fail(LSTM_HIP_EINVAL, "decode: null code with %llu code bytes", (unsigned long long)code_off[streams]);
+    if (text_off[streams] > 0 && !text) return fail(LSTM_HIP_EINVAL, "decode: null text with %llu bytes to decode", (unsigned long long)text_off[streams]);
+    if (h->cfg.N > 16384) return fail(LSTM_HIP_EINVAL, "decode: hidden width %d above 16384", h->cfg.N);
+    return run_coder(h, true, streams, text_off, nullptr, text, code, code_off, nullptr, nullptr, nullptr, nullptr);
 }
 
 int lstm_hip_debug_stamps(lstm_hip_t *h, uint64_t *out, size_t count) {

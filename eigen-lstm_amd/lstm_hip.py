@@ -56,7 +56,7 @@ SYMBOLS = [
     "lstm_hip_sample", "lstm_hip_generate", "lstm_hip_synchronize", "lstm_hip_set_profiling", "lstm_hip_kernel_stat_count",
     "lstm_hip_kernel_stat", "lstm_hip_reset_kernel_stats", "lstm_hip_device_info", "lstm_hip_debug_stamps",
     "lstm_hip_set_grad_clip", "lstm_hip_get_grad_norms", "lstm_hip_set_optimizer", "lstm_hip_get_optimizer_steps",
-    "lstm_hip_set_optimizer_steps",
+    "lstm_hip_set_optimizer_steps", "lstm_hip_coder_version", "lstm_hip_code_bound", "lstm_hip_encode", "lstm_hip_decode",
 ]
 
 
@@ -72,12 +72,39 @@ def load_library():
     lib.lstm_hip_last_error.restype = C.c_char_p
     lib.lstm_hip_param_count.restype = C.c_size_t
     lib.lstm_hip_param_count.argtypes = [C.c_int32, C.c_int32]
+    lib.lstm_hip_coder_version.restype = C.c_uint32
+    lib.lstm_hip_coder_version.argtypes = []
+    lib.lstm_hip_code_bound.restype = C.c_size_t
+    lib.lstm_hip_code_bound.argtypes = [C.c_uint64]
     _lib = lib
     return lib
 
 
 def param_count(N, M=VOCAB):
     return load_library().lstm_hip_param_count(N, M)
+
+
+def coder_version():
+    """lstm_hip_coder_version: changes whenever the arithmetic that feeds the range coder changes (a code decodes only with
+    the same version, parameters and LSTM_HIP_FAST_MATH setting)."""
+    return int(load_library().lstm_hip_coder_version())
+
+
+def code_bound(n):
+    """lstm_hip_code_bound: the largest code a stream of n bytes can have (0 for n = 0, else 3n + 4)."""
+    return int(load_library().lstm_hip_code_bound(int(n)))
+
+
+def _bytes_list(texts):
+    return [np.frombuffer(bytes(p), np.uint8) if isinstance(p, (bytes, bytearray)) else np.asarray(p, np.uint8).ravel()
+            for p in texts]
+
+
+def _offsets(parts):
+    off = np.zeros(len(parts) + 1, np.uint64)
+    off[1:] = np.cumsum([q.size for q in parts])
+    data = np.ascontiguousarray(np.concatenate(parts) if off[-1] > 0 else np.zeros(1, np.uint8))
+    return data, off
 
 
 def _chk(rc):
@@ -331,6 +358,39 @@ class Lstm:
                                         C.c_int32(count), _ptr(out, C.c_uint8), _ptr(bits, C.c_double) if score else None,
                                         _ptr(h), _ptr(c)))
         return out, bits, h, c
+
+    def encode(self, texts, trace=False):
+        """lstm_hip_encode: each of `texts` (bytes or uint8 arrays) is one stream, coded from a zero state.  Returns
+        (codes: list of bytes, bits: float64 [streams] -- the ideal length under the quantised model) and, with trace,
+        a uint32 [total bytes, 3] array of (cum, freq, total) per coded byte in text order."""
+        parts = _bytes_list(texts)
+        streams = len(parts)
+        data, off = _offsets(parts)
+        cap = sum(code_bound(q.size) for q in parts)
+        code = np.zeros(max(cap, 1), np.uint8)
+        code_off = np.zeros(streams + 1, np.uint64)
+        bits = np.zeros(streams, np.float64)
+        tr = np.zeros((max(int(off[-1]), 1), 3), np.uint32) if trace else None
+        _chk(self.lib.lstm_hip_encode(self._h, C.c_int32(streams), _ptr(data, C.c_uint8), _ptr(off, C.c_uint64),
+                                      _ptr(code, C.c_uint8), C.c_uint64(cap), _ptr(code_off, C.c_uint64),
+                                      _ptr(bits, C.c_double), _ptr(tr, C.c_uint32) if trace else None))
+        codes = [code[int(code_off[s]):int(code_off[s + 1])].tobytes() for s in range(streams)]
+        if trace:
+            return codes, bits, tr[:int(off[-1])]
+        return codes, bits
+
+    def decode(self, codes, lengths):
+        """lstm_hip_decode: stream s decodes `lengths[s]` bytes from codes[s].  Returns a list of bytes."""
+        parts = _bytes_list(codes)
+        streams = len(parts)
+        assert len(lengths) == streams, (len(lengths), streams)
+        data, code_off = _offsets(parts)
+        text_off = np.zeros(streams + 1, np.uint64)
+        text_off[1:] = np.cumsum([int(n) for n in lengths])
+        text = np.zeros(max(int(text_off[-1]), 1), np.uint8)
+        _chk(self.lib.lstm_hip_decode(self._h, C.c_int32(streams), _ptr(data, C.c_uint8), _ptr(code_off, C.c_uint64),
+                                      _ptr(text_off, C.c_uint64), _ptr(text, C.c_uint8)))
+        return [text[int(text_off[s]):int(text_off[s + 1])].tobytes() for s in range(streams)]
 
     def debug_stamps(self):
         out = np.zeros((4, self.S, 16), np.uint64)  # [fwd wg0, fwd wg1, bwd wg0, bwd wg1][step][slot]

@@ -245,6 +245,40 @@ int lstm_hip_generate(lstm_hip_t *h, int32_t streams, const uint8_t *prompts, co
                       const float *h0, const float *c0, double temperature, const double *u, int32_t count,
                       uint8_t *out, double *bits, float *h_out, float *c_out);
 
+/* ---- arithmetic coding of bytes with the model.  Stream s is text[text_off[s] .. text_off[s+1]),
+ *      1 <= streams <= 4096, each coded on its own from h = c = 0 (empty streams allowed: their code is empty).
+ *        which bytes   EVERY byte, the first one included: byte j is coded with the distribution of the state after inputs
+ *                      0..j-1 (for j = 0 the zero state, so z = by).  Unlike lstm_hip_eval_bits and the prompt bits of
+ *                      lstm_hip_generate, which never score byte 0.
+ *        distribution  z = Why*h + by summed as lstm_hip_generate sums it (sequentially in k, no contraction), then
+ *                      p_m = expf(z_m - max z) / sum_k expf(z_k - max z): ALWAYS max-shifted, whatever
+ *                      LSTM_HIP_STABLE_SOFTMAX says.  Only the fp32 parameters are read (a bf16 handle codes as an fp32 one);
+ *                      LSTM_HIP_FAST_MATH applies to the recurrence as in lstm_hip_generate.
+ *        quantisation  q_m = 1 + (uint32)(p_m * 65024.0f) (truncated), T = sum_m q_m (256 <= T <= 65281 < 2^16),
+ *                      cum_m = sum_{k<m} q_k.  Every byte keeps q >= 1, so any input can be coded.
+ *        coder         the carryless 32-bit range coder (Subbotin: TOP = 2^24, BOT = 2^16), 4-byte flush; a code never
+ *                      rewrites a byte it has written.  The decoder reads 0 for every byte past the end of its stream's
+ *                      code and never reads outside it.
+ *      code_bound(len) = 0 for len = 0, else 3*len + 4: the proven worst case of a stream's code (SIZE_MAX on overflow).
+ *      A code decodes only with the same coder version (lstm_hip_coder_version, bumped whenever the logits, the softmax,
+ *      the quantisation or the coder change), the same parameters and the same LSTM_HIP_FAST_MATH setting.
+ *      Nothing of the handle is read or written except P (as lstm_hip_generate): gradients, optimizer state and step count,
+ *      window, cursors, carry, loss mode and clip setting stay as they are.  Working memory stays with the handle.
+ *      LSTM_HIP_EINVAL: streams outside 1..4096, offsets missing, not starting at 0 or decreasing, a null buffer where bytes
+ *      are due, code_cap below the bound; and (never expected) a frequency total above 2^16 or a code past its bound on
+ *      the device, in which case the call fails instead of returning a corrupt code. */
+uint32_t lstm_hip_coder_version(void);
+size_t lstm_hip_code_bound(uint64_t len);
+/* code: code_cap >= sum_s lstm_hip_code_bound(len_s) bytes; the codes are written back to back and code_off[0..streams]
+ * (out) delimits them.  bits (may be NULL): per stream, sum over its bytes of -log2(q/T) in double (the ideal length under
+ * the quantised model).  trace (may be NULL): 3 uint32 per coded byte, in text order: cum, freq (= q), total (= T). */
+int lstm_hip_encode(lstm_hip_t *h, int32_t streams, const uint8_t *text, const uint64_t *text_off, uint8_t *code,
+                    uint64_t code_cap, uint64_t *code_off, double *bits, uint32_t *trace);
+/* code[code_off[s] .. code_off[s+1]) is stream s's code; text_off gives each stream's decoded length (the lengths belong to
+ * the container, not to the code) and where it goes in text.  A truncated code decodes to the requested length. */
+int lstm_hip_decode(lstm_hip_t *h, int32_t streams, const uint8_t *code, const uint64_t *code_off, const uint64_t *text_off,
+                    uint8_t *text);
+
 /* ---- measurement.  With profiling on, every kernel launch is bracketed by HIP events on the
  *      handle's stream and per-kernel totals accumulate. */
 int lstm_hip_synchronize(lstm_hip_t *h);
