@@ -354,4 +354,25 @@ struct CodeHeadArgs {
 };
 void code_head(const CodeHeadArgs &a, long long t, hipStream_t st);
 
+// ---- adaptive coding (lstm_hip_encode_adaptive / lstm_hip_decode_adaptive): the training window of
+// block k, built from the coder's device text buffer.  With L = S - 1 and e_j = byte j of a stream (empty for j < 0), row t of
+// the window holds target e_{kL+t-1} and input e_{kL+t-2}: what slide_window leaves after k + 1 slides of stride L from an
+// empty window with the stream's cursor at its first byte.  Flat xi / ti and the rings (head = 0) are both written; column
+// S-1 of H and C moves to column 0 (16-byte accesses).  Workgroup 0 also folds the ideal bits coded since the last fold into
+// *block_bits (per-stream differences against bits_prev, summed in one fixed tree order; bits null: nothing kept).
+// build = 0: the fold only (the tail).  Every stream must hold at least (k + 1) * L bytes.  `cus`: the handle's CU count
+// (the grid never exceeds it).
+struct BlockWindowArgs {
+    const uint8_t *text;        // the coder's text buffer
+    const uint64_t *text_off;   // B + 1
+    int32_t *xi, *ti, *Xr, *Tr, *head;
+    float *H, *C;
+    const double *bits;         // per stream, accumulated by code_head (null: decoder)
+    double *bits_prev;          // per stream: the value at the last fold
+    double *block_bits;         // where this fold goes
+    long long k;
+    int S, B, NB4, build;
+};
+void block_window(const BlockWindowArgs &a, int cus, hipStream_t st);
+
 } // namespace lstmk

@@ -2000,6 +2000,58 @@ void code_head(const CodeHeadArgs &a, long long t, hipStream_t st) {
     }
 #undef CODE_HEAD_CASE
 }
+// ------------------------------------------------------------------------------------------------
+// block_window: the training window of block k of the adaptive coder (kernels.h), straight from the
+// coder's text buffer: no cursors, no ring walk, no wrap.  Every element is independent, so the window, the rings' copy and
+// the carry are grid-stride loops over all workgroups; workgroup 0 then folds the block's ideal bits.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_block_window(BlockWindowArgs a) {
+    const int tid = blockIdx.x * 256 + threadIdx.x, nth = gridDim.x * 256;
+    if (a.build) {
+        const long long first = a.k * (long long)(a.S - 1) - 1; // byte index of row 0's target
+        for (int i = tid; i < a.S * a.B; i += nth) {
+            const int t = i / a.B, b = i - t * a.B;
+            const uint8_t *p = a.text + a.text_off[b];
+            const long long jt = first + t, jx = jt - 1;
+            const int tv = jt >= 0 ? (int)p[jt] : -1, xv = jx >= 0 ? (int)p[jx] : -1;
+            a.xi[i] = xv;
+            a.ti[i] = tv;
+            a.Xr[i] = xv; // the rings with head = 0: ring row = window row
+            a.Tr[i] = tv;
+        }
+        if (tid == 0) *a.head = 0;
+        const float4 *Hs = reinterpret_cast<const float4 *>(a.H) + (size_t)(a.S - 1) * a.NB4;
+        const float4 *Cs = reinterpret_cast<const float4 *>(a.C) + (size_t)(a.S - 1) * a.NB4;
+        for (int i = tid; i < a.NB4; i += nth) { // carry: column S-1 -> column 0 (S >= 2: different columns)
+            reinterpret_cast<float4 *>(a.H)[i] = Hs[i];
+            reinterpret_cast<float4 *>(a.C)[i] = Cs[i];
+        }
+    }
+    if (blockIdx.x != 0 || a.bits == nullptr) return;
+    __shared__ double part[256];
+    double sum = 0.0;
+    for (int s = threadIdx.x; s < a.B; s += 256) { // streams m, m + 256, ... in order
+        const double v = a.bits[s];
+        sum += v - a.bits_prev[s];
+        a.bits_prev[s] = v;
+    }
+    part[threadIdx.x] = sum;
+    __syncthreads();
+    for (int d = 128; d > 0; d >>= 1) { // fixed tree
+        if ((int)threadIdx.x < d) part[threadIdx.x] += part[threadIdx.x + d];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *a.block_bits = part[0];
+}
+void block_window(const BlockWindowArgs &a, int cus, hipStream_t st) {
+    const long long cols = (long long)a.S * a.B;
+    const long long work = !a.build ? 1 : cols > a.NB4 ? cols : (long long)a.NB4;
+    int blocks = (int)((work + 1023) / 1024); // about four elements per thread
+    if (blocks > cus) blocks = cus;
+    if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL(k_block_window, dim3(blocks), dim3(256), 0, st, a);
+}
+
 void sample(const float *P, int N, float *hc, const double *u, int count, uint8_t *out, float *, bool stable, hipStream_t st) {
     const size_t lds = (size_t)(6 * N + 256) * sizeof(float);
     if (stable) hipLaunchKernelGGL(k_sample<true>, dim3(1), dim3(1024), lds, st, P, N, hc, u, count, out);

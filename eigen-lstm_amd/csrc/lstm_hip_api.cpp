@@ -52,12 +52,13 @@ enum KernelId {
     K_GRAD_SUMSQ, K_GRAD_NORM, // global-norm clipping (lstm_hip_set_grad_clip): partial sums of d^2, then norm and coefficient
     K_ADAM,                    // the update launch on a handle set to LSTM_HIP_OPT_ADAM (K_ADAGRAD's launch with the Adam rule)
     K_CODE_HEAD,               // one step of the range coder (lstm_hip_encode / lstm_hip_decode)
+    K_BLOCK_WINDOW,            // adaptive coding: a block's training window, carry and bit fold (one launch per block)
     K_COUNT
 };
 const char *const kKernelNames[K_COUNT] = {
     "pack_U", "fwd_step", "gemm_Y", "softmax_loss_dy", "loss_reduce", "gemm_DHy", "bwd_step", "gemm_dWhy", "gemm_dU",
     "dW_db", "loss_dby", "adagrad", "slide", "allreduce", "fwd_persistent", "bwd_persistent", "gen_head", "side_sums",
-    "gemm_dU_halves", "grad_sumsq", "grad_norm", "adam", "code_head"};
+    "gemm_dU_halves", "grad_sumsq", "grad_norm", "adam", "code_head", "block_window"};
 
 // ---- RCCL, loaded on first use so single-GPU users never touch it --------------------------
 struct UniqueId {
@@ -1187,22 +1188,45 @@ int lstm_hip_set_loss_mode(lstm_hip_t *h, int32_t mode) {
     return 0;
 }
 
+// the window loops (lstm_hip_train_windows, the adaptive coder): room for `count` per-window losses
+static int ensure_losses(lstm_hip_ctx *h, int64_t count) {
+    if (count <= h->losses_cap) return 0;
+    const int64_t cap = count < 8192 ? 8192 : count;
+    HIP_TRY(hipStreamSynchronize(h->st));
+    if (h->d_losses) HIP_TRY(hipFree(h->d_losses));
+    if (h->h_losses) HIP_TRY(hipHostFree(h->h_losses));
+    h->d_losses = nullptr;
+    h->h_losses = nullptr;
+    h->losses_cap = 0;
+    HIP_TRY(hipMalloc((void **)&h->d_losses, sizeof(double) * cap));
+    HIP_TRY(hipHostMalloc((void **)&h->h_losses, sizeof(double) * cap, hipHostMallocDefault));
+    h->losses_cap = cap;
+    return 0;
+}
+struct LoopGuard { // leaves the loop state clean on every return path
+    lstm_hip_ctx *h;
+    bool completed = false;
+    ~LoopGuard() {
+        h->in_loop = false;
+        if (completed) return;
+        // error exit somewhere inside a window: nothing of that window may leak into a later standalone call
+        h->fold_pending = false;
+        h->early_reduced = false;
+        h->dU_reduced = 0;
+        h->n_slabs_dU = 0;
+        h->dby_done = false;
+        h->fwd_done = false;
+        h->carry_slide = false;
+        if (h->st2) (void)hipStreamSynchronize(h->st2); // side-stream work of the broken window (folds, early all-reduce)
+        if (h->st) (void)hipStreamSynchronize(h->st);
+    }
+};
+
 int lstm_hip_train_windows(lstm_hip_t *h, int64_t count, double learning_rate, double *losses, float *elapsed_ms) {
     CHECK(h);
     if (count < 0) return fail(LSTM_HIP_EINVAL, "train_windows: count < 0");
     if (!h->text) return fail(LSTM_HIP_ESTATE, "train_windows before set_text/set_cursors");
-    if (count > h->losses_cap) {
-        const int64_t cap = count < 8192 ? 8192 : count;
-        HIP_TRY(hipStreamSynchronize(h->st));
-        if (h->d_losses) HIP_TRY(hipFree(h->d_losses));
-        if (h->h_losses) HIP_TRY(hipHostFree(h->h_losses));
-        h->d_losses = nullptr;
-        h->h_losses = nullptr;
-        h->losses_cap = 0;
-        HIP_TRY(hipMalloc((void **)&h->d_losses, sizeof(double) * cap));
-        HIP_TRY(hipHostMalloc((void **)&h->h_losses, sizeof(double) * cap, hipHostMallocDefault));
-        h->losses_cap = cap;
-    }
+    if (int rc = ensure_losses(h, count)) return rc;
     h->norms_n = -1;
     const bool clip = h->clip_max > 0.0;
     if (clip)
@@ -1211,24 +1235,7 @@ int lstm_hip_train_windows(lstm_hip_t *h, int64_t count, double learning_rate, d
     // device time, which a 20-window measurement would carry)
     if (elapsed_ms) HIP_TRY(hipEventRecord(h->evt0, h->st));
     h->in_loop = true;
-    struct LoopGuard { // leaves the loop state clean on every return path
-        lstm_hip_ctx *h;
-        bool completed = false;
-        ~LoopGuard() {
-            h->in_loop = false;
-            if (completed) return;
-            // error exit somewhere inside a window: nothing of that window may leak into a later standalone call
-            h->fold_pending = false;
-            h->early_reduced = false;
-            h->dU_reduced = 0;
-            h->n_slabs_dU = 0;
-            h->dby_done = false;
-            h->fwd_done = false;
-            h->carry_slide = false;
-            if (h->st2) (void)hipStreamSynchronize(h->st2); // side-stream work of the broken window (folds, early all-reduce)
-            if (h->st) (void)hipStreamSynchronize(h->st);
-        }
-    } guard{h};
+    LoopGuard guard{h};
     for (int64_t i = 0; i < count; i++) {
         // (from the second window on the slide has been done by the previous window's Adagrad launch, in extra workgroups)
         if (!h->pre_slid)
@@ -1545,21 +1552,38 @@ static int check_offsets(const char *what, const char *name, const uint64_t *off
 }
 
 // Both directions: per step one code_head launch and one k_fwd_step over all streams (the generator's loop), from the fp32
-// master parameters P and a fragment image of U made for this call, in the handle's generator scratch memory.  Encoder:
-// `text` in, the streams' codes (at lstm_hip_code_bound offsets) out; decoder: `code` at `code_off` in, `text` out.
-static int run_coder(lstm_hip_t *h, bool decode, int32_t streams, const uint64_t *text_off, const uint8_t *text_in,
-                     uint8_t *text_out, const uint8_t *code_in, const uint64_t *code_off_in, uint8_t *code_out,
-                     uint64_t *code_off_out, double *bits, uint32_t *trace) {
+// master parameters P and a fragment image of U made for the call (the adaptive calls: remade for every block), in the
+// handle's generator scratch memory.  Encoder: `text` in, the streams' codes (at lstm_hip_code_bound offsets) out; decoder:
+// `code` at `code_off` in, `text` out.  A run is begun once, stepped over ranges of t that together cover [0, max_len) in
+// order (the static calls: one range), and finished once; the coder state of every stream, x_next and the H / C ping-pong
+// live on the device or in the run between ranges, so a pause between two ranges changes no code.
+struct CoderRun {
+    CodeHeadArgs a{};
+    bool decode = false;
+    int32_t streams = 0;
+    uint64_t total = 0, max_len = 0, code_bytes = 0;
+    std::vector<uint64_t> base; // each stream's code range on the device
+    size_t n = 0;               // N * streams
+    float4 *Ufwd = nullptr;
+    float *H = nullptr, *Cs = nullptr, *G = nullptr;
+    double *bits_prev = nullptr, *block_bits = nullptr; // adaptive calls: per-stream bits at the last fold, per-block totals
+    int cur = 0;
+};
+static int coder_begin(lstm_hip_t *h, CoderRun &r, bool decode, int32_t streams, const uint64_t *text_off, const uint8_t *text_in,
+                       const uint8_t *code_in, const uint64_t *code_off_in, bool want_trace, int64_t n_block_bits) {
     const int N = h->cfg.N;
-    const uint64_t total = text_off[streams];
-    uint64_t max_len = 0;
-    for (int s = 0; s < streams; s++) max_len = std::max<uint64_t>(max_len, text_off[s + 1] - text_off[s]);
-    std::vector<uint64_t> base(streams + 1, 0); // each stream's code range on the device
-    if (decode) base.assign(code_off_in, code_off_in + streams + 1);
+    r.decode = decode;
+    r.streams = streams;
+    r.total = text_off[streams];
+    r.max_len = 0;
+    for (int s = 0; s < streams; s++) r.max_len = std::max<uint64_t>(r.max_len, text_off[s + 1] - text_off[s]);
+    r.base.assign(streams + 1, 0);
+    if (decode) r.base.assign(code_off_in, code_off_in + streams + 1);
     else
-        for (int s = 0; s < streams; s++) base[s + 1] = base[s] + lstm_hip_code_bound(text_off[s + 1] - text_off[s]);
-    const uint64_t code_bytes = base[streams];
-    const size_t n = (size_t)N * streams;
+        for (int s = 0; s < streams; s++) r.base[s + 1] = r.base[s] + lstm_hip_code_bound(text_off[s + 1] - text_off[s]);
+    r.code_bytes = r.base[streams];
+    const uint64_t total = r.total, code_bytes = r.code_bytes;
+    const size_t n = r.n = (size_t)N * streams;
 
     size_t bytes = 0;
     auto piece = [&](size_t b) {
@@ -1572,12 +1596,17 @@ static int run_coder(lstm_hip_t *h, bool decode, int32_t streams, const uint64_t
                  o_toff = piece(sizeof(uint64_t) * (streams + 1)), o_base = piece(sizeof(uint64_t) * (streams + 1)),
                  o_text = piece(total), o_code = piece(code_bytes), o_st = piece(sizeof(CoderState) * streams),
                  o_len = piece(sizeof(uint64_t) * streams), o_bits = piece(sizeof(double) * streams),
-                 o_tr = piece(trace ? sizeof(uint32_t) * 3 * total : 0), o_err = piece(sizeof(uint32_t));
+                 o_tr = piece(want_trace ? sizeof(uint32_t) * 3 * total : 0), o_err = piece(sizeof(uint32_t)),
+                 o_prev = piece(n_block_bits ? sizeof(double) * streams : 0), o_bb = piece(sizeof(double) * n_block_bits);
     if (int rc = reserve_gen_scratch(h, bytes)) return rc;
     char *b0 = h->gen_scratch;
-    float4 *Ufwd = reinterpret_cast<float4 *>(b0 + o_U);
-    float *H = reinterpret_cast<float *>(b0 + o_H), *Cs = reinterpret_cast<float *>(b0 + o_C), *G = reinterpret_cast<float *>(b0 + o_G);
-    CodeHeadArgs a{};
+    r.Ufwd = reinterpret_cast<float4 *>(b0 + o_U);
+    r.H = reinterpret_cast<float *>(b0 + o_H), r.Cs = reinterpret_cast<float *>(b0 + o_C), r.G = reinterpret_cast<float *>(b0 + o_G);
+    r.bits_prev = n_block_bits ? reinterpret_cast<double *>(b0 + o_prev) : nullptr;
+    r.block_bits = n_block_bits ? reinterpret_cast<double *>(b0 + o_bb) : nullptr;
+    r.cur = 0;
+    CodeHeadArgs &a = r.a;
+    a = CodeHeadArgs{};
     a.Why = h->P + h->pl.Why;
     a.by = h->P + h->pl.by;
     a.text_off = reinterpret_cast<uint64_t *>(b0 + o_toff);
@@ -1587,35 +1616,53 @@ static int run_coder(lstm_hip_t *h, bool decode, int32_t streams, const uint64_t
     a.code_len = reinterpret_cast<uint64_t *>(b0 + o_len);
     a.state = reinterpret_cast<CoderState *>(b0 + o_st);
     a.bits = decode ? nullptr : reinterpret_cast<double *>(b0 + o_bits);
-    a.trace = trace && !decode ? reinterpret_cast<uint32_t *>(b0 + o_tr) : nullptr;
+    a.trace = want_trace && !decode ? reinterpret_cast<uint32_t *>(b0 + o_tr) : nullptr;
     a.x_next = reinterpret_cast<int32_t *>(b0 + o_x);
     a.err = reinterpret_cast<uint32_t *>(b0 + o_err);
     a.N = N;
     a.streams = streams;
     a.decode = decode ? 1 : 0;
 
-    HIP_TRY(hipMemsetAsync(H, 0, sizeof(float) * n, h->st)); // every stream starts from h = c = 0 (padding rows too)
-    HIP_TRY(hipMemsetAsync(Cs, 0, sizeof(float) * n, h->st));
+    HIP_TRY(hipMemsetAsync(r.H, 0, sizeof(float) * n, h->st)); // every stream starts from h = c = 0 (padding rows too)
+    HIP_TRY(hipMemsetAsync(r.Cs, 0, sizeof(float) * n, h->st));
     HIP_TRY(hipMemcpyAsync(const_cast<uint64_t *>(a.text_off), text_off, sizeof(uint64_t) * (streams + 1), hipMemcpyHostToDevice, h->st));
-    HIP_TRY(hipMemcpyAsync(const_cast<uint64_t *>(a.code_base), base.data(), sizeof(uint64_t) * (streams + 1), hipMemcpyHostToDevice, h->st));
+    HIP_TRY(hipMemcpyAsync(const_cast<uint64_t *>(a.code_base), r.base.data(), sizeof(uint64_t) * (streams + 1), hipMemcpyHostToDevice, h->st));
     if (!decode && total) HIP_TRY(hipMemcpyAsync(a.text, text_in, total, hipMemcpyHostToDevice, h->st));
     if (decode && code_bytes) HIP_TRY(hipMemcpyAsync(a.code, code_in, code_bytes, hipMemcpyHostToDevice, h->st));
     HIP_TRY(hipMemsetAsync(a.code_len, 0, sizeof(uint64_t) * streams, h->st)); // (empty streams: no code)
     HIP_TRY(hipMemsetAsync(b0 + o_bits, 0, sizeof(double) * streams, h->st));
     HIP_TRY(hipMemsetAsync(a.err, 0, sizeof(uint32_t), h->st));
-    if (max_len) RUN(K_PACK_U, pack_U(h->P + h->pl.U, Ufwd, nullptr, N, h->st));
-
-    const bool fast = (h->cfg.flags & LSTM_HIP_FAST_MATH) != 0;
-    int cur = 0;
-    for (long long t = 0; t < (long long)max_len; t++) {
-        a.H = H + cur * n;
-        RUN(K_CODE_HEAD, code_head(a, t, h->st));
-        if (t + 1 == (long long)max_len) break;
-        RUN(K_FWD_STEP, fwd_step(Ufwd, h->P + h->pl.W, h->P + h->pl.b, H + cur * n, Cs + cur * n, H + (cur ^ 1) * n,
-                                 Cs + (cur ^ 1) * n, G, a.x_next, N, streams, fast, h->st));
-        cur ^= 1;
+    if (n_block_bits) {
+        HIP_TRY(hipMemsetAsync(r.bits_prev, 0, sizeof(double) * streams, h->st));
+        HIP_TRY(hipMemsetAsync(r.block_bits, 0, sizeof(double) * n_block_bits, h->st));
     }
-
+    return 0;
+}
+// steps t0 .. t1-1 with the current P: the image of U is remade first, then per step code_head and (except behind the last
+// byte of the longest stream) fwd_step on the byte just coded
+static int coder_steps(lstm_hip_t *h, CoderRun &r, uint64_t t0, uint64_t t1) {
+    if (t0 >= t1) return 0;
+    const int N = h->cfg.N;
+    const size_t n = r.n;
+    RUN(K_PACK_U, pack_U(h->P + h->pl.U, r.Ufwd, nullptr, N, h->st));
+    const bool fast = (h->cfg.flags & LSTM_HIP_FAST_MATH) != 0;
+    for (long long t = (long long)t0; t < (long long)t1; t++) {
+        r.a.H = r.H + r.cur * n;
+        RUN(K_CODE_HEAD, code_head(r.a, t, h->st));
+        if (t + 1 == (long long)r.max_len) break;
+        RUN(K_FWD_STEP, fwd_step(r.Ufwd, h->P + h->pl.W, h->P + h->pl.b, r.H + r.cur * n, r.Cs + r.cur * n, r.H + (r.cur ^ 1) * n,
+                                 r.Cs + (r.cur ^ 1) * n, r.G, r.a.x_next, N, r.streams, fast, h->st));
+        r.cur ^= 1;
+    }
+    return 0;
+}
+static int coder_finish(lstm_hip_t *h, CoderRun &r, uint8_t *text_out, uint8_t *code_out, uint64_t *code_off_out, double *bits,
+                        uint32_t *trace, double *block_bits, int64_t n_block_bits) {
+    const bool decode = r.decode;
+    const int32_t streams = r.streams;
+    const uint64_t total = r.total, code_bytes = r.code_bytes;
+    const CodeHeadArgs &a = r.a;
+    const char *what = decode ? "decode" : "encode";
     uint32_t err = 0;
     std::vector<uint64_t> len(streams);
     HIP_TRY(hipMemcpyAsync(&err, a.err, sizeof(uint32_t), hipMemcpyDeviceToHost, h->st));
@@ -1626,19 +1673,29 @@ static int run_coder(lstm_hip_t *h, bool decode, int32_t streams, const uint64_t
         if (code_bytes) HIP_TRY(hipMemcpyAsync(code_out, a.code, code_bytes, hipMemcpyDeviceToHost, h->st));
         if (bits) HIP_TRY(hipMemcpyAsync(bits, a.bits, sizeof(double) * streams, hipMemcpyDeviceToHost, h->st));
         if (trace && total) HIP_TRY(hipMemcpyAsync(trace, a.trace, sizeof(uint32_t) * 3 * total, hipMemcpyDeviceToHost, h->st));
+        if (block_bits && n_block_bits)
+            HIP_TRY(hipMemcpyAsync(block_bits, r.block_bits, sizeof(double) * n_block_bits, hipMemcpyDeviceToHost, h->st));
     }
     HIP_TRY(hipStreamSynchronize(h->st));
-    if (err & CODE_ERR_TOTAL) return fail(LSTM_HIP_EINVAL, "%s: a frequency total passed 2^16 (the quantisation bound)", decode ? "decode" : "encode");
-    if (err & CODE_ERR_BOUND) return fail(LSTM_HIP_EINVAL, "%s: a code passed lstm_hip_code_bound", decode ? "decode" : "encode");
+    if (err & CODE_ERR_TOTAL) return fail(LSTM_HIP_EINVAL, "%s: a frequency total passed 2^16 (the quantisation bound)", what);
+    if (err & CODE_ERR_BOUND) return fail(LSTM_HIP_EINVAL, "%s: a code passed lstm_hip_code_bound", what);
     if (!decode) { // the codes back to back: move each down from its bound-sized range (memmove: ranges overlap in order)
         code_off_out[0] = 0;
         for (int s = 0; s < streams; s++) {
-            if (len[s] > base[s + 1] - base[s]) return fail(LSTM_HIP_EINVAL, "encode: stream %d's code passed its bound", s);
-            if (len[s]) memmove(code_out + code_off_out[s], code_out + base[s], len[s]);
+            if (len[s] > r.base[s + 1] - r.base[s]) return fail(LSTM_HIP_EINVAL, "encode: stream %d's code passed its bound", s);
+            if (len[s]) memmove(code_out + code_off_out[s], code_out + r.base[s], len[s]);
             code_off_out[s + 1] = code_off_out[s] + len[s];
         }
     }
     return 0;
+}
+static int run_coder(lstm_hip_t *h, bool decode, int32_t streams, const uint64_t *text_off, const uint8_t *text_in,
+                     uint8_t *text_out, const uint8_t *code_in, const uint64_t *code_off_in, uint8_t *code_out,
+                     uint64_t *code_off_out, double *bits, uint32_t *trace) {
+    CoderRun r;
+    if (int rc = coder_begin(h, r, decode, streams, text_off, text_in, code_in, code_off_in, trace != nullptr, 0)) return rc;
+    if (int rc = coder_steps(h, r, 0, r.max_len)) return rc;
+    return coder_finish(h, r, text_out, code_out, code_off_out, bits, trace, nullptr, 0);
 }
 
 int lstm_hip_encode(lstm_hip_t *h, int32_t streams, const uint8_t *text, const uint64_t *text_off, uint8_t *code,
@@ -1672,6 +1729,128 @@ int lstm_hip_decode(lstm_hip_t *h, int32_t streams, const uint8_t *code, const u
     if (text_off[streams] > 0 && !text) return fail(LSTM_HIP_EINVAL, "decode: null text with %llu bytes to decode", (unsigned long long)text_off[streams]);
     if (h->cfg.N > 16384) return fail(LSTM_HIP_EINVAL, "decode: hidden width %d above 16384", h->cfg.N);
     return run_coder(h, true, streams, text_off, nullptr, text, code, code_off, nullptr, nullptr, nullptr, nullptr);
+}
+
+// ---- adaptive coding: the model trains on the bytes it has coded (include/lstm_hip.h)
+uint32_t lstm_hip_adaptive_version(void) { return 1; }
+
+int64_t lstm_hip_adaptive_blocks(int32_t S, int32_t B, const uint64_t *text_off) {
+    if (S < 2 || B < 1) return fail(LSTM_HIP_EINVAL, "adaptive_blocks: need S >= 2 and B >= 1 (got %d, %d)", S, B);
+    if (int rc = check_offsets("adaptive_blocks", "text_off", text_off, B)) return rc;
+    uint64_t shortest = UINT64_MAX;
+    for (int s = 0; s < B; s++) shortest = std::min<uint64_t>(shortest, text_off[s + 1] - text_off[s]);
+    return (int64_t)(shortest / (uint64_t)(S - 1));
+}
+
+int lstm_hip_plan_identity(lstm_hip_t *h, char *buf, size_t cap) {
+    if (!h || !buf || cap == 0) return fail(LSTM_HIP_EINVAL, "plan_identity: null handle or buffer");
+    const EnginePlan &p = h->plan;
+    const int n = snprintf(buf, cap, "np%d fwd%d bwd%d fused%d bc%d gp%d fc%d lc%d gc%d quad%d dusplit%d side%d dgt%d sw%d su%d", h->cfg.N,
+                           (int)p.fwd, (int)p.bwd, (int)p.fused, p.bwd_cols, p.gpart_cols, p.fwd_cols, p.launch_cols, p.group_cols,
+                           (int)p.adagrad_quad, (int)p.du_split, (int)p.side_stream, (int)p.direct_dgt, h->splits_dWhy, h->splits_dU);
+    if (n < 0 || (size_t)n >= cap) return fail(LSTM_HIP_EINVAL, "plan_identity: the buffer needs %d bytes", n + 1);
+    return 0;
+}
+
+// Both adaptive calls.  Per block: the code pass (coder_steps: the image of U remade from the current P, then the static
+// coder's steps), block_window (the block's training window from the coder's text buffer, the carry, the bit fold), then one
+// window of the training loop exactly as lstm_hip_train_windows runs it, without a slide riding in the update launch (the
+// next block's bytes do not exist yet in the decoder).  The tail is coded only.
+static int run_adaptive(lstm_hip_t *h, bool decode, const uint64_t *text_off, const uint8_t *text_in, uint8_t *text_out,
+                        const uint8_t *code_in, const uint64_t *code_off_in, uint8_t *code_out, uint64_t *code_off_out, double lr,
+                        double *bits, double *block_bits, uint32_t *trace) {
+    const int S = h->cfg.S, B = h->cfg.B, N = h->cfg.N;
+    const uint64_t L = (uint64_t)(S - 1);
+    const int64_t n_blocks = lstm_hip_adaptive_blocks(S, B, text_off);
+    if (n_blocks < 0) return (int)n_blocks;
+    if (int rc = ensure_losses(h, n_blocks)) return rc;
+    h->norms_n = -1;
+    h->pre_slid = false;
+    const bool clip = h->clip_max > 0.0;
+    if (clip)
+        if (int rc = ensure_norms(h, n_blocks)) return rc;
+    // reset: empty window, zero states
+    if (int rc = lstm_hip_reset_window(h)) return rc;
+    HIP_TRY(hipMemsetAsync(h->H, 0, sizeof(float) * (size_t)S * N * B, h->st));
+    HIP_TRY(hipMemsetAsync(h->C, 0, sizeof(float) * (size_t)S * N * B, h->st));
+    CoderRun r;
+    const int64_t n_bb = decode ? 0 : n_blocks + 1;
+    if (int rc = coder_begin(h, r, decode, B, text_off, text_in, code_in, code_off_in, trace != nullptr, n_bb)) return rc;
+    BlockWindowArgs w{};
+    w.text = r.a.text, w.text_off = r.a.text_off;
+    w.xi = h->xi, w.ti = h->ti, w.Xr = h->Xr, w.Tr = h->Tr, w.head = h->head;
+    w.H = h->H, w.C = h->C;
+    w.bits = r.a.bits, w.bits_prev = r.bits_prev;
+    w.S = S, w.B = B, w.NB4 = N * B / 4;
+    h->in_loop = true;
+    LoopGuard guard{h};
+    for (int64_t k = 0; k < n_blocks; k++) {
+        int rc = 0;
+        if ((rc = coder_steps(h, r, (uint64_t)k * L, (uint64_t)(k + 1) * L))) return rc;
+        w.k = k, w.build = 1, w.block_bits = decode ? nullptr : r.block_bits + k;
+        RUN(K_BLOCK_WINDOW, block_window(w, h->plan.n_cus, h->st));
+        if ((rc = do_forward(h))) return rc;
+        RUN(K_LOSS, loss_reduce(loss_src(h), loss_steps(h), B, h->global_B, h->d_losses + k, h->dby_part, h->n_dby_parts,
+                                h->dP + h->pl.by, h->st, loss_scale(h)));
+        h->dby_done = true;
+        if ((rc = do_backward(h))) return rc;
+        h->carry_slide = false;
+        if ((rc = do_adagrad(h, lr, k))) return rc;
+    }
+    if (int rc = coder_steps(h, r, (uint64_t)n_blocks * L, r.max_len)) return rc;
+    if (!decode) {
+        w.k = n_blocks, w.build = 0, w.block_bits = r.block_bits + n_blocks;
+        RUN(K_BLOCK_WINDOW, block_window(w, h->plan.n_cus, h->st));
+    }
+    const int rc = coder_finish(h, r, text_out, code_out, code_off_out, bits, trace, block_bits, n_bb);
+    if (int ab = check_abort(h)) return ab;
+    if (rc) return rc;
+    guard.completed = true;
+    if (clip) h->norms_n = n_blocks;
+    return 0;
+}
+
+static int adaptive_checks(lstm_hip_t *h, const char *what, double lr) {
+    if (h->comm) return fail(LSTM_HIP_ESTATE, "%s: a handle with a communicator cannot code adaptively", what);
+    if (!std::isfinite(lr) || lr < 0.0) return fail(LSTM_HIP_EINVAL, "%s: learning_rate must be finite and >= 0 (got %g)", what, lr);
+    if (h->cfg.N > 16384) return fail(LSTM_HIP_EINVAL, "%s: hidden width %d above 16384", what, h->cfg.N);
+    if (h->cfg.B > 4096) return fail(LSTM_HIP_EINVAL, "%s: more than 4096 streams (B = %d)", what, h->cfg.B);
+    return 0;
+}
+
+int lstm_hip_encode_adaptive(lstm_hip_t *h, const uint8_t *text, const uint64_t *text_off, double learning_rate, uint8_t *code,
+                             uint64_t code_cap, uint64_t *code_off, double *bits, double *block_bits, uint32_t *trace) {
+    CHECK(h);
+    const char *what = "encode_adaptive";
+    if (int rc = adaptive_checks(h, what, learning_rate)) return rc;
+    const int32_t streams = h->cfg.B;
+    if (int rc = check_offsets(what, "text_off", text_off, streams)) return rc;
+    if (!code_off) return fail(LSTM_HIP_EINVAL, "%s: null code_off", what);
+    if (text_off[streams] > 0 && !text) return fail(LSTM_HIP_EINVAL, "%s: null text with %llu bytes to code", what, (unsigned long long)text_off[streams]);
+    uint64_t need = 0;
+    for (int s = 0; s < streams; s++) {
+        const size_t b = lstm_hip_code_bound(text_off[s + 1] - text_off[s]);
+        if (b == SIZE_MAX || need > UINT64_MAX - b) return fail(LSTM_HIP_EINVAL, "%s: text too long", what);
+        need += b;
+    }
+    if (code_cap < need)
+        return fail(LSTM_HIP_EINVAL, "%s: code_cap %llu is below the bound %llu (sum of lstm_hip_code_bound)", what,
+                    (unsigned long long)code_cap, (unsigned long long)need);
+    if (need > 0 && !code) return fail(LSTM_HIP_EINVAL, "%s: null code", what);
+    return run_adaptive(h, false, text_off, text, nullptr, nullptr, nullptr, code, code_off, learning_rate, bits, block_bits, trace);
+}
+
+int lstm_hip_decode_adaptive(lstm_hip_t *h, const uint8_t *code, const uint64_t *code_off, const uint64_t *text_off,
+                             double learning_rate, uint8_t *text) {
+    CHECK(h);
+    const char *what = "decode_adaptive";
+    if (int rc = adaptive_checks(h, what, learning_rate)) return rc;
+    const int32_t streams = h->cfg.B;
+    if (int rc = check_offsets(what, "code_off", code_off, streams)) return rc;
+    if (int rc = check_offsets(what, "text_off", text_off, streams)) return rc;
+    if (code_off[streams] > 0 && !code) return fail(LSTM_HIP_EINVAL, "%s: null code with %llu code bytes", what, (unsigned long long)code_off[streams]);
+    if (text_off[streams] > 0 && !text) return fail(LSTM_HIP_EINVAL, "%s: null text with %llu bytes to decode", what, (unsigned long long)text_off[streams]);
+    return run_adaptive(h, true, text_off, nullptr, text, code, code_off, nullptr, nullptr, learning_rate, nullptr, nullptr, nullptr);
 }
 
 int lstm_hip_debug_stamps(lstm_hip_t *h, uint64_t *out, size_t count) {

@@ -16,10 +16,29 @@
 //   u32 magic "LHAC" | u32 format version | u32 coder version | u32 N | u32 flags (LSTM_HIP_FAST_MATH or 0)
 //   | u64 FNV-1a of the logical parameter block (its float32 bytes) | u64 original length | u32 K | u32 CRC32 of the original
 //   | K x u64 code lengths | the K codes back to back
+//
+//   lstm_compress --adapt (-c|-d) IN OUT [--hidden N --seq S --streams B --lr X --seed K --optimizer adagrad|adam
+//                 --adam-betas B1,B2 --adam-eps E --weight-decay W --clip-norm X --stable-softmax --bf16 --fast-math
+//                 --load PREFIX --device D]
+//
+// --adapt codes with no checkpoint (lstm_hip_encode_adaptive / lstm_hip_decode_adaptive): the model
+// starts from the seeded initialisation of `lstm` (rng.h: W, U, Why ~ N(0, 0.01) in that order, b = by = 0) -- or, with
+// --load, from a checkpoint as a prior -- and trains on every block of S-1 bytes per stream after it was coded.  The B
+// streams split IN as above.  -d takes everything from the container (only --device, and --load where a prior was used);
+// the decoder repeats the training, so it needs the same device model and engine plan, which the container records.
+//
+// Adaptive container, little-endian (312-byte header):
+//   u32 magic "LHAD" | u32 format version | u32 coder version | u32 adaptive version | u32 N | u32 S | u32 B | u32 create flags
+//   | u64 lr (the double's bits) | u32 optimizer kind | u32 prior (1: --load) | 4 x u64 beta1, beta2, eps, weight decay (bits)
+//   | u64 clip norm (bits) | u32 seed | u32 CU count | u64 FNV-1a of the INITIAL logical parameter block | u64 original length
+//   | u32 CRC32 of the original | u32 0 | char[64] device name | char[128] plan identity (lstm_hip_plan_identity)
+//   | B x u64 code lengths | the B codes back to back
 #include "../../include/lstm_hip.h"
 #include "checkpoint.h"
+#include "rng.h"
 
 #include <cerrno>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -28,10 +47,19 @@
 
 namespace {
 
-const char *const kUsage = "usage: lstm_compress --load PREFIX (-c|-d) IN OUT [--streams K] [--fast-math] [--device D]\n";
+const char *const kUsage = "usage: lstm_compress --load PREFIX (-c|-d) IN OUT [--streams K] [--fast-math] [--device D]\n"
+                            "       lstm_compress --adapt (-c|-d) IN OUT [--hidden N --seq S --streams B --lr X --seed K\n"
+                            "                     --optimizer adagrad|adam --adam-betas B1,B2 --adam-eps E --weight-decay W\n"
+                            "                     --clip-norm X --stable-softmax --bf16 --fast-math\n"
+                            "                     --load PREFIX --device D]   (-d: only --device, and --load for a prior)\n";
 constexpr uint32_t kMagic = 0x4341484Cu; // "LHAC"
 constexpr uint32_t kFormat = 1;
 constexpr size_t kHeader = 44;
+constexpr uint32_t kMagicAdaptive = 0x4441484Cu; // "LHAD"
+constexpr uint32_t kFormatAdaptive = 1;
+constexpr size_t kHeaderAdaptive = 312, kNameBytes = 64, kPlanBytes = 128;
+constexpr uint32_t kKnownFlags = LSTM_HIP_FAST_MATH | LSTM_HIP_BF16_RECURRENCE | LSTM_HIP_PAD_HIDDEN |
+                                 LSTM_HIP_STABLE_SOFTMAX;
 constexpr uint64_t kBytesPerStream = 16384; // default K: one stream per 16 KB ...
 constexpr long kDefaultMaxStreams = 256;   // ... up to 256 streams
 
@@ -63,7 +91,36 @@ struct Options {
     char mode = 0; // 'c' or 'd'
     long streams = 0, device = 0; // streams 0: the default rule
     unsigned flags = 0;
+    // --adapt
+    bool adapt = false;
+    std::string model_opt; // the last option given that only --adapt -c takes
+    long N = 128, S = 32;
+    uint32_t seed = 1;
+    double lr = 0.05, beta1 = 0.9, beta2 = 0.999, adam_eps = 1e-8, weight_decay = 0.0, clip_norm = 0.0;
+    bool adam = false;
+    std::string adam_opt; // the last Adam option given (refused without --optimizer adam)
 };
+
+double parse_double(const std::string &opt, const std::string &v, double lo, bool lo_open, double hi, bool inf_ok) {
+    char *end = nullptr;
+    errno = 0;
+    const double x = strtod(v.c_str(), &end);
+    const bool inf = std::isinf(x) && x > 0; // (hi is exclusive; +inf passes only where the option takes it)
+    if (v.empty() || *end != '\0' || std::isnan(x) || x < lo || (lo_open && x == lo) || (inf ? !inf_ok : x >= hi))
+        usage(opt + " needs a number " + (lo_open ? "> " : ">= ") + std::to_string(lo) + (std::isinf(hi) ? "" : " and < " + std::to_string(hi)) +
+              ", got '" + v + "'");
+    return x;
+}
+uint64_t dbits(double x) {
+    uint64_t u;
+    memcpy(&u, &x, 8);
+    return u;
+}
+double bits_to_double(uint64_t u) {
+    double x;
+    memcpy(&x, &u, 8);
+    return x;
+}
 
 Options parse(int argc, char **argv) {
     Options o;
@@ -83,13 +140,39 @@ Options parse(int argc, char **argv) {
         } else if (a == "--streams") o.streams = parse_int(a, val(), 1, 4096);
         else if (a == "--device") o.device = parse_int(a, val(), 0, 1 << 20);
         else if (a == "--fast-math") o.flags |= LSTM_HIP_FAST_MATH;
+        else if (a == "--adapt") o.adapt = true;
+        else if (a == "--hidden") o.N = parse_int(o.model_opt = a, val(), 1, 16384);
+        else if (a == "--seq") o.S = parse_int(o.model_opt = a, val(), 2, 1 << 16);
+        else if (a == "--seed") o.seed = (uint32_t)parse_int(o.model_opt = a, val(), 0, 0xFFFFFFFFl);
+        else if (a == "--lr") o.lr = parse_double(o.model_opt = a, val(), 0.0, false, INFINITY, false);
+        else if (a == "--clip-norm") o.clip_norm = parse_double(o.model_opt = a, val(), 0.0, false, INFINITY, true);
+        else if (a == "--stable-softmax") o.model_opt = a, o.flags |= LSTM_HIP_STABLE_SOFTMAX;
+        else if (a == "--bf16") o.model_opt = a, o.flags |= LSTM_HIP_BF16_RECURRENCE;
+        else if (a == "--optimizer") {
+            const std::string v = val();
+            if (v != "adagrad" && v != "adam") usage("--optimizer needs adagrad or adam, got '" + v + "'");
+            o.model_opt = a, o.adam = v == "adam";
+        } else if (a == "--adam-betas") {
+            const std::string v = val();
+            const size_t comma = v.find(',');
+            if (comma == std::string::npos) usage("--adam-betas needs B1,B2, got '" + v + "'");
+            o.beta1 = parse_double(a, v.substr(0, comma), 0.0, false, 1.0, false);
+            o.beta2 = parse_double(a, v.substr(comma + 1), 0.0, false, 1.0, false);
+            o.model_opt = o.adam_opt = a;
+        } else if (a == "--adam-eps") o.adam_eps = parse_double(o.model_opt = o.adam_opt = a, val(), 0.0, true, INFINITY, false);
+        else if (a == "--weight-decay") o.weight_decay = parse_double(o.model_opt = o.adam_opt = a, val(), 0.0, false, INFINITY, false);
         else if (a == "-h" || a == "--help") {
             printf("%s", kUsage);
             exit(0);
         } else usage("unknown argument " + a);
     }
-    if (o.load.empty()) usage("--load PREFIX is required");
+    if (!o.adapt) {
+        if (!o.model_opt.empty()) usage(o.model_opt + " needs --adapt");
+        if (o.load.empty()) usage("--load PREFIX is required");
+    }
     if (!o.mode) usage("nothing to do: give -c or -d");
+    if (o.adapt && o.mode == 'd' && !o.model_opt.empty()) usage(o.model_opt + " is read from the container with -d");
+    if (!o.adam_opt.empty() && !o.adam) usage(o.adam_opt + " needs --optimizer adam");
     if (o.mode == 'd' && o.streams) usage("--streams is read from the container with -d");
     if (o.mode == 'd' && o.flags) usage("--fast-math is read from the container with -d");
     return o;
@@ -223,6 +306,8 @@ void compress(const Options &o) {
 void decompress(const Options &o) {
     std::vector<uint8_t> in;
     if (!read_file(o.in, in)) die("cannot read " + o.in);
+    if (in.size() >= 4 && get32(&in[0]) == kMagicAdaptive)
+        die(o.in + ": an adaptive lstm_compress file (LHAD): decode it with --adapt -d");
     if (in.size() < kHeader) die(o.in + ": truncated header (" + std::to_string(in.size()) + " bytes)");
     if (get32(&in[0]) != kMagic) die(o.in + ": not an lstm_compress file (bad magic)");
     if (get32(&in[4]) != kFormat) die(o.in + ": container format " + std::to_string(get32(&in[4])) + ", this program reads " + std::to_string(kFormat));
@@ -258,10 +343,188 @@ void decompress(const Options &o) {
     write_file(o.out, text);
 }
 
+// ---- --adapt ------------------------------------------------------------------------------------------------------------
+struct Adaptive { // what fixes the model and its training: the container's fields
+    uint32_t N = 0, S = 0, B = 0, flags = 0, opt = LSTM_HIP_OPT_ADAGRAD, prior = 0, seed = 0;
+    double lr = 0.0, beta1 = 0.0, beta2 = 0.0, eps = 0.0, wd = 0.0, clip = 0.0;
+};
+// the initial logical parameter block: lstm's seeded initialisation, or the checkpoint where a prior was given
+std::vector<float> initial_params(const Adaptive &m, const std::string &load, const std::string &what) {
+    const int M = LSTM_HIP_VOCAB;
+    std::vector<float> P;
+    if (m.prior) {
+        const int Nc = load_model(load, P);
+        if ((uint32_t)Nc != m.N) die(what + ": a hidden size of " + std::to_string(m.N) + ", the checkpoint " + load + " has " + std::to_string(Nc));
+        return P;
+    }
+    P.assign(lstm_hip_param_count((int32_t)m.N, M), 0.0f);
+    SeededRng rng(m.seed);
+    const auto bl = checkpoint::blocks((int)m.N, M);
+    rng.randn(P.data() + bl[0].off, 4 * (int)m.N, M, 0.0, 0.01);
+    rng.randn(P.data() + bl[1].off, 4 * (int)m.N, (int)m.N, 0.0, 0.01);
+    rng.randn(P.data() + bl[3].off, M, (int)m.N, 0.0, 0.01);
+    return P;
+}
+struct Identity {
+    char name[kNameBytes] = {};
+    char plan[kPlanBytes] = {};
+    int32_t cus = 0;
+};
+lstm_hip_t *make_adaptive_handle(const Adaptive &m, const std::vector<float> &P, long device, Identity &id) {
+    lstm_hip_config cfg{(int32_t)m.N, LSTM_HIP_VOCAB, (int32_t)m.S, (int32_t)m.B, (int32_t)device, m.flags};
+    lstm_hip_t *h = nullptr;
+    CK(lstm_hip_create(&cfg, &h));
+    CK(lstm_hip_set_params(h, 0, P.data()));
+    if (m.opt == LSTM_HIP_OPT_ADAM) CK(lstm_hip_set_optimizer(h, LSTM_HIP_OPT_ADAM, m.beta1, m.beta2, m.eps, m.wd));
+    if (m.clip > 0.0) CK(lstm_hip_set_grad_clip(h, m.clip));
+    int32_t mhz = 0;
+    CK(lstm_hip_device_info((int32_t)device, id.name, &id.cus, &mhz));
+    CK(lstm_hip_plan_identity(h, id.plan, sizeof(id.plan)));
+    return h;
+}
+
+void compress_adaptive(const Options &o) {
+    std::vector<uint8_t> text;
+    if (!read_file(o.in, text)) die("cannot read " + o.in);
+    const uint64_t len = text.size();
+    Adaptive m;
+    m.N = (uint32_t)o.N, m.S = (uint32_t)o.S, m.flags = o.flags | LSTM_HIP_PAD_HIDDEN, m.seed = o.seed, m.lr = o.lr, m.clip = o.clip_norm;
+    m.prior = o.load.empty() ? 0 : 1;
+    if (o.adam) m.opt = LSTM_HIP_OPT_ADAM, m.beta1 = o.beta1, m.beta2 = o.beta2, m.eps = o.adam_eps, m.wd = o.weight_decay;
+    if (m.prior) {
+        std::string err;
+        const int Nc = checkpoint::hidden_size(o.load, LSTM_HIP_VOCAB, &err);
+        if (Nc == 0) die(err);
+        m.N = (uint32_t)Nc; // the prior decides the hidden size
+    }
+    long K = o.streams;
+    if (K == 0) K = (long)std::min<uint64_t>(kDefaultMaxStreams, std::max<uint64_t>(1, len / kBytesPerStream));
+    m.B = (uint32_t)K;
+    const std::vector<float> P = initial_params(m, o.load, o.in);
+    std::vector<uint64_t> off(K + 1);
+    for (long s = 0; s <= K; s++) off[s] = (uint64_t)((unsigned __int128)s * len / (unsigned)K);
+    uint64_t cap = 0;
+    for (long s = 0; s < K; s++) cap += lstm_hip_code_bound(off[s + 1] - off[s]);
+    std::vector<uint8_t> code(cap ? cap : 1);
+    std::vector<uint64_t> code_off(K + 1);
+    std::vector<double> bits(K);
+    Identity id;
+    lstm_hip_t *h = make_adaptive_handle(m, P, o.device, id);
+    CK(lstm_hip_encode_adaptive(h, text.data(), off.data(), m.lr, code.data(), cap, code_off.data(), bits.data(), nullptr, nullptr));
+    CK(lstm_hip_destroy(h));
+
+    std::vector<uint8_t> out;
+    put32(out, kMagicAdaptive);
+    put32(out, kFormatAdaptive);
+    put32(out, lstm_hip_coder_version());
+    put32(out, lstm_hip_adaptive_version());
+    put32(out, m.N);
+    put32(out, m.S);
+    put32(out, m.B);
+    put32(out, m.flags);
+    put64(out, dbits(m.lr));
+    put32(out, m.opt);
+    put32(out, m.prior);
+    put64(out, dbits(m.beta1));
+    put64(out, dbits(m.beta2));
+    put64(out, dbits(m.eps));
+    put64(out, dbits(m.wd));
+    put64(out, dbits(m.clip));
+    put32(out, m.seed);
+    put32(out, (uint32_t)id.cus);
+    put64(out, fnv1a(P));
+    put64(out, len);
+    put32(out, crc32(text));
+    put32(out, 0);
+    out.insert(out.end(), id.name, id.name + kNameBytes);
+    out.insert(out.end(), id.plan, id.plan + kPlanBytes);
+    if (out.size() != kHeaderAdaptive) die("internal: adaptive header size");
+    for (long s = 0; s < K; s++) put64(out, code_off[s + 1] - code_off[s]);
+    out.insert(out.end(), code.begin(), code.begin() + code_off[K]);
+    write_file(o.out, out);
+    double sum = 0.0;
+    for (double b : bits) sum += b;
+    const double n = len ? (double)len : 1.0;
+    printf("in %llu bytes, out %zu bytes, code %llu bytes in %ld streams, %lld trained blocks: %.5f bits/char (model %.5f bits/char)\n",
+           (unsigned long long)len, out.size(), (unsigned long long)code_off[K], K,
+           (long long)lstm_hip_adaptive_blocks((int32_t)m.S, (int32_t)m.B, off.data()), 8.0 * (double)code_off[K] / n, sum / n);
+}
+
+void decompress_adaptive(const Options &o) {
+    std::vector<uint8_t> in;
+    if (!read_file(o.in, in)) die("cannot read " + o.in);
+    if (in.size() >= 4 && get32(&in[0]) == kMagic) die(o.in + ": a static lstm_compress file (LHAC): decode it with --load PREFIX -d");
+    if (in.size() < kHeaderAdaptive) die(o.in + ": truncated header (" + std::to_string(in.size()) + " bytes)");
+    if (get32(&in[0]) != kMagicAdaptive) die(o.in + ": not an adaptive lstm_compress file (bad magic)");
+    if (get32(&in[4]) != kFormatAdaptive)
+        die(o.in + ": container format " + std::to_string(get32(&in[4])) + ", this program reads " + std::to_string(kFormatAdaptive));
+    if (get32(&in[8]) != lstm_hip_coder_version())
+        die(o.in + ": coder version " + std::to_string(get32(&in[8])) + ", this library codes version " + std::to_string(lstm_hip_coder_version()));
+    if (get32(&in[12]) != lstm_hip_adaptive_version())
+        die(o.in + ": adaptive version " + std::to_string(get32(&in[12])) + ", this library codes version " +
+            std::to_string(lstm_hip_adaptive_version()));
+    Adaptive m;
+    m.N = get32(&in[16]), m.S = get32(&in[20]), m.B = get32(&in[24]), m.flags = get32(&in[28]);
+    m.lr = bits_to_double(get64(&in[32]));
+    m.opt = get32(&in[40]), m.prior = get32(&in[44]);
+    m.beta1 = bits_to_double(get64(&in[48])), m.beta2 = bits_to_double(get64(&in[56]));
+    m.eps = bits_to_double(get64(&in[64])), m.wd = bits_to_double(get64(&in[72]));
+    m.clip = bits_to_double(get64(&in[80]));
+    m.seed = get32(&in[88]);
+    const uint32_t cus = get32(&in[92]), crc = get32(&in[112]);
+    const uint64_t hash = get64(&in[96]), len = get64(&in[104]);
+    if (m.N < 1 || m.N > 16384) die(o.in + ": hidden size " + std::to_string(m.N) + " outside [1, 16384]");
+    if (m.S < 2 || m.S > (1u << 16)) die(o.in + ": window of " + std::to_string(m.S) + " columns outside [2, 65536]");
+    if (m.B < 1 || m.B > 4096) die(o.in + ": stream count " + std::to_string(m.B) + " outside [1, 4096]");
+    if ((m.flags & ~kKnownFlags) || !(m.flags & LSTM_HIP_PAD_HIDDEN)) die(o.in + ": unknown flags " + std::to_string(m.flags));
+    if (!std::isfinite(m.lr) || m.lr < 0.0) die(o.in + ": corrupt learning rate");
+    if (m.opt != LSTM_HIP_OPT_ADAGRAD && m.opt != LSTM_HIP_OPT_ADAM) die(o.in + ": unknown optimizer kind " + std::to_string(m.opt));
+    if (m.prior > 1) die(o.in + ": corrupt prior field");
+    if (std::isnan(m.clip) || m.clip < 0.0) die(o.in + ": corrupt clip norm");
+    const uint32_t K = m.B;
+    if (in.size() < kHeaderAdaptive + 8ull * K) die(o.in + ": truncated header (" + std::to_string(in.size()) + " bytes)");
+    std::vector<uint64_t> code_off(K + 1, 0), text_off(K + 1);
+    for (uint32_t s = 0; s < K; s++) {
+        const uint64_t n = get64(&in[kHeaderAdaptive + 8 * s]);
+        if (n > in.size()) die(o.in + ": corrupt code length");
+        code_off[s + 1] = code_off[s] + n;
+    }
+    const uint64_t have = in.size() - kHeaderAdaptive - 8ull * K;
+    if (code_off[K] != have) die(o.in + ": " + std::to_string(have) + " code bytes, the header says " + std::to_string(code_off[K]));
+    for (uint32_t s = 0; s <= K; s++) text_off[s] = (uint64_t)((unsigned __int128)s * len / K);
+    if (m.prior && o.load.empty()) die(o.in + ": coded with a checkpoint as prior: give it with --load PREFIX");
+    if (!m.prior && !o.load.empty()) die(o.in + ": coded from the seeded initialisation, not from a checkpoint: drop --load");
+    const std::vector<float> P = initial_params(m, o.load, o.in + ": coded with");
+    if (fnv1a(P) != hash) die(o.in + ": the initial parameters differ from the coder's (parameter hash differs)");
+
+    std::vector<uint8_t> text(len ? len : 1);
+    Identity id;
+    lstm_hip_t *h = make_adaptive_handle(m, P, o.device, id);
+    char name[kNameBytes + 1] = {}, plan[kPlanBytes + 1] = {};
+    memcpy(name, &in[120], kNameBytes);
+    memcpy(plan, &in[120 + kNameBytes], kPlanBytes);
+    if (strncmp(name, id.name, kNameBytes) != 0)
+        die(o.in + ": coded on device name '" + name + "', this device is '" + id.name + "' (the training sums would differ)");
+    if ((int32_t)cus != id.cus)
+        die(o.in + ": coded with a CU count of " + std::to_string(cus) + ", this device has " + std::to_string(id.cus));
+    if (strncmp(plan, id.plan, kPlanBytes) != 0)
+        die(o.in + ": coded with plan identity '" + plan + "', this library and device choose '" + id.plan + "'");
+    CK(lstm_hip_decode_adaptive(h, in.data() + kHeaderAdaptive + 8ull * K, code_off.data(), text_off.data(), m.lr, text.data()));
+    CK(lstm_hip_destroy(h));
+    text.resize(len);
+    if (crc32(text) != crc) die(o.in + ": CRC32 of the decoded text differs; " + o.out + " not written");
+    write_file(o.out, text);
+}
+
 } // namespace
 
 int main(int argc, char **argv) {
     const Options o = parse(argc, argv);
+    if (o.adapt) {
+        if (o.mode == 'c') compress_adaptive(o);
+        else decompress_adaptive(o);
+        return 0;
+    }
     if (o.mode == 'c') compress(o);
     else decompress(o);
     return 0;

@@ -57,6 +57,8 @@ SYMBOLS = [
     "lstm_hip_kernel_stat", "lstm_hip_reset_kernel_stats", "lstm_hip_device_info", "lstm_hip_debug_stamps",
     "lstm_hip_set_grad_clip", "lstm_hip_get_grad_norms", "lstm_hip_set_optimizer", "lstm_hip_get_optimizer_steps",
     "lstm_hip_set_optimizer_steps", "lstm_hip_coder_version", "lstm_hip_code_bound", "lstm_hip_encode", "lstm_hip_decode",
+    "lstm_hip_adaptive_version", "lstm_hip_adaptive_blocks", "lstm_hip_encode_adaptive", "lstm_hip_decode_adaptive",
+    "lstm_hip_plan_identity",
 ]
 
 
@@ -76,6 +78,10 @@ def load_library():
     lib.lstm_hip_coder_version.argtypes = []
     lib.lstm_hip_code_bound.restype = C.c_size_t
     lib.lstm_hip_code_bound.argtypes = [C.c_uint64]
+    lib.lstm_hip_adaptive_version.restype = C.c_uint32
+    lib.lstm_hip_adaptive_version.argtypes = []
+    lib.lstm_hip_adaptive_blocks.restype = C.c_int64
+    lib.lstm_hip_adaptive_blocks.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_uint64)]
     _lib = lib
     return lib
 
@@ -93,6 +99,21 @@ def coder_version():
 def code_bound(n):
     """lstm_hip_code_bound: the largest code a stream of n bytes can have (0 for n = 0, else 3n + 4)."""
     return int(load_library().lstm_hip_code_bound(int(n)))
+
+
+def adaptive_version():
+    """lstm_hip_adaptive_version: changes whenever the adaptive schedule or anything it calls changes a code."""
+    return int(load_library().lstm_hip_adaptive_version())
+
+
+def adaptive_blocks(S, B, text_off):
+    """lstm_hip_adaptive_blocks: floor(shortest stream / (S - 1)), the number of trained blocks; needs no device."""
+    off = np.ascontiguousarray(text_off, dtype=np.uint64)
+    assert off.size == B + 1, (off.size, B)
+    n = int(load_library().lstm_hip_adaptive_blocks(S, B, _ptr(off, C.c_uint64)))
+    if n < 0:
+        _chk(n)
+    return n
 
 
 def _bytes_list(texts):
@@ -391,6 +412,51 @@ class Lstm:
         _chk(self.lib.lstm_hip_decode(self._h, C.c_int32(streams), _ptr(data, C.c_uint8), _ptr(code_off, C.c_uint64),
                                       _ptr(text_off, C.c_uint64), _ptr(text, C.c_uint8)))
         return [text[int(text_off[s]):int(text_off[s + 1])].tobytes() for s in range(streams)]
+
+    def encode_adaptive(self, texts, lr, trace=False):
+        """lstm_hip_encode_adaptive: the handle's B streams coded block by block, the model trained on every block after it
+        was coded (this CHANGES the handle: parameters, optimizer state and step count, window, carry).  Returns (codes: list
+        of bytes, bits: float64 [B], block_bits: float64 [n_blocks + 1], the last entry the untrained tail's) and, with
+        trace, the uint32 [total bytes, 3] array of (cum, freq, total) in text order."""
+        parts = _bytes_list(texts)
+        assert len(parts) == self.B, (len(parts), self.B)
+        data, off = _offsets(parts)
+        n_blocks = adaptive_blocks(self.S, self.B, off)
+        cap = sum(code_bound(q.size) for q in parts)
+        code = np.zeros(max(cap, 1), np.uint8)
+        code_off = np.zeros(self.B + 1, np.uint64)
+        bits = np.zeros(self.B, np.float64)
+        block_bits = np.zeros(n_blocks + 1, np.float64)
+        tr = np.zeros((max(int(off[-1]), 1), 3), np.uint32) if trace else None
+        _chk(self.lib.lstm_hip_encode_adaptive(self._h, _ptr(data, C.c_uint8), _ptr(off, C.c_uint64), C.c_double(lr),
+                                               _ptr(code, C.c_uint8), C.c_uint64(cap), _ptr(code_off, C.c_uint64),
+                                               _ptr(bits, C.c_double), _ptr(block_bits, C.c_double),
+                                               _ptr(tr, C.c_uint32) if trace else None))
+        self._steps = n_blocks
+        codes = [code[int(code_off[s]):int(code_off[s + 1])].tobytes() for s in range(self.B)]
+        if trace:
+            return codes, bits, block_bits, tr[:int(off[-1])]
+        return codes, bits, block_bits
+
+    def decode_adaptive(self, codes, lengths, lr):
+        """lstm_hip_decode_adaptive on a handle identical to the encoder's before its call: stream s decodes lengths[s]
+        bytes from codes[s], and the handle ends as the encoder's did.  Returns a list of bytes."""
+        parts = _bytes_list(codes)
+        assert len(parts) == self.B and len(lengths) == self.B, (len(parts), len(lengths), self.B)
+        data, code_off = _offsets(parts)
+        text_off = np.zeros(self.B + 1, np.uint64)
+        text_off[1:] = np.cumsum([int(n) for n in lengths])
+        text = np.zeros(max(int(text_off[-1]), 1), np.uint8)
+        _chk(self.lib.lstm_hip_decode_adaptive(self._h, _ptr(data, C.c_uint8), _ptr(code_off, C.c_uint64),
+                                               _ptr(text_off, C.c_uint64), C.c_double(lr), _ptr(text, C.c_uint8)))
+        self._steps = adaptive_blocks(self.S, self.B, text_off)
+        return [text[int(text_off[s]):int(text_off[s + 1])].tobytes() for s in range(self.B)]
+
+    def plan_identity(self):
+        """lstm_hip_plan_identity: what of the engine plan decides the order of a training window's sums."""
+        buf = C.create_string_buffer(256)
+        _chk(self.lib.lstm_hip_plan_identity(self._h, buf, C.c_size_t(256)))
+        return buf.value.decode()
 
     def debug_stamps(self):
         out = np.zeros((4, self.S, 16), np.uint64)  # [fwd wg0, fwd wg1, bwd wg0, bwd wg1][step][slot]

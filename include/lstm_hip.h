@@ -279,6 +279,52 @@ int lstm_hip_encode(lstm_hip_t *h, int32_t streams, const uint8_t *text, const u
 int lstm_hip_decode(lstm_hip_t *h, int32_t streams, const uint8_t *code, const uint64_t *code_off, const uint64_t *text_off,
                     uint8_t *text);
 
+/* ---- adaptive coding: no checkpoint, the model trains on the bytes it has coded.  The handle's B
+ *      streams are the coder's streams: stream s is text[text_off[s] .. text_off[s+1]), s < cfg.B (at most 4096).  With
+ *      L = S - 1 and n_blocks = floor(min_s len_s / L) (lstm_hip_adaptive_blocks) both calls run this schedule:
+ *        reset       window to empty columns, every state column of H and C to zero, coder state (h, c) of every stream to zero
+ *        block k     code pass: bytes [kL, (k+1)L) of every stream, one step at a time, with the CURRENT fp32 parameters:
+ *                    exactly lstm_hip_encode's rule per step (distribution, quantisation, coder; then the recurrence step on
+ *                    the byte), the coder's (h, c) and range coder state carried over from block k-1; the image of U the
+ *                    step kernel reads is remade from the parameters first.
+ *                    train pass: one training window on those same bytes, exactly what lstm_hip_train_windows(1, lr) does
+ *                    on a handle with lstm_hip_set_stride(S-1, S-1) whose cursors stood at text_off[s] + kL: window row t
+ *                    holds target byte kL+t-1 and input byte kL+t-2 of the stream (empty before the stream's start), h[0],
+ *                    c[0] <- column S-1, forward, loss, backward, clip if set, the handle's optimizer step with its own
+ *                    step count.  The train pass runs on the engine the handle's plan chose.
+ *        tail        the remaining bytes of every stream, coded, not trained on
+ *        flush       4 bytes per non-empty stream, as lstm_hip_encode
+ *      The decoder trains on the bytes it has decoded and so holds the encoder's parameters at every step, PROVIDED it starts
+ *      from an identical handle: same config and flags, parameters, optimizer kind / numbers / state / step count, clip
+ *      setting, learning_rate, and the same engine plan on the same kind of device (lstm_hip_plan_identity, the device's
+ *      name and CU count: they decide the order of the training sums).  A code decodes only with the same
+ *      lstm_hip_coder_version AND lstm_hip_adaptive_version (bumped when the schedule or anything it calls changes a code).
+ *      The coder's (h, c) and the trainer's carry are two separate states.  Parameters that have gone non-finite keep
+ *      coding (q = 1 for NaN), so a diverged run still round-trips; it stops compressing.
+ *      Unlike the static calls these CHANGE the handle: parameters, gradients, optimizer state and step count, window, rings
+ *      and carry are those of the last train pass (the model after the call is the adapted one).  The stride, loss mode,
+ *      text and cursors set by the caller are neither read nor written: they stay as they are.  With clipping on,
+ *      lstm_hip_get_grad_norms afterwards returns the n_blocks pre-clip norms of the call's train passes.
+ *      code_cap, the offsets' checks and the device error bits are those of lstm_hip_encode / lstm_hip_decode;
+ *      learning_rate must be finite and >= 0 (0 still runs the train pass); a handle with a communicator is LSTM_HIP_ESTATE.
+ *      A truncated or damaged code decodes to the requested lengths; from the block after the first wrong byte on the decoder
+ *      trains on other bytes than the encoder did, so every stream may differ from there (a container's checksum catches it). */
+uint32_t lstm_hip_adaptive_version(void);
+/* n_blocks of the schedule above; needs no device.  < 0 (LSTM_HIP_EINVAL): S < 2, B < 1, offsets missing, not starting at
+ * 0 or decreasing */
+int64_t lstm_hip_adaptive_blocks(int32_t S, int32_t B, const uint64_t *text_off);
+/* bits (may be NULL): per stream, as lstm_hip_encode.  block_bits (may be NULL): n_blocks + 1 doubles, the ideal bits of all
+ * streams in each block's code pass, the last one the tail's.  trace (may be NULL): as lstm_hip_encode. */
+int lstm_hip_encode_adaptive(lstm_hip_t *h, const uint8_t *text, const uint64_t *text_off, double learning_rate,
+                             uint8_t *code, uint64_t code_cap, uint64_t *code_off, double *bits, double *block_bits,
+                             uint32_t *trace);
+int lstm_hip_decode_adaptive(lstm_hip_t *h, const uint8_t *code, const uint64_t *code_off, const uint64_t *text_off,
+                             double learning_rate, uint8_t *text);
+/* a short text naming everything of the handle's engine plan that decides the order of a training window's sums (internal
+ * width, the form of each recurrence, column grouping, split counts): two handles train to the same bits only when it, the
+ * device name and the CU count agree.  cap >= 128 is enough. */
+int lstm_hip_plan_identity(lstm_hip_t *h, char *buf, size_t cap);
+
 /* ---- measurement.  With profiling on, every kernel launch is bracketed by HIP events on the
  *      handle's stream and per-kernel totals accumulate. */
 int lstm_hip_synchronize(lstm_hip_t *h);
