@@ -194,6 +194,7 @@ void pack_bf16(const float *src, size_t n, unsigned short *dst, hipStream_t st);
 // colloss[col] = -log2 p[target] (0 for an empty target); dby_part[wave][256] partial row sums of dY.
 // stable: the max-shifted form of LSTM_HIP_STABLE_SOFTMAX (probs = exp(z - max z)/sum, log-sum-exp surprisal).
 // Processes columns [col0, col1) (col0 a multiple of 8) with global indexing, so a window can be done in time chunks.
+// P null: the probabilities are not stored (dy, the losses and the dby partials are unchanged).
 int softmax_parts(int T);
 void softmax_loss_dy(float *Y, float *P, const float *by, const int32_t *ti, float *colloss, float *dby_part, int col0,
                      int col1, bool stable, hipStream_t st); // stable: LSTM_HIP_STABLE_SOFTMAX (kernels.hip)
@@ -216,14 +217,30 @@ void dW_sums(const float *DG, int T, int G4, float *dW, float *db, void *scratch
 
 // ---- Adagrad over the flat block (R/lstm.cc:261-272; eps added in double, :25,46-48)
 // the NEXT window's slide (slide_window's arguments), carried by an Adagrad launch in extra workgroups: inside the window loop
-// the slide of window i+1 needs nothing Adagrad of window i produces and touches nothing it reads
+// the slide of window i+1 needs nothing Adagrad of window i produces and touches nothing it reads.  Several workgroups share
+// it without waiting for each other, so the cursors and the ring head are read from pos / headp and the new ones written to
+// pos_out / head_out (other memory: the caller flips its live copies after the launch); the result is slide_window's.
 struct SlideJob {
     const uint8_t *text;
     uint64_t len;
-    uint64_t *pos;
-    int32_t *Xr, *Tr, *headp, *xi, *ti;
+    const uint64_t *pos;
+    int32_t *Xr, *Tr;
+    const int32_t *headp;
+    int32_t *xi, *ti;
     float *H, *C;
     int S, B, N, stride, carry_col;
+    uint64_t *pos_out;
+    int32_t *head_out;
+};
+// the window's loss sum and dby fold (loss_reduce's arguments), carried by the update launch of the same window in extra
+// workgroups: same sums in the same order; dby goes to dP and the carrying workgroups update by themselves
+struct TailJob {
+    const float *colloss;
+    int steps, B, B_global;
+    float scale;
+    double *loss_out;
+    const float *dby_part;
+    int n_parts;
 };
 // One Adagrad launch: the update of the flat block P / dP / mem (n floats, U at float offset u_off) and what it carries:
 //  - the live images of U, refreshed from the updated block: fp32 Ufwd / Ubwd (16x16x4 tiles) and Ufwd4 / Ubwd4 in the
@@ -232,7 +249,8 @@ struct SlideJob {
 //  - gpart != null: the gradient still in pieces -- n_groups partial blocks [dW | - | db | dWhy] group_stride floats apart and,
 //    when slabs != null, n_slabs split-K slabs of dU slab_stride floats apart; they are summed here in the order the separate
 //    folds use and the sums are also stored to dP (by_off: float offset of dby, final in dP)
-//  - slide: the next window's slide (or null); quad: the two-half images (Ufwd4 + Ubwd4 with half_forms 5, or uf6b) are
+//  - skip_dP_store: the sums of the pieces are used but not stored (nobody reads dP before the next window overwrites it)
+//  - tail: this window's loss sum and dby fold (or null; needs by_off); slide: the next window's slide (or null); quad: the two-half images (Ufwd4 + Ubwd4 with half_forms 5, or uf6b) are
 //    written through quad transposes
 //  - v != null: the update is Adam with decoupled weight decay (lstm_hip_set_optimizer) instead of Adagrad: mem holds the
 //    first moment m, v the second moment, and `adam` the step's scalars, computed in double on the host and narrowed:
@@ -260,6 +278,8 @@ struct AdagradJob {
     int n_groups, n_slabs;
     size_t group_stride, slab_stride, by_off;
     const SlideJob *slide;
+    const TailJob *tail;
+    bool skip_dP_store;
     bool quad;
     const float *clip; // global-norm clipping: the coefficient grad_norm wrote (the step uses d * coef where coef < 1); null: off
     float *v;          // Adam's second moment (n floats); null: Adagrad

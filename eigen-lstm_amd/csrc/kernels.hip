@@ -600,7 +600,7 @@ __global__ __launch_bounds__(256) void k_softmax_loss_dy(float *__restrict__ Y, 
         p.y = e.y / s;
         p.z = e.z / s;
         p.w = e.w / s;
-        reinterpret_cast<float4 *>(P + (size_t)col * 256)[l] = p;
+        if (P != nullptr) reinterpret_cast<float4 *>(P + (size_t)col * 256)[l] = p; // (null: nobody will read this window's)
         const int tk = ti[col];
         float4 d = p;
         if (tk >= 0 && (tk >> 2) == l) {
@@ -656,12 +656,13 @@ void softmax_loss_dy(float *Y, float *P, const float *by, const int32_t *ti, flo
 // loss += surprisals.sum() / B per step (OV/lstm_eigen_opt/lstm.cc:249): float sum over the columns
 // of a step, divided by the (global) batch, accumulated over steps in double.
 // block 0: window loss; blocks 1..4 (when dby != null): dby = rowsum(dY) from the per-wave partials, 64 rows each
-__global__ __launch_bounds__(1024) void k_loss_dby(const float *__restrict__ colloss, int steps, int B, int Bg,
-                                                   double *__restrict__ out, const float *__restrict__ dby_part,
-                                                   int n_parts, float *__restrict__ dby, float scale) {
-    __shared__ float4 red[16][64];
-    if (blockIdx.x >= 1) { // 16 float4 row groups x 64 phases; phases folded in order
-        const int m4 = (blockIdx.x - 1) * 16 + (threadIdx.x & 15), ph = threadIdx.x >> 4;
+// (both parts as device functions of any workgroup size that divides 1024: the window loop's update launch runs them in
+// extra 256-thread workgroups, k_adagrad<.., EXTRA>; slot e of the 1024 is taken by thread e % blockDim.x, so the sums and
+// their order do not depend on the workgroup size)
+// dby rows 16*grp .. 16*grp+15 (float4 groups); red: 1024 float4.  Threads 0..15 return the sum of float4 group 16*grp + tid.
+__device__ __forceinline__ float4 dby_fold_body(const float *__restrict__ dby_part, int n_parts, int grp, float4 *r) {
+    for (int e = threadIdx.x; e < 1024; e += blockDim.x) { // 16 float4 row groups x 64 phases; phases folded in order
+        const int m4 = grp * 16 + (e & 15), ph = e >> 4;
         float4 s = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll 4
         for (int p = ph; p < n_parts; p += 64) {
@@ -671,46 +672,60 @@ __global__ __launch_bounds__(1024) void k_loss_dby(const float *__restrict__ col
             s.z += v.z;
             s.w += v.w;
         }
-        float4 *r = &red[0][0];
-        r[ph * 16 + (threadIdx.x & 15)] = s;
-        __syncthreads();
-        if (ph == 0) {
-            float4 t = r[threadIdx.x & 15];
-            for (int i = 1; i < 64; i++) {
-                const float4 v = r[i * 16 + (threadIdx.x & 15)];
-                t.x += v.x;
-                t.y += v.y;
-                t.z += v.z;
-                t.w += v.w;
+        r[ph * 16 + (e & 15)] = s;
+    }
+    __syncthreads();
+    float4 t = {0.f, 0.f, 0.f, 0.f};
+    if (threadIdx.x < 16) {
+        t = r[threadIdx.x];
+        for (int i = 1; i < 64; i++) {
+            const float4 v = r[i * 16 + threadIdx.x];
+            t.x += v.x;
+            t.y += v.y;
+            t.z += v.z;
+            t.w += v.w;
+        }
+    }
+    return t;
+}
+// loss: slot j of 1024 walks the B columns of steps j, j + 1024, ... in order (the reference's float sum over a step's
+// columns, OV/lstm_eigen_opt/lstm.cc:249) with 8 loads in flight; steps are then added in order in double.  part: 1024 doubles.
+__device__ __forceinline__ void loss_sum_body(const float *__restrict__ colloss, int steps, int B, int Bg, float scale,
+                                              double *__restrict__ out, double *part) {
+    for (int j = threadIdx.x; j < 1024 && j < steps; j += blockDim.x) {
+        double acc = 0.0;
+        for (int t = j; t < steps; t += 1024) {
+            const float *cl = colloss + (size_t)t * B;
+            float s = 0.0f;
+            int b = 0;
+            for (; b + 8 <= B; b += 8) {
+                const float v0 = cl[b], v1 = cl[b + 1], v2 = cl[b + 2], v3 = cl[b + 3], v4 = cl[b + 4], v5 = cl[b + 5],
+                            v6 = cl[b + 6], v7 = cl[b + 7];
+                s = (((((((s + v0) + v1) + v2) + v3) + v4) + v5) + v6) + v7;
             }
-            reinterpret_cast<float4 *>(dby)[m4] = t;
+            for (; b < B; b++) s += cl[b];
+            acc += (double)((s * scale) / (float)Bg); // scale: 1 (bits) or ln 2 (nats, last-step mode)
         }
-        return;
+        part[j] = acc;
     }
-    // loss: one thread per timestep walks its B columns in order (the reference's float sum over a step's
-    // columns, OV/lstm_eigen_opt/lstm.cc:249) with 8 loads in flight; steps are then added in order in double
-    double *part = reinterpret_cast<double *>(&red[0][0]);
-    double acc = 0.0;
-    for (int t = threadIdx.x; t < steps; t += blockDim.x) {
-        const float *cl = colloss + (size_t)t * B;
-        float s = 0.0f;
-        int b = 0;
-        for (; b + 8 <= B; b += 8) {
-            const float v0 = cl[b], v1 = cl[b + 1], v2 = cl[b + 2], v3 = cl[b + 3], v4 = cl[b + 4], v5 = cl[b + 5],
-                        v6 = cl[b + 6], v7 = cl[b + 7];
-            s = (((((((s + v0) + v1) + v2) + v3) + v4) + v5) + v6) + v7;
-        }
-        for (; b < B; b++) s += cl[b];
-        acc += (double)((s * scale) / (float)Bg); // scale: 1 (bits) or ln 2 (nats, last-step mode)
-    }
-    part[threadIdx.x] = acc;
     __syncthreads();
     if (threadIdx.x == 0) {
         double tot = 0.0;
-        const int n = steps < (int)blockDim.x ? steps : (int)blockDim.x;
+        const int n = steps < 1024 ? steps : 1024;
         for (int i = 0; i < n; i++) tot += part[i];
         out[0] = tot;
     }
+}
+__global__ __launch_bounds__(1024) void k_loss_dby(const float *__restrict__ colloss, int steps, int B, int Bg,
+                                                   double *__restrict__ out, const float *__restrict__ dby_part,
+                                                   int n_parts, float *__restrict__ dby, float scale) {
+    __shared__ float4 red[16][64];
+    if (blockIdx.x >= 1) {
+        const float4 t = dby_fold_body(dby_part, n_parts, blockIdx.x - 1, &red[0][0]);
+        if (threadIdx.x < 16) reinterpret_cast<float4 *>(dby)[(blockIdx.x - 1) * 16 + threadIdx.x] = t;
+        return;
+    }
+    loss_sum_body(colloss, steps, B, Bg, scale, out, reinterpret_cast<double *>(&red[0][0]));
 }
 void loss_reduce(const float *colloss, int steps, int B, int B_global, double *out, const float *dby_part, int n_parts,
                  float *dby, hipStream_t st, float scale) {
@@ -1079,51 +1094,89 @@ __device__ __forceinline__ float adam1(float p, float d, float &m, float &v, con
 // the split-K slabs of the dU product -- and is summed here, in the order gemm_fold / k_gemm_reduce use (bit-identical),
 // then also stored to dP.  Saves three reduction launches and a round trip of the sums (single-GPU loop only: an
 // all-reduce needs the summed block first).
-// (k_slide_window's body once more as a device function: the window loop's Adagrad launch carries the NEXT window's slide in
-// extra workgroups for short windows, k_adagrad<.., SLIDE>)
+// EXTRA: the window loop's launch carries, in extra workgroups at the LOWEST block indices (dispatched first, so they end inside
+// the update's own time), work that nothing inside the window waits for:
+//  - the window's loss sum and dby fold (TailArgs; k_loss_dby's two parts, same sums in the same order), with the update of by
+//    done by the folding workgroups themselves (the main grid leaves that range alone);
+//  - the NEXT window's slide (SlideArgs; k_slide_window's result, bit for bit), spread over several workgroups.
+// There is no grid-wide wait and the extra workgroups need not be co-resident, so no workgroup reads what another one of the
+// same launch writes: the cursors and the ring head are double-buffered (read from pos / headp, written to pos_out / head_out
+// by the one owner workgroup, which also writes the new ring rows; the host flips the live copies), and the workgroups that
+// rebuild the flat xi / ti read only ring rows the owner does not write -- rows `stride` .. S-1 behind the old head -- and
+// recompute the `stride` newest entries of a column from the text and the old cursor themselves.
 struct SlideArgs {
     const uint8_t *text; // null: nothing to do
     uint64_t len;
-    uint64_t *pos;
-    int32_t *Xr, *Tr, *headp, *xi, *ti;
+    const uint64_t *pos;
+    uint64_t *pos_out;
+    int32_t *Xr, *Tr;
+    const int32_t *headp;
+    int32_t *head_out, *xi, *ti;
     float *H, *C;
     int S, B, NB4, stride, carry_col;
+    int idx_blocks, copy_blocks; // workgroups: [idx_blocks: flat indices][1: owner][copy_blocks: carry]
 };
-__device__ __forceinline__ void slide_body(const SlideArgs &a, int bid, int nblk) {
-    if (bid > 0) { // carry: column 0 of the next window is column `carry_col` of this one (opt:205-206: 1)
+struct TailArgs {
+    const float *colloss; // null: nothing to do
+    int steps, B, Bg;
+    float scale;
+    double *loss_out;
+    const float *dby_part;
+    int n_parts;
+};
+constexpr int TAIL_BLOCKS = 5; // loss, four dby groups (k_loss_dby's grid)
+__device__ __forceinline__ void slide_body(const SlideArgs &a, int bid) {
+    const int S = a.S, B = a.B;
+    if (bid > a.idx_blocks) { // carry: column 0 of the next window is column `carry_col` of this one (opt:205-206: 1)
         const size_t src = (size_t)a.carry_col * a.NB4;
-        for (int i = (bid - 1) * blockDim.x + threadIdx.x; i < a.NB4; i += (nblk - 1) * blockDim.x) {
+        for (int i = (bid - a.idx_blocks - 1) * blockDim.x + threadIdx.x; i < a.NB4; i += a.copy_blocks * blockDim.x) {
             reinterpret_cast<float4 *>(a.H)[i] = reinterpret_cast<const float4 *>(a.H)[src + i];
             reinterpret_cast<float4 *>(a.C)[i] = reinterpret_cast<const float4 *>(a.C)[src + i];
         }
         return;
     }
-    const int S = a.S, B = a.B;
-    int head = *a.headp;
-    for (int b = threadIdx.x; b < B; b += blockDim.x) {
-        uint64_t p = a.pos[b];
-        int hd = head;
-        for (int k = 0; k < a.stride; k++) { // stride > 1: the segment variant advances several bytes per window
-            hd = (hd + 1) % S;
-            const int last = (hd + S - 1) % S, prev = (hd + S - 2) % S;
-            const int event = a.text[p];
-            p++;
-            if (p >= a.len) p = (uint64_t)S;
-            a.Tr[last * B + b] = event;
-            a.Xr[last * B + b] = a.Tr[prev * B + b];
+    const int head = *a.headp;
+    const int newest = (head + S - 1) % S; // ring row of the window's last step: x of the first new entry is its target
+    if (bid == a.idx_blocks) {             // owner: cursors, head and the ring rows that fall off (head .. head+stride-1)
+        for (int b = threadIdx.x; b < B; b += blockDim.x) {
+            uint64_t p = a.pos[b];
+            int x = a.Tr[newest * B + b];
+            for (int k = 0; k < a.stride; k++) { // stride > 1: the segment variant advances several bytes per window
+                const int last = (head + k) % S;
+                const int event = a.text[p];
+                p++;
+                if (p >= a.len) p = (uint64_t)S;
+                a.Tr[last * B + b] = event;
+                a.Xr[last * B + b] = x;
+                x = event;
+            }
+            a.pos_out[b] = p;
         }
-        a.pos[b] = p;
+        if (threadIdx.x == 0) *a.head_out = (head + a.stride) % S;
+        return;
     }
-    head = (head + a.stride) % S;
-    __syncthreads();
-    for (int i = threadIdx.x; i < S * B; i += blockDim.x) {
+    const int keep = S - a.stride; // steps of the new window that were steps of the old one
+    for (int i = bid * blockDim.x + threadIdx.x; i < S * B; i += a.idx_blocks * blockDim.x) {
         const int t = i / B, b = i - t * B;
-        const int row = (head + t) % S;
-        a.xi[i] = a.Xr[row * B + b];
-        a.ti[i] = a.Tr[row * B + b];
+        int x, tg;
+        if (t < keep) {
+            const int row = (head + a.stride + t) % S;
+            x = a.Xr[row * B + b];
+            tg = a.Tr[row * B + b];
+        } else {
+            uint64_t p = a.pos[b];
+            x = a.Tr[newest * B + b];
+            tg = 0;
+            for (int k = 0; k <= t - keep; k++) {
+                if (k > 0) x = tg;
+                tg = a.text[p];
+                p++;
+                if (p >= a.len) p = (uint64_t)S;
+            }
+        }
+        a.xi[i] = x;
+        a.ti[i] = tg;
     }
-    __syncthreads();
-    if (threadIdx.x == 0) *a.headp = head;
 }
 struct GradFold {
     const float *gpart;  // null: no fold
@@ -1139,8 +1192,10 @@ struct GradFold {
     int uf6_uw;
     unsigned short *why_b, *whyT_b; // bf16 path: Why as bf16 in place order [hidden][256] and transposed [256][hidden]; or null
     size_t why_off4, why_n4;        // float4 range of Why in the flat block
-    SlideArgs slide;                // the next window's slide, done by the workgroups past ada_blocks (text null: none)
-    int ada_blocks;
+    SlideArgs slide;                // EXTRA: the next window's slide (text null: none)
+    TailArgs tail;                  // EXTRA: this window's loss sum and dby fold (colloss null: none)
+    int extra_blocks;               // EXTRA: workgroups in front of the update's own: [tail][slide]
+    int store_dp;                   // FOLD: also store the summed gradient to dP (0: nobody will read this window's)
 };
 template <int CTRL> __device__ __forceinline__ float quad_dpp(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
@@ -1153,7 +1208,7 @@ template <int CTRL> __device__ __forceinline__ float quad_dpp(float v) {
 // *clip is below 1 (the summed gradient is in dP by then: k_grad_sumsq did the fold, so FOLD is false with CLIP).
 // ADAM (lstm_hip_set_optimizer): the step is adam1 with m in `mem` and the second moment in v, at the same (QUAD-remapped)
 // index; everything else -- fold, clip, images, slide -- as for Adagrad.  The Adagrad instantiations never read v or adam.
-template <bool FOLD, bool SLIDE = false, bool QUAD = false, bool CLIP = false, bool ADAM = false>
+template <bool FOLD, bool EXTRA = false, bool QUAD = false, bool CLIP = false, bool ADAM = false>
 __global__ __launch_bounds__(256) void k_adagrad(float *__restrict__ P, float *__restrict__ dP,
                                                  float *__restrict__ mem, size_t n4, float lr, size_t u_off4, int N,
                                                  float4 *__restrict__ Ufwd, float4 *__restrict__ Ubwd,
@@ -1161,14 +1216,51 @@ __global__ __launch_bounds__(256) void k_adagrad(float *__restrict__ P, float *_
                                                  int half_forms, const float *__restrict__ clip, float *__restrict__ v,
                                                  AdamScalars adam) {
     static_assert(!(FOLD && CLIP), "with clipping the fold is done by k_grad_sumsq");
-    if (SLIDE && (int)blockIdx.x >= fold.ada_blocks) { // the next window's slide: touches nothing this launch reads or writes
-        slide_body(fold.slide, (int)blockIdx.x - fold.ada_blocks, (int)gridDim.x - fold.ada_blocks);
-        return;
+    const int first = EXTRA ? fold.extra_blocks : 0; // the update's own workgroups start here
+    if constexpr (EXTRA) {
+        if ((int)blockIdx.x < first) { // touches nothing the update's own workgroups read or write
+            const int n_tail = fold.tail.colloss != nullptr ? TAIL_BLOCKS : 0;
+            if ((int)blockIdx.x >= n_tail) {
+                slide_body(fold.slide, (int)blockIdx.x - n_tail);
+                return;
+            }
+            __shared__ float4 red[1024];
+            const TailArgs &t = fold.tail;
+            if (blockIdx.x == 0) {
+                loss_sum_body(t.colloss, t.steps, t.B, t.Bg, t.scale, t.loss_out, reinterpret_cast<double *>(red));
+                return;
+            }
+            // dby = rowsum(dY), 64 rows per workgroup, and the update of those entries of by (the last 64 float4s of the block)
+            const float4 d = dby_fold_body(t.dby_part, t.n_parts, (int)blockIdx.x - 1, red);
+            if (threadIdx.x < 16) {
+                const size_t i = fold.by_off4 + ((int)blockIdx.x - 1) * 16 + threadIdx.x;
+                reinterpret_cast<float4 *>(dP)[i] = d;
+                float4 p = reinterpret_cast<float4 *>(P)[i];
+                float4 m = reinterpret_cast<float4 *>(mem)[i];
+                if (ADAM) {
+                    float4 s = reinterpret_cast<float4 *>(v)[i];
+                    p.x = adam1(p.x, d.x, m.x, s.x, adam);
+                    p.y = adam1(p.y, d.y, m.y, s.y, adam);
+                    p.z = adam1(p.z, d.z, m.z, s.z, adam);
+                    p.w = adam1(p.w, d.w, m.w, s.w, adam);
+                    reinterpret_cast<float4 *>(v)[i] = s;
+                } else {
+                    p.x = adagrad1(p.x, d.x, m.x, lr);
+                    p.y = adagrad1(p.y, d.y, m.y, lr);
+                    p.z = adagrad1(p.z, d.z, m.z, lr);
+                    p.w = adagrad1(p.w, d.w, m.w, lr);
+                }
+                reinterpret_cast<float4 *>(P)[i] = p;
+                reinterpret_cast<float4 *>(mem)[i] = m;
+            }
+            return;
+        }
+        if (fold.tail.colloss != nullptr) n4 = fold.by_off4; // (by: done by the folding workgroups above)
     }
     const float coef = CLIP ? *clip : 1.0f;
-    const size_t stride_ = (size_t)(SLIDE ? fold.ada_blocks : (int)gridDim.x) * blockDim.x;
+    const size_t stride_ = (size_t)((int)gridDim.x - first) * blockDim.x;
     const size_t u_n4 = (size_t)N * N; // float4 count of U
-    for (size_t i0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i0 < n4; i0 += stride_) {
+    for (size_t i0 = (size_t)((int)blockIdx.x - first) * blockDim.x + threadIdx.x; i0 < n4; i0 += stride_) {
         size_t i = i0;
         int q_kb4 = 0;
         if (QUAD && i0 >= u_off4 && i0 < u_off4 + u_n4) { // (quads are aligned: every range of the flat block is a multiple of 4 float4s)
@@ -1195,7 +1287,7 @@ __global__ __launch_bounds__(256) void k_adagrad(float *__restrict__ P, float *_
                     d.z += q.z;
                     d.w += q.w;
                 }
-                reinterpret_cast<float4 *>(dP)[i] = d;
+                if (fold.store_dp) reinterpret_cast<float4 *>(dP)[i] = d;
             }
         } else {
             d = reinterpret_cast<const float4 *>(dP)[i];
@@ -1340,18 +1432,27 @@ void adagrad(const AdagradJob &j, hipStream_t st) {
     int blocks = (int)((n4 + 255) / 256);
     if (blocks > 2048) blocks = 2048;
     SlideArgs sl{};
+    TailArgs tail{};
     int extra = 0;
+    if (j.tail != nullptr) {
+        const TailJob &t = *j.tail;
+        tail = TailArgs{t.colloss, t.steps, t.B, t.B_global, t.scale, t.loss_out, t.dby_part, t.n_parts};
+        extra += TAIL_BLOCKS;
+    }
     if (j.slide != nullptr) {
         const SlideJob &s = *j.slide;
         const int nb4 = s.N * s.B / 4;
         int copy_blocks = (nb4 + 255) / 256;
         if (copy_blocks > 128) copy_blocks = 128;
-        sl = SlideArgs{s.text, s.len, s.pos, s.Xr, s.Tr, s.headp, s.xi, s.ti, s.H, s.C, s.S, s.B, nb4, s.stride, s.carry_col};
-        extra = 1 + copy_blocks;
+        int idx_blocks = (s.S * s.B + 255) / 256;
+        if (idx_blocks > 64) idx_blocks = 64;
+        sl = SlideArgs{s.text, s.len, s.pos, s.pos_out, s.Xr, s.Tr, s.headp, s.head_out, s.xi, s.ti, s.H, s.C, s.S, s.B, nb4,
+                       s.stride, s.carry_col, idx_blocks, copy_blocks};
+        extra += idx_blocks + 1 + copy_blocks;
     }
     const GradFold fold{j.gpart, j.n_groups, j.group_stride, j.by_off / 4, j.slabs, j.n_slabs, j.slab_stride,
                         reinterpret_cast<uint2 *>(j.u6b), j.u6_uw, reinterpret_cast<uint2 *>(j.uf6b), j.uf6_uw, j.why_b, j.whyT_b,
-                        j.why_off / 4, (size_t)256 * j.N / 4, sl, blocks};
+                        j.why_off / 4, (size_t)256 * j.N / 4, sl, tail, extra, j.skip_dP_store ? 0 : 1};
     blocks += extra;
     if (j.v != nullptr) launch_update<true>(j, fold, blocks, extra != 0, st);
     else launch_update<false>(j, fold, blocks, extra != 0, st);

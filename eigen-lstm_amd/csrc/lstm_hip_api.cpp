@@ -120,6 +120,13 @@ struct lstm_hip_ctx {
     void *Ufwd6b = nullptr;                       // two-half bf16 forward form: weights image
     unsigned short *Hxb = nullptr;                // ... and bf16 hand-off ring
     bool carry_slide = false, pre_slid = false;   // window loop: this Adagrad launch carries the next window's slide / it has been done
+    // window loops, single GPU, fused gradients, no clipping, not profiling (loop_window): the window's loss sum and dby fold ride
+    // in its update launch instead of a launch of their own, and only the loop's last window stores what nothing inside the
+    // loop reads -- the probabilities and the folded gradient
+    bool tail = false;                            // this window's loss / dby go with its update launch ...
+    double *tail_loss = nullptr;                  // ... the loss to here
+    bool keep_outputs = true;                     // this window stores Pr and the folded dP
+    bool pr_stale = false, dp_stale = false;      // Pr / dP do not hold the last window's values: get_activations / get_grads refuse
     bool dgt_written = false;                     // the backward recurrence wrote the transposed bf16 image of dg itself
     bool packed6b = false;                        // Ubwd6b is current (written by the Adagrad launch)
     bool packedf6b = false;                       // ... and Ufwd6b
@@ -166,7 +173,9 @@ struct lstm_hip_ctx {
     float *adam_v = nullptr;     // Adam's second moment (flat block); allocated when Adam is first selected
     uint8_t *text = nullptr;
     uint64_t text_len = 0;
-    uint64_t *pos = nullptr;
+    uint64_t *pos = nullptr;     // the live cursors and ring head: one half of pos_buf [2][B] / head_buf [2].  A slide carried
+    uint64_t *pos_buf = nullptr; // by an update launch reads the live half and writes the other, then the halves change roles
+    int32_t *head_buf = nullptr; // (do_adagrad)
     int32_t global_B = 0;
     lstm_hip_ctx *eval_h = nullptr; // internal B = 1 handle used by lstm_hip_eval_bits
     char *gen_scratch = nullptr;    // lstm_hip_generate's working memory: grows to the largest call, freed with the handle
@@ -361,8 +370,10 @@ int do_forward(lstm_hip_ctx *h) {
     } else
     RUN(K_GEMM_Y, gemm(false, false, 256, h->T, N, h->P + h->pl.Why, 256, h->H + (size_t)N * B, N,
                        h->Y + (size_t)256 * B, 256, 1, nullptr, h->st));
-    RUN(K_SOFTMAX, softmax_loss_dy(h->Y + (size_t)256 * B, h->Pr + (size_t)256 * B, h->P + h->pl.by, h->ti + B,
-                                   h->colloss, h->dby_part, 0, h->T, (h->cfg.flags & LSTM_HIP_STABLE_SOFTMAX) != 0, h->st));
+    h->pr_stale = h->in_loop && !h->keep_outputs;
+    RUN(K_SOFTMAX, softmax_loss_dy(h->Y + (size_t)256 * B, h->pr_stale ? nullptr : h->Pr + (size_t)256 * B, h->P + h->pl.by,
+                                   h->ti + B, h->colloss, h->dby_part, 0, h->T, (h->cfg.flags & LSTM_HIP_STABLE_SOFTMAX) != 0,
+                                   h->st));
     h->fwd_done = true;
     return 0;
 }
@@ -465,6 +476,7 @@ int do_backward(lstm_hip_ctx *h) {
     // Inside the single-GPU loop nobody reads the gradient block between here and Adagrad: the folds of the group
     // partials and of the dU slabs are left to the Adagrad launch (do_adagrad), three launches fewer per window.
     const bool defer_fold = fused && h->in_loop && !h->comm;
+    h->dp_stale = defer_fold && !h->keep_outputs;
     if (defer_fold) {
         h->fold_pending = true;
     } else if (fused) { // accumulated per column group inside the recurrence: fold the groups in order
@@ -580,8 +592,11 @@ int do_allreduce(lstm_hip_ctx *h) {
 int do_adagrad(lstm_hip_ctx *h, double lr, int64_t norm_idx) {
     const EnginePlan &p = h->plan;
     const int N = h->cfg.N;
+    uint64_t *pos_next = h->pos == h->pos_buf ? h->pos_buf + h->cfg.B : h->pos_buf;
+    int32_t *head_next = h->head == h->head_buf ? h->head_buf + 1 : h->head_buf;
     const SlideJob slide{h->text, h->text_len, h->pos, h->Xr, h->Tr, h->head, h->xi, h->ti, h->H, h->C,
-                         h->cfg.S, h->cfg.B, N, h->stride, h->carry_col};
+                         h->cfg.S, h->cfg.B, N, h->stride, h->carry_col, pos_next, head_next};
+    const TailJob tail{loss_src(h), loss_steps(h), h->cfg.B, h->global_B, loss_scale(h), h->tail_loss, h->dby_part, h->n_dby_parts};
     AdagradJob job{};
     job.P = h->P, job.dP = h->dP, job.mem = h->mem, job.n = h->pl.total, job.u_off = h->pl.U, job.N = N, job.lr = (float)lr;
     // The same launch refreshes every live image of U: the fp32 ones in the layouts of the plan's forms; on the bf16 path (whose
@@ -599,7 +614,11 @@ int do_adagrad(lstm_hip_ctx *h, double lr, int64_t norm_idx) {
         job.gpart = h->gpart, job.n_groups = (h->cfg.B + p.gpart_cols - 1) / p.gpart_cols, job.group_stride = bwd_partial_floats(N);
         job.slabs = h->n_slabs_dU > 0 ? h->slabs_dU : nullptr, job.n_slabs = h->n_slabs_dU, job.slab_stride = (size_t)4 * N * N;
         job.by_off = h->pl.by;
-    }
+        job.skip_dP_store = !h->keep_outputs;
+        job.tail = h->tail ? &tail : nullptr;
+    } else if (h->tail)
+        return fail(LSTM_HIP_ESTATE, "update launch: a loss tail without a pending gradient fold");
+    h->tail = false;
     job.slide = h->carry_slide ? &slide : nullptr;
     job.quad = p.adagrad_quad;
     if (h->clip_max > 0.0) { // norm of the whole (summed, all-reduced) block first; the fold moves into k_grad_sumsq
@@ -622,7 +641,11 @@ int do_adagrad(lstm_hip_ctx *h, double lr, int64_t norm_idx) {
     }
     RUN(adam ? K_ADAM : K_ADAGRAD, adagrad(job, h->st));
     h->opt_steps++;
-    if (job.slide) h->pre_slid = true;
+    if (job.slide) { // the launch wrote the next window's cursors and head to the other halves
+        h->pre_slid = true;
+        h->pos = pos_next;
+        h->head = head_next;
+    }
     h->carry_slide = false;
     h->packed = true; // the fp32 U images were refreshed by the same launch (the bf16 path has none)
     h->packed16 = false;
@@ -760,9 +783,11 @@ static int create_body(lstm_hip_ctx *h, const lstm_hip_config *cfg) {
     ALLOC(h->ti, S * B, 0xff);
     ALLOC(h->Xr, S * B, 0xff);
     ALLOC(h->Tr, S * B, 0xff);
-    ALLOC(h->head, 1);
+    ALLOC(h->head_buf, 2);
+    h->head = h->head_buf;
     ALLOC(h->d_loss, 1);
-    ALLOC(h->pos, B);
+    ALLOC(h->pos_buf, 2 * (size_t)B);
+    h->pos = h->pos_buf;
     h->cnt_bytes = persistent_counter_bytes((int)S, (int)B);
     ALLOC(h->cnt, 2 * h->cnt_bytes / sizeof(unsigned));
     ALLOC(h->abortp, 4);
@@ -814,7 +839,7 @@ int lstm_hip_destroy(lstm_hip_t *h) {
     if (h->st2) (void)hipStreamSynchronize(h->st2);
     if (h->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(h->comm);
     void *bufs[] = {h->P, h->dP, h->mem, h->Ufwd, h->Ubwd, h->Ubwd4, h->Ufwd4, h->Hx, h->DGx, h->H, h->C, h->G, h->DG, h->Y, h->Pr, h->DHy, h->dcnext,
-                    h->colloss, h->dby_part, h->slabs, h->slabs_dU, h->gpart, h->Hb, h->DGb, h->Ufwd16, h->Ubwd16, h->Ubwd6b, h->Ufwd6b, h->Hxb, h->WhyT_b, h->Why_b, h->Ht_b, h->dYt_b, h->DGt_b, h->dYb, h->dw_scratch, h->xi, h->ti, h->Xr, h->Tr, h->head, h->cnt, h->abortp, h->stamps, h->d_loss, h->d_losses, h->text, h->pos, h->stage, h->gen_scratch};
+                    h->colloss, h->dby_part, h->slabs, h->slabs_dU, h->gpart, h->Hb, h->DGb, h->Ufwd16, h->Ubwd16, h->Ubwd6b, h->Ufwd6b, h->Hxb, h->WhyT_b, h->Why_b, h->Ht_b, h->dYt_b, h->DGt_b, h->dYb, h->dw_scratch, h->xi, h->ti, h->Xr, h->Tr, h->head_buf, h->cnt, h->abortp, h->stamps, h->d_loss, h->d_losses, h->text, h->pos_buf, h->stage, h->gen_scratch};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     if (h->h_losses) (void)hipHostFree(h->h_losses);
@@ -863,6 +888,8 @@ int lstm_hip_get_params(lstm_hip_t *h, int which, float *host_block) {
     if (int rc = check_block(h, which, "get_params")) return rc;
     float *src = block_of(h, which);
     if (!src || !host_block) return fail(LSTM_HIP_EINVAL, "get_params: bad block id %d or null pointer", which);
+    if (which == 1 && h->dp_stale)
+        return fail(LSTM_HIP_ESTATE, "get_params: the gradient block holds no whole window (a window loop ended early); run backward first");
     if (h->padded()) {
         const PadMap m = pad_map_params(h->N_log, h->cfg.N, h->cfg.M);
         pad_copy(src, h->stage, m, false, h->st);
@@ -921,6 +948,8 @@ int lstm_hip_get_activations(lstm_hip_t *h, int32_t t, float *g_t, float *probs_
     CHECK(h);
     if (t < 1 || t >= h->cfg.S) return fail(LSTM_HIP_EINVAL, "get_activations: t=%d outside [1,%d)", t, h->cfg.S);
     const size_t B = h->cfg.B, G4 = 4 * (size_t)h->cfg.N;
+    if (probs_t && h->pr_stale)
+        return fail(LSTM_HIP_ESTATE, "get_activations: the probabilities hold no whole window (a window loop ended early); run forward first");
     if (g_t && h->padded()) { // gate blocks [i;o;f;u] of Np rows -> of N_log rows
         const PadMap m = pad_map_rows(4, h->N_log, h->cfg.N, h->cfg.B);
         pad_copy(h->G + t * G4 * B, h->stage, m, false, h->st);
@@ -1203,11 +1232,22 @@ static int ensure_losses(lstm_hip_ctx *h, int64_t count) {
     h->losses_cap = cap;
     return 0;
 }
+// One window of a device-resident loop, before its forward pass: does its loss ride in the update launch (wherever the
+// gradient fold does, do_backward's defer_fold, but not under clipping -- the norm needs dby first -- nor in a profiling pass,
+// which times the launches one by one), and does it store the probabilities and the folded gradient (`last`: nothing inside
+// the loop reads them, and only the last window's can be seen afterwards).  Returns whether the caller launches the loss itself.
+static bool loop_window(lstm_hip_ctx *h, bool last, double *loss_out) {
+    h->tail = h->plan.fused && !h->comm && !h->profiling && !(h->clip_max > 0.0);
+    h->tail_loss = loss_out;
+    h->keep_outputs = last || !h->tail;
+    return !h->tail;
+}
 struct LoopGuard { // leaves the loop state clean on every return path
     lstm_hip_ctx *h;
     bool completed = false;
     ~LoopGuard() {
         h->in_loop = false;
+        h->keep_outputs = true;
         if (completed) return;
         // error exit somewhere inside a window: nothing of that window may leak into a later standalone call
         h->fold_pending = false;
@@ -1217,6 +1257,8 @@ struct LoopGuard { // leaves the loop state clean on every return path
         h->dby_done = false;
         h->fwd_done = false;
         h->carry_slide = false;
+        h->tail = false;
+        h->pr_stale = h->dp_stale = true; // (whichever window broke: its stores may have been skipped or never reached)
         if (h->st2) (void)hipStreamSynchronize(h->st2); // side-stream work of the broken window (folds, early all-reduce)
         if (h->st) (void)hipStreamSynchronize(h->st);
     }
@@ -1243,17 +1285,17 @@ int lstm_hip_train_windows(lstm_hip_t *h, int64_t count, double learning_rate, d
                                       h->cfg.S, h->cfg.B, h->cfg.N, h->stride, h->carry_col, h->st));
         h->pre_slid = false;
         int rc = 0;
+        const bool own_loss = loop_window(h, i + 1 == count, h->d_losses + i);
         if ((rc = do_forward(h))) return rc;
-        RUN(K_LOSS, loss_reduce(loss_src(h), loss_steps(h), h->cfg.B, h->global_B, h->d_losses + i, h->dby_part,
-                                h->n_dby_parts, h->dP + h->pl.by, h->st, loss_scale(h)));
+        if (own_loss)
+            RUN(K_LOSS, loss_reduce(loss_src(h), loss_steps(h), h->cfg.B, h->global_B, h->d_losses + i, h->dby_part,
+                                    h->n_dby_parts, h->dP + h->pl.by, h->st, loss_scale(h)));
         h->dby_done = true;
         if ((rc = do_backward(h))) return rc;
         if ((rc = do_allreduce(h))) return rc;
-        // not behind the last window (the handle is left on the window it trained on) and not in a profiling pass
-        // ... and only for windows of up to 2 048 columns: the slide's one window-building workgroup has 256 threads there
-        // instead of 1 024 and outlasts the Adagrad workgroups at the headline shape (6 400 columns: 0.660 -> 0.665 ms, while
-        // configs[1] gains 4 us, configs[0] 2, configs[4] 3)
-        h->carry_slide = i + 1 < count && !h->profiling && (int64_t)h->cfg.S * h->cfg.B <= 2048;
+        // not behind the last window (the handle is left on the window it trained on) and not in a profiling pass.  The
+        // paths that keep their separate loss launch (loop_window) also keep the slide's for windows above 2 048 columns.
+        h->carry_slide = i + 1 < count && !h->profiling && (h->tail || (int64_t)h->cfg.S * h->cfg.B <= 2048);
         if ((rc = do_adagrad(h, learning_rate, i))) return rc;
     }
     if (elapsed_ms) {
@@ -1789,9 +1831,11 @@ static int run_adaptive(lstm_hip_t *h, bool decode, const uint64_t *text_off, co
         if ((rc = coder_steps(h, r, (uint64_t)k * L, (uint64_t)(k + 1) * L))) return rc;
         w.k = k, w.build = 1, w.block_bits = decode ? nullptr : r.block_bits + k;
         RUN(K_BLOCK_WINDOW, block_window(w, h->plan.n_cus, h->st));
+        const bool own_loss = loop_window(h, k + 1 == n_blocks, h->d_losses + k);
         if ((rc = do_forward(h))) return rc;
-        RUN(K_LOSS, loss_reduce(loss_src(h), loss_steps(h), B, h->global_B, h->d_losses + k, h->dby_part, h->n_dby_parts,
-                                h->dP + h->pl.by, h->st, loss_scale(h)));
+        if (own_loss)
+            RUN(K_LOSS, loss_reduce(loss_src(h), loss_steps(h), B, h->global_B, h->d_losses + k, h->dby_part, h->n_dby_parts,
+                                    h->dP + h->pl.by, h->st, loss_scale(h)));
         h->dby_done = true;
         if ((rc = do_backward(h))) return rc;
         h->carry_slide = false;

@@ -193,7 +193,11 @@ int lstm_hip_allreduce_grads(lstm_hip_t *h);
  *      forward; loss; backward; [all-reduce]; Adagrad.  losses (may be NULL) receives `count`
  *      per-window losses (what the reference adds to epoch_loss); for ranks of a communicator
  *      that is the local sum over this rank's streams divided by the GLOBAL batch.
- *      elapsed_ms (may be NULL) receives the HIP-event time of the loop on the handle's stream. */
+ *      elapsed_ms (may be NULL) receives the HIP-event time of the loop on the handle's stream.
+ *      After the call the handle holds the LAST window: its states, gates, probabilities and gradient block.  (The windows
+ *      before it need not have stored their probabilities and summed gradient: should the call, or an adaptive coding
+ *      call, end with an error, lstm_hip_get_activations' probs and lstm_hip_get_params(which = 1) answer LSTM_HIP_ESTATE
+ *      until a forward / backward pass has filled them again.) */
 int lstm_hip_set_text(lstm_hip_t *h, const uint8_t *text, size_t len);
 int lstm_hip_set_cursors(lstm_hip_t *h, const uint64_t *pos);
 int lstm_hip_get_cursors(lstm_hip_t *h, uint64_t *pos);
