@@ -341,8 +341,18 @@ struct GenHeadArgs {
     int N, streams, count;
     int mode;                   // 0: temperature 1 (expf as the sampler: unshifted, or shifted when stable), 1: tempered, 2: greedy
     float tau;
+    // sampling controls (lstm_hip_generate_ex): read only by the FILTER instantiation, which
+    // gen_head takes when `end` is set
+    int keep_k;                 // top-k: 1..255, or 256 (off)
+    int nucleus;                // 1: top_p < 1 was asked for
+    float top_p;                // (float)top_p, the mass the nucleus prefix has to reach
+    int filter;                 // 1: top-k or nucleus on (tempered draws are filtered)
+    int stop_byte;              // -1: none; else a stream ends with its first drawn byte equal to it
+    int32_t *end;               // [streams] number of bytes each stream draws: `count` at the start, i + 1 once draw i stops it
+    uint16_t *kept;             // [count][streams] bytes kept per draw (null: not wanted); zeroed by the caller
 };
 void gen_head(const GenHeadArgs &a, long long t, bool stable, hipStream_t st); // stable: LSTM_HIP_STABLE_SOFTMAX
+int gen_head_status();          // 0, or the HIP error of a refused LDS request (sticky until read)
 int gen_head_group(int N, int streams); // streams per workgroup of gen_head
 
 // ---- model-driven range coder (lstm_hip_encode / lstm_hip_decode): per step code_head on the state

@@ -1737,19 +1737,36 @@ __global__ __launch_bounds__(1024) void k_sample(const float *__restrict__ P, in
 // (contraction is off in this file), so a stream's bytes do not depend on SB, on its position or on the other streams.
 // STABLE (LSTM_HIP_STABLE_SOFTMAX): scored prompt bytes and mode-0 draws shift by max z too, and a prompt byte scores
 // lse_surprisal (the max and the target's logit are taken by the stream's max thread).
+// FILTER (lstm_hip_generate_ex with a filter, a stop byte or `kept` wanted): the instantiation with
+// FILTER = false is the code above and nothing else.  With it,
+//   a.filter    a tempered draw keeps the `keep` most likely bytes: thread m ranks its logit among the stream's 256 (z
+//               descending, index ascending: 256 broadcast reads of the z still in ps), the normalised terms p are scattered
+//               to sorted[rank], the stream's owner lane walks them in rank order until the float sum reaches a.top_p (at
+//               most a.keep_k of them), every thread clears its term if its rank is not kept, and the owner lane sums the
+//               kept terms in index order and walks the CDF of p / that sum; past every edge the byte is the largest kept
+//               index.  A stream's bytes still depend on nothing but its own h.  Greedy draws and prompt bytes ignore it.
+//   a.stop_byte a stream draws a.end[s] bytes, not a.count: the owner lane sets it to i + 1 when draw i is the stop byte, so
+//               the next launch copies the state after that byte to h_out / c_out and the stream idles.
+//   a.kept      keep per filtered draw, 256 per unfiltered one, 1 per greedy one.
 // ------------------------------------------------------------------------------------------------
 // what stream s does at step t: 0 idle, 1 prompt byte scored, 2 drawn byte, 3 prompt byte not scored; *len = its prompt length
-__device__ __forceinline__ int gen_phase(const GenHeadArgs &a, int s, long long t, long long *len) {
+// (*drawn: the bytes the stream draws -- the call's count, or with FILTER its own end index)
+template <bool FILTER>
+__device__ __forceinline__ int gen_phase(const GenHeadArgs &a, int s, long long t, long long *len, int *drawn = nullptr) {
     *len = a.off ? (long long)(a.off[s + 1] - a.off[s]) : 0;
+    const int n = FILTER ? a.end[s] : a.count;
+    if (drawn) *drawn = n;
     if (t < *len) return (t >= 1 && a.bits) ? 1 : 3;
-    return t - *len < a.count ? 2 : 0;
+    return t - *len < n ? 2 : 0;
 }
-template <int SB, bool STABLE>
+template <int SB, bool STABLE, bool FILTER>
 __global__ __launch_bounds__(256) void k_gen_head(GenHeadArgs a, long long t) {
     extern __shared__ __attribute__((aligned(16))) float hs[]; // [N][SB]
     __shared__ float ps[SB][256];
     __shared__ float s_zmax[SB], s_sum[SB], s_zt[STABLE ? SB : 1];
     __shared__ int s_arg[SB];
+    __shared__ float sorted[FILTER ? SB : 1][FILTER ? 256 : 1]; // p in rank order
+    __shared__ int s_keep[FILTER ? SB : 1], s_last[FILTER ? SB : 1]; // bytes kept; the largest kept index
     const int m = threadIdx.x, N = a.N, s0 = blockIdx.x * SB;
     int phase[SB]; // (the same in every thread)
     bool need = false;
@@ -1759,9 +1776,10 @@ __global__ __launch_bounds__(256) void k_gen_head(GenHeadArgs a, long long t) {
         phase[j] = 0;
         if (s >= a.streams) continue;
         long long len;
-        phase[j] = gen_phase(a, s, t, &len);
+        int drawn;
+        phase[j] = gen_phase<FILTER>(a, s, t, &len, &drawn);
         need |= phase[j] == 1 || phase[j] == 2;
-        if (t == len + a.count) { // the state after the stream's last input
+        if (t == len + drawn) { // the state after the stream's last input
             if (a.h_out)
                 for (int k = m; k < N; k += 256) a.h_out[(size_t)s * N + k] = a.H[(size_t)s * N + k];
             if (a.c_out)
@@ -1788,17 +1806,38 @@ __global__ __launch_bounds__(256) void k_gen_head(GenHeadArgs a, long long t) {
         }
         const float bym = a.by[m];
         bool any_max = false;
+        [[maybe_unused]] bool any_filter = false;
 #pragma unroll
         for (int j = 0; j < SB; j++) {
             y[j] = y[j] + bym; // the logit z
             ps[j][m] = y[j];
             any_max |= phase[j] == 2 && a.mode != 0;
             if constexpr (STABLE) any_max |= phase[j] == 1 || phase[j] == 2;
+            if constexpr (FILTER) any_filter |= phase[j] == 2 && a.mode != 2 && a.filter;
         }
+        [[maybe_unused]] int rank[FILTER ? SB : 1]; // of this thread's logit: #{z_i > z_m} + #{i < m: z_i == z_m}, in 0..255
+        if constexpr (FILTER)
+            if (any_filter) { // (uniform)
+                __syncthreads();
+#pragma unroll
+                for (int j = 0; j < SB; j++) {
+                    rank[j] = 0;
+                    if (phase[j] != 2) continue;
+                    const float zm = y[j];
+                    int r = 0;
+#pragma unroll 8
+                    for (int i = 0; i < 256; i++) {
+                        const float zi = ps[j][i];
+                        r += (zi > zm) | ((zi == zm) & (i < m));
+                    }
+                    rank[j] = r;
+                }
+                __syncthreads(); // (ps is overwritten below)
+            }
         if (any_max) { // max z / argmax z of each tempered or greedy stream (every order gives the same max)
             __syncthreads();
             long long len;
-            const int pm = m < SB && s0 + m < a.streams ? gen_phase(a, s0 + m, t, &len) : 0;
+            const int pm = m < SB && s0 + m < a.streams ? gen_phase<FILTER>(a, s0 + m, t, &len) : 0;
             if (pm == 2 || (STABLE && pm == 1)) {
                 float best = ps[m][0];
                 int arg = 0;
@@ -1821,7 +1860,7 @@ __global__ __launch_bounds__(256) void k_gen_head(GenHeadArgs a, long long t) {
         }
         __syncthreads();
         long long len;
-        const int pm = m < SB && s0 + m < a.streams ? gen_phase(a, s0 + m, t, &len) : 0;
+        const int pm = m < SB && s0 + m < a.streams ? gen_phase<FILTER>(a, s0 + m, t, &len) : 0;
         if (pm == 1 || (pm == 2 && a.mode != 2)) {
             float s = 0.0f;
             for (int i = 0; i < 256; i++) s += ps[m][i];
@@ -1832,13 +1871,48 @@ __global__ __launch_bounds__(256) void k_gen_head(GenHeadArgs a, long long t) {
         for (int j = 0; j < SB; j++)
             if (phase[j] == 1 || (phase[j] == 2 && a.mode != 2)) ps[j][m] = ps[j][m] / s_sum[j]; // p, the CDF's terms
         __syncthreads();
+        if constexpr (FILTER)
+            if (any_filter) { // (uniform)
+#pragma unroll
+                for (int j = 0; j < SB; j++)
+                    if (phase[j] == 2) sorted[j][rank[j]] = ps[j][m];
+                if (m < SB) s_last[m] = 0;
+                __syncthreads();
+                // the stream's owner lane (as below) walks the nucleus prefix: most likely first, one float sum
+                const int jo = (m & 63) * 4 + (m >> 6);
+                if (jo < SB && s0 + jo < a.streams) {
+                    long long lo;
+                    if (gen_phase<FILTER>(a, s0 + jo, t, &lo) == 2) {
+                        int keep = a.keep_k;
+                        if (a.nucleus) {
+                            float sum = 0.0f;
+                            for (int r = 0; r < keep; r++) { // (past keep_k the nucleus no longer matters)
+                                sum += sorted[jo][r];
+                                if (sum >= a.top_p) {
+                                    keep = r + 1;
+                                    break;
+                                }
+                            }
+                        }
+                        s_keep[jo] = keep;
+                    }
+                }
+                __syncthreads();
+#pragma unroll
+                for (int j = 0; j < SB; j++) {
+                    if (phase[j] != 2) continue;
+                    if (rank[j] < s_keep[j]) atomicMax(&s_last[j], m);
+                    else ps[j][m] = 0.0f;
+                }
+                __syncthreads();
+            }
     }
     // one owner thread per stream, spread over the four waves
     const int j = (m & 63) * 4 + (m >> 6);
     if (j >= SB || s0 + j >= a.streams) return;
     const int s = s0 + j;
     long long len;
-    const int ph = gen_phase(a, s, t, &len);
+    const int ph = gen_phase<FILTER>(a, s, t, &len);
     int x = -1;
     if (ph == 1 || ph == 3) {
         x = a.prompts[a.off[s] + t];
@@ -1848,8 +1922,25 @@ __global__ __launch_bounds__(256) void k_gen_head(GenHeadArgs a, long long t) {
         }
     } else if (ph == 2) {
         const size_t i = (size_t)(t - len);
-        if (a.mode == 2) x = s_arg[j];
-        else {
+        [[maybe_unused]] int kept = 256;
+        if (a.mode == 2) {
+            x = s_arg[j];
+            kept = 1;
+        } else if (FILTER && a.filter) {
+            kept = s_keep[j];
+            const float r = (float)a.u[i * a.streams + s];
+            float sum = 0.0f; // of the kept terms, in index order
+            for (int k = 0; k < 256; k++) sum += ps[j][k];
+            float cdf = 0.0f;
+            x = s_last[j];
+            for (int k = 0; k < 256; k++) {
+                cdf += ps[j][k] / sum;
+                if (r < cdf) {
+                    x = k;
+                    break;
+                }
+            }
+        } else {
             const float r = (float)a.u[i * a.streams + s];
             float cdf = 0.0f;
             x = 0;
@@ -1862,6 +1953,10 @@ __global__ __launch_bounds__(256) void k_gen_head(GenHeadArgs a, long long t) {
             }
         }
         a.out[i * a.streams + s] = (uint8_t)x;
+        if constexpr (FILTER) {
+            if (a.kept) a.kept[i * a.streams + s] = (uint16_t)kept;
+            if (x == a.stop_byte) a.end[s] = (int32_t)i + 1; // (read again by the next launch only)
+        }
     }
     a.x_next[s] = x;
 }
@@ -1870,6 +1965,12 @@ int gen_head_group(int N, int streams) {
     while (sb < 16 && streams >= 256 * 2 * sb && (size_t)2 * sb * N <= 16384) sb *= 2;
     return sb;
 }
+static thread_local hipError_t g_gen_head_error = hipSuccess;
+int gen_head_status() {
+    const hipError_t e = g_gen_head_error;
+    g_gen_head_error = hipSuccess;
+    return (int)e;
+}
 template <bool STABLE> static void gen_head_launch(const GenHeadArgs &a, long long t, hipStream_t st) {
     const int sb = gen_head_group(a.N, a.streams);
     const size_t lds = (size_t)sb * a.N * sizeof(float);
@@ -1877,17 +1978,41 @@ template <bool STABLE> static void gen_head_launch(const GenHeadArgs &a, long lo
 #define GEN_HEAD_CASE(SB)                                                                                                   \
     case SB:                                                                                                                \
         if (lds > 32768)                                                                                                    \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_gen_head<SB, STABLE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((k_gen_head<SB, STABLE>), grid, dim3(256), lds, st, a, t);                                      \
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_gen_head<SB, STABLE, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+        hipLaunchKernelGGL((k_gen_head<SB, STABLE, false>), grid, dim3(256), lds, st, a, t);                               \
         break;
-    switch (sb) {
-        GEN_HEAD_CASE(1)
-        GEN_HEAD_CASE(2)
-        GEN_HEAD_CASE(4)
-        GEN_HEAD_CASE(8)
-        GEN_HEAD_CASE(16)
+    // FILTER: static LDS is up to 33 KB (ps, sorted), dynamic up to 64 KB; a refused request is an error, not a launch
+#define GEN_HEAD_FILTER_CASE(SB)                                                                                            \
+    case SB: {                                                                                                              \
+        static size_t granted = 32768;                                                                                      \
+        if (lds > granted) {                                                                                                \
+            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_gen_head<SB, STABLE, true>),          \
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                 \
+            if (e != hipSuccess) {                                                                                          \
+                g_gen_head_error = e;                                                                                       \
+                return;                                                                                                     \
+            }                                                                                                               \
+            granted = lds;                                                                                                  \
+        }                                                                                                                   \
+        hipLaunchKernelGGL((k_gen_head<SB, STABLE, true>), grid, dim3(256), lds, st, a, t);                                 \
+        break;                                                                                                              \
     }
+    if (a.end) switch (sb) {
+            GEN_HEAD_FILTER_CASE(1)
+            GEN_HEAD_FILTER_CASE(2)
+            GEN_HEAD_FILTER_CASE(4)
+            GEN_HEAD_FILTER_CASE(8)
+            GEN_HEAD_FILTER_CASE(16)
+        }
+    else switch (sb) {
+            GEN_HEAD_CASE(1)
+            GEN_HEAD_CASE(2)
+            GEN_HEAD_CASE(4)
+            GEN_HEAD_CASE(8)
+            GEN_HEAD_CASE(16)
+        }
 #undef GEN_HEAD_CASE
+#undef GEN_HEAD_FILTER_CASE
 }
 void gen_head(const GenHeadArgs &a, long long t, bool stable, hipStream_t st) {
     if (stable) gen_head_launch<true>(a, t, st);

@@ -1453,10 +1453,27 @@ static int reserve_gen_scratch(lstm_hip_t *h, size_t bytes) {
 // gen_head launch (logits, prompt bits, the next input of every stream, final states) and one k_fwd_step over all streams,
 // from the fp32 master parameters P and a fragment image of U made for this call.  Nothing of the training state is
 // read or written except P; everything else lives in one scratch allocation kept on the handle (gen_scratch).
+// Sampling controls: a filter, a stop byte or a request for `kept` selects gen_head's FILTER
+// instantiation (a.end set); without them the launches are those of lstm_hip_generate before the controls existed.
 int lstm_hip_generate(lstm_hip_t *h, int32_t streams, const uint8_t *prompts, const uint64_t *prompt_off, const float *h0,
                       const float *c0, double temperature, const double *u, int32_t count, uint8_t *out, double *bits,
                       float *h_out, float *c_out) {
+    const lstm_hip_sampling opt{(uint32_t)sizeof(lstm_hip_sampling), temperature, 0, 1.0, -1};
+    return lstm_hip_generate_ex(h, streams, prompts, prompt_off, h0, c0, &opt, u, count, out, bits, h_out, c_out, nullptr, nullptr);
+}
+
+int lstm_hip_generate_ex(lstm_hip_t *h, int32_t streams, const uint8_t *prompts, const uint64_t *prompt_off, const float *h0,
+                         const float *c0, const lstm_hip_sampling *opt, const double *u, int32_t count, uint8_t *out,
+                         double *bits, float *h_out, float *c_out, int32_t *out_len, uint16_t *kept) {
     CHECK(h);
+    if (!opt) return fail(LSTM_HIP_EINVAL, "generate: null sampling options");
+    if (opt->size != sizeof(lstm_hip_sampling))
+        return fail(LSTM_HIP_EINVAL, "generate: sampling options of %u bytes, expected %zu", opt->size, sizeof(lstm_hip_sampling));
+    const double temperature = opt->temperature;
+    if (opt->top_k < 0 || opt->top_k > 256) return fail(LSTM_HIP_EINVAL, "generate: top_k must be in [0, 256] (got %d)", opt->top_k);
+    if (!(opt->top_p > 0.0 && opt->top_p <= 1.0)) return fail(LSTM_HIP_EINVAL, "generate: top_p must be in (0, 1] (got %g)", opt->top_p);
+    if (opt->stop_byte < -1 || opt->stop_byte > 255)
+        return fail(LSTM_HIP_EINVAL, "generate: stop_byte must be -1 or in [0, 255] (got %d)", opt->stop_byte);
     if (streams < 1 || streams > 4096) return fail(LSTM_HIP_EINVAL, "generate: streams must be in [1, 4096] (got %d)", streams);
     if (count < 0) return fail(LSTM_HIP_EINVAL, "generate: count < 0 (%d)", count);
     if (!std::isfinite(temperature) || temperature < 0.0)
@@ -1480,6 +1497,8 @@ int lstm_hip_generate(lstm_hip_t *h, int32_t streams, const uint8_t *prompts, co
     const uint64_t total = prompt_off ? prompt_off[streams] : 0;
     const size_t n = (size_t)N * streams, nl = (size_t)Nl * streams, nd = (size_t)count * streams;
     const bool keep = h_out || c_out;
+    const bool top_k_on = opt->top_k >= 1 && opt->top_k <= 255, nucleus = opt->top_p < 1.0;
+    const bool controls = top_k_on || nucleus || opt->stop_byte >= 0 || kept; // gen_head's FILTER instantiation
 
     // one scratch allocation, 256-byte aligned pieces
     size_t bytes = 0;
@@ -1493,7 +1512,8 @@ int lstm_hip_generate(lstm_hip_t *h, int32_t streams, const uint8_t *prompts, co
                  o_st = piece(h->padded() ? sizeof(float) * 2 * nl : 0), o_x = piece(sizeof(int32_t) * streams),
                  o_off = piece(prompt_off ? sizeof(uint64_t) * (streams + 1) : 0), o_p = piece(total),
                  o_u = piece(count > 0 && temperature >= (double)FLT_MIN ? sizeof(double) * nd : 0), o_out = piece(nd),
-                 o_bits = piece(sizeof(double) * streams);
+                 o_bits = piece(sizeof(double) * streams), o_end = piece(controls ? sizeof(int32_t) * streams : 0),
+                 o_kept = piece(kept ? sizeof(uint16_t) * nd : 0);
     if (int rc = reserve_gen_scratch(h, bytes)) return rc;
     char *base = h->gen_scratch;
     float4 *Ufwd = reinterpret_cast<float4 *>(base + o_U);
@@ -1506,6 +1526,8 @@ int lstm_hip_generate(lstm_hip_t *h, int32_t streams, const uint8_t *prompts, co
     double *d_u = count > 0 && temperature >= (double)FLT_MIN ? reinterpret_cast<double *>(base + o_u) : nullptr;
     uint8_t *d_out = reinterpret_cast<uint8_t *>(base + o_out);
     double *d_bits = reinterpret_cast<double *>(base + o_bits);
+    int32_t *d_end = controls ? reinterpret_cast<int32_t *>(base + o_end) : nullptr;
+    uint16_t *d_kept = kept ? reinterpret_cast<uint16_t *>(base + o_kept) : nullptr;
 
     // start state (padding rows zero), inputs
     const PadMap map = pad_map_rows(1, Nl, N, streams);
@@ -1524,6 +1546,9 @@ int lstm_hip_generate(lstm_hip_t *h, int32_t streams, const uint8_t *prompts, co
     if (d_prompts) HIP_TRY(hipMemcpyAsync(d_prompts, prompts, total, hipMemcpyHostToDevice, h->st));
     if (d_u) HIP_TRY(hipMemcpyAsync(d_u, u, sizeof(double) * nd, hipMemcpyHostToDevice, h->st));
     HIP_TRY(hipMemsetAsync(d_bits, 0, sizeof(double) * streams, h->st));
+    if (d_end) HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_end), count, streams, h->st));
+    if (d_kept && nd) HIP_TRY(hipMemsetAsync(d_kept, 0, sizeof(uint16_t) * nd, h->st)); // 0 wherever a stream has stopped
+    if (opt->stop_byte >= 0 && nd) HIP_TRY(hipMemsetAsync(d_out, 0, nd, h->st));
     RUN(K_PACK_U, pack_U(h->P + h->pl.U, Ufwd, nullptr, N, h->st));
 
     GenHeadArgs a{};
@@ -1544,6 +1569,13 @@ int lstm_hip_generate(lstm_hip_t *h, int32_t streams, const uint8_t *prompts, co
     // would give 0 / 0 at the maximum)
     a.mode = temperature < (double)FLT_MIN ? 2 : temperature == 1.0 ? 0 : 1;
     a.tau = (float)temperature;
+    a.keep_k = top_k_on ? opt->top_k : 256;
+    a.nucleus = nucleus;
+    a.top_p = (float)opt->top_p;
+    a.filter = top_k_on || nucleus;
+    a.stop_byte = opt->stop_byte;
+    a.end = d_end;
+    a.kept = d_kept;
     const bool fast = (h->cfg.flags & LSTM_HIP_FAST_MATH) != 0, stable = (h->cfg.flags & LSTM_HIP_STABLE_SOFTMAX) != 0;
     const long long steps = (long long)max_len + count; // inputs of the longest stream
     int cur = 0;
@@ -1551,6 +1583,9 @@ int lstm_hip_generate(lstm_hip_t *h, int32_t streams, const uint8_t *prompts, co
         a.H = H + cur * n;
         a.C = Cs + cur * n;
         RUN(K_GEN_HEAD, gen_head(a, t, stable, h->st));
+        if (controls)
+            if (const int e = gen_head_status())
+                return fail(LSTM_HIP_EHIP, "generate: the LDS request of gen_head was refused: %s", hipGetErrorString((hipError_t)e));
         if (t == steps) break;
         RUN(K_FWD_STEP, fwd_step(Ufwd, h->P + h->pl.W, h->P + h->pl.b, H + cur * n, Cs + cur * n, H + (cur ^ 1) * n,
                                  Cs + (cur ^ 1) * n, G, xi, N, streams, fast, h->st));
@@ -1559,6 +1594,11 @@ int lstm_hip_generate(lstm_hip_t *h, int32_t streams, const uint8_t *prompts, co
 
     if (count > 0) HIP_TRY(hipMemcpyAsync(out, d_out, nd, hipMemcpyDeviceToHost, h->st));
     if (bits) HIP_TRY(hipMemcpyAsync(bits, d_bits, sizeof(double) * streams, hipMemcpyDeviceToHost, h->st));
+    if (out_len) {
+        if (d_end) HIP_TRY(hipMemcpyAsync(out_len, d_end, sizeof(int32_t) * streams, hipMemcpyDeviceToHost, h->st));
+        else std::fill(out_len, out_len + streams, count);
+    }
+    if (kept && nd) HIP_TRY(hipMemcpyAsync(kept, d_kept, sizeof(uint16_t) * nd, hipMemcpyDeviceToHost, h->st));
     for (int k = 0; k < 2; k++) {
         float *dst = k ? c_out : h_out;
         if (!dst) continue;

@@ -3,14 +3,17 @@
 // over many streams at once.  No HIP, no torch here.
 //
 //   lstm_generate --load PREFIX [--score FILE ...] [--count C --streams K --prime TEXT|--prime-file F
-//                 --temperature T --seed S] [--fast-math] [--stable-softmax] [--device D]
+//                 --temperature T --top-k K --top-p P --stop-byte B --seed S] [--fast-math] [--stable-softmax] [--device D]
 //
 // --load reads the five-file text checkpoint PREFIX_{W,U,Why,b,by}.txt (checkpoint.h); N is the rows of W / 4.
 // --score runs every FILE as one stream from h = c = 0 and prints "FILE: X.XXXXX bits/char (n bytes)" per file (bits over
 // the n - 1 predicted bytes, as lstm_hip_eval_bits) and a total weighted by those bytes.
 // --count prints K samples of C bytes, each continuing from the prompt (--prime / --prime-file, default none) from a zero
 // state; the draws come from SeededRng(S) (rng.h), byte i of stream s taking draw i*K + s, so a seed gives the same text.
-// --temperature 0 is greedy decoding and takes no draws.  --stable-softmax scores and draws at temperature 1 with the
+// --temperature 0 is greedy decoding and takes no draws.  --top-k K (1..255) draws among the K most likely bytes, --top-p P
+// (0 < P < 1) among the smallest most-likely-first set of mass P, and with --stop-byte B (decimal, 0..255; 10 is a newline)
+// a sample ends with its first drawn byte B: it is printed up to and including that byte (lstm_hip_generate_ex).
+// --stable-softmax scores and draws at temperature 1 with the
 // max-shifted softmax (LSTM_HIP_STABLE_SOFTMAX), for checkpoints whose logits pass expf's range.
 #include "../../include/lstm_hip.h"
 #include "checkpoint.h"
@@ -28,7 +31,11 @@ namespace {
 
 const char *const kUsage =
     "usage: lstm_generate --load PREFIX [--score FILE ...] [--count C --streams K --prime TEXT|--prime-file F\n"
-    "                     --temperature T --seed S] [--fast-math] [--stable-softmax] [--device D]\n";
+    "                     --temperature T --top-k K --top-p P --stop-byte B --seed S]\n"
+    "                     [--fast-math] [--stable-softmax] [--device D]\n"
+    "  --top-k K      draw among the K most likely bytes (1..255; 0 or 256: all)\n"
+    "  --top-p P      draw among the smallest most-likely-first set of bytes whose mass reaches P (0 < P <= 1)\n"
+    "  --stop-byte B  end a sample with its first drawn byte B (decimal, 0..255) and print it up to that byte\n";
 
 [[noreturn]] void usage(const std::string &m) {
     fprintf(stderr, "lstm_generate: %s\n%s", m.c_str(), kUsage);
@@ -75,7 +82,8 @@ struct Options {
     std::vector<std::string> sampling_opts; // options that only mean something with --count
     std::vector<std::string> score;
     long count = -1, streams = 1, device = 0;
-    double temperature = 1.0;
+    double temperature = 1.0, top_p = 1.0;
+    long top_k = 0, stop_byte = -1;
     uint32_t seed = 1;
     unsigned flags = 0;
 };
@@ -106,6 +114,16 @@ Options parse(int argc, char **argv) {
             o.sampling_opts.push_back(a);
         } else if (a == "--temperature") {
             o.temperature = parse_double(a, val());
+            o.sampling_opts.push_back(a);
+        } else if (a == "--top-k") {
+            o.top_k = parse_int(a, val(), 0, 256);
+            o.sampling_opts.push_back(a);
+        } else if (a == "--top-p") {
+            o.top_p = parse_double(a, val());
+            if (!(o.top_p > 0.0 && o.top_p <= 1.0)) usage(a + " needs a number in (0, 1]");
+            o.sampling_opts.push_back(a);
+        } else if (a == "--stop-byte") {
+            o.stop_byte = parse_int(a, val(), 0, 255);
             o.sampling_opts.push_back(a);
         } else if (a == "--seed") {
             o.seed = (uint32_t)parse_int(a, val(), 0, 0xFFFFFFFFL);
@@ -192,12 +210,14 @@ int main(int argc, char **argv) {
             for (double &x : u) x = rng.uniform();
         }
         std::vector<uint8_t> out((size_t)C * K);
-        CK(lstm_hip_generate(h, K, prompts.data(), off.data(), nullptr, nullptr, o.temperature, u.empty() ? nullptr : u.data(), C,
-                             out.data(), nullptr, nullptr, nullptr));
+        const lstm_hip_sampling opt{(uint32_t)sizeof(lstm_hip_sampling), o.temperature, (int32_t)o.top_k, o.top_p, (int32_t)o.stop_byte};
+        std::vector<int32_t> out_len(K);
+        CK(lstm_hip_generate_ex(h, K, prompts.data(), off.data(), nullptr, nullptr, &opt, u.empty() ? nullptr : u.data(), C,
+                                out.data(), nullptr, nullptr, nullptr, out_len.data(), nullptr));
         for (int s = 0; s < K; s++) {
             printf("== sample %d ==\n", s);
             fwrite(prime.data(), 1, prime.size(), stdout);
-            for (int i = 0; i < C; i++) fputc(out[(size_t)i * K + s], stdout);
+            for (int i = 0; i < out_len[s]; i++) fputc(out[(size_t)i * K + s], stdout);
             fputc('\n', stdout);
         }
     }

@@ -38,6 +38,11 @@ class LstmHipError(RuntimeError):
     pass
 
 
+class _Sampling(C.Structure):  # lstm_hip_sampling
+    _fields_ = [("size", C.c_uint32), ("temperature", C.c_double), ("top_k", C.c_int32), ("top_p", C.c_double),
+                ("stop_byte", C.c_int32)]
+
+
 class _Config(C.Structure):
     _fields_ = [("N", C.c_int32), ("M", C.c_int32), ("S", C.c_int32), ("B", C.c_int32), ("device", C.c_int32),
                 ("flags", C.c_uint32)]
@@ -53,7 +58,7 @@ SYMBOLS = [
     "lstm_hip_adagrad", "lstm_hip_comm_unique_id", "lstm_hip_comm_init", "lstm_hip_allreduce_grads",
     "lstm_hip_set_text", "lstm_hip_set_cursors", "lstm_hip_get_cursors", "lstm_hip_reset_window",
     "lstm_hip_get_window", "lstm_hip_train_windows", "lstm_hip_set_global_batch", "lstm_hip_set_loss_mode", "lstm_hip_set_stride", "lstm_hip_eval_bits",
-    "lstm_hip_sample", "lstm_hip_generate", "lstm_hip_synchronize", "lstm_hip_set_profiling", "lstm_hip_kernel_stat_count",
+    "lstm_hip_sample", "lstm_hip_generate", "lstm_hip_generate_ex", "lstm_hip_synchronize", "lstm_hip_set_profiling", "lstm_hip_kernel_stat_count",
     "lstm_hip_kernel_stat", "lstm_hip_reset_kernel_stats", "lstm_hip_device_info", "lstm_hip_debug_stamps",
     "lstm_hip_set_grad_clip", "lstm_hip_get_grad_norms", "lstm_hip_set_optimizer", "lstm_hip_get_optimizer_steps",
     "lstm_hip_set_optimizer_steps", "lstm_hip_coder_version", "lstm_hip_code_bound", "lstm_hip_encode", "lstm_hip_decode",
@@ -347,11 +352,16 @@ class Lstm:
                                       _ptr(out, C.c_uint8)))
         return out, h0, c0
 
-    def generate(self, prompts=None, count=0, u=None, temperature=1.0, h0=None, c0=None, streams=None, score=False):
+    def generate(self, prompts=None, count=0, u=None, temperature=1.0, h0=None, c0=None, streams=None, score=False,
+                 top_k=0, top_p=1.0, stop_byte=None, info=False):
         """lstm_hip_generate: `streams` independent streams, each fed its prompt (bytes or a uint8 array) and then `count`
         drawn bytes.  u: draws [count, streams] (may be None only at temperature 0); h0, c0: [streams, N] or None (zeros).
         Returns (out [count, streams] uint8, bits [streams] float64 -- the prompts' summed -log2 p, or None unless
-        score --, h [streams, N], c [streams, N]: the state after each stream's last input)."""
+        score --, h [streams, N], c [streams, N]: the state after each stream's last input).
+        top_k (1..255), top_p (< 1) and stop_byte (0..255) are the sampling controls of lstm_hip_generate_ex: keep the k
+        most likely bytes, the smallest most-likely-first prefix of mass top_p, and end a stream with its first drawn
+        stop_byte (out is 0 behind it, h / c are the state after it).  info=True adds a fifth element
+        {"out_len": int32 [streams], "kept": uint16 [count, streams]}: bytes each stream produced, bytes kept per draw."""
         if streams is None:
             streams = len(prompts) if prompts is not None else (np.asarray(h0).shape[0] if h0 is not None else
                                                                 (np.asarray(u).reshape(count, -1).shape[1] if u is not None and count > 0 else 1))
@@ -372,13 +382,21 @@ class Lstm:
         bits = np.zeros(streams, np.float64) if score else None
         h = np.empty((streams, self.N), np.float32)
         c = np.empty((streams, self.N), np.float32)
-        _chk(self.lib.lstm_hip_generate(self._h, C.c_int32(streams), _ptr(d_p, C.c_uint8) if d_p is not None else None,
-                                        _ptr(d_off, C.c_uint64) if d_off is not None else None,
-                                        _ptr(hh) if hh is not None else None, _ptr(cc) if cc is not None else None,
-                                        C.c_double(temperature), _ptr(uu, C.c_double) if uu is not None else None,
-                                        C.c_int32(count), _ptr(out, C.c_uint8), _ptr(bits, C.c_double) if score else None,
-                                        _ptr(h), _ptr(c)))
-        return out, bits, h, c
+        args = (self._h, C.c_int32(streams), _ptr(d_p, C.c_uint8) if d_p is not None else None,
+                _ptr(d_off, C.c_uint64) if d_off is not None else None,
+                _ptr(hh) if hh is not None else None, _ptr(cc) if cc is not None else None)
+        tail = (_ptr(uu, C.c_double) if uu is not None else None, C.c_int32(count), _ptr(out, C.c_uint8),
+                _ptr(bits, C.c_double) if score else None, _ptr(h), _ptr(c))
+        if top_k == 0 and top_p == 1.0 and stop_byte is None and not info:
+            _chk(self.lib.lstm_hip_generate(*args, C.c_double(temperature), *tail))
+            return out, bits, h, c
+        opt = _Sampling(C.sizeof(_Sampling), float(temperature), int(top_k), float(top_p),
+                        -1 if stop_byte is None else int(stop_byte))
+        out_len = np.zeros(streams, np.int32)
+        kept = np.zeros((count, streams), np.uint16)
+        _chk(self.lib.lstm_hip_generate_ex(*args, C.byref(opt), *tail, _ptr(out_len, C.c_int32),
+                                           _ptr(kept, C.c_uint16) if info else None))
+        return (out, bits, h, c, {"out_len": out_len, "kept": kept}) if info else (out, bits, h, c)
 
     def encode(self, texts, trace=False):
         """lstm_hip_encode: each of `texts` (bytes or uint8 arrays) is one stream, coded from a zero state.  Returns

@@ -248,6 +248,47 @@ int lstm_hip_sample(lstm_hip_t *h, float *h0, float *c0, const double *u, int32_
 int lstm_hip_generate(lstm_hip_t *h, int32_t streams, const uint8_t *prompts, const uint64_t *prompt_off,
                       const float *h0, const float *c0, double temperature, const double *u, int32_t count,
                       uint8_t *out, double *bits, float *h_out, float *c_out);
+/* ---- the same call with sampling controls.  Everything lstm_hip_generate documents holds: prompts,
+ *      scoring, the order the draws are consumed in, final states, what of the handle is read, the refusals.  With top_k 0 or
+ *      256, top_p 1 and stop_byte -1 the call is bit for bit lstm_hip_generate(..., opt->temperature, ...), which is a thin
+ *      caller of this function.
+ *        filter  per drawn byte, after temperature; greedy draws (temperature below FLT_MIN) and prompt scoring ignore it.
+ *                z: the stream's 256 logits; p: the normalised terms of the CDF walk above (in the mode the temperature and
+ *                LSTM_HIP_STABLE_SOFTMAX select).
+ *                  1. rank_m = #{i : z_i > z_m} + #{i < m : z_i == z_m} (z descending, index ascending: top_k = 1 is
+ *                     greedy decoding, lowest index on ties)
+ *                  2. keep_k = top_k if 1..255, else 256
+ *                  3. keep_p = 256 if top_p == 1; else walk ranks r = 0, 1, .. adding p[rank r] into one float:
+ *                     keep_p = r + 1 at the first r where the sum >= (float)top_p, 256 if it never is
+ *                  4. keep = min(keep_k, keep_p) >= 1
+ *                  5. p'_m = p_m where rank_m < keep, else 0; s' = the sequential float sum of p' in index order;
+ *                     p''_m = p'_m / s'
+ *                  6. the byte is the first m with u < cdf[m] (sequential float sum of p''); if u passes every edge, the
+ *                     largest kept index (a filtered draw is always a kept byte; unfiltered draws keep byte 0 there)
+ *                kept[i*streams + s] (may be NULL) = keep for a filtered draw, 256 for an unfiltered one, 1 for a greedy
+ *                one, 0 for positions after the stream has stopped.
+ *                Without LSTM_HIP_STABLE_SOFTMAX, expf(z) can overflow at temperature 1: the byte is then unspecified (but a
+ *                byte, and nothing faults).
+ *        stop    stream s ends with its first DRAWN byte equal to stop_byte, at draw i (prompt bytes never stop it):
+ *                out_len[s] (may be NULL) = i + 1, or count if it never comes; out[j*streams + s] = 0 for j >= out_len[s].
+ *                The stop byte is still fed as an input: h_out / c_out are the state after it (the state after the
+ *                stream's last input, with the stream's own length).  Draw i uses u[i*streams + s] as ever, so a stopped
+ *                run is the prefix of the unstopped run with the same draws.
+ *                The call still runs all max prompt length + count steps: stopped streams idle, no result is read back
+ *                inside the loop and the loop does not end early.
+ *      LSTM_HIP_EINVAL (the handle stays usable), beside lstm_hip_generate's: opt NULL or opt->size != sizeof(lstm_hip_sampling),
+ *      top_k outside 0..256, top_p NaN, <= 0 or > 1, stop_byte outside -1..255. */
+typedef struct lstm_hip_sampling {
+    uint32_t size;        /* sizeof(lstm_hip_sampling); anything else: LSTM_HIP_EINVAL */
+    double   temperature; /* as lstm_hip_generate */
+    int32_t  top_k;       /* 0 or 256: off; 1..255: keep the k most likely bytes */
+    double   top_p;       /* 1.0: off; 0 < top_p < 1: keep the smallest most-likely-first prefix whose mass reaches top_p */
+    int32_t  stop_byte;   /* -1: off; 0..255: a stream ends with the first DRAWN byte equal to it */
+} lstm_hip_sampling;
+int lstm_hip_generate_ex(lstm_hip_t *h, int32_t streams, const uint8_t *prompts, const uint64_t *prompt_off,
+                         const float *h0, const float *c0, const lstm_hip_sampling *opt, const double *u, int32_t count,
+                         uint8_t *out, double *bits, float *h_out, float *c_out,
+                         int32_t *out_len /* [streams], may be NULL */, uint16_t *kept /* [count*streams], may be NULL */);
 
 /* ---- arithmetic coding of bytes with the model.  Stream s is text[text_off[s] .. text_off[s+1]),
  *      1 <= streams <= 4096, each coded on its own from h = c = 0 (empty streams allowed: their code is empty).
