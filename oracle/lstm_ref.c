@@ -73,6 +73,12 @@ void ref_set_descending_sums(int on) { g_desc_sums = on; }
  * once), accumulate in fp32.  Biases, dW/db/dby (sums, no products), the elementwise math and Adagrad stay fp32. */
 static int g_bf16_products = 0;
 void ref_set_bf16_products(int on) { g_bf16_products = on; }
+/* Mutation for tests/test_param_statistics_cpu.py: ref_forward clamps every gate pre-activation to [-x, x] before its sigmoid / tanh,
+ * the classic shortcut of a fast kernel.  Parameters whose pre-activations stay inside the bound give the same bits; a model
+ * with saturated gates does not.  0 (the default) is off and leaves every result bit for bit as it was. */
+static double g_gate_clamp = 0.0;
+void ref_set_gate_clamp(double x) { g_gate_clamp = x; }
+#define GATE_PRE(v) (g_gate_clamp > 0.0 ? ((v) > g_gate_clamp ? g_gate_clamp : (v) < -g_gate_clamp ? -g_gate_clamp : (v)) : (v))
 static inline float bf16_rne(float x) {
     uint32_t u;
     memcpy(&u, &x, 4);
@@ -257,8 +263,8 @@ void FN(ref_forward)(int N, int M, int S, int B, const REAL *P, const int32_t *x
                 gc[r] = (acc + gc[r]) + p.b[r];
             }
             /* sigmoid on i,o,f; tanh on u   (opt:222-224) */
-            for (int r = 0; r < 3 * N; r++) gc[r] = logistic(gc[r]);
-            for (int r = 3 * N; r < G; r++) gc[r] = TANH(gc[r]);
+            for (int r = 0; r < 3 * N; r++) gc[r] = logistic((REAL)GATE_PRE(gc[r]));
+            for (int r = 3 * N; r < G; r++) gc[r] = TANH((REAL)GATE_PRE(gc[r]));
             /* c = tanh(i*u + f*c_prev); h = o*c   (opt:226-233) */
             for (int j = 0; j < N; j++) {
                 REAL z = gc[j] * gc[3 * N + j] + gc[2 * N + j] * cp[(size_t)b * N + j];

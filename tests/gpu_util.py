@@ -176,3 +176,92 @@ def db_minus_dW(d, N, M=256):
     """db - sum over the input bytes of dW, in float64: the empty columns' share of db (x is one-hot or empty)."""
     p = split_params(np.asarray(d), N, M)
     return p["b"][:, 0].astype(np.float64) - p["W"].astype(np.float64).sum(axis=1)
+
+
+# ---- parameters and states with the statistics of a trained model (tests/test_param_statistics*.py) ---------------------
+# random_case draws every parameter from one Gaussian of scale 0.02-0.08: every gate is about 0.5, tanh is linear and the
+# softmax is flat.  The regimes below give saturated gates, cells near +-1 and peaked outputs.  Pure numpy, seeded.
+PARAM_REGIMES = ("gauss", "saturated", "mild", "tiled_A", "tiled_B", "unit_scales")
+STATE_REGIMES = ("small", "carried")
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+# (W, U * sqrt(N), b, forget-row offset of b, Why * sqrt(N), by)
+_SCALES = dict(saturated=(3.0, 2.0, 2.0, 3.0, 4.0, 3.0), mild=(1.5, 1.0, 1.0, 1.5, 2.0, 1.0))
+
+
+def fixture(name):
+    """tests/golden/fixture_{A,B}.npz: the reference's trained weights (hidden 32 / 16), its held-out text, its logged bits."""
+    fx = np.load(os.path.join(GOLDEN, f"fixture_{name}.npz"))
+    return dict(N=int(fx["N"]), params=fx["params"].astype(np.float32), text=fx["text"], bits=float(fx["expected_bits"]))
+
+
+def join_params(W, U, b, Why, by):
+    """Flat block from W [M, 4N], U [N, 4N], b [4N], Why [N, M], by [M]: each the C-order bytes of the column-major matrix."""
+    return np.concatenate([np.asarray(a, np.float32).ravel() for a in (W, U, b, Why, by)])
+
+
+def tile_params(P, n, k, M=256):
+    """The hidden-n model P block-tiled to hidden k * n: the rows of W and b of each gate repeated k times, each gate block of
+    U block-diagonal with k copies, Why repeated k times along its columns and divided by k, by unchanged.  Every block of n
+    units then carries the small model's h (from a state tiled the same way) and the logits are the small model's."""
+    p = split_params(np.asarray(P, np.float32), n, M)
+    N = k * n
+    W = np.tile(p["W"].T.reshape(M, 4, 1, n), (1, 1, k, 1)).reshape(M, 4 * N)
+    b = np.tile(p["b"][:, 0].reshape(4, 1, n), (1, k, 1)).reshape(4 * N)
+    Us = p["U"].T.reshape(n, 4, n)                       # [column, gate, row]
+    U = np.zeros((k, n, 4, k, n), np.float32)
+    for c in range(k):
+        U[c, :, :, c, :] = Us
+    Why = np.tile(p["Why"].T, (k, 1)) / np.float32(k)    # [N, M]
+    return join_params(W, U.reshape(N, 4 * N), b, Why, p["by"][:, 0])
+
+
+def regime_params(regime, N, seed, scale=0.08, M=256):
+    """The flat parameter block of one of PARAM_REGIMES at hidden N (gate row order [i; o; f; u])."""
+    rs = np.random.RandomState(seed)
+    if regime == "gauss":
+        return random_case(N, 2, 1, seed, scale=scale, M=M)[0]
+    if regime in _SCALES:
+        w, u, b_, f, why, by_ = _SCALES[regime]
+        W = w * rs.randn(M, 4 * N)
+        U = u / np.sqrt(N) * rs.randn(N, 4 * N)
+        b = b_ * rs.randn(4 * N)
+        b[2 * N:3 * N] += f
+        return join_params(W, U, b, why / np.sqrt(N) * rs.randn(N, M), by_ * rs.randn(M))
+    if regime in ("tiled_A", "tiled_B"):
+        fx = fixture(regime[-1])
+        assert N % fx["N"] == 0, (regime, N)
+        return tile_params(fx["params"], fx["N"], N // fx["N"], M)
+    if regime == "unit_scales":
+        p = split_params(random_case(N, 2, 1, seed, scale=0.08, M=M)[0].copy(), N, M)      # views of the one block
+        f = np.exp(rs.uniform(np.log(0.01), np.log(3.0), N)).astype(np.float32)             # one factor per hidden unit
+        rows = np.tile(f, 4)
+        W, U, b, Why = (p["W"] * rows[:, None]).T, (p["U"] * rows[:, None]).T, p["b"][:, 0] * rows, (p["Why"] * f[None, :]).T
+        return join_params(W, U, b, Why, p["by"][:, 0])
+    raise ValueError(regime)
+
+
+def regime_state(kind, N, B, seed, tile=1):
+    """h0, c0 [B, N] float32.  small: 0.1 N(0,1) as random_case; carried: c0 = tanh(2 N(0,1)), h0 = sigmoid(3 N(0,1)) c0, so
+    that |c0| reaches 0.999 (cut at 0.9995).  tile = k draws the state of N / k units and repeats it k times (for tile_params' models)."""
+    rs = np.random.RandomState(seed + 7919)
+    n = N // tile
+    if kind == "small":
+        h0, c0 = rs.randn(B, n) * 0.1, rs.randn(B, n) * 0.1
+    elif kind == "carried":
+        c0 = np.clip(np.tanh(2.0 * rs.randn(B, n)), -0.9995, 0.9995)      # (a float32 cell is never 1.0, which tanh(9) rounds to)
+        h0 = c0 / (1.0 + np.exp(-3.0 * rs.randn(B, n)))
+    else:
+        raise ValueError(kind)
+    return np.tile(h0, (1, tile)).astype(np.float32), np.tile(c0, (1, tile)).astype(np.float32)
+
+
+def text_windows(text, S, B):
+    """xi, ti [S, B]: B overlapping windows of the text, their starts spread evenly over it, target = the next byte."""
+    text = np.asarray(text, np.uint8)
+    assert text.size > S
+    start = np.linspace(0, text.size - S, B).round().astype(np.int64)
+    at = start[None, :] + np.arange(S)[:, None]          # row t reads text[start + t - 1]; row 0 is unused
+    xi = text[np.maximum(at - 1, 0)].astype(np.int32)
+    ti = text[at].astype(np.int32)
+    xi[0], ti[0] = xi[1], ti[1]
+    return np.ascontiguousarray(xi), np.ascontiguousarray(ti)

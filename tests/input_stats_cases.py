@@ -141,13 +141,22 @@ def selected_cases(request):
 class ReferencePool:
     """reference() of every case, computed ahead in worker processes (spawned: the parent may hold a GPU context)."""
 
-    def __init__(self, cases, with_f32=False):
+    def __init__(self, cases, with_f32=False, fn=None, key=None):
+        """fn(case, with_f32) computes a reference (default: reference), key(case) names it (default: case_id); cases with
+        one key share one reference, which get() hands to each of them and then lets go."""
         workers = max(1, min(16, cpu_share()))
         self.ex = concurrent.futures.ProcessPoolExecutor(max_workers=workers, mp_context=multiprocessing.get_context("spawn"))
-        self.futures = {case_id(c): self.ex.submit(reference, c, with_f32) for c in cases}
+        self.key = key or case_id
+        self.users = collections.Counter(self.key(c) for c in cases)
+        self.futures = {}
+        for c in cases:
+            if self.key(c) not in self.futures:
+                self.futures[self.key(c)] = self.ex.submit(fn or reference, c, with_f32)
 
     def get(self, case):
-        return self.futures.pop(case_id(case)).result()
+        k = self.key(case)
+        self.users[k] -= 1
+        return (self.futures[k] if self.users[k] > 0 else self.futures.pop(k)).result()
 
     def close(self):
         self.ex.shutdown(wait=True, cancel_futures=True)
@@ -189,3 +198,12 @@ def check_window(case, got, ref, xi, fraction=1.0):
 def parse_plan(text):
     """'np512 fwd4 bwd4 fused1 ...' -> {'np': 512, 'fwd': 4, ...}"""
     return {k: int(v) for k, v in re.findall(r"([a-z]+)(\d+)", text)}
+
+
+def assert_plan(L, want):
+    """The handle's plan string, after asserting the fields of `want` in it: a case fails, not skips, on another path."""
+    text = L.plan_identity()
+    plan = parse_plan(text)
+    off = {k: (plan.get(k), v) for k, v in want.items() if plan.get(k) != v}
+    assert not off, f"not the intended path: plan '{text}' (got, wanted): {off}"
+    return text

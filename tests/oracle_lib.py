@@ -84,6 +84,14 @@ class Oracle:
         this is the complete bf16 MFMA path of BASELINE configs[4]."""
         self.lib.ref_set_bf16_products(1 if on else 0)
 
+    def set_descending_sums(self, on):
+        """every contraction of the window over its index in descending order: as correct, another rounding sequence."""
+        self.lib.ref_set_descending_sums(1 if on else 0)
+
+    def set_gate_clamp(self, x):
+        """test-only mutation: the window forward clamps every gate pre-activation to [-x, x]; 0 switches it off."""
+        self.lib.ref_set_gate_clamp(C.c_double(x))
+
     # ---- RNG -------------------------------------------------------------------------------
     def rng(self, seed):
         buf = C.create_string_buffer(self.lib.ref_rng_sizeof())

@@ -65,12 +65,7 @@ def references(request):
     _report(dict(file="tests/test_input_statistics.py", wall_seconds=round(time.time() - t0, 1), cases=len(cases)))
 
 
-def _assert_plan(L, want):
-    text = L.plan_identity()
-    plan = isc.parse_plan(text)
-    off = {k: (plan.get(k), v) for k, v in want.items() if plan.get(k) != v}
-    assert not off, f"not the intended path: plan '{text}' (got, wanted): {off}"
-    return text
+_assert_plan = isc.assert_plan
 
 
 @pytest.mark.parametrize("case", isc.CASES, ids=isc.case_id)
