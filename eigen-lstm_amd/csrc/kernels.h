@@ -355,6 +355,28 @@ void gen_head(const GenHeadArgs &a, long long t, bool stable, hipStream_t st); /
 int gen_head_status();          // 0, or the HIP error of a refused LDS request (sticky until read)
 int gen_head_group(int N, int streams); // streams per workgroup of gen_head
 
+// ---- beam search (lstm_hip_beam_search): per step beam_head on the state after t inputs, then
+// fwd_step over all streams * W columns with x_next as inputs, reading the REORDERED state beam_head wrote.  Column
+// c = s * W + r is slot r of stream s; per-slot arrays are [streams * W], the tables [count][streams * W].
+struct BeamHeadArgs {
+    const float *Why, *by;
+    const float *H, *C;         // state after t inputs, [streams * W][N]
+    float *Hr, *Cr;             // the same columns in the order of the new slots (never the buffers H, C)
+    const uint8_t *prompts;     // concatenated prompts (null: none)
+    const uint64_t *off;        // streams + 1 prompt offsets (null: no prompts)
+    int32_t *x_next;            // the next input of every column (-1: none)
+    double *cost;               // per slot: summed bits (slot 0 starts at 0, the others at +inf)
+    int32_t *len, *fin;         // per slot: selected bytes so far; 1 once the stop byte was selected
+    uint8_t *trace_parent, *trace_byte; // per selection and slot: the slot it extends, the byte (0 for a finished parent)
+    int N, streams, W, count;
+    int stop_byte;              // -1: none
+};
+void beam_head(const BeamHeadArgs &a, long long t, hipStream_t st);
+int beam_head_status();         // 0, or the HIP error of a refused LDS request (sticky until read)
+// out[(s * W + r) * count + i]: byte i of final slot r of stream s, walked back through the tables; 0 from len on
+void beam_backtrack(const uint8_t *trace_parent, const uint8_t *trace_byte, const int32_t *len, uint8_t *out, int streams,
+                    int W, int count, hipStream_t st);
+
 // ---- model-driven range coder (lstm_hip_encode / lstm_hip_decode): per step code_head on the state
 // after t inputs (byte t of every stream with more than t bytes is coded), then fwd_step over all streams with x_next.
 // Stream s owns text[text_off[s] .. text_off[s+1]) and code[code_base[s] .. code_base[s+1]): the encoder never writes past

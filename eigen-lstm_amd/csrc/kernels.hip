@@ -2020,6 +2020,253 @@ void gen_head(const GenHeadArgs &a, long long t, bool stable, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// beam_head: one step of beam search (lstm_hip_beam_search).  One workgroup per stream s, whose W
+// slots are columns s*W .. s*W+W-1; with L = the stream's prompt length:
+//   t <  L          every slot gets input prompt[t]; the state is copied to Hr / Cr as it is
+//   L <= t < L + C  selection i = t - L (below), the state gathered to Hr / Cr by parent
+//   otherwise       the stream idles (x = -1)
+// Selection: as k_gen_head with SB = W, thread m owns logit m of all W slots (h of the slots in LDS, k-major; the same k
+// order and 16-deep load batching, so a logit has the bits of the generator's).  Per live slot j an owner lane takes
+// zmax = max z and s = the sequential float sum of expf(z - zmax); thread m's candidate (j, m) costs
+// cost_j + (double)lse_surprisal(s, zmax, z_m), NaN taken as +inf.  A finished slot offers one candidate, held by thread 0:
+// itself, cost unchanged, byte 0.  Then W rounds of a block-wide arg-min under (cost ascending, parent ascending, z
+// descending, byte ascending): the thread's best of its register-held candidates (all of one byte, so: lowest cost, then
+// lowest parent; rescanned only after one of them was retired), 6 shuffle steps inside the wave, the four waves through
+// LDS; the winner's thread retires it.  There are always at least W candidates, so every round finds one.  New slot r
+// is round r's winner: tables, cost, length, finished flag and next input are written by thread r.
+// WP: W rounded up to a power of two (register arrays); EXACT: W == WP, so that the LDS stride is a constant.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool beam_before(double c1, int i1, float z1, double c2, int i2, float z2) { // idx = parent * 256 + byte
+    if (c1 != c2) return c1 < c2;
+    if ((i1 >> 8) != (i2 >> 8)) return (i1 >> 8) < (i2 >> 8);
+    if (z1 != z2) return z1 > z2;
+    return (i1 & 255) < (i2 & 255);
+}
+template <int WP, bool EXACT>
+__global__ __launch_bounds__(256) void k_beam_head(BeamHeadArgs a, long long t) {
+    extern __shared__ __attribute__((aligned(16))) float hs[]; // [N][W]
+    __shared__ float ps[WP][256];
+    __shared__ double s_cost[WP], sel_cost[WP], w_cost[4];
+    __shared__ float s_zmax[WP], s_sum[WP], w_z[4];
+    __shared__ int s_len[WP], s_fin[WP], sel_idx[WP], w_idx[4];
+    const int m = threadIdx.x, N = a.N, s = blockIdx.x, W = EXACT ? WP : a.W;
+    const size_t c0 = (size_t)s * W, SW = (size_t)a.streams * W;
+    const long long len = a.off ? (long long)(a.off[s + 1] - a.off[s]) : 0;
+    const bool select = t >= len && t - len < a.count; // (uniform)
+    constexpr int NONE = WP << 8;                      // no candidate: behind every real one (parent WP)
+    if (m < W) sel_idx[m] = m << 8;                    // the gather of a step without a selection: every slot stays
+    if (!select) {
+        if (m < W) a.x_next[c0 + m] = t < len ? (int32_t)a.prompts[a.off[s] + t] : -1;
+    } else {
+        if (m < W) {
+            s_cost[m] = a.cost[c0 + m];
+            s_len[m] = a.len[c0 + m];
+            s_fin[m] = a.fin[c0 + m];
+        }
+        for (int i = m; i < N * W; i += 256) {
+            const int k = i / W, j = i - k * W;
+            hs[i] = a.H[(c0 + j) * N + k];
+        }
+        __syncthreads();
+        float y[WP];
+        int jo[WP]; // slot whose h register j reads (registers W..WP-1 repeat the last slot and are never candidates)
+#pragma unroll
+        for (int j = 0; j < WP; j++) {
+            y[j] = 0.0f;
+            jo[j] = EXACT || j < W ? j : W - 1;
+        }
+        for (int k0 = 0; k0 < N; k0 += 16) { // as k_gen_head: 16 loads in flight, the additions in k order
+            float wv[16];
+#pragma unroll
+            for (int i = 0; i < 16; i++) wv[i] = a.Why[(size_t)(k0 + i) * 256 + m];
+#pragma unroll
+            for (int i = 0; i < 16; i++)
+#pragma unroll
+                for (int j = 0; j < WP; j++) y[j] += wv[i] * hs[(k0 + i) * W + jo[j]];
+        }
+        const float bym = a.by[m];
+#pragma unroll
+        for (int j = 0; j < WP; j++) {
+            y[j] = y[j] + bym; // the logit z
+            if (j < W) ps[j][m] = y[j];
+        }
+        __syncthreads();
+        const int own = (m & 63) * 4 + (m >> 6); // one owner thread per slot, spread over the four waves
+        const bool owner = own < W && !s_fin[own];
+        if (owner) { // (every order gives the same max)
+            float best = ps[own][0];
+            for (int i = 1; i < 256; i++) best = ps[own][i] > best ? ps[own][i] : best;
+            s_zmax[own] = best;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < WP; j++)
+            if (j < W && !s_fin[j]) ps[j][m] = expf(y[j] - s_zmax[j]);
+        __syncthreads();
+        if (owner) {
+            float sum = 0.0f;
+            for (int i = 0; i < 256; i++) sum += ps[own][i];
+            s_sum[own] = sum;
+        }
+        __syncthreads();
+        double ck[WP];        // this thread's candidates: slot j extended by byte m
+        unsigned live = 0;    // ... those that exist and are not yet selected
+#pragma unroll
+        for (int j = 0; j < WP; j++) {
+            ck[j] = (double)INFINITY;
+            if (j >= W) continue;
+            if (s_fin[j]) {
+                if (m == 0) {
+                    ck[j] = s_cost[j];
+                    live |= 1u << j;
+                }
+                y[j] = 0.0f;
+            } else {
+                const double v = s_cost[j] + (double)lse_surprisal(s_sum[j], s_zmax[j], y[j]);
+                ck[j] = v != v ? (double)INFINITY : v;
+                live |= 1u << j;
+            }
+        }
+        double lc = (double)INFINITY; // the thread's best live candidate
+        float lz = 0.0f;
+        int li = NONE;
+        bool rescan = true;
+        for (int r = 0; r < W; r++) {
+            if (rescan) {
+                lc = (double)INFINITY;
+                lz = 0.0f;
+                li = NONE;
+#pragma unroll
+                for (int j = 0; j < WP; j++)
+                    if (((live >> j) & 1u) && (li == NONE || ck[j] < lc)) {
+                        lc = ck[j];
+                        lz = y[j];
+                        li = (j << 8) | m;
+                    }
+                rescan = false;
+            }
+            double bc = lc;
+            float bz = lz;
+            int bi = li;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const double oc = __shfl_xor(bc, o, 64);
+                const float oz = __shfl_xor(bz, o, 64);
+                const int oi = __shfl_xor(bi, o, 64);
+                if (beam_before(oc, oi, oz, bc, bi, bz)) {
+                    bc = oc;
+                    bz = oz;
+                    bi = oi;
+                }
+            }
+            if ((m & 63) == 0) {
+                w_cost[m >> 6] = bc;
+                w_z[m >> 6] = bz;
+                w_idx[m >> 6] = bi;
+            }
+            __syncthreads();
+            bc = w_cost[0];
+            bz = w_z[0];
+            bi = w_idx[0];
+#pragma unroll
+            for (int w = 1; w < 4; w++)
+                if (beam_before(w_cost[w], w_idx[w], w_z[w], bc, bi, bz)) {
+                    bc = w_cost[w];
+                    bz = w_z[w];
+                    bi = w_idx[w];
+                }
+            if (bi < NONE && (bi & 255) == m) { // mine: retired
+                live &= ~(1u << (bi >> 8));
+                rescan = true;
+            }
+            if (m == 0) {
+                sel_idx[r] = bi < NONE ? bi : (W - 1) << 8; // (a round always finds a candidate; the table stays in bounds regardless)
+                sel_cost[r] = bc;
+            }
+            __syncthreads();
+        }
+        if (m < W) {
+            const int p = sel_idx[m] >> 8, b = sel_idx[m] & 255, pf = s_fin[p];
+            const size_t i = (size_t)(t - len);
+            a.trace_parent[i * SW + c0 + m] = (uint8_t)p;
+            a.trace_byte[i * SW + c0 + m] = (uint8_t)b;
+            a.cost[c0 + m] = sel_cost[m];
+            a.len[c0 + m] = s_len[p] + (pf ? 0 : 1);
+            a.fin[c0 + m] = pf || b == a.stop_byte ? 1 : 0;
+            a.x_next[c0 + m] = pf ? -1 : b;
+        }
+    }
+    __syncthreads();
+    // states follow their parents (the workgroup owns every column it reads and writes; Hr / Cr are other buffers)
+    for (int i = m; i < N * W; i += 256) {
+        const int r = i / N, k = i - r * N, p = sel_idx[r] >> 8;
+        a.Hr[(c0 + r) * N + k] = a.H[(c0 + p) * N + k];
+        a.Cr[(c0 + r) * N + k] = a.C[(c0 + p) * N + k];
+    }
+}
+static thread_local hipError_t g_beam_head_error = hipSuccess;
+int beam_head_status() {
+    const hipError_t e = g_beam_head_error;
+    g_beam_head_error = hipSuccess;
+    return (int)e;
+}
+template <int WP, bool EXACT> static void beam_head_launch(const BeamHeadArgs &a, long long t, hipStream_t st) {
+    // static LDS is up to 33 KB (ps), dynamic up to 64 KB; a refused request is an error, not a launch
+    static size_t granted = 0;
+    const size_t lds = (size_t)a.W * a.N * sizeof(float);
+    if (lds > granted) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_beam_head<WP, EXACT>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) {
+            g_beam_head_error = e;
+            return;
+        }
+        granted = lds;
+    }
+    hipLaunchKernelGGL((k_beam_head<WP, EXACT>), dim3(a.streams), dim3(256), lds, st, a, t);
+}
+void beam_head(const BeamHeadArgs &a, long long t, hipStream_t st) {
+    int wp = 1;
+    while (wp < a.W) wp *= 2;
+#define BEAM_HEAD_CASE(WP)                                                                                                  \
+    case WP:                                                                                                                \
+        if (a.W == WP) beam_head_launch<WP, true>(a, t, st);                                                                \
+        else beam_head_launch<WP, false>(a, t, st);                                                                         \
+        break;
+    switch (wp) {
+        BEAM_HEAD_CASE(1)
+        BEAM_HEAD_CASE(2)
+        BEAM_HEAD_CASE(4)
+        BEAM_HEAD_CASE(8)
+        BEAM_HEAD_CASE(16)
+        BEAM_HEAD_CASE(32)
+    }
+#undef BEAM_HEAD_CASE
+}
+// one thread per hypothesis: final slot r of stream s walked back through the tables.  Finished slots only pass
+// through, so the selections that gave the hypothesis a byte are its first len ones.
+__global__ __launch_bounds__(256) void k_beam_backtrack(const uint8_t *__restrict__ trace_parent, const uint8_t *__restrict__ trace_byte,
+                                                        const int32_t *__restrict__ len, uint8_t *__restrict__ out, int streams,
+                                                        int W, int count) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= streams * W) return;
+    const size_t SW = (size_t)streams * W, base = (size_t)(c / W) * W;
+    const int n = len[c];
+    int slot = c % W;
+    for (int i = count - 1; i >= 0; i--) {
+        const size_t e = (size_t)i * SW + base + slot;
+        out[(size_t)c * count + i] = i < n ? trace_byte[e] : (uint8_t)0;
+        const int p = trace_parent[e];
+        slot = p < W ? p : W - 1;
+    }
+}
+void beam_backtrack(const uint8_t *trace_parent, const uint8_t *trace_byte, const int32_t *len, uint8_t *out, int streams, int W,
+                    int count, hipStream_t st) {
+    hipLaunchKernelGGL(k_beam_backtrack, dim3((streams * W + 255) / 256), dim3(256), 0, st, trace_parent, trace_byte, len, out,
+                       streams, W, count);
+}
+
+// ------------------------------------------------------------------------------------------------
 // code_head: one step of the model-driven range coder (lstm_hip_encode / lstm_hip_decode).  Per
 // stream s with more than t bytes, byte t is coded with the distribution of the state after t inputs:
 //   z = Why*h + by        k_gen_head's sum: sequential in k, separate multiply and add, the same SB grouping rule

@@ -53,12 +53,14 @@ enum KernelId {
     K_ADAM,                    // the update launch on a handle set to LSTM_HIP_OPT_ADAM (K_ADAGRAD's launch with the Adam rule)
     K_CODE_HEAD,               // one step of the range coder (lstm_hip_encode / lstm_hip_decode)
     K_BLOCK_WINDOW,            // adaptive coding: a block's training window, carry and bit fold (one launch per block)
+    K_BEAM_HEAD,               // one step of beam search (lstm_hip_beam_search): logits, selection, reordered states
+    K_BEAM_BACKTRACK,          // ... and the walk through its tables, once per call
     K_COUNT
 };
 const char *const kKernelNames[K_COUNT] = {
     "pack_U", "fwd_step", "gemm_Y", "softmax_loss_dy", "loss_reduce", "gemm_DHy", "bwd_step", "gemm_dWhy", "gemm_dU",
     "dW_db", "loss_dby", "adagrad", "slide", "allreduce", "fwd_persistent", "bwd_persistent", "gen_head", "side_sums",
-    "gemm_dU_halves", "grad_sumsq", "grad_norm", "adam", "code_head", "block_window"};
+    "gemm_dU_halves", "grad_sumsq", "grad_norm", "adam", "code_head", "block_window", "beam_head", "beam_backtrack"};
 
 // ---- RCCL, loaded on first use so single-GPU users never touch it --------------------------
 struct UniqueId {
@@ -1630,6 +1632,139 @@ static int check_offsets(const char *what, const char *name, const uint64_t *off
         if (off[s + 1] < off[s])
             return fail(LSTM_HIP_EINVAL, "%s: %s decreases at stream %d (%llu < %llu)", what, name, s,
                         (unsigned long long)off[s + 1], (unsigned long long)off[s]);
+    return 0;
+}
+
+// Beam search (include/lstm_hip.h): the generator's loop over streams * beams columns.  Per step one
+// beam_head launch (selection, tables, the states gathered by parent into the second pair of buffers) and one k_fwd_step
+// from that pair back into the first; after the loop one beam_backtrack launch.  No readback inside the loop.
+int lstm_hip_beam_search(lstm_hip_t *h, int32_t streams, const uint8_t *prompts, const uint64_t *prompt_off, const float *h0,
+                         const float *c0, const lstm_hip_beam *opt, int32_t count, uint8_t *out, int32_t *out_len, double *bits,
+                         uint8_t *trace_parent, uint8_t *trace_byte) {
+    CHECK(h);
+    if (!opt) return fail(LSTM_HIP_EINVAL, "beam_search: null options");
+    if (opt->size != sizeof(lstm_hip_beam))
+        return fail(LSTM_HIP_EINVAL, "beam_search: options of %u bytes, expected %zu", opt->size, sizeof(lstm_hip_beam));
+    const int W = opt->beams;
+    if (W < 1 || W > 32) return fail(LSTM_HIP_EINVAL, "beam_search: beams must be in [1, 32] (got %d)", W);
+    if (opt->stop_byte < -1 || opt->stop_byte > 255)
+        return fail(LSTM_HIP_EINVAL, "beam_search: stop_byte must be -1 or in [0, 255] (got %d)", opt->stop_byte);
+    if (streams < 1 || (long long)streams * W > 4096)
+        return fail(LSTM_HIP_EINVAL, "beam_search: streams must be >= 1 and streams * beams <= 4096 (got %d x %d)", streams, W);
+    if (count < 0) return fail(LSTM_HIP_EINVAL, "beam_search: count < 0 (%d)", count);
+    if (count > 0 && (!out || !out_len || !bits)) return fail(LSTM_HIP_EINVAL, "beam_search: null out, out_len or bits with count > 0");
+    if (prompts && !prompt_off) return fail(LSTM_HIP_EINVAL, "beam_search: prompts without prompt_off");
+    uint64_t max_len = 0;
+    if (prompt_off) {
+        if (int rc = check_offsets("beam_search", "prompt_off", prompt_off, streams)) return rc;
+        for (int s = 0; s < streams; s++) max_len = std::max<uint64_t>(max_len, prompt_off[s + 1] - prompt_off[s]);
+        if (prompt_off[streams] > 0 && !prompts) return fail(LSTM_HIP_EINVAL, "beam_search: prompt_off without prompts");
+    }
+    const int N = h->cfg.N, Nl = h->N_log, cols = streams * W;
+    if ((long long)N * W > 16384)
+        return fail(LSTM_HIP_EINVAL, "beam_search: hidden width %d x %d beams above 16384 floats of LDS", N, W);
+    if (count == 0) { // nothing is selected: every slot is as it starts
+        for (int c = 0; c < cols; c++) {
+            if (out_len) out_len[c] = 0;
+            if (bits) bits[c] = c % W == 0 ? 0.0 : (double)INFINITY;
+        }
+        return 0;
+    }
+    const uint64_t total = prompt_off ? prompt_off[streams] : 0;
+    const size_t n = (size_t)N * cols, nl = (size_t)Nl * cols, nd = (size_t)count * cols;
+
+    size_t bytes = 0;
+    auto piece = [&](size_t b) {
+        const size_t o = bytes;
+        bytes += (b + 255) / 256 * 256;
+        return o;
+    };
+    const size_t o_U = piece(sizeof(float) * 4 * (size_t)N * N), o_H = piece(sizeof(float) * 2 * n), o_C = piece(sizeof(float) * 2 * n),
+                 o_G = piece(sizeof(float) * 4 * n), o_st = piece(h->padded() ? sizeof(float) * 2 * nl : 0),
+                 o_x = piece(sizeof(int32_t) * cols), o_off = piece(prompt_off ? sizeof(uint64_t) * (streams + 1) : 0),
+                 o_p = piece(total), o_tp = piece(nd), o_tb = piece(nd), o_out = piece(nd), o_cost = piece(sizeof(double) * cols),
+                 o_len = piece(sizeof(int32_t) * cols), o_fin = piece(sizeof(int32_t) * cols);
+    if (int rc = reserve_gen_scratch(h, bytes)) return rc;
+    char *base = h->gen_scratch;
+    float4 *Ufwd = reinterpret_cast<float4 *>(base + o_U);
+    float *H = reinterpret_cast<float *>(base + o_H), *Cs = reinterpret_cast<float *>(base + o_C);
+    float *G = reinterpret_cast<float *>(base + o_G), *stage = reinterpret_cast<float *>(base + o_st);
+    int32_t *xi = reinterpret_cast<int32_t *>(base + o_x);
+    uint64_t *d_off = prompt_off ? reinterpret_cast<uint64_t *>(base + o_off) : nullptr;
+    uint8_t *d_prompts = total ? reinterpret_cast<uint8_t *>(base + o_p) : nullptr;
+    uint8_t *d_tp = reinterpret_cast<uint8_t *>(base + o_tp), *d_tb = reinterpret_cast<uint8_t *>(base + o_tb);
+    uint8_t *d_out = reinterpret_cast<uint8_t *>(base + o_out);
+    double *d_cost = reinterpret_cast<double *>(base + o_cost);
+    int32_t *d_len = reinterpret_cast<int32_t *>(base + o_len), *d_fin = reinterpret_cast<int32_t *>(base + o_fin);
+
+    // start state: every slot of a stream starts from the stream's column (padding rows zero)
+    const PadMap map = pad_map_rows(1, Nl, N, cols);
+    std::vector<float> rep;
+    for (int k = 0; k < 2; k++) {
+        const float *src = k ? c0 : h0;
+        float *dst = k ? Cs : H;
+        if (!src) {
+            HIP_TRY(hipMemsetAsync(dst, 0, sizeof(float) * n, h->st));
+            continue;
+        }
+        rep.resize(nl);
+        for (int c = 0; c < cols; c++) std::copy(src + (size_t)(c / W) * Nl, src + (size_t)(c / W + 1) * Nl, rep.begin() + (size_t)c * Nl);
+        if (h->padded()) {
+            HIP_TRY(hipMemcpyAsync(stage + k * nl, rep.data(), sizeof(float) * nl, hipMemcpyHostToDevice, h->st));
+            pad_copy(stage + k * nl, dst, map, true, h->st);
+            if (int rc = pad_status()) return rc;
+        } else
+            HIP_TRY(hipMemcpyAsync(dst, rep.data(), sizeof(float) * n, hipMemcpyHostToDevice, h->st));
+        HIP_TRY(hipStreamSynchronize(h->st)); // (rep is reused)
+    }
+    if (d_off) HIP_TRY(hipMemcpyAsync(d_off, prompt_off, sizeof(uint64_t) * (streams + 1), hipMemcpyHostToDevice, h->st));
+    if (d_prompts) HIP_TRY(hipMemcpyAsync(d_prompts, prompts, total, hipMemcpyHostToDevice, h->st));
+    std::vector<double> cost0(cols, (double)INFINITY);
+    for (int s = 0; s < streams; s++) cost0[(size_t)s * W] = 0.0;
+    HIP_TRY(hipMemcpyAsync(d_cost, cost0.data(), sizeof(double) * cols, hipMemcpyHostToDevice, h->st));
+    HIP_TRY(hipMemsetAsync(d_len, 0, sizeof(int32_t) * cols, h->st));
+    HIP_TRY(hipMemsetAsync(d_fin, 0, sizeof(int32_t) * cols, h->st));
+    HIP_TRY(hipMemsetAsync(d_tp, 0, nd, h->st));
+    HIP_TRY(hipMemsetAsync(d_tb, 0, nd, h->st));
+    RUN(K_PACK_U, pack_U(h->P + h->pl.U, Ufwd, nullptr, N, h->st));
+
+    BeamHeadArgs a{};
+    a.Why = h->P + h->pl.Why;
+    a.by = h->P + h->pl.by;
+    a.H = H;
+    a.C = Cs;
+    a.Hr = H + n;
+    a.Cr = Cs + n;
+    a.prompts = d_prompts;
+    a.off = d_off;
+    a.x_next = xi;
+    a.cost = d_cost;
+    a.len = d_len;
+    a.fin = d_fin;
+    a.trace_parent = d_tp;
+    a.trace_byte = d_tb;
+    a.N = N;
+    a.streams = streams;
+    a.W = W;
+    a.count = count;
+    a.stop_byte = opt->stop_byte;
+    const bool fast = (h->cfg.flags & LSTM_HIP_FAST_MATH) != 0;
+    const long long steps = (long long)max_len + count; // the longest stream's last selection is at step steps - 1
+    for (long long t = 0; t < steps; t++) {
+        RUN(K_BEAM_HEAD, beam_head(a, t, h->st));
+        if (const int e = beam_head_status())
+            return fail(LSTM_HIP_EHIP, "beam_search: the LDS request of beam_head was refused: %s", hipGetErrorString((hipError_t)e));
+        if (t + 1 == steps) break;
+        RUN(K_FWD_STEP, fwd_step(Ufwd, h->P + h->pl.W, h->P + h->pl.b, a.Hr, a.Cr, H, Cs, G, xi, N, cols, fast, h->st));
+    }
+    RUN(K_BEAM_BACKTRACK, beam_backtrack(d_tp, d_tb, d_len, d_out, streams, W, count, h->st));
+
+    HIP_TRY(hipMemcpyAsync(out, d_out, nd, hipMemcpyDeviceToHost, h->st));
+    HIP_TRY(hipMemcpyAsync(out_len, d_len, sizeof(int32_t) * cols, hipMemcpyDeviceToHost, h->st));
+    HIP_TRY(hipMemcpyAsync(bits, d_cost, sizeof(double) * cols, hipMemcpyDeviceToHost, h->st));
+    if (trace_parent) HIP_TRY(hipMemcpyAsync(trace_parent, d_tp, nd, hipMemcpyDeviceToHost, h->st));
+    if (trace_byte) HIP_TRY(hipMemcpyAsync(trace_byte, d_tb, nd, hipMemcpyDeviceToHost, h->st));
+    HIP_TRY(hipStreamSynchronize(h->st));
     return 0;
 }
 

@@ -3,7 +3,8 @@
 // over many streams at once.  No HIP, no torch here.
 //
 //   lstm_generate --load PREFIX [--score FILE ...] [--count C --streams K --prime TEXT|--prime-file F
-//                 --temperature T --top-k K --top-p P --stop-byte B --seed S] [--fast-math] [--stable-softmax] [--device D]
+//                 --temperature T --top-k K --top-p P --stop-byte B --seed S | --beams W --nbest K --length-alpha A]
+//                 [--fast-math] [--stable-softmax] [--device D]
 //
 // --load reads the five-file text checkpoint PREFIX_{W,U,Why,b,by}.txt (checkpoint.h); N is the rows of W / 4.
 // --score runs every FILE as one stream from h = c = 0 and prints "FILE: X.XXXXX bits/char (n bytes)" per file (bits over
@@ -13,6 +14,11 @@
 // --temperature 0 is greedy decoding and takes no draws.  --top-k K (1..255) draws among the K most likely bytes, --top-p P
 // (0 < P < 1) among the smallest most-likely-first set of mass P, and with --stop-byte B (decimal, 0..255; 10 is a newline)
 // a sample ends with its first drawn byte B: it is printed up to and including that byte (lstm_hip_generate_ex).
+// --beams W (1..32) searches instead of drawing (lstm_hip_beam_search): per stream the W most likely continuations of C bytes
+// the beam search finds, of which the --nbest K (default 1) best are printed under "== sample s hypothesis k: X bits ==",
+// ranked by their bits, or with --length-alpha A > 0 by bits / length^A.  It takes --prime, --count, --streams and
+// --stop-byte (a hypothesis ends with its first selected byte B); it draws nothing, so the sampling options are refused.
+// --beams 1 prints the text of --temperature 0.
 // --stable-softmax scores and draws at temperature 1 with the
 // max-shifted softmax (LSTM_HIP_STABLE_SOFTMAX), for checkpoints whose logits pass expf's range.
 #include "../../include/lstm_hip.h"
@@ -31,11 +37,15 @@ namespace {
 
 const char *const kUsage =
     "usage: lstm_generate --load PREFIX [--score FILE ...] [--count C --streams K --prime TEXT|--prime-file F\n"
-    "                     --temperature T --top-k K --top-p P --stop-byte B --seed S]\n"
+    "                     --temperature T --top-k K --top-p P --stop-byte B --seed S\n"
+    "                     | --beams W --nbest K --length-alpha A]\n"
     "                     [--fast-math] [--stable-softmax] [--device D]\n"
     "  --top-k K      draw among the K most likely bytes (1..255; 0 or 256: all)\n"
     "  --top-p P      draw among the smallest most-likely-first set of bytes whose mass reaches P (0 < P <= 1)\n"
-    "  --stop-byte B  end a sample with its first drawn byte B (decimal, 0..255) and print it up to that byte\n";
+    "  --stop-byte B  end a sample with its first drawn byte B (decimal, 0..255) and print it up to that byte\n"
+    "  --beams W      beam search with W hypotheses per stream (1..32) instead of drawing; W x --streams <= 4096\n"
+    "  --nbest K      print the K best hypotheses of every stream (1..W, default 1) with their bits\n"
+    "  --length-alpha A  rank hypotheses by bits / length^A (default 0: by bits)\n";
 
 [[noreturn]] void usage(const std::string &m) {
     fprintf(stderr, "lstm_generate: %s\n%s", m.c_str(), kUsage);
@@ -84,6 +94,9 @@ struct Options {
     long count = -1, streams = 1, device = 0;
     double temperature = 1.0, top_p = 1.0;
     long top_k = 0, stop_byte = -1;
+    long beams = 0, nbest = 1; // beams 0: draw
+    double length_alpha = 0.0;
+    std::vector<std::string> draw_opts, beam_opts; // options that only mean something without / with --beams
     uint32_t seed = 1;
     unsigned flags = 0;
 };
@@ -115,19 +128,34 @@ Options parse(int argc, char **argv) {
         } else if (a == "--temperature") {
             o.temperature = parse_double(a, val());
             o.sampling_opts.push_back(a);
+            o.draw_opts.push_back(a);
         } else if (a == "--top-k") {
             o.top_k = parse_int(a, val(), 0, 256);
             o.sampling_opts.push_back(a);
+            o.draw_opts.push_back(a);
         } else if (a == "--top-p") {
             o.top_p = parse_double(a, val());
             if (!(o.top_p > 0.0 && o.top_p <= 1.0)) usage(a + " needs a number in (0, 1]");
             o.sampling_opts.push_back(a);
+            o.draw_opts.push_back(a);
         } else if (a == "--stop-byte") {
             o.stop_byte = parse_int(a, val(), 0, 255);
             o.sampling_opts.push_back(a);
         } else if (a == "--seed") {
             o.seed = (uint32_t)parse_int(a, val(), 0, 0xFFFFFFFFL);
             o.sampling_opts.push_back(a);
+            o.draw_opts.push_back(a);
+        } else if (a == "--beams") {
+            o.beams = parse_int(a, val(), 1, 32);
+            o.sampling_opts.push_back(a);
+        } else if (a == "--nbest") {
+            o.nbest = parse_int(a, val(), 1, 32);
+            o.sampling_opts.push_back(a);
+            o.beam_opts.push_back(a);
+        } else if (a == "--length-alpha") {
+            o.length_alpha = parse_double(a, val());
+            o.sampling_opts.push_back(a);
+            o.beam_opts.push_back(a);
         }
         else if (a == "--device") o.device = parse_int(a, val(), 0, 1 << 20);
         else if (a == "--fast-math") o.flags |= LSTM_HIP_FAST_MATH;
@@ -142,6 +170,13 @@ Options parse(int argc, char **argv) {
     if (o.has_prime && !o.prime_file.empty()) usage("--prime and --prime-file exclude each other");
     if (o.count < 0 && !o.sampling_opts.empty()) usage(o.sampling_opts[0] + " needs --count");
     if ((long long)std::max(o.count, 0L) * o.streams > (1LL << 31) - 1) usage("--count x --streams is too large");
+    if (o.beams == 0 && !o.beam_opts.empty()) usage(o.beam_opts[0] + " needs --beams");
+    if (o.beams > 0) {
+        if (!o.draw_opts.empty()) usage(o.draw_opts[0] + " means nothing with --beams: a beam search draws nothing");
+        if (o.nbest > o.beams) usage("--nbest cannot pass --beams");
+        if (o.beams * o.streams > 4096) usage("--beams x --streams must be at most 4096");
+        if ((long long)std::max(o.count, 0L) * o.streams * o.beams > (1LL << 31) - 1) usage("--count x --streams x --beams is too large");
+    }
     return o;
 }
 
@@ -195,7 +230,34 @@ int main(int argc, char **argv) {
         printf("total: %.5f bits/char (%.0f bytes scored in %zu files)\n", sum_bits / sum_chars, sum_chars, texts.size());
     }
 
-    if (o.count >= 0) {
+    if (o.count >= 0 && o.beams > 0) {
+        const int K = (int)o.streams, C = (int)o.count, W = (int)o.beams;
+        std::vector<uint64_t> off(K + 1);
+        std::vector<uint8_t> prompts;
+        for (int s = 0; s < K; s++) {
+            prompts.insert(prompts.end(), prime.begin(), prime.end());
+            off[s + 1] = prompts.size();
+        }
+        std::vector<uint8_t> out((size_t)C * K * W + 1);
+        std::vector<int32_t> out_len((size_t)K * W);
+        std::vector<double> bits((size_t)K * W);
+        const lstm_hip_beam opt{(uint32_t)sizeof(lstm_hip_beam), (int32_t)W, (int32_t)o.stop_byte};
+        CK(lstm_hip_beam_search(h, K, prompts.data(), off.data(), nullptr, nullptr, &opt, C, out.data(), out_len.data(), bits.data(),
+                                nullptr, nullptr));
+        for (int s = 0; s < K; s++) {
+            std::vector<int> order(W);
+            for (int r = 0; r < W; r++) order[r] = s * W + r;
+            auto score = [&](int c) { return bits[c] / std::pow((double)std::max(out_len[c], 1), o.length_alpha); };
+            if (o.length_alpha > 0.0) std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return score(x) < score(y); });
+            for (int k = 0; k < (int)o.nbest; k++) {
+                const int c = order[k];
+                printf("== sample %d hypothesis %d: %.5f bits ==\n", s, k, bits[c]);
+                fwrite(prime.data(), 1, prime.size(), stdout);
+                fwrite(out.data() + (size_t)c * C, 1, (size_t)out_len[c], stdout);
+                fputc('\n', stdout);
+            }
+        }
+    } else if (o.count >= 0) {
         const int K = (int)o.streams, C = (int)o.count;
         std::vector<uint64_t> off(K + 1);
         std::vector<uint8_t> prompts;

@@ -43,6 +43,10 @@ class _Sampling(C.Structure):  # lstm_hip_sampling
                 ("stop_byte", C.c_int32)]
 
 
+class _Beam(C.Structure):  # lstm_hip_beam
+    _fields_ = [("size", C.c_uint32), ("beams", C.c_int32), ("stop_byte", C.c_int32)]
+
+
 class _Config(C.Structure):
     _fields_ = [("N", C.c_int32), ("M", C.c_int32), ("S", C.c_int32), ("B", C.c_int32), ("device", C.c_int32),
                 ("flags", C.c_uint32)]
@@ -63,7 +67,7 @@ SYMBOLS = [
     "lstm_hip_set_grad_clip", "lstm_hip_get_grad_norms", "lstm_hip_set_optimizer", "lstm_hip_get_optimizer_steps",
     "lstm_hip_set_optimizer_steps", "lstm_hip_coder_version", "lstm_hip_code_bound", "lstm_hip_encode", "lstm_hip_decode",
     "lstm_hip_adaptive_version", "lstm_hip_adaptive_blocks", "lstm_hip_encode_adaptive", "lstm_hip_decode_adaptive",
-    "lstm_hip_plan_identity",
+    "lstm_hip_plan_identity", "lstm_hip_beam_search",
 ]
 
 
@@ -397,6 +401,47 @@ class Lstm:
         _chk(self.lib.lstm_hip_generate_ex(*args, C.byref(opt), *tail, _ptr(out_len, C.c_int32),
                                            _ptr(kept, C.c_uint16) if info else None))
         return (out, bits, h, c, {"out_len": out_len, "kept": kept}) if info else (out, bits, h, c)
+
+    def beam_search(self, prompts=None, count=0, beams=4, stop_byte=-1, h0=None, c0=None, streams=None, length_alpha=0.0,
+                    trace=False):
+        """lstm_hip_beam_search: per stream the `beams` most likely continuations of its prompt the search finds.  Returns a
+        list (one entry per stream) of lists of (bytes, bits), best first: the hypothesis cut to its length (a stop byte
+        included) and its cost.  length_alpha > 0 re-ranks each stream's list on the host by bits / len**length_alpha (a
+        stable sort; empty hypotheses rank by their bits); the ABI itself always returns raw cost order.  trace=True adds a
+        second result {"out": uint8 [streams, beams, count], "out_len": int32 [streams, beams], "bits": float64 [streams,
+        beams], "parent", "byte": uint8 [count, streams * beams]} with the call's raw arrays."""
+        if streams is None:
+            streams = len(prompts) if prompts is not None else (np.asarray(h0).shape[0] if h0 is not None else 1)
+        streams, count, W = int(streams), int(count), int(beams)
+        d_p = d_off = None
+        if prompts is not None:
+            assert len(prompts) == streams, (len(prompts), streams)
+            d_p, d_off = _offsets(_bytes_list(prompts))
+        hh = None if h0 is None else _f32(h0).reshape(streams, self.N)
+        cc = None if c0 is None else _f32(c0).reshape(streams, self.N)
+        cols = max(streams * W, 1)
+        out = np.zeros((cols, max(count, 0)), np.uint8)
+        out_len = np.zeros(cols, np.int32)
+        bits = np.zeros(cols, np.float64)
+        tp = np.zeros((max(count, 0), cols), np.uint8)
+        tb = np.zeros((max(count, 0), cols), np.uint8)
+        opt = _Beam(C.sizeof(_Beam), W, int(stop_byte))
+        _chk(self.lib.lstm_hip_beam_search(
+            self._h, C.c_int32(streams), _ptr(d_p, C.c_uint8) if d_p is not None else None,
+            _ptr(d_off, C.c_uint64) if d_off is not None else None, _ptr(hh) if hh is not None else None,
+            _ptr(cc) if cc is not None else None, C.byref(opt), C.c_int32(count), _ptr(out, C.c_uint8),
+            _ptr(out_len, C.c_int32), _ptr(bits, C.c_double), _ptr(tp, C.c_uint8) if trace else None,
+            _ptr(tb, C.c_uint8) if trace else None))
+        res = []
+        for s in range(streams):
+            hyp = [(out[s * W + r, :out_len[s * W + r]].tobytes(), float(bits[s * W + r])) for r in range(W)]
+            if length_alpha > 0:
+                hyp.sort(key=lambda e: e[1] / max(len(e[0]), 1) ** length_alpha)
+            res.append(hyp)
+        if trace:
+            return res, {"out": out.reshape(streams, W, count), "out_len": out_len.reshape(streams, W),
+                         "bits": bits.reshape(streams, W), "parent": tp, "byte": tb}
+        return res
 
     def encode(self, texts, trace=False):
         """lstm_hip_encode: each of `texts` (bytes or uint8 arrays) is one stream, coded from a zero state.  Returns

@@ -289,6 +289,49 @@ int lstm_hip_generate_ex(lstm_hip_t *h, int32_t streams, const uint8_t *prompts,
                          const float *h0, const float *c0, const lstm_hip_sampling *opt, const double *u, int32_t count,
                          uint8_t *out, double *bits, float *h_out, float *c_out,
                          int32_t *out_len /* [streams], may be NULL */, uint16_t *kept /* [count*streams], may be NULL */);
+/* ---- beam search: per stream the W = opt->beams most likely continuations of its prompt that the
+ *      search finds, with their costs in bits.  Prompts, prompt_off, h0 / c0 (N x streams; NULL = zeros) are those of
+ *      lstm_hip_generate.  Stream s is fed its prompt of length L (nothing is scored during the prompt) and makes selection
+ *      i = t - L at steps t = L .. L+count-1.  It keeps W slots; all start from the stream's start state, slot 0 with cost 0
+ *      and slots 1..W-1 with cost +inf, so the first selection expands slot 0 only.
+ *        cost       of extending live slot j by byte m: z = Why*h_j + by summed as lstm_hip_generate sums it (sequentially in
+ *                   k, separate multiply and add); zmax = max z; s = the sequential float sum, in index order, of
+ *                   expf(z_k - zmax); c_m = log2f(s) + (zmax - z_m) * 1.44269504088896341f in float (the surprisal of the
+ *                   LSTM_HIP_STABLE_SOFTMAX prompt scorer: ALWAYS max-shifted, whatever that flag says).  The candidate
+ *                   costs the double cost_j + (double)c_m.  Only the fp32 parameters are read (a bf16 handle searches as an
+ *                   fp32 one); LSTM_HIP_FAST_MATH applies to the recurrence only, as in lstm_hip_generate.
+ *        finished   a slot is finished by its first SELECTED byte equal to stop_byte.  A finished slot offers exactly one
+ *                   candidate: itself, cost unchanged, byte 0, no new input.
+ *        selection  of all candidates of the stream, the first W in this order are selected: cost ascending (NaN taken as
+ *                   +inf), then parent slot ascending, then z descending, then byte ascending; new slot r is the r-th of
+ *                   them.  (Ordering by z inside one parent makes beams = 1 exactly greedy decoding, lowest index on ties.)
+ *        records    trace_parent[i*streams*W + s*W + r] and trace_byte[..] (both may be NULL): the slot that new slot r
+ *                   extends and the byte.  The slot's length is its parent's + 1 for a live parent, unchanged for a finished
+ *                   one; it is finished when the selected byte is stop_byte.  A live slot's byte is its next input (the stop
+ *                   byte is still fed, though no output depends on it); a finished slot gets no input.  States follow parents.
+ *        results    per stream the final slots in rank order r = 0..W-1; hypothesis r is found by walking the back-pointers
+ *                   from the last selection.  out[(s*W + r)*count + i] holds its bytes and is 0 from out_len[s*W + r] on;
+ *                   out_len includes the stop byte; bits[s*W + r] is the cost (raw cost order: no length normalisation).
+ *      No final states are returned: feed prompt + hypothesis to lstm_hip_generate with count 0 to continue from one.  The
+ *      loop runs max L + count steps with no readback and no early exit.  Nothing of the handle but P is read or written,
+ *      as for lstm_hip_generate.  With count 0 nothing is selected: out_len = 0 and bits = the start costs, where given.
+ *      With non-finite parameters the hypotheses are unspecified, but they are bytes and every index stays in its table.
+ *      LSTM_HIP_EINVAL (the handle stays usable): opt NULL or opt->size != sizeof(lstm_hip_beam), beams outside 1..32,
+ *      streams < 1 or streams * beams > 4096, internal hidden width * beams > 16384, count < 0, stop_byte outside -1..255,
+ *      offsets not starting at 0 or decreasing, prompts without offsets or offsets without prompts, out, out_len or bits
+ *      NULL with count > 0.  LSTM_HIP_EHIP: the device refused the kernel's LDS request. */
+typedef struct lstm_hip_beam {
+    uint32_t size;      /* sizeof(lstm_hip_beam); anything else: LSTM_HIP_EINVAL */
+    int32_t  beams;     /* W: 1..32 hypotheses kept per stream */
+    int32_t  stop_byte; /* -1: off; 0..255: a hypothesis is finished by its first SELECTED byte equal to it */
+} lstm_hip_beam;
+int lstm_hip_beam_search(lstm_hip_t *h, int32_t streams, const uint8_t *prompts, const uint64_t *prompt_off,
+                         const float *h0, const float *c0, const lstm_hip_beam *opt, int32_t count,
+                         uint8_t *out      /* [streams][W][count] */,
+                         int32_t *out_len  /* [streams*W] */,
+                         double  *bits     /* [streams*W] */,
+                         uint8_t *trace_parent /* [count][streams*W], may be NULL */,
+                         uint8_t *trace_byte   /* [count][streams*W], may be NULL */);
 
 /* ---- arithmetic coding of bytes with the model.  Stream s is text[text_off[s] .. text_off[s+1]),
  *      1 <= streams <= 4096, each coded on its own from h = c = 0 (empty streams allowed: their code is empty).
