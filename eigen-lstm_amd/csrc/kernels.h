@@ -321,10 +321,13 @@ PadMap pad_map_rows(int blocks, int N, int Np, int cols); // `cols` columns of `
 void pad_copy(const float *src, float *dst, const PadMap &map, bool to_padded, hipStream_t st);
 
 // ---- B = 1 recurrence for the evaluator / sampler (OV/lstm_eigen_class_CUDA/lstm.cc:578-720)
-void eval_bits(const float *P, int N, const uint8_t *text, uint64_t len, double *out_bits_sum, float *scratch, bool stable,
-               hipStream_t st);
-void sample(const float *P, int N, float *hc /*2N*/, const double *u, int count, uint8_t *out, float *scratch, bool stable,
-            hipStream_t st);
+// One workgroup with b1_lds_bytes(N) of dynamic LDS, which the caller checks against the device's opt-in limit first; both
+// return the status of the grant and of the launch.
+size_t b1_lds_bytes(int N);
+hipError_t eval_bits(const float *P, int N, const uint8_t *text, uint64_t len, double *out_bits_sum, float *scratch, bool stable,
+                     hipStream_t st);
+hipError_t sample(const float *P, int N, float *hc /*2N*/, const double *u, int count, uint8_t *out, float *scratch, bool stable,
+                  hipStream_t st);
 
 // ---- batched generator (lstm_hip_generate): per step gen_head on the state after t inputs, then fwd_step over all
 // streams with x_next as inputs.  Arrays are [streams] or [count][streams]; H, C, h_out, c_out are [streams][N], N % 16 == 0

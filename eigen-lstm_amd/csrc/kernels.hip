@@ -1674,11 +1674,25 @@ __global__ __launch_bounds__(1024) void k_eval_bits(const float *__restrict__ P,
     }
     if (threadIdx.x == 0) out[0] = err;
 }
-void eval_bits(const float *P, int N, const uint8_t *text, uint64_t len, double *out_bits_sum, float *, bool stable,
-               hipStream_t st) {
-    const size_t lds = (size_t)(6 * N + 256) * sizeof(float);
-    if (stable) hipLaunchKernelGGL(k_eval_bits<true>, dim3(1), dim3(1024), lds, st, P, N, text, len, out_bits_sum);
-    else hipLaunchKernelGGL(k_eval_bits<false>, dim3(1), dim3(1024), lds, st, P, N, text, len, out_bits_sum);
+// h, c, the four gates and the 256 outputs of the one workgroup
+size_t b1_lds_bytes(int N) { return (size_t)(6 * N + 256) * sizeof(float); }
+// Above 32 KB the request is granted to the kernel first (64 KB is what a launch gets unasked, N = 2688); a refused grant or
+// launch is returned, never passed over.  The caller has compared b1_lds_bytes with the device's opt-in limit.
+#define B1_LAUNCH(kernel, ...)                                                                                              \
+    do {                                                                                                                    \
+        if (lds > 32768) {                                                                                                  \
+            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),                                \
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                 \
+            if (e != hipSuccess) return e;                                                                                  \
+        }                                                                                                                   \
+        hipLaunchKernelGGL(kernel, dim3(1), dim3(1024), lds, st, __VA_ARGS__);                                              \
+        return hipGetLastError();                                                                                           \
+    } while (0)
+hipError_t eval_bits(const float *P, int N, const uint8_t *text, uint64_t len, double *out_bits_sum, float *, bool stable,
+                     hipStream_t st) {
+    const size_t lds = b1_lds_bytes(N);
+    if (stable) B1_LAUNCH(k_eval_bits<true>, P, N, text, len, out_bits_sum);
+    else B1_LAUNCH(k_eval_bits<false>, P, N, text, len, out_bits_sum);
 }
 template <bool STABLE>
 __global__ __launch_bounds__(1024) void k_sample(const float *__restrict__ P, int N, float *__restrict__ hc,
@@ -2525,11 +2539,13 @@ void block_window(const BlockWindowArgs &a, int cus, hipStream_t st) {
     hipLaunchKernelGGL(k_block_window, dim3(blocks), dim3(256), 0, st, a);
 }
 
-void sample(const float *P, int N, float *hc, const double *u, int count, uint8_t *out, float *, bool stable, hipStream_t st) {
-    const size_t lds = (size_t)(6 * N + 256) * sizeof(float);
-    if (stable) hipLaunchKernelGGL(k_sample<true>, dim3(1), dim3(1024), lds, st, P, N, hc, u, count, out);
-    else hipLaunchKernelGGL(k_sample<false>, dim3(1), dim3(1024), lds, st, P, N, hc, u, count, out);
+hipError_t sample(const float *P, int N, float *hc, const double *u, int count, uint8_t *out, float *, bool stable,
+                  hipStream_t st) {
+    const size_t lds = b1_lds_bytes(N);
+    if (stable) B1_LAUNCH(k_sample<true>, P, N, hc, u, count, out);
+    else B1_LAUNCH(k_sample<false>, P, N, hc, u, count, out);
 }
+#undef B1_LAUNCH
 
 // ------------------------------------------------------------------------------------------------
 // pad_copy: logical <-> padded hidden width (kernels.h).  One thread per DESTINATION float (grid-stride), so every float of

@@ -1329,11 +1329,28 @@ static int ensure_aux_handle(lstm_hip_ctx *h) {
     return lstm_hip_create(&c, &h->eval_h);
 }
 
+// The one-workgroup evaluator and sampler of a handle on the per-step engine keep h, c and the gates in LDS: refused, before
+// anything is allocated, where the device cannot grant that much to one workgroup.
+static int b1_lds_check(lstm_hip_ctx *h, const char *who) {
+    int optin = 0;
+    HIP_TRY(hipDeviceGetAttribute(&optin, hipDeviceAttributeSharedMemPerBlockOptin, h->cfg.device));
+    const size_t need = b1_lds_bytes(h->cfg.N);
+    if (need > (size_t)optin)
+        return fail(LSTM_HIP_EINVAL, "%s: N=%d (internal width %d) needs %zu bytes of LDS in one workgroup, the device grants %d (N <= %d)",
+                    who, h->N_log, h->cfg.N, need, optin, (optin / 4 - 256) / 6 / 16 * 16);
+    return 0;
+}
+static int b1_status(const char *who, hipError_t e) {
+    if (e != hipSuccess) return fail(LSTM_HIP_EHIP, "launch of %s failed: %s", who, hipGetErrorString(e));
+    return 0;
+}
+
 int lstm_hip_eval_bits(lstm_hip_t *h, const uint8_t *text, size_t len, double *bits_per_char) {
     CHECK(h);
     if (!text || len < 2 || !bits_per_char) return fail(LSTM_HIP_EINVAL, "eval_bits: need >= 2 bytes and an output pointer");
     const int N = h->cfg.N;
     if (!h->plan.persistent()) {
+        if (int rc = b1_lds_check(h, "eval_bits")) return rc;
         uint8_t *d_text = nullptr;
         struct Free {
             uint8_t *&p;
@@ -1343,7 +1360,9 @@ int lstm_hip_eval_bits(lstm_hip_t *h, const uint8_t *text, size_t len, double *b
         } free_text{d_text};
         HIP_TRY(hipMalloc((void **)&d_text, len));
         HIP_TRY(hipMemcpyAsync(d_text, text, len, hipMemcpyHostToDevice, h->st));
-        eval_bits(h->P, N, d_text, len, h->d_loss, nullptr, (h->cfg.flags & LSTM_HIP_STABLE_SOFTMAX) != 0, h->st);
+        if (int rc = b1_status("eval_bits", eval_bits(h->P, N, d_text, len, h->d_loss, nullptr,
+                                                      (h->cfg.flags & LSTM_HIP_STABLE_SOFTMAX) != 0, h->st)))
+            return rc;
         double sum = 0.0;
         HIP_TRY(hipMemcpyAsync(&sum, h->d_loss, sizeof(double), hipMemcpyDeviceToHost, h->st));
         HIP_TRY(hipStreamSynchronize(h->st));
@@ -1396,6 +1415,7 @@ int lstm_hip_sample(lstm_hip_t *h, float *h0, float *c0, const double *u, int32_
     if (h->plan.persistent() && count > 0)
         return lstm_hip_generate(h, 1, nullptr, nullptr, h0, c0, 1.0, u, count, out, nullptr, h0, c0);
     const int N = h->cfg.N;
+    if (int rc = b1_lds_check(h, "sample")) return rc;
     float *d_hc = nullptr;
     double *d_u = nullptr;
     uint8_t *d_out = nullptr;
@@ -1423,7 +1443,9 @@ int lstm_hip_sample(lstm_hip_t *h, float *h0, float *c0, const double *u, int32_
         HIP_TRY(hipMemcpyAsync(d_hc + N, c0, sizeof(float) * N, hipMemcpyHostToDevice, h->st));
     }
     HIP_TRY(hipMemcpyAsync(d_u, u, sizeof(double) * count, hipMemcpyHostToDevice, h->st));
-    sample(h->P, N, d_hc, d_u, count, d_out, nullptr, (h->cfg.flags & LSTM_HIP_STABLE_SOFTMAX) != 0, h->st);
+    if (int rc = b1_status("sample", sample(h->P, N, d_hc, d_u, count, d_out, nullptr,
+                                            (h->cfg.flags & LSTM_HIP_STABLE_SOFTMAX) != 0, h->st)))
+        return rc;
     if (h->padded()) {
         pad_copy(d_hc, h->stage, hc_map, false, h->st);
         if (int rc = pad_status()) return rc;

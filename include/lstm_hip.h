@@ -224,7 +224,11 @@ int lstm_hip_set_loss_mode(lstm_hip_t *h, int32_t mode);
 
 /* ---- held-out evaluator and sampler on the device (OV/lstm_eigen_class_CUDA/lstm.cc:661-720,
  *      578-659; R/lstm.cc:293-356).  eval: bits/char of `text` from h = c = 0.  sample: `count`
- *      bytes from state (h0,c0) (N floats each, in/out) using the caller's uniform draws u[i]. */
+ *      bytes from state (h0,c0) (N floats each, in/out) using the caller's uniform draws u[i].
+ *      Limit: a handle on the per-step engine (every width without a persistent recurrence, so every N > 1024) runs
+ *      both in one workgroup with (6 Np + 256) * 4 bytes of LDS, Np the internal width.  Where that exceeds the
+ *      device's opt-in limit per workgroup (160 KB on gfx950, which holds Np <= 6784) both return LSTM_HIP_EINVAL with a message
+ *      naming N, before anything runs; the handle stays usable.  A launch the runtime refuses is LSTM_HIP_EHIP. */
 int lstm_hip_eval_bits(lstm_hip_t *h, const uint8_t *text, size_t len, double *bits_per_char);
 int lstm_hip_sample(lstm_hip_t *h, float *h0, float *c0, const double *u, int32_t count, uint8_t *out);
 /* ---- batched, prompted sampling and per-text scoring (the loops of R/lstm.cc:293-356 and

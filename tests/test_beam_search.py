@@ -59,7 +59,7 @@ def _check_shape_of_a_result(res, W, count, stop):
                 assert len(t) == count, t
 
 
-@pytest.mark.parametrize("N", [64, 512])
+@pytest.mark.parametrize("N", [64, 192, 512])   # (192: a width the plan puts on the per-step engine)
 def test_one_beam_is_greedy_decoding(N):
     count = 40
     P = _params(N, seed=3, scale=0.3 if N == 64 else 0.1)

@@ -73,6 +73,7 @@ FORMS = [  # (N, S, B, flags, stride): every engine form the plan picks
     (1024, 20, 16, ("BF16_RECURRENCE",), 1),
     (256, 10, 16, ("NO_FUSED_GRADS",), 1),
     (128, 16, 8, (), 8),                      # segment variant: stride S/2
+    (192, 6, 17, (), 1),                      # a width without a persistent recurrence: the plan's own per-step engine
 ]
 
 

@@ -379,8 +379,7 @@ def _synthetic_text(n, seed=3):
     return rs.choice(np.arange(32, 127), size=n, p=None).astype(np.uint8)
 
 
-@pytest.mark.parametrize("N,S,B,windows", [(32, 6, 4, 40), (64, 10, 20, 25)])
-def test_device_resident_loop_follows_the_oracle_trainer(N, S, B, windows, oracle32):
+def device_loop_follows_the_oracle_trainer(N, S, B, windows, orc, plan=None, lr=0.1):
     """lstm_hip_train_windows (slide + forward + loss + BPTT + Adagrad on the device) against the
     oracle's restatement of the reference loop (OV/lstm_eigen_opt/lstm.cc:186-318), same seed.
     Starts with an EMPTY window (all-zero x/target columns) and a text short enough that the cursors
@@ -390,13 +389,18 @@ def test_device_resident_loop_follows_the_oracle_trainer(N, S, B, windows, oracl
     before every window the device's parameters, Adagrad memory and carry are re-synchronised to the
     oracle's, so each window is compared from identical state: loss |d| <= 2e-5*(S-1), parameters
     after the step |d| <= 2e-4*lr where the gradient is above noise.  The window indices and cursors
-    live on the device the whole time and must match bit for bit."""
+    live on the device the whole time and must match bit for bit.
+    plan: fields of lstm_hip_plan_identity the handle must show (input_stats_cases.assert_plan).  Returns the largest
+    distances seen: dict(loss, state, params)."""
+    import input_stats_cases
     import lstm_hip
     text = _synthetic_text(S + 24)
-    lr = 0.1
-    tr = oracle32.trainer(text, N, S, B, lr=lr, seed=1)
+    tr = orc.trainer(text, N, S, B, lr=lr, seed=1)
     tr.epoch_reset()
     L = lstm_hip.Lstm(N, S, B)
+    if plan:
+        input_stats_cases.assert_plan(L, plan)
+    fig = dict(loss=0.0, state=0.0, params=0.0)
     L.set_text(text)
     pos0 = lstm_hip.initial_cursors(len(text), S, B)
     L.set_cursors(pos0)
@@ -411,13 +415,22 @@ def test_device_resident_loop_follows_the_oracle_trainer(N, S, B, windows, oracl
         xi, ti = L.get_window()
         assert np.array_equal(xi, tr.xi) and np.array_equal(ti, tr.ti), w          # bit-exact index work
         h1, c1 = L.get_state(1)
-        assert gu.max_rel(h1, tr.h[1]) <= ACT_TOL and gu.max_rel(c1, tr.c[1]) <= ACT_TOL
+        state = max(gu.max_rel(h1, tr.h[1]), gu.max_rel(c1, tr.c[1]))
+        assert state <= ACT_TOL, (w, state)
         d = tr.grads
         mask = np.abs(d) > 1e-3 * np.abs(d).max()
-        assert np.abs(L.get_params()[mask] - tr.params[mask]).max() <= 2e-4 * lr + 1e-6, w
+        p_err = float(np.abs(L.get_params()[mask] - tr.params[mask]).max())
+        assert p_err <= 2e-4 * lr + 1e-6, (w, p_err)
+        fig = dict(loss=max(fig["loss"], float(abs(got - want))), state=max(fig["state"], state), params=max(fig["params"], p_err))
     want_pos = np.array([_wrap(int(p), windows, len(text), S) for p in pos0])
     assert np.array_equal(L.get_cursors().astype(np.int64), want_pos)
     L.close()
+    return fig
+
+
+@pytest.mark.parametrize("N,S,B,windows", [(32, 6, 4, 40), (64, 10, 20, 25)])
+def test_device_resident_loop_follows_the_oracle_trainer(N, S, B, windows, oracle32):
+    device_loop_follows_the_oracle_trainer(N, S, B, windows, oracle32)
 
 
 # HIP-vs-oracle distance allowed, in units of the largest distance between two correct CPU implementations (the controls).

@@ -122,7 +122,8 @@ def _case(N, S, B, flags, seed, t0, wd, loop):
 
 
 RULE_SHAPES = [(512, 100, 64, ()), (256, 10, 16, ()), (512, 10, 16, ("BF16_RECURRENCE",)), (64, 6, 4, ("STEP_KERNELS",)),
-               (256, 10, 16, ("NO_FUSED_GRADS",)), (128, 25, 1, ())]
+               (256, 10, 16, ("NO_FUSED_GRADS",)), (128, 25, 1, ()),
+               (192, 6, 17, ())]   # a width without a persistent recurrence: the plan's own per-step engine
 
 
 @pytest.mark.parametrize("loop", [True, False], ids=["train_windows", "adagrad"])
