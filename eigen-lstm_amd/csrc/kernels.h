@@ -353,6 +353,11 @@ struct GenHeadArgs {
     int stop_byte;              // -1: none; else a stream ends with its first drawn byte equal to it
     int32_t *end;               // [streams] number of bytes each stream draws: `count` at the start, i + 1 once draw i stops it
     uint16_t *kept;             // [count][streams] bytes kept per draw (null: not wanted); zeroed by the caller
+    // byte automaton (lstm_hip_generate_constrained): read only by the CONSTRAIN instantiation, which
+    // gen_head takes when `ctab` is set (`end` is set with it)
+    const uint16_t *ctab;       // [states][256] the state after byte b in state q, 0xFFFF: b is forbidden there
+    const uint16_t *ccount;     // [states] allowed bytes of each state (>= 1 for every state a stream can reach)
+    int32_t *cstate;            // [streams] the state of every stream: after its prompt at the start, then after each drawn byte
 };
 void gen_head(const GenHeadArgs &a, long long t, bool stable, hipStream_t st); // stable: LSTM_HIP_STABLE_SOFTMAX
 int gen_head_status();          // 0, or the HIP error of a refused LDS request (sticky until read)

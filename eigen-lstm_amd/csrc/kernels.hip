@@ -1762,6 +1762,12 @@ __global__ __launch_bounds__(1024) void k_sample(const float *__restrict__ P, in
 //   a.stop_byte a stream draws a.end[s] bytes, not a.count: the owner lane sets it to i + 1 when draw i is the stop byte, so
 //               the next launch copies the state after that byte to h_out / c_out and the stream idles.
 //   a.kept      keep per filtered draw, 256 per unfiltered one, 1 per greedy one.
+// CONSTRAIN (lstm_hip_generate_constrained; implies FILTER, and without it the instantiation is the
+// code above and nothing else): stream s is in state q = a.cstate[s] of the byte automaton a.ctab.  For a drawn byte thread m
+// loads a.ctab[q * 256 + m] and, where that is 0xFFFF (forbidden), sets its logit to -inf before the logit goes to ps: rank,
+// max, expf and sum all see the masked value.  A tempered draw is then always a filtered one, keep capped by a.ccount[q] (the
+// allowed bytes of q), so the kept bytes are allowed ones.  The owner lane replaces a byte that is forbidden all the same
+// (non-finite logits only) by the lowest allowed byte of q and writes the next state to a.cstate[s].  Prompt bytes ignore it.
 // ------------------------------------------------------------------------------------------------
 // what stream s does at step t: 0 idle, 1 prompt byte scored, 2 drawn byte, 3 prompt byte not scored; *len = its prompt length
 // (*drawn: the bytes the stream draws -- the call's count, or with FILTER its own end index)
@@ -1773,8 +1779,9 @@ __device__ __forceinline__ int gen_phase(const GenHeadArgs &a, int s, long long 
     if (t < *len) return (t >= 1 && a.bits) ? 1 : 3;
     return t - *len < n ? 2 : 0;
 }
-template <int SB, bool STABLE, bool FILTER>
+template <int SB, bool STABLE, bool FILTER, bool CONSTRAIN = false>
 __global__ __launch_bounds__(256) void k_gen_head(GenHeadArgs a, long long t) {
+    static_assert(FILTER || !CONSTRAIN, "CONSTRAIN implies FILTER");
     extern __shared__ __attribute__((aligned(16))) float hs[]; // [N][SB]
     __shared__ float ps[SB][256];
     __shared__ float s_zmax[SB], s_sum[SB], s_zt[STABLE ? SB : 1];
@@ -1783,6 +1790,7 @@ __global__ __launch_bounds__(256) void k_gen_head(GenHeadArgs a, long long t) {
     __shared__ int s_keep[FILTER ? SB : 1], s_last[FILTER ? SB : 1]; // bytes kept; the largest kept index
     const int m = threadIdx.x, N = a.N, s0 = blockIdx.x * SB;
     int phase[SB]; // (the same in every thread)
+    [[maybe_unused]] int cq[CONSTRAIN ? SB : 1]; // the automaton state of each drawing stream (read before any barrier)
     bool need = false;
 #pragma unroll
     for (int j = 0; j < SB; j++) {
@@ -1793,6 +1801,7 @@ __global__ __launch_bounds__(256) void k_gen_head(GenHeadArgs a, long long t) {
         int drawn;
         phase[j] = gen_phase<FILTER>(a, s, t, &len, &drawn);
         need |= phase[j] == 1 || phase[j] == 2;
+        if constexpr (CONSTRAIN) cq[j] = phase[j] == 2 ? a.cstate[s] : 0;
         if (t == len + drawn) { // the state after the stream's last input
             if (a.h_out)
                 for (int k = m; k < N; k += 256) a.h_out[(size_t)s * N + k] = a.H[(size_t)s * N + k];
@@ -1801,6 +1810,11 @@ __global__ __launch_bounds__(256) void k_gen_head(GenHeadArgs a, long long t) {
         }
     }
     if (need) { // (uniform)
+        [[maybe_unused]] bool banned[CONSTRAIN ? SB : 1]; // is byte m forbidden where stream j stands?  (loaded ahead of the product)
+        if constexpr (CONSTRAIN) {
+#pragma unroll
+            for (int j = 0; j < SB; j++) banned[j] = phase[j] == 2 && a.ctab[(size_t)cq[j] * 256 + m] == 0xFFFF;
+        }
         for (int i = m; i < N * SB; i += 256) {
             const int k = i / SB, j = i - k * SB;
             hs[i] = s0 + j < a.streams ? a.H[(size_t)(s0 + j) * N + k] : 0.0f;
@@ -1824,10 +1838,12 @@ __global__ __launch_bounds__(256) void k_gen_head(GenHeadArgs a, long long t) {
 #pragma unroll
         for (int j = 0; j < SB; j++) {
             y[j] = y[j] + bym; // the logit z
+            if constexpr (CONSTRAIN)
+                if (banned[j]) y[j] = -INFINITY;
             ps[j][m] = y[j];
             any_max |= phase[j] == 2 && a.mode != 0;
             if constexpr (STABLE) any_max |= phase[j] == 1 || phase[j] == 2;
-            if constexpr (FILTER) any_filter |= phase[j] == 2 && a.mode != 2 && a.filter;
+            if constexpr (FILTER) any_filter |= phase[j] == 2 && a.mode != 2 && (CONSTRAIN || a.filter);
         }
         [[maybe_unused]] int rank[FILTER ? SB : 1]; // of this thread's logit: #{z_i > z_m} + #{i < m: z_i == z_m}, in 0..255
         if constexpr (FILTER)
@@ -1898,6 +1914,10 @@ __global__ __launch_bounds__(256) void k_gen_head(GenHeadArgs a, long long t) {
                     long long lo;
                     if (gen_phase<FILTER>(a, s0 + jo, t, &lo) == 2) {
                         int keep = a.keep_k;
+                        if constexpr (CONSTRAIN) {
+                            const int allowed = a.ccount[a.cstate[s0 + jo]];
+                            if (allowed < keep) keep = allowed;
+                        }
                         if (a.nucleus) {
                             float sum = 0.0f;
                             for (int r = 0; r < keep; r++) { // (past keep_k the nucleus no longer matters)
@@ -1940,7 +1960,7 @@ __global__ __launch_bounds__(256) void k_gen_head(GenHeadArgs a, long long t) {
         if (a.mode == 2) {
             x = s_arg[j];
             kept = 1;
-        } else if (FILTER && a.filter) {
+        } else if (FILTER && (CONSTRAIN || a.filter)) {
             kept = s_keep[j];
             const float r = (float)a.u[i * a.streams + s];
             float sum = 0.0f; // of the kept terms, in index order
@@ -1965,6 +1985,12 @@ __global__ __launch_bounds__(256) void k_gen_head(GenHeadArgs a, long long t) {
                     break;
                 }
             }
+        }
+        if constexpr (CONSTRAIN) { // advance the automaton; a forbidden byte gives way to the state's lowest allowed one
+            const uint16_t *row = a.ctab + (size_t)a.cstate[s] * 256;
+            if (row[x] == 0xFFFF)
+                for (x = 0; x < 255 && row[x] == 0xFFFF; x++) {}
+            if (row[x] != 0xFFFF) a.cstate[s] = row[x]; // (an empty row cannot be reached: the state never leaves the table)
         }
         a.out[i * a.streams + s] = (uint8_t)x;
         if constexpr (FILTER) {
@@ -1996,11 +2022,11 @@ template <bool STABLE> static void gen_head_launch(const GenHeadArgs &a, long lo
         hipLaunchKernelGGL((k_gen_head<SB, STABLE, false>), grid, dim3(256), lds, st, a, t);                               \
         break;
     // FILTER: static LDS is up to 33 KB (ps, sorted), dynamic up to 64 KB; a refused request is an error, not a launch
-#define GEN_HEAD_FILTER_CASE(SB)                                                                                            \
+#define GEN_HEAD_FILTER_CASE(SB, CONSTRAIN)                                                                                 \
     case SB: {                                                                                                              \
         static size_t granted = 32768;                                                                                      \
         if (lds > granted) {                                                                                                \
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_gen_head<SB, STABLE, true>),          \
+            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_gen_head<SB, STABLE, true, CONSTRAIN>), \
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                 \
             if (e != hipSuccess) {                                                                                          \
                 g_gen_head_error = e;                                                                                       \
@@ -2008,15 +2034,22 @@ template <bool STABLE> static void gen_head_launch(const GenHeadArgs &a, long lo
             }                                                                                                               \
             granted = lds;                                                                                                  \
         }                                                                                                                   \
-        hipLaunchKernelGGL((k_gen_head<SB, STABLE, true>), grid, dim3(256), lds, st, a, t);                                 \
+        hipLaunchKernelGGL((k_gen_head<SB, STABLE, true, CONSTRAIN>), grid, dim3(256), lds, st, a, t);                      \
         break;                                                                                                              \
     }
-    if (a.end) switch (sb) {
-            GEN_HEAD_FILTER_CASE(1)
-            GEN_HEAD_FILTER_CASE(2)
-            GEN_HEAD_FILTER_CASE(4)
-            GEN_HEAD_FILTER_CASE(8)
-            GEN_HEAD_FILTER_CASE(16)
+    if (a.ctab) switch (sb) { // (the caller sets a.end too)
+            GEN_HEAD_FILTER_CASE(1, true)
+            GEN_HEAD_FILTER_CASE(2, true)
+            GEN_HEAD_FILTER_CASE(4, true)
+            GEN_HEAD_FILTER_CASE(8, true)
+            GEN_HEAD_FILTER_CASE(16, true)
+        }
+    else if (a.end) switch (sb) {
+            GEN_HEAD_FILTER_CASE(1, false)
+            GEN_HEAD_FILTER_CASE(2, false)
+            GEN_HEAD_FILTER_CASE(4, false)
+            GEN_HEAD_FILTER_CASE(8, false)
+            GEN_HEAD_FILTER_CASE(16, false)
         }
     else switch (sb) {
             GEN_HEAD_CASE(1)

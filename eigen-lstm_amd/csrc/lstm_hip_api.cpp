@@ -1479,6 +1479,9 @@ static int reserve_gen_scratch(lstm_hip_t *h, size_t bytes) {
 // read or written except P; everything else lives in one scratch allocation kept on the handle (gen_scratch).
 // Sampling controls: a filter, a stop byte or a request for `kept` selects gen_head's FILTER
 // instantiation (a.end set); without them the launches are those of lstm_hip_generate before the controls existed.
+// Constraint: a byte automaton selects gen_head's CONSTRAIN instantiation (a.ctab set).  The table is
+// validated and every stream's state walked over its prompt here, on the host, before anything is launched; the table, the
+// allowed counts and the states then live in the same scratch allocation.  Without one the call is lstm_hip_generate_ex's.
 int lstm_hip_generate(lstm_hip_t *h, int32_t streams, const uint8_t *prompts, const uint64_t *prompt_off, const float *h0,
                       const float *c0, double temperature, const double *u, int32_t count, uint8_t *out, double *bits,
                       float *h_out, float *c_out) {
@@ -1489,6 +1492,68 @@ int lstm_hip_generate(lstm_hip_t *h, int32_t streams, const uint8_t *prompts, co
 int lstm_hip_generate_ex(lstm_hip_t *h, int32_t streams, const uint8_t *prompts, const uint64_t *prompt_off, const float *h0,
                          const float *c0, const lstm_hip_sampling *opt, const double *u, int32_t count, uint8_t *out,
                          double *bits, float *h_out, float *c_out, int32_t *out_len, uint16_t *kept) {
+    return lstm_hip_generate_constrained(h, streams, prompts, prompt_off, h0, c0, opt, u, count, out, bits, h_out, c_out, out_len,
+                                         kept, nullptr, nullptr, nullptr);
+}
+
+// the well-formed-UTF-8 automaton (include/lstm_hip.h): state 0 is the character boundary, 1..2 await one / two more
+// continuation bytes, 3..4 follow E0 / ED, 5 awaits three, 6..7 follow F0 / F4
+int32_t lstm_hip_dfa_utf8(uint16_t *next) {
+    if (!next) return 8;
+    std::fill(next, next + 8 * 256, (uint16_t)0xFFFF);
+    auto range = [&](int q, int lo, int hi, int to) {
+        for (int b = lo; b <= hi; b++) next[q * 256 + b] = (uint16_t)to;
+    };
+    range(0, 0x00, 0x7F, 0);
+    range(0, 0xC2, 0xDF, 1);
+    range(0, 0xE0, 0xE0, 3);
+    range(0, 0xE1, 0xEC, 2);
+    range(0, 0xED, 0xED, 4);
+    range(0, 0xEE, 0xEF, 2);
+    range(0, 0xF0, 0xF0, 6);
+    range(0, 0xF1, 0xF3, 5);
+    range(0, 0xF4, 0xF4, 7);
+    range(1, 0x80, 0xBF, 0);
+    range(2, 0x80, 0xBF, 1);
+    range(3, 0xA0, 0xBF, 1);
+    range(4, 0x80, 0x9F, 1);
+    range(5, 0x80, 0xBF, 2);
+    range(6, 0x90, 0xBF, 2);
+    range(7, 0x80, 0x8F, 2);
+    return 8;
+}
+
+int lstm_hip_dfa_restrict(uint16_t *next, int32_t states, const uint8_t allow[256]) {
+    if (!next || !allow) return fail(LSTM_HIP_EINVAL, "dfa_restrict: null table or allow list");
+    if (states < 1 || states > 4096) return fail(LSTM_HIP_EINVAL, "dfa_restrict: states must be in [1, 4096] (got %d)", states);
+    for (size_t e = 0; e < (size_t)states * 256; e++)
+        if (next[e] != 0xFFFF && next[e] >= states)
+            return fail(LSTM_HIP_EINVAL, "dfa_restrict: entry next[%zu][%zu] = %u is neither a state below %d nor 0xFFFF", e / 256,
+                        e % 256, (unsigned)next[e], states);
+    for (int q = 0; q < states; q++)
+        for (int b = 0; b < 256; b++)
+            if (!allow[b]) next[(size_t)q * 256 + b] = 0xFFFF;
+    std::vector<char> empty(states);
+    for (bool changed = true; changed;) { // forbid what leads into a state with no allowed byte, until nothing changes
+        changed = false;
+        for (int q = 0; q < states; q++) {
+            const uint16_t *row = next + (size_t)q * 256;
+            empty[q] = std::all_of(row, row + 256, [](uint16_t v) { return v == 0xFFFF; });
+        }
+        for (size_t e = 0; e < (size_t)states * 256; e++)
+            if (next[e] != 0xFFFF && empty[next[e]]) {
+                next[e] = 0xFFFF;
+                changed = true;
+            }
+    }
+    if (empty[0]) return fail(LSTM_HIP_EINVAL, "dfa_restrict: state 0 has no allowed byte left");
+    return 0;
+}
+
+int lstm_hip_generate_constrained(lstm_hip_t *h, int32_t streams, const uint8_t *prompts, const uint64_t *prompt_off,
+                                  const float *h0, const float *c0, const lstm_hip_sampling *opt, const double *u, int32_t count,
+                                  uint8_t *out, double *bits, float *h_out, float *c_out, int32_t *out_len, uint16_t *kept,
+                                  const lstm_hip_constraint *con, const int32_t *start_state, int32_t *end_state) {
     CHECK(h);
     if (!opt) return fail(LSTM_HIP_EINVAL, "generate: null sampling options");
     if (opt->size != sizeof(lstm_hip_sampling))
@@ -1518,11 +1583,64 @@ int lstm_hip_generate_ex(lstm_hip_t *h, int32_t streams, const uint8_t *prompts,
     }
     const int N = h->cfg.N, Nl = h->N_log;
     if (N > 16384) return fail(LSTM_HIP_EINVAL, "generate: hidden width %d above 16384", N);
+    // the constraint: the table is checked, then every stream's state walks its prompt
+    std::vector<int32_t> cstate; // [streams] the state after each prompt
+    std::vector<uint16_t> ccount; // [states] allowed bytes
+    const int Q = con ? con->states : 0;
+    if (!con && (start_state || end_state)) return fail(LSTM_HIP_EINVAL, "generate: start_state / end_state given without a constraint");
+    if (con) {
+        if (con->size != sizeof(lstm_hip_constraint))
+            return fail(LSTM_HIP_EINVAL, "generate: constraint of %u bytes, expected %zu", con->size, sizeof(lstm_hip_constraint));
+        if (Q < 1 || Q > 4096) return fail(LSTM_HIP_EINVAL, "generate: constraint states must be in [1, 4096] (got %d)", Q);
+        if (!con->next) return fail(LSTM_HIP_EINVAL, "generate: constraint with a null table");
+        ccount.assign(Q, 0);
+        for (int q = 0; q < Q; q++)
+            for (int b = 0; b < 256; b++) {
+                const uint16_t v = con->next[(size_t)q * 256 + b];
+                if (v != 0xFFFF && v >= Q)
+                    return fail(LSTM_HIP_EINVAL, "generate: constraint entry next[%d][%d] = %u is neither a state below %d nor 0xFFFF",
+                                q, b, (unsigned)v, Q);
+                ccount[q] += v != 0xFFFF;
+            }
+        cstate.assign(streams, 0);
+        std::vector<char> seen(Q, 0);
+        std::vector<int32_t> queue; // breadth-first from the start states
+        for (int s = 0; s < streams; s++) {
+            if (start_state) cstate[s] = start_state[s];
+            if (cstate[s] < 0 || cstate[s] >= Q)
+                return fail(LSTM_HIP_EINVAL, "generate: start_state[%d] = %d is outside [0, %d)", s, cstate[s], Q);
+            if (!seen[cstate[s]]) {
+                seen[cstate[s]] = 1;
+                queue.push_back(cstate[s]);
+            }
+        }
+        for (size_t i = 0; i < queue.size(); i++) {
+            const int q = queue[i];
+            if (ccount[q] == 0)
+                return fail(LSTM_HIP_EINVAL, "generate: constraint state %d can be reached and has no allowed byte", q);
+            for (int b = 0; b < 256; b++) {
+                const uint16_t v = con->next[(size_t)q * 256 + b];
+                if (v != 0xFFFF && !seen[v]) {
+                    seen[v] = 1;
+                    queue.push_back(v);
+                }
+            }
+        }
+        if (prompt_off)
+            for (int s = 0; s < streams; s++)
+                for (uint64_t j = prompt_off[s]; j < prompt_off[s + 1]; j++) {
+                    const uint16_t v = con->next[(size_t)cstate[s] * 256 + prompts[j]];
+                    if (v == 0xFFFF)
+                        return fail(LSTM_HIP_EINVAL, "generate: stream %d: prompt byte 0x%02x at offset %llu is forbidden in state %d", s,
+                                    (unsigned)prompts[j], (unsigned long long)(j - prompt_off[s]), cstate[s]);
+                    cstate[s] = v;
+                }
+    }
     const uint64_t total = prompt_off ? prompt_off[streams] : 0;
     const size_t n = (size_t)N * streams, nl = (size_t)Nl * streams, nd = (size_t)count * streams;
     const bool keep = h_out || c_out;
     const bool top_k_on = opt->top_k >= 1 && opt->top_k <= 255, nucleus = opt->top_p < 1.0;
-    const bool controls = top_k_on || nucleus || opt->stop_byte >= 0 || kept; // gen_head's FILTER instantiation
+    const bool controls = top_k_on || nucleus || opt->stop_byte >= 0 || kept || con; // gen_head's FILTER instantiation
 
     // one scratch allocation, 256-byte aligned pieces
     size_t bytes = 0;
@@ -1537,7 +1655,8 @@ int lstm_hip_generate_ex(lstm_hip_t *h, int32_t streams, const uint8_t *prompts,
                  o_off = piece(prompt_off ? sizeof(uint64_t) * (streams + 1) : 0), o_p = piece(total),
                  o_u = piece(count > 0 && temperature >= (double)FLT_MIN ? sizeof(double) * nd : 0), o_out = piece(nd),
                  o_bits = piece(sizeof(double) * streams), o_end = piece(controls ? sizeof(int32_t) * streams : 0),
-                 o_kept = piece(kept ? sizeof(uint16_t) * nd : 0);
+                 o_kept = piece(kept ? sizeof(uint16_t) * nd : 0), o_tab = piece(sizeof(uint16_t) * 256 * (size_t)Q),
+                 o_cnt = piece(sizeof(uint16_t) * Q), o_q = piece(con ? sizeof(int32_t) * streams : 0);
     if (int rc = reserve_gen_scratch(h, bytes)) return rc;
     char *base = h->gen_scratch;
     float4 *Ufwd = reinterpret_cast<float4 *>(base + o_U);
@@ -1552,6 +1671,9 @@ int lstm_hip_generate_ex(lstm_hip_t *h, int32_t streams, const uint8_t *prompts,
     double *d_bits = reinterpret_cast<double *>(base + o_bits);
     int32_t *d_end = controls ? reinterpret_cast<int32_t *>(base + o_end) : nullptr;
     uint16_t *d_kept = kept ? reinterpret_cast<uint16_t *>(base + o_kept) : nullptr;
+    uint16_t *d_tab = con ? reinterpret_cast<uint16_t *>(base + o_tab) : nullptr;
+    uint16_t *d_cnt = con ? reinterpret_cast<uint16_t *>(base + o_cnt) : nullptr;
+    int32_t *d_q = con ? reinterpret_cast<int32_t *>(base + o_q) : nullptr;
 
     // start state (padding rows zero), inputs
     const PadMap map = pad_map_rows(1, Nl, N, streams);
@@ -1573,6 +1695,11 @@ int lstm_hip_generate_ex(lstm_hip_t *h, int32_t streams, const uint8_t *prompts,
     if (d_end) HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_end), count, streams, h->st));
     if (d_kept && nd) HIP_TRY(hipMemsetAsync(d_kept, 0, sizeof(uint16_t) * nd, h->st)); // 0 wherever a stream has stopped
     if (opt->stop_byte >= 0 && nd) HIP_TRY(hipMemsetAsync(d_out, 0, nd, h->st));
+    if (con) {
+        HIP_TRY(hipMemcpyAsync(d_tab, con->next, sizeof(uint16_t) * 256 * (size_t)Q, hipMemcpyHostToDevice, h->st));
+        HIP_TRY(hipMemcpyAsync(d_cnt, ccount.data(), sizeof(uint16_t) * Q, hipMemcpyHostToDevice, h->st));
+        HIP_TRY(hipMemcpyAsync(d_q, cstate.data(), sizeof(int32_t) * streams, hipMemcpyHostToDevice, h->st));
+    }
     RUN(K_PACK_U, pack_U(h->P + h->pl.U, Ufwd, nullptr, N, h->st));
 
     GenHeadArgs a{};
@@ -1600,6 +1727,9 @@ int lstm_hip_generate_ex(lstm_hip_t *h, int32_t streams, const uint8_t *prompts,
     a.stop_byte = opt->stop_byte;
     a.end = d_end;
     a.kept = d_kept;
+    a.ctab = d_tab;
+    a.ccount = d_cnt;
+    a.cstate = d_q;
     const bool fast = (h->cfg.flags & LSTM_HIP_FAST_MATH) != 0, stable = (h->cfg.flags & LSTM_HIP_STABLE_SOFTMAX) != 0;
     const long long steps = (long long)max_len + count; // inputs of the longest stream
     int cur = 0;
@@ -1623,6 +1753,7 @@ int lstm_hip_generate_ex(lstm_hip_t *h, int32_t streams, const uint8_t *prompts,
         else std::fill(out_len, out_len + streams, count);
     }
     if (kept && nd) HIP_TRY(hipMemcpyAsync(kept, d_kept, sizeof(uint16_t) * nd, hipMemcpyDeviceToHost, h->st));
+    if (end_state) HIP_TRY(hipMemcpyAsync(end_state, d_q, sizeof(int32_t) * streams, hipMemcpyDeviceToHost, h->st));
     for (int k = 0; k < 2; k++) {
         float *dst = k ? c_out : h_out;
         if (!dst) continue;

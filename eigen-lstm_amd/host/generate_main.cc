@@ -3,7 +3,8 @@
 // over many streams at once.  No HIP, no torch here.
 //
 //   lstm_generate --load PREFIX [--score FILE ...] [--count C --streams K --prime TEXT|--prime-file F
-//                 --temperature T --top-k K --top-p P --stop-byte B --seed S | --beams W --nbest K --length-alpha A]
+//                 --temperature T --top-k K --top-p P --stop-byte B --seed S --utf8 --allow SPEC --ban SPEC
+//                 | --beams W --nbest K --length-alpha A]
 //                 [--fast-math] [--stable-softmax] [--device D]
 //
 // --load reads the five-file text checkpoint PREFIX_{W,U,Why,b,by}.txt (checkpoint.h); N is the rows of W / 4.
@@ -14,6 +15,11 @@
 // --temperature 0 is greedy decoding and takes no draws.  --top-k K (1..255) draws among the K most likely bytes, --top-p P
 // (0 < P < 1) among the smallest most-likely-first set of mass P, and with --stop-byte B (decimal, 0..255; 10 is a newline)
 // a sample ends with its first drawn byte B: it is printed up to and including that byte (lstm_hip_generate_ex).
+// --utf8 draws well-formed UTF-8 only (lstm_hip_generate_constrained under the table of lstm_hip_dfa_utf8; the prompt must be
+// well-formed too) and prints a sample without an incomplete final character.  --allow SPEC draws only the listed bytes, --ban
+// SPEC never the listed ones; SPEC is comma-separated bytes and ranges, decimal or 0x hex (0x20-0x7e,10).  With --utf8 they
+// restrict its table (lstm_hip_dfa_restrict: a lead byte goes with its last continuation byte); without it the table has one
+// state.  None of the three goes with --beams or --score.
 // --beams W (1..32) searches instead of drawing (lstm_hip_beam_search): per stream the W most likely continuations of C bytes
 // the beam search finds, of which the --nbest K (default 1) best are printed under "== sample s hypothesis k: X bits ==",
 // ranked by their bits, or with --length-alpha A > 0 by bits / length^A.  It takes --prime, --count, --streams and
@@ -38,11 +44,15 @@ namespace {
 const char *const kUsage =
     "usage: lstm_generate --load PREFIX [--score FILE ...] [--count C --streams K --prime TEXT|--prime-file F\n"
     "                     --temperature T --top-k K --top-p P --stop-byte B --seed S\n"
+    "                     --utf8 --allow SPEC --ban SPEC\n"
     "                     | --beams W --nbest K --length-alpha A]\n"
     "                     [--fast-math] [--stable-softmax] [--device D]\n"
     "  --top-k K      draw among the K most likely bytes (1..255; 0 or 256: all)\n"
     "  --top-p P      draw among the smallest most-likely-first set of bytes whose mass reaches P (0 < P <= 1)\n"
     "  --stop-byte B  end a sample with its first drawn byte B (decimal, 0..255) and print it up to that byte\n"
+    "  --utf8         draw well-formed UTF-8 only; a sample is printed without an incomplete final character\n"
+    "  --allow SPEC   draw only these bytes: comma-separated bytes and ranges, decimal or 0x hex (0x20-0x7e,10)\n"
+    "  --ban SPEC     never draw these bytes (same SPEC); with --utf8 both restrict the UTF-8 table\n"
     "  --beams W      beam search with W hypotheses per stream (1..32) instead of drawing; W x --streams <= 4096\n"
     "  --nbest K      print the K best hypotheses of every stream (1..W, default 1) with their bits\n"
     "  --length-alpha A  rank hypotheses by bits / length^A (default 0: by bits)\n";
@@ -86,6 +96,31 @@ double parse_double(const std::string &opt, const std::string &v) {
     return x;
 }
 
+// SPEC: comma-separated bytes and ranges lo-hi, decimal or 0x hex; sets flag[b] = 1 for every listed byte
+void parse_spec(const std::string &opt, const std::string &v, uint8_t flag[256]) {
+    auto bad = [&]() { usage(opt + " needs bytes and ranges such as 0x20-0x7e,10 (each in [0, 255]), got '" + v + "'"); };
+    auto number = [&](const std::string &t) -> long {
+        const bool hex = t.size() > 2 && t[0] == '0' && (t[1] == 'x' || t[1] == 'X');
+        const std::string digits = hex ? t.substr(2) : t;
+        if (digits.empty() || digits.size() > 3 ||
+            digits.find_first_not_of(hex ? "0123456789abcdefABCDEF" : "0123456789") != std::string::npos)
+            bad();
+        const long x = strtol(digits.c_str(), nullptr, hex ? 16 : 10);
+        if (x > 255) bad();
+        return x;
+    };
+    if (v.empty()) bad();
+    for (size_t at = 0; at <= v.size();) {
+        const size_t comma = std::min(v.find(',', at), v.size());
+        const std::string item = v.substr(at, comma - at);
+        const size_t dash = item.find('-');
+        const long lo = number(item.substr(0, dash)), hi = dash == std::string::npos ? lo : number(item.substr(dash + 1));
+        if (hi < lo) bad();
+        for (long b = lo; b <= hi; b++) flag[b] = 1;
+        at = comma + 1;
+    }
+}
+
 struct Options {
     std::string load, prime, prime_file;
     bool has_prime = false;
@@ -97,8 +132,13 @@ struct Options {
     long beams = 0, nbest = 1; // beams 0: draw
     double length_alpha = 0.0;
     std::vector<std::string> draw_opts, beam_opts; // options that only mean something without / with --beams
+    std::vector<std::string> constraint_opts;      // --utf8, --allow, --ban as given
     uint32_t seed = 1;
     unsigned flags = 0;
+    bool utf8 = false, has_allow = false, has_ban = false;
+    uint8_t allow[256] = {}, ban[256] = {};
+    std::vector<uint16_t> table; // the constraint of --utf8 / --allow / --ban (empty: none), `states` rows of 256
+    int32_t states = 0;
 };
 
 Options parse(int argc, char **argv) {
@@ -145,6 +185,18 @@ Options parse(int argc, char **argv) {
             o.seed = (uint32_t)parse_int(a, val(), 0, 0xFFFFFFFFL);
             o.sampling_opts.push_back(a);
             o.draw_opts.push_back(a);
+        } else if (a == "--utf8" || a == "--allow" || a == "--ban") {
+            if (a == "--utf8") o.utf8 = true;
+            else if (a == "--allow") {
+                parse_spec(a, val(), o.allow);
+                o.has_allow = true;
+            } else {
+                parse_spec(a, val(), o.ban);
+                o.has_ban = true;
+            }
+            o.sampling_opts.push_back(a);
+            o.draw_opts.push_back(a);
+            o.constraint_opts.push_back(a);
         } else if (a == "--beams") {
             o.beams = parse_int(a, val(), 1, 32);
             o.sampling_opts.push_back(a);
@@ -176,6 +228,16 @@ Options parse(int argc, char **argv) {
         if (o.nbest > o.beams) usage("--nbest cannot pass --beams");
         if (o.beams * o.streams > 4096) usage("--beams x --streams must be at most 4096");
         if ((long long)std::max(o.count, 0L) * o.streams * o.beams > (1LL << 31) - 1) usage("--count x --streams x --beams is too large");
+    }
+    if (!o.constraint_opts.empty()) {
+        if (!o.score.empty()) usage(o.constraint_opts[0] + " does not go with --score: scoring ignores a constraint");
+        o.states = o.utf8 ? lstm_hip_dfa_utf8(nullptr) : 1;
+        o.table.assign((size_t)o.states * 256, 0); // one state: every byte leads back to it
+        if (o.utf8) lstm_hip_dfa_utf8(o.table.data());
+        uint8_t allow[256];
+        for (int b = 0; b < 256; b++) allow[b] = (!o.has_allow || o.allow[b]) && !o.ban[b];
+        if (lstm_hip_dfa_restrict(o.table.data(), o.states, allow) != 0)
+            usage(std::string("--allow / --ban leave nothing to draw: ") + lstm_hip_last_error());
     }
     return o;
 }
@@ -274,12 +336,30 @@ int main(int argc, char **argv) {
         std::vector<uint8_t> out((size_t)C * K);
         const lstm_hip_sampling opt{(uint32_t)sizeof(lstm_hip_sampling), o.temperature, (int32_t)o.top_k, o.top_p, (int32_t)o.stop_byte};
         std::vector<int32_t> out_len(K);
-        CK(lstm_hip_generate_ex(h, K, prompts.data(), off.data(), nullptr, nullptr, &opt, u.empty() ? nullptr : u.data(), C,
-                                out.data(), nullptr, nullptr, nullptr, out_len.data(), nullptr));
+        std::vector<int32_t> end_state(K, 0);
+        if (o.table.empty())
+            CK(lstm_hip_generate_ex(h, K, prompts.data(), off.data(), nullptr, nullptr, &opt, u.empty() ? nullptr : u.data(), C,
+                                    out.data(), nullptr, nullptr, nullptr, out_len.data(), nullptr));
+        else {
+            const lstm_hip_constraint con{(uint32_t)sizeof(lstm_hip_constraint), o.states, o.table.data()};
+            CK(lstm_hip_generate_constrained(h, K, prompts.data(), off.data(), nullptr, nullptr, &opt, u.empty() ? nullptr : u.data(),
+                                             C, out.data(), nullptr, nullptr, nullptr, out_len.data(), nullptr, &con, nullptr,
+                                             end_state.data()));
+        }
         for (int s = 0; s < K; s++) {
             printf("== sample %d ==\n", s);
-            fwrite(prime.data(), 1, prime.size(), stdout);
-            for (int i = 0; i < out_len[s]; i++) fputc(out[(size_t)i * K + s], stdout);
+            std::vector<uint8_t> text(prime);
+            for (int i = 0; i < out_len[s]; i++) text.push_back(out[(size_t)i * K + s]);
+            size_t n = text.size();
+            if (o.utf8 && end_state[s] != 0) { // cut back to the last character boundary (state 0 of the table)
+                int32_t q = 0;
+                n = 0;
+                for (size_t i = 0; i < text.size(); i++) {
+                    q = o.table[(size_t)q * 256 + text[i]];
+                    if (q == 0) n = i + 1;
+                }
+            }
+            fwrite(text.data(), 1, n, stdout);
             fputc('\n', stdout);
         }
     }

@@ -43,6 +43,10 @@ class _Sampling(C.Structure):  # lstm_hip_sampling
                 ("stop_byte", C.c_int32)]
 
 
+class _Constraint(C.Structure):  # lstm_hip_constraint
+    _fields_ = [("size", C.c_uint32), ("states", C.c_int32), ("next", C.POINTER(C.c_uint16))]
+
+
 class _Beam(C.Structure):  # lstm_hip_beam
     _fields_ = [("size", C.c_uint32), ("beams", C.c_int32), ("stop_byte", C.c_int32)]
 
@@ -67,7 +71,8 @@ SYMBOLS = [
     "lstm_hip_set_grad_clip", "lstm_hip_get_grad_norms", "lstm_hip_set_optimizer", "lstm_hip_get_optimizer_steps",
     "lstm_hip_set_optimizer_steps", "lstm_hip_coder_version", "lstm_hip_code_bound", "lstm_hip_encode", "lstm_hip_decode",
     "lstm_hip_adaptive_version", "lstm_hip_adaptive_blocks", "lstm_hip_encode_adaptive", "lstm_hip_decode_adaptive",
-    "lstm_hip_plan_identity", "lstm_hip_beam_search",
+    "lstm_hip_plan_identity", "lstm_hip_beam_search", "lstm_hip_generate_constrained", "lstm_hip_dfa_utf8",
+    "lstm_hip_dfa_restrict",
 ]
 
 
@@ -123,6 +128,28 @@ def adaptive_blocks(S, B, text_off):
     if n < 0:
         _chk(n)
     return n
+
+
+def dfa_utf8():
+    """lstm_hip_dfa_utf8: the automaton of well-formed UTF-8 as an (8, 256) uint16 table for Lstm.generate(constraint=...).
+    Entry [q, b] is the state after byte b in state q, 0xFFFF where b is forbidden; state 0 is the start state and the
+    only character boundary.  Needs no device."""
+    lib = load_library()
+    lib.lstm_hip_dfa_utf8.restype = C.c_int32
+    table = np.zeros((int(lib.lstm_hip_dfa_utf8(None)), 256), np.uint16)
+    lib.lstm_hip_dfa_utf8(_ptr(table, C.c_uint16))
+    return table
+
+
+def dfa_restrict(table, allow):
+    """lstm_hip_dfa_restrict: a copy of `table` ((states, 256) uint16) that forbids every byte b with allow[b] == 0 (allow:
+    256 flags) and, repeatedly, every transition into a state left with no allowed byte.  State numbers do not change.
+    Raises LstmHipError when state 0 ends up empty.  Needs no device."""
+    table = np.array(table, dtype=np.uint16, order="C")
+    assert table.ndim == 2 and table.shape[1] == 256, table.shape
+    flags = np.ascontiguousarray(np.asarray(allow).reshape(256) != 0, dtype=np.uint8)
+    _chk(load_library().lstm_hip_dfa_restrict(_ptr(table, C.c_uint16), C.c_int32(table.shape[0]), _ptr(flags, C.c_uint8)))
+    return table
 
 
 def _bytes_list(texts):
@@ -357,7 +384,7 @@ class Lstm:
         return out, h0, c0
 
     def generate(self, prompts=None, count=0, u=None, temperature=1.0, h0=None, c0=None, streams=None, score=False,
-                 top_k=0, top_p=1.0, stop_byte=None, info=False):
+                 top_k=0, top_p=1.0, stop_byte=None, info=False, constraint=None, start_state=None):
         """lstm_hip_generate: `streams` independent streams, each fed its prompt (bytes or a uint8 array) and then `count`
         drawn bytes.  u: draws [count, streams] (may be None only at temperature 0); h0, c0: [streams, N] or None (zeros).
         Returns (out [count, streams] uint8, bits [streams] float64 -- the prompts' summed -log2 p, or None unless
@@ -365,7 +392,11 @@ class Lstm:
         top_k (1..255), top_p (< 1) and stop_byte (0..255) are the sampling controls of lstm_hip_generate_ex: keep the k
         most likely bytes, the smallest most-likely-first prefix of mass top_p, and end a stream with its first drawn
         stop_byte (out is 0 behind it, h / c are the state after it).  info=True adds a fifth element
-        {"out_len": int32 [streams], "kept": uint16 [count, streams]}: bytes each stream produced, bytes kept per draw."""
+        {"out_len": int32 [streams], "kept": uint16 [count, streams]}: bytes each stream produced, bytes kept per draw.
+        constraint: a (states, 256) uint16 table (dfa_utf8(), dfa_restrict(), or the caller's own: the state after byte b in
+        state q, 0xFFFF where b is forbidden) for lstm_hip_generate_constrained: every stream draws only bytes its state
+        allows, from start_state [streams] (None: 0) advanced over its prompt; info then also has "end_state": int32
+        [streams].  With constraint=None the calls are those made without the argument."""
         if streams is None:
             streams = len(prompts) if prompts is not None else (np.asarray(h0).shape[0] if h0 is not None else
                                                                 (np.asarray(u).reshape(count, -1).shape[1] if u is not None and count > 0 else 1))
@@ -391,13 +422,25 @@ class Lstm:
                 _ptr(hh) if hh is not None else None, _ptr(cc) if cc is not None else None)
         tail = (_ptr(uu, C.c_double) if uu is not None else None, C.c_int32(count), _ptr(out, C.c_uint8),
                 _ptr(bits, C.c_double) if score else None, _ptr(h), _ptr(c))
-        if top_k == 0 and top_p == 1.0 and stop_byte is None and not info:
+        if constraint is None and start_state is not None:
+            raise LstmHipError("generate: start_state given without a constraint")
+        if constraint is None and top_k == 0 and top_p == 1.0 and stop_byte is None and not info:
             _chk(self.lib.lstm_hip_generate(*args, C.c_double(temperature), *tail))
             return out, bits, h, c
         opt = _Sampling(C.sizeof(_Sampling), float(temperature), int(top_k), float(top_p),
                         -1 if stop_byte is None else int(stop_byte))
         out_len = np.zeros(streams, np.int32)
         kept = np.zeros((count, streams), np.uint16)
+        if constraint is not None:
+            table = np.ascontiguousarray(constraint, dtype=np.uint16)
+            assert table.ndim == 2 and table.shape[1] == 256, table.shape
+            con = _Constraint(C.sizeof(_Constraint), table.shape[0], _ptr(table, C.c_uint16))
+            q0 = None if start_state is None else np.ascontiguousarray(start_state, dtype=np.int32).reshape(streams)
+            q1 = np.zeros(streams, np.int32)
+            _chk(self.lib.lstm_hip_generate_constrained(
+                *args, C.byref(opt), *tail, _ptr(out_len, C.c_int32), _ptr(kept, C.c_uint16) if info else None, C.byref(con),
+                _ptr(q0, C.c_int32) if q0 is not None else None, _ptr(q1, C.c_int32)))
+            return (out, bits, h, c, {"out_len": out_len, "kept": kept, "end_state": q1}) if info else (out, bits, h, c)
         _chk(self.lib.lstm_hip_generate_ex(*args, C.byref(opt), *tail, _ptr(out_len, C.c_int32),
                                            _ptr(kept, C.c_uint16) if info else None))
         return (out, bits, h, c, {"out_len": out_len, "kept": kept}) if info else (out, bits, h, c)

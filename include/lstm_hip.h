@@ -293,6 +293,57 @@ int lstm_hip_generate_ex(lstm_hip_t *h, int32_t streams, const uint8_t *prompts,
                          const float *h0, const float *c0, const lstm_hip_sampling *opt, const double *u, int32_t count,
                          uint8_t *out, double *bits, float *h_out, float *c_out,
                          int32_t *out_len /* [streams], may be NULL */, uint16_t *kept /* [count*streams], may be NULL */);
+/* ---- the same call under a constraint: a byte-level DFA decides, per stream, which bytes may come next (DESIGN.md section
+ *      3.10).  Everything lstm_hip_generate_ex documents holds, and it is a thin caller of this function with con = NULL,
+ *      start_state = end_state = NULL: that call makes the launches it made before this function existed.
+ *        table   con->next[q*256 + b], con->states = Q states (1..4096): the state after byte b in state q (a value < Q), or
+ *                0xFFFF: byte b is forbidden in state q.  A_q is the number of allowed bytes of state q.  There are no
+ *                accepting states: the caller reads the final state.
+ *        prompt  q starts at start_state[s] (NULL: 0) and is advanced over the stream's prompt bytes on the host, before
+ *                anything is launched; a prompt byte that is forbidden where it stands is LSTM_HIP_EINVAL (the message names
+ *                the stream and the byte's offset in its prompt).  Prompt scoring (bits) ignores the constraint: it stays the
+ *                text's evaluation bits.
+ *        draw    z'_m = z_m where next[q][m] is allowed, -inf otherwise.  Rules 1-6 above run on z' (and on p formed from z':
+ *                max, expf and the normalising sum see the masked logits), with keep = min(keep_k, keep_p, A_q), and a
+ *                constrained draw is ALWAYS a filtered draw, also with top_k and top_p off: its terms are divided by the
+ *                index-order float sum of the kept terms, and if u passes every edge the byte is the largest kept index.
+ *                Greedy draws take the argmax of z', lowest index on ties.  kept = keep (<= A_q), 1 for a greedy draw.
+ *        advance q <- next[q][x].  Should x be forbidden where it stands (possible only with non-finite parameters or an
+ *                overflowing expf), the byte written and fed is the lowest allowed byte of q instead: out is always accepted
+ *                by the table and q never leaves it.
+ *        stop    as above; a stop byte that is forbidden never comes.
+ *        final   end_state[s] (may be NULL) = q after the stream's last drawn byte, the state after its prompt if it drew
+ *                none.  A second call with h0 / c0 = h_out / c_out, no prompt, start_state = end_state and the remaining
+ *                draws gives the bytes and states of the one long call, bit for bit.
+ *      LSTM_HIP_EINVAL (the handle stays usable, the message says which), beside lstm_hip_generate_ex's: start_state or
+ *      end_state given with con NULL; con->size != sizeof(lstm_hip_constraint); states outside 1..4096; next NULL; an entry
+ *      that is neither < states nor 0xFFFF; a start state outside 0..states-1; a state that can be reached from some stream's
+ *      start state and has no allowed byte (breadth-first from the start states: unreachable rows may be empty); a prompt
+ *      byte the table rejects.  Beam search, the coders and lstm_hip_sample take no constraint. */
+typedef struct lstm_hip_constraint {
+    uint32_t size;        /* sizeof(lstm_hip_constraint); anything else: LSTM_HIP_EINVAL */
+    int32_t  states;      /* Q: 1..4096 */
+    const uint16_t *next; /* [Q*256]: next state, or 0xFFFF = forbidden */
+} lstm_hip_constraint;
+int lstm_hip_generate_constrained(lstm_hip_t *h, int32_t streams, const uint8_t *prompts, const uint64_t *prompt_off,
+                                  const float *h0, const float *c0, const lstm_hip_sampling *opt, const double *u, int32_t count,
+                                  uint8_t *out, double *bits, float *h_out, float *c_out, int32_t *out_len, uint16_t *kept,
+                                  const lstm_hip_constraint *con, const int32_t *start_state /* [streams], may be NULL: all 0 */,
+                                  int32_t *end_state /* [streams], may be NULL */);
+/* Two tables for it; neither needs a device or a handle.
+ * lstm_hip_dfa_utf8 returns 8 and, if next is not NULL, fills 8*256 entries with the automaton of well-formed UTF-8 (no
+ * overlong forms, no surrogates, nothing above U+10FFFF).  The numbering is part of the contract; state 0 is the start state and
+ * the only character boundary, so a stream whose end_state is 0 ended on a whole character.
+ *      state 0: 00-7F -> 0, C2-DF -> 1, E0 -> 3, E1-EC -> 2, ED -> 4, EE-EF -> 2, F0 -> 6, F1-F3 -> 5, F4 -> 7
+ *      state 1: 80-BF -> 0      state 2: 80-BF -> 1      state 3: A0-BF -> 1      state 4: 80-9F -> 1
+ *      state 5: 80-BF -> 2      state 6: 90-BF -> 2      state 7: 80-8F -> 2      everything else is forbidden
+ * (allowed bytes per state: 179, 64, 64, 32, 32, 64, 48, 16.)
+ * lstm_hip_dfa_restrict forbids every transition on a byte b with allow[b] == 0 in a table of `states` states, then
+ * repeatedly forbids the transitions into states that have no allowed byte left, until nothing changes.  State numbers do not
+ * change.  Returns 0, or LSTM_HIP_EINVAL when state 0 ends up with no allowed byte (or the table is not one: NULL, states
+ * outside 1..4096, an entry that is neither a state nor 0xFFFF). */
+int32_t lstm_hip_dfa_utf8(uint16_t *next);
+int lstm_hip_dfa_restrict(uint16_t *next, int32_t states, const uint8_t allow[256]);
 /* ---- beam search: per stream the W = opt->beams most likely continuations of its prompt that the
  *      search finds, with their costs in bits.  Prompts, prompt_off, h0 / c0 (N x streams; NULL = zeros) are those of
  *      lstm_hip_generate.  Stream s is fed its prompt of length L (nothing is scored during the prompt) and makes selection
