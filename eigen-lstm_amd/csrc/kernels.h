@@ -164,6 +164,25 @@ size_t bwd_partial_floats(int N);
 // C[M x Nn] = op(A)[M x K] * op(B)[K x Nn], column-major; TA: A is stored K x M; TB: B is stored Nn x K.  (TA && TB is
 // not a product of the window and is refused.)  splits > 1 writes partial slabs into `slabs` (each M*Nn floats, ld = M)
 // and gemm_fold sums them into C in slab order (deterministic).  `slabs` must hold splits*M*Nn floats.
+//
+// Contract (nothing below is checked at run time; tests/product_cases.py contract_violations() is this list as code, and
+// tests/test_products_cpu.py holds every product do_forward / do_backward issue against it).  An operand is "k fast" when the
+// contraction index is its contiguous one -- A when TA, B when !TB -- and "k slow" otherwise.
+//   forms     (TA, TB) = (0, 1) k slow x k slow (dU, dWhy), (0, 0) k slow x k fast (Y), (1, 0) k fast x k fast (DHy).
+//             (1, 1) does not exist: gemm launches nothing, gemm_slabs / gemm_regs return -1.
+//   K         any K >= 1 when both operands are k slow (the K % 8 tail is a predicated group); K % 8 == 0 as soon as one
+//             operand is k fast (a tail would be dropped silently).  splits: any value; fewer slabs may be used, K is cut in
+//             multiples of 8 (the count is gemm_slabs' return value, and gemm_pick_splits' values are returned unchanged).
+//   k-slow A  a lane loads and STORES four consecutive rows (two with the small tile) as one vector and clamps the last
+//             vector to row M - 4: M % 4 == 0, M >= 4, lda % 4 == 0, lda >= M, A 16-byte aligned; and for C: ldc % 4 == 0,
+//             C 16-byte aligned.  (Rows M - M % 4 .. M - 1 of another M would never be stored.)
+//   k-slow B  two consecutive rows per lane, the last pair clamped to row Nn - 2: Nn % 2 == 0, Nn >= 2, ldb % 2 == 0,
+//             ldb >= Nn, B 8-byte aligned.
+//   k-fast    16-byte loads of four consecutive k, rows clamped to the last one: any row count >= 1 (M for A, Nn for B),
+//             ld % 4 == 0, ld >= K, base 16-byte aligned.  A k-fast A stores C one float at a time: any ldc >= M, any C.
+//   C         ldc >= M; rows M .. ldc-1 of a column are never written.  slabs: 16-byte aligned, M*Nn floats each, ld = M.
+//   sizes     lane and k-group offsets are 32-bit: (K - 1) * ld + rows (k slow) or (rows - 1) * ld + K (k fast) < 2^32.
+//   reads     only the elements the layout spans: k < K and rows < M / Nn of every line, never the rest of a line of ld.
 void gemm(bool TA, bool TB, int M, int Nn, int K, const float *A, int lda, const float *B, int ldb, float *C, int ldc,
           int splits, float *slabs, hipStream_t st);
 // how many slabs the shape rule wants (1: no slabs); a static function of the shape and the device's compute-unit count
