@@ -433,6 +433,30 @@ struct CodeHeadArgs {
 };
 void code_head(const CodeHeadArgs &a, long long t, hipStream_t st);
 
+// ---- per-byte scores (lstm_hip_score): per step score_head on the state after t inputs (byte t of
+// every stream with more than t bytes is scored, byte 0 only when `first`), then fwd_step over all streams with x_next.
+// Per-position arrays are indexed like text (entry off[s] + j for byte j of stream s) and zeroed by the caller: the entries of
+// unscored bytes are never written.  A null output is not computed; rank, top_byte or top_bits select the DETAIL
+// instantiation, ctab the CONSTRAIN one.
+struct ScoreHeadArgs {
+    const float *Why, *by;
+    const float *H, *C;         // state after t inputs, [streams][N]
+    const uint8_t *text;        // concatenated texts
+    const uint64_t *off;        // streams + 1 text offsets
+    float *surprisal, *entropy; // [total]
+    uint8_t *rank;              // [total]
+    uint8_t *top_byte;          // [total][top_n]
+    float *top_bits;            // [total][top_n]
+    double *bits;               // [streams] sum of the stream's surprisals, accumulated in text order
+    int32_t *x_next;            // the next input of every stream (-1: none)
+    float *h_out, *c_out;       // the state after each stream's last byte (null: not kept)
+    const uint16_t *ctab;       // [states][256] the byte automaton (GenHeadArgs::ctab), or null
+    const uint16_t *qpos;       // [total] the automaton state each byte stands in (walked by the host); with ctab
+    int N, streams, first, top_n;
+};
+void score_head(const ScoreHeadArgs &a, long long t, bool stable, hipStream_t st); // stable: LSTM_HIP_STABLE_SOFTMAX
+int score_head_status();        // 0, or the HIP error of a refused LDS request (sticky until read)
+
 // ---- adaptive coding (lstm_hip_encode_adaptive / lstm_hip_decode_adaptive): the training window of
 // block k, built from the coder's device text buffer.  With L = S - 1 and e_j = byte j of a stream (empty for j < 0), row t of
 // the window holds target e_{kL+t-1} and input e_{kL+t-2}: what slide_window leaves after k + 1 slides of stride L from an

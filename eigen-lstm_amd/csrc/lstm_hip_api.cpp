@@ -55,12 +55,14 @@ enum KernelId {
     K_BLOCK_WINDOW,            // adaptive coding: a block's training window, carry and bit fold (one launch per block)
     K_BEAM_HEAD,               // one step of beam search (lstm_hip_beam_search): logits, selection, reordered states
     K_BEAM_BACKTRACK,          // ... and the walk through its tables, once per call
+    K_SCORE_HEAD,              // one step of lstm_hip_score: logits, surprisal, entropy, rank and alternatives of every stream
     K_COUNT
 };
 const char *const kKernelNames[K_COUNT] = {
     "pack_U", "fwd_step", "gemm_Y", "softmax_loss_dy", "loss_reduce", "gemm_DHy", "bwd_step", "gemm_dWhy", "gemm_dU",
     "dW_db", "loss_dby", "adagrad", "slide", "allreduce", "fwd_persistent", "bwd_persistent", "gen_head", "side_sums",
-    "gemm_dU_halves", "grad_sumsq", "grad_norm", "adam", "code_head", "block_window", "beam_head", "beam_backtrack"};
+    "gemm_dU_halves", "grad_sumsq", "grad_norm", "adam", "code_head", "block_window", "beam_head", "beam_backtrack",
+    "score_head"};
 
 // ---- RCCL, loaded on first use so single-GPU users never touch it --------------------------
 struct UniqueId {
@@ -1550,6 +1552,51 @@ int lstm_hip_dfa_restrict(uint16_t *next, int32_t states, const uint8_t allow[25
     return 0;
 }
 
+// the table checks of a byte automaton (include/lstm_hip.h, lstm_hip_generate_constrained): on success ccount holds the allowed
+// bytes of every state and cstate every stream's start state
+static int check_constraint(const char *what, const lstm_hip_constraint *con, int32_t streams, const int32_t *start_state,
+                            std::vector<int32_t> &cstate, std::vector<uint16_t> &ccount) {
+    const int Q = con->states;
+    if (con->size != sizeof(lstm_hip_constraint))
+        return fail(LSTM_HIP_EINVAL, "%s: constraint of %u bytes, expected %zu", what, con->size, sizeof(lstm_hip_constraint));
+    if (Q < 1 || Q > 4096) return fail(LSTM_HIP_EINVAL, "%s: constraint states must be in [1, 4096] (got %d)", what, Q);
+    if (!con->next) return fail(LSTM_HIP_EINVAL, "%s: constraint with a null table", what);
+    ccount.assign(Q, 0);
+    for (int q = 0; q < Q; q++)
+        for (int b = 0; b < 256; b++) {
+            const uint16_t v = con->next[(size_t)q * 256 + b];
+            if (v != 0xFFFF && v >= Q)
+                return fail(LSTM_HIP_EINVAL, "%s: constraint entry next[%d][%d] = %u is neither a state below %d nor 0xFFFF", what,
+                            q, b, (unsigned)v, Q);
+            ccount[q] += v != 0xFFFF;
+        }
+    cstate.assign(streams, 0);
+    std::vector<char> seen(Q, 0);
+    std::vector<int32_t> queue; // breadth-first from the start states
+    for (int s = 0; s < streams; s++) {
+        if (start_state) cstate[s] = start_state[s];
+        if (cstate[s] < 0 || cstate[s] >= Q)
+            return fail(LSTM_HIP_EINVAL, "%s: start_state[%d] = %d is outside [0, %d)", what, s, cstate[s], Q);
+        if (!seen[cstate[s]]) {
+            seen[cstate[s]] = 1;
+            queue.push_back(cstate[s]);
+        }
+    }
+    for (size_t i = 0; i < queue.size(); i++) {
+        const int q = queue[i];
+        if (ccount[q] == 0)
+            return fail(LSTM_HIP_EINVAL, "%s: constraint state %d can be reached and has no allowed byte", what, q);
+        for (int b = 0; b < 256; b++) {
+            const uint16_t v = con->next[(size_t)q * 256 + b];
+            if (v != 0xFFFF && !seen[v]) {
+                seen[v] = 1;
+                queue.push_back(v);
+            }
+        }
+    }
+    return 0;
+}
+
 int lstm_hip_generate_constrained(lstm_hip_t *h, int32_t streams, const uint8_t *prompts, const uint64_t *prompt_off,
                                   const float *h0, const float *c0, const lstm_hip_sampling *opt, const double *u, int32_t count,
                                   uint8_t *out, double *bits, float *h_out, float *c_out, int32_t *out_len, uint16_t *kept,
@@ -1589,43 +1636,7 @@ int lstm_hip_generate_constrained(lstm_hip_t *h, int32_t streams, const uint8_t 
     const int Q = con ? con->states : 0;
     if (!con && (start_state || end_state)) return fail(LSTM_HIP_EINVAL, "generate: start_state / end_state given without a constraint");
     if (con) {
-        if (con->size != sizeof(lstm_hip_constraint))
-            return fail(LSTM_HIP_EINVAL, "generate: constraint of %u bytes, expected %zu", con->size, sizeof(lstm_hip_constraint));
-        if (Q < 1 || Q > 4096) return fail(LSTM_HIP_EINVAL, "generate: constraint states must be in [1, 4096] (got %d)", Q);
-        if (!con->next) return fail(LSTM_HIP_EINVAL, "generate: constraint with a null table");
-        ccount.assign(Q, 0);
-        for (int q = 0; q < Q; q++)
-            for (int b = 0; b < 256; b++) {
-                const uint16_t v = con->next[(size_t)q * 256 + b];
-                if (v != 0xFFFF && v >= Q)
-                    return fail(LSTM_HIP_EINVAL, "generate: constraint entry next[%d][%d] = %u is neither a state below %d nor 0xFFFF",
-                                q, b, (unsigned)v, Q);
-                ccount[q] += v != 0xFFFF;
-            }
-        cstate.assign(streams, 0);
-        std::vector<char> seen(Q, 0);
-        std::vector<int32_t> queue; // breadth-first from the start states
-        for (int s = 0; s < streams; s++) {
-            if (start_state) cstate[s] = start_state[s];
-            if (cstate[s] < 0 || cstate[s] >= Q)
-                return fail(LSTM_HIP_EINVAL, "generate: start_state[%d] = %d is outside [0, %d)", s, cstate[s], Q);
-            if (!seen[cstate[s]]) {
-                seen[cstate[s]] = 1;
-                queue.push_back(cstate[s]);
-            }
-        }
-        for (size_t i = 0; i < queue.size(); i++) {
-            const int q = queue[i];
-            if (ccount[q] == 0)
-                return fail(LSTM_HIP_EINVAL, "generate: constraint state %d can be reached and has no allowed byte", q);
-            for (int b = 0; b < 256; b++) {
-                const uint16_t v = con->next[(size_t)q * 256 + b];
-                if (v != 0xFFFF && !seen[v]) {
-                    seen[v] = 1;
-                    queue.push_back(v);
-                }
-            }
-        }
+        if (int rc = check_constraint("generate", con, streams, start_state, cstate, ccount)) return rc;
         if (prompt_off)
             for (int s = 0; s < streams; s++)
                 for (uint64_t j = prompt_off[s]; j < prompt_off[s + 1]; j++) {
@@ -1918,6 +1929,171 @@ int lstm_hip_beam_search(lstm_hip_t *h, int32_t streams, const uint8_t *prompts,
     if (trace_parent) HIP_TRY(hipMemcpyAsync(trace_parent, d_tp, nd, hipMemcpyDeviceToHost, h->st));
     if (trace_byte) HIP_TRY(hipMemcpyAsync(trace_byte, d_tb, nd, hipMemcpyDeviceToHost, h->st));
     HIP_TRY(hipStreamSynchronize(h->st));
+    return 0;
+}
+
+// Per-byte scores (include/lstm_hip.h): the generator's loop with score_head in gen_head's place.  Per
+// step one score_head launch (byte t of every stream: logits, surprisal, entropy, rank, alternatives, the next input, final
+// states) and one k_fwd_step; max length + 1 head launches, max length steps, no readback inside the loop.  A constraint is
+// checked and every stream's text walked through it here, on the host, before anything is launched: the state each byte stands
+// in is uploaded beside the text.  Only P of the handle is read; the working memory is gen_scratch.
+int lstm_hip_score(lstm_hip_t *h, int32_t streams, const uint8_t *text, const uint64_t *text_off, const float *h0, const float *c0,
+                   const lstm_hip_scoring *opt, const int32_t *start_state, const lstm_hip_scores *out, float *h_out,
+                   float *c_out) {
+    CHECK(h);
+    if (!opt) return fail(LSTM_HIP_EINVAL, "score: null options");
+    if (opt->size != sizeof(lstm_hip_scoring))
+        return fail(LSTM_HIP_EINVAL, "score: options of %u bytes, expected %zu", opt->size, sizeof(lstm_hip_scoring));
+    if (out && out->size != sizeof(lstm_hip_scores))
+        return fail(LSTM_HIP_EINVAL, "score: outputs of %u bytes, expected %zu", out->size, sizeof(lstm_hip_scores));
+    if (opt->first != 0 && opt->first != 1) return fail(LSTM_HIP_EINVAL, "score: first must be 0 or 1 (got %d)", opt->first);
+    const int top_n = opt->top_n;
+    if (top_n < 0 || top_n > 8) return fail(LSTM_HIP_EINVAL, "score: top_n must be in [0, 8] (got %d)", top_n);
+    lstm_hip_scores o{};
+    if (out) o = *out;
+    if (top_n == 0 && (o.top_byte || o.top_bits)) return fail(LSTM_HIP_EINVAL, "score: top_byte / top_bits given with top_n = 0");
+    const lstm_hip_constraint *con = opt->con;
+    if (!con && (start_state || o.end_state)) return fail(LSTM_HIP_EINVAL, "score: start_state / end_state given without a constraint");
+    if (streams < 1 || streams > 4096) return fail(LSTM_HIP_EINVAL, "score: streams must be in [1, 4096] (got %d)", streams);
+    if (int rc = check_offsets("score", "text_off", text_off, streams)) return rc;
+    const uint64_t total = text_off[streams];
+    if (total > 0 && !text) return fail(LSTM_HIP_EINVAL, "score: null text with %llu bytes to score", (unsigned long long)total);
+    uint64_t max_len = 0;
+    for (int s = 0; s < streams; s++) max_len = std::max<uint64_t>(max_len, text_off[s + 1] - text_off[s]);
+    const int N = h->cfg.N, Nl = h->N_log;
+    if (N > 16384) return fail(LSTM_HIP_EINVAL, "score: hidden width %d above 16384", N);
+    std::vector<int32_t> cstate;  // [streams] each stream's state: at its start, then after its text
+    std::vector<uint16_t> ccount; // (the allowed counts are checked, not used)
+    std::vector<uint16_t> qpos;   // [total] the state each byte stands in
+    const int Q = con ? con->states : 0;
+    if (con) {
+        if (int rc = check_constraint("score", con, streams, start_state, cstate, ccount)) return rc;
+        qpos.resize(total);
+        for (int s = 0; s < streams; s++)
+            for (uint64_t j = text_off[s]; j < text_off[s + 1]; j++) {
+                const uint16_t v = con->next[(size_t)cstate[s] * 256 + text[j]];
+                if (v == 0xFFFF)
+                    return fail(LSTM_HIP_EINVAL, "score: stream %d: byte 0x%02x at offset %llu is forbidden in state %d", s,
+                                (unsigned)text[j], (unsigned long long)(j - text_off[s]), cstate[s]);
+                qpos[j] = (uint16_t)cstate[s];
+                cstate[s] = v;
+            }
+    }
+    const size_t n = (size_t)N * streams, nl = (size_t)Nl * streams, tot = (size_t)total;
+    const bool keep = h_out || c_out;
+
+    // one scratch allocation, 256-byte aligned pieces
+    size_t bytes = 0;
+    auto piece = [&](size_t b) {
+        const size_t at = bytes;
+        bytes += (b + 255) / 256 * 256;
+        return at;
+    };
+    const size_t o_U = piece(sizeof(float) * 4 * (size_t)N * N), o_H = piece(sizeof(float) * 2 * n), o_C = piece(sizeof(float) * 2 * n),
+                 o_G = piece(sizeof(float) * 4 * n), o_ho = piece(keep ? sizeof(float) * 2 * n : 0),
+                 o_st = piece(h->padded() ? sizeof(float) * 2 * nl : 0), o_x = piece(sizeof(int32_t) * streams),
+                 o_off = piece(sizeof(uint64_t) * (streams + 1)), o_t = piece(tot), o_bits = piece(sizeof(double) * streams),
+                 o_sur = piece(o.surprisal ? sizeof(float) * tot : 0), o_ent = piece(o.entropy ? sizeof(float) * tot : 0),
+                 o_rank = piece(o.rank ? tot : 0), o_tby = piece(o.top_byte ? tot * top_n : 0),
+                 o_tbi = piece(o.top_bits ? sizeof(float) * tot * top_n : 0), o_tab = piece(sizeof(uint16_t) * 256 * (size_t)Q),
+                 o_q = piece(con ? sizeof(uint16_t) * tot : 0);
+    if (int rc = reserve_gen_scratch(h, bytes)) return rc;
+    char *base = h->gen_scratch;
+    float4 *Ufwd = reinterpret_cast<float4 *>(base + o_U);
+    float *H = reinterpret_cast<float *>(base + o_H), *Cs = reinterpret_cast<float *>(base + o_C);
+    float *G = reinterpret_cast<float *>(base + o_G), *stage = reinterpret_cast<float *>(base + o_st);
+    float *ho = keep ? reinterpret_cast<float *>(base + o_ho) : nullptr;
+    int32_t *xi = reinterpret_cast<int32_t *>(base + o_x);
+    uint64_t *d_off = reinterpret_cast<uint64_t *>(base + o_off);
+    uint8_t *d_text = reinterpret_cast<uint8_t *>(base + o_t);
+    double *d_bits = reinterpret_cast<double *>(base + o_bits);
+    float *d_sur = o.surprisal && tot ? reinterpret_cast<float *>(base + o_sur) : nullptr;
+    float *d_ent = o.entropy && tot ? reinterpret_cast<float *>(base + o_ent) : nullptr;
+    uint8_t *d_rank = o.rank && tot ? reinterpret_cast<uint8_t *>(base + o_rank) : nullptr;
+    uint8_t *d_tby = o.top_byte && tot ? reinterpret_cast<uint8_t *>(base + o_tby) : nullptr;
+    float *d_tbi = o.top_bits && tot ? reinterpret_cast<float *>(base + o_tbi) : nullptr;
+    uint16_t *d_tab = con ? reinterpret_cast<uint16_t *>(base + o_tab) : nullptr;
+    uint16_t *d_q = con ? reinterpret_cast<uint16_t *>(base + o_q) : nullptr;
+
+    // start state (padding rows zero), inputs, zeroed outputs (the entries of unscored bytes stay zero)
+    const PadMap map = pad_map_rows(1, Nl, N, streams);
+    for (int k = 0; k < 2; k++) {
+        const float *src = k ? c0 : h0;
+        float *dst = k ? Cs : H;
+        if (!src) HIP_TRY(hipMemsetAsync(dst, 0, sizeof(float) * n, h->st));
+        else if (h->padded()) {
+            HIP_TRY(hipMemcpyAsync(stage + k * nl, src, sizeof(float) * nl, hipMemcpyHostToDevice, h->st));
+            pad_copy(stage + k * nl, dst, map, true, h->st);
+            if (int rc = pad_status()) return rc;
+        } else
+            HIP_TRY(hipMemcpyAsync(dst, src, sizeof(float) * n, hipMemcpyHostToDevice, h->st));
+    }
+    HIP_TRY(hipMemcpyAsync(d_off, text_off, sizeof(uint64_t) * (streams + 1), hipMemcpyHostToDevice, h->st));
+    if (tot) HIP_TRY(hipMemcpyAsync(d_text, text, tot, hipMemcpyHostToDevice, h->st));
+    HIP_TRY(hipMemsetAsync(d_bits, 0, sizeof(double) * streams, h->st));
+    if (d_sur) HIP_TRY(hipMemsetAsync(d_sur, 0, sizeof(float) * tot, h->st));
+    if (d_ent) HIP_TRY(hipMemsetAsync(d_ent, 0, sizeof(float) * tot, h->st));
+    if (d_rank) HIP_TRY(hipMemsetAsync(d_rank, 0, tot, h->st));
+    if (d_tby) HIP_TRY(hipMemsetAsync(d_tby, 0, tot * top_n, h->st));
+    if (d_tbi) HIP_TRY(hipMemsetAsync(d_tbi, 0, sizeof(float) * tot * top_n, h->st));
+    if (con) {
+        HIP_TRY(hipMemcpyAsync(d_tab, con->next, sizeof(uint16_t) * 256 * (size_t)Q, hipMemcpyHostToDevice, h->st));
+        if (tot) HIP_TRY(hipMemcpyAsync(d_q, qpos.data(), sizeof(uint16_t) * tot, hipMemcpyHostToDevice, h->st));
+    }
+    RUN(K_PACK_U, pack_U(h->P + h->pl.U, Ufwd, nullptr, N, h->st));
+
+    ScoreHeadArgs a{};
+    a.Why = h->P + h->pl.Why;
+    a.by = h->P + h->pl.by;
+    a.text = d_text;
+    a.off = d_off;
+    a.surprisal = d_sur;
+    a.entropy = d_ent;
+    a.rank = d_rank;
+    a.top_byte = d_tby;
+    a.top_bits = d_tbi;
+    a.bits = o.bits ? d_bits : nullptr;
+    a.x_next = xi;
+    a.h_out = ho;
+    a.c_out = ho ? ho + n : nullptr;
+    a.ctab = d_tab;
+    a.qpos = d_q;
+    a.N = N;
+    a.streams = streams;
+    a.first = opt->first;
+    a.top_n = top_n;
+    const bool fast = (h->cfg.flags & LSTM_HIP_FAST_MATH) != 0, stable = (h->cfg.flags & LSTM_HIP_STABLE_SOFTMAX) != 0;
+    int cur = 0;
+    for (uint64_t t = 0;; t++) {
+        a.H = H + cur * n;
+        a.C = Cs + cur * n;
+        RUN(K_SCORE_HEAD, score_head(a, (long long)t, stable, h->st));
+        if (const int e = score_head_status())
+            return fail(LSTM_HIP_EHIP, "score: the LDS request of score_head was refused: %s", hipGetErrorString((hipError_t)e));
+        if (t == max_len) break;
+        RUN(K_FWD_STEP, fwd_step(Ufwd, h->P + h->pl.W, h->P + h->pl.b, H + cur * n, Cs + cur * n, H + (cur ^ 1) * n,
+                                 Cs + (cur ^ 1) * n, G, xi, N, streams, fast, h->st));
+        cur ^= 1;
+    }
+
+    if (d_sur) HIP_TRY(hipMemcpyAsync(o.surprisal, d_sur, sizeof(float) * tot, hipMemcpyDeviceToHost, h->st));
+    if (d_ent) HIP_TRY(hipMemcpyAsync(o.entropy, d_ent, sizeof(float) * tot, hipMemcpyDeviceToHost, h->st));
+    if (d_rank) HIP_TRY(hipMemcpyAsync(o.rank, d_rank, tot, hipMemcpyDeviceToHost, h->st));
+    if (d_tby) HIP_TRY(hipMemcpyAsync(o.top_byte, d_tby, tot * top_n, hipMemcpyDeviceToHost, h->st));
+    if (d_tbi) HIP_TRY(hipMemcpyAsync(o.top_bits, d_tbi, sizeof(float) * tot * top_n, hipMemcpyDeviceToHost, h->st));
+    if (o.bits) HIP_TRY(hipMemcpyAsync(o.bits, d_bits, sizeof(double) * streams, hipMemcpyDeviceToHost, h->st));
+    for (int k = 0; k < 2; k++) {
+        float *dst = k ? c_out : h_out;
+        if (!dst) continue;
+        if (h->padded()) {
+            pad_copy(ho + k * n, stage + k * nl, map, false, h->st);
+            if (int rc = pad_status()) return rc;
+            HIP_TRY(hipMemcpyAsync(dst, stage + k * nl, sizeof(float) * nl, hipMemcpyDeviceToHost, h->st));
+        } else
+            HIP_TRY(hipMemcpyAsync(dst, ho + k * n, sizeof(float) * n, hipMemcpyDeviceToHost, h->st));
+    }
+    HIP_TRY(hipStreamSynchronize(h->st));
+    if (o.end_state) std::copy(cstate.begin(), cstate.end(), o.end_state);
     return 0;
 }
 

@@ -2,7 +2,7 @@
 // (include/lstm_hip.h).  The reference's test() and sample() (OV/lstm_eigen_class_CUDA/lstm.cc:578-720, R/lstm.cc:293-356)
 // over many streams at once.  No HIP, no torch here.
 //
-//   lstm_generate --load PREFIX [--score FILE ...] [--count C --streams K --prime TEXT|--prime-file F
+//   lstm_generate --load PREFIX [--score FILE ...] [--score-bytes FILE [--top N]] [--count C --streams K --prime TEXT|--prime-file F
 //                 --temperature T --top-k K --top-p P --stop-byte B --seed S --utf8 --allow SPEC --ban SPEC
 //                 | --beams W --nbest K --length-alpha A]
 //                 [--fast-math] [--stable-softmax] [--device D]
@@ -10,6 +10,12 @@
 // --load reads the five-file text checkpoint PREFIX_{W,U,Why,b,by}.txt (checkpoint.h); N is the rows of W / 4.
 // --score runs every FILE as one stream from h = c = 0 and prints "FILE: X.XXXXX bits/char (n bytes)" per file (bits over
 // the n - 1 predicted bytes, as lstm_hip_eval_bits) and a total weighted by those bytes.
+// --score-bytes FILE prints one tab-separated row per byte of FILE (lstm_hip_score): its offset, the byte in hex, its surprisal
+// in bits, the entropy of the distribution it was scored under, its rank (0: the model's first guess), then with --top N
+// (1..8) the N most likely bytes at that place, each as hex byte and bits; after the rows the --score line of FILE.  The first
+// byte is an input only, as for --score, and its row holds zeros.  With --utf8 / --allow / --ban every byte is scored under
+// that table (forbidden bytes have no mass; a FILE the table rejects is refused) and the first byte is scored too, from
+// the zero state, so the closing line then divides by all n bytes.  It goes with neither --score nor --count.
 // --count prints K samples of C bytes, each continuing from the prompt (--prime / --prime-file, default none) from a zero
 // state; the draws come from SeededRng(S) (rng.h), byte i of stream s taking draw i*K + s, so a seed gives the same text.
 // --temperature 0 is greedy decoding and takes no draws.  --top-k K (1..255) draws among the K most likely bytes, --top-p P
@@ -42,11 +48,14 @@
 namespace {
 
 const char *const kUsage =
-    "usage: lstm_generate --load PREFIX [--score FILE ...] [--count C --streams K --prime TEXT|--prime-file F\n"
+    "usage: lstm_generate --load PREFIX [--score FILE ...] [--score-bytes FILE [--top N]]\n"
+    "                     [--count C --streams K --prime TEXT|--prime-file F\n"
     "                     --temperature T --top-k K --top-p P --stop-byte B --seed S\n"
     "                     --utf8 --allow SPEC --ban SPEC\n"
     "                     | --beams W --nbest K --length-alpha A]\n"
     "                     [--fast-math] [--stable-softmax] [--device D]\n"
+    "  --score-bytes FILE  one row per byte: offset, byte, surprisal, entropy, rank; then the --score line of FILE\n"
+    "  --top N        with --score-bytes: add the N most likely bytes of every place (1..8) with their bits\n"
     "  --top-k K      draw among the K most likely bytes (1..255; 0 or 256: all)\n"
     "  --top-p P      draw among the smallest most-likely-first set of bytes whose mass reaches P (0 < P <= 1)\n"
     "  --stop-byte B  end a sample with its first drawn byte B (decimal, 0..255) and print it up to that byte\n"
@@ -126,6 +135,8 @@ struct Options {
     bool has_prime = false;
     std::vector<std::string> sampling_opts; // options that only mean something with --count
     std::vector<std::string> score;
+    std::string score_bytes; // --score-bytes FILE
+    long top = -1;           // --top N (-1: not given)
     long count = -1, streams = 1, device = 0;
     double temperature = 1.0, top_p = 1.0;
     long top_k = 0, stop_byte = -1;
@@ -153,7 +164,9 @@ Options parse(int argc, char **argv) {
         else if (a == "--score") {
             o.score.push_back(val());
             while (i + 1 < argc && std::string(argv[i + 1]).rfind("--", 0) != 0) o.score.push_back(argv[++i]);
-        } else if (a == "--count") o.count = parse_int(a, val(), 0, 1L << 30);
+        } else if (a == "--score-bytes") o.score_bytes = val();
+        else if (a == "--top") o.top = parse_int(a, val(), 1, 8);
+        else if (a == "--count") o.count = parse_int(a, val(), 0, 1L << 30);
         else if (a == "--streams") {
             o.streams = parse_int(a, val(), 1, 4096);
             o.sampling_opts.push_back(a);
@@ -218,7 +231,14 @@ Options parse(int argc, char **argv) {
         } else usage("unknown argument " + a);
     }
     if (o.load.empty()) usage("--load PREFIX is required");
-    if (o.score.empty() && o.count < 0) usage("nothing to do: give --score and/or --count");
+    if (o.score.empty() && o.count < 0 && o.score_bytes.empty()) usage("nothing to do: give --score, --score-bytes and/or --count");
+    if (o.top >= 0 && o.score_bytes.empty()) usage("--top needs --score-bytes");
+    if (!o.score_bytes.empty()) { // a mode of its own; of the sampling options it takes the constraint's
+        if (o.count >= 0 || !o.score.empty()) usage("--score-bytes goes with neither --count nor --score");
+        for (const std::string &a : o.sampling_opts)
+            if (std::find(o.constraint_opts.begin(), o.constraint_opts.end(), a) == o.constraint_opts.end()) usage(a + " needs --count");
+        o.sampling_opts.clear();
+    }
     if (o.has_prime && !o.prime_file.empty()) usage("--prime and --prime-file exclude each other");
     if (o.count < 0 && !o.sampling_opts.empty()) usage(o.sampling_opts[0] + " needs --count");
     if ((long long)std::max(o.count, 0L) * o.streams > (1LL << 31) - 1) usage("--count x --streams is too large");
@@ -290,6 +310,29 @@ int main(int argc, char **argv) {
             }
         }
         printf("total: %.5f bits/char (%.0f bytes scored in %zu files)\n", sum_bits / sum_chars, sum_chars, texts.size());
+    }
+
+    if (!o.score_bytes.empty()) { // one stream from h = c = 0
+        std::vector<uint8_t> text;
+        if (!read_file(o.score_bytes, text)) die("cannot read " + o.score_bytes);
+        if (text.size() < 2) die(o.score_bytes + ": need at least 2 bytes to score");
+        const size_t n = text.size(), top = o.top > 0 ? (size_t)o.top : 0;
+        const bool constrained = !o.table.empty();
+        const uint64_t off[2] = {0, n};
+        std::vector<float> surprisal(n), entropy(n), top_bits(n * top);
+        std::vector<uint8_t> rank(n), top_byte(n * top);
+        double bits = 0.0;
+        const lstm_hip_constraint con{(uint32_t)sizeof(lstm_hip_constraint), o.states, o.table.data()};
+        const lstm_hip_scoring opt{(uint32_t)sizeof(lstm_hip_scoring), constrained ? 1 : 0, (int32_t)top, constrained ? &con : nullptr};
+        const lstm_hip_scores out{(uint32_t)sizeof(lstm_hip_scores), surprisal.data(), entropy.data(), rank.data(),
+                                  top ? top_byte.data() : nullptr, top ? top_bits.data() : nullptr, &bits, nullptr};
+        CK(lstm_hip_score(h, 1, text.data(), off, nullptr, nullptr, &opt, nullptr, &out, nullptr, nullptr));
+        for (size_t j = 0; j < n; j++) {
+            printf("%zu\t%02x\t%.5f\t%.5f\t%d", j, (unsigned)text[j], surprisal[j], entropy[j], (int)rank[j]);
+            for (size_t r = 0; r < top; r++) printf("\t%02x\t%.5f", (unsigned)top_byte[j * top + r], top_bits[j * top + r]);
+            fputc('\n', stdout);
+        }
+        printf("%s: %.5f bits/char (%zu bytes)\n", o.score_bytes.c_str(), bits / (double)(constrained ? n : n - 1), n);
     }
 
     if (o.count >= 0 && o.beams > 0) {

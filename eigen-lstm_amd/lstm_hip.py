@@ -51,6 +51,16 @@ class _Beam(C.Structure):  # lstm_hip_beam
     _fields_ = [("size", C.c_uint32), ("beams", C.c_int32), ("stop_byte", C.c_int32)]
 
 
+class _Scoring(C.Structure):  # lstm_hip_scoring
+    _fields_ = [("size", C.c_uint32), ("first", C.c_int32), ("top_n", C.c_int32), ("con", C.POINTER(_Constraint))]
+
+
+class _Scores(C.Structure):  # lstm_hip_scores
+    _fields_ = [("size", C.c_uint32), ("surprisal", C.POINTER(C.c_float)), ("entropy", C.POINTER(C.c_float)),
+                ("rank", C.POINTER(C.c_uint8)), ("top_byte", C.POINTER(C.c_uint8)), ("top_bits", C.POINTER(C.c_float)),
+                ("bits", C.POINTER(C.c_double)), ("end_state", C.POINTER(C.c_int32))]
+
+
 class _Config(C.Structure):
     _fields_ = [("N", C.c_int32), ("M", C.c_int32), ("S", C.c_int32), ("B", C.c_int32), ("device", C.c_int32),
                 ("flags", C.c_uint32)]
@@ -72,7 +82,7 @@ SYMBOLS = [
     "lstm_hip_set_optimizer_steps", "lstm_hip_coder_version", "lstm_hip_code_bound", "lstm_hip_encode", "lstm_hip_decode",
     "lstm_hip_adaptive_version", "lstm_hip_adaptive_blocks", "lstm_hip_encode_adaptive", "lstm_hip_decode_adaptive",
     "lstm_hip_plan_identity", "lstm_hip_beam_search", "lstm_hip_generate_constrained", "lstm_hip_dfa_utf8",
-    "lstm_hip_dfa_restrict",
+    "lstm_hip_dfa_restrict", "lstm_hip_score",
 ]
 
 
@@ -444,6 +454,46 @@ class Lstm:
         _chk(self.lib.lstm_hip_generate_ex(*args, C.byref(opt), *tail, _ptr(out_len, C.c_int32),
                                            _ptr(kept, C.c_uint16) if info else None))
         return (out, bits, h, c, {"out_len": out_len, "kept": kept}) if info else (out, bits, h, c)
+
+    def score(self, texts, h0=None, c0=None, first=False, top_n=0, constraint=None, start_state=None):
+        """lstm_hip_score: what the model thinks of every byte of `texts` (bytes or uint8 arrays, one stream each; h0, c0:
+        [streams, N] or None for zeros).  Byte j is scored on the state after bytes 0..j-1; byte 0 only with first=True
+        (its entries are 0 otherwise).  Returns a dict: "surprisal", "entropy" (float32 [len]), "rank" (uint8 [len]),
+        "top_byte" (uint8 [len, top_n]) and "top_bits" (float32 [len, top_n]) are lists with one array per text; "bits"
+        float64 [streams], each stream's summed surprisal (with first=False and no constraint: generate(score=True)'s bits);
+        "h", "c" [streams, N], the state after each text's last byte; "end_state" int32 [streams] under a constraint, else
+        None.  constraint / start_state as in generate: forbidden bytes are masked out of the distribution every byte is
+        scored under, and a text the table rejects is refused.  A long text scored in pieces, each later piece with
+        first=True, h0 / c0 = the h / c and start_state = the end_state before it, gives the entries of the one call."""
+        parts = _bytes_list(texts)
+        streams, top_n = len(parts), int(top_n)
+        data, off = _offsets(parts)
+        total = int(off[-1])
+        hh = None if h0 is None else _f32(h0).reshape(streams, self.N)
+        cc = None if c0 is None else _f32(c0).reshape(streams, self.N)
+        sur, ent = np.zeros(max(total, 1), np.float32), np.zeros(max(total, 1), np.float32)
+        rank = np.zeros(max(total, 1), np.uint8)
+        tby, tbi = np.zeros((max(total, 1), top_n), np.uint8), np.zeros((max(total, 1), top_n), np.float32)
+        bits = np.zeros(streams, np.float64)
+        h, c = np.empty((streams, self.N), np.float32), np.empty((streams, self.N), np.float32)
+        if constraint is None and start_state is not None:
+            raise LstmHipError("score: start_state given without a constraint")
+        con = table = q0 = q1 = None
+        if constraint is not None:
+            table = np.ascontiguousarray(constraint, dtype=np.uint16)
+            assert table.ndim == 2 and table.shape[1] == 256, table.shape
+            con = _Constraint(C.sizeof(_Constraint), table.shape[0], _ptr(table, C.c_uint16))
+            q0 = None if start_state is None else np.ascontiguousarray(start_state, dtype=np.int32).reshape(streams)
+            q1 = np.zeros(streams, np.int32)
+        opt = _Scoring(C.sizeof(_Scoring), int(bool(first)), top_n, C.pointer(con) if con is not None else None)
+        out = _Scores(C.sizeof(_Scores), _ptr(sur), _ptr(ent), _ptr(rank, C.c_uint8), _ptr(tby, C.c_uint8) if top_n else None,
+                      _ptr(tbi) if top_n else None, _ptr(bits, C.c_double), _ptr(q1, C.c_int32) if q1 is not None else None)
+        _chk(self.lib.lstm_hip_score(self._h, C.c_int32(streams), _ptr(data, C.c_uint8), _ptr(off, C.c_uint64),
+                                     _ptr(hh) if hh is not None else None, _ptr(cc) if cc is not None else None, C.byref(opt),
+                                     _ptr(q0, C.c_int32) if q0 is not None else None, C.byref(out), _ptr(h), _ptr(c)))
+        cut = lambda a: [a[int(off[s]):int(off[s + 1])] for s in range(streams)]
+        return {"surprisal": cut(sur), "entropy": cut(ent), "rank": cut(rank), "top_byte": cut(tby), "top_bits": cut(tbi),
+                "bits": bits, "h": h, "c": c, "end_state": q1}
 
     def beam_search(self, prompts=None, count=0, beams=4, stop_byte=-1, h0=None, c0=None, streams=None, length_alpha=0.0,
                     trace=False):

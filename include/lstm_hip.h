@@ -387,6 +387,57 @@ int lstm_hip_beam_search(lstm_hip_t *h, int32_t streams, const uint8_t *prompts,
                          double  *bits     /* [streams*W] */,
                          uint8_t *trace_parent /* [count][streams*W], may be NULL */,
                          uint8_t *trace_byte   /* [count][streams*W], may be NULL */);
+/* ---- per-byte scores: what the model thinks of every byte of given texts.  Stream s is
+ *      text[text_off[s] .. text_off[s+1]), 1 <= streams <= 4096; empty streams are allowed (no entries, h_out = the start
+ *      state).  h0 / c0 / h_out / c_out are N x streams as in lstm_hip_generate (NULL = zeros / not wanted); h_out is the
+ *      state after the stream's last byte.  Per-position outputs are indexed like text: byte j of stream s is entry
+ *      text_off[s] + j; an unscored byte (j = 0 with first = 0) has all-zero entries.
+ *        rule       byte j, value x, is scored on the state after inputs 0..j-1 (the start state for j = 0).
+ *                   z = Why*h + by summed as lstm_hip_generate sums it.  With con: z_m = -inf where next[q][m] is forbidden, q
+ *                   the state byte j stands in (start_state[s] advanced over bytes 0..j-1); everything below sees the mask.
+ *                   Without LSTM_HIP_STABLE_SOFTMAX: e_m = expf(z_m), s = the sequential float sum of e in index order,
+ *                   p_m = e_m / s, surprisal(b) = -log2f(p_b).  With it: e_m = expf(z_m - max z), s and p as before,
+ *                   surprisal(b) = log2f(s) + (max z - z_b) * 1.44269504088896341f.
+ *        surprisal  surprisal(x).  bits[s] adds (double)surprisal in text order: with first = 0 and no constraint these are the
+ *                   additions of lstm_hip_generate's prompt bits, so the two agree bit for bit.
+ *        entropy    -(sequential float sum in index order of p_m * log2f(p_m), a term being 0 where p_m is not above 0).
+ *        rank       #{i : z_i > z_x} + #{i < x : z_i == z_x}: rule 1 of lstm_hip_generate_ex; 0 = the model's first guess.
+ *        top        top_byte[.. * top_n + r] is the byte of rank r < top_n, top_bits its surprisal.  Under a constraint the
+ *                   ranks from A_q on are the forbidden bytes in index order, with +inf bits.
+ *        chaining   a text scored in pieces -- every call after the first with first = 1, h0 / c0 = the h_out / c_out and
+ *                   start_state = the end_state of the call before -- gives the entries of the one long call, bit for bit.
+ *        end_state  the state after the stream's last byte (start_state[s] for an empty stream).
+ *      Without LSTM_HIP_STABLE_SOFTMAX expf may overflow: the float outputs of that position are then unspecified, ranks and
+ *      bytes are still in 0..255 and nothing faults.  Only the fp32 parameters are read (a bf16 handle scores as an fp32 one;
+ *      LSTM_HIP_FAST_MATH applies to the recurrence only); gradients, optimizer state, window, cursors and carry are untouched.
+ *      The loop runs max length + 1 head launches and max length recurrence steps, with no readback inside it.
+ *      LSTM_HIP_EINVAL (the handle stays usable): opt NULL, opt->size or out->size wrong, first not 0 or 1, top_n outside 0..8,
+ *      top_byte or top_bits given with top_n = 0, start_state or end_state given with con NULL, streams outside 1..4096,
+ *      offsets missing, not starting at 0 or decreasing, text NULL with bytes to score, the table refusals of
+ *      lstm_hip_generate_constrained, a byte its table rejects (the message names the stream and the offset).
+ *      LSTM_HIP_EHIP: the device refused the kernel's LDS request. */
+typedef struct lstm_hip_scoring {
+    uint32_t size;      /* sizeof(lstm_hip_scoring); anything else: LSTM_HIP_EINVAL */
+    int32_t  first;     /* 0: byte 0 of a stream is an input only (as the prompt bits of lstm_hip_generate);
+                           1: it is scored too, from the stream's start state */
+    int32_t  top_n;     /* 0..8: alternatives recorded per scored byte */
+    const lstm_hip_constraint *con;  /* may be NULL */
+} lstm_hip_scoring;
+typedef struct lstm_hip_scores {     /* outputs; every pointer may be NULL.  total = text_off[streams] */
+    uint32_t size;      /* sizeof(lstm_hip_scores); anything else: LSTM_HIP_EINVAL */
+    float   *surprisal;  /* [total]          bits of the byte that stands at that position of `text` */
+    float   *entropy;    /* [total]          bits, of the distribution that byte was scored under */
+    uint8_t *rank;       /* [total]          0 = the byte was the model's first guess */
+    uint8_t *top_byte;   /* [total * top_n]  the bytes of rank 0..top_n-1 */
+    float   *top_bits;   /* [total * top_n]  their surprisals */
+    double  *bits;       /* [streams]        sum of the stream's surprisals */
+    int32_t *end_state;  /* [streams]        only with con */
+} lstm_hip_scores;
+int lstm_hip_score(lstm_hip_t *h, int32_t streams, const uint8_t *text, const uint64_t *text_off, const float *h0,
+                   const float *c0, const lstm_hip_scoring *opt,
+                   const int32_t *start_state /* [streams], may be NULL: all 0; only with con */,
+                   const lstm_hip_scores *out /* may be NULL: nothing but h_out / c_out is wanted */, float *h_out,
+                   float *c_out);
 
 /* ---- arithmetic coding of bytes with the model.  Stream s is text[text_off[s] .. text_off[s+1]),
  *      1 <= streams <= 4096, each coded on its own from h = c = 0 (empty streams allowed: their code is empty).
