@@ -397,6 +397,13 @@ struct BeamHeadArgs {
     uint8_t *trace_parent, *trace_byte; // per selection and slot: the slot it extends, the byte (0 for a finished parent)
     int N, streams, W, count;
     int stop_byte;              // -1: none
+    // byte automaton (lstm_hip_beam_search_constrained): read only by the CONSTRAIN instantiation,
+    // which beam_head takes when `ctab` is set; all null / 0 in the unconstrained call
+    const uint16_t *ctab;       // [states][256] the state after byte b in state q, 0xFFFF: b is forbidden there
+    int32_t *cstate;            // per slot: its state, read at the start of a selection and rewritten in place at its end
+    const uint8_t *accept;      // [states] nonzero: a hypothesis may end there (null: everywhere, and no deadline)
+    const uint32_t *frows;      // [count][fwords] bit q of row R: an accepted end can be reached from q with R more bytes
+    int fwords;                 // words of one row: (states + 31) / 32
 };
 void beam_head(const BeamHeadArgs &a, long long t, hipStream_t st);
 int beam_head_status();         // 0, or the HIP error of a refused LDS request (sticky until read)

@@ -2082,6 +2082,15 @@ void gen_head(const GenHeadArgs &a, long long t, bool stable, hipStream_t st) {
 // LDS; the winner's thread retires it.  There are always at least W candidates, so every round finds one.  New slot r
 // is round r's winner: tables, cost, length, finished flag and next input are written by thread r.
 // WP: W rounded up to a power of two (register arrays); EXACT: W == WP, so that the LDS stride is a constant.
+// CONSTRAIN (lstm_hip_beam_search_constrained): the instantiation with CONSTRAIN = false is the code
+// above and nothing else.  With it every slot carries a state q of the byte automaton a.ctab (s_q, read into LDS with the
+// costs).  Thread m reads next[q_j][m] of every live slot j (one table row per slot, 2-byte coalesced loads) and keeps two
+// masks, a bit per slot: `allowed` (the entry is not 0xFFFF) and `exists` (allowed, and with a.accept the deadline: at
+// selection i the byte must lead to a state from which an accepted end is count - i - 1 bytes away -- bit next of row
+// count - i - 1 of a.frows --, the stop byte into an accepting state).  z is set to -inf where the byte is not allowed, before
+// the max and before expf, so a forbidden term adds 0.0f to the sum: cost, zmax and sum are the scorer's under the same
+// table.  Only candidates that exist are offered.  Thread r writes the new slot's state: its parent's if that was finished,
+// else next[q_p][b].
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ bool beam_before(double c1, int i1, float z1, double c2, int i2, float z2) { // idx = parent * 256 + byte
     if (c1 != c2) return c1 < c2;
@@ -2089,13 +2098,14 @@ __device__ __forceinline__ bool beam_before(double c1, int i1, float z1, double 
     if (z1 != z2) return z1 > z2;
     return (i1 & 255) < (i2 & 255);
 }
-template <int WP, bool EXACT>
+template <int WP, bool EXACT, bool CONSTRAIN = false>
 __global__ __launch_bounds__(256) void k_beam_head(BeamHeadArgs a, long long t) {
     extern __shared__ __attribute__((aligned(16))) float hs[]; // [N][W]
     __shared__ float ps[WP][256];
     __shared__ double s_cost[WP], sel_cost[WP], w_cost[4];
     __shared__ float s_zmax[WP], s_sum[WP], w_z[4];
     __shared__ int s_len[WP], s_fin[WP], sel_idx[WP], w_idx[4];
+    __shared__ int s_q[CONSTRAIN ? WP : 1];
     const int m = threadIdx.x, N = a.N, s = blockIdx.x, W = EXACT ? WP : a.W;
     const size_t c0 = (size_t)s * W, SW = (size_t)a.streams * W;
     const long long len = a.off ? (long long)(a.off[s + 1] - a.off[s]) : 0;
@@ -2109,12 +2119,27 @@ __global__ __launch_bounds__(256) void k_beam_head(BeamHeadArgs a, long long t) 
             s_cost[m] = a.cost[c0 + m];
             s_len[m] = a.len[c0 + m];
             s_fin[m] = a.fin[c0 + m];
+            if constexpr (CONSTRAIN) s_q[m] = a.cstate[c0 + m];
         }
         for (int i = m; i < N * W; i += 256) {
             const int k = i / W, j = i - k * W;
             hs[i] = a.H[(c0 + j) * N + k];
         }
         __syncthreads();
+        [[maybe_unused]] unsigned allowed = 0, exists = 0; // a bit per slot: byte m may follow it / is offered as a candidate
+        if constexpr (CONSTRAIN) {
+            const uint32_t *frow = a.frows ? a.frows + (size_t)(a.count - 1 - (t - len)) * a.fwords : nullptr;
+#pragma unroll
+            for (int j = 0; j < WP; j++) {
+                if (j >= W || s_fin[j]) continue;
+                const unsigned nx = a.ctab[(size_t)s_q[j] * 256 + m];
+                if (nx == 0xFFFFu) continue;
+                allowed |= 1u << j;
+                bool ok = true;
+                if (a.accept) ok = m == a.stop_byte ? a.accept[nx] != 0 : ((frow[nx >> 5] >> (nx & 31)) & 1u) != 0;
+                if (ok) exists |= 1u << j;
+            }
+        }
         float y[WP];
         int jo[WP]; // slot whose h register j reads (registers W..WP-1 repeat the last slot and are never candidates)
 #pragma unroll
@@ -2135,6 +2160,8 @@ __global__ __launch_bounds__(256) void k_beam_head(BeamHeadArgs a, long long t) 
 #pragma unroll
         for (int j = 0; j < WP; j++) {
             y[j] = y[j] + bym; // the logit z
+            if constexpr (CONSTRAIN)
+                if (!((allowed >> j) & 1u)) y[j] = -INFINITY; // (finished slots too: their z is not read)
             if (j < W) ps[j][m] = y[j];
         }
         __syncthreads();
@@ -2171,7 +2198,7 @@ __global__ __launch_bounds__(256) void k_beam_head(BeamHeadArgs a, long long t) 
             } else {
                 const double v = s_cost[j] + (double)lse_surprisal(s_sum[j], s_zmax[j], y[j]);
                 ck[j] = v != v ? (double)INFINITY : v;
-                live |= 1u << j;
+                if (!CONSTRAIN || ((exists >> j) & 1u)) live |= 1u << j;
             }
         }
         double lc = (double)INFINITY; // the thread's best live candidate
@@ -2241,6 +2268,12 @@ __global__ __launch_bounds__(256) void k_beam_head(BeamHeadArgs a, long long t) 
             a.len[c0 + m] = s_len[p] + (pf ? 0 : 1);
             a.fin[c0 + m] = pf || b == a.stop_byte ? 1 : 0;
             a.x_next[c0 + m] = pf ? -1 : b;
+            if constexpr (CONSTRAIN) {
+                // every read of the old states comes from s_q, filled before the first barrier: writing the array in place
+                // races with nothing (the workgroup owns its slots)
+                const unsigned nx = pf ? 0xFFFFu : a.ctab[(size_t)s_q[p] * 256 + b];
+                a.cstate[c0 + m] = nx == 0xFFFFu ? s_q[p] : (int)nx; // (a selected byte is allowed; the state stays in the table regardless)
+            }
         }
     }
     __syncthreads();
@@ -2257,12 +2290,12 @@ int beam_head_status() {
     g_beam_head_error = hipSuccess;
     return (int)e;
 }
-template <int WP, bool EXACT> static void beam_head_launch(const BeamHeadArgs &a, long long t, hipStream_t st) {
+template <int WP, bool EXACT, bool CONSTRAIN> static void beam_head_launch(const BeamHeadArgs &a, long long t, hipStream_t st) {
     // static LDS is up to 33 KB (ps), dynamic up to 64 KB; a refused request is an error, not a launch
-    static size_t granted = 0;
+    static size_t granted = 0; // (one per instantiation)
     const size_t lds = (size_t)a.W * a.N * sizeof(float);
     if (lds > granted) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_beam_head<WP, EXACT>),
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_beam_head<WP, EXACT, CONSTRAIN>),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) {
             g_beam_head_error = e;
@@ -2270,15 +2303,18 @@ template <int WP, bool EXACT> static void beam_head_launch(const BeamHeadArgs &a
         }
         granted = lds;
     }
-    hipLaunchKernelGGL((k_beam_head<WP, EXACT>), dim3(a.streams), dim3(256), lds, st, a, t);
+    hipLaunchKernelGGL((k_beam_head<WP, EXACT, CONSTRAIN>), dim3(a.streams), dim3(256), lds, st, a, t);
 }
 void beam_head(const BeamHeadArgs &a, long long t, hipStream_t st) {
     int wp = 1;
     while (wp < a.W) wp *= 2;
 #define BEAM_HEAD_CASE(WP)                                                                                                  \
     case WP:                                                                                                                \
-        if (a.W == WP) beam_head_launch<WP, true>(a, t, st);                                                                \
-        else beam_head_launch<WP, false>(a, t, st);                                                                         \
+        if (a.ctab) {                                                                                                       \
+            if (a.W == WP) beam_head_launch<WP, true, true>(a, t, st);                                                      \
+            else beam_head_launch<WP, false, true>(a, t, st);                                                               \
+        } else if (a.W == WP) beam_head_launch<WP, true, false>(a, t, st);                                                  \
+        else beam_head_launch<WP, false, false>(a, t, st);                                                                  \
         break;
     switch (wp) {
         BEAM_HEAD_CASE(1)

@@ -1802,9 +1802,22 @@ static int check_offsets(const char *what, const char *name, const uint64_t *off
 // Beam search (include/lstm_hip.h): the generator's loop over streams * beams columns.  Per step one
 // beam_head launch (selection, tables, the states gathered by parent into the second pair of buffers) and one k_fwd_step
 // from that pair back into the first; after the loop one beam_backtrack launch.  No readback inside the loop.
+// Constraint: a byte automaton selects beam_head's CONSTRAIN instantiation (a.ctab set).  As in
+// lstm_hip_generate_constrained the table is validated and every stream's state walked over its prompt on the host before
+// anything is launched; with accepting states the reachability rows F[R][q] are made here too, one bit per (R, q).  The
+// table, the slots' states, the accept bytes and the rows are the last pieces of the scratch layout, so that without a
+// constraint every offset, upload and launch is that of the call before constraints existed.
 int lstm_hip_beam_search(lstm_hip_t *h, int32_t streams, const uint8_t *prompts, const uint64_t *prompt_off, const float *h0,
                          const float *c0, const lstm_hip_beam *opt, int32_t count, uint8_t *out, int32_t *out_len, double *bits,
                          uint8_t *trace_parent, uint8_t *trace_byte) {
+    return lstm_hip_beam_search_constrained(h, streams, prompts, prompt_off, h0, c0, opt, count, out, out_len, bits, trace_parent,
+                                            trace_byte, nullptr, nullptr, nullptr);
+}
+
+int lstm_hip_beam_search_constrained(lstm_hip_t *h, int32_t streams, const uint8_t *prompts, const uint64_t *prompt_off,
+                                     const float *h0, const float *c0, const lstm_hip_beam *opt, int32_t count, uint8_t *out,
+                                     int32_t *out_len, double *bits, uint8_t *trace_parent, uint8_t *trace_byte,
+                                     const lstm_hip_beam_constraint *bc, const int32_t *start_state, int32_t *end_state) {
     CHECK(h);
     if (!opt) return fail(LSTM_HIP_EINVAL, "beam_search: null options");
     if (opt->size != sizeof(lstm_hip_beam))
@@ -1827,10 +1840,74 @@ int lstm_hip_beam_search(lstm_hip_t *h, int32_t streams, const uint8_t *prompts,
     const int N = h->cfg.N, Nl = h->N_log, cols = streams * W;
     if ((long long)N * W > 16384)
         return fail(LSTM_HIP_EINVAL, "beam_search: hidden width %d x %d beams above 16384 floats of LDS", N, W);
+    // the constraint: the table is checked, every stream's state walks its prompt, then the deadline rows
+    if (!bc && (start_state || end_state)) return fail(LSTM_HIP_EINVAL, "beam_search: start_state / end_state given without a constraint");
+    if (bc && bc->size != sizeof(lstm_hip_beam_constraint))
+        return fail(LSTM_HIP_EINVAL, "beam_search: beam constraint of %u bytes, expected %zu", bc->size, sizeof(lstm_hip_beam_constraint));
+    if (bc && !bc->con) return fail(LSTM_HIP_EINVAL, "beam_search: beam constraint with a null constraint");
+    const lstm_hip_constraint *con = bc ? bc->con : nullptr;
+    const uint8_t *accept = bc ? bc->accept : nullptr;
+    std::vector<int32_t> cstate;  // [streams] the state after each prompt (q0)
+    std::vector<uint16_t> ccount; // (the allowed counts are checked, not used)
+    std::vector<uint32_t> frows;  // [count + 1][fwords] bit q of row R: F[R][q]
+    const int Q = con ? con->states : 0, fwords = (Q + 31) / 32;
+    if (con) {
+        if (int rc = check_constraint("beam_search", con, streams, start_state, cstate, ccount)) return rc;
+        if (prompt_off)
+            for (int s = 0; s < streams; s++)
+                for (uint64_t j = prompt_off[s]; j < prompt_off[s + 1]; j++) {
+                    const uint16_t v = con->next[(size_t)cstate[s] * 256 + prompts[j]];
+                    if (v == 0xFFFF)
+                        return fail(LSTM_HIP_EINVAL, "beam_search: stream %d: prompt byte 0x%02x at offset %llu is forbidden in state %d",
+                                    s, (unsigned)prompts[j], (unsigned long long)(j - prompt_off[s]), cstate[s]);
+                    cstate[s] = v;
+                }
+    }
+    if (accept) {
+        if (((long long)count + 1) * Q > (1ll << 28))
+            return fail(LSTM_HIP_EINVAL, "beam_search: (count + 1) x states = %lld above 2^28 with accepting states", ((long long)count + 1) * Q);
+        // F[0][q] = acc(q); F[R][q] = some allowed byte b of q: acc(next) if b is the stop byte, else F[R - 1][next]
+        std::vector<std::vector<uint16_t>> succ(Q); // the distinct states q's allowed bytes other than the stop byte lead to
+        std::vector<char> stops(Q, 0);              // q's stop byte is allowed and leads into an accepting state
+        for (int q = 0; q < Q; q++) {
+            for (int b = 0; b < 256; b++) {
+                const uint16_t v = con->next[(size_t)q * 256 + b];
+                if (v == 0xFFFF) continue;
+                if (b == opt->stop_byte) stops[q] = accept[v] != 0;
+                else succ[q].push_back(v);
+            }
+            std::sort(succ[q].begin(), succ[q].end());
+            succ[q].erase(std::unique(succ[q].begin(), succ[q].end()), succ[q].end());
+        }
+        frows.assign((size_t)(count + 1) * fwords, 0u);
+        auto bit = [&](int R, int q) { return (frows[(size_t)R * fwords + (q >> 5)] >> (q & 31)) & 1u; };
+        for (int q = 0; q < Q; q++)
+            if (accept[q]) frows[q >> 5] |= 1u << (q & 31);
+        // a row is a function of the row before it: once two rows in sequence are equal every later one is, and is copied
+        bool settled = false;
+        for (int R = 1; R <= count; R++) {
+            uint32_t *row = frows.data() + (size_t)R * fwords;
+            if (settled) {
+                std::copy(row - fwords, row, row);
+                continue;
+            }
+            for (int q = 0; q < Q; q++) {
+                bool f = stops[q];
+                for (size_t i = 0; !f && i < succ[q].size(); i++) f = bit(R - 1, succ[q][i]);
+                if (f) row[q >> 5] |= 1u << (q & 31);
+            }
+            settled = std::equal(row, row + fwords, row - fwords);
+        }
+        for (int s = 0; s < streams; s++)
+            if (!bit(count, cstate[s]))
+                return fail(LSTM_HIP_EINVAL, "beam_search: stream %d: no accepted string of %d bytes or fewer ending in the stop byte "
+                            "from state %d", s, count, cstate[s]);
+    }
     if (count == 0) { // nothing is selected: every slot is as it starts
         for (int c = 0; c < cols; c++) {
             if (out_len) out_len[c] = 0;
             if (bits) bits[c] = c % W == 0 ? 0.0 : (double)INFINITY;
+            if (end_state) end_state[c] = cstate[c / W];
         }
         return 0;
     }
@@ -1847,7 +1924,9 @@ int lstm_hip_beam_search(lstm_hip_t *h, int32_t streams, const uint8_t *prompts,
                  o_G = piece(sizeof(float) * 4 * n), o_st = piece(h->padded() ? sizeof(float) * 2 * nl : 0),
                  o_x = piece(sizeof(int32_t) * cols), o_off = piece(prompt_off ? sizeof(uint64_t) * (streams + 1) : 0),
                  o_p = piece(total), o_tp = piece(nd), o_tb = piece(nd), o_out = piece(nd), o_cost = piece(sizeof(double) * cols),
-                 o_len = piece(sizeof(int32_t) * cols), o_fin = piece(sizeof(int32_t) * cols);
+                 o_len = piece(sizeof(int32_t) * cols), o_fin = piece(sizeof(int32_t) * cols),
+                 o_tab = piece(sizeof(uint16_t) * 256 * (size_t)Q), o_q = piece(con ? sizeof(int32_t) * cols : 0),
+                 o_acc = piece(accept ? (size_t)Q : 0), o_F = piece(accept ? sizeof(uint32_t) * (size_t)count * fwords : 0);
     if (int rc = reserve_gen_scratch(h, bytes)) return rc;
     char *base = h->gen_scratch;
     float4 *Ufwd = reinterpret_cast<float4 *>(base + o_U);
@@ -1860,6 +1939,10 @@ int lstm_hip_beam_search(lstm_hip_t *h, int32_t streams, const uint8_t *prompts,
     uint8_t *d_out = reinterpret_cast<uint8_t *>(base + o_out);
     double *d_cost = reinterpret_cast<double *>(base + o_cost);
     int32_t *d_len = reinterpret_cast<int32_t *>(base + o_len), *d_fin = reinterpret_cast<int32_t *>(base + o_fin);
+    uint16_t *d_tab = con ? reinterpret_cast<uint16_t *>(base + o_tab) : nullptr;
+    int32_t *d_q = con ? reinterpret_cast<int32_t *>(base + o_q) : nullptr;
+    uint8_t *d_acc = accept ? reinterpret_cast<uint8_t *>(base + o_acc) : nullptr;
+    uint32_t *d_F = accept ? reinterpret_cast<uint32_t *>(base + o_F) : nullptr;
 
     // start state: every slot of a stream starts from the stream's column (padding rows zero)
     const PadMap map = pad_map_rows(1, Nl, N, cols);
@@ -1888,6 +1971,20 @@ int lstm_hip_beam_search(lstm_hip_t *h, int32_t streams, const uint8_t *prompts,
     HIP_TRY(hipMemcpyAsync(d_cost, cost0.data(), sizeof(double) * cols, hipMemcpyHostToDevice, h->st));
     HIP_TRY(hipMemsetAsync(d_len, 0, sizeof(int32_t) * cols, h->st));
     HIP_TRY(hipMemsetAsync(d_fin, 0, sizeof(int32_t) * cols, h->st));
+    std::vector<int32_t> fin0, q0; // (alive until the synchronize below)
+    if (con) { // slots 1..W-1 start finished ("no such hypothesis"), every slot in its stream's state
+        fin0.assign(cols, 1);
+        q0.resize(cols);
+        for (int c = 0; c < cols; c++) q0[c] = cstate[c / W];
+        for (int s = 0; s < streams; s++) fin0[(size_t)s * W] = 0;
+        HIP_TRY(hipMemcpyAsync(d_fin, fin0.data(), sizeof(int32_t) * cols, hipMemcpyHostToDevice, h->st));
+        HIP_TRY(hipMemcpyAsync(d_q, q0.data(), sizeof(int32_t) * cols, hipMemcpyHostToDevice, h->st));
+        HIP_TRY(hipMemcpyAsync(d_tab, con->next, sizeof(uint16_t) * 256 * (size_t)Q, hipMemcpyHostToDevice, h->st));
+    }
+    if (accept) { // rows 0 .. count - 1: selection i reads row count - 1 - i
+        HIP_TRY(hipMemcpyAsync(d_acc, accept, (size_t)Q, hipMemcpyHostToDevice, h->st));
+        HIP_TRY(hipMemcpyAsync(d_F, frows.data(), sizeof(uint32_t) * (size_t)count * fwords, hipMemcpyHostToDevice, h->st));
+    }
     HIP_TRY(hipMemsetAsync(d_tp, 0, nd, h->st));
     HIP_TRY(hipMemsetAsync(d_tb, 0, nd, h->st));
     RUN(K_PACK_U, pack_U(h->P + h->pl.U, Ufwd, nullptr, N, h->st));
@@ -1912,6 +2009,11 @@ int lstm_hip_beam_search(lstm_hip_t *h, int32_t streams, const uint8_t *prompts,
     a.W = W;
     a.count = count;
     a.stop_byte = opt->stop_byte;
+    a.ctab = d_tab;
+    a.cstate = d_q;
+    a.accept = d_acc;
+    a.frows = d_F;
+    a.fwords = fwords;
     const bool fast = (h->cfg.flags & LSTM_HIP_FAST_MATH) != 0;
     const long long steps = (long long)max_len + count; // the longest stream's last selection is at step steps - 1
     for (long long t = 0; t < steps; t++) {
@@ -1928,6 +2030,7 @@ int lstm_hip_beam_search(lstm_hip_t *h, int32_t streams, const uint8_t *prompts,
     HIP_TRY(hipMemcpyAsync(bits, d_cost, sizeof(double) * cols, hipMemcpyDeviceToHost, h->st));
     if (trace_parent) HIP_TRY(hipMemcpyAsync(trace_parent, d_tp, nd, hipMemcpyDeviceToHost, h->st));
     if (trace_byte) HIP_TRY(hipMemcpyAsync(trace_byte, d_tb, nd, hipMemcpyDeviceToHost, h->st));
+    if (end_state) HIP_TRY(hipMemcpyAsync(end_state, d_q, sizeof(int32_t) * cols, hipMemcpyDeviceToHost, h->st));
     HIP_TRY(hipStreamSynchronize(h->st));
     return 0;
 }

@@ -4,7 +4,7 @@
 //
 //   lstm_generate --load PREFIX [--score FILE ...] [--score-bytes FILE [--top N]] [--count C --streams K --prime TEXT|--prime-file F
 //                 --temperature T --top-k K --top-p P --stop-byte B --seed S --utf8 --allow SPEC --ban SPEC
-//                 | --beams W --nbest K --length-alpha A]
+//                 | --beams W --nbest K --length-alpha A [--constrain-search --utf8 --allow SPEC --ban SPEC]]
 //                 [--fast-math] [--stable-softmax] [--device D]
 //
 // --load reads the five-file text checkpoint PREFIX_{W,U,Why,b,by}.txt (checkpoint.h); N is the rows of W / 4.
@@ -25,12 +25,17 @@
 // well-formed too) and prints a sample without an incomplete final character.  --allow SPEC draws only the listed bytes, --ban
 // SPEC never the listed ones; SPEC is comma-separated bytes and ranges, decimal or 0x hex (0x20-0x7e,10).  With --utf8 they
 // restrict its table (lstm_hip_dfa_restrict: a lead byte goes with its last continuation byte); without it the table has one
-// state.  None of the three goes with --beams or --score.
+// state.  None of the three goes with --score, and with --beams they need --constrain-search (below).
 // --beams W (1..32) searches instead of drawing (lstm_hip_beam_search): per stream the W most likely continuations of C bytes
 // the beam search finds, of which the --nbest K (default 1) best are printed under "== sample s hypothesis k: X bits ==",
 // ranked by their bits, or with --length-alpha A > 0 by bits / length^A.  It takes --prime, --count, --streams and
 // --stop-byte (a hypothesis ends with its first selected byte B); it draws nothing, so the sampling options are refused.
-// --beams 1 prints the text of --temperature 0.
+// --beams 1 prints the text of --temperature 0.  With --constrain-search it goes with --utf8 / --allow / --ban: the search is
+// over the continuations that table accepts (lstm_hip_beam_search_constrained).  With --utf8 the only accepting state is the
+// character boundary, so every printed hypothesis is whole characters; with --allow / --ban alone there are no accepting
+// states.  A stream whose table allows fewer than W continuations has fewer hypotheses: those that do not exist are not
+// printed, and --nbest counts the ones that do.  Without --constrain-search the three are refused with --beams, as they were
+// before the search took a constraint: they are options of drawing, and a script that relied on the refusal still gets it.
 // --stable-softmax scores and draws at temperature 1 with the
 // max-shifted softmax (LSTM_HIP_STABLE_SOFTMAX), for checkpoints whose logits pass expf's range.
 #include "../../include/lstm_hip.h"
@@ -52,7 +57,8 @@ const char *const kUsage =
     "                     [--count C --streams K --prime TEXT|--prime-file F\n"
     "                     --temperature T --top-k K --top-p P --stop-byte B --seed S\n"
     "                     --utf8 --allow SPEC --ban SPEC\n"
-    "                     | --beams W --nbest K --length-alpha A]\n"
+    "                     | --beams W --nbest K --length-alpha A\n"
+    "                       [--constrain-search --utf8 --allow SPEC --ban SPEC]]\n"
     "                     [--fast-math] [--stable-softmax] [--device D]\n"
     "  --score-bytes FILE  one row per byte: offset, byte, surprisal, entropy, rank; then the --score line of FILE\n"
     "  --top N        with --score-bytes: add the N most likely bytes of every place (1..8) with their bits\n"
@@ -60,9 +66,12 @@ const char *const kUsage =
     "  --top-p P      draw among the smallest most-likely-first set of bytes whose mass reaches P (0 < P <= 1)\n"
     "  --stop-byte B  end a sample with its first drawn byte B (decimal, 0..255) and print it up to that byte\n"
     "  --utf8         draw well-formed UTF-8 only; a sample is printed without an incomplete final character\n"
+    "                 (with --beams --constrain-search: search whole characters only)\n"
     "  --allow SPEC   draw only these bytes: comma-separated bytes and ranges, decimal or 0x hex (0x20-0x7e,10)\n"
     "  --ban SPEC     never draw these bytes (same SPEC); with --utf8 both restrict the UTF-8 table\n"
-    "  --beams W      beam search with W hypotheses per stream (1..32) instead of drawing; W x --streams <= 4096\n"
+    "  --beams W      beam search with W hypotheses per stream (1..32) instead of drawing; W x --streams <= 4096;\n"
+    "  --constrain-search  with --beams: let --utf8 / --allow / --ban constrain the search to the continuations they\n"
+    "                 accept (without it they are refused with --beams); hypotheses that do not exist are not printed\n"
     "  --nbest K      print the K best hypotheses of every stream (1..W, default 1) with their bits\n"
     "  --length-alpha A  rank hypotheses by bits / length^A (default 0: by bits)\n";
 
@@ -147,6 +156,7 @@ struct Options {
     uint32_t seed = 1;
     unsigned flags = 0;
     bool utf8 = false, has_allow = false, has_ban = false;
+    bool constrain_search = false; // --constrain-search: with --beams the constraint options constrain the search
     uint8_t allow[256] = {}, ban[256] = {};
     std::vector<uint16_t> table; // the constraint of --utf8 / --allow / --ban (empty: none), `states` rows of 256
     int32_t states = 0;
@@ -208,11 +218,14 @@ Options parse(int argc, char **argv) {
                 o.has_ban = true;
             }
             o.sampling_opts.push_back(a);
-            o.draw_opts.push_back(a);
             o.constraint_opts.push_back(a);
         } else if (a == "--beams") {
             o.beams = parse_int(a, val(), 1, 32);
             o.sampling_opts.push_back(a);
+        } else if (a == "--constrain-search") {
+            o.constrain_search = true;
+            o.sampling_opts.push_back(a);
+            o.beam_opts.push_back(a);
         } else if (a == "--nbest") {
             o.nbest = parse_int(a, val(), 1, 32);
             o.sampling_opts.push_back(a);
@@ -245,6 +258,9 @@ Options parse(int argc, char **argv) {
     if (o.beams == 0 && !o.beam_opts.empty()) usage(o.beam_opts[0] + " needs --beams");
     if (o.beams > 0) {
         if (!o.draw_opts.empty()) usage(o.draw_opts[0] + " means nothing with --beams: a beam search draws nothing");
+        if (!o.constraint_opts.empty() && !o.constrain_search)
+            usage(o.constraint_opts[0] + " is an option of drawing: with --beams it needs --constrain-search");
+        if (o.constrain_search && o.constraint_opts.empty()) usage("--constrain-search needs --utf8, --allow or --ban");
         if (o.nbest > o.beams) usage("--nbest cannot pass --beams");
         if (o.beams * o.streams > 4096) usage("--beams x --streams must be at most 4096");
         if ((long long)std::max(o.count, 0L) * o.streams * o.beams > (1LL << 31) - 1) usage("--count x --streams x --beams is too large");
@@ -347,14 +363,24 @@ int main(int argc, char **argv) {
         std::vector<int32_t> out_len((size_t)K * W);
         std::vector<double> bits((size_t)K * W);
         const lstm_hip_beam opt{(uint32_t)sizeof(lstm_hip_beam), (int32_t)W, (int32_t)o.stop_byte};
-        CK(lstm_hip_beam_search(h, K, prompts.data(), off.data(), nullptr, nullptr, &opt, C, out.data(), out_len.data(), bits.data(),
-                                nullptr, nullptr));
+        if (o.table.empty())
+            CK(lstm_hip_beam_search(h, K, prompts.data(), off.data(), nullptr, nullptr, &opt, C, out.data(), out_len.data(),
+                                    bits.data(), nullptr, nullptr));
+        else { // --utf8: a hypothesis may end on a character boundary only (state 0 of the table)
+            const lstm_hip_constraint con{(uint32_t)sizeof(lstm_hip_constraint), o.states, o.table.data()};
+            std::vector<uint8_t> accept(o.states, 0);
+            accept[0] = 1;
+            const lstm_hip_beam_constraint bc{(uint32_t)sizeof(lstm_hip_beam_constraint), &con, o.utf8 ? accept.data() : nullptr};
+            CK(lstm_hip_beam_search_constrained(h, K, prompts.data(), off.data(), nullptr, nullptr, &opt, C, out.data(),
+                                                out_len.data(), bits.data(), nullptr, nullptr, &bc, nullptr, nullptr));
+        }
         for (int s = 0; s < K; s++) {
-            std::vector<int> order(W);
-            for (int r = 0; r < W; r++) order[r] = s * W + r;
+            std::vector<int> order;
+            for (int r = 0; r < W; r++) // under a constraint, infinite bits and no bytes: no such hypothesis
+                if (o.table.empty() || !(std::isinf(bits[s * W + r]) && out_len[s * W + r] == 0)) order.push_back(s * W + r);
             auto score = [&](int c) { return bits[c] / std::pow((double)std::max(out_len[c], 1), o.length_alpha); };
             if (o.length_alpha > 0.0) std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return score(x) < score(y); });
-            for (int k = 0; k < (int)o.nbest; k++) {
+            for (int k = 0; k < (int)std::min<size_t>(o.nbest, order.size()); k++) {
                 const int c = order[k];
                 printf("== sample %d hypothesis %d: %.5f bits ==\n", s, k, bits[c]);
                 fwrite(prime.data(), 1, prime.size(), stdout);

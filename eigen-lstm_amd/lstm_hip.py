@@ -51,6 +51,10 @@ class _Beam(C.Structure):  # lstm_hip_beam
     _fields_ = [("size", C.c_uint32), ("beams", C.c_int32), ("stop_byte", C.c_int32)]
 
 
+class _BeamConstraint(C.Structure):  # lstm_hip_beam_constraint
+    _fields_ = [("size", C.c_uint32), ("con", C.POINTER(_Constraint)), ("accept", C.POINTER(C.c_uint8))]
+
+
 class _Scoring(C.Structure):  # lstm_hip_scoring
     _fields_ = [("size", C.c_uint32), ("first", C.c_int32), ("top_n", C.c_int32), ("con", C.POINTER(_Constraint))]
 
@@ -82,7 +86,7 @@ SYMBOLS = [
     "lstm_hip_set_optimizer_steps", "lstm_hip_coder_version", "lstm_hip_code_bound", "lstm_hip_encode", "lstm_hip_decode",
     "lstm_hip_adaptive_version", "lstm_hip_adaptive_blocks", "lstm_hip_encode_adaptive", "lstm_hip_decode_adaptive",
     "lstm_hip_plan_identity", "lstm_hip_beam_search", "lstm_hip_generate_constrained", "lstm_hip_dfa_utf8",
-    "lstm_hip_dfa_restrict", "lstm_hip_score",
+    "lstm_hip_dfa_restrict", "lstm_hip_score", "lstm_hip_beam_search_constrained",
 ]
 
 
@@ -496,13 +500,22 @@ class Lstm:
                 "bits": bits, "h": h, "c": c, "end_state": q1}
 
     def beam_search(self, prompts=None, count=0, beams=4, stop_byte=-1, h0=None, c0=None, streams=None, length_alpha=0.0,
-                    trace=False):
+                    trace=False, constraint=None, start_state=None, accept=None):
         """lstm_hip_beam_search: per stream the `beams` most likely continuations of its prompt the search finds.  Returns a
         list (one entry per stream) of lists of (bytes, bits), best first: the hypothesis cut to its length (a stop byte
         included) and its cost.  length_alpha > 0 re-ranks each stream's list on the host by bits / len**length_alpha (a
         stable sort; empty hypotheses rank by their bits); the ABI itself always returns raw cost order.  trace=True adds a
         second result {"out": uint8 [streams, beams, count], "out_len": int32 [streams, beams], "bits": float64 [streams,
-        beams], "parent", "byte": uint8 [count, streams * beams]} with the call's raw arrays."""
+        beams], "parent", "byte": uint8 [count, streams * beams]} with the call's raw arrays.
+        constraint: a (states, 256) uint16 table as in generate, for lstm_hip_beam_search_constrained: the search is over the
+        continuations the table accepts, from start_state [streams] (None: 0) advanced over the prompts.  accept: [states]
+        flags, nonzero where a hypothesis may end (None: everywhere); with it every hypothesis of finite bits ends in an
+        accepting state, by its stop byte or with exactly `count` bytes.  A stream whose table allows fewer than `beams`
+        strings fills its list with (b"", inf) entries, "no such hypothesis": they are kept, last, and the length_alpha
+        re-ranking leaves entries of infinite bits where they are.  Under a constraint the result is ALWAYS a pair: the
+        second element has "end_state": int32 [streams, beams], the DFA state of every final slot in the ABI's raw cost
+        order (like "out_len" and "bits", which it also holds), and with trace=True the other raw arrays as above.  With
+        constraint=None the call and its result are those made without the argument."""
         if streams is None:
             streams = len(prompts) if prompts is not None else (np.asarray(h0).shape[0] if h0 is not None else 1)
         streams, count, W = int(streams), int(count), int(beams)
@@ -519,21 +532,46 @@ class Lstm:
         tp = np.zeros((max(count, 0), cols), np.uint8)
         tb = np.zeros((max(count, 0), cols), np.uint8)
         opt = _Beam(C.sizeof(_Beam), W, int(stop_byte))
-        _chk(self.lib.lstm_hip_beam_search(
-            self._h, C.c_int32(streams), _ptr(d_p, C.c_uint8) if d_p is not None else None,
-            _ptr(d_off, C.c_uint64) if d_off is not None else None, _ptr(hh) if hh is not None else None,
-            _ptr(cc) if cc is not None else None, C.byref(opt), C.c_int32(count), _ptr(out, C.c_uint8),
-            _ptr(out_len, C.c_int32), _ptr(bits, C.c_double), _ptr(tp, C.c_uint8) if trace else None,
-            _ptr(tb, C.c_uint8) if trace else None))
+        args = (self._h, C.c_int32(streams), _ptr(d_p, C.c_uint8) if d_p is not None else None,
+                _ptr(d_off, C.c_uint64) if d_off is not None else None, _ptr(hh) if hh is not None else None,
+                _ptr(cc) if cc is not None else None, C.byref(opt), C.c_int32(count), _ptr(out, C.c_uint8),
+                _ptr(out_len, C.c_int32), _ptr(bits, C.c_double), _ptr(tp, C.c_uint8) if trace else None,
+                _ptr(tb, C.c_uint8) if trace else None)
+        if constraint is None and (start_state is not None or accept is not None):
+            raise LstmHipError("beam_search: start_state / accept given without a constraint")
+        q1 = None
+        if constraint is None:
+            _chk(self.lib.lstm_hip_beam_search(*args))
+        else:
+            table = np.ascontiguousarray(constraint, dtype=np.uint16)
+            assert table.ndim == 2 and table.shape[1] == 256, table.shape
+            con = _Constraint(C.sizeof(_Constraint), table.shape[0], _ptr(table, C.c_uint16))
+            acc = None if accept is None else np.ascontiguousarray(np.asarray(accept).reshape(table.shape[0]) != 0, dtype=np.uint8)
+            bc = _BeamConstraint(C.sizeof(_BeamConstraint), C.pointer(con), _ptr(acc, C.c_uint8) if acc is not None else None)
+            q0 = None if start_state is None else np.ascontiguousarray(start_state, dtype=np.int32).reshape(streams)
+            q1 = np.zeros(cols, np.int32)
+            _chk(self.lib.lstm_hip_beam_search_constrained(*args, C.byref(bc), _ptr(q0, C.c_int32) if q0 is not None else None,
+                                                           _ptr(q1, C.c_int32)))
         res = []
         for s in range(streams):
             hyp = [(out[s * W + r, :out_len[s * W + r]].tobytes(), float(bits[s * W + r])) for r in range(W)]
             if length_alpha > 0:
-                hyp.sort(key=lambda e: e[1] / max(len(e[0]), 1) ** length_alpha)
+                if constraint is None:
+                    hyp.sort(key=lambda e: e[1] / max(len(e[0]), 1) ** length_alpha)
+                else:  # entries of infinite bits (no such hypothesis) stay where they are
+                    ranked = iter(sorted((e for e in hyp if e[1] != float("inf")),
+                                         key=lambda e: e[1] / max(len(e[0]), 1) ** length_alpha))
+                    hyp = [e if e[1] == float("inf") else next(ranked) for e in hyp]
             res.append(hyp)
         if trace:
-            return res, {"out": out.reshape(streams, W, count), "out_len": out_len.reshape(streams, W),
-                         "bits": bits.reshape(streams, W), "parent": tp, "byte": tb}
+            raw = {"out": out.reshape(streams, W, count), "out_len": out_len.reshape(streams, W),
+                   "bits": bits.reshape(streams, W), "parent": tp, "byte": tb}
+            if q1 is not None:
+                raw["end_state"] = q1.reshape(streams, W)
+            return res, raw
+        if q1 is not None:
+            return res, {"out_len": out_len.reshape(streams, W), "bits": bits.reshape(streams, W),
+                         "end_state": q1.reshape(streams, W)}
         return res
 
     def encode(self, texts, trace=False):

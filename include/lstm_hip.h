@@ -319,7 +319,8 @@ int lstm_hip_generate_ex(lstm_hip_t *h, int32_t streams, const uint8_t *prompts,
  *      end_state given with con NULL; con->size != sizeof(lstm_hip_constraint); states outside 1..4096; next NULL; an entry
  *      that is neither < states nor 0xFFFF; a start state outside 0..states-1; a state that can be reached from some stream's
  *      start state and has no allowed byte (breadth-first from the start states: unreachable rows may be empty); a prompt
- *      byte the table rejects.  Beam search, the coders and lstm_hip_sample take no constraint. */
+ *      byte the table rejects.  The coders and lstm_hip_sample take no constraint (beam search does: see
+ *      lstm_hip_beam_search_constrained). */
 typedef struct lstm_hip_constraint {
     uint32_t size;        /* sizeof(lstm_hip_constraint); anything else: LSTM_HIP_EINVAL */
     int32_t  states;      /* Q: 1..4096 */
@@ -387,6 +388,56 @@ int lstm_hip_beam_search(lstm_hip_t *h, int32_t streams, const uint8_t *prompts,
                          double  *bits     /* [streams*W] */,
                          uint8_t *trace_parent /* [count][streams*W], may be NULL */,
                          uint8_t *trace_byte   /* [count][streams*W], may be NULL */);
+/* ---- beam search under a constraint, with accepting states: per stream the most likely
+ *      continuations THAT THE TABLE ACCEPTS.  lstm_hip_beam_search is a thin caller of this function with bc = start_state =
+ *      end_state = NULL, and that call makes the launches it made before this function existed.  Everything
+ *      lstm_hip_beam_search documents holds under a constraint, except:
+ *        states     every slot carries a state q of bc->con (the table of lstm_hip_generate_constrained).  The stream's state
+ *                   starts at start_state[s] (NULL: 0) and is advanced over the stream's prompt on the host before anything is
+ *                   launched; a prompt byte forbidden where it stands is LSTM_HIP_EINVAL (the message names the stream and the
+ *                   offset).  All W slots start in the resulting state q0.  A live slot extended by byte m moves to
+ *                   next[q][m]; a finished slot keeps its state; states follow parents like h and c.  end_state[s*W + r] (may
+ *                   be NULL) is the state of final slot r.
+ *        absent     slots 1..W-1 start FINISHED: cost +inf, length 0, state q0 (in the unconstrained call they start live
+ *                   with cost +inf).  They offer themselves as any finished slot does and are selected only when fewer than W
+ *                   other candidates exist, so a hypothesis with bits = +inf and out_len = 0 is "no such hypothesis": a table
+ *                   that allows fewer than W strings returns fewer.  Every live slot offers at least one candidate (deadline)
+ *                   and every finished slot exactly one, so a selection always finds W.
+ *        cost       z'_m = z_m where next[q][m] is allowed, -inf otherwise; zmax, the sequential float sum of
+ *                   expf(z'_k - zmax) and the surprisal are taken on z'.  A forbidden term adds 0.0f, so the sum is the one
+ *                   over the allowed bytes in index order: this is the max-shifted surprisal lstm_hip_score computes under
+ *                   the same table, and a hypothesis's bits is, bit for bit, the double sum in text order of the surprisal[]
+ *                   entries a LSTM_HIP_STABLE_SOFTMAX handle's lstm_hip_score(con) gives its bytes.  The deadline removes
+ *                   candidates; it never changes a cost.
+ *        deadline   only with bc->accept.  acc(q) = accept[q] != 0.  F[0][q] = acc(q); for R >= 1, F[R][q] = OR over the
+ *                   allowed bytes b of q of: acc(next[q][b]) if b is the stop byte, F[R-1][next[q][b]] otherwise ("from q an
+ *                   accepted end is reached by exactly R more bytes, or fewer when the last is the stop byte").  At selection
+ *                   i, with R = count - i, candidate (slot j, byte m) EXISTS iff slot j is live, nx = next[q_j][m] is allowed,
+ *                   and acc(nx) if m is the stop byte, F[R-1][nx] otherwise.  Candidates that do not exist are not offered.
+ *                   F[count][q0] is checked, and the rule keeps F[R][q] true for every live slot, so it always offers a
+ *                   candidate.  Hence every hypothesis with finite bits ends in an accepting state: finished by a stop byte
+ *                   into one, or holding exactly count bytes and standing in one.  With accept = NULL every state accepts, no
+ *                   table is built or read and there is no deadline (a stop byte may then end a hypothesis anywhere).
+ *                   Building F is host work before the first launch: at most count * (transitions between distinct states)
+ *                   steps, and only copies once two rows in sequence are equal (for the UTF-8 table: from row 4 on).
+ *        order      among the candidates that exist, the four-key order of lstm_hip_beam_search.
+ *        count 0    out_len = 0, bits = the start costs, end_state = q0 for every slot; with accept, q0 must be accepting.
+ *      LSTM_HIP_EINVAL (the handle stays usable, the message says which), beside those of lstm_hip_beam_search: start_state
+ *      or end_state given with bc NULL; bc->size != sizeof(lstm_hip_beam_constraint); bc->con NULL; every table refusal of
+ *      lstm_hip_generate_constrained; a prompt byte the table rejects; with accept: F[count][q0] false for some stream (the
+ *      message names it: "no accepted string of `count` bytes or fewer ending in the stop byte"), or (count + 1) * states
+ *      above 2^28. */
+typedef struct lstm_hip_beam_constraint {
+    uint32_t size;                    /* sizeof(lstm_hip_beam_constraint); anything else: LSTM_HIP_EINVAL */
+    const lstm_hip_constraint *con;   /* the table, as lstm_hip_generate_constrained takes it; required */
+    const uint8_t *accept;            /* [con->states], nonzero = accepting; NULL: every state accepts */
+} lstm_hip_beam_constraint;
+int lstm_hip_beam_search_constrained(lstm_hip_t *h, int32_t streams, const uint8_t *prompts, const uint64_t *prompt_off,
+                                     const float *h0, const float *c0, const lstm_hip_beam *opt, int32_t count,
+                                     uint8_t *out, int32_t *out_len, double *bits, uint8_t *trace_parent, uint8_t *trace_byte,
+                                     const lstm_hip_beam_constraint *bc /* NULL: exactly lstm_hip_beam_search */,
+                                     const int32_t *start_state /* [streams], may be NULL: all 0 */,
+                                     int32_t *end_state /* [streams*W], may be NULL */);
 /* ---- per-byte scores: what the model thinks of every byte of given texts.  Stream s is
  *      text[text_off[s] .. text_off[s+1]), 1 <= streams <= 4096; empty streams are allowed (no entries, h_out = the start
  *      state).  h0 / c0 / h_out / c_out are N x streams as in lstm_hip_generate (NULL = zeros / not wanted); h_out is the

@@ -4,8 +4,13 @@
       N = 512, 64 streams x W in {4, 16} beams: the beam step (lstm_hip_beam_search) and the generator's greedy step
       (lstm_hip_generate, temperature 0) at the same number of columns, 64 * W streams.  Both are taken twice, alternately
       (beam, greedy, beam, greedy); one JSON line per measurement and one per shape with the ratios.
-  python tools/beam_cost.py prof [--count 200]
+  python tools/beam_cost.py prof [--count 200] [--constraint trivial|utf8]
       one search per shape and nothing else timed, for `rocprofv3 --kernel-trace --stats` (tools/kernel_stats_from_db.py).
+  python tools/beam_cost.py step --constraint none|trivial|utf8 [--label NAME]
+      the beam step alone at both shapes, one JSON line per shape (profiles/beam/constrained_cost.jsonl; DESIGN.md section
+      3.12): unconstrained, under a one-state table that allows everything, or under the UTF-8 table with state 0 accepting
+      (lstm_hip_beam_search_constrained).  One process measures one side; the sides -- the parent commit's library through
+      LSTM_HIP_LIB with `none`, then this build's three -- are run alternately, twice each, by the caller.
 
 A step's time is the call's wall time (it ends in a stream synchronise) over `count`; the best and the median of `repeats`
 calls after one untimed call.  The model is the seeded initialisation with the output layer scaled by 9, as peaked as a
@@ -47,18 +52,30 @@ def _time(call, count, repeats):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", choices=("steps", "prof"))
+    ap.add_argument("mode", choices=("steps", "prof", "step"))
+    ap.add_argument("--constraint", choices=("none", "trivial", "utf8"), default="none")
+    ap.add_argument("--label", default="")
     ap.add_argument("--count", type=int, default=2000)
     ap.add_argument("--repeats", type=int, default=5)
     a = ap.parse_args()
     L = _handle()
     rs = np.random.RandomState(7)
+    con = {}
+    if a.constraint == "trivial":
+        con = dict(constraint=np.zeros((1, 256), np.uint16))
+    elif a.constraint == "utf8":
+        con = dict(constraint=lstm_hip.dfa_utf8(), accept=np.arange(8) == 0)
     for W in BEAMS:
         h0 = (rs.randn(STREAMS, N) * 0.1).astype(np.float32)
         c0 = (rs.randn(STREAMS, N) * 0.1).astype(np.float32)
-        beam = lambda: L.beam_search(count=a.count, beams=W, h0=h0, c0=c0, streams=STREAMS)
+        beam = lambda: L.beam_search(count=a.count, beams=W, h0=h0, c0=c0, streams=STREAMS, **con)
         if a.mode == "prof":
             beam()
+            continue
+        if a.mode == "step":
+            best, med = _time(beam, a.count, a.repeats)
+            print(json.dumps(dict(case="beam", side=a.label or a.constraint, constraint=a.constraint, N=N, streams=STREAMS, beams=W,
+                                  count=a.count, repeats=a.repeats, us_per_step=best, us_per_step_median=med)), flush=True)
             continue
         hw, cw = np.repeat(h0, W, axis=0), np.repeat(c0, W, axis=0)
         greedy = lambda: L.generate(count=a.count, temperature=0.0, h0=hw, c0=cw, streams=STREAMS * W)
