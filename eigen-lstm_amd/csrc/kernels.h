@@ -61,6 +61,8 @@ struct EnginePlan {
     bool adagrad_quad = false; // Adagrad refreshes the two-half images (Ufwd5 + Ubwd6, or Ufwd6b) with quad transposes
     bool du_split = false;    // LSTM_HIP_DU_SPLIT (fp32, communicator loop): dU as two column halves, the first reduced early
     bool stamps = false;      // LSTM_HIP_DEBUG_STAMPS on a shape whose forms carry stamps
+    unsigned epoch_limit = 1u << 26; // LSTM_HIP_EPOCH_LIMIT: a recurrence that has made this many launches on the cumulative
+                                     // hand-off counters clears them and restarts its epoch (do_forward / do_backward)
     // live images and rings (sizes in elements; 0: none)
     size_t hx_floats = 0;        // Hx
     size_t hxb_halfwords = 0;    // Hxb

@@ -193,6 +193,7 @@ struct lstm_hip_ctx {
     unsigned long long *stamps = nullptr; // LSTM_HIP_DEBUG_STAMPS: [fwd, bwd][2 workgroups][S][16] s_memtime values
     int loss_mode = 0; // LSTM_HIP_LOSS_*
     unsigned fwd_epoch = 0, bwd_epoch = 0; // launches so far on the cumulative hand-off counters
+    int64_t counter_resets = 0;            // times either direction cleared its counters at EnginePlan::epoch_limit
 
     void *comm = nullptr;
     int nranks = 1, rank = 0;
@@ -307,9 +308,10 @@ int do_forward(lstm_hip_ctx *h) {
     }
     h->n_dby_parts = softmax_parts(h->T);
     if (p.persistent()) {
-        if (h->fwd_epoch >= (1u << 26)) { // keep epoch * arrivals inside 32 bits
+        if (h->fwd_epoch >= p.epoch_limit) { // keep epoch * arrivals inside 32 bits
             HIP_TRY(hipMemsetAsync(h->cnt, 0, h->cnt_bytes, h->st));
             h->fwd_epoch = 0;
+            h->counter_resets++;
         }
         h->fwd_epoch++;
     }
@@ -415,9 +417,10 @@ int do_backward(lstm_hip_ctx *h) {
     unsigned long long *stamps_b = h->stamps ? h->stamps + (size_t)2 * S * 16 : nullptr;
     float *gpart = fused ? h->gpart : nullptr;
     if (p.persistent()) {
-        if (h->bwd_epoch >= (1u << 26)) {
+        if (h->bwd_epoch >= p.epoch_limit) {
             HIP_TRY(hipMemsetAsync(cb, 0, h->cnt_bytes, h->st));
             h->bwd_epoch = 0;
+            h->counter_resets++;
         }
         h->bwd_epoch++;
     }
@@ -504,6 +507,12 @@ int do_backward(lstm_hip_ctx *h) {
         dW_sums(h->DG + (size_t)G4 * B, T, G4, h->dP + h->pl.W, h->dP + h->pl.b, h->dw_scratch, h->st2);
         if (int rc = launch_status(K_SIDE_SUMS)) return rc;
         HIP_TRY(hipEventRecord(h->ev_join, h->st2));
+    } else if (p.side_stream) {
+        // a side-stream shape in a profiling pass or under a communicator: the side stream's own passes, in line.  (dW_db takes
+        // its one-pass table for short windows, which sums in another order: a profiled window must give the bits of an
+        // unprofiled one.)
+        RUN(K_DW_DB, (dW_sort(h->xi + B, T, G4, h->dw_scratch, h->st),
+                      dW_sums(h->DG + (size_t)G4 * B, T, G4, h->dP + h->pl.W, h->dP + h->pl.b, h->dw_scratch, h->st)));
     } else {
         RUN(K_DW_DB, dW_db(h->DG + (size_t)G4 * B, h->xi + B, T, G4, h->dP + h->pl.W, h->dP + h->pl.b, h->dw_scratch, h->st));
     }
@@ -2523,9 +2532,17 @@ int lstm_hip_set_profiling(lstm_hip_t *h, int32_t on) {
     h->profiling = on != 0;
     return 0;
 }
-int lstm_hip_kernel_stat_count(lstm_hip_t *) { return K_COUNT; }
+// the kernels' rows and, behind them, one row that is no kernel: "counter_resets", the times a recurrence cleared its hand-off
+// counters (do_forward / do_backward), counted whether or not profiling is on; its time is 0
+int lstm_hip_kernel_stat_count(lstm_hip_t *) { return K_COUNT + 1; }
 int lstm_hip_kernel_stat(lstm_hip_t *h, int32_t idx, const char **name, int64_t *launches, double *total_ms) {
-    if (!h || idx < 0 || idx >= K_COUNT) return fail(LSTM_HIP_EINVAL, "kernel_stat: bad index %d", idx);
+    if (!h || idx < 0 || idx > K_COUNT) return fail(LSTM_HIP_EINVAL, "kernel_stat: bad index %d", idx);
+    if (idx == K_COUNT) {
+        if (name) *name = "counter_resets";
+        if (launches) *launches = h->counter_resets;
+        if (total_ms) *total_ms = 0.0;
+        return 0;
+    }
     if (name) *name = kKernelNames[idx];
     if (launches) *launches = h->launches[idx];
     if (total_ms) *total_ms = h->total_ms[idx];
@@ -2535,6 +2552,7 @@ int lstm_hip_reset_kernel_stats(lstm_hip_t *h) {
     if (!h) return fail(LSTM_HIP_EINVAL, "null handle");
     memset(h->launches, 0, sizeof(h->launches));
     memset(h->total_ms, 0, sizeof(h->total_ms));
+    h->counter_resets = 0;
     return 0;
 }
 

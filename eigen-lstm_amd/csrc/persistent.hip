@@ -3794,7 +3794,8 @@ void bwd_persistent(const float4 *Ubwd, float *DG, const float *DHy, const float
 // Every rule of the window lives here, next to the occupancy checks it rests on; the launchers and the window code follow the
 // plan.  Environment switches, read here (per handle): LSTM_HIP_FWD_HALVES=0 / LSTM_HIP_BWD_HALVES=0 select the one-recurrence
 // forms where the shape has them (other BWD_HALVES values carry the scatter kernel's test bits, value >> 1),
-// LSTM_HIP_BWD_SPREAD=1 keeps the dispatch-order mapping of the backward recurrence, LSTM_HIP_DU_SPLIT=1.
+// LSTM_HIP_BWD_SPREAD=1 keeps the dispatch-order mapping of the backward recurrence, LSTM_HIP_DU_SPLIT=1,
+// LSTM_HIP_EPOCH_LIMIT=1..2^26 (test hook: the launch count at which the hand-off counters are cleared; anything else is refused).
 static int env_int(const char *name, int dflt) { return getenv(name) ? atoi(getenv(name)) : dflt; }
 EnginePlan plan_engine(int N, int B, unsigned flags, int n_cus) {
     EnginePlan p;
@@ -3805,6 +3806,13 @@ EnginePlan plan_engine(int N, int B, unsigned flags, int n_cus) {
     p.n_cus = n_cus;
     const int fwd_halves = env_int("LSTM_HIP_FWD_HALVES", 1), bwd_halves = env_int("LSTM_HIP_BWD_HALVES", 1);
     p.bwd_spread = env_int("LSTM_HIP_BWD_SPREAD", 0) != 0;
+    if (const char *lim = getenv("LSTM_HIP_EPOCH_LIMIT")) { // default 2^26: epoch * arrivals and (epoch << 4) | id stay in 32 bits
+        char *end = nullptr;
+        const long long v = strtoll(lim, &end, 10);
+        if (end == lim || *end != '\0' || v < 1 || v > (1ll << 26))
+            return refuse("LSTM_HIP_EPOCH_LIMIT must be a whole number in [1, %d] (got '%.32s')", 1 << 26, lim);
+        p.epoch_limit = (unsigned)v;
+    }
     const bool step = (flags & LSTM_HIP_STEP_KERNELS) != 0;
     if (flags & LSTM_HIP_BF16_RECURRENCE) { // every product is a bf16 GEMM of its own, nothing is fused into the recurrence
         if (step || N % 128 != 0 || N > 1024)

@@ -577,6 +577,8 @@ int lstm_hip_synchronize(lstm_hip_t *h);
  * slot meanings: persistent.hip, FSTAMP / BSTAMP) */
 int lstm_hip_debug_stamps(lstm_hip_t *h, uint64_t *out, size_t count);
 int lstm_hip_set_profiling(lstm_hip_t *h, int32_t on);
+/* rows 0 .. count-1; the last row, "counter_resets", is no kernel: its launches are the times a persistent recurrence
+ * cleared its hand-off counters (every 2^26 launches, or LSTM_HIP_EPOCH_LIMIT), counted with profiling on or off, time 0 */
 int lstm_hip_kernel_stat_count(lstm_hip_t *h);
 int lstm_hip_kernel_stat(lstm_hip_t *h, int32_t idx, const char **name, int64_t *launches, double *total_ms);
 int lstm_hip_reset_kernel_stats(lstm_hip_t *h);
