@@ -341,6 +341,12 @@ PadMap pad_map_params(int N, int Np, int M);              // the flat block [W |
 PadMap pad_map_rows(int blocks, int N, int Np, int cols); // `cols` columns of `blocks` x N rows (h, c: 1; g: 4)
 void pad_copy(const float *src, float *dst, const PadMap &map, bool to_padded, hipStream_t st);
 
+// ---- running weight average (lstm_hip_set_averaging): one launch of its own after the update launch, on due updates only.
+//      copy: a <- p, no arithmetic (the first due update); else a <- a + w * (p - a) in fp32, three separately rounded
+//      operations, no FMA.  p and a are 16-byte aligned blocks of n floats that do not overlap; at most 8 * cus workgroups
+//      of 256 threads stride over them in float4.  Plain vector loads and stores only.
+void average(const float *p, float *a, size_t n, float w, bool copy, int cus, hipStream_t st);
+
 // ---- B = 1 recurrence for the evaluator / sampler (OV/lstm_eigen_class_CUDA/lstm.cc:578-720)
 // One workgroup with b1_lds_bytes(N) of dynamic LDS, which the caller checks against the device's opt-in limit first; both
 // return the status of the grant and of the launch.

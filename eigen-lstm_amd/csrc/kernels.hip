@@ -2857,6 +2857,42 @@ PadMap pad_map_params(int N, int Np, int M) {
     m.total_p = p.total;
     return m;
 }
+// ------------------------------------------------------------------------------------------------
+// average: one step of the running weight average (kernels.h).  Grid-stride over the block in float4:
+// p is read once, a is read and written once (COPY: written only), 16 bytes per lane, lanes of a wave on consecutive float4.
+// The blend is three separately rounded fp32 operations, written as plain expressions under this file's fp contract(off):
+// v_sub, v_mul, v_add in the code object, no FMA.  (Not __fadd_rn(a, __fmul_rn(w, __fsub_rn(p, a))): those are header inlines
+// compiled with contraction allowed, and the compiler fuses the pair into v_fma.)  So a + w * (p - a) on float32 arrays
+// reproduces it bit for bit.  A block whose length is no
+// multiple of 4 ends in up to three scalars, done by the first lanes of workgroup 0 (no handle has such a block: N % 16 == 0).
+template <bool COPY>
+__global__ __launch_bounds__(256) void k_average(const float *__restrict__ p, float *__restrict__ a, size_t n, float w) {
+    const size_t n4 = n / 4;
+    const float4 *__restrict__ p4 = reinterpret_cast<const float4 *>(p);
+    float4 *__restrict__ a4 = reinterpret_cast<float4 *>(a);
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+        float4 pv = p4[i];
+        if (!COPY) {
+            const float4 av = a4[i];
+            pv.x = av.x + w * (pv.x - av.x);
+            pv.y = av.y + w * (pv.y - av.y);
+            pv.z = av.z + w * (pv.z - av.z);
+            pv.w = av.w + w * (pv.w - av.w);
+        }
+        a4[i] = pv;
+    }
+    const size_t r = n4 * 4 + threadIdx.x;
+    if (blockIdx.x == 0 && r < n) a[r] = COPY ? p[r] : a[r] + w * (p[r] - a[r]);
+}
+void average(const float *p, float *a, size_t n, float w, bool copy, int cus, hipStream_t st) {
+    if (n == 0) return;
+    const size_t want = (n / 4 + 255) / 256;
+    const size_t cap = (size_t)(cus > 0 ? cus : 1) * 8; // eight 256-thread workgroups fill a CU's 32 wave slots
+    const int blocks = (int)(want < 1 ? 1 : want > cap ? cap : want);
+    if (copy) hipLaunchKernelGGL(k_average<true>, dim3(blocks), dim3(256), 0, st, p, a, n, w);
+    else hipLaunchKernelGGL(k_average<false>, dim3(blocks), dim3(256), 0, st, p, a, n, w);
+}
+
 PadMap pad_map_rows(int blocks, int N, int Np, int cols) {
     PadMap m{};
     m.piece[0] = {0, 0, blocks, N, Np, cols, cols};

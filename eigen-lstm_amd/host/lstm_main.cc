@@ -7,7 +7,8 @@
 //        [--windows W] [--sample C] [--lr-warmup-windows X] [--save PREFIX] [--load PREFIX]
 //        [--eval-file F] [--stride K] [--forget-bias V] [--test-percent F] [--test-every SEC] [--log PREFIX]
 //        [--fast-math] [--step-kernels] [--stable-softmax] [--clip-norm X] [--optimizer adagrad|adam]
-//        [--adam-betas B1,B2] [--adam-eps E] [--weight-decay W] [--quiet]
+//        [--adam-betas B1,B2] [--adam-eps E] [--weight-decay W] [--average ema|uniform] [--average-decay D]
+//        [--average-every K] [--average-start W] [--quiet]
 //
 // stdout follows the reference: "Read N bytes (file)" (R/lstm.cc:398), the carriage-return progress
 // line (OV/lstm_eigen_opt/lstm.cc:320-331), the epoch summary (R/lstm.cc:284-291: GFLOP uses 2^30,
@@ -28,6 +29,12 @@
 // --optimizer adam trains with Adam / AdamW (lstm_hip_set_optimizer; --adam-betas, default 0.9,0.999, --adam-eps, default
 // 1e-8, --weight-decay, default 0) instead of Adagrad.  Its checkpoints carry PREFIX_adam_{m,v}_*.txt and
 // PREFIX_adam_steps.txt in place of the Adagrad memory; each rule loads only its own state.
+// --average ema|uniform keeps a running average of the weights (lstm_hip_set_averaging): --average-decay D (ema only, default
+// 0.999), --average-every K (every K-th update, default 1), --average-start W (averaging is turned on once W windows of
+// this run are done, default 0; a resumed average goes on at once).  Every held-out test then adds one line with the
+// averaged model's bits/char; --save also writes the average as a checkpoint of its own, PREFIX_avg_{W,U,b,Why,by}.txt (so
+// --load PREFIX_avg works in lstm_generate and lstm_compress), and PREFIX_avg_state.txt (kind, decay, every, seen, n);
+// --load PREFIX with the same --average kind resumes both, another kind or no --average ignores them.
 #include "../../include/lstm_hip.h"
 
 // referenced weakly: the program still links against a library without them and refuses --clip-norm / --optimizer adam there
@@ -36,6 +43,13 @@
 #pragma weak lstm_hip_set_optimizer
 #pragma weak lstm_hip_get_optimizer_steps
 #pragma weak lstm_hip_set_optimizer_steps
+// ... and --average
+#pragma weak lstm_hip_set_averaging
+#pragma weak lstm_hip_get_average
+#pragma weak lstm_hip_set_average
+#pragma weak lstm_hip_get_averaging_counts
+#pragma weak lstm_hip_set_averaging_counts
+#pragma weak lstm_hip_set_inference_source
 #include "checkpoint.h"
 #include "matrix_io.h"
 #include "rng.h"
@@ -81,6 +95,10 @@ struct Options {
     double clip_norm = 0.0;      // --clip-norm: 0 = off
     bool adam = false;           // --optimizer adam
     double beta1 = 0.9, beta2 = 0.999, adam_eps = 1e-8, weight_decay = 0.0;
+    int avg_kind = LSTM_HIP_AVG_OFF; // --average
+    double avg_decay = 0.0;          // --average-decay (ema: default 0.999)
+    int avg_every = 1;               // --average-every
+    long avg_start = 0;              // --average-start
 };
 
 [[noreturn]] void die(const std::string &m) {
@@ -167,10 +185,22 @@ double finite_number(const std::string &opt, const std::string &v) {
     return x;
 }
 
+long whole_number(const std::string &opt, const std::string &v, long least) {
+    char *end = nullptr;
+    errno = 0;
+    const long x = strtol(v.c_str(), &end, 10);
+    if (end == v.c_str() || *end != '\0' || errno != 0 || x < least)
+        die(opt + " needs a whole number >= " + std::to_string(least) + ", got " + v);
+    return x;
+}
+const char *avg_name(int kind) { return kind == LSTM_HIP_AVG_EMA ? "ema" : "uniform"; }
+
 Options parse(int argc, char **argv) {
     Options o;
     std::vector<std::string> pos;
     std::string adam_opt; // the last Adam option given (refused without --optimizer adam)
+    std::string avg_opt;  // the last averaging option given (refused without --average)
+    bool avg_decay_given = false;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto val = [&]() -> std::string {
@@ -229,6 +259,24 @@ Options parse(int argc, char **argv) {
             if (o.weight_decay < 0.0) die("--weight-decay needs a number >= 0");
             adam_opt = a;
         }
+        else if (a == "--average") {
+            const std::string v = val();
+            if (v != "ema" && v != "uniform") die("--average needs ema or uniform, got " + v);
+            o.avg_kind = v == "ema" ? LSTM_HIP_AVG_EMA : LSTM_HIP_AVG_UNIFORM;
+        } else if (a == "--average-decay") {
+            o.avg_decay = finite_number(a, val());
+            if (o.avg_decay < 0.0 || o.avg_decay >= 1.0) die("--average-decay needs 0 <= D < 1");
+            avg_decay_given = true;
+            avg_opt = a;
+        } else if (a == "--average-every") {
+            const long k = whole_number(a, val(), 1);
+            if (k > 2147483647L) die("--average-every is too large");
+            o.avg_every = (int)k;
+            avg_opt = a;
+        } else if (a == "--average-start") {
+            o.avg_start = whole_number(a, val(), 0);
+            avg_opt = a;
+        }
         else if (a == "--last-step-loss") o.last_step_loss = true;
         else if (a == "--last-step-loss-bits") o.last_step_bits = true;
         else if (a == "--quiet") o.quiet = true;
@@ -237,7 +285,8 @@ Options parse(int argc, char **argv) {
                    "            --lr-warmup-windows X --save PREFIX --load PREFIX --eval-file F --stride K --forget-bias V\n"
                    "            --test-percent F --test-every SEC --log PREFIX --last-step-loss --last-step-loss-bits --fast-math --step-kernels\n"
                    "            --stable-softmax --clip-norm X --optimizer adagrad|adam --adam-betas B1,B2 --adam-eps E\n"
-                   "            --weight-decay W --quiet]\n");
+                   "            --weight-decay W --average ema|uniform --average-decay D --average-every K --average-start W\n"
+                   "            --quiet]\n");
             exit(0);
         } else if (a.rfind("--", 0) == 0) die("unknown option " + a);
         else pos.push_back(a);
@@ -247,6 +296,15 @@ Options parse(int argc, char **argv) {
                    lstm_hip_set_optimizer_steps == nullptr))
         die("--optimizer adam: the loaded liblstm_hip has no lstm_hip_set_optimizer / lstm_hip_get_optimizer_steps / "
             "lstm_hip_set_optimizer_steps");
+    if (!avg_opt.empty() && o.avg_kind == LSTM_HIP_AVG_OFF) die(avg_opt + " needs --average ema|uniform");
+    if (avg_decay_given && o.avg_kind != LSTM_HIP_AVG_EMA) die("--average-decay needs --average ema");
+    if (o.avg_kind == LSTM_HIP_AVG_EMA && !avg_decay_given) o.avg_decay = 0.999;
+    if (o.avg_kind != LSTM_HIP_AVG_OFF &&
+        (lstm_hip_set_averaging == nullptr || lstm_hip_get_average == nullptr || lstm_hip_set_average == nullptr ||
+         lstm_hip_get_averaging_counts == nullptr || lstm_hip_set_averaging_counts == nullptr ||
+         lstm_hip_set_inference_source == nullptr))
+        die("--average: the loaded liblstm_hip has no lstm_hip_set_averaging / lstm_hip_get_average / lstm_hip_set_average / "
+            "lstm_hip_get_averaging_counts / lstm_hip_set_averaging_counts / lstm_hip_set_inference_source");
     if (pos.size() > 0) o.data = pos[0];
     if (pos.size() > 1) o.N = atoi(pos[1].c_str());
     if (pos.size() > 2) o.S = atoi(pos[2].c_str());
@@ -324,6 +382,25 @@ int run_rank(const Options &o, int rank, int up, int down) {
             if (lead) printf("Loaded Adagrad memory from %s_mem_{W,U,Why,b,by}.txt\n", o.load.c_str());
         }
     }
+    // the running average: resumed from a checkpoint of the same kind (on at once), else turned on after --average-start windows
+    bool avg_on = false;
+    if (o.avg_kind != LSTM_HIP_AVG_OFF && !o.load.empty()) {
+        std::ifstream f(o.load + "_avg_state.txt");
+        std::string key, kind;
+        double decay = 0.0;
+        long long every = 0, seen = -1, n = -1;
+        if (f && (f >> key >> kind >> key >> decay >> key >> every >> key >> seen >> key >> n) && kind == avg_name(o.avg_kind) &&
+            n >= 0 && n <= seen) {
+            std::vector<float> a(np, 0.0f);
+            if (n == 0 || load_params(o.load + "_avg", a, N, M)) {
+                CK(lstm_hip_set_averaging(h, o.avg_kind, o.avg_decay, o.avg_every));
+                if (n > 0) CK(lstm_hip_set_average(h, a.data()));
+                CK(lstm_hip_set_averaging_counts(h, seen, n));
+                avg_on = true;
+                if (lead) printf("Loaded the %s average (seen = %lld, n = %lld) from %s_avg_{W,U,Why,b,by}.txt\n", kind.c_str(), seen, n, o.load.c_str());
+            }
+        }
+    }
     CK(lstm_hip_set_text(h, data.data(), length));
 
     // cursors: deterministic stand-in for rand() % (length - S) + S (OV/lstm_eigen_opt/lstm.cc:140-144)
@@ -354,6 +431,18 @@ int run_rank(const Options &o, int rank, int up, int down) {
         if (evaldata.size() > 1) CK(lstm_hip_eval_bits(h, evaldata.data(), evaldata.size(), &test_error));
         printf("\nTrain error: %g, Test error: %g\n", train_error, test_error);
         if (evaldata.size() > 1) printf("Test error: %.5f bits/char (%s)\n", test_error, evalname.c_str());
+        if (avg_on && evaldata.size() > 1) { // the same text through the averaged model (the log keeps its columns)
+            int64_t seen = 0, n = 0;
+            CK(lstm_hip_get_averaging_counts(h, &seen, &n));
+            if (n >= 1) {
+                double avg_error = NAN;
+                CK(lstm_hip_set_inference_source(h, LSTM_HIP_SRC_AVERAGE));
+                CK(lstm_hip_eval_bits(h, evaldata.data(), evaldata.size(), &avg_error));
+                CK(lstm_hip_set_inference_source(h, LSTM_HIP_SRC_PARAMS));
+                printf("Test error of the %s average (n = %lld): %.5f bits/char (%s)\n", avg_name(o.avg_kind), (long long)n, avg_error,
+                       evalname.c_str());
+            }
+        }
         if (!o.log.empty()) {
             results.push_back({(double)results.size(), test_time, train_error, test_error, gflops});
             printf("%6g %6g %6g %6g %6g\n\n", results.back()[0], test_time, train_error, test_error, gflops);
@@ -398,6 +487,13 @@ int run_rank(const Options &o, int rank, int up, int down) {
             if (done_windows < o.lr_warmup) {
                 lr = 0.0;
                 chunk = std::min<long>(chunk, o.lr_warmup - done_windows);
+            }
+            if (o.avg_kind != LSTM_HIP_AVG_OFF && !avg_on) { // (every rank: the same rule on the same parameters)
+                if (done_windows >= o.avg_start) {
+                    CK(lstm_hip_set_averaging(h, o.avg_kind, o.avg_decay, o.avg_every));
+                    avg_on = true;
+                } else
+                    chunk = std::min<long>(chunk, o.avg_start - done_windows);
             }
             losses.resize(chunk);
             CK(lstm_hip_train_windows(h, chunk, lr, losses.data(), nullptr));
@@ -483,6 +579,22 @@ int run_rank(const Options &o, int rank, int up, int down) {
                     if (!(f << (long long)t << "\n")) die("cannot write " + o.save + "_adam_steps.txt");
                 } else
                     save_params(o.save + "_mem", mem, N, M, 9);
+                if (avg_on) { // the average as a parameter checkpoint of its own (once it holds one) and its state
+                    int64_t seen = 0, n = 0;
+                    CK(lstm_hip_get_averaging_counts(h, &seen, &n));
+                    if (n >= 1) {
+                        CK(lstm_hip_get_average(h, mem.data()));
+                        save_params(o.save + "_avg", mem, N, M, 9);
+                    }
+                    std::ofstream f(o.save + "_avg_state.txt");
+                    char decay[40];
+                    snprintf(decay, sizeof(decay), "%.17g", o.avg_decay);
+                    if (!(f << "kind " << avg_name(o.avg_kind) << "\ndecay " << decay << "\nevery " << o.avg_every << "\nseen "
+                            << (long long)seen << "\nn " << (long long)n << "\n"))
+                        die("cannot write " + o.save + "_avg_state.txt");
+                    printf("Saved the %s average (seen = %lld, n = %lld) to %s_avg_{W,U,Why,b,by}.txt\n", avg_name(o.avg_kind),
+                           (long long)seen, (long long)n, o.save.c_str());
+                }
                 std::vector<uint64_t> all(o.B); // every stream has advanced by the same number of bytes
                 const uint64_t span = (uint64_t)(length - S), adv = (uint64_t)done_windows * (uint64_t)o.stride;
                 for (int b = 0; b < o.B; b++) all[b] = (uint64_t)S + ((start_all[b] - S) + adv) % span;

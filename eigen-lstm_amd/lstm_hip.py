@@ -32,6 +32,8 @@ VOCAB = 256
 P_PARAMS, P_GRADS, P_MEM = 0, 1, 2
 P_ADAM_V = 3  # Adam's second moment (P_MEM is its first moment on an Adam handle)
 OPT_ADAGRAD, OPT_ADAM = 0, 1  # update rules of lstm_hip_set_optimizer (include/lstm_hip.h)
+AVG_OFF, AVG_EMA, AVG_UNIFORM = 0, 1, 2  # kinds of lstm_hip_set_averaging
+SRC_PARAMS, SRC_AVERAGE = 0, 1  # what the inference calls read (lstm_hip_set_inference_source)
 
 
 class LstmHipError(RuntimeError):
@@ -87,6 +89,8 @@ SYMBOLS = [
     "lstm_hip_adaptive_version", "lstm_hip_adaptive_blocks", "lstm_hip_encode_adaptive", "lstm_hip_decode_adaptive",
     "lstm_hip_plan_identity", "lstm_hip_beam_search", "lstm_hip_generate_constrained", "lstm_hip_dfa_utf8",
     "lstm_hip_dfa_restrict", "lstm_hip_score", "lstm_hip_beam_search_constrained",
+    "lstm_hip_set_averaging", "lstm_hip_get_average", "lstm_hip_set_average", "lstm_hip_get_averaging_counts",
+    "lstm_hip_set_averaging_counts", "lstm_hip_set_inference_source",
 ]
 
 
@@ -333,6 +337,37 @@ class Lstm:
 
     def set_optimizer_steps(self, t):
         _chk(self.lib.lstm_hip_set_optimizer_steps(self._h, C.c_int64(t)))
+
+    # ---- the running weight average and inference from it (lstm_hip_set_averaging) ---------------
+    def set_averaging(self, kind, decay=0.0, every=1):
+        """AVG_OFF, AVG_EMA (0 <= decay < 1) or AVG_UNIFORM (decay 0): after every `every`-th update the average takes the
+        new parameters, a = p at its first update and a + w * (p - a) after it (w = 1 - decay, or 1 / n).  A new kind
+        zeroes the average and its counters; the same kind again keeps them."""
+        _chk(self.lib.lstm_hip_set_averaging(self._h, C.c_int32(kind), C.c_double(decay), C.c_int32(every)))
+
+    def get_average(self):
+        out = np.empty(self.np, np.float32)
+        _chk(self.lib.lstm_hip_get_average(self._h, _ptr(out)))
+        return out
+
+    def set_average(self, block):
+        block = _f32(block)
+        assert block.size == self.np, (block.size, self.np)
+        _chk(self.lib.lstm_hip_set_average(self._h, _ptr(block)))
+
+    def averaging_counts(self):
+        """(seen, n): updates launched with averaging on, and how many of them the average has taken."""
+        seen, n = C.c_int64(), C.c_int64()
+        _chk(self.lib.lstm_hip_get_averaging_counts(self._h, C.byref(seen), C.byref(n)))
+        return seen.value, n.value
+
+    def set_averaging_counts(self, seen, n):
+        _chk(self.lib.lstm_hip_set_averaging_counts(self._h, C.c_int64(seen), C.c_int64(n)))
+
+    def set_inference_source(self, source):
+        """SRC_PARAMS (the default) or SRC_AVERAGE: what eval_bits, sample, generate, beam_search, score, encode and decode
+        read.  Training never reads it; the adaptive coders refuse SRC_AVERAGE."""
+        _chk(self.lib.lstm_hip_set_inference_source(self._h, C.c_int32(source)))
 
     # ---- data-parallel -----------------------------------------------------------------------
     def comm_init(self, unique_id, nranks, rank):

@@ -177,6 +177,54 @@ int lstm_hip_set_optimizer(lstm_hip_t *h, int32_t kind, double beta1, double bet
 int lstm_hip_get_optimizer_steps(lstm_hip_t *h, int64_t *steps);
 int lstm_hip_set_optimizer_steps(lstm_hip_t *h, int64_t steps);
 
+/* ---- a running average of the weights over the trajectory, and inference from it
+ *   LSTM_HIP_AVG_OFF      the default: no block, no counters, no launch; decay must be 0
+ *   LSTM_HIP_AVG_EMA      exponential moving average; needs 0 <= decay < 1, finite
+ *   LSTM_HIP_AVG_UNIFORM  the uniform running mean of the averaged iterates (SWA); decay must be 0
+ *   every >= 1 for all three.  Anything else, an unknown kind and NaN included, is LSTM_HIP_EINVAL; the message says which
+ *   number, and the handle stays usable.
+ * Which updates count: every update the handle launches, the rule of the optimizer step counter -- lstm_hip_adagrad, each
+ * window of lstm_hip_train_windows, each train pass of the adaptive coders; lr = 0 updates too.  With averaging on, after
+ * each update seen += 1, and the update is DUE when seen % every == 0.  At a due update n += 1 and the average block a is
+ * updated from the parameters p AFTER that update, per element of the whole flat block [W|U|b|Why|by]:
+ *     n == 1   a = p                   an exact copy, no arithmetic: neither kind needs a bias correction
+ *     n  > 1   a = a + w * (p - a)     fp32, three separately rounded operations, no fused multiply-add
+ *              EMA: w = (float)(1.0 - decay);  UNIFORM: w = (float)(1.0 / (double)n);  both computed in double on the host
+ * (NumPy's a + w * (p - a) on float32 arrays is bit for bit the same.)  Non-finite values propagate as they are.  The average
+ * is written by one launch of its own on the handle's stream, after the update launch and only at due updates: nothing is
+ * read back, nothing waits, and how lstm_hip_train_windows calls are cut into chunks does not show.  A handle that never
+ * turns averaging on makes the launches it made before this call existed.  With a communicator every rank applies the same
+ * rule to the same parameters; nothing is exchanged.  A LSTM_HIP_PAD_HIDDEN handle keeps the average at the internal width
+ * with zero padding (0 in p, and written as 0 by lstm_hip_set_average, as lstm_hip_set_params does).
+ * State: a new kind allocates the block if needed, zeroes it, sets seen = n = 0 and puts the inference source back to
+ * LSTM_HIP_SRC_PARAMS; the same kind again keeps the block and both counters and takes the new decay and every;
+ * LSTM_HIP_AVG_OFF drops averaging.  Per handle, may change between calls, not part of the engine plan.
+ * lstm_hip_get_average / lstm_hip_set_average move the block as lstm_hip_get_params / lstm_hip_set_params move theirs
+ * (logical-N flat block; with n == 0 get returns the zero block).  The average is not a fifth `which` block: which = 4 stays
+ * LSTM_HIP_EINVAL there.  lstm_hip_set_averaging_counts needs 0 <= n <= seen (else LSTM_HIP_EINVAL; n = 0 while the inference
+ * source is the average: LSTM_HIP_ESTATE); it exists for resuming, in this order: lstm_hip_set_averaging,
+ * lstm_hip_set_average, lstm_hip_set_averaging_counts.  These four answer LSTM_HIP_ESTATE on a handle without averaging,
+ * LSTM_HIP_EINVAL for a null pointer. */
+#define LSTM_HIP_AVG_OFF 0
+#define LSTM_HIP_AVG_EMA 1
+#define LSTM_HIP_AVG_UNIFORM 2
+int lstm_hip_set_averaging(lstm_hip_t *h, int32_t kind, double decay, int32_t every);
+int lstm_hip_get_average(lstm_hip_t *h, float *host_block);        /* logical-N flat block, as get_params */
+int lstm_hip_set_average(lstm_hip_t *h, const float *host_block);
+int lstm_hip_get_averaging_counts(lstm_hip_t *h, int64_t *seen, int64_t *n);
+int lstm_hip_set_averaging_counts(lstm_hip_t *h, int64_t seen, int64_t n);
+/* which fp32 block lstm_hip_eval_bits, lstm_hip_sample, lstm_hip_generate*, lstm_hip_beam_search*, lstm_hip_score,
+ * lstm_hip_encode and lstm_hip_decode read: the parameters (the default) or the average.  With LSTM_HIP_SRC_AVERAGE they take
+ * W, b, Why and by from the average and pack their image of U from it, so every result is bit for bit what a second handle
+ * of the same configuration gives after lstm_hip_set_params(0, the average).  Training never reads the source: parameters,
+ * optimizer state and losses are those of a handle without it.  LSTM_HIP_SRC_AVERAGE is LSTM_HIP_ESTATE while averaging is
+ * off or n == 0 (a zero model is never what the caller meant); the adaptive coders answer LSTM_HIP_ESTATE while the source
+ * is the average (they code with the model they train); an unknown source is LSTM_HIP_EINVAL.  The source stays until it is
+ * set again, averaging is turned off or a new kind is chosen. */
+#define LSTM_HIP_SRC_PARAMS 0
+#define LSTM_HIP_SRC_AVERAGE 1
+int lstm_hip_set_inference_source(lstm_hip_t *h, int32_t source);
+
 /* ---- data-parallel exchange (new; the reference is single-device).  One SUM all-reduce of the
  *      flat gradient block per window over RCCL; every rank then applies the identical Adagrad step.
  *      With LSTM_HIP_PAD_HIDDEN the payload is the padded block (Np from N and the flags, so every
