@@ -386,8 +386,9 @@ struct GenHeadArgs {
     const uint16_t *ccount;     // [states] allowed bytes of each state (>= 1 for every state a stream can reach)
     int32_t *cstate;            // [streams] the state of every stream: after its prompt at the start, then after each drawn byte
 };
-void gen_head(const GenHeadArgs &a, long long t, bool stable, hipStream_t st); // stable: LSTM_HIP_STABLE_SOFTMAX
-int gen_head_status();          // 0, or the HIP error of a refused LDS request (sticky until read)
+// stable: LSTM_HIP_STABLE_SOFTMAX.  hipSuccess, or the HIP error of a refused LDS request with nothing launched (the FILTER
+// instantiations only; beam_head and score_head likewise)
+hipError_t gen_head(const GenHeadArgs &a, long long t, bool stable, hipStream_t st);
 int gen_head_group(int N, int streams); // streams per workgroup of gen_head
 
 // ---- beam search (lstm_hip_beam_search): per step beam_head on the state after t inputs, then
@@ -413,8 +414,7 @@ struct BeamHeadArgs {
     const uint32_t *frows;      // [count][fwords] bit q of row R: an accepted end can be reached from q with R more bytes
     int fwords;                 // words of one row: (states + 31) / 32
 };
-void beam_head(const BeamHeadArgs &a, long long t, hipStream_t st);
-int beam_head_status();         // 0, or the HIP error of a refused LDS request (sticky until read)
+hipError_t beam_head(const BeamHeadArgs &a, long long t, hipStream_t st);
 // out[(s * W + r) * count + i]: byte i of final slot r of stream s, walked back through the tables; 0 from len on
 void beam_backtrack(const uint8_t *trace_parent, const uint8_t *trace_byte, const int32_t *len, uint8_t *out, int streams,
                     int W, int count, hipStream_t st);
@@ -469,8 +469,7 @@ struct ScoreHeadArgs {
     const uint16_t *qpos;       // [total] the automaton state each byte stands in (walked by the host); with ctab
     int N, streams, first, top_n;
 };
-void score_head(const ScoreHeadArgs &a, long long t, bool stable, hipStream_t st); // stable: LSTM_HIP_STABLE_SOFTMAX
-int score_head_status();        // 0, or the HIP error of a refused LDS request (sticky until read)
+hipError_t score_head(const ScoreHeadArgs &a, long long t, bool stable, hipStream_t st); // stable: LSTM_HIP_STABLE_SOFTMAX
 
 // ---- adaptive coding (lstm_hip_encode_adaptive / lstm_hip_decode_adaptive): the training window of
 // block k, built from the coder's device text buffer.  With L = S - 1 and e_j = byte j of a stream (empty for j < 0), row t of

@@ -2005,13 +2005,19 @@ int gen_head_group(int N, int streams) {
     while (sb < 16 && streams >= 256 * 2 * sb && (size_t)2 * sb * N <= 16384) sb *= 2;
     return sb;
 }
-static thread_local hipError_t g_gen_head_error = hipSuccess;
-int gen_head_status() {
-    const hipError_t e = g_gen_head_error;
-    g_gen_head_error = hipSuccess;
-    return (int)e;
+// The heads' dynamic LDS, up to 64 KB beside static LDS of up to 33 KB: above FLOOR (what needs no request) the size is requested
+// of the kernel first; `granted` remembers the largest request that went through (one per kernel instantiation, per process).
+// A refused request is returned and nothing is launched: an error, not a launch.
+template <auto KERNEL, size_t FLOOR> static hipError_t grant_lds(size_t lds) {
+    static size_t granted = FLOOR;
+    if (lds > granted) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+        granted = lds;
+    }
+    return hipSuccess;
 }
-template <bool STABLE> static void gen_head_launch(const GenHeadArgs &a, long long t, hipStream_t st) {
+template <bool STABLE> static hipError_t gen_head_launch(const GenHeadArgs &a, long long t, hipStream_t st) {
     const int sb = gen_head_group(a.N, a.streams);
     const size_t lds = (size_t)sb * a.N * sizeof(float);
     const dim3 grid((a.streams + sb - 1) / sb);
@@ -2021,22 +2027,12 @@ template <bool STABLE> static void gen_head_launch(const GenHeadArgs &a, long lo
             (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_gen_head<SB, STABLE, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
         hipLaunchKernelGGL((k_gen_head<SB, STABLE, false>), grid, dim3(256), lds, st, a, t);                               \
         break;
-    // FILTER: static LDS is up to 33 KB (ps, sorted), dynamic up to 64 KB; a refused request is an error, not a launch
+    // FILTER: static LDS is up to 33 KB (ps, sorted), dynamic up to 64 KB
 #define GEN_HEAD_FILTER_CASE(SB, CONSTRAIN)                                                                                 \
-    case SB: {                                                                                                              \
-        static size_t granted = 32768;                                                                                      \
-        if (lds > granted) {                                                                                                \
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_gen_head<SB, STABLE, true, CONSTRAIN>), \
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                 \
-            if (e != hipSuccess) {                                                                                          \
-                g_gen_head_error = e;                                                                                       \
-                return;                                                                                                     \
-            }                                                                                                               \
-            granted = lds;                                                                                                  \
-        }                                                                                                                   \
+    case SB:                                                                                                                \
+        if (const hipError_t e = grant_lds<k_gen_head<SB, STABLE, true, CONSTRAIN>, 32768>(lds)) return e;                  \
         hipLaunchKernelGGL((k_gen_head<SB, STABLE, true, CONSTRAIN>), grid, dim3(256), lds, st, a, t);                      \
-        break;                                                                                                              \
-    }
+        break;
     if (a.ctab) switch (sb) { // (the caller sets a.end too)
             GEN_HEAD_FILTER_CASE(1, true)
             GEN_HEAD_FILTER_CASE(2, true)
@@ -2060,10 +2056,10 @@ template <bool STABLE> static void gen_head_launch(const GenHeadArgs &a, long lo
         }
 #undef GEN_HEAD_CASE
 #undef GEN_HEAD_FILTER_CASE
+    return hipSuccess;
 }
-void gen_head(const GenHeadArgs &a, long long t, bool stable, hipStream_t st) {
-    if (stable) gen_head_launch<true>(a, t, st);
-    else gen_head_launch<false>(a, t, st);
+hipError_t gen_head(const GenHeadArgs &a, long long t, bool stable, hipStream_t st) {
+    return stable ? gen_head_launch<true>(a, t, st) : gen_head_launch<false>(a, t, st);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2284,38 +2280,24 @@ __global__ __launch_bounds__(256) void k_beam_head(BeamHeadArgs a, long long t) 
         a.Cr[(c0 + r) * N + k] = a.C[(c0 + p) * N + k];
     }
 }
-static thread_local hipError_t g_beam_head_error = hipSuccess;
-int beam_head_status() {
-    const hipError_t e = g_beam_head_error;
-    g_beam_head_error = hipSuccess;
-    return (int)e;
-}
-template <int WP, bool EXACT, bool CONSTRAIN> static void beam_head_launch(const BeamHeadArgs &a, long long t, hipStream_t st) {
-    // static LDS is up to 33 KB (ps), dynamic up to 64 KB; a refused request is an error, not a launch
-    static size_t granted = 0; // (one per instantiation)
+template <int WP, bool EXACT, bool CONSTRAIN> static hipError_t beam_head_launch(const BeamHeadArgs &a, long long t, hipStream_t st) {
+    // static LDS is up to 33 KB (ps), dynamic up to 64 KB
     const size_t lds = (size_t)a.W * a.N * sizeof(float);
-    if (lds > granted) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_beam_head<WP, EXACT, CONSTRAIN>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) {
-            g_beam_head_error = e;
-            return;
-        }
-        granted = lds;
-    }
+    if (const hipError_t e = grant_lds<k_beam_head<WP, EXACT, CONSTRAIN>, 0>(lds)) return e;
     hipLaunchKernelGGL((k_beam_head<WP, EXACT, CONSTRAIN>), dim3(a.streams), dim3(256), lds, st, a, t);
+    return hipSuccess;
 }
-void beam_head(const BeamHeadArgs &a, long long t, hipStream_t st) {
+hipError_t beam_head(const BeamHeadArgs &a, long long t, hipStream_t st) {
     int wp = 1;
     while (wp < a.W) wp *= 2;
 #define BEAM_HEAD_CASE(WP)                                                                                                  \
     case WP:                                                                                                                \
         if (a.ctab) {                                                                                                       \
-            if (a.W == WP) beam_head_launch<WP, true, true>(a, t, st);                                                      \
-            else beam_head_launch<WP, false, true>(a, t, st);                                                               \
-        } else if (a.W == WP) beam_head_launch<WP, true, false>(a, t, st);                                                  \
-        else beam_head_launch<WP, false, false>(a, t, st);                                                                  \
-        break;
+            if (a.W == WP) return beam_head_launch<WP, true, true>(a, t, st);                                               \
+            return beam_head_launch<WP, false, true>(a, t, st);                                                             \
+        }                                                                                                                   \
+        if (a.W == WP) return beam_head_launch<WP, true, false>(a, t, st);                                                  \
+        return beam_head_launch<WP, false, false>(a, t, st);
     switch (wp) {
         BEAM_HEAD_CASE(1)
         BEAM_HEAD_CASE(2)
@@ -2325,6 +2307,7 @@ void beam_head(const BeamHeadArgs &a, long long t, hipStream_t st) {
         BEAM_HEAD_CASE(32)
     }
 #undef BEAM_HEAD_CASE
+    return hipSuccess; // (W outside [1, 32]: the caller has refused it)
 }
 // one thread per hypothesis: final slot r of stream s walked back through the tables.  Finished slots only pass
 // through, so the selections that gave the hypothesis a byte are its first len ones.
@@ -2708,32 +2691,16 @@ __global__ __launch_bounds__(256) void k_score_head(ScoreHeadArgs a, long long t
             }
     }
 }
-static thread_local hipError_t g_score_head_error = hipSuccess;
-int score_head_status() {
-    const hipError_t e = g_score_head_error;
-    g_score_head_error = hipSuccess;
-    return (int)e;
-}
-template <bool STABLE, bool DETAIL, bool CONSTRAIN> static void score_head_launch(const ScoreHeadArgs &a, long long t, hipStream_t st) {
+template <bool STABLE, bool DETAIL, bool CONSTRAIN> static hipError_t score_head_launch(const ScoreHeadArgs &a, long long t, hipStream_t st) {
     const int sb = gen_head_group(a.N, a.streams);
     const size_t lds = (size_t)sb * a.N * sizeof(float);
     const dim3 grid((a.streams + sb - 1) / sb);
-    // static LDS is up to 16 KB (ps), dynamic up to 64 KB; a refused request is an error, not a launch
+    // static LDS is up to 16 KB (ps), dynamic up to 64 KB
 #define SCORE_HEAD_CASE(SB)                                                                                                 \
-    case SB: {                                                                                                              \
-        static size_t granted = 32768;                                                                                      \
-        if (lds > granted) {                                                                                                \
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_score_head<SB, STABLE, DETAIL, CONSTRAIN>), \
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                 \
-            if (e != hipSuccess) {                                                                                          \
-                g_score_head_error = e;                                                                                     \
-                return;                                                                                                     \
-            }                                                                                                               \
-            granted = lds;                                                                                                  \
-        }                                                                                                                   \
+    case SB:                                                                                                                \
+        if (const hipError_t e = grant_lds<k_score_head<SB, STABLE, DETAIL, CONSTRAIN>, 32768>(lds)) return e;              \
         hipLaunchKernelGGL((k_score_head<SB, STABLE, DETAIL, CONSTRAIN>), grid, dim3(256), lds, st, a, t);                  \
-        break;                                                                                                              \
-    }
+        break;
     switch (sb) {
         SCORE_HEAD_CASE(1)
         SCORE_HEAD_CASE(2)
@@ -2742,8 +2709,9 @@ template <bool STABLE, bool DETAIL, bool CONSTRAIN> static void score_head_launc
         SCORE_HEAD_CASE(16)
     }
 #undef SCORE_HEAD_CASE
+    return hipSuccess;
 }
-void score_head(const ScoreHeadArgs &a, long long t, bool stable, hipStream_t st) {
+hipError_t score_head(const ScoreHeadArgs &a, long long t, bool stable, hipStream_t st) {
     const bool detail = a.rank || a.top_byte || a.top_bits, con = a.ctab != nullptr;
 #define SCORE_HEAD_GO(S_, D_, C_)                                                                                           \
     if (stable == S_ && detail == D_ && con == C_) return score_head_launch<S_, D_, C_>(a, t, st);
@@ -2756,6 +2724,7 @@ void score_head(const ScoreHeadArgs &a, long long t, bool stable, hipStream_t st
     SCORE_HEAD_GO(true, true, false)
     SCORE_HEAD_GO(true, true, true)
 #undef SCORE_HEAD_GO
+    return hipSuccess; // (not reached: the eight cases are all there are)
 }
 // ------------------------------------------------------------------------------------------------
 // block_window: the training window of block k of the adaptive coder (kernels.h), straight from the

@@ -1590,8 +1590,13 @@ int lstm_hip_sample(lstm_hip_t *h, float *h0, float *c0, const double *u, int32_
     return 0;
 }
 
+} // extern "C"
+
+// ---- what generate, beam search, score and the coders share around their loops (the loops themselves differ and stay apart)
+namespace {
+
 // the generator's and the coder's working memory: one allocation on the handle, grown to the largest call
-static int reserve_gen_scratch(lstm_hip_t *h, size_t bytes) {
+int reserve_gen_scratch(lstm_hip_t *h, size_t bytes) {
     if (bytes > h->gen_scratch_bytes) { // (kept between calls: hipFree waits for the whole device)
         HIP_TRY(hipStreamSynchronize(h->st));
         if (h->gen_scratch) HIP_TRY(hipFree(h->gen_scratch));
@@ -1602,6 +1607,130 @@ static int reserve_gen_scratch(lstm_hip_t *h, size_t bytes) {
     }
     return 0;
 }
+
+// A call's layout of that memory: 256-byte aligned pieces in the order they are named.  Each piece is named once: the pointer
+// to fill, its element count, and whether it is there at all.  An absent piece takes no room and leaves its pointer null (the
+// kernels test some of them); a present one gets an address even when it has no elements.  commit reserves the sum and fills
+// the pointers.
+class Scratch {
+    struct Piece {
+        void *slot; // the caller's T *
+        size_t at;
+    };
+    std::vector<Piece> pieces;
+    size_t bytes = 0;
+
+  public:
+    template <class T> Scratch &piece(T *&p, size_t count, bool present = true) {
+        p = nullptr;
+        if (present) {
+            pieces.push_back({&p, bytes});
+            bytes += (count * sizeof(T) + 255) / 256 * 256;
+        }
+        return *this;
+    }
+    int commit(lstm_hip_t *h) {
+        if (int rc = reserve_gen_scratch(h, bytes)) return rc;
+        for (const Piece &q : pieces) {
+            char *at = h->gen_scratch + q.at;
+            memcpy(q.slot, &at, sizeof(at));
+        }
+        return 0;
+    }
+};
+
+// The start state of `cols` columns, host h0 / c0 (either may be null: zeros) to the device's H / Cs.  A padded handle takes
+// the logical-width columns through `stage` ([2][cols * N_log], a piece of the call's scratch) and pad_copy: padding rows zero.
+int upload_states(lstm_hip_t *h, const float *h0, const float *c0, float *H, float *Cs, float *stage, int cols) {
+    const size_t n = (size_t)h->cfg.N * cols, nl = (size_t)h->N_log * cols;
+    const PadMap map = pad_map_rows(1, h->N_log, h->cfg.N, cols);
+    for (int k = 0; k < 2; k++) {
+        const float *src = k ? c0 : h0;
+        float *dst = k ? Cs : H;
+        if (!src) HIP_TRY(hipMemsetAsync(dst, 0, sizeof(float) * n, h->st));
+        else if (h->padded()) {
+            HIP_TRY(hipMemcpyAsync(stage + k * nl, src, sizeof(float) * nl, hipMemcpyHostToDevice, h->st));
+            pad_copy(stage + k * nl, dst, map, true, h->st);
+            if (int rc = pad_status()) return rc;
+        } else
+            HIP_TRY(hipMemcpyAsync(dst, src, sizeof(float) * n, hipMemcpyHostToDevice, h->st));
+    }
+    return 0;
+}
+// the same in reverse: the device's H / Cs to those of h_out / c_out that are wanted
+int download_states(lstm_hip_t *h, float *h_out, float *c_out, const float *H, const float *Cs, float *stage, int cols) {
+    const size_t n = (size_t)h->cfg.N * cols, nl = (size_t)h->N_log * cols;
+    const PadMap map = pad_map_rows(1, h->N_log, h->cfg.N, cols);
+    for (int k = 0; k < 2; k++) {
+        float *dst = k ? c_out : h_out;
+        const float *src = k ? Cs : H;
+        if (!dst) continue;
+        if (h->padded()) {
+            pad_copy(src, stage + k * nl, map, false, h->st);
+            if (int rc = pad_status()) return rc;
+            HIP_TRY(hipMemcpyAsync(dst, stage + k * nl, sizeof(float) * nl, hipMemcpyDeviceToHost, h->st));
+        } else
+            HIP_TRY(hipMemcpyAsync(dst, src, sizeof(float) * n, hipMemcpyDeviceToHost, h->st));
+    }
+    return 0;
+}
+
+// offsets of `streams` streams: off[0] == 0, never decreasing
+int check_offsets(const char *what, const char *name, const uint64_t *off, int32_t streams) {
+    if (!off) return fail(LSTM_HIP_EINVAL, "%s: null %s", what, name);
+    if (off[0] != 0) return fail(LSTM_HIP_EINVAL, "%s: %s[0] must be 0 (got %llu)", what, name, (unsigned long long)off[0]);
+    for (int s = 0; s < streams; s++)
+        if (off[s + 1] < off[s])
+            return fail(LSTM_HIP_EINVAL, "%s: %s decreases at stream %d (%llu < %llu)", what, name, s,
+                        (unsigned long long)off[s + 1], (unsigned long long)off[s]);
+    return 0;
+}
+uint64_t longest(const uint64_t *off, int32_t streams) { // the longest stream of checked offsets
+    uint64_t len = 0;
+    for (int s = 0; s < streams; s++) len = std::max<uint64_t>(len, off[s + 1] - off[s]);
+    return len;
+}
+
+// Every stream's bytes walked through a checked byte automaton, from cstate[s] to the state after them.  A forbidden byte is
+// refused (`noun`: what the caller calls a byte); qpos, where given, takes the state each byte stands in.
+int walk_constraint(const char *what, const char *noun, const lstm_hip_constraint *con, int32_t streams, const uint8_t *bytes,
+                    const uint64_t *off, std::vector<int32_t> &cstate, uint16_t *qpos) {
+    for (int s = 0; s < streams; s++)
+        for (uint64_t j = off[s]; j < off[s + 1]; j++) {
+            const uint16_t v = con->next[(size_t)cstate[s] * 256 + bytes[j]];
+            if (v == 0xFFFF)
+                return fail(LSTM_HIP_EINVAL, "%s: stream %d: %s 0x%02x at offset %llu is forbidden in state %d", what, s, noun,
+                            (unsigned)bytes[j], (unsigned long long)(j - off[s]), cstate[s]);
+            if (qpos) qpos[j] = (uint16_t)cstate[s];
+            cstate[s] = v;
+        }
+    return 0;
+}
+
+// the model an inference call reads: the five pieces of infer_block(h), resolved once per call
+struct Model {
+    const float *W, *U, *b, *Why, *by;
+};
+Model model_of(const lstm_hip_ctx *h) {
+    const float *P = infer_block(h);
+    return {P + h->pl.W, P + h->pl.U, P + h->pl.b, P + h->pl.Why, P + h->pl.by};
+}
+// one k_fwd_step over `cols` columns: the inputs xi and the state (Hf, Cf) to the state (Ht, Ct)
+int step_columns(lstm_hip_t *h, const Model &m, const float4 *Ufwd, const float *Hf, const float *Cf, float *Ht, float *Ct,
+                 float *G, const int32_t *xi, int cols) {
+    const bool fast = (h->cfg.flags & LSTM_HIP_FAST_MATH) != 0;
+    RUN(K_FWD_STEP, fwd_step(Ufwd, m.W, m.b, Hf, Cf, Ht, Ct, G, xi, h->cfg.N, cols, fast, h->st));
+    return 0;
+}
+
+// a head's launcher that returned an error has launched nothing: its request for dynamic LDS was refused
+int head_refused(const char *what, const char *head, hipError_t e) {
+    return fail(LSTM_HIP_EHIP, "%s: the LDS request of %s was refused: %s", what, head, hipGetErrorString(e));
+}
+
+} // namespace
+
+extern "C" {
 
 // Batched, prompted generation and per-text scoring (include/lstm_hip.h).  All streams advance together: per step one
 // gen_head launch (logits, prompt bits, the next input of every stream, final states) and one k_fwd_step over all streams,
@@ -1745,18 +1874,12 @@ int lstm_hip_generate_constrained(lstm_hip_t *h, int32_t streams, const uint8_t 
     if (count > 0 && temperature > 0.0 && !u) return fail(LSTM_HIP_EINVAL, "generate: draws u are needed unless temperature is 0");
     if (count > 0 && !out) return fail(LSTM_HIP_EINVAL, "generate: null out with count > 0");
     if (prompts && !prompt_off) return fail(LSTM_HIP_EINVAL, "generate: prompts without prompt_off");
-    uint64_t max_len = 0;
     if (prompt_off) {
-        if (prompt_off[0] != 0) return fail(LSTM_HIP_EINVAL, "generate: prompt_off[0] must be 0 (got %llu)", (unsigned long long)prompt_off[0]);
-        for (int s = 0; s < streams; s++) {
-            if (prompt_off[s + 1] < prompt_off[s])
-                return fail(LSTM_HIP_EINVAL, "generate: prompt_off decreases at stream %d (%llu < %llu)", s,
-                            (unsigned long long)prompt_off[s + 1], (unsigned long long)prompt_off[s]);
-            max_len = std::max<uint64_t>(max_len, prompt_off[s + 1] - prompt_off[s]);
-        }
+        if (int rc = check_offsets("generate", "prompt_off", prompt_off, streams)) return rc;
         if (prompt_off[streams] > 0 && !prompts) return fail(LSTM_HIP_EINVAL, "generate: prompt_off without prompts");
     }
-    const int N = h->cfg.N, Nl = h->N_log;
+    const uint64_t max_len = prompt_off ? longest(prompt_off, streams) : 0;
+    const int N = h->cfg.N;
     if (N > 16384) return fail(LSTM_HIP_EINVAL, "generate: hidden width %d above 16384", N);
     // the constraint: the table is checked, then every stream's state walks its prompt
     std::vector<int32_t> cstate; // [streams] the state after each prompt
@@ -1766,67 +1889,32 @@ int lstm_hip_generate_constrained(lstm_hip_t *h, int32_t streams, const uint8_t 
     if (con) {
         if (int rc = check_constraint("generate", con, streams, start_state, cstate, ccount)) return rc;
         if (prompt_off)
-            for (int s = 0; s < streams; s++)
-                for (uint64_t j = prompt_off[s]; j < prompt_off[s + 1]; j++) {
-                    const uint16_t v = con->next[(size_t)cstate[s] * 256 + prompts[j]];
-                    if (v == 0xFFFF)
-                        return fail(LSTM_HIP_EINVAL, "generate: stream %d: prompt byte 0x%02x at offset %llu is forbidden in state %d", s,
-                                    (unsigned)prompts[j], (unsigned long long)(j - prompt_off[s]), cstate[s]);
-                    cstate[s] = v;
-                }
+            if (int rc = walk_constraint("generate", "prompt byte", con, streams, prompts, prompt_off, cstate, nullptr)) return rc;
     }
     const uint64_t total = prompt_off ? prompt_off[streams] : 0;
-    const size_t n = (size_t)N * streams, nl = (size_t)Nl * streams, nd = (size_t)count * streams;
+    const size_t n = (size_t)N * streams, nl = (size_t)h->N_log * streams, nd = (size_t)count * streams;
     const bool keep = h_out || c_out;
     const bool top_k_on = opt->top_k >= 1 && opt->top_k <= 255, nucleus = opt->top_p < 1.0;
     const bool controls = top_k_on || nucleus || opt->stop_byte >= 0 || kept || con; // gen_head's FILTER instantiation
 
-    // one scratch allocation, 256-byte aligned pieces
-    size_t bytes = 0;
-    auto piece = [&](size_t b) {
-        const size_t o = bytes;
-        bytes += (b + 255) / 256 * 256;
-        return o;
-    };
-    const size_t o_U = piece(sizeof(float) * 4 * (size_t)N * N), o_H = piece(sizeof(float) * 2 * n), o_C = piece(sizeof(float) * 2 * n),
-                 o_G = piece(sizeof(float) * 4 * n), o_ho = piece(keep ? sizeof(float) * 2 * n : 0),
-                 o_st = piece(h->padded() ? sizeof(float) * 2 * nl : 0), o_x = piece(sizeof(int32_t) * streams),
-                 o_off = piece(prompt_off ? sizeof(uint64_t) * (streams + 1) : 0), o_p = piece(total),
-                 o_u = piece(count > 0 && temperature >= (double)FLT_MIN ? sizeof(double) * nd : 0), o_out = piece(nd),
-                 o_bits = piece(sizeof(double) * streams), o_end = piece(controls ? sizeof(int32_t) * streams : 0),
-                 o_kept = piece(kept ? sizeof(uint16_t) * nd : 0), o_tab = piece(sizeof(uint16_t) * 256 * (size_t)Q),
-                 o_cnt = piece(sizeof(uint16_t) * Q), o_q = piece(con ? sizeof(int32_t) * streams : 0);
-    if (int rc = reserve_gen_scratch(h, bytes)) return rc;
-    char *base = h->gen_scratch;
-    float4 *Ufwd = reinterpret_cast<float4 *>(base + o_U);
-    float *H = reinterpret_cast<float *>(base + o_H), *Cs = reinterpret_cast<float *>(base + o_C);
-    float *G = reinterpret_cast<float *>(base + o_G), *stage = reinterpret_cast<float *>(base + o_st);
-    float *ho = keep ? reinterpret_cast<float *>(base + o_ho) : nullptr;
-    int32_t *xi = reinterpret_cast<int32_t *>(base + o_x);
-    uint64_t *d_off = prompt_off ? reinterpret_cast<uint64_t *>(base + o_off) : nullptr;
-    uint8_t *d_prompts = total ? reinterpret_cast<uint8_t *>(base + o_p) : nullptr;
-    double *d_u = count > 0 && temperature >= (double)FLT_MIN ? reinterpret_cast<double *>(base + o_u) : nullptr;
-    uint8_t *d_out = reinterpret_cast<uint8_t *>(base + o_out);
-    double *d_bits = reinterpret_cast<double *>(base + o_bits);
-    int32_t *d_end = controls ? reinterpret_cast<int32_t *>(base + o_end) : nullptr;
-    uint16_t *d_kept = kept ? reinterpret_cast<uint16_t *>(base + o_kept) : nullptr;
-    uint16_t *d_tab = con ? reinterpret_cast<uint16_t *>(base + o_tab) : nullptr;
-    uint16_t *d_cnt = con ? reinterpret_cast<uint16_t *>(base + o_cnt) : nullptr;
-    int32_t *d_q = con ? reinterpret_cast<int32_t *>(base + o_q) : nullptr;
+    float4 *Ufwd;
+    float *H, *Cs, *G, *ho, *stage;
+    int32_t *xi, *d_end, *d_q;
+    uint64_t *d_off;
+    uint8_t *d_prompts, *d_out;
+    double *d_u, *d_bits;
+    uint16_t *d_kept, *d_tab, *d_cnt;
+    Scratch mem;
+    mem.piece(Ufwd, (size_t)N * N).piece(H, 2 * n).piece(Cs, 2 * n).piece(G, 4 * n).piece(ho, 2 * n, keep);
+    mem.piece(stage, 2 * nl, h->padded()).piece(xi, streams);
+    mem.piece(d_off, streams + 1, prompt_off != nullptr).piece(d_prompts, total, total != 0);
+    mem.piece(d_u, nd, count > 0 && temperature >= (double)FLT_MIN).piece(d_out, nd).piece(d_bits, streams);
+    mem.piece(d_end, streams, controls).piece(d_kept, nd, kept != nullptr);
+    mem.piece(d_tab, 256 * (size_t)Q, con != nullptr).piece(d_cnt, Q, con != nullptr).piece(d_q, streams, con != nullptr);
+    if (int rc = mem.commit(h)) return rc;
 
     // start state (padding rows zero), inputs
-    const PadMap map = pad_map_rows(1, Nl, N, streams);
-    for (int k = 0; k < 2; k++) {
-        const float *src = k ? c0 : h0;
-        float *dst = k ? Cs : H;
-        if (!src) HIP_TRY(hipMemsetAsync(dst, 0, sizeof(float) * n, h->st));
-        else if (h->padded()) {
-            HIP_TRY(hipMemcpyAsync(stage + k * nl, src, sizeof(float) * nl, hipMemcpyHostToDevice, h->st));
-            pad_copy(stage + k * nl, dst, map, true, h->st);
-            if (int rc = pad_status()) return rc;
-        } else
-            HIP_TRY(hipMemcpyAsync(dst, src, sizeof(float) * n, hipMemcpyHostToDevice, h->st));
-    }
+    if (int rc = upload_states(h, h0, c0, H, Cs, stage, streams)) return rc;
     if (d_off) HIP_TRY(hipMemcpyAsync(d_off, prompt_off, sizeof(uint64_t) * (streams + 1), hipMemcpyHostToDevice, h->st));
     if (d_prompts) HIP_TRY(hipMemcpyAsync(d_prompts, prompts, total, hipMemcpyHostToDevice, h->st));
     if (d_u) HIP_TRY(hipMemcpyAsync(d_u, u, sizeof(double) * nd, hipMemcpyHostToDevice, h->st));
@@ -1839,11 +1927,12 @@ int lstm_hip_generate_constrained(lstm_hip_t *h, int32_t streams, const uint8_t 
         HIP_TRY(hipMemcpyAsync(d_cnt, ccount.data(), sizeof(uint16_t) * Q, hipMemcpyHostToDevice, h->st));
         HIP_TRY(hipMemcpyAsync(d_q, cstate.data(), sizeof(int32_t) * streams, hipMemcpyHostToDevice, h->st));
     }
-    RUN(K_PACK_U, pack_U(infer_block(h) + h->pl.U, Ufwd, nullptr, N, h->st));
+    const Model m = model_of(h);
+    RUN(K_PACK_U, pack_U(m.U, Ufwd, nullptr, N, h->st));
 
     GenHeadArgs a{};
-    a.Why = infer_block(h) + h->pl.Why;
-    a.by = infer_block(h) + h->pl.by;
+    a.Why = m.Why;
+    a.by = m.by;
     a.prompts = d_prompts;
     a.off = d_off;
     a.u = d_u;
@@ -1869,19 +1958,17 @@ int lstm_hip_generate_constrained(lstm_hip_t *h, int32_t streams, const uint8_t 
     a.ctab = d_tab;
     a.ccount = d_cnt;
     a.cstate = d_q;
-    const bool fast = (h->cfg.flags & LSTM_HIP_FAST_MATH) != 0, stable = (h->cfg.flags & LSTM_HIP_STABLE_SOFTMAX) != 0;
+    const bool stable = (h->cfg.flags & LSTM_HIP_STABLE_SOFTMAX) != 0;
     const long long steps = (long long)max_len + count; // inputs of the longest stream
     int cur = 0;
     for (long long t = 0;; t++) {
         a.H = H + cur * n;
         a.C = Cs + cur * n;
-        RUN(K_GEN_HEAD, gen_head(a, t, stable, h->st));
-        if (controls)
-            if (const int e = gen_head_status())
-                return fail(LSTM_HIP_EHIP, "generate: the LDS request of gen_head was refused: %s", hipGetErrorString((hipError_t)e));
+        hipError_t refused = hipSuccess; // (only the FILTER instantiations ever report one)
+        RUN(K_GEN_HEAD, refused = gen_head(a, t, stable, h->st));
+        if (refused != hipSuccess) return head_refused("generate", "gen_head", refused);
         if (t == steps) break;
-        RUN(K_FWD_STEP, fwd_step(Ufwd, infer_block(h) + h->pl.W, infer_block(h) + h->pl.b, H + cur * n, Cs + cur * n, H + (cur ^ 1) * n,
-                                 Cs + (cur ^ 1) * n, G, xi, N, streams, fast, h->st));
+        if (int rc = step_columns(h, m, Ufwd, a.H, a.C, H + (cur ^ 1) * n, Cs + (cur ^ 1) * n, G, xi, streams)) return rc;
         cur ^= 1;
     }
 
@@ -1893,16 +1980,7 @@ int lstm_hip_generate_constrained(lstm_hip_t *h, int32_t streams, const uint8_t 
     }
     if (kept && nd) HIP_TRY(hipMemcpyAsync(kept, d_kept, sizeof(uint16_t) * nd, hipMemcpyDeviceToHost, h->st));
     if (end_state) HIP_TRY(hipMemcpyAsync(end_state, d_q, sizeof(int32_t) * streams, hipMemcpyDeviceToHost, h->st));
-    for (int k = 0; k < 2; k++) {
-        float *dst = k ? c_out : h_out;
-        if (!dst) continue;
-        if (h->padded()) {
-            pad_copy(ho + k * n, stage + k * nl, map, false, h->st);
-            if (int rc = pad_status()) return rc;
-            HIP_TRY(hipMemcpyAsync(dst, stage + k * nl, sizeof(float) * nl, hipMemcpyDeviceToHost, h->st));
-        } else
-            HIP_TRY(hipMemcpyAsync(dst, ho + k * n, sizeof(float) * n, hipMemcpyDeviceToHost, h->st));
-    }
+    if (int rc = download_states(h, h_out, c_out, a.h_out, a.c_out, stage, streams)) return rc;
     HIP_TRY(hipStreamSynchronize(h->st));
     return 0;
 }
@@ -1914,17 +1992,6 @@ size_t lstm_hip_code_bound(uint64_t len) {
     if (len == 0) return 0;
     if (len > (SIZE_MAX - 4) / 3) return SIZE_MAX;
     return (size_t)(3 * len + 4);
-}
-
-// offsets of `streams` streams: off[0] == 0, never decreasing
-static int check_offsets(const char *what, const char *name, const uint64_t *off, int32_t streams) {
-    if (!off) return fail(LSTM_HIP_EINVAL, "%s: null %s", what, name);
-    if (off[0] != 0) return fail(LSTM_HIP_EINVAL, "%s: %s[0] must be 0 (got %llu)", what, name, (unsigned long long)off[0]);
-    for (int s = 0; s < streams; s++)
-        if (off[s + 1] < off[s])
-            return fail(LSTM_HIP_EINVAL, "%s: %s decreases at stream %d (%llu < %llu)", what, name, s,
-                        (unsigned long long)off[s + 1], (unsigned long long)off[s]);
-    return 0;
 }
 
 // Beam search (include/lstm_hip.h): the generator's loop over streams * beams columns.  Per step one
@@ -1959,12 +2026,11 @@ int lstm_hip_beam_search_constrained(lstm_hip_t *h, int32_t streams, const uint8
     if (count < 0) return fail(LSTM_HIP_EINVAL, "beam_search: count < 0 (%d)", count);
     if (count > 0 && (!out || !out_len || !bits)) return fail(LSTM_HIP_EINVAL, "beam_search: null out, out_len or bits with count > 0");
     if (prompts && !prompt_off) return fail(LSTM_HIP_EINVAL, "beam_search: prompts without prompt_off");
-    uint64_t max_len = 0;
     if (prompt_off) {
         if (int rc = check_offsets("beam_search", "prompt_off", prompt_off, streams)) return rc;
-        for (int s = 0; s < streams; s++) max_len = std::max<uint64_t>(max_len, prompt_off[s + 1] - prompt_off[s]);
         if (prompt_off[streams] > 0 && !prompts) return fail(LSTM_HIP_EINVAL, "beam_search: prompt_off without prompts");
     }
+    const uint64_t max_len = prompt_off ? longest(prompt_off, streams) : 0;
     const int N = h->cfg.N, Nl = h->N_log, cols = streams * W;
     if ((long long)N * W > 16384)
         return fail(LSTM_HIP_EINVAL, "beam_search: hidden width %d x %d beams above 16384 floats of LDS", N, W);
@@ -1982,14 +2048,7 @@ int lstm_hip_beam_search_constrained(lstm_hip_t *h, int32_t streams, const uint8
     if (con) {
         if (int rc = check_constraint("beam_search", con, streams, start_state, cstate, ccount)) return rc;
         if (prompt_off)
-            for (int s = 0; s < streams; s++)
-                for (uint64_t j = prompt_off[s]; j < prompt_off[s + 1]; j++) {
-                    const uint16_t v = con->next[(size_t)cstate[s] * 256 + prompts[j]];
-                    if (v == 0xFFFF)
-                        return fail(LSTM_HIP_EINVAL, "beam_search: stream %d: prompt byte 0x%02x at offset %llu is forbidden in state %d",
-                                    s, (unsigned)prompts[j], (unsigned long long)(j - prompt_off[s]), cstate[s]);
-                    cstate[s] = v;
-                }
+            if (int rc = walk_constraint("beam_search", "prompt byte", con, streams, prompts, prompt_off, cstate, nullptr)) return rc;
     }
     if (accept) {
         if (((long long)count + 1) * Q > (1ll << 28))
@@ -2042,56 +2101,33 @@ int lstm_hip_beam_search_constrained(lstm_hip_t *h, int32_t streams, const uint8
     const uint64_t total = prompt_off ? prompt_off[streams] : 0;
     const size_t n = (size_t)N * cols, nl = (size_t)Nl * cols, nd = (size_t)count * cols;
 
-    size_t bytes = 0;
-    auto piece = [&](size_t b) {
-        const size_t o = bytes;
-        bytes += (b + 255) / 256 * 256;
-        return o;
-    };
-    const size_t o_U = piece(sizeof(float) * 4 * (size_t)N * N), o_H = piece(sizeof(float) * 2 * n), o_C = piece(sizeof(float) * 2 * n),
-                 o_G = piece(sizeof(float) * 4 * n), o_st = piece(h->padded() ? sizeof(float) * 2 * nl : 0),
-                 o_x = piece(sizeof(int32_t) * cols), o_off = piece(prompt_off ? sizeof(uint64_t) * (streams + 1) : 0),
-                 o_p = piece(total), o_tp = piece(nd), o_tb = piece(nd), o_out = piece(nd), o_cost = piece(sizeof(double) * cols),
-                 o_len = piece(sizeof(int32_t) * cols), o_fin = piece(sizeof(int32_t) * cols),
-                 o_tab = piece(sizeof(uint16_t) * 256 * (size_t)Q), o_q = piece(con ? sizeof(int32_t) * cols : 0),
-                 o_acc = piece(accept ? (size_t)Q : 0), o_F = piece(accept ? sizeof(uint32_t) * (size_t)count * fwords : 0);
-    if (int rc = reserve_gen_scratch(h, bytes)) return rc;
-    char *base = h->gen_scratch;
-    float4 *Ufwd = reinterpret_cast<float4 *>(base + o_U);
-    float *H = reinterpret_cast<float *>(base + o_H), *Cs = reinterpret_cast<float *>(base + o_C);
-    float *G = reinterpret_cast<float *>(base + o_G), *stage = reinterpret_cast<float *>(base + o_st);
-    int32_t *xi = reinterpret_cast<int32_t *>(base + o_x);
-    uint64_t *d_off = prompt_off ? reinterpret_cast<uint64_t *>(base + o_off) : nullptr;
-    uint8_t *d_prompts = total ? reinterpret_cast<uint8_t *>(base + o_p) : nullptr;
-    uint8_t *d_tp = reinterpret_cast<uint8_t *>(base + o_tp), *d_tb = reinterpret_cast<uint8_t *>(base + o_tb);
-    uint8_t *d_out = reinterpret_cast<uint8_t *>(base + o_out);
-    double *d_cost = reinterpret_cast<double *>(base + o_cost);
-    int32_t *d_len = reinterpret_cast<int32_t *>(base + o_len), *d_fin = reinterpret_cast<int32_t *>(base + o_fin);
-    uint16_t *d_tab = con ? reinterpret_cast<uint16_t *>(base + o_tab) : nullptr;
-    int32_t *d_q = con ? reinterpret_cast<int32_t *>(base + o_q) : nullptr;
-    uint8_t *d_acc = accept ? reinterpret_cast<uint8_t *>(base + o_acc) : nullptr;
-    uint32_t *d_F = accept ? reinterpret_cast<uint32_t *>(base + o_F) : nullptr;
+    float4 *Ufwd;
+    float *H, *Cs, *G, *stage;
+    int32_t *xi, *d_len, *d_fin, *d_q;
+    uint64_t *d_off;
+    uint8_t *d_prompts, *d_tp, *d_tb, *d_out, *d_acc;
+    double *d_cost;
+    uint16_t *d_tab;
+    uint32_t *d_F;
+    Scratch mem;
+    mem.piece(Ufwd, (size_t)N * N).piece(H, 2 * n).piece(Cs, 2 * n).piece(G, 4 * n);
+    mem.piece(stage, 2 * nl, h->padded()).piece(xi, cols);
+    mem.piece(d_off, streams + 1, prompt_off != nullptr).piece(d_prompts, total, total != 0);
+    mem.piece(d_tp, nd).piece(d_tb, nd).piece(d_out, nd).piece(d_cost, cols).piece(d_len, cols).piece(d_fin, cols);
+    mem.piece(d_tab, 256 * (size_t)Q, con != nullptr).piece(d_q, cols, con != nullptr);
+    mem.piece(d_acc, Q, accept != nullptr).piece(d_F, (size_t)count * fwords, accept != nullptr);
+    if (int rc = mem.commit(h)) return rc;
 
     // start state: every slot of a stream starts from the stream's column (padding rows zero)
-    const PadMap map = pad_map_rows(1, Nl, N, cols);
-    std::vector<float> rep;
+    std::vector<float> rep[2]; // (h0 / c0 with each column W times: alive until the synchronize behind the upload)
     for (int k = 0; k < 2; k++) {
         const float *src = k ? c0 : h0;
-        float *dst = k ? Cs : H;
-        if (!src) {
-            HIP_TRY(hipMemsetAsync(dst, 0, sizeof(float) * n, h->st));
-            continue;
-        }
-        rep.resize(nl);
-        for (int c = 0; c < cols; c++) std::copy(src + (size_t)(c / W) * Nl, src + (size_t)(c / W + 1) * Nl, rep.begin() + (size_t)c * Nl);
-        if (h->padded()) {
-            HIP_TRY(hipMemcpyAsync(stage + k * nl, rep.data(), sizeof(float) * nl, hipMemcpyHostToDevice, h->st));
-            pad_copy(stage + k * nl, dst, map, true, h->st);
-            if (int rc = pad_status()) return rc;
-        } else
-            HIP_TRY(hipMemcpyAsync(dst, rep.data(), sizeof(float) * n, hipMemcpyHostToDevice, h->st));
-        HIP_TRY(hipStreamSynchronize(h->st)); // (rep is reused)
+        if (!src) continue;
+        rep[k].resize(nl);
+        for (int c = 0; c < cols; c++) std::copy(src + (size_t)(c / W) * Nl, src + (size_t)(c / W + 1) * Nl, rep[k].begin() + (size_t)c * Nl);
     }
+    if (int rc = upload_states(h, h0 ? rep[0].data() : nullptr, c0 ? rep[1].data() : nullptr, H, Cs, stage, cols)) return rc;
+    if (h0 || c0) HIP_TRY(hipStreamSynchronize(h->st));
     if (d_off) HIP_TRY(hipMemcpyAsync(d_off, prompt_off, sizeof(uint64_t) * (streams + 1), hipMemcpyHostToDevice, h->st));
     if (d_prompts) HIP_TRY(hipMemcpyAsync(d_prompts, prompts, total, hipMemcpyHostToDevice, h->st));
     std::vector<double> cost0(cols, (double)INFINITY);
@@ -2115,11 +2151,12 @@ int lstm_hip_beam_search_constrained(lstm_hip_t *h, int32_t streams, const uint8
     }
     HIP_TRY(hipMemsetAsync(d_tp, 0, nd, h->st));
     HIP_TRY(hipMemsetAsync(d_tb, 0, nd, h->st));
-    RUN(K_PACK_U, pack_U(infer_block(h) + h->pl.U, Ufwd, nullptr, N, h->st));
+    const Model m = model_of(h);
+    RUN(K_PACK_U, pack_U(m.U, Ufwd, nullptr, N, h->st));
 
     BeamHeadArgs a{};
-    a.Why = infer_block(h) + h->pl.Why;
-    a.by = infer_block(h) + h->pl.by;
+    a.Why = m.Why;
+    a.by = m.by;
     a.H = H;
     a.C = Cs;
     a.Hr = H + n;
@@ -2142,14 +2179,13 @@ int lstm_hip_beam_search_constrained(lstm_hip_t *h, int32_t streams, const uint8
     a.accept = d_acc;
     a.frows = d_F;
     a.fwords = fwords;
-    const bool fast = (h->cfg.flags & LSTM_HIP_FAST_MATH) != 0;
     const long long steps = (long long)max_len + count; // the longest stream's last selection is at step steps - 1
     for (long long t = 0; t < steps; t++) {
-        RUN(K_BEAM_HEAD, beam_head(a, t, h->st));
-        if (const int e = beam_head_status())
-            return fail(LSTM_HIP_EHIP, "beam_search: the LDS request of beam_head was refused: %s", hipGetErrorString((hipError_t)e));
+        hipError_t refused = hipSuccess;
+        RUN(K_BEAM_HEAD, refused = beam_head(a, t, h->st));
+        if (refused != hipSuccess) return head_refused("beam_search", "beam_head", refused);
         if (t + 1 == steps) break;
-        RUN(K_FWD_STEP, fwd_step(Ufwd, infer_block(h) + h->pl.W, infer_block(h) + h->pl.b, a.Hr, a.Cr, H, Cs, G, xi, N, cols, fast, h->st));
+        if (int rc = step_columns(h, m, Ufwd, a.Hr, a.Cr, H, Cs, G, xi, cols)) return rc;
     }
     RUN(K_BEAM_BACKTRACK, beam_backtrack(d_tp, d_tb, d_len, d_out, streams, W, count, h->st));
 
@@ -2189,9 +2225,8 @@ int lstm_hip_score(lstm_hip_t *h, int32_t streams, const uint8_t *text, const ui
     if (int rc = check_offsets("score", "text_off", text_off, streams)) return rc;
     const uint64_t total = text_off[streams];
     if (total > 0 && !text) return fail(LSTM_HIP_EINVAL, "score: null text with %llu bytes to score", (unsigned long long)total);
-    uint64_t max_len = 0;
-    for (int s = 0; s < streams; s++) max_len = std::max<uint64_t>(max_len, text_off[s + 1] - text_off[s]);
-    const int N = h->cfg.N, Nl = h->N_log;
+    const uint64_t max_len = longest(text_off, streams);
+    const int N = h->cfg.N;
     if (N > 16384) return fail(LSTM_HIP_EINVAL, "score: hidden width %d above 16384", N);
     std::vector<int32_t> cstate;  // [streams] each stream's state: at its start, then after its text
     std::vector<uint16_t> ccount; // (the allowed counts are checked, not used)
@@ -2200,65 +2235,30 @@ int lstm_hip_score(lstm_hip_t *h, int32_t streams, const uint8_t *text, const ui
     if (con) {
         if (int rc = check_constraint("score", con, streams, start_state, cstate, ccount)) return rc;
         qpos.resize(total);
-        for (int s = 0; s < streams; s++)
-            for (uint64_t j = text_off[s]; j < text_off[s + 1]; j++) {
-                const uint16_t v = con->next[(size_t)cstate[s] * 256 + text[j]];
-                if (v == 0xFFFF)
-                    return fail(LSTM_HIP_EINVAL, "score: stream %d: byte 0x%02x at offset %llu is forbidden in state %d", s,
-                                (unsigned)text[j], (unsigned long long)(j - text_off[s]), cstate[s]);
-                qpos[j] = (uint16_t)cstate[s];
-                cstate[s] = v;
-            }
+        if (int rc = walk_constraint("score", "byte", con, streams, text, text_off, cstate, qpos.data())) return rc;
     }
-    const size_t n = (size_t)N * streams, nl = (size_t)Nl * streams, tot = (size_t)total;
+    const size_t n = (size_t)N * streams, nl = (size_t)h->N_log * streams, tot = (size_t)total;
     const bool keep = h_out || c_out;
 
-    // one scratch allocation, 256-byte aligned pieces
-    size_t bytes = 0;
-    auto piece = [&](size_t b) {
-        const size_t at = bytes;
-        bytes += (b + 255) / 256 * 256;
-        return at;
-    };
-    const size_t o_U = piece(sizeof(float) * 4 * (size_t)N * N), o_H = piece(sizeof(float) * 2 * n), o_C = piece(sizeof(float) * 2 * n),
-                 o_G = piece(sizeof(float) * 4 * n), o_ho = piece(keep ? sizeof(float) * 2 * n : 0),
-                 o_st = piece(h->padded() ? sizeof(float) * 2 * nl : 0), o_x = piece(sizeof(int32_t) * streams),
-                 o_off = piece(sizeof(uint64_t) * (streams + 1)), o_t = piece(tot), o_bits = piece(sizeof(double) * streams),
-                 o_sur = piece(o.surprisal ? sizeof(float) * tot : 0), o_ent = piece(o.entropy ? sizeof(float) * tot : 0),
-                 o_rank = piece(o.rank ? tot : 0), o_tby = piece(o.top_byte ? tot * top_n : 0),
-                 o_tbi = piece(o.top_bits ? sizeof(float) * tot * top_n : 0), o_tab = piece(sizeof(uint16_t) * 256 * (size_t)Q),
-                 o_q = piece(con ? sizeof(uint16_t) * tot : 0);
-    if (int rc = reserve_gen_scratch(h, bytes)) return rc;
-    char *base = h->gen_scratch;
-    float4 *Ufwd = reinterpret_cast<float4 *>(base + o_U);
-    float *H = reinterpret_cast<float *>(base + o_H), *Cs = reinterpret_cast<float *>(base + o_C);
-    float *G = reinterpret_cast<float *>(base + o_G), *stage = reinterpret_cast<float *>(base + o_st);
-    float *ho = keep ? reinterpret_cast<float *>(base + o_ho) : nullptr;
-    int32_t *xi = reinterpret_cast<int32_t *>(base + o_x);
-    uint64_t *d_off = reinterpret_cast<uint64_t *>(base + o_off);
-    uint8_t *d_text = reinterpret_cast<uint8_t *>(base + o_t);
-    double *d_bits = reinterpret_cast<double *>(base + o_bits);
-    float *d_sur = o.surprisal && tot ? reinterpret_cast<float *>(base + o_sur) : nullptr;
-    float *d_ent = o.entropy && tot ? reinterpret_cast<float *>(base + o_ent) : nullptr;
-    uint8_t *d_rank = o.rank && tot ? reinterpret_cast<uint8_t *>(base + o_rank) : nullptr;
-    uint8_t *d_tby = o.top_byte && tot ? reinterpret_cast<uint8_t *>(base + o_tby) : nullptr;
-    float *d_tbi = o.top_bits && tot ? reinterpret_cast<float *>(base + o_tbi) : nullptr;
-    uint16_t *d_tab = con ? reinterpret_cast<uint16_t *>(base + o_tab) : nullptr;
-    uint16_t *d_q = con ? reinterpret_cast<uint16_t *>(base + o_q) : nullptr;
+    // (an output of a call without bytes is absent: nothing to zero, nothing to copy back, null to the head)
+    float4 *Ufwd;
+    float *H, *Cs, *G, *ho, *stage, *d_sur, *d_ent, *d_tbi;
+    int32_t *xi;
+    uint64_t *d_off;
+    uint8_t *d_text, *d_rank, *d_tby;
+    double *d_bits;
+    uint16_t *d_tab, *d_q;
+    Scratch mem;
+    mem.piece(Ufwd, (size_t)N * N).piece(H, 2 * n).piece(Cs, 2 * n).piece(G, 4 * n).piece(ho, 2 * n, keep);
+    mem.piece(stage, 2 * nl, h->padded()).piece(xi, streams);
+    mem.piece(d_off, streams + 1).piece(d_text, tot).piece(d_bits, streams);
+    mem.piece(d_sur, tot, o.surprisal && tot).piece(d_ent, tot, o.entropy && tot).piece(d_rank, tot, o.rank && tot);
+    mem.piece(d_tby, tot * top_n, o.top_byte && tot).piece(d_tbi, tot * top_n, o.top_bits && tot);
+    mem.piece(d_tab, 256 * (size_t)Q, con != nullptr).piece(d_q, tot, con != nullptr);
+    if (int rc = mem.commit(h)) return rc;
 
     // start state (padding rows zero), inputs, zeroed outputs (the entries of unscored bytes stay zero)
-    const PadMap map = pad_map_rows(1, Nl, N, streams);
-    for (int k = 0; k < 2; k++) {
-        const float *src = k ? c0 : h0;
-        float *dst = k ? Cs : H;
-        if (!src) HIP_TRY(hipMemsetAsync(dst, 0, sizeof(float) * n, h->st));
-        else if (h->padded()) {
-            HIP_TRY(hipMemcpyAsync(stage + k * nl, src, sizeof(float) * nl, hipMemcpyHostToDevice, h->st));
-            pad_copy(stage + k * nl, dst, map, true, h->st);
-            if (int rc = pad_status()) return rc;
-        } else
-            HIP_TRY(hipMemcpyAsync(dst, src, sizeof(float) * n, hipMemcpyHostToDevice, h->st));
-    }
+    if (int rc = upload_states(h, h0, c0, H, Cs, stage, streams)) return rc;
     HIP_TRY(hipMemcpyAsync(d_off, text_off, sizeof(uint64_t) * (streams + 1), hipMemcpyHostToDevice, h->st));
     if (tot) HIP_TRY(hipMemcpyAsync(d_text, text, tot, hipMemcpyHostToDevice, h->st));
     HIP_TRY(hipMemsetAsync(d_bits, 0, sizeof(double) * streams, h->st));
@@ -2271,11 +2271,12 @@ int lstm_hip_score(lstm_hip_t *h, int32_t streams, const uint8_t *text, const ui
         HIP_TRY(hipMemcpyAsync(d_tab, con->next, sizeof(uint16_t) * 256 * (size_t)Q, hipMemcpyHostToDevice, h->st));
         if (tot) HIP_TRY(hipMemcpyAsync(d_q, qpos.data(), sizeof(uint16_t) * tot, hipMemcpyHostToDevice, h->st));
     }
-    RUN(K_PACK_U, pack_U(infer_block(h) + h->pl.U, Ufwd, nullptr, N, h->st));
+    const Model m = model_of(h);
+    RUN(K_PACK_U, pack_U(m.U, Ufwd, nullptr, N, h->st));
 
     ScoreHeadArgs a{};
-    a.Why = infer_block(h) + h->pl.Why;
-    a.by = infer_block(h) + h->pl.by;
+    a.Why = m.Why;
+    a.by = m.by;
     a.text = d_text;
     a.off = d_off;
     a.surprisal = d_sur;
@@ -2293,17 +2294,16 @@ int lstm_hip_score(lstm_hip_t *h, int32_t streams, const uint8_t *text, const ui
     a.streams = streams;
     a.first = opt->first;
     a.top_n = top_n;
-    const bool fast = (h->cfg.flags & LSTM_HIP_FAST_MATH) != 0, stable = (h->cfg.flags & LSTM_HIP_STABLE_SOFTMAX) != 0;
+    const bool stable = (h->cfg.flags & LSTM_HIP_STABLE_SOFTMAX) != 0;
     int cur = 0;
     for (uint64_t t = 0;; t++) {
         a.H = H + cur * n;
         a.C = Cs + cur * n;
-        RUN(K_SCORE_HEAD, score_head(a, (long long)t, stable, h->st));
-        if (const int e = score_head_status())
-            return fail(LSTM_HIP_EHIP, "score: the LDS request of score_head was refused: %s", hipGetErrorString((hipError_t)e));
+        hipError_t refused = hipSuccess;
+        RUN(K_SCORE_HEAD, refused = score_head(a, (long long)t, stable, h->st));
+        if (refused != hipSuccess) return head_refused("score", "score_head", refused);
         if (t == max_len) break;
-        RUN(K_FWD_STEP, fwd_step(Ufwd, infer_block(h) + h->pl.W, infer_block(h) + h->pl.b, H + cur * n, Cs + cur * n, H + (cur ^ 1) * n,
-                                 Cs + (cur ^ 1) * n, G, xi, N, streams, fast, h->st));
+        if (int rc = step_columns(h, m, Ufwd, a.H, a.C, H + (cur ^ 1) * n, Cs + (cur ^ 1) * n, G, xi, streams)) return rc;
         cur ^= 1;
     }
 
@@ -2313,16 +2313,7 @@ int lstm_hip_score(lstm_hip_t *h, int32_t streams, const uint8_t *text, const ui
     if (d_tby) HIP_TRY(hipMemcpyAsync(o.top_byte, d_tby, tot * top_n, hipMemcpyDeviceToHost, h->st));
     if (d_tbi) HIP_TRY(hipMemcpyAsync(o.top_bits, d_tbi, sizeof(float) * tot * top_n, hipMemcpyDeviceToHost, h->st));
     if (o.bits) HIP_TRY(hipMemcpyAsync(o.bits, d_bits, sizeof(double) * streams, hipMemcpyDeviceToHost, h->st));
-    for (int k = 0; k < 2; k++) {
-        float *dst = k ? c_out : h_out;
-        if (!dst) continue;
-        if (h->padded()) {
-            pad_copy(ho + k * n, stage + k * nl, map, false, h->st);
-            if (int rc = pad_status()) return rc;
-            HIP_TRY(hipMemcpyAsync(dst, stage + k * nl, sizeof(float) * nl, hipMemcpyDeviceToHost, h->st));
-        } else
-            HIP_TRY(hipMemcpyAsync(dst, ho + k * n, sizeof(float) * n, hipMemcpyDeviceToHost, h->st));
-    }
+    if (int rc = download_states(h, h_out, c_out, a.h_out, a.c_out, stage, streams)) return rc;
     HIP_TRY(hipStreamSynchronize(h->st));
     if (o.end_state) std::copy(cstate.begin(), cstate.end(), o.end_state);
     return 0;
@@ -2341,6 +2332,7 @@ struct CoderRun {
     uint64_t total = 0, max_len = 0, code_bytes = 0;
     std::vector<uint64_t> base; // each stream's code range on the device
     size_t n = 0;               // N * streams
+    Model m{};
     float4 *Ufwd = nullptr;
     float *H = nullptr, *Cs = nullptr, *G = nullptr;
     double *bits_prev = nullptr, *block_bits = nullptr; // adaptive calls: per-stream bits at the last fold, per-block totals
@@ -2352,8 +2344,7 @@ static int coder_begin(lstm_hip_t *h, CoderRun &r, bool decode, int32_t streams,
     r.decode = decode;
     r.streams = streams;
     r.total = text_off[streams];
-    r.max_len = 0;
-    for (int s = 0; s < streams; s++) r.max_len = std::max<uint64_t>(r.max_len, text_off[s + 1] - text_off[s]);
+    r.max_len = longest(text_off, streams);
     r.base.assign(streams + 1, 0);
     if (decode) r.base.assign(code_off_in, code_off_in + streams + 1);
     else
@@ -2362,52 +2353,38 @@ static int coder_begin(lstm_hip_t *h, CoderRun &r, bool decode, int32_t streams,
     const uint64_t total = r.total, code_bytes = r.code_bytes;
     const size_t n = r.n = (size_t)N * streams;
 
-    size_t bytes = 0;
-    auto piece = [&](size_t b) {
-        const size_t o = bytes;
-        bytes += (b + 255) / 256 * 256;
-        return o;
-    };
-    const size_t o_U = piece(sizeof(float) * 4 * (size_t)N * N), o_H = piece(sizeof(float) * 2 * n), o_C = piece(sizeof(float) * 2 * n),
-                 o_G = piece(sizeof(float) * 4 * n), o_x = piece(sizeof(int32_t) * streams),
-                 o_toff = piece(sizeof(uint64_t) * (streams + 1)), o_base = piece(sizeof(uint64_t) * (streams + 1)),
-                 o_text = piece(total), o_code = piece(code_bytes), o_st = piece(sizeof(CoderState) * streams),
-                 o_len = piece(sizeof(uint64_t) * streams), o_bits = piece(sizeof(double) * streams),
-                 o_tr = piece(want_trace ? sizeof(uint32_t) * 3 * total : 0), o_err = piece(sizeof(uint32_t)),
-                 o_prev = piece(n_block_bits ? sizeof(double) * streams : 0), o_bb = piece(sizeof(double) * n_block_bits);
-    if (int rc = reserve_gen_scratch(h, bytes)) return rc;
-    char *b0 = h->gen_scratch;
-    r.Ufwd = reinterpret_cast<float4 *>(b0 + o_U);
-    r.H = reinterpret_cast<float *>(b0 + o_H), r.Cs = reinterpret_cast<float *>(b0 + o_C), r.G = reinterpret_cast<float *>(b0 + o_G);
-    r.bits_prev = n_block_bits ? reinterpret_cast<double *>(b0 + o_prev) : nullptr;
-    r.block_bits = n_block_bits ? reinterpret_cast<double *>(b0 + o_bb) : nullptr;
-    r.cur = 0;
     CodeHeadArgs &a = r.a;
     a = CodeHeadArgs{};
-    a.Why = infer_block(h) + h->pl.Why;
-    a.by = infer_block(h) + h->pl.by;
-    a.text_off = reinterpret_cast<uint64_t *>(b0 + o_toff);
-    a.text = reinterpret_cast<uint8_t *>(b0 + o_text);
-    a.code = reinterpret_cast<uint8_t *>(b0 + o_code);
-    a.code_base = reinterpret_cast<uint64_t *>(b0 + o_base);
-    a.code_len = reinterpret_cast<uint64_t *>(b0 + o_len);
-    a.state = reinterpret_cast<CoderState *>(b0 + o_st);
-    a.bits = decode ? nullptr : reinterpret_cast<double *>(b0 + o_bits);
-    a.trace = want_trace && !decode ? reinterpret_cast<uint32_t *>(b0 + o_tr) : nullptr;
-    a.x_next = reinterpret_cast<int32_t *>(b0 + o_x);
-    a.err = reinterpret_cast<uint32_t *>(b0 + o_err);
+    uint64_t *d_toff, *d_base;
+    double *d_bits;   // (the encoder's; carved and zeroed for the decoder too, which gets no pointer to them)
+    uint32_t *d_trace;
+    Scratch mem;
+    mem.piece(r.Ufwd, (size_t)N * N).piece(r.H, 2 * n).piece(r.Cs, 2 * n).piece(r.G, 4 * n).piece(a.x_next, streams);
+    mem.piece(d_toff, streams + 1).piece(d_base, streams + 1).piece(a.text, total).piece(a.code, code_bytes);
+    mem.piece(a.state, streams).piece(a.code_len, streams).piece(d_bits, streams);
+    mem.piece(d_trace, 3 * total, want_trace).piece(a.err, 1);
+    mem.piece(r.bits_prev, streams, n_block_bits != 0).piece(r.block_bits, n_block_bits, n_block_bits != 0);
+    if (int rc = mem.commit(h)) return rc;
+    r.cur = 0;
+    r.m = model_of(h);
+    a.Why = r.m.Why;
+    a.by = r.m.by;
+    a.text_off = d_toff;
+    a.code_base = d_base;
+    a.bits = decode ? nullptr : d_bits;
+    a.trace = decode ? nullptr : d_trace;
     a.N = N;
     a.streams = streams;
     a.decode = decode ? 1 : 0;
 
     HIP_TRY(hipMemsetAsync(r.H, 0, sizeof(float) * n, h->st)); // every stream starts from h = c = 0 (padding rows too)
     HIP_TRY(hipMemsetAsync(r.Cs, 0, sizeof(float) * n, h->st));
-    HIP_TRY(hipMemcpyAsync(const_cast<uint64_t *>(a.text_off), text_off, sizeof(uint64_t) * (streams + 1), hipMemcpyHostToDevice, h->st));
-    HIP_TRY(hipMemcpyAsync(const_cast<uint64_t *>(a.code_base), r.base.data(), sizeof(uint64_t) * (streams + 1), hipMemcpyHostToDevice, h->st));
+    HIP_TRY(hipMemcpyAsync(d_toff, text_off, sizeof(uint64_t) * (streams + 1), hipMemcpyHostToDevice, h->st));
+    HIP_TRY(hipMemcpyAsync(d_base, r.base.data(), sizeof(uint64_t) * (streams + 1), hipMemcpyHostToDevice, h->st));
     if (!decode && total) HIP_TRY(hipMemcpyAsync(a.text, text_in, total, hipMemcpyHostToDevice, h->st));
     if (decode && code_bytes) HIP_TRY(hipMemcpyAsync(a.code, code_in, code_bytes, hipMemcpyHostToDevice, h->st));
     HIP_TRY(hipMemsetAsync(a.code_len, 0, sizeof(uint64_t) * streams, h->st)); // (empty streams: no code)
-    HIP_TRY(hipMemsetAsync(b0 + o_bits, 0, sizeof(double) * streams, h->st));
+    HIP_TRY(hipMemsetAsync(d_bits, 0, sizeof(double) * streams, h->st));
     HIP_TRY(hipMemsetAsync(a.err, 0, sizeof(uint32_t), h->st));
     if (n_block_bits) {
         HIP_TRY(hipMemsetAsync(r.bits_prev, 0, sizeof(double) * streams, h->st));
@@ -2419,16 +2396,15 @@ static int coder_begin(lstm_hip_t *h, CoderRun &r, bool decode, int32_t streams,
 // byte of the longest stream) fwd_step on the byte just coded
 static int coder_steps(lstm_hip_t *h, CoderRun &r, uint64_t t0, uint64_t t1) {
     if (t0 >= t1) return 0;
-    const int N = h->cfg.N;
     const size_t n = r.n;
-    RUN(K_PACK_U, pack_U(infer_block(h) + h->pl.U, r.Ufwd, nullptr, N, h->st));
-    const bool fast = (h->cfg.flags & LSTM_HIP_FAST_MATH) != 0;
+    RUN(K_PACK_U, pack_U(r.m.U, r.Ufwd, nullptr, h->cfg.N, h->st));
     for (long long t = (long long)t0; t < (long long)t1; t++) {
         r.a.H = r.H + r.cur * n;
         RUN(K_CODE_HEAD, code_head(r.a, t, h->st));
         if (t + 1 == (long long)r.max_len) break;
-        RUN(K_FWD_STEP, fwd_step(r.Ufwd, infer_block(h) + h->pl.W, infer_block(h) + h->pl.b, r.H + r.cur * n, r.Cs + r.cur * n, r.H + (r.cur ^ 1) * n,
-                                 r.Cs + (r.cur ^ 1) * n, r.G, r.a.x_next, N, r.streams, fast, h->st));
+        if (int rc = step_columns(h, r.m, r.Ufwd, r.a.H, r.Cs + r.cur * n, r.H + (r.cur ^ 1) * n, r.Cs + (r.cur ^ 1) * n, r.G,
+                                  r.a.x_next, r.streams))
+            return rc;
         r.cur ^= 1;
     }
     return 0;

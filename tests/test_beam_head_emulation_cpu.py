@@ -22,7 +22,7 @@ def emulator(tmp_path_factory):
     src = open(os.path.join(ROOT, "eigen-lstm_amd", "csrc", "kernels.hip")).read()
     a = src.index("__device__ __forceinline__ float lse_surprisal(")
     lse = src[a:src.index("}\n", a) + 2]
-    body = src[src.index("__device__ __forceinline__ bool beam_before("):src.index("static thread_local hipError_t g_beam_head_error")]
+    body = src[src.index("__device__ __forceinline__ bool beam_before("):src.index("template <int WP, bool EXACT, bool CONSTRAIN> static hipError_t beam_head_launch(")]
     lds = "    extern __shared__ __attribute__((aligned(16))) float hs[]; // [N][W]\n"
     assert body.count(lds) == 1
     (d / "beam_body.inc").write_text(lse + body.replace(lds, "    float *hs = g_hs;\n"))

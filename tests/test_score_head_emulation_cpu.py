@@ -21,7 +21,7 @@ def emulator(tmp_path_factory):
     d = tmp_path_factory.mktemp("score_head")
     src = open(os.path.join(ROOT, "eigen-lstm_amd", "csrc", "kernels.hip")).read()
     body = src[src.index("template <int SB, bool STABLE, bool DETAIL, bool CONSTRAIN>\n__global__"):
-               src.index("static thread_local hipError_t g_score_head_error")]
+               src.index("template <bool STABLE, bool DETAIL, bool CONSTRAIN> static hipError_t score_head_launch(")]
     lds = "    extern __shared__ __attribute__((aligned(16))) float hs[]; // [N][SB]\n"
     assert body.count(lds) == 1
     (d / "head_body.inc").write_text(body.replace(lds, "    float *hs = g_hs;\n"))
