@@ -3122,22 +3122,10 @@ size_t persistent_counter_bytes(int S, int B) {
     return (size_t)(S + 1) * NG * CNT_SLOTS * CNT_STRIDE * sizeof(unsigned);
 }
 
-template <class K> static int blocks_per_cu(K kernel, int threads, size_t dyn_lds = 0) {
-    if (dyn_lds > 0)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_lds);
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, threads, dyn_lds) != hipSuccess) return 0;
-    return n;
-}
-
-#define FWD_CASES(X) X(1) X(2) X(4) X(8) X(16)
-#define BWD_CASES(X) X(2) X(4) X(8) X(16) X(32)
-constexpr size_t DW_TABLE_BYTES = 257 * 64 * sizeof(float); // dynamic LDS of the fused backward form
-
 // which forward kernel serves a shape (one rule, no switches):
 //   8-column form (k_fwd_persistent4): N = 256, 512, 1024, more than one 8-column group, one workgroup per CU fits
 //   second form (k_fwd_persistent2):   N = 128, 256, 512, 1024 otherwise (e.g. the evaluator's B = 1)
-//   first form (k_fwd_persistent):     every other multiple of 64
+//   first form (k_fwd_persistent):     N = 64 (the other multiples of 64 have no co-resident form: per-step engine)
 static bool fwd_second_form(int N) { return N == 128 || N == 256 || N == 512 || N == 1024; }
 // Columns one launch of the fp32 two-half forms takes (N = 256, 512): as many 8-column groups as are co-resident at one
 // workgroup per CU.  A wider batch runs as several launches over column ranges (the streams are independent recurrences).
@@ -3158,113 +3146,6 @@ static bool fwd_uses_8col_form(int N, int B, int n_cus) {
 static int bwd_group_cols(int N, int B, int n_cus) { return (N / 16) * ((B + 7) / 8) <= n_cus || two_half_wide(N, B, n_cus) ? 8 : 16; }
 // floats in one column group's partial gradient block [dW | dU | db | dWhy]
 size_t bwd_partial_floats(int N) { return (size_t)4 * N * 256 + (size_t)4 * N * N + (size_t)4 * N + (size_t)256 * N; }
-
-static bool bwd_scatter_supported(int N, int B, int n_cus, bool fused);
-// All workgroups of a recurrence wait on each other, so its grid must be co-resident.  The occupancy API is asked about
-// exactly the instantiation that will be launched, with its dynamic LDS; it can over-report by one block per CU
-// (MI355X_MICROARCH.md, residency), so one is taken off wherever more than one is claimed.
-static bool grid_fits(size_t grid, int per_cu, int n_cus) {
-    if (per_cu > 1) per_cu -= 1;
-    if (per_cu > 8) per_cu = 8;
-    return per_cu >= 1 && grid <= (size_t)per_cu * n_cus;
-}
-static bool persistent_supported(int N, int B, int n_cus, bool fused) {
-    if (N % 64 != 0 || N > 1024) return false;
-    if (two_half_wide(N, B, n_cus)) // several launches per direction: the two-half forms or nothing
-        return (N == 512 ? blocks_per_cu(k_fwd_persistent6<512, false>, FWD4_THREADS) : blocks_per_cu(k_fwd_persistent6<256, false>, FWD4_THREADS)) >= 1 &&
-               bwd_scatter_supported(N, B, n_cus, fused);
-    int fb = 0, bb = 0;
-    size_t fwd_grid = 0;
-    if (fwd_uses_8col_form(N, B, n_cus)) {
-        fwd_grid = (size_t)(N / 16) * ((B + 7) / 8);
-        if (N == 512 && blocks_per_cu(k_fwd_persistent6<512, false>, FWD4_THREADS) < 1) return false;
-        if (N == 256 && blocks_per_cu(k_fwd_persistent6<256, false>, FWD4_THREADS) < 1) return false;
-        switch (N / 256) {
-#define X(k) case k: fb = blocks_per_cu(k_fwd_persistent4<k, false>, FWD4_THREADS); break;
-            X(1) X(2) X(4)
-#undef X
-        }
-    } else if (fwd_second_form(N)) {
-        fwd_grid = (size_t)(N / 8) * ((B + 15) / 16);
-        switch (N / 128) {
-#define X(k) case k: fb = blocks_per_cu(k_fwd_persistent2<k, false>, 512); break;
-            X(1) X(2) X(4) X(8)
-#undef X
-        }
-    } else {
-        fwd_grid = (size_t)(N / 4) * ((B + 15) / 16);
-        switch (N / 64) {
-#define X(k) case k: fb = blocks_per_cu(k_fwd_persistent<k, false>, 256); break;
-            FWD_CASES(X)
-#undef X
-            default: return false;
-        }
-    }
-    const int cols = bwd_group_cols(N, B, n_cus);
-    const bool fuse = fused && cols == 8;
-    const size_t lds = fuse ? DW_TABLE_BYTES : 0;
-    switch (N / 32) {
-#define X(k)                                                                                                           \
-    case k:                                                                                                            \
-        if (cols == 8 && fuse) bb = blocks_per_cu(k_bwd_persistent<k, 8, true, false, false, true>, 512, lds);         \
-        else if (cols == 8) bb = blocks_per_cu(k_bwd_persistent<k, 8, false, false, false, true>, 512, 0);             \
-        else bb = blocks_per_cu(k_bwd_persistent<k, 16, false>, 512, 0);                                               \
-        break;
-        BWD_CASES(X)
-#undef X
-        default: return false;
-    }
-    return grid_fits(fwd_grid, fb, n_cus) && grid_fits((size_t)(N / 16) * ((B + cols - 1) / cols), bb, n_cus);
-}
-// the bf16 recurrence launches other instantiations on other grids: 8-column groups in the backward recurrence when they
-// are co-resident (bwd_group_cols_bf16), else 16-column groups two workgroups to a CU
-static int bwd_bf16_blocks(int N, int cols, bool fused) {
-    int bb = 0;
-    switch (N / 32) {
-#define X(k)                                                                                             \
-    case k:                                                                                              \
-        bb = cols == 16 ? blocks_per_cu(k_bwd_persistent<k, 16, false, false, true>, 512, 0)             \
-             : cols == 4 ? blocks_per_cu(k_bwd_persistent<k, 4, false, false, true>, 512, 0)             \
-             : fused    ? blocks_per_cu(k_bwd_persistent<k, 8, true, false, true>, 512, DW_TABLE_BYTES)  \
-                        : blocks_per_cu(k_bwd_persistent<k, 8, false, false, true>, 512, 0);             \
-        break;
-        X(4) X(8) X(16) X(32)
-#undef X
-    }
-    return bb;
-}
-static int bwd_group_cols_bf16(int N, int B, int n_cus, bool fused) {
-    // 4-column groups when even 8-column groups would leave half the CUs idle (BASELINE configs[4]: hidden 1024, 16 streams
-    // per GPU = 128 workgroups of 8 columns): twice the CUs, each pulling and multiplying half as much per step
-    if (!fused && B % 4 == 0 && (size_t)(N / 16) * ((B + 7) / 8) * 2 <= (size_t)n_cus &&
-        grid_fits((size_t)(N / 16) * (B / 4), bwd_bf16_blocks(N, 4, false), n_cus))
-        return 4;
-    if (grid_fits((size_t)(N / 16) * ((B + 7) / 8), bwd_bf16_blocks(N, 8, fused), n_cus)) return 8;
-    return 16;
-}
-static bool persistent_supported_bf16(int N, int B, int n_cus, bool fused) {
-    if (N % 128 != 0 || N > 1024) return false;
-    int fb = 0, bb = 0;
-    size_t fwd_grid = 0;
-    if (N % 256 == 0) {
-        fwd_grid = (size_t)(N / 8) * ((B + 15) / 16);
-        switch (N / 256) {
-#define X(k) case k: fb = blocks_per_cu(k_fwd_persistent2_bf16<k, false>, 512); break;
-            X(1) X(2) X(4)
-#undef X
-        }
-    } else {
-        fwd_grid = (size_t)(N / 4) * ((B + 15) / 16);
-        switch (N / 128) {
-#define X(k) case k: fb = blocks_per_cu(k_fwd_persistent_bf16<k, false>, 256); break;
-            X(1) X(2) X(4) X(8)
-#undef X
-        }
-    }
-    const int cols = bwd_group_cols_bf16(N, B, n_cus, fused);
-    bb = bwd_bf16_blocks(N, cols, fused && cols == 8);
-    return grid_fits(fwd_grid, fb, n_cus) && grid_fits((size_t)(N / 16) * ((B + cols - 1) / cols), bb, n_cus);
-}
 
 // ------------------------------------------------------------------------------------------------
 // One stream, hidden <= 128 (the reference's own default: R/lstm.cc, alice29, N = 128, S = 25, batch 1 = BASELINE configs[0]):
@@ -3426,93 +3307,238 @@ __global__ __launch_bounds__(SMALL_BWD_THREADS) void k_small_bwd(const float4 *_
     }
 }
 static bool small_recurrence_supported(int N, int B) { return B == 1 && (N == 128 || N == 64); }
-void small_fwd(const float *U, const float *W, const float *bias, float *H, float *C, float *G, const int32_t *xi, int N, int S, bool fast,
-               hipStream_t st) {
-#define GO(n)                                                                                                     \
-    do {                                                                                                          \
-        if (fast) hipLaunchKernelGGL((k_small_fwd<n, true>), dim3(1), dim3(1024), 0, st, U, W, bias, H, C, G, xi, S);  \
-        else hipLaunchKernelGGL((k_small_fwd<n, false>), dim3(1), dim3(1024), 0, st, U, W, bias, H, C, G, xi, S);      \
-    } while (0)
-    if (N == 128) GO(128);
-    else GO(64);
-#undef GO
+
+// ---- resolvers: one per kernel template, shared by the occupancy questions and the launchers ----------------------------
+// A resolver maps the runtime values that select an instantiation (N, fast, stamps, columns per group, fuse, bf16) to the
+// typed kernel with its block size and dynamic LDS -- a Rung -- and hands that to a callable; it returns false where no
+// instantiation serves those values.  The questions of plan_engine (Occupancy) and the launchers (launch) go through the same
+// resolver, so a form is asked about and launched as one and the same instantiation.  The kernel pointer stays typed: a
+// launch checks its arguments against the kernel's parameters.
+template <class K> struct Rung {
+    K kern;
+    int threads;
+    size_t lds;   // dynamic LDS
+    bool stamped; // a STAMP instantiation (LSTM_HIP_DEBUG_STAMPS); only these are handed the stamp buffer
+};
+template <class K> static Rung<K> rung(K kern, int threads, size_t lds = 0, bool stamped = false) { return {kern, threads, lds, stamped}; }
+// (asked for with every question and every launch: a process may hold handles on several devices)
+template <class K> static void request_lds(const Rung<K> &r) {
+    if (r.lds > 0) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(r.kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)r.lds);
 }
-void small_bwd(const float4 *Ubwd, const float *Why, const float *dY, const float *G, const float *C, float *DG, int N, int S, hipStream_t st) {
-    if (N == 128) hipLaunchKernelGGL((k_small_bwd<128>), dim3(1), dim3(SMALL_BWD_THREADS), 0, st, Ubwd, Why, dY, G, C, DG, S);
-    else hipLaunchKernelGGL((k_small_bwd<64>), dim3(1), dim3(SMALL_BWD_THREADS), 0, st, Ubwd, Why, dY, G, C, DG, S);
+struct Occupancy { // the callable of the questions: workgroups per CU of the rung (0: no rung, or the runtime refused)
+    int per_cu = 0;
+    template <class K> void operator()(const Rung<K> &r) {
+        request_lds(r);
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, r.kern, r.threads, r.lds) != hipSuccess) per_cu = 0;
+    }
+};
+template <class K, class... A> static void launch(const Rung<K> &r, dim3 grid, hipStream_t st, A... args) {
+    request_lds(r);
+    hipLaunchKernelGGL(r.kern, grid, dim3(r.threads), r.lds, st, args...);
+}
+template <class F> static bool with_flag(bool b, F &&f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+
+// k_fwd_persistent (N = 64) / k_fwd_persistent2: FwdForm::Persistent
+template <class F> static bool with_fwd_persistent(int N, bool fast, F &&f) {
+    return with_flag(fast, [&](auto fm) {
+        constexpr bool FAST = decltype(fm)::value;
+        switch (N) {
+        case 64: return f(rung(k_fwd_persistent<1, FAST>, 256)), true;
+        case 128: return f(rung(k_fwd_persistent2<1, FAST>, 512)), true;
+        case 256: return f(rung(k_fwd_persistent2<2, FAST>, 512)), true;
+        case 512: return f(rung(k_fwd_persistent2<4, FAST>, 512)), true;
+        case 1024: return f(rung(k_fwd_persistent2<8, FAST>, 512)), true;
+        default: return false;
+        }
+    });
+}
+// k_fwd_persistent4: FwdForm::Cols8 (the stamped build exists for the headline shape, without fast math)
+template <class F> static bool with_fwd_cols8(int N, bool fast, bool stamp, F &&f) {
+    if (stamp && N == 512) return f(rung(k_fwd_persistent4<2, false, true>, FWD4_THREADS, 0, true)), true;
+    return with_flag(fast, [&](auto fm) {
+        constexpr bool FAST = decltype(fm)::value;
+        switch (N) {
+        case 256: return f(rung(k_fwd_persistent4<1, FAST>, FWD4_THREADS)), true;
+        case 512: return f(rung(k_fwd_persistent4<2, FAST>, FWD4_THREADS)), true;
+        case 1024: return f(rung(k_fwd_persistent4<4, FAST>, FWD4_THREADS)), true;
+        default: return false;
+        }
+    });
+}
+// k_fwd_persistent6: FwdForm::TwoHalf (likewise)
+template <class F> static bool with_fwd_two_half(int N, bool fast, bool stamp, F &&f) {
+    if (stamp && N == 512) return f(rung(k_fwd_persistent6<512, false, true>, FWD4_THREADS, 0, true)), true;
+    return with_flag(fast, [&](auto fm) {
+        constexpr bool FAST = decltype(fm)::value;
+        switch (N) {
+        case 256: return f(rung(k_fwd_persistent6<256, FAST>, FWD4_THREADS)), true;
+        case 512: return f(rung(k_fwd_persistent6<512, FAST>, FWD4_THREADS)), true;
+        default: return false;
+        }
+    });
+}
+// k_fwd_persistent_bf16 (N = 128) / k_fwd_persistent2_bf16 on 8- or 16-column groups: FwdForm::Bf16
+template <int NKS2, bool FAST, class F> static bool fwd2_bf16_rung(int cols, F &&f) {
+    if (cols == 8) f(rung(k_fwd_persistent2_bf16<NKS2, FAST, 8>, 512));
+    else f(rung(k_fwd_persistent2_bf16<NKS2, FAST>, 512));
+    return true;
+}
+template <class F> static bool with_fwd_bf16(int N, bool fast, int cols, F &&f) {
+    return with_flag(fast, [&](auto fm) {
+        constexpr bool FAST = decltype(fm)::value;
+        switch (N) {
+        case 128: return f(rung(k_fwd_persistent_bf16<1, FAST>, 256)), true;
+        case 256: return fwd2_bf16_rung<1, FAST>(cols, f);
+        case 512: return fwd2_bf16_rung<2, FAST>(cols, f);
+        case 1024: return fwd2_bf16_rung<4, FAST>(cols, f);
+        default: return false;
+        }
+    });
+}
+// k_fwd_halves_bf16: FwdForm::Bf16Halves (stamped builds for every shape, without fast math)
+template <int N_, int UW, class F> static bool fwd_halves_bf16_rung(bool fast, bool stamp, F &&f) {
+    using Sh = FwdhbShape<N_, UW>;
+    if (stamp) f(rung(k_fwd_halves_bf16<N_, UW, false, true>, Sh::THREADS, Sh::LDS, true));
+    else if (fast) f(rung(k_fwd_halves_bf16<N_, UW, true>, Sh::THREADS, Sh::LDS));
+    else f(rung(k_fwd_halves_bf16<N_, UW, false>, Sh::THREADS, Sh::LDS));
+    return true;
+}
+template <class F> static bool with_fwd_halves_bf16(int N, bool fast, bool stamp, F &&f) {
+    switch (N) {
+    case 256: return fwd_halves_bf16_rung<256, 16>(fast, stamp, f);
+    case 512: return fwd_halves_bf16_rung<512, 16>(fast, stamp, f);
+    case 1024: return fwd_halves_bf16_rung<1024, 32>(fast, stamp, f);
+    default: return false;
+    }
+}
+// k_bwd_persistent: BwdForm::Persistent (16-column groups on 16x16x4 tiles), Cols8 (4x4x1; fused sums with the dW table in
+// dynamic LDS; stamped builds for the headline shape) and Bf16 (4-, 8- or 16-column groups)
+constexpr size_t DW_TABLE_BYTES = 257 * 64 * sizeof(float);
+template <int NR4W, class F> static bool bwd_persistent_rung(int cols, bool fuse, bool stamp, bool bf16, F &&f) {
+    if (bf16) {
+        if constexpr (NR4W >= 4) {
+            if (cols == 16) f(rung(k_bwd_persistent<NR4W, 16, false, false, true>, 512));
+            else if (cols == 4) f(rung(k_bwd_persistent<NR4W, 4, false, false, true>, 512));
+            else if (fuse) f(rung(k_bwd_persistent<NR4W, 8, true, false, true>, 512, DW_TABLE_BYTES));
+            else f(rung(k_bwd_persistent<NR4W, 8, false, false, true>, 512));
+            return true;
+        }
+        return false;
+    }
+    if (cols != 8) return f(rung(k_bwd_persistent<NR4W, 16, false>, 512)), true;
+    if constexpr (NR4W == 16) {
+        if (stamp) {
+            if (fuse) f(rung(k_bwd_persistent<16, 8, true, true, false, true>, 512, DW_TABLE_BYTES, true));
+            else f(rung(k_bwd_persistent<16, 8, false, true, false, true>, 512, 0, true));
+            return true;
+        }
+    }
+    if (fuse) f(rung(k_bwd_persistent<NR4W, 8, true, false, false, true>, 512, DW_TABLE_BYTES));
+    else f(rung(k_bwd_persistent<NR4W, 8, false, false, false, true>, 512));
+    return true;
+}
+template <class F> static bool with_bwd_persistent(int N, int cols, bool fuse, bool stamp, bool bf16, F &&f) {
+    switch (N) {
+    case 64: return bwd_persistent_rung<2>(cols, fuse, stamp, bf16, f);
+    case 128: return bwd_persistent_rung<4>(cols, fuse, stamp, bf16, f);
+    case 256: return bwd_persistent_rung<8>(cols, fuse, stamp, bf16, f);
+    case 512: return bwd_persistent_rung<16>(cols, fuse, stamp, bf16, f);
+    case 1024: return bwd_persistent_rung<32>(cols, fuse, stamp, bf16, f);
+    default: return false;
+    }
+}
+// k_bwd_scatter: BwdForm::Scatter (stamped builds for the headline shape)
+template <class F> static bool with_bwd_scatter(int N, bool fuse, bool stamp, F &&f) {
+    return with_flag(fuse, [&](auto fu) {
+        constexpr bool FUSE = decltype(fu)::value;
+        constexpr size_t lds = bwdh_lds_bytes(FUSE);
+        if (N == 256) f(rung(k_bwd_scatter<256, FUSE, false>, BWDH_THREADS, lds));
+        else if (N != 512) return false;
+        else if (stamp) f(rung(k_bwd_scatter<512, FUSE, true>, BWDH_THREADS, lds, true));
+        else f(rung(k_bwd_scatter<512, FUSE, false>, BWDH_THREADS, lds));
+        return true;
+    });
+}
+// k_bwd_scatter_bf16: BwdForm::Bf16Scatter (stamped builds for N = 512 and 1024)
+template <class F> static bool with_bwd_scatter_bf16(int N, bool stamp, F &&f) {
+    if (N == 256) f(rung(k_bwd_scatter_bf16<256, 16>, BwdsbShape<256, 16>::THREADS));
+    else if (N == 512 && stamp) f(rung(k_bwd_scatter_bf16<512, 16, true>, BwdsbShape<512, 16>::THREADS, 0, true));
+    else if (N == 512) f(rung(k_bwd_scatter_bf16<512, 16>, BwdsbShape<512, 16>::THREADS));
+    else if (N == 1024 && stamp) f(rung(k_bwd_scatter_bf16<1024, 32, true>, BwdsbShape<1024, 32>::THREADS, 0, true));
+    else if (N == 1024) f(rung(k_bwd_scatter_bf16<1024, 32>, BwdsbShape<1024, 32>::THREADS));
+    else return false;
+    return true;
+}
+// k_small_fwd / k_small_bwd: FwdForm::Small, BwdForm::Small (one workgroup)
+template <class F> static bool with_small_fwd(int N, bool fast, F &&f) {
+    return with_flag(fast, [&](auto fm) {
+        constexpr bool FAST = decltype(fm)::value;
+        switch (N) {
+        case 64: return f(rung(k_small_fwd<64, FAST>, 1024)), true;
+        case 128: return f(rung(k_small_fwd<128, FAST>, 1024)), true;
+        default: return false;
+        }
+    });
+}
+template <class F> static bool with_small_bwd(int N, F &&f) {
+    switch (N) {
+    case 64: return f(rung(k_small_bwd<64>, SMALL_BWD_THREADS)), true;
+    case 128: return f(rung(k_small_bwd<128>, SMALL_BWD_THREADS)), true;
+    default: return false;
+    }
 }
 
-// ---- forward ---------------------------------------------------------------------------------------------------------
+// ---- the launchers: each resolves its rung and launches it with that form's own arguments -----------------------------
+void small_fwd(const float *U, const float *W, const float *bias, float *H, float *C, float *G, const int32_t *xi, int N, int S, bool fast,
+               hipStream_t st) {
+    with_small_fwd(N, fast, [&](auto r) { launch(r, dim3(1), st, U, W, bias, H, C, G, xi, S); });
+}
+void small_bwd(const float4 *Ubwd, const float *Why, const float *dY, const float *G, const float *C, float *DG, int N, int S, hipStream_t st) {
+    with_small_bwd(N, [&](auto r) { launch(r, dim3(1), st, Ubwd, Why, dY, G, C, DG, S); });
+}
+// units of a workgroup of the one-recurrence forward forms: 8 in the second form, 4 in the first
+static int fwd_units(int N) { return fwd_second_form(N) ? 8 : 4; }
+static int fwd_units_bf16(int N) { return N % 256 == 0 ? 8 : 4; }
 void fwd_persistent(const float4 *Ufwd, const float *W, const float *bias, float *H, float *C, float *G,
                     const int32_t *xi, unsigned *cnt, unsigned *abortp, unsigned epoch, int N, int S, int B, bool fast,
                     hipStream_t st) {
-    if (fwd_second_form(N)) {
-        const dim3 grid2(N / 8, (B + 15) / 16), block2(512);
-        switch (N / 128) {
-#define X(k)                                                                                                          \
-    case k:                                                                                                           \
-        if (fast) hipLaunchKernelGGL((k_fwd_persistent2<k, true>), grid2, block2, 0, st, Ufwd, W, bias, H, C, G, xi, cnt, abortp, epoch, S, B); \
-        else hipLaunchKernelGGL((k_fwd_persistent2<k, false>), grid2, block2, 0, st, Ufwd, W, bias, H, C, G, xi, cnt, abortp, epoch, S, B);    \
-        break;
-            X(1) X(2) X(4) X(8)
-#undef X
-        }
-        return;
-    }
-    const dim3 grid(N / 4, (B + 15) / 16), block(256);
-    switch (N / 64) {
-#define X(k)                                                                                                          \
-    case k:                                                                                                           \
-        if (fast) hipLaunchKernelGGL((k_fwd_persistent<k, true>), grid, block, 0, st, Ufwd, W, bias, H, C, G, xi, cnt, abortp, epoch, S, B); \
-        else hipLaunchKernelGGL((k_fwd_persistent<k, false>), grid, block, 0, st, Ufwd, W, bias, H, C, G, xi, cnt, abortp, epoch, S, B);    \
-        break;
-        FWD_CASES(X)
-#undef X
-    }
+    with_fwd_persistent(N, fast, [&](auto r) {
+        launch(r, dim3(N / fwd_units(N), (B + 15) / 16), st, Ufwd, W, bias, H, C, G, xi, cnt, abortp, epoch, S, B);
+    });
 }
 
 int fwd_ring_advance(int ring_base, int S) { return (ring_base + S - 1) & (HX_RING - 1); }
 void fwd_persistent4(const float4 *Ufwd4, const float *W, const float *bias, float *H, float *C, float *G, const int32_t *xi,
                      float *Hx, unsigned *cnt, unsigned *abortp, unsigned epoch, int ring_base, int N, int S, int B, bool fast,
                      int poll_cfg, hipStream_t st, unsigned long long *stamps) {
-    const dim3 grid(N / 16, (B + 7) / 8), block(FWD4_THREADS);
-    if (stamps != nullptr && N == 512) { // diagnostic build of the headline shape
-        hipLaunchKernelGGL((k_fwd_persistent4<2, false, true>), grid, block, 0, st, Ufwd4, W, bias, H, C, G, xi, Hx, cnt, abortp,
-                           epoch, ring_base, S, B, poll_cfg, stamps);
-        return;
-    }
-    switch (N / 256) {
-#define X(k)                                                                                                          \
-    case k:                                                                                                           \
-        if (fast) hipLaunchKernelGGL((k_fwd_persistent4<k, true>), grid, block, 0, st, Ufwd4, W, bias, H, C, G, xi, Hx, cnt, abortp, epoch, ring_base, S, B, poll_cfg, nullptr); \
-        else hipLaunchKernelGGL((k_fwd_persistent4<k, false>), grid, block, 0, st, Ufwd4, W, bias, H, C, G, xi, Hx, cnt, abortp, epoch, ring_base, S, B, poll_cfg, nullptr);    \
-        break;
-        X(1) X(2) X(4)
-#undef X
-    }
+    with_fwd_cols8(N, fast, stamps != nullptr, [&](auto r) {
+        launch(r, dim3(N / 16, (B + 7) / 8), st, Ufwd4, W, bias, H, C, G, xi, Hx, cnt, abortp, epoch, ring_base, S, B, poll_cfg,
+               r.stamped ? stamps : nullptr);
+    });
+}
+
+// One launch of a multi-launch form takes the columns [col0, col0 + cols) of the batch, in groups of GC.  Fewer than 8
+// groups run pinned where the plan allows it: eight groups' worth of workgroups, one group per XCD (see the kernels).
+struct ColumnRange {
+    int groups, first_group, grid_groups;
+    bool pinned;
+};
+static ColumnRange column_range(int col0, int cols, int GC, bool pin) {
+    const int groups = (cols + GC - 1) / GC;
+    const bool pinned = pin && groups < 8;
+    return {groups, col0 / GC, pinned ? 8 : groups, pinned};
 }
 
 // two-half form (k_fwd_persistent6): N = 512 or 256 on the grid of the 8-column form
 void fwd_persistent6(const float4 *Ufwd5, const float *W, const float *bias, float *H, float *C, float *G, const int32_t *xi,
                      float *Hx, unsigned *cnt, unsigned *abortp, unsigned epoch, int ring_base, int N, int S, int B, bool fast,
                      int poll_cfg, int col0, int cols, int GC, bool pin, hipStream_t st, unsigned long long *stamps) {
-    const int NGh = (cols + GC - 1) / GC; // groups of this launch: columns [col0, col0 + cols)
-    const bool pinned = pin && NGh < 8;   // one group per XCD (see the kernel)
-    poll_cfg = (poll_cfg & 0xffff) | (pinned ? NGh << 16 : 0) | ((col0 / GC) << 20) | (GC == 4 ? 1 << 28 : 0);
-    const dim3 grid(N / 16, pinned ? 8 : NGh), block(FWD4_THREADS);
-#define F6_GO(...)                                                                                                            \
-    hipLaunchKernelGGL((k_fwd_persistent6<__VA_ARGS__>), grid, block, 0, st, Ufwd5, W, bias, H, C, G, xi, Hx, cnt, abortp, epoch, \
-                       ring_base, S, B, poll_cfg, stamps)
-    if (N == 512) {
-        if (stamps != nullptr) F6_GO(512, false, true);
-        else if (fast) F6_GO(512, true);
-        else F6_GO(512, false);
-    } else {
-        stamps = nullptr; // (stamped builds exist for the headline shape)
-        if (fast) F6_GO(256, true);
-        else F6_GO(256, false);
-    }
-#undef F6_GO
+    const ColumnRange cr = column_range(col0, cols, GC, pin);
+    poll_cfg = (poll_cfg & 0xffff) | (cr.pinned ? cr.groups << 16 : 0) | (cr.first_group << 20) | (GC == 4 ? 1 << 28 : 0);
+    with_fwd_two_half(N, fast, stamps != nullptr, [&](auto r) {
+        launch(r, dim3(N / 16, cr.grid_groups), st, Ufwd5, W, bias, H, C, G, xi, Hx, cnt, abortp, epoch, ring_base, S, B, poll_cfg,
+               r.stamped ? stamps : nullptr);
+    });
 }
 
 // 8-column groups in the bf16 forward recurrence (second form) when 16-column groups would leave half the CUs idle
@@ -3551,12 +3577,6 @@ void pack_Ufwd6_bf16(const float *U, void *img, int N, hipStream_t st) {
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(k_pack_Ufwd6_bf16, dim3(blocks), dim3(256), 0, st, U, reinterpret_cast<uint2 *>(img), N, fwd_halves_bf16_units(N));
 }
-#define FHB_DISPATCH(GO)                  \
-    do {                                  \
-        if (N == 1024) GO(1024, 32);      \
-        else if (N == 512) GO(512, 16);   \
-        else GO(256, 16);                 \
-    } while (0)
 // columns one launch takes: as many 8-column groups as are co-resident, one workgroup per CU (a wider batch runs as several
 // launches over column ranges -- the streams are independent recurrences)
 // Columns per workgroup: 8 (two alternating halves), or 4 -- one half per workgroup, twice the workgroups -- where the whole
@@ -3570,80 +3590,26 @@ static int bf16_group_cols(int N, int B, int n_cus) {
     if (B % 4 != 0 || (B + 3) / 4 > fit) return 8;
     return BF16_SINGLE_HALF_DEFAULT ? 4 : 8;
 }
-static bool fwd_halves_bf16_supported(int N, int B, int n_cus) {
-    if (N != 256 && N != 512 && N != 1024) return false;
-    if (B % 4 != 0) return false; // 8-byte ring pieces and Hb rows
-    if (n_cus / (N / fwd_halves_bf16_units(N)) < 1) return false;
-    int per_cu = 0;
-#define GO(n, u)                                                                                                                  \
-    per_cu = blocks_per_cu(k_fwd_halves_bf16<n, u, false>, FwdhbShape<n, u>::THREADS, FwdhbShape<n, u>::LDS) > 0 &&               \
-                     blocks_per_cu(k_fwd_halves_bf16<n, u, true>, FwdhbShape<n, u>::THREADS, FwdhbShape<n, u>::LDS) > 0           \
-                 ? 1                                                                                                              \
-                 : 0
-    FHB_DISPATCH(GO);
-#undef GO
-    return per_cu >= 1;
-}
 // one launch: columns [col0, col0 + cols) of the B, cols <= EnginePlan::launch_cols; ring_base is that column range's own
 void fwd_halves_bf16(const void *Ufwd6b, const float *W, const float *bias, float *H, unsigned short *Hb, float *C, float *G,
                      const int32_t *xi, void *Hxb, unsigned *cnt, unsigned *abortp, unsigned epoch, int ring_base, int N, int S,
                      int B, int col0, int cols, int GC, bool pin, bool fast, hipStream_t st, unsigned long long *stamps) {
-    const int NB = N / fwd_halves_bf16_units(N), NG = (cols + GC - 1) / GC;
-    const int pinned = pin && NG < 8;
-    const dim3 grid(pinned ? 8 * NB : NB * NG);
-    const FwdhbArgs args = {reinterpret_cast<const uint2 *>(Ufwd6b), W, bias, H, Hb, C, G, xi, reinterpret_cast<unsigned *>(Hxb), cnt, abortp,
-                            epoch, ring_base, S, B, NG, pinned, col0, GC, stamps};
-#define GO(n, u)                                                                                                               \
-    do {                                                                                                                       \
-        if (stamps) hipLaunchKernelGGL((k_fwd_halves_bf16<n, u, false, true>), grid, dim3(FwdhbShape<n, u>::THREADS), (FwdhbShape<n, u>::LDS), st, args); \
-        else if (fast) hipLaunchKernelGGL((k_fwd_halves_bf16<n, u, true>), grid, dim3(FwdhbShape<n, u>::THREADS), (FwdhbShape<n, u>::LDS), st, args); \
-        else hipLaunchKernelGGL((k_fwd_halves_bf16<n, u, false>), grid, dim3(FwdhbShape<n, u>::THREADS), (FwdhbShape<n, u>::LDS), st, args);     \
-    } while (0)
-    FHB_DISPATCH(GO);
-#undef GO
+    const ColumnRange cr = column_range(col0, cols, GC, pin);
+    with_fwd_halves_bf16(N, fast, stamps != nullptr, [&](auto r) {
+        const FwdhbArgs args = {reinterpret_cast<const uint2 *>(Ufwd6b), W, bias, H, Hb, C, G, xi, reinterpret_cast<unsigned *>(Hxb), cnt, abortp,
+                                epoch, ring_base, S, B, cr.groups, cr.pinned, col0, GC, r.stamped ? stamps : nullptr};
+        launch(r, dim3(N / fwd_halves_bf16_units(N) * cr.grid_groups), st, args);
+    });
 }
-#undef FHB_DISPATCH
 
 void fwd_persistent_bf16(const void *Ufwd16, const float *W, const float *bias, float *H, unsigned short *Hb, float *C,
                          float *G, const int32_t *xi, unsigned *cnt, unsigned *abortp, unsigned epoch, int N, int S, int B,
                          bool fast, int cols, hipStream_t st) {
-    const u32x4 *U16 = reinterpret_cast<const u32x4 *>(Ufwd16);
-    if (N % 256 == 0) {
-        if (cols == 8) {
-            const dim3 grid8(N / 8, (B + 7) / 8), block2(512);
-            switch (N / 256) {
-#define X(k)                                                                                                             \
-    case k:                                                                                                              \
-        if (fast) hipLaunchKernelGGL((k_fwd_persistent2_bf16<k, true, 8>), grid8, block2, 0, st, U16, W, bias, H, Hb, C, G, xi, cnt, abortp, epoch, S, B); \
-        else hipLaunchKernelGGL((k_fwd_persistent2_bf16<k, false, 8>), grid8, block2, 0, st, U16, W, bias, H, Hb, C, G, xi, cnt, abortp, epoch, S, B);    \
-        break;
-                X(1) X(2) X(4)
-#undef X
-            }
-            return;
-        }
-        const dim3 grid2(N / 8, (B + 15) / 16), block2(512);
-        switch (N / 256) {
-#define X(k)                                                                                                             \
-    case k:                                                                                                              \
-        if (fast) hipLaunchKernelGGL((k_fwd_persistent2_bf16<k, true>), grid2, block2, 0, st, U16, W, bias, H, Hb, C, G, xi, cnt, abortp, epoch, S, B); \
-        else hipLaunchKernelGGL((k_fwd_persistent2_bf16<k, false>), grid2, block2, 0, st, U16, W, bias, H, Hb, C, G, xi, cnt, abortp, epoch, S, B);    \
-        break;
-            X(1) X(2) X(4)
-#undef X
-        }
-        return;
-    }
-    const dim3 grid(N / 4, (B + 15) / 16), block(256);
-    switch (N / 128) {
-#define X(k)                                                                                                             \
-    case k:                                                                                                              \
-        if (fast) hipLaunchKernelGGL((k_fwd_persistent_bf16<k, true>), grid, block, 0, st, U16, W, bias, H, Hb, C, G, xi, cnt, abortp, epoch, S, B); \
-        else hipLaunchKernelGGL((k_fwd_persistent_bf16<k, false>), grid, block, 0, st, U16, W, bias, H, Hb, C, G, xi, cnt, abortp, epoch, S, B);    \
-        break;
-        X(1) X(2) X(4) X(8)
-#undef X
-    }
+    const int gc = N % 256 == 0 && cols == 8 ? 8 : 16; // columns of a group (the first form has 16-column groups only)
+    with_fwd_bf16(N, fast, gc, [&](auto r) {
+        launch(r, dim3(N / fwd_units_bf16(N), (B + gc - 1) / gc), st, reinterpret_cast<const u32x4 *>(Ufwd16), W, bias, H, Hb, C, G, xi, cnt,
+               abortp, epoch, S, B);
+    });
 }
 
 // ---- backward --------------------------------------------------------------------------------------------------------
@@ -3657,50 +3623,17 @@ int bwds_ring_advance(int ring_base, int S) {
     return (ring_base - (S - 2)) & (HX_RING - 1);
 }
 
-// scatter form of the backward recurrence (k_bwd_scatter): the shapes of the two-half form
-static bool bwd_scatter_supported(int N, int B, int n_cus, bool fused) {
-    if ((N != 512 && N != 256) || bwd_group_cols(N, B, n_cus) != 8) return false;
-    const int lg = two_half_launch_cols(N, n_cus) / 8, ng = (B + 7) / 8;
-    const size_t grid = (size_t)(N / 16) * (ng < lg ? ng : lg); // of one launch
-    int per_cu = 0;
-    if (N == 512)
-        per_cu = fused ? blocks_per_cu(k_bwd_scatter<512, true>, BWDH_THREADS, bwdh_lds_bytes(true))
-                       : blocks_per_cu(k_bwd_scatter<512, false>, BWDH_THREADS, bwdh_lds_bytes(false));
-    else
-        per_cu = fused ? blocks_per_cu(k_bwd_scatter<256, true>, BWDH_THREADS, bwdh_lds_bytes(true))
-                       : blocks_per_cu(k_bwd_scatter<256, false>, BWDH_THREADS, bwdh_lds_bytes(false));
-    return per_cu >= 1 && grid <= (size_t)n_cus;
-}
 void bwd_scatter(const float4 *Ubwd6, float *DG, const float *Why, const float *dY, const float *G, const float *C, const float *H,
                  const int32_t *xi, float *gpart, float *Qx, unsigned *cnt, unsigned *abortp, unsigned epoch, int ring_base, int N,
                  int S, int B, int cfg, int col0, int cols, int GC, bool pin, hipStream_t st, unsigned long long *stamps) {
-    // fewer than 8 groups: pinned launch, one group per XCD (see BWDH_COMMON); pin is off with cfg bit 16 (spread mapping, tests)
-    const int NGh = (cols + GC - 1) / GC; // groups of this launch: columns [col0, col0 + cols)
-    cfg = (cfg & 0xffff) | ((col0 / GC) << 20) | (GC == 4 ? 1 << 28 : 0);
-    const bool pinned = pin && NGh < 8;
-    if (pinned) cfg |= NGh << 16;
-    const dim3 grid(N / 16, pinned ? 8 : NGh), block(BWDH_THREADS);
-    const bool fuse = gpart != nullptr;
-    const size_t lds = bwdh_lds_bytes(fuse);
-#define BS_GO(...)                                                                                                                   \
-    do {                                                                                                                             \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_bwd_scatter<__VA_ARGS__>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                  (int)lds);                                                                                         \
-        hipLaunchKernelGGL((k_bwd_scatter<__VA_ARGS__>), grid, block, lds, st, args);                                                \
-    } while (0)
-    const BwdhArgs args = {Ubwd6, DG, Why, dY, G, C, H, xi, gpart, Qx, cnt, abortp, epoch, ring_base, S, B, cfg,
-                           N == 512 ? stamps : nullptr};
-    if (N == 256) {
-        if (fuse) BS_GO(256, true, false);
-        else BS_GO(256, false, false);
-    } else if (stamps != nullptr) {
-        if (fuse) BS_GO(512, true, true);
-        else BS_GO(512, false, true);
-    } else if (fuse)
-        BS_GO(512, true, false);
-    else
-        BS_GO(512, false, false);
-#undef BS_GO
+    // pin is off with cfg bit 16 (spread mapping, tests)
+    const ColumnRange cr = column_range(col0, cols, GC, pin);
+    cfg = (cfg & 0xffff) | (cr.pinned ? cr.groups << 16 : 0) | (cr.first_group << 20) | (GC == 4 ? 1 << 28 : 0);
+    with_bwd_scatter(N, gpart != nullptr, stamps != nullptr, [&](auto r) {
+        const BwdhArgs args = {Ubwd6, DG, Why, dY, G, C, H, xi, gpart, Qx, cnt, abortp, epoch, ring_base, S, B, cfg,
+                               r.stamped ? stamps : nullptr};
+        launch(r, dim3(N / 16, cr.grid_groups), st, args);
+    });
 }
 
 // bf16 scatter form (k_bwd_scatter_bf16): N = 256 / 512 / 1024, 8-column groups.  Hidden 1024 runs 32 units to a workgroup so
@@ -3710,84 +3643,108 @@ void bwd_scatter(const float4 *Ubwd6, float *DG, const float *Why, const float *
 int bwd_scatter_bf16_units(int N) { return N == 1024 ? 32 : 16; }
 // publication number of the next launch's first hand-off (slot = low two bits, parity = bit 2)
 int bwd_scatter_bf16_ring_advance(int base, int S) { return (base + (S > 2 ? S - 2 : 0)) & 7; }
-static bool bwd_scatter_bf16_supported(int N, int n_cus) {
-    if (N != 256 && N != 512 && N != 1024) return false;
-    if (n_cus / (N / bwd_scatter_bf16_units(N)) < 1) return false;
-    int per_cu = 0;
-    if (N == 1024) per_cu = blocks_per_cu(k_bwd_scatter_bf16<1024, 32>, BwdsbShape<1024, 32>::THREADS);
-    else if (N == 512) per_cu = blocks_per_cu(k_bwd_scatter_bf16<512, 16>, BwdsbShape<512, 16>::THREADS);
-    else per_cu = blocks_per_cu(k_bwd_scatter_bf16<256, 16>, BwdsbShape<256, 16>::THREADS);
-    return per_cu >= 1;
-}
 // one launch: columns [col0, col0 + cols) of the B, cols <= EnginePlan::launch_cols
 void bwd_scatter_bf16(const void *Ubwd6b, float *DG, const float *DHy, const float *G, const float *C, float *Qx, unsigned *cnt,
                       unsigned *abortp, unsigned epoch, int ring_base, int N, int S, int B, int col0, int cols, int GC, bool pin,
                       hipStream_t st, unsigned long long *stamps, unsigned short *DGt_b, int Tpad) {
-    const int NB = N / bwd_scatter_bf16_units(N), NG = (cols + GC - 1) / GC;
-    const int pinned = pin && NG < 8;
-    const dim3 grid(pinned ? 8 * NB : NB * NG);
-    const BwdsbArgs args = {reinterpret_cast<const uint2 *>(Ubwd6b), DG, DHy, G, C, Qx, cnt, abortp, epoch, ring_base, S, B, NG, pinned, col0, GC, DGt_b, Tpad, stamps};
-    if (N == 1024 && stamps) hipLaunchKernelGGL((k_bwd_scatter_bf16<1024, 32, true>), grid, dim3(BwdsbShape<1024, 32>::THREADS), 0, st, args);
-    else if (N == 1024) hipLaunchKernelGGL((k_bwd_scatter_bf16<1024, 32>), grid, dim3(BwdsbShape<1024, 32>::THREADS), 0, st, args);
-    else if (N == 512 && stamps) hipLaunchKernelGGL((k_bwd_scatter_bf16<512, 16, true>), grid, dim3(BwdsbShape<512, 16>::THREADS), 0, st, args);
-    else if (N == 512) hipLaunchKernelGGL((k_bwd_scatter_bf16<512, 16>), grid, dim3(BwdsbShape<512, 16>::THREADS), 0, st, args);
-    else hipLaunchKernelGGL((k_bwd_scatter_bf16<256, 16>), grid, dim3(BwdsbShape<256, 16>::THREADS), 0, st, args);
+    const ColumnRange cr = column_range(col0, cols, GC, pin);
+    with_bwd_scatter_bf16(N, stamps != nullptr, [&](auto r) {
+        const BwdsbArgs args = {reinterpret_cast<const uint2 *>(Ubwd6b), DG, DHy, G, C, Qx, cnt, abortp, epoch, ring_base, S, B, cr.groups,
+                                cr.pinned, col0, GC, DGt_b, Tpad, r.stamped ? stamps : nullptr};
+        launch(r, dim3(N / bwd_scatter_bf16_units(N) * cr.grid_groups), st, args);
+    });
 }
 
+// DGb != null: the bf16 recurrence (Ubwd is the Ubwd16 image); cols == 8 in fp32: Ubwd is the 4x4x1 image (BwdForm::Cols8)
 void bwd_persistent(const float4 *Ubwd, float *DG, const float *DHy, const float *G, const float *C, const float *H,
                     const int32_t *xi, float *gpart, const float *Why, const float *dY, unsigned *cnt, unsigned *abortp,
                     unsigned epoch, int N, int S, int B, int cols, bool spread_groups, hipStream_t st, unsigned long long *stamps,
                     unsigned short *DGb) {
-    const dim3 grid(N / 16, (B + cols - 1) / cols), block(512);
-    const bool fuse = gpart != nullptr;
-    const size_t lds = fuse ? DW_TABLE_BYTES : 0;
     const int spread = spread_groups ? 1 : 0; // test hook: keep the dispatch-order workgroup mapping (groups over all XCDs)
-#define BWD_GO(...)                                                                                                    \
-    do {                                                                                                               \
-        if (fuse) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_bwd_persistent<__VA_ARGS__>),           \
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)DW_TABLE_BYTES);          \
-        hipLaunchKernelGGL((k_bwd_persistent<__VA_ARGS__>), grid, block, lds, st, Ubwd, DG, DHy, G, C, H, xi, gpart, Why, dY, cnt, \
-                           abortp, epoch, S, B, spread, stamps, DGb);                                                  \
-    } while (0)
-    if (DGb != nullptr) { // bf16 recurrence: 8- or 16-column groups, 16x16x32 tiles, counter hand-off
-        switch (N / 32) {
-#define X(k)                                                  \
-    case k:                                                   \
-        if (cols == 16) BWD_GO(k, 16, false, false, true);    \
-        else if (cols == 4) BWD_GO(k, 4, false, false, true); \
-        else if (fuse) BWD_GO(k, 8, true, false, true);       \
-        else BWD_GO(k, 8, false, false, true);                \
-        break;
-            X(4) X(8) X(16) X(32)
-#undef X
-        }
-        return;
+    with_bwd_persistent(N, cols, gpart != nullptr, stamps != nullptr, DGb != nullptr, [&](auto r) {
+        launch(r, dim3(N / 16, (B + cols - 1) / cols), st, Ubwd, DG, DHy, G, C, H, xi, gpart, Why, dY, cnt, abortp, epoch, S, B, spread,
+               r.stamped ? stamps : nullptr, DGb);
+    });
+}
+
+// ---- the occupancy questions -----------------------------------------------------------------------------------------
+// All workgroups of a recurrence wait on each other, so its grid must be co-resident.  The occupancy API is asked about
+// exactly the instantiation that will be launched, with its dynamic LDS (the resolvers above see to that: `fast` and
+// `stamp` are the handle's LSTM_HIP_FAST_MATH and LSTM_HIP_DEBUG_STAMPS); it can over-report by one block per CU
+// (MI355X_MICROARCH.md, residency), so one is taken off wherever more than one is claimed.
+static bool grid_fits(size_t grid, int per_cu, int n_cus) {
+    if (per_cu > 1) per_cu -= 1;
+    if (per_cu > 8) per_cu = 8;
+    return per_cu >= 1 && grid <= (size_t)per_cu * n_cus;
+}
+// scatter form of the backward recurrence (k_bwd_scatter): the shapes of the two-half form
+static bool bwd_scatter_supported(int N, int B, int n_cus, bool fused, bool stamp) {
+    if ((N != 512 && N != 256) || bwd_group_cols(N, B, n_cus) != 8) return false;
+    const int lg = two_half_launch_cols(N, n_cus) / 8, ng = (B + 7) / 8;
+    const size_t grid = (size_t)(N / 16) * (ng < lg ? ng : lg); // of one launch
+    Occupancy bwd;
+    with_bwd_scatter(N, fused, stamp, bwd);
+    return bwd.per_cu >= 1 && grid <= (size_t)n_cus;
+}
+static bool persistent_supported(int N, int B, int n_cus, bool fused, bool fast, bool stamp) {
+    if (N % 64 != 0 || N > 1024) return false;
+    Occupancy half, fwd, bwd;
+    if (two_half_wide(N, B, n_cus)) // several launches per direction: the two-half forms or nothing
+        return with_fwd_two_half(N, fast, stamp, half) && half.per_cu >= 1 && bwd_scatter_supported(N, B, n_cus, fused, stamp);
+    size_t fwd_grid = 0;
+    if (fwd_uses_8col_form(N, B, n_cus)) { // N = 256, 512: the two-half form too (LSTM_HIP_FWD_HALVES picks either)
+        fwd_grid = (size_t)(N / 16) * ((B + 7) / 8);
+        if (with_fwd_two_half(N, fast, stamp, half) && half.per_cu < 1) return false;
+        with_fwd_cols8(N, fast, stamp, fwd);
+    } else {
+        fwd_grid = (size_t)(N / fwd_units(N)) * ((B + 15) / 16);
+        if (!with_fwd_persistent(N, fast, fwd)) return false;
     }
-    if (cols == 8) { // Ubwd is the 4x4x1 image here (BwdForm::Cols8)
-        if (stamps != nullptr && N == 512) { // diagnostic build of the headline shape
-            if (fuse) BWD_GO(16, 8, true, true, false, true);
-            else BWD_GO(16, 8, false, true, false, true);
-            return;
-        }
-        stamps = nullptr;
-        switch (N / 32) {
-#define X(k)                                                                   \
-    case k:                                                                    \
-        if (fuse) BWD_GO(k, 8, true, false, false, true);                      \
-        else BWD_GO(k, 8, false, false, false, true);                          \
-        break;
-            X(2) X(4) X(8) X(16) X(32)
-#undef X
-        }
-        return;
-    }
-    stamps = nullptr;
-    switch (N / 32) { // 16-column groups on 16x16x4 tiles (batches too large for 8-column groups on one workgroup per CU)
-#define X(k) case k: BWD_GO(k, 16, false); break;
-        BWD_CASES(X)
-#undef X
-    }
-#undef BWD_GO
+    const int cols = bwd_group_cols(N, B, n_cus);
+    if (!with_bwd_persistent(N, cols, fused && cols == 8, stamp, false, bwd)) return false;
+    return grid_fits(fwd_grid, fwd.per_cu, n_cus) && grid_fits((size_t)(N / 16) * ((B + cols - 1) / cols), bwd.per_cu, n_cus);
+}
+// the bf16 recurrence launches other instantiations on other grids: 8-column groups in the backward recurrence when they
+// are co-resident (bwd_group_cols_bf16), else 16-column groups two workgroups to a CU
+static int bwd_bf16_blocks(int N, int cols, bool fused) {
+    Occupancy bwd;
+    with_bwd_persistent(N, cols, fused, false, true, bwd);
+    return bwd.per_cu;
+}
+static int bwd_group_cols_bf16(int N, int B, int n_cus, bool fused) {
+    // 4-column groups when even 8-column groups would leave half the CUs idle (BASELINE configs[4]: hidden 1024, 16 streams
+    // per GPU = 128 workgroups of 8 columns): twice the CUs, each pulling and multiplying half as much per step
+    if (!fused && B % 4 == 0 && (size_t)(N / 16) * ((B + 7) / 8) * 2 <= (size_t)n_cus &&
+        grid_fits((size_t)(N / 16) * (B / 4), bwd_bf16_blocks(N, 4, false), n_cus))
+        return 4;
+    if (grid_fits((size_t)(N / 16) * ((B + 7) / 8), bwd_bf16_blocks(N, 8, fused), n_cus)) return 8;
+    return 16;
+}
+static bool persistent_supported_bf16(int N, int B, int n_cus, bool fused, bool fast) {
+    if (N % 128 != 0 || N > 1024) return false;
+    // (the forward question is put about the group width that will be launched and its grid; fwd_bf16_cols picks 8 only
+    // where that grid is at most n_cus, so there the answer is "does one workgroup fit", as for the 16-column grid before)
+    const int fwd_cols = fwd_bf16_cols(N, B, n_cus);
+    Occupancy fwd;
+    with_fwd_bf16(N, fast, fwd_cols, fwd);
+    const int cols = bwd_group_cols_bf16(N, B, n_cus, fused);
+    return grid_fits((size_t)(N / fwd_units_bf16(N)) * ((B + fwd_cols - 1) / fwd_cols), fwd.per_cu, n_cus) &&
+           grid_fits((size_t)(N / 16) * ((B + cols - 1) / cols), bwd_bf16_blocks(N, cols, fused && cols == 8), n_cus);
+}
+// The bf16 two-half forms, one workgroup per CU.  A handle launches their stamped builds only if it ends up on both of
+// them, so with `stamp` the question is put about the stamped and the plain instantiation.
+static bool fwd_halves_bf16_supported(int N, int B, int n_cus, bool fast, bool stamp) {
+    Occupancy plain, stamped;
+    if (B % 4 != 0) return false; // 8-byte ring pieces and Hb rows
+    if (!with_fwd_halves_bf16(N, fast, false, plain)) return false; // N = 256, 512, 1024
+    if (n_cus / (N / fwd_halves_bf16_units(N)) < 1) return false;
+    return plain.per_cu >= 1 && (!stamp || (with_fwd_halves_bf16(N, fast, true, stamped) && stamped.per_cu >= 1));
+}
+static bool bwd_scatter_bf16_supported(int N, int n_cus, bool stamp) {
+    Occupancy plain, stamped;
+    if (!with_bwd_scatter_bf16(N, false, plain)) return false; // N = 256, 512, 1024
+    if (n_cus / (N / bwd_scatter_bf16_units(N)) < 1) return false;
+    return plain.per_cu >= 1 && (!stamp || (with_bwd_scatter_bf16(N, true, stamped) && stamped.per_cu >= 1));
 }
 
 // ---- the engine plan: which form each recurrence of a handle runs, decided once at create ------------------------------
@@ -3814,14 +3771,15 @@ EnginePlan plan_engine(int N, int B, unsigned flags, int n_cus) {
         p.epoch_limit = (unsigned)v;
     }
     const bool step = (flags & LSTM_HIP_STEP_KERNELS) != 0;
+    const bool fast = (flags & LSTM_HIP_FAST_MATH) != 0, stamp = (flags & LSTM_HIP_DEBUG_STAMPS) != 0; // choose instantiations
     if (flags & LSTM_HIP_BF16_RECURRENCE) { // every product is a bf16 GEMM of its own, nothing is fused into the recurrence
         if (step || N % 128 != 0 || N > 1024)
             return refuse("LSTM_HIP_BF16_RECURRENCE needs the persistent engine and N a multiple of 128, <= 1024 (N=%d, B=%d)", N, B);
         if (B % 8 != 0)
             return refuse("LSTM_HIP_BF16_RECURRENCE needs a multiple of 8 streams (16-byte aligned bf16 operand rows); B=%d", B);
         // the two-half forms (one workgroup per CU, 8-column groups) or, where a shape has none, the one-recurrence forms
-        const bool halves = fwd_halves_bf16_supported(N, B, n_cus), scatter = bwd_scatter_bf16_supported(N, n_cus);
-        const bool older = persistent_supported_bf16(N, B, n_cus, false);
+        const bool halves = fwd_halves_bf16_supported(N, B, n_cus, fast, stamp), scatter = bwd_scatter_bf16_supported(N, n_cus, stamp);
+        const bool older = persistent_supported_bf16(N, B, n_cus, false, fast);
         if (!(halves && scatter) && !older)
             return refuse("LSTM_HIP_BF16_RECURRENCE: the bf16 recurrence grids for N=%d, B=%d are not co-resident on %d CUs", N, B, n_cus);
         p.fwd = halves && !(older && fwd_halves == 0) ? FwdForm::Bf16Halves : FwdForm::Bf16;
@@ -3844,7 +3802,7 @@ EnginePlan plan_engine(int N, int B, unsigned flags, int n_cus) {
         p.hxb_halfwords = p.fwd == FwdForm::Bf16Halves ? (size_t)HX_RING * N * B : 0; // bf16 h of every step slot
         p.dgx_floats = p.bwd == BwdForm::Bf16Scatter ? bwdsb_ring_floats(N, bwd_scatter_bf16_units(N), B) : 0; // a region per group
         p.u16 = p.fwd == FwdForm::Bf16 || p.bwd == BwdForm::Bf16;
-        p.stamps = (flags & LSTM_HIP_DEBUG_STAMPS) && p.fwd == FwdForm::Bf16Halves && p.bwd == BwdForm::Bf16Scatter;
+        p.stamps = stamp && p.fwd == FwdForm::Bf16Halves && p.bwd == BwdForm::Bf16Scatter;
         return p;
     }
     // one stream at hidden <= 128 (the reference's default shape): single-CU recurrences, unfused sums.  Fused sums up to
@@ -3852,7 +3810,7 @@ EnginePlan plan_engine(int N, int B, unsigned flags, int n_cus) {
     const bool small = !step && small_recurrence_supported(N, B);
     const bool want_fused = !(flags & LSTM_HIP_NO_FUSED_GRADS) && N <= 512 && !small;
     p.du_split = env_int("LSTM_HIP_DU_SPLIT", 0) != 0;
-    if (step || !persistent_supported(N, B, n_cus, want_fused)) return p;
+    if (step || !persistent_supported(N, B, n_cus, want_fused, fast, stamp)) return p;
     if (small) {
         p.fwd = FwdForm::Small, p.bwd = BwdForm::Small;
         return p;
@@ -3862,7 +3820,7 @@ EnginePlan plan_engine(int N, int B, unsigned flags, int n_cus) {
     else p.fwd = (N == 512 || N == 256) && (fwd_halves != 0 || wide) ? FwdForm::TwoHalf : FwdForm::Cols8;
     p.bwd_cols = bwd_group_cols(N, B, n_cus);
     if (p.bwd_cols != 8) p.bwd = BwdForm::Persistent;
-    else p.bwd = (bwd_halves != 0 || wide) && bwd_scatter_supported(N, B, n_cus, want_fused) ? BwdForm::Scatter : BwdForm::Cols8;
+    else p.bwd = (bwd_halves != 0 || wide) && bwd_scatter_supported(N, B, n_cus, want_fused, stamp) ? BwdForm::Scatter : BwdForm::Cols8;
     p.fused = want_fused && p.bwd_cols == 8;
     if (p.fwd == FwdForm::TwoHalf || p.bwd == BwdForm::Scatter)
         p.launch_cols = two_half_launch_cols(N, n_cus), p.group_cols = two_half_group_cols(N, B, n_cus);
@@ -3880,7 +3838,7 @@ EnginePlan plan_engine(int N, int B, unsigned flags, int n_cus) {
     p.adagrad_quad = p.fwd == FwdForm::TwoHalf && p.bwd == BwdForm::Scatter;
     p.hx_floats = p.ufwd4() ? (size_t)HX_RING * N * B : 0;
     p.dgx_floats = p.bwd == BwdForm::Scatter ? bwd_ring_floats(N, B) : 0;
-    p.stamps = (flags & LSTM_HIP_DEBUG_STAMPS) && N == 512 && p.ufwd4() && p.ubwd4();
+    p.stamps = stamp && N == 512 && p.ufwd4() && p.ubwd4(); // (at N = 512 the two go together: the stamped builds were asked about)
     return p;
 }
 } // namespace lstmk

@@ -21,7 +21,7 @@ from oracle_lib import split_params
 from input_stats_cases import FWD_STEP, BWD_STEP, TOL_FP32, ReferencePool, assert_plan, check_window, selected_cases  # noqa: F401
 
 CH = 8                                   # k-steps of 16 per operand chunk of k_fwd_step and k_bwd_step (csrc/kernels.hip)
-PERSISTENT_WIDTHS = (64, 128, 256, 512, 1024)   # FWD_CASES x 64 and BWD_CASES x 32 (csrc/persistent.hip)
+PERSISTENT_WIDTHS = (64, 128, 256, 512, 1024)   # the widths with_fwd_persistent and with_bwd_persistent resolve (csrc/persistent.hip)
 STEP = dict(fwd=FWD_STEP, bwd=BWD_STEP)
 LR = 0.1                                 # the Adagrad step of every case, as test_hip_parity.py::test_window_matches_oracle
 

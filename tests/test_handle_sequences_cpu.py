@@ -304,8 +304,9 @@ def test_the_mirrored_constants_are_the_sources():
     for fn in ("persistent_supported", "persistent_supported_bf16"):
         body = src[src.index(f"static bool {fn}(int N"):]
         assert re.match(r"[^\n]*\n\s*if \(N % \d+ != 0 \|\| N > 1024\) return false;", body), fn
-    assert "const dim3 grid(N / 16, (B + cols - 1) / cols), block(512);" in src   # bwd_persistent's grid: NBK = N / 16
-    assert set(map(int, re.findall(r"BWD_GO\(k, (\d+),", src))) == set(GROUP_COLS)
+    assert "launch(r, dim3(N / 16, (B + cols - 1) / cols), st, Ubwd, DG, DHy," in src   # bwd_persistent's grid: NBK = N / 16
+    rungs = re.findall(r"rung\(k_bwd_persistent<(?:NR4W|16), (\d+), [^>]*>, (\d+)", src)   # its resolver: columns, block size
+    assert len(rungs) == 9 and {int(c) for c, _ in rungs} == set(GROUP_COLS) and {t for _, t in rungs} == {"512"}
     assert src.count("epoch << 4) | (__builtin_amdgcn_s_getreg") == src.count("<< 4) | (__builtin_amdgcn_s_getreg") == 6   # the XCC table
     # the limit: default 2^26 in the plan, read at create, and nothing else decides when the counters are cleared
     assert "unsigned epoch_limit = 1u << 26;" in open(os.path.join(CSRC, "kernels.h")).read()

@@ -49,13 +49,16 @@ def test_step_kernels_stream_their_operands_in_chunks_of_CH():
 
 def test_persistent_widths_match_the_plan_source():
     src = _src("persistent.hip")
-    fwd = [int(k) for k in re.findall(r"X\((\d+)\)", re.search(r"#define FWD_CASES\(X\)(.*)", src).group(1))]
-    bwd = [int(k) for k in re.findall(r"X\((\d+)\)", re.search(r"#define BWD_CASES\(X\)(.*)", src).group(1))]
-    assert tuple(64 * k for k in fwd) == tuple(32 * k for k in bwd) == hwc.PERSISTENT_WIDTHS
-    body = _body(src, "static bool persistent_supported(int N, int B, int n_cus, bool fused)")
+    # the resolvers of the fp32 one-recurrence forms name the widths that have an instantiation, and refuse every other
+    fwd_rungs = _body(src, "template <class F> static bool with_fwd_persistent(int N, bool fast, F &&f)")
+    bwd_rungs = _body(src, "template <class F> static bool with_bwd_persistent(int N, int cols, bool fuse, bool stamp, bool bf16, F &&f)")
+    for rungs in (fwd_rungs, bwd_rungs):
+        assert tuple(int(n) for n in re.findall(r"case (\d+): return ", rungs)) == hwc.PERSISTENT_WIDTHS
+        assert "default: return false;" in rungs
+    body = _body(src, "static bool persistent_supported(int N, int B, int n_cus, bool fused, bool fast, bool stamp)")
     assert "if (N % 64 != 0 || N > 1024) return false;" in body
-    assert re.search(r"switch \(N / 64\) \{.*?FWD_CASES\(X\).*?default: return false;", body, re.S)
-    assert re.search(r"switch \(N / 32\) \{.*?BWD_CASES\(X\).*?default: return false;", body, re.S)
+    assert "if (!with_fwd_persistent(N, fast, fwd)) return false;" in body
+    assert "if (!with_bwd_persistent(N, cols, fused && cols == 8, stamp, false, bwd)) return false;" in body
 
 
 def test_evaluator_and_sampler_lds_request_matches_the_source():
