@@ -347,6 +347,13 @@ void pad_copy(const float *src, float *dst, const PadMap &map, bool to_padded, h
 //      of 256 threads stride over them in float4.  Plain vector loads and stores only.
 void average(const float *p, float *a, size_t n, float w, bool copy, int cus, hipStream_t st);
 
+// ---- weight drop (lstm_hip_set_weight_drop; the rule is weight_drop.h): dst <- keep ? src * scale : +0.0f over the internal
+//      4Np x Np matrix U, whose logical part is 4Nl x Nl (Nl <= Np, Np % 16 == 0); padding entries are written as 0.  src
+//      and dst are 16-byte aligned and either equal or disjoint.  One launch of at most 8 * cus workgroups of 256 threads,
+//      plain vector loads and stores only.  Used on P.U -> Ue before the packers and on dP.U in place behind the dU product.
+void weight_drop_mask(const float *src, float *dst, int Np, int Nl, uint64_t seed, uint64_t t, uint32_t thr, float scale, int cus,
+                      hipStream_t st);
+
 // ---- B = 1 recurrence for the evaluator / sampler (OV/lstm_eigen_class_CUDA/lstm.cc:578-720)
 // One workgroup with b1_lds_bytes(N) of dynamic LDS, which the caller checks against the device's opt-in limit first; both
 // return the status of the grant and of the launch.

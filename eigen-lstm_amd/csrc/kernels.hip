@@ -7,6 +7,7 @@
 //   v_mfma_f32_16x16x4_f32 : A[i=l&15][k=l>>4], B[k=l>>4][j=l&15], D[row=(l>>4)*4+reg][col=l&15]
 //   v_mfma_f32_32x32x2_f32 : A[i=l&31][k=l>>5], B[k=l>>5][j=l&31], D[row=(reg&3)+8*(reg>>2)+4*(l>>5)][col=l&31]
 #include "kernels.h"
+#include "weight_drop.h"
 
 #include <cstdlib>
 
@@ -2860,6 +2861,53 @@ void average(const float *p, float *a, size_t n, float w, bool copy, int cus, hi
     const int blocks = (int)(want < 1 ? 1 : want > cap ? cap : want);
     if (copy) hipLaunchKernelGGL(k_average<true>, dim3(blocks), dim3(256), 0, st, p, a, n, w);
     else hipLaunchKernelGGL(k_average<false>, dim3(blocks), dim3(256), 0, st, p, a, n, w);
+}
+
+// ------------------------------------------------------------------------------------------------
+// weight_drop: DropConnect on U (kernels.h).  Grid-stride over the internal 4Np x Np matrix in float4:
+// four consecutive rows of one gate block and one column (Np % 16 == 0), 16 bytes read and 16 written per lane, lanes of a
+// wave on consecutive float4.  Element (g * Nl + j, k) of the logical matrix has the number e = g * Nl + j + 4 Nl k and takes
+// word e & 3 of the Philox call of quad e >> 2 (weight_drop.h).  Unpadded (Nl == Np) the four e of a float4 are one quad: one
+// call.  Padded, g * Nl need not be a multiple of 4 and the float4 can span two quads: the call is remade when the quad
+// changes, twice at the most.  Padding entries (j >= Nl or k >= Nl) are written as +0.0f whatever src holds.  The product is a
+// plain expression under this file's fp contract(off): one v_mul_f32, what NumPy's float32 multiply gives.  src == dst is
+// allowed (every float4 is read and written by the same lane).
+__global__ __launch_bounds__(256) void k_weight_drop(const float *src, float *dst, int Np, int Nl, uint64_t seed, uint64_t t,
+                                                     uint32_t thr, float scale) {
+    const size_t n4 = (size_t)Np * Np;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+        const int k = (int)(i / Np), rp = 4 * (int)(i - (size_t)k * Np), g = rp / Np, j0 = rp - g * Np;
+        float4 out = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (k < Nl && j0 < Nl) {
+            const float4 v = reinterpret_cast<const float4 *>(src)[i];
+            const float in[4] = {v.x, v.y, v.z, v.w};
+            float o[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            const uint64_t e0 = (uint64_t)g * Nl + j0 + (uint64_t)4 * Nl * k;
+            uint64_t quad = e0 >> 2;
+            weight_drop::Words w = weight_drop::quad_words(quad, seed, t);
+#pragma unroll
+            for (int c = 0; c < 4; c++) {
+                const uint64_t e = e0 + c;
+                if (j0 + c < Nl) {
+                    if ((e >> 2) != quad) {
+                        quad = e >> 2;
+                        w = weight_drop::quad_words(quad, seed, t);
+                    }
+                    const uint32_t word = (e & 3) == 0 ? w.w[0] : (e & 3) == 1 ? w.w[1] : (e & 3) == 2 ? w.w[2] : w.w[3];
+                    if (weight_drop::keep_word(word, thr)) o[c] = in[c] * scale;
+                }
+            }
+            out = make_float4(o[0], o[1], o[2], o[3]);
+        }
+        reinterpret_cast<float4 *>(dst)[i] = out;
+    }
+}
+void weight_drop_mask(const float *src, float *dst, int Np, int Nl, uint64_t seed, uint64_t t, uint32_t thr, float scale, int cus,
+                      hipStream_t st) {
+    const size_t want = ((size_t)Np * Np + 255) / 256;
+    const size_t cap = (size_t)(cus > 0 ? cus : 1) * 8; // as average(): eight 256-thread workgroups fill a CU's 32 wave slots
+    const int blocks = (int)(want < 1 ? 1 : want > cap ? cap : want);
+    hipLaunchKernelGGL(k_weight_drop, dim3(blocks), dim3(256), 0, st, src, dst, Np, Nl, seed, t, thr, scale);
 }
 
 PadMap pad_map_rows(int blocks, int N, int Np, int cols) {

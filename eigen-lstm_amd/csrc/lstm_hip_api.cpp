@@ -10,6 +10,7 @@
 // so the time-batched products see plain column-major matrices with T = (S-1)*B columns.
 #include "../../include/lstm_hip.h"
 #include "kernels.h"
+#include "weight_drop.h"
 
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
@@ -182,6 +183,13 @@ struct lstm_hip_ctx {
     int64_t avg_seen = 0, avg_n = 0; // updates launched with averaging on / of those, the due ones (the average's own count)
     float *avg = nullptr;            // the average (flat block, internal width); allocated when averaging is first turned on
     int infer_src = LSTM_HIP_SRC_PARAMS; // the block the inference calls read (infer_block)
+    // weight drop (lstm_hip_set_weight_drop): rate 0 = off.  While it is on, a training window's recurrences read images
+    // packed from Ue, and `packed` / `packed16` say that the images AND Ue are those of the current (rate, seed, t)
+    double wd_rate = 0.0;
+    uint64_t wd_seed = 0, wd_t = 0;
+    uint32_t wd_thr = 0;         // floor(rate * 2^32)
+    float wd_scale = 1.0f;       // 1 / (1 - rate)
+    float *Ue = nullptr;         // the masked, rescaled U (4Np^2 floats); allocated when weight drop is first turned on
     uint8_t *text = nullptr;
     uint64_t text_len = 0;
     uint64_t *pos = nullptr;     // the live cursors and ring head: one half of pos_buf [2][B] / head_buf [2].  A slide carried
@@ -303,13 +311,29 @@ const float *loss_src(const lstm_hip_ctx *h) {
 int loss_steps(const lstm_hip_ctx *h) { return loss_last_step(h) ? 1 : h->cfg.S - 1; }
 float loss_scale(const lstm_hip_ctx *h) { return h->loss_mode == LSTM_HIP_LOSS_LAST_STEP_NATS ? 0.693147180559945f : 1.0f; }
 
+// Weight drop (lstm_hip_set_weight_drop): one elementwise launch over U with the mask of the handle's (rate, seed, t), on the
+// handle's stream.  Like average it is not one of the window's timed kernels: its own status check, no statistics row.
+int weight_drop_status() {
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(LSTM_HIP_EHIP, "launch of weight_drop failed: %s", hipGetErrorString(e));
+    return 0;
+}
+int weight_drop_launch(lstm_hip_ctx *h, const float *src, float *dst) {
+    weight_drop_mask(src, dst, h->cfg.N, h->N_log, h->wd_seed, h->wd_t, h->wd_thr, h->wd_scale, h->plan.n_cus, h->st);
+    return weight_drop_status();
+}
+
 int do_forward(lstm_hip_ctx *h) {
     const EnginePlan &p = h->plan;
     const int N = h->cfg.N, B = h->cfg.B, S = h->cfg.S, G4 = 4 * N;
     const bool fast = (h->cfg.flags & LSTM_HIP_FAST_MATH) != 0;
     float *W = h->P + h->pl.W, *bias = h->P + h->pl.b;
+    // weight drop: the window's images of U are packed from the masked copy, remade whenever they are
+    const float *Usrc = h->wd_rate > 0.0 ? h->Ue : h->P + h->pl.U;
+    if (h->wd_rate > 0.0 && !(p.bf16() ? h->packed16 : h->packed))
+        if (int rc = weight_drop_launch(h, h->P + h->pl.U, h->Ue)) return rc;
     if (!h->packed && !p.bf16()) { // (the bf16 path packs its own images below)
-        RUN(K_PACK_U, pack_U(h->P + h->pl.U, p.ufwd4() ? nullptr : h->Ufwd, p.ubwd4() ? nullptr : h->Ubwd, N, h->st, h->Ubwd4,
+        RUN(K_PACK_U, pack_U(Usrc, p.ufwd4() ? nullptr : h->Ufwd, p.ubwd4() ? nullptr : h->Ubwd, N, h->st, h->Ubwd4,
                              h->Ufwd4, p.half_forms())); // one image per direction is live
         h->packed = true;
     }
@@ -323,9 +347,9 @@ int do_forward(lstm_hip_ctx *h) {
         h->fwd_epoch++;
     }
     if (p.bf16() && !h->packed16) { // (the one-recurrence forms' images only where one of them runs)
-        RUN(K_PACK_U, (p.u16 ? pack_U_bf16(h->P + h->pl.U, h->Ufwd16, h->Ubwd16, N, h->st) : (void)0,
-                       p.bwd == BwdForm::Bf16Scatter && !h->packed6b ? pack_U6_bf16(h->P + h->pl.U, h->Ubwd6b, N, h->st) : (void)0,
-                       p.fwd == FwdForm::Bf16Halves && !h->packedf6b ? pack_Ufwd6_bf16(h->P + h->pl.U, h->Ufwd6b, N, h->st) : (void)0));
+        RUN(K_PACK_U, (p.u16 ? pack_U_bf16(Usrc, h->Ufwd16, h->Ubwd16, N, h->st) : (void)0,
+                       p.bwd == BwdForm::Bf16Scatter && !h->packed6b ? pack_U6_bf16(Usrc, h->Ubwd6b, N, h->st) : (void)0,
+                       p.fwd == FwdForm::Bf16Halves && !h->packedf6b ? pack_Ufwd6_bf16(Usrc, h->Ufwd6b, N, h->st) : (void)0));
         h->packed16 = true;
     }
     switch (p.fwd) {
@@ -337,7 +361,7 @@ int do_forward(lstm_hip_ctx *h) {
         }
         break;
     case FwdForm::Small:
-        RUN(K_FWD_PERSIST, small_fwd(h->P + h->pl.U, W, bias, h->H, h->C, h->G, h->xi, N, S, fast, h->st));
+        RUN(K_FWD_PERSIST, small_fwd(Usrc, W, bias, h->H, h->C, h->G, h->xi, N, S, fast, h->st));
         break;
     case FwdForm::Persistent:
         RUN(K_FWD_PERSIST, fwd_persistent(h->Ufwd, W, bias, h->H, h->C, h->G, h->xi, h->cnt, h->abortp, h->fwd_epoch, N, S, B, fast,
@@ -575,7 +599,7 @@ int do_backward(lstm_hip_ctx *h) {
         RUN(K_GEMM_DU, (h->dgt_written ? (void)0 : transpose_pack_bf16(h->DG + (size_t)G4 * B, T, G4, G4, h->DGt_b, h->Tpad, h->st),
                         gemm_bf16(G4, N, h->Tpad, h->DGt_b, h->Tpad, h->Ht_b, h->SBpad, h->dP + h->pl.U, G4, h->splits_dU,
                                   h->slabs_dU, h->st)));
-    } else if (defer_fold && h->splits_dU > 1)
+    } else if (defer_fold && h->splits_dU > 1 && !(h->wd_rate > 0.0)) // (weight drop masks the finished dU: no deferral)
         RUN(K_GEMM_DU, h->n_slabs_dU = gemm_slabs(false, true, G4, N, T, h->DG + (size_t)G4 * B, G4, h->H, N, h->slabs_dU,
                                                    h->splits_dU, h->st));
     else {
@@ -583,6 +607,9 @@ int do_backward(lstm_hip_ctx *h) {
         RUN(K_GEMM_DU, gemm(false, true, G4, N, T, h->DG + (size_t)G4 * B, G4, h->H, N, h->dP + h->pl.U, G4, h->splits_dU,
                             h->slabs_dU, h->st));
     }
+    // weight drop: dU <- keep ? dUe * s : 0, the gradient with respect to U itself, before any all-reduce, norm or update
+    if (h->wd_rate > 0.0)
+        if (int rc = weight_drop_launch(h, h->dP + h->pl.U, h->dP + h->pl.U)) return rc;
     if (side) HIP_TRY(hipStreamWaitEvent(h->st, h->ev_join, 0)); // the gradient block is complete on `st` from here
     return 0;
 }
@@ -697,6 +724,10 @@ int do_adagrad(lstm_hip_ctx *h, double lr, int64_t norm_idx) {
     h->packed6b = p.bwd == BwdForm::Bf16Scatter;
     h->packedf6b = p.fwd == FwdForm::Bf16Halves && p.adagrad_quad; // (k_adagrad writes that image in its quad form only)
     h->why_packed = p.bf16(); // (the bf16 path's Adagrad launch has just rewritten both bf16 copies of Why)
+    if (h->wd_rate > 0.0) { // weight drop: the next window has the next mask, and the launch's images are of the unmasked U
+        h->wd_t++;
+        h->packed = h->packed16 = h->packed6b = h->packedf6b = false;
+    }
     // the running average, in a launch of its own behind the update launch (never inside it: include/lstm_hip.h)
     if (h->avg_kind != LSTM_HIP_AVG_OFF) return average_step(h);
     return 0;
@@ -890,7 +921,7 @@ int lstm_hip_destroy(lstm_hip_t *h) {
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     if (h->h_losses) (void)hipHostFree(h->h_losses);
-    for (void *p : {(void *)h->d_norms, (void *)h->norm_part, (void *)h->clip_coef, (void *)h->adam_v, (void *)h->avg})
+    for (void *p : {(void *)h->d_norms, (void *)h->norm_part, (void *)h->clip_coef, (void *)h->adam_v, (void *)h->avg, (void *)h->Ue})
         if (p) (void)hipFree(p);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -1260,6 +1291,43 @@ int lstm_hip_set_inference_source(lstm_hip_t *h, int32_t source) {
         return fail(LSTM_HIP_ESTATE, "set_inference_source: LSTM_HIP_SRC_AVERAGE needs averaging on and at least one averaged "
                                      "update (n >= 1): the average is still the zero block");
     h->infer_src = source;
+    return 0;
+}
+
+// weight drop (include/lstm_hip.h).  Every call drops fwd_done and marks every image of U stale, so
+// the next forward pass packs from the right source: Ue under the new (rate, seed, t), or the parameters once it is off.
+static bool weight_drop_rate_ok(double rate) { return rate >= 0.0 && rate < 1.0; } // (NaN fails both comparisons)
+int lstm_hip_set_weight_drop(lstm_hip_t *h, double rate, uint64_t seed, uint64_t t) {
+    CHECK(h);
+    if (!weight_drop_rate_ok(rate)) return fail(LSTM_HIP_EINVAL, "set_weight_drop: rate must be 0 (off) or 0 < rate < 1 (got %g)", rate);
+    if (h->plan.du_split)
+        return fail(LSTM_HIP_ESTATE, "set_weight_drop: this handle runs the dU product in halves (LSTM_HIP_DU_SPLIT), whose first "
+                                     "half is all-reduced before the mask could be applied");
+    if (rate > 0.0 && !h->Ue) {
+        HIP_TRY(hipMalloc((void **)&h->Ue, sizeof(float) * 4 * h->cfg.N * h->cfg.N));
+        HIP_TRY(hipMemsetAsync(h->Ue, 0, sizeof(float) * 4 * h->cfg.N * h->cfg.N, h->st));
+    }
+    h->wd_rate = rate, h->wd_seed = seed, h->wd_t = t;
+    h->wd_thr = rate > 0.0 ? weight_drop::threshold(rate) : 0;
+    h->wd_scale = rate > 0.0 ? weight_drop::scale(rate) : 1.0f;
+    h->packed = h->packed16 = h->packed6b = h->packedf6b = false;
+    h->fwd_done = false;
+    return 0;
+}
+int lstm_hip_get_weight_drop(lstm_hip_t *h, double *rate, uint64_t *seed, uint64_t *t) {
+    if (!h || !rate || !seed || !t) return fail(LSTM_HIP_EINVAL, "get_weight_drop: null argument");
+    *rate = h->wd_rate, *seed = h->wd_seed, *t = h->wd_t;
+    return 0;
+}
+int lstm_hip_weight_drop_mask(int32_t N, double rate, uint64_t seed, uint64_t t, uint8_t *keep) {
+    if (N < 1 || !keep) return fail(LSTM_HIP_EINVAL, "weight_drop_mask: need N >= 1 and an output pointer (got N = %d)", N);
+    if (!weight_drop_rate_ok(rate)) return fail(LSTM_HIP_EINVAL, "weight_drop_mask: rate must be 0 (off) or 0 < rate < 1 (got %g)", rate);
+    const uint64_t n = (uint64_t)4 * N * N;
+    const uint32_t thr = rate > 0.0 ? weight_drop::threshold(rate) : 0; // (rate 0: every word >= 0, all kept)
+    for (uint64_t q = 0; 4 * q < n; q++) {
+        const weight_drop::Words w = weight_drop::quad_words(q, seed, t);
+        for (uint64_t c = 0; c < 4 && 4 * q + c < n; c++) keep[4 * q + c] = weight_drop::keep_word(w.w[c], thr) ? 1 : 0;
+    }
     return 0;
 }
 
@@ -2569,6 +2637,8 @@ static int adaptive_checks(lstm_hip_t *h, const char *what, double lr) {
     if (h->comm) return fail(LSTM_HIP_ESTATE, "%s: a handle with a communicator cannot code adaptively", what);
     if (h->infer_src == LSTM_HIP_SRC_AVERAGE) // (it codes with the model it trains: the setting cannot be honoured)
         return fail(LSTM_HIP_ESTATE, "%s: the inference source is LSTM_HIP_SRC_AVERAGE; adaptive coding reads the parameters it trains", what);
+    if (h->wd_rate > 0.0) // (the containers record no mask: DESIGN.md section 3.15)
+        return fail(LSTM_HIP_ESTATE, "%s: weight drop is on (lstm_hip_set_weight_drop); the adaptive coders train without it", what);
     if (!std::isfinite(lr) || lr < 0.0) return fail(LSTM_HIP_EINVAL, "%s: learning_rate must be finite and >= 0 (got %g)", what, lr);
     if (h->cfg.N > 16384) return fail(LSTM_HIP_EINVAL, "%s: hidden width %d above 16384", what, h->cfg.N);
     if (h->cfg.B > 4096) return fail(LSTM_HIP_EINVAL, "%s: more than 4096 streams (B = %d)", what, h->cfg.B);

@@ -8,7 +8,7 @@
 //        [--eval-file F] [--stride K] [--forget-bias V] [--test-percent F] [--test-every SEC] [--log PREFIX]
 //        [--fast-math] [--step-kernels] [--stable-softmax] [--clip-norm X] [--optimizer adagrad|adam]
 //        [--adam-betas B1,B2] [--adam-eps E] [--weight-decay W] [--average ema|uniform] [--average-decay D]
-//        [--average-every K] [--average-start W] [--quiet]
+//        [--average-every K] [--average-start W] [--weight-drop R] [--weight-drop-seed K] [--quiet]
 //
 // stdout follows the reference: "Read N bytes (file)" (R/lstm.cc:398), the carriage-return progress
 // line (OV/lstm_eigen_opt/lstm.cc:320-331), the epoch summary (R/lstm.cc:284-291: GFLOP uses 2^30,
@@ -35,6 +35,10 @@
 // averaged model's bits/char; --save also writes the average as a checkpoint of its own, PREFIX_avg_{W,U,b,Why,by}.txt (so
 // --load PREFIX_avg works in lstm_generate and lstm_compress), and PREFIX_avg_state.txt (kind, decay, every, seen, n);
 // --load PREFIX with the same --average kind resumes both, another kind or no --average ignores them.
+// --weight-drop R (0 < R < 1) trains with DropConnect on the hidden-to-hidden matrix U, one mask per window
+// (lstm_hip_set_weight_drop; --weight-drop-seed K, default 0, picks the mask sequence).  Held-out tests, samples and saved
+// parameters are those of the unmasked model.  --save also writes PREFIX_weight_drop.txt (rate, seed, t); --load PREFIX with
+// --weight-drop again resumes the mask index t (and the seed, unless --weight-drop-seed is given).
 #include "../../include/lstm_hip.h"
 
 // referenced weakly: the program still links against a library without them and refuses --clip-norm / --optimizer adam there
@@ -50,6 +54,9 @@
 #pragma weak lstm_hip_get_averaging_counts
 #pragma weak lstm_hip_set_averaging_counts
 #pragma weak lstm_hip_set_inference_source
+// ... and --weight-drop
+#pragma weak lstm_hip_set_weight_drop
+#pragma weak lstm_hip_get_weight_drop
 #include "checkpoint.h"
 #include "matrix_io.h"
 #include "rng.h"
@@ -99,6 +106,9 @@ struct Options {
     double avg_decay = 0.0;          // --average-decay (ema: default 0.999)
     int avg_every = 1;               // --average-every
     long avg_start = 0;              // --average-start
+    double wd_rate = 0.0;            // --weight-drop: 0 = off
+    uint64_t wd_seed = 0;            // --weight-drop-seed
+    bool wd_seed_given = false;
 };
 
 [[noreturn]] void die(const std::string &m) {
@@ -277,6 +287,19 @@ Options parse(int argc, char **argv) {
             o.avg_start = whole_number(a, val(), 0);
             avg_opt = a;
         }
+        else if (a == "--weight-drop") {
+            const std::string v = val();
+            o.wd_rate = finite_number(a, v);
+            if (!(o.wd_rate > 0.0 && o.wd_rate < 1.0)) die("--weight-drop needs a rate 0 < R < 1, got " + v);
+        } else if (a == "--weight-drop-seed") {
+            const std::string v = val();
+            char *end = nullptr;
+            errno = 0;
+            const unsigned long long k = strtoull(v.c_str(), &end, 10);
+            if (end == v.c_str() || *end != '\0' || errno != 0 || v[0] == '-') die(a + " needs a whole number >= 0, got " + v);
+            o.wd_seed = (uint64_t)k;
+            o.wd_seed_given = true;
+        }
         else if (a == "--last-step-loss") o.last_step_loss = true;
         else if (a == "--last-step-loss-bits") o.last_step_bits = true;
         else if (a == "--quiet") o.quiet = true;
@@ -286,7 +309,7 @@ Options parse(int argc, char **argv) {
                    "            --test-percent F --test-every SEC --log PREFIX --last-step-loss --last-step-loss-bits --fast-math --step-kernels\n"
                    "            --stable-softmax --clip-norm X --optimizer adagrad|adam --adam-betas B1,B2 --adam-eps E\n"
                    "            --weight-decay W --average ema|uniform --average-decay D --average-every K --average-start W\n"
-                   "            --quiet]\n");
+                   "            --weight-drop R --weight-drop-seed K --quiet]\n");
             exit(0);
         } else if (a.rfind("--", 0) == 0) die("unknown option " + a);
         else pos.push_back(a);
@@ -305,6 +328,9 @@ Options parse(int argc, char **argv) {
          lstm_hip_set_inference_source == nullptr))
         die("--average: the loaded liblstm_hip has no lstm_hip_set_averaging / lstm_hip_get_average / lstm_hip_set_average / "
             "lstm_hip_get_averaging_counts / lstm_hip_set_averaging_counts / lstm_hip_set_inference_source");
+    if (o.wd_seed_given && !(o.wd_rate > 0.0)) die("--weight-drop-seed needs --weight-drop R");
+    if (o.wd_rate > 0.0 && (lstm_hip_set_weight_drop == nullptr || lstm_hip_get_weight_drop == nullptr))
+        die("--weight-drop: the loaded liblstm_hip has no lstm_hip_set_weight_drop / lstm_hip_get_weight_drop");
     if (pos.size() > 0) o.data = pos[0];
     if (pos.size() > 1) o.N = atoi(pos[1].c_str());
     if (pos.size() > 2) o.S = atoi(pos[2].c_str());
@@ -400,6 +426,21 @@ int run_rank(const Options &o, int rank, int up, int down) {
                 if (lead) printf("Loaded the %s average (seen = %lld, n = %lld) from %s_avg_{W,U,Why,b,by}.txt\n", kind.c_str(), seen, n, o.load.c_str());
             }
         }
+    }
+    if (o.wd_rate > 0.0) { // weight drop (every rank: the same three numbers); a checkpoint's mask index is resumed
+        uint64_t seed = o.wd_seed, t = 0;
+        if (!o.load.empty()) {
+            std::ifstream f(o.load + "_weight_drop.txt");
+            std::string key;
+            double rate = 0.0;
+            unsigned long long fseed = 0, ft = 0;
+            if (f && (f >> key >> rate >> key >> fseed >> key >> ft)) {
+                if (!o.wd_seed_given) seed = fseed;
+                t = ft;
+                if (lead) printf("Loaded weight drop (seed = %llu, t = %llu) from %s_weight_drop.txt\n", (unsigned long long)seed, ft, o.load.c_str());
+            }
+        }
+        CK(lstm_hip_set_weight_drop(h, o.wd_rate, seed, t));
     }
     CK(lstm_hip_set_text(h, data.data(), length));
 
@@ -594,6 +635,18 @@ int run_rank(const Options &o, int rank, int up, int down) {
                         die("cannot write " + o.save + "_avg_state.txt");
                     printf("Saved the %s average (seen = %lld, n = %lld) to %s_avg_{W,U,Why,b,by}.txt\n", avg_name(o.avg_kind),
                            (long long)seen, (long long)n, o.save.c_str());
+                }
+                if (o.wd_rate > 0.0) { // weight drop: the three numbers a resumed run sets
+                    double rate = 0.0;
+                    uint64_t seed = 0, t = 0;
+                    CK(lstm_hip_get_weight_drop(h, &rate, &seed, &t));
+                    std::ofstream f(o.save + "_weight_drop.txt");
+                    char r[40];
+                    snprintf(r, sizeof(r), "%.17g", rate);
+                    if (!(f << "rate " << r << "\nseed " << (unsigned long long)seed << "\nt " << (unsigned long long)t << "\n"))
+                        die("cannot write " + o.save + "_weight_drop.txt");
+                    printf("Saved weight drop (rate = %s, seed = %llu, t = %llu) to %s_weight_drop.txt\n", r, (unsigned long long)seed,
+                           (unsigned long long)t, o.save.c_str());
                 }
                 std::vector<uint64_t> all(o.B); // every stream has advanced by the same number of bytes
                 const uint64_t span = (uint64_t)(length - S), adv = (uint64_t)done_windows * (uint64_t)o.stride;

@@ -91,6 +91,7 @@ SYMBOLS = [
     "lstm_hip_dfa_restrict", "lstm_hip_score", "lstm_hip_beam_search_constrained",
     "lstm_hip_set_averaging", "lstm_hip_get_average", "lstm_hip_set_average", "lstm_hip_get_averaging_counts",
     "lstm_hip_set_averaging_counts", "lstm_hip_set_inference_source",
+    "lstm_hip_set_weight_drop", "lstm_hip_get_weight_drop", "lstm_hip_weight_drop_mask",
 ]
 
 
@@ -146,6 +147,15 @@ def adaptive_blocks(S, B, text_off):
     if n < 0:
         _chk(n)
     return n
+
+
+def weight_drop_mask(N, rate, seed=0, t=0):
+    """lstm_hip_weight_drop_mask: the keep mask of lstm_hip_set_weight_drop for a logical hidden size N, as a bool array
+    [4N, N] (True where element (r, k) of U is kept).  The shipped rule running on the CPU: needs no device."""
+    keep = np.empty(4 * N * N, np.uint8)
+    _chk(load_library().lstm_hip_weight_drop_mask(C.c_int32(N), C.c_double(rate), C.c_uint64(seed), C.c_uint64(t),
+                                                  _ptr(keep, C.c_uint8)))
+    return keep.reshape(N, 4 * N).T != 0  # (keep[r + 4N * k]: column-major)
 
 
 def dfa_utf8():
@@ -368,6 +378,19 @@ class Lstm:
         """SRC_PARAMS (the default) or SRC_AVERAGE: what eval_bits, sample, generate, beam_search, score, encode and decode
         read.  Training never reads it; the adaptive coders refuse SRC_AVERAGE."""
         _chk(self.lib.lstm_hip_set_inference_source(self._h, C.c_int32(source)))
+
+    # ---- weight drop: DropConnect on U, one mask per training window (lstm_hip_set_weight_drop) ----
+    def set_weight_drop(self, rate, seed=0, t=0):
+        """rate 0: off (the default); 0 < rate < 1: every training window reads U masked by the Philox mask of (seed, t) and
+        rescaled by 1 / (1 - rate), and dU gets the same mask and scale.  t advances with every update.  Everything that is
+        not a training window reads the unmasked parameters.  Drops the forward pass."""
+        _chk(self.lib.lstm_hip_set_weight_drop(self._h, C.c_double(rate), C.c_uint64(seed), C.c_uint64(t)))
+
+    def weight_drop(self):
+        """(rate, seed, t) of lstm_hip_get_weight_drop."""
+        rate, seed, t = C.c_double(), C.c_uint64(), C.c_uint64()
+        _chk(self.lib.lstm_hip_get_weight_drop(self._h, C.byref(rate), C.byref(seed), C.byref(t)))
+        return rate.value, seed.value, t.value
 
     # ---- data-parallel -----------------------------------------------------------------------
     def comm_init(self, unique_id, nranks, rank):

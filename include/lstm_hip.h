@@ -225,6 +225,43 @@ int lstm_hip_set_averaging_counts(lstm_hip_t *h, int64_t seen, int64_t n);
 #define LSTM_HIP_SRC_AVERAGE 1
 int lstm_hip_set_inference_source(lstm_hip_t *h, int32_t source);
 
+/* ---- weight drop: DropConnect on the hidden-to-hidden matrix U, one mask per training window
+ * rate == 0 is off (the default); 0 < rate < 1 is on; anything else (negative, >= 1, NaN, infinite) is LSTM_HIP_EINVAL, the
+ * message names the number and the handle stays usable.
+ *
+ * Numbering.  Element (r, k) of the logical 4N x N matrix U, r = g * N + j with the gates g in the order i, o, f, u, has the
+ * number e = r + 4N * k, N being the handle's logical N: independent of padding and of the create flags, so fp32, bf16 and
+ * LSTM_HIP_PAD_HIDDEN handles of one logical N share their masks.
+ * Random word.  Philox4x32-10 with counter (c0, c1, c2, c3) = (low 32, high 32 bits of e >> 2, low 32, high 32 bits of t) and
+ * key (k0, k1) = (low 32, high 32 bits of seed); round multipliers 0xD2511F53 (M0, for c0) and 0xCD9E8D57 (M1, for c2), key
+ * increments 0x9E3779B9 and 0xBB67AE85; per round c <- (hi(M1*c2) ^ c1 ^ k0, lo(M1*c2), hi(M0*c0) ^ c3 ^ k1, lo(M0*c0)), then
+ * the key is bumped; ten rounds.  The word of element e is output word e & 3.
+ * Keep.  keep(e) <=> word >= thr, thr = (uint32) floor(rate * 2^32) computed in double on the host.
+ * Scale.  s = (float)(1.0 / (1.0 - rate)), computed in double on the host and narrowed.
+ *
+ * Every recurrence of a training window (lstm_hip_forward / lstm_hip_backward, each window of lstm_hip_train_windows) reads
+ * Ue, Ue_e = keep(e) ? U_e * s (one fp32 multiply) : +0.0f.  After the dU product the gradient block holds
+ * dU_e = keep(e) ? dUe_e * s : +0.0f, the gradient with respect to U itself: lstm_hip_get_params(which = 1) returns it, the
+ * clip norm is taken on it and the all-reduce sums it.  W, b, Why, by and their gradients are untouched.
+ * The mask index t advances by one with every update the handle launches while weight drop is on (the rule of the optimizer
+ * step counter: lstm_hip_adagrad, each window of lstm_hip_train_windows, lr = 0 too); a forward and a backward pass between
+ * two updates use one mask.  set takes (rate, seed, t) together, get returns them; resuming is set with the saved t.
+ *
+ * Everything that is not a training window reads the unmasked parameters with no rescaling (inverted dropout):
+ * lstm_hip_eval_bits, lstm_hip_sample, lstm_hip_generate*, lstm_hip_beam_search*, lstm_hip_score, lstm_hip_encode,
+ * lstm_hip_decode, the running average and lstm_hip_get_params(0).
+ * lstm_hip_set_weight_drop drops the forward pass: lstm_hip_backward after it is LSTM_HIP_ESTATE until a new
+ * lstm_hip_forward.  The adaptive coders answer LSTM_HIP_ESTATE while weight drop is on (their containers record no mask); a
+ * handle whose plan runs the dU product in halves (LSTM_HIP_DU_SPLIT) refuses set with LSTM_HIP_ESTATE.  With a communicator
+ * every rank must be given the same (rate, seed, t); nothing is exchanged.  Per handle, may change between calls, not part of
+ * the engine plan; a handle that never turns it on makes the launches it made before this call existed.
+ *
+ * lstm_hip_weight_drop_mask needs no device and no handle: keep[r + 4N * k] = 1 where element (r, k) is kept, else 0
+ * (4N * N bytes; rate 0 keeps everything).  It runs the text the device runs. */
+int lstm_hip_set_weight_drop(lstm_hip_t *h, double rate, uint64_t seed, uint64_t t);
+int lstm_hip_get_weight_drop(lstm_hip_t *h, double *rate, uint64_t *seed, uint64_t *t);
+int lstm_hip_weight_drop_mask(int32_t N, double rate, uint64_t seed, uint64_t t, uint8_t *keep);
+
 /* ---- data-parallel exchange (new; the reference is single-device).  One SUM all-reduce of the
  *      flat gradient block per window over RCCL; every rank then applies the identical Adagrad step.
  *      With LSTM_HIP_PAD_HIDDEN the payload is the padded block (Np from N and the flags, so every
