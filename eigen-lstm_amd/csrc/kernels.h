@@ -392,6 +392,11 @@ struct GenHeadArgs {
     const uint16_t *ctab;       // [states][256] the state after byte b in state q, 0xFFFF: b is forbidden there
     const uint16_t *ccount;     // [states] allowed bytes of each state (>= 1 for every state a stream can reach)
     int32_t *cstate;            // [streams] the state of every stream: after its prompt at the start, then after each drawn byte
+    // accepting states (lstm_hip_generate_accepting): read only by the DEADLINE instantiation, which
+    // gen_head takes when `frows` is set (`ctab` is set with it); all null / 0 otherwise
+    const uint8_t *accept;      // [states] nonzero: a stream may end there
+    const uint32_t *frows;      // [count][fwords] bit q of row R: an accepted end can be reached from q with R more bytes
+    int fwords;                 // words of one row: (states + 31) / 32
 };
 // stable: LSTM_HIP_STABLE_SOFTMAX.  hipSuccess, or the HIP error of a refused LDS request with nothing launched (the FILTER
 // instantiations only; beam_head and score_head likewise)

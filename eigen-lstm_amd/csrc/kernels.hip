@@ -1769,6 +1769,13 @@ __global__ __launch_bounds__(1024) void k_sample(const float *__restrict__ P, in
 // max, expf and sum all see the masked value.  A tempered draw is then always a filtered one, keep capped by a.ccount[q] (the
 // allowed bytes of q), so the kept bytes are allowed ones.  The owner lane replaces a byte that is forbidden all the same
 // (non-finite logits only) by the lowest allowed byte of q and writes the next state to a.cstate[s].  Prompt bytes ignore it.
+// DEADLINE (lstm_hip_generate_accepting; implies CONSTRAIN, and without it the instantiation is the code
+// above and nothing else): at draw i of a stream, R = a.count - i draws remain.  Byte m EXISTS iff nx = a.ctab[q * 256 + m] is
+// allowed and a.accept[nx] (m the stop byte) or bit nx of row R - 1 of a.frows (any other byte): an accepted end can still be
+// reached behind it.  A byte that does not exist is masked like a forbidden one; thread m tests its own byte (one more load,
+// ahead of the product: the row differs per stream, as prompts differ in length) and the group counts the existing bytes E of
+// every stream in LDS, which caps keep in place of a.ccount[q].  The owner lane replaces a byte that does not exist by the
+// lowest existing one.  The host has checked F[count][q0], so E >= 1 at every draw and the stream ends in an accepting state.
 // ------------------------------------------------------------------------------------------------
 // what stream s does at step t: 0 idle, 1 prompt byte scored, 2 drawn byte, 3 prompt byte not scored; *len = its prompt length
 // (*drawn: the bytes the stream draws -- the call's count, or with FILTER its own end index)
@@ -1780,18 +1787,28 @@ __device__ __forceinline__ int gen_phase(const GenHeadArgs &a, int s, long long 
     if (t < *len) return (t >= 1 && a.bits) ? 1 : 3;
     return t - *len < n ? 2 : 0;
 }
-template <int SB, bool STABLE, bool FILTER, bool CONSTRAIN = false>
+// does byte x exist for a stream in the state whose table row is `row`, `left` draws before its last one?  (DEADLINE)
+__device__ __forceinline__ bool gen_exists(const GenHeadArgs &a, const uint16_t *row, int x, long long left) {
+    const uint16_t nx = row[x];
+    if (nx == 0xFFFF) return false;
+    if (x == a.stop_byte) return a.accept[nx] != 0;
+    return (a.frows[(size_t)left * a.fwords + (nx >> 5)] >> (nx & 31)) & 1u;
+}
+template <int SB, bool STABLE, bool FILTER, bool CONSTRAIN = false, bool DEADLINE = false>
 __global__ __launch_bounds__(256) void k_gen_head(GenHeadArgs a, long long t) {
     static_assert(FILTER || !CONSTRAIN, "CONSTRAIN implies FILTER");
+    static_assert(CONSTRAIN || !DEADLINE, "DEADLINE implies CONSTRAIN");
     extern __shared__ __attribute__((aligned(16))) float hs[]; // [N][SB]
     __shared__ float ps[SB][256];
     __shared__ float s_zmax[SB], s_sum[SB], s_zt[STABLE ? SB : 1];
     __shared__ int s_arg[SB];
     __shared__ float sorted[FILTER ? SB : 1][FILTER ? 256 : 1]; // p in rank order
     __shared__ int s_keep[FILTER ? SB : 1], s_last[FILTER ? SB : 1]; // bytes kept; the largest kept index
+    [[maybe_unused]] __shared__ int s_exist[DEADLINE ? SB : 1]; // E: the bytes that exist for each drawing stream
     const int m = threadIdx.x, N = a.N, s0 = blockIdx.x * SB;
     int phase[SB]; // (the same in every thread)
     [[maybe_unused]] int cq[CONSTRAIN ? SB : 1]; // the automaton state of each drawing stream (read before any barrier)
+    [[maybe_unused]] long long left[DEADLINE ? SB : 1]; // draws each drawing stream has before its last one: R - 1
     bool need = false;
 #pragma unroll
     for (int j = 0; j < SB; j++) {
@@ -1803,6 +1820,7 @@ __global__ __launch_bounds__(256) void k_gen_head(GenHeadArgs a, long long t) {
         phase[j] = gen_phase<FILTER>(a, s, t, &len, &drawn);
         need |= phase[j] == 1 || phase[j] == 2;
         if constexpr (CONSTRAIN) cq[j] = phase[j] == 2 ? a.cstate[s] : 0;
+        if constexpr (DEADLINE) left[j] = phase[j] == 2 ? a.count - 1 - (t - len) : 0;
         if (t == len + drawn) { // the state after the stream's last input
             if (a.h_out)
                 for (int k = m; k < N; k += 256) a.h_out[(size_t)s * N + k] = a.H[(size_t)s * N + k];
@@ -1814,8 +1832,13 @@ __global__ __launch_bounds__(256) void k_gen_head(GenHeadArgs a, long long t) {
         [[maybe_unused]] bool banned[CONSTRAIN ? SB : 1]; // is byte m forbidden where stream j stands?  (loaded ahead of the product)
         if constexpr (CONSTRAIN) {
 #pragma unroll
-            for (int j = 0; j < SB; j++) banned[j] = phase[j] == 2 && a.ctab[(size_t)cq[j] * 256 + m] == 0xFFFF;
+            for (int j = 0; j < SB; j++) {
+                if constexpr (DEADLINE) banned[j] = phase[j] == 2 && !gen_exists(a, a.ctab + (size_t)cq[j] * 256, m, left[j]);
+                else banned[j] = phase[j] == 2 && a.ctab[(size_t)cq[j] * 256 + m] == 0xFFFF;
+            }
         }
+        if constexpr (DEADLINE)
+            if (m < SB) s_exist[m] = 0; // (counted behind the barrier below)
         for (int i = m; i < N * SB; i += 256) {
             const int k = i / SB, j = i - k * SB;
             hs[i] = s0 + j < a.streams ? a.H[(size_t)(s0 + j) * N + k] : 0.0f;
@@ -1832,6 +1855,11 @@ __global__ __launch_bounds__(256) void k_gen_head(GenHeadArgs a, long long t) {
             for (int i = 0; i < 16; i++)
 #pragma unroll
                 for (int j = 0; j < SB; j++) y[j] += wv[i] * hs[(k0 + i) * SB + j];
+        }
+        if constexpr (DEADLINE) {
+#pragma unroll
+            for (int j = 0; j < SB; j++)
+                if (phase[j] == 2 && !banned[j]) atomicAdd(&s_exist[j], 1); // (read behind the filter's barriers)
         }
         const float bym = a.by[m];
         bool any_max = false;
@@ -1915,7 +1943,9 @@ __global__ __launch_bounds__(256) void k_gen_head(GenHeadArgs a, long long t) {
                     long long lo;
                     if (gen_phase<FILTER>(a, s0 + jo, t, &lo) == 2) {
                         int keep = a.keep_k;
-                        if constexpr (CONSTRAIN) {
+                        if constexpr (DEADLINE) {
+                            if (s_exist[jo] < keep) keep = s_exist[jo];
+                        } else if constexpr (CONSTRAIN) {
                             const int allowed = a.ccount[a.cstate[s0 + jo]];
                             if (allowed < keep) keep = allowed;
                         }
@@ -1989,7 +2019,11 @@ __global__ __launch_bounds__(256) void k_gen_head(GenHeadArgs a, long long t) {
         }
         if constexpr (CONSTRAIN) { // advance the automaton; a forbidden byte gives way to the state's lowest allowed one
             const uint16_t *row = a.ctab + (size_t)a.cstate[s] * 256;
-            if (row[x] == 0xFFFF)
+            if constexpr (DEADLINE) { // a byte that does not exist gives way to the lowest existing one
+                const long long lf = a.count - 1 - (long long)i;
+                if (!gen_exists(a, row, x, lf))
+                    for (x = 0; x < 255 && !gen_exists(a, row, x, lf); x++) {}
+            } else if (row[x] == 0xFFFF)
                 for (x = 0; x < 255 && row[x] == 0xFFFF; x++) {}
             if (row[x] != 0xFFFF) a.cstate[s] = row[x]; // (an empty row cannot be reached: the state never leaves the table)
         }
@@ -2029,12 +2063,19 @@ template <bool STABLE> static hipError_t gen_head_launch(const GenHeadArgs &a, l
         hipLaunchKernelGGL((k_gen_head<SB, STABLE, false>), grid, dim3(256), lds, st, a, t);                               \
         break;
     // FILTER: static LDS is up to 33 KB (ps, sorted), dynamic up to 64 KB
-#define GEN_HEAD_FILTER_CASE(SB, CONSTRAIN)                                                                                 \
+#define GEN_HEAD_FILTER_CASE(SB, ...)                                                                                       \
     case SB:                                                                                                                \
-        if (const hipError_t e = grant_lds<k_gen_head<SB, STABLE, true, CONSTRAIN>, 32768>(lds)) return e;                  \
-        hipLaunchKernelGGL((k_gen_head<SB, STABLE, true, CONSTRAIN>), grid, dim3(256), lds, st, a, t);                      \
+        if (const hipError_t e = grant_lds<k_gen_head<SB, STABLE, true, __VA_ARGS__>, 32768>(lds)) return e;                \
+        hipLaunchKernelGGL((k_gen_head<SB, STABLE, true, __VA_ARGS__>), grid, dim3(256), lds, st, a, t);                    \
         break;
-    if (a.ctab) switch (sb) { // (the caller sets a.end too)
+    if (a.frows) switch (sb) { // (the caller sets a.ctab and a.end too)
+            GEN_HEAD_FILTER_CASE(1, true, true)
+            GEN_HEAD_FILTER_CASE(2, true, true)
+            GEN_HEAD_FILTER_CASE(4, true, true)
+            GEN_HEAD_FILTER_CASE(8, true, true)
+            GEN_HEAD_FILTER_CASE(16, true, true)
+        }
+    else if (a.ctab) switch (sb) { // (the caller sets a.end too)
             GEN_HEAD_FILTER_CASE(1, true)
             GEN_HEAD_FILTER_CASE(2, true)
             GEN_HEAD_FILTER_CASE(4, true)

@@ -11,6 +11,7 @@
 #include "../../include/lstm_hip.h"
 #include "kernels.h"
 #include "weight_drop.h"
+#include "dfa_regex.h"
 
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
@@ -1877,6 +1878,53 @@ int lstm_hip_dfa_restrict(uint16_t *next, int32_t states, const uint8_t allow[25
     return 0;
 }
 
+// The deadline rows of a checked byte automaton with accepting states (include/lstm_hip.h, lstm_hip_beam_search_constrained):
+// frows[R * fwords + q / 32] bit q % 32 is F[R][q] for R = 0 .. count.  F[0][q] = acc(q); F[R][q] = some allowed byte b of q:
+// acc(next) if b is the stop byte, else F[R - 1][next].  Every stream must start (cstate: the state after its prompt) where
+// F[count] holds.  Shared by beam search and the accepting sampler.
+static int deadline_rows(const char *what, const lstm_hip_constraint *con, const uint8_t *accept, int stop_byte, int32_t count,
+                         const std::vector<int32_t> &cstate, std::vector<uint32_t> &frows) {
+    const int Q = con->states, fwords = (Q + 31) / 32;
+    if (((long long)count + 1) * Q > (1ll << 28))
+        return fail(LSTM_HIP_EINVAL, "%s: (count + 1) x states = %lld above 2^28 with accepting states", what, ((long long)count + 1) * Q);
+    std::vector<std::vector<uint16_t>> succ(Q); // the distinct states q's allowed bytes other than the stop byte lead to
+    std::vector<char> stops(Q, 0);              // q's stop byte is allowed and leads into an accepting state
+    for (int q = 0; q < Q; q++) {
+        for (int b = 0; b < 256; b++) {
+            const uint16_t v = con->next[(size_t)q * 256 + b];
+            if (v == 0xFFFF) continue;
+            if (b == stop_byte) stops[q] = accept[v] != 0;
+            else succ[q].push_back(v);
+        }
+        std::sort(succ[q].begin(), succ[q].end());
+        succ[q].erase(std::unique(succ[q].begin(), succ[q].end()), succ[q].end());
+    }
+    frows.assign((size_t)(count + 1) * fwords, 0u);
+    auto bit = [&](int R, int q) { return (frows[(size_t)R * fwords + (q >> 5)] >> (q & 31)) & 1u; };
+    for (int q = 0; q < Q; q++)
+        if (accept[q]) frows[q >> 5] |= 1u << (q & 31);
+    // a row is a function of the row before it: once two rows in sequence are equal every later one is, and is copied
+    bool settled = false;
+    for (int R = 1; R <= count; R++) {
+        uint32_t *row = frows.data() + (size_t)R * fwords;
+        if (settled) {
+            std::copy(row - fwords, row, row);
+            continue;
+        }
+        for (int q = 0; q < Q; q++) {
+            bool f = stops[q];
+            for (size_t i = 0; !f && i < succ[q].size(); i++) f = bit(R - 1, succ[q][i]);
+            if (f) row[q >> 5] |= 1u << (q & 31);
+        }
+        settled = std::equal(row, row + fwords, row - fwords);
+    }
+    for (size_t s = 0; s < cstate.size(); s++)
+        if (!bit(count, cstate[s]))
+            return fail(LSTM_HIP_EINVAL, "%s: stream %d: no accepted string of %d bytes or fewer ending in the stop byte "
+                        "from state %d", what, (int)s, count, cstate[s]);
+    return 0;
+}
+
 // the table checks of a byte automaton (include/lstm_hip.h, lstm_hip_generate_constrained): on success ccount holds the allowed
 // bytes of every state and cstate every stream's start state
 static int check_constraint(const char *what, const lstm_hip_constraint *con, int32_t streams, const int32_t *start_state,
@@ -1922,10 +1970,37 @@ static int check_constraint(const char *what, const lstm_hip_constraint *con, in
     return 0;
 }
 
+// the regex compiler and the product of two tables (dfa_regex.cpp; neither needs a device or a handle)
+int32_t lstm_hip_dfa_regex(const uint8_t *pattern, size_t len, int32_t stop_byte, uint16_t *next, uint8_t *accept, int32_t cap,
+                           int32_t *error_pos) {
+    std::string msg;
+    const int32_t q = dfa::regex(pattern, len, stop_byte, next, accept, cap, error_pos, msg);
+    return q < 0 ? fail(LSTM_HIP_EINVAL, "%s", msg.c_str()) : q;
+}
+
+int32_t lstm_hip_dfa_intersect(const uint16_t *a, int32_t qa, const uint8_t *acc_a, const uint16_t *b, int32_t qb,
+                               const uint8_t *acc_b, uint16_t *next, uint8_t *accept, int32_t cap) {
+    std::string msg;
+    const int32_t q = dfa::intersect(a, qa, acc_a, b, qb, acc_b, next, accept, cap, msg);
+    return q < 0 ? fail(LSTM_HIP_EINVAL, "%s", msg.c_str()) : q;
+}
+
 int lstm_hip_generate_constrained(lstm_hip_t *h, int32_t streams, const uint8_t *prompts, const uint64_t *prompt_off,
                                   const float *h0, const float *c0, const lstm_hip_sampling *opt, const double *u, int32_t count,
                                   uint8_t *out, double *bits, float *h_out, float *c_out, int32_t *out_len, uint16_t *kept,
                                   const lstm_hip_constraint *con, const int32_t *start_state, int32_t *end_state) {
+    const lstm_hip_beam_constraint bc{(uint32_t)sizeof(lstm_hip_beam_constraint), con, nullptr};
+    return lstm_hip_generate_accepting(h, streams, prompts, prompt_off, h0, c0, opt, u, count, out, bits, h_out, c_out, out_len,
+                                       kept, con ? &bc : nullptr, start_state, end_state);
+}
+
+// Accepting states: with bc->accept the deadline rows F are made on the host as beam search makes them,
+// and gen_head's DEADLINE instantiation (a.frows set) masks what the rows rule out.  The accept bytes and the rows are the last
+// pieces of the scratch layout: without them every offset, upload and launch is lstm_hip_generate_constrained's.
+int lstm_hip_generate_accepting(lstm_hip_t *h, int32_t streams, const uint8_t *prompts, const uint64_t *prompt_off,
+                                const float *h0, const float *c0, const lstm_hip_sampling *opt, const double *u, int32_t count,
+                                uint8_t *out, double *bits, float *h_out, float *c_out, int32_t *out_len, uint16_t *kept,
+                                const lstm_hip_beam_constraint *bc, const int32_t *start_state, int32_t *end_state) {
     CHECK(h);
     if (!opt) return fail(LSTM_HIP_EINVAL, "generate: null sampling options");
     if (opt->size != sizeof(lstm_hip_sampling))
@@ -1952,13 +2027,21 @@ int lstm_hip_generate_constrained(lstm_hip_t *h, int32_t streams, const uint8_t 
     // the constraint: the table is checked, then every stream's state walks its prompt
     std::vector<int32_t> cstate; // [streams] the state after each prompt
     std::vector<uint16_t> ccount; // [states] allowed bytes
-    const int Q = con ? con->states : 0;
-    if (!con && (start_state || end_state)) return fail(LSTM_HIP_EINVAL, "generate: start_state / end_state given without a constraint");
+    std::vector<uint32_t> frows;  // [count + 1][fwords] bit q of row R: F[R][q]
+    if (!bc && (start_state || end_state)) return fail(LSTM_HIP_EINVAL, "generate: start_state / end_state given without a constraint");
+    if (bc && bc->size != sizeof(lstm_hip_beam_constraint))
+        return fail(LSTM_HIP_EINVAL, "generate: beam constraint of %u bytes, expected %zu", bc->size, sizeof(lstm_hip_beam_constraint));
+    if (bc && !bc->con) return fail(LSTM_HIP_EINVAL, "generate: beam constraint with a null constraint");
+    const lstm_hip_constraint *con = bc ? bc->con : nullptr;
+    const uint8_t *accept = bc ? bc->accept : nullptr;
+    const int Q = con ? con->states : 0, fwords = (Q + 31) / 32;
     if (con) {
         if (int rc = check_constraint("generate", con, streams, start_state, cstate, ccount)) return rc;
         if (prompt_off)
             if (int rc = walk_constraint("generate", "prompt byte", con, streams, prompts, prompt_off, cstate, nullptr)) return rc;
     }
+    if (accept) // (with count 0 this asks that every stream stands in an accepting state)
+        if (int rc = deadline_rows("generate", con, accept, opt->stop_byte, count, cstate, frows)) return rc;
     const uint64_t total = prompt_off ? prompt_off[streams] : 0;
     const size_t n = (size_t)N * streams, nl = (size_t)h->N_log * streams, nd = (size_t)count * streams;
     const bool keep = h_out || c_out;
@@ -1969,7 +2052,8 @@ int lstm_hip_generate_constrained(lstm_hip_t *h, int32_t streams, const uint8_t 
     float *H, *Cs, *G, *ho, *stage;
     int32_t *xi, *d_end, *d_q;
     uint64_t *d_off;
-    uint8_t *d_prompts, *d_out;
+    uint8_t *d_prompts, *d_out, *d_acc;
+    uint32_t *d_F;
     double *d_u, *d_bits;
     uint16_t *d_kept, *d_tab, *d_cnt;
     Scratch mem;
@@ -1979,6 +2063,7 @@ int lstm_hip_generate_constrained(lstm_hip_t *h, int32_t streams, const uint8_t 
     mem.piece(d_u, nd, count > 0 && temperature >= (double)FLT_MIN).piece(d_out, nd).piece(d_bits, streams);
     mem.piece(d_end, streams, controls).piece(d_kept, nd, kept != nullptr);
     mem.piece(d_tab, 256 * (size_t)Q, con != nullptr).piece(d_cnt, Q, con != nullptr).piece(d_q, streams, con != nullptr);
+    mem.piece(d_acc, Q, accept != nullptr).piece(d_F, (size_t)count * fwords, accept != nullptr);
     if (int rc = mem.commit(h)) return rc;
 
     // start state (padding rows zero), inputs
@@ -1994,6 +2079,10 @@ int lstm_hip_generate_constrained(lstm_hip_t *h, int32_t streams, const uint8_t 
         HIP_TRY(hipMemcpyAsync(d_tab, con->next, sizeof(uint16_t) * 256 * (size_t)Q, hipMemcpyHostToDevice, h->st));
         HIP_TRY(hipMemcpyAsync(d_cnt, ccount.data(), sizeof(uint16_t) * Q, hipMemcpyHostToDevice, h->st));
         HIP_TRY(hipMemcpyAsync(d_q, cstate.data(), sizeof(int32_t) * streams, hipMemcpyHostToDevice, h->st));
+    }
+    if (accept) { // rows 0 .. count - 1: draw i reads row count - 1 - i
+        HIP_TRY(hipMemcpyAsync(d_acc, accept, (size_t)Q, hipMemcpyHostToDevice, h->st));
+        if (count > 0) HIP_TRY(hipMemcpyAsync(d_F, frows.data(), sizeof(uint32_t) * (size_t)count * fwords, hipMemcpyHostToDevice, h->st));
     }
     const Model m = model_of(h);
     RUN(K_PACK_U, pack_U(m.U, Ufwd, nullptr, N, h->st));
@@ -2026,6 +2115,9 @@ int lstm_hip_generate_constrained(lstm_hip_t *h, int32_t streams, const uint8_t 
     a.ctab = d_tab;
     a.ccount = d_cnt;
     a.cstate = d_q;
+    a.accept = d_acc;
+    a.frows = d_F;
+    a.fwords = fwords;
     const bool stable = (h->cfg.flags & LSTM_HIP_STABLE_SOFTMAX) != 0;
     const long long steps = (long long)max_len + count; // inputs of the longest stream
     int cur = 0;
@@ -2118,46 +2210,8 @@ int lstm_hip_beam_search_constrained(lstm_hip_t *h, int32_t streams, const uint8
         if (prompt_off)
             if (int rc = walk_constraint("beam_search", "prompt byte", con, streams, prompts, prompt_off, cstate, nullptr)) return rc;
     }
-    if (accept) {
-        if (((long long)count + 1) * Q > (1ll << 28))
-            return fail(LSTM_HIP_EINVAL, "beam_search: (count + 1) x states = %lld above 2^28 with accepting states", ((long long)count + 1) * Q);
-        // F[0][q] = acc(q); F[R][q] = some allowed byte b of q: acc(next) if b is the stop byte, else F[R - 1][next]
-        std::vector<std::vector<uint16_t>> succ(Q); // the distinct states q's allowed bytes other than the stop byte lead to
-        std::vector<char> stops(Q, 0);              // q's stop byte is allowed and leads into an accepting state
-        for (int q = 0; q < Q; q++) {
-            for (int b = 0; b < 256; b++) {
-                const uint16_t v = con->next[(size_t)q * 256 + b];
-                if (v == 0xFFFF) continue;
-                if (b == opt->stop_byte) stops[q] = accept[v] != 0;
-                else succ[q].push_back(v);
-            }
-            std::sort(succ[q].begin(), succ[q].end());
-            succ[q].erase(std::unique(succ[q].begin(), succ[q].end()), succ[q].end());
-        }
-        frows.assign((size_t)(count + 1) * fwords, 0u);
-        auto bit = [&](int R, int q) { return (frows[(size_t)R * fwords + (q >> 5)] >> (q & 31)) & 1u; };
-        for (int q = 0; q < Q; q++)
-            if (accept[q]) frows[q >> 5] |= 1u << (q & 31);
-        // a row is a function of the row before it: once two rows in sequence are equal every later one is, and is copied
-        bool settled = false;
-        for (int R = 1; R <= count; R++) {
-            uint32_t *row = frows.data() + (size_t)R * fwords;
-            if (settled) {
-                std::copy(row - fwords, row, row);
-                continue;
-            }
-            for (int q = 0; q < Q; q++) {
-                bool f = stops[q];
-                for (size_t i = 0; !f && i < succ[q].size(); i++) f = bit(R - 1, succ[q][i]);
-                if (f) row[q >> 5] |= 1u << (q & 31);
-            }
-            settled = std::equal(row, row + fwords, row - fwords);
-        }
-        for (int s = 0; s < streams; s++)
-            if (!bit(count, cstate[s]))
-                return fail(LSTM_HIP_EINVAL, "beam_search: stream %d: no accepted string of %d bytes or fewer ending in the stop byte "
-                            "from state %d", s, count, cstate[s]);
-    }
+    if (accept)
+        if (int rc = deadline_rows("beam_search", con, accept, opt->stop_byte, count, cstate, frows)) return rc;
     if (count == 0) { // nothing is selected: every slot is as it starts
         for (int c = 0; c < cols; c++) {
             if (out_len) out_len[c] = 0;

@@ -3,8 +3,8 @@
 // over many streams at once.  No HIP, no torch here.
 //
 //   lstm_generate --load PREFIX [--score FILE ...] [--score-bytes FILE [--top N]] [--count C --streams K --prime TEXT|--prime-file F
-//                 --temperature T --top-k K --top-p P --stop-byte B --seed S --utf8 --allow SPEC --ban SPEC
-//                 | --beams W --nbest K --length-alpha A [--constrain-search --utf8 --allow SPEC --ban SPEC]]
+//                 --temperature T --top-k K --top-p P --stop-byte B --seed S --utf8 --allow SPEC --ban SPEC --regex PATTERN
+//                 | --beams W --nbest K --length-alpha A [--constrain-search --utf8 --allow SPEC --ban SPEC --regex PATTERN]]
 //                 [--fast-math] [--stable-softmax] [--device D]
 //
 // --load reads the five-file text checkpoint PREFIX_{W,U,Why,b,by}.txt (checkpoint.h); N is the rows of W / 4.
@@ -36,6 +36,16 @@
 // states.  A stream whose table allows fewer than W continuations has fewer hypotheses: those that do not exist are not
 // printed, and --nbest counts the ones that do.  Without --constrain-search the three are refused with --beams, as they were
 // before the search took a constraint: they are options of drawing, and a script that relied on the refusal still gets it.
+// --regex PATTERN draws whole matches of PATTERN only (lstm_hip_dfa_regex, lstm_hip_generate_accepting): a byte regular
+// expression with the meaning Python's re.fullmatch gives a bytes pattern, in the subset include/lstm_hip.h lists (a
+// quantifier binds the last byte: group a multi-byte character before repeating it).  With --stop-byte B a sample is a match
+// of at most C - 1 bytes followed by B, and B must not occur in a match; WITHOUT --stop-byte a sample is a match of EXACTLY C
+// bytes; a pattern that has none of that length is refused, and so is one with a match that nothing can follow (its table
+// would hold a state without an allowed byte, which the calls refuse): such patterns take a stop byte.  The prompt is walked through the pattern first, so it must
+// begin a match.  With --utf8 the matches are also well-formed UTF-8 (lstm_hip_dfa_intersect with the UTF-8 table, whole
+// characters only); --allow / --ban then restrict the resulting table (lstm_hip_dfa_restrict).  With --beams
+// --constrain-search the same table and accepting states go to the search.  A pattern the compiler refuses ends the program
+// with the library's message, which names the offending byte of the pattern.
 // --stable-softmax scores and draws at temperature 1 with the
 // max-shifted softmax (LSTM_HIP_STABLE_SOFTMAX), for checkpoints whose logits pass expf's range.
 #include "../../include/lstm_hip.h"
@@ -56,9 +66,9 @@ const char *const kUsage =
     "usage: lstm_generate --load PREFIX [--score FILE ...] [--score-bytes FILE [--top N]]\n"
     "                     [--count C --streams K --prime TEXT|--prime-file F\n"
     "                     --temperature T --top-k K --top-p P --stop-byte B --seed S\n"
-    "                     --utf8 --allow SPEC --ban SPEC\n"
+    "                     --utf8 --allow SPEC --ban SPEC --regex PATTERN\n"
     "                     | --beams W --nbest K --length-alpha A\n"
-    "                       [--constrain-search --utf8 --allow SPEC --ban SPEC]]\n"
+    "                       [--constrain-search --utf8 --allow SPEC --ban SPEC --regex PATTERN]]\n"
     "                     [--fast-math] [--stable-softmax] [--device D]\n"
     "  --score-bytes FILE  one row per byte: offset, byte, surprisal, entropy, rank; then the --score line of FILE\n"
     "  --top N        with --score-bytes: add the N most likely bytes of every place (1..8) with their bits\n"
@@ -69,6 +79,9 @@ const char *const kUsage =
     "                 (with --beams --constrain-search: search whole characters only)\n"
     "  --allow SPEC   draw only these bytes: comma-separated bytes and ranges, decimal or 0x hex (0x20-0x7e,10)\n"
     "  --ban SPEC     never draw these bytes (same SPEC); with --utf8 both restrict the UTF-8 table\n"
+    "  --regex PATTERN  draw whole matches of this byte regular expression only (re.fullmatch on bytes; a quantifier\n"
+    "                 binds the last byte).  With --stop-byte B: a match, then B.  Without it: a match of exactly --count\n"
+    "                 bytes.  --utf8 intersects with well-formed UTF-8; --allow / --ban restrict the result\n"
     "  --beams W      beam search with W hypotheses per stream (1..32) instead of drawing; W x --streams <= 4096;\n"
     "  --constrain-search  with --beams: let --utf8 / --allow / --ban constrain the search to the continuations they\n"
     "                 accept (without it they are refused with --beams); hypotheses that do not exist are not printed\n"
@@ -155,7 +168,9 @@ struct Options {
     std::vector<std::string> constraint_opts;      // --utf8, --allow, --ban as given
     uint32_t seed = 1;
     unsigned flags = 0;
-    bool utf8 = false, has_allow = false, has_ban = false;
+    bool utf8 = false, has_allow = false, has_ban = false, has_regex = false;
+    std::string regex;           // --regex PATTERN
+    std::vector<uint8_t> accept; // with --regex: the accepting states of `table`
     bool constrain_search = false; // --constrain-search: with --beams the constraint options constrain the search
     uint8_t allow[256] = {}, ban[256] = {};
     std::vector<uint16_t> table; // the constraint of --utf8 / --allow / --ban (empty: none), `states` rows of 256
@@ -219,6 +234,11 @@ Options parse(int argc, char **argv) {
             }
             o.sampling_opts.push_back(a);
             o.constraint_opts.push_back(a);
+        } else if (a == "--regex") {
+            o.regex = val();
+            o.has_regex = true;
+            o.sampling_opts.push_back(a);
+            o.constraint_opts.push_back(a);
         } else if (a == "--beams") {
             o.beams = parse_int(a, val(), 1, 32);
             o.sampling_opts.push_back(a);
@@ -260,7 +280,7 @@ Options parse(int argc, char **argv) {
         if (!o.draw_opts.empty()) usage(o.draw_opts[0] + " means nothing with --beams: a beam search draws nothing");
         if (!o.constraint_opts.empty() && !o.constrain_search)
             usage(o.constraint_opts[0] + " is an option of drawing: with --beams it needs --constrain-search");
-        if (o.constrain_search && o.constraint_opts.empty()) usage("--constrain-search needs --utf8, --allow or --ban");
+        if (o.constrain_search && o.constraint_opts.empty()) usage("--constrain-search needs --utf8, --allow, --ban or --regex");
         if (o.nbest > o.beams) usage("--nbest cannot pass --beams");
         if (o.beams * o.streams > 4096) usage("--beams x --streams must be at most 4096");
         if ((long long)std::max(o.count, 0L) * o.streams * o.beams > (1LL << 31) - 1) usage("--count x --streams x --beams is too large");
@@ -270,6 +290,32 @@ Options parse(int argc, char **argv) {
         o.states = o.utf8 ? lstm_hip_dfa_utf8(nullptr) : 1;
         o.table.assign((size_t)o.states * 256, 0); // one state: every byte leads back to it
         if (o.utf8) lstm_hip_dfa_utf8(o.table.data());
+        if (o.has_regex) { // the pattern's table (followed by the stop byte, if any), then its product with the UTF-8 table
+            const uint8_t *pat = reinterpret_cast<const uint8_t *>(o.regex.data());
+            int32_t q = lstm_hip_dfa_regex(pat, o.regex.size(), (int32_t)o.stop_byte, nullptr, nullptr, 0, nullptr);
+            if (q < 0) die(std::string("--regex: ") + lstm_hip_last_error());
+            std::vector<uint16_t> rx((size_t)q * 256);
+            std::vector<uint8_t> acc(q);
+            if (lstm_hip_dfa_regex(pat, o.regex.size(), (int32_t)o.stop_byte, rx.data(), acc.data(), q, nullptr) != q)
+                die(std::string("--regex: ") + lstm_hip_last_error());
+            if (o.stop_byte < 0) // the calls refuse a table with a reachable row that allows nothing, and pruning it would drop matches
+                for (int32_t s = 0; s < q; s++)
+                    if (acc[s] && std::all_of(rx.begin() + (size_t)s * 256, rx.begin() + (size_t)(s + 1) * 256, [](uint16_t v) { return v == 0xFFFF; }))
+                        die("--regex without --stop-byte: the pattern has a match that nothing can follow, so its table has a state "
+                            "without an allowed byte; give --stop-byte B (a match, then B)");
+            if (o.utf8) {
+                std::vector<uint8_t> boundary(o.states, 0);
+                boundary[0] = 1;
+                const int32_t p = lstm_hip_dfa_intersect(rx.data(), q, acc.data(), o.table.data(), o.states, boundary.data(), nullptr, nullptr, 0);
+                if (p < 0) die(std::string("--regex with --utf8: ") + lstm_hip_last_error());
+                std::vector<uint16_t> both((size_t)p * 256);
+                std::vector<uint8_t> acc2(p);
+                if (lstm_hip_dfa_intersect(rx.data(), q, acc.data(), o.table.data(), o.states, boundary.data(), both.data(), acc2.data(), p) != p)
+                    die(std::string("--regex with --utf8: ") + lstm_hip_last_error());
+                rx.swap(both), acc.swap(acc2), q = p;
+            }
+            o.table.swap(rx), o.accept.swap(acc), o.states = q;
+        }
         uint8_t allow[256];
         for (int b = 0; b < 256; b++) allow[b] = (!o.has_allow || o.allow[b]) && !o.ban[b];
         if (lstm_hip_dfa_restrict(o.table.data(), o.states, allow) != 0)
@@ -366,11 +412,12 @@ int main(int argc, char **argv) {
         if (o.table.empty())
             CK(lstm_hip_beam_search(h, K, prompts.data(), off.data(), nullptr, nullptr, &opt, C, out.data(), out_len.data(),
                                     bits.data(), nullptr, nullptr));
-        else { // --utf8: a hypothesis may end on a character boundary only (state 0 of the table)
+        else { // --utf8: a hypothesis may end on a character boundary only (state 0 of the table); --regex: on a match
             const lstm_hip_constraint con{(uint32_t)sizeof(lstm_hip_constraint), o.states, o.table.data()};
             std::vector<uint8_t> accept(o.states, 0);
             accept[0] = 1;
-            const lstm_hip_beam_constraint bc{(uint32_t)sizeof(lstm_hip_beam_constraint), &con, o.utf8 ? accept.data() : nullptr};
+            if (o.has_regex) accept = o.accept;
+            const lstm_hip_beam_constraint bc{(uint32_t)sizeof(lstm_hip_beam_constraint), &con, o.utf8 || o.has_regex ? accept.data() : nullptr};
             CK(lstm_hip_beam_search_constrained(h, K, prompts.data(), off.data(), nullptr, nullptr, &opt, C, out.data(),
                                                 out_len.data(), bits.data(), nullptr, nullptr, &bc, nullptr, nullptr));
         }
@@ -409,7 +456,13 @@ int main(int argc, char **argv) {
         if (o.table.empty())
             CK(lstm_hip_generate_ex(h, K, prompts.data(), off.data(), nullptr, nullptr, &opt, u.empty() ? nullptr : u.data(), C,
                                     out.data(), nullptr, nullptr, nullptr, out_len.data(), nullptr));
-        else {
+        else if (o.has_regex) { // whole matches only: the accepting states and the deadline of --count
+            const lstm_hip_constraint con{(uint32_t)sizeof(lstm_hip_constraint), o.states, o.table.data()};
+            const lstm_hip_beam_constraint bc{(uint32_t)sizeof(lstm_hip_beam_constraint), &con, o.accept.data()};
+            CK(lstm_hip_generate_accepting(h, K, prompts.data(), off.data(), nullptr, nullptr, &opt, u.empty() ? nullptr : u.data(), C,
+                                           out.data(), nullptr, nullptr, nullptr, out_len.data(), nullptr, &bc, nullptr,
+                                           end_state.data()));
+        } else {
             const lstm_hip_constraint con{(uint32_t)sizeof(lstm_hip_constraint), o.states, o.table.data()};
             CK(lstm_hip_generate_constrained(h, K, prompts.data(), off.data(), nullptr, nullptr, &opt, u.empty() ? nullptr : u.data(),
                                              C, out.data(), nullptr, nullptr, nullptr, out_len.data(), nullptr, &con, nullptr,
@@ -420,7 +473,7 @@ int main(int argc, char **argv) {
             std::vector<uint8_t> text(prime);
             for (int i = 0; i < out_len[s]; i++) text.push_back(out[(size_t)i * K + s]);
             size_t n = text.size();
-            if (o.utf8 && end_state[s] != 0) { // cut back to the last character boundary (state 0 of the table)
+            if (o.utf8 && !o.has_regex && end_state[s] != 0) { // cut back to the last character boundary (state 0 of the table)
                 int32_t q = 0;
                 n = 0;
                 for (size_t i = 0; i < text.size(); i++) {

@@ -92,6 +92,7 @@ SYMBOLS = [
     "lstm_hip_set_averaging", "lstm_hip_get_average", "lstm_hip_set_average", "lstm_hip_get_averaging_counts",
     "lstm_hip_set_averaging_counts", "lstm_hip_set_inference_source",
     "lstm_hip_set_weight_drop", "lstm_hip_get_weight_drop", "lstm_hip_weight_drop_mask",
+    "lstm_hip_dfa_regex", "lstm_hip_dfa_intersect", "lstm_hip_generate_accepting",
 ]
 
 
@@ -178,6 +179,63 @@ def dfa_restrict(table, allow):
     flags = np.ascontiguousarray(np.asarray(allow).reshape(256) != 0, dtype=np.uint8)
     _chk(load_library().lstm_hip_dfa_restrict(_ptr(table, C.c_uint16), C.c_int32(table.shape[0]), _ptr(flags, C.c_uint8)))
     return table
+
+
+def dfa_regex(pattern, stop_byte=-1):
+    """lstm_hip_dfa_regex: a byte regular expression (bytes, or str taken as UTF-8) compiled to (table, accept): the minimal
+    automaton of the language as a (states, 256) uint16 table and its accepting states as uint8 flags [states].  A match is
+    a whole-string match, with the meaning re.fullmatch gives a bytes pattern, for the subset include/lstm_hip.h lists; a
+    quantifier binds the last BYTE, so group a multi-byte character before repeating it.  stop_byte 0..255 gives the table of the language followed by that
+    byte, whose one accepting state loops on it: the form Lstm.generate(constraint=, accept=, stop_byte=) and
+    Lstm.beam_search take as it is.  Raises LstmHipError with the library's message (it names the pattern byte); the
+    exception's error_pos holds that offset, -1 where there is none.  Needs no device."""
+    lib = load_library()
+    pat = np.frombuffer(pattern.encode("utf-8") if isinstance(pattern, str) else bytes(pattern), np.uint8)
+    lib.lstm_hip_dfa_regex.restype = C.c_int32
+    lib.lstm_hip_dfa_regex.argtypes = [C.POINTER(C.c_uint8), C.c_size_t, C.c_int32, C.POINTER(C.c_uint16), C.POINTER(C.c_uint8),
+                                       C.c_int32, C.POINTER(C.c_int32)]
+    data = np.ascontiguousarray(pat if pat.size else np.zeros(1, np.uint8))
+    pos = C.c_int32(-1)
+    table = accept = None
+    for _ in range(2):  # the size, then the table
+        q = int(lib.lstm_hip_dfa_regex(_ptr(data, C.c_uint8), pat.size, int(stop_byte),
+                                       _ptr(table, C.c_uint16) if table is not None else None,
+                                       _ptr(accept, C.c_uint8) if accept is not None else None,
+                                       0 if table is None else table.shape[0], C.byref(pos)))
+        if q < 0:
+            err = LstmHipError(f"lstm_hip error {q}: {lib.lstm_hip_last_error().decode()}")
+            err.error_pos = int(pos.value)
+            raise err
+        if table is None:
+            table, accept = np.zeros((q, 256), np.uint16), np.zeros(q, np.uint8)
+    return table, accept
+
+
+def dfa_intersect(a, acc_a, b, acc_b):
+    """lstm_hip_dfa_intersect: (table, accept) of the strings both automata accept: tables a, b as (states, 256) uint16,
+    acc_a, acc_b their accepting flags [states] or None (every state accepts).  The product is trimmed, minimised and
+    numbered as dfa_regex's results are.  Raises LstmHipError when nothing is accepted by both or the result has more than
+    4096 states.  Needs no device."""
+    lib = load_library()
+    lib.lstm_hip_dfa_intersect.restype = C.c_int32
+    tabs, accs = [], []
+    for t, acc in ((a, acc_a), (b, acc_b)):
+        t = np.ascontiguousarray(t, dtype=np.uint16)
+        assert t.ndim == 2 and t.shape[1] == 256, t.shape
+        tabs.append(t)
+        accs.append(None if acc is None else np.ascontiguousarray(np.asarray(acc).reshape(t.shape[0]) != 0, dtype=np.uint8))
+    table = accept = None
+    for _ in range(2):  # the size, then the table
+        q = int(lib.lstm_hip_dfa_intersect(
+            _ptr(tabs[0], C.c_uint16), C.c_int32(tabs[0].shape[0]), _ptr(accs[0], C.c_uint8) if accs[0] is not None else None,
+            _ptr(tabs[1], C.c_uint16), C.c_int32(tabs[1].shape[0]), _ptr(accs[1], C.c_uint8) if accs[1] is not None else None,
+            _ptr(table, C.c_uint16) if table is not None else None, _ptr(accept, C.c_uint8) if accept is not None else None,
+            C.c_int32(0 if table is None else table.shape[0])))
+        if q < 0:
+            _chk(q)
+        if table is None:
+            table, accept = np.zeros((q, 256), np.uint16), np.zeros(q, np.uint8)
+    return table, accept
 
 
 def _bytes_list(texts):
@@ -456,7 +514,7 @@ class Lstm:
         return out, h0, c0
 
     def generate(self, prompts=None, count=0, u=None, temperature=1.0, h0=None, c0=None, streams=None, score=False,
-                 top_k=0, top_p=1.0, stop_byte=None, info=False, constraint=None, start_state=None):
+                 top_k=0, top_p=1.0, stop_byte=None, info=False, constraint=None, start_state=None, accept=None):
         """lstm_hip_generate: `streams` independent streams, each fed its prompt (bytes or a uint8 array) and then `count`
         drawn bytes.  u: draws [count, streams] (may be None only at temperature 0); h0, c0: [streams, N] or None (zeros).
         Returns (out [count, streams] uint8, bits [streams] float64 -- the prompts' summed -log2 p, or None unless
@@ -468,7 +526,11 @@ class Lstm:
         constraint: a (states, 256) uint16 table (dfa_utf8(), dfa_restrict(), or the caller's own: the state after byte b in
         state q, 0xFFFF where b is forbidden) for lstm_hip_generate_constrained: every stream draws only bytes its state
         allows, from start_state [streams] (None: 0) advanced over its prompt; info then also has "end_state": int32
-        [streams].  With constraint=None the calls are those made without the argument."""
+        [streams].  With constraint=None the calls are those made without the argument.
+        accept: [states] flags, nonzero where a stream may end, with the meaning it has in beam_search
+        (lstm_hip_generate_accepting): a byte is drawn only where an accepted end can still be reached within `count`, so
+        every stream ends in an accepting state, by its stop byte or with exactly `count` bytes.  accept=None is the call
+        made without the argument."""
         if streams is None:
             streams = len(prompts) if prompts is not None else (np.asarray(h0).shape[0] if h0 is not None else
                                                                 (np.asarray(u).reshape(count, -1).shape[1] if u is not None and count > 0 else 1))
@@ -496,6 +558,8 @@ class Lstm:
                 _ptr(bits, C.c_double) if score else None, _ptr(h), _ptr(c))
         if constraint is None and start_state is not None:
             raise LstmHipError("generate: start_state given without a constraint")
+        if constraint is None and accept is not None:
+            raise LstmHipError("generate: accept given without a constraint")
         if constraint is None and top_k == 0 and top_p == 1.0 and stop_byte is None and not info:
             _chk(self.lib.lstm_hip_generate(*args, C.c_double(temperature), *tail))
             return out, bits, h, c
@@ -509,6 +573,13 @@ class Lstm:
             con = _Constraint(C.sizeof(_Constraint), table.shape[0], _ptr(table, C.c_uint16))
             q0 = None if start_state is None else np.ascontiguousarray(start_state, dtype=np.int32).reshape(streams)
             q1 = np.zeros(streams, np.int32)
+            if accept is not None:
+                acc = np.ascontiguousarray(np.asarray(accept).reshape(table.shape[0]) != 0, dtype=np.uint8)
+                bc = _BeamConstraint(C.sizeof(_BeamConstraint), C.pointer(con), _ptr(acc, C.c_uint8))
+                _chk(self.lib.lstm_hip_generate_accepting(
+                    *args, C.byref(opt), *tail, _ptr(out_len, C.c_int32), _ptr(kept, C.c_uint16) if info else None, C.byref(bc),
+                    _ptr(q0, C.c_int32) if q0 is not None else None, _ptr(q1, C.c_int32)))
+                return (out, bits, h, c, {"out_len": out_len, "kept": kept, "end_state": q1}) if info else (out, bits, h, c)
             _chk(self.lib.lstm_hip_generate_constrained(
                 *args, C.byref(opt), *tail, _ptr(out_len, C.c_int32), _ptr(kept, C.c_uint16) if info else None, C.byref(con),
                 _ptr(q0, C.c_int32) if q0 is not None else None, _ptr(q1, C.c_int32)))

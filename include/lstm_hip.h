@@ -383,7 +383,7 @@ int lstm_hip_generate_ex(lstm_hip_t *h, int32_t streams, const uint8_t *prompts,
  *      start_state = end_state = NULL: that call makes the launches it made before this function existed.
  *        table   con->next[q*256 + b], con->states = Q states (1..4096): the state after byte b in state q (a value < Q), or
  *                0xFFFF: byte b is forbidden in state q.  A_q is the number of allowed bytes of state q.  There are no
- *                accepting states: the caller reads the final state.
+ *                accepting states: the caller reads the final state (lstm_hip_generate_accepting, below, has them).
  *        prompt  q starts at start_state[s] (NULL: 0) and is advanced over the stream's prompt bytes on the host, before
  *                anything is launched; a prompt byte that is forbidden where it stands is LSTM_HIP_EINVAL (the message names
  *                the stream and the byte's offset in its prompt).  Prompt scoring (bits) ignores the constraint: it stays the
@@ -430,6 +430,55 @@ int lstm_hip_generate_constrained(lstm_hip_t *h, int32_t streams, const uint8_t 
  * outside 1..4096, an entry that is neither a state nor 0xFFFF). */
 int32_t lstm_hip_dfa_utf8(uint16_t *next);
 int lstm_hip_dfa_restrict(uint16_t *next, int32_t states, const uint8_t allow[256]);
+/* ---- a byte regular expression compiled to such a table.  Host only: no handle, no device.
+ *      Returns the number of states Q, 1..4096.  With next == NULL && accept == NULL it only returns Q and ignores cap;
+ *      otherwise cap >= Q is required, next takes Q*256 entries (a next state, or 0xFFFF) and accept Q flags (1: accepting).
+ *      Every failure returns LSTM_HIP_EINVAL; lstm_hip_last_error() says what is wrong and at which byte of the pattern, and
+ *      *error_pos (may be NULL) gets that byte offset, or -1 for a failure without a position: too many states, an empty
+ *      language, a stop-byte conflict, cap too small.
+ *        language  a match is ALWAYS a whole-string match; the pattern is bytes, with the meaning Python's re.fullmatch gives a
+ *                  bytes pattern without flags, for this subset:
+ *                    literals     any byte other than \ . [ ] ( ) | * + ? { } ^ $ stands for itself, bytes >= 0x80 included:
+ *                                 UTF-8 text in a pattern is its byte sequence, and A QUANTIFIER BINDS THE LAST BYTE, as in
+ *                                 Python: group a multi-byte character before repeating it, (?:\xC3\xA9)+.
+ *                    .            any byte except 0x0A
+ *                    escapes      \n \r \t \f \v \xHH; \d \D \w \W \s \S with their ASCII meaning (\w = [A-Za-z0-9_], \s =
+ *                                 [ \t\n\r\f\v], the upper-case forms their complements over 0..255); a backslash before an
+ *                                 ASCII punctuation byte is that byte; before any other byte it is refused
+ *                    classes      [...] and [^...] of single bytes, ranges a-z and the escapes above (class escapes included,
+ *                                 though not as a range end); a - that comes first or last is a literal; ] and [ must be
+ *                                 escaped; a raw byte >= 0x80 is refused (write \xHH); [^...] is the complement over 0..255
+ *                    groups       ( ) and (?: ), both only grouping, nested at most 200 deep; every other (? form is refused
+ *                    alternation  | ; empty alternatives are allowed, and the empty pattern matches the empty string
+ *                    quantifiers  * + ? {m} {m,} {m,n} {,n} with m <= n <= 4095.  A quantifier directly behind a quantifier
+ *                                 is refused (lazy and possessive forms, a**: group first), and so is a { that does not start
+ *                                 a well-formed quantifier (stricter than Python)
+ *                    anchors      ^ and $ are refused: there is nothing to anchor
+ *        result    the MINIMAL automaton of the language, trimmed: every state can be reached from state 0 and can reach an
+ *                  accepting state.  State 0 is the start state; states are numbered breadth-first from it, the bytes of a
+ *                  state visited in ascending order, so two patterns with the same language (a|b and [ab]) give byte-identical
+ *                  tables.  A pattern that matches nothing, or whose automaton has more than 4096 states, is refused.
+ *        limits    the construction is bounded, so a pattern whose automaton explodes fails quickly instead of exhausting
+ *                  memory: at most 2^20 nodes of the unrolled pattern (a bounded repeat is copies of its operand), 32768
+ *                  states and 2^27 node visits of the subset construction before minimisation.  Past any of them:
+ *                  LSTM_HIP_EINVAL, "too many states".
+ *        stop_byte -1: the table of the language L itself, accept = L's accepting states.  Such a table can hold accepting
+ *                  states whose rows are empty; the table checks of the calls that take it apply.
+ *                  0..255: the table of L followed by the stop byte.  If the trimmed automaton of L has a transition on the
+ *                  stop byte the call fails ("the pattern can match the stop byte": a stream ends at its first drawn stop
+ *                  byte).  Otherwise every accepting state of L gets a transition on the stop byte into one new final state,
+ *                  the only accepting state, whose row allows the stop byte alone, back to itself: no reachable row is empty,
+ *                  and the generator, the scorer and beam search take the table as it is.
+ * lstm_hip_dfa_intersect builds the product of two tables from (0, 0): a byte is allowed iff both allow it, a product state
+ * accepts iff both components do (a NULL accept array: every state accepts).  The product goes through the same trimming,
+ * minimisation and numbering, with the same two-call sizing; the product may have at most 32768 states before minimisation.
+ * LSTM_HIP_EINVAL: more than 4096 states, an empty language, cap too small, or a table that is not one (NULL, states outside
+ * 1..4096, an entry that is neither a state nor 0xFFFF).  --utf8 --regex of lstm_generate is this call with the UTF-8 table
+ * and accept = {0}. */
+int32_t lstm_hip_dfa_regex(const uint8_t *pattern, size_t len, int32_t stop_byte /* -1: none */, uint16_t *next, uint8_t *accept,
+                           int32_t cap, int32_t *error_pos /* may be NULL */);
+int32_t lstm_hip_dfa_intersect(const uint16_t *a, int32_t qa, const uint8_t *acc_a /* may be NULL */, const uint16_t *b, int32_t qb,
+                               const uint8_t *acc_b /* may be NULL */, uint16_t *next, uint8_t *accept, int32_t cap);
 /* ---- beam search: per stream the W = opt->beams most likely continuations of its prompt that the
  *      search finds, with their costs in bits.  Prompts, prompt_off, h0 / c0 (N x streams; NULL = zeros) are those of
  *      lstm_hip_generate.  Stream s is fed its prompt of length L (nothing is scored during the prompt) and makes selection
@@ -523,6 +572,38 @@ int lstm_hip_beam_search_constrained(lstm_hip_t *h, int32_t streams, const uint8
                                      const lstm_hip_beam_constraint *bc /* NULL: exactly lstm_hip_beam_search */,
                                      const int32_t *start_state /* [streams], may be NULL: all 0 */,
                                      int32_t *end_state /* [streams*W], may be NULL */);
+/* ---- sampling with accepting states: lstm_hip_generate_constrained with the deadline rule of beam
+ *      search, so that every stream ends on a whole accepted string and never in the middle of a pattern.
+ *      lstm_hip_generate_constrained is a thin caller of this function, and two cases are exactly the earlier calls, with the
+ *      launches and the bits they had before this function existed: bc == NULL is lstm_hip_generate_ex, and bc->accept == NULL
+ *      is lstm_hip_generate_constrained(bc->con).  With bc->accept everything lstm_hip_generate_constrained documents holds,
+ *      except:
+ *        table F   as in lstm_hip_beam_search_constrained, with opt->stop_byte: acc(q) = accept[q] != 0; F[0][q] = acc(q);
+ *                  F[R][q] = OR over the allowed bytes b of q of acc(next[q][b]) if b is the stop byte, F[R-1][next[q][b]]
+ *                  otherwise.  It is built on the host before the first launch.
+ *        exists    at draw i of stream s, with R = count - i, q the stream's state and nx = next[q][m], byte m EXISTS iff nx is
+ *                  allowed and: acc(nx) if m is the stop byte, F[R-1][nx] otherwise.  E is the number of existing bytes;
+ *                  E >= 1 at every draw of every stream, because F[count][q0] is checked and the rule keeps F[R][q] true.
+ *        draw      z'_m = z_m where m exists, -inf otherwise; everything said of z' holds with E in place of A_q: rank, max,
+ *                  expf and the normalising sum see the mask, a tempered draw is a filtered draw with keep = min(keep_k,
+ *                  keep_p, E), greedy takes the argmax of z'.  A byte that does not exist and was chosen all the same
+ *                  (non-finite logits only) is replaced by the lowest EXISTING byte.  Prompt scoring ignores all of this.
+ *        end       a stream ends with its first drawn stop byte, which now exists only where it leads into an accepting state;
+ *                  a stream that never draws it holds exactly count bytes and stands in an accepting state.  So
+ *                  acc(end_state[s]) holds for every stream, always, also with non-finite parameters.
+ *        chaining  two calls in sequence are NOT the one long call any more: each call has its own deadline, so the first
+ *                  call ends every stream in an accepting state where the long call would only have passed through.
+ *        count 0   nothing is drawn; every stream's state after its prompt must be accepting.
+ *      LSTM_HIP_EINVAL (the handle stays usable, nothing is launched), beside those of lstm_hip_generate_constrained:
+ *      bc->size != sizeof(lstm_hip_beam_constraint); bc->con NULL; F[count][q0] false for some stream (the message names it:
+ *      "no accepted string of `count` bytes or fewer ending in the stop byte"; with count 0: q0 not accepting); (count + 1) *
+ *      states above 2^28. */
+int lstm_hip_generate_accepting(lstm_hip_t *h, int32_t streams, const uint8_t *prompts, const uint64_t *prompt_off,
+                                const float *h0, const float *c0, const lstm_hip_sampling *opt, const double *u, int32_t count,
+                                uint8_t *out, double *bits, float *h_out, float *c_out, int32_t *out_len, uint16_t *kept,
+                                const lstm_hip_beam_constraint *bc /* NULL: exactly lstm_hip_generate_ex */,
+                                const int32_t *start_state /* [streams], may be NULL: all 0 */,
+                                int32_t *end_state /* [streams], may be NULL */);
 /* ---- per-byte scores: what the model thinks of every byte of given texts.  Stream s is
  *      text[text_off[s] .. text_off[s+1]), 1 <= streams <= 4096; empty streams are allowed (no entries, h_out = the start
  *      state).  h0 / c0 / h_out / c_out are N x streams as in lstm_hip_generate (NULL = zeros / not wanted); h_out is the
