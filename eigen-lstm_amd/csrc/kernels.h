@@ -354,6 +354,35 @@ void average(const float *p, float *a, size_t n, float w, bool copy, int cus, hi
 void weight_drop_mask(const float *src, float *dst, int Np, int Nl, uint64_t seed, uint64_t t, uint32_t thr, float scale, int cus,
                       hipStream_t st);
 
+// ---- forward-only evaluation of many texts (lstm_hip_eval_texts), around the unchanged forward
+//      path of an internal handle with S = EVAL_STEPS + 1 and B = lanes.  slot[w * lanes + l] is the stream lane l holds in
+//      window w (-1: idle); that window holds steps EVAL_STEPS * (w - first[s]) .. of stream s in rows 1 .. EVAL_STEPS.
+//      eval_window writes rows 1 .. of xi / ti (input byte j, target byte j + 1 where j + 1 >= skip[s], else -1; both -1 past
+//      the stream's end or on an idle lane) and column 0 of H / C of every busy lane: the stream's column of H0 / C0 in its
+//      first window, else column EVAL_STEPS of the same lane.  eval_fold, behind the softmax launch: one thread per lane adds
+//      (double)colloss of the lane's scored rows, in row order, into bits[s] and scatters the floats to sur (may be null) at
+//      the scored byte's place, off[s] + j + 1; the stream's last column goes to column s of Hout / Cout (may be null) in
+//      the window where it ends.  Both: one launch of at most `cus` workgroups of 256 threads striding over lanes x rows and
+//      lanes x N, plain vector loads and stores only.
+constexpr int EVAL_STEPS = 128;
+struct EvalArgs {
+    const uint8_t *text;
+    const uint64_t *off;    // [streams + 1]
+    const uint64_t *skip;   // [streams]
+    const int32_t *slot;    // [windows][lanes]
+    const int64_t *first;   // [streams]
+    const float *H0, *C0;   // [streams][N]
+    int32_t *xi, *ti;       // [EVAL_STEPS + 1][lanes]
+    float *H, *C;           // [EVAL_STEPS + 1][lanes][N]
+    const float *colloss;   // [EVAL_STEPS][lanes]
+    double *bits;           // [streams]
+    float *sur;             // [off[streams]] or null
+    float *Hout, *Cout;     // [streams][N] or null
+    int lanes, N;
+};
+void eval_window(const EvalArgs &a, int64_t w, int cus, hipStream_t st);
+void eval_fold(const EvalArgs &a, int64_t w, int cus, hipStream_t st);
+
 // ---- B = 1 recurrence for the evaluator / sampler (OV/lstm_eigen_class_CUDA/lstm.cc:578-720)
 // One workgroup with b1_lds_bytes(N) of dynamic LDS, which the caller checks against the device's opt-in limit first; both
 // return the status of the grant and of the launch.

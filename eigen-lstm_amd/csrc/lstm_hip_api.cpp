@@ -198,6 +198,7 @@ struct lstm_hip_ctx {
     int32_t *head_buf = nullptr; // (do_adagrad)
     int32_t global_B = 0;
     lstm_hip_ctx *eval_h = nullptr; // internal B = 1 handle used by lstm_hip_eval_bits
+    lstm_hip_ctx *texts_h = nullptr; // internal B = lanes handle used by lstm_hip_eval_texts (remade when lanes changes)
     char *gen_scratch = nullptr;    // lstm_hip_generate's working memory: grows to the largest call, freed with the handle
     size_t gen_scratch_bytes = 0;
     int stride = 1, carry_col = 1; // window advance per iteration and the column that becomes the carry
@@ -914,6 +915,7 @@ int lstm_hip_destroy(lstm_hip_t *h) {
     if (!h) return 0;
     (void)hipSetDevice(h->cfg.device);
     if (h->eval_h) (void)lstm_hip_destroy(h->eval_h);
+    if (h->texts_h) (void)lstm_hip_destroy(h->texts_h);
     if (h->st) (void)hipStreamSynchronize(h->st);
     if (h->st2) (void)hipStreamSynchronize(h->st2);
     if (h->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(h->comm);
@@ -2438,6 +2440,172 @@ int lstm_hip_score(lstm_hip_t *h, int32_t streams, const uint8_t *text, const ui
     if (int rc = download_states(h, h_out, c_out, a.h_out, a.c_out, stage, streams)) return rc;
     HIP_TRY(hipStreamSynchronize(h->st));
     if (o.end_state) std::copy(cstate.begin(), cstate.end(), o.end_state);
+    return 0;
+}
+
+// Held-out bits of many texts (include/lstm_hip.h).  The schedule first: host only.
+static int64_t eval_plan(int32_t lanes, int32_t streams, const uint64_t *off, int32_t *lane_of, int64_t *first_window,
+                         std::vector<int32_t> *slot) { // slot (may be null): [windows][lanes], the stream a lane holds, -1 idle
+    std::vector<int64_t> next(lanes, 0);              // every lane's next free window
+    std::vector<std::pair<int32_t, int64_t>> placed(streams, {-1, -1});
+    // lowest next free window, lowest lane on ties: a heap of (window, lane) pairs
+    typedef std::pair<int64_t, int32_t> Free;
+    std::vector<Free> heap;
+    for (int32_t l = 0; l < lanes; l++) heap.push_back({0, l});
+    const auto later = [](const Free &a, const Free &b) { return a > b; };
+    std::make_heap(heap.begin(), heap.end(), later);
+    int64_t windows = 0;
+    for (int32_t s = 0; s < streams; s++) {
+        const uint64_t len = off[s + 1] - off[s], n = len > 0 ? len - 1 : 0;
+        if (n > 0) {
+            std::pop_heap(heap.begin(), heap.end(), later);
+            Free &f = heap.back();
+            placed[s] = {f.second, f.first};
+            f.first += (int64_t)((n + LSTM_HIP_EVAL_STEPS - 1) / LSTM_HIP_EVAL_STEPS);
+            next[f.second] = f.first;
+            windows = std::max(windows, f.first);
+            std::push_heap(heap.begin(), heap.end(), later);
+        }
+        if (lane_of) lane_of[s] = placed[s].first;
+        if (first_window) first_window[s] = placed[s].second;
+    }
+    if (slot) {
+        slot->assign((size_t)windows * lanes, -1);
+        for (int32_t s = 0; s < streams; s++) {
+            if (placed[s].first < 0) continue;
+            const uint64_t n = off[s + 1] - off[s] - 1;
+            const int64_t k = (int64_t)((n + LSTM_HIP_EVAL_STEPS - 1) / LSTM_HIP_EVAL_STEPS);
+            for (int64_t w = placed[s].second; w < placed[s].second + k; w++) (*slot)[(size_t)w * lanes + placed[s].first] = s;
+        }
+    }
+    return windows;
+}
+static int eval_status(const char *which) { // (not among the window's timed kernels: no statistics row)
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(LSTM_HIP_EHIP, "launch of %s failed: %s", which, hipGetErrorString(e));
+    return 0;
+}
+
+int64_t lstm_hip_eval_plan(int32_t lanes, int32_t streams, const uint64_t *text_off, int32_t *lane_of, int64_t *first_window) {
+    if (lanes < 1 || lanes > 4096) return fail(LSTM_HIP_EINVAL, "eval_plan: lanes must be in [1, 4096] (got %d)", lanes);
+    if (streams < 1) return fail(LSTM_HIP_EINVAL, "eval_plan: streams must be >= 1 (got %d)", streams);
+    if (int rc = check_offsets("eval_plan", "text_off", text_off, streams)) return rc;
+    return eval_plan(lanes, streams, text_off, lane_of, first_window, nullptr);
+}
+
+// The device loop: per window k_eval_window, the internal handle's unchanged do_forward, k_eval_fold, all on the internal
+// handle's stream; the uploads and the state copies at either end run on the parent's, as every inference call's do, with the
+// parent's generator scratch as working memory.  The internal handle runs in the window loop's mode that skips the
+// probability store (nothing reads them); its profiling is off, so the parent's kernel statistics do not move.
+int lstm_hip_eval_texts(lstm_hip_t *h, int32_t streams, const uint8_t *text, const uint64_t *text_off, const float *h0, const float *c0,
+                        const uint64_t *skip, const lstm_hip_eval_opt *opt, double *bits, float *surprisal, float *h_out,
+                        float *c_out, float *elapsed_ms) {
+    CHECK(h);
+    if (opt && opt->size != sizeof(lstm_hip_eval_opt))
+        return fail(LSTM_HIP_EINVAL, "eval_texts: options of %u bytes, expected %zu", opt->size, sizeof(lstm_hip_eval_opt));
+    if (opt && (opt->lanes < 0 || opt->lanes > 4096))
+        return fail(LSTM_HIP_EINVAL, "eval_texts: lanes must be in [0, 4096] (got %d)", opt->lanes);
+    if (streams < 1) return fail(LSTM_HIP_EINVAL, "eval_texts: streams must be >= 1 (got %d)", streams);
+    if (int rc = check_offsets("eval_texts", "text_off", text_off, streams)) return rc;
+    const uint64_t total = text_off[streams];
+    if (total > 0 && !text) return fail(LSTM_HIP_EINVAL, "eval_texts: null text with %llu bytes to read", (unsigned long long)total);
+    const int lanes = opt && opt->lanes > 0 ? opt->lanes : h->cfg.B;
+    const int N = h->cfg.N;
+
+    std::vector<int32_t> slot;
+    std::vector<int64_t> first(streams);
+    const int64_t windows = eval_plan(lanes, streams, text_off, nullptr, first.data(), &slot);
+
+    HIP_TRY(hipStreamSynchronize(h->st));
+    if (h->texts_h && h->texts_h->cfg.B != lanes) {
+        (void)lstm_hip_destroy(h->texts_h);
+        h->texts_h = nullptr;
+    }
+    if (!h->texts_h) {
+        lstm_hip_config c = h->cfg; // (cfg.N is the parent's internal width, as for the B = 1 evaluator's handle)
+        c.S = LSTM_HIP_EVAL_STEPS + 1;
+        c.B = lanes;
+        c.flags = (h->cfg.flags & (LSTM_HIP_FAST_MATH | LSTM_HIP_STABLE_SOFTMAX | LSTM_HIP_STEP_KERNELS)) | LSTM_HIP_NO_FUSED_GRADS;
+        if (int rc = lstm_hip_create(&c, &h->texts_h)) return rc;
+    }
+    lstm_hip_ctx *e = h->texts_h;
+
+    const size_t n = (size_t)N * streams, nl = (size_t)h->N_log * streams, tot = (size_t)total;
+    const bool keep = h_out || c_out;
+    float *H0, *C0, *ho, *stage, *d_sur;
+    uint64_t *d_off, *d_skip;
+    int64_t *d_first;
+    int32_t *d_slot;
+    uint8_t *d_text;
+    double *d_bits;
+    Scratch mem;
+    mem.piece(H0, n).piece(C0, n).piece(ho, 2 * n, keep).piece(stage, 2 * nl, h->padded());
+    mem.piece(d_off, streams + 1).piece(d_skip, streams).piece(d_first, streams).piece(d_slot, slot.size());
+    mem.piece(d_text, tot).piece(d_bits, streams).piece(d_sur, tot, surprisal && tot);
+    if (int rc = mem.commit(h)) return rc;
+
+    HIP_TRY(hipMemcpyAsync(e->P, infer_block(h), sizeof(float) * h->pl.total, hipMemcpyDeviceToDevice, h->st));
+    e->packed = false;
+    if (int rc = upload_states(h, h0, c0, H0, C0, stage, streams)) return rc;
+    if (keep) { // a stream without a step never reaches the fold: its final state is its start state
+        HIP_TRY(hipMemcpyAsync(ho, H0, sizeof(float) * n, hipMemcpyDeviceToDevice, h->st));
+        HIP_TRY(hipMemcpyAsync(ho + n, C0, sizeof(float) * n, hipMemcpyDeviceToDevice, h->st));
+    }
+    HIP_TRY(hipMemcpyAsync(d_off, text_off, sizeof(uint64_t) * (streams + 1), hipMemcpyHostToDevice, h->st));
+    if (skip) HIP_TRY(hipMemcpyAsync(d_skip, skip, sizeof(uint64_t) * streams, hipMemcpyHostToDevice, h->st));
+    else HIP_TRY(hipMemsetAsync(d_skip, 0, sizeof(uint64_t) * streams, h->st));
+    HIP_TRY(hipMemcpyAsync(d_first, first.data(), sizeof(int64_t) * streams, hipMemcpyHostToDevice, h->st));
+    if (!slot.empty()) HIP_TRY(hipMemcpyAsync(d_slot, slot.data(), sizeof(int32_t) * slot.size(), hipMemcpyHostToDevice, h->st));
+    if (tot) HIP_TRY(hipMemcpyAsync(d_text, text, tot, hipMemcpyHostToDevice, h->st));
+    HIP_TRY(hipMemsetAsync(d_bits, 0, sizeof(double) * streams, h->st));
+    if (d_sur) HIP_TRY(hipMemsetAsync(d_sur, 0, sizeof(float) * tot, h->st));
+    HIP_TRY(hipStreamSynchronize(h->st)); // (the host vectors are pageable: their copies are done; the loop is on e's stream)
+
+    EvalArgs a{};
+    a.text = d_text;
+    a.off = d_off;
+    a.skip = d_skip;
+    a.slot = d_slot;
+    a.first = d_first;
+    a.H0 = H0;
+    a.C0 = C0;
+    a.xi = e->xi;
+    a.ti = e->ti;
+    a.H = e->H;
+    a.C = e->C;
+    a.colloss = e->colloss;
+    a.bits = d_bits;
+    a.sur = d_sur;
+    a.Hout = h_out ? ho : nullptr;
+    a.Cout = c_out ? ho + n : nullptr;
+    a.lanes = lanes;
+    a.N = N;
+    struct LoopMode { // the internal handle is back in its standalone mode on every return path
+        lstm_hip_ctx *e;
+        ~LoopMode() { e->in_loop = false, e->keep_outputs = true; }
+    } loop_mode{e};
+    e->in_loop = true;
+    e->keep_outputs = false;
+    if (elapsed_ms) HIP_TRY(hipEventRecord(e->evt0, e->st));
+    for (int64_t w = 0; w < windows; w++) {
+        eval_window(a, w, e->plan.n_cus, e->st);
+        if (int rc = eval_status("eval_window")) return rc;
+        if (int rc = do_forward(e)) return rc;
+        eval_fold(a, w, e->plan.n_cus, e->st);
+        if (int rc = eval_status("eval_fold")) return rc;
+    }
+    if (elapsed_ms) {
+        HIP_TRY(hipEventRecord(e->evt1, e->st));
+        HIP_TRY(hipEventSynchronize(e->evt1));
+        HIP_TRY(hipEventElapsedTime(elapsed_ms, e->evt0, e->evt1));
+    }
+    HIP_TRY(hipStreamSynchronize(e->st));
+    if (int rc = check_abort(e)) return rc;
+
+    if (bits) HIP_TRY(hipMemcpyAsync(bits, d_bits, sizeof(double) * streams, hipMemcpyDeviceToHost, h->st));
+    if (d_sur) HIP_TRY(hipMemcpyAsync(surprisal, d_sur, sizeof(float) * tot, hipMemcpyDeviceToHost, h->st));
+    if (int rc = download_states(h, h_out, c_out, ho, ho ? ho + n : nullptr, stage, streams)) return rc;
+    HIP_TRY(hipStreamSynchronize(h->st));
     return 0;
 }
 

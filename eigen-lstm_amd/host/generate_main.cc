@@ -5,11 +5,14 @@
 //   lstm_generate --load PREFIX [--score FILE ...] [--score-bytes FILE [--top N]] [--count C --streams K --prime TEXT|--prime-file F
 //                 --temperature T --top-k K --top-p P --stop-byte B --seed S --utf8 --allow SPEC --ban SPEC --regex PATTERN
 //                 | --beams W --nbest K --length-alpha A [--constrain-search --utf8 --allow SPEC --ban SPEC --regex PATTERN]]
-//                 [--fast-math] [--stable-softmax] [--device D]
+//                 [--score-streams K [--score-warmup W]] [--fast-math] [--stable-softmax] [--device D]
 //
 // --load reads the five-file text checkpoint PREFIX_{W,U,Why,b,by}.txt (checkpoint.h); N is the rows of W / 4.
 // --score runs every FILE as one stream from h = c = 0 and prints "FILE: X.XXXXX bits/char (n bytes)" per file (bits over
 // the n - 1 predicted bytes, as lstm_hip_eval_bits) and a total weighted by those bytes.
+// With --score-streams K (1..4096) every FILE is cut into K streams and all files are scored in one lstm_hip_eval_texts call, on
+// the training window's forward path (eval_split.h): each piece after a file's first starts from a zero state --score-warmup W
+// bytes (default 0) before its first scored byte; every byte but a file's first is still scored once, and the lines are the same.
 // --score-bytes FILE prints one tab-separated row per byte of FILE (lstm_hip_score): its offset, the byte in hex, its surprisal
 // in bits, the entropy of the distribution it was scored under, its rank (0: the model's first guess), then with --top N
 // (1..8) the N most likely bytes at that place, each as hex byte and bits; after the rows the --score line of FILE.  The first
@@ -50,6 +53,7 @@
 // max-shifted softmax (LSTM_HIP_STABLE_SOFTMAX), for checkpoints whose logits pass expf's range.
 #include "../../include/lstm_hip.h"
 #include "checkpoint.h"
+#include "eval_split.h"
 #include "rng.h"
 
 #include <cerrno>
@@ -69,7 +73,9 @@ const char *const kUsage =
     "                     --utf8 --allow SPEC --ban SPEC --regex PATTERN\n"
     "                     | --beams W --nbest K --length-alpha A\n"
     "                       [--constrain-search --utf8 --allow SPEC --ban SPEC --regex PATTERN]]\n"
-    "                     [--fast-math] [--stable-softmax] [--device D]\n"
+    "                     [--score-streams K [--score-warmup W]] [--fast-math] [--stable-softmax] [--device D]\n"
+    "  --score-streams K   with --score: cut every FILE into K streams (1..4096) and score all files in one call on the\n"
+    "                 trainer's forward path; --score-warmup W feeds W bytes before each later piece's first scored byte\n"
     "  --score-bytes FILE  one row per byte: offset, byte, surprisal, entropy, rank; then the --score line of FILE\n"
     "  --top N        with --score-bytes: add the N most likely bytes of every place (1..8) with their bits\n"
     "  --top-k K      draw among the K most likely bytes (1..255; 0 or 256: all)\n"
@@ -158,6 +164,7 @@ struct Options {
     std::vector<std::string> sampling_opts; // options that only mean something with --count
     std::vector<std::string> score;
     std::string score_bytes; // --score-bytes FILE
+    long score_streams = 0, score_warmup = -1; // --score-streams K (0: lstm_hip_generate's prompt bits), --score-warmup W
     long top = -1;           // --top N (-1: not given)
     long count = -1, streams = 1, device = 0;
     double temperature = 1.0, top_p = 1.0;
@@ -190,6 +197,8 @@ Options parse(int argc, char **argv) {
             o.score.push_back(val());
             while (i + 1 < argc && std::string(argv[i + 1]).rfind("--", 0) != 0) o.score.push_back(argv[++i]);
         } else if (a == "--score-bytes") o.score_bytes = val();
+        else if (a == "--score-streams") o.score_streams = parse_int(a, val(), 1, 4096);
+        else if (a == "--score-warmup") o.score_warmup = parse_int(a, val(), 0, 1L << 30);
         else if (a == "--top") o.top = parse_int(a, val(), 1, 8);
         else if (a == "--count") o.count = parse_int(a, val(), 0, 1L << 30);
         else if (a == "--streams") {
@@ -266,6 +275,9 @@ Options parse(int argc, char **argv) {
     if (o.load.empty()) usage("--load PREFIX is required");
     if (o.score.empty() && o.count < 0 && o.score_bytes.empty()) usage("nothing to do: give --score, --score-bytes and/or --count");
     if (o.top >= 0 && o.score_bytes.empty()) usage("--top needs --score-bytes");
+    if (o.score_streams > 0 && o.score.empty()) usage("--score-streams needs --score");
+    if (o.score_warmup >= 0 && o.score_streams == 0) usage("--score-warmup needs --score-streams");
+    if (o.score_streams > 0 && o.score.size() * (size_t)o.score_streams > (size_t)1 << 30) usage("--score-streams x files is too large");
     if (!o.score_bytes.empty()) { // a mode of its own; of the sampling options it takes the constraint's
         if (o.count >= 0 || !o.score.empty()) usage("--score-bytes goes with neither --count nor --score");
         for (const std::string &a : o.sampling_opts)
@@ -353,6 +365,18 @@ int main(int argc, char **argv) {
 
     if (!texts.empty()) { // one stream per file, in chunks of at most 4096 files
         double sum_bits = 0.0, sum_chars = 0.0;
+        if (o.score_streams > 0) { // every file in K pieces, all of them in one call
+            EvalSplit split;
+            for (const std::vector<uint8_t> &t : texts) split.add(t.data(), t.size(), (size_t)o.score_streams, (size_t)std::max(o.score_warmup, 0L));
+            std::vector<double> bits;
+            CK(split.run(h, bits));
+            for (size_t s = 0; s < texts.size(); s++) {
+                const size_t n = texts[s].size();
+                printf("%s: %.5f bits/char (%zu bytes)\n", o.score[s].c_str(), bits[s] / (double)(n - 1), n);
+                sum_bits += bits[s];
+                sum_chars += (double)(n - 1);
+            }
+        } else
         for (size_t f0 = 0; f0 < texts.size(); f0 += 4096) {
             const size_t k = std::min<size_t>(4096, texts.size() - f0);
             std::vector<uint64_t> off(k + 1, 0);

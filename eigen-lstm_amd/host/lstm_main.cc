@@ -8,7 +8,8 @@
 //        [--eval-file F] [--stride K] [--forget-bias V] [--test-percent F] [--test-every SEC] [--log PREFIX]
 //        [--fast-math] [--step-kernels] [--stable-softmax] [--clip-norm X] [--optimizer adagrad|adam]
 //        [--adam-betas B1,B2] [--adam-eps E] [--weight-decay W] [--average ema|uniform] [--average-decay D]
-//        [--average-every K] [--average-start W] [--weight-drop R] [--weight-drop-seed K] [--quiet]
+//        [--average-every K] [--average-start W] [--weight-drop R] [--weight-drop-seed K] [--test-streams K]
+//        [--test-warmup W] [--quiet]
 //
 // stdout follows the reference: "Read N bytes (file)" (R/lstm.cc:398), the carriage-return progress
 // line (OV/lstm_eigen_opt/lstm.cc:320-331), the epoch summary (R/lstm.cc:284-291: GFLOP uses 2^30,
@@ -39,6 +40,10 @@
 // (lstm_hip_set_weight_drop; --weight-drop-seed K, default 0, picks the mask sequence).  Held-out tests, samples and saved
 // parameters are those of the unmasked model.  --save also writes PREFIX_weight_drop.txt (rate, seed, t); --load PREFIX with
 // --weight-drop again resumes the mask index t (and the seed, unless --weight-drop-seed is given).
+// --test-streams K (1..65536) runs the held-out tests through lstm_hip_eval_texts: the held-out text is cut into K streams
+// that are evaluated side by side on the training window's forward path (eval_split.h), each piece after the first starting
+// from a zero state --test-warmup W bytes (default 0) before its first scored byte.  Every byte but the first is still scored
+// exactly once; K = 1 is the one stream of the default path.  Without the option the tests run lstm_hip_eval_bits as before.
 #include "../../include/lstm_hip.h"
 
 // referenced weakly: the program still links against a library without them and refuses --clip-norm / --optimizer adam there
@@ -57,6 +62,9 @@
 // ... and --weight-drop
 #pragma weak lstm_hip_set_weight_drop
 #pragma weak lstm_hip_get_weight_drop
+// ... and --test-streams
+#pragma weak lstm_hip_eval_texts
+#include "eval_split.h"
 #include "checkpoint.h"
 #include "matrix_io.h"
 #include "rng.h"
@@ -109,6 +117,8 @@ struct Options {
     double wd_rate = 0.0;            // --weight-drop: 0 = off
     uint64_t wd_seed = 0;            // --weight-drop-seed
     bool wd_seed_given = false;
+    long test_streams = 0;           // --test-streams: 0 = lstm_hip_eval_bits
+    long test_warmup = -1;           // --test-warmup (-1: not given)
 };
 
 [[noreturn]] void die(const std::string &m) {
@@ -300,6 +310,10 @@ Options parse(int argc, char **argv) {
             o.wd_seed = (uint64_t)k;
             o.wd_seed_given = true;
         }
+        else if (a == "--test-streams") {
+            o.test_streams = whole_number(a, val(), 1);
+            if (o.test_streams > 65536) die("--test-streams must be at most 65536");
+        } else if (a == "--test-warmup") o.test_warmup = whole_number(a, val(), 0);
         else if (a == "--last-step-loss") o.last_step_loss = true;
         else if (a == "--last-step-loss-bits") o.last_step_bits = true;
         else if (a == "--quiet") o.quiet = true;
@@ -309,7 +323,7 @@ Options parse(int argc, char **argv) {
                    "            --test-percent F --test-every SEC --log PREFIX --last-step-loss --last-step-loss-bits --fast-math --step-kernels\n"
                    "            --stable-softmax --clip-norm X --optimizer adagrad|adam --adam-betas B1,B2 --adam-eps E\n"
                    "            --weight-decay W --average ema|uniform --average-decay D --average-every K --average-start W\n"
-                   "            --weight-drop R --weight-drop-seed K --quiet]\n");
+                   "            --weight-drop R --weight-drop-seed K --test-streams K --test-warmup W --quiet]\n");
             exit(0);
         } else if (a.rfind("--", 0) == 0) die("unknown option " + a);
         else pos.push_back(a);
@@ -329,6 +343,8 @@ Options parse(int argc, char **argv) {
         die("--average: the loaded liblstm_hip has no lstm_hip_set_averaging / lstm_hip_get_average / lstm_hip_set_average / "
             "lstm_hip_get_averaging_counts / lstm_hip_set_averaging_counts / lstm_hip_set_inference_source");
     if (o.wd_seed_given && !(o.wd_rate > 0.0)) die("--weight-drop-seed needs --weight-drop R");
+    if (o.test_warmup >= 0 && o.test_streams == 0) die("--test-warmup needs --test-streams K");
+    if (o.test_streams > 0 && lstm_hip_eval_texts == nullptr) die("--test-streams: the loaded liblstm_hip has no lstm_hip_eval_texts");
     if (o.wd_rate > 0.0 && (lstm_hip_set_weight_drop == nullptr || lstm_hip_get_weight_drop == nullptr))
         die("--weight-drop: the loaded liblstm_hip has no lstm_hip_set_weight_drop / lstm_hip_get_weight_drop");
     if (pos.size() > 0) o.data = pos[0];
@@ -464,12 +480,22 @@ int run_rank(const Options &o, int rank, int up, int down) {
     std::vector<std::vector<double>> results;
     double last_test = now();
     SeededRng log_rng(o.seed + 7919u); // sampling for the log must not disturb the training stream
+    EvalSplit split; // --test-streams: the held-out text cut once
+    if (o.test_streams > 0 && evaldata.size() > 1)
+        split.add(evaldata.data(), evaldata.size(), (size_t)o.test_streams, (size_t)std::max(o.test_warmup, 0L));
+    auto heldout = [&](double *bits_per_char) { // bits/char of the held-out text under the current inference source
+        if (o.test_streams == 0) return lstm_hip_eval_bits(h, evaldata.data(), evaldata.size(), bits_per_char);
+        std::vector<double> bits;
+        if (int rc = split.run(h, bits)) return rc;
+        *bits_per_char = bits[0] / (double)(evaldata.size() - 1);
+        return 0;
+    };
     // test(p, testdata) + results row + checkpoint + sample file, OV/lstm_eigen_class_CUDA/lstm.cc:186-236 (lead rank only:
     // the evaluator and the sampler are local to one handle, the other ranks wait at the next all-reduce)
     auto test_and_log = [&](double train_error, double gflops) {
         const double test_time = now() - last_test;
         double test_error = NAN;
-        if (evaldata.size() > 1) CK(lstm_hip_eval_bits(h, evaldata.data(), evaldata.size(), &test_error));
+        if (evaldata.size() > 1) CK(heldout(&test_error));
         printf("\nTrain error: %g, Test error: %g\n", train_error, test_error);
         if (evaldata.size() > 1) printf("Test error: %.5f bits/char (%s)\n", test_error, evalname.c_str());
         if (avg_on && evaldata.size() > 1) { // the same text through the averaged model (the log keeps its columns)
@@ -478,7 +504,7 @@ int run_rank(const Options &o, int rank, int up, int down) {
             if (n >= 1) {
                 double avg_error = NAN;
                 CK(lstm_hip_set_inference_source(h, LSTM_HIP_SRC_AVERAGE));
-                CK(lstm_hip_eval_bits(h, evaldata.data(), evaldata.size(), &avg_error));
+                CK(heldout(&avg_error));
                 CK(lstm_hip_set_inference_source(h, LSTM_HIP_SRC_PARAMS));
                 printf("Test error of the %s average (n = %lld): %.5f bits/char (%s)\n", avg_name(o.avg_kind), (long long)n, avg_error,
                        evalname.c_str());

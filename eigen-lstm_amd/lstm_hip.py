@@ -67,6 +67,10 @@ class _Scores(C.Structure):  # lstm_hip_scores
                 ("bits", C.POINTER(C.c_double)), ("end_state", C.POINTER(C.c_int32))]
 
 
+class _EvalOpt(C.Structure):  # lstm_hip_eval_opt
+    _fields_ = [("size", C.c_uint32), ("lanes", C.c_int32)]
+
+
 class _Config(C.Structure):
     _fields_ = [("N", C.c_int32), ("M", C.c_int32), ("S", C.c_int32), ("B", C.c_int32), ("device", C.c_int32),
                 ("flags", C.c_uint32)]
@@ -93,6 +97,7 @@ SYMBOLS = [
     "lstm_hip_set_averaging_counts", "lstm_hip_set_inference_source",
     "lstm_hip_set_weight_drop", "lstm_hip_get_weight_drop", "lstm_hip_weight_drop_mask",
     "lstm_hip_dfa_regex", "lstm_hip_dfa_intersect", "lstm_hip_generate_accepting",
+    "lstm_hip_eval_plan", "lstm_hip_eval_texts",
 ]
 
 
@@ -116,6 +121,10 @@ def load_library():
     lib.lstm_hip_adaptive_version.argtypes = []
     lib.lstm_hip_adaptive_blocks.restype = C.c_int64
     lib.lstm_hip_adaptive_blocks.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_uint64)]
+    if hasattr(lib, "lstm_hip_eval_plan"):  # (an older library named by LSTM_HIP_LIB lacks it)
+        lib.lstm_hip_eval_plan.restype = C.c_int64
+        lib.lstm_hip_eval_plan.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_int32),
+                                           C.POINTER(C.c_int64)]
     _lib = lib
     return lib
 
@@ -148,6 +157,35 @@ def adaptive_blocks(S, B, text_off):
     if n < 0:
         _chk(n)
     return n
+
+
+EVAL_STEPS = 128  # LSTM_HIP_EVAL_STEPS
+
+
+def eval_plan(lanes, lengths):
+    """lstm_hip_eval_plan: the schedule lstm_hip_eval_texts runs for streams of these byte lengths on `lanes` lanes; needs
+    no device.  Returns (windows, lane_of int32 [streams], first_window int64 [streams]); a stream of fewer than 2 bytes has
+    no step and gets -1, -1."""
+    lengths = [int(v) for v in lengths]
+    off = np.zeros(len(lengths) + 1, np.uint64)
+    off[1:] = np.cumsum(lengths, dtype=np.uint64)
+    lane_of, first = np.zeros(max(len(lengths), 1), np.int32), np.zeros(max(len(lengths), 1), np.int64)
+    n = int(load_library().lstm_hip_eval_plan(int(lanes), len(lengths), _ptr(off, C.c_uint64), _ptr(lane_of, C.c_int32),
+                                              _ptr(first, C.c_int64)))
+    if n < 0:
+        _chk(n)
+    return n, lane_of[:len(lengths)], first[:len(lengths)]
+
+
+def eval_split_pieces(length, pieces, warm=0):
+    """The cut Lstm.eval_split makes of a text of `length` bytes: a list of (start, stop, skip).  Piece i scores the bytes
+    a_i .. a_{i+1} - 1 with a_i = 1 + floor(i (length - 1) / pieces); its stream is text[max(0, a_i - 1 - warm) : a_{i+1}]
+    and skip = a_i - start, so the bytes before a_i are fed as warm-up and every byte 1 .. length - 1 is scored once."""
+    length, pieces, warm = int(length), int(pieces), int(warm)
+    if length < 2 or pieces < 1 or warm < 0:
+        raise LstmHipError(f"eval_split: need >= 2 bytes, >= 1 piece, warm >= 0 (got {length}, {pieces}, {warm})")
+    a = [1 + i * (length - 1) // pieces for i in range(pieces + 1)]
+    return [(max(0, a[i] - 1 - warm), a[i + 1], a[i] - max(0, a[i] - 1 - warm)) for i in range(pieces)]
 
 
 def weight_drop_mask(N, rate, seed=0, t=0):
@@ -504,6 +542,45 @@ class Lstm:
         out = C.c_double()
         _chk(self.lib.lstm_hip_eval_bits(self._h, _ptr(text, C.c_uint8), C.c_size_t(text.size), C.byref(out)))
         return out.value
+
+    def eval_texts(self, texts, h0=None, c0=None, skip=None, lanes=0, surprisal=False, want_time=False):
+        """lstm_hip_eval_texts: held-out bits of `texts` (bytes or uint8 arrays, one stream each) through the training
+        window's forward path, `lanes` streams side by side (0: the handle's B).  Byte j >= 1 of a text is scored on the
+        state after bytes 0..j-1, byte 0 never; bytes below skip[s] (None: no skip) are fed but not scored.  h0, c0:
+        [streams, N] or None for zeros.  Returns a dict: "bits" float64 [streams], each stream's summed surprisal; "h", "c"
+        [streams, N], the state after each text's last FED byte, its last but one (not score()'s state after the last byte:
+        the next piece of a chained text starts with this piece's last byte again); "surprisal", with surprisal=True, one
+        float32 array per text indexed like it (0 for unscored bytes), else None; "ms", with want_time=True, the HIP-event
+        time of the device loop, else None."""
+        parts = _bytes_list(texts)
+        streams = len(parts)
+        data, off = _offsets(parts)
+        total = int(off[-1])
+        hh = None if h0 is None else _f32(h0).reshape(streams, self.N)
+        cc = None if c0 is None else _f32(c0).reshape(streams, self.N)
+        sk = None if skip is None else np.ascontiguousarray(skip, dtype=np.uint64).reshape(streams)
+        sur = np.zeros(max(total, 1), np.float32) if surprisal else None
+        bits = np.zeros(max(streams, 1), np.float64)
+        h, c = np.empty((max(streams, 1), self.N), np.float32), np.empty((max(streams, 1), self.N), np.float32)
+        opt = _EvalOpt(C.sizeof(_EvalOpt), int(lanes))
+        ms = C.c_float(0)
+        _chk(self.lib.lstm_hip_eval_texts(self._h, C.c_int32(streams), _ptr(data, C.c_uint8), _ptr(off, C.c_uint64),
+                                          _ptr(hh) if hh is not None else None, _ptr(cc) if cc is not None else None,
+                                          _ptr(sk, C.c_uint64) if sk is not None else None, C.byref(opt), _ptr(bits, C.c_double),
+                                          _ptr(sur) if sur is not None else None, _ptr(h), _ptr(c),
+                                          C.byref(ms) if want_time else None))
+        return {"bits": bits[:streams], "h": h[:streams], "c": c[:streams],
+                "surprisal": [sur[int(off[s]):int(off[s + 1])] for s in range(streams)] if surprisal else None,
+                "ms": ms.value if want_time else None}
+
+    def eval_split(self, text, pieces, warm=0, lanes=0):
+        """Bits per character of one text, cut into `pieces` streams that are evaluated side by side (eval_split_pieces):
+        piece i > 0 starts from a zero state `warm` bytes before its first scored byte, so the figure is the single
+        stream's only in the limit of a long warm-up (warm >= len(text): exactly the single stream's rule)."""
+        text = _bytes_list([text])[0]
+        cut = eval_split_pieces(text.size, pieces, warm)
+        r = self.eval_texts([text[a:b] for a, b, _ in cut], skip=[k for _, _, k in cut], lanes=lanes)
+        return float(r["bits"].sum()) / (text.size - 1)
 
     def sample(self, h0, c0, u):
         h0, c0 = _f32(h0).copy(), _f32(c0).copy()

@@ -656,6 +656,57 @@ int lstm_hip_score(lstm_hip_t *h, int32_t streams, const uint8_t *text, const ui
                    const lstm_hip_scores *out /* may be NULL: nothing but h_out / c_out is wanted */, float *h_out,
                    float *c_out);
 
+/* ---- held-out bits of many texts at the trainer's forward speed: the training window's forward
+ *      path (recurrence, time-batched Why*H, softmax launch) run forward-only, on a cached internal handle of
+ *      `lanes` columns and LSTM_HIP_EVAL_STEPS steps, in a device loop with no readback.  Stream s is
+ *      text[text_off[s] .. text_off[s+1]) with L bytes, streams >= 1; h0 / c0 / h_out / c_out are N x streams as in
+ *      lstm_hip_generate (NULL = zeros / not wanted).
+ *        rule       a stream has n = max(L - 1, 0) steps; step j (0-based) feeds byte j and scores byte j + 1 on the state
+ *                   after inputs 0..j.  Byte 0 is never scored (as lstm_hip_eval_bits, and first = 0 of lstm_hip_score); the
+ *                   last byte is scored but never fed.  Bytes j + 1 < skip[s] are fed but not scored (warm-up); skip 0 and
+ *                   skip 1 mean the same.  The arithmetic is a training window's: the handle's forward recurrence in fp32,
+ *                   z = Why*h for all steps of a window in one product, the softmax launch's surprisal.
+ *        surprisal  indexed like text, as lstm_hip_score's: entry text_off[s] + i belongs to byte i of stream s and is the
+ *                   float the softmax launch wrote for it, -log2f(p), or the log-sum-exp form under LSTM_HIP_STABLE_SOFTMAX;
+ *                   0.0f for every unscored byte (byte 0, bytes below skip[s]).
+ *        bits       bits[s] adds (double)surprisal over the stream's scored bytes in text order.
+ *        h_out      the state after the stream's last FED byte, byte L - 2 (for L <= 1 the start state).  This is NOT
+ *                   lstm_hip_score's "state after the last byte": the last byte has not been fed.
+ *        chaining   a text evaluated in pieces: the next piece starts with byte L - 1 of this one AGAIN (pieces overlap by
+ *                   one byte) and takes h0 / c0 = this piece's h_out / c_out.
+ *        plan       lstm_hip_eval_plan, host only (no handle, no device), is the schedule the call runs.  Window k of a stream
+ *                   holds its steps 128k .. 128k + 127 in rows 1..128 (both indices -1 past the end); a stream needs
+ *                   ceil(n / 128) windows; one with n = 0 gets no lane (lane_of = first_window = -1).  Streams are placed in
+ *                   index order, each on the lane whose next free window is lowest (lowest lane on ties), in consecutive
+ *                   windows there.  Column 0 of a stream's first window is its h0 / c0 column, column 0 of every later window
+ *                   column 128 of that lane's window before; an idle lane has empty rows.  Returns the number of windows
+ *                   (the largest next free window, >= 0); LSTM_HIP_EINVAL for lanes outside 1..4096, streams < 1, offsets
+ *                   missing, not starting at 0 or decreasing.  lane_of / first_window: [streams], either may be NULL.
+ *      opt NULL or lanes = 0: the handle's B lanes.  The internal handle has the parent's internal width and its
+ *      LSTM_HIP_FAST_MATH, LSTM_HIP_STABLE_SOFTMAX and LSTM_HIP_STEP_KERNELS, is always fp32 (a bf16 handle evaluates from its
+ *      fp32 parameters, like every inference call), is remade when `lanes` changes and freed with the handle.  Per window: one
+ *      launch that builds the window, the forward path (a width on the per-step engine: one launch per step), one launch that
+ *      folds the surprisals.  The block lstm_hip_set_inference_source names is copied in at every call; weight drop is never
+ *      applied.  Nothing else of the handle is read and nothing is written: parameters, gradients, optimizer state and counts,
+ *      window, rings, cursors, carry, averaging and weight-drop state, clip norms and kernel statistics stay as they were.
+ *      elapsed_ms (may be NULL): HIP-event time of the device loop.
+ *      LSTM_HIP_EINVAL (the handle stays usable, nothing is launched): opt->size wrong, lanes outside 0..4096, streams < 1,
+ *      offsets missing, not starting at 0 or decreasing, text NULL with bytes to read. */
+#define LSTM_HIP_EVAL_STEPS 128          /* steps per evaluation window */
+typedef struct lstm_hip_eval_opt {
+    uint32_t size;   /* sizeof(lstm_hip_eval_opt); anything else: LSTM_HIP_EINVAL */
+    int32_t  lanes;  /* streams evaluated side by side; 0: the handle's B; else 1..4096 */
+} lstm_hip_eval_opt;
+int64_t lstm_hip_eval_plan(int32_t lanes, int32_t streams, const uint64_t *text_off, int32_t *lane_of, int64_t *first_window);
+int lstm_hip_eval_texts(lstm_hip_t *h, int32_t streams, const uint8_t *text, const uint64_t *text_off,
+                        const float *h0, const float *c0,        /* N x streams, NULL = zeros */
+                        const uint64_t *skip,                    /* [streams], NULL = none */
+                        const lstm_hip_eval_opt *opt,            /* NULL: lanes = the handle's B */
+                        double *bits,                            /* [streams], may be NULL */
+                        float *surprisal,                        /* [text_off[streams]], may be NULL */
+                        float *h_out, float *c_out,              /* N x streams, may be NULL */
+                        float *elapsed_ms);                      /* may be NULL */
+
 /* ---- arithmetic coding of bytes with the model.  Stream s is text[text_off[s] .. text_off[s+1]),
  *      1 <= streams <= 4096, each coded on its own from h = c = 0 (empty streams allowed: their code is empty).
  *        which bytes   EVERY byte, the first one included: byte j is coded with the distribution of the state after inputs
