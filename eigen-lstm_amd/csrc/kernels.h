@@ -219,6 +219,11 @@ void pack_bf16(const float *src, size_t n, unsigned short *dst, hipStream_t st);
 int softmax_parts(int T);
 void softmax_loss_dy(float *Y, float *P, const float *by, const int32_t *ti, float *colloss, float *dby_part, int col0,
                      int col1, bool stable, hipStream_t st); // stable: LSTM_HIP_STABLE_SOFTMAX (kernels.hip)
+// the variant of the text windows (lstm_hip_train_text_windows): a column with an empty target gets
+// dy = 0 (and colloss = 0) instead of dy = probs, so a row without a target adds nothing to any gradient.  Everything else,
+// the order of every sum included, is softmax_loss_dy's.
+void softmax_loss_dy_text(float *Y, float *P, const float *by, const int32_t *ti, float *colloss, float *dby_part, int col0,
+                          int col1, bool stable, hipStream_t st);
 // window loss as the reference sums it: for each t a float sum over b, / B_global, accumulated in double;
 // when dby != null a second workgroup folds the per-wave partials into dby = rowsum(dY) (R/lstm.cc:227)
 void loss_reduce(const float *colloss, int steps, int B, int B_global, double *out, const float *dby_part, int n_parts,
@@ -532,5 +537,30 @@ struct BlockWindowArgs {
     int S, B, NB4, build;
 };
 void block_window(const BlockWindowArgs &a, int cus, hipStream_t st);
+
+// ---- training on separate texts (lstm_hip_train_text_windows): window w of the plan
+// lstm_hip_text_plan(S - 1, B, ...) on the training handle.  slot[w * B + l] is the stream lane l holds in window w (-1: idle);
+// with L = S - 1 and j0 = L * (w - first[s]), row t of the lane holds step j0 + t - 1 of stream s: input byte j0 + t - 1,
+// target byte j0 + t (row 0: the step before the window's first, as a slid window has it; it is never read).  A row without a
+// step -- before the text's start, past its last step, an idle lane -- is xi = ti = -1.
+// text_window: flat xi / ti and the rings (head = 0) are both written, as block_window writes them; column 0 of H and C of a
+// lane that continues its text (w > first[s]) is column S - 1 of the same lane, of every other lane zero (16-byte accesses;
+// S >= 2, so the column read is never the column written).  One launch of at most `cus` workgroups of 256 threads striding
+// over S x B entries and B x N / 4 float4s.
+// text_fold, behind the softmax launch: one thread per lane adds (double)colloss of the lane's rows that hold a step, in row
+// order, into bits[s]: per stream the additions are sequential in text order, one window after the other.
+struct TextWindowArgs {
+    const uint8_t *text;
+    const uint64_t *off;        // [streams + 1]
+    const int32_t *slot;        // [windows][B]
+    const int64_t *first;       // [streams]
+    int32_t *xi, *ti, *Xr, *Tr, *head;
+    float *H, *C;
+    const float *colloss;       // [S - 1][B]
+    double *bits;               // [streams]
+    int S, B, N;
+};
+void text_window(const TextWindowArgs &a, int64_t w, int cus, hipStream_t st);
+void text_fold(const TextWindowArgs &a, int64_t w, int cus, hipStream_t st);
 
 } // namespace lstmk

@@ -562,11 +562,12 @@ void pack_bf16(const float *src, size_t n, unsigned short *dst, hipStream_t st) 
 //   probs = exp(z - zmax) / sum,  surprisal = log2(sum) + (zmax - z[target]) log2(e); the sum's order is the default's
 // ------------------------------------------------------------------------------------------------
 constexpr int SM_COLS_PER_WAVE = 2;
-template <bool STABLE>
-__global__ __launch_bounds__(256) void k_softmax_loss_dy(float *__restrict__ Y, float *__restrict__ P,
-                                                         const float *__restrict__ by, const int32_t *__restrict__ ti,
-                                                         float *__restrict__ colloss, float *__restrict__ dby_part,
-                                                         int col0, int T) {
+// TEXT (the text windows, lstm_hip_train_text_windows): a column without a target gets dy = 0, not dy = probs
+template <bool STABLE, bool TEXT>
+__device__ __forceinline__ void softmax_loss_dy_body(float *__restrict__ Y, float *__restrict__ P,
+                                                     const float *__restrict__ by, const int32_t *__restrict__ ti,
+                                                     float *__restrict__ colloss, float *__restrict__ dby_part,
+                                                     int col0, int T) {
     const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
     __shared__ float4 part[4][64];
     const int gw = col0 / SM_COLS_PER_WAVE + blockIdx.x * 4 + w; // global wave index: columns 2*gw, 2*gw+1
@@ -619,6 +620,8 @@ __global__ __launch_bounds__(256) void k_softmax_loss_dy(float *__restrict__ Y, 
             else d.w -= 1.0f;
         }
         if (tk < 0 && l == 0) colloss[col] = 0.0f;
+        if constexpr (TEXT)
+            if (tk < 0) d = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         *yp = d;
         dsum.x += d.x;
         dsum.y += d.y;
@@ -639,6 +642,20 @@ __global__ __launch_bounds__(256) void k_softmax_loss_dy(float *__restrict__ Y, 
         reinterpret_cast<float4 *>(dby_part + (size_t)(col0 / (4 * SM_COLS_PER_WAVE) + blockIdx.x) * 256)[l] = s;
     }
 }
+template <bool STABLE>
+__global__ __launch_bounds__(256) void k_softmax_loss_dy(float *__restrict__ Y, float *__restrict__ P,
+                                                         const float *__restrict__ by, const int32_t *__restrict__ ti,
+                                                         float *__restrict__ colloss, float *__restrict__ dby_part,
+                                                         int col0, int T) {
+    softmax_loss_dy_body<STABLE, false>(Y, P, by, ti, colloss, dby_part, col0, T);
+}
+template <bool STABLE>
+__global__ __launch_bounds__(256) void k_softmax_loss_dy_text(float *__restrict__ Y, float *__restrict__ P,
+                                                              const float *__restrict__ by, const int32_t *__restrict__ ti,
+                                                              float *__restrict__ colloss, float *__restrict__ dby_part,
+                                                              int col0, int T) {
+    softmax_loss_dy_body<STABLE, true>(Y, P, by, ti, colloss, dby_part, col0, T);
+}
 // columns [col0, col1) of a T-column problem; col0 must be a multiple of 8.  dby_part needs
 // softmax_parts(T) rows of 256 floats; rows of waves past col1 are written as zeros.
 int softmax_parts(int T) { return (T + 4 * SM_COLS_PER_WAVE - 1) / (4 * SM_COLS_PER_WAVE) + 4; } // one row per workgroup
@@ -650,6 +667,15 @@ void softmax_loss_dy(float *Y, float *P, const float *by, const int32_t *ti, flo
         hipLaunchKernelGGL(k_softmax_loss_dy<true>, dim3(blocks), dim3(256), 0, st, Y, P, by, ti, colloss, dby_part, col0, col1);
     else
         hipLaunchKernelGGL(k_softmax_loss_dy<false>, dim3(blocks), dim3(256), 0, st, Y, P, by, ti, colloss, dby_part, col0, col1);
+}
+void softmax_loss_dy_text(float *Y, float *P, const float *by, const int32_t *ti, float *colloss, float *dby_part, int col0,
+                          int col1, bool stable, hipStream_t st) {
+    const int waves = (col1 - col0 + SM_COLS_PER_WAVE - 1) / SM_COLS_PER_WAVE;
+    const int blocks = (waves + 3) / 4;
+    if (stable)
+        hipLaunchKernelGGL(k_softmax_loss_dy_text<true>, dim3(blocks), dim3(256), 0, st, Y, P, by, ti, colloss, dby_part, col0, col1);
+    else
+        hipLaunchKernelGGL(k_softmax_loss_dy_text<false>, dim3(blocks), dim3(256), 0, st, Y, P, by, ti, colloss, dby_part, col0, col1);
 }
 
 // dby = rowsum(dY) (R/lstm.cc:227): fold the per-wave partials.  1024 threads = 64 float4 row groups
@@ -3040,6 +3066,79 @@ void eval_window(const EvalArgs &a, int64_t w, int cus, hipStream_t st) {
 void eval_fold(const EvalArgs &a, int64_t w, int cus, hipStream_t st) {
     const long long work = a.Hout || a.Cout ? (long long)a.lanes * (a.N / 4) : a.lanes;
     hipLaunchKernelGGL(k_eval_fold, dim3(eval_blocks(work, cus)), dim3(256), 0, st, a, (long long)w);
+}
+
+// ------------------------------------------------------------------------------------------------
+// text_window / text_fold: the two launches lstm_hip_train_text_windows puts around a training window (kernels.h; DESIGN.md
+// section 3.18).  As in eval_window every element is independent: a stream sits on one lane, a lane holds one stream per
+// window.  The carry reads column S - 1 and writes column 0 of the same lane, and S >= 2, so no thread reads what another
+// writes in this launch.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_text_window(TextWindowArgs a, long long w) {
+    const long long tid = (long long)blockIdx.x * 256 + threadIdx.x, nth = (long long)gridDim.x * 256;
+    const int32_t *slot = a.slot + w * a.B;
+    const int L = a.S - 1;
+    for (long long i = tid; i < (long long)a.S * a.B; i += nth) {
+        const int t = (int)(i / a.B), l = (int)(i - (long long)t * a.B);
+        const int s = slot[l];
+        int xv = -1, tv = -1;
+        if (s >= 0) {
+            const uint64_t o = a.off[s], len = a.off[s + 1] - o;
+            const long long j = (w - a.first[s]) * L + t - 1; // the step: feeds byte j, has byte j + 1 as its target
+            if (j >= 0 && (uint64_t)j + 1 < len) {
+                xv = (int)a.text[o + j];
+                tv = (int)a.text[o + j + 1];
+            }
+        }
+        a.xi[i] = xv;
+        a.ti[i] = tv;
+        a.Xr[i] = xv; // the rings with head = 0: ring row = window row
+        a.Tr[i] = tv;
+    }
+    if (tid == 0) *a.head = 0;
+    const int N4 = a.N / 4;
+    float4 *H4 = reinterpret_cast<float4 *>(a.H), *C4 = reinterpret_cast<float4 *>(a.C);
+    const size_t last = (size_t)L * a.B * N4; // column S - 1 of lane 0
+    for (long long i = tid; i < (long long)a.B * N4; i += nth) {
+        const int l = (int)(i / N4);
+        const int s = slot[l];
+        float4 hv = make_float4(0.0f, 0.0f, 0.0f, 0.0f), cv = hv; // a text's start, or an idle lane
+        if (s >= 0 && w > a.first[s]) {
+            hv = H4[last + i];
+            cv = C4[last + i];
+        }
+        H4[i] = hv;
+        C4[i] = cv;
+    }
+}
+__global__ __launch_bounds__(256) void k_text_fold(TextWindowArgs a, long long w) {
+    const long long tid = (long long)blockIdx.x * 256 + threadIdx.x, nth = (long long)gridDim.x * 256;
+    const int32_t *slot = a.slot + w * a.B;
+    const int L = a.S - 1;
+    for (long long l = tid; l < a.B; l += nth) {
+        const int s = slot[l];
+        if (s < 0) continue;
+        const uint64_t n = a.off[s + 1] - a.off[s] - 1, j0 = (uint64_t)(w - a.first[s]) * L; // (a placed stream has n >= 1)
+        const int rows = n - j0 < (uint64_t)L ? (int)(n - j0) : L;
+        const float *__restrict__ col = a.colloss + l;
+        double sum = a.bits[s];
+        for (int r0 = 0; r0 < rows; r0 += 16) { // sixteen independent loads in flight, then their additions in row order
+            float v[16];
+#pragma unroll
+            for (int u = 0; u < 16; u++) v[u] = r0 + u < rows ? col[(size_t)(r0 + u) * a.B] : 0.0f;
+#pragma unroll
+            for (int u = 0; u < 16; u++)
+                if (r0 + u < rows) sum += (double)v[u];
+        }
+        a.bits[s] = sum;
+    }
+}
+void text_window(const TextWindowArgs &a, int64_t w, int cus, hipStream_t st) {
+    const long long work = (long long)a.B * (a.S > a.N / 4 ? a.S : a.N / 4);
+    hipLaunchKernelGGL(k_text_window, dim3(eval_blocks(work, cus)), dim3(256), 0, st, a, (long long)w);
+}
+void text_fold(const TextWindowArgs &a, int64_t w, int cus, hipStream_t st) {
+    hipLaunchKernelGGL(k_text_fold, dim3(eval_blocks(a.B, cus)), dim3(256), 0, st, a, (long long)w);
 }
 
 PadMap pad_map_rows(int blocks, int N, int Np, int cols) {

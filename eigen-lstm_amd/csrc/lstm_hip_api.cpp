@@ -55,7 +55,10 @@ enum KernelId {
     K_ADAM,                    // the update launch on a handle set to LSTM_HIP_OPT_ADAM (K_ADAGRAD's launch with the Adam rule)
     K_CODE_HEAD,               // one step of the range coder (lstm_hip_encode / lstm_hip_decode)
     K_BLOCK_WINDOW,            // adaptive coding: a block's training window, carry and bit fold (one launch per block)
-    K_BEAM_HEAD,               // one step of beam search (lstm_hip_beam_search): logits, selection, reordered states
+    K_TEXT_WINDOW,             // training on separate texts (lstm_hip_train_text_windows): a plan window's indices and carry ...
+    K_TEXT_FOLD,               // ... the fold of its surprisals into the streams' bits ...
+    K_SOFTMAX_TEXT,            // ... and K_SOFTMAX's launch in the form that gives a column without a target dy = 0
+    K_BEAM_HEAD,              // one step of beam search (lstm_hip_beam_search): logits, selection, reordered states
     K_BEAM_BACKTRACK,          // ... and the walk through its tables, once per call
     K_SCORE_HEAD,              // one step of lstm_hip_score: logits, surprisal, entropy, rank and alternatives of every stream
     K_COUNT
@@ -63,8 +66,8 @@ enum KernelId {
 const char *const kKernelNames[K_COUNT] = {
     "pack_U", "fwd_step", "gemm_Y", "softmax_loss_dy", "loss_reduce", "gemm_DHy", "bwd_step", "gemm_dWhy", "gemm_dU",
     "dW_db", "loss_dby", "adagrad", "slide", "allreduce", "fwd_persistent", "bwd_persistent", "gen_head", "side_sums",
-    "gemm_dU_halves", "grad_sumsq", "grad_norm", "adam", "code_head", "block_window", "beam_head", "beam_backtrack",
-    "score_head"};
+    "gemm_dU_halves", "grad_sumsq", "grad_norm", "adam", "code_head", "block_window", "text_window", "text_fold",
+    "softmax_loss_dy_text", "beam_head", "beam_backtrack", "score_head"};
 
 // ---- RCCL, loaded on first use so single-GPU users never touch it --------------------------
 struct UniqueId {
@@ -197,6 +200,16 @@ struct lstm_hip_ctx {
     uint64_t *pos_buf = nullptr; // by an update launch reads the live half and writes the other, then the halves change roles
     int32_t *head_buf = nullptr; // (do_adagrad)
     int32_t global_B = 0;
+    // training on separate texts (lstm_hip_set_train_texts): the texts, their offsets, the tables of the plan
+    // lstm_hip_text_plan(S - 1, B, ...) and the streams' prequential bits, all on the device; tt_streams 0: none set
+    uint8_t *tt_text = nullptr;
+    uint64_t *tt_off = nullptr;   // [streams + 1]
+    int32_t *tt_slot = nullptr;   // [windows][B]
+    int64_t *tt_first = nullptr;  // [streams]
+    double *tt_bits = nullptr;    // [streams]
+    int32_t tt_streams = 0;
+    int64_t tt_windows = 0, tt_next = 0; // the plan's length, the next window to run
+    bool text_window = false;     // the window under way is one of those: do_forward launches the softmax's text form
     lstm_hip_ctx *eval_h = nullptr; // internal B = 1 handle used by lstm_hip_eval_bits
     lstm_hip_ctx *texts_h = nullptr; // internal B = lanes handle used by lstm_hip_eval_texts (remade when lanes changes)
     char *gen_scratch = nullptr;    // lstm_hip_generate's working memory: grows to the largest call, freed with the handle
@@ -410,6 +423,11 @@ int do_forward(lstm_hip_ctx *h) {
     RUN(K_GEMM_Y, gemm(false, false, 256, h->T, N, h->P + h->pl.Why, 256, h->H + (size_t)N * B, N,
                        h->Y + (size_t)256 * B, 256, 1, nullptr, h->st));
     h->pr_stale = h->in_loop && !h->keep_outputs;
+    if (h->text_window) // (lstm_hip_train_text_windows only: a column without a target gets dy = 0)
+        RUN(K_SOFTMAX_TEXT, softmax_loss_dy_text(h->Y + (size_t)256 * B, h->pr_stale ? nullptr : h->Pr + (size_t)256 * B,
+                                                 h->P + h->pl.by, h->ti + B, h->colloss, h->dby_part, 0, h->T,
+                                                 (h->cfg.flags & LSTM_HIP_STABLE_SOFTMAX) != 0, h->st));
+    else
     RUN(K_SOFTMAX, softmax_loss_dy(h->Y + (size_t)256 * B, h->pr_stale ? nullptr : h->Pr + (size_t)256 * B, h->P + h->pl.by,
                                    h->ti + B, h->colloss, h->dby_part, 0, h->T, (h->cfg.flags & LSTM_HIP_STABLE_SOFTMAX) != 0,
                                    h->st));
@@ -924,7 +942,8 @@ int lstm_hip_destroy(lstm_hip_t *h) {
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     if (h->h_losses) (void)hipHostFree(h->h_losses);
-    for (void *p : {(void *)h->d_norms, (void *)h->norm_part, (void *)h->clip_coef, (void *)h->adam_v, (void *)h->avg, (void *)h->Ue})
+    for (void *p : {(void *)h->d_norms, (void *)h->norm_part, (void *)h->clip_coef, (void *)h->adam_v, (void *)h->avg, (void *)h->Ue,
+                    (void *)h->tt_text, (void *)h->tt_off, (void *)h->tt_slot, (void *)h->tt_first, (void *)h->tt_bits})
         if (p) (void)hipFree(p);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -2443,10 +2462,10 @@ int lstm_hip_score(lstm_hip_t *h, int32_t streams, const uint8_t *text, const ui
     return 0;
 }
 
-// Held-out bits of many texts (include/lstm_hip.h).  The schedule first: host only.
-static int64_t eval_plan(int32_t lanes, int32_t streams, const uint64_t *off, int32_t *lane_of, int64_t *first_window,
+// Held-out bits of many texts (include/lstm_hip.h).  The schedule first: host only.  It is the
+// schedule of the text windows too (lstm_hip_text_plan, section 3.18), which have `steps` = S - 1 rows where these have 128.
+static int64_t text_plan(int32_t steps, int32_t lanes, int32_t streams, const uint64_t *off, int32_t *lane_of, int64_t *first_window,
                          std::vector<int32_t> *slot) { // slot (may be null): [windows][lanes], the stream a lane holds, -1 idle
-    std::vector<int64_t> next(lanes, 0);              // every lane's next free window
     std::vector<std::pair<int32_t, int64_t>> placed(streams, {-1, -1});
     // lowest next free window, lowest lane on ties: a heap of (window, lane) pairs
     typedef std::pair<int64_t, int32_t> Free;
@@ -2461,8 +2480,7 @@ static int64_t eval_plan(int32_t lanes, int32_t streams, const uint64_t *off, in
             std::pop_heap(heap.begin(), heap.end(), later);
             Free &f = heap.back();
             placed[s] = {f.second, f.first};
-            f.first += (int64_t)((n + LSTM_HIP_EVAL_STEPS - 1) / LSTM_HIP_EVAL_STEPS);
-            next[f.second] = f.first;
+            f.first += (int64_t)((n + steps - 1) / steps);
             windows = std::max(windows, f.first);
             std::push_heap(heap.begin(), heap.end(), later);
         }
@@ -2474,11 +2492,20 @@ static int64_t eval_plan(int32_t lanes, int32_t streams, const uint64_t *off, in
         for (int32_t s = 0; s < streams; s++) {
             if (placed[s].first < 0) continue;
             const uint64_t n = off[s + 1] - off[s] - 1;
-            const int64_t k = (int64_t)((n + LSTM_HIP_EVAL_STEPS - 1) / LSTM_HIP_EVAL_STEPS);
+            const int64_t k = (int64_t)((n + steps - 1) / steps);
             for (int64_t w = placed[s].second; w < placed[s].second + k; w++) (*slot)[(size_t)w * lanes + placed[s].first] = s;
         }
     }
     return windows;
+}
+// both public plans, under the caller's name in a refusal
+static int64_t checked_plan(const char *what, int32_t steps, int32_t lanes, int32_t streams, const uint64_t *text_off,
+                            int32_t *lane_of, int64_t *first_window, std::vector<int32_t> *slot) {
+    if (steps < 1) return fail(LSTM_HIP_EINVAL, "%s: steps must be >= 1 (got %d)", what, steps);
+    if (lanes < 1 || lanes > 4096) return fail(LSTM_HIP_EINVAL, "%s: lanes must be in [1, 4096] (got %d)", what, lanes);
+    if (streams < 1) return fail(LSTM_HIP_EINVAL, "%s: streams must be >= 1 (got %d)", what, streams);
+    if (int rc = check_offsets(what, "text_off", text_off, streams)) return rc;
+    return text_plan(steps, lanes, streams, text_off, lane_of, first_window, slot);
 }
 static int eval_status(const char *which) { // (not among the window's timed kernels: no statistics row)
     const hipError_t e = hipGetLastError();
@@ -2486,11 +2513,12 @@ static int eval_status(const char *which) { // (not among the window's timed ker
     return 0;
 }
 
+int64_t lstm_hip_text_plan(int32_t steps, int32_t lanes, int32_t streams, const uint64_t *text_off, int32_t *lane_of,
+                           int64_t *first_window) {
+    return checked_plan("text_plan", steps, lanes, streams, text_off, lane_of, first_window, nullptr);
+}
 int64_t lstm_hip_eval_plan(int32_t lanes, int32_t streams, const uint64_t *text_off, int32_t *lane_of, int64_t *first_window) {
-    if (lanes < 1 || lanes > 4096) return fail(LSTM_HIP_EINVAL, "eval_plan: lanes must be in [1, 4096] (got %d)", lanes);
-    if (streams < 1) return fail(LSTM_HIP_EINVAL, "eval_plan: streams must be >= 1 (got %d)", streams);
-    if (int rc = check_offsets("eval_plan", "text_off", text_off, streams)) return rc;
-    return eval_plan(lanes, streams, text_off, lane_of, first_window, nullptr);
+    return checked_plan("eval_plan", LSTM_HIP_EVAL_STEPS, lanes, streams, text_off, lane_of, first_window, nullptr);
 }
 
 // The device loop: per window k_eval_window, the internal handle's unchanged do_forward, k_eval_fold, all on the internal
@@ -2514,7 +2542,7 @@ int lstm_hip_eval_texts(lstm_hip_t *h, int32_t streams, const uint8_t *text, con
 
     std::vector<int32_t> slot;
     std::vector<int64_t> first(streams);
-    const int64_t windows = eval_plan(lanes, streams, text_off, nullptr, first.data(), &slot);
+    const int64_t windows = text_plan(LSTM_HIP_EVAL_STEPS, lanes, streams, text_off, nullptr, first.data(), &slot);
 
     HIP_TRY(hipStreamSynchronize(h->st));
     if (h->texts_h && h->texts_h->cfg.B != lanes) {
@@ -2900,6 +2928,122 @@ int lstm_hip_decode_adaptive(lstm_hip_t *h, const uint8_t *code, const uint64_t 
     if (code_off[streams] > 0 && !code) return fail(LSTM_HIP_EINVAL, "%s: null code with %llu code bytes", what, (unsigned long long)code_off[streams]);
     if (text_off[streams] > 0 && !text) return fail(LSTM_HIP_EINVAL, "%s: null text with %llu bytes to decode", what, (unsigned long long)text_off[streams]);
     return run_adaptive(h, true, text_off, nullptr, text, code, code_off, nullptr, nullptr, learning_rate, nullptr, nullptr, nullptr);
+}
+
+// Training on separate texts (include/lstm_hip.h).  set: the texts, their offsets and the tables of
+// the plan go to the device once and stay with the handle.  train: per window text_window (indices, rings, carry or zero
+// state), the handle's own forward path with the softmax launch in its text form, text_fold (the streams' bits), then the
+// adaptive train pass's sequence -- loss, backward, clip, update, no slide riding in the update launch.
+static int drop_train_texts(lstm_hip_ctx *h) {
+    HIP_TRY(hipStreamSynchronize(h->st));
+    for (void *p : {(void *)h->tt_text, (void *)h->tt_off, (void *)h->tt_slot, (void *)h->tt_first, (void *)h->tt_bits})
+        if (p) HIP_TRY(hipFree(p));
+    h->tt_text = nullptr, h->tt_off = nullptr, h->tt_slot = nullptr, h->tt_first = nullptr, h->tt_bits = nullptr;
+    h->tt_streams = 0;
+    h->tt_windows = h->tt_next = 0;
+    return 0;
+}
+int lstm_hip_set_train_texts(lstm_hip_t *h, int32_t streams, const uint8_t *text, const uint64_t *text_off) {
+    CHECK(h);
+    if (streams == 0 && !text && !text_off) return drop_train_texts(h);
+    std::vector<int32_t> slot;
+    std::vector<int64_t> first(streams > 0 ? streams : 0);
+    const int64_t windows = checked_plan("set_train_texts", h->cfg.S - 1, h->cfg.B, streams, text_off, nullptr, first.data(), &slot);
+    if (windows < 0) return (int)windows;
+    const uint64_t total = text_off[streams];
+    if (total > 0 && !text) return fail(LSTM_HIP_EINVAL, "set_train_texts: null text with %llu bytes to read", (unsigned long long)total);
+    if (int rc = drop_train_texts(h)) return rc;
+    // (at least one element each, so that a set plan always has its five buffers)
+    HIP_TRY(hipMalloc((void **)&h->tt_text, total ? total : 1));
+    HIP_TRY(hipMalloc((void **)&h->tt_off, sizeof(uint64_t) * (streams + 1)));
+    HIP_TRY(hipMalloc((void **)&h->tt_slot, sizeof(int32_t) * (slot.empty() ? 1 : slot.size())));
+    HIP_TRY(hipMalloc((void **)&h->tt_first, sizeof(int64_t) * streams));
+    HIP_TRY(hipMalloc((void **)&h->tt_bits, sizeof(double) * streams));
+    if (total) HIP_TRY(hipMemcpy(h->tt_text, text, total, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->tt_off, text_off, sizeof(uint64_t) * (streams + 1), hipMemcpyHostToDevice));
+    if (!slot.empty()) HIP_TRY(hipMemcpy(h->tt_slot, slot.data(), sizeof(int32_t) * slot.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->tt_first, first.data(), sizeof(int64_t) * streams, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(h->tt_bits, 0, sizeof(double) * streams));
+    h->tt_streams = streams;
+    h->tt_windows = windows;
+    h->tt_next = 0;
+    return 0;
+}
+int lstm_hip_get_train_texts(lstm_hip_t *h, int64_t *windows, int64_t *next) {
+    if (!h) return fail(LSTM_HIP_EINVAL, "null handle");
+    if (h->tt_streams == 0) return fail(LSTM_HIP_ESTATE, "get_train_texts before set_train_texts");
+    if (windows) *windows = h->tt_windows;
+    if (next) *next = h->tt_next;
+    return 0;
+}
+int lstm_hip_get_train_texts_bits(lstm_hip_t *h, double *bits) {
+    CHECK(h);
+    if (h->tt_streams == 0) return fail(LSTM_HIP_ESTATE, "get_train_texts_bits before set_train_texts");
+    if (!bits) return fail(LSTM_HIP_EINVAL, "get_train_texts_bits: null pointer");
+    HIP_TRY(hipMemcpyAsync(bits, h->tt_bits, sizeof(double) * h->tt_streams, hipMemcpyDeviceToHost, h->st));
+    HIP_TRY(hipStreamSynchronize(h->st));
+    return 0;
+}
+int lstm_hip_train_text_windows(lstm_hip_t *h, int64_t count, double learning_rate, double *losses, float *elapsed_ms) {
+    CHECK(h);
+    if (h->tt_streams == 0) return fail(LSTM_HIP_ESTATE, "train_text_windows before set_train_texts");
+    if (count < 0 || count > h->tt_windows - h->tt_next)
+        return fail(LSTM_HIP_EINVAL, "train_text_windows: count %lld outside [0, %lld] (the plan has %lld windows, the next is %lld)",
+                    (long long)count, (long long)(h->tt_windows - h->tt_next), (long long)h->tt_windows, (long long)h->tt_next);
+    if (!std::isfinite(learning_rate) || learning_rate < 0.0)
+        return fail(LSTM_HIP_EINVAL, "train_text_windows: learning_rate must be finite and >= 0 (got %g)", learning_rate);
+    if (h->comm) return fail(LSTM_HIP_ESTATE, "train_text_windows: a handle with a communicator cannot train on separate texts");
+    if (h->loss_mode != LSTM_HIP_LOSS_ALL_STEPS_BITS)
+        return fail(LSTM_HIP_ESTATE, "train_text_windows: the loss mode is %d; the text windows report LSTM_HIP_LOSS_ALL_STEPS_BITS only",
+                    h->loss_mode);
+    if (int rc = ensure_losses(h, count)) return rc;
+    h->norms_n = -1;
+    h->pre_slid = false;
+    const bool clip = h->clip_max > 0.0;
+    if (clip)
+        if (int rc = ensure_norms(h, count)) return rc;
+    const int B = h->cfg.B;
+    TextWindowArgs a{};
+    a.text = h->tt_text, a.off = h->tt_off, a.slot = h->tt_slot, a.first = h->tt_first;
+    a.xi = h->xi, a.ti = h->ti, a.Xr = h->Xr, a.Tr = h->Tr, a.head = h->head;
+    a.H = h->H, a.C = h->C;
+    a.colloss = h->colloss, a.bits = h->tt_bits;
+    a.S = h->cfg.S, a.B = B, a.N = h->cfg.N;
+    if (elapsed_ms) HIP_TRY(hipEventRecord(h->evt0, h->st));
+    h->in_loop = true;
+    LoopGuard guard{h};
+    struct TextMode { // the softmax launch is back in its own form on every return path
+        lstm_hip_ctx *h;
+        ~TextMode() { h->text_window = false; }
+    } text_mode{h};
+    h->text_window = true;
+    for (int64_t i = 0; i < count; i++) {
+        int rc = 0;
+        RUN(K_TEXT_WINDOW, text_window(a, h->tt_next, h->plan.n_cus, h->st));
+        const bool own_loss = loop_window(h, i + 1 == count, h->d_losses + i);
+        if ((rc = do_forward(h))) return rc;
+        RUN(K_TEXT_FOLD, text_fold(a, h->tt_next, h->plan.n_cus, h->st));
+        if (own_loss)
+            RUN(K_LOSS, loss_reduce(loss_src(h), loss_steps(h), B, h->global_B, h->d_losses + i, h->dby_part, h->n_dby_parts,
+                                    h->dP + h->pl.by, h->st, loss_scale(h)));
+        h->dby_done = true;
+        if ((rc = do_backward(h))) return rc;
+        h->carry_slide = false;
+        if ((rc = do_adagrad(h, learning_rate, i))) return rc;
+        h->tt_next++;
+    }
+    if (elapsed_ms) {
+        HIP_TRY(hipEventRecord(h->evt1, h->st));
+        HIP_TRY(hipEventSynchronize(h->evt1));
+        HIP_TRY(hipEventElapsedTime(elapsed_ms, h->evt0, h->evt1));
+    }
+    if (losses && count > 0)
+        HIP_TRY(hipMemcpyAsync(h->h_losses, h->d_losses, sizeof(double) * count, hipMemcpyDeviceToHost, h->st));
+    HIP_TRY(hipStreamSynchronize(h->st));
+    if (losses && count > 0) std::memcpy(losses, h->h_losses, sizeof(double) * count);
+    guard.completed = true;
+    if (clip) h->norms_n = count;
+    return check_abort(h);
 }
 
 int lstm_hip_debug_stamps(lstm_hip_t *h, uint64_t *out, size_t count) {

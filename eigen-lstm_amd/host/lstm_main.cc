@@ -9,7 +9,7 @@
 //        [--fast-math] [--step-kernels] [--stable-softmax] [--clip-norm X] [--optimizer adagrad|adam]
 //        [--adam-betas B1,B2] [--adam-eps E] [--weight-decay W] [--average ema|uniform] [--average-decay D]
 //        [--average-every K] [--average-start W] [--weight-drop R] [--weight-drop-seed K] [--test-streams K]
-//        [--test-warmup W] [--quiet]
+//        [--test-warmup W] [--records] [--record-delim B] [--shuffle-seed K] [--quiet]
 //
 // stdout follows the reference: "Read N bytes (file)" (R/lstm.cc:398), the carriage-return progress
 // line (OV/lstm_eigen_opt/lstm.cc:320-331), the epoch summary (R/lstm.cc:284-291: GFLOP uses 2^30,
@@ -44,6 +44,14 @@
 // that are evaluated side by side on the training window's forward path (eval_split.h), each piece after the first starting
 // from a zero state --test-warmup W bytes (default 0) before its first scored byte.  Every byte but the first is still scored
 // exactly once; K = 1 is the one stream of the default path.  Without the option the tests run lstm_hip_eval_bits as before.
+// --records trains on separate texts, each from its zero state (lstm_hip_train_text_windows): --data is cut after every
+// delimiter byte (--record-delim B, 0..255, default 10); the delimiter stays the last byte of its record, so the model learns
+// where a record ends, which is what lstm_generate --stop-byte reads.  Every epoch trains on all records in a new order
+// (--shuffle-seed K, default 0, seeds the shuffle), placed on the batch lanes by lstm_hip_text_plan; --windows caps the
+// windows of an epoch.  The epoch line's bits/char are prequential: every byte scored under the parameters its window had
+// before its update.  --lr-warmup-windows, --average, --weight-drop, --clip-norm, --save and --load work as without it (the
+// saved cursors are those of the flat text, which --records does not move).  One GPU only; --stride and the last-step losses
+// do not apply.
 #include "../../include/lstm_hip.h"
 
 // referenced weakly: the program still links against a library without them and refuses --clip-norm / --optimizer adam there
@@ -64,6 +72,12 @@
 #pragma weak lstm_hip_get_weight_drop
 // ... and --test-streams
 #pragma weak lstm_hip_eval_texts
+// ... and --records
+#pragma weak lstm_hip_text_plan
+#pragma weak lstm_hip_set_train_texts
+#pragma weak lstm_hip_get_train_texts
+#pragma weak lstm_hip_train_text_windows
+#pragma weak lstm_hip_get_train_texts_bits
 #include "eval_split.h"
 #include "checkpoint.h"
 #include "matrix_io.h"
@@ -119,6 +133,9 @@ struct Options {
     bool wd_seed_given = false;
     long test_streams = 0;           // --test-streams: 0 = lstm_hip_eval_bits
     long test_warmup = -1;           // --test-warmup (-1: not given)
+    bool records = false;            // --records: train on the records of --data, each from its zero state
+    int record_delim = 10;           // --record-delim
+    uint32_t shuffle_seed = 0;       // --shuffle-seed
 };
 
 [[noreturn]] void die(const std::string &m) {
@@ -221,6 +238,7 @@ Options parse(int argc, char **argv) {
     std::string adam_opt; // the last Adam option given (refused without --optimizer adam)
     std::string avg_opt;  // the last averaging option given (refused without --average)
     bool avg_decay_given = false;
+    std::string records_opt; // the last option given that needs --records
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto val = [&]() -> std::string {
@@ -314,6 +332,18 @@ Options parse(int argc, char **argv) {
             o.test_streams = whole_number(a, val(), 1);
             if (o.test_streams > 65536) die("--test-streams must be at most 65536");
         } else if (a == "--test-warmup") o.test_warmup = whole_number(a, val(), 0);
+        else if (a == "--records") o.records = true;
+        else if (a == "--record-delim") {
+            const long b = whole_number(a, val(), 0);
+            if (b > 255) die("--record-delim needs a byte value 0..255");
+            o.record_delim = (int)b;
+            records_opt = a;
+        } else if (a == "--shuffle-seed") {
+            const long k = whole_number(a, val(), 0);
+            if (k > 4294967295L) die("--shuffle-seed is too large");
+            o.shuffle_seed = (uint32_t)k;
+            records_opt = a;
+        }
         else if (a == "--last-step-loss") o.last_step_loss = true;
         else if (a == "--last-step-loss-bits") o.last_step_bits = true;
         else if (a == "--quiet") o.quiet = true;
@@ -323,7 +353,8 @@ Options parse(int argc, char **argv) {
                    "            --test-percent F --test-every SEC --log PREFIX --last-step-loss --last-step-loss-bits --fast-math --step-kernels\n"
                    "            --stable-softmax --clip-norm X --optimizer adagrad|adam --adam-betas B1,B2 --adam-eps E\n"
                    "            --weight-decay W --average ema|uniform --average-decay D --average-every K --average-start W\n"
-                   "            --weight-drop R --weight-drop-seed K --test-streams K --test-warmup W --quiet]\n");
+                   "            --weight-drop R --weight-drop-seed K --test-streams K --test-warmup W\n"
+                   "            --records --record-delim B --shuffle-seed K --quiet]\n");
             exit(0);
         } else if (a.rfind("--", 0) == 0) die("unknown option " + a);
         else pos.push_back(a);
@@ -347,6 +378,14 @@ Options parse(int argc, char **argv) {
     if (o.test_streams > 0 && lstm_hip_eval_texts == nullptr) die("--test-streams: the loaded liblstm_hip has no lstm_hip_eval_texts");
     if (o.wd_rate > 0.0 && (lstm_hip_set_weight_drop == nullptr || lstm_hip_get_weight_drop == nullptr))
         die("--weight-drop: the loaded liblstm_hip has no lstm_hip_set_weight_drop / lstm_hip_get_weight_drop");
+    if (!records_opt.empty() && !o.records) die(records_opt + " needs --records");
+    if (o.records && (lstm_hip_text_plan == nullptr || lstm_hip_set_train_texts == nullptr || lstm_hip_get_train_texts == nullptr ||
+                      lstm_hip_train_text_windows == nullptr || lstm_hip_get_train_texts_bits == nullptr))
+        die("--records: the loaded liblstm_hip has no lstm_hip_text_plan / lstm_hip_set_train_texts / lstm_hip_get_train_texts / "
+            "lstm_hip_train_text_windows / lstm_hip_get_train_texts_bits");
+    if (o.records && o.gpus != 1) die("--records runs on one GPU (every rank would have to run the same number of windows)");
+    if (o.records && o.stride != 1) die("--records does not take --stride (a text window always advances by seq - 1)");
+    if (o.records && (o.last_step_loss || o.last_step_bits)) die("--records reports the all-steps loss only");
     if (pos.size() > 0) o.data = pos[0];
     if (pos.size() > 1) o.N = atoi(pos[1].c_str());
     if (pos.size() > 2) o.S = atoi(pos[2].c_str());
@@ -529,8 +568,37 @@ int run_rank(const Options &o, int rank, int up, int down) {
         }
         last_test = now();
     };
-    const long windows_per_epoch = (o.windows > 0) ? o.windows : (long)((length - S + o.stride - 1) / o.stride);
-    long done_windows = 0;
+    long windows_per_epoch = (o.windows > 0) ? o.windows : (long)((length - S + o.stride - 1) / o.stride);
+    long done_windows = 0, flat_windows = 0; // updates of this run / those of them that moved the flat text's cursors
+    // --records: the training text cut after every delimiter byte; a last record may lack its delimiter
+    std::vector<uint64_t> rec_begin;
+    if (o.records) {
+        if (Bl > 4096) die("--records takes at most 4096 batch lanes");
+        rec_begin.push_back(0);
+        for (size_t i = 0; i + 1 < length; i++)
+            if (data[i] == (uint8_t)o.record_delim) rec_begin.push_back(i + 1);
+        if (rec_begin.size() > 2147483647u) die("--records: too many records");
+        printf("Records: %zu, cut after byte %d\n", rec_begin.size(), o.record_delim);
+    }
+    const size_t n_rec = rec_begin.size();
+    rec_begin.push_back(length);
+    SeededRng shuffle_rng(o.shuffle_seed);
+    std::vector<uint32_t> order(n_rec);
+    for (size_t r = 0; r < n_rec; r++) order[r] = (uint32_t)r;
+    std::vector<uint8_t> rec_text(o.records ? length : 0);
+    std::vector<uint64_t> rec_off(n_rec + 1, 0);
+    std::vector<int64_t> rec_first(n_rec);
+    // scored bytes (steps) in the first w windows of the epoch's plan
+    auto steps_in = [&](long w) {
+        double steps = 0.0;
+        for (size_t r = 0; r < n_rec; r++) {
+            const uint64_t len = rec_off[r + 1] - rec_off[r];
+            if (rec_first[r] < 0 || len < 2) continue;
+            const int64_t room = ((int64_t)w - rec_first[r]) * (S - 1);
+            steps += (double)std::min<int64_t>(std::max<int64_t>(room, 0), (int64_t)len - 1);
+        }
+        return steps;
+    };
     std::vector<float> hs((size_t)N * o.B), cs((size_t)N * o.B);
     std::vector<double> losses, norms;
 
@@ -541,6 +609,21 @@ int run_rank(const Options &o, int rank, int up, int down) {
             rng.randn(hs.data(), N, o.B, 0.0, 0.1);
             rng.randn(cs.data(), N, o.B, 0.0, 0.1);
             CK(lstm_hip_set_state(h, t, hs.data() + (size_t)rank * Bl * N, cs.data() + (size_t)rank * Bl * N));
+        }
+        if (o.records) { // this epoch's order (Fisher-Yates on the shuffle's own generator), its texts and its plan
+            for (size_t i = n_rec; i > 1; i--) std::swap(order[i - 1], order[shuffle_rng.u32() % i]);
+            for (size_t r = 0; r < n_rec; r++) {
+                const uint64_t a = rec_begin[order[r]], b = rec_begin[order[r] + 1];
+                std::copy(data.begin() + a, data.begin() + b, rec_text.begin() + rec_off[r]);
+                rec_off[r + 1] = rec_off[r] + (b - a);
+            }
+            CK(lstm_hip_set_train_texts(h, (int32_t)n_rec, rec_text.data(), rec_off.data()));
+            int64_t plan_windows = 0;
+            CK(lstm_hip_get_train_texts(h, &plan_windows, nullptr));
+            if (plan_windows < 1) die("--records: no record has two bytes");
+            if (lstm_hip_text_plan(S - 1, Bl, (int32_t)n_rec, rec_off.data(), nullptr, rec_first.data()) != plan_windows)
+                die("--records: the plan of lstm_hip_text_plan is not the handle's");
+            windows_per_epoch = o.windows > 0 ? (long)std::min<int64_t>(o.windows, plan_windows) : (long)plan_windows;
         }
         double epoch_loss = 0.0;
         long nan_windows = 0;
@@ -563,7 +646,9 @@ int run_rank(const Options &o, int rank, int up, int down) {
                     chunk = std::min<long>(chunk, o.avg_start - done_windows);
             }
             losses.resize(chunk);
-            CK(lstm_hip_train_windows(h, chunk, lr, losses.data(), nullptr));
+            if (o.records) CK(lstm_hip_train_text_windows(h, chunk, lr, losses.data(), nullptr));
+            else CK(lstm_hip_train_windows(h, chunk, lr, losses.data(), nullptr));
+            if (!o.records) flat_windows += chunk;
             if (o.clip_norm > 0.0) {
                 norms.resize(chunk);
                 CK(lstm_hip_get_grad_norms(h, norms.data(), chunk));
@@ -585,11 +670,12 @@ int run_rank(const Options &o, int rank, int up, int down) {
             // (local surprisal sum / GLOBAL batch); the ranks exchange sums once per epoch, not here, so the running figure is
             // the lead's share scaled by the rank count -- an estimate over its streams, labelled as what the reference prints
             if (lead && o.test_every > 0 && now() - last_test > o.test_every)
-                test_and_log(epoch_loss * (double)o.gpus / ((double)S * (double)i),
+                test_and_log(o.records ? epoch_loss * (double)o.B / std::max(steps_in(i), 1.0)
+                                       : epoch_loss * (double)o.gpus / ((double)S * (double)i),
                              (i * flops_per_iteration / std::pow(2.0, 30)) / (now() - t0));
             if (lead && !o.quiet) {
                 const double t1 = now();
-                printf("%9.2f%% %9.2f GFlOP/s\r", 100.0 * (double)(i + S) / (double)length,
+                printf("%9.2f%% %9.2f GFlOP/s\r", o.records ? 100.0 * (double)i / (double)windows_per_epoch : 100.0 * (double)(i + S) / (double)length,
                        (chunk * flops_per_iteration / std::pow(2.0, 30)) / (t1 - tf));
                 fflush(stdout);
                 tf = t1;
@@ -601,11 +687,18 @@ int run_rank(const Options &o, int rank, int up, int down) {
             if (read(down, &epoch_loss, sizeof(double)) != (ssize_t)sizeof(double)) die("pipe read");
         }
         if (lead) {
-            const double chars = (double)(S - 1) * o.B * windows_per_epoch;
+            const double rows = (double)(S - 1) * o.B * windows_per_epoch;
+            const double chars = o.records ? steps_in(windows_per_epoch) : rows; // (a text window's rows are not all filled)
+            // R/lstm.cc:290: loss/(S*length); --records: the prequential bits of the epoch over its scored bytes
+            const double train_bits = o.records ? epoch_loss * (double)o.B / std::max(chars, 1.0)
+                                                : epoch_loss / ((double)S * (double)(windows_per_epoch + S));
             printf("\n====================================================================================\n");
             printf("Epoch %ld/%ld, t = %.3f s, est GFLOP/s = %.3f, avg loss = %.3f bits/char\n", e + 1, o.epochs, epoch_time,
                    (flops_per_iteration * windows_per_epoch / std::pow(2.0, 30)) / epoch_time,
-                   epoch_loss / ((double)S * (double)(windows_per_epoch + S))); // R/lstm.cc:290: loss/(S*length)
+                   train_bits);
+            if (o.records)
+                printf("records: %zu texts in %ld windows, %.1f%% of the rows filled, %.5f prequential bits/char over %.0f bytes\n", n_rec,
+                       windows_per_epoch, 100.0 * chars / rows, train_bits, chars);
             printf("chars/s through fwd+BPTT = %.1f (%ld windows, %d GPU%s)\n", chars / epoch_time, windows_per_epoch, o.gpus,
                    o.gpus > 1 ? "s" : "");
             if (o.clip_norm > 0.0)
@@ -616,7 +709,7 @@ int run_rank(const Options &o, int rank, int up, int down) {
                        nan_windows, windows_per_epoch,
                        (o.flags & LSTM_HIP_STABLE_SOFTMAX) ? "" : ". --stable-softmax keeps large logits finite.");
             if (evaldata.size() > 1 || !o.log.empty())
-                test_and_log(epoch_loss / ((double)S * (double)(windows_per_epoch + S)),
+                test_and_log(train_bits,
                              (flops_per_iteration * windows_per_epoch / std::pow(2.0, 30)) / epoch_time);
             if (o.sample > 0) { // R/lstm.cc:293-356
                 std::vector<float> h0(N), c0(N);
@@ -675,7 +768,7 @@ int run_rank(const Options &o, int rank, int up, int down) {
                            (unsigned long long)t, o.save.c_str());
                 }
                 std::vector<uint64_t> all(o.B); // every stream has advanced by the same number of bytes
-                const uint64_t span = (uint64_t)(length - S), adv = (uint64_t)done_windows * (uint64_t)o.stride;
+                const uint64_t span = (uint64_t)(length - S), adv = (uint64_t)flat_windows * (uint64_t)o.stride;
                 for (int b = 0; b < o.B; b++) all[b] = (uint64_t)S + ((start_all[b] - S) + adv) % span;
                 std::vector<uint64_t> mine(Bl);
                 CK(lstm_hip_get_cursors(h, mine.data()));

@@ -98,6 +98,8 @@ SYMBOLS = [
     "lstm_hip_set_weight_drop", "lstm_hip_get_weight_drop", "lstm_hip_weight_drop_mask",
     "lstm_hip_dfa_regex", "lstm_hip_dfa_intersect", "lstm_hip_generate_accepting",
     "lstm_hip_eval_plan", "lstm_hip_eval_texts",
+    "lstm_hip_text_plan", "lstm_hip_set_train_texts", "lstm_hip_get_train_texts", "lstm_hip_train_text_windows",
+    "lstm_hip_get_train_texts_bits",
 ]
 
 
@@ -124,6 +126,10 @@ def load_library():
     if hasattr(lib, "lstm_hip_eval_plan"):  # (an older library named by LSTM_HIP_LIB lacks it)
         lib.lstm_hip_eval_plan.restype = C.c_int64
         lib.lstm_hip_eval_plan.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_int32),
+                                           C.POINTER(C.c_int64)]
+    if hasattr(lib, "lstm_hip_text_plan"):
+        lib.lstm_hip_text_plan.restype = C.c_int64
+        lib.lstm_hip_text_plan.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_int32),
                                            C.POINTER(C.c_int64)]
     _lib = lib
     return lib
@@ -172,6 +178,20 @@ def eval_plan(lanes, lengths):
     lane_of, first = np.zeros(max(len(lengths), 1), np.int32), np.zeros(max(len(lengths), 1), np.int64)
     n = int(load_library().lstm_hip_eval_plan(int(lanes), len(lengths), _ptr(off, C.c_uint64), _ptr(lane_of, C.c_int32),
                                               _ptr(first, C.c_int64)))
+    if n < 0:
+        _chk(n)
+    return n, lane_of[:len(lengths)], first[:len(lengths)]
+
+
+def text_plan(steps, lanes, lengths):
+    """lstm_hip_text_plan: eval_plan's rule with `steps` rows per window, the schedule Lstm.train_text_windows runs with
+    steps = S - 1 and lanes = B; needs no device.  Returns (windows, lane_of int32 [streams], first_window int64 [streams])."""
+    lengths = [int(v) for v in lengths]
+    off = np.zeros(len(lengths) + 1, np.uint64)
+    off[1:] = np.cumsum(lengths, dtype=np.uint64)
+    lane_of, first = np.zeros(max(len(lengths), 1), np.int32), np.zeros(max(len(lengths), 1), np.int64)
+    n = int(load_library().lstm_hip_text_plan(int(steps), int(lanes), len(lengths), _ptr(off, C.c_uint64),
+                                              _ptr(lane_of, C.c_int32), _ptr(first, C.c_int64)))
     if n < 0:
         _chk(n)
     return n, lane_of[:len(lengths)], first[:len(lengths)]
@@ -535,6 +555,48 @@ class Lstm:
         if want_time:
             return losses, ms.value
         return losses
+
+    # ---- training on separate texts, each from its zero state (lstm_hip_set_train_texts) -------------
+    def set_train_texts(self, texts):
+        """lstm_hip_set_train_texts: the texts (bytes or uint8 arrays, one stream each) the next train_text_windows calls
+        train on, placed on the B lanes by text_plan(S - 1, B, lengths).  Zeroes the streams' bits and starts at window 0;
+        None or an empty list drops the texts.  Returns the plan's number of windows."""
+        if not texts:
+            _chk(self.lib.lstm_hip_set_train_texts(self._h, C.c_int32(0), None, None))
+            self._train_streams = 0
+            return 0
+        parts = _bytes_list(texts)
+        data, off = _offsets(parts)
+        _chk(self.lib.lstm_hip_set_train_texts(self._h, C.c_int32(len(parts)), _ptr(data, C.c_uint8), _ptr(off, C.c_uint64)))
+        self._train_streams = len(parts)
+        return self.train_texts_progress()[0]
+
+    def train_texts_progress(self):
+        """lstm_hip_get_train_texts: (windows of the plan, the next window to run)."""
+        windows, nxt = C.c_int64(), C.c_int64()
+        _chk(self.lib.lstm_hip_get_train_texts(self._h, C.byref(windows), C.byref(nxt)))
+        return windows.value, nxt.value
+
+    def train_text_windows(self, count, lr, want_losses=True, want_time=False):
+        """lstm_hip_train_text_windows: the next `count` windows of the plan, one update each; every text starts from
+        h = c = 0 and a row without a target adds nothing to the gradient.  Returns the windows' losses (all-steps bits), and
+        the HIP-event time of the loop with want_time."""
+        losses = np.zeros(count, np.float64) if want_losses else None
+        ms = C.c_float(0)
+        _chk(self.lib.lstm_hip_train_text_windows(self._h, C.c_int64(count), C.c_double(lr),
+                                                  _ptr(losses, C.c_double) if want_losses else None,
+                                                  C.byref(ms) if want_time else None))
+        self._steps = count
+        if want_time:
+            return losses, ms.value
+        return losses
+
+    def train_texts_bits(self):
+        """lstm_hip_get_train_texts_bits: float64 [streams], each text's summed surprisal so far, every byte scored under
+        the parameters its window had before its update (prequential bits)."""
+        bits = np.zeros(max(getattr(self, "_train_streams", 0), 1), np.float64)
+        _chk(self.lib.lstm_hip_get_train_texts_bits(self._h, _ptr(bits, C.c_double)))
+        return bits[:getattr(self, "_train_streams", 0)]
 
     # ---- evaluator / sampler -------------------------------------------------------------------
     def eval_bits(self, text):

@@ -707,6 +707,58 @@ int lstm_hip_eval_texts(lstm_hip_t *h, int32_t streams, const uint8_t *text, con
                         float *h_out, float *c_out,              /* N x streams, may be NULL */
                         float *elapsed_ms);                      /* may be NULL */
 
+/* ---- training on separate texts, each from its zero state: the trio set_text / set_cursors /
+ *      train_windows for texts.  Stream s is text[text_off[s] .. text_off[s+1]) with L bytes; a stream has
+ *      n = max(L - 1, 0) steps, step j feeds byte j and has byte j + 1 as its target.
+ *        plan       lstm_hip_text_plan, host only (no handle, no device), is lstm_hip_eval_plan's rule with `steps` (>= 1) rows
+ *                   per window in place of 128: window k of a stream holds its steps k*steps .. k*steps + steps - 1 in rows
+ *                   1..steps; a stream needs ceil(n / steps) windows; one with n = 0 gets no lane (lane_of = first_window =
+ *                   -1).  Streams are placed in index order, each on the lane whose next free window is lowest (lowest lane on
+ *                   ties), in consecutive windows there.  Returns the number of windows; LSTM_HIP_EINVAL for steps < 1 and
+ *                   for everything lstm_hip_eval_plan refuses.  lstm_hip_eval_plan(...) is lstm_hip_text_plan(128, ...).
+ *        set        lstm_hip_set_train_texts uploads the texts, the offsets and the tables of
+ *                   lstm_hip_text_plan(S - 1, B, ...), zeroes the per-stream bits and sets next = 0.  The memory stays with
+ *                   the handle; a second set replaces the first; streams = 0 with both pointers NULL drops it.
+ *                   lstm_hip_get_train_texts returns the plan's length and the next window to run (either may be NULL).
+ *        train      lstm_hip_train_text_windows runs windows next .. next + count - 1 of the plan, one update each; how a
+ *                   plan is cut into calls shows in no result.  Per window:
+ *                     window    one launch for all B lanes.  Row t (1..S-1) of a lane that holds step j of its stream gets
+ *                               xi = byte j, ti = byte j + 1 (row 0 holds the step before row 1's where the text has one, as
+ *                               a slid window does; it is never read); every other row -- past a text's end, an idle lane -- gets xi = -1 and no target
+ *                               (ti = -1).  Column 0 of H and C is zero for a lane that starts a text in this window and for
+ *                               an idle lane; for a lane that continues its text it is column S-1 of the handle's state,
+ *                               read where lstm_hip_train_windows reads its carry (a call in between that rewrites that
+ *                               column changes the result, as it would there).  The ring form of the window and its head are
+ *                               written too, so a later lstm_hip_train_windows or lstm_hip_get_window sees a whole window.
+ *                     forward   the handle's own training forward path on the engine its plan chose, weight drop included
+ *                               when it is on.
+ *                     targets   a column with ti < 0 gets dy = 0 and a surprisal of 0 HERE (in every other call it gets
+ *                               dy = probs, the reference's rule).  For a row past a text's end dy = 0 and the gradients
+ *                               arriving from later rows are 0 by induction from the window's end, so the row adds exactly
+ *                               zero to every gradient, on every backward form.
+ *                     loss      losses[i] (may be NULL) is the LSTM_HIP_LOSS_ALL_STEPS_BITS figure of the window: rows without
+ *                               a target add 0, the sum is still divided by the global batch.  Each stream's surprisals are
+ *                               added in double, in text order, into its entry of the bits block:
+ *                               lstm_hip_get_train_texts_bits returns the [streams] prequential bits, every byte scored
+ *                               under the parameters its window had before its update.
+ *                     update    backward, clip if set, the handle's optimizer step, exactly as the adaptive train pass runs
+ *                               them: Adam's t, the averaging counts and the weight-drop index advance once per window, and
+ *                               with clipping on lstm_hip_get_grad_norms afterwards returns the call's `count` norms.
+ *                   After the call the handle holds the last window (states, gates, probabilities, gradient block), as after
+ *                   lstm_hip_train_windows.  Text, cursors, stride and loss mode are neither read nor written.
+ *                   elapsed_ms (may be NULL): HIP-event time of the device loop.
+ *      Refusals (the handle stays usable, nothing is launched).  LSTM_HIP_ESTATE: no texts set (train, get, bits); a
+ *      communicator on the handle (every rank would have to run the same number of windows); a loss mode other than
+ *      LSTM_HIP_LOSS_ALL_STEPS_BITS.  LSTM_HIP_EINVAL: count < 0 or past the plan's end; learning_rate negative or not
+ *      finite; for set: streams < 1, more than 4096 lanes (B), offsets missing, not starting at 0 or decreasing, text NULL
+ *      with bytes to read. */
+int64_t lstm_hip_text_plan(int32_t steps, int32_t lanes, int32_t streams, const uint64_t *text_off, int32_t *lane_of,
+                           int64_t *first_window);
+int lstm_hip_set_train_texts(lstm_hip_t *h, int32_t streams, const uint8_t *text, const uint64_t *text_off);
+int lstm_hip_get_train_texts(lstm_hip_t *h, int64_t *windows, int64_t *next);   /* plan length, next window to run */
+int lstm_hip_train_text_windows(lstm_hip_t *h, int64_t count, double learning_rate, double *losses, float *elapsed_ms);
+int lstm_hip_get_train_texts_bits(lstm_hip_t *h, double *bits /* [streams] */);
+
 /* ---- arithmetic coding of bytes with the model.  Stream s is text[text_off[s] .. text_off[s+1]),
  *      1 <= streams <= 4096, each coded on its own from h = c = 0 (empty streams allowed: their code is empty).
  *        which bytes   EVERY byte, the first one included: byte j is coded with the distribution of the state after inputs
