@@ -224,6 +224,20 @@ void softmax_loss_dy(float *Y, float *P, const float *by, const int32_t *ti, flo
 // the order of every sum included, is softmax_loss_dy's.
 void softmax_loss_dy_text(float *Y, float *P, const float *by, const int32_t *ti, float *colloss, float *dby_part, int col0,
                           int col1, bool stable, hipStream_t st);
+// the launch with soft targets (lstm_hip_set_soft_targets): probs, colloss, the dby_part rows and the
+// column ranges are softmax_loss_dy's; dy = alpha * (probs - r) + oma_tau * (softmax(z / tau) - softmax(zT / tau)) with
+// r = ome * onehot + eps256 (0 in a column without a target) and zT = Yt + by_t the teacher's logits of the same column.
+// Yt null: no teacher, dy = probs - r (alpha is 1 then).  colkl[col] = KL(q || p_tau) of the column in bits (teacher only).
+struct SoftTargetArgs {
+    const float *Yt;   // the teacher's logit block at the window's first column, [T][256]; null: no teacher
+    const float *by_t; // the teacher's by
+    float *colkl;      // [T]
+    float alpha, oma_tau, inv_tau; // alpha, (1 - alpha) * tau, 1 / tau
+    float ome, eps256;             // 1 - eps, eps / 256
+    bool tempered;                 // tau != 1: p_tau is a second, max-shifted softmax of z / tau
+};
+void softmax_soft(float *Y, float *P, const float *by, const int32_t *ti, float *colloss, float *dby_part, int col0, int col1,
+                  bool stable, const SoftTargetArgs &a, hipStream_t st);
 // window loss as the reference sums it: for each t a float sum over b, / B_global, accumulated in double;
 // when dby != null a second workgroup folds the per-wave partials into dby = rowsum(dY) (R/lstm.cc:227)
 void loss_reduce(const float *colloss, int steps, int B, int B_global, double *out, const float *dby_part, int n_parts,

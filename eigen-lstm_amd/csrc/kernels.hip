@@ -678,6 +678,190 @@ void softmax_loss_dy_text(float *Y, float *P, const float *by, const int32_t *ti
         hipLaunchKernelGGL(k_softmax_loss_dy_text<false>, dim3(blocks), dim3(256), 0, st, Y, P, by, ti, colloss, dby_part, col0, col1);
 }
 
+// ------------------------------------------------------------------------------------------------
+// softmax_soft (lstm_hip_set_soft_targets): the softmax launch with soft targets.  The layout, the
+// column ranges, the dby_part protocol and the null P are softmax_loss_dy_body's; probs and colloss are computed by its
+// expressions in its order, so they are what the plain launch stores.  With k the column's target (k < 0: none):
+//   r  = ome * e_k + eps256 (k >= 0), 0 (k < 0)
+//   TEACHER: zT = teacher's logits + teacher's by;  q = softmax(zT * inv_tau), max-shifted
+//            TEMPERED: pt = softmax(z * inv_tau), max-shifted;  else pt = probs (tau = 1)
+//            dy = alpha * (probs - r) + oma_tau * (pt - q);   colkl = sum_m q_m (log2 q_m - log2 pt_m), log-sum-exp form
+//   else     dy = probs - r
+// Everything of a column stays in registers: one pass over Y, one over the teacher's Y.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float max4(float4 v) { return fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w)); }
+template <bool STABLE, bool TEACHER, bool TEMPERED>
+__global__ __launch_bounds__(256) void k_softmax_soft(float *__restrict__ Y, float *__restrict__ P, const float *__restrict__ by,
+                                                      const int32_t *__restrict__ ti, float *__restrict__ colloss,
+                                                      float *__restrict__ dby_part, int col0, int T, SoftTargetArgs a) {
+    const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
+    __shared__ float4 part[4][64];
+    const int gw = col0 / SM_COLS_PER_WAVE + blockIdx.x * 4 + w; // global wave index: columns 2*gw, 2*gw+1
+    const float4 b4 = reinterpret_cast<const float4 *>(by)[l];
+    float4 bt4 = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (TEACHER) bt4 = reinterpret_cast<const float4 *>(a.by_t)[l];
+    constexpr float LOG2E = 1.44269504088896341f;
+    float4 dsum = {0.f, 0.f, 0.f, 0.f};
+    for (int q = 0; q < SM_COLS_PER_WAVE; q++) {
+        const int col = gw * SM_COLS_PER_WAVE + q;
+        if (col >= T) break;
+        float4 *yp = reinterpret_cast<float4 *>(Y + (size_t)col * 256) + l;
+        const float4 y = *yp;
+        float4 z, e; // z = y + by
+        z.x = y.x + b4.x;
+        z.y = y.y + b4.y;
+        z.z = y.z + b4.z;
+        z.w = y.w + b4.w;
+        float zmax = 0.0f;
+        if constexpr (STABLE) zmax = wave_max(max4(z));
+        if constexpr (STABLE) {
+            e.x = expf(z.x - zmax);
+            e.y = expf(z.y - zmax);
+            e.z = expf(z.z - zmax);
+            e.w = expf(z.w - zmax);
+        } else {
+            e.x = expf(z.x);
+            e.y = expf(z.y);
+            e.z = expf(z.z);
+            e.w = expf(z.w);
+        }
+        const float s = wave_sum((e.x + e.y) + (e.z + e.w));
+        float4 p;
+        p.x = e.x / s;
+        p.y = e.y / s;
+        p.z = e.z / s;
+        p.w = e.w / s;
+        if (P != nullptr) reinterpret_cast<float4 *>(P + (size_t)col * 256)[l] = p; // (null: nobody will read this window's)
+        const int tk = ti[col];
+        // hard term: p - r
+        float4 d = p;
+        if (tk >= 0) {
+            d.x -= a.eps256;
+            d.y -= a.eps256;
+            d.z -= a.eps256;
+            d.w -= a.eps256;
+            if ((tk >> 2) == l) {
+                const int c = tk & 3;
+                if constexpr (STABLE) {
+                    const float zt = c == 0 ? z.x : c == 1 ? z.y : c == 2 ? z.z : z.w;
+                    colloss[col] = lse_surprisal(s, zmax, zt);
+                } else {
+                    const float pt = c == 0 ? p.x : c == 1 ? p.y : c == 2 ? p.z : p.w;
+                    colloss[col] = -log2f(pt);
+                }
+                if (c == 0) d.x -= a.ome;
+                else if (c == 1) d.y -= a.ome;
+                else if (c == 2) d.z -= a.ome;
+                else d.w -= a.ome;
+            }
+        } else if (l == 0)
+            colloss[col] = 0.0f;
+        if constexpr (TEACHER) {
+            const float4 yt = reinterpret_cast<const float4 *>(a.Yt + (size_t)col * 256)[l];
+            float4 u, eq; // u = zT / tau
+            u.x = (yt.x + bt4.x) * a.inv_tau;
+            u.y = (yt.y + bt4.y) * a.inv_tau;
+            u.z = (yt.z + bt4.z) * a.inv_tau;
+            u.w = (yt.w + bt4.w) * a.inv_tau;
+            const float umax = wave_max(max4(u));
+            u.x -= umax; // log q_m = u_m - log sq from here on
+            u.y -= umax;
+            u.z -= umax;
+            u.w -= umax;
+            eq.x = expf(u.x);
+            eq.y = expf(u.y);
+            eq.z = expf(u.z);
+            eq.w = expf(u.w);
+            const float sq = wave_sum((eq.x + eq.y) + (eq.z + eq.w));
+            float4 qv, pt, v; // v_m = log pt_m + log st
+            qv.x = eq.x / sq;
+            qv.y = eq.y / sq;
+            qv.z = eq.z / sq;
+            qv.w = eq.w / sq;
+            float st;
+            if constexpr (TEMPERED) {
+                v.x = z.x * a.inv_tau;
+                v.y = z.y * a.inv_tau;
+                v.z = z.z * a.inv_tau;
+                v.w = z.w * a.inv_tau;
+                const float vmax = wave_max(max4(v));
+                v.x -= vmax;
+                v.y -= vmax;
+                v.z -= vmax;
+                v.w -= vmax;
+                float4 ev;
+                ev.x = expf(v.x);
+                ev.y = expf(v.y);
+                ev.z = expf(v.z);
+                ev.w = expf(v.w);
+                st = wave_sum((ev.x + ev.y) + (ev.z + ev.w));
+                pt.x = ev.x / st;
+                pt.y = ev.y / st;
+                pt.z = ev.z / st;
+                pt.w = ev.w / st;
+            } else {
+                v.x = z.x - zmax; // (zmax = 0 in the unshifted mode: log p_m = z_m - log s)
+                v.y = z.y - zmax;
+                v.z = z.z - zmax;
+                v.w = z.w - zmax;
+                st = s;
+                pt = p;
+            }
+            // kl = sum_m q_m ((log q_m - log pt_m) log2 e), log q_m - log pt_m = (u_m - v_m) + (log st - log sq); 0 where q_m is 0
+            const float lz = log2f(st) - log2f(sq);
+            float4 k;
+            k.x = qv.x > 0.0f ? qv.x * ((u.x - v.x) * LOG2E + lz) : 0.0f;
+            k.y = qv.y > 0.0f ? qv.y * ((u.y - v.y) * LOG2E + lz) : 0.0f;
+            k.z = qv.z > 0.0f ? qv.z * ((u.z - v.z) * LOG2E + lz) : 0.0f;
+            k.w = qv.w > 0.0f ? qv.w * ((u.w - v.w) * LOG2E + lz) : 0.0f;
+            const float kl = wave_sum((k.x + k.y) + (k.z + k.w));
+            if (l == 0) a.colkl[col] = kl;
+            d.x = a.alpha * d.x + a.oma_tau * (pt.x - qv.x);
+            d.y = a.alpha * d.y + a.oma_tau * (pt.y - qv.y);
+            d.z = a.alpha * d.z + a.oma_tau * (pt.z - qv.z);
+            d.w = a.alpha * d.w + a.oma_tau * (pt.w - qv.w);
+        }
+        *yp = d;
+        dsum.x += d.x;
+        dsum.y += d.y;
+        dsum.z += d.z;
+        dsum.w += d.w;
+    }
+    part[w][l] = dsum;
+    __syncthreads();
+    if (w == 0) {
+        float4 s = part[0][l];
+#pragma unroll
+        for (int i = 1; i < 4; i++) {
+            s.x += part[i][l].x;
+            s.y += part[i][l].y;
+            s.z += part[i][l].z;
+            s.w += part[i][l].w;
+        }
+        reinterpret_cast<float4 *>(dby_part + (size_t)(col0 / (4 * SM_COLS_PER_WAVE) + blockIdx.x) * 256)[l] = s;
+    }
+}
+template <bool STABLE>
+static void softmax_soft_launch(float *Y, float *P, const float *by, const int32_t *ti, float *colloss, float *dby_part, int col0,
+                                int col1, const SoftTargetArgs &a, int blocks, hipStream_t st) {
+    if (a.Yt == nullptr)
+        hipLaunchKernelGGL((k_softmax_soft<STABLE, false, false>), dim3(blocks), dim3(256), 0, st, Y, P, by, ti, colloss, dby_part,
+                           col0, col1, a);
+    else if (!a.tempered)
+        hipLaunchKernelGGL((k_softmax_soft<STABLE, true, false>), dim3(blocks), dim3(256), 0, st, Y, P, by, ti, colloss, dby_part,
+                           col0, col1, a);
+    else
+        hipLaunchKernelGGL((k_softmax_soft<STABLE, true, true>), dim3(blocks), dim3(256), 0, st, Y, P, by, ti, colloss, dby_part,
+                           col0, col1, a);
+}
+void softmax_soft(float *Y, float *P, const float *by, const int32_t *ti, float *colloss, float *dby_part, int col0, int col1,
+                  bool stable, const SoftTargetArgs &a, hipStream_t st) {
+    const int waves = (col1 - col0 + SM_COLS_PER_WAVE - 1) / SM_COLS_PER_WAVE;
+    const int blocks = (waves + 3) / 4;
+    if (stable) softmax_soft_launch<true>(Y, P, by, ti, colloss, dby_part, col0, col1, a, blocks, st);
+    else softmax_soft_launch<false>(Y, P, by, ti, colloss, dby_part, col0, col1, a, blocks, st);
+}
+
 // dby = rowsum(dY) (R/lstm.cc:227): fold the per-wave partials.  1024 threads = 64 float4 row groups
 // x 16 phases; phase q sums partials q, q+16, ... in order, then the 16 phase sums are added in order.
 // loss += surprisals.sum() / B per step (OV/lstm_eigen_opt/lstm.cc:249): float sum over the columns

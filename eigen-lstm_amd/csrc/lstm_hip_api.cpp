@@ -61,13 +61,17 @@ enum KernelId {
     K_BEAM_HEAD,              // one step of beam search (lstm_hip_beam_search): logits, selection, reordered states
     K_BEAM_BACKTRACK,          // ... and the walk through its tables, once per call
     K_SCORE_HEAD,              // one step of lstm_hip_score: logits, surprisal, entropy, rank and alternatives of every stream
+    K_COUNT_BASE, // the ids above have their names in kKernelNames, the ids from here on in kKernelNamesMore (kernel_name)
+    K_SOFTMAX_SOFT = K_COUNT_BASE, // K_SOFTMAX's launch with soft targets (lstm_hip_set_soft_targets): label smoothing, a teacher's term
     K_COUNT
 };
-const char *const kKernelNames[K_COUNT] = {
+const char *const kKernelNames[K_COUNT] = { // (K_COUNT_BASE names; the rows behind them stay null)
     "pack_U", "fwd_step", "gemm_Y", "softmax_loss_dy", "loss_reduce", "gemm_DHy", "bwd_step", "gemm_dWhy", "gemm_dU",
     "dW_db", "loss_dby", "adagrad", "slide", "allreduce", "fwd_persistent", "bwd_persistent", "gen_head", "side_sums",
     "gemm_dU_halves", "grad_sumsq", "grad_norm", "adam", "code_head", "block_window", "text_window", "text_fold",
     "softmax_loss_dy_text", "beam_head", "beam_backtrack", "score_head"};
+const char *const kKernelNamesMore[K_COUNT - K_COUNT_BASE] = {"softmax_soft"};
+inline const char *kernel_name(int id) { return id < K_COUNT_BASE ? kKernelNames[id] : kKernelNamesMore[id - K_COUNT_BASE]; }
 
 // ---- RCCL, loaded on first use so single-GPU users never touch it --------------------------
 struct UniqueId {
@@ -210,6 +214,20 @@ struct lstm_hip_ctx {
     int32_t tt_streams = 0;
     int64_t tt_windows = 0, tt_next = 0; // the plan's length, the next window to run
     bool text_window = false;     // the window under way is one of those: do_forward launches the softmax's text form
+    // soft targets (lstm_hip_set_soft_targets): off unless soft_on.  A student borrows its teacher:
+    // before its own forward pass it runs the teacher's recurrence and Why * H product on its own stream (one stream: the
+    // two handles' persistent recurrences are never in flight together) and its softmax launch reads the teacher's Y and by
+    bool soft_on = false;
+    lstm_hip_ctx *teacher = nullptr;
+    lstm_hip_soft_targets soft_opt{};
+    float *colkl = nullptr;       // [T] per-column KL(q || p_tau) in bits (teacher only)
+    double *d_kls = nullptr;      // the per-window KL figures of the last forward / train_windows call
+    int64_t kls_cap = 0, kls_n = -1, kl_idx = 0; // d_kls holds this many / figures of the last call (-1: none) / the window under way
+    hipEvent_t ev_soft[2] = {nullptr, nullptr}; // the teacher's own stream -> the student's, and back
+    // ... and on the teacher's side
+    int lent = 0;                 // students that hold this handle as their teacher (lstm_hip_destroy refuses while > 0)
+    bool teacher_pass = false;    // do_forward stops before the softmax launch: Y keeps the logits
+    bool last_fwd_teacher = false; // the last forward pass was such a pass (lstm_hip_backward says so)
     lstm_hip_ctx *eval_h = nullptr; // internal B = 1 handle used by lstm_hip_eval_bits
     lstm_hip_ctx *texts_h = nullptr; // internal B = lanes handle used by lstm_hip_eval_texts (remade when lanes changes)
     char *gen_scratch = nullptr;    // lstm_hip_generate's working memory: grows to the largest call, freed with the handle
@@ -239,7 +257,7 @@ namespace {
 // window to complete "successfully" on stale buffers.
 int launch_status(int id) {
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(LSTM_HIP_EHIP, "launch of %s failed: %s", kKernelNames[id], hipGetErrorString(e));
+    if (e != hipSuccess) return fail(LSTM_HIP_EHIP, "launch of %s failed: %s", kernel_name(id), hipGetErrorString(e));
     return 0;
 }
 int pad_status() { // the boundary's layout copies (not one of the window's timed kernels)
@@ -338,11 +356,60 @@ int weight_drop_launch(lstm_hip_ctx *h, const float *src, float *dst) {
     return weight_drop_status();
 }
 
+int do_forward(lstm_hip_ctx *h);
+// A student's window, before its own forward pass: the teacher gets the window's inputs and, inside a window loop, slides as
+// the student slid (its own column carry_col becomes its column 0); then its recurrence and its Why * H product run in the
+// forms of its own plan.  The caller has put the teacher on the student's stream (TeacherStream).
+int teacher_forward(lstm_hip_ctx *h) {
+    lstm_hip_ctx *t = h->teacher;
+    const size_t cols = (size_t)h->cfg.S * h->cfg.B, n = (size_t)t->cfg.N * t->cfg.B;
+    HIP_TRY(hipMemcpyAsync(t->xi, h->xi, sizeof(int32_t) * cols, hipMemcpyDeviceToDevice, h->st));
+    if (h->in_loop && h->carry_col > 0) {
+        HIP_TRY(hipMemcpyAsync(t->H, t->H + h->carry_col * n, sizeof(float) * n, hipMemcpyDeviceToDevice, h->st));
+        HIP_TRY(hipMemcpyAsync(t->C, t->C + h->carry_col * n, sizeof(float) * n, hipMemcpyDeviceToDevice, h->st));
+    }
+    t->teacher_pass = true;
+    const int rc = do_forward(t);
+    t->teacher_pass = false;
+    return rc;
+}
+// Puts a borrowed teacher on its student's stream for one call: an event pair each way orders what the caller left on the
+// teacher's own stream before the call, and what the call leaves, before the teacher's next boundary call.  No host wait.
+struct TeacherStream {
+    lstm_hip_ctx *h, *t;
+    hipStream_t own = nullptr;
+    explicit TeacherStream(lstm_hip_ctx *h_) : h(h_), t(h_->soft_on ? h_->teacher : nullptr) {}
+    int begin() {
+        if (!t) return 0;
+        HIP_TRY(hipEventRecord(h->ev_soft[0], t->st));
+        HIP_TRY(hipStreamWaitEvent(h->st, h->ev_soft[0], 0));
+        own = t->st;
+        t->st = h->st;
+        return 0;
+    }
+    ~TeacherStream() {
+        if (!own) return;
+        t->st = own;
+        if (hipEventRecord(h->ev_soft[1], h->st) == hipSuccess) (void)hipStreamWaitEvent(own, h->ev_soft[1], 0);
+        else (void)hipStreamSynchronize(h->st);
+    }
+};
+// before anything of a student's window is launched
+int soft_precheck(lstm_hip_ctx *h, const char *what) {
+    if (!h->soft_on || !h->teacher) return 0;
+    if (h->teacher->wd_rate > 0.0)
+        return fail(LSTM_HIP_ESTATE, "%s: the teacher has weight drop on (lstm_hip_set_weight_drop); a teacher runs its unmasked "
+                                     "parameters", what);
+    return 0;
+}
+
 int do_forward(lstm_hip_ctx *h) {
     const EnginePlan &p = h->plan;
     const int N = h->cfg.N, B = h->cfg.B, S = h->cfg.S, G4 = 4 * N;
     const bool fast = (h->cfg.flags & LSTM_HIP_FAST_MATH) != 0;
     float *W = h->P + h->pl.W, *bias = h->P + h->pl.b;
+    if (h->soft_on && h->teacher) // the teacher's logits of this window first, on this stream
+        if (int rc = teacher_forward(h)) return rc;
     // weight drop: the window's images of U are packed from the masked copy, remade whenever they are
     const float *Usrc = h->wd_rate > 0.0 ? h->Ue : h->P + h->pl.U;
     if (h->wd_rate > 0.0 && !(p.bf16() ? h->packed16 : h->packed))
@@ -422,7 +489,26 @@ int do_forward(lstm_hip_ctx *h) {
     } else
     RUN(K_GEMM_Y, gemm(false, false, 256, h->T, N, h->P + h->pl.Why, 256, h->H + (size_t)N * B, N,
                        h->Y + (size_t)256 * B, 256, 1, nullptr, h->st));
+    h->last_fwd_teacher = h->teacher_pass;
+    if (h->teacher_pass) { // (a borrowed teacher: its student's softmax launch reads the logits; no training forward)
+        h->pr_stale = true;
+        h->fwd_done = false;
+        return 0;
+    }
     h->pr_stale = h->in_loop && !h->keep_outputs;
+    if (h->soft_on) {
+        const lstm_hip_soft_targets &o = h->soft_opt; // the scalars in double, narrowed (include/lstm_hip.h)
+        SoftTargetArgs a{};
+        a.alpha = (float)o.alpha, a.oma_tau = (float)((1.0 - o.alpha) * o.temperature), a.inv_tau = (float)(1.0 / o.temperature);
+        a.ome = (float)(1.0 - o.smoothing), a.eps256 = (float)(o.smoothing / 256.0);
+        a.tempered = o.temperature != 1.0;
+        if (const lstm_hip_ctx *t = h->teacher) a.Yt = t->Y + (size_t)256 * B, a.by_t = t->P + t->pl.by, a.colkl = h->colkl;
+        RUN(K_SOFTMAX_SOFT, softmax_soft(h->Y + (size_t)256 * B, h->pr_stale ? nullptr : h->Pr + (size_t)256 * B, h->P + h->pl.by,
+                                         h->ti + B, h->colloss, h->dby_part, 0, h->T,
+                                         (h->cfg.flags & LSTM_HIP_STABLE_SOFTMAX) != 0, a, h->st));
+        if (h->teacher) // the window's KL figure: every step, in bits, summed as the window loss is
+            RUN(K_LOSS, loss_reduce(h->colkl, S - 1, B, h->global_B, h->d_kls + h->kl_idx, nullptr, 0, nullptr, h->st, 1.0f));
+    } else
     if (h->text_window) // (lstm_hip_train_text_windows only: a column without a target gets dy = 0)
         RUN(K_SOFTMAX_TEXT, softmax_loss_dy_text(h->Y + (size_t)256 * B, h->pr_stale ? nullptr : h->Pr + (size_t)256 * B,
                                                  h->P + h->pl.by, h->ti + B, h->colloss, h->dby_part, 0, h->T,
@@ -438,6 +524,8 @@ int do_forward(lstm_hip_ctx *h) {
 int do_backward(lstm_hip_ctx *h) {
     const EnginePlan &p = h->plan;
     const int N = h->cfg.N, B = h->cfg.B, S = h->cfg.S, G4 = 4 * N, T = h->T;
+    if (!h->fwd_done && h->last_fwd_teacher)
+        return fail(LSTM_HIP_ESTATE, "backward: this handle's last forward pass was a teacher's, not a training forward");
     if (!h->fwd_done) return fail(LSTM_HIP_ESTATE, "backward called before forward");
     float *dY = h->Y + (size_t)256 * B;
     // dby = rowsum(dY) (R/lstm.cc:227): folded with the loss when the loop runs on the device
@@ -931,7 +1019,12 @@ extern "C" {
 
 int lstm_hip_destroy(lstm_hip_t *h) {
     if (!h) return 0;
+    if (h->lent > 0)
+        return fail(LSTM_HIP_ESTATE, "destroy: %d student handle(s) hold this handle as their teacher (lstm_hip_set_soft_targets); "
+                                     "clear or destroy them first", h->lent);
     (void)hipSetDevice(h->cfg.device);
+    if (h->teacher) h->teacher->lent--;
+    h->teacher = nullptr;
     if (h->eval_h) (void)lstm_hip_destroy(h->eval_h);
     if (h->texts_h) (void)lstm_hip_destroy(h->texts_h);
     if (h->st) (void)hipStreamSynchronize(h->st);
@@ -943,8 +1036,11 @@ int lstm_hip_destroy(lstm_hip_t *h) {
         if (p) (void)hipFree(p);
     if (h->h_losses) (void)hipHostFree(h->h_losses);
     for (void *p : {(void *)h->d_norms, (void *)h->norm_part, (void *)h->clip_coef, (void *)h->adam_v, (void *)h->avg, (void *)h->Ue,
-                    (void *)h->tt_text, (void *)h->tt_off, (void *)h->tt_slot, (void *)h->tt_first, (void *)h->tt_bits})
+                    (void *)h->tt_text, (void *)h->tt_off, (void *)h->tt_slot, (void *)h->tt_first, (void *)h->tt_bits,
+                    (void *)h->colkl, (void *)h->d_kls})
         if (p) (void)hipFree(p);
+    for (hipEvent_t e : h->ev_soft)
+        if (e) (void)hipEventDestroy(e);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->evt0) (void)hipEventDestroy(h->evt0);
@@ -1148,7 +1244,14 @@ int lstm_hip_slide_state(lstm_hip_t *h) {
 
 int lstm_hip_forward(lstm_hip_t *h) {
     CHECK(h);
-    return do_forward(h);
+    if (int rc = soft_precheck(h, "forward")) return rc;
+    TeacherStream ts{h};
+    if (int rc = ts.begin()) return rc;
+    h->kl_idx = 0;
+    h->kls_n = -1;
+    if (int rc = do_forward(h)) return rc;
+    if (h->soft_on && h->teacher) h->kls_n = 1;
+    return 0;
 }
 int lstm_hip_loss(lstm_hip_t *h, double *loss_bits) {
     CHECK(h);
@@ -1157,6 +1260,8 @@ int lstm_hip_loss(lstm_hip_t *h, double *loss_bits) {
     RUN(K_LOSS, loss_reduce(loss_src(h), loss_steps(h), h->cfg.B, h->global_B, h->d_loss, nullptr, 0, nullptr, h->st, loss_scale(h)));
     HIP_TRY(hipMemcpyAsync(loss_bits, h->d_loss, sizeof(double), hipMemcpyDeviceToHost, h->st));
     HIP_TRY(hipStreamSynchronize(h->st));
+    if (h->soft_on && h->teacher)
+        if (int rc = check_abort(h->teacher)) return rc;
     return check_abort(h);
 }
 int lstm_hip_backward(lstm_hip_t *h) {
@@ -1353,6 +1458,71 @@ int lstm_hip_weight_drop_mask(int32_t N, double rate, uint64_t seed, uint64_t t,
     return 0;
 }
 
+// soft targets (include/lstm_hip.h).  Everything is checked before anything changes; a successful call
+// drops the forward pass, as lstm_hip_set_weight_drop does.
+static int ensure_kls(lstm_hip_ctx *h, int64_t count);
+int lstm_hip_set_soft_targets(lstm_hip_t *h, lstm_hip_t *teacher, const lstm_hip_soft_targets *opt) {
+    CHECK(h);
+    const char *what = "set_soft_targets";
+    if (!opt && teacher) return fail(LSTM_HIP_EINVAL, "%s: a teacher needs options (opt is NULL)", what);
+    lstm_hip_soft_targets o{(uint32_t)sizeof(lstm_hip_soft_targets), 1.0, 1.0, 0.0};
+    if (opt) {
+        if (opt->size != sizeof(lstm_hip_soft_targets))
+            return fail(LSTM_HIP_EINVAL, "%s: opt->size is %u, not sizeof(lstm_hip_soft_targets) = %zu", what, opt->size,
+                        sizeof(lstm_hip_soft_targets));
+        o = *opt;
+    }
+    if (!(o.alpha >= 0.0 && o.alpha <= 1.0)) return fail(LSTM_HIP_EINVAL, "%s: alpha must lie in [0, 1] (got %g)", what, o.alpha);
+    if (!(o.temperature > 0.0) || !std::isfinite(o.temperature))
+        return fail(LSTM_HIP_EINVAL, "%s: temperature must be finite and > 0 (got %g)", what, o.temperature);
+    if (!(o.smoothing >= 0.0 && o.smoothing < 1.0))
+        return fail(LSTM_HIP_EINVAL, "%s: smoothing must lie in [0, 1) (got %g)", what, o.smoothing);
+    if (!teacher && (o.alpha != 1.0 || o.temperature != 1.0))
+        return fail(LSTM_HIP_EINVAL, "%s: without a teacher alpha and temperature must be 1 (got %g, %g)", what, o.alpha, o.temperature);
+    if (teacher) {
+        if (teacher == h) return fail(LSTM_HIP_EINVAL, "%s: a handle cannot be its own teacher", what);
+        if (teacher->teacher) return fail(LSTM_HIP_EINVAL, "%s: the teacher has a teacher of its own", what);
+        if (h->lent > 0) return fail(LSTM_HIP_EINVAL, "%s: this handle is itself held as a teacher", what);
+        if (teacher->cfg.S != h->cfg.S || teacher->cfg.B != h->cfg.B || teacher->cfg.device != h->cfg.device)
+            return fail(LSTM_HIP_EINVAL, "%s: the teacher's (S, B, device) = (%d, %d, %d) differ from the student's (%d, %d, %d)", what,
+                        teacher->cfg.S, teacher->cfg.B, teacher->cfg.device, h->cfg.S, h->cfg.B, h->cfg.device);
+    }
+    const bool on = teacher || o.smoothing != 0.0;
+    if (on && h->comm)
+        return fail(LSTM_HIP_ESTATE, "%s: this handle has a communicator; soft targets run on one device", what);
+    if (teacher) { // the teacher's memory, before anything changes
+        if (!h->colkl) HIP_TRY(hipMalloc((void **)&h->colkl, sizeof(float) * h->T));
+        if (int rc = ensure_kls(h, 1)) return rc;
+        for (hipEvent_t &e : h->ev_soft)
+            if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+    if (h->teacher) h->teacher->lent--;
+    h->teacher = teacher;
+    if (teacher) teacher->lent++;
+    h->soft_on = on;
+    h->soft_opt = o;
+    h->kls_n = -1;
+    h->fwd_done = false;
+    return 0;
+}
+int lstm_hip_get_soft_targets(lstm_hip_t *h, lstm_hip_t **teacher, lstm_hip_soft_targets *opt) {
+    if (!h || !teacher || !opt) return fail(LSTM_HIP_EINVAL, "get_soft_targets: null argument");
+    *teacher = h->teacher;
+    *opt = lstm_hip_soft_targets{(uint32_t)sizeof(lstm_hip_soft_targets), 1.0, 1.0, 0.0};
+    if (h->soft_on) *opt = h->soft_opt;
+    return 0;
+}
+int lstm_hip_get_teacher_kl(lstm_hip_t *h, double *kl_bits, int64_t n) {
+    CHECK(h);
+    if (!h->teacher) return fail(LSTM_HIP_ESTATE, "get_teacher_kl: this handle has no teacher (lstm_hip_set_soft_targets)");
+    if (h->kls_n < 0) return fail(LSTM_HIP_ESTATE, "get_teacher_kl: no forward / train_windows call since the teacher was set");
+    if (n < 0 || n > h->kls_n || (n > 0 && !kl_bits))
+        return fail(LSTM_HIP_EINVAL, "get_teacher_kl: n = %lld outside [0, %lld] or null pointer", (long long)n, (long long)h->kls_n);
+    if (n > 0) HIP_TRY(hipMemcpyAsync(kl_bits, h->d_kls, sizeof(double) * n, hipMemcpyDeviceToHost, h->st));
+    HIP_TRY(hipStreamSynchronize(h->st));
+    return 0;
+}
+
 int lstm_hip_comm_unique_id(uint8_t id[LSTM_HIP_UNIQUE_ID_BYTES]) {
     int rc = rccl_load();
     if (rc) return rc;
@@ -1365,6 +1535,7 @@ int lstm_hip_comm_unique_id(uint8_t id[LSTM_HIP_UNIQUE_ID_BYTES]) {
 int lstm_hip_comm_init(lstm_hip_t *h, const uint8_t id[LSTM_HIP_UNIQUE_ID_BYTES], int32_t nranks, int32_t rank) {
     CHECK(h);
     if (nranks < 1 || rank < 0 || rank >= nranks) return fail(LSTM_HIP_EINVAL, "comm_init: rank %d of %d", rank, nranks);
+    if (h->soft_on) return fail(LSTM_HIP_ESTATE, "comm_init: soft targets are on (lstm_hip_set_soft_targets); they run on one device");
     int rc = rccl_load();
     if (rc) return rc;
     UniqueId u;
@@ -1436,6 +1607,17 @@ int lstm_hip_set_loss_mode(lstm_hip_t *h, int32_t mode) {
 }
 
 // the window loops (lstm_hip_train_windows, the adaptive coder): room for `count` per-window losses
+static int ensure_kls(lstm_hip_ctx *h, int64_t count) { // (as ensure_norms)
+    if (count <= h->kls_cap) return 0;
+    const int64_t cap = count < 8192 ? 8192 : count;
+    HIP_TRY(hipStreamSynchronize(h->st));
+    if (h->d_kls) HIP_TRY(hipFree(h->d_kls));
+    h->d_kls = nullptr;
+    h->kls_cap = 0;
+    HIP_TRY(hipMalloc((void **)&h->d_kls, sizeof(double) * cap));
+    h->kls_cap = cap;
+    return 0;
+}
 static int ensure_losses(lstm_hip_ctx *h, int64_t count) {
     if (count <= h->losses_cap) return 0;
     const int64_t cap = count < 8192 ? 8192 : count;
@@ -1486,7 +1668,18 @@ int lstm_hip_train_windows(lstm_hip_t *h, int64_t count, double learning_rate, d
     CHECK(h);
     if (count < 0) return fail(LSTM_HIP_EINVAL, "train_windows: count < 0");
     if (!h->text) return fail(LSTM_HIP_ESTATE, "train_windows before set_text/set_cursors");
+    if (int rc = soft_precheck(h, "train_windows")) return rc;
     if (int rc = ensure_losses(h, count)) return rc;
+    const bool distil = h->soft_on && h->teacher;
+    h->kls_n = -1;
+    if (distil)
+        if (int rc = ensure_kls(h, count)) return rc;
+    TeacherStream ts{h};
+    if (int rc = ts.begin()) return rc;
+    struct KlIndex { // the single-window calls fold their figure into slot 0
+        lstm_hip_ctx *h;
+        ~KlIndex() { h->kl_idx = 0; }
+    } kl_index{h};
     h->norms_n = -1;
     const bool clip = h->clip_max > 0.0;
     if (clip)
@@ -1504,6 +1697,7 @@ int lstm_hip_train_windows(lstm_hip_t *h, int64_t count, double learning_rate, d
         h->pre_slid = false;
         int rc = 0;
         const bool own_loss = loop_window(h, i + 1 == count, h->d_losses + i);
+        h->kl_idx = i;
         if ((rc = do_forward(h))) return rc;
         if (own_loss)
             RUN(K_LOSS, loss_reduce(loss_src(h), loss_steps(h), h->cfg.B, h->global_B, h->d_losses + i, h->dby_part,
@@ -1527,6 +1721,10 @@ int lstm_hip_train_windows(lstm_hip_t *h, int64_t count, double learning_rate, d
     if (losses && count > 0) std::memcpy(losses, h->h_losses, sizeof(double) * count);
     guard.completed = true;
     if (clip) h->norms_n = count;
+    if (distil) {
+        h->kls_n = count;
+        if (int rc = check_abort(h->teacher)) return rc; // (still on this stream, which has just been drained)
+    }
     return check_abort(h);
 }
 
@@ -2887,6 +3085,8 @@ static int adaptive_checks(lstm_hip_t *h, const char *what, double lr) {
     if (h->comm) return fail(LSTM_HIP_ESTATE, "%s: a handle with a communicator cannot code adaptively", what);
     if (h->infer_src == LSTM_HIP_SRC_AVERAGE) // (it codes with the model it trains: the setting cannot be honoured)
         return fail(LSTM_HIP_ESTATE, "%s: the inference source is LSTM_HIP_SRC_AVERAGE; adaptive coding reads the parameters it trains", what);
+    if (h->soft_on) // (the decoder would need the teacher and the settings: the containers record neither)
+        return fail(LSTM_HIP_ESTATE, "%s: soft targets are on (lstm_hip_set_soft_targets); the adaptive coders train on hard targets", what);
     if (h->wd_rate > 0.0) // (the containers record no mask: DESIGN.md section 3.15)
         return fail(LSTM_HIP_ESTATE, "%s: weight drop is on (lstm_hip_set_weight_drop); the adaptive coders train without it", what);
     if (!std::isfinite(lr) || lr < 0.0) return fail(LSTM_HIP_EINVAL, "%s: learning_rate must be finite and >= 0 (got %g)", what, lr);
@@ -2993,6 +3193,8 @@ int lstm_hip_train_text_windows(lstm_hip_t *h, int64_t count, double learning_ra
     if (!std::isfinite(learning_rate) || learning_rate < 0.0)
         return fail(LSTM_HIP_EINVAL, "train_text_windows: learning_rate must be finite and >= 0 (got %g)", learning_rate);
     if (h->comm) return fail(LSTM_HIP_ESTATE, "train_text_windows: a handle with a communicator cannot train on separate texts");
+    if (h->soft_on)
+        return fail(LSTM_HIP_ESTATE, "train_text_windows: soft targets are on (lstm_hip_set_soft_targets); the text windows train on hard targets");
     if (h->loss_mode != LSTM_HIP_LOSS_ALL_STEPS_BITS)
         return fail(LSTM_HIP_ESTATE, "train_text_windows: the loss mode is %d; the text windows report LSTM_HIP_LOSS_ALL_STEPS_BITS only",
                     h->loss_mode);
@@ -3076,7 +3278,7 @@ int lstm_hip_kernel_stat(lstm_hip_t *h, int32_t idx, const char **name, int64_t 
         if (total_ms) *total_ms = 0.0;
         return 0;
     }
-    if (name) *name = kKernelNames[idx];
+    if (name) *name = kernel_name(idx);
     if (launches) *launches = h->launches[idx];
     if (total_ms) *total_ms = h->total_ms[idx];
     return 0;

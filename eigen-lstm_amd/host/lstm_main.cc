@@ -9,7 +9,8 @@
 //        [--fast-math] [--step-kernels] [--stable-softmax] [--clip-norm X] [--optimizer adagrad|adam]
 //        [--adam-betas B1,B2] [--adam-eps E] [--weight-decay W] [--average ema|uniform] [--average-decay D]
 //        [--average-every K] [--average-start W] [--weight-drop R] [--weight-drop-seed K] [--test-streams K]
-//        [--test-warmup W] [--records] [--record-delim B] [--shuffle-seed K] [--quiet]
+//        [--test-warmup W] [--records] [--record-delim B] [--shuffle-seed K] [--label-smoothing E] [--teacher PREFIX]
+//        [--distill-alpha A] [--distill-temperature T] [--teacher-bf16] [--quiet]
 //
 // stdout follows the reference: "Read N bytes (file)" (R/lstm.cc:398), the carriage-return progress
 // line (OV/lstm_eigen_opt/lstm.cc:320-331), the epoch summary (R/lstm.cc:284-291: GFLOP uses 2^30,
@@ -54,6 +55,12 @@
 // do not apply.
 #include "../../include/lstm_hip.h"
 
+// --label-smoothing E (0 <= E < 1) trains toward (1 - E) onehot + E / 256; --teacher PREFIX distils from the checkpoint
+// PREFIX_{W,U,b,Why,by}.txt (lstm_hip_set_soft_targets): the teacher's hidden size is read from the checkpoint, its handle is
+// padded like the student's and takes the student's fast-math setting, --teacher-bf16 runs it on the bf16 recurrence (hidden
+// sizes up to 1024); --distill-alpha A (default 0.5) weighs the hard-target term, --distill-temperature T (default 1) is the
+// temperature of the teacher's term.  Reported losses stay hard-target bits; with a teacher the epoch line, the test line and
+// the rows of --log carry the mean teacher KL in bits/char as one more field.  One GPU only, not with --records.
 // referenced weakly: the program still links against a library without them and refuses --clip-norm / --optimizer adam there
 #pragma weak lstm_hip_set_grad_clip
 #pragma weak lstm_hip_get_grad_norms
@@ -72,6 +79,9 @@
 #pragma weak lstm_hip_get_weight_drop
 // ... and --test-streams
 #pragma weak lstm_hip_eval_texts
+// ... and --label-smoothing / --teacher
+#pragma weak lstm_hip_set_soft_targets
+#pragma weak lstm_hip_get_teacher_kl
 // ... and --records
 #pragma weak lstm_hip_text_plan
 #pragma weak lstm_hip_set_train_texts
@@ -136,6 +146,11 @@ struct Options {
     bool records = false;            // --records: train on the records of --data, each from its zero state
     int record_delim = 10;           // --record-delim
     uint32_t shuffle_seed = 0;       // --shuffle-seed
+    double smoothing = 0.0;          // --label-smoothing
+    std::string teacher;             // --teacher: checkpoint prefix (empty: none)
+    double distill_alpha = 0.5;      // --distill-alpha
+    double distill_tau = 1.0;        // --distill-temperature
+    bool teacher_bf16 = false;       // --teacher-bf16
 };
 
 [[noreturn]] void die(const std::string &m) {
@@ -239,6 +254,7 @@ Options parse(int argc, char **argv) {
     std::string avg_opt;  // the last averaging option given (refused without --average)
     bool avg_decay_given = false;
     std::string records_opt; // the last option given that needs --records
+    std::string teacher_opt; // the last option given that needs --teacher
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto val = [&]() -> std::string {
@@ -344,6 +360,27 @@ Options parse(int argc, char **argv) {
             o.shuffle_seed = (uint32_t)k;
             records_opt = a;
         }
+        else if (a == "--label-smoothing") {
+            const std::string v = val();
+            o.smoothing = atof(v.c_str());
+            if (!(o.smoothing >= 0.0 && o.smoothing < 1.0)) die("--label-smoothing needs 0 <= E < 1, got " + v);
+        } else if (a == "--teacher") {
+            o.teacher = val();
+            if (o.teacher.empty()) die("--teacher needs a checkpoint prefix");
+        } else if (a == "--distill-alpha") {
+            const std::string v = val();
+            o.distill_alpha = atof(v.c_str());
+            if (!(o.distill_alpha >= 0.0 && o.distill_alpha <= 1.0)) die("--distill-alpha needs 0 <= A <= 1, got " + v);
+            teacher_opt = a;
+        } else if (a == "--distill-temperature") {
+            const std::string v = val();
+            o.distill_tau = atof(v.c_str());
+            if (!(o.distill_tau > 0.0) || !std::isfinite(o.distill_tau)) die("--distill-temperature needs a finite T > 0, got " + v);
+            teacher_opt = a;
+        } else if (a == "--teacher-bf16") {
+            o.teacher_bf16 = true;
+            teacher_opt = a;
+        }
         else if (a == "--last-step-loss") o.last_step_loss = true;
         else if (a == "--last-step-loss-bits") o.last_step_bits = true;
         else if (a == "--quiet") o.quiet = true;
@@ -354,7 +391,8 @@ Options parse(int argc, char **argv) {
                    "            --stable-softmax --clip-norm X --optimizer adagrad|adam --adam-betas B1,B2 --adam-eps E\n"
                    "            --weight-decay W --average ema|uniform --average-decay D --average-every K --average-start W\n"
                    "            --weight-drop R --weight-drop-seed K --test-streams K --test-warmup W\n"
-                   "            --records --record-delim B --shuffle-seed K --quiet]\n");
+                   "            --records --record-delim B --shuffle-seed K --label-smoothing E --teacher PREFIX\n"
+                   "            --distill-alpha A --distill-temperature T --teacher-bf16 --quiet]\n");
             exit(0);
         } else if (a.rfind("--", 0) == 0) die("unknown option " + a);
         else pos.push_back(a);
@@ -379,6 +417,13 @@ Options parse(int argc, char **argv) {
     if (o.wd_rate > 0.0 && (lstm_hip_set_weight_drop == nullptr || lstm_hip_get_weight_drop == nullptr))
         die("--weight-drop: the loaded liblstm_hip has no lstm_hip_set_weight_drop / lstm_hip_get_weight_drop");
     if (!records_opt.empty() && !o.records) die(records_opt + " needs --records");
+    if (!teacher_opt.empty() && o.teacher.empty()) die(teacher_opt + " needs --teacher PREFIX");
+    if ((o.smoothing > 0.0 || !o.teacher.empty()) && (lstm_hip_set_soft_targets == nullptr || lstm_hip_get_teacher_kl == nullptr))
+        die("--label-smoothing / --teacher: the loaded liblstm_hip has no lstm_hip_set_soft_targets / lstm_hip_get_teacher_kl");
+    if (!o.teacher.empty() && o.gpus != 1) die("--teacher runs on one GPU (each rank would need a teacher of its own)");
+    if (!o.teacher.empty() && o.records) die("--teacher does not go with --records (the text windows train on hard targets)");
+    if (o.smoothing > 0.0 && o.gpus != 1) die("--label-smoothing runs on one GPU");
+    if (o.smoothing > 0.0 && o.records) die("--label-smoothing does not go with --records (the text windows train on hard targets)");
     if (o.records && (lstm_hip_text_plan == nullptr || lstm_hip_set_train_texts == nullptr || lstm_hip_get_train_texts == nullptr ||
                       lstm_hip_train_text_windows == nullptr || lstm_hip_get_train_texts_bits == nullptr))
         die("--records: the loaded liblstm_hip has no lstm_hip_text_plan / lstm_hip_set_train_texts / lstm_hip_get_train_texts / "
@@ -411,6 +456,21 @@ int run_rank(const Options &o, int rank, int up, int down) {
     if (data.size() <= (size_t)S + 1) die("text too short");
     const size_t length = data.size();
 
+    // --teacher: the checkpoint is read before anything touches the GPU, so a bad one is refused at once
+    int Nt = 0;
+    std::vector<float> Pt;
+    if (!o.teacher.empty()) {
+        if (!std::ifstream(o.teacher + "_W.txt").good()) die("--teacher: no checkpoint at " + o.teacher + "_W.txt");
+        std::string err;
+        Nt = checkpoint::hidden_size(o.teacher, M, &err);
+        if (Nt < 1) die("--teacher: " + err);
+        if (o.teacher_bf16 && (Nt + 127) / 128 * 128 > 1024)
+            die("--teacher-bf16: the bf16 recurrence runs hidden sizes up to 1024; the teacher's is " + std::to_string(Nt));
+        Pt.assign(lstm_hip_param_count(Nt, M), 0.0f);
+        const int got = checkpoint::load_params(o.teacher, Pt, Nt, M, &err);
+        if (got < 0) die("--teacher: " + err);
+        if (got == 0) die("--teacher: the checkpoint " + o.teacher + "_{W,U,b,Why,by}.txt is not complete");
+    }
     // the reference takes any hidden size (R/lstm.cc:53): the library pads it internally; every shape here stays N
     lstm_hip_config cfg{N, M, S, Bl, rank, o.flags | LSTM_HIP_PAD_HIDDEN};
     lstm_hip_t *h = nullptr;
@@ -446,6 +506,24 @@ int run_rank(const Options &o, int rank, int up, int down) {
         } else if (lead) printf("fopen error: (%s_W.txt) -- keeping the random initialisation\n", o.load.c_str());
     }
     CK(lstm_hip_set_params(h, 0, P.data()));
+    // soft targets: the teacher is a second handle with the student's S and B, borrowed by the student for every window
+    lstm_hip_t *teacher = nullptr;
+    if (!o.teacher.empty()) {
+        lstm_hip_config tcfg{Nt, M, S, Bl, rank,
+                             (o.flags & LSTM_HIP_FAST_MATH) | LSTM_HIP_PAD_HIDDEN | (o.teacher_bf16 ? LSTM_HIP_BF16_RECURRENCE : 0u)};
+        CK(lstm_hip_create(&tcfg, &teacher));
+        CK(lstm_hip_set_params(teacher, 0, Pt.data()));
+        printf("Teacher: hidden %d from %s_{W,U,Why,b,by}.txt%s, alpha %g, temperature %g\n", Nt, o.teacher.c_str(),
+               o.teacher_bf16 ? " (bf16 recurrence)" : "", o.distill_alpha, o.distill_tau);
+    }
+    if (teacher || o.smoothing > 0.0) {
+        const lstm_hip_soft_targets st{(uint32_t)sizeof(lstm_hip_soft_targets), teacher ? o.distill_alpha : 1.0,
+                                       teacher ? o.distill_tau : 1.0, o.smoothing};
+        CK(lstm_hip_set_soft_targets(h, teacher, &st));
+    }
+    double kl_sum = 0.0;  // teacher KL of the epoch so far, summed over its windows
+    long kl_windows = 0;
+    auto kl_per_char = [&]() { return kl_windows > 0 ? kl_sum / ((double)(S - 1) * (double)kl_windows) : 0.0; };
     if (!o.load.empty() && o.adam) { // resume: Adam's moments and step count, when the checkpoint has them (never _mem_*)
         std::vector<float> m(np, 0.0f), v(np, 0.0f);
         long long t = -1;
@@ -535,6 +613,8 @@ int run_rank(const Options &o, int rank, int up, int down) {
         const double test_time = now() - last_test;
         double test_error = NAN;
         if (evaldata.size() > 1) CK(heldout(&test_error));
+        if (teacher) printf("\nTrain error: %g, Test error: %g, Teacher KL: %g\n", train_error, test_error, kl_per_char());
+        else
         printf("\nTrain error: %g, Test error: %g\n", train_error, test_error);
         if (evaldata.size() > 1) printf("Test error: %.5f bits/char (%s)\n", test_error, evalname.c_str());
         if (avg_on && evaldata.size() > 1) { // the same text through the averaged model (the log keeps its columns)
@@ -551,6 +631,10 @@ int run_rank(const Options &o, int rank, int up, int down) {
         }
         if (!o.log.empty()) {
             results.push_back({(double)results.size(), test_time, train_error, test_error, gflops});
+            if (teacher) {
+                results.back().push_back(kl_per_char());
+                printf("%6g %6g %6g %6g %6g %6g\n\n", results.back()[0], test_time, train_error, test_error, gflops, results.back()[5]);
+            } else
             printf("%6g %6g %6g %6g %6g\n\n", results.back()[0], test_time, train_error, test_error, gflops);
             write_results(o.log + ".txt", results);
             CK(lstm_hip_get_params(h, 0, P.data()));
@@ -600,7 +684,7 @@ int run_rank(const Options &o, int rank, int up, int down) {
         return steps;
     };
     std::vector<float> hs((size_t)N * o.B), cs((size_t)N * o.B);
-    std::vector<double> losses, norms;
+    std::vector<double> losses, norms, kls;
 
     for (long e = 0; e < o.epochs; e++) {
         // epoch start: h[t], c[t] ~ N(0, 0.1) for every t (OV/lstm_eigen_opt/lstm.cc:176-181); drawn for
@@ -626,6 +710,7 @@ int run_rank(const Options &o, int rank, int up, int down) {
             windows_per_epoch = o.windows > 0 ? (long)std::min<int64_t>(o.windows, plan_windows) : (long)plan_windows;
         }
         double epoch_loss = 0.0;
+        kl_sum = 0.0, kl_windows = 0;
         long nan_windows = 0;
         double norm_sum = 0.0, norm_max = 0.0;
         long clipped = 0, norm_count = 0;
@@ -660,6 +745,12 @@ int run_rank(const Options &o, int rank, int up, int down) {
                     if (std::isfinite(v) && (float)(o.clip_norm / (v + 1e-6)) < 1.0f) clipped++;
                 }
             }
+            if (teacher) {
+                kls.resize(chunk);
+                CK(lstm_hip_get_teacher_kl(h, kls.data(), chunk));
+                for (double v : kls)
+                    if (!std::isnan(v)) kl_sum += v, kl_windows++;
+            }
             for (double v : losses) {
                 if (!std::isnan(v)) epoch_loss += v; // NaN guard as OV/lstm_eigen_class_CUDA/lstm.cc:325-326
                 else nan_windows++;
@@ -693,6 +784,11 @@ int run_rank(const Options &o, int rank, int up, int down) {
             const double train_bits = o.records ? epoch_loss * (double)o.B / std::max(chars, 1.0)
                                                 : epoch_loss / ((double)S * (double)(windows_per_epoch + S));
             printf("\n====================================================================================\n");
+            if (teacher)
+                printf("Epoch %ld/%ld, t = %.3f s, est GFLOP/s = %.3f, avg loss = %.3f bits/char, teacher KL = %.5f bits/char\n", e + 1,
+                       o.epochs, epoch_time, (flops_per_iteration * windows_per_epoch / std::pow(2.0, 30)) / epoch_time, train_bits,
+                       kl_per_char());
+            else
             printf("Epoch %ld/%ld, t = %.3f s, est GFLOP/s = %.3f, avg loss = %.3f bits/char\n", e + 1, o.epochs, epoch_time,
                    (flops_per_iteration * windows_per_epoch / std::pow(2.0, 30)) / epoch_time,
                    train_bits);
@@ -787,7 +883,8 @@ int run_rank(const Options &o, int rank, int up, int down) {
             for (int k = 0; k < o.sample; k++) (void)rng.uniform();
         }
     }
-    CK(lstm_hip_destroy(h));
+    CK(lstm_hip_destroy(h)); // (releases the teacher)
+    if (teacher) CK(lstm_hip_destroy(teacher));
     return 0;
 }
 

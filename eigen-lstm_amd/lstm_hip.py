@@ -71,6 +71,10 @@ class _EvalOpt(C.Structure):  # lstm_hip_eval_opt
     _fields_ = [("size", C.c_uint32), ("lanes", C.c_int32)]
 
 
+class _SoftTargets(C.Structure):  # lstm_hip_soft_targets
+    _fields_ = [("size", C.c_uint32), ("alpha", C.c_double), ("temperature", C.c_double), ("smoothing", C.c_double)]
+
+
 class _Config(C.Structure):
     _fields_ = [("N", C.c_int32), ("M", C.c_int32), ("S", C.c_int32), ("B", C.c_int32), ("device", C.c_int32),
                 ("flags", C.c_uint32)]
@@ -100,6 +104,7 @@ SYMBOLS = [
     "lstm_hip_eval_plan", "lstm_hip_eval_texts",
     "lstm_hip_text_plan", "lstm_hip_set_train_texts", "lstm_hip_get_train_texts", "lstm_hip_train_text_windows",
     "lstm_hip_get_train_texts_bits",
+    "lstm_hip_set_soft_targets", "lstm_hip_get_soft_targets", "lstm_hip_get_teacher_kl",
 ]
 
 
@@ -348,8 +353,9 @@ class Lstm:
 
     def close(self):
         if self._h:
-            self.lib.lstm_hip_destroy(self._h)
+            _chk(self.lib.lstm_hip_destroy(self._h))  # (refused while a student holds this handle as its teacher)
             self._h = C.c_void_p()
+            self._teacher = None
 
     def __del__(self):
         try:
@@ -421,6 +427,7 @@ class Lstm:
     # ---- cuLSTM::forward / calculate_loss / backward, cuda_adagrad ------------------------------
     def forward(self):
         _chk(self.lib.lstm_hip_forward(self._h))
+        self._kls = 1
 
     def loss(self):
         out = C.c_double()
@@ -508,6 +515,31 @@ class Lstm:
         _chk(self.lib.lstm_hip_get_weight_drop(self._h, C.byref(rate), C.byref(seed), C.byref(t)))
         return rate.value, seed.value, t.value
 
+    # ---- soft targets: label smoothing and distillation from a teacher (lstm_hip_set_soft_targets) ----
+    def set_soft_targets(self, teacher=None, alpha=1.0, temperature=1.0, smoothing=0.0):
+        """dy = alpha (p - r) + (1 - alpha) tau (softmax(z / tau) - softmax(z_T / tau)), r the target smoothed by `smoothing`
+        and z_T the logits of `teacher`, an Lstm with the same S, B and device that this handle borrows: every forward pass
+        here overwrites its window, states and logits.  The defaults turn the feature off.  Reported losses stay the
+        hard-target bits.  Drops the forward pass.  The student keeps a reference to the teacher until it is re-set or closed."""
+        opt = _SoftTargets(C.sizeof(_SoftTargets), alpha, temperature, smoothing)
+        _chk(self.lib.lstm_hip_set_soft_targets(self._h, teacher._h if teacher is not None else None, C.byref(opt)))
+        self._teacher = teacher
+
+    def soft_targets(self):
+        """(teacher, alpha, temperature, smoothing) of lstm_hip_get_soft_targets; teacher is the Lstm given to
+        set_soft_targets, or None."""
+        t, opt = C.c_void_p(), _SoftTargets()
+        _chk(self.lib.lstm_hip_get_soft_targets(self._h, C.byref(t), C.byref(opt)))
+        return (getattr(self, "_teacher", None) if t.value else None), opt.alpha, opt.temperature, opt.smoothing
+
+    def teacher_kl(self, n=None):
+        """KL(q || p_tau) in bits per window of the last forward (1) / train_windows (count) call, oldest first, summed over
+        the window's steps as the loss is; n=None: all of them.  Needs a teacher."""
+        k = getattr(self, "_kls", 0) if n is None else int(n)
+        out = np.zeros(k, np.float64)
+        _chk(self.lib.lstm_hip_get_teacher_kl(self._h, _ptr(out, C.c_double), C.c_int64(k)))
+        return out
+
     # ---- data-parallel -----------------------------------------------------------------------
     def comm_init(self, unique_id, nranks, rank):
         buf = (C.c_uint8 * UNIQUE_ID_BYTES).from_buffer_copy(unique_id)
@@ -551,7 +583,7 @@ class Lstm:
         _chk(self.lib.lstm_hip_train_windows(self._h, C.c_int64(count), C.c_double(lr),
                                              _ptr(losses, C.c_double) if want_losses else None,
                                              C.byref(ms) if want_time else None))
-        self._steps = count
+        self._steps = self._kls = count
         if want_time:
             return losses, ms.value
         return losses

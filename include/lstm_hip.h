@@ -262,6 +262,53 @@ int lstm_hip_set_weight_drop(lstm_hip_t *h, double rate, uint64_t seed, uint64_t
 int lstm_hip_get_weight_drop(lstm_hip_t *h, double *rate, uint64_t *seed, uint64_t *t);
 int lstm_hip_weight_drop_mask(int32_t N, double rate, uint64_t seed, uint64_t t, uint8_t *keep);
 
+/* ---- soft targets: label smoothing and distillation from a teacher
+ * Per column (one stream at one step, target byte k, k < 0 for an empty target), with z = Why h + by the student's logits and
+ * p their softmax in the handle's own mode (unshifted, or max-shifted under LSTM_HIP_STABLE_SOFTMAX):
+ *   r    = (1 - eps) e_k + eps / 256 for k >= 0;  r = 0 for k < 0 (no smoothing mass: the hard term is dy = probs there)
+ *   q    = softmax(z_T / tau), p_tau = softmax(z / tau), both max-shifted; z_T the teacher's logits of the same column.
+ *          At tau = 1 p_tau is p itself, with no second softmax
+ *   dy   = alpha (p - r) + (1 - alpha) tau (p_tau - q)     (without a teacher the second term is absent)
+ * the gradient, in nats, of alpha CE(r, p) + (1 - alpha) tau^2 KL(q || p_tau).  The teacher's term applies to every column,
+ * those with an empty target included.  dby = rowsum(dy).  The probabilities, the surprisals and every reported loss stay the
+ * hard-target figures of p, so losses compare between runs with and without soft targets.
+ * alpha, 1 - alpha, tau, 1 / tau, 1 - eps and eps / 256 are computed in double on the host and narrowed; the elementwise work
+ * is fp32.  Results are held to tolerances, not to bits -- except when the feature is off: teacher NULL with opt NULL or
+ * (alpha, tau, eps) = (1, 1, 0) leaves a handle that makes exactly the launches it made before this call existed.
+ *
+ * The teacher is a handle of the caller's with the same S, B and device; any N and any create flags.  It is borrowed: its
+ * window, states and logit block are overwritten, its parameters (which = 0) only read, its inference source and average
+ * ignored.  A forward pass of the student (lstm_hip_forward, each window of lstm_hip_train_windows) copies the student's
+ * window inputs to the teacher, runs the teacher's forward recurrence and Why H product in the forms of the teacher's plan,
+ * without its softmax launch, and then the student's forward pass, all on the student's stream: the two handles' recurrences
+ * are never in flight together.  In lstm_hip_train_windows the teacher slides as the student does (its own column carry_col
+ * becomes its column 0 before every window); in the single-window calls its column 0 is what the caller left there.
+ * lstm_hip_slide_state and lstm_hip_set_state on the student never touch the teacher.  lstm_hip_backward on the teacher after
+ * such a pass is LSTM_HIP_ESTATE.
+ *
+ * Teacher KL.  kl = sum_m q_m (log2 q_m - log2 p_tau,m) per column, in log-sum-exp form, 0 where q_m is 0; per window
+ * sum_t (sum_b kl) / B_global, summed as the window loss is, without the tau^2 factor.  lstm_hip_get_teacher_kl returns the
+ * figures of the last lstm_hip_forward (1) or lstm_hip_train_windows (count), oldest first; n <= that number (else
+ * LSTM_HIP_EINVAL); LSTM_HIP_ESTATE without a teacher.  They stay on the device until asked for.
+ *
+ * Refusals (the handle stays usable, nothing is launched).  LSTM_HIP_EINVAL: a wrong size, alpha outside [0, 1], tau <= 0 or
+ * not finite, eps outside [0, 1), NaN anywhere, alpha != 1 or tau != 1 without a teacher, teacher == h, a teacher that has a
+ * teacher (or a student that is one), a teacher whose S, B or device differ.  LSTM_HIP_ESTATE: a communicator on the student;
+ * lstm_hip_train_text_windows and the adaptive coders while soft targets are on; a student forward while the teacher has
+ * weight drop on; lstm_hip_destroy(teacher) while a student holds it (destroying or re-setting the student releases it).
+ * Per handle, may change between calls, not part of the engine plan or of checkpoints.  A set drops the forward pass:
+ * lstm_hip_backward is LSTM_HIP_ESTATE until a new lstm_hip_forward. */
+typedef struct lstm_hip_soft_targets {
+    uint32_t size;        /* sizeof(lstm_hip_soft_targets); anything else: LSTM_HIP_EINVAL */
+    double alpha;         /* weight of the hard-target term, 0..1; must be 1 without a teacher */
+    double temperature;   /* tau > 0 of the teacher term; must be 1 without a teacher */
+    double smoothing;     /* eps in [0, 1): label smoothing of the hard target */
+} lstm_hip_soft_targets;
+int lstm_hip_set_soft_targets(lstm_hip_t *h, lstm_hip_t *teacher /* may be NULL */,
+                              const lstm_hip_soft_targets *opt /* NULL with teacher NULL: off */);
+int lstm_hip_get_soft_targets(lstm_hip_t *h, lstm_hip_t **teacher, lstm_hip_soft_targets *opt);
+int lstm_hip_get_teacher_kl(lstm_hip_t *h, double *kl_bits, int64_t n);
+
 /* ---- data-parallel exchange (new; the reference is single-device).  One SUM all-reduce of the
  *      flat gradient block per window over RCCL; every rank then applies the identical Adagrad step.
  *      With LSTM_HIP_PAD_HIDDEN the payload is the padded block (Np from N and the flags, so every
