@@ -74,6 +74,27 @@ template <bool FAST> __device__ __forceinline__ float p_tanh(float x) {
     const float e = p_exp_neg(2.0f * __builtin_fabsf(x));
     return __builtin_copysignf((1.0f - e) * __builtin_amdgcn_rcpf(1.0f + e), x);
 }
+// Two p_exp_neg side by side on the packed fp32 ALU (v_pk_mul_f32 / v_pk_fma_f32 / v_pk_add_f32): element for element
+// the operations of p_exp_neg in its order, so the same bits at half the instructions; v_exp_f32 has no packed form.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ f32x2 p_exp_neg2(f32x2 x) {
+    const float hi = 1.44269502162933349609375f, lo = 1.925963033500011e-08f;
+    const f32x2 nx = -x, hi2 = {hi, hi};
+    const f32x2 t = nx * hi2;
+    const f32x2 r = __builtin_elementwise_fma(nx, hi2, -t) - x * lo;
+    const f32x2 m = 1.0f + r * 0.693147180559945f;
+    return f32x2{__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)} * m;
+}
+// the four gates (i, o, f sigmoid; u tanh) of p_sigm<false> / p_tanh<false> from the four pre-activations: the four
+// exponential arguments depend on the pre-activations alone and run as two packed chains
+__device__ __forceinline__ void p_gates4(f32x2 pa, f32x2 pb, float &ig, float &og, float &fg, float &ug) {
+    const f32x2 ea = p_exp_neg2(pa), eb = p_exp_neg2(f32x2{pb.x, 2.0f * __builtin_fabsf(pb.y)});
+    const f32x2 da = 1.0f + ea, db = 1.0f + eb;
+    ig = __builtin_amdgcn_rcpf(da.x);
+    og = __builtin_amdgcn_rcpf(da.y);
+    fg = __builtin_amdgcn_rcpf(db.x);
+    ug = __builtin_copysignf((1.0f - eb.y) * __builtin_amdgcn_rcpf(db.y), pb.y);
+}
 
 // the value of `v` in lane l ^ 16 / l ^ 32, on the vector ALU (v_permlane16_swap / v_permlane32_swap; a ds_bpermute through
 // the LDS crossbar costs ~10x the latency): both operands of the swap are v, so the odd rows / upper half find the partner's
@@ -889,12 +910,19 @@ __global__ __launch_bounds__(FWD4_THREADS) void k_fwd_persistent6(const float4 *
                 for (int gt = 0; gt < 4; gt++) wx[gt] = W[(size_t)xnext * G4 + gt * N + j];
             }
             if (t + 1 < S) xnext = xi[(t + 1) * B + colc];
+            // Where h_t and the reset go does not depend on h_t: the addresses are made here, while the wave waits for the
+            // product, and pinned so that the compiler does not sink them (64-bit multiplies and shifts) behind the gates.
+            const size_t e_pub = ((size_t)((t + ring_base) & (HX_RING - 1)) * B + col) * N + j;
+            const size_t e_rst = ((size_t)((t + 2 + ring_base) & (HX_RING - 1)) * B + col) * N + j;
+            size_t b_pub = e_pub * sizeof(float), b_rst = e_rst * sizeof(float); // byte offsets in the ring
+            asm volatile("" : "+v"(b_pub), "+v"(b_rst));
             FSTAMP(8, 0)
             {   // all eight partial-sum images of this half and step are in LDS
                 bool in = false;
+                const unsigned need = 8u * (unsigned)((t + 1) / 2); // steps 1..t of the parity of t: (t + 1) / 2 of them
                 for (int spins = 0; spins <= SPIN_LIMIT; spins++) {
-                    // steps 1..t of the parity of t: (t + 1) / 2 of them
-                    in = __hip_atomic_load(&s_done[hf][t & 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >= 8u * (unsigned)((t + 1) / 2);
+                    in = __hip_atomic_load(&s_done[hf][t & 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >= need;
+                    // (both words on every miss: DESIGN.md 4.4)
                     if (in || __hip_atomic_load(&s_abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) break;
                     __builtin_amdgcn_s_sleep(1);
                 }
@@ -921,46 +949,72 @@ __global__ __launch_bounds__(FWD4_THREADS) void k_fwd_persistent6(const float4 *
                 local_pub = (XCD_FORCE_LOCAL || __all(same)) && NB3 <= 64;
             }
             // the four gates of (unit gu, column gc) sit side by side in every wave's row gc: one 16-byte read each
-            float4 uh = *reinterpret_cast<const float4 *>(rp);
+            // All eight reads are issued before the first sum (left to itself the compiler issues three and then one at a
+            // time, each with its own wait: four LDS round trips in a row); the sums keep the ascending order of the waves
+            // and run two gates to a v_pk_add_f32.
+            // (N = 256: in two batches of four, which keeps the kernel within the registers it had)
+            constexpr int RB = N == 512 ? 8 : 4;
+            f32x2 ua, ub;
 #pragma unroll
-            for (int ww = 1; ww < 8; ww++) {
-                const float4 v = *reinterpret_cast<const float4 *>(rp + ww * 4 * RS);
-                uh.x += v.x;
-                uh.y += v.y;
-                uh.z += v.z;
-                uh.w += v.w;
+            for (int w0 = 0; w0 < 8; w0 += RB) {
+                float4 im[RB];
+#pragma unroll
+                for (int ww = 0; ww < RB; ww++) im[ww] = *reinterpret_cast<const float4 *>(rp + (w0 + ww) * 4 * RS);
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int ww = 0; ww < RB; ww++) {
+                    if (w0 + ww == 0) {
+                        ua = f32x2{im[0].x, im[0].y}, ub = f32x2{im[0].z, im[0].w};
+                    } else {
+                        ua += f32x2{im[ww].x, im[ww].y};
+                        ub += f32x2{im[ww].z, im[ww].w};
+                    }
+                }
+                if (RB < 8) __builtin_amdgcn_sched_barrier(0);
             }
-            const float pre0 = (wx[0] + uh.x) + bs[0], pre1 = (wx[1] + uh.y) + bs[1]; // R/lstm.cc:176
-            const float pre2 = (wx[2] + uh.z) + bs[2], pre3 = (wx[3] + uh.w) + bs[3];
-            const float ig = p_sigm<FAST>(pre0), og = p_sigm<FAST>(pre1), fg = p_sigm<FAST>(pre2); // :179
-            const float ug_ = p_tanh<FAST>(pre3);                                                 // :182
+            const f32x2 pa = (f32x2{wx[0], wx[1]} + ua) + f32x2{bs[0], bs[1]}; // R/lstm.cc:176
+            const f32x2 pb = (f32x2{wx[2], wx[3]} + ub) + f32x2{bs[2], bs[3]};
+            float ig, og, fg, ug_;
+            if (!FAST) {
+                p_gates4(pa, pb, ig, og, fg, ug_); // :179, :182
+            } else {
+                ig = p_sigm<FAST>(pa.x), og = p_sigm<FAST>(pa.y), fg = p_sigm<FAST>(pb.x); // :179
+                ug_ = p_tanh<FAST>(pb.y);                                                 // :182
+            }
             const float cv = p_tanh<FAST>(ig * ug_ + fg * cprev);                                 // :185-189
             const float hv = og * cv;                                                             // :192
             cprev = cv;
+            // the ring takes the canonical value: made once, ahead of the four lane moves (H takes h_t as it is, below)
+            const float hc = hx_canon(hv);
+            float4 hp;
+            hp.x = dpp_f<0x00>(hc);
+            hp.y = dpp_f<0x55>(hc);
+            hp.z = dpp_f<0xAA>(hc);
+            hp.w = dpp_f<0xFF>(hc);
+            FSTAMP(8, 2)
+            // the reset this wave issued a step ago (and every older store) has completed before h_t can be seen
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            FSTAMP(8, 3)
+            const bool pub_lane = (gu & 3) == 0 && col < B;
+            if (pub_lane) {
+                const float4 sent = {__uint_as_float(HX_SENT), __uint_as_float(HX_SENT), __uint_as_float(HX_SENT),
+                                     __uint_as_float(HX_SENT)};
+                if (XCD_LOCAL && local_pub) {
+                    *reinterpret_cast<float4 *>(reinterpret_cast<char *>(Hx) + b_pub) = hp;
+                    *reinterpret_cast<float4 *>(reinterpret_cast<char *>(Hx) + b_rst) = sent;
+                } else {
+                    st_sc1(hp, rHx, (int)b_pub);
+                    st_sc1(sent, rHx, (int)b_rst);
+                }
+            }
+            asm volatile("" ::: "memory");
+            // behind the publish, off the chain: the window's own copies of the step
             float4 h4;
             h4.x = dpp_f<0x00>(hv);
             h4.y = dpp_f<0x55>(hv);
             h4.z = dpp_f<0xAA>(hv);
             h4.w = dpp_f<0xFF>(hv);
-            FSTAMP(8, 2)
-            // the reset this wave issued a step ago (and every older store) has completed before h_t can be seen
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            FSTAMP(8, 3)
-            if ((gu & 3) == 0 && col < B) {
-                const float4 hp = {hx_canon(h4.x), hx_canon(h4.y), hx_canon(h4.z), hx_canon(h4.w)};
-                const float4 sent = {__uint_as_float(HX_SENT), __uint_as_float(HX_SENT), __uint_as_float(HX_SENT),
-                                     __uint_as_float(HX_SENT)};
-                const size_t e_pub = ((size_t)((t + ring_base) & (HX_RING - 1)) * B + col) * N + j;
-                const size_t e_rst = ((size_t)((t + 2 + ring_base) & (HX_RING - 1)) * B + col) * N + j;
-                if (XCD_LOCAL && local_pub) {
-                    *reinterpret_cast<float4 *>(Hx + e_pub) = hp;
-                    *reinterpret_cast<float4 *>(Hx + e_rst) = sent;
-                } else {
-                    st_sc1(hp, rHx, (int)(e_pub * sizeof(float)));
-                    st_sc1(sent, rHx, (int)(e_rst * sizeof(float)));
-                }
-                *reinterpret_cast<float4 *>(H + ((size_t)t * B + col) * N + j) = h4;
-            }
+            if (pub_lane) *reinterpret_cast<float4 *>(H + ((size_t)t * B + col) * N + j) = h4;
             if (col < B) {
                 float *gcp = G + ((size_t)t * B + col) * G4 + j;
                 gcp[0] = ig;
@@ -2037,10 +2091,10 @@ template <int N_, bool FUSE, bool STAMP> __device__ __forceinline__ void bwds_pr
 #undef S6
                 if (hf == 0) { SSTAMP(3, 10) } else { SSTAMP(3, 6) }
                 float4 q; // register r = column r of the half
-                q.x = hx_canon((c0[0] + c1[0]) + (c2[0] + c3[0]));
-                q.y = hx_canon((c0[1] + c1[1]) + (c2[1] + c3[1]));
-                q.z = hx_canon((c0[2] + c1[2]) + (c2[2] + c3[2]));
-                q.w = hx_canon((c0[3] + c1[3]) + (c2[3] + c3[3]));
+                {   // (c0 + c1) + (c2 + c3) per column, two columns to a v_pk_add_f32
+                    const f32x2 lo = (c0.lo + c1.lo) + (c2.lo + c3.lo), hi = (c0.hi + c1.hi) + (c2.hi + c3.hi);
+                    q = float4{hx_canon(lo.x), hx_canon(lo.y), hx_canon(hi.x), hx_canon(hi.y)};
+                }
                 if (tagged_) {
                     const unsigned ph = (unsigned)((ring_base + (S - 1 - t)) >> 2) & 1u;
                     q = float4{tag_mark(q.x, ph), tag_mark(q.y, ph), tag_mark(q.z, ph), tag_mark(q.w, ph)};
@@ -2049,6 +2103,7 @@ template <int N_, bool FUSE, bool STAMP> __device__ __forceinline__ void bwds_pr
                                      __uint_as_float(HX_SENT)};
                 // this wave's older stores (the last reset) are complete
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                // (the offsets are made here, not ahead of the wait for dg_t: DESIGN.md 4.4)
                 const size_t e_pub = qoff(t, hf), e_rst = qoff(t - 2, hf);
                 if (d < NB) { // (N = 256: every lane of an active wave has a destination; kept for clarity)
                     if (XCD_LOCAL && local) {
@@ -2167,14 +2222,14 @@ template <int N_, bool FUSE, bool STAMP> __device__ __forceinline__ void bwds_el
                 for (int i = 0; i < NLD; i++) v[i] = float4{tag_value(v[i].x), tag_value(v[i].y), tag_value(v[i].z), tag_value(v[i].w)};
             }
             // sum over the sources: lane-local over sources 4i + q (ascending i), then over the four rows q of 16 lanes
-            float4 sm = v[0];
+            // (two columns to a v_pk_add_f32)
+            f32x2 sa = {v[0].x, v[0].y}, sb = {v[0].z, v[0].w};
 #pragma unroll
             for (int i = 1; i < NLD; i++) {
-                sm.x += v[i].x;
-                sm.y += v[i].y;
-                sm.z += v[i].z;
-                sm.w += v[i].w;
+                sa += f32x2{v[i].x, v[i].y};
+                sb += f32x2{v[i].z, v[i].w};
             }
+            const float4 sm = {sa.x, sa.y, sb.x, sb.y};
             // 4 x 4 transpose-sum: row q = l >> 4 needs column q.  Round 1 (partner row q ^ 1): keep the columns of q's
             // parity, send the other two; round 2 (partner row q ^ 2): keep column q, send the other.
             const int q = l >> 4;
