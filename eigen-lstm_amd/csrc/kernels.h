@@ -224,6 +224,12 @@ void softmax_loss_dy(float *Y, float *P, const float *by, const int32_t *ti, flo
 // the order of every sum included, is softmax_loss_dy's.
 void softmax_loss_dy_text(float *Y, float *P, const float *by, const int32_t *ti, float *colloss, float *dby_part, int col0,
                           int col1, bool stable, hipStream_t st);
+// the text variant with a weight per column (lstm_hip_set_train_texts_weighted): wt[col] is the weight
+// of the column's target, laid out like ti.  A column with a target gets dy = wt * (probs - target) and colloss = wt *
+// surprisal (one fp32 multiply each behind the text variant's value); wt == 0 selects dy = +0 and colloss = 0 whatever probs
+// holds; a column without a target is the text variant's.  wt == 1 everywhere gives the text variant's bytes.
+void softmax_loss_dy_weighted(float *Y, float *P, const float *by, const int32_t *ti, const float *wt, float *colloss,
+                              float *dby_part, int col0, int col1, bool stable, hipStream_t st);
 // the launch with soft targets (lstm_hip_set_soft_targets): probs, colloss, the dby_part rows and the
 // column ranges are softmax_loss_dy's; dy = alpha * (probs - r) + oma_tau * (softmax(z / tau) - softmax(zT / tau)) with
 // r = ome * onehot + eps256 (0 in a column without a target) and zT = Yt + by_t the teacher's logits of the same column.
@@ -573,6 +579,10 @@ struct TextWindowArgs {
     const float *colloss;       // [S - 1][B]
     double *bits;               // [streams]
     int S, B, N;
+    // weighted texts (lstm_hip_set_train_texts_weighted), both null otherwise: weight is indexed like text, and text_window
+    // writes wt [S][B] beside ti: the weight of the row's target byte (entry j + 1 for step j), 0 for a row without a step
+    const float *weight;
+    float *wt;
 };
 void text_window(const TextWindowArgs &a, int64_t w, int cus, hipStream_t st);
 void text_fold(const TextWindowArgs &a, int64_t w, int cus, hipStream_t st);

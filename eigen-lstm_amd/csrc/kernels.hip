@@ -563,11 +563,16 @@ void pack_bf16(const float *src, size_t n, unsigned short *dst, hipStream_t st) 
 // ------------------------------------------------------------------------------------------------
 constexpr int SM_COLS_PER_WAVE = 2;
 // TEXT (the text windows, lstm_hip_train_text_windows): a column without a target gets dy = 0, not dy = probs
-template <bool STABLE, bool TEXT>
+// WEIGHTED (the text windows with per-byte weights, lstm_hip_set_train_texts_weighted; implies TEXT): a column with a target
+// and the weight w = wt[col] gets dy = w * (probs - target) and colloss = w * surprisal, one multiply each behind the text
+// form's value; w == 0 SELECTS dy = +0 and colloss = 0, so a context byte with a non-finite p poisons nothing.  wt is read
+// beside ti, one wave-uniform float per column that no address depends on; with the flag off wt is never touched.
+template <bool STABLE, bool TEXT, bool WEIGHTED = false>
 __device__ __forceinline__ void softmax_loss_dy_body(float *__restrict__ Y, float *__restrict__ P,
                                                      const float *__restrict__ by, const int32_t *__restrict__ ti,
                                                      float *__restrict__ colloss, float *__restrict__ dby_part,
-                                                     int col0, int T) {
+                                                     int col0, int T, const float *__restrict__ wt = nullptr) {
+    static_assert(TEXT || !WEIGHTED, "the weighted form is a form of the text windows");
     const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
     __shared__ float4 part[4][64];
     const int gw = col0 / SM_COLS_PER_WAVE + blockIdx.x * 4 + w; // global wave index: columns 2*gw, 2*gw+1
@@ -604,23 +609,31 @@ __device__ __forceinline__ void softmax_loss_dy_body(float *__restrict__ Y, floa
         p.w = e.w / s;
         if (P != nullptr) reinterpret_cast<float4 *>(P + (size_t)col * 256)[l] = p; // (null: nobody will read this window's)
         const int tk = ti[col];
+        float wv = 1.0f;
+        if constexpr (WEIGHTED) wv = wt[col];
         float4 d = p;
         if (tk >= 0 && (tk >> 2) == l) {
             const int c = tk & 3;
+            float sp;
             if constexpr (STABLE) {
                 const float zt = c == 0 ? y.x : c == 1 ? y.y : c == 2 ? y.z : y.w;
-                colloss[col] = lse_surprisal(s, zmax, zt);
+                sp = lse_surprisal(s, zmax, zt);
             } else {
                 const float pt = c == 0 ? p.x : c == 1 ? p.y : c == 2 ? p.z : p.w;
-                colloss[col] = -log2f(pt);
+                sp = -log2f(pt);
             }
+            if constexpr (WEIGHTED) sp = wv == 0.0f ? 0.0f : wv * sp;
+            colloss[col] = sp;
             if (c == 0) d.x -= 1.0f;
             else if (c == 1) d.y -= 1.0f;
             else if (c == 2) d.z -= 1.0f;
             else d.w -= 1.0f;
         }
         if (tk < 0 && l == 0) colloss[col] = 0.0f;
-        if constexpr (TEXT)
+        if constexpr (WEIGHTED) {
+            if (tk < 0 || wv == 0.0f) d = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            else d = make_float4(d.x * wv, d.y * wv, d.z * wv, d.w * wv);
+        } else if constexpr (TEXT)
             if (tk < 0) d = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         *yp = d;
         dsum.x += d.x;
@@ -656,6 +669,13 @@ __global__ __launch_bounds__(256) void k_softmax_loss_dy_text(float *__restrict_
                                                               int col0, int T) {
     softmax_loss_dy_body<STABLE, true>(Y, P, by, ti, colloss, dby_part, col0, T);
 }
+template <bool STABLE>
+__global__ __launch_bounds__(256) void k_softmax_loss_dy_weighted(float *__restrict__ Y, float *__restrict__ P,
+                                                                  const float *__restrict__ by, const int32_t *__restrict__ ti,
+                                                                  const float *__restrict__ wt, float *__restrict__ colloss,
+                                                                  float *__restrict__ dby_part, int col0, int T) {
+    softmax_loss_dy_body<STABLE, true, true>(Y, P, by, ti, colloss, dby_part, col0, T, wt);
+}
 // columns [col0, col1) of a T-column problem; col0 must be a multiple of 8.  dby_part needs
 // softmax_parts(T) rows of 256 floats; rows of waves past col1 are written as zeros.
 int softmax_parts(int T) { return (T + 4 * SM_COLS_PER_WAVE - 1) / (4 * SM_COLS_PER_WAVE) + 4; } // one row per workgroup
@@ -676,6 +696,15 @@ void softmax_loss_dy_text(float *Y, float *P, const float *by, const int32_t *ti
         hipLaunchKernelGGL(k_softmax_loss_dy_text<true>, dim3(blocks), dim3(256), 0, st, Y, P, by, ti, colloss, dby_part, col0, col1);
     else
         hipLaunchKernelGGL(k_softmax_loss_dy_text<false>, dim3(blocks), dim3(256), 0, st, Y, P, by, ti, colloss, dby_part, col0, col1);
+}
+void softmax_loss_dy_weighted(float *Y, float *P, const float *by, const int32_t *ti, const float *wt, float *colloss,
+                              float *dby_part, int col0, int col1, bool stable, hipStream_t st) {
+    const int waves = (col1 - col0 + SM_COLS_PER_WAVE - 1) / SM_COLS_PER_WAVE;
+    const int blocks = (waves + 3) / 4;
+    if (stable)
+        hipLaunchKernelGGL(k_softmax_loss_dy_weighted<true>, dim3(blocks), dim3(256), 0, st, Y, P, by, ti, wt, colloss, dby_part, col0, col1);
+    else
+        hipLaunchKernelGGL(k_softmax_loss_dy_weighted<false>, dim3(blocks), dim3(256), 0, st, Y, P, by, ti, wt, colloss, dby_part, col0, col1);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3266,18 +3295,21 @@ __global__ __launch_bounds__(256) void k_text_window(TextWindowArgs a, long long
         const int t = (int)(i / a.B), l = (int)(i - (long long)t * a.B);
         const int s = slot[l];
         int xv = -1, tv = -1;
+        float wv = 0.0f; // (weighted texts only) the weight of the row's target byte; a row without a step: 0
         if (s >= 0) {
             const uint64_t o = a.off[s], len = a.off[s + 1] - o;
             const long long j = (w - a.first[s]) * L + t - 1; // the step: feeds byte j, has byte j + 1 as its target
             if (j >= 0 && (uint64_t)j + 1 < len) {
                 xv = (int)a.text[o + j];
                 tv = (int)a.text[o + j + 1];
+                if (a.wt) wv = a.weight[o + j + 1];
             }
         }
         a.xi[i] = xv;
         a.ti[i] = tv;
         a.Xr[i] = xv; // the rings with head = 0: ring row = window row
         a.Tr[i] = tv;
+        if (a.wt) a.wt[i] = wv;
     }
     if (tid == 0) *a.head = 0;
     const int N4 = a.N / 4;

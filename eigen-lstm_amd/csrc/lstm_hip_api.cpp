@@ -63,6 +63,7 @@ enum KernelId {
     K_SCORE_HEAD,              // one step of lstm_hip_score: logits, surprisal, entropy, rank and alternatives of every stream
     K_COUNT_BASE, // the ids above have their names in kKernelNames, the ids from here on in kKernelNamesMore (kernel_name)
     K_SOFTMAX_SOFT = K_COUNT_BASE, // K_SOFTMAX's launch with soft targets (lstm_hip_set_soft_targets): label smoothing, a teacher's term
+    K_SOFTMAX_WEIGHTED,            // K_SOFTMAX_TEXT's launch with a weight per target byte (lstm_hip_set_train_texts_weighted)
     K_COUNT
 };
 const char *const kKernelNames[K_COUNT] = { // (K_COUNT_BASE names; the rows behind them stay null)
@@ -70,7 +71,7 @@ const char *const kKernelNames[K_COUNT] = { // (K_COUNT_BASE names; the rows beh
     "dW_db", "loss_dby", "adagrad", "slide", "allreduce", "fwd_persistent", "bwd_persistent", "gen_head", "side_sums",
     "gemm_dU_halves", "grad_sumsq", "grad_norm", "adam", "code_head", "block_window", "text_window", "text_fold",
     "softmax_loss_dy_text", "beam_head", "beam_backtrack", "score_head"};
-const char *const kKernelNamesMore[K_COUNT - K_COUNT_BASE] = {"softmax_soft"};
+const char *const kKernelNamesMore[K_COUNT - K_COUNT_BASE] = {"softmax_soft", "softmax_loss_dy_weighted"};
 inline const char *kernel_name(int id) { return id < K_COUNT_BASE ? kKernelNames[id] : kKernelNamesMore[id - K_COUNT_BASE]; }
 
 // ---- RCCL, loaded on first use so single-GPU users never touch it --------------------------
@@ -211,6 +212,8 @@ struct lstm_hip_ctx {
     int32_t *tt_slot = nullptr;   // [windows][B]
     int64_t *tt_first = nullptr;  // [streams]
     double *tt_bits = nullptr;    // [streams]
+    float *tt_weight = nullptr;   // (lstm_hip_set_train_texts_weighted; null: unweighted) a weight per byte, indexed like tt_text
+    float *tt_wt = nullptr;       // ... and the window's weights beside ti, [S][B]: scratch that text_window rewrites every window
     int32_t tt_streams = 0;
     int64_t tt_windows = 0, tt_next = 0; // the plan's length, the next window to run
     bool text_window = false;     // the window under way is one of those: do_forward launches the softmax's text form
@@ -509,6 +512,11 @@ int do_forward(lstm_hip_ctx *h) {
         if (h->teacher) // the window's KL figure: every step, in bits, summed as the window loss is
             RUN(K_LOSS, loss_reduce(h->colkl, S - 1, B, h->global_B, h->d_kls + h->kl_idx, nullptr, 0, nullptr, h->st, 1.0f));
     } else
+    if (h->text_window && h->tt_weight) // (lstm_hip_train_text_windows on weighted texts: dy = weight * (probs - target))
+        RUN(K_SOFTMAX_WEIGHTED, softmax_loss_dy_weighted(h->Y + (size_t)256 * B, h->pr_stale ? nullptr : h->Pr + (size_t)256 * B,
+                                                         h->P + h->pl.by, h->ti + B, h->tt_wt + B, h->colloss, h->dby_part, 0,
+                                                         h->T, (h->cfg.flags & LSTM_HIP_STABLE_SOFTMAX) != 0, h->st));
+    else
     if (h->text_window) // (lstm_hip_train_text_windows only: a column without a target gets dy = 0)
         RUN(K_SOFTMAX_TEXT, softmax_loss_dy_text(h->Y + (size_t)256 * B, h->pr_stale ? nullptr : h->Pr + (size_t)256 * B,
                                                  h->P + h->pl.by, h->ti + B, h->colloss, h->dby_part, 0, h->T,
@@ -1037,6 +1045,7 @@ int lstm_hip_destroy(lstm_hip_t *h) {
     if (h->h_losses) (void)hipHostFree(h->h_losses);
     for (void *p : {(void *)h->d_norms, (void *)h->norm_part, (void *)h->clip_coef, (void *)h->adam_v, (void *)h->avg, (void *)h->Ue,
                     (void *)h->tt_text, (void *)h->tt_off, (void *)h->tt_slot, (void *)h->tt_first, (void *)h->tt_bits,
+                    (void *)h->tt_weight, (void *)h->tt_wt,
                     (void *)h->colkl, (void *)h->d_kls})
         if (p) (void)hipFree(p);
     for (hipEvent_t e : h->ev_soft)
@@ -3134,24 +3143,39 @@ int lstm_hip_decode_adaptive(lstm_hip_t *h, const uint8_t *code, const uint64_t 
 // the plan go to the device once and stay with the handle.  train: per window text_window (indices, rings, carry or zero
 // state), the handle's own forward path with the softmax launch in its text form, text_fold (the streams' bits), then the
 // adaptive train pass's sequence -- loss, backward, clip, update, no slide riding in the update launch.
+// Weighted texts (lstm_hip_set_train_texts_weighted, section 3.20): a float per byte goes up with the texts; text_window then
+// writes the window's weights beside ti and do_forward launches the softmax's weighted form.  Nothing else differs, and the
+// unweighted set is the weighted one with weight = NULL.
 static int drop_train_texts(lstm_hip_ctx *h) {
     HIP_TRY(hipStreamSynchronize(h->st));
-    for (void *p : {(void *)h->tt_text, (void *)h->tt_off, (void *)h->tt_slot, (void *)h->tt_first, (void *)h->tt_bits})
+    for (void *p : {(void *)h->tt_text, (void *)h->tt_off, (void *)h->tt_slot, (void *)h->tt_first, (void *)h->tt_bits,
+                    (void *)h->tt_weight, (void *)h->tt_wt})
         if (p) HIP_TRY(hipFree(p));
     h->tt_text = nullptr, h->tt_off = nullptr, h->tt_slot = nullptr, h->tt_first = nullptr, h->tt_bits = nullptr;
+    h->tt_weight = nullptr, h->tt_wt = nullptr;
     h->tt_streams = 0;
     h->tt_windows = h->tt_next = 0;
     return 0;
 }
 int lstm_hip_set_train_texts(lstm_hip_t *h, int32_t streams, const uint8_t *text, const uint64_t *text_off) {
+    return lstm_hip_set_train_texts_weighted(h, streams, text, text_off, nullptr);
+}
+int lstm_hip_set_train_texts_weighted(lstm_hip_t *h, int32_t streams, const uint8_t *text, const uint64_t *text_off,
+                                      const float *weight) {
     CHECK(h);
-    if (streams == 0 && !text && !text_off) return drop_train_texts(h);
+    if (streams == 0 && !text && !text_off && !weight) return drop_train_texts(h);
     std::vector<int32_t> slot;
     std::vector<int64_t> first(streams > 0 ? streams : 0);
     const int64_t windows = checked_plan("set_train_texts", h->cfg.S - 1, h->cfg.B, streams, text_off, nullptr, first.data(), &slot);
     if (windows < 0) return (int)windows;
     const uint64_t total = text_off[streams];
     if (total > 0 && !text) return fail(LSTM_HIP_EINVAL, "set_train_texts: null text with %llu bytes to read", (unsigned long long)total);
+    if (weight)
+        for (int32_t s = 0; s < streams; s++)
+            for (uint64_t i = text_off[s]; i < text_off[s + 1]; i++)
+                if (!(weight[i] >= 0.0f) || std::isinf(weight[i]))
+                    return fail(LSTM_HIP_EINVAL, "set_train_texts_weighted: the weight of byte %llu of stream %d is %g; a weight must be finite and >= 0",
+                                (unsigned long long)(i - text_off[s]), s, (double)weight[i]);
     if (int rc = drop_train_texts(h)) return rc;
     // (at least one element each, so that a set plan always has its five buffers)
     HIP_TRY(hipMalloc((void **)&h->tt_text, total ? total : 1));
@@ -3164,6 +3188,12 @@ int lstm_hip_set_train_texts(lstm_hip_t *h, int32_t streams, const uint8_t *text
     if (!slot.empty()) HIP_TRY(hipMemcpy(h->tt_slot, slot.data(), sizeof(int32_t) * slot.size(), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(h->tt_first, first.data(), sizeof(int64_t) * streams, hipMemcpyHostToDevice));
     HIP_TRY(hipMemset(h->tt_bits, 0, sizeof(double) * streams));
+    if (weight) {
+        HIP_TRY(hipMalloc((void **)&h->tt_weight, sizeof(float) * (total ? total : 1)));
+        HIP_TRY(hipMalloc((void **)&h->tt_wt, sizeof(float) * h->cfg.S * h->cfg.B));
+        if (total) HIP_TRY(hipMemcpy(h->tt_weight, weight, sizeof(float) * total, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemset(h->tt_wt, 0, sizeof(float) * h->cfg.S * h->cfg.B));
+    }
     h->tt_streams = streams;
     h->tt_windows = windows;
     h->tt_next = 0;
@@ -3211,6 +3241,7 @@ int lstm_hip_train_text_windows(lstm_hip_t *h, int64_t count, double learning_ra
     a.H = h->H, a.C = h->C;
     a.colloss = h->colloss, a.bits = h->tt_bits;
     a.S = h->cfg.S, a.B = B, a.N = h->cfg.N;
+    a.weight = h->tt_weight, a.wt = h->tt_wt; // (both null on unweighted texts)
     if (elapsed_ms) HIP_TRY(hipEventRecord(h->evt0, h->st));
     h->in_loop = true;
     LoopGuard guard{h};

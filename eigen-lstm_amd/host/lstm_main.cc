@@ -10,7 +10,7 @@
 //        [--adam-betas B1,B2] [--adam-eps E] [--weight-decay W] [--average ema|uniform] [--average-decay D]
 //        [--average-every K] [--average-start W] [--weight-drop R] [--weight-drop-seed K] [--test-streams K]
 //        [--test-warmup W] [--records] [--record-delim B] [--shuffle-seed K] [--label-smoothing E] [--teacher PREFIX]
-//        [--distill-alpha A] [--distill-temperature T] [--teacher-bf16] [--quiet]
+//        [--distill-alpha A] [--distill-temperature T] [--teacher-bf16] [--train-after B] [--quiet]
 //
 // stdout follows the reference: "Read N bytes (file)" (R/lstm.cc:398), the carriage-return progress
 // line (OV/lstm_eigen_opt/lstm.cc:320-331), the epoch summary (R/lstm.cc:284-291: GFLOP uses 2^30,
@@ -53,6 +53,10 @@
 // before its update.  --lr-warmup-windows, --average, --weight-drop, --clip-norm, --save and --load work as without it (the
 // saved cursors are those of the flat text, which --records does not move).  One GPU only; --stride and the last-step losses
 // do not apply.
+// --records --train-after B (B a byte value 0..255) is completion-only training (lstm_hip_set_train_texts_weighted): in every
+// record the bytes up to and including the first byte B are context -- fed, never a target that counts -- and every byte after
+// it is learned with weight 1; a record without B trains nothing.  The epoch line's prequential figure is then the weighted
+// bits over the weight-1 target bytes ("trained bytes").  Needs --records.
 #include "../../include/lstm_hip.h"
 
 // --label-smoothing E (0 <= E < 1) trains toward (1 - E) onehot + E / 256; --teacher PREFIX distils from the checkpoint
@@ -88,6 +92,8 @@
 #pragma weak lstm_hip_get_train_texts
 #pragma weak lstm_hip_train_text_windows
 #pragma weak lstm_hip_get_train_texts_bits
+// ... and --train-after
+#pragma weak lstm_hip_set_train_texts_weighted
 #include "eval_split.h"
 #include "checkpoint.h"
 #include "matrix_io.h"
@@ -146,6 +152,7 @@ struct Options {
     bool records = false;            // --records: train on the records of --data, each from its zero state
     int record_delim = 10;           // --record-delim
     uint32_t shuffle_seed = 0;       // --shuffle-seed
+    int train_after = -1;            // --train-after: the separator byte of completion-only training, -1: every byte is learned
     double smoothing = 0.0;          // --label-smoothing
     std::string teacher;             // --teacher: checkpoint prefix (empty: none)
     double distill_alpha = 0.5;      // --distill-alpha
@@ -359,6 +366,11 @@ Options parse(int argc, char **argv) {
             if (k > 4294967295L) die("--shuffle-seed is too large");
             o.shuffle_seed = (uint32_t)k;
             records_opt = a;
+        } else if (a == "--train-after") {
+            const long b = whole_number(a, val(), 0);
+            if (b > 255) die("--train-after needs a byte value 0..255");
+            o.train_after = (int)b;
+            records_opt = a;
         }
         else if (a == "--label-smoothing") {
             const std::string v = val();
@@ -392,7 +404,7 @@ Options parse(int argc, char **argv) {
                    "            --weight-decay W --average ema|uniform --average-decay D --average-every K --average-start W\n"
                    "            --weight-drop R --weight-drop-seed K --test-streams K --test-warmup W\n"
                    "            --records --record-delim B --shuffle-seed K --label-smoothing E --teacher PREFIX\n"
-                   "            --distill-alpha A --distill-temperature T --teacher-bf16 --quiet]\n");
+                   "            --distill-alpha A --distill-temperature T --teacher-bf16 --train-after B --quiet]\n");
             exit(0);
         } else if (a.rfind("--", 0) == 0) die("unknown option " + a);
         else pos.push_back(a);
@@ -428,6 +440,8 @@ Options parse(int argc, char **argv) {
                       lstm_hip_train_text_windows == nullptr || lstm_hip_get_train_texts_bits == nullptr))
         die("--records: the loaded liblstm_hip has no lstm_hip_text_plan / lstm_hip_set_train_texts / lstm_hip_get_train_texts / "
             "lstm_hip_train_text_windows / lstm_hip_get_train_texts_bits");
+    if (o.train_after >= 0 && lstm_hip_set_train_texts_weighted == nullptr)
+        die("--train-after: the loaded liblstm_hip has no lstm_hip_set_train_texts_weighted");
     if (o.records && o.gpus != 1) die("--records runs on one GPU (every rank would have to run the same number of windows)");
     if (o.records && o.stride != 1) die("--records does not take --stride (a text window always advances by seq - 1)");
     if (o.records && (o.last_step_loss || o.last_step_bits)) die("--records reports the all-steps loss only");
@@ -672,6 +686,9 @@ int run_rank(const Options &o, int rank, int up, int down) {
     std::vector<uint8_t> rec_text(o.records ? length : 0);
     std::vector<uint64_t> rec_off(n_rec + 1, 0);
     std::vector<int64_t> rec_first(n_rec);
+    // --train-after: a weight per byte of rec_text, and per record the offset of its first separator (its length: none)
+    std::vector<float> rec_weight(o.train_after >= 0 ? length : 0);
+    std::vector<uint64_t> rec_sep(o.train_after >= 0 ? n_rec : 0);
     // scored bytes (steps) in the first w windows of the epoch's plan
     auto steps_in = [&](long w) {
         double steps = 0.0;
@@ -683,6 +700,19 @@ int run_rank(const Options &o, int rank, int up, int down) {
         }
         return steps;
     };
+    // ... and the weight-1 targets among them (--train-after): the scored bytes behind the record's first separator
+    auto trained_in = [&](long w) {
+        double trained = 0.0;
+        for (size_t r = 0; r < n_rec; r++) {
+            const uint64_t len = rec_off[r + 1] - rec_off[r];
+            if (rec_first[r] < 0 || len < 2) continue;
+            const int64_t room = ((int64_t)w - rec_first[r]) * (S - 1);
+            const int64_t scored = std::min<int64_t>(std::max<int64_t>(room, 0), (int64_t)len - 1); // targets: bytes 1 .. scored
+            trained += (double)std::max<int64_t>(scored - (int64_t)rec_sep[r], 0);
+        }
+        return trained;
+    };
+    auto chars_in = [&](long w) { return o.train_after >= 0 ? trained_in(w) : steps_in(w); };
     std::vector<float> hs((size_t)N * o.B), cs((size_t)N * o.B);
     std::vector<double> losses, norms, kls;
 
@@ -701,6 +731,14 @@ int run_rank(const Options &o, int rank, int up, int down) {
                 std::copy(data.begin() + a, data.begin() + b, rec_text.begin() + rec_off[r]);
                 rec_off[r + 1] = rec_off[r] + (b - a);
             }
+            if (o.train_after >= 0) { // (the weights of lstm_hip.completion_weights: 1 behind the record's first separator)
+                for (size_t r = 0; r < n_rec; r++) {
+                    const uint8_t *b = rec_text.data() + rec_off[r], *e = rec_text.data() + rec_off[r + 1];
+                    rec_sep[r] = (uint64_t)(std::find(b, e, (uint8_t)o.train_after) - b);
+                    for (uint64_t i = 0; i < (uint64_t)(e - b); i++) rec_weight[rec_off[r] + i] = i > rec_sep[r] ? 1.0f : 0.0f;
+                }
+                CK(lstm_hip_set_train_texts_weighted(h, (int32_t)n_rec, rec_text.data(), rec_off.data(), rec_weight.data()));
+            } else
             CK(lstm_hip_set_train_texts(h, (int32_t)n_rec, rec_text.data(), rec_off.data()));
             int64_t plan_windows = 0;
             CK(lstm_hip_get_train_texts(h, &plan_windows, nullptr));
@@ -761,7 +799,7 @@ int run_rank(const Options &o, int rank, int up, int down) {
             // (local surprisal sum / GLOBAL batch); the ranks exchange sums once per epoch, not here, so the running figure is
             // the lead's share scaled by the rank count -- an estimate over its streams, labelled as what the reference prints
             if (lead && o.test_every > 0 && now() - last_test > o.test_every)
-                test_and_log(o.records ? epoch_loss * (double)o.B / std::max(steps_in(i), 1.0)
+                test_and_log(o.records ? epoch_loss * (double)o.B / std::max(chars_in(i), 1.0)
                                        : epoch_loss * (double)o.gpus / ((double)S * (double)i),
                              (i * flops_per_iteration / std::pow(2.0, 30)) / (now() - t0));
             if (lead && !o.quiet) {
@@ -781,7 +819,9 @@ int run_rank(const Options &o, int rank, int up, int down) {
             const double rows = (double)(S - 1) * o.B * windows_per_epoch;
             const double chars = o.records ? steps_in(windows_per_epoch) : rows; // (a text window's rows are not all filled)
             // R/lstm.cc:290: loss/(S*length); --records: the prequential bits of the epoch over its scored bytes
-            const double train_bits = o.records ? epoch_loss * (double)o.B / std::max(chars, 1.0)
+            // (--train-after: the weighted bits over the weight-1 target bytes)
+            const double trained = o.records ? chars_in(windows_per_epoch) : 0.0;
+            const double train_bits = o.records ? epoch_loss * (double)o.B / std::max(trained, 1.0)
                                                 : epoch_loss / ((double)S * (double)(windows_per_epoch + S));
             printf("\n====================================================================================\n");
             if (teacher)
@@ -793,8 +833,8 @@ int run_rank(const Options &o, int rank, int up, int down) {
                    (flops_per_iteration * windows_per_epoch / std::pow(2.0, 30)) / epoch_time,
                    train_bits);
             if (o.records)
-                printf("records: %zu texts in %ld windows, %.1f%% of the rows filled, %.5f prequential bits/char over %.0f bytes\n", n_rec,
-                       windows_per_epoch, 100.0 * chars / rows, train_bits, chars);
+                printf("records: %zu texts in %ld windows, %.1f%% of the rows filled, %.5f prequential bits/char over %.0f %sbytes\n", n_rec,
+                       windows_per_epoch, 100.0 * chars / rows, train_bits, trained, o.train_after >= 0 ? "trained " : "");
             printf("chars/s through fwd+BPTT = %.1f (%ld windows, %d GPU%s)\n", chars / epoch_time, windows_per_epoch, o.gpus,
                    o.gpus > 1 ? "s" : "");
             if (o.clip_norm > 0.0)

@@ -103,7 +103,7 @@ SYMBOLS = [
     "lstm_hip_dfa_regex", "lstm_hip_dfa_intersect", "lstm_hip_generate_accepting",
     "lstm_hip_eval_plan", "lstm_hip_eval_texts",
     "lstm_hip_text_plan", "lstm_hip_set_train_texts", "lstm_hip_get_train_texts", "lstm_hip_train_text_windows",
-    "lstm_hip_get_train_texts_bits",
+    "lstm_hip_get_train_texts_bits", "lstm_hip_set_train_texts_weighted",
     "lstm_hip_set_soft_targets", "lstm_hip_get_soft_targets", "lstm_hip_get_teacher_kl",
 ]
 
@@ -211,6 +211,23 @@ def eval_split_pieces(length, pieces, warm=0):
         raise LstmHipError(f"eval_split: need >= 2 bytes, >= 1 piece, warm >= 0 (got {length}, {pieces}, {warm})")
     a = [1 + i * (length - 1) // pieces for i in range(pieces + 1)]
     return [(max(0, a[i] - 1 - warm), a[i + 1], a[i] - max(0, a[i] - 1 - warm)) for i in range(pieces)]
+
+
+def completion_weights(texts, sep):
+    """The weights of completion-only training for Lstm.set_train_texts(texts, weights=...): per text a float32 array of its
+    length, 1.0 for every byte after the first `sep` byte (a byte value 0..255), 0.0 for the rest -- the prompt and the
+    separator itself are context, the completion is learned.  A text without `sep` is all zeros.  Needs no device."""
+    sep = int(sep)
+    if not 0 <= sep <= 255:
+        raise LstmHipError(f"completion_weights: sep must be a byte value 0..255 (got {sep})")
+    out = []
+    for t in _bytes_list(texts):
+        w = np.zeros(t.size, np.float32)
+        at = np.flatnonzero(t == sep)
+        if at.size:
+            w[at[0] + 1:] = 1.0
+        out.append(w)
+    return out
 
 
 def weight_drop_mask(N, rate, seed=0, t=0):
@@ -589,17 +606,34 @@ class Lstm:
         return losses
 
     # ---- training on separate texts, each from its zero state (lstm_hip_set_train_texts) -------------
-    def set_train_texts(self, texts):
+    def set_train_texts(self, texts, weights=None):
         """lstm_hip_set_train_texts: the texts (bytes or uint8 arrays, one stream each) the next train_text_windows calls
         train on, placed on the B lanes by text_plan(S - 1, B, lengths).  Zeroes the streams' bits and starts at window 0;
-        None or an empty list drops the texts.  Returns the plan's number of windows."""
+        None or an empty list drops the texts.  Returns the plan's number of windows.
+        weights (lstm_hip_set_train_texts_weighted): per text a float array of the text's length -- entry i weighs byte i as
+        a target in the loss and the gradient -- or a scalar for the whole text; completion_weights(texts, sep) makes those
+        of completion-only training.  None is the unweighted call."""
         if not texts:
             _chk(self.lib.lstm_hip_set_train_texts(self._h, C.c_int32(0), None, None))
             self._train_streams = 0
             return 0
         parts = _bytes_list(texts)
         data, off = _offsets(parts)
-        _chk(self.lib.lstm_hip_set_train_texts(self._h, C.c_int32(len(parts)), _ptr(data, C.c_uint8), _ptr(off, C.c_uint64)))
+        if weights is None:
+            _chk(self.lib.lstm_hip_set_train_texts(self._h, C.c_int32(len(parts)), _ptr(data, C.c_uint8), _ptr(off, C.c_uint64)))
+        else:
+            if len(weights) != len(parts):
+                raise LstmHipError(f"set_train_texts: {len(weights)} weight arrays for {len(parts)} texts")
+            ws = []
+            for s, (t, w) in enumerate(zip(parts, weights)):
+                w = np.asarray(w, np.float32)
+                w = np.full(t.size, w, np.float32) if w.ndim == 0 else w.ravel()
+                if w.size != t.size:
+                    raise LstmHipError(f"set_train_texts: text {s} has {t.size} bytes and {w.size} weights")
+                ws.append(w)
+            wdata = np.ascontiguousarray(np.concatenate(ws) if off[-1] > 0 else np.zeros(1, np.float32))
+            _chk(self.lib.lstm_hip_set_train_texts_weighted(self._h, C.c_int32(len(parts)), _ptr(data, C.c_uint8),
+                                                            _ptr(off, C.c_uint64), _ptr(wdata, C.c_float)))
         self._train_streams = len(parts)
         return self.train_texts_progress()[0]
 

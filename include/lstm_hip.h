@@ -798,10 +798,41 @@ int lstm_hip_eval_texts(lstm_hip_t *h, int32_t streams, const uint8_t *text, con
  *      communicator on the handle (every rank would have to run the same number of windows); a loss mode other than
  *      LSTM_HIP_LOSS_ALL_STEPS_BITS.  LSTM_HIP_EINVAL: count < 0 or past the plan's end; learning_rate negative or not
  *      finite; for set: streams < 1, more than 4096 lanes (B), offsets missing, not starting at 0 or decreasing, text NULL
- *      with bytes to read. */
+ *      with bytes to read.
+ *
+ *      Weights per byte: completion-only training, importance weights.
+ *      lstm_hip_set_train_texts_weighted is lstm_hip_set_train_texts with a float per byte: weight[text_off[s] + i] is the
+ *      weight of byte i of stream s AS A TARGET, so the weight of step j (feeds byte j, target byte j + 1) is entry j + 1,
+ *      indexed like the surprisal output of lstm_hip_eval_texts.  Byte 0 of a stream is never a target: its entry is
+ *      validated and never used.  The weights are uploaded once with the texts and stay with the handle.
+ *      lstm_hip_set_train_texts(h, ...) is this call with weight = NULL, which is the unweighted set above: its launches and
+ *      its bytes.  streams = 0 with all three pointers NULL drops the texts; a second set replaces the first, weighted or
+ *      not; plan, placement, next = 0 and the zeroed bits are the same.  With weights set a window is everything above, and
+ *        dy         a column with a target k and the weight w gets dy = w * (p - e_k): one fp32 multiply per element behind
+ *                   the subtraction.  A column with w == 0 gets dy = +0.0f in every element and a surprisal of 0.0f BY
+ *                   SELECTION, not by multiplication, so a context byte whose p is NaN or inf poisons nothing.  A column
+ *                   without a target (ti < 0) is as above: dy = 0, surprisal 0.  A byte of weight 0 inside a text is NOT a
+ *                   text's end: its row adds nothing of its own, and the gradients of the later rows flow back through its
+ *                   state -- it is context.
+ *        loss       the column's figure is w * surprisal, one fp32 multiply of the float the unweighted window writes
+ *                   (-log2f(p_k), or the log-sum-exp form under LSTM_HIP_STABLE_SOFTMAX).  losses[i] and
+ *                   lstm_hip_get_train_texts_bits are therefore the WEIGHTED figures, folded by the same launches in the
+ *                   same order; nothing is divided by the weights' sum (callers divide).  The probabilities
+ *                   (lstm_hip_get_activations) stay the plain p.
+ *        identity   w == 1.0f everywhere gives the unweighted call's bytes: a multiply by 1 is exact.
+ *        gradients  dby = rowsum(dy), dWhy, the clip norm and the update see the weighted dy; nothing else changes.  A window
+ *                   whose weights are all 0 still runs one update (the counters advance); with Adagrad its parameters and
+ *                   memory come out byte-identical.
+ *      The softmax launch of a weighted window has its own statistics row, softmax_loss_dy_weighted (softmax_loss_dy_text
+ *      stays 0).  The window's weights are scratch: they show in no later call.
+ *      Refused with LSTM_HIP_EINVAL, nothing launched, a previous set kept: an entry of weight[0 .. text_off[streams]) that
+ *      is negative, NaN or infinite (the message names the stream and the byte's offset in it), and everything
+ *      lstm_hip_set_train_texts refuses, in its words.  lstm_hip_train_text_windows refuses what it refuses above. */
 int64_t lstm_hip_text_plan(int32_t steps, int32_t lanes, int32_t streams, const uint64_t *text_off, int32_t *lane_of,
                            int64_t *first_window);
 int lstm_hip_set_train_texts(lstm_hip_t *h, int32_t streams, const uint8_t *text, const uint64_t *text_off);
+int lstm_hip_set_train_texts_weighted(lstm_hip_t *h, int32_t streams, const uint8_t *text, const uint64_t *text_off,
+                                      const float *weight /* [text_off[streams]], indexed like text; NULL: unweighted */);
 int lstm_hip_get_train_texts(lstm_hip_t *h, int64_t *windows, int64_t *next);   /* plan length, next window to run */
 int lstm_hip_train_text_windows(lstm_hip_t *h, int64_t count, double learning_rate, double *losses, float *elapsed_ms);
 int lstm_hip_get_train_texts_bits(lstm_hip_t *h, double *bits /* [streams] */);
