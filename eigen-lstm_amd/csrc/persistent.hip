@@ -1696,7 +1696,14 @@ struct BwdhArgs {
     int ring_base, S, B, cfg;
     unsigned long long *stamps;
 };
-constexpr int BWDH_SYNC = 16; // words at the head of the LDS block: abort, -, -, s_stage[2], s_dy, s_ol, s_tab, s_done[2][2], s_loc[2], s_wy, consumed
+constexpr int BWDH_SYNC = 16; // words at the head of the LDS block: abort, s_wyc[0], s_wyc[1], s_stage[2], s_dy, s_ol, s_tab, s_done[2][2], s_loc[2], s_wy, s_wyc[2]
+// s_wyc[k]: product waves that have consumed slot k of the dy / h ring of the dWhy sums (bwdh_output_layer stages step tu
+// into slot tu % 3), 8 a use of the slot.  One count per SLOT, not one for the ring: a product wave runs up to two steps
+// ahead of another wave of its workgroup (its step t-2 needs the others' products of step t, not their dWhy share of it,
+// which comes behind them), so in one running count its early releases stood in for the late wave's missing one and the
+// slot was staged over before the late wave had read it.  A release into a slot's own count needs the slot staged for that
+// step, which needs the wait for the step before: nothing can stand in.
+__device__ __forceinline__ unsigned *bwdh_wy_count(unsigned *sync_, int slot) { return sync_ + (slot == 2 ? 15 : 1 + slot); }
 #define BWDH_COMMON(p)                                                                                                          \
     constexpr int N = N_, G4 = 4 * N, Kw = N / 2, NL = Kw / 64; /* NL 16-byte loads per lane, half and step */                  \
     static_assert(N == 512 || N == 256, "two-half backward form: hidden 512 or 256");                                           \
@@ -1873,8 +1880,9 @@ template <int N_, bool FUSE, bool STAMP> __device__ __forceinline__ void bwdh_ou
             }
         }
         HSTAMP(11, 13)
-        if (FUSE) { // dy_tu and h_tu for the dWhy sums of the product waves (three-deep ring; sync_[15]: waves that have consumed)
-            if (tu + 3 <= S - 1 && !lds_wait(&sync_[15], 8u * (unsigned)(S - tu - 3))) {
+        if (FUSE) { // dy_tu and h_tu for the dWhy sums of the product waves (three-deep ring; s_wyc: waves that have consumed)
+            // slot tu % 3 held steps tu + 3, tu + 6, ...: (S - 1 - tu) / 3 uses, every one consumed by all eight waves
+            if (tu + 3 <= S - 1 && !lds_wait(bwdh_wy_count(sync_, tu % 3), 8u * (unsigned)((S - 1 - tu) / 3))) {
                 give_up();
                 break;
             }
@@ -2035,7 +2043,7 @@ template <int N_, bool FUSE, bool STAMP> __device__ __forceinline__ void bwds_pr
     // memory pipe.  Staged by wave 10, whose dW table work runs late at the lowest priority, the product waves waited for
     // it: 300 us.)
     float hq[8], dq[8]; // h_tu[unit l & 15][column c] (zero for a padding column: no dWhy from it), dy_tu[64 wmg + l][column c]
-    unsigned *s_wy = sync_ + 14;   // steps staged by wave 10 (S - tu); sync_[15]: product waves that have consumed, 8 a step
+    unsigned *s_wy = sync_ + 14;   // steps staged by wave 11 (S - tu); s_wyc[slot]: product waves that have consumed, 8 a use
     float *wyS = red + 1024;       // [step % 3][8 columns][256 rows | 16 units]: beside the dg hand-off buffers in `red`
     auto wfetch = [&](int tu) -> bool {
         if (!lds_wait(s_wy, (unsigned)(S - tu))) return false;
@@ -2047,9 +2055,9 @@ template <int N_, bool FUSE, bool STAMP> __device__ __forceinline__ void bwds_pr
         }
         return true;
     };
-    auto wrelease = [&]() {
+    auto wrelease = [&](int tu) { // this wave holds step tu's operands in registers: its slot's own count (BWDH_SYNC)
         asm volatile("" ::: "memory");
-        if (l == 0) __hip_atomic_fetch_add(&sync_[15], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (l == 0) __hip_atomic_fetch_add(bwdh_wy_count(sync_, tu % 3), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     };
     auto wstep = [&]() {
 #pragma unroll
@@ -2124,13 +2132,13 @@ template <int N_, bool FUSE, bool STAMP> __device__ __forceinline__ void bwds_pr
                 break;
             }
             if (!(cfg & 8)) wstep();
-            wrelease();
+            wrelease(t);
         }
     }
     if (FUSE && live) { // step 1 (or S - 1 = 1: the only step)
         if (wfetch(1)) {
             if (!(cfg & 8)) wstep();
-            wrelease();
+            wrelease(1);
         } else
             give_up();
     }
@@ -2201,8 +2209,22 @@ template <int N_, bool FUSE, bool STAMP> __device__ __forceinline__ void bwds_el
                 bool gd = true;
 #pragma unroll
                 for (int i = 0; i < NLD; i++) v[i] = ld_sc1(rQ, off + i * (4 * 64 * (int)sizeof(float)));
+                if (!tagged_) {
+                    // HX_SENT is the largest uint32: "no word is the sentinel" is "the unsigned maximum is not" (v_max3_u32).
+                    // Taken in load order, every piece but the last is folded in while the later loads are in flight: four
+                    // instructions behind the last load (word by word: 22).  tests/test_chain_schedule_cpu.py: same predicate
+                    unsigned m = max(__float_as_uint(v[0].x), __float_as_uint(v[0].y));
+                    m = max(max(m, __float_as_uint(v[0].z)), __float_as_uint(v[0].w));
 #pragma unroll
-                for (int i = 0; i < NLD; i++) gd = gd && (tagged_ ? tag_ready(v[i], ph) : hx_ready(v[i]));
+                    for (int i = 1; i < NLD; i++) {
+                        m = max(max(m, __float_as_uint(v[i].x)), __float_as_uint(v[i].y));
+                        m = max(max(m, __float_as_uint(v[i].z)), __float_as_uint(v[i].w));
+                    }
+                    gd = m != HX_SENT;
+                } else {
+#pragma unroll
+                    for (int i = 0; i < NLD; i++) gd = gd && tag_ready(v[i], ph);
+                }
                 if (__all(gd)) {
                     ok = true;
                     break;
@@ -2350,7 +2372,7 @@ template <int N_, bool FUSE, bool STAMP = false> __global__ __launch_bounds__(BW
         s_stage[0] = s_stage[1] = 0;
         *s_dy = *s_ol = 0;
         *s_tab = 0;
-        sync_[12] = sync_[13] = sync_[14] = sync_[15] = 0;
+        sync_[1] = sync_[2] = sync_[12] = sync_[13] = sync_[14] = sync_[15] = 0;
         if (XCD_LOCAL) {
             __hip_atomic_store(xcc_tab + kb, (epoch << 4) | (__builtin_amdgcn_s_getreg(6164) & 15u), __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT);
