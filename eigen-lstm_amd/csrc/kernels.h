@@ -339,6 +339,15 @@ void adagrad(const AdagradJob &job, hipStream_t st);
 int grad_norm_parts(size_t n);
 void grad_sumsq(const AdagradJob &job, double *part, hipStream_t st);
 void grad_norm(const double *part, int n_parts, double max_norm, double *norm_out, float *coef_out, hipStream_t st);
+// ---- gradient accumulation (lstm_hip_set_grad_accumulation), one launch per window in place of (all but the last window of a
+// cycle) or in front of (the last) the update: g is the window's gradient of `job` as grad_sumsq forms it -- job.dP, or the
+// fold pieces job.gpart / job.slabs summed in the same order -- and acc the handle's accumulator of job.n floats.
+//   GRAD_ACC_FIRST  acc = g            and g is left in dP
+//   GRAD_ACC_ADD    acc = acc + g      and g is left in dP
+//   GRAD_ACC_LAST   dP = acc + g, then (scale) dP = dP * w: fp32, separately rounded, no FMA; acc is only read
+// The update's grid of 256-thread workgroups over float4; plain vector loads and stores, no LDS, no atomics.
+enum { GRAD_ACC_FIRST = 0, GRAD_ACC_ADD = 1, GRAD_ACC_LAST = 2 };
+void grad_accumulate(const AdagradJob &job, float *acc, int mode, bool scale, float w, hipStream_t st);
 int fwd_halves_bf16_units(int N);
 
 // ---- window builder on the device (OV/lstm_eigen_opt/lstm.cc:190-213): x/target rings + flat copies,

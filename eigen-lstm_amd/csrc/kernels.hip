@@ -1716,29 +1716,39 @@ __device__ __forceinline__ double block_sum256(double v, double *red) {
     __syncthreads();
     return red[0];
 }
+// The window's summed gradient at float4 index i of the flat block: the one text for it outside k_adagrad<FOLD>, shared by
+// k_grad_sumsq and k_grad_accumulate.  With a fold the pieces are added here, first piece first; the by range and a dU that is
+// already final are read from dP.  `folded` says that the value was summed here, i.e. that dP does not hold it yet.
+__device__ __forceinline__ float4 grad_fold_at(const float *dP, size_t i, size_t u_off4, size_t u_n4, const GradFold &fold,
+                                               bool &folded) {
+    float4 d;
+    const bool in_u = i >= u_off4 && i < u_off4 + u_n4;
+    folded = fold.gpart != nullptr && i < fold.by_off4 && !(in_u && fold.slabs == nullptr);
+    if (folded) {
+        const float *src = in_u ? fold.slabs + 4 * (i - u_off4) : fold.gpart + 4 * i;
+        const size_t stride = in_u ? fold.slab_stride : fold.group_stride;
+        const int n = in_u ? fold.n_slabs : fold.n_groups;
+        d = *reinterpret_cast<const float4 *>(src);
+        for (int z = 1; z < n; z++) {
+            const float4 q = *reinterpret_cast<const float4 *>(src + (size_t)z * stride);
+            d.x += q.x;
+            d.y += q.y;
+            d.z += q.z;
+            d.w += q.w;
+        }
+    } else {
+        d = reinterpret_cast<const float4 *>(dP)[i];
+    }
+    return d;
+}
 __global__ __launch_bounds__(256) void k_grad_sumsq(float *__restrict__ dP, size_t n4, size_t u_off4, size_t u_n4, GradFold fold,
                                                     double *__restrict__ part) {
     __shared__ double red[256];
     double s = 0.0;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
-        float4 d;
-        const bool in_u = i >= u_off4 && i < u_off4 + u_n4;
-        if (fold.gpart != nullptr && i < fold.by_off4 && !(in_u && fold.slabs == nullptr)) {
-            const float *src = in_u ? fold.slabs + 4 * (i - u_off4) : fold.gpart + 4 * i;
-            const size_t stride = in_u ? fold.slab_stride : fold.group_stride;
-            const int n = in_u ? fold.n_slabs : fold.n_groups;
-            d = *reinterpret_cast<const float4 *>(src);
-            for (int z = 1; z < n; z++) {
-                const float4 q = *reinterpret_cast<const float4 *>(src + (size_t)z * stride);
-                d.x += q.x;
-                d.y += q.y;
-                d.z += q.z;
-                d.w += q.w;
-            }
-            reinterpret_cast<float4 *>(dP)[i] = d;
-        } else {
-            d = reinterpret_cast<const float4 *>(dP)[i];
-        }
+        bool folded;
+        const float4 d = grad_fold_at(dP, i, u_off4, u_n4, fold, folded);
+        if (folded) reinterpret_cast<float4 *>(dP)[i] = d;
         s += (double)d.x * (double)d.x;
         s += (double)d.y * (double)d.y;
         s += (double)d.z * (double)d.z;
@@ -1774,6 +1784,67 @@ void grad_sumsq(const AdagradJob &j, double *part, hipStream_t st) {
 }
 void grad_norm(const double *part, int n_parts, double max_norm, double *norm_out, float *coef_out, hipStream_t st) {
     hipLaunchKernelGGL(k_grad_norm, dim3(1), dim3(256), 0, st, part, n_parts, max_norm, norm_out, coef_out);
+}
+
+// ------------------------------------------------------------------------------------------------
+// grad_accumulate: one window of gradient accumulation (lstm_hip_set_grad_accumulation; kernels.h).
+// Grid-stride over the flat block in float4, lanes of a wave on consecutive float4.  g is the window's gradient exactly as
+// k_grad_sumsq forms it (grad_fold_at); then, per element and in fp32,
+//   FIRST  acc = g                      (a copy)
+//   ADD    acc = acc + g                (one add)
+//   LAST   dP  = acc + g, then * w when SCALE: two separately rounded operations, plain expressions under this file's fp
+//          contract(off), so v_add and v_mul in the code object and no FMA; acc is not written (the next cycle starts with FIRST)
+// FIRST and ADD store a g that was summed here to dP (where it was read from dP it is there already), so the gradient block
+// holds the window's own gradient afterwards.  Plain vector loads and stores; no LDS, no atomics.
+// ------------------------------------------------------------------------------------------------
+template <int MODE, bool SCALE>
+__global__ __launch_bounds__(256) void k_grad_accumulate(float *__restrict__ dP, float *__restrict__ acc, size_t n4, size_t u_off4,
+                                                         size_t u_n4, GradFold fold, float w) {
+    float4 *__restrict__ acc4 = reinterpret_cast<float4 *>(acc);
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
+        bool folded;
+        const float4 g = grad_fold_at(dP, i, u_off4, u_n4, fold, folded);
+        if (MODE == GRAD_ACC_LAST) {
+            const float4 a = acc4[i];
+            float4 d;
+            d.x = a.x + g.x;
+            d.y = a.y + g.y;
+            d.z = a.z + g.z;
+            d.w = a.w + g.w;
+            if (SCALE) {
+                d.x = d.x * w;
+                d.y = d.y * w;
+                d.z = d.z * w;
+                d.w = d.w * w;
+            }
+            reinterpret_cast<float4 *>(dP)[i] = d;
+        } else {
+            float4 a = g;
+            if (MODE == GRAD_ACC_ADD) {
+                a = acc4[i];
+                a.x = a.x + g.x;
+                a.y = a.y + g.y;
+                a.z = a.z + g.z;
+                a.w = a.w + g.w;
+            }
+            acc4[i] = a;
+            if (folded) reinterpret_cast<float4 *>(dP)[i] = g;
+        }
+    }
+}
+void grad_accumulate(const AdagradJob &j, float *acc, int mode, bool scale, float w, hipStream_t st) {
+    const GradFold fold{j.gpart, j.n_groups, j.group_stride, j.by_off / 4, j.slabs, j.n_slabs, j.slab_stride};
+    const size_t n4 = j.n / 4;
+    int blocks = (int)((n4 + 255) / 256); // the update's own grid (adagrad)
+    if (blocks > 2048) blocks = 2048;
+#define ACC_GO(M, S_)                                                                                                         \
+    hipLaunchKernelGGL((k_grad_accumulate<M, S_>), dim3(blocks), dim3(256), 0, st, j.dP, acc, n4, j.u_off / 4, (size_t)j.N * j.N, \
+                       fold, w)
+    if (mode == GRAD_ACC_FIRST) ACC_GO(GRAD_ACC_FIRST, false);
+    else if (mode == GRAD_ACC_ADD) ACC_GO(GRAD_ACC_ADD, false);
+    else if (scale) ACC_GO(GRAD_ACC_LAST, true);
+    else ACC_GO(GRAD_ACC_LAST, false);
+#undef ACC_GO
 }
 
 // ------------------------------------------------------------------------------------------------

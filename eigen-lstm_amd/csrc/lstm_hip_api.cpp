@@ -64,6 +64,7 @@ enum KernelId {
     K_COUNT_BASE, // the ids above have their names in kKernelNames, the ids from here on in kKernelNamesMore (kernel_name)
     K_SOFTMAX_SOFT = K_COUNT_BASE, // K_SOFTMAX's launch with soft targets (lstm_hip_set_soft_targets): label smoothing, a teacher's term
     K_SOFTMAX_WEIGHTED,            // K_SOFTMAX_TEXT's launch with a weight per target byte (lstm_hip_set_train_texts_weighted)
+    K_GRAD_ACCUMULATE,             // gradient accumulation (lstm_hip_set_grad_accumulation): a window's gradient into the accumulator
     K_COUNT
 };
 const char *const kKernelNames[K_COUNT] = { // (K_COUNT_BASE names; the rows behind them stay null)
@@ -71,7 +72,7 @@ const char *const kKernelNames[K_COUNT] = { // (K_COUNT_BASE names; the rows beh
     "dW_db", "loss_dby", "adagrad", "slide", "allreduce", "fwd_persistent", "bwd_persistent", "gen_head", "side_sums",
     "gemm_dU_halves", "grad_sumsq", "grad_norm", "adam", "code_head", "block_window", "text_window", "text_fold",
     "softmax_loss_dy_text", "beam_head", "beam_backtrack", "score_head"};
-const char *const kKernelNamesMore[K_COUNT - K_COUNT_BASE] = {"softmax_soft", "softmax_loss_dy_weighted"};
+const char *const kKernelNamesMore[K_COUNT - K_COUNT_BASE] = {"softmax_soft", "softmax_loss_dy_weighted", "grad_accumulate"};
 inline const char *kernel_name(int id) { return id < K_COUNT_BASE ? kKernelNames[id] : kKernelNamesMore[id - K_COUNT_BASE]; }
 
 // ---- RCCL, loaded on first use so single-GPU users never touch it --------------------------
@@ -180,6 +181,10 @@ struct lstm_hip_ctx {
     float *clip_coef = nullptr;  // the coefficient of the step under way
     int64_t norms_cap = 0;       // d_norms holds this many
     int64_t norms_n = -1;        // steps of the last adagrad / train_windows call that recorded norms; -1: clipping was off
+    int64_t call_updates = 0;    // updates launched by the call under way (do_adagrad): the slot of d_norms the next one writes
+    // gradient accumulation (lstm_hip_set_grad_accumulation): acc_every 1 = off
+    int32_t acc_every = 1, acc_mean = 0, acc_pending = 0; // windows per update / divide by it / windows summed in `acc` so far
+    float *acc = nullptr;        // their summed gradient (flat block, internal width); allocated when accumulation is first turned on
     // the update rule (lstm_hip_set_optimizer): Adagrad, or Adam with m in `mem` and v in adam_v
     int opt_kind = LSTM_HIP_OPT_ADAGRAD;
     double beta1 = 0.0, beta2 = 0.0, adam_eps = 0.0, weight_decay = 0.0;
@@ -776,7 +781,9 @@ int average_step(lstm_hip_ctx *h) {
 // the fp32 block the inference calls read (lstm_hip_set_inference_source); training never asks
 const float *infer_block(const lstm_hip_ctx *h) { return h->infer_src == LSTM_HIP_SRC_AVERAGE ? h->avg : h->P; }
 
-// norm_idx: the slot of d_norms this step's norm goes to (clipping on only)
+// One micro-window's gradient: the update, or under gradient accumulation (acc_every > 1) the accumulate launch and, at
+// the last window of a cycle only, the update on the accumulated block.
+// norm_idx: the slot of d_norms this step's norm goes to (clipping on only): the index of the update within the call
 int do_adagrad(lstm_hip_ctx *h, double lr, int64_t norm_idx) {
     const EnginePlan &p = h->plan;
     const int N = h->cfg.N;
@@ -807,6 +814,18 @@ int do_adagrad(lstm_hip_ctx *h, double lr, int64_t norm_idx) {
     } else if (h->tail)
         return fail(LSTM_HIP_ESTATE, "update launch: a loss tail without a pending gradient fold");
     h->tail = false;
+    if (h->acc_every > 1) { // (loop_window keeps the tail off: the loss and dby are in place, keep_outputs is true)
+        const bool last = h->acc_pending + 1 == h->acc_every;
+        const int mode = last ? GRAD_ACC_LAST : h->acc_pending == 0 ? GRAD_ACC_FIRST : GRAD_ACC_ADD;
+        RUN(K_GRAD_ACCUMULATE, grad_accumulate(job, h->acc, mode, h->acc_mean != 0, (float)(1.0 / (double)h->acc_every), h->st));
+        if (!last) { // no update: the slide, if any, is the next window's own launch
+            h->acc_pending++;
+            h->carry_slide = false;
+            return 0;
+        }
+        h->acc_pending = 0;
+        job.gpart = nullptr, job.slabs = nullptr; // the gradient block holds the cycle's sum: the update reads it plainly
+    }
     job.slide = h->carry_slide ? &slide : nullptr;
     job.quad = p.adagrad_quad;
     if (h->clip_max > 0.0) { // norm of the whole (summed, all-reduced) block first; the fold moves into k_grad_sumsq
@@ -829,6 +848,7 @@ int do_adagrad(lstm_hip_ctx *h, double lr, int64_t norm_idx) {
     }
     RUN(adam ? K_ADAM : K_ADAGRAD, adagrad(job, h->st));
     h->opt_steps++;
+    h->call_updates++;
     if (job.slide) { // the launch wrote the next window's cursors and head to the other halves
         h->pre_slid = true;
         h->pos = pos_next;
@@ -1043,7 +1063,7 @@ int lstm_hip_destroy(lstm_hip_t *h) {
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     if (h->h_losses) (void)hipHostFree(h->h_losses);
-    for (void *p : {(void *)h->d_norms, (void *)h->norm_part, (void *)h->clip_coef, (void *)h->adam_v, (void *)h->avg, (void *)h->Ue,
+    for (void *p : {(void *)h->d_norms, (void *)h->norm_part, (void *)h->clip_coef, (void *)h->adam_v, (void *)h->avg, (void *)h->Ue, (void *)h->acc,
                     (void *)h->tt_text, (void *)h->tt_off, (void *)h->tt_slot, (void *)h->tt_first, (void *)h->tt_bits,
                     (void *)h->tt_weight, (void *)h->tt_wt,
                     (void *)h->colkl, (void *)h->d_kls})
@@ -1280,8 +1300,9 @@ int lstm_hip_backward(lstm_hip_t *h) {
 int lstm_hip_adagrad(lstm_hip_t *h, double learning_rate) {
     CHECK(h);
     h->norms_n = -1;
-    if (int rc = do_adagrad(h, learning_rate, 0)) return rc;
-    if (h->clip_max > 0.0) h->norms_n = 1;
+    h->call_updates = 0;
+    if (int rc = do_adagrad(h, learning_rate, h->call_updates)) return rc;
+    if (h->clip_max > 0.0) h->norms_n = h->call_updates;
     return 0;
 }
 
@@ -1317,6 +1338,50 @@ int lstm_hip_get_grad_norms(lstm_hip_t *h, double *norms, int64_t n) {
         return fail(LSTM_HIP_EINVAL, "get_grad_norms: n = %lld outside [0, %lld] or null pointer", (long long)n, (long long)h->norms_n);
     if (n > 0) HIP_TRY(hipMemcpyAsync(norms, h->d_norms, sizeof(double) * n, hipMemcpyDeviceToHost, h->st));
     HIP_TRY(hipStreamSynchronize(h->st));
+    return 0;
+}
+
+// gradient accumulation (include/lstm_hip.h).  The block is allocated when accumulation is first
+// turned on and kept with the handle; a new (every, mean) pair starts an empty cycle, the same pair again keeps the cycle.
+int lstm_hip_set_grad_accumulation(lstm_hip_t *h, int32_t every, int32_t mean) {
+    CHECK(h);
+    if (every < 1) return fail(LSTM_HIP_EINVAL, "set_grad_accumulation: every must be >= 1 (1 = off; got %d)", every);
+    if (mean != 0 && mean != 1) return fail(LSTM_HIP_EINVAL, "set_grad_accumulation: mean must be 0 or 1 (got %d)", mean);
+    if (every > 1 && h->comm)
+        return fail(LSTM_HIP_ESTATE, "set_grad_accumulation: a handle with a communicator cannot accumulate gradients");
+    if (every == h->acc_every && mean == h->acc_mean) return 0;
+    if (every > 1 && !h->acc) HIP_TRY(hipMalloc((void **)&h->acc, sizeof(float) * h->pl.total));
+    h->acc_every = every, h->acc_mean = mean, h->acc_pending = 0;
+    return 0;
+}
+int lstm_hip_get_grad_accumulation(lstm_hip_t *h, int32_t *every, int32_t *mean, int32_t *pending) {
+    if (!h || !every || !mean || !pending) return fail(LSTM_HIP_EINVAL, "get_grad_accumulation: null argument");
+    *every = h->acc_every, *mean = h->acc_mean, *pending = h->acc_pending;
+    return 0;
+}
+static int need_accumulation(lstm_hip_ctx *h, const char *what) {
+    if (h->acc_every == 1) return fail(LSTM_HIP_ESTATE, "%s: gradient accumulation is off on this handle (lstm_hip_set_grad_accumulation)", what);
+    return 0;
+}
+int lstm_hip_get_grad_accumulator(lstm_hip_t *h, float *host_block) {
+    CHECK(h);
+    if (!host_block) return fail(LSTM_HIP_EINVAL, "get_grad_accumulator: null pointer");
+    if (int rc = need_accumulation(h, "get_grad_accumulator")) return rc;
+    if (h->acc_pending == 0) { // (nothing summed yet: the block's bytes are those of an earlier cycle, or none)
+        std::memset(host_block, 0, sizeof(float) * ParamLayout::make(h->N_log, h->cfg.M).total);
+        return 0;
+    }
+    if (int rc = block_to_host(h, h->acc, host_block)) return rc;
+    return check_abort(h);
+}
+int lstm_hip_set_grad_accumulator(lstm_hip_t *h, const float *host_block, int32_t pending) {
+    CHECK(h);
+    if (!host_block) return fail(LSTM_HIP_EINVAL, "set_grad_accumulator: null pointer");
+    if (int rc = need_accumulation(h, "set_grad_accumulator")) return rc;
+    if (pending < 0 || pending >= h->acc_every)
+        return fail(LSTM_HIP_EINVAL, "set_grad_accumulator: pending must be in [0, %d] (got %d)", h->acc_every - 1, pending);
+    if (int rc = block_from_host(h, h->acc, host_block)) return rc;
+    h->acc_pending = pending;
     return 0;
 }
 
@@ -1545,6 +1610,8 @@ int lstm_hip_comm_init(lstm_hip_t *h, const uint8_t id[LSTM_HIP_UNIQUE_ID_BYTES]
     CHECK(h);
     if (nranks < 1 || rank < 0 || rank >= nranks) return fail(LSTM_HIP_EINVAL, "comm_init: rank %d of %d", rank, nranks);
     if (h->soft_on) return fail(LSTM_HIP_ESTATE, "comm_init: soft targets are on (lstm_hip_set_soft_targets); they run on one device");
+    if (h->acc_every > 1)
+        return fail(LSTM_HIP_ESTATE, "comm_init: gradient accumulation is on (lstm_hip_set_grad_accumulation); it runs on one device");
     int rc = rccl_load();
     if (rc) return rc;
     UniqueId u;
@@ -1643,10 +1710,11 @@ static int ensure_losses(lstm_hip_ctx *h, int64_t count) {
 }
 // One window of a device-resident loop, before its forward pass: does its loss ride in the update launch (wherever the
 // gradient fold does, do_backward's defer_fold, but not under clipping -- the norm needs dby first -- nor in a profiling pass,
-// which times the launches one by one), and does it store the probabilities and the folded gradient (`last`: nothing inside
+// which times the launches one by one, nor under gradient accumulation, whose accumulating windows have no update launch),
+// and does it store the probabilities and the folded gradient (`last`: nothing inside
 // the loop reads them, and only the last window's can be seen afterwards).  Returns whether the caller launches the loss itself.
 static bool loop_window(lstm_hip_ctx *h, bool last, double *loss_out) {
-    h->tail = h->plan.fused && !h->comm && !h->profiling && !(h->clip_max > 0.0);
+    h->tail = h->plan.fused && !h->comm && !h->profiling && !(h->clip_max > 0.0) && h->acc_every == 1;
     h->tail_loss = loss_out;
     h->keep_outputs = last || !h->tail;
     return !h->tail;
@@ -1690,6 +1758,7 @@ int lstm_hip_train_windows(lstm_hip_t *h, int64_t count, double learning_rate, d
         ~KlIndex() { h->kl_idx = 0; }
     } kl_index{h};
     h->norms_n = -1;
+    h->call_updates = 0;
     const bool clip = h->clip_max > 0.0;
     if (clip)
         if (int rc = ensure_norms(h, count)) return rc;
@@ -1717,7 +1786,7 @@ int lstm_hip_train_windows(lstm_hip_t *h, int64_t count, double learning_rate, d
         // not behind the last window (the handle is left on the window it trained on) and not in a profiling pass.  The
         // paths that keep their separate loss launch (loop_window) also keep the slide's for windows above 2 048 columns.
         h->carry_slide = i + 1 < count && !h->profiling && (h->tail || (int64_t)h->cfg.S * h->cfg.B <= 2048);
-        if ((rc = do_adagrad(h, learning_rate, i))) return rc;
+        if ((rc = do_adagrad(h, learning_rate, h->call_updates))) return rc;
     }
     if (elapsed_ms) {
         HIP_TRY(hipEventRecord(h->evt1, h->st));
@@ -1729,7 +1798,7 @@ int lstm_hip_train_windows(lstm_hip_t *h, int64_t count, double learning_rate, d
     HIP_TRY(hipStreamSynchronize(h->st));
     if (losses && count > 0) std::memcpy(losses, h->h_losses, sizeof(double) * count);
     guard.completed = true;
-    if (clip) h->norms_n = count;
+    if (clip) h->norms_n = h->call_updates; // (one norm per update: `count` of them unless gradient accumulation is on)
     if (distil) {
         h->kls_n = count;
         if (int rc = check_abort(h->teacher)) return rc; // (still on this stream, which has just been drained)
@@ -3043,6 +3112,7 @@ static int run_adaptive(lstm_hip_t *h, bool decode, const uint64_t *text_off, co
     if (n_blocks < 0) return (int)n_blocks;
     if (int rc = ensure_losses(h, n_blocks)) return rc;
     h->norms_n = -1;
+    h->call_updates = 0;
     h->pre_slid = false;
     const bool clip = h->clip_max > 0.0;
     if (clip)
@@ -3075,7 +3145,7 @@ static int run_adaptive(lstm_hip_t *h, bool decode, const uint64_t *text_off, co
         h->dby_done = true;
         if ((rc = do_backward(h))) return rc;
         h->carry_slide = false;
-        if ((rc = do_adagrad(h, lr, k))) return rc;
+        if ((rc = do_adagrad(h, lr, h->call_updates))) return rc;
     }
     if (int rc = coder_steps(h, r, (uint64_t)n_blocks * L, r.max_len)) return rc;
     if (!decode) {
@@ -3098,6 +3168,8 @@ static int adaptive_checks(lstm_hip_t *h, const char *what, double lr) {
         return fail(LSTM_HIP_ESTATE, "%s: soft targets are on (lstm_hip_set_soft_targets); the adaptive coders train on hard targets", what);
     if (h->wd_rate > 0.0) // (the containers record no mask: DESIGN.md section 3.15)
         return fail(LSTM_HIP_ESTATE, "%s: weight drop is on (lstm_hip_set_weight_drop); the adaptive coders train without it", what);
+    if (h->acc_every > 1) // (the containers record no K)
+        return fail(LSTM_HIP_ESTATE, "%s: gradient accumulation is on (lstm_hip_set_grad_accumulation); the adaptive coders update after every block", what);
     if (!std::isfinite(lr) || lr < 0.0) return fail(LSTM_HIP_EINVAL, "%s: learning_rate must be finite and >= 0 (got %g)", what, lr);
     if (h->cfg.N > 16384) return fail(LSTM_HIP_EINVAL, "%s: hidden width %d above 16384", what, h->cfg.N);
     if (h->cfg.B > 4096) return fail(LSTM_HIP_EINVAL, "%s: more than 4096 streams (B = %d)", what, h->cfg.B);
@@ -3230,6 +3302,7 @@ int lstm_hip_train_text_windows(lstm_hip_t *h, int64_t count, double learning_ra
                     h->loss_mode);
     if (int rc = ensure_losses(h, count)) return rc;
     h->norms_n = -1;
+    h->call_updates = 0;
     h->pre_slid = false;
     const bool clip = h->clip_max > 0.0;
     if (clip)
@@ -3262,7 +3335,7 @@ int lstm_hip_train_text_windows(lstm_hip_t *h, int64_t count, double learning_ra
         h->dby_done = true;
         if ((rc = do_backward(h))) return rc;
         h->carry_slide = false;
-        if ((rc = do_adagrad(h, learning_rate, i))) return rc;
+        if ((rc = do_adagrad(h, learning_rate, h->call_updates))) return rc;
         h->tt_next++;
     }
     if (elapsed_ms) {
@@ -3275,7 +3348,7 @@ int lstm_hip_train_text_windows(lstm_hip_t *h, int64_t count, double learning_ra
     HIP_TRY(hipStreamSynchronize(h->st));
     if (losses && count > 0) std::memcpy(losses, h->h_losses, sizeof(double) * count);
     guard.completed = true;
-    if (clip) h->norms_n = count;
+    if (clip) h->norms_n = h->call_updates;
     return check_abort(h);
 }
 

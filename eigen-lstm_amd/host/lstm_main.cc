@@ -9,6 +9,7 @@
 //        [--fast-math] [--step-kernels] [--stable-softmax] [--clip-norm X] [--optimizer adagrad|adam]
 //        [--adam-betas B1,B2] [--adam-eps E] [--weight-decay W] [--average ema|uniform] [--average-decay D]
 //        [--average-every K] [--average-start W] [--weight-drop R] [--weight-drop-seed K] [--test-streams K]
+//        [--accumulate K] [--accumulate-mean]
 //        [--test-warmup W] [--records] [--record-delim B] [--shuffle-seed K] [--label-smoothing E] [--teacher PREFIX]
 //        [--distill-alpha A] [--distill-temperature T] [--teacher-bf16] [--train-after B] [--quiet]
 //
@@ -37,6 +38,10 @@
 // averaged model's bits/char; --save also writes the average as a checkpoint of its own, PREFIX_avg_{W,U,b,Why,by}.txt (so
 // --load PREFIX_avg works in lstm_generate and lstm_compress), and PREFIX_avg_state.txt (kind, decay, every, seen, n);
 // --load PREFIX with the same --average kind resumes both, another kind or no --average ignores them.
+// --accumulate K (K >= 2) makes one update per K training windows on the sum of their gradients, --accumulate-mean on their
+// mean (lstm_hip_set_grad_accumulation); one GPU only; the epoch line is unchanged.  --save also writes what is pending as a
+// checkpoint-shaped block PREFIX_accum_{W,U,b,Why,by}.txt and PREFIX_accum_state.txt (every, mean, pending); --load PREFIX
+// with the same K and mean resumes them, another setting or no --accumulate ignores them.
 // --weight-drop R (0 < R < 1) trains with DropConnect on the hidden-to-hidden matrix U, one mask per window
 // (lstm_hip_set_weight_drop; --weight-drop-seed K, default 0, picks the mask sequence).  Held-out tests, samples and saved
 // parameters are those of the unmasked model.  --save also writes PREFIX_weight_drop.txt (rate, seed, t); --load PREFIX with
@@ -71,6 +76,11 @@
 #pragma weak lstm_hip_set_optimizer
 #pragma weak lstm_hip_get_optimizer_steps
 #pragma weak lstm_hip_set_optimizer_steps
+// ... and --accumulate
+#pragma weak lstm_hip_set_grad_accumulation
+#pragma weak lstm_hip_get_grad_accumulation
+#pragma weak lstm_hip_get_grad_accumulator
+#pragma weak lstm_hip_set_grad_accumulator
 // ... and --average
 #pragma weak lstm_hip_set_averaging
 #pragma weak lstm_hip_get_average
@@ -144,6 +154,8 @@ struct Options {
     double avg_decay = 0.0;          // --average-decay (ema: default 0.999)
     int avg_every = 1;               // --average-every
     long avg_start = 0;              // --average-start
+    int accumulate = 1;              // --accumulate (1: off)
+    bool accumulate_mean = false;    // --accumulate-mean
     double wd_rate = 0.0;            // --weight-drop: 0 = off
     uint64_t wd_seed = 0;            // --weight-drop-seed
     bool wd_seed_given = false;
@@ -334,6 +346,12 @@ Options parse(int argc, char **argv) {
             if (k > 2147483647L) die("--average-every is too large");
             o.avg_every = (int)k;
             avg_opt = a;
+        } else if (a == "--accumulate") {
+            const long k = whole_number(a, val(), 2);
+            if (k > 2147483647L) die("--accumulate is too large");
+            o.accumulate = (int)k;
+        } else if (a == "--accumulate-mean") {
+            o.accumulate_mean = true;
         } else if (a == "--average-start") {
             o.avg_start = whole_number(a, val(), 0);
             avg_opt = a;
@@ -404,7 +422,8 @@ Options parse(int argc, char **argv) {
                    "            --weight-decay W --average ema|uniform --average-decay D --average-every K --average-start W\n"
                    "            --weight-drop R --weight-drop-seed K --test-streams K --test-warmup W\n"
                    "            --records --record-delim B --shuffle-seed K --label-smoothing E --teacher PREFIX\n"
-                   "            --distill-alpha A --distill-temperature T --teacher-bf16 --train-after B --quiet]\n");
+                   "            --distill-alpha A --distill-temperature T --teacher-bf16 --train-after B\n"
+                   "            --accumulate K --accumulate-mean --quiet]\n");
             exit(0);
         } else if (a.rfind("--", 0) == 0) die("unknown option " + a);
         else pos.push_back(a);
@@ -423,6 +442,12 @@ Options parse(int argc, char **argv) {
          lstm_hip_set_inference_source == nullptr))
         die("--average: the loaded liblstm_hip has no lstm_hip_set_averaging / lstm_hip_get_average / lstm_hip_set_average / "
             "lstm_hip_get_averaging_counts / lstm_hip_set_averaging_counts / lstm_hip_set_inference_source");
+    if (o.accumulate_mean && o.accumulate == 1) die("--accumulate-mean needs --accumulate K");
+    if (o.accumulate > 1 && o.gpus != 1) die("--accumulate runs on one GPU");
+    if (o.accumulate > 1 && (lstm_hip_set_grad_accumulation == nullptr || lstm_hip_get_grad_accumulation == nullptr ||
+                             lstm_hip_get_grad_accumulator == nullptr || lstm_hip_set_grad_accumulator == nullptr))
+        die("--accumulate: the loaded liblstm_hip has no lstm_hip_set_grad_accumulation / lstm_hip_get_grad_accumulation / "
+            "lstm_hip_get_grad_accumulator / lstm_hip_set_grad_accumulator");
     if (o.wd_seed_given && !(o.wd_rate > 0.0)) die("--weight-drop-seed needs --weight-drop R");
     if (o.test_warmup >= 0 && o.test_streams == 0) die("--test-warmup needs --test-streams K");
     if (o.test_streams > 0 && lstm_hip_eval_texts == nullptr) die("--test-streams: the loaded liblstm_hip has no lstm_hip_eval_texts");
@@ -571,6 +596,20 @@ int run_rank(const Options &o, int rank, int up, int down) {
                 CK(lstm_hip_set_averaging_counts(h, seen, n));
                 avg_on = true;
                 if (lead) printf("Loaded the %s average (seen = %lld, n = %lld) from %s_avg_{W,U,Why,b,by}.txt\n", kind.c_str(), seen, n, o.load.c_str());
+            }
+        }
+    }
+    if (o.accumulate > 1) { // gradient accumulation; what a checkpoint of the same setting had pending is resumed
+        CK(lstm_hip_set_grad_accumulation(h, o.accumulate, o.accumulate_mean ? 1 : 0));
+        if (!o.load.empty()) {
+            std::ifstream f(o.load + "_accum_state.txt");
+            std::string key;
+            long long every = 0, mean = -1, pending = -1;
+            std::vector<float> a(np, 0.0f);
+            if (f && (f >> key >> every >> key >> mean >> key >> pending) && every == o.accumulate &&
+                mean == (o.accumulate_mean ? 1 : 0) && pending > 0 && pending < every && load_params(o.load + "_accum", a, N, M)) {
+                CK(lstm_hip_set_grad_accumulator(h, a.data(), (int32_t)pending));
+                if (lead) printf("Loaded the gradient accumulator (every = %lld, pending = %lld) from %s_accum_{W,U,Why,b,by}.txt\n", every, pending, o.load.c_str());
             }
         }
     }
@@ -769,12 +808,18 @@ int run_rank(const Options &o, int rank, int up, int down) {
                     chunk = std::min<long>(chunk, o.avg_start - done_windows);
             }
             losses.resize(chunk);
+            long updates = chunk; // (one norm per update: under --accumulate one per full cycle)
+            if (o.accumulate > 1) {
+                int32_t every = 1, mean = 0, pending = 0;
+                CK(lstm_hip_get_grad_accumulation(h, &every, &mean, &pending));
+                updates = (pending + chunk) / every;
+            }
             if (o.records) CK(lstm_hip_train_text_windows(h, chunk, lr, losses.data(), nullptr));
             else CK(lstm_hip_train_windows(h, chunk, lr, losses.data(), nullptr));
             if (!o.records) flat_windows += chunk;
             if (o.clip_norm > 0.0) {
-                norms.resize(chunk);
-                CK(lstm_hip_get_grad_norms(h, norms.data(), chunk));
+                norms.resize(updates);
+                CK(lstm_hip_get_grad_norms(h, norms.data(), updates));
                 for (double v : norms) { // (the rule of lstm_hip_set_grad_clip: scaled where the norm is finite and the float
                                          // coefficient below 1)
                     norm_sum += v;
@@ -890,6 +935,17 @@ int run_rank(const Options &o, int rank, int up, int down) {
                         die("cannot write " + o.save + "_avg_state.txt");
                     printf("Saved the %s average (seen = %lld, n = %lld) to %s_avg_{W,U,Why,b,by}.txt\n", avg_name(o.avg_kind),
                            (long long)seen, (long long)n, o.save.c_str());
+                }
+                if (o.accumulate > 1) { // the pending sum as a checkpoint-shaped block (zeros when nothing is pending) and its state
+                    int32_t every = 1, mean = 0, pending = 0;
+                    CK(lstm_hip_get_grad_accumulation(h, &every, &mean, &pending));
+                    CK(lstm_hip_get_grad_accumulator(h, mem.data()));
+                    save_params(o.save + "_accum", mem, N, M, 9);
+                    std::ofstream f(o.save + "_accum_state.txt");
+                    if (!(f << "every " << every << "\nmean " << mean << "\npending " << pending << "\n"))
+                        die("cannot write " + o.save + "_accum_state.txt");
+                    printf("Saved the gradient accumulator (every = %d, mean = %d, pending = %d) to %s_accum_{W,U,Why,b,by}.txt\n", every,
+                           mean, pending, o.save.c_str());
                 }
                 if (o.wd_rate > 0.0) { // weight drop: the three numbers a resumed run sets
                     double rate = 0.0;

@@ -105,6 +105,8 @@ SYMBOLS = [
     "lstm_hip_text_plan", "lstm_hip_set_train_texts", "lstm_hip_get_train_texts", "lstm_hip_train_text_windows",
     "lstm_hip_get_train_texts_bits", "lstm_hip_set_train_texts_weighted",
     "lstm_hip_set_soft_targets", "lstm_hip_get_soft_targets", "lstm_hip_get_teacher_kl",
+    "lstm_hip_set_grad_accumulation", "lstm_hip_get_grad_accumulation", "lstm_hip_get_grad_accumulator",
+    "lstm_hip_set_grad_accumulator",
 ]
 
 
@@ -455,8 +457,9 @@ class Lstm:
         _chk(self.lib.lstm_hip_backward(self._h))
 
     def adagrad(self, lr):
+        steps = self._updates_in(1)
         _chk(self.lib.lstm_hip_adagrad(self._h, C.c_double(lr)))
-        self._steps = 1
+        self._steps = steps
 
     # ---- global-norm gradient clipping (lstm_hip_set_grad_clip) --------------------------------
     def set_grad_clip(self, max_norm):
@@ -470,6 +473,38 @@ class Lstm:
         out = np.zeros(k, np.float64)
         _chk(self.lib.lstm_hip_get_grad_norms(self._h, _ptr(out, C.c_double), C.c_int64(k)))
         return out
+
+    # ---- gradient accumulation (lstm_hip_set_grad_accumulation) --------------------------------
+    def set_grad_accumulation(self, every, mean=False):
+        """every = 1: off (the default).  every = K >= 2: the gradients of K consecutive windows (adagrad calls, windows of
+        train_windows and of train_text_windows) are summed in fp32, divided by K with `mean`, and one update is made on the
+        sum, at the K-th.  A different (every, mean) discards what is pending; the same pair again keeps it."""
+        _chk(self.lib.lstm_hip_set_grad_accumulation(self._h, C.c_int32(every), C.c_int32(int(mean))))
+
+    def grad_accumulation(self):
+        """(every, mean, pending): the setting, and how many windows the accumulator holds (0 .. every - 1)."""
+        every, mean, pending = C.c_int32(), C.c_int32(), C.c_int32()
+        _chk(self.lib.lstm_hip_get_grad_accumulation(self._h, C.byref(every), C.byref(mean), C.byref(pending)))
+        return every.value, bool(mean.value), pending.value
+
+    def grad_accumulator(self):
+        """the summed gradient of the pending windows (logical-N flat block; zeros while pending is 0)"""
+        out = np.empty(self.np, np.float32)
+        _chk(self.lib.lstm_hip_get_grad_accumulator(self._h, _ptr(out)))
+        return out
+
+    def set_grad_accumulator(self, block, pending):
+        """resuming: after set_grad_accumulation, the saved block and its count of windows"""
+        block = _f32(block)
+        assert block.size == self.np, (block.size, self.np)
+        _chk(self.lib.lstm_hip_set_grad_accumulator(self._h, _ptr(block), C.c_int32(pending)))
+
+    def _updates_in(self, count):
+        """updates that the next `count` windows make: all of them, or one per full cycle under gradient accumulation"""
+        if not hasattr(self.lib, "lstm_hip_get_grad_accumulation"):  # (an older library named by LSTM_HIP_LIB lacks it)
+            return count
+        every, _, pending = self.grad_accumulation()
+        return (pending + count) // every
 
     # ---- the update rule (lstm_hip_set_optimizer) ----------------------------------------------
     def set_optimizer(self, kind, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0):
@@ -597,10 +632,11 @@ class Lstm:
     def train_windows(self, count, lr, want_losses=True, want_time=False):
         losses = np.zeros(count, np.float64) if want_losses else None
         ms = C.c_float(0)
+        steps = self._updates_in(count)
         _chk(self.lib.lstm_hip_train_windows(self._h, C.c_int64(count), C.c_double(lr),
                                              _ptr(losses, C.c_double) if want_losses else None,
                                              C.byref(ms) if want_time else None))
-        self._steps = self._kls = count
+        self._steps, self._kls = steps, count
         if want_time:
             return losses, ms.value
         return losses
@@ -649,10 +685,11 @@ class Lstm:
         the HIP-event time of the loop with want_time."""
         losses = np.zeros(count, np.float64) if want_losses else None
         ms = C.c_float(0)
+        steps = self._updates_in(count)
         _chk(self.lib.lstm_hip_train_text_windows(self._h, C.c_int64(count), C.c_double(lr),
                                                   _ptr(losses, C.c_double) if want_losses else None,
                                                   C.byref(ms) if want_time else None))
-        self._steps = count
+        self._steps = steps
         if want_time:
             return losses, ms.value
         return losses

@@ -148,8 +148,44 @@ int lstm_hip_adagrad(lstm_hip_t *h, double learning_rate);
  * which=1) keeps the unclipped d.  Per handle, may change between calls, not part of checkpoints. */
 int lstm_hip_set_grad_clip(lstm_hip_t *h, double max_norm);
 /* the pre-clip norms of the Adagrad steps of the last lstm_hip_adagrad (1) or lstm_hip_train_windows (count) call,
- * oldest first; n <= that number (else LSTM_HIP_EINVAL); LSTM_HIP_ESTATE when clipping was off for that call */
+ * oldest first; n <= that number (else LSTM_HIP_EINVAL); LSTM_HIP_ESTATE when clipping was off for that call.  Under
+ * gradient accumulation (below) a call records one norm per UPDATE it made, possibly none. */
 int lstm_hip_get_grad_norms(lstm_hip_t *h, double *norms, int64_t n);
+
+/* ---- gradient accumulation: one update per `every` training windows
+ *   every == 1   off (the default): no block, no counter, no launch; mean must still be 0 or 1
+ *   every >= 2   on; mean = 0 keeps the sum of the windows' gradients, mean = 1 divides it by every
+ *   anything else is LSTM_HIP_EINVAL, the message names the number and the handle stays usable.
+ * A micro-window is every place an update is made today: lstm_hip_adagrad, each window of lstm_hip_train_windows and of
+ * lstm_hip_train_text_windows.  Let g be the window's gradient block, summed from its pieces in the order the handle uses
+ * without accumulation.  The handle keeps an fp32 block acc and a count pending in 0 .. every - 1:
+ *   pending + 1 < every    acc = g when pending == 0 (an exact copy), else acc = acc + g (one fp32 add per element);
+ *                          pending += 1.  No update: parameters, optimizer state and step count, averaging counts, the
+ *                          weight-drop index t and every image of the weights stay as they are, and the call's learning rate
+ *                          is not read.  lstm_hip_get_params(which = 1) returns this window's own g.
+ *   pending + 1 == every   d = acc + g; with mean, d = d * (float)(1.0 / every): a second, separately rounded fp32 operation
+ *                          with the factor computed in double on the host, no fused multiply-add.  d goes to the gradient
+ *                          block (which = 1 returns it, unclipped) and the update runs on d exactly as a plain window's runs
+ *                          on its gradient: the clip norm is taken on d, the step uses this call's learning rate, Adam's t,
+ *                          the averaging count `seen` and the weight-drop index t advance by one.  pending = 0.
+ * (NumPy's (acc + g) * np.float32(1.0 / every) on float32 arrays is bit for bit the same.)  Non-finite values propagate as
+ * they are.  acc and pending live with the handle across calls: how a run is cut into lstm_hip_train_windows,
+ * lstm_hip_train_text_windows and lstm_hip_adagrad calls shows in no result.  Losses, the teacher's KL and the text windows'
+ * per-stream bits stay per window; lstm_hip_get_grad_norms returns one norm per update.  Under weight drop one mask lasts
+ * the `every` windows of a cycle.  A LSTM_HIP_PAD_HIDDEN handle keeps acc at the internal width with zero padding.
+ * State: a different (every, mean) pair, off included, discards what is pending (pending = 0); the same pair again keeps it.
+ * lstm_hip_get_grad_accumulator / lstm_hip_set_grad_accumulator move acc as lstm_hip_get_params / lstm_hip_set_params move
+ * their blocks (logical-N flat block; with pending == 0 get returns the zero block: nothing is summed); set needs
+ * 0 <= pending < every (else LSTM_HIP_EINVAL) and exists for resuming, in this order: lstm_hip_set_grad_accumulation,
+ * lstm_hip_set_grad_accumulator.  Both answer LSTM_HIP_ESTATE while accumulation is off; the four answer LSTM_HIP_EINVAL for
+ * a null pointer.  Accumulation runs on one device: turning it on with a communicator on the handle, and
+ * lstm_hip_comm_init while it is on, are LSTM_HIP_ESTATE; so are the adaptive coders while it is on (their containers
+ * record no `every`).  Per handle, may change between calls, not part of the engine plan; a handle that never turns it on
+ * makes the launches it made before this call existed. */
+int lstm_hip_set_grad_accumulation(lstm_hip_t *h, int32_t every, int32_t mean);
+int lstm_hip_get_grad_accumulation(lstm_hip_t *h, int32_t *every, int32_t *mean, int32_t *pending);
+int lstm_hip_get_grad_accumulator(lstm_hip_t *h, float *host_block);        /* logical-N flat block, as get_params */
+int lstm_hip_set_grad_accumulator(lstm_hip_t *h, const float *host_block, int32_t pending);
 
 /* ---- the update rule of lstm_hip_adagrad and of every window of lstm_hip_train_windows (the name is kept for the seam)
  *   LSTM_HIP_OPT_ADAGRAD  the default above; beta1, beta2, eps and weight_decay must all be 0
