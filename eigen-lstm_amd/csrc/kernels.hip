@@ -52,10 +52,10 @@ __device__ __forceinline__ float wave_max(float v) {
     const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
     return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
 }
-// LSTM_HIP_STABLE_SOFTMAX: -log2 p_t of p = exp(z - zmax) / s in log-sum-exp form (finite where p_t underflows to 0)
-__device__ __forceinline__ float lse_surprisal(float s, float zmax, float zt) {
-    return log2f(s) + (zmax - zt) * 1.44269504088896341f;
-}
+// The inference heads (heads/*.inc, included below where each kernel stood) name their dynamic LDS array through this macro,
+// so that the host emulations under tests/ can back it with ordinary memory.
+#define HEAD_DYNAMIC_LDS(T, name) extern __shared__ __attribute__((aligned(16))) T name[]
+#include "heads/lse_surprisal.h"
 
 // ------------------------------------------------------------------------------------------------
 // pack_U: build the MFMA A-fragment images of U (4N x N) for both recurrences.
@@ -2047,304 +2047,7 @@ __global__ __launch_bounds__(1024) void k_sample(const float *__restrict__ P, in
         hc[N + j] = cs[j];
     }
 }
-// ------------------------------------------------------------------------------------------------
-// gen_head: one step of the batched generator (lstm_hip_generate; lstm_hip_sample on the persistent engine is its
-// streams = 1 case).  Per step the host launches this kernel on the state after t inputs, then one k_fwd_step over all
-// streams with the inputs it chose.  Per stream s, with L = its prompt length:
-//   t <  L          input prompt[t]; for t >= 1 (and bits requested) bits[s] += -log2 p(prompt[t]) at temperature 1
-//   L <= t < L + C  byte i = t - L drawn from p (mode 0: expf(z) unshifted, as b1_output, or expf(z - max z) when STABLE;
-//                   1: expf((z - max z) / tau);
-//                   2: argmax z, lowest index on ties) by the sequential float CDF walk of R/lstm.cc:321-338 (index 0
-//                   if u passes every edge); it goes to out[i * streams + s] and becomes the next input
-//   t == L + C      the state is the stream's final one: copied to h_out / c_out (the stream idles afterwards, x = -1)
-// Workgroup g owns streams g*SB .. g*SB+SB-1; thread m owns logit m of all of them, so each Why element read serves SB
-// streams (h of the group in LDS, k-major).  Each logit is summed sequentially in k with separate multiply and add
-// (contraction is off in this file), so a stream's bytes do not depend on SB, on its position or on the other streams.
-// STABLE (LSTM_HIP_STABLE_SOFTMAX): scored prompt bytes and mode-0 draws shift by max z too, and a prompt byte scores
-// lse_surprisal (the max and the target's logit are taken by the stream's max thread).
-// FILTER (lstm_hip_generate_ex with a filter, a stop byte or `kept` wanted): the instantiation with
-// FILTER = false is the code above and nothing else.  With it,
-//   a.filter    a tempered draw keeps the `keep` most likely bytes: thread m ranks its logit among the stream's 256 (z
-//               descending, index ascending: 256 broadcast reads of the z still in ps), the normalised terms p are scattered
-//               to sorted[rank], the stream's owner lane walks them in rank order until the float sum reaches a.top_p (at
-//               most a.keep_k of them), every thread clears its term if its rank is not kept, and the owner lane sums the
-//               kept terms in index order and walks the CDF of p / that sum; past every edge the byte is the largest kept
-//               index.  A stream's bytes still depend on nothing but its own h.  Greedy draws and prompt bytes ignore it.
-//   a.stop_byte a stream draws a.end[s] bytes, not a.count: the owner lane sets it to i + 1 when draw i is the stop byte, so
-//               the next launch copies the state after that byte to h_out / c_out and the stream idles.
-//   a.kept      keep per filtered draw, 256 per unfiltered one, 1 per greedy one.
-// CONSTRAIN (lstm_hip_generate_constrained; implies FILTER, and without it the instantiation is the
-// code above and nothing else): stream s is in state q = a.cstate[s] of the byte automaton a.ctab.  For a drawn byte thread m
-// loads a.ctab[q * 256 + m] and, where that is 0xFFFF (forbidden), sets its logit to -inf before the logit goes to ps: rank,
-// max, expf and sum all see the masked value.  A tempered draw is then always a filtered one, keep capped by a.ccount[q] (the
-// allowed bytes of q), so the kept bytes are allowed ones.  The owner lane replaces a byte that is forbidden all the same
-// (non-finite logits only) by the lowest allowed byte of q and writes the next state to a.cstate[s].  Prompt bytes ignore it.
-// DEADLINE (lstm_hip_generate_accepting; implies CONSTRAIN, and without it the instantiation is the code
-// above and nothing else): at draw i of a stream, R = a.count - i draws remain.  Byte m EXISTS iff nx = a.ctab[q * 256 + m] is
-// allowed and a.accept[nx] (m the stop byte) or bit nx of row R - 1 of a.frows (any other byte): an accepted end can still be
-// reached behind it.  A byte that does not exist is masked like a forbidden one; thread m tests its own byte (one more load,
-// ahead of the product: the row differs per stream, as prompts differ in length) and the group counts the existing bytes E of
-// every stream in LDS, which caps keep in place of a.ccount[q].  The owner lane replaces a byte that does not exist by the
-// lowest existing one.  The host has checked F[count][q0], so E >= 1 at every draw and the stream ends in an accepting state.
-// ------------------------------------------------------------------------------------------------
-// what stream s does at step t: 0 idle, 1 prompt byte scored, 2 drawn byte, 3 prompt byte not scored; *len = its prompt length
-// (*drawn: the bytes the stream draws -- the call's count, or with FILTER its own end index)
-template <bool FILTER>
-__device__ __forceinline__ int gen_phase(const GenHeadArgs &a, int s, long long t, long long *len, int *drawn = nullptr) {
-    *len = a.off ? (long long)(a.off[s + 1] - a.off[s]) : 0;
-    const int n = FILTER ? a.end[s] : a.count;
-    if (drawn) *drawn = n;
-    if (t < *len) return (t >= 1 && a.bits) ? 1 : 3;
-    return t - *len < n ? 2 : 0;
-}
-// does byte x exist for a stream in the state whose table row is `row`, `left` draws before its last one?  (DEADLINE)
-__device__ __forceinline__ bool gen_exists(const GenHeadArgs &a, const uint16_t *row, int x, long long left) {
-    const uint16_t nx = row[x];
-    if (nx == 0xFFFF) return false;
-    if (x == a.stop_byte) return a.accept[nx] != 0;
-    return (a.frows[(size_t)left * a.fwords + (nx >> 5)] >> (nx & 31)) & 1u;
-}
-template <int SB, bool STABLE, bool FILTER, bool CONSTRAIN = false, bool DEADLINE = false>
-__global__ __launch_bounds__(256) void k_gen_head(GenHeadArgs a, long long t) {
-    static_assert(FILTER || !CONSTRAIN, "CONSTRAIN implies FILTER");
-    static_assert(CONSTRAIN || !DEADLINE, "DEADLINE implies CONSTRAIN");
-    extern __shared__ __attribute__((aligned(16))) float hs[]; // [N][SB]
-    __shared__ float ps[SB][256];
-    __shared__ float s_zmax[SB], s_sum[SB], s_zt[STABLE ? SB : 1];
-    __shared__ int s_arg[SB];
-    __shared__ float sorted[FILTER ? SB : 1][FILTER ? 256 : 1]; // p in rank order
-    __shared__ int s_keep[FILTER ? SB : 1], s_last[FILTER ? SB : 1]; // bytes kept; the largest kept index
-    [[maybe_unused]] __shared__ int s_exist[DEADLINE ? SB : 1]; // E: the bytes that exist for each drawing stream
-    const int m = threadIdx.x, N = a.N, s0 = blockIdx.x * SB;
-    int phase[SB]; // (the same in every thread)
-    [[maybe_unused]] int cq[CONSTRAIN ? SB : 1]; // the automaton state of each drawing stream (read before any barrier)
-    [[maybe_unused]] long long left[DEADLINE ? SB : 1]; // draws each drawing stream has before its last one: R - 1
-    bool need = false;
-#pragma unroll
-    for (int j = 0; j < SB; j++) {
-        const int s = s0 + j;
-        phase[j] = 0;
-        if (s >= a.streams) continue;
-        long long len;
-        int drawn;
-        phase[j] = gen_phase<FILTER>(a, s, t, &len, &drawn);
-        need |= phase[j] == 1 || phase[j] == 2;
-        if constexpr (CONSTRAIN) cq[j] = phase[j] == 2 ? a.cstate[s] : 0;
-        if constexpr (DEADLINE) left[j] = phase[j] == 2 ? a.count - 1 - (t - len) : 0;
-        if (t == len + drawn) { // the state after the stream's last input
-            if (a.h_out)
-                for (int k = m; k < N; k += 256) a.h_out[(size_t)s * N + k] = a.H[(size_t)s * N + k];
-            if (a.c_out)
-                for (int k = m; k < N; k += 256) a.c_out[(size_t)s * N + k] = a.C[(size_t)s * N + k];
-        }
-    }
-    if (need) { // (uniform)
-        [[maybe_unused]] bool banned[CONSTRAIN ? SB : 1]; // is byte m forbidden where stream j stands?  (loaded ahead of the product)
-        if constexpr (CONSTRAIN) {
-#pragma unroll
-            for (int j = 0; j < SB; j++) {
-                if constexpr (DEADLINE) banned[j] = phase[j] == 2 && !gen_exists(a, a.ctab + (size_t)cq[j] * 256, m, left[j]);
-                else banned[j] = phase[j] == 2 && a.ctab[(size_t)cq[j] * 256 + m] == 0xFFFF;
-            }
-        }
-        if constexpr (DEADLINE)
-            if (m < SB) s_exist[m] = 0; // (counted behind the barrier below)
-        for (int i = m; i < N * SB; i += 256) {
-            const int k = i / SB, j = i - k * SB;
-            hs[i] = s0 + j < a.streams ? a.H[(size_t)(s0 + j) * N + k] : 0.0f;
-        }
-        __syncthreads();
-        float y[SB];
-#pragma unroll
-        for (int j = 0; j < SB; j++) y[j] = 0.0f;
-        for (int k0 = 0; k0 < N; k0 += 16) { // 16 loads in flight; the additions stay in k order (as b1_output)
-            float wv[16];
-#pragma unroll
-            for (int i = 0; i < 16; i++) wv[i] = a.Why[(size_t)(k0 + i) * 256 + m];
-#pragma unroll
-            for (int i = 0; i < 16; i++)
-#pragma unroll
-                for (int j = 0; j < SB; j++) y[j] += wv[i] * hs[(k0 + i) * SB + j];
-        }
-        if constexpr (DEADLINE) {
-#pragma unroll
-            for (int j = 0; j < SB; j++)
-                if (phase[j] == 2 && !banned[j]) atomicAdd(&s_exist[j], 1); // (read behind the filter's barriers)
-        }
-        const float bym = a.by[m];
-        bool any_max = false;
-        [[maybe_unused]] bool any_filter = false;
-#pragma unroll
-        for (int j = 0; j < SB; j++) {
-            y[j] = y[j] + bym; // the logit z
-            if constexpr (CONSTRAIN)
-                if (banned[j]) y[j] = -INFINITY;
-            ps[j][m] = y[j];
-            any_max |= phase[j] == 2 && a.mode != 0;
-            if constexpr (STABLE) any_max |= phase[j] == 1 || phase[j] == 2;
-            if constexpr (FILTER) any_filter |= phase[j] == 2 && a.mode != 2 && (CONSTRAIN || a.filter);
-        }
-        [[maybe_unused]] int rank[FILTER ? SB : 1]; // of this thread's logit: #{z_i > z_m} + #{i < m: z_i == z_m}, in 0..255
-        if constexpr (FILTER)
-            if (any_filter) { // (uniform)
-                __syncthreads();
-#pragma unroll
-                for (int j = 0; j < SB; j++) {
-                    rank[j] = 0;
-                    if (phase[j] != 2) continue;
-                    const float zm = y[j];
-                    int r = 0;
-#pragma unroll 8
-                    for (int i = 0; i < 256; i++) {
-                        const float zi = ps[j][i];
-                        r += (zi > zm) | ((zi == zm) & (i < m));
-                    }
-                    rank[j] = r;
-                }
-                __syncthreads(); // (ps is overwritten below)
-            }
-        if (any_max) { // max z / argmax z of each tempered or greedy stream (every order gives the same max)
-            __syncthreads();
-            long long len;
-            const int pm = m < SB && s0 + m < a.streams ? gen_phase<FILTER>(a, s0 + m, t, &len) : 0;
-            if (pm == 2 || (STABLE && pm == 1)) {
-                float best = ps[m][0];
-                int arg = 0;
-                for (int i = 1; i < 256; i++)
-                    if (ps[m][i] > best) {
-                        best = ps[m][i];
-                        arg = i;
-                    }
-                s_zmax[m] = best;
-                s_arg[m] = arg;
-                if constexpr (STABLE)
-                    if (pm == 1) s_zt[m] = ps[m][a.prompts[a.off[s0 + m] + t]];
-            }
-            __syncthreads();
-        }
-#pragma unroll
-        for (int j = 0; j < SB; j++) {
-            if (phase[j] == 1 || (phase[j] == 2 && a.mode == 0)) ps[j][m] = STABLE ? expf(y[j] - s_zmax[j]) : expf(y[j]);
-            else if (phase[j] == 2 && a.mode == 1) ps[j][m] = expf((y[j] - s_zmax[j]) / a.tau);
-        }
-        __syncthreads();
-        long long len;
-        const int pm = m < SB && s0 + m < a.streams ? gen_phase<FILTER>(a, s0 + m, t, &len) : 0;
-        if (pm == 1 || (pm == 2 && a.mode != 2)) {
-            float s = 0.0f;
-            for (int i = 0; i < 256; i++) s += ps[m][i];
-            s_sum[m] = s;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < SB; j++)
-            if (phase[j] == 1 || (phase[j] == 2 && a.mode != 2)) ps[j][m] = ps[j][m] / s_sum[j]; // p, the CDF's terms
-        __syncthreads();
-        if constexpr (FILTER)
-            if (any_filter) { // (uniform)
-#pragma unroll
-                for (int j = 0; j < SB; j++)
-                    if (phase[j] == 2) sorted[j][rank[j]] = ps[j][m];
-                if (m < SB) s_last[m] = 0;
-                __syncthreads();
-                // the stream's owner lane (as below) walks the nucleus prefix: most likely first, one float sum
-                const int jo = (m & 63) * 4 + (m >> 6);
-                if (jo < SB && s0 + jo < a.streams) {
-                    long long lo;
-                    if (gen_phase<FILTER>(a, s0 + jo, t, &lo) == 2) {
-                        int keep = a.keep_k;
-                        if constexpr (DEADLINE) {
-                            if (s_exist[jo] < keep) keep = s_exist[jo];
-                        } else if constexpr (CONSTRAIN) {
-                            const int allowed = a.ccount[a.cstate[s0 + jo]];
-                            if (allowed < keep) keep = allowed;
-                        }
-                        if (a.nucleus) {
-                            float sum = 0.0f;
-                            for (int r = 0; r < keep; r++) { // (past keep_k the nucleus no longer matters)
-                                sum += sorted[jo][r];
-                                if (sum >= a.top_p) {
-                                    keep = r + 1;
-                                    break;
-                                }
-                            }
-                        }
-                        s_keep[jo] = keep;
-                    }
-                }
-                __syncthreads();
-#pragma unroll
-                for (int j = 0; j < SB; j++) {
-                    if (phase[j] != 2) continue;
-                    if (rank[j] < s_keep[j]) atomicMax(&s_last[j], m);
-                    else ps[j][m] = 0.0f;
-                }
-                __syncthreads();
-            }
-    }
-    // one owner thread per stream, spread over the four waves
-    const int j = (m & 63) * 4 + (m >> 6);
-    if (j >= SB || s0 + j >= a.streams) return;
-    const int s = s0 + j;
-    long long len;
-    const int ph = gen_phase<FILTER>(a, s, t, &len);
-    int x = -1;
-    if (ph == 1 || ph == 3) {
-        x = a.prompts[a.off[s] + t];
-        if (ph == 1) {
-            if constexpr (STABLE) a.bits[s] += (double)lse_surprisal(s_sum[j], s_zmax[j], s_zt[j]);
-            else a.bits[s] += -(double)log2f(ps[j][x]);
-        }
-    } else if (ph == 2) {
-        const size_t i = (size_t)(t - len);
-        [[maybe_unused]] int kept = 256;
-        if (a.mode == 2) {
-            x = s_arg[j];
-            kept = 1;
-        } else if (FILTER && (CONSTRAIN || a.filter)) {
-            kept = s_keep[j];
-            const float r = (float)a.u[i * a.streams + s];
-            float sum = 0.0f; // of the kept terms, in index order
-            for (int k = 0; k < 256; k++) sum += ps[j][k];
-            float cdf = 0.0f;
-            x = s_last[j];
-            for (int k = 0; k < 256; k++) {
-                cdf += ps[j][k] / sum;
-                if (r < cdf) {
-                    x = k;
-                    break;
-                }
-            }
-        } else {
-            const float r = (float)a.u[i * a.streams + s];
-            float cdf = 0.0f;
-            x = 0;
-            for (int k = 0; k < 256; k++) {
-                cdf += ps[j][k];
-                if (r < cdf) {
-                    x = k;
-                    break;
-                }
-            }
-        }
-        if constexpr (CONSTRAIN) { // advance the automaton; a forbidden byte gives way to the state's lowest allowed one
-            const uint16_t *row = a.ctab + (size_t)a.cstate[s] * 256;
-            if constexpr (DEADLINE) { // a byte that does not exist gives way to the lowest existing one
-                const long long lf = a.count - 1 - (long long)i;
-                if (!gen_exists(a, row, x, lf))
-                    for (x = 0; x < 255 && !gen_exists(a, row, x, lf); x++) {}
-            } else if (row[x] == 0xFFFF)
-                for (x = 0; x < 255 && row[x] == 0xFFFF; x++) {}
-            if (row[x] != 0xFFFF) a.cstate[s] = row[x]; // (an empty row cannot be reached: the state never leaves the table)
-        }
-        a.out[i * a.streams + s] = (uint8_t)x;
-        if constexpr (FILTER) {
-            if (a.kept) a.kept[i * a.streams + s] = (uint16_t)kept;
-            if (x == a.stop_byte) a.end[s] = (int32_t)i + 1; // (read again by the next launch only)
-        }
-    }
-    a.x_next[s] = x;
-}
+#include "heads/gen_head.inc"
 int gen_head_group(int N, int streams) {
     int sb = 1; // enough workgroups to cover the chip before Why is shared, and h of the group within 64 KB of LDS
     while (sb < 16 && streams >= 256 * 2 * sb && (size_t)2 * sb * N <= 16384) sb *= 2;
@@ -2414,224 +2117,7 @@ hipError_t gen_head(const GenHeadArgs &a, long long t, bool stable, hipStream_t 
     return stable ? gen_head_launch<true>(a, t, st) : gen_head_launch<false>(a, t, st);
 }
 
-// ------------------------------------------------------------------------------------------------
-// beam_head: one step of beam search (lstm_hip_beam_search).  One workgroup per stream s, whose W
-// slots are columns s*W .. s*W+W-1; with L = the stream's prompt length:
-//   t <  L          every slot gets input prompt[t]; the state is copied to Hr / Cr as it is
-//   L <= t < L + C  selection i = t - L (below), the state gathered to Hr / Cr by parent
-//   otherwise       the stream idles (x = -1)
-// Selection: as k_gen_head with SB = W, thread m owns logit m of all W slots (h of the slots in LDS, k-major; the same k
-// order and 16-deep load batching, so a logit has the bits of the generator's).  Per live slot j an owner lane takes
-// zmax = max z and s = the sequential float sum of expf(z - zmax); thread m's candidate (j, m) costs
-// cost_j + (double)lse_surprisal(s, zmax, z_m), NaN taken as +inf.  A finished slot offers one candidate, held by thread 0:
-// itself, cost unchanged, byte 0.  Then W rounds of a block-wide arg-min under (cost ascending, parent ascending, z
-// descending, byte ascending): the thread's best of its register-held candidates (all of one byte, so: lowest cost, then
-// lowest parent; rescanned only after one of them was retired), 6 shuffle steps inside the wave, the four waves through
-// LDS; the winner's thread retires it.  There are always at least W candidates, so every round finds one.  New slot r
-// is round r's winner: tables, cost, length, finished flag and next input are written by thread r.
-// WP: W rounded up to a power of two (register arrays); EXACT: W == WP, so that the LDS stride is a constant.
-// CONSTRAIN (lstm_hip_beam_search_constrained): the instantiation with CONSTRAIN = false is the code
-// above and nothing else.  With it every slot carries a state q of the byte automaton a.ctab (s_q, read into LDS with the
-// costs).  Thread m reads next[q_j][m] of every live slot j (one table row per slot, 2-byte coalesced loads) and keeps two
-// masks, a bit per slot: `allowed` (the entry is not 0xFFFF) and `exists` (allowed, and with a.accept the deadline: at
-// selection i the byte must lead to a state from which an accepted end is count - i - 1 bytes away -- bit next of row
-// count - i - 1 of a.frows --, the stop byte into an accepting state).  z is set to -inf where the byte is not allowed, before
-// the max and before expf, so a forbidden term adds 0.0f to the sum: cost, zmax and sum are the scorer's under the same
-// table.  Only candidates that exist are offered.  Thread r writes the new slot's state: its parent's if that was finished,
-// else next[q_p][b].
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool beam_before(double c1, int i1, float z1, double c2, int i2, float z2) { // idx = parent * 256 + byte
-    if (c1 != c2) return c1 < c2;
-    if ((i1 >> 8) != (i2 >> 8)) return (i1 >> 8) < (i2 >> 8);
-    if (z1 != z2) return z1 > z2;
-    return (i1 & 255) < (i2 & 255);
-}
-template <int WP, bool EXACT, bool CONSTRAIN = false>
-__global__ __launch_bounds__(256) void k_beam_head(BeamHeadArgs a, long long t) {
-    extern __shared__ __attribute__((aligned(16))) float hs[]; // [N][W]
-    __shared__ float ps[WP][256];
-    __shared__ double s_cost[WP], sel_cost[WP], w_cost[4];
-    __shared__ float s_zmax[WP], s_sum[WP], w_z[4];
-    __shared__ int s_len[WP], s_fin[WP], sel_idx[WP], w_idx[4];
-    __shared__ int s_q[CONSTRAIN ? WP : 1];
-    const int m = threadIdx.x, N = a.N, s = blockIdx.x, W = EXACT ? WP : a.W;
-    const size_t c0 = (size_t)s * W, SW = (size_t)a.streams * W;
-    const long long len = a.off ? (long long)(a.off[s + 1] - a.off[s]) : 0;
-    const bool select = t >= len && t - len < a.count; // (uniform)
-    constexpr int NONE = WP << 8;                      // no candidate: behind every real one (parent WP)
-    if (m < W) sel_idx[m] = m << 8;                    // the gather of a step without a selection: every slot stays
-    if (!select) {
-        if (m < W) a.x_next[c0 + m] = t < len ? (int32_t)a.prompts[a.off[s] + t] : -1;
-    } else {
-        if (m < W) {
-            s_cost[m] = a.cost[c0 + m];
-            s_len[m] = a.len[c0 + m];
-            s_fin[m] = a.fin[c0 + m];
-            if constexpr (CONSTRAIN) s_q[m] = a.cstate[c0 + m];
-        }
-        for (int i = m; i < N * W; i += 256) {
-            const int k = i / W, j = i - k * W;
-            hs[i] = a.H[(c0 + j) * N + k];
-        }
-        __syncthreads();
-        [[maybe_unused]] unsigned allowed = 0, exists = 0; // a bit per slot: byte m may follow it / is offered as a candidate
-        if constexpr (CONSTRAIN) {
-            const uint32_t *frow = a.frows ? a.frows + (size_t)(a.count - 1 - (t - len)) * a.fwords : nullptr;
-#pragma unroll
-            for (int j = 0; j < WP; j++) {
-                if (j >= W || s_fin[j]) continue;
-                const unsigned nx = a.ctab[(size_t)s_q[j] * 256 + m];
-                if (nx == 0xFFFFu) continue;
-                allowed |= 1u << j;
-                bool ok = true;
-                if (a.accept) ok = m == a.stop_byte ? a.accept[nx] != 0 : ((frow[nx >> 5] >> (nx & 31)) & 1u) != 0;
-                if (ok) exists |= 1u << j;
-            }
-        }
-        float y[WP];
-        int jo[WP]; // slot whose h register j reads (registers W..WP-1 repeat the last slot and are never candidates)
-#pragma unroll
-        for (int j = 0; j < WP; j++) {
-            y[j] = 0.0f;
-            jo[j] = EXACT || j < W ? j : W - 1;
-        }
-        for (int k0 = 0; k0 < N; k0 += 16) { // as k_gen_head: 16 loads in flight, the additions in k order
-            float wv[16];
-#pragma unroll
-            for (int i = 0; i < 16; i++) wv[i] = a.Why[(size_t)(k0 + i) * 256 + m];
-#pragma unroll
-            for (int i = 0; i < 16; i++)
-#pragma unroll
-                for (int j = 0; j < WP; j++) y[j] += wv[i] * hs[(k0 + i) * W + jo[j]];
-        }
-        const float bym = a.by[m];
-#pragma unroll
-        for (int j = 0; j < WP; j++) {
-            y[j] = y[j] + bym; // the logit z
-            if constexpr (CONSTRAIN)
-                if (!((allowed >> j) & 1u)) y[j] = -INFINITY; // (finished slots too: their z is not read)
-            if (j < W) ps[j][m] = y[j];
-        }
-        __syncthreads();
-        const int own = (m & 63) * 4 + (m >> 6); // one owner thread per slot, spread over the four waves
-        const bool owner = own < W && !s_fin[own];
-        if (owner) { // (every order gives the same max)
-            float best = ps[own][0];
-            for (int i = 1; i < 256; i++) best = ps[own][i] > best ? ps[own][i] : best;
-            s_zmax[own] = best;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < WP; j++)
-            if (j < W && !s_fin[j]) ps[j][m] = expf(y[j] - s_zmax[j]);
-        __syncthreads();
-        if (owner) {
-            float sum = 0.0f;
-            for (int i = 0; i < 256; i++) sum += ps[own][i];
-            s_sum[own] = sum;
-        }
-        __syncthreads();
-        double ck[WP];        // this thread's candidates: slot j extended by byte m
-        unsigned live = 0;    // ... those that exist and are not yet selected
-#pragma unroll
-        for (int j = 0; j < WP; j++) {
-            ck[j] = (double)INFINITY;
-            if (j >= W) continue;
-            if (s_fin[j]) {
-                if (m == 0) {
-                    ck[j] = s_cost[j];
-                    live |= 1u << j;
-                }
-                y[j] = 0.0f;
-            } else {
-                const double v = s_cost[j] + (double)lse_surprisal(s_sum[j], s_zmax[j], y[j]);
-                ck[j] = v != v ? (double)INFINITY : v;
-                if (!CONSTRAIN || ((exists >> j) & 1u)) live |= 1u << j;
-            }
-        }
-        double lc = (double)INFINITY; // the thread's best live candidate
-        float lz = 0.0f;
-        int li = NONE;
-        bool rescan = true;
-        for (int r = 0; r < W; r++) {
-            if (rescan) {
-                lc = (double)INFINITY;
-                lz = 0.0f;
-                li = NONE;
-#pragma unroll
-                for (int j = 0; j < WP; j++)
-                    if (((live >> j) & 1u) && (li == NONE || ck[j] < lc)) {
-                        lc = ck[j];
-                        lz = y[j];
-                        li = (j << 8) | m;
-                    }
-                rescan = false;
-            }
-            double bc = lc;
-            float bz = lz;
-            int bi = li;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const double oc = __shfl_xor(bc, o, 64);
-                const float oz = __shfl_xor(bz, o, 64);
-                const int oi = __shfl_xor(bi, o, 64);
-                if (beam_before(oc, oi, oz, bc, bi, bz)) {
-                    bc = oc;
-                    bz = oz;
-                    bi = oi;
-                }
-            }
-            if ((m & 63) == 0) {
-                w_cost[m >> 6] = bc;
-                w_z[m >> 6] = bz;
-                w_idx[m >> 6] = bi;
-            }
-            __syncthreads();
-            bc = w_cost[0];
-            bz = w_z[0];
-            bi = w_idx[0];
-#pragma unroll
-            for (int w = 1; w < 4; w++)
-                if (beam_before(w_cost[w], w_idx[w], w_z[w], bc, bi, bz)) {
-                    bc = w_cost[w];
-                    bz = w_z[w];
-                    bi = w_idx[w];
-                }
-            if (bi < NONE && (bi & 255) == m) { // mine: retired
-                live &= ~(1u << (bi >> 8));
-                rescan = true;
-            }
-            if (m == 0) {
-                sel_idx[r] = bi < NONE ? bi : (W - 1) << 8; // (a round always finds a candidate; the table stays in bounds regardless)
-                sel_cost[r] = bc;
-            }
-            __syncthreads();
-        }
-        if (m < W) {
-            const int p = sel_idx[m] >> 8, b = sel_idx[m] & 255, pf = s_fin[p];
-            const size_t i = (size_t)(t - len);
-            a.trace_parent[i * SW + c0 + m] = (uint8_t)p;
-            a.trace_byte[i * SW + c0 + m] = (uint8_t)b;
-            a.cost[c0 + m] = sel_cost[m];
-            a.len[c0 + m] = s_len[p] + (pf ? 0 : 1);
-            a.fin[c0 + m] = pf || b == a.stop_byte ? 1 : 0;
-            a.x_next[c0 + m] = pf ? -1 : b;
-            if constexpr (CONSTRAIN) {
-                // every read of the old states comes from s_q, filled before the first barrier: writing the array in place
-                // races with nothing (the workgroup owns its slots)
-                const unsigned nx = pf ? 0xFFFFu : a.ctab[(size_t)s_q[p] * 256 + b];
-                a.cstate[c0 + m] = nx == 0xFFFFu ? s_q[p] : (int)nx; // (a selected byte is allowed; the state stays in the table regardless)
-            }
-        }
-    }
-    __syncthreads();
-    // states follow their parents (the workgroup owns every column it reads and writes; Hr / Cr are other buffers)
-    for (int i = m; i < N * W; i += 256) {
-        const int r = i / N, k = i - r * N, p = sel_idx[r] >> 8;
-        a.Hr[(c0 + r) * N + k] = a.H[(c0 + p) * N + k];
-        a.Cr[(c0 + r) * N + k] = a.C[(c0 + p) * N + k];
-    }
-}
+#include "heads/beam_head.inc"
 template <int WP, bool EXACT, bool CONSTRAIN> static hipError_t beam_head_launch(const BeamHeadArgs &a, long long t, hipStream_t st) {
     // static LDS is up to 33 KB (ps), dynamic up to 64 KB
     const size_t lds = (size_t)a.W * a.N * sizeof(float);
@@ -2684,194 +2170,7 @@ void beam_backtrack(const uint8_t *trace_parent, const uint8_t *trace_byte, cons
                        streams, W, count);
 }
 
-// ------------------------------------------------------------------------------------------------
-// code_head: one step of the model-driven range coder (lstm_hip_encode / lstm_hip_decode).  Per
-// stream s with more than t bytes, byte t is coded with the distribution of the state after t inputs:
-//   z = Why*h + by        k_gen_head's sum: sequential in k, separate multiply and add, the same SB grouping rule
-//   p_m = expf(z_m - max z) / s,  s = sum_m expf(z_m - max z) in index order (always max-shifted)
-//   q_m = 1 + (uint32)(p_m * 65024.0f),  cum_m = sum_{k<m} q_k (exclusive scan over the 256 threads),  T = cum_256
-// then the stream's owner lane runs one step of the carryless range coder (Subbotin; rc_* below) on (cum_x, q_x, T).
-// The float work depends only on the stream's h, so the encoder (x = the text byte) and the decoder (x found in cum) see
-// the same table at every step; `decode` is a runtime argument of one instantiation per SB.
-// ------------------------------------------------------------------------------------------------
-constexpr uint32_t RC_TOP = 1u << 24, RC_BOT = 1u << CODER_TOTAL_BITS;
-constexpr int RC_MAX_SHIFTS = 3; // bytes one coding step can move; a fourth is an error, never a loop
-__device__ __forceinline__ void rc_put(const CodeHeadArgs &a, int s, CoderState &c, uint32_t byte) {
-    const uint64_t beg = a.code_base[s], cap = a.code_base[s + 1] - beg;
-    if (c.pos < cap) a.code[beg + c.pos] = (uint8_t)byte;
-    else atomicOr(a.err, CODE_ERR_BOUND);
-    c.pos++;
-}
-__device__ __forceinline__ uint32_t rc_get(const CodeHeadArgs &a, int s, CoderState &c) {
-    const uint64_t beg = a.code_base[s], cap = a.code_base[s + 1] - beg;
-    const uint32_t byte = c.pos < cap ? a.code[beg + c.pos] : 0u; // past the end of the stream's code: 0
-    c.pos++;
-    return byte;
-}
-// after low += cum * r; range = freq * r: shift out (encoder) or in (decoder) every settled top byte
-__device__ __forceinline__ void rc_normalize(const CodeHeadArgs &a, int s, CoderState &c) {
-    for (int n = 0;; n++) {
-        if ((c.low ^ (c.low + c.range)) >= RC_TOP) { // top bytes differ
-            if (c.range >= RC_BOT) break;
-            c.range = (0u - c.low) & (RC_BOT - 1); // the carryless cut: end the interval at the next multiple of 2^16
-        }
-        if (n == RC_MAX_SHIFTS) {
-            atomicOr(a.err, CODE_ERR_BOUND);
-            break;
-        }
-        if (a.decode) c.code = (c.code << 8) | rc_get(a, s, c);
-        else rc_put(a, s, c, c.low >> 24);
-        c.low <<= 8;
-        c.range <<= 8;
-    }
-}
-template <int SB>
-__global__ __launch_bounds__(256) void k_code_head(CodeHeadArgs a, long long t) {
-    extern __shared__ __attribute__((aligned(16))) float hs[]; // [N][SB]
-    __shared__ uint32_t tab[SB][260]; // the logits, then expf terms (as float), then cum_0 .. cum_256
-    __shared__ float s_zmax[SB], s_sum[SB];
-    __shared__ uint32_t s_wave[4][SB];
-    const int m = threadIdx.x, N = a.N, s0 = blockIdx.x * SB, lane = m & 63, wave = m >> 6;
-    bool act[SB]; // (the same in every thread)
-    bool need = false;
-#pragma unroll
-    for (int j = 0; j < SB; j++) {
-        const int s = s0 + j;
-        act[j] = s < a.streams && (unsigned long long)t < a.text_off[s + 1] - a.text_off[s];
-        need |= act[j];
-    }
-    if (need) { // (uniform)
-        float *ps = reinterpret_cast<float *>(&tab[0][0]);
-        for (int i = m; i < N * SB; i += 256) {
-            const int k = i / SB, j = i - k * SB;
-            hs[i] = s0 + j < a.streams ? a.H[(size_t)(s0 + j) * N + k] : 0.0f;
-        }
-        __syncthreads();
-        float y[SB];
-#pragma unroll
-        for (int j = 0; j < SB; j++) y[j] = 0.0f;
-        for (int k0 = 0; k0 < N; k0 += 16) { // as k_gen_head: 16 loads in flight, the additions in k order
-            float wv[16];
-#pragma unroll
-            for (int i = 0; i < 16; i++) wv[i] = a.Why[(size_t)(k0 + i) * 256 + m];
-#pragma unroll
-            for (int i = 0; i < 16; i++)
-#pragma unroll
-                for (int j = 0; j < SB; j++) y[j] += wv[i] * hs[(k0 + i) * SB + j];
-        }
-        const float bym = a.by[m];
-#pragma unroll
-        for (int j = 0; j < SB; j++) {
-            y[j] = y[j] + bym; // the logit z
-            ps[j * 260 + m] = y[j];
-        }
-        __syncthreads();
-        const bool own = m < SB && s0 + m < a.streams && (unsigned long long)t < a.text_off[s0 + m + 1] - a.text_off[s0 + m];
-        if (own) { // max z of stream m (every order gives the same max)
-            float best = ps[m * 260];
-            for (int i = 1; i < 256; i++)
-                if (ps[m * 260 + i] > best) best = ps[m * 260 + i];
-            s_zmax[m] = best;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < SB; j++)
-            if (act[j]) ps[j * 260 + m] = expf(y[j] - s_zmax[j]);
-        __syncthreads();
-        if (own) {
-            float s = 0.0f;
-            for (int i = 0; i < 256; i++) s += ps[m * 260 + i];
-            s_sum[m] = s;
-        }
-        __syncthreads();
-        // quantise; exclusive integer scan of q over the 256 threads (wave scan, then the wave totals through LDS)
-        uint32_t q[SB], incl[SB];
-#pragma unroll
-        for (int j = 0; j < SB; j++) {
-            const float v = ps[j * 260 + m] / s_sum[j] * 65024.0f; // p_m * 65024, in [0, 65024] (NaN: q = 1)
-            q[j] = act[j] ? 1u + (v >= 1.0f ? (uint32_t)v : 0u) : 1u;
-            int x = (int)q[j];
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const int o = __shfl_up(x, d, 64);
-                if (lane >= d) x += o;
-            }
-            incl[j] = (uint32_t)x;
-        }
-        if (lane == 63)
-#pragma unroll
-            for (int j = 0; j < SB; j++) s_wave[wave][j] = incl[j];
-        __syncthreads(); // (also: every read of the expf terms is done)
-#pragma unroll
-        for (int j = 0; j < SB; j++) {
-            uint32_t before = 0;
-            for (int w = 0; w < wave; w++) before += s_wave[w][j];
-            tab[j][m] = before + incl[j] - q[j];
-            if (m == 255) tab[j][256] = before + incl[j];
-        }
-        __syncthreads();
-    }
-    // one owner thread per stream, spread over the four waves
-    const int j = lane * 4 + wave;
-    if (j >= SB || s0 + j >= a.streams) return;
-    const int s = s0 + j;
-    const uint64_t beg = a.text_off[s], len = a.text_off[s + 1] - beg;
-    if ((unsigned long long)t >= len) {
-        a.x_next[s] = -1;
-        return;
-    }
-    CoderState c;
-    if (t == 0) {
-        c.low = 0;
-        c.range = 0xFFFFFFFFu;
-        c.code = 0;
-        c.pad = 0;
-        c.pos = 0;
-        if (a.decode)
-            for (int i = 0; i < 4; i++) c.code = (c.code << 8) | rc_get(a, s, c);
-    } else
-        c = a.state[s];
-    const uint32_t T = tab[j][256];
-    int x = a.decode ? 0 : a.text[beg + t];
-    if (T > RC_BOT) atomicOr(a.err, CODE_ERR_TOTAL); // (cannot happen; the call fails)
-    else {
-        c.range /= T; // >= 1: range >= 2^16 >= T after every normalisation
-        if (a.decode) {
-            uint32_t v = (c.code - c.low) / c.range;
-            if (v >= T) v = T - 1; // (a damaged or truncated code: still some byte, never outside the table)
-            int lo = 0, hi = 256; // tab[j][lo] <= v < tab[j][hi]; cum is strictly increasing (every q >= 1)
-            while (hi - lo > 1) {
-                const int mid = (lo + hi) >> 1;
-                if (tab[j][mid] <= v) lo = mid;
-                else hi = mid;
-            }
-            x = lo;
-        }
-        const uint32_t cum = tab[j][x], freq = tab[j][x + 1] - cum;
-        c.low += cum * c.range;
-        c.range *= freq;
-        rc_normalize(a, s, c);
-        if (a.decode) a.text[beg + t] = (uint8_t)x;
-        else {
-            if (a.trace) {
-                uint32_t *tr = a.trace + 3 * (size_t)(beg + t);
-                tr[0] = cum;
-                tr[1] = freq;
-                tr[2] = T;
-            }
-            if (a.bits) a.bits[s] += -log2((double)freq / (double)T);
-            if ((unsigned long long)t + 1 == len) { // flush: the four bytes of low
-                for (int i = 0; i < 4; i++) {
-                    rc_put(a, s, c, c.low >> 24);
-                    c.low <<= 8;
-                }
-                a.code_len[s] = c.pos;
-            }
-        }
-    }
-    a.state[s] = c;
-    a.x_next[s] = x;
-}
+#include "heads/code_head.inc"
 void code_head(const CodeHeadArgs &a, long long t, hipStream_t st) {
     const int sb = gen_head_group(a.N, a.streams);
     const size_t lds = (size_t)sb * a.N * sizeof(float);
@@ -2891,158 +2190,7 @@ void code_head(const CodeHeadArgs &a, long long t, hipStream_t st) {
     }
 #undef CODE_HEAD_CASE
 }
-// ------------------------------------------------------------------------------------------------
-// score_head: one step of lstm_hip_score (kernels.h).  At step t every stream with more than t bytes
-// hands byte t to the recurrence, and the byte is scored with the distribution of the state after t inputs unless it is byte
-// 0 of a call with first = 0:
-//   z = Why*h + by        k_gen_head's sum: sequential in k, separate multiply and add, the same SB grouping rule
-//   CONSTRAIN             z_m = -inf where a.ctab[q * 256 + m] is 0xFFFF, q = a.qpos[position]: everything below sees the mask
-//   e_m = expf(z_m) (STABLE: expf(z_m - max z)), s = the sum of e in index order, p_m = e_m / s
-//   surprisal(m) = -log2f(p_m) (STABLE: lse_surprisal(s, max z, z_m)): k_gen_head's prompt bits, term by term
-//   entropy = -(the sum in index order of p_m * log2f(p_m), 0 where p_m is not above 0)
-//   DETAIL                rank_m = #{z_i > z_m} + #{i < m: z_i == z_m} (256 broadcast reads, as the FILTER head ranks); the
-//                         thread of rank r < top_n writes alternative r: its byte and surprisal(m)
-// Thread m owns logit m of the workgroup's SB streams; the stream's owner lane makes the three serial passes (max, s, entropy);
-// thread x, the text byte's, writes surprisal and rank and adds the surprisal to bits.  Nothing is read back and no array of
-// the call is read after it was written, so the launches of a call only chain through H.
-// ------------------------------------------------------------------------------------------------
-template <int SB, bool STABLE, bool DETAIL, bool CONSTRAIN>
-__global__ __launch_bounds__(256) void k_score_head(ScoreHeadArgs a, long long t) {
-    extern __shared__ __attribute__((aligned(16))) float hs[]; // [N][SB]
-    __shared__ float ps[SB][256]; // the logits, then the expf terms, then the entropy terms
-    __shared__ float s_zmax[STABLE ? SB : 1], s_sum[SB];
-    const int m = threadIdx.x, N = a.N, s0 = blockIdx.x * SB;
-    bool act[SB]; // stream j scores a byte at this step (the same in every thread)
-    int xs[SB];   // that byte
-    bool need = false;
-#pragma unroll
-    for (int j = 0; j < SB; j++) {
-        const int s = s0 + j;
-        act[j] = false;
-        xs[j] = 0;
-        if (s >= a.streams) continue;
-        const unsigned long long len = a.off[s + 1] - a.off[s];
-        if ((unsigned long long)t < len) {
-            xs[j] = a.text[a.off[s] + t];
-            act[j] = t >= 1 || a.first;
-        } else if ((unsigned long long)t == len) { // the state after the stream's last byte
-            if (a.h_out)
-                for (int k = m; k < N; k += 256) a.h_out[(size_t)s * N + k] = a.H[(size_t)s * N + k];
-            if (a.c_out)
-                for (int k = m; k < N; k += 256) a.c_out[(size_t)s * N + k] = a.C[(size_t)s * N + k];
-        }
-        need |= act[j];
-    }
-    const int jo = (m & 63) * 4 + (m >> 6); // one owner thread per stream, spread over the four waves
-    const bool owner = jo < SB && s0 + jo < a.streams;
-    if (owner) {
-        const int s = s0 + jo;
-        a.x_next[s] = (unsigned long long)t < a.off[s + 1] - a.off[s] ? (int)a.text[a.off[s] + t] : -1;
-    }
-    if (!need) return; // (uniform)
-    [[maybe_unused]] bool banned[CONSTRAIN ? SB : 1]; // is byte m forbidden where stream j stands?  (loaded ahead of the product)
-    if constexpr (CONSTRAIN) {
-#pragma unroll
-        for (int j = 0; j < SB; j++)
-            banned[j] = act[j] && a.ctab[(size_t)a.qpos[a.off[s0 + j] + t] * 256 + m] == 0xFFFF;
-    }
-    for (int i = m; i < N * SB; i += 256) {
-        const int k = i / SB, j = i - k * SB;
-        hs[i] = s0 + j < a.streams ? a.H[(size_t)(s0 + j) * N + k] : 0.0f;
-    }
-    __syncthreads();
-    float y[SB];
-#pragma unroll
-    for (int j = 0; j < SB; j++) y[j] = 0.0f;
-    for (int k0 = 0; k0 < N; k0 += 16) { // as k_gen_head: 16 loads in flight, the additions in k order
-        float wv[16];
-#pragma unroll
-        for (int i = 0; i < 16; i++) wv[i] = a.Why[(size_t)(k0 + i) * 256 + m];
-#pragma unroll
-        for (int i = 0; i < 16; i++)
-#pragma unroll
-            for (int j = 0; j < SB; j++) y[j] += wv[i] * hs[(k0 + i) * SB + j];
-    }
-    const float bym = a.by[m];
-#pragma unroll
-    for (int j = 0; j < SB; j++) {
-        y[j] = y[j] + bym; // the logit z
-        if constexpr (CONSTRAIN)
-            if (banned[j]) y[j] = -INFINITY;
-        ps[j][m] = y[j];
-    }
-    __syncthreads();
-    [[maybe_unused]] int rank[DETAIL ? SB : 1]; // of this thread's logit, in 0..255
-    if constexpr (DETAIL) {
-#pragma unroll
-        for (int j = 0; j < SB; j++) rank[j] = 0;
-        // i outside, the streams inside: SB broadcast reads in flight, not SB * 8 (with the streams outside, as the FILTER head
-        // ranks, the SB = 16 instantiation needs more than 256 registers).  Idle streams are ranked too; nothing reads that.
-#pragma unroll 2
-        for (int i = 0; i < 256; i++)
-#pragma unroll
-            for (int j = 0; j < SB; j++) {
-                const float zi = ps[j][i];
-                rank[j] += (zi > y[j]) | ((zi == y[j]) & (i < m));
-            }
-    }
-    const bool own = owner && ((unsigned long long)t < a.off[s0 + jo + 1] - a.off[s0 + jo]) && (t >= 1 || a.first);
-    if constexpr (STABLE) {
-        if (own) { // max z (every order gives the same max)
-            float best = ps[jo][0];
-            for (int i = 1; i < 256; i++)
-                if (ps[jo][i] > best) best = ps[jo][i];
-            s_zmax[jo] = best;
-        }
-    }
-    __syncthreads(); // (ps is overwritten below)
-#pragma unroll
-    for (int j = 0; j < SB; j++) {
-        if (!act[j]) continue;
-        if constexpr (STABLE) ps[j][m] = expf(y[j] - s_zmax[j]);
-        else ps[j][m] = expf(y[j]);
-    }
-    __syncthreads();
-    if (own) {
-        float s = 0.0f;
-        for (int i = 0; i < 256; i++) s += ps[jo][i];
-        s_sum[jo] = s;
-    }
-    __syncthreads();
-    float sp[SB]; // surprisal of byte m
-#pragma unroll
-    for (int j = 0; j < SB; j++) {
-        sp[j] = 0.0f;
-        if (!act[j]) continue;
-        const float p = ps[j][m] / s_sum[j];
-        if constexpr (STABLE) sp[j] = lse_surprisal(s_sum[j], s_zmax[j], y[j]);
-        else sp[j] = -log2f(p);
-        ps[j][m] = p > 0.0f ? p * log2f(p) : 0.0f;
-    }
-    __syncthreads();
-    if (own && a.entropy) {
-        float s = 0.0f;
-        for (int i = 0; i < 256; i++) s += ps[jo][i];
-        a.entropy[a.off[s0 + jo] + t] = -s;
-    }
-#pragma unroll
-    for (int j = 0; j < SB; j++) {
-        if (!act[j]) continue;
-        const int s = s0 + j;
-        const size_t pos = (size_t)(a.off[s] + t);
-        if (m == xs[j]) {
-            if (a.surprisal) a.surprisal[pos] = sp[j];
-            if (a.bits) a.bits[s] += (double)sp[j];
-            if constexpr (DETAIL)
-                if (a.rank) a.rank[pos] = (uint8_t)rank[j];
-        }
-        if constexpr (DETAIL)
-            if (rank[j] < a.top_n) {
-                if (a.top_byte) a.top_byte[pos * a.top_n + rank[j]] = (uint8_t)m;
-                if (a.top_bits) a.top_bits[pos * a.top_n + rank[j]] = sp[j];
-            }
-    }
-}
+#include "heads/score_head.inc"
 template <bool STABLE, bool DETAIL, bool CONSTRAIN> static hipError_t score_head_launch(const ScoreHeadArgs &a, long long t, hipStream_t st) {
     const int sb = gen_head_group(a.N, a.streams);
     const size_t lds = (size_t)sb * a.N * sizeof(float);

@@ -1,67 +1,22 @@
 // Host emulation of k_beam_head's CONSTRAIN instantiation (eigen-lstm_amd/csrc/kernels.hip) for
 // tests/test_beam_head_constrained_emulation_cpu.py, made as tests/beam_head_emulation.cc makes the unconstrained one: the
-// kernel's own text (cut out of kernels.hip by the test into beam_body.inc, with the real lse_surprisal; BeamHeadArgs into
-// beam_args.inc) compiled for the host, one std::thread per work-item, a std::barrier for __syncthreads, function-static
-// arrays for LDS, cross-lane shuffles through a table.  It checks the head's logic under a table -- the two masks, the masked
+// kernel's own text (csrc/heads/beam_head.inc, the file kernels.hip includes, with heads/head_args.h and
+// heads/lse_surprisal.h) compiled for the host over tests/device_shim.h, one std::thread per work-item, a std::barrier for
+// __syncthreads, function-static arrays for LDS, cross-lane shuffles through a table.  It checks the head's logic under a table -- the two masks, the masked
 // max and sum, the W selection rounds over the candidates that exist, tables, costs, lengths, flags, next inputs, the new
 // states, the gather -- without a device; it says nothing about the GPU build.
 //   beam_head_constrained_emulation DIR N streams W count steps stop_byte states has_accept
 // reads why, by, hs and cs ([steps][streams*W][N], the state before each step), off, prompts, table ([states][256]), q0 (the
 // slots' start states), and with has_accept accept ([states]) and frows ([count][(states + 31) / 32]) (.bin) from DIR and
 // writes the tables tp / tb, and per step xlog, costlog, lenlog, finlog, qlog, hr, cr.  Slots 1..W-1 start finished.
-#include <barrier>
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <thread>
-#include <vector>
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __launch_bounds__(x)
-#define __shared__ static
-struct Dim { int x; };
-thread_local Dim threadIdx, blockIdx;
-std::barrier<> *g_bar;
-void __syncthreads() { g_bar->arrive_and_wait(); }
-alignas(8) unsigned char g_lane[256][8];
-template <class T> T __shfl_xor(T v, int o, int) { // (every work-item of the group calls it: the kernel's rounds are uniform)
-    memcpy(g_lane[threadIdx.x], &v, sizeof(T));
-    g_bar->arrive_and_wait();
-    T r;
-    memcpy(&r, g_lane[threadIdx.x ^ o], sizeof(T));
-    g_bar->arrive_and_wait();
-    return r;
-}
-float g_hs[16 * 1024];
+#include "device_shim.h"
+#include "heads/head_args.h"
+using namespace lstmk;
+#include "heads/lse_surprisal.h"
+#include "heads/beam_head.inc"
 
-#include "beam_args.inc"
-#include "beam_body.inc"
-
-template <typename T> std::vector<T> load(const char *path) {
-    FILE *f = fopen(path, "rb"); if (!f) { perror(path); exit(1); }
-    fseek(f, 0, SEEK_END); long n = ftell(f); fseek(f, 0, SEEK_SET);
-    std::vector<T> v(n / sizeof(T)); if (fread(v.data(), 1, n, f) != (size_t)n) exit(1); fclose(f); return v;
-}
-template <typename T> void save(const char *path, const std::vector<T> &v) {
-    FILE *f = fopen(path, "wb"); fwrite(v.data(), sizeof(T), v.size(), f); fclose(f);
-}
 template <int WP, bool EXACT> void launch(const BeamHeadArgs &a, long long t) {
-    for (int b = 0; b < a.streams; b++) {
-        std::barrier<> bar(256);
-        g_bar = &bar;
-        std::vector<std::thread> th;
-        for (int m = 0; m < 256; m++)
-            th.emplace_back([&, m, b]() {
-                threadIdx.x = m; blockIdx.x = b;
-                k_beam_head<WP, EXACT, true>(a, t);
-                bar.arrive_and_drop();
-            });
-        for (auto &x : th) x.join();
-    }
+    run_blocks(a.streams, [&] { k_beam_head<WP, EXACT, true>(a, t); });
 }
 int main(int argc, char **argv) {
     if (argc != 10) return 2;

@@ -1,6 +1,6 @@
 // Host emulation of k_gen_head<SB, false, true, true, true>, the DEADLINE instantiation (eigen-lstm_amd/csrc/kernels.hip), for
 // tests/test_deadline_head_emulation_cpu.py, as tests/gen_head_constrained_emulation.cc emulates the CONSTRAIN one: the kernel's own text
-// (cut out of kernels.hip by the test into head_body.inc, GenHeadArgs into args.inc) compiled for the host, one std::thread
+// (csrc/heads/gen_head.inc, the file kernels.hip includes) compiled for the host over tests/device_shim.h, one std::thread
 // per work-item, a std::barrier for __syncthreads, function-static arrays for LDS.  It checks the head's logic -- the bytes
 // that exist within the deadline, their count in the group, the masked logits, ranks, the capped keep, nucleus walk,
 // renormalisation, CDF walk, the automaton's advance, stop index, final-state copy -- without a device; it says nothing about
@@ -10,57 +10,14 @@
 // ([states] uint16), q ([streams] int32: the state after each prompt), acc ([states] uint8), frows ([count][fwords] uint32)
 // (.bin) from DIR and writes out, kept, end, ho, xlog
 // (x_next after every step), bits, qend ([streams] the final automaton states).
-#include <atomic>
-#include <barrier>
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <mutex>
-#include <string>
-#include <thread>
-#include <vector>
-#include <cstring>
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __launch_bounds__(x)
-#define __shared__ static
-struct Dim { int x; };
-thread_local Dim threadIdx, blockIdx;
-std::barrier<> *g_bar;
-void __syncthreads() { g_bar->arrive_and_wait(); }
-std::mutex g_mu;
-int atomicMax(int *p, int v) { std::lock_guard<std::mutex> l(g_mu); int o = *p; if (v > o) *p = v; return o; }
-int atomicAdd(int *p, int v) { std::lock_guard<std::mutex> l(g_mu); int o = *p; *p = o + v; return o; }
-float lse_surprisal(float, float, float) { return 0.f; }
-float g_hs[16 * 1024];
+#include "device_shim.h"
+#include "heads/head_args.h"
+using namespace lstmk;
+#include "heads/lse_surprisal.h"
+#include "heads/gen_head.inc"
 
-#include "args.inc"
-#include "head_body.inc"
-
-template <typename T> std::vector<T> load(const char *path) {
-    FILE *f = fopen(path, "rb"); if (!f) { perror(path); exit(1); }
-    fseek(f, 0, SEEK_END); long n = ftell(f); fseek(f, 0, SEEK_SET);
-    std::vector<T> v(n / sizeof(T)); if (fread(v.data(), 1, n, f) != (size_t)n) exit(1); fclose(f); return v;
-}
-template <typename T> void save(const char *path, const std::vector<T> &v) {
-    FILE *f = fopen(path, "wb"); fwrite(v.data(), sizeof(T), v.size(), f); fclose(f);
-}
 template <int SB> void launch(const GenHeadArgs &a, long long t) {
-    const int grid = (a.streams + SB - 1) / SB;
-    for (int b = 0; b < grid; b++) {
-        std::barrier<> bar(256);
-        g_bar = &bar;
-        std::vector<std::thread> th;
-        for (int m = 0; m < 256; m++)
-            th.emplace_back([&, m, b]() {
-                threadIdx.x = m; blockIdx.x = b;
-                k_gen_head<SB, false, true, true, true>(a, t);
-                bar.arrive_and_drop();
-            });
-        for (auto &x : th) x.join();
-    }
+    run_blocks((a.streams + SB - 1) / SB, [&] { k_gen_head<SB, false, true, true, true>(a, t); });
 }
 // argv: dir N streams count steps sb mode tau keep_k nucleus top_p filter stop_byte
 int main(int argc, char **argv) {

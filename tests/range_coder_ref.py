@@ -1,4 +1,4 @@
-"""A pure-Python copy of the device's range coder (eigen-lstm_amd/csrc/kernels.hip, rc_* and k_code_head; DESIGN.md
+"""A pure-Python copy of the device's range coder (eigen-lstm_amd/csrc/heads/code_head.inc, rc_* and k_code_head; DESIGN.md
 section 3.6): the carryless 32-bit coder (Subbotin), TOP = 2^24, BOT = 2^16, a 4-byte flush, totals <= 2^16, at most three
 byte moves per coded symbol.  Test helper: it re-encodes a device trace of (cum, freq, total) and decodes codes back."""
 TOP = 1 << 24

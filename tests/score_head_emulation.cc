@@ -1,57 +1,20 @@
 // Host emulation of k_score_head (eigen-lstm_amd/csrc/kernels.hip), for
 // tests/test_score_head_emulation_cpu.py, as tests/gen_head_constrained_emulation.cc emulates the generator's head: the
-// kernel's own text (cut out of kernels.hip by the test into head_body.inc, lse_surprisal into lse.inc, ScoreHeadArgs out of
-// kernels.h into args.inc) compiled for the host, one std::thread per work-item, a std::barrier for __syncthreads,
-// function-static arrays for LDS.  It checks the head's logic -- which bytes are scored, the masked logits, the serial sums,
+// kernel's own text (csrc/heads/score_head.inc, the file kernels.hip includes, with heads/head_args.h and
+// heads/lse_surprisal.h) compiled for the host over tests/device_shim.h, one std::thread per work-item, a std::barrier for
+// __syncthreads, function-static arrays for LDS.  It checks the head's logic -- which bytes are scored, the masked logits, the serial sums,
 // ranks, alternatives, the bits, the next inputs, the final-state copy -- without a device; it says nothing about the GPU build.
 //   score_head_emulation DIR N streams steps SB stable detail constrain first top_n
 // reads why, by, hs ([steps+1][streams][N], the state before each step), off, text, tab ([states][256] uint16), qpos ([total]
 // uint16) (.bin) from DIR and writes surprisal, entropy, rank, top_byte, top_bits, bits, ho, xlog (x_next after every step).
-#include <barrier>
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <string>
-#include <thread>
-#include <vector>
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __launch_bounds__(x)
-#define __shared__ static
-struct Dim { int x; };
-thread_local Dim threadIdx, blockIdx;
-std::barrier<> *g_bar;
-void __syncthreads() { g_bar->arrive_and_wait(); }
-float g_hs[16 * 1024];
+#include "device_shim.h"
+#include "heads/head_args.h"
+using namespace lstmk;
+#include "heads/lse_surprisal.h"
+#include "heads/score_head.inc"
 
-#include "lse.inc"
-#include "args.inc"
-#include "head_body.inc"
-
-template <typename T> std::vector<T> load(const char *path) {
-    FILE *f = fopen(path, "rb"); if (!f) { perror(path); exit(1); }
-    fseek(f, 0, SEEK_END); long n = ftell(f); fseek(f, 0, SEEK_SET);
-    std::vector<T> v(n / sizeof(T)); if (fread(v.data(), 1, n, f) != (size_t)n) exit(1); fclose(f); return v;
-}
-template <typename T> void save(const char *path, const std::vector<T> &v) {
-    FILE *f = fopen(path, "wb"); fwrite(v.data(), sizeof(T), v.size(), f); fclose(f);
-}
 template <int SB, bool STABLE, bool DETAIL, bool CONSTRAIN> void launch(const ScoreHeadArgs &a, long long t) {
-    const int grid = (a.streams + SB - 1) / SB;
-    for (int b = 0; b < grid; b++) {
-        std::barrier<> bar(256);
-        g_bar = &bar;
-        std::vector<std::thread> th;
-        for (int m = 0; m < 256; m++)
-            th.emplace_back([&, m, b]() {
-                threadIdx.x = m; blockIdx.x = b;
-                k_score_head<SB, STABLE, DETAIL, CONSTRAIN>(a, t);
-                bar.arrive_and_drop();
-            });
-        for (auto &x : th) x.join();
-    }
+    run_blocks((a.streams + SB - 1) / SB, [&] { k_score_head<SB, STABLE, DETAIL, CONSTRAIN>(a, t); });
 }
 template <int SB> void launch_sb(const ScoreHeadArgs &a, long long t, int variant) {
     switch (variant) {

@@ -1,6 +1,6 @@
-"""CPU: the logic of k_beam_head's CONSTRAIN instantiation (eigen-lstm_amd/csrc/kernels.hip) run on
+"""CPU: the logic of k_beam_head's CONSTRAIN instantiation (eigen-lstm_amd/csrc/heads/beam_head.inc) run on
 the host -- the kernel's own text and the real lse_surprisal compiled with one thread per work-item
-(tests/beam_head_constrained_emulation.cc), cut out of kernels.hip exactly as tests/test_beam_head_emulation_cpu.py cuts it --
+(tests/beam_head_constrained_emulation.cc), the files tests/test_beam_head_emulation_cpu.py compiles too --
 against the constrained select32 of tests/beam_constraint_ref.py: tables, costs, lengths, finished flags, next inputs, new
 states and the gather of h / c, bit for bit.  Logits are exact by construction (parameters and states are multiples of 1/16,
 N = 16), 56 pairs of bytes have equal logits and slots often share a state, so costs tie inside a parent and across parents.
@@ -9,7 +9,6 @@ Three tables: `random` (six states, each allowing about 40 % of the bytes; the s
 early), `narrow` (a chain with two bytes per state: fewer than W candidates exist, so absent slots are selected), and `accept`
 (four states, state 3 accepting; the stop byte is allowed in states 0 and 1 but leads into the accepting state only from 0,
 and only a few bytes of state 2 lead to state 3, so the deadline removes candidates in the last two selections)."""
-import os
 import subprocess
 
 import numpy as np
@@ -17,8 +16,8 @@ import pytest
 
 import beam_constraint_ref as bcr
 import beam_ref as br
+import head_emulation
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N = 16
 f32 = np.float32
 FORBID = bcr.FORBID
@@ -27,21 +26,7 @@ STOP = 100  # of the `accept` table
 
 @pytest.fixture(scope="module")
 def emulator(tmp_path_factory):
-    d = tmp_path_factory.mktemp("beam_head_constrained")
-    src = open(os.path.join(ROOT, "eigen-lstm_amd", "csrc", "kernels.hip")).read()
-    a = src.index("__device__ __forceinline__ float lse_surprisal(")
-    lse = src[a:src.index("}\n", a) + 2]
-    body = src[src.index("__device__ __forceinline__ bool beam_before("):src.index("template <int WP, bool EXACT, bool CONSTRAIN> static hipError_t beam_head_launch(")]
-    lds = "    extern __shared__ __attribute__((aligned(16))) float hs[]; // [N][W]\n"
-    assert body.count(lds) == 1
-    (d / "beam_body.inc").write_text(lse + body.replace(lds, "    float *hs = g_hs;\n"))
-    hdr = open(os.path.join(ROOT, "eigen-lstm_amd", "csrc", "kernels.h")).read()
-    a = hdr.index("struct BeamHeadArgs {")
-    (d / "beam_args.inc").write_text(hdr[a:hdr.index("};", a) + 2] + "\n")
-    exe = d / "beam_head_constrained_emulation"
-    subprocess.check_call(["g++", "-O1", "-std=c++20", "-pthread", "-ffp-contract=off", "-I", str(d),
-                           os.path.join(ROOT, "tests", "beam_head_constrained_emulation.cc"), "-o", str(exe)])
-    return str(exe)
+    return head_emulation.build(tmp_path_factory.mktemp("beam_head_constrained"), "beam_head_constrained_emulation")
 
 
 def _table(kind, rs):

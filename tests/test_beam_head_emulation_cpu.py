@@ -1,38 +1,23 @@
-"""CPU: the logic of k_beam_head (eigen-lstm_amd/csrc/kernels.hip) run on the host -- the kernel's own
+"""CPU: the logic of k_beam_head (eigen-lstm_amd/csrc/heads/beam_head.inc) run on the host -- the kernel's own
 text and the real lse_surprisal compiled with one thread per work-item (tests/beam_head_emulation.cc) -- against beam32's
 selection (tests/beam_ref.py): tables, costs, lengths, finished flags, next inputs and the gather of the states, bit for
 bit.  Logits are exact by construction (parameters and states are multiples of 1/16, N = 16) and slots often share a state,
 so costs tie inside a parent and across parents; expf and log2f are the C library's on both sides."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
 import beam_ref as br
+import head_emulation
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N = 16
 f32 = np.float32
 
 
 @pytest.fixture(scope="module")
 def emulator(tmp_path_factory):
-    d = tmp_path_factory.mktemp("beam_head")
-    src = open(os.path.join(ROOT, "eigen-lstm_amd", "csrc", "kernels.hip")).read()
-    a = src.index("__device__ __forceinline__ float lse_surprisal(")
-    lse = src[a:src.index("}\n", a) + 2]
-    body = src[src.index("__device__ __forceinline__ bool beam_before("):src.index("template <int WP, bool EXACT, bool CONSTRAIN> static hipError_t beam_head_launch(")]
-    lds = "    extern __shared__ __attribute__((aligned(16))) float hs[]; // [N][W]\n"
-    assert body.count(lds) == 1
-    (d / "beam_body.inc").write_text(lse + body.replace(lds, "    float *hs = g_hs;\n"))
-    hdr = open(os.path.join(ROOT, "eigen-lstm_amd", "csrc", "kernels.h")).read()
-    a = hdr.index("struct BeamHeadArgs {")
-    (d / "beam_args.inc").write_text(hdr[a:hdr.index("};", a) + 2] + "\n")
-    exe = d / "beam_head_emulation"
-    subprocess.check_call(["g++", "-O1", "-std=c++20", "-pthread", "-ffp-contract=off", "-I", str(d),
-                           os.path.join(ROOT, "tests", "beam_head_emulation.cc"), "-o", str(exe)])
-    return str(exe)
+    return head_emulation.build(tmp_path_factory.mktemp("beam_head"), "beam_head_emulation")
 
 
 def _reference(Why, by, Hs, lengths, K, W, count, stop):

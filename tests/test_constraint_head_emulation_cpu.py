@@ -1,36 +1,23 @@
-"""CPU: the logic of k_gen_head's CONSTRAIN instantiation (eigen-lstm_amd/csrc/kernels.hip) run on
+"""CPU: the logic of k_gen_head's CONSTRAIN instantiation (eigen-lstm_amd/csrc/heads/gen_head.inc) run on
 the host -- the kernel's own text compiled with one thread per work-item (tests/gen_head_constrained_emulation.cc) --
 against the float32 reference of tests/constraint_ref.py: bytes, kept counts, stop indices, end states, final states and the
 inputs handed to the recurrence, bit for bit.  Logits are exact by construction (parameters and states are multiples of
 1/16, N = 16), so they hold many ties, and expf is the C library's on both sides."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
 import constraint_ref as cr
+import head_emulation
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N = 16
 f32 = np.float32
 
 
 @pytest.fixture(scope="module")
 def emulator(tmp_path_factory):
-    d = tmp_path_factory.mktemp("gen_head_constrained")
-    src = open(os.path.join(ROOT, "eigen-lstm_amd", "csrc", "kernels.hip")).read()
-    body = src[src.index("template <bool FILTER>\n__device__ __forceinline__ int gen_phase"):src.index("int gen_head_group(int N, int streams)")]
-    lds = "    extern __shared__ __attribute__((aligned(16))) float hs[]; // [N][SB]\n"
-    assert body.count(lds) == 1
-    (d / "head_body.inc").write_text(body.replace(lds, "    float *hs = g_hs;\n"))
-    hdr = open(os.path.join(ROOT, "eigen-lstm_amd", "csrc", "kernels.h")).read()
-    a = hdr.index("struct GenHeadArgs {")
-    (d / "args.inc").write_text(hdr[a:hdr.index("};", a) + 2] + "\n")
-    exe = d / "gen_head_constrained_emulation"
-    subprocess.check_call(["g++", "-O1", "-std=c++20", "-pthread", "-ffp-contract=off", "-I", str(d),
-                           os.path.join(ROOT, "tests", "gen_head_constrained_emulation.cc"), "-o", str(exe)])
-    return str(exe)
+    return head_emulation.build(tmp_path_factory.mktemp("gen_head_constrained"), "gen_head_constrained_emulation")
 
 
 def _table(rs):

@@ -1,39 +1,23 @@
-"""CPU: the logic of k_score_head (eigen-lstm_amd/csrc/kernels.hip) run on the host -- the kernel's
+"""CPU: the logic of k_score_head (eigen-lstm_amd/csrc/heads/score_head.inc) run on the host -- the kernel's
 own text compiled with one thread per work-item (tests/score_head_emulation.cc) -- against the float32 statement of the rule
 in tests/score_ref.py: surprisal, entropy, rank, alternatives and their bits, the streams' bits, the inputs handed to the
 recurrence and the final states, bit for bit.  Logits are exact by construction (parameters and states are multiples of 1/16,
 N = 16), so they hold many ties, and expf and log2f are the C library's on both sides."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
+import head_emulation
 import score_ref as sc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N = 16
 f32 = np.float32
 
 
 @pytest.fixture(scope="module")
 def emulator(tmp_path_factory):
-    d = tmp_path_factory.mktemp("score_head")
-    src = open(os.path.join(ROOT, "eigen-lstm_amd", "csrc", "kernels.hip")).read()
-    body = src[src.index("template <int SB, bool STABLE, bool DETAIL, bool CONSTRAIN>\n__global__"):
-               src.index("template <bool STABLE, bool DETAIL, bool CONSTRAIN> static hipError_t score_head_launch(")]
-    lds = "    extern __shared__ __attribute__((aligned(16))) float hs[]; // [N][SB]\n"
-    assert body.count(lds) == 1
-    (d / "head_body.inc").write_text(body.replace(lds, "    float *hs = g_hs;\n"))
-    a = src.index("__device__ __forceinline__ float lse_surprisal(")
-    (d / "lse.inc").write_text(src[a:src.index("\n}\n", a) + 3])
-    hdr = open(os.path.join(ROOT, "eigen-lstm_amd", "csrc", "kernels.h")).read()
-    a = hdr.index("struct ScoreHeadArgs {")
-    (d / "args.inc").write_text(hdr[a:hdr.index("};", a) + 2] + "\n")
-    exe = d / "score_head_emulation"
-    subprocess.check_call(["g++", "-O1", "-std=c++20", "-pthread", "-ffp-contract=off", "-I", str(d),
-                           os.path.join(ROOT, "tests", "score_head_emulation.cc"), "-o", str(exe)])
-    return str(exe)
+    return head_emulation.build(tmp_path_factory.mktemp("score_head"), "score_head_emulation")
 
 
 def _table(rs):
