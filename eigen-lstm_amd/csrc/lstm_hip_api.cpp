@@ -236,6 +236,7 @@ struct lstm_hip_ctx {
     int lent = 0;                 // students that hold this handle as their teacher (lstm_hip_destroy refuses while > 0)
     bool teacher_pass = false;    // do_forward stops before the softmax launch: Y keeps the logits
     bool last_fwd_teacher = false; // the last forward pass was such a pass (lstm_hip_backward says so)
+    bool window_lent = false;     // a student's forward pass of the call under way has overwritten xi (TeacherStream hands the rest over)
     lstm_hip_ctx *eval_h = nullptr; // internal B = 1 handle used by lstm_hip_eval_bits
     lstm_hip_ctx *texts_h = nullptr; // internal B = lanes handle used by lstm_hip_eval_texts (remade when lanes changes)
     char *gen_scratch = nullptr;    // lstm_hip_generate's working memory: grows to the largest call, freed with the handle
@@ -376,6 +377,7 @@ int teacher_forward(lstm_hip_ctx *h) {
         HIP_TRY(hipMemcpyAsync(t->H, t->H + h->carry_col * n, sizeof(float) * n, hipMemcpyDeviceToDevice, h->st));
         HIP_TRY(hipMemcpyAsync(t->C, t->C + h->carry_col * n, sizeof(float) * n, hipMemcpyDeviceToDevice, h->st));
     }
+    t->window_lent = true; // (the end of the call brings its targets and its ring form along: TeacherStream)
     t->teacher_pass = true;
     const int rc = do_forward(t);
     t->teacher_pass = false;
@@ -395,8 +397,23 @@ struct TeacherStream {
         t->st = h->st;
         return 0;
     }
+    // A teacher whose inputs a forward pass of this call overwrote gets the rest of the student's window too: the targets and
+    // the ring form the device-side slide reads, head 0, as lstm_hip_set_window would leave them.  Its window is then one
+    // window again -- the one lstm_hip_get_window returns is the one its own next lstm_hip_train_windows slides from -- and
+    // not the student's inputs over its own targets and ring.  Once per call, on the student's stream.
+    void hand_back_window() {
+        if (!t->window_lent) return;
+        t->window_lent = false;
+        const size_t bytes = sizeof(int32_t) * h->cfg.S * h->cfg.B;
+        (void)hipMemcpyAsync(t->ti, h->ti, bytes, hipMemcpyDeviceToDevice, h->st);
+        (void)hipMemcpyAsync(t->Xr, t->xi, bytes, hipMemcpyDeviceToDevice, h->st);
+        (void)hipMemcpyAsync(t->Tr, h->ti, bytes, hipMemcpyDeviceToDevice, h->st);
+        (void)hipMemsetAsync(t->head, 0, sizeof(int32_t), h->st);
+        t->pre_slid = false;
+    }
     ~TeacherStream() {
         if (!own) return;
+        hand_back_window();
         t->st = own;
         if (hipEventRecord(h->ev_soft[1], h->st) == hipSuccess) (void)hipStreamWaitEvent(own, h->ev_soft[1], 0);
         else (void)hipStreamSynchronize(h->st);

@@ -320,7 +320,11 @@ int lstm_hip_weight_drop_mask(int32_t N, double rate, uint64_t seed, uint64_t t,
  * are never in flight together.  In lstm_hip_train_windows the teacher slides as the student does (its own column carry_col
  * becomes its column 0 before every window); in the single-window calls its column 0 is what the caller left there.
  * lstm_hip_slide_state and lstm_hip_set_state on the student never touch the teacher.  lstm_hip_backward on the teacher after
- * such a pass is LSTM_HIP_ESTATE.
+ * such a pass is LSTM_HIP_ESTATE.  When a call of the student that ran a forward pass returns, the teacher's window is the
+ * student's last window as a whole, inputs AND targets, as if given to it by lstm_hip_set_window: lstm_hip_get_window on the
+ * teacher returns it, and the teacher's own next lstm_hip_train_windows slides on from it with the teacher's own text and
+ * cursors, which a student never touches.  (A teacher that is to go on training on its own text gets its window back from
+ * its caller with lstm_hip_set_window.)
  *
  * Teacher KL.  kl = sum_m q_m (log2 q_m - log2 p_tau,m) per column, in log-sum-exp form, 0 where q_m is 0; per window
  * sum_t (sum_b kl) / B_global, summed as the window loss is, without the tau^2 factor.  lstm_hip_get_teacher_kl returns the

@@ -5,6 +5,11 @@ A script is a fixed list of ops (tests/handle_replay.py: run_op) with the length
 run time, so a failure reproduces.  A shape is one row per pair of recurrence forms: N, B, flags and environment of the row
 of param_stats_cases.SHAPES with those forms (the plan depends on N, B, flags and the CU count only), the window cut to an odd
 S between 5 and 9 so that the hand-off rings' slots walk through every residue from launch to launch.
+
+The first seven scripts are those of the first version of the test and stay as they are.  The seven behind them mix the
+features added since (weight drop, accumulation, averaging and the inference source, text windows, eval_texts, soft targets
+with a borrowed teacher) into stream windows on one handle; each is listed with the adjacent runs it exists for in
+tests/test_handle_sequences_cpu.py (NEW_RUNS).
 """
 import collections
 
@@ -13,7 +18,8 @@ from param_stats_cases import FWD_PERSISTENT, FWD_COLS8, FWD_TWO_HALF, FWD_BF16,
     BWD_STEP, BWD_SMALL, BWD_PERSISTENT, BWD_COLS8, BWD_SCATTER, BWD_BF16, BWD_BF16_SCATTER, HALVES_OFF  # noqa: F401
 
 Script = collections.namedtuple("Script", "name text_len ops needs")
-# needs: "all" (every shape), "adaptive" (shapes of at most 64 streams: AD codes B streams), "inference" (INFERENCE_ROWS)
+# needs: "all" (every shape), "adaptive" (shapes of at most 64 streams: AD codes B streams), "inference" (INFERENCE_ROWS),
+# "distill" (DISTILL_ROWS)
 T1, T2, T3 = ("T", 1), ("T", 2), ("T", 3)
 FB, W, RW = ("FB",), ("W",), ("RW",)
 LONG, SHORT = 4000, 23   # SHORT: text_len - S is 14 to 18, every cursor wraps within a dozen windows
@@ -38,6 +44,35 @@ SCRIPTS = [
     Script("evaluator_refusals", LONG, [("EV", 1), T2, ("EV", 2), ("SA", 1), T1, ("SA", 2), T1, ("BAD", "stride"), T2,
                                         ("G", 6), ("BAD", "score_top_n"), ("SC", 5), ("BAD", "cursor"), T1, ("BAD", "clip"),
                                         FB], "inference"),
+    # ---- the features added since the first seven scripts, each with state of its own ----
+    # weight drop: the images alternate between the masked copy and the update launch's unmasked ones, and a host upload lands
+    # mid-mask.  The head comes to the first WD(0) with every image flag set by a forward pass alone, on MASKED images (the
+    # upload clears what the case's first forward left, the updates under the mask clear theirs): only set_weight_drop itself
+    # can mark them stale there.  Further on the flags are the update launch's when the rate changes
+    Script("drop_images", LONG, [("SP", 6), ("WD", .5), W, W, FB, ("WD", 0), T1, ("WD", .5), T2, FB, T1, ("SP", 4), T2, ("WD", 0),
+                                 T1], "all"),
+    # accumulation: accumulate-only windows between a carried slide and a fold, a cycle cut across T, W and call boundaries,
+    # pending gradient discarded by a new pair; two refusals while it is on
+    Script("accumulate", LONG, [("ACC", 3, 0), T1, ("SP", 5), T2, ("BAD", "acc_adaptive"), ("BAD", "acc_pending"), ("ACC", 3, 0), T1,
+                                FB, T1, W, T2, ("ACC", 2, 1), T3, ("ACC", 1, 0), T2], "all"),
+    # one mask per cycle, and the average takes the unmasked p; then clip and optimizer switched while a window is pending
+    Script("drop_accumulate_average", LONG, [("WD", .5), ("ACC", 2, 0), ("AVG", "ema", 2), T3, FB, T1, ("WD", 0), T2,
+                                             ("AVG", "uniform", 1), T2, ("AVG", "off"), T1, ("CLIP", 1), ("OPT", "adam"), T2], "all"),
+    # text windows between stream windows (loss mode 0 throughout).  After RW the window has empty targets, the only columns
+    # on which the text form of the softmax differs from the plain one; odd ids carry weights, which must not show in a T;
+    # under ACC(2,0) one cycle spans train_windows and train_text_windows
+    Script("texts_and_stream", LONG, [("TX", 3, 1), RW, T2, ("ACC", 2, 0), ("TX", 1, 2), T1, ("TXC", 1), RW, T2, ("ACC", 1, 0),
+                                      ("TX", 2, 1), W, ("TXC", 2), FB, ("CUR", 2), T1], "all"),
+    # every inference image is packed from a block that moved since the last call: the average, then the parameters again
+    Script("averaged_inference", LONG, [("AVG", "ema", 1), T2, ("SRC", 1), ("G", 5), ("SC", 1), T1, ("G", 5), ("EVT", 0), ("EVT", 5),
+                                        T1, ("EVT", 0), ("BS", 1), ("EN", 1), ("DE", 1), ("SRC", 0), ("G", 5)], "inference"),
+    # eval_texts: its cached handle (remade when lanes changes, given the source block at every call), its pieces in the
+    # scratch every inference call shares, never weight drop; and the average refused as a source before its first update
+    Script("eval_texts_scratch", LONG, [("AVG", "ema", 1), ("BAD", "src_average_n0"), ("G", 64), ("EVT", 0), ("G", 3), ("EVT", 5),
+                                        ("SC", 1), T1, ("EVT", 5), ("EV", 1), ("EVT", 0), ("WD", .5), T1, ("EVT", 0)], "inference"),
+    # a borrowed teacher: smoothing alone, then distillation; the teacher trains itself between its student's calls (TTR)
+    Script("distill", LONG, [("SOFT", "smooth"), T2, ("SOFT", "distill"), T2, FB, W, T1, ("TTR", 2), T2, ("TTR", 1), FB,
+                             ("BAD", "text_windows_soft"), ("SOFT", "off"), T1], "distill"),
 ]
 SCRIPT = {s.name: s for s in SCRIPTS}
 # the counter reset (LSTM_HIP_EPOCH_LIMIT): every kind of window, single launches and loops, 10 windows per direction
@@ -88,6 +123,10 @@ SHAPES = [
 # inference reads the fp32 parameters only: one fp32 two-half row, one bf16 row, one padded row and the Step control
 INFERENCE_ROWS = ("TwoHalf / Scatter, fused, 4-column pinned groups", "Bf16Halves / Bf16Scatter", "padded Persistent / Cols8",
                   "control: Step / Step")
+# distillation: the fused fp32 two-half row, a bf16 row, a padded row, an unfused row and the Step control (the teacher is
+# hidden 128 with default flags at the row's S and B, hidden 64 on the per-step engine for the control: handle_replay)
+DISTILL_ROWS = ("TwoHalf / Scatter, fused, 4-column pinned groups", "Bf16Halves / Bf16Scatter", "padded Persistent / Cols8",
+                "Cols8 / Cols8, unfused", "control: Step / Step")
 ADAPTIVE_MAX_B = 64
 
 
@@ -101,6 +140,8 @@ def runs(script, shape):
         return shape.B <= ADAPTIVE_MAX_B
     if script.needs == "inference":
         return shape.forms in INFERENCE_ROWS
+    if script.needs == "distill":
+        return shape.forms in DISTILL_ROWS
     if script.needs == "persistent":
         return persistent(shape)
     return True
