@@ -40,6 +40,19 @@
 // ahead of the product: the row differs per stream, as prompts differ in length) and the group counts the existing bytes E of
 // every stream in LDS, which caps keep in place of a.ccount[q].  The owner lane replaces a byte that does not exist by the
 // lowest existing one.  The host has checked F[count][q0], so E >= 1 at every draw and the stream ends in an accepting state.
+// PROCESS (lstm_hip_generate_processed; DESIGN.md section 3.22; implies FILTER, goes with any of the three above, and without it
+// the instantiation is the code above and nothing else): per drawn byte, in this order,
+//   a.bias      thread m adds a.bias[m] to its logit (one float add behind by; greedy draws see it, prompt bytes do not).
+//   a.no_repeat ahead of the product the group's 256 threads scan the stream's text T = a.ptext[a.ptoff[s] ..) ++ its column of
+//               a.out (draws 0 .. i - 1, strided by streams) in strides of 256 positions: where T[p .. p + n - 1) equals T's
+//               last n - 1 bytes (and p + n - 1 < |T|) byte T[p + n - 1] is banned, an atomicOr into the stream's 256-bit mask
+//               s_ban (zeroed one barrier earlier; the barrier behind the hs fill publishes it).  Thread m counts itself into
+//               s_surv[j] if its byte is valid (allowed / existing) and not banned; one more barrier behind the product, and
+//               with s_surv[j] == 0 the ban is dropped for this draw (the table always wins).  Otherwise a banned logit is
+//               -inf like a forbidden one and s_surv[j] caps keep.  The scan is linear in |T| at every draw.
+//   a.min_p     a tempered draw is always a filtered one; behind the nucleus walk (bounded by keep_k and the survivors, as
+//               before) the owner lane walks sorted[1 .. keep) and cuts at the first term below a.min_p * sorted[0].
+//   the owner lane replaces a byte that is not a survivor (non-finite logits only) by the lowest surviving one.
 // ------------------------------------------------------------------------------------------------
 // what stream s does at step t: 0 idle, 1 prompt byte scored, 2 drawn byte, 3 prompt byte not scored; *len = its prompt length
 // (*drawn: the bytes the stream draws -- the call's count, or with FILTER its own end index)
@@ -58,9 +71,10 @@ __device__ __forceinline__ bool gen_exists(const GenHeadArgs &a, const uint16_t 
     if (x == a.stop_byte) return a.accept[nx] != 0;
     return (a.frows[(size_t)left * a.fwords + (nx >> 5)] >> (nx & 31)) & 1u;
 }
-template <int SB, bool STABLE, bool FILTER, bool CONSTRAIN = false, bool DEADLINE = false>
+template <int SB, bool STABLE, bool FILTER, bool CONSTRAIN = false, bool DEADLINE = false, bool PROCESS = false>
 __global__ __launch_bounds__(256) void k_gen_head(GenHeadArgs a, long long t) {
     static_assert(FILTER || !CONSTRAIN, "CONSTRAIN implies FILTER");
+    static_assert(FILTER || !PROCESS, "PROCESS implies FILTER");
     static_assert(CONSTRAIN || !DEADLINE, "DEADLINE implies CONSTRAIN");
     HEAD_DYNAMIC_LDS(float, hs); // [N][SB]
     __shared__ float ps[SB][256];
@@ -69,10 +83,13 @@ __global__ __launch_bounds__(256) void k_gen_head(GenHeadArgs a, long long t) {
     __shared__ float sorted[FILTER ? SB : 1][FILTER ? 256 : 1]; // p in rank order
     __shared__ int s_keep[FILTER ? SB : 1], s_last[FILTER ? SB : 1]; // bytes kept; the largest kept index
     [[maybe_unused]] __shared__ int s_exist[DEADLINE ? SB : 1]; // E: the bytes that exist for each drawing stream
+    [[maybe_unused]] __shared__ unsigned s_ban[PROCESS ? SB : 1][8]; // bit b: byte b is banned by the n-gram rule (PROCESS)
+    [[maybe_unused]] __shared__ int s_surv[PROCESS ? SB : 1]; // S: the valid bytes the ban leaves each drawing stream
     const int m = threadIdx.x, N = a.N, s0 = blockIdx.x * SB;
     int phase[SB]; // (the same in every thread)
     [[maybe_unused]] int cq[CONSTRAIN ? SB : 1]; // the automaton state of each drawing stream (read before any barrier)
     [[maybe_unused]] long long left[DEADLINE ? SB : 1]; // draws each drawing stream has before its last one: R - 1
+    [[maybe_unused]] long long drew[PROCESS ? SB : 1]; // bytes each drawing stream has drawn so far: i
     bool need = false;
 #pragma unroll
     for (int j = 0; j < SB; j++) {
@@ -85,6 +102,7 @@ __global__ __launch_bounds__(256) void k_gen_head(GenHeadArgs a, long long t) {
         need |= phase[j] == 1 || phase[j] == 2;
         if constexpr (CONSTRAIN) cq[j] = phase[j] == 2 ? a.cstate[s] : 0;
         if constexpr (DEADLINE) left[j] = phase[j] == 2 ? a.count - 1 - (t - len) : 0;
+        if constexpr (PROCESS) drew[j] = phase[j] == 2 ? t - len : 0;
         if (t == len + drawn) { // the state after the stream's last input
             if (a.h_out)
                 for (int k = m; k < N; k += 256) a.h_out[(size_t)s * N + k] = a.H[(size_t)s * N + k];
@@ -103,11 +121,45 @@ __global__ __launch_bounds__(256) void k_gen_head(GenHeadArgs a, long long t) {
         }
         if constexpr (DEADLINE)
             if (m < SB) s_exist[m] = 0; // (counted behind the barrier below)
+        if constexpr (PROCESS) {
+            if (m < SB * 8) (&s_ban[0][0])[m] = 0u;
+            if (m < SB) s_surv[m] = 0; // (counted behind the barrier below)
+            if (a.no_repeat > 0) { // (uniform) the n-gram scan: position p of the text to thread p % 256
+                __syncthreads();
+                const long long n1 = a.no_repeat - 1;
+#pragma unroll
+                for (int j = 0; j < SB; j++) {
+                    if (phase[j] != 2) continue;
+                    const int s = s0 + j;
+                    const uint8_t *text = a.ptext + a.ptoff[s];
+                    const long long tl = (long long)(a.ptoff[s + 1] - a.ptoff[s]), tlen = tl + drew[j];
+                    auto at = [&](long long p) -> unsigned { return p < tl ? text[p] : a.out[(size_t)(p - tl) * a.streams + s]; };
+                    for (long long p = m; p + n1 < tlen; p += 256) {
+                        long long k = 0;
+                        while (k < n1 && at(p + k) == at(tlen - n1 + k)) k++;
+                        if (k == n1) {
+                            const unsigned b = at(p + n1);
+                            atomicOr(&s_ban[j][b >> 5], 1u << (b & 31));
+                        }
+                    }
+                }
+            }
+        }
         for (int i = m; i < N * SB; i += 256) {
             const int k = i / SB, j = i - k * SB;
             hs[i] = s0 + j < a.streams ? a.H[(size_t)(s0 + j) * N + k] : 0.0f;
         }
         __syncthreads();
+        [[maybe_unused]] bool cut[PROCESS ? SB : 1]; // is byte m banned by the n-gram rule for stream j?
+        if constexpr (PROCESS) {
+#pragma unroll
+            for (int j = 0; j < SB; j++) {
+                cut[j] = phase[j] == 2 && ((s_ban[j][m >> 5] >> (m & 31)) & 1u);
+                bool valid = phase[j] == 2 && !cut[j];
+                if constexpr (CONSTRAIN) valid = valid && !banned[j];
+                if (valid) atomicAdd(&s_surv[j], 1); // (read behind the barrier that follows the product)
+            }
+        }
         float y[SB];
 #pragma unroll
         for (int j = 0; j < SB; j++) y[j] = 0.0f;
@@ -125,18 +177,27 @@ __global__ __launch_bounds__(256) void k_gen_head(GenHeadArgs a, long long t) {
             for (int j = 0; j < SB; j++)
                 if (phase[j] == 2 && !banned[j]) atomicAdd(&s_exist[j], 1); // (read behind the filter's barriers)
         }
+        [[maybe_unused]] float bias_m = 0.0f;
+        if constexpr (PROCESS) {
+            if (a.bias) bias_m = a.bias[m];
+            __syncthreads(); // s_surv (and s_exist) are complete
+        }
         const float bym = a.by[m];
         bool any_max = false;
         [[maybe_unused]] bool any_filter = false;
 #pragma unroll
         for (int j = 0; j < SB; j++) {
             y[j] = y[j] + bym; // the logit z
+            if constexpr (PROCESS)
+                if (a.bias && phase[j] == 2) y[j] = y[j] + bias_m;
             if constexpr (CONSTRAIN)
                 if (banned[j]) y[j] = -INFINITY;
+            if constexpr (PROCESS)
+                if (cut[j] && s_surv[j] > 0) y[j] = -INFINITY; // (no survivor: the ban is dropped for this draw)
             ps[j][m] = y[j];
             any_max |= phase[j] == 2 && a.mode != 0;
             if constexpr (STABLE) any_max |= phase[j] == 1 || phase[j] == 2;
-            if constexpr (FILTER) any_filter |= phase[j] == 2 && a.mode != 2 && (CONSTRAIN || a.filter);
+            if constexpr (FILTER) any_filter |= phase[j] == 2 && a.mode != 2 && (CONSTRAIN || PROCESS || a.filter);
         }
         [[maybe_unused]] int rank[FILTER ? SB : 1]; // of this thread's logit: #{z_i > z_m} + #{i < m: z_i == z_m}, in 0..255
         if constexpr (FILTER)
@@ -213,6 +274,8 @@ __global__ __launch_bounds__(256) void k_gen_head(GenHeadArgs a, long long t) {
                             const int allowed = a.ccount[a.cstate[s0 + jo]];
                             if (allowed < keep) keep = allowed;
                         }
+                        if constexpr (PROCESS)
+                            if (s_surv[jo] > 0 && s_surv[jo] < keep) keep = s_surv[jo]; // (S <= the valid bytes)
                         if (a.nucleus) {
                             float sum = 0.0f;
                             for (int r = 0; r < keep; r++) { // (past keep_k the nucleus no longer matters)
@@ -223,6 +286,15 @@ __global__ __launch_bounds__(256) void k_gen_head(GenHeadArgs a, long long t) {
                                 }
                             }
                         }
+                        if constexpr (PROCESS)
+                            if (a.min_p > 0.0f) { // behind the nucleus walk: the first term below min_p * the largest
+                                const float thr = a.min_p * sorted[jo][0];
+                                for (int r = 1; r < keep; r++)
+                                    if (sorted[jo][r] < thr) {
+                                        keep = r;
+                                        break;
+                                    }
+                            }
                         s_keep[jo] = keep;
                     }
                 }
@@ -255,7 +327,7 @@ __global__ __launch_bounds__(256) void k_gen_head(GenHeadArgs a, long long t) {
         if (a.mode == 2) {
             x = s_arg[j];
             kept = 1;
-        } else if (FILTER && (CONSTRAIN || a.filter)) {
+        } else if (FILTER && (CONSTRAIN || PROCESS || a.filter)) {
             kept = s_keep[j];
             const float r = (float)a.u[i * a.streams + s];
             float sum = 0.0f; // of the kept terms, in index order
@@ -281,7 +353,21 @@ __global__ __launch_bounds__(256) void k_gen_head(GenHeadArgs a, long long t) {
                 }
             }
         }
-        if constexpr (CONSTRAIN) { // advance the automaton; a forbidden byte gives way to the state's lowest allowed one
+        if constexpr (PROCESS) { // a byte that is no survivor gives way to the lowest surviving one; the automaton advances
+            const bool drop = s_surv[j] == 0;
+            [[maybe_unused]] const uint16_t *row = nullptr;
+            if constexpr (CONSTRAIN) row = a.ctab + (size_t)a.cstate[s] * 256;
+            auto survives = [&](int b) {
+                if (!drop && ((s_ban[j][b >> 5] >> (b & 31)) & 1u)) return false;
+                if constexpr (DEADLINE) return gen_exists(a, row, b, a.count - 1 - (long long)i);
+                else if constexpr (CONSTRAIN) return row[b] != 0xFFFF;
+                else return true;
+            };
+            if (!survives(x))
+                for (x = 0; x < 255 && !survives(x); x++) {}
+            if constexpr (CONSTRAIN)
+                if (row[x] != 0xFFFF) a.cstate[s] = row[x];
+        } else if constexpr (CONSTRAIN) { // advance the automaton; a forbidden byte gives way to the state's lowest allowed one
             const uint16_t *row = a.ctab + (size_t)a.cstate[s] * 256;
             if constexpr (DEADLINE) { // a byte that does not exist gives way to the lowest existing one
                 const long long lf = a.count - 1 - (long long)i;

@@ -40,6 +40,14 @@ struct GenHeadArgs {
     const uint8_t *accept;      // [states] nonzero: a stream may end there
     const uint32_t *frows;      // [count][fwords] bit q of row R: an accepted end can be reached from q with R more bytes
     int fwords;                 // words of one row: (states + 31) / 32
+    // logit processors (lstm_hip_generate_processed): read only by the PROCESS instantiation, which
+    // gen_head takes when `process` is set (`end` is set with it); all null / 0 otherwise
+    int process;                // 1: some processor is on (a tempered draw is then a filtered one)
+    const float *bias;          // [256] added to the logits of a drawn byte (null: none)
+    float min_p;                // (float)min_p: 0 off, else terms below min_p * the largest term are cut
+    int no_repeat;              // n: 0 off, else 1..64
+    const uint8_t *ptext;       // each stream's history ++ prompt, concatenated (null: all empty); with no_repeat
+    const uint64_t *ptoff;      // streams + 1 offsets into ptext; with no_repeat
 };
 
 // ---- beam search (lstm_hip_beam_search): per step beam_head on the state after t inputs, then

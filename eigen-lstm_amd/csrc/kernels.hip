@@ -2081,7 +2081,30 @@ template <bool STABLE> static hipError_t gen_head_launch(const GenHeadArgs &a, l
         if (const hipError_t e = grant_lds<k_gen_head<SB, STABLE, true, __VA_ARGS__>, 32768>(lds)) return e;                \
         hipLaunchKernelGGL((k_gen_head<SB, STABLE, true, __VA_ARGS__>), grid, dim3(256), lds, st, a, t);                    \
         break;
-    if (a.frows) switch (sb) { // (the caller sets a.ctab and a.end too)
+    // PROCESS (logit processors; the caller sets a.end too): static LDS grows by 36 bytes a stream (s_ban, s_surv), 576 at
+    // SB = 16, so the 33 KB above still holds
+    if (a.process && a.frows) switch (sb) {
+            GEN_HEAD_FILTER_CASE(1, true, true, true)
+            GEN_HEAD_FILTER_CASE(2, true, true, true)
+            GEN_HEAD_FILTER_CASE(4, true, true, true)
+            GEN_HEAD_FILTER_CASE(8, true, true, true)
+            GEN_HEAD_FILTER_CASE(16, true, true, true)
+        }
+    else if (a.process && a.ctab) switch (sb) {
+            GEN_HEAD_FILTER_CASE(1, true, false, true)
+            GEN_HEAD_FILTER_CASE(2, true, false, true)
+            GEN_HEAD_FILTER_CASE(4, true, false, true)
+            GEN_HEAD_FILTER_CASE(8, true, false, true)
+            GEN_HEAD_FILTER_CASE(16, true, false, true)
+        }
+    else if (a.process) switch (sb) {
+            GEN_HEAD_FILTER_CASE(1, false, false, true)
+            GEN_HEAD_FILTER_CASE(2, false, false, true)
+            GEN_HEAD_FILTER_CASE(4, false, false, true)
+            GEN_HEAD_FILTER_CASE(8, false, false, true)
+            GEN_HEAD_FILTER_CASE(16, false, false, true)
+        }
+    else if (a.frows) switch (sb) { // (the caller sets a.ctab and a.end too)
             GEN_HEAD_FILTER_CASE(1, true, true)
             GEN_HEAD_FILTER_CASE(2, true, true)
             GEN_HEAD_FILTER_CASE(4, true, true)

@@ -2315,6 +2315,19 @@ int lstm_hip_generate_accepting(lstm_hip_t *h, int32_t streams, const uint8_t *p
                                 const float *h0, const float *c0, const lstm_hip_sampling *opt, const double *u, int32_t count,
                                 uint8_t *out, double *bits, float *h_out, float *c_out, int32_t *out_len, uint16_t *kept,
                                 const lstm_hip_beam_constraint *bc, const int32_t *start_state, int32_t *end_state) {
+    return lstm_hip_generate_processed(h, streams, prompts, prompt_off, h0, c0, opt, u, count, out, bits, h_out, c_out, out_len, kept,
+                                       bc, start_state, end_state, nullptr);
+}
+
+// Logit processors: a bias, min-p or the n-gram rule selects gen_head's PROCESS instantiation
+// (a.process set).  The block is checked here before anything is launched; the bias and each stream's history ++ prompt (the
+// text the n-gram rule scans, with the drawn bytes behind it) are the last pieces of the scratch layout: with lp NULL or
+// everything off every offset, upload and launch is lstm_hip_generate_accepting's.
+int lstm_hip_generate_processed(lstm_hip_t *h, int32_t streams, const uint8_t *prompts, const uint64_t *prompt_off,
+                                const float *h0, const float *c0, const lstm_hip_sampling *opt, const double *u, int32_t count,
+                                uint8_t *out, double *bits, float *h_out, float *c_out, int32_t *out_len, uint16_t *kept,
+                                const lstm_hip_beam_constraint *bc, const int32_t *start_state, int32_t *end_state,
+                                const lstm_hip_logit_processors *lp) {
     CHECK(h);
     if (!opt) return fail(LSTM_HIP_EINVAL, "generate: null sampling options");
     if (opt->size != sizeof(lstm_hip_sampling))
@@ -2338,6 +2351,47 @@ int lstm_hip_generate_accepting(lstm_hip_t *h, int32_t streams, const uint8_t *p
     const uint64_t max_len = prompt_off ? longest(prompt_off, streams) : 0;
     const int N = h->cfg.N;
     if (N > 16384) return fail(LSTM_HIP_EINVAL, "generate: hidden width %d above 16384", N);
+    // the logit processors: the block is checked, then each stream's history ++ prompt is laid out for the n-gram scan
+    std::vector<uint8_t> ptext;
+    std::vector<uint64_t> ptoff;
+    if (lp) {
+        if (lp->size != sizeof(lstm_hip_logit_processors))
+            return fail(LSTM_HIP_EINVAL, "generate: logit processors of %u bytes, expected %zu", lp->size, sizeof(lstm_hip_logit_processors));
+        if (lp->bias)
+            for (int b = 0; b < 256; b++)
+                if (!std::isfinite(lp->bias[b]))
+                    return fail(LSTM_HIP_EINVAL, "generate: bias[%d] = %g is not finite (to ban a byte, restrict a table with "
+                                "lstm_hip_dfa_restrict)", b, (double)lp->bias[b]);
+        if (!(lp->min_p >= 0.0 && lp->min_p <= 1.0)) return fail(LSTM_HIP_EINVAL, "generate: min_p must be in [0, 1] (got %g)", lp->min_p);
+        if (lp->no_repeat < 0 || lp->no_repeat > 64)
+            return fail(LSTM_HIP_EINVAL, "generate: no_repeat must be in [0, 64] (got %d)", lp->no_repeat);
+        if (lp->history && !lp->history_off) return fail(LSTM_HIP_EINVAL, "generate: history without history_off");
+        if (lp->history_off && !lp->history) return fail(LSTM_HIP_EINVAL, "generate: history_off without history");
+        if (lp->history_off)
+            if (int rc = check_offsets("generate", "history_off", lp->history_off, streams)) return rc;
+        if (lp->history && lp->no_repeat == 0) return fail(LSTM_HIP_EINVAL, "generate: history given with no_repeat 0: nothing reads it");
+        if (lp->no_repeat > 0) {
+            ptoff.assign((size_t)streams + 1, 0);
+            uint64_t most = 0;
+            for (int s = 0; s < streams; s++) {
+                const uint64_t hl = lp->history_off ? lp->history_off[s + 1] - lp->history_off[s] : 0;
+                const uint64_t pl = prompt_off ? prompt_off[s + 1] - prompt_off[s] : 0;
+                ptoff[s + 1] = ptoff[s] + hl + pl;
+                most = std::max(most, hl + pl);
+            }
+            if (most + (uint64_t)count > 65536)
+                return fail(LSTM_HIP_EINVAL, "generate: no_repeat over a text of %llu bytes (the longest history + prompt, + count), "
+                            "above 65536: the scan is linear in the text at every draw", (unsigned long long)(most + (uint64_t)count));
+            ptext.resize(ptoff[streams]);
+            for (int s = 0; s < streams; s++) {
+                uint8_t *to = ptext.data() + ptoff[s];
+                if (lp->history_off) to = std::copy(lp->history + lp->history_off[s], lp->history + lp->history_off[s + 1], to);
+                if (prompt_off) std::copy(prompts + prompt_off[s], prompts + prompt_off[s + 1], to);
+            }
+        }
+    }
+    const bool lp_bias = lp && lp->bias, lp_min_p = lp && lp->min_p > 0.0, lp_ngram = lp && lp->no_repeat > 0;
+    const bool process = lp_bias || lp_min_p || lp_ngram; // gen_head's PROCESS instantiation
     // the constraint: the table is checked, then every stream's state walks its prompt
     std::vector<int32_t> cstate; // [streams] the state after each prompt
     std::vector<uint16_t> ccount; // [states] allowed bytes
@@ -2360,13 +2414,13 @@ int lstm_hip_generate_accepting(lstm_hip_t *h, int32_t streams, const uint8_t *p
     const size_t n = (size_t)N * streams, nl = (size_t)h->N_log * streams, nd = (size_t)count * streams;
     const bool keep = h_out || c_out;
     const bool top_k_on = opt->top_k >= 1 && opt->top_k <= 255, nucleus = opt->top_p < 1.0;
-    const bool controls = top_k_on || nucleus || opt->stop_byte >= 0 || kept || con; // gen_head's FILTER instantiation
+    const bool controls = top_k_on || nucleus || opt->stop_byte >= 0 || kept || con || process; // gen_head's FILTER instantiation
 
     float4 *Ufwd;
-    float *H, *Cs, *G, *ho, *stage;
+    float *H, *Cs, *G, *ho, *stage, *d_bias;
     int32_t *xi, *d_end, *d_q;
-    uint64_t *d_off;
-    uint8_t *d_prompts, *d_out, *d_acc;
+    uint64_t *d_off, *d_ptoff;
+    uint8_t *d_prompts, *d_out, *d_acc, *d_ptext;
     uint32_t *d_F;
     double *d_u, *d_bits;
     uint16_t *d_kept, *d_tab, *d_cnt;
@@ -2378,6 +2432,7 @@ int lstm_hip_generate_accepting(lstm_hip_t *h, int32_t streams, const uint8_t *p
     mem.piece(d_end, streams, controls).piece(d_kept, nd, kept != nullptr);
     mem.piece(d_tab, 256 * (size_t)Q, con != nullptr).piece(d_cnt, Q, con != nullptr).piece(d_q, streams, con != nullptr);
     mem.piece(d_acc, Q, accept != nullptr).piece(d_F, (size_t)count * fwords, accept != nullptr);
+    mem.piece(d_bias, 256, lp_bias).piece(d_ptoff, (size_t)streams + 1, lp_ngram).piece(d_ptext, ptext.size(), !ptext.empty());
     if (int rc = mem.commit(h)) return rc;
 
     // start state (padding rows zero), inputs
@@ -2397,6 +2452,11 @@ int lstm_hip_generate_accepting(lstm_hip_t *h, int32_t streams, const uint8_t *p
     if (accept) { // rows 0 .. count - 1: draw i reads row count - 1 - i
         HIP_TRY(hipMemcpyAsync(d_acc, accept, (size_t)Q, hipMemcpyHostToDevice, h->st));
         if (count > 0) HIP_TRY(hipMemcpyAsync(d_F, frows.data(), sizeof(uint32_t) * (size_t)count * fwords, hipMemcpyHostToDevice, h->st));
+    }
+    if (lp_bias) HIP_TRY(hipMemcpyAsync(d_bias, lp->bias, sizeof(float) * 256, hipMemcpyHostToDevice, h->st));
+    if (lp_ngram) {
+        HIP_TRY(hipMemcpyAsync(d_ptoff, ptoff.data(), sizeof(uint64_t) * ((size_t)streams + 1), hipMemcpyHostToDevice, h->st));
+        if (d_ptext) HIP_TRY(hipMemcpyAsync(d_ptext, ptext.data(), ptext.size(), hipMemcpyHostToDevice, h->st));
     }
     const Model m = model_of(h);
     RUN(K_PACK_U, pack_U(m.U, Ufwd, nullptr, N, h->st));
@@ -2432,6 +2492,12 @@ int lstm_hip_generate_accepting(lstm_hip_t *h, int32_t streams, const uint8_t *p
     a.accept = d_acc;
     a.frows = d_F;
     a.fwords = fwords;
+    a.process = process;
+    a.bias = d_bias;
+    a.min_p = lp ? (float)lp->min_p : 0.0f;
+    a.no_repeat = lp ? lp->no_repeat : 0;
+    a.ptext = d_ptext;
+    a.ptoff = d_ptoff;
     const bool stable = (h->cfg.flags & LSTM_HIP_STABLE_SOFTMAX) != 0;
     const long long steps = (long long)max_len + count; // inputs of the longest stream
     int cur = 0;

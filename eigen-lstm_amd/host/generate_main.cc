@@ -4,6 +4,7 @@
 //
 //   lstm_generate --load PREFIX [--score FILE ...] [--score-bytes FILE [--top N]] [--count C --streams K --prime TEXT|--prime-file F
 //                 --temperature T --top-k K --top-p P --stop-byte B --seed S --utf8 --allow SPEC --ban SPEC --regex PATTERN
+//                 --logit-bias BIAS --min-p P --no-repeat-ngram N
 //                 | --beams W --nbest K --length-alpha A [--constrain-search --utf8 --allow SPEC --ban SPEC --regex PATTERN]]
 //                 [--score-streams K [--score-warmup W]] [--fast-math] [--stable-softmax] [--device D]
 //
@@ -49,6 +50,13 @@
 // characters only); --allow / --ban then restrict the resulting table (lstm_hip_dfa_restrict).  With --beams
 // --constrain-search the same table and accepting states go to the search.  A pattern the compiler refuses ends the program
 // with the library's message, which names the offending byte of the pattern.
+// --logit-bias BIAS, --min-p P and --no-repeat-ngram N are the logit processors of lstm_hip_generate_processed, applied to drawn
+// bytes only, under whatever table the options above made: BIAS is comma-separated SPEC:VALUE items in the range syntax of
+// --allow (0x41-0x5a:-2.5,10:+1) whose VALUE is added to the logits of those bytes (greedy decoding sees it); P (0 < P <= 1)
+// cuts the bytes less than P times as likely as the most likely one; N (1..64) never draws a byte that would complete an N-byte
+// sequence the sample, prompt included, already holds -- it ends the loops of --temperature 0 -- and gives way where the table
+// would otherwise have no byte left.  The scan behind N is linear in the sample's length at every draw.  All three are options of
+// drawing and are refused with --beams: beam search, the scorer and the coders take no processors.
 // --stable-softmax scores and draws at temperature 1 with the
 // max-shifted softmax (LSTM_HIP_STABLE_SOFTMAX), for checkpoints whose logits pass expf's range.
 #include "../../include/lstm_hip.h"
@@ -71,6 +79,7 @@ const char *const kUsage =
     "                     [--count C --streams K --prime TEXT|--prime-file F\n"
     "                     --temperature T --top-k K --top-p P --stop-byte B --seed S\n"
     "                     --utf8 --allow SPEC --ban SPEC --regex PATTERN\n"
+    "                     --logit-bias BIAS --min-p P --no-repeat-ngram N\n"
     "                     | --beams W --nbest K --length-alpha A\n"
     "                       [--constrain-search --utf8 --allow SPEC --ban SPEC --regex PATTERN]]\n"
     "                     [--score-streams K [--score-warmup W]] [--fast-math] [--stable-softmax] [--device D]\n"
@@ -88,6 +97,11 @@ const char *const kUsage =
     "  --regex PATTERN  draw whole matches of this byte regular expression only (re.fullmatch on bytes; a quantifier\n"
     "                 binds the last byte).  With --stop-byte B: a match, then B.  Without it: a match of exactly --count\n"
     "                 bytes.  --utf8 intersects with well-formed UTF-8; --allow / --ban restrict the result\n"
+    "  --logit-bias BIAS  add VALUE to the logits of the listed bytes before every draw: comma-separated SPEC:VALUE items\n"
+    "                 (0x41-0x5a:-2.5,10:+1); greedy decoding sees it too\n"
+    "  --min-p P      draw among the bytes at least P times as likely as the most likely one (0 < P <= 1; 0: off)\n"
+    "  --no-repeat-ngram N  never draw a byte that would complete an N-byte sequence the sample (prompt included) already\n"
+    "                 holds (1..64; 0: off); a table (--utf8, --allow, --ban, --regex) wins where the two leave no byte\n"
     "  --beams W      beam search with W hypotheses per stream (1..32) instead of drawing; W x --streams <= 4096;\n"
     "  --constrain-search  with --beams: let --utf8 / --allow / --ban constrain the search to the continuations they\n"
     "                 accept (without it they are refused with --beams); hypotheses that do not exist are not printed\n"
@@ -158,7 +172,33 @@ void parse_spec(const std::string &opt, const std::string &v, uint8_t flag[256])
     }
 }
 
+// BIAS: comma-separated SPEC:VALUE items, SPEC one byte or range as above, VALUE a finite number with an optional sign
+// (0x41-0x5a:-2.5,10:+1); a byte listed twice takes the later value
+void parse_bias(const std::string &opt, const std::string &v, float bias[256]) {
+    auto bad = [&]() { usage(opt + " needs items byte-or-range:value such as 0x41-0x5a:-2.5,10:+1 (finite values), got '" + v + "'"); };
+    if (v.empty()) bad();
+    for (size_t at = 0; at <= v.size();) {
+        const size_t comma = std::min(v.find(',', at), v.size());
+        const std::string item = v.substr(at, comma - at);
+        const size_t colon = item.find(':');
+        if (colon == std::string::npos || colon == 0 || colon + 1 == item.size() || item.find(',') != std::string::npos) bad();
+        uint8_t flag[256] = {};
+        parse_spec(opt, item.substr(0, colon), flag);
+        const std::string num = item.substr(colon + 1);
+        char *end = nullptr;
+        const double x = strtod(num.c_str(), &end);
+        if (*end != '\0' || !std::isfinite(x) || !std::isfinite((float)x)) bad();
+        for (int b = 0; b < 256; b++)
+            if (flag[b]) bias[b] = (float)x;
+        at = comma + 1;
+    }
+}
+
 struct Options {
+    bool has_bias = false;   // --logit-bias
+    float bias[256] = {};
+    double min_p = 0.0;      // --min-p
+    long no_repeat = 0;      // --no-repeat-ngram
     std::string load, prime, prime_file;
     bool has_prime = false;
     std::vector<std::string> sampling_opts; // options that only mean something with --count
@@ -228,6 +268,20 @@ Options parse(int argc, char **argv) {
         } else if (a == "--stop-byte") {
             o.stop_byte = parse_int(a, val(), 0, 255);
             o.sampling_opts.push_back(a);
+        } else if (a == "--logit-bias") {
+            parse_bias(a, val(), o.bias);
+            o.has_bias = true;
+            o.sampling_opts.push_back(a);
+            o.draw_opts.push_back(a);
+        } else if (a == "--min-p") {
+            o.min_p = parse_double(a, val());
+            if (!(o.min_p <= 1.0)) usage(a + " needs a number in [0, 1]");
+            o.sampling_opts.push_back(a);
+            o.draw_opts.push_back(a);
+        } else if (a == "--no-repeat-ngram") {
+            o.no_repeat = parse_int(a, val(), 0, 64);
+            o.sampling_opts.push_back(a);
+            o.draw_opts.push_back(a);
         } else if (a == "--seed") {
             o.seed = (uint32_t)parse_int(a, val(), 0, 0xFFFFFFFFL);
             o.sampling_opts.push_back(a);
@@ -477,7 +531,16 @@ int main(int argc, char **argv) {
         const lstm_hip_sampling opt{(uint32_t)sizeof(lstm_hip_sampling), o.temperature, (int32_t)o.top_k, o.top_p, (int32_t)o.stop_byte};
         std::vector<int32_t> out_len(K);
         std::vector<int32_t> end_state(K, 0);
-        if (o.table.empty())
+        if (o.has_bias || o.min_p > 0.0 || o.no_repeat > 0) { // logit processors, under whatever table the options made
+            const lstm_hip_constraint con{(uint32_t)sizeof(lstm_hip_constraint), o.states, o.table.data()};
+            const lstm_hip_beam_constraint bc{(uint32_t)sizeof(lstm_hip_beam_constraint), &con, o.has_regex ? o.accept.data() : nullptr};
+            const lstm_hip_logit_processors lp{(uint32_t)sizeof(lstm_hip_logit_processors), o.has_bias ? o.bias : nullptr, o.min_p,
+                                               (int32_t)o.no_repeat, nullptr, nullptr};
+            const bool tab = !o.table.empty();
+            CK(lstm_hip_generate_processed(h, K, prompts.data(), off.data(), nullptr, nullptr, &opt, u.empty() ? nullptr : u.data(), C,
+                                           out.data(), nullptr, nullptr, nullptr, out_len.data(), nullptr, tab ? &bc : nullptr, nullptr,
+                                           tab ? end_state.data() : nullptr, &lp));
+        } else if (o.table.empty())
             CK(lstm_hip_generate_ex(h, K, prompts.data(), off.data(), nullptr, nullptr, &opt, u.empty() ? nullptr : u.data(), C,
                                     out.data(), nullptr, nullptr, nullptr, out_len.data(), nullptr));
         else if (o.has_regex) { // whole matches only: the accepting states and the deadline of --count

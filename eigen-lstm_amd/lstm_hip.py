@@ -57,6 +57,11 @@ class _BeamConstraint(C.Structure):  # lstm_hip_beam_constraint
     _fields_ = [("size", C.c_uint32), ("con", C.POINTER(_Constraint)), ("accept", C.POINTER(C.c_uint8))]
 
 
+class _LogitProcessors(C.Structure):  # lstm_hip_logit_processors
+    _fields_ = [("size", C.c_uint32), ("bias", C.POINTER(C.c_float)), ("min_p", C.c_double), ("no_repeat", C.c_int32),
+                ("history", C.POINTER(C.c_uint8)), ("history_off", C.POINTER(C.c_uint64))]
+
+
 class _Scoring(C.Structure):  # lstm_hip_scoring
     _fields_ = [("size", C.c_uint32), ("first", C.c_int32), ("top_n", C.c_int32), ("con", C.POINTER(_Constraint))]
 
@@ -107,6 +112,7 @@ SYMBOLS = [
     "lstm_hip_set_soft_targets", "lstm_hip_get_soft_targets", "lstm_hip_get_teacher_kl",
     "lstm_hip_set_grad_accumulation", "lstm_hip_get_grad_accumulation", "lstm_hip_get_grad_accumulator",
     "lstm_hip_set_grad_accumulator",
+    "lstm_hip_generate_processed",
 ]
 
 
@@ -756,7 +762,8 @@ class Lstm:
         return out, h0, c0
 
     def generate(self, prompts=None, count=0, u=None, temperature=1.0, h0=None, c0=None, streams=None, score=False,
-                 top_k=0, top_p=1.0, stop_byte=None, info=False, constraint=None, start_state=None, accept=None):
+                 top_k=0, top_p=1.0, stop_byte=None, info=False, constraint=None, start_state=None, accept=None,
+                 logit_bias=None, min_p=0.0, no_repeat_ngram=0, history=None):
         """lstm_hip_generate: `streams` independent streams, each fed its prompt (bytes or a uint8 array) and then `count`
         drawn bytes.  u: draws [count, streams] (may be None only at temperature 0); h0, c0: [streams, N] or None (zeros).
         Returns (out [count, streams] uint8, bits [streams] float64 -- the prompts' summed -log2 p, or None unless
@@ -772,7 +779,12 @@ class Lstm:
         accept: [states] flags, nonzero where a stream may end, with the meaning it has in beam_search
         (lstm_hip_generate_accepting): a byte is drawn only where an accepted end can still be reached within `count`, so
         every stream ends in an accepting state, by its stop byte or with exactly `count` bytes.  accept=None is the call
-        made without the argument."""
+        made without the argument.
+        logit_bias (a 256-array or a {byte: value} dict, added to the logits of drawn bytes), min_p (0 < min_p <= 1: cut the
+        terms below min_p times the largest) and no_repeat_ngram (n in 1..64: no byte is drawn that would complete an n-gram
+        the stream's text already holds; history: per stream the bytes that precede its prompt for this rule only) are the
+        logit processors of lstm_hip_generate_processed.  They go with every argument above; with all four at their
+        defaults the calls are those made without them."""
         if streams is None:
             streams = len(prompts) if prompts is not None else (np.asarray(h0).shape[0] if h0 is not None else
                                                                 (np.asarray(u).reshape(count, -1).shape[1] if u is not None and count > 0 else 1))
@@ -802,6 +814,9 @@ class Lstm:
             raise LstmHipError("generate: start_state given without a constraint")
         if constraint is None and accept is not None:
             raise LstmHipError("generate: accept given without a constraint")
+        if logit_bias is not None or min_p != 0.0 or no_repeat_ngram != 0 or history is not None:
+            return self._generate_processed(args, tail, streams, count, temperature, top_k, top_p, stop_byte, info, constraint,
+                                            start_state, accept, logit_bias, min_p, no_repeat_ngram, history, out, bits, h, c)
         if constraint is None and top_k == 0 and top_p == 1.0 and stop_byte is None and not info:
             _chk(self.lib.lstm_hip_generate(*args, C.c_double(temperature), *tail))
             return out, bits, h, c
@@ -829,6 +844,47 @@ class Lstm:
         _chk(self.lib.lstm_hip_generate_ex(*args, C.byref(opt), *tail, _ptr(out_len, C.c_int32),
                                            _ptr(kept, C.c_uint16) if info else None))
         return (out, bits, h, c, {"out_len": out_len, "kept": kept}) if info else (out, bits, h, c)
+
+    def _generate_processed(self, args, tail, streams, count, temperature, top_k, top_p, stop_byte, info, constraint,
+                            start_state, accept, logit_bias, min_p, no_repeat_ngram, history, out, bits, h, c):
+        """generate() with a logit processor on: one lstm_hip_generate_processed call"""
+        opt = _Sampling(C.sizeof(_Sampling), float(temperature), int(top_k), float(top_p),
+                        -1 if stop_byte is None else int(stop_byte))
+        out_len = np.zeros(streams, np.int32)
+        kept = np.zeros((count, streams), np.uint16)
+        bc = q0 = q1 = None
+        if constraint is not None:
+            table = np.ascontiguousarray(constraint, dtype=np.uint16)
+            assert table.ndim == 2 and table.shape[1] == 256, table.shape
+            con = _Constraint(C.sizeof(_Constraint), table.shape[0], _ptr(table, C.c_uint16))
+            q0 = None if start_state is None else np.ascontiguousarray(start_state, dtype=np.int32).reshape(streams)
+            q1 = np.zeros(streams, np.int32)
+            acc = None if accept is None else np.ascontiguousarray(np.asarray(accept).reshape(table.shape[0]) != 0, dtype=np.uint8)
+            bc = _BeamConstraint(C.sizeof(_BeamConstraint), C.pointer(con), _ptr(acc, C.c_uint8) if acc is not None else None)
+        bias = None
+        if isinstance(logit_bias, dict):
+            bias = np.zeros(256, np.float32)
+            for b, v in logit_bias.items():
+                bias[int(b)] = v
+        elif logit_bias is not None:
+            bias = _f32(logit_bias).reshape(256)
+        d_h = d_hoff = None
+        if history is not None:
+            assert len(history) == streams, (len(history), streams)
+            d_h, d_hoff = _offsets(_bytes_list(history))
+        lp = _LogitProcessors(C.sizeof(_LogitProcessors), _ptr(bias) if bias is not None else None, float(min_p),
+                              int(no_repeat_ngram), _ptr(d_h, C.c_uint8) if d_h is not None else None,
+                              _ptr(d_hoff, C.c_uint64) if d_hoff is not None else None)
+        _chk(self.lib.lstm_hip_generate_processed(
+            *args, C.byref(opt), *tail, _ptr(out_len, C.c_int32), _ptr(kept, C.c_uint16) if info else None,
+            C.byref(bc) if bc is not None else None, _ptr(q0, C.c_int32) if q0 is not None else None,
+            _ptr(q1, C.c_int32) if q1 is not None else None, C.byref(lp)))
+        if not info:
+            return out, bits, h, c
+        extra = {"out_len": out_len, "kept": kept}
+        if q1 is not None:
+            extra["end_state"] = q1
+        return out, bits, h, c, extra
 
     def score(self, texts, h0=None, c0=None, first=False, top_n=0, constraint=None, start_state=None):
         """lstm_hip_score: what the model thinks of every byte of `texts` (bytes or uint8 arrays, one stream each; h0, c0:

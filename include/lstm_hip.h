@@ -691,6 +691,54 @@ int lstm_hip_generate_accepting(lstm_hip_t *h, int32_t streams, const uint8_t *p
                                 const lstm_hip_beam_constraint *bc /* NULL: exactly lstm_hip_generate_ex */,
                                 const int32_t *start_state /* [streams], may be NULL: all 0 */,
                                 int32_t *end_state /* [streams], may be NULL */);
+/* ---- the same call with logit processors: an additive bias, min-p, and the no-repeat n-gram rule,
+ *      applied on the device inside the step loop, with no readback.  lstm_hip_generate_accepting is a thin caller of this
+ *      function with lp = NULL, and two cases are exactly that call, with its scratch offsets, uploads, kernel instantiations
+ *      and bytes: lp == NULL, and a block with everything off (bias NULL, min_p 0, no_repeat 0).  Everything
+ *      lstm_hip_generate_accepting documents holds, except what follows.  Only DRAWN bytes are processed: prompt scoring
+ *      (bits) ignores all of it, as it ignores a constraint.  Per drawn byte of stream s, from z_m = Why*h + by summed as ever:
+ *        1 bias      z_m <- z_m + bias[m], one float add.  Greedy draws see it too.
+ *        2 valid     V_m: the table allows byte m (with accept: byte m EXISTS under the deadline); without a table every m.
+ *        3 ban       T = history[s] ++ prompt[s] ++ the bytes drawn so far, len = |T|, n = no_repeat.  If len >= n - 1, suf is
+ *                    the last n - 1 bytes of T and B_m holds iff some j with j + n - 1 < len has T[j .. j+n-1) == suf and
+ *                    T[j+n-1] == m (n = 1 bans every byte that occurs in T); otherwise B is empty.  This is the
+ *                    no_repeat_ngram_size rule of the usual toolkits, on bytes.  The history is never fed and never scored.
+ *                    COST: the device scans T at every draw (256 positions at a time per stream, up to n - 1 byte compares
+ *                    each): linear in len per draw, quadratic over a call; hence the 65536-byte limit below.
+ *        4 survive   S = #{m : V_m and not B_m}.  If S == 0 the ban is DROPPED FOR THIS DRAW (B <- empty, S = #V): the table
+ *                    always wins, and the guarantees of lstm_hip_generate_constrained and lstm_hip_generate_accepting (out is
+ *                    accepted, the end state accepts) hold unchanged.  z'_m = z_m where V_m and not B_m, -inf otherwise.
+ *        5 filter    rank, max, expf and the normalising sum see z'.  Rules 1-6 of lstm_hip_generate_ex apply with one more
+ *                    cap: thr = (float)min_p * sorted[0] (one float multiply; sorted: the normalised terms in rank order),
+ *                    keep_m = the first rank r with sorted[r] < thr, 256 if there is none (>= 1), and
+ *                    keep = min(keep_k, keep_p, keep_m, S).  The owner lane takes the nucleus walk FIRST, bounded by keep_k and
+ *                    S as before, and the min-p walk SECOND, over the ranks the nucleus walk kept (the minimum is the same).
+ *        6 draw      a draw with any processor on is ALWAYS a filtered draw, as a constrained one is: the kept terms are divided
+ *                    by their index-order float sum, past every edge the byte is the largest kept index, kept = keep.  Greedy
+ *                    draws take the argmax of z', lowest index on ties, kept = 1; they ignore min_p.
+ *        7 replace   a chosen byte that is no survivor (non-finite logits only) gives way to the lowest surviving byte.
+ *        chaining    without accept, a second call with h0 / c0 = h_out / c_out, start_state = end_state, no prompt and
+ *                    history[s] = the first call's history ++ prompt ++ drawn bytes gives the bytes and states of the one long
+ *                    call, bit for bit.
+ *      Beam search, the scorer, the coders and lstm_hip_sample take no processors.
+ *      LSTM_HIP_EINVAL (the handle stays usable, nothing is launched, the message says which), beside those of
+ *      lstm_hip_generate_accepting: lp->size wrong; a bias entry that is NaN or infinite (to ban a byte, restrict a table:
+ *      lstm_hip_dfa_restrict); min_p NaN, negative or above 1; no_repeat outside 0..64; history without history_off or
+ *      history_off without history; history_off not starting at 0 or decreasing; history given with no_repeat 0; with
+ *      no_repeat > 0, the longest (history + prompt) + count above 65536. */
+typedef struct lstm_hip_logit_processors {
+    uint32_t size;               /* sizeof(lstm_hip_logit_processors); anything else: LSTM_HIP_EINVAL */
+    const float *bias;           /* [256] added to the logits of every drawn byte, or NULL: none */
+    double   min_p;              /* 0: off; 0 < min_p <= 1 */
+    int32_t  no_repeat;          /* 0: off; n in 1..64: no n-gram of a stream's text occurs twice */
+    const uint8_t  *history;     /* bytes that precede each stream's prompt for the n-gram rule only, or NULL */
+    const uint64_t *history_off; /* [streams + 1]; NULL with history NULL */
+} lstm_hip_logit_processors;
+int lstm_hip_generate_processed(lstm_hip_t *h, int32_t streams, const uint8_t *prompts, const uint64_t *prompt_off,
+                                const float *h0, const float *c0, const lstm_hip_sampling *opt, const double *u, int32_t count,
+                                uint8_t *out, double *bits, float *h_out, float *c_out, int32_t *out_len, uint16_t *kept,
+                                const lstm_hip_beam_constraint *bc, const int32_t *start_state, int32_t *end_state,
+                                const lstm_hip_logit_processors *lp /* NULL: exactly lstm_hip_generate_accepting */);
 /* ---- per-byte scores: what the model thinks of every byte of given texts.  Stream s is
  *      text[text_off[s] .. text_off[s+1]), 1 <= streams <= 4096; empty streams are allowed (no entries, h_out = the start
  *      state).  h0 / c0 / h_out / c_out are N x streams as in lstm_hip_generate (NULL = zeros / not wanted); h_out is the
