@@ -419,6 +419,41 @@ struct EvalArgs {
 void eval_window(const EvalArgs &a, int64_t w, int cus, hipStream_t st);
 void eval_fold(const EvalArgs &a, int64_t w, int cus, hipStream_t st);
 
+// ---- hidden states of many texts (lstm_hip_embed_texts; the kernels are embed.hip), around the same
+//      unchanged forward path and on the same plan tables as above, made from offsets that count every stream one byte
+//      longer: a stream of L bytes has L steps, step j feeds byte j, and row r + 1 of a window with j0 = EVAL_STEPS *
+//      (w - first[s]) holds position j0 + r, the state after inputs 0 .. j0 + r.  off / skip are the caller's.
+//      embed_window is eval_window under that rule: xi = byte j for j < L; ti = byte j + 1 where j + 1 < L and
+//      j + 1 >= skip[s], else -1; column 0 as there.
+//      embed_fold, behind the softmax launch.  bits: as eval_fold, over the rows that have a target.  Per wanted source x
+//      (0: H, 1: C; a source is wanted when last[x] is not null, and then sum, mean, maxv and last of it are all there): a
+//      workgroup per (lane, 32 float4s of N) loads the lane's live rows at or above skip[s] at once, as 8 chunks of 16 rows,
+//      and adds (double)v into four doubles per float4 chunk after chunk, in row order, keeping four float maxima; both are
+//      carried in sum[x] / maxv[x] [streams][N] from the stream's window before (fresh in its first); in the window where the stream ends it writes last[x] = the row of position L - 1,
+//      mean[x] = (float)(sum / (double)count) and, for an empty pool, mean[x] = maxv[x] = +0.0f.  Rows past the stream's end are
+//      never read.  picks [pick_lo, pick_hi) of the table (lane, row, k) are the window's: row `row` of lane `lane` goes to
+//      column k of picked[x] ([npick][N], null: not wanted).  One launch of at most 8 * cus workgroups of 256 threads, plain
+//      vector loads and stores only.
+struct EmbedArgs {
+    const uint8_t *text;
+    const uint64_t *off;    // [streams + 1]
+    const uint64_t *skip;   // [streams]
+    const int32_t *slot;    // [windows][lanes]
+    const int64_t *first;   // [streams]
+    const float *H0, *C0;   // [streams][N]
+    int32_t *xi, *ti;       // [EVAL_STEPS + 1][lanes]
+    float *H, *C;           // [EVAL_STEPS + 1][lanes][N]
+    const float *colloss;   // [EVAL_STEPS][lanes]
+    double *bits;           // [streams]
+    double *sum[2];         // [streams][N] each
+    float *mean[2], *maxv[2], *last[2];
+    const int32_t *picks;   // [npick][3], sorted by window
+    float *picked[2];       // [npick][N]
+    int lanes, N;
+};
+void embed_window(const EmbedArgs &a, int64_t w, int cus, hipStream_t st);
+void embed_fold(const EmbedArgs &a, int64_t w, int64_t pick_lo, int64_t pick_hi, int cus, hipStream_t st);
+
 // ---- B = 1 recurrence for the evaluator / sampler (OV/lstm_eigen_class_CUDA/lstm.cc:578-720)
 // One workgroup with b1_lds_bytes(N) of dynamic LDS, which the caller checks against the device's opt-in limit first; both
 // return the status of the grant and of the launch.

@@ -2872,6 +2872,23 @@ static int eval_status(const char *which) { // (not among the window's timed ker
     return 0;
 }
 
+// the cached internal handle of lstm_hip_eval_texts and lstm_hip_embed_texts: remade when `lanes` changes
+static int texts_handle(lstm_hip_t *h, int lanes) {
+    HIP_TRY(hipStreamSynchronize(h->st));
+    if (h->texts_h && h->texts_h->cfg.B != lanes) {
+        (void)lstm_hip_destroy(h->texts_h);
+        h->texts_h = nullptr;
+    }
+    if (!h->texts_h) {
+        lstm_hip_config c = h->cfg; // (cfg.N is the parent's internal width, as for the B = 1 evaluator's handle)
+        c.S = LSTM_HIP_EVAL_STEPS + 1;
+        c.B = lanes;
+        c.flags = (h->cfg.flags & (LSTM_HIP_FAST_MATH | LSTM_HIP_STABLE_SOFTMAX | LSTM_HIP_STEP_KERNELS)) | LSTM_HIP_NO_FUSED_GRADS;
+        if (int rc = lstm_hip_create(&c, &h->texts_h)) return rc;
+    }
+    return 0;
+}
+
 int64_t lstm_hip_text_plan(int32_t steps, int32_t lanes, int32_t streams, const uint64_t *text_off, int32_t *lane_of,
                            int64_t *first_window) {
     return checked_plan("text_plan", steps, lanes, streams, text_off, lane_of, first_window, nullptr);
@@ -2903,18 +2920,7 @@ int lstm_hip_eval_texts(lstm_hip_t *h, int32_t streams, const uint8_t *text, con
     std::vector<int64_t> first(streams);
     const int64_t windows = text_plan(LSTM_HIP_EVAL_STEPS, lanes, streams, text_off, nullptr, first.data(), &slot);
 
-    HIP_TRY(hipStreamSynchronize(h->st));
-    if (h->texts_h && h->texts_h->cfg.B != lanes) {
-        (void)lstm_hip_destroy(h->texts_h);
-        h->texts_h = nullptr;
-    }
-    if (!h->texts_h) {
-        lstm_hip_config c = h->cfg; // (cfg.N is the parent's internal width, as for the B = 1 evaluator's handle)
-        c.S = LSTM_HIP_EVAL_STEPS + 1;
-        c.B = lanes;
-        c.flags = (h->cfg.flags & (LSTM_HIP_FAST_MATH | LSTM_HIP_STABLE_SOFTMAX | LSTM_HIP_STEP_KERNELS)) | LSTM_HIP_NO_FUSED_GRADS;
-        if (int rc = lstm_hip_create(&c, &h->texts_h)) return rc;
-    }
+    if (int rc = texts_handle(h, lanes)) return rc;
     lstm_hip_ctx *e = h->texts_h;
 
     const size_t n = (size_t)N * streams, nl = (size_t)h->N_log * streams, tot = (size_t)total;
@@ -2993,6 +2999,175 @@ int lstm_hip_eval_texts(lstm_hip_t *h, int32_t streams, const uint8_t *text, con
     if (d_sur) HIP_TRY(hipMemcpyAsync(surprisal, d_sur, sizeof(float) * tot, hipMemcpyDeviceToHost, h->st));
     if (int rc = download_states(h, h_out, c_out, ho, ho ? ho + n : nullptr, stage, streams)) return rc;
     HIP_TRY(hipStreamSynchronize(h->st));
+    return 0;
+}
+
+// Hidden states of many texts (include/lstm_hip.h): lstm_hip_eval_texts' device loop with
+// embed_window / embed_fold around the same do_forward, on the plan of offsets that count every stream one byte longer
+// (n = L steps: the last byte is fed).  The outputs are blocks of internal-width columns in the call's scratch, [streams][N]
+// per pool and source and [npick][N] per picked source, brought home through download_states like any state.
+int lstm_hip_embed_texts(lstm_hip_t *h, int32_t streams, const uint8_t *text, const uint64_t *text_off, const float *h0, const float *c0,
+                         const uint64_t *skip, const lstm_hip_eval_opt *opt, const uint64_t *pick, int64_t npick,
+                         const lstm_hip_embedding *out, float *elapsed_ms) {
+    CHECK(h);
+    if (opt && opt->size != sizeof(lstm_hip_eval_opt))
+        return fail(LSTM_HIP_EINVAL, "embed_texts: options of %u bytes, expected %zu", opt->size, sizeof(lstm_hip_eval_opt));
+    if (opt && (opt->lanes < 0 || opt->lanes > 4096))
+        return fail(LSTM_HIP_EINVAL, "embed_texts: lanes must be in [0, 4096] (got %d)", opt->lanes);
+    if (streams < 1) return fail(LSTM_HIP_EINVAL, "embed_texts: streams must be >= 1 (got %d)", streams);
+    if (int rc = check_offsets("embed_texts", "text_off", text_off, streams)) return rc;
+    const uint64_t total = text_off[streams];
+    if (total > 0 && !text) return fail(LSTM_HIP_EINVAL, "embed_texts: null text with %llu bytes to read", (unsigned long long)total);
+    if (!out) return fail(LSTM_HIP_EINVAL, "embed_texts: null out");
+    if (out->size != sizeof(lstm_hip_embedding))
+        return fail(LSTM_HIP_EINVAL, "embed_texts: outputs of %u bytes, expected %zu", out->size, sizeof(lstm_hip_embedding));
+    if (npick < 0) return fail(LSTM_HIP_EINVAL, "embed_texts: npick must be >= 0 (got %lld)", (long long)npick);
+    if (npick > 0 && !pick) return fail(LSTM_HIP_EINVAL, "embed_texts: null pick with npick = %lld", (long long)npick);
+    for (int64_t k = 0; k < npick; k++) {
+        if (pick[k] >= total)
+            return fail(LSTM_HIP_EINVAL, "embed_texts: pick[%lld] = %llu is not below text_off[streams] = %llu", (long long)k,
+                        (unsigned long long)pick[k], (unsigned long long)total);
+        if (k > 0 && pick[k] <= pick[k - 1])
+            return fail(LSTM_HIP_EINVAL, "embed_texts: pick must be strictly increasing (pick[%lld] = %llu after %llu)", (long long)k,
+                        (unsigned long long)pick[k], (unsigned long long)pick[k - 1]);
+    }
+    const int pick_sources = (out->picked_h ? 1 : 0) + (out->picked_c ? 1 : 0);
+    if (npick == 0 && pick_sources) return fail(LSTM_HIP_EINVAL, "embed_texts: picked_h / picked_c given with npick = 0");
+    if (npick > 0 && !pick_sources) return fail(LSTM_HIP_EINVAL, "embed_texts: npick = %lld with neither picked_h nor picked_c", (long long)npick);
+    const int N = h->cfg.N;
+    const uint64_t pick_limit = (uint64_t)1 << 30;
+    if ((uint64_t)npick > pick_limit / ((uint64_t)N * sizeof(float) * (pick_sources ? pick_sources : 1)))
+        return fail(LSTM_HIP_EINVAL, "embed_texts: %lld picked positions of width %d from %d source(s) need more than %llu bytes",
+                    (long long)npick, N, pick_sources, (unsigned long long)pick_limit);
+    const int lanes = opt && opt->lanes > 0 ? opt->lanes : h->cfg.B;
+
+    // the plan of streams one byte longer: a stream of L bytes gets ceil(L / 128) windows, an empty one no lane
+    std::vector<uint64_t> off1(streams + 1);
+    for (int32_t s = 0; s <= streams; s++) off1[s] = text_off[s] + (uint64_t)s;
+    std::vector<int32_t> slot, lane_of(streams);
+    std::vector<int64_t> first(streams);
+    const int64_t windows = text_plan(LSTM_HIP_EVAL_STEPS, lanes, streams, off1.data(), lane_of.data(), first.data(), &slot);
+
+    // every pick as (lane, row, k), sorted by window; pick_at[w] .. pick_at[w + 1] are window w's
+    std::vector<int64_t> pick_at(windows + 1, 0);
+    std::vector<int32_t> table((size_t)npick * 3);
+    {
+        std::vector<int64_t> win(npick);
+        int32_t s = 0;
+        for (int64_t k = 0; k < npick; k++) { // (increasing picks: the stream index only moves forward)
+            while (pick[k] >= text_off[s + 1]) s++;
+            win[k] = first[s] + (int64_t)((pick[k] - text_off[s]) / LSTM_HIP_EVAL_STEPS);
+            pick_at[win[k] + 1]++;
+        }
+        for (int64_t w = 0; w < windows; w++) pick_at[w + 1] += pick_at[w];
+        std::vector<int64_t> next(pick_at.begin(), pick_at.end() - 1);
+        s = 0;
+        for (int64_t k = 0; k < npick; k++) {
+            while (pick[k] >= text_off[s + 1]) s++;
+            int32_t *t = &table[(size_t)next[win[k]]++ * 3];
+            t[0] = lane_of[s];
+            t[1] = (int32_t)((pick[k] - text_off[s]) % LSTM_HIP_EVAL_STEPS) + 1;
+            t[2] = (int32_t)k;
+        }
+    }
+
+    if (int rc = texts_handle(h, lanes)) return rc;
+    lstm_hip_ctx *e = h->texts_h;
+
+    const size_t n = (size_t)N * streams, tot = (size_t)total, np = (size_t)N * npick;
+    const bool want[2] = {out->mean_h || out->max_h || out->last_h, out->mean_c || out->max_c || out->last_c};
+    const size_t stage_cols = std::max((size_t)streams, (size_t)npick);
+    float *H0, *C0, *stage, *pool[2], *picked[2];
+    double *d_sum[2], *d_bits;
+    uint64_t *d_off, *d_skip;
+    int64_t *d_first;
+    int32_t *d_slot, *d_picks;
+    uint8_t *d_text;
+    Scratch mem;
+    mem.piece(H0, n).piece(C0, n).piece(stage, 2 * (size_t)h->N_log * stage_cols, h->padded());
+    for (int x = 0; x < 2; x++) mem.piece(d_sum[x], n, want[x]).piece(pool[x], 3 * n, want[x]); // mean | max | last
+    mem.piece(picked[0], np, out->picked_h != nullptr).piece(picked[1], np, out->picked_c != nullptr);
+    mem.piece(d_picks, table.size(), npick > 0);
+    mem.piece(d_off, streams + 1).piece(d_skip, streams).piece(d_first, streams).piece(d_slot, slot.size());
+    mem.piece(d_text, tot).piece(d_bits, streams);
+    if (int rc = mem.commit(h)) return rc;
+
+    HIP_TRY(hipMemcpyAsync(e->P, infer_block(h), sizeof(float) * h->pl.total, hipMemcpyDeviceToDevice, h->st));
+    e->packed = false;
+    if (int rc = upload_states(h, h0, c0, H0, C0, stage, streams)) return rc;
+    for (int x = 0; x < 2; x++) { // a stream without a byte never reaches the fold: empty pools, last = its start state
+        if (!want[x]) continue;
+        HIP_TRY(hipMemsetAsync(pool[x], 0, sizeof(float) * 2 * n, h->st));
+        HIP_TRY(hipMemcpyAsync(pool[x] + 2 * n, x ? C0 : H0, sizeof(float) * n, hipMemcpyDeviceToDevice, h->st));
+    }
+    HIP_TRY(hipMemcpyAsync(d_off, text_off, sizeof(uint64_t) * (streams + 1), hipMemcpyHostToDevice, h->st));
+    if (skip) HIP_TRY(hipMemcpyAsync(d_skip, skip, sizeof(uint64_t) * streams, hipMemcpyHostToDevice, h->st));
+    else HIP_TRY(hipMemsetAsync(d_skip, 0, sizeof(uint64_t) * streams, h->st));
+    HIP_TRY(hipMemcpyAsync(d_first, first.data(), sizeof(int64_t) * streams, hipMemcpyHostToDevice, h->st));
+    if (!slot.empty()) HIP_TRY(hipMemcpyAsync(d_slot, slot.data(), sizeof(int32_t) * slot.size(), hipMemcpyHostToDevice, h->st));
+    if (npick) HIP_TRY(hipMemcpyAsync(d_picks, table.data(), sizeof(int32_t) * table.size(), hipMemcpyHostToDevice, h->st));
+    if (tot) HIP_TRY(hipMemcpyAsync(d_text, text, tot, hipMemcpyHostToDevice, h->st));
+    HIP_TRY(hipMemsetAsync(d_bits, 0, sizeof(double) * streams, h->st));
+    HIP_TRY(hipStreamSynchronize(h->st)); // (the host vectors are pageable: their copies are done; the loop is on e's stream)
+
+    EmbedArgs a{};
+    a.text = d_text;
+    a.off = d_off;
+    a.skip = d_skip;
+    a.slot = d_slot;
+    a.first = d_first;
+    a.H0 = H0;
+    a.C0 = C0;
+    a.xi = e->xi;
+    a.ti = e->ti;
+    a.H = e->H;
+    a.C = e->C;
+    a.colloss = e->colloss;
+    a.bits = d_bits;
+    for (int x = 0; x < 2; x++) {
+        a.sum[x] = d_sum[x];
+        a.mean[x] = pool[x];
+        a.maxv[x] = want[x] ? pool[x] + n : nullptr;
+        a.last[x] = want[x] ? pool[x] + 2 * n : nullptr;
+        a.picked[x] = picked[x];
+    }
+    a.picks = d_picks;
+    a.lanes = lanes;
+    a.N = N;
+    struct LoopMode { // the internal handle is back in its standalone mode on every return path
+        lstm_hip_ctx *e;
+        ~LoopMode() { e->in_loop = false, e->keep_outputs = true; }
+    } loop_mode{e};
+    e->in_loop = true;
+    e->keep_outputs = false;
+    if (elapsed_ms) HIP_TRY(hipEventRecord(e->evt0, e->st));
+    for (int64_t w = 0; w < windows; w++) {
+        embed_window(a, w, e->plan.n_cus, e->st);
+        if (int rc = eval_status("embed_window")) return rc;
+        if (int rc = do_forward(e)) return rc;
+        embed_fold(a, w, pick_at[w], pick_at[w + 1], e->plan.n_cus, e->st);
+        if (int rc = eval_status("embed_fold")) return rc;
+    }
+    if (elapsed_ms) {
+        HIP_TRY(hipEventRecord(e->evt1, e->st));
+        HIP_TRY(hipEventSynchronize(e->evt1));
+        HIP_TRY(hipEventElapsedTime(elapsed_ms, e->evt0, e->evt1));
+    }
+    HIP_TRY(hipStreamSynchronize(e->st));
+    if (int rc = check_abort(e)) return rc;
+
+    if (out->bits) HIP_TRY(hipMemcpyAsync(out->bits, d_bits, sizeof(double) * streams, hipMemcpyDeviceToHost, h->st));
+    if (int rc = download_states(h, out->mean_h, out->mean_c, pool[0], pool[1], stage, streams)) return rc;
+    if (int rc = download_states(h, out->max_h, out->max_c, a.maxv[0], a.maxv[1], stage, streams)) return rc;
+    if (int rc = download_states(h, out->last_h, out->last_c, a.last[0], a.last[1], stage, streams)) return rc;
+    if (npick)
+        if (int rc = download_states(h, out->picked_h, out->picked_c, picked[0], picked[1], stage, (int)npick)) return rc;
+    HIP_TRY(hipStreamSynchronize(h->st));
+    if (out->count)
+        for (int32_t s = 0; s < streams; s++) {
+            const uint64_t L = text_off[s + 1] - text_off[s], k = skip ? skip[s] : 0;
+            out->count[s] = k < L ? (int64_t)(L - k) : 0;
+        }
     return 0;
 }
 

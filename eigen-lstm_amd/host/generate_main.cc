@@ -7,6 +7,8 @@
 //                 --logit-bias BIAS --min-p P --no-repeat-ngram N
 //                 | --beams W --nbest K --length-alpha A [--constrain-search --utf8 --allow SPEC --ban SPEC --regex PATTERN]]
 //                 [--score-streams K [--score-warmup W]] [--fast-math] [--stable-softmax] [--device D]
+//   lstm_generate --load PREFIX --embed FILE [--embed-delim B] [--pool last|mean|max|concat] [--embed-cell] [--embed-streams K]
+//                 --embed-out OUT
 //
 // --load reads the five-file text checkpoint PREFIX_{W,U,Why,b,by}.txt (checkpoint.h); N is the rows of W / 4.
 // --score runs every FILE as one stream from h = c = 0 and prints "FILE: X.XXXXX bits/char (n bytes)" per file (bits over
@@ -57,6 +59,12 @@
 // sequence the sample, prompt included, already holds -- it ends the loops of --temperature 0 -- and gives way where the table
 // would otherwise have no byte left.  The scan behind N is linear in the sample's length at every draw.  All three are options of
 // drawing and are refused with --beams: beam search, the scorer and the coders take no processors.
+// --embed FILE writes what the model computed about every record of FILE (lstm_hip_embed_texts): FILE is cut after every
+// delimiter byte (--embed-delim B, 0..255, default 10; the delimiter stays the last byte of its record and a last record may
+// lack it, as lstm --records cuts), all records are embedded in one call from h = c = 0, --embed-streams K of them side by side
+// (1..4096, default 64), and OUT gets one tab-separated row of %.9g floats per record: the hidden state pooled as --pool says
+// -- last (the default: the state after the record's last byte), mean or max over all its positions, or concat: last, max,
+// mean, in that order -- and with --embed-cell the same of the cell state behind it.  It goes with neither --count nor --score*.
 // --stable-softmax scores and draws at temperature 1 with the
 // max-shifted softmax (LSTM_HIP_STABLE_SOFTMAX), for checkpoints whose logits pass expf's range.
 #include "../../include/lstm_hip.h"
@@ -83,6 +91,12 @@ const char *const kUsage =
     "                     | --beams W --nbest K --length-alpha A\n"
     "                       [--constrain-search --utf8 --allow SPEC --ban SPEC --regex PATTERN]]\n"
     "                     [--score-streams K [--score-warmup W]] [--fast-math] [--stable-softmax] [--device D]\n"
+    "       lstm_generate --load PREFIX --embed FILE [--embed-delim B] [--pool last|mean|max|concat] [--embed-cell]\n"
+    "                     [--embed-streams K] --embed-out OUT\n"
+    "  --embed FILE   cut FILE into records after every delimiter byte (--embed-delim B, default 10) and write one\n"
+    "                 tab-separated row per record to --embed-out OUT: the hidden state pooled as --pool says (last, mean,\n"
+    "                 max, or concat = last, max, mean), with --embed-cell the cell state too; --embed-streams K records\n"
+    "                 side by side (1..4096, default 64)\n"
     "  --score-streams K   with --score: cut every FILE into K streams (1..4096) and score all files in one call on the\n"
     "                 trainer's forward path; --score-warmup W feeds W bytes before each later piece's first scored byte\n"
     "  --score-bytes FILE  one row per byte: offset, byte, surprisal, entropy, rank; then the --score line of FILE\n"
@@ -206,6 +220,10 @@ struct Options {
     std::string score_bytes; // --score-bytes FILE
     long score_streams = 0, score_warmup = -1; // --score-streams K (0: lstm_hip_generate's prompt bits), --score-warmup W
     long top = -1;           // --top N (-1: not given)
+    std::string embed, embed_out, pool; // --embed FILE, --embed-out OUT, --pool (empty: last)
+    long embed_delim = 10, embed_streams = 64;
+    bool embed_cell = false;
+    std::string embed_opt;   // the last option given that needs --embed
     long count = -1, streams = 1, device = 0;
     double temperature = 1.0, top_p = 1.0;
     long top_k = 0, stop_byte = -1;
@@ -240,6 +258,16 @@ Options parse(int argc, char **argv) {
         else if (a == "--score-streams") o.score_streams = parse_int(a, val(), 1, 4096);
         else if (a == "--score-warmup") o.score_warmup = parse_int(a, val(), 0, 1L << 30);
         else if (a == "--top") o.top = parse_int(a, val(), 1, 8);
+        else if (a == "--embed") o.embed = val();
+        else if (a == "--embed-out") o.embed_out = val(), o.embed_opt = a;
+        else if (a == "--embed-delim") o.embed_delim = parse_int(a, val(), 0, 255), o.embed_opt = a;
+        else if (a == "--embed-streams") o.embed_streams = parse_int(a, val(), 1, 4096), o.embed_opt = a;
+        else if (a == "--embed-cell") o.embed_cell = true, o.embed_opt = a;
+        else if (a == "--pool") {
+            o.pool = val(), o.embed_opt = a;
+            if (o.pool != "last" && o.pool != "mean" && o.pool != "max" && o.pool != "concat")
+                usage(a + " needs one of last, mean, max, concat, got '" + o.pool + "'");
+        }
         else if (a == "--count") o.count = parse_int(a, val(), 0, 1L << 30);
         else if (a == "--streams") {
             o.streams = parse_int(a, val(), 1, 4096);
@@ -327,7 +355,13 @@ Options parse(int argc, char **argv) {
         } else usage("unknown argument " + a);
     }
     if (o.load.empty()) usage("--load PREFIX is required");
-    if (o.score.empty() && o.count < 0 && o.score_bytes.empty()) usage("nothing to do: give --score, --score-bytes and/or --count");
+    if (!o.embed_opt.empty() && o.embed.empty()) usage(o.embed_opt + " needs --embed");
+    if (!o.embed.empty()) { // a mode of its own
+        if (o.count >= 0 || !o.score.empty() || !o.score_bytes.empty()) usage("--embed goes with neither --count nor --score / --score-bytes");
+        if (o.embed_out.empty()) usage("--embed needs --embed-out OUT");
+    }
+    if (o.score.empty() && o.count < 0 && o.score_bytes.empty() && o.embed.empty())
+        usage("nothing to do: give --score, --score-bytes, --embed and/or --count");
     if (o.top >= 0 && o.score_bytes.empty()) usage("--top needs --score-bytes");
     if (o.score_streams > 0 && o.score.empty()) usage("--score-streams needs --score");
     if (o.score_warmup >= 0 && o.score_streams == 0) usage("--score-warmup needs --score-streams");
@@ -473,6 +507,48 @@ int main(int argc, char **argv) {
             fputc('\n', stdout);
         }
         printf("%s: %.5f bits/char (%zu bytes)\n", o.score_bytes.c_str(), bits / (double)(constrained ? n : n - 1), n);
+    }
+
+    if (!o.embed.empty()) { // every record of the file, all in one call
+        std::vector<uint8_t> text;
+        if (!read_file(o.embed, text)) die("cannot read " + o.embed);
+        std::vector<uint64_t> off(1, 0);
+        for (size_t i = 0; i < text.size(); i++)
+            if (text[i] == (uint8_t)o.embed_delim) off.push_back(i + 1);
+        if (off.back() != text.size()) off.push_back(text.size()); // a last record may lack its delimiter
+        const size_t K = off.size() - 1;
+        if (K == 0) die(o.embed + ": no record to embed");
+        if (K > (size_t)1 << 30) die(o.embed + ": too many records");
+        const std::string pool = o.pool.empty() ? "last" : o.pool;
+        const bool concat = pool == "concat";
+        std::vector<float> block[2][3]; // [h, c][last, max, mean]: the order of concat
+        lstm_hip_embedding out{};
+        out.size = (uint32_t)sizeof(lstm_hip_embedding);
+        float **slot[2][3] = {{&out.last_h, &out.max_h, &out.mean_h}, {&out.last_c, &out.max_c, &out.mean_c}};
+        const char *const name[3] = {"last", "max", "mean"};
+        for (int x = 0; x < (o.embed_cell ? 2 : 1); x++)
+            for (int k = 0; k < 3; k++)
+                if (concat || pool == name[k]) {
+                    block[x][k].resize(K * (size_t)N);
+                    *slot[x][k] = block[x][k].data();
+                }
+        const lstm_hip_eval_opt eopt{(uint32_t)sizeof(lstm_hip_eval_opt), (int32_t)std::min<size_t>((size_t)o.embed_streams, K)};
+        CK(lstm_hip_embed_texts(h, (int32_t)K, text.data(), off.data(), nullptr, nullptr, nullptr, &eopt, nullptr, 0, &out, nullptr));
+        FILE *fp = fopen(o.embed_out.c_str(), "w");
+        if (!fp) die("cannot write " + o.embed_out);
+        for (size_t s = 0; s < K; s++) {
+            bool first = true;
+            for (int x = 0; x < 2; x++)
+                for (int k = 0; k < 3; k++)
+                    for (size_t i = 0; i < (block[x][k].empty() ? 0 : (size_t)N); i++) {
+                        fprintf(fp, first ? "%.9g" : "\t%.9g", (double)block[x][k][s * N + i]);
+                        first = false;
+                    }
+            fputc('\n', fp);
+        }
+        if (fclose(fp) != 0) die("cannot write " + o.embed_out);
+        fprintf(stderr, "lstm_generate: %zu records embedded (%s%s, %zu floats each)\n", K, pool.c_str(), o.embed_cell ? ", cell" : "",
+                (size_t)N * (concat ? 3 : 1) * (o.embed_cell ? 2 : 1));
     }
 
     if (o.count >= 0 && o.beams > 0) {

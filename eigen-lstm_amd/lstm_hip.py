@@ -76,6 +76,13 @@ class _EvalOpt(C.Structure):  # lstm_hip_eval_opt
     _fields_ = [("size", C.c_uint32), ("lanes", C.c_int32)]
 
 
+class _Embedding(C.Structure):  # lstm_hip_embedding
+    _fields_ = [("size", C.c_uint32), ("mean_h", C.POINTER(C.c_float)), ("max_h", C.POINTER(C.c_float)),
+                ("last_h", C.POINTER(C.c_float)), ("mean_c", C.POINTER(C.c_float)), ("max_c", C.POINTER(C.c_float)),
+                ("last_c", C.POINTER(C.c_float)), ("count", C.POINTER(C.c_int64)), ("bits", C.POINTER(C.c_double)),
+                ("picked_h", C.POINTER(C.c_float)), ("picked_c", C.POINTER(C.c_float))]
+
+
 class _SoftTargets(C.Structure):  # lstm_hip_soft_targets
     _fields_ = [("size", C.c_uint32), ("alpha", C.c_double), ("temperature", C.c_double), ("smoothing", C.c_double)]
 
@@ -113,6 +120,7 @@ SYMBOLS = [
     "lstm_hip_set_grad_accumulation", "lstm_hip_get_grad_accumulation", "lstm_hip_get_grad_accumulator",
     "lstm_hip_set_grad_accumulator",
     "lstm_hip_generate_processed",
+    "lstm_hip_embed_texts",
 ]
 
 
@@ -743,6 +751,57 @@ class Lstm:
         return {"bits": bits[:streams], "h": h[:streams], "c": c[:streams],
                 "surprisal": [sur[int(off[s]):int(off[s + 1])] for s in range(streams)] if surprisal else None,
                 "ms": ms.value if want_time else None}
+
+    def embed_texts(self, texts, h0=None, c0=None, skip=None, lanes=0, pool=("mean", "max", "last"), cell=False, pick=None,
+                    want_time=False):
+        """lstm_hip_embed_texts: what the model computed about `texts` (bytes or uint8 arrays, one stream each), on
+        eval_texts' engine.  Unlike eval_texts every byte is fed: position i of a text is the state after its bytes 0..i.
+        pool: which of "mean", "max", "last" to return -- mean and max over the positions skip[s] .. L - 1 (None: all), last
+        the state after the whole text; each comes back as pool + "_h" [streams, N], and with cell=True as pool + "_c" too.
+        pick: positions indexed like the concatenated texts, strictly increasing, or "all" for every position; their
+        states come back as "picked_h" (and "picked_c") [npick, N].  Also "count" int64 [streams], the pooled positions,
+        "bits" float64 [streams], eval_texts' figure, and "ms" with want_time=True."""
+        parts = _bytes_list(texts)
+        streams = len(parts)
+        data, off = _offsets(parts)
+        total = int(off[-1])
+        hh = None if h0 is None else _f32(h0).reshape(streams, self.N)
+        cc = None if c0 is None else _f32(c0).reshape(streams, self.N)
+        sk = None if skip is None else np.ascontiguousarray(skip, dtype=np.uint64).reshape(streams)
+        pool = (pool,) if isinstance(pool, str) else tuple(pool)
+        for name in pool:
+            if name not in ("mean", "max", "last"):
+                raise LstmHipError(f"embed_texts: pool {name!r} is none of mean, max, last")
+        if isinstance(pick, str):
+            if pick != "all":
+                raise LstmHipError(f"embed_texts: pick {pick!r} is neither positions nor \"all\"")
+            pick = np.arange(total, dtype=np.uint64)
+        pk = None if pick is None else np.ascontiguousarray(pick, dtype=np.uint64).reshape(-1)
+        npick = 0 if pk is None else int(pk.size)
+        res = {}
+        out = _Embedding(size=C.sizeof(_Embedding))
+        for src in ("h", "c") if cell else ("h",):
+            for name in pool:
+                res[f"{name}_{src}"] = np.empty((max(streams, 1), self.N), np.float32)
+                setattr(out, f"{name}_{src}", _ptr(res[f"{name}_{src}"]))
+            if npick:
+                res[f"picked_{src}"] = np.empty((npick, self.N), np.float32)
+                setattr(out, f"picked_{src}", _ptr(res[f"picked_{src}"]))
+        count, bits = np.zeros(max(streams, 1), np.int64), np.zeros(max(streams, 1), np.float64)
+        out.count, out.bits = _ptr(count, C.c_int64), _ptr(bits, C.c_double)
+        opt = _EvalOpt(C.sizeof(_EvalOpt), int(lanes))
+        ms = C.c_float(0)
+        _chk(self.lib.lstm_hip_embed_texts(self._h, C.c_int32(streams), _ptr(data, C.c_uint8), _ptr(off, C.c_uint64),
+                                           _ptr(hh) if hh is not None else None, _ptr(cc) if cc is not None else None,
+                                           _ptr(sk, C.c_uint64) if sk is not None else None, C.byref(opt),
+                                           _ptr(pk, C.c_uint64) if npick else None, C.c_int64(npick), C.byref(out),
+                                           C.byref(ms) if want_time else None))
+        res = {k: (v if k.startswith("picked") else v[:streams]) for k, v in res.items()}
+        if pk is not None and not npick:
+            for src in ("h", "c") if cell else ("h",):
+                res[f"picked_{src}"] = np.empty((0, self.N), np.float32)
+        res.update(count=count[:streams], bits=bits[:streams], ms=ms.value if want_time else None)
+        return res
 
     def eval_split(self, text, pieces, warm=0, lanes=0):
         """Bits per character of one text, cut into `pieces` streams that are evaluated side by side (eval_split_pieces):

@@ -842,6 +842,54 @@ int lstm_hip_eval_texts(lstm_hip_t *h, int32_t streams, const uint8_t *text, con
                         float *h_out, float *c_out,              /* N x streams, may be NULL */
                         float *elapsed_ms);                      /* may be NULL */
 
+/* ---- hidden states of many texts: pooled, last and picked positions.  lstm_hip_eval_texts' engine
+ *      -- the same cached internal handle, the same device loop without readback, the same arithmetic (the handle's forward
+ *      recurrence in fp32, from the fp32 block lstm_hip_set_inference_source names; weight drop is never applied) -- read for
+ *      what the model computed, not for what it predicted.  Stream s is text[text_off[s] .. text_off[s+1]) with L bytes;
+ *      h0 / c0 / skip / opt are lstm_hip_eval_texts'.
+ *        rule       a stream has n = L steps, NOT lstm_hip_eval_texts' L - 1: there the last byte is scored and never fed, and
+ *                   an embedding must have seen the whole text.  Step j feeds byte j; its target is byte j + 1 where
+ *                   j + 1 < L and j + 1 >= skip[s], else the step has no target.  "Position i" is the state after inputs
+ *                   0..i, indexed like text: text_off[s] + i.
+ *        last_*     position L - 1; for L = 0 the start state.  skip does not affect it.
+ *        pool       positions max(skip[s], 0) .. L - 1; count[s] is their number, max(L - skip[s], 0).
+ *        mean_*     (double) of every pooled float is added in text order into one double per element, carried across the
+ *                   stream's windows in device memory; the result is (float)(sum / (double)count).
+ *        max_*      the largest pooled value, exactly one of the floats.
+ *                   An empty pool gives mean = max = +0.0f.  With non-finite states which value comes out is unspecified;
+ *                   nothing faults.
+ *        picked_*   pick[0 .. npick) are positions, strictly increasing; column k of picked_h / picked_c (N x npick) is the
+ *                   state at position pick[k], whether or not it lies below skip.
+ *        bits       lstm_hip_eval_texts' figure for the same stream and skip within its tolerance (not bit-equal: the
+ *                   placement differs by the extra step).
+ *        plan       the schedule is lstm_hip_text_plan(128, lanes, streams, off') with off'[s] = text_off[s] + s: every stream
+ *                   counted one byte longer, which gives n = L from the planner's n = L' - 1.  Window k of a stream holds its
+ *                   positions 128k .. 128k + 127 in rows 1..128; column 0 and later windows follow lstm_hip_eval_texts; a
+ *                   stream with L = 0 gets no lane, its outputs are written before the loop (last = start state, count 0).
+ *      Every pointer of `out` may be NULL (not wanted).  All state outputs are N x streams (picked: N x npick), column s =
+ *      stream s, as h_out elsewhere.  Per window: one launch that builds the window, the forward path, one launch that folds
+ *      pools, picks, last states and bits; the two launches have no kernel statistics row.  What of the handle is touched is
+ *      lstm_hip_eval_texts' paragraph word for word: the block the inference source names is copied in at every call, nothing
+ *      else is read and nothing is written.  elapsed_ms (may be NULL): HIP-event time of the device loop.
+ *      LSTM_HIP_EINVAL (the handle stays usable, nothing is launched): everything lstm_hip_eval_texts refuses, in its words
+ *      under the name embed_texts; out NULL or of the wrong size; npick < 0; pick NULL with npick > 0; a pick >=
+ *      text_off[streams] or not above the one before it; picked_* given with npick == 0, or npick > 0 with neither given; a
+ *      picked block (internal width x npick x 4 bytes x sources) above 1 GiB. */
+typedef struct lstm_hip_embedding {   /* outputs; every pointer may be NULL */
+    uint32_t size;                    /* sizeof(lstm_hip_embedding); anything else: LSTM_HIP_EINVAL */
+    float   *mean_h, *max_h, *last_h; /* N x streams each */
+    float   *mean_c, *max_c, *last_c; /* the same of the cell state */
+    int64_t *count;                   /* [streams] pooled positions */
+    double  *bits;                    /* [streams] as lstm_hip_eval_texts' bits */
+    float   *picked_h, *picked_c;     /* N x npick */
+} lstm_hip_embedding;
+int lstm_hip_embed_texts(lstm_hip_t *h, int32_t streams, const uint8_t *text, const uint64_t *text_off,
+                         const float *h0, const float *c0,        /* N x streams, NULL = zeros */
+                         const uint64_t *skip,                    /* [streams], NULL = none */
+                         const lstm_hip_eval_opt *opt,            /* NULL: lanes = the handle's B */
+                         const uint64_t *pick, int64_t npick,     /* may be NULL / 0 */
+                         const lstm_hip_embedding *out, float *elapsed_ms);
+
 /* ---- training on separate texts, each from its zero state: the trio set_text / set_cursors /
  *      train_windows for texts.  Stream s is text[text_off[s] .. text_off[s+1]) with L bytes; a stream has
  *      n = max(L - 1, 0) steps, step j feeds byte j and has byte j + 1 as its target.
