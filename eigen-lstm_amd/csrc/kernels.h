@@ -390,18 +390,21 @@ void average(const float *p, float *a, size_t n, float w, bool copy, int cus, hi
 void weight_drop_mask(const float *src, float *dst, int Np, int Nl, uint64_t seed, uint64_t t, uint32_t thr, float scale, int cus,
                       hipStream_t st);
 
-// ---- forward-only evaluation of many texts (lstm_hip_eval_texts), around the unchanged forward
-//      path of an internal handle with S = EVAL_STEPS + 1 and B = lanes.  slot[w * lanes + l] is the stream lane l holds in
-//      window w (-1: idle); that window holds steps EVAL_STEPS * (w - first[s]) .. of stream s in rows 1 .. EVAL_STEPS.
-//      eval_window writes rows 1 .. of xi / ti (input byte j, target byte j + 1 where j + 1 >= skip[s], else -1; both -1 past
-//      the stream's end or on an idle lane) and column 0 of H / C of every busy lane: the stream's column of H0 / C0 in its
-//      first window, else column EVAL_STEPS of the same lane.  eval_fold, behind the softmax launch: one thread per lane adds
-//      (double)colloss of the lane's scored rows, in row order, into bits[s] and scatters the floats to sur (may be null) at
-//      the scored byte's place, off[s] + j + 1; the stream's last column goes to column s of Hout / Cout (may be null) in
-//      the window where it ends.  Both: one launch of at most `cus` workgroups of 256 threads striding over lanes x rows and
+// ---- many texts on the lanes of the forward path (lstm_hip_eval_texts, lstm_hip_embed_texts; DESIGN.md sections 3.17 and
+//      3.23; the kernels are text_lanes.hip), around the unchanged forward path of an internal handle with S = EVAL_STEPS + 1
+//      and B = lanes.  slot[w * lanes + l] is the stream lane l holds in window w (-1: idle); that window holds steps
+//      j0 .. j0 + EVAL_STEPS - 1 of stream s, j0 = EVAL_STEPS * (w - first[s]), in rows 1 .. EVAL_STEPS.  Stream s has
+//      L = off[s + 1] - off[s] bytes.  The rule: step j feeds byte j; it exists iff j + 1 < L + feed_last, and it has a target,
+//      byte j + 1, iff j + 1 < L && j + 1 >= skip[s].  feed_last = 0 (eval_texts): L - 1 steps, the last byte is a target
+//      only.  feed_last = 1 (embed_texts): L steps, the last byte is fed too, row r + 1 holds position j0 + r, the state
+//      after inputs 0 .. j0 + r, and the plan tables come from offsets that count every stream one byte longer; off / skip
+//      are the caller's.
+//      lane_window writes rows 1 .. of xi / ti (input byte j, target byte j + 1, each -1 where the rule gives none or on an
+//      idle lane) and column 0 of H / C of every busy lane: the stream's column of H0 / C0 in its first window, else column
+//      EVAL_STEPS of the same lane.  One launch of at most `cus` workgroups of 256 threads striding over lanes x rows and
 //      lanes x N, plain vector loads and stores only.
 constexpr int EVAL_STEPS = 128;
-struct EvalArgs {
+struct LaneArgs {
     const uint8_t *text;
     const uint64_t *off;    // [streams + 1]
     const uint64_t *skip;   // [streams]
@@ -412,46 +415,38 @@ struct EvalArgs {
     float *H, *C;           // [EVAL_STEPS + 1][lanes][N]
     const float *colloss;   // [EVAL_STEPS][lanes]
     double *bits;           // [streams]
+    int lanes, N;
+    int feed_last;          // 0: a stream of L bytes has L - 1 steps; 1: L steps
+};
+void lane_window(const LaneArgs &a, int64_t w, int cus, hipStream_t st);
+
+// ---- the folds, behind the softmax launch.  Both: one thread per lane adds (double)colloss of the lane's rows that have a
+//      target, in row order, into bits[s].
+//      eval_fold also scatters those floats to sur (may be null) at the scored byte's place, off[s] + j + 1; the stream's last
+//      column goes to column s of Hout / Cout (may be null) in the window where it ends.  One launch of at most `cus`
+//      workgroups of 256 threads, plain vector loads and stores only.
+struct EvalArgs : LaneArgs {
     float *sur;             // [off[streams]] or null
     float *Hout, *Cout;     // [streams][N] or null
-    int lanes, N;
 };
-void eval_window(const EvalArgs &a, int64_t w, int cus, hipStream_t st);
 void eval_fold(const EvalArgs &a, int64_t w, int cus, hipStream_t st);
 
-// ---- hidden states of many texts (lstm_hip_embed_texts; the kernels are embed.hip), around the same
-//      unchanged forward path and on the same plan tables as above, made from offsets that count every stream one byte
-//      longer: a stream of L bytes has L steps, step j feeds byte j, and row r + 1 of a window with j0 = EVAL_STEPS *
-//      (w - first[s]) holds position j0 + r, the state after inputs 0 .. j0 + r.  off / skip are the caller's.
-//      embed_window is eval_window under that rule: xi = byte j for j < L; ti = byte j + 1 where j + 1 < L and
-//      j + 1 >= skip[s], else -1; column 0 as there.
-//      embed_fold, behind the softmax launch.  bits: as eval_fold, over the rows that have a target.  Per wanted source x
-//      (0: H, 1: C; a source is wanted when last[x] is not null, and then sum, mean, maxv and last of it are all there): a
+//      embed_fold also pools and picks.  Per wanted source x (0: H, 1: C; a source is wanted when last[x] is not null, and
+//      then sum, mean, maxv and last of it are all there): a
 //      workgroup per (lane, 32 float4s of N) loads the lane's live rows at or above skip[s] at once, as 8 chunks of 16 rows,
 //      and adds (double)v into four doubles per float4 chunk after chunk, in row order, keeping four float maxima; both are
-//      carried in sum[x] / maxv[x] [streams][N] from the stream's window before (fresh in its first); in the window where the stream ends it writes last[x] = the row of position L - 1,
+//      carried in sum[x] / maxv[x] [streams][N] from the stream's window before (fresh in its first); in the window where the
+//      stream ends it writes last[x] = the row of position L - 1,
 //      mean[x] = (float)(sum / (double)count) and, for an empty pool, mean[x] = maxv[x] = +0.0f.  Rows past the stream's end are
 //      never read.  picks [pick_lo, pick_hi) of the table (lane, row, k) are the window's: row `row` of lane `lane` goes to
 //      column k of picked[x] ([npick][N], null: not wanted).  One launch of at most 8 * cus workgroups of 256 threads, plain
 //      vector loads and stores only.
-struct EmbedArgs {
-    const uint8_t *text;
-    const uint64_t *off;    // [streams + 1]
-    const uint64_t *skip;   // [streams]
-    const int32_t *slot;    // [windows][lanes]
-    const int64_t *first;   // [streams]
-    const float *H0, *C0;   // [streams][N]
-    int32_t *xi, *ti;       // [EVAL_STEPS + 1][lanes]
-    float *H, *C;           // [EVAL_STEPS + 1][lanes][N]
-    const float *colloss;   // [EVAL_STEPS][lanes]
-    double *bits;           // [streams]
+struct EmbedArgs : LaneArgs {
     double *sum[2];         // [streams][N] each
     float *mean[2], *maxv[2], *last[2];
     const int32_t *picks;   // [npick][3], sorted by window
     float *picked[2];       // [npick][N]
-    int lanes, N;
 };
-void embed_window(const EmbedArgs &a, int64_t w, int cus, hipStream_t st);
 void embed_fold(const EmbedArgs &a, int64_t w, int64_t pick_lo, int64_t pick_hi, int cus, hipStream_t st);
 
 // ---- B = 1 recurrence for the evaluator / sampler (OV/lstm_eigen_class_CUDA/lstm.cc:578-720)

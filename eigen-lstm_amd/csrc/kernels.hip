@@ -2433,101 +2433,10 @@ void weight_drop_mask(const float *src, float *dst, int Np, int Nl, uint64_t see
 }
 
 // ------------------------------------------------------------------------------------------------
-// eval_window / eval_fold: the two launches lstm_hip_eval_texts puts around the forward path (kernels.h; DESIGN.md section
-// 3.17).  Every element is independent (a stream sits on one lane, a lane holds one stream per window), so both are
-// grid-stride loops: over lanes x rows for the indices, over lanes x N / 4 for the state columns in float4 (N % 16 == 0 and
-// every column starts on a 16-byte boundary), and over the lanes for the fold, whose additions per stream are sequential in
-// text order: one thread, one window after the other on the stream.
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_eval_window(EvalArgs a, long long w) {
-    const long long tid = (long long)blockIdx.x * 256 + threadIdx.x, nth = (long long)gridDim.x * 256;
-    const int32_t *slot = a.slot + w * a.lanes;
-    for (long long i = tid; i < (long long)EVAL_STEPS * a.lanes; i += nth) {
-        const int r = (int)(i / a.lanes), l = (int)(i - (long long)r * a.lanes); // row r + 1 of the window
-        const int s = slot[l];
-        int xv = -1, tv = -1;
-        if (s >= 0) {
-            const uint64_t o = a.off[s], len = a.off[s + 1] - o;
-            const uint64_t j = (uint64_t)(w - a.first[s]) * EVAL_STEPS + r; // the step: feeds byte j, scores byte j + 1
-            if (j + 1 < len) {
-                xv = (int)a.text[o + j];
-                if (j + 1 >= a.skip[s]) tv = (int)a.text[o + j + 1];
-            }
-        }
-        a.xi[(size_t)(r + 1) * a.lanes + l] = xv;
-        a.ti[(size_t)(r + 1) * a.lanes + l] = tv;
-    }
-    const int N4 = a.N / 4;
-    float4 *H4 = reinterpret_cast<float4 *>(a.H), *C4 = reinterpret_cast<float4 *>(a.C);
-    for (long long i = tid; i < (long long)a.lanes * N4; i += nth) {
-        const int l = (int)(i / N4), q = (int)(i - (long long)l * N4);
-        const int s = slot[l];
-        if (s < 0) continue;
-        if (w == a.first[s]) { // the stream's start state
-            H4[i] = reinterpret_cast<const float4 *>(a.H0)[(size_t)s * N4 + q];
-            C4[i] = reinterpret_cast<const float4 *>(a.C0)[(size_t)s * N4 + q];
-        } else { // the lane's last column of the window before (S >= 2: another column)
-            H4[i] = H4[(size_t)EVAL_STEPS * a.lanes * N4 + i];
-            C4[i] = C4[(size_t)EVAL_STEPS * a.lanes * N4 + i];
-        }
-    }
-}
-__global__ __launch_bounds__(256) void k_eval_fold(EvalArgs a, long long w) {
-    const long long tid = (long long)blockIdx.x * 256 + threadIdx.x, nth = (long long)gridDim.x * 256;
-    const int32_t *slot = a.slot + w * a.lanes;
-    for (long long l = tid; l < a.lanes; l += nth) {
-        const int s = slot[l];
-        if (s < 0) continue;
-        const uint64_t o = a.off[s], n = a.off[s + 1] - o - 1, j0 = (uint64_t)(w - a.first[s]) * EVAL_STEPS, skip = a.skip[s];
-        const int rows = n - j0 < (uint64_t)EVAL_STEPS ? (int)(n - j0) : EVAL_STEPS;
-        const float *__restrict__ col = a.colloss + l;
-        double sum = a.bits[s];
-        for (int r0 = 0; r0 < rows; r0 += 16) { // sixteen independent loads in flight, then their additions in row order
-            float v[16];
-#pragma unroll
-            for (int u = 0; u < 16; u++) v[u] = r0 + u < rows ? col[(size_t)(r0 + u) * a.lanes] : 0.0f;
-#pragma unroll
-            for (int u = 0; u < 16; u++) {
-                if (r0 + u >= rows || j0 + r0 + u + 1 < skip) continue; // past the end / fed, not scored
-                sum += (double)v[u];
-                if (a.sur) a.sur[o + j0 + r0 + u + 1] = v[u];
-            }
-        }
-        a.bits[s] = sum;
-    }
-    if (a.Hout == nullptr && a.Cout == nullptr) return;
-    const int N4 = a.N / 4;
-    for (long long i = tid; i < (long long)a.lanes * N4; i += nth) {
-        const int l = (int)(i / N4), q = (int)(i - (long long)l * N4);
-        const int s = slot[l];
-        if (s < 0) continue;
-        const uint64_t n = a.off[s + 1] - a.off[s] - 1, j0 = (uint64_t)(w - a.first[s]) * EVAL_STEPS;
-        if (n - j0 > (uint64_t)EVAL_STEPS) continue; // the stream goes on in the next window
-        const size_t src = (size_t)(n - j0) * a.lanes * N4 + i; // the column of its last step
-        if (a.Hout) reinterpret_cast<float4 *>(a.Hout)[(size_t)s * N4 + q] = reinterpret_cast<const float4 *>(a.H)[src];
-        if (a.Cout) reinterpret_cast<float4 *>(a.Cout)[(size_t)s * N4 + q] = reinterpret_cast<const float4 *>(a.C)[src];
-    }
-}
-static int eval_blocks(long long work, int cus) {
-    long long blocks = (work + 255) / 256; // one element per thread while the grid stays within the CUs: every element is a
-                                           // chain of dependent loads (slot, offsets, byte), so more threads, not longer loops
-    if (blocks > cus) blocks = cus;
-    return blocks < 1 ? 1 : (int)blocks;
-}
-void eval_window(const EvalArgs &a, int64_t w, int cus, hipStream_t st) {
-    const long long work = (long long)a.lanes * (EVAL_STEPS > a.N / 4 ? EVAL_STEPS : a.N / 4);
-    hipLaunchKernelGGL(k_eval_window, dim3(eval_blocks(work, cus)), dim3(256), 0, st, a, (long long)w);
-}
-void eval_fold(const EvalArgs &a, int64_t w, int cus, hipStream_t st) {
-    const long long work = a.Hout || a.Cout ? (long long)a.lanes * (a.N / 4) : a.lanes;
-    hipLaunchKernelGGL(k_eval_fold, dim3(eval_blocks(work, cus)), dim3(256), 0, st, a, (long long)w);
-}
-
-// ------------------------------------------------------------------------------------------------
 // text_window / text_fold: the two launches lstm_hip_train_text_windows puts around a training window (kernels.h; DESIGN.md
-// section 3.18).  As in eval_window every element is independent: a stream sits on one lane, a lane holds one stream per
-// window.  The carry reads column S - 1 and writes column 0 of the same lane, and S >= 2, so no thread reads what another
-// writes in this launch.
+// section 3.18).  As in lane_window (text_lanes.hip) every element is independent: a stream sits on one lane, a lane holds
+// one stream per window.  The carry reads column S - 1 and writes column 0 of the same lane, and S >= 2, so no thread reads
+// what another writes in this launch.
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_text_window(TextWindowArgs a, long long w) {
     const long long tid = (long long)blockIdx.x * 256 + threadIdx.x, nth = (long long)gridDim.x * 256;
@@ -2590,6 +2499,12 @@ __global__ __launch_bounds__(256) void k_text_fold(TextWindowArgs a, long long w
         }
         a.bits[s] = sum;
     }
+}
+static int eval_blocks(long long work, int cus) {
+    long long blocks = (work + 255) / 256; // one element per thread while the grid stays within the CUs: every element is a
+                                           // chain of dependent loads (slot, offsets, byte), so more threads, not longer loops
+    if (blocks > cus) blocks = cus;
+    return blocks < 1 ? 1 : (int)blocks;
 }
 void text_window(const TextWindowArgs &a, int64_t w, int cus, hipStream_t st) {
     const long long work = (long long)a.B * (a.S > a.N / 4 ? a.S : a.N / 4);

@@ -22,6 +22,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <tuple>
@@ -2897,136 +2898,172 @@ int64_t lstm_hip_eval_plan(int32_t lanes, int32_t streams, const uint64_t *text_
     return checked_plan("eval_plan", LSTM_HIP_EVAL_STEPS, lanes, streams, text_off, lane_of, first_window, nullptr);
 }
 
-// The device loop: per window k_eval_window, the internal handle's unchanged do_forward, k_eval_fold, all on the internal
-// handle's stream; the uploads and the state copies at either end run on the parent's, as every inference call's do, with the
-// parent's generator scratch as working memory.  The internal handle runs in the window loop's mode that skips the
-// probability store (nothing reads them); its profiling is off, so the parent's kernel statistics do not move.
+// What lstm_hip_eval_texts and lstm_hip_embed_texts share: the checks, the plan, the internal handle, the pieces of the call's
+// scratch that every lane launch reads, their uploads, and the device loop.  Per window: lane_window, the internal handle's
+// unchanged do_forward, the caller's fold, all on the internal handle's stream; the uploads and the state copies at either
+// end run on the parent's, as every inference call's do, with the parent's generator scratch as working memory.  The internal
+// handle runs in the window loop's mode that skips the probability store (nothing reads them); its profiling is off, so the
+// parent's kernel statistics do not move.  A call goes checks, (its own checks), plan, (its own pieces), upload, (its own
+// fills on h->st), loop, (its downloads).
+struct TextsRun {
+    lstm_hip_t *h = nullptr;
+    lstm_hip_ctx *e = nullptr; // the internal handle
+    int32_t streams = 0;
+    int lanes = 0, feed_last = 0;
+    const uint8_t *text = nullptr;
+    const uint64_t *text_off = nullptr;
+    uint64_t total = 0;
+    int64_t windows = 0;
+    std::vector<int32_t> slot, lane_of; // [windows][lanes]; [streams]
+    std::vector<int64_t> first;         // [streams]
+    float *H0 = nullptr, *C0 = nullptr, *stage = nullptr;
+    uint64_t *d_off = nullptr, *d_skip = nullptr;
+    int64_t *d_first = nullptr;
+    int32_t *d_slot = nullptr;
+    uint8_t *d_text = nullptr;
+    double *d_bits = nullptr;
+    Scratch mem; // the call's pieces: the shared ones from plan(), the caller's own between plan() and upload()
+
+    // the refusals both calls have, under the caller's name; chooses `lanes`
+    int checks(lstm_hip_t *handle, const char *what, int32_t n_streams, const uint8_t *bytes, const uint64_t *off,
+              const lstm_hip_eval_opt *opt) {
+        CHECK(handle);
+        if (opt && opt->size != sizeof(lstm_hip_eval_opt))
+            return fail(LSTM_HIP_EINVAL, "%s: options of %u bytes, expected %zu", what, opt->size, sizeof(lstm_hip_eval_opt));
+        if (opt && (opt->lanes < 0 || opt->lanes > 4096))
+            return fail(LSTM_HIP_EINVAL, "%s: lanes must be in [0, 4096] (got %d)", what, opt->lanes);
+        if (n_streams < 1) return fail(LSTM_HIP_EINVAL, "%s: streams must be >= 1 (got %d)", what, n_streams);
+        if (int rc = check_offsets(what, "text_off", off, n_streams)) return rc;
+        if (off[n_streams] > 0 && !bytes)
+            return fail(LSTM_HIP_EINVAL, "%s: null text with %llu bytes to read", what, (unsigned long long)off[n_streams]);
+        h = handle, streams = n_streams, text = bytes, text_off = off, total = off[n_streams];
+        lanes = opt && opt->lanes > 0 ? opt->lanes : h->cfg.B;
+        return 0;
+    }
+    // The plan (host only) -- with feed_last that of streams one byte longer: a stream of L bytes gets ceil(L / 128) windows,
+    // an empty one no lane -- then the internal handle and the shared pieces.  `stage_cols`: the widest download of the call.
+    int plan(int feed, size_t stage_cols) {
+        feed_last = feed;
+        std::vector<uint64_t> longer;
+        for (int32_t s = 0; feed_last && s <= streams; s++) longer.push_back(text_off[s] + (uint64_t)s);
+        lane_of.resize(streams), first.resize(streams);
+        windows = text_plan(LSTM_HIP_EVAL_STEPS, lanes, streams, feed_last ? longer.data() : text_off, lane_of.data(), first.data(), &slot);
+        if (int rc = texts_handle(h, lanes)) return rc;
+        e = h->texts_h;
+        const size_t n = (size_t)h->cfg.N * streams;
+        mem.piece(H0, n).piece(C0, n).piece(stage, 2 * (size_t)h->N_log * stage_cols, h->padded());
+        mem.piece(d_off, streams + 1).piece(d_skip, streams).piece(d_first, streams).piece(d_slot, slot.size());
+        mem.piece(d_text, (size_t)total).piece(d_bits, streams);
+        return 0;
+    }
+    // commits the scratch, brings the parameters, the start states and the tables to the device (on h->st) and fills `a`
+    int upload(const float *h0, const float *c0, const uint64_t *skip, LaneArgs &a) {
+        if (int rc = mem.commit(h)) return rc;
+        HIP_TRY(hipMemcpyAsync(e->P, infer_block(h), sizeof(float) * h->pl.total, hipMemcpyDeviceToDevice, h->st));
+        e->packed = false;
+        if (int rc = upload_states(h, h0, c0, H0, C0, stage, streams)) return rc;
+        HIP_TRY(hipMemcpyAsync(d_off, text_off, sizeof(uint64_t) * (streams + 1), hipMemcpyHostToDevice, h->st));
+        if (skip) HIP_TRY(hipMemcpyAsync(d_skip, skip, sizeof(uint64_t) * streams, hipMemcpyHostToDevice, h->st));
+        else HIP_TRY(hipMemsetAsync(d_skip, 0, sizeof(uint64_t) * streams, h->st));
+        HIP_TRY(hipMemcpyAsync(d_first, first.data(), sizeof(int64_t) * streams, hipMemcpyHostToDevice, h->st));
+        if (!slot.empty()) HIP_TRY(hipMemcpyAsync(d_slot, slot.data(), sizeof(int32_t) * slot.size(), hipMemcpyHostToDevice, h->st));
+        if (total) HIP_TRY(hipMemcpyAsync(d_text, text, (size_t)total, hipMemcpyHostToDevice, h->st));
+        HIP_TRY(hipMemsetAsync(d_bits, 0, sizeof(double) * streams, h->st));
+        a.text = d_text;
+        a.off = d_off;
+        a.skip = d_skip;
+        a.slot = d_slot;
+        a.first = d_first;
+        a.H0 = H0;
+        a.C0 = C0;
+        a.xi = e->xi;
+        a.ti = e->ti;
+        a.H = e->H;
+        a.C = e->C;
+        a.colloss = e->colloss;
+        a.bits = d_bits;
+        a.lanes = lanes;
+        a.N = h->cfg.N;
+        a.feed_last = feed_last;
+        return 0;
+    }
+    // the device loop; `fold` launches window w's fold on e->st and returns its status.  elapsed_ms (may be null): the loop's
+    // HIP-event time
+    int loop(const LaneArgs &a, const std::function<int(int64_t)> &fold, float *elapsed_ms) {
+        HIP_TRY(hipStreamSynchronize(h->st)); // (the host vectors are pageable: their copies are done; the loop is on e's stream)
+        struct LoopMode { // the internal handle is back in its standalone mode on every return path
+            lstm_hip_ctx *e;
+            ~LoopMode() { e->in_loop = false, e->keep_outputs = true; }
+        } loop_mode{e};
+        e->in_loop = true;
+        e->keep_outputs = false;
+        if (elapsed_ms) HIP_TRY(hipEventRecord(e->evt0, e->st));
+        for (int64_t w = 0; w < windows; w++) {
+            lane_window(a, w, e->plan.n_cus, e->st);
+            if (int rc = eval_status("lane_window")) return rc;
+            if (int rc = do_forward(e)) return rc;
+            if (int rc = fold(w)) return rc;
+        }
+        if (elapsed_ms) {
+            HIP_TRY(hipEventRecord(e->evt1, e->st));
+            HIP_TRY(hipEventSynchronize(e->evt1));
+            HIP_TRY(hipEventElapsedTime(elapsed_ms, e->evt0, e->evt1));
+        }
+        HIP_TRY(hipStreamSynchronize(e->st));
+        return check_abort(e);
+    }
+};
+
+// Held-out bits: the run with feed_last = 0 and eval_fold.
 int lstm_hip_eval_texts(lstm_hip_t *h, int32_t streams, const uint8_t *text, const uint64_t *text_off, const float *h0, const float *c0,
                         const uint64_t *skip, const lstm_hip_eval_opt *opt, double *bits, float *surprisal, float *h_out,
                         float *c_out, float *elapsed_ms) {
-    CHECK(h);
-    if (opt && opt->size != sizeof(lstm_hip_eval_opt))
-        return fail(LSTM_HIP_EINVAL, "eval_texts: options of %u bytes, expected %zu", opt->size, sizeof(lstm_hip_eval_opt));
-    if (opt && (opt->lanes < 0 || opt->lanes > 4096))
-        return fail(LSTM_HIP_EINVAL, "eval_texts: lanes must be in [0, 4096] (got %d)", opt->lanes);
-    if (streams < 1) return fail(LSTM_HIP_EINVAL, "eval_texts: streams must be >= 1 (got %d)", streams);
-    if (int rc = check_offsets("eval_texts", "text_off", text_off, streams)) return rc;
-    const uint64_t total = text_off[streams];
-    if (total > 0 && !text) return fail(LSTM_HIP_EINVAL, "eval_texts: null text with %llu bytes to read", (unsigned long long)total);
-    const int lanes = opt && opt->lanes > 0 ? opt->lanes : h->cfg.B;
-    const int N = h->cfg.N;
-
-    std::vector<int32_t> slot;
-    std::vector<int64_t> first(streams);
-    const int64_t windows = text_plan(LSTM_HIP_EVAL_STEPS, lanes, streams, text_off, nullptr, first.data(), &slot);
-
-    if (int rc = texts_handle(h, lanes)) return rc;
-    lstm_hip_ctx *e = h->texts_h;
-
-    const size_t n = (size_t)N * streams, nl = (size_t)h->N_log * streams, tot = (size_t)total;
-    const bool keep = h_out || c_out;
-    float *H0, *C0, *ho, *stage, *d_sur;
-    uint64_t *d_off, *d_skip;
-    int64_t *d_first;
-    int32_t *d_slot;
-    uint8_t *d_text;
-    double *d_bits;
-    Scratch mem;
-    mem.piece(H0, n).piece(C0, n).piece(ho, 2 * n, keep).piece(stage, 2 * nl, h->padded());
-    mem.piece(d_off, streams + 1).piece(d_skip, streams).piece(d_first, streams).piece(d_slot, slot.size());
-    mem.piece(d_text, tot).piece(d_bits, streams).piece(d_sur, tot, surprisal && tot);
-    if (int rc = mem.commit(h)) return rc;
-
-    HIP_TRY(hipMemcpyAsync(e->P, infer_block(h), sizeof(float) * h->pl.total, hipMemcpyDeviceToDevice, h->st));
-    e->packed = false;
-    if (int rc = upload_states(h, h0, c0, H0, C0, stage, streams)) return rc;
-    if (keep) { // a stream without a step never reaches the fold: its final state is its start state
-        HIP_TRY(hipMemcpyAsync(ho, H0, sizeof(float) * n, hipMemcpyDeviceToDevice, h->st));
-        HIP_TRY(hipMemcpyAsync(ho + n, C0, sizeof(float) * n, hipMemcpyDeviceToDevice, h->st));
-    }
-    HIP_TRY(hipMemcpyAsync(d_off, text_off, sizeof(uint64_t) * (streams + 1), hipMemcpyHostToDevice, h->st));
-    if (skip) HIP_TRY(hipMemcpyAsync(d_skip, skip, sizeof(uint64_t) * streams, hipMemcpyHostToDevice, h->st));
-    else HIP_TRY(hipMemsetAsync(d_skip, 0, sizeof(uint64_t) * streams, h->st));
-    HIP_TRY(hipMemcpyAsync(d_first, first.data(), sizeof(int64_t) * streams, hipMemcpyHostToDevice, h->st));
-    if (!slot.empty()) HIP_TRY(hipMemcpyAsync(d_slot, slot.data(), sizeof(int32_t) * slot.size(), hipMemcpyHostToDevice, h->st));
-    if (tot) HIP_TRY(hipMemcpyAsync(d_text, text, tot, hipMemcpyHostToDevice, h->st));
-    HIP_TRY(hipMemsetAsync(d_bits, 0, sizeof(double) * streams, h->st));
-    if (d_sur) HIP_TRY(hipMemsetAsync(d_sur, 0, sizeof(float) * tot, h->st));
-    HIP_TRY(hipStreamSynchronize(h->st)); // (the host vectors are pageable: their copies are done; the loop is on e's stream)
-
+    TextsRun r;
+    if (int rc = r.checks(h, "eval_texts", streams, text, text_off, opt)) return rc;
+    const size_t n = (size_t)h->cfg.N * streams, tot = (size_t)r.total;
+    float *ho, *d_sur;
+    if (int rc = r.plan(0, streams)) return rc;
+    r.mem.piece(ho, 2 * n, h_out || c_out).piece(d_sur, tot, surprisal && tot);
     EvalArgs a{};
-    a.text = d_text;
-    a.off = d_off;
-    a.skip = d_skip;
-    a.slot = d_slot;
-    a.first = d_first;
-    a.H0 = H0;
-    a.C0 = C0;
-    a.xi = e->xi;
-    a.ti = e->ti;
-    a.H = e->H;
-    a.C = e->C;
-    a.colloss = e->colloss;
-    a.bits = d_bits;
+    if (int rc = r.upload(h0, c0, skip, a)) return rc;
+    if (ho) { // a stream without a step never reaches the fold: its final state is its start state
+        HIP_TRY(hipMemcpyAsync(ho, r.H0, sizeof(float) * n, hipMemcpyDeviceToDevice, h->st));
+        HIP_TRY(hipMemcpyAsync(ho + n, r.C0, sizeof(float) * n, hipMemcpyDeviceToDevice, h->st));
+    }
+    if (d_sur) HIP_TRY(hipMemsetAsync(d_sur, 0, sizeof(float) * tot, h->st));
     a.sur = d_sur;
     a.Hout = h_out ? ho : nullptr;
     a.Cout = c_out ? ho + n : nullptr;
-    a.lanes = lanes;
-    a.N = N;
-    struct LoopMode { // the internal handle is back in its standalone mode on every return path
-        lstm_hip_ctx *e;
-        ~LoopMode() { e->in_loop = false, e->keep_outputs = true; }
-    } loop_mode{e};
-    e->in_loop = true;
-    e->keep_outputs = false;
-    if (elapsed_ms) HIP_TRY(hipEventRecord(e->evt0, e->st));
-    for (int64_t w = 0; w < windows; w++) {
-        eval_window(a, w, e->plan.n_cus, e->st);
-        if (int rc = eval_status("eval_window")) return rc;
-        if (int rc = do_forward(e)) return rc;
-        eval_fold(a, w, e->plan.n_cus, e->st);
-        if (int rc = eval_status("eval_fold")) return rc;
-    }
-    if (elapsed_ms) {
-        HIP_TRY(hipEventRecord(e->evt1, e->st));
-        HIP_TRY(hipEventSynchronize(e->evt1));
-        HIP_TRY(hipEventElapsedTime(elapsed_ms, e->evt0, e->evt1));
-    }
-    HIP_TRY(hipStreamSynchronize(e->st));
-    if (int rc = check_abort(e)) return rc;
+    const auto fold = [&](int64_t w) {
+        eval_fold(a, w, r.e->plan.n_cus, r.e->st);
+        return eval_status("eval_fold");
+    };
+    if (int rc = r.loop(a, fold, elapsed_ms)) return rc;
 
-    if (bits) HIP_TRY(hipMemcpyAsync(bits, d_bits, sizeof(double) * streams, hipMemcpyDeviceToHost, h->st));
+    if (bits) HIP_TRY(hipMemcpyAsync(bits, r.d_bits, sizeof(double) * streams, hipMemcpyDeviceToHost, h->st));
     if (d_sur) HIP_TRY(hipMemcpyAsync(surprisal, d_sur, sizeof(float) * tot, hipMemcpyDeviceToHost, h->st));
-    if (int rc = download_states(h, h_out, c_out, ho, ho ? ho + n : nullptr, stage, streams)) return rc;
+    if (int rc = download_states(h, h_out, c_out, ho, ho ? ho + n : nullptr, r.stage, streams)) return rc;
     HIP_TRY(hipStreamSynchronize(h->st));
     return 0;
 }
 
-// Hidden states of many texts (include/lstm_hip.h): lstm_hip_eval_texts' device loop with
-// embed_window / embed_fold around the same do_forward, on the plan of offsets that count every stream one byte longer
-// (n = L steps: the last byte is fed).  The outputs are blocks of internal-width columns in the call's scratch, [streams][N]
-// per pool and source and [npick][N] per picked source, brought home through download_states like any state.
+// Hidden states of many texts (include/lstm_hip.h): the run with feed_last = 1 (n = L steps: the last
+// byte is fed) and embed_fold.  The outputs are blocks of internal-width columns in the call's scratch, [streams][N] per pool
+// and source and [npick][N] per picked source, brought home through download_states like any state.
 int lstm_hip_embed_texts(lstm_hip_t *h, int32_t streams, const uint8_t *text, const uint64_t *text_off, const float *h0, const float *c0,
                          const uint64_t *skip, const lstm_hip_eval_opt *opt, const uint64_t *pick, int64_t npick,
                          const lstm_hip_embedding *out, float *elapsed_ms) {
-    CHECK(h);
-    if (opt && opt->size != sizeof(lstm_hip_eval_opt))
-        return fail(LSTM_HIP_EINVAL, "embed_texts: options of %u bytes, expected %zu", opt->size, sizeof(lstm_hip_eval_opt));
-    if (opt && (opt->lanes < 0 || opt->lanes > 4096))
-        return fail(LSTM_HIP_EINVAL, "embed_texts: lanes must be in [0, 4096] (got %d)", opt->lanes);
-    if (streams < 1) return fail(LSTM_HIP_EINVAL, "embed_texts: streams must be >= 1 (got %d)", streams);
-    if (int rc = check_offsets("embed_texts", "text_off", text_off, streams)) return rc;
-    const uint64_t total = text_off[streams];
-    if (total > 0 && !text) return fail(LSTM_HIP_EINVAL, "embed_texts: null text with %llu bytes to read", (unsigned long long)total);
+    TextsRun r;
+    if (int rc = r.checks(h, "embed_texts", streams, text, text_off, opt)) return rc;
     if (!out) return fail(LSTM_HIP_EINVAL, "embed_texts: null out");
     if (out->size != sizeof(lstm_hip_embedding))
         return fail(LSTM_HIP_EINVAL, "embed_texts: outputs of %u bytes, expected %zu", out->size, sizeof(lstm_hip_embedding));
     if (npick < 0) return fail(LSTM_HIP_EINVAL, "embed_texts: npick must be >= 0 (got %lld)", (long long)npick);
     if (npick > 0 && !pick) return fail(LSTM_HIP_EINVAL, "embed_texts: null pick with npick = %lld", (long long)npick);
     for (int64_t k = 0; k < npick; k++) {
-        if (pick[k] >= total)
+        if (pick[k] >= r.total)
             return fail(LSTM_HIP_EINVAL, "embed_texts: pick[%lld] = %llu is not below text_off[streams] = %llu", (long long)k,
-                        (unsigned long long)pick[k], (unsigned long long)total);
+                        (unsigned long long)pick[k], (unsigned long long)r.total);
         if (k > 0 && pick[k] <= pick[k - 1])
             return fail(LSTM_HIP_EINVAL, "embed_texts: pick must be strictly increasing (pick[%lld] = %llu after %llu)", (long long)k,
                         (unsigned long long)pick[k], (unsigned long long)pick[k - 1]);
@@ -3039,91 +3076,48 @@ int lstm_hip_embed_texts(lstm_hip_t *h, int32_t streams, const uint8_t *text, co
     if ((uint64_t)npick > pick_limit / ((uint64_t)N * sizeof(float) * (pick_sources ? pick_sources : 1)))
         return fail(LSTM_HIP_EINVAL, "embed_texts: %lld picked positions of width %d from %d source(s) need more than %llu bytes",
                     (long long)npick, N, pick_sources, (unsigned long long)pick_limit);
-    const int lanes = opt && opt->lanes > 0 ? opt->lanes : h->cfg.B;
 
-    // the plan of streams one byte longer: a stream of L bytes gets ceil(L / 128) windows, an empty one no lane
-    std::vector<uint64_t> off1(streams + 1);
-    for (int32_t s = 0; s <= streams; s++) off1[s] = text_off[s] + (uint64_t)s;
-    std::vector<int32_t> slot, lane_of(streams);
-    std::vector<int64_t> first(streams);
-    const int64_t windows = text_plan(LSTM_HIP_EVAL_STEPS, lanes, streams, off1.data(), lane_of.data(), first.data(), &slot);
+    if (int rc = r.plan(1, std::max((size_t)streams, (size_t)npick))) return rc;
 
     // every pick as (lane, row, k), sorted by window; pick_at[w] .. pick_at[w + 1] are window w's
-    std::vector<int64_t> pick_at(windows + 1, 0);
+    std::vector<int64_t> pick_at(r.windows + 1, 0);
     std::vector<int32_t> table((size_t)npick * 3);
     {
         std::vector<int64_t> win(npick);
         int32_t s = 0;
         for (int64_t k = 0; k < npick; k++) { // (increasing picks: the stream index only moves forward)
             while (pick[k] >= text_off[s + 1]) s++;
-            win[k] = first[s] + (int64_t)((pick[k] - text_off[s]) / LSTM_HIP_EVAL_STEPS);
+            win[k] = r.first[s] + (int64_t)((pick[k] - text_off[s]) / LSTM_HIP_EVAL_STEPS);
             pick_at[win[k] + 1]++;
         }
-        for (int64_t w = 0; w < windows; w++) pick_at[w + 1] += pick_at[w];
+        for (int64_t w = 0; w < r.windows; w++) pick_at[w + 1] += pick_at[w];
         std::vector<int64_t> next(pick_at.begin(), pick_at.end() - 1);
         s = 0;
         for (int64_t k = 0; k < npick; k++) {
             while (pick[k] >= text_off[s + 1]) s++;
             int32_t *t = &table[(size_t)next[win[k]]++ * 3];
-            t[0] = lane_of[s];
+            t[0] = r.lane_of[s];
             t[1] = (int32_t)((pick[k] - text_off[s]) % LSTM_HIP_EVAL_STEPS) + 1;
             t[2] = (int32_t)k;
         }
     }
 
-    if (int rc = texts_handle(h, lanes)) return rc;
-    lstm_hip_ctx *e = h->texts_h;
-
-    const size_t n = (size_t)N * streams, tot = (size_t)total, np = (size_t)N * npick;
+    const size_t n = (size_t)N * streams, np = (size_t)N * npick;
     const bool want[2] = {out->mean_h || out->max_h || out->last_h, out->mean_c || out->max_c || out->last_c};
-    const size_t stage_cols = std::max((size_t)streams, (size_t)npick);
-    float *H0, *C0, *stage, *pool[2], *picked[2];
-    double *d_sum[2], *d_bits;
-    uint64_t *d_off, *d_skip;
-    int64_t *d_first;
-    int32_t *d_slot, *d_picks;
-    uint8_t *d_text;
-    Scratch mem;
-    mem.piece(H0, n).piece(C0, n).piece(stage, 2 * (size_t)h->N_log * stage_cols, h->padded());
-    for (int x = 0; x < 2; x++) mem.piece(d_sum[x], n, want[x]).piece(pool[x], 3 * n, want[x]); // mean | max | last
-    mem.piece(picked[0], np, out->picked_h != nullptr).piece(picked[1], np, out->picked_c != nullptr);
-    mem.piece(d_picks, table.size(), npick > 0);
-    mem.piece(d_off, streams + 1).piece(d_skip, streams).piece(d_first, streams).piece(d_slot, slot.size());
-    mem.piece(d_text, tot).piece(d_bits, streams);
-    if (int rc = mem.commit(h)) return rc;
-
-    HIP_TRY(hipMemcpyAsync(e->P, infer_block(h), sizeof(float) * h->pl.total, hipMemcpyDeviceToDevice, h->st));
-    e->packed = false;
-    if (int rc = upload_states(h, h0, c0, H0, C0, stage, streams)) return rc;
+    float *pool[2], *picked[2];
+    double *d_sum[2];
+    int32_t *d_picks;
+    for (int x = 0; x < 2; x++) r.mem.piece(d_sum[x], n, want[x]).piece(pool[x], 3 * n, want[x]); // mean | max | last
+    r.mem.piece(picked[0], np, out->picked_h != nullptr).piece(picked[1], np, out->picked_c != nullptr);
+    r.mem.piece(d_picks, table.size(), npick > 0);
+    EmbedArgs a{};
+    if (int rc = r.upload(h0, c0, skip, a)) return rc;
     for (int x = 0; x < 2; x++) { // a stream without a byte never reaches the fold: empty pools, last = its start state
         if (!want[x]) continue;
         HIP_TRY(hipMemsetAsync(pool[x], 0, sizeof(float) * 2 * n, h->st));
-        HIP_TRY(hipMemcpyAsync(pool[x] + 2 * n, x ? C0 : H0, sizeof(float) * n, hipMemcpyDeviceToDevice, h->st));
+        HIP_TRY(hipMemcpyAsync(pool[x] + 2 * n, x ? r.C0 : r.H0, sizeof(float) * n, hipMemcpyDeviceToDevice, h->st));
     }
-    HIP_TRY(hipMemcpyAsync(d_off, text_off, sizeof(uint64_t) * (streams + 1), hipMemcpyHostToDevice, h->st));
-    if (skip) HIP_TRY(hipMemcpyAsync(d_skip, skip, sizeof(uint64_t) * streams, hipMemcpyHostToDevice, h->st));
-    else HIP_TRY(hipMemsetAsync(d_skip, 0, sizeof(uint64_t) * streams, h->st));
-    HIP_TRY(hipMemcpyAsync(d_first, first.data(), sizeof(int64_t) * streams, hipMemcpyHostToDevice, h->st));
-    if (!slot.empty()) HIP_TRY(hipMemcpyAsync(d_slot, slot.data(), sizeof(int32_t) * slot.size(), hipMemcpyHostToDevice, h->st));
     if (npick) HIP_TRY(hipMemcpyAsync(d_picks, table.data(), sizeof(int32_t) * table.size(), hipMemcpyHostToDevice, h->st));
-    if (tot) HIP_TRY(hipMemcpyAsync(d_text, text, tot, hipMemcpyHostToDevice, h->st));
-    HIP_TRY(hipMemsetAsync(d_bits, 0, sizeof(double) * streams, h->st));
-    HIP_TRY(hipStreamSynchronize(h->st)); // (the host vectors are pageable: their copies are done; the loop is on e's stream)
-
-    EmbedArgs a{};
-    a.text = d_text;
-    a.off = d_off;
-    a.skip = d_skip;
-    a.slot = d_slot;
-    a.first = d_first;
-    a.H0 = H0;
-    a.C0 = C0;
-    a.xi = e->xi;
-    a.ti = e->ti;
-    a.H = e->H;
-    a.C = e->C;
-    a.colloss = e->colloss;
-    a.bits = d_bits;
     for (int x = 0; x < 2; x++) {
         a.sum[x] = d_sum[x];
         a.mean[x] = pool[x];
@@ -3132,36 +3126,18 @@ int lstm_hip_embed_texts(lstm_hip_t *h, int32_t streams, const uint8_t *text, co
         a.picked[x] = picked[x];
     }
     a.picks = d_picks;
-    a.lanes = lanes;
-    a.N = N;
-    struct LoopMode { // the internal handle is back in its standalone mode on every return path
-        lstm_hip_ctx *e;
-        ~LoopMode() { e->in_loop = false, e->keep_outputs = true; }
-    } loop_mode{e};
-    e->in_loop = true;
-    e->keep_outputs = false;
-    if (elapsed_ms) HIP_TRY(hipEventRecord(e->evt0, e->st));
-    for (int64_t w = 0; w < windows; w++) {
-        embed_window(a, w, e->plan.n_cus, e->st);
-        if (int rc = eval_status("embed_window")) return rc;
-        if (int rc = do_forward(e)) return rc;
-        embed_fold(a, w, pick_at[w], pick_at[w + 1], e->plan.n_cus, e->st);
-        if (int rc = eval_status("embed_fold")) return rc;
-    }
-    if (elapsed_ms) {
-        HIP_TRY(hipEventRecord(e->evt1, e->st));
-        HIP_TRY(hipEventSynchronize(e->evt1));
-        HIP_TRY(hipEventElapsedTime(elapsed_ms, e->evt0, e->evt1));
-    }
-    HIP_TRY(hipStreamSynchronize(e->st));
-    if (int rc = check_abort(e)) return rc;
+    const auto fold = [&](int64_t w) {
+        embed_fold(a, w, pick_at[w], pick_at[w + 1], r.e->plan.n_cus, r.e->st);
+        return eval_status("embed_fold");
+    };
+    if (int rc = r.loop(a, fold, elapsed_ms)) return rc;
 
-    if (out->bits) HIP_TRY(hipMemcpyAsync(out->bits, d_bits, sizeof(double) * streams, hipMemcpyDeviceToHost, h->st));
-    if (int rc = download_states(h, out->mean_h, out->mean_c, pool[0], pool[1], stage, streams)) return rc;
-    if (int rc = download_states(h, out->max_h, out->max_c, a.maxv[0], a.maxv[1], stage, streams)) return rc;
-    if (int rc = download_states(h, out->last_h, out->last_c, a.last[0], a.last[1], stage, streams)) return rc;
+    if (out->bits) HIP_TRY(hipMemcpyAsync(out->bits, r.d_bits, sizeof(double) * streams, hipMemcpyDeviceToHost, h->st));
+    if (int rc = download_states(h, out->mean_h, out->mean_c, pool[0], pool[1], r.stage, streams)) return rc;
+    if (int rc = download_states(h, out->max_h, out->max_c, a.maxv[0], a.maxv[1], r.stage, streams)) return rc;
+    if (int rc = download_states(h, out->last_h, out->last_c, a.last[0], a.last[1], r.stage, streams)) return rc;
     if (npick)
-        if (int rc = download_states(h, out->picked_h, out->picked_c, picked[0], picked[1], stage, (int)npick)) return rc;
+        if (int rc = download_states(h, out->picked_h, out->picked_c, picked[0], picked[1], r.stage, (int)npick)) return rc;
     HIP_TRY(hipStreamSynchronize(h->st));
     if (out->count)
         for (int32_t s = 0; s < streams; s++) {

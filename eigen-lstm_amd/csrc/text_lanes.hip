@@ -1,16 +1,17 @@
-// embed.hip -- embed_window / embed_fold: the two launches lstm_hip_embed_texts puts around the forward path (kernels.h;
-// DESIGN.md section 3.23).  A file of its own, so that the code object of the training window's kernels is the one it was.
+// text_lanes.hip -- lane_window, eval_fold, embed_fold: the launches lstm_hip_eval_texts and lstm_hip_embed_texts put around
+// the forward path (kernels.h; DESIGN.md sections 3.17 and 3.23).  A file of its own, apart from the training window's kernels.
 //
-// As in eval_window / eval_fold a stream sits on one lane and a lane holds one stream per window, so no two workgroups
-// touch the same stream's element.  N % 16 == 0 and every column starts on a 16-byte boundary, so the state columns move as
-// float4.
+// A stream sits on one lane and a lane holds one stream per window, so every element is independent and no two workgroups
+// touch the same stream's element: grid-stride loops over lanes x rows for the indices, over lanes x N / 4 for the state
+// columns in float4 (N % 16 == 0 and every column starts on a 16-byte boundary), and over the lanes for the bits, whose
+// additions per stream are sequential in text order: one thread, one window after the other on the stream.
 #include "kernels.h"
 
 #include <algorithm>
 
 namespace lstmk {
 
-__global__ __launch_bounds__(256) void k_embed_window(EmbedArgs a, long long w) {
+__global__ __launch_bounds__(256) void k_lane_window(LaneArgs a, long long w) {
     const long long tid = (long long)blockIdx.x * 256 + threadIdx.x, nth = (long long)gridDim.x * 256;
     const int32_t *slot = a.slot + w * a.lanes;
     for (long long i = tid; i < (long long)EVAL_STEPS * a.lanes; i += nth) {
@@ -20,7 +21,7 @@ __global__ __launch_bounds__(256) void k_embed_window(EmbedArgs a, long long w) 
         if (s >= 0) {
             const uint64_t o = a.off[s], len = a.off[s + 1] - o;
             const uint64_t j = (uint64_t)(w - a.first[s]) * EVAL_STEPS + r; // the step: feeds byte j; its target is byte j + 1
-            if (j < len) {
+            if (j + 1 < len + a.feed_last) {
                 xv = (int)a.text[o + j];
                 if (j + 1 < len && j + 1 >= a.skip[s]) tv = (int)a.text[o + j + 1];
             }
@@ -44,33 +45,56 @@ __global__ __launch_bounds__(256) void k_embed_window(EmbedArgs a, long long w) 
     }
 }
 
+// The bits of the lane's stream in window w, for the thread that holds the lane: steps j0 .. j0 + rows - 1 of the stream's
+// L - 1 steps with a target are in this window, in rows 1 .. rows; those at or above skip are scored.  Adds (double)colloss of
+// the scored rows to bits[s] in row order and scatters the floats to sur (may be null) at the scored byte's place.
+__device__ __forceinline__ void lane_bits(const LaneArgs &a, long long w, long long l, int s, float *sur) {
+    const uint64_t o = a.off[s], n = a.off[s + 1] - o - 1; // (a placed stream has at least one byte)
+    const uint64_t j0 = (uint64_t)(w - a.first[s]) * EVAL_STEPS, skip = a.skip[s];
+    if (j0 >= n) return; // (feed_last: the window of the last byte alone)
+    const int rows = n - j0 < (uint64_t)EVAL_STEPS ? (int)(n - j0) : EVAL_STEPS;
+    const float *__restrict__ col = a.colloss + l;
+    double sum = a.bits[s];
+    for (int r0 = 0; r0 < rows; r0 += 16) { // sixteen independent loads in flight (a row past the last: the last again, so
+        float v[16];                        // that no load hides behind a branch), then their additions in row order
+#pragma unroll
+        for (int u = 0; u < 16; u++) v[u] = col[(size_t)(r0 + u < rows ? r0 + u : rows - 1) * a.lanes];
+#pragma unroll
+        for (int u = 0; u < 16; u++) {
+            if (r0 + u >= rows || j0 + r0 + u + 1 < skip) continue; // past the end / fed, not scored
+            sum += (double)v[u];
+            if (sur) sur[o + j0 + r0 + u + 1] = v[u];
+        }
+    }
+    a.bits[s] = sum;
+}
+
+__global__ __launch_bounds__(256) void k_eval_fold(EvalArgs a, long long w) {
+    const long long tid = (long long)blockIdx.x * 256 + threadIdx.x, nth = (long long)gridDim.x * 256;
+    const int32_t *slot = a.slot + w * a.lanes;
+    for (long long l = tid; l < a.lanes; l += nth)
+        if (slot[l] >= 0) lane_bits(a, w, l, slot[l], a.sur);
+    if (a.Hout == nullptr && a.Cout == nullptr) return;
+    const int N4 = a.N / 4;
+    for (long long i = tid; i < (long long)a.lanes * N4; i += nth) {
+        const int l = (int)(i / N4), q = (int)(i - (long long)l * N4);
+        const int s = slot[l];
+        if (s < 0) continue;
+        const uint64_t n = a.off[s + 1] - a.off[s] - 1, j0 = (uint64_t)(w - a.first[s]) * EVAL_STEPS;
+        if (n - j0 > (uint64_t)EVAL_STEPS) continue; // the stream goes on in the next window
+        const size_t src = (size_t)(n - j0) * a.lanes * N4 + i; // the column of its last step
+        if (a.Hout) reinterpret_cast<float4 *>(a.Hout)[(size_t)s * N4 + q] = reinterpret_cast<const float4 *>(a.H)[src];
+        if (a.Cout) reinterpret_cast<float4 *>(a.Cout)[(size_t)s * N4 + q] = reinterpret_cast<const float4 *>(a.C)[src];
+    }
+}
+
 __global__ __launch_bounds__(256) void k_embed_fold(EmbedArgs a, long long w, long long pick_lo, long long pick_hi) {
     __shared__ double s_sum[32][4];
     __shared__ float4 s_max[8][32];
     const long long tid = (long long)blockIdx.x * 256 + threadIdx.x, nth = (long long)gridDim.x * 256;
     const int32_t *slot = a.slot + w * a.lanes;
-    for (long long l = tid; l < a.lanes; l += nth) {
-        const int s = slot[l];
-        if (s < 0) continue;
-        // steps j0 .. j0 + rows - 1 are in this window; step j has a target where j + 1 < L and j + 1 >= skip
-        const uint64_t o = a.off[s], L = a.off[s + 1] - o, j0 = (uint64_t)(w - a.first[s]) * EVAL_STEPS, skip = a.skip[s];
-        const uint64_t n = L - 1; // (a placed stream has L >= 1)
-        if (j0 >= n) continue;
-        const int rows = n - j0 < (uint64_t)EVAL_STEPS ? (int)(n - j0) : EVAL_STEPS;
-        const float *__restrict__ col = a.colloss + l;
-        double sum = a.bits[s];
-        for (int r0 = 0; r0 < rows; r0 += 16) { // sixteen independent loads in flight (a row past the last: the last again, so
-            float v[16];                        // that no load hides behind a branch), then their additions in row order
-#pragma unroll
-            for (int u = 0; u < 16; u++) v[u] = col[(size_t)(r0 + u < rows ? r0 + u : rows - 1) * a.lanes];
-#pragma unroll
-            for (int u = 0; u < 16; u++) {
-                if (r0 + u >= rows || j0 + r0 + u + 1 < skip) continue;
-                sum += (double)v[u];
-            }
-        }
-        a.bits[s] = sum;
-    }
+    for (long long l = tid; l < a.lanes; l += nth)
+        if (slot[l] >= 0) lane_bits(a, w, l, slot[l], nullptr);
     const int N4 = a.N / 4;
     const size_t stride = (size_t)a.lanes * N4; // float4s per row of H / C
     // The pools.  A workgroup takes one (source, lane, 32 float4s of N) at a time as 8 chunks of 16 rows x 32 threads: every
@@ -168,14 +192,19 @@ __global__ __launch_bounds__(256) void k_embed_fold(EmbedArgs a, long long w, lo
     }
 }
 
-static int window_blocks(long long work, int cus) { // as eval_window: at most one workgroup per CU
-    long long blocks = (work + 255) / 256;
+static int window_blocks(long long work, int cus) {
+    long long blocks = (work + 255) / 256; // one element per thread while the grid stays within the CUs: every element is a
+                                           // chain of dependent loads (slot, offsets, byte), so more threads, not longer loops
     if (blocks > cus) blocks = cus;
     return blocks < 1 ? 1 : (int)blocks;
 }
-void embed_window(const EmbedArgs &a, int64_t w, int cus, hipStream_t st) {
+void lane_window(const LaneArgs &a, int64_t w, int cus, hipStream_t st) {
     const long long work = (long long)a.lanes * (EVAL_STEPS > a.N / 4 ? EVAL_STEPS : a.N / 4);
-    hipLaunchKernelGGL(k_embed_window, dim3(window_blocks(work, cus)), dim3(256), 0, st, a, (long long)w);
+    hipLaunchKernelGGL(k_lane_window, dim3(window_blocks(work, cus)), dim3(256), 0, st, a, (long long)w);
+}
+void eval_fold(const EvalArgs &a, int64_t w, int cus, hipStream_t st) {
+    const long long work = a.Hout || a.Cout ? (long long)a.lanes * (a.N / 4) : a.lanes;
+    hipLaunchKernelGGL(k_eval_fold, dim3(window_blocks(work, cus)), dim3(256), 0, st, a, (long long)w);
 }
 void embed_fold(const EmbedArgs &a, int64_t w, int64_t pick_lo, int64_t pick_hi, int cus, hipStream_t st) {
     const long long N4 = a.N / 4, nsrc = (a.last[0] ? 1 : 0) + (a.last[1] ? 1 : 0);

@@ -16,7 +16,7 @@ section 3.23).
       `ratio` line per shape from the medians of all lines of an arm.
   python tools/embed_cost.py one --N 512 --lanes 64 [--arm embed_cell]
       a single call after an untimed one, for a `rocprofv3 --kernel-trace --stats` run of its own
-      (tools/kernel_stats_from_db.py): the share of k_embed_window and k_embed_fold in the window.
+      (tools/kernel_stats_from_db.py): the share of k_lane_window and k_embed_fold in the window.
 
 The model is the seeded initialisation: speed does not depend on the weights."""
 import argparse

@@ -15,7 +15,7 @@ section 3.17).
       one `ratio` line per shape from the medians of all lines of an arm.
   python tools/eval_cost.py one --N 512 --lanes 64
       a single eval_texts call after an untimed one, for a `rocprofv3 --kernel-trace --stats` run of its own
-      (tools/kernel_stats_from_db.py): the share of k_eval_window and k_eval_fold in the window.
+      (tools/kernel_stats_from_db.py): the share of k_lane_window and k_eval_fold in the window.
 
 MB/s counts the scored bytes (1 MiB - 1, or 64 KiB - 1) over the wall time of the call, which ends in a stream synchronise and
 includes the uploads.  The model is the seeded initialisation: speed does not depend on the weights."""
