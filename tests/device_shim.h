@@ -35,6 +35,16 @@ template <class T> T __shfl_xor(T v, int o, int) { // (every work-item of the gr
     g_bar->arrive_and_wait();
     return r;
 }
+// (a template, so that an emulation which brings an atomicOr of its own keeps it: the plain function is the better match)
+template <class T> T atomicOr(T *p, T v) { std::lock_guard<std::mutex> l(g_mu); T o = *p; *p = o | v; return o; }
+template <class T> T __shfl_up(T v, int d, int) { // lane = work-item mod 64; lanes below d keep their own value
+    memcpy(g_lane[threadIdx.x], &v, sizeof(T));
+    g_bar->arrive_and_wait();
+    T r = v;
+    if ((threadIdx.x & 63) >= d) memcpy(&r, g_lane[threadIdx.x - d], sizeof(T));
+    g_bar->arrive_and_wait();
+    return r;
+}
 alignas(16) inline unsigned char g_dynamic_lds[64 * 1024]; // the most a head is granted
 #define HEAD_DYNAMIC_LDS(T, name) T *name = reinterpret_cast<T *>(g_dynamic_lds)
 

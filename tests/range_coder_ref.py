@@ -1,6 +1,8 @@
 """A pure-Python copy of the device's range coder (eigen-lstm_amd/csrc/heads/code_head.inc, rc_* and k_code_head; DESIGN.md
 section 3.6): the carryless 32-bit coder (Subbotin), TOP = 2^24, BOT = 2^16, a 4-byte flush, totals <= 2^16, at most three
-byte moves per coded symbol.  Test helper: it re-encodes a device trace of (cum, freq, total) and decodes codes back."""
+byte moves per coded symbol.  Test helper: it re-encodes a device trace of (cum, freq, total) and decodes codes back.
+encode and decode take an optional Stats, which counts the paths a run took and keeps the coder's final state; it changes
+no result."""
 TOP = 1 << 24
 BOT = 1 << 16
 MASK = 0xFFFFFFFF
@@ -11,13 +13,30 @@ class CoderError(RuntimeError):
     """the device would flag this call (a total above 2^16, or a fourth byte move in one step)"""
 
 
-def _normalize(low, rng, move):
+class Stats:
+    """cuts: steps that took the carryless cut; moves: the byte moves of every step, max_moves the most of them; clamps:
+    decode steps whose (code - low) / r was >= T and was clamped to T - 1; and the state after the last step as the device
+    keeps it: low, range, code (decoder), pos (code bytes written or read, the encoder's four flush bytes included)."""
+
+    def __init__(self):
+        self.cuts = self.max_moves = self.clamps = 0
+        self.moves = []
+        self.low = self.range = self.code = self.pos = None
+
+
+def _normalize(low, rng, move, stats=None):
     n = 0
+    cut = False
     while True:
         if (low ^ ((low + rng) & MASK)) >= TOP:  # top bytes differ
             if rng >= BOT:
+                if stats is not None:
+                    stats.moves.append(n)
+                    stats.cuts += cut
+                    stats.max_moves = max(stats.max_moves, n)
                 return low, rng
             rng = (-low) & (BOT - 1)  # the carryless cut
+            cut = True
         if n == MAX_SHIFTS:
             raise CoderError("more than three byte moves in one step")
         move(low >> 24)
@@ -26,7 +45,7 @@ def _normalize(low, rng, move):
         n += 1
 
 
-def encode(symbols):
+def encode(symbols, stats=None):
     """symbols: iterable of (cum, freq, total).  Returns the code (empty for no symbols)."""
     out = bytearray()
     low, rng, n = 0, MASK, 0
@@ -37,16 +56,18 @@ def encode(symbols):
         r = rng // total
         low = (low + cum * r) & MASK
         rng = (freq * r) & MASK
-        low, rng = _normalize(low, rng, out.append)
+        low, rng = _normalize(low, rng, out.append, stats)
         n += 1
     if n:
         for _ in range(4):
             out.append(low >> 24)
             low = (low << 8) & MASK
+    if stats is not None and n:
+        stats.low, stats.range, stats.code, stats.pos = low, rng, 0, len(out)
     return bytes(out)
 
 
-def decode(code, count, model):
+def decode(code, count, model, stats=None):
     """Decodes `count` symbols.  model(i) -> (total, find) for step i, where find(v) gives (symbol, cum, freq) of the
     interval holding v (cum <= v < cum + freq).  Bytes past the end of `code` read as 0.  Returns the symbols."""
     pos = 0
@@ -67,7 +88,11 @@ def decode(code, count, model):
         if total > BOT:
             raise CoderError(f"total {total} above 2^16")
         rng //= total
-        v = min(((c - low) & MASK) // rng, total - 1)
+        v = ((c - low) & MASK) // rng
+        if v >= total:
+            v = total - 1
+            if stats is not None:
+                stats.clamps += 1
         sym, cum, freq = find(v)
         low = (low + cum * rng) & MASK
         rng = (freq * rng) & MASK
@@ -76,8 +101,10 @@ def decode(code, count, model):
             nonlocal c
             c = ((c << 8) | get()) & MASK
 
-        low, rng = _normalize(low, rng, move)
+        low, rng = _normalize(low, rng, move, stats)
         out.append(sym)
+    if stats is not None and count:
+        stats.low, stats.range, stats.code, stats.pos = low, rng, c, pos
     return out
 
 

@@ -17,6 +17,7 @@ import constraint_ref as cr
 import deadline_ref as dr
 import logit_processor_ref as lr
 import sampling_ref as sr
+from logits_ref import logits32 as _logits32
 from oracle_lib import split_params
 
 pytestmark = pytest.mark.gpu
@@ -112,14 +113,6 @@ def _group_rule():
             sb *= 2
         return sb
     return group
-
-
-def _logits32(Why, by, h):
-    """z = Why*h + by as gen_head sums it: sequentially in k, separate float multiply and add"""
-    z = np.zeros(M, f32)
-    for k in range(h.size):
-        z = (z + (Why[:, k] * h[k]).astype(f32)).astype(f32)
-    return (z + by).astype(f32)
 
 
 # (temperature, top_k, top_p, stop byte, table (0 none, 1 table, 2 accepting), bias, min_p, n, history)
