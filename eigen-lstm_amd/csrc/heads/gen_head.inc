@@ -42,6 +42,9 @@
 // lowest existing one.  The host has checked F[count][q0], so E >= 1 at every draw and the stream ends in an accepting state.
 // PROCESS (lstm_hip_generate_processed; DESIGN.md section 3.22; implies FILTER, goes with any of the three above, and without it
 // the instantiation is the code above and nothing else): per drawn byte, in this order,
+//   a.gsum      (guides; lstm_hip_generate_guided, DESIGN.md section 3.24) thread m's logit becomes a.wmain * z + a.gsum[s * 256 + m],
+//               a multiply and an add rounded separately behind by; the sum is k_guide_logits' of this step (guide_logits.inc).
+//               With a.gsum null nothing is read and the logit is z.
 //   a.bias      thread m adds a.bias[m] to its logit (one float add behind by; greedy draws see it, prompt bytes do not).
 //   a.no_repeat ahead of the product the group's 256 threads scan the stream's text T = a.ptext[a.ptoff[s] ..) ++ its column of
 //               a.out (draws 0 .. i - 1, strided by streams) in strides of 256 positions: where T[p .. p + n - 1) equals T's
@@ -188,8 +191,10 @@ __global__ __launch_bounds__(256) void k_gen_head(GenHeadArgs a, long long t) {
 #pragma unroll
         for (int j = 0; j < SB; j++) {
             y[j] = y[j] + bym; // the logit z
-            if constexpr (PROCESS)
+            if constexpr (PROCESS) {
+                if (a.gsum && phase[j] == 2) y[j] = a.wmain * y[j] + a.gsum[(size_t)(s0 + j) * 256 + m]; // (uniform test; two roundings)
                 if (a.bias && phase[j] == 2) y[j] = y[j] + bias_m;
+            }
             if constexpr (CONSTRAIN)
                 if (banned[j]) y[j] = -INFINITY;
             if constexpr (PROCESS)

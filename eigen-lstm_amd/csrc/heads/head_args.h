@@ -1,4 +1,4 @@
-// head_args.h -- the argument blocks of the inference heads (k_gen_head, k_beam_head, k_code_head, k_score_head), in plain
+// head_args.h -- the argument blocks of the inference heads (k_gen_head, k_guide_logits, k_beam_head, k_code_head, k_score_head), in plain
 // C++ so that the host emulations under tests/ compile the same declarations as the library.  kernels.h includes it and
 // declares the launchers.
 #pragma once
@@ -48,6 +48,30 @@ struct GenHeadArgs {
     int no_repeat;              // n: 0 off, else 1..64
     const uint8_t *ptext;       // each stream's history ++ prompt, concatenated (null: all empty); with no_repeat
     const uint64_t *ptoff;      // streams + 1 offsets into ptext; with no_repeat
+    // guides (lstm_hip_generate_guided): read only by the PROCESS instantiation (`process` is set with
+    // it); null / 0 otherwise
+    const float *gsum;          // [streams][256] the guides' weighted logit sum of this step, written by k_guide_logits (null: none)
+    float wmain;                // (float)main_weight: a drawn byte's logit becomes wmain * z + gsum ahead of the bias
+};
+
+// ---- guides (lstm_hip_generate_guided / lstm_hip_score_guided): per step guide_logits on every guide's
+// state after t inputs, ahead of the head: gsum[s][m] = w[0] * z^0_m, then + w[k] * z^k_m for k = 1.. in index order, for the
+// streams whose head needs logits at this step; and each guide's state to its h_out / c_out at the step where the head copies
+// the main model's.  Afterwards one fwd_step per guide on the head's x_next.  H, C, h_out, c_out of guide k are [streams][N[k]].
+constexpr int MAX_GUIDES = 4;   // LSTM_HIP_MAX_GUIDES
+struct GuideLogitsArgs {
+    const float *Why[MAX_GUIDES], *by[MAX_GUIDES];
+    const float *H[MAX_GUIDES], *C[MAX_GUIDES]; // state after t inputs
+    float *h_out[MAX_GUIDES], *c_out[MAX_GUIDES]; // the state after each stream's last input (null: not kept)
+    int N[MAX_GUIDES];          // internal widths, each % 16 == 0
+    float w[MAX_GUIDES];        // (float)weight
+    float *gsum;                // [streams][256]
+    int nguides, streams;
+    const uint64_t *off;        // streams + 1 offsets: the generator's prompts (null: none) or the scorer's texts
+    int scorer;                 // 0: the generator's streams (off, end, count as GenHeadArgs), 1: the scorer's (off, first)
+    int32_t *end;               // generator: GenHeadArgs::end, only read (always set: a guided draw is a processed one)
+    int count;                  // generator: GenHeadArgs::count
+    int first;                  // scorer: ScoreHeadArgs::first
 };
 
 // ---- beam search (lstm_hip_beam_search): per step beam_head on the state after t inputs, then
@@ -122,6 +146,10 @@ struct ScoreHeadArgs {
     const uint16_t *ctab;       // [states][256] the byte automaton (GenHeadArgs::ctab), or null
     const uint16_t *qpos;       // [total] the automaton state each byte stands in (walked by the host); with ctab
     int N, streams, first, top_n;
+    // guides (lstm_hip_score_guided), as GenHeadArgs::gsum / wmain: a scored byte's logit becomes
+    // wmain * z + gsum ahead of the constraint mask
+    const float *gsum;          // [streams][256], or null
+    float wmain;
 };
 
 } // namespace lstmk

@@ -6,6 +6,8 @@
 // hands byte t to the recurrence, and the byte is scored with the distribution of the state after t inputs unless it is byte
 // 0 of a call with first = 0:
 //   z = Why*h + by        k_gen_head's sum: sequential in k, separate multiply and add, the same SB grouping rule
+//   a.gsum (guides)       z_m <- a.wmain * z_m + a.gsum[s * 256 + m] (lstm_hip_score_guided, DESIGN.md section 3.24: a multiply and
+//                         an add rounded separately; k_guide_logits' sum of this step); with a.gsum null nothing is read
 //   CONSTRAIN             z_m = -inf where a.ctab[q * 256 + m] is 0xFFFF, q = a.qpos[position]: everything below sees the mask
 //   e_m = expf(z_m) (STABLE: expf(z_m - max z)), s = the sum of e in index order, p_m = e_m / s
 //   surprisal(m) = -log2f(p_m) (STABLE: lse_surprisal(s, max z, z_m)): k_gen_head's prompt bits, term by term
@@ -77,6 +79,7 @@ __global__ __launch_bounds__(256) void k_score_head(ScoreHeadArgs a, long long t
 #pragma unroll
     for (int j = 0; j < SB; j++) {
         y[j] = y[j] + bym; // the logit z
+        if (a.gsum && act[j]) y[j] = a.wmain * y[j] + a.gsum[(size_t)(s0 + j) * 256 + m]; // (uniform test; two roundings)
         if constexpr (CONSTRAIN)
             if (banned[j]) y[j] = -INFINITY;
         ps[j][m] = y[j];

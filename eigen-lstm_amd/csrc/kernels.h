@@ -459,12 +459,15 @@ hipError_t sample(const float *P, int N, float *hc /*2N*/, const double *u, int 
                   hipStream_t st);
 
 // ---- the inference heads: one launch per step on the state after t inputs, then fwd_step over all columns with x_next as
-// inputs.  Their argument blocks (GenHeadArgs, BeamHeadArgs, CoderState and CodeHeadArgs, ScoreHeadArgs) are described in
+// inputs.  Their argument blocks (GenHeadArgs, GuideLogitsArgs, BeamHeadArgs, CoderState and CodeHeadArgs, ScoreHeadArgs) are described in
 // heads/head_args.h, included above; the kernels are heads/*.inc, included by kernels.hip.
 // stable: LSTM_HIP_STABLE_SOFTMAX.  hipSuccess, or the HIP error of a refused LDS request with nothing launched (the FILTER
 // instantiations only; beam_head and score_head likewise)
 hipError_t gen_head(const GenHeadArgs &a, long long t, bool stable, hipStream_t st);
 int gen_head_group(int N, int streams); // streams per workgroup of gen_head
+// the guides of a guided call (GuideLogitsArgs, heads/guide_logits.inc): one launch per step ahead of the head, for all guides;
+// the group size is gen_head_group(the widest guide, streams).  hipSuccess, or the HIP error of a refused LDS request
+hipError_t guide_logits(const GuideLogitsArgs &a, long long t, hipStream_t st);
 hipError_t beam_head(const BeamHeadArgs &a, long long t, hipStream_t st);
 // out[(s * W + r) * count + i]: byte i of final slot r of stream s, walked back through the tables; 0 from len on
 void beam_backtrack(const uint8_t *trace_parent, const uint8_t *trace_byte, const int32_t *len, uint8_t *out, int streams,

@@ -2140,6 +2140,29 @@ hipError_t gen_head(const GenHeadArgs &a, long long t, bool stable, hipStream_t 
     return stable ? gen_head_launch<true>(a, t, st) : gen_head_launch<false>(a, t, st);
 }
 
+#include "heads/guide_logits.inc"
+hipError_t guide_logits(const GuideLogitsArgs &a, long long t, hipStream_t st) {
+    int widest = 16;
+    for (int g = 0; g < a.nguides; g++) widest = a.N[g] > widest ? a.N[g] : widest;
+    const int sb = gen_head_group(widest, a.streams); // (h of the group within 64 KB of LDS; no static LDS)
+    const size_t lds = (size_t)sb * widest * sizeof(float);
+    const dim3 grid((a.streams + sb - 1) / sb);
+#define GUIDE_LOGITS_CASE(SB)                                                                                               \
+    case SB:                                                                                                                \
+        if (const hipError_t e = grant_lds<k_guide_logits<SB>, 0>(lds)) return e;                                           \
+        hipLaunchKernelGGL((k_guide_logits<SB>), grid, dim3(256), lds, st, a, t);                                           \
+        break;
+    switch (sb) {
+        GUIDE_LOGITS_CASE(1)
+        GUIDE_LOGITS_CASE(2)
+        GUIDE_LOGITS_CASE(4)
+        GUIDE_LOGITS_CASE(8)
+        GUIDE_LOGITS_CASE(16)
+    }
+#undef GUIDE_LOGITS_CASE
+    return hipSuccess;
+}
+
 #include "heads/beam_head.inc"
 template <int WP, bool EXACT, bool CONSTRAIN> static hipError_t beam_head_launch(const BeamHeadArgs &a, long long t, hipStream_t st) {
     // static LDS is up to 33 KB (ps), dynamic up to 64 KB

@@ -66,6 +66,8 @@ enum KernelId {
     K_SOFTMAX_SOFT = K_COUNT_BASE, // K_SOFTMAX's launch with soft targets (lstm_hip_set_soft_targets): label smoothing, a teacher's term
     K_SOFTMAX_WEIGHTED,            // K_SOFTMAX_TEXT's launch with a weight per target byte (lstm_hip_set_train_texts_weighted)
     K_GRAD_ACCUMULATE,             // gradient accumulation (lstm_hip_set_grad_accumulation): a window's gradient into the accumulator
+    K_COUNT_MORE, // ... and the ids from here on in kKernelNamesLast
+    K_GUIDE_LOGITS = K_COUNT_MORE, // one step of the guides of a guided call (lstm_hip_generate_guided / lstm_hip_score_guided)
     K_COUNT
 };
 const char *const kKernelNames[K_COUNT] = { // (K_COUNT_BASE names; the rows behind them stay null)
@@ -73,8 +75,11 @@ const char *const kKernelNames[K_COUNT] = { // (K_COUNT_BASE names; the rows beh
     "dW_db", "loss_dby", "adagrad", "slide", "allreduce", "fwd_persistent", "bwd_persistent", "gen_head", "side_sums",
     "gemm_dU_halves", "grad_sumsq", "grad_norm", "adam", "code_head", "block_window", "text_window", "text_fold",
     "softmax_loss_dy_text", "beam_head", "beam_backtrack", "score_head"};
-const char *const kKernelNamesMore[K_COUNT - K_COUNT_BASE] = {"softmax_soft", "softmax_loss_dy_weighted", "grad_accumulate"};
-inline const char *kernel_name(int id) { return id < K_COUNT_BASE ? kKernelNames[id] : kKernelNamesMore[id - K_COUNT_BASE]; }
+const char *const kKernelNamesMore[K_COUNT_MORE - K_COUNT_BASE] = {"softmax_soft", "softmax_loss_dy_weighted", "grad_accumulate"};
+const char *const kKernelNamesLast[K_COUNT - K_COUNT_MORE] = {"guide_logits"};
+inline const char *kernel_name(int id) {
+    return id < K_COUNT_BASE ? kKernelNames[id] : id < K_COUNT_MORE ? kKernelNamesMore[id - K_COUNT_BASE] : kKernelNamesLast[id - K_COUNT_MORE];
+}
 
 // ---- RCCL, loaded on first use so single-GPU users never touch it --------------------------
 struct UniqueId {
@@ -2025,14 +2030,15 @@ class Scratch {
 
 // The start state of `cols` columns, host h0 / c0 (either may be null: zeros) to the device's H / Cs.  A padded handle takes
 // the logical-width columns through `stage` ([2][cols * N_log], a piece of the call's scratch) and pad_copy: padding rows zero.
-int upload_states(lstm_hip_t *h, const float *h0, const float *c0, float *H, float *Cs, float *stage, int cols) {
-    const size_t n = (size_t)h->cfg.N * cols, nl = (size_t)h->N_log * cols;
-    const PadMap map = pad_map_rows(1, h->N_log, h->cfg.N, cols);
+// (N, N_log: the internal and the logical width of the model whose state it is -- the handle's own, or a guide's)
+int upload_states(lstm_hip_t *h, int N, int N_log, const float *h0, const float *c0, float *H, float *Cs, float *stage, int cols) {
+    const size_t n = (size_t)N * cols, nl = (size_t)N_log * cols;
+    const PadMap map = pad_map_rows(1, N_log, N, cols);
     for (int k = 0; k < 2; k++) {
         const float *src = k ? c0 : h0;
         float *dst = k ? Cs : H;
         if (!src) HIP_TRY(hipMemsetAsync(dst, 0, sizeof(float) * n, h->st));
-        else if (h->padded()) {
+        else if (N_log != N) {
             HIP_TRY(hipMemcpyAsync(stage + k * nl, src, sizeof(float) * nl, hipMemcpyHostToDevice, h->st));
             pad_copy(stage + k * nl, dst, map, true, h->st);
             if (int rc = pad_status()) return rc;
@@ -2041,15 +2047,19 @@ int upload_states(lstm_hip_t *h, const float *h0, const float *c0, float *H, flo
     }
     return 0;
 }
+int upload_states(lstm_hip_t *h, const float *h0, const float *c0, float *H, float *Cs, float *stage, int cols) {
+    return upload_states(h, h->cfg.N, h->N_log, h0, c0, H, Cs, stage, cols);
+}
 // the same in reverse: the device's H / Cs to those of h_out / c_out that are wanted
-int download_states(lstm_hip_t *h, float *h_out, float *c_out, const float *H, const float *Cs, float *stage, int cols) {
-    const size_t n = (size_t)h->cfg.N * cols, nl = (size_t)h->N_log * cols;
-    const PadMap map = pad_map_rows(1, h->N_log, h->cfg.N, cols);
+int download_states(lstm_hip_t *h, int N, int N_log, float *h_out, float *c_out, const float *H, const float *Cs, float *stage,
+                    int cols) {
+    const size_t n = (size_t)N * cols, nl = (size_t)N_log * cols;
+    const PadMap map = pad_map_rows(1, N_log, N, cols);
     for (int k = 0; k < 2; k++) {
         float *dst = k ? c_out : h_out;
         const float *src = k ? Cs : H;
         if (!dst) continue;
-        if (h->padded()) {
+        if (N_log != N) {
             pad_copy(src, stage + k * nl, map, false, h->st);
             if (int rc = pad_status()) return rc;
             HIP_TRY(hipMemcpyAsync(dst, stage + k * nl, sizeof(float) * nl, hipMemcpyDeviceToHost, h->st));
@@ -2057,6 +2067,10 @@ int download_states(lstm_hip_t *h, float *h_out, float *c_out, const float *H, c
             HIP_TRY(hipMemcpyAsync(dst, src, sizeof(float) * n, hipMemcpyDeviceToHost, h->st));
     }
     return 0;
+}
+
+int download_states(lstm_hip_t *h, float *h_out, float *c_out, const float *H, const float *Cs, float *stage, int cols) {
+    return download_states(h, h->cfg.N, h->N_log, h_out, c_out, H, Cs, stage, cols);
 }
 
 // offsets of `streams` streams: off[0] == 0, never decreasing
@@ -2099,17 +2113,140 @@ Model model_of(const lstm_hip_ctx *h) {
     const float *P = infer_block(h);
     return {P + h->pl.W, P + h->pl.U, P + h->pl.b, P + h->pl.Why, P + h->pl.by};
 }
-// one k_fwd_step over `cols` columns: the inputs xi and the state (Hf, Cf) to the state (Ht, Ct)
+// one k_fwd_step over `cols` columns: the inputs xi and the state (Hf, Cf) to the state (Ht, Ct), on h's stream.  N and fast are
+// the width and the LSTM_HIP_FAST_MATH flag of the model m belongs to: the handle's own, or a guide's
+int step_columns(lstm_hip_t *h, const Model &m, int N, bool fast, const float4 *Ufwd, const float *Hf, const float *Cf, float *Ht,
+                 float *Ct, float *G, const int32_t *xi, int cols) {
+    RUN(K_FWD_STEP, fwd_step(Ufwd, m.W, m.b, Hf, Cf, Ht, Ct, G, xi, N, cols, fast, h->st));
+    return 0;
+}
 int step_columns(lstm_hip_t *h, const Model &m, const float4 *Ufwd, const float *Hf, const float *Cf, float *Ht, float *Ct,
                  float *G, const int32_t *xi, int cols) {
-    const bool fast = (h->cfg.flags & LSTM_HIP_FAST_MATH) != 0;
-    RUN(K_FWD_STEP, fwd_step(Ufwd, m.W, m.b, Hf, Cf, Ht, Ct, G, xi, h->cfg.N, cols, fast, h->st));
-    return 0;
+    return step_columns(h, m, h->cfg.N, (h->cfg.flags & LSTM_HIP_FAST_MATH) != 0, Ufwd, Hf, Cf, Ht, Ct, G, xi, cols);
 }
 
 // a head's launcher that returned an error has launched nothing: its request for dynamic LDS was refused
 int head_refused(const char *what, const char *head, hipError_t e) {
     return fail(LSTM_HIP_EHIP, "%s: the LDS request of %s was refused: %s", what, head, hipGetErrorString(e));
+}
+
+// ---- the guides of lstm_hip_generate_guided / lstm_hip_score_guided: other models fed the main
+// model's inputs, each with a state of its own, their logits mixed into the head's.  Everything of a guide is only read: its
+// parameter block, its widths, its flags and its stream (once, for the event the call waits on).  A guide's fragment image of
+// U, its two state pairs, its gate scratch and the mixed sum are pieces of the MAIN handle's scratch, behind every other piece.
+struct Guides {
+    int count = 0; // 0: an unguided call -- nothing below is touched, no piece is added, nothing is launched
+    float wmain = 1.0f;
+    float *gsum = nullptr; // [streams][256]
+    struct One {
+        lstm_hip_ctx *g;
+        Model m;
+        int N, N_log;
+        bool fast;
+        float w;
+        size_t n; // N * streams
+        float4 *Ufwd;
+        float *H, *Cs, *G, *ho, *stage;
+    } r[LSTM_HIP_MAX_GUIDES];
+};
+// the refusals of a guidance block (include/lstm_hip.h); on success gs holds what the call reads of every guide
+int check_guidance(const char *what, lstm_hip_t *h, const lstm_hip_guidance *gd, Guides &gs) {
+    if (gd->size != sizeof(lstm_hip_guidance))
+        return fail(LSTM_HIP_EINVAL, "%s: guidance of %u bytes, expected %zu", what, gd->size, sizeof(lstm_hip_guidance));
+    if (gd->nguides < 1 || gd->nguides > LSTM_HIP_MAX_GUIDES)
+        return fail(LSTM_HIP_EINVAL, "%s: nguides must be in [1, %d] (got %d)", what, LSTM_HIP_MAX_GUIDES, gd->nguides);
+    if (!gd->guides) return fail(LSTM_HIP_EINVAL, "%s: guidance with null guides", what);
+    if (!std::isfinite(gd->main_weight)) return fail(LSTM_HIP_EINVAL, "%s: main_weight must be finite (got %g)", what, gd->main_weight);
+    for (int k = 0; k < gd->nguides; k++) {
+        const lstm_hip_guide &u = gd->guides[k];
+        if (!u.model) return fail(LSTM_HIP_EINVAL, "%s: guide %d: null model", what, k);
+        if (!std::isfinite(u.weight)) return fail(LSTM_HIP_EINVAL, "%s: guide %d: weight must be finite (got %g)", what, k, u.weight);
+        if (u.model->cfg.device != h->cfg.device)
+            return fail(LSTM_HIP_EINVAL, "%s: guide %d is on device %d, the call's handle on device %d", what, k, u.model->cfg.device,
+                        h->cfg.device);
+        if (u.model->cfg.N > 16384) return fail(LSTM_HIP_EINVAL, "%s: guide %d: hidden width %d above 16384", what, k, u.model->cfg.N);
+    }
+    gs.count = gd->nguides;
+    gs.wmain = (float)gd->main_weight;
+    for (int k = 0; k < gs.count; k++) {
+        Guides::One &r = gs.r[k];
+        r.g = gd->guides[k].model;
+        r.m = model_of(r.g);
+        r.N = r.g->cfg.N;
+        r.N_log = r.g->N_log;
+        r.fast = (r.g->cfg.flags & LSTM_HIP_FAST_MATH) != 0;
+        r.w = (float)gd->guides[k].weight;
+    }
+    return 0;
+}
+// the guides' pieces of the call's scratch: named last, so that every earlier offset is the unguided call's
+void guide_pieces(Scratch &mem, Guides &gs, const lstm_hip_guidance *gd, int streams) {
+    for (int k = 0; k < gs.count; k++) {
+        Guides::One &r = gs.r[k];
+        r.n = (size_t)r.N * streams;
+        mem.piece(r.Ufwd, (size_t)r.N * r.N).piece(r.H, 2 * r.n).piece(r.Cs, 2 * r.n).piece(r.G, 4 * r.n);
+        mem.piece(r.ho, 2 * r.n, gd->guides[k].h_out || gd->guides[k].c_out);
+        mem.piece(r.stage, 2 * (size_t)r.N_log * streams, r.N_log != r.N);
+    }
+    mem.piece(gs.gsum, (size_t)256 * streams, gs.count > 0);
+}
+// ahead of the loop: the main stream waits for what the caller queued on every other guide's stream, then the guides' start
+// states and fragment images; ga gets what does not change from step to step
+int guides_begin(lstm_hip_t *h, Guides &gs, const lstm_hip_guidance *gd, int streams, GuideLogitsArgs &ga) {
+    for (int k = 0; k < gs.count; k++) {
+        Guides::One &r = gs.r[k];
+        if (r.g != h) {
+            hipEvent_t ev;
+            HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+            hipError_t e = hipEventRecord(ev, r.g->st);
+            if (e == hipSuccess) e = hipStreamWaitEvent(h->st, ev, 0);
+            (void)hipEventDestroy(ev); // (released once it has completed)
+            HIP_TRY(e);
+        }
+        if (int rc = upload_states(h, r.N, r.N_log, gd->guides[k].h0, gd->guides[k].c0, r.H, r.Cs, r.stage, streams)) return rc;
+        RUN(K_PACK_U, pack_U(r.m.U, r.Ufwd, nullptr, r.N, h->st));
+        ga.Why[k] = r.m.Why;
+        ga.by[k] = r.m.by;
+        ga.h_out[k] = r.ho;
+        ga.c_out[k] = r.ho ? r.ho + r.n : nullptr;
+        ga.N[k] = r.N;
+        ga.w[k] = r.w;
+    }
+    ga.gsum = gs.gsum;
+    ga.nguides = gs.count;
+    ga.streams = streams;
+    return 0;
+}
+// per step, ahead of the head: the guides' weighted logit sum on their states `cur`
+int guides_logits(lstm_hip_t *h, const char *what, const Guides &gs, GuideLogitsArgs &ga, int cur, long long t) {
+    for (int k = 0; k < gs.count; k++) {
+        ga.H[k] = gs.r[k].H + cur * gs.r[k].n;
+        ga.C[k] = gs.r[k].Cs + cur * gs.r[k].n;
+    }
+    hipError_t refused = hipSuccess;
+    RUN(K_GUIDE_LOGITS, refused = guide_logits(ga, t, h->st));
+    if (refused != hipSuccess) return head_refused(what, "guide_logits", refused);
+    return 0;
+}
+// per step, behind the main model's: every guide from its state `cur` to the other one, on the same inputs
+int guides_step(lstm_hip_t *h, const Guides &gs, int cur, const int32_t *xi, int streams) {
+    for (int k = 0; k < gs.count; k++) {
+        const Guides::One &r = gs.r[k];
+        if (int rc = step_columns(h, r.m, r.N, r.fast, r.Ufwd, r.H + cur * r.n, r.Cs + cur * r.n, r.H + (cur ^ 1) * r.n,
+                                  r.Cs + (cur ^ 1) * r.n, r.G, xi, streams))
+            return rc;
+    }
+    return 0;
+}
+// behind the loop: the guides' end states home
+int guides_finish(lstm_hip_t *h, const Guides &gs, const lstm_hip_guidance *gd, int streams) {
+    for (int k = 0; k < gs.count; k++) {
+        const Guides::One &r = gs.r[k];
+        if (int rc = download_states(h, r.N, r.N_log, gd->guides[k].h_out, gd->guides[k].c_out, r.ho, r.ho ? r.ho + r.n : nullptr,
+                                     r.stage, streams))
+            return rc;
+    }
+    return 0;
 }
 
 } // namespace
@@ -2323,12 +2460,28 @@ int lstm_hip_generate_accepting(lstm_hip_t *h, int32_t streams, const uint8_t *p
 // Logit processors: a bias, min-p or the n-gram rule selects gen_head's PROCESS instantiation
 // (a.process set).  The block is checked here before anything is launched; the bias and each stream's history ++ prompt (the
 // text the n-gram rule scans, with the drawn bytes behind it) are the last pieces of the scratch layout: with lp NULL or
-// everything off every offset, upload and launch is lstm_hip_generate_accepting's.
+// everything off every offset, upload and launch is lstm_hip_generate_accepting's.  (The body is lstm_hip_generate_guided's,
+// below: this function is its caller with gd = NULL.)
 int lstm_hip_generate_processed(lstm_hip_t *h, int32_t streams, const uint8_t *prompts, const uint64_t *prompt_off,
                                 const float *h0, const float *c0, const lstm_hip_sampling *opt, const double *u, int32_t count,
                                 uint8_t *out, double *bits, float *h_out, float *c_out, int32_t *out_len, uint16_t *kept,
                                 const lstm_hip_beam_constraint *bc, const int32_t *start_state, int32_t *end_state,
                                 const lstm_hip_logit_processors *lp) {
+    return lstm_hip_generate_guided(h, streams, prompts, prompt_off, h0, c0, opt, u, count, out, bits, h_out, c_out, out_len, kept, bc,
+                                    start_state, end_state, lp, nullptr);
+}
+
+// Guides: other models, fed the same bytes from states of their own, whose logits are mixed into the
+// main model's ahead of the processors.  Per step one guide_logits launch ahead of the head (all guides: their weighted logit
+// sum, and their end states where a stream has had its last input) and one k_fwd_step per guide behind the main model's; the
+// head's PROCESS instantiation (a.gsum set) mixes.  The block is checked here before anything is launched; the guides' images,
+// states and the sum are the last pieces of the scratch layout: with gd NULL every offset, upload and launch is
+// lstm_hip_generate_processed's.
+int lstm_hip_generate_guided(lstm_hip_t *h, int32_t streams, const uint8_t *prompts, const uint64_t *prompt_off, const float *h0,
+                             const float *c0, const lstm_hip_sampling *opt, const double *u, int32_t count, uint8_t *out,
+                             double *bits, float *h_out, float *c_out, int32_t *out_len, uint16_t *kept,
+                             const lstm_hip_beam_constraint *bc, const int32_t *start_state, int32_t *end_state,
+                             const lstm_hip_logit_processors *lp, const lstm_hip_guidance *gd) {
     CHECK(h);
     if (!opt) return fail(LSTM_HIP_EINVAL, "generate: null sampling options");
     if (opt->size != sizeof(lstm_hip_sampling))
@@ -2392,7 +2545,7 @@ int lstm_hip_generate_processed(lstm_hip_t *h, int32_t streams, const uint8_t *p
         }
     }
     const bool lp_bias = lp && lp->bias, lp_min_p = lp && lp->min_p > 0.0, lp_ngram = lp && lp->no_repeat > 0;
-    const bool process = lp_bias || lp_min_p || lp_ngram; // gen_head's PROCESS instantiation
+    const bool processors = lp_bias || lp_min_p || lp_ngram; // gen_head's PROCESS instantiation (as guides: `process` below)
     // the constraint: the table is checked, then every stream's state walks its prompt
     std::vector<int32_t> cstate; // [streams] the state after each prompt
     std::vector<uint16_t> ccount; // [states] allowed bytes
@@ -2411,6 +2564,10 @@ int lstm_hip_generate_processed(lstm_hip_t *h, int32_t streams, const uint8_t *p
     }
     if (accept) // (with count 0 this asks that every stream stands in an accepting state)
         if (int rc = deadline_rows("generate", con, accept, opt->stop_byte, count, cstate, frows)) return rc;
+    Guides gs; // (a guided draw is a processed draw)
+    if (gd)
+        if (int rc = check_guidance("generate", h, gd, gs)) return rc;
+    const bool process = processors || gs.count > 0;
     const uint64_t total = prompt_off ? prompt_off[streams] : 0;
     const size_t n = (size_t)N * streams, nl = (size_t)h->N_log * streams, nd = (size_t)count * streams;
     const bool keep = h_out || c_out;
@@ -2434,6 +2591,7 @@ int lstm_hip_generate_processed(lstm_hip_t *h, int32_t streams, const uint8_t *p
     mem.piece(d_tab, 256 * (size_t)Q, con != nullptr).piece(d_cnt, Q, con != nullptr).piece(d_q, streams, con != nullptr);
     mem.piece(d_acc, Q, accept != nullptr).piece(d_F, (size_t)count * fwords, accept != nullptr);
     mem.piece(d_bias, 256, lp_bias).piece(d_ptoff, (size_t)streams + 1, lp_ngram).piece(d_ptext, ptext.size(), !ptext.empty());
+    guide_pieces(mem, gs, gd, streams);
     if (int rc = mem.commit(h)) return rc;
 
     // start state (padding rows zero), inputs
@@ -2461,6 +2619,11 @@ int lstm_hip_generate_processed(lstm_hip_t *h, int32_t streams, const uint8_t *p
     }
     const Model m = model_of(h);
     RUN(K_PACK_U, pack_U(m.U, Ufwd, nullptr, N, h->st));
+    GuideLogitsArgs ga{};
+    if (int rc = guides_begin(h, gs, gd, streams, ga)) return rc;
+    ga.off = d_off;
+    ga.end = d_end;
+    ga.count = count;
 
     GenHeadArgs a{};
     a.Why = m.Why;
@@ -2499,17 +2662,22 @@ int lstm_hip_generate_processed(lstm_hip_t *h, int32_t streams, const uint8_t *p
     a.no_repeat = lp ? lp->no_repeat : 0;
     a.ptext = d_ptext;
     a.ptoff = d_ptoff;
+    a.gsum = gs.gsum;
+    a.wmain = gs.wmain;
     const bool stable = (h->cfg.flags & LSTM_HIP_STABLE_SOFTMAX) != 0;
     const long long steps = (long long)max_len + count; // inputs of the longest stream
     int cur = 0;
     for (long long t = 0;; t++) {
         a.H = H + cur * n;
         a.C = Cs + cur * n;
+        if (gs.count)
+            if (int rc = guides_logits(h, "generate", gs, ga, cur, t)) return rc;
         hipError_t refused = hipSuccess; // (only the FILTER instantiations ever report one)
         RUN(K_GEN_HEAD, refused = gen_head(a, t, stable, h->st));
         if (refused != hipSuccess) return head_refused("generate", "gen_head", refused);
         if (t == steps) break;
         if (int rc = step_columns(h, m, Ufwd, a.H, a.C, H + (cur ^ 1) * n, Cs + (cur ^ 1) * n, G, xi, streams)) return rc;
+        if (int rc = guides_step(h, gs, cur, xi, streams)) return rc;
         cur ^= 1;
     }
 
@@ -2522,6 +2690,7 @@ int lstm_hip_generate_processed(lstm_hip_t *h, int32_t streams, const uint8_t *p
     if (kept && nd) HIP_TRY(hipMemcpyAsync(kept, d_kept, sizeof(uint16_t) * nd, hipMemcpyDeviceToHost, h->st));
     if (end_state) HIP_TRY(hipMemcpyAsync(end_state, d_q, sizeof(int32_t) * streams, hipMemcpyDeviceToHost, h->st));
     if (int rc = download_states(h, h_out, c_out, a.h_out, a.c_out, stage, streams)) return rc;
+    if (int rc = guides_finish(h, gs, gd, streams)) return rc;
     HIP_TRY(hipStreamSynchronize(h->st));
     return 0;
 }
@@ -2710,6 +2879,15 @@ int lstm_hip_beam_search_constrained(lstm_hip_t *h, int32_t streams, const uint8
 int lstm_hip_score(lstm_hip_t *h, int32_t streams, const uint8_t *text, const uint64_t *text_off, const float *h0, const float *c0,
                    const lstm_hip_scoring *opt, const int32_t *start_state, const lstm_hip_scores *out, float *h_out,
                    float *c_out) {
+    return lstm_hip_score_guided(h, streams, text, text_off, h0, c0, opt, start_state, out, h_out, c_out, nullptr);
+}
+
+// Guides, as in lstm_hip_generate_guided: per step one guide_logits launch ahead of score_head (a.gsum
+// set: every scored byte is scored under the mixed logits, the constraint mask behind the mix) and one k_fwd_step per guide.  The
+// guides' pieces are the last of the scratch layout: with gd NULL every offset, upload and launch is lstm_hip_score's.
+int lstm_hip_score_guided(lstm_hip_t *h, int32_t streams, const uint8_t *text, const uint64_t *text_off, const float *h0,
+                          const float *c0, const lstm_hip_scoring *opt, const int32_t *start_state, const lstm_hip_scores *out,
+                          float *h_out, float *c_out, const lstm_hip_guidance *gd) {
     CHECK(h);
     if (!opt) return fail(LSTM_HIP_EINVAL, "score: null options");
     if (opt->size != sizeof(lstm_hip_scoring))
@@ -2740,6 +2918,9 @@ int lstm_hip_score(lstm_hip_t *h, int32_t streams, const uint8_t *text, const ui
         qpos.resize(total);
         if (int rc = walk_constraint("score", "byte", con, streams, text, text_off, cstate, qpos.data())) return rc;
     }
+    Guides gs;
+    if (gd)
+        if (int rc = check_guidance("score", h, gd, gs)) return rc;
     const size_t n = (size_t)N * streams, nl = (size_t)h->N_log * streams, tot = (size_t)total;
     const bool keep = h_out || c_out;
 
@@ -2758,6 +2939,7 @@ int lstm_hip_score(lstm_hip_t *h, int32_t streams, const uint8_t *text, const ui
     mem.piece(d_sur, tot, o.surprisal && tot).piece(d_ent, tot, o.entropy && tot).piece(d_rank, tot, o.rank && tot);
     mem.piece(d_tby, tot * top_n, o.top_byte && tot).piece(d_tbi, tot * top_n, o.top_bits && tot);
     mem.piece(d_tab, 256 * (size_t)Q, con != nullptr).piece(d_q, tot, con != nullptr);
+    guide_pieces(mem, gs, gd, streams);
     if (int rc = mem.commit(h)) return rc;
 
     // start state (padding rows zero), inputs, zeroed outputs (the entries of unscored bytes stay zero)
@@ -2776,6 +2958,11 @@ int lstm_hip_score(lstm_hip_t *h, int32_t streams, const uint8_t *text, const ui
     }
     const Model m = model_of(h);
     RUN(K_PACK_U, pack_U(m.U, Ufwd, nullptr, N, h->st));
+    GuideLogitsArgs ga{};
+    if (int rc = guides_begin(h, gs, gd, streams, ga)) return rc;
+    ga.off = d_off;
+    ga.scorer = 1;
+    ga.first = opt->first;
 
     ScoreHeadArgs a{};
     a.Why = m.Why;
@@ -2797,16 +2984,21 @@ int lstm_hip_score(lstm_hip_t *h, int32_t streams, const uint8_t *text, const ui
     a.streams = streams;
     a.first = opt->first;
     a.top_n = top_n;
+    a.gsum = gs.gsum;
+    a.wmain = gs.wmain;
     const bool stable = (h->cfg.flags & LSTM_HIP_STABLE_SOFTMAX) != 0;
     int cur = 0;
     for (uint64_t t = 0;; t++) {
         a.H = H + cur * n;
         a.C = Cs + cur * n;
+        if (gs.count)
+            if (int rc = guides_logits(h, "score", gs, ga, cur, (long long)t)) return rc;
         hipError_t refused = hipSuccess;
         RUN(K_SCORE_HEAD, refused = score_head(a, (long long)t, stable, h->st));
         if (refused != hipSuccess) return head_refused("score", "score_head", refused);
         if (t == max_len) break;
         if (int rc = step_columns(h, m, Ufwd, a.H, a.C, H + (cur ^ 1) * n, Cs + (cur ^ 1) * n, G, xi, streams)) return rc;
+        if (int rc = guides_step(h, gs, cur, xi, streams)) return rc;
         cur ^= 1;
     }
 
@@ -2817,6 +3009,7 @@ int lstm_hip_score(lstm_hip_t *h, int32_t streams, const uint8_t *text, const ui
     if (d_tbi) HIP_TRY(hipMemcpyAsync(o.top_bits, d_tbi, sizeof(float) * tot * top_n, hipMemcpyDeviceToHost, h->st));
     if (o.bits) HIP_TRY(hipMemcpyAsync(o.bits, d_bits, sizeof(double) * streams, hipMemcpyDeviceToHost, h->st));
     if (int rc = download_states(h, h_out, c_out, a.h_out, a.c_out, stage, streams)) return rc;
+    if (int rc = guides_finish(h, gs, gd, streams)) return rc;
     HIP_TRY(hipStreamSynchronize(h->st));
     if (o.end_state) std::copy(cstate.begin(), cstate.end(), o.end_state);
     return 0;

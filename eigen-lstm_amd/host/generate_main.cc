@@ -5,6 +5,7 @@
 //   lstm_generate --load PREFIX [--score FILE ...] [--score-bytes FILE [--top N]] [--count C --streams K --prime TEXT|--prime-file F
 //                 --temperature T --top-k K --top-p P --stop-byte B --seed S --utf8 --allow SPEC --ban SPEC --regex PATTERN
 //                 --logit-bias BIAS --min-p P --no-repeat-ngram N
+//                 [--guide PREFIX --guide-weight B]... [--main-weight A] | --guidance G [--negative-prime TEXT]
 //                 | --beams W --nbest K --length-alpha A [--constrain-search --utf8 --allow SPEC --ban SPEC --regex PATTERN]]
 //                 [--score-streams K [--score-warmup W]] [--fast-math] [--stable-softmax] [--device D]
 //   lstm_generate --load PREFIX --embed FILE [--embed-delim B] [--pool last|mean|max|concat] [--embed-cell] [--embed-streams K]
@@ -59,6 +60,16 @@
 // sequence the sample, prompt included, already holds -- it ends the loops of --temperature 0 -- and gives way where the table
 // would otherwise have no byte left.  The scan behind N is linear in the sample's length at every draw.  All three are options of
 // drawing and are refused with --beams: beam search, the scorer and the coders take no processors.
+// --guide PREFIX --guide-weight B loads a second checkpoint, of any width, as a guide (lstm_hip_generate_guided /
+// lstm_hip_score_guided): it is fed the bytes the loaded model is fed, from a zero state of its own, and every drawn byte's
+// logits become A * z + the sum of B * the guide's logits, ahead of the processors above; A is --main-weight (default 1).  The
+// pair is repeatable up to four times, each --guide with the --guide-weight that follows it.  1.5 and -0.5 with a smaller model
+// is contrastive decoding; weights that sum to 1 are the geometric mean of an ensemble.  With --score F or --score-bytes F
+// (and no --count) the files are scored under the mix instead; it does not go with --score-streams.
+// --guidance G --negative-prime TEXT uses the loaded model as its own guide, with the weights (1 + G, -G): the guide is primed
+// with TEXT (empty by default) instead of --prime.  Both primings are calls that draw nothing and hand their end state over, and
+// the drawing call then gets no prompt (a table's state and the n-gram rule's history are handed over with it).  It goes with
+// --count only and not with --guide.  --beams refuses all of these: beam search takes no guides.
 // --embed FILE writes what the model computed about every record of FILE (lstm_hip_embed_texts): FILE is cut after every
 // delimiter byte (--embed-delim B, 0..255, default 10; the delimiter stays the last byte of its record and a last record may
 // lack it, as lstm --records cuts), all records are embedded in one call from h = c = 0, --embed-streams K of them side by side
@@ -88,6 +99,7 @@ const char *const kUsage =
     "                     --temperature T --top-k K --top-p P --stop-byte B --seed S\n"
     "                     --utf8 --allow SPEC --ban SPEC --regex PATTERN\n"
     "                     --logit-bias BIAS --min-p P --no-repeat-ngram N\n"
+    "                     [--guide PREFIX --guide-weight B]... [--main-weight A] | --guidance G [--negative-prime TEXT]\n"
     "                     | --beams W --nbest K --length-alpha A\n"
     "                       [--constrain-search --utf8 --allow SPEC --ban SPEC --regex PATTERN]]\n"
     "                     [--score-streams K [--score-warmup W]] [--fast-math] [--stable-softmax] [--device D]\n"
@@ -116,6 +128,13 @@ const char *const kUsage =
     "  --min-p P      draw among the bytes at least P times as likely as the most likely one (0 < P <= 1; 0: off)\n"
     "  --no-repeat-ngram N  never draw a byte that would complete an N-byte sequence the sample (prompt included) already\n"
     "                 holds (1..64; 0: off); a table (--utf8, --allow, --ban, --regex) wins where the two leave no byte\n"
+    "  --guide PREFIX  load a second checkpoint (any width) as a guide, fed the same bytes: the logits of every drawn byte\n"
+    "                 become A * z + the sum of B * the guide's; repeatable up to four times, each with its --guide-weight.\n"
+    "                 With --score / --score-bytes (and no --count) the files are scored under the mix\n"
+    "  --guide-weight B  the weight of the --guide before it (finite; negative: contrast against that model)\n"
+    "  --main-weight A  the weight of the loaded model's own logits (finite, default 1); needs --guide\n"
+    "  --guidance G   the loaded model as its own guide with the weights (1 + G, -G), primed with --negative-prime\n"
+    "  --negative-prime TEXT  what the guide of --guidance reads in place of --prime (default: nothing)\n"
     "  --beams W      beam search with W hypotheses per stream (1..32) instead of drawing; W x --streams <= 4096;\n"
     "  --constrain-search  with --beams: let --utf8 / --allow / --ban constrain the search to the continuations they\n"
     "                 accept (without it they are refused with --beams); hypotheses that do not exist are not printed\n"
@@ -208,7 +227,22 @@ void parse_bias(const std::string &opt, const std::string &v, float bias[256]) {
     }
 }
 
+// a finite number of either sign: "", "1x", inf and nan are usage errors
+double parse_finite(const std::string &opt, const std::string &v) {
+    char *end = nullptr;
+    const double x = strtod(v.c_str(), &end);
+    if (v.empty() || *end != '\0' || !std::isfinite(x)) usage(opt + " needs a finite number, got '" + v + "'");
+    return x;
+}
+
 struct Options {
+    std::vector<std::string> guides;      // --guide PREFIX, up to LSTM_HIP_MAX_GUIDES of them
+    std::vector<double> guide_weights;    // --guide-weight B, one per --guide
+    double main_weight = 1.0;             // --main-weight A
+    bool has_main_weight = false;
+    double guidance = 0.0;                // --guidance G
+    bool has_guidance = false, has_negative_prime = false;
+    std::string negative_prime;           // --negative-prime TEXT
     bool has_bias = false;   // --logit-bias
     float bias[256] = {};
     double min_p = 0.0;      // --min-p
@@ -310,6 +344,25 @@ Options parse(int argc, char **argv) {
             o.no_repeat = parse_int(a, val(), 0, 64);
             o.sampling_opts.push_back(a);
             o.draw_opts.push_back(a);
+        } else if (a == "--guide") {
+            if (o.guides.size() != o.guide_weights.size()) usage("--guide " + o.guides.back() + " needs a --guide-weight before the next --guide");
+            if (o.guides.size() == LSTM_HIP_MAX_GUIDES) usage("--guide may be given at most " + std::to_string(LSTM_HIP_MAX_GUIDES) + " times");
+            o.guides.push_back(val());
+            o.draw_opts.push_back(a);
+        } else if (a == "--guide-weight") {
+            if (o.guides.size() != o.guide_weights.size() + 1) usage("--guide-weight follows the --guide it belongs to");
+            o.guide_weights.push_back(parse_finite(a, val()));
+        } else if (a == "--main-weight") {
+            o.main_weight = parse_finite(a, val());
+            o.has_main_weight = true;
+        } else if (a == "--guidance") {
+            o.guidance = parse_finite(a, val());
+            o.has_guidance = true;
+            o.sampling_opts.push_back(a);
+            o.draw_opts.push_back(a);
+        } else if (a == "--negative-prime") {
+            o.negative_prime = val();
+            o.has_negative_prime = true;
         } else if (a == "--seed") {
             o.seed = (uint32_t)parse_int(a, val(), 0, 0xFFFFFFFFL);
             o.sampling_opts.push_back(a);
@@ -362,6 +415,16 @@ Options parse(int argc, char **argv) {
     }
     if (o.score.empty() && o.count < 0 && o.score_bytes.empty() && o.embed.empty())
         usage("nothing to do: give --score, --score-bytes, --embed and/or --count");
+    if (o.guides.size() != o.guide_weights.size()) usage("--guide " + o.guides.back() + " needs a --guide-weight");
+    if (o.has_main_weight && o.guides.empty()) usage("--main-weight needs --guide");
+    if (o.has_negative_prime && !o.has_guidance) usage("--negative-prime needs --guidance");
+    if (o.has_guidance && !o.guides.empty()) usage("--guidance does not go with --guide: it makes the loaded model its own guide");
+    if (o.has_guidance && !o.score.empty()) usage("--guidance guides the drawing: it does not go with --score");
+    if (!o.guides.empty()) {
+        if (!o.embed.empty()) usage("--guide does not go with --embed");
+        if (o.score_streams > 0) usage("--guide does not go with --score-streams: that path takes no guides");
+        if (o.count >= 0 && !o.score.empty()) usage("--guide with --count guides the drawing: score the files in a run of their own");
+    }
     if (o.top >= 0 && o.score_bytes.empty()) usage("--top needs --score-bytes");
     if (o.score_streams > 0 && o.score.empty()) usage("--score-streams needs --score");
     if (o.score_warmup >= 0 && o.score_streams == 0) usage("--score-warmup needs --score-streams");
@@ -451,6 +514,53 @@ int main(int argc, char **argv) {
     CK(lstm_hip_create(&cfg, &h));
     CK(lstm_hip_set_params(h, 0, P.data()));
 
+    // the guides: a handle per --guide checkpoint, each of its own width; --guidance takes the loaded model itself
+    std::vector<lstm_hip_t *> guide_handles;
+    std::vector<lstm_hip_guide> guides;
+    for (size_t k = 0; k < o.guides.size(); k++) {
+        const int Ng = checkpoint::hidden_size(o.guides[k], M, &err);
+        if (Ng == 0) die(err);
+        std::vector<float> Pg(lstm_hip_param_count(Ng, M));
+        const int rg = checkpoint::load_params(o.guides[k], Pg, Ng, M, &err);
+        if (rg == 0) die("missing a file of " + o.guides[k] + "_{W,U,Why,b,by}.txt");
+        if (rg < 0) die(err);
+        lstm_hip_config gcfg{Ng, M, 2, 1, (int32_t)o.device, o.flags | LSTM_HIP_PAD_HIDDEN};
+        lstm_hip_t *g = nullptr;
+        CK(lstm_hip_create(&gcfg, &g));
+        CK(lstm_hip_set_params(g, 0, Pg.data()));
+        guide_handles.push_back(g);
+        guides.push_back(lstm_hip_guide{g, o.guide_weights[k], nullptr, nullptr, nullptr, nullptr});
+    }
+    if (o.has_guidance) guides.push_back(lstm_hip_guide{h, -o.guidance, nullptr, nullptr, nullptr, nullptr});
+    const lstm_hip_guidance gd{(uint32_t)sizeof(lstm_hip_guidance), o.has_guidance ? 1.0 + o.guidance : o.main_weight,
+                               (int32_t)guides.size(), guides.data()};
+    const bool guided = !guides.empty();
+
+    if (!texts.empty() && guided) { // every file as one stream under the mix: lstm_hip_score_guided's bits (byte 0 an input only)
+        double sum_bits = 0.0, sum_chars = 0.0;
+        for (size_t f0 = 0; f0 < texts.size(); f0 += 4096) {
+            const size_t k = std::min<size_t>(4096, texts.size() - f0);
+            std::vector<uint64_t> off(k + 1, 0);
+            std::vector<uint8_t> all;
+            for (size_t s = 0; s < k; s++) {
+                all.insert(all.end(), texts[f0 + s].begin(), texts[f0 + s].end());
+                off[s + 1] = all.size();
+            }
+            std::vector<double> bits(k);
+            const lstm_hip_scoring opt{(uint32_t)sizeof(lstm_hip_scoring), 0, 0, nullptr};
+            lstm_hip_scores out{};
+            out.size = (uint32_t)sizeof(lstm_hip_scores);
+            out.bits = bits.data();
+            CK(lstm_hip_score_guided(h, (int32_t)k, all.data(), off.data(), nullptr, nullptr, &opt, nullptr, &out, nullptr, nullptr, &gd));
+            for (size_t s = 0; s < k; s++) {
+                const size_t n = texts[f0 + s].size();
+                printf("%s: %.5f bits/char (%zu bytes)\n", o.score[f0 + s].c_str(), bits[s] / (double)(n - 1), n);
+                sum_bits += bits[s];
+                sum_chars += (double)(n - 1);
+            }
+        }
+        printf("total: %.5f bits/char (%.0f bytes scored in %zu files)\n", sum_bits / sum_chars, sum_chars, texts.size());
+    } else
     if (!texts.empty()) { // one stream per file, in chunks of at most 4096 files
         double sum_bits = 0.0, sum_chars = 0.0;
         if (o.score_streams > 0) { // every file in K pieces, all of them in one call
@@ -500,7 +610,7 @@ int main(int argc, char **argv) {
         const lstm_hip_scoring opt{(uint32_t)sizeof(lstm_hip_scoring), constrained ? 1 : 0, (int32_t)top, constrained ? &con : nullptr};
         const lstm_hip_scores out{(uint32_t)sizeof(lstm_hip_scores), surprisal.data(), entropy.data(), rank.data(),
                                   top ? top_byte.data() : nullptr, top ? top_bits.data() : nullptr, &bits, nullptr};
-        CK(lstm_hip_score(h, 1, text.data(), off, nullptr, nullptr, &opt, nullptr, &out, nullptr, nullptr));
+        CK(lstm_hip_score_guided(h, 1, text.data(), off, nullptr, nullptr, &opt, nullptr, &out, nullptr, nullptr, guided ? &gd : nullptr));
         for (size_t j = 0; j < n; j++) {
             printf("%zu\t%02x\t%.5f\t%.5f\t%d", j, (unsigned)text[j], surprisal[j], entropy[j], (int)rank[j]);
             for (size_t r = 0; r < top; r++) printf("\t%02x\t%.5f", (unsigned)top_byte[j * top + r], top_bits[j * top + r]);
@@ -607,7 +717,55 @@ int main(int argc, char **argv) {
         const lstm_hip_sampling opt{(uint32_t)sizeof(lstm_hip_sampling), o.temperature, (int32_t)o.top_k, o.top_p, (int32_t)o.stop_byte};
         std::vector<int32_t> out_len(K);
         std::vector<int32_t> end_state(K, 0);
-        if (o.has_bias || o.min_p > 0.0 || o.no_repeat > 0) { // logit processors, under whatever table the options made
+        if (guided) { // the mix, ahead of the processors, under whatever table the options made
+            const lstm_hip_constraint con{(uint32_t)sizeof(lstm_hip_constraint), o.states, o.table.data()};
+            const lstm_hip_beam_constraint bc{(uint32_t)sizeof(lstm_hip_beam_constraint), &con, o.has_regex ? o.accept.data() : nullptr};
+            const bool tab = !o.table.empty();
+            lstm_hip_logit_processors lp{(uint32_t)sizeof(lstm_hip_logit_processors), o.has_bias ? o.bias : nullptr, o.min_p,
+                                         (int32_t)o.no_repeat, nullptr, nullptr};
+            if (!o.has_guidance)
+                CK(lstm_hip_generate_guided(h, K, prompts.data(), off.data(), nullptr, nullptr, &opt, u.empty() ? nullptr : u.data(), C,
+                                            out.data(), nullptr, nullptr, nullptr, out_len.data(), nullptr, tab ? &bc : nullptr, nullptr,
+                                            tab ? end_state.data() : nullptr, &lp, &gd));
+            else { // both primings are calls that draw nothing; their end states start the drawing call, which gets no prompt
+                const size_t n = (size_t)K * N;
+                std::vector<float> hm(n), cm(n), hn, cn;
+                CK(lstm_hip_generate(h, K, prompts.data(), off.data(), nullptr, nullptr, 1.0, nullptr, 0, nullptr, nullptr, hm.data(),
+                                     cm.data()));
+                if (!o.negative_prime.empty()) {
+                    std::vector<uint64_t> noff(K + 1);
+                    std::vector<uint8_t> neg;
+                    for (int s = 0; s < K; s++) {
+                        neg.insert(neg.end(), o.negative_prime.begin(), o.negative_prime.end());
+                        noff[s + 1] = neg.size();
+                    }
+                    hn.resize(n), cn.resize(n);
+                    CK(lstm_hip_generate(h, K, neg.data(), noff.data(), nullptr, nullptr, 1.0, nullptr, 0, nullptr, nullptr, hn.data(),
+                                         cn.data()));
+                }
+                lstm_hip_guide self = guides[0];
+                self.h0 = hn.empty() ? nullptr : hn.data();
+                self.c0 = cn.empty() ? nullptr : cn.data();
+                const lstm_hip_guidance own{(uint32_t)sizeof(lstm_hip_guidance), gd.main_weight, 1, &self};
+                std::vector<int32_t> start(K, 0); // the table's state behind the prime, which the drawing call no longer walks
+                if (tab) {
+                    int32_t q = 0;
+                    for (size_t i = 0; i < prime.size(); i++) {
+                        const uint16_t v = o.table[(size_t)q * 256 + prime[i]];
+                        if (v == 0xFFFF) die("--prime: byte " + std::to_string(i) + " is forbidden by the table the options made");
+                        q = v;
+                    }
+                    std::fill(start.begin(), start.end(), q);
+                }
+                if (o.no_repeat > 0) { // the rule still sees the prime: as the history
+                    lp.history = prompts.data();
+                    lp.history_off = off.data();
+                }
+                CK(lstm_hip_generate_guided(h, K, nullptr, nullptr, hm.data(), cm.data(), &opt, u.empty() ? nullptr : u.data(), C,
+                                            out.data(), nullptr, nullptr, nullptr, out_len.data(), nullptr, tab ? &bc : nullptr,
+                                            tab ? start.data() : nullptr, tab ? end_state.data() : nullptr, &lp, &own));
+            }
+        } else if (o.has_bias || o.min_p > 0.0 || o.no_repeat > 0) { // logit processors, under whatever table the options made
             const lstm_hip_constraint con{(uint32_t)sizeof(lstm_hip_constraint), o.states, o.table.data()};
             const lstm_hip_beam_constraint bc{(uint32_t)sizeof(lstm_hip_beam_constraint), &con, o.has_regex ? o.accept.data() : nullptr};
             const lstm_hip_logit_processors lp{(uint32_t)sizeof(lstm_hip_logit_processors), o.has_bias ? o.bias : nullptr, o.min_p,
@@ -648,6 +806,7 @@ int main(int argc, char **argv) {
             fputc('\n', stdout);
         }
     }
+    for (lstm_hip_t *g : guide_handles) CK(lstm_hip_destroy(g));
     CK(lstm_hip_destroy(h));
     return 0;
 }

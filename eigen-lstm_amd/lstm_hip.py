@@ -62,6 +62,15 @@ class _LogitProcessors(C.Structure):  # lstm_hip_logit_processors
                 ("history", C.POINTER(C.c_uint8)), ("history_off", C.POINTER(C.c_uint64))]
 
 
+class _Guide(C.Structure):  # lstm_hip_guide
+    _fields_ = [("model", C.c_void_p), ("weight", C.c_double), ("h0", C.POINTER(C.c_float)), ("c0", C.POINTER(C.c_float)),
+                ("h_out", C.POINTER(C.c_float)), ("c_out", C.POINTER(C.c_float))]
+
+
+class _Guidance(C.Structure):  # lstm_hip_guidance
+    _fields_ = [("size", C.c_uint32), ("main_weight", C.c_double), ("nguides", C.c_int32), ("guides", C.POINTER(_Guide))]
+
+
 class _Scoring(C.Structure):  # lstm_hip_scoring
     _fields_ = [("size", C.c_uint32), ("first", C.c_int32), ("top_n", C.c_int32), ("con", C.POINTER(_Constraint))]
 
@@ -121,6 +130,7 @@ SYMBOLS = [
     "lstm_hip_set_grad_accumulator",
     "lstm_hip_generate_processed",
     "lstm_hip_embed_texts",
+    "lstm_hip_generate_guided", "lstm_hip_score_guided",
 ]
 
 
@@ -357,6 +367,24 @@ def _f32(a):
 
 def _ptr(a, t=C.c_float):
     return a.ctypes.data_as(C.POINTER(t))
+
+
+def _guidance(guides, main_weight, streams):
+    """the lstm_hip_guidance block of guides = [(model, weight[, h0[, c0]]), ...]: (block, the guides' h_out arrays, their
+    c_out arrays, what has to stay alive until the call returns)"""
+    items = [tuple(g) + (None,) * (4 - len(tuple(g))) for g in guides]
+    arr = (_Guide * max(len(items), 1))()
+    gh, gc, alive = [], [], [arr]
+    for k, (model, weight, h0, c0) in enumerate(items):
+        n = model.N
+        hh = None if h0 is None else _f32(h0).reshape(streams, n)
+        cc = None if c0 is None else _f32(c0).reshape(streams, n)
+        gh.append(np.empty((streams, n), np.float32))
+        gc.append(np.empty((streams, n), np.float32))
+        alive += [hh, cc]
+        arr[k] = _Guide(model._h.value, float(weight), _ptr(hh) if hh is not None else None, _ptr(cc) if cc is not None else None,
+                        _ptr(gh[k]), _ptr(gc[k]))
+    return _Guidance(C.sizeof(_Guidance), float(main_weight), len(items), arr), gh, gc, alive
 
 
 def device_info(device=0):
@@ -822,7 +850,7 @@ class Lstm:
 
     def generate(self, prompts=None, count=0, u=None, temperature=1.0, h0=None, c0=None, streams=None, score=False,
                  top_k=0, top_p=1.0, stop_byte=None, info=False, constraint=None, start_state=None, accept=None,
-                 logit_bias=None, min_p=0.0, no_repeat_ngram=0, history=None):
+                 logit_bias=None, min_p=0.0, no_repeat_ngram=0, history=None, guides=None, main_weight=1.0):
         """lstm_hip_generate: `streams` independent streams, each fed its prompt (bytes or a uint8 array) and then `count`
         drawn bytes.  u: draws [count, streams] (may be None only at temperature 0); h0, c0: [streams, N] or None (zeros).
         Returns (out [count, streams] uint8, bits [streams] float64 -- the prompts' summed -log2 p, or None unless
@@ -843,7 +871,12 @@ class Lstm:
         terms below min_p times the largest) and no_repeat_ngram (n in 1..64: no byte is drawn that would complete an n-gram
         the stream's text already holds; history: per stream the bytes that precede its prompt for this rule only) are the
         logit processors of lstm_hip_generate_processed.  They go with every argument above; with all four at their
-        defaults the calls are those made without them."""
+        defaults the calls are those made without them.
+        guides: [(model, weight, h0, c0), ...] (lstm_hip_generate_guided; 1 to 4 entries, h0 / c0 [streams, model.N] or None
+        or left out: zeros; model may be this object).  Every guide is fed this call's prompts and drawn bytes from its own
+        state, and a drawn byte's logits become main_weight * z + the sum of weight * the guide's logits, ahead of every
+        processor.  With info=True the guides' end states are info["guide_h"], info["guide_c"]: one [streams, model.N] array
+        per guide.  Without guides the calls are those made without the argument."""
         if streams is None:
             streams = len(prompts) if prompts is not None else (np.asarray(h0).shape[0] if h0 is not None else
                                                                 (np.asarray(u).reshape(count, -1).shape[1] if u is not None and count > 0 else 1))
@@ -873,9 +906,12 @@ class Lstm:
             raise LstmHipError("generate: start_state given without a constraint")
         if constraint is None and accept is not None:
             raise LstmHipError("generate: accept given without a constraint")
-        if logit_bias is not None or min_p != 0.0 or no_repeat_ngram != 0 or history is not None:
+        if guides is None and main_weight != 1.0:
+            raise LstmHipError("generate: main_weight given without guides")
+        if logit_bias is not None or min_p != 0.0 or no_repeat_ngram != 0 or history is not None or guides is not None:
             return self._generate_processed(args, tail, streams, count, temperature, top_k, top_p, stop_byte, info, constraint,
-                                            start_state, accept, logit_bias, min_p, no_repeat_ngram, history, out, bits, h, c)
+                                            start_state, accept, logit_bias, min_p, no_repeat_ngram, history, out, bits, h, c,
+                                            guides, main_weight)
         if constraint is None and top_k == 0 and top_p == 1.0 and stop_byte is None and not info:
             _chk(self.lib.lstm_hip_generate(*args, C.c_double(temperature), *tail))
             return out, bits, h, c
@@ -905,8 +941,9 @@ class Lstm:
         return (out, bits, h, c, {"out_len": out_len, "kept": kept}) if info else (out, bits, h, c)
 
     def _generate_processed(self, args, tail, streams, count, temperature, top_k, top_p, stop_byte, info, constraint,
-                            start_state, accept, logit_bias, min_p, no_repeat_ngram, history, out, bits, h, c):
-        """generate() with a logit processor on: one lstm_hip_generate_processed call"""
+                            start_state, accept, logit_bias, min_p, no_repeat_ngram, history, out, bits, h, c, guides=None,
+                            main_weight=1.0):
+        """generate() with a logit processor on: one lstm_hip_generate_processed call (with guides: lstm_hip_generate_guided)"""
         opt = _Sampling(C.sizeof(_Sampling), float(temperature), int(top_k), float(top_p),
                         -1 if stop_byte is None else int(stop_byte))
         out_len = np.zeros(streams, np.int32)
@@ -934,13 +971,16 @@ class Lstm:
         lp = _LogitProcessors(C.sizeof(_LogitProcessors), _ptr(bias) if bias is not None else None, float(min_p),
                               int(no_repeat_ngram), _ptr(d_h, C.c_uint8) if d_h is not None else None,
                               _ptr(d_hoff, C.c_uint64) if d_hoff is not None else None)
-        _chk(self.lib.lstm_hip_generate_processed(
-            *args, C.byref(opt), *tail, _ptr(out_len, C.c_int32), _ptr(kept, C.c_uint16) if info else None,
-            C.byref(bc) if bc is not None else None, _ptr(q0, C.c_int32) if q0 is not None else None,
-            _ptr(q1, C.c_int32) if q1 is not None else None, C.byref(lp)))
+        call = self.lib.lstm_hip_generate_processed if guides is None else self.lib.lstm_hip_generate_guided
+        gd, gh, gc, _alive = (None, None, None, None) if guides is None else _guidance(guides, main_weight, streams)
+        _chk(call(*args, C.byref(opt), *tail, _ptr(out_len, C.c_int32), _ptr(kept, C.c_uint16) if info else None,
+                  C.byref(bc) if bc is not None else None, _ptr(q0, C.c_int32) if q0 is not None else None,
+                  _ptr(q1, C.c_int32) if q1 is not None else None, C.byref(lp), *(() if gd is None else (C.byref(gd),))))
         if not info:
             return out, bits, h, c
         extra = {"out_len": out_len, "kept": kept}
+        if gd is not None:
+            extra["guide_h"], extra["guide_c"] = gh, gc
         if q1 is not None:
             extra["end_state"] = q1
         return out, bits, h, c, extra
@@ -955,6 +995,20 @@ class Lstm:
         None.  constraint / start_state as in generate: forbidden bytes are masked out of the distribution every byte is
         scored under, and a text the table rejects is refused.  A long text scored in pieces, each later piece with
         first=True, h0 / c0 = the h / c and start_state = the end_state before it, gives the entries of the one call."""
+        return self._score(texts, h0, c0, first, top_n, constraint, start_state, None, 1.0)
+
+    def score_guided(self, texts, guides, main_weight=1.0, h0=None, c0=None, first=False, top_n=0, constraint=None,
+                     start_state=None):
+        """lstm_hip_score_guided: score() under a mix with other models.  guides / main_weight as in generate: every byte is
+        scored under main_weight * z + the sum of weight * the guide's logits, the constraint mask behind the mix; the dict
+        then also has "guide_h", "guide_c", one [streams, model.N] array per guide (to hand over with h / c when a text is
+        scored in pieces).  score() keeps the signature it had: it makes the call it made before guides existed."""
+        if guides is None:
+            raise LstmHipError("score: score_guided without guides")
+        return self._score(texts, h0, c0, first, top_n, constraint, start_state, guides, main_weight)
+
+    def _score(self, texts, h0, c0, first, top_n, constraint, start_state, guides, main_weight):
+        """score() and score_guided(): one lstm_hip_score / lstm_hip_score_guided call"""
         parts = _bytes_list(texts)
         streams, top_n = len(parts), int(top_n)
         data, off = _offsets(parts)
@@ -978,12 +1032,20 @@ class Lstm:
         opt = _Scoring(C.sizeof(_Scoring), int(bool(first)), top_n, C.pointer(con) if con is not None else None)
         out = _Scores(C.sizeof(_Scores), _ptr(sur), _ptr(ent), _ptr(rank, C.c_uint8), _ptr(tby, C.c_uint8) if top_n else None,
                       _ptr(tbi) if top_n else None, _ptr(bits, C.c_double), _ptr(q1, C.c_int32) if q1 is not None else None)
-        _chk(self.lib.lstm_hip_score(self._h, C.c_int32(streams), _ptr(data, C.c_uint8), _ptr(off, C.c_uint64),
-                                     _ptr(hh) if hh is not None else None, _ptr(cc) if cc is not None else None, C.byref(opt),
-                                     _ptr(q0, C.c_int32) if q0 is not None else None, C.byref(out), _ptr(h), _ptr(c)))
+        if guides is None and main_weight != 1.0:
+            raise LstmHipError("score: main_weight given without guides")
+        call = self.lib.lstm_hip_score if guides is None else self.lib.lstm_hip_score_guided
+        gd, gh, gc, _alive = (None, None, None, None) if guides is None else _guidance(guides, main_weight, streams)
+        _chk(call(self._h, C.c_int32(streams), _ptr(data, C.c_uint8), _ptr(off, C.c_uint64),
+                  _ptr(hh) if hh is not None else None, _ptr(cc) if cc is not None else None, C.byref(opt),
+                  _ptr(q0, C.c_int32) if q0 is not None else None, C.byref(out), _ptr(h), _ptr(c),
+                  *(() if gd is None else (C.byref(gd),))))
         cut = lambda a: [a[int(off[s]):int(off[s + 1])] for s in range(streams)]
-        return {"surprisal": cut(sur), "entropy": cut(ent), "rank": cut(rank), "top_byte": cut(tby), "top_bits": cut(tbi),
-                "bits": bits, "h": h, "c": c, "end_state": q1}
+        res = {"surprisal": cut(sur), "entropy": cut(ent), "rank": cut(rank), "top_byte": cut(tby), "top_bits": cut(tbi),
+               "bits": bits, "h": h, "c": c, "end_state": q1}
+        if gd is not None:
+            res["guide_h"], res["guide_c"] = gh, gc
+        return res
 
     def beam_search(self, prompts=None, count=0, beams=4, stop_byte=-1, h0=None, c0=None, streams=None, length_alpha=0.0,
                     trace=False, constraint=None, start_state=None, accept=None):

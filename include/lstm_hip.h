@@ -739,6 +739,62 @@ int lstm_hip_generate_processed(lstm_hip_t *h, int32_t streams, const uint8_t *p
                                 uint8_t *out, double *bits, float *h_out, float *c_out, int32_t *out_len, uint16_t *kept,
                                 const lstm_hip_beam_constraint *bc, const int32_t *start_state, int32_t *end_state,
                                 const lstm_hip_logit_processors *lp /* NULL: exactly lstm_hip_generate_accepting */);
+/* ---- guided generation and scoring: a log-linear mix of the logits of several models that are fed
+ *      the same bytes, each carrying its own recurrent state: z' = a*z + SUM_k b_k*z^k.  (1+g, -g) with a smaller model is
+ *      contrastive decoding, with the same model on another context it is guidance with a negative context, and weights that
+ *      sum to 1 are the geometric mean of an ensemble.  lstm_hip_generate_processed and lstm_hip_score are thin callers of the
+ *      two functions below with gd = NULL, and that case is exactly the earlier call, with its scratch offsets, uploads,
+ *      launches and bytes.  Everything lstm_hip_generate_processed / lstm_hip_score document holds, except what follows.
+ *        feeding    every guide is fed the inputs the main model is fed, in the same steps: the prompt bytes, then the drawn
+ *                   bytes; for the scorer the text.  Each guide advances its own state from its own h0 / c0 (N_k x streams, N_k
+ *                   the guide's logical N; NULL = zeros) through its own W, U, b.  The block its
+ *                   lstm_hip_set_inference_source names is read, its LSTM_HIP_FAST_MATH applies to its recurrence, weight drop is
+ *                   never applied.  A guide is only read, nothing of it is written: model == h is allowed (the same weights with
+ *                   a second state: the guidance case), and so is the same handle in two guides.
+ *        logits     z^k_m = Why_k*h_k + by_k summed as lstm_hip_generate sums it (sequentially in the hidden index, multiply and
+ *                   add separately rounded, by added last): bit for bit what guide k's own call computes from that state.
+ *        mixing     g_m = b_1*z^1_m, then g_m = g_m + b_k*z^k_m for k = 2.. in index order, then z_m <- a*z_m + g_m.  Every
+ *                   weight is narrowed to float on the host; every multiply and every add is one fp32 operation, no contraction.
+ *        generator  mixing is step 0 of the processors' list, ahead of the bias.  Only DRAWN bytes are mixed, greedy draws see
+ *                   it; prompt bits ignore it, as they ignore the processors and the table.  A guided draw is a processed draw
+ *                   (always filtered, kept = keep).  Tables, accepting states, the n-gram rule, min-p, top-k / top-p and the
+ *                   replace rules then run on the mixed logits unchanged; out is still always accepted by the table.
+ *        stopping   a stream that has stopped idles in every guide too.  guide.h_out / c_out is the guide's state after the
+ *                   stream's last input, the stop byte included: the rule of the main h_out.
+ *        chaining   (generator) a second call that passes every model's h_out / c_out as its h0 / c0, start_state = end_state
+ *                   and the history as lstm_hip_generate_processed hands it over gives the one long call, bit for bit.
+ *        scorer     every scored byte is scored under the mixed logits: surprisal, entropy, rank, top bytes and top bits, and
+ *                   bits are defined on z' exactly as they are on z.  The constraint mask comes after the mix.  With first = 1
+ *                   byte 0 sees every guide's start state.  Chaining in pieces holds with the guides' states handed over too.
+ *        ordering   all launches go on the main handle's stream.  Where model != h the call first makes that stream wait on an
+ *                   event recorded on the guide's stream, so work the caller queued on the guide is finished.  The call ends
+ *                   synchronised.  A guide may not be used by another host thread during the call.
+ *        cost       per step one more launch for all guides together (their logits and the mix) and one recurrence step per guide;
+ *                   the guides' images of U, states and the sum live in the MAIN handle's working memory.
+ *      Beam search, the coders, lstm_hip_sample, lstm_hip_eval_texts and lstm_hip_embed_texts take no guides.
+ *      LSTM_HIP_EINVAL (the handle stays usable, nothing is launched; the message names the guide's index), beside those of the
+ *      unguided call, which come first: gd->size wrong; nguides outside 1..LSTM_HIP_MAX_GUIDES; guides NULL; main_weight or a
+ *      weight NaN or infinite; a NULL model; a guide on another device; a guide whose internal width is above 16384.
+ *      LSTM_HIP_EHIP: the device refused the LDS request of the guides' kernel (nothing of that step is launched). */
+#define LSTM_HIP_MAX_GUIDES 4
+typedef struct lstm_hip_guide {
+    lstm_hip_t *model;          /* any handle on the same device, any N and flags; MAY BE h ITSELF */
+    double weight;              /* b_k: finite; negative and 0 allowed */
+    const float *h0, *c0;       /* N_k x streams (the guide's logical N), NULL = zeros */
+    float *h_out, *c_out;       /* N_k x streams, may be NULL: the guide's state after the stream's last input */
+} lstm_hip_guide;
+typedef struct lstm_hip_guidance {
+    uint32_t size;              /* sizeof(lstm_hip_guidance); anything else: LSTM_HIP_EINVAL */
+    double main_weight;         /* a: finite */
+    int32_t nguides;            /* 1..LSTM_HIP_MAX_GUIDES */
+    const lstm_hip_guide *guides;
+} lstm_hip_guidance;
+int lstm_hip_generate_guided(lstm_hip_t *h, int32_t streams, const uint8_t *prompts, const uint64_t *prompt_off,
+                             const float *h0, const float *c0, const lstm_hip_sampling *opt, const double *u, int32_t count,
+                             uint8_t *out, double *bits, float *h_out, float *c_out, int32_t *out_len, uint16_t *kept,
+                             const lstm_hip_beam_constraint *bc, const int32_t *start_state, int32_t *end_state,
+                             const lstm_hip_logit_processors *lp,
+                             const lstm_hip_guidance *gd /* NULL: exactly lstm_hip_generate_processed */);
 /* ---- per-byte scores: what the model thinks of every byte of given texts.  Stream s is
  *      text[text_off[s] .. text_off[s+1]), 1 <= streams <= 4096; empty streams are allowed (no entries, h_out = the start
  *      state).  h0 / c0 / h_out / c_out are N x streams as in lstm_hip_generate (NULL = zeros / not wanted); h_out is the
@@ -790,6 +846,10 @@ int lstm_hip_score(lstm_hip_t *h, int32_t streams, const uint8_t *text, const ui
                    const int32_t *start_state /* [streams], may be NULL: all 0; only with con */,
                    const lstm_hip_scores *out /* may be NULL: nothing but h_out / c_out is wanted */, float *h_out,
                    float *c_out);
+/* the same call under a mix with other models: the block, the rule and the refusals stand at lstm_hip_generate_guided */
+int lstm_hip_score_guided(lstm_hip_t *h, int32_t streams, const uint8_t *text, const uint64_t *text_off, const float *h0,
+                          const float *c0, const lstm_hip_scoring *opt, const int32_t *start_state, const lstm_hip_scores *out,
+                          float *h_out, float *c_out, const lstm_hip_guidance *gd /* NULL: exactly lstm_hip_score */);
 
 /* ---- held-out bits of many texts at the trainer's forward speed: the training window's forward
  *      path (recurrence, time-batched Why*H, softmax launch) run forward-only, on a cached internal handle of
