@@ -304,11 +304,7 @@ void launch_regs(int M, int Nn, int K, const float *A, int lda, const float *B, 
     const int tiles_m = (M + TM - 1) / TM, tiles_n = (Nn + TN - 1) / TN;
     const size_t lds = sizeof(float) * 4 * 64 * (size_t)NW * VB * 4 * VA;
     auto kern = k_gemm_regs<AKF, BKF, VA, VB, NW, DEPTH>;
-    static bool attr_done = false; // per instantiation
-    if (!attr_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_done = true;
-    }
+    (void)grant_lds<k_gemm_regs<AKF, BKF, VA, VB, NW, DEPTH>, 0>(lds); // (one size per instantiation)
     hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n, splits), dim3(64 * NW), lds, st, M, Nn, K, A, lda, B, ldb, C, ldc, tiles_m,
                        tiles_n, kchunk, slab_stride);
 }

@@ -23,6 +23,30 @@ struct ParamLayout {
     }
 };
 
+// ---- the request for dynamic LDS: the one place a kernel is granted more than a launch gets unasked ----------------------
+// A refused request is returned.  A launcher that returns hipError_t passes it on and launches nothing; a void launcher may
+// drop it: the launch it then makes is refused too, and the caller's launch check reports that.
+template <class K> inline hipError_t request_lds(K kernel, size_t bytes) {
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+}
+// The same behind a cache: above FLOOR (what needs no request) the size is requested of the kernel first, and the largest
+// request that went through is remembered per kernel instantiation and per device.  The device is the calling thread's
+// current one, which every entry point of lstm_hip_api.cpp notes here as it sets it (so a cached launch asks the runtime
+// nothing, as before the table had a device); a device the table has no row for is asked every time.
+extern thread_local int lds_device; // (kernels.hip; 0 until an entry point says otherwise)
+template <auto KERNEL, size_t FLOOR> inline hipError_t grant_lds(size_t lds) {
+    constexpr int kDevices = 128;
+    static size_t granted[kDevices] = {};
+    if (lds <= FLOOR) return hipSuccess;
+    const int dev = lds_device;
+    if (dev < 0 || dev >= kDevices) return request_lds(KERNEL, lds);
+    if (lds > granted[dev]) {
+        if (const hipError_t e = request_lds(KERNEL, lds)) return e;
+        granted[dev] = lds;
+    }
+    return hipSuccess;
+}
+
 // ---- which form of each recurrence a handle runs (plan_engine, persistent.hip) ------------------------------------------
 // Decided once per handle at create from the shape, the create flags and the CU count; every launch of the window follows it.
 enum class FwdForm {

@@ -13,6 +13,8 @@
 
 namespace lstmk {
 
+thread_local int lds_device = 0; // grant_lds (kernels.h)
+
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -506,7 +508,7 @@ void gemm_bf16(int M, int Nn, int K, const unsigned short *A, int lda, const uns
         hipLaunchKernelGGL((k_gemm_bf16<64, 64>), dim3((M + 63) / 64, (Nn + 63) / 64, splits), dim3(256), lds, st, M, Nn, K, A, lda, B, ldb,
                            out, ldo, kchunk, stride);
     } else {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm_bf16<128, 128>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)grant_lds<k_gemm_bf16<128, 128>, 0>(lds);
         hipLaunchKernelGGL((k_gemm_bf16<128, 128>), dim3((M + 127) / 128, (Nn + 127) / 128, splits), dim3(256), lds, st, M, Nn, K, A, lda, B,
                            ldb, out, ldo, kchunk, stride);
     }
@@ -1222,12 +1224,7 @@ void dW_sort(const int32_t *xi, int T, int G4, void *scratch, hipStream_t st) {
     const DwScratch d = dw_carve(scratch, T, G4);
     if (T <= 64 * 16 * RANK_SLOTS) {
         const size_t lds = (size_t)((T + 63) / 64) * 257 * sizeof(unsigned short);
-        static bool attr_set = false;
-        if (!attr_set) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_bucket_columns_rank),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024);
-            attr_set = true;
-        }
+        (void)grant_lds<k_bucket_columns_rank, 0>(140 * 1024); // (once, for every window length of this path)
         hipLaunchKernelGGL(k_bucket_columns_rank, dim3(1), dim3(1024), lds, st, xi, T, d.perm, d.chunk_start,
                            d.bucket_chunk, d.n_chunks);
     } else {
@@ -1991,11 +1988,7 @@ size_t b1_lds_bytes(int N) { return (size_t)(6 * N + 256) * sizeof(float); }
 // launch is returned, never passed over.  The caller has compared b1_lds_bytes with the device's opt-in limit.
 #define B1_LAUNCH(kernel, ...)                                                                                              \
     do {                                                                                                                    \
-        if (lds > 32768) {                                                                                                  \
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),                                \
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                 \
-            if (e != hipSuccess) return e;                                                                                  \
-        }                                                                                                                   \
+        if (const hipError_t e = grant_lds<kernel, 32768>(lds)) return e;                                                   \
         hipLaunchKernelGGL(kernel, dim3(1), dim3(1024), lds, st, __VA_ARGS__);                                              \
         return hipGetLastError();                                                                                           \
     } while (0)
@@ -2053,26 +2046,15 @@ int gen_head_group(int N, int streams) {
     while (sb < 16 && streams >= 256 * 2 * sb && (size_t)2 * sb * N <= 16384) sb *= 2;
     return sb;
 }
-// The heads' dynamic LDS, up to 64 KB beside static LDS of up to 33 KB: above FLOOR (what needs no request) the size is requested
-// of the kernel first; `granted` remembers the largest request that went through (one per kernel instantiation, per process).
-// A refused request is returned and nothing is launched: an error, not a launch.
-template <auto KERNEL, size_t FLOOR> static hipError_t grant_lds(size_t lds) {
-    static size_t granted = FLOOR;
-    if (lds > granted) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        granted = lds;
-    }
-    return hipSuccess;
-}
+// The heads' dynamic LDS, up to 64 KB beside static LDS of up to 33 KB, goes through grant_lds (kernels.h): a refused request is
+// returned and nothing is launched: an error, not a launch.
 template <bool STABLE> static hipError_t gen_head_launch(const GenHeadArgs &a, long long t, hipStream_t st) {
     const int sb = gen_head_group(a.N, a.streams);
     const size_t lds = (size_t)sb * a.N * sizeof(float);
     const dim3 grid((a.streams + sb - 1) / sb);
 #define GEN_HEAD_CASE(SB)                                                                                                   \
     case SB:                                                                                                                \
-        if (lds > 32768)                                                                                                    \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_gen_head<SB, STABLE, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+        if (const hipError_t e = grant_lds<k_gen_head<SB, STABLE, false>, 32768>(lds)) return e;                            \
         hipLaunchKernelGGL((k_gen_head<SB, STABLE, false>), grid, dim3(256), lds, st, a, t);                               \
         break;
     // FILTER: static LDS is up to 33 KB (ps, sorted), dynamic up to 64 KB
@@ -2223,8 +2205,7 @@ void code_head(const CodeHeadArgs &a, long long t, hipStream_t st) {
     const dim3 grid((a.streams + sb - 1) / sb);
 #define CODE_HEAD_CASE(SB)                                                                                                  \
     case SB:                                                                                                                \
-        if (lds > 32768)                                                                                                    \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_code_head<SB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+        (void)grant_lds<k_code_head<SB>, 32768>(lds);                                                                       \
         hipLaunchKernelGGL((k_code_head<SB>), grid, dim3(256), lds, st, a, t);                                             \
         break;
     switch (sb) {

@@ -26,6 +26,7 @@
 #include <map>
 #include <mutex>
 #include <tuple>
+#include <type_traits>
 #include <string>
 #include <vector>
 
@@ -46,6 +47,115 @@ int fail(int code, const char *fmt, ...) {
         hipError_t e_ = (expr);                                                                         \
         if (e_ != hipSuccess) return fail(LSTM_HIP_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
+#define TRY(expr)                         \
+    do {                                  \
+        if (int rc_ = (expr)) return rc_; \
+    } while (0)
+
+// ---- the owner of a handle's memory -------------------------------------------------------------------------------------
+// Every device allocation of a handle goes through its DeviceMem, and so does its one pinned host array (h_losses, the
+// second kind): what was allocated is what lstm_hip_destroy frees, on a half-built handle too, and no buffer has to be named
+// twice.  The handle's members stay plain pointers; the owner keeps the list.
+class DeviceMem {
+    struct Held {
+        void *p;
+        bool pinned;
+    };
+    std::vector<Held> held;
+
+  public:
+    static constexpr int kNoFill = -1; // for a buffer that is written whole before it is read
+    // p = `count` elements (bytes, for a void pointer), every byte set to fill_byte
+    template <class T> int alloc(T *&p, size_t count, int fill_byte = 0) {
+        const size_t bytes = count * sizeof(std::conditional_t<std::is_void_v<T>, char, T>);
+        void *q = nullptr;
+        HIP_TRY(hipMalloc(&q, bytes));
+        held.push_back({q, false});
+        p = static_cast<T *>(q);
+        if (fill_byte != kNoFill) HIP_TRY(hipMemset(q, fill_byte, bytes));
+        return 0;
+    }
+    template <class T> int alloc_pinned(T *&p, size_t count) {
+        void *q = nullptr;
+        HIP_TRY(hipHostMalloc(&q, count * sizeof(T), hipHostMallocDefault));
+        held.push_back({q, true});
+        p = static_cast<T *>(q);
+        return 0;
+    }
+    // frees p, which alloc or alloc_pinned gave, and nulls it; a null p is nothing to do
+    template <class T> int release(T *&p) {
+        if (!p) return 0;
+        const auto it = std::find_if(held.begin(), held.end(), [&](const Held &e) { return e.p == p; });
+        const bool pinned = it != held.end() && it->pinned;
+        if (it != held.end()) held.erase(it);
+        void *q = p;
+        p = nullptr;
+        HIP_TRY(pinned ? hipHostFree(q) : hipFree(q));
+        return 0;
+    }
+    // Room for `count` elements in a buffer that grows to its largest call and is kept: nothing to do while it fits (hipFree
+    // waits for the whole device); otherwise `st` is drained, the buffer released and max(count, floor) elements allocated,
+    // unfilled.  cap is 0 while there is no buffer.
+    template <class T, class C> int grow(hipStream_t st, T *&p, C &cap, C count, C floor = 0) {
+        if (count <= cap) return 0;
+        HIP_TRY(hipStreamSynchronize(st));
+        TRY(release(p));
+        cap = 0;
+        const C n = std::max(count, floor);
+        TRY(alloc(p, (size_t)n, kNoFill));
+        cap = n;
+        return 0;
+    }
+    void free_all() {
+        for (const Held &e : held) (void)(e.pinned ? hipHostFree(e.p) : hipFree(e.p));
+        held.clear();
+    }
+};
+// A device temporary of one call: allocated where the call can still refuse, freed on every return path.  (Not a piece of
+// the handle's generator scratch: that is kept, and an evaluator's text can be large.)
+template <class T> struct DeviceTemp {
+    T *p = nullptr;
+    DeviceTemp() = default;
+    DeviceTemp(const DeviceTemp &) = delete;
+    DeviceTemp &operator=(const DeviceTemp &) = delete;
+    ~DeviceTemp() {
+        if (p) (void)hipFree(p);
+    }
+    int alloc(size_t count) {
+        HIP_TRY(hipMalloc((void **)&p, count * sizeof(T)));
+        return 0;
+    }
+    operator T *() const { return p; }
+};
+
+// ---- the freshness of a handle's weight images --------------------------------------------------------------------------
+// Which images of U and Why hold the current parameters.  Under weight drop the U flags say more: that the images AND the
+// masked copy Ue are those of the current (rate, seed, t).  Three events make images stale or fresh, named here; the fourth,
+// a training window that needs them, is the window_images_* functions below.  Nothing else writes a flag.
+struct WeightImages {
+    bool packed = false;     // the fp32 images of the plan's forms (Ufwd / Ubwd / Ufwd4 / Ubwd4)
+    bool packed16 = false;   // the bf16 images as a set (what the one-recurrence forms read: Ufwd16 / Ubwd16)
+    bool packed6b = false;   // Ubwd6b alone is current (written by the update launch)
+    bool packedf6b = false;  // ... and Ufwd6b
+    bool why_packed = false; // both bf16 copies of Why
+
+    bool u_current(const EnginePlan &p) const { return p.bf16() ? packed16 : packed; }
+    // the parameter block was written from outside (lstm_hip_set_params, the internal handles' copy of the parent's block)
+    void params_written() { *this = WeightImages{}; }
+    // weight drop got another (rate, seed, t) or went off: every image of U is of another source; Why is not masked
+    void mask_changed() { packed = packed16 = packed6b = packedf6b = false; }
+    // An update launch ran.  It refreshed the fp32 images of U (the bf16 path has none) and, on the bf16 path, the two-half
+    // images (Ufwd6b in its quad form only) and both bf16 copies of Why; pack_U_bf16 repacks the one-recurrence images.
+    // Under weight drop the launch's images are of the unmasked U and the next window has the next mask.
+    void update_ran(const EnginePlan &p, bool weight_drop) {
+        packed = true;
+        packed16 = false;
+        packed6b = p.bwd == BwdForm::Bf16Scatter;
+        packedf6b = p.fwd == FwdForm::Bf16Halves && p.adagrad_quad;
+        why_packed = p.bf16();
+        if (weight_drop) mask_changed();
+    }
+};
 
 enum KernelId {
     K_PACK_U, K_FWD_STEP, K_GEMM_Y, K_SOFTMAX, K_LOSS, K_GEMM_DHY, K_BWD_STEP, K_GEMM_DWHY, K_GEMM_DU, K_DW_DB,
@@ -134,7 +244,8 @@ struct lstm_hip_ctx {
     bool early_reduced = false; // [dW] and [db | dWhy | dby] are already being all-reduced on st2 (ev_join marks the end)
     float *slabs_dU = nullptr; // split-K slabs of dU
     EnginePlan plan;           // the form of each recurrence and everything derived from it (plan_engine)
-    bool packed16 = false;
+    DeviceMem own;             // every device buffer below (and the pinned h_losses) is allocated and freed through it
+    WeightImages img;          // which of the weight images below are current
     unsigned short *Hb = nullptr, *DGb = nullptr; // bf16 hand-off copies of h and dg
     void *Ufwd16 = nullptr, *Ubwd16 = nullptr;    // bf16 fragment images of U (the one-recurrence forms)
     void *Ubwd6b = nullptr;                       // ... of the scatter-form backward (BwdForm::Bf16Scatter)
@@ -149,13 +260,10 @@ struct lstm_hip_ctx {
     bool keep_outputs = true;                     // this window stores Pr and the folded dP
     bool pr_stale = false, dp_stale = false;      // Pr / dP do not hold the last window's values: get_activations / get_grads refuse
     bool dgt_written = false;                     // the backward recurrence wrote the transposed bf16 image of dg itself
-    bool packed6b = false;                        // Ubwd6b is current (written by the Adagrad launch)
-    bool packedf6b = false;                       // ... and Ufwd6b
     // bf16 operands of the four time-batched products, k contiguous (kernels.h, gemm_bf16): Why^T and Why; per window
     // h^T [N][SBpad], dy^T [256][Tpad], dg^T [4N][Tpad] and dy [T][256]
     unsigned short *WhyT_b = nullptr, *Why_b = nullptr, *Ht_b = nullptr, *dYt_b = nullptr, *DGt_b = nullptr, *dYb = nullptr;
     int Tpad = 0, SBpad = 0;
-    bool why_packed = false;
     float *gpart = nullptr;    // per-column-group partial [dW|dU|db|dWhy] blocks of the fused backward recurrence
 
     float *P = nullptr, *dP = nullptr, *mem = nullptr;
@@ -166,7 +274,6 @@ struct lstm_hip_ctx {
     int ring_base = 0;       // slot of step 0 in the next launch
     float *DGx = nullptr;    // backward scatter forms: the same kind of ring for the partial sums
     int ring_base_b = 0;
-    bool packed = false;
     float *H = nullptr, *C = nullptr, *G = nullptr, *DG = nullptr, *Y = nullptr, *Pr = nullptr, *DHy = nullptr;
     float *dcnext = nullptr, *colloss = nullptr, *dby_part = nullptr, *slabs = nullptr;
     char *dw_scratch = nullptr;
@@ -204,7 +311,7 @@ struct lstm_hip_ctx {
     float *avg = nullptr;            // the average (flat block, internal width); allocated when averaging is first turned on
     int infer_src = LSTM_HIP_SRC_PARAMS; // the block the inference calls read (infer_block)
     // weight drop (lstm_hip_set_weight_drop): rate 0 = off.  While it is on, a training window's recurrences read images
-    // packed from Ue, and `packed` / `packed16` say that the images AND Ue are those of the current (rate, seed, t)
+    // packed from Ue, and the U flags of `img` say that the images AND Ue are those of the current (rate, seed, t)
     double wd_rate = 0.0;
     uint64_t wd_seed = 0, wd_t = 0;
     uint32_t wd_thr = 0;         // floor(rate * 2^32)
@@ -275,9 +382,11 @@ int launch_status(int id) {
     if (e != hipSuccess) return fail(LSTM_HIP_EHIP, "launch of %s failed: %s", kernel_name(id), hipGetErrorString(e));
     return 0;
 }
-int pad_status() { // the boundary's layout copies (not one of the window's timed kernels)
+// ... and the launches that are not among the window's timed kernels and have no statistics row, under their own names:
+// pad_copy (the boundary's layout copies), weight_drop, average, and lane_window / eval_fold / embed_fold of the text lanes
+int untimed_status(const char *name) {
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(LSTM_HIP_EHIP, "launch of pad_copy failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(LSTM_HIP_EHIP, "launch of %s failed: %s", name, hipGetErrorString(e));
     return 0;
 }
 template <class F> int timed(lstm_hip_ctx *h, int id, F &&launch) {
@@ -302,20 +411,10 @@ template <class F> int timed(lstm_hip_ctx *h, int id, F &&launch) {
         if (rc_) return rc_;                                       \
     } while (0)
 
-template <class T> int dalloc(T **p, size_t count, int fill_byte = 0) {
-    HIP_TRY(hipMalloc((void **)p, count * sizeof(T)));
-    HIP_TRY(hipMemset(*p, fill_byte, count * sizeof(T)));
-    return 0;
-}
-#define ALLOC(p, ...)                         \
-    do {                                      \
-        int rc_ = dalloc(&(p), __VA_ARGS__); \
-        if (rc_) return rc_;                  \
-    } while (0)
-
 int check(lstm_hip_ctx *h) {
     if (!h) return fail(LSTM_HIP_EINVAL, "null handle");
     HIP_TRY(hipSetDevice(h->cfg.device));
+    lds_device = h->cfg.device; // (grant_lds, kernels.h)
     return 0;
 }
 #define CHECK(h)             \
@@ -360,15 +459,10 @@ int loss_steps(const lstm_hip_ctx *h) { return loss_last_step(h) ? 1 : h->cfg.S 
 float loss_scale(const lstm_hip_ctx *h) { return h->loss_mode == LSTM_HIP_LOSS_LAST_STEP_NATS ? 0.693147180559945f : 1.0f; }
 
 // Weight drop (lstm_hip_set_weight_drop): one elementwise launch over U with the mask of the handle's (rate, seed, t), on the
-// handle's stream.  Like average it is not one of the window's timed kernels: its own status check, no statistics row.
-int weight_drop_status() {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(LSTM_HIP_EHIP, "launch of weight_drop failed: %s", hipGetErrorString(e));
-    return 0;
-}
+// handle's stream.  Like average it is not one of the window's timed kernels: untimed_status, no statistics row.
 int weight_drop_launch(lstm_hip_ctx *h, const float *src, float *dst) {
     weight_drop_mask(src, dst, h->cfg.N, h->N_log, h->wd_seed, h->wd_t, h->wd_thr, h->wd_scale, h->plan.n_cus, h->st);
-    return weight_drop_status();
+    return untimed_status("weight_drop");
 }
 
 int do_forward(lstm_hip_ctx *h);
@@ -434,6 +528,42 @@ int soft_precheck(lstm_hip_ctx *h, const char *what) {
     return 0;
 }
 
+// A training window needs the images (the fourth event of WeightImages): whatever is stale is made from Usrc -- the
+// parameters' U, or under weight drop the masked copy Ue, itself remade first -- and marked current.  Three functions, one
+// per place the launches have in the window: the mask and the fp32 images before the hand-off epoch of do_forward, the bf16
+// images of U behind it, the bf16 copies of Why behind the recurrence.
+int window_images_fp32(lstm_hip_ctx *h, const float *Usrc) {
+    const EnginePlan &p = h->plan;
+    if (h->wd_rate > 0.0 && !h->img.u_current(p))
+        if (int rc = weight_drop_launch(h, h->P + h->pl.U, h->Ue)) return rc;
+    if (!h->img.packed && !p.bf16()) { // (the bf16 path packs its own images: window_images_bf16)
+        RUN(K_PACK_U, pack_U(Usrc, p.ufwd4() ? nullptr : h->Ufwd, p.ubwd4() ? nullptr : h->Ubwd, h->cfg.N, h->st, h->Ubwd4,
+                             h->Ufwd4, p.half_forms())); // one image per direction is live
+        h->img.packed = true;
+    }
+    return 0;
+}
+int window_images_bf16(lstm_hip_ctx *h, const float *Usrc) {
+    const EnginePlan &p = h->plan;
+    const int N = h->cfg.N;
+    if (p.bf16() && !h->img.packed16) { // (the one-recurrence forms' images only where one of them runs)
+        RUN(K_PACK_U, (p.u16 ? pack_U_bf16(Usrc, h->Ufwd16, h->Ubwd16, N, h->st) : (void)0,
+                       p.bwd == BwdForm::Bf16Scatter && !h->img.packed6b ? pack_U6_bf16(Usrc, h->Ubwd6b, N, h->st) : (void)0,
+                       p.fwd == FwdForm::Bf16Halves && !h->img.packedf6b ? pack_Ufwd6_bf16(Usrc, h->Ufwd6b, N, h->st) : (void)0));
+        h->img.packed16 = true;
+    }
+    return 0;
+}
+int window_images_why(lstm_hip_ctx *h) { // Why rounded once per update
+    const int N = h->cfg.N;
+    if (h->plan.bf16() && !h->img.why_packed) {
+        RUN(K_PACK_U, (transpose_pack_bf16(h->P + h->pl.Why, N, 256, 256, h->WhyT_b, N, h->st),
+                       pack_bf16(h->P + h->pl.Why, (size_t)256 * N, h->Why_b, h->st)));
+        h->img.why_packed = true;
+    }
+    return 0;
+}
+
 int do_forward(lstm_hip_ctx *h) {
     const EnginePlan &p = h->plan;
     const int N = h->cfg.N, B = h->cfg.B, S = h->cfg.S, G4 = 4 * N;
@@ -443,13 +573,7 @@ int do_forward(lstm_hip_ctx *h) {
         if (int rc = teacher_forward(h)) return rc;
     // weight drop: the window's images of U are packed from the masked copy, remade whenever they are
     const float *Usrc = h->wd_rate > 0.0 ? h->Ue : h->P + h->pl.U;
-    if (h->wd_rate > 0.0 && !(p.bf16() ? h->packed16 : h->packed))
-        if (int rc = weight_drop_launch(h, h->P + h->pl.U, h->Ue)) return rc;
-    if (!h->packed && !p.bf16()) { // (the bf16 path packs its own images below)
-        RUN(K_PACK_U, pack_U(Usrc, p.ufwd4() ? nullptr : h->Ufwd, p.ubwd4() ? nullptr : h->Ubwd, N, h->st, h->Ubwd4,
-                             h->Ufwd4, p.half_forms())); // one image per direction is live
-        h->packed = true;
-    }
+    TRY(window_images_fp32(h, Usrc));
     h->n_dby_parts = softmax_parts(h->T);
     if (p.persistent()) {
         if (h->fwd_epoch >= p.epoch_limit) { // keep epoch * arrivals inside 32 bits
@@ -459,12 +583,7 @@ int do_forward(lstm_hip_ctx *h) {
         }
         h->fwd_epoch++;
     }
-    if (p.bf16() && !h->packed16) { // (the one-recurrence forms' images only where one of them runs)
-        RUN(K_PACK_U, (p.u16 ? pack_U_bf16(Usrc, h->Ufwd16, h->Ubwd16, N, h->st) : (void)0,
-                       p.bwd == BwdForm::Bf16Scatter && !h->packed6b ? pack_U6_bf16(Usrc, h->Ubwd6b, N, h->st) : (void)0,
-                       p.fwd == FwdForm::Bf16Halves && !h->packedf6b ? pack_Ufwd6_bf16(Usrc, h->Ufwd6b, N, h->st) : (void)0));
-        h->packed16 = true;
-    }
+    TRY(window_images_bf16(h, Usrc));
     switch (p.fwd) {
     case FwdForm::Step:
         for (int t = 1; t < S; t++) {
@@ -509,12 +628,8 @@ int do_forward(lstm_hip_ctx *h) {
         break;
     }
     // Y = Why * H[1..S-1]   (R/lstm.cc:195 for every step at once)
+    TRY(window_images_why(h));
     if (p.bf16()) { // bf16 operands (Why rounded once per update, the recurrence's own bf16 copy of h), fp32 accumulate
-        if (!h->why_packed) {
-            RUN(K_PACK_U, (transpose_pack_bf16(h->P + h->pl.Why, N, 256, 256, h->WhyT_b, N, h->st),
-                           pack_bf16(h->P + h->pl.Why, (size_t)256 * N, h->Why_b, h->st)));
-            h->why_packed = true;
-        }
         RUN(K_GEMM_Y, gemm_bf16(256, h->T, N, h->WhyT_b, N, h->Hb + (size_t)N * B, N, h->Y + (size_t)256 * B, 256, 1, nullptr,
                                 h->st));
     } else
@@ -782,20 +897,15 @@ int do_allreduce(lstm_hip_ctx *h) {
 // The running weight average (lstm_hip_set_averaging) after an update of a handle that asked for it: count the update and,
 // when it is due, fold the parameters the update has just written into the average.  n and w are host numbers; the launch
 // goes to the handle's stream behind the update launch, with no readback and no synchronisation.  Like pad_copy it is not
-// one of the window's timed kernels: it has its own status check and no statistics row.  The counters move only once the
-// launch has been accepted.
-int average_status() {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(LSTM_HIP_EHIP, "launch of average failed: %s", hipGetErrorString(e));
-    return 0;
-}
+// one of the window's timed kernels: untimed_status and no statistics row.  The counters move only once the launch has
+// been accepted.
 int average_step(lstm_hip_ctx *h) {
     const int64_t seen = h->avg_seen + 1;
     if (seen % h->avg_every == 0) {
         const int64_t n = h->avg_n + 1;
         const float w = h->avg_kind == LSTM_HIP_AVG_EMA ? (float)(1.0 - h->avg_decay) : (float)(1.0 / (double)n);
         average(h->P, h->avg, h->pl.total, w, n == 1, h->plan.n_cus, h->st);
-        if (int rc = average_status()) return rc;
+        if (int rc = untimed_status("average")) return rc;
         h->avg_n = n;
     }
     h->avg_seen = seen;
@@ -878,15 +988,8 @@ int do_adagrad(lstm_hip_ctx *h, double lr, int64_t norm_idx) {
         h->head = head_next;
     }
     h->carry_slide = false;
-    h->packed = true; // the fp32 U images were refreshed by the same launch (the bf16 path has none)
-    h->packed16 = false;
-    h->packed6b = p.bwd == BwdForm::Bf16Scatter;
-    h->packedf6b = p.fwd == FwdForm::Bf16Halves && p.adagrad_quad; // (k_adagrad writes that image in its quad form only)
-    h->why_packed = p.bf16(); // (the bf16 path's Adagrad launch has just rewritten both bf16 copies of Why)
-    if (h->wd_rate > 0.0) { // weight drop: the next window has the next mask, and the launch's images are of the unmasked U
-        h->wd_t++;
-        h->packed = h->packed16 = h->packed6b = h->packedf6b = false;
-    }
+    h->img.update_ran(p, h->wd_rate > 0.0); // the same launch refreshed the images it is given above
+    if (h->wd_rate > 0.0) h->wd_t++;        // weight drop: the next window has the next mask
     // the running average, in a launch of its own behind the update launch (never inside it: include/lstm_hip.h)
     if (h->avg_kind != LSTM_HIP_AVG_OFF) return average_step(h);
     return 0;
@@ -952,6 +1055,7 @@ int lstm_hip_create(const lstm_hip_config *user_cfg, lstm_hip_t **out) {
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
         return fail(LSTM_HIP_ENODEV, "device %d is %s; this library is built for gfx950 only", cfg->device, prop.gcnArchName);
     HIP_TRY(hipSetDevice(cfg->device));
+    lds_device = cfg->device;
     // everything that can be refused is refused before the first allocation
     const EnginePlan plan = plan_engine(cfg->N, cfg->B, cfg->flags, prop.multiProcessorCount);
     if (plan.refusal[0]) return fail(LSTM_HIP_EINVAL, "%s", plan.refusal);
@@ -963,7 +1067,7 @@ int lstm_hip_create(const lstm_hip_config *user_cfg, lstm_hip_t **out) {
     if (rc != 0) {
         char keep[sizeof(g_err)];
         memcpy(keep, g_err, sizeof(keep)); // destroy must not overwrite the reason
-        (void)lstm_hip_destroy(h);         // frees whatever had been allocated (every member is null-checked)
+        (void)lstm_hip_destroy(h);         // frees whatever had been allocated (the owner's list; the rest is null-checked)
         memcpy(g_err, keep, sizeof(keep));
         return rc;
     }
@@ -992,19 +1096,20 @@ static int create_body(lstm_hip_ctx *h, const lstm_hip_config *cfg) {
         HIP_TRY(hipEventElapsedTime(&ms, h->evt0, h->evt1));
     }
     const EnginePlan &p = h->plan;
-    ALLOC(h->P, h->pl.total);
-    ALLOC(h->dP, h->pl.total);
-    ALLOC(h->mem, h->pl.total);
-    ALLOC(h->H, N * B * S);
-    ALLOC(h->C, N * B * S);
-    ALLOC(h->G, G4 * B * S);
-    ALLOC(h->DG, G4 * B * S);
-    ALLOC(h->Y, 256 * B * S);
-    ALLOC(h->Pr, 256 * B * S);
-    ALLOC(h->DHy, N * B * S);
-    ALLOC(h->dcnext, N * B);
-    ALLOC(h->colloss, B * S);
-    ALLOC(h->dby_part, (size_t)256 * softmax_parts(h->T));
+    DeviceMem &m = h->own;
+    TRY(m.alloc(h->P, h->pl.total));
+    TRY(m.alloc(h->dP, h->pl.total));
+    TRY(m.alloc(h->mem, h->pl.total));
+    TRY(m.alloc(h->H, N * B * S));
+    TRY(m.alloc(h->C, N * B * S));
+    TRY(m.alloc(h->G, G4 * B * S));
+    TRY(m.alloc(h->DG, G4 * B * S));
+    TRY(m.alloc(h->Y, 256 * B * S));
+    TRY(m.alloc(h->Pr, 256 * B * S));
+    TRY(m.alloc(h->DHy, N * B * S));
+    TRY(m.alloc(h->dcnext, N * B));
+    TRY(m.alloc(h->colloss, B * S));
+    TRY(m.alloc(h->dby_part, (size_t)256 * softmax_parts(h->T)));
     h->splits_dWhy = gemm_pick_splits(false, true, 256, (int)N, h->T, p.n_cus);
     h->splits_dU = gemm_pick_splits(false, true, (int)G4, (int)N, h->T, p.n_cus);
     if (p.bf16()) {
@@ -1013,55 +1118,55 @@ static int create_body(lstm_hip_ctx *h, const lstm_hip_config *cfg) {
         h->splits_dWhy = gemm_bf16_pick_splits(256, (int)N, h->Tpad);
         h->splits_dU = gemm_bf16_pick_splits((int)G4, (int)N, h->Tpad);
     }
-    ALLOC(h->slabs, (size_t)h->splits_dWhy * 256 * N);
-    ALLOC(h->slabs_dU, (size_t)h->splits_dU * G4 * N);
-    ALLOC(h->dw_scratch, dW_scratch_bytes(h->T, (int)G4));
-    ALLOC(h->xi, S * B, 0xff); // -1: all-zero columns (opt:122,125)
-    ALLOC(h->ti, S * B, 0xff);
-    ALLOC(h->Xr, S * B, 0xff);
-    ALLOC(h->Tr, S * B, 0xff);
-    ALLOC(h->head_buf, 2);
+    TRY(m.alloc(h->slabs, (size_t)h->splits_dWhy * 256 * N));
+    TRY(m.alloc(h->slabs_dU, (size_t)h->splits_dU * G4 * N));
+    TRY(m.alloc(h->dw_scratch, dW_scratch_bytes(h->T, (int)G4)));
+    TRY(m.alloc(h->xi, S * B, 0xff)); // -1: all-zero columns (opt:122,125)
+    TRY(m.alloc(h->ti, S * B, 0xff));
+    TRY(m.alloc(h->Xr, S * B, 0xff));
+    TRY(m.alloc(h->Tr, S * B, 0xff));
+    TRY(m.alloc(h->head_buf, 2));
     h->head = h->head_buf;
-    ALLOC(h->d_loss, 1);
-    ALLOC(h->pos_buf, 2 * (size_t)B);
+    TRY(m.alloc(h->d_loss, 1));
+    TRY(m.alloc(h->pos_buf, 2 * (size_t)B));
     h->pos = h->pos_buf;
     h->cnt_bytes = persistent_counter_bytes((int)S, (int)B);
-    ALLOC(h->cnt, 2 * h->cnt_bytes / sizeof(unsigned));
-    ALLOC(h->abortp, 4);
+    TRY(m.alloc(h->cnt, 2 * h->cnt_bytes / sizeof(unsigned)));
+    TRY(m.alloc(h->abortp, 4));
     // what the plan's forms use: weight images, bf16 operand copies, hand-off rings (sentinel-filled), partial blocks
     if (!p.bf16()) {
-        ALLOC(h->Ufwd, N * N);
-        ALLOC(h->Ubwd, N * N);
+        TRY(m.alloc(h->Ufwd, N * N));
+        TRY(m.alloc(h->Ubwd, N * N));
     }
-    if (p.ufwd4()) ALLOC(h->Ufwd4, N * N);
-    if (p.ubwd4()) ALLOC(h->Ubwd4, N * N);
+    if (p.ufwd4()) TRY(m.alloc(h->Ufwd4, N * N));
+    if (p.ubwd4()) TRY(m.alloc(h->Ubwd4, N * N));
     if (p.bf16()) {
-        ALLOC(h->Hb, S * B * N);
-        ALLOC(h->DGb, S * B * G4);
-        ALLOC(h->WhyT_b, 256 * N);
-        ALLOC(h->Why_b, 256 * N);
-        ALLOC(h->Ht_b, N * (size_t)h->SBpad);
-        ALLOC(h->dYt_b, (size_t)256 * h->Tpad);
-        ALLOC(h->DGt_b, G4 * (size_t)h->Tpad);
-        ALLOC(h->dYb, (size_t)h->T * 256);
+        TRY(m.alloc(h->Hb, S * B * N));
+        TRY(m.alloc(h->DGb, S * B * G4));
+        TRY(m.alloc(h->WhyT_b, 256 * N));
+        TRY(m.alloc(h->Why_b, 256 * N));
+        TRY(m.alloc(h->Ht_b, N * (size_t)h->SBpad));
+        TRY(m.alloc(h->dYt_b, (size_t)256 * h->Tpad));
+        TRY(m.alloc(h->DGt_b, G4 * (size_t)h->Tpad));
+        TRY(m.alloc(h->dYb, (size_t)h->T * 256));
     }
     if (p.u16) {
-        HIP_TRY(hipMalloc(&h->Ufwd16, (size_t)8 * N * N));
-        HIP_TRY(hipMalloc(&h->Ubwd16, (size_t)8 * N * N));
+        TRY(m.alloc(h->Ufwd16, (size_t)8 * N * N, DeviceMem::kNoFill));
+        TRY(m.alloc(h->Ubwd16, (size_t)8 * N * N, DeviceMem::kNoFill));
     }
-    if (p.fwd == FwdForm::Bf16Halves) HIP_TRY(hipMalloc(&h->Ufwd6b, (size_t)8 * N * N));
-    if (p.bwd == BwdForm::Bf16Scatter) HIP_TRY(hipMalloc(&h->Ubwd6b, (size_t)8 * N * N));
-    if (p.hx_floats) ALLOC(h->Hx, p.hx_floats, 0xff);
-    if (p.hxb_halfwords) ALLOC(h->Hxb, p.hxb_halfwords, 0xff);
-    if (p.dgx_floats) ALLOC(h->DGx, p.dgx_floats, 0xff);
-    if (p.fused) ALLOC(h->gpart, (size_t)((B + p.gpart_cols - 1) / p.gpart_cols) * bwd_partial_floats(cfg->N));
+    if (p.fwd == FwdForm::Bf16Halves) TRY(m.alloc(h->Ufwd6b, (size_t)8 * N * N, DeviceMem::kNoFill));
+    if (p.bwd == BwdForm::Bf16Scatter) TRY(m.alloc(h->Ubwd6b, (size_t)8 * N * N, DeviceMem::kNoFill));
+    if (p.hx_floats) TRY(m.alloc(h->Hx, p.hx_floats, 0xff));
+    if (p.hxb_halfwords) TRY(m.alloc(h->Hxb, p.hxb_halfwords, 0xff));
+    if (p.dgx_floats) TRY(m.alloc(h->DGx, p.dgx_floats, 0xff));
+    if (p.fused) TRY(m.alloc(h->gpart, (size_t)((B + p.gpart_cols - 1) / p.gpart_cols) * bwd_partial_floats(cfg->N)));
     HIP_TRY(hipStreamCreateWithFlags(&h->st2, hipStreamNonBlocking));
     HIP_TRY(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&h->ev_mid, hipEventDisableTiming));
-    if (p.stamps) ALLOC(h->stamps, 4 * S * 16);
+    if (p.stamps) TRY(m.alloc(h->stamps, 4 * S * 16));
     if (h->padded()) // the largest logical-width copy: the parameter block, or g of one step (4N x B; h0 and c0 for the sampler)
-        ALLOC(h->stage, std::max({ParamLayout::make(h->N_log, cfg->M).total, (size_t)4 * h->N_log * B, (size_t)2 * h->N_log}));
+        TRY(m.alloc(h->stage, std::max({ParamLayout::make(h->N_log, cfg->M).total, (size_t)4 * h->N_log * B, (size_t)2 * h->N_log})));
     HIP_TRY(hipDeviceSynchronize());
     return 0;
 }
@@ -1074,6 +1179,7 @@ int lstm_hip_destroy(lstm_hip_t *h) {
         return fail(LSTM_HIP_ESTATE, "destroy: %d student handle(s) hold this handle as their teacher (lstm_hip_set_soft_targets); "
                                      "clear or destroy them first", h->lent);
     (void)hipSetDevice(h->cfg.device);
+    lds_device = h->cfg.device;
     if (h->teacher) h->teacher->lent--;
     h->teacher = nullptr;
     if (h->eval_h) (void)lstm_hip_destroy(h->eval_h);
@@ -1081,16 +1187,7 @@ int lstm_hip_destroy(lstm_hip_t *h) {
     if (h->st) (void)hipStreamSynchronize(h->st);
     if (h->st2) (void)hipStreamSynchronize(h->st2);
     if (h->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(h->comm);
-    void *bufs[] = {h->P, h->dP, h->mem, h->Ufwd, h->Ubwd, h->Ubwd4, h->Ufwd4, h->Hx, h->DGx, h->H, h->C, h->G, h->DG, h->Y, h->Pr, h->DHy, h->dcnext,
-                    h->colloss, h->dby_part, h->slabs, h->slabs_dU, h->gpart, h->Hb, h->DGb, h->Ufwd16, h->Ubwd16, h->Ubwd6b, h->Ufwd6b, h->Hxb, h->WhyT_b, h->Why_b, h->Ht_b, h->dYt_b, h->DGt_b, h->dYb, h->dw_scratch, h->xi, h->ti, h->Xr, h->Tr, h->head_buf, h->cnt, h->abortp, h->stamps, h->d_loss, h->d_losses, h->text, h->pos_buf, h->stage, h->gen_scratch};
-    for (void *p : bufs)
-        if (p) (void)hipFree(p);
-    if (h->h_losses) (void)hipHostFree(h->h_losses);
-    for (void *p : {(void *)h->d_norms, (void *)h->norm_part, (void *)h->clip_coef, (void *)h->adam_v, (void *)h->avg, (void *)h->Ue, (void *)h->acc,
-                    (void *)h->tt_text, (void *)h->tt_off, (void *)h->tt_slot, (void *)h->tt_first, (void *)h->tt_bits,
-                    (void *)h->tt_weight, (void *)h->tt_wt,
-                    (void *)h->colkl, (void *)h->d_kls})
-        if (p) (void)hipFree(p);
+    h->own.free_all();
     for (hipEvent_t e : h->ev_soft)
         if (e) (void)hipEventDestroy(e);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -1121,7 +1218,7 @@ static int block_from_host(lstm_hip_ctx *h, float *dst, const float *host_block)
         const PadMap m = pad_map_params(h->N_log, h->cfg.N, h->cfg.M);
         HIP_TRY(hipMemcpyAsync(h->stage, host_block, sizeof(float) * m.total_l, hipMemcpyHostToDevice, h->st));
         pad_copy(h->stage, dst, m, true, h->st);
-        if (int rc = pad_status()) return rc;
+        if (int rc = untimed_status("pad_copy")) return rc;
     } else
     HIP_TRY(hipMemcpyAsync(dst, host_block, sizeof(float) * h->pl.total, hipMemcpyHostToDevice, h->st));
     HIP_TRY(hipStreamSynchronize(h->st));
@@ -1131,7 +1228,7 @@ static int block_to_host(lstm_hip_ctx *h, const float *src, float *host_block) {
     if (h->padded()) {
         const PadMap m = pad_map_params(h->N_log, h->cfg.N, h->cfg.M);
         pad_copy(src, h->stage, m, false, h->st);
-        if (int rc = pad_status()) return rc;
+        if (int rc = untimed_status("pad_copy")) return rc;
         HIP_TRY(hipMemcpyAsync(host_block, h->stage, sizeof(float) * m.total_l, hipMemcpyDeviceToHost, h->st));
     } else
     HIP_TRY(hipMemcpyAsync(host_block, src, sizeof(float) * h->pl.total, hipMemcpyDeviceToHost, h->st));
@@ -1145,7 +1242,7 @@ int lstm_hip_set_params(lstm_hip_t *h, int which, const float *host_block) {
     float *dst = block_of(h, which);
     if (!dst || !host_block) return fail(LSTM_HIP_EINVAL, "set_params: bad block id %d or null pointer", which);
     if (int rc = block_from_host(h, dst, host_block)) return rc;
-    if (which == 0) h->packed = h->packed16 = h->packed6b = h->packedf6b = h->why_packed = false;
+    if (which == 0) h->img.params_written();
     return 0;
 }
 int lstm_hip_get_params(lstm_hip_t *h, int which, float *host_block) {
@@ -1171,7 +1268,7 @@ int lstm_hip_set_state(lstm_hip_t *h, int32_t t, const float *h_t, const float *
             if (!src) continue;
             HIP_TRY(hipMemcpyAsync(h->stage, src, sizeof(float) * m.total_l, hipMemcpyHostToDevice, h->st));
             pad_copy(h->stage, (k ? h->C : h->H) + t * n, m, true, h->st);
-            if (int rc = pad_status()) return rc;
+            if (int rc = untimed_status("pad_copy")) return rc;
         }
         HIP_TRY(hipStreamSynchronize(h->st));
         return 0;
@@ -1191,7 +1288,7 @@ int lstm_hip_get_state(lstm_hip_t *h, int32_t t, float *h_t, float *c_t) {
             float *dst = k ? c_t : h_t;
             if (!dst) continue;
             pad_copy((k ? h->C : h->H) + t * n, h->stage, m, false, h->st);
-            if (int rc = pad_status()) return rc;
+            if (int rc = untimed_status("pad_copy")) return rc;
             HIP_TRY(hipMemcpyAsync(dst, h->stage, sizeof(float) * m.total_l, hipMemcpyDeviceToHost, h->st));
             HIP_TRY(hipStreamSynchronize(h->st)); // (the staging buffer is reused for c)
         }
@@ -1211,7 +1308,7 @@ int lstm_hip_get_activations(lstm_hip_t *h, int32_t t, float *g_t, float *probs_
     if (g_t && h->padded()) { // gate blocks [i;o;f;u] of Np rows -> of N_log rows
         const PadMap m = pad_map_rows(4, h->N_log, h->cfg.N, h->cfg.B);
         pad_copy(h->G + t * G4 * B, h->stage, m, false, h->st);
-        if (int rc = pad_status()) return rc;
+        if (int rc = untimed_status("pad_copy")) return rc;
         HIP_TRY(hipMemcpyAsync(g_t, h->stage, sizeof(float) * m.total_l, hipMemcpyDeviceToHost, h->st));
     } else
     if (g_t) HIP_TRY(hipMemcpyAsync(g_t, h->G + t * G4 * B, sizeof(float) * G4 * B, hipMemcpyDeviceToHost, h->st));
@@ -1331,16 +1428,9 @@ int lstm_hip_adagrad(lstm_hip_t *h, double learning_rate) {
 
 // global-norm clipping before every Adagrad step (include/lstm_hip.h).  The scratch memory is made on the first use and kept
 // with the handle: d_norms grows with the longest train_windows call (train_windows, outside its loop).
+static const int64_t FIGURES_FLOOR = 8192; // the least room a per-window array of figures (norms, KLs, losses) is given
 static int ensure_norms(lstm_hip_ctx *h, int64_t count) {
-    if (count <= h->norms_cap) return 0;
-    const int64_t cap = count < 8192 ? 8192 : count;
-    HIP_TRY(hipStreamSynchronize(h->st));
-    if (h->d_norms) HIP_TRY(hipFree(h->d_norms));
-    h->d_norms = nullptr;
-    h->norms_cap = 0;
-    HIP_TRY(hipMalloc((void **)&h->d_norms, sizeof(double) * cap));
-    h->norms_cap = cap;
-    return 0;
+    return h->own.grow(h->st, h->d_norms, h->norms_cap, count, FIGURES_FLOOR);
 }
 int lstm_hip_set_grad_clip(lstm_hip_t *h, double max_norm) {
     CHECK(h);
@@ -1348,8 +1438,8 @@ int lstm_hip_set_grad_clip(lstm_hip_t *h, double max_norm) {
         return fail(LSTM_HIP_EINVAL, "set_grad_clip: max_norm must be >= 0 (0 = off, +inf = measure only; got %g)", max_norm);
     if (max_norm > 0.0) {
         if (int rc = ensure_norms(h, 1)) return rc;
-        if (!h->norm_part) HIP_TRY(hipMalloc((void **)&h->norm_part, sizeof(double) * grad_norm_parts(h->pl.total)));
-        if (!h->clip_coef) HIP_TRY(hipMalloc((void **)&h->clip_coef, sizeof(float)));
+        if (!h->norm_part) TRY(h->own.alloc(h->norm_part, grad_norm_parts(h->pl.total), DeviceMem::kNoFill));
+        if (!h->clip_coef) TRY(h->own.alloc(h->clip_coef, 1, DeviceMem::kNoFill));
     }
     h->clip_max = max_norm;
     return 0;
@@ -1373,7 +1463,7 @@ int lstm_hip_set_grad_accumulation(lstm_hip_t *h, int32_t every, int32_t mean) {
     if (every > 1 && h->comm)
         return fail(LSTM_HIP_ESTATE, "set_grad_accumulation: a handle with a communicator cannot accumulate gradients");
     if (every == h->acc_every && mean == h->acc_mean) return 0;
-    if (every > 1 && !h->acc) HIP_TRY(hipMalloc((void **)&h->acc, sizeof(float) * h->pl.total));
+    if (every > 1 && !h->acc) TRY(h->own.alloc(h->acc, h->pl.total, DeviceMem::kNoFill));
     h->acc_every = every, h->acc_mean = mean, h->acc_pending = 0;
     return 0;
 }
@@ -1425,7 +1515,7 @@ int lstm_hip_set_optimizer(lstm_hip_t *h, int32_t kind, double beta1, double bet
         return fail(LSTM_HIP_EINVAL, "set_optimizer: unknown kind %d", kind);
     if (kind != h->opt_kind) {
         HIP_TRY(hipStreamSynchronize(h->st));
-        if (kind == LSTM_HIP_OPT_ADAM && !h->adam_v) HIP_TRY(hipMalloc((void **)&h->adam_v, sizeof(float) * h->pl.total));
+        if (kind == LSTM_HIP_OPT_ADAM && !h->adam_v) TRY(h->own.alloc(h->adam_v, h->pl.total, DeviceMem::kNoFill));
         HIP_TRY(hipMemsetAsync(h->mem, 0, sizeof(float) * h->pl.total, h->st));
         if (h->adam_v) HIP_TRY(hipMemsetAsync(h->adam_v, 0, sizeof(float) * h->pl.total, h->st));
         HIP_TRY(hipStreamSynchronize(h->st));
@@ -1463,7 +1553,7 @@ int lstm_hip_set_averaging(lstm_hip_t *h, int32_t kind, double decay, int32_t ev
     if (kind != h->avg_kind) {
         if (kind != LSTM_HIP_AVG_OFF) {
             HIP_TRY(hipStreamSynchronize(h->st));
-            if (!h->avg) HIP_TRY(hipMalloc((void **)&h->avg, sizeof(float) * h->pl.total));
+            if (!h->avg) TRY(h->own.alloc(h->avg, h->pl.total, DeviceMem::kNoFill));
             HIP_TRY(hipMemsetAsync(h->avg, 0, sizeof(float) * h->pl.total, h->st));
             HIP_TRY(hipStreamSynchronize(h->st));
         }
@@ -1528,13 +1618,13 @@ int lstm_hip_set_weight_drop(lstm_hip_t *h, double rate, uint64_t seed, uint64_t
         return fail(LSTM_HIP_ESTATE, "set_weight_drop: this handle runs the dU product in halves (LSTM_HIP_DU_SPLIT), whose first "
                                      "half is all-reduced before the mask could be applied");
     if (rate > 0.0 && !h->Ue) {
-        HIP_TRY(hipMalloc((void **)&h->Ue, sizeof(float) * 4 * h->cfg.N * h->cfg.N));
+        TRY(h->own.alloc(h->Ue, (size_t)4 * h->cfg.N * h->cfg.N, DeviceMem::kNoFill));
         HIP_TRY(hipMemsetAsync(h->Ue, 0, sizeof(float) * 4 * h->cfg.N * h->cfg.N, h->st));
     }
     h->wd_rate = rate, h->wd_seed = seed, h->wd_t = t;
     h->wd_thr = rate > 0.0 ? weight_drop::threshold(rate) : 0;
     h->wd_scale = rate > 0.0 ? weight_drop::scale(rate) : 1.0f;
-    h->packed = h->packed16 = h->packed6b = h->packedf6b = false;
+    h->img.mask_changed();
     h->fwd_done = false;
     return 0;
 }
@@ -1588,7 +1678,7 @@ int lstm_hip_set_soft_targets(lstm_hip_t *h, lstm_hip_t *teacher, const lstm_hip
     if (on && h->comm)
         return fail(LSTM_HIP_ESTATE, "%s: this handle has a communicator; soft targets run on one device", what);
     if (teacher) { // the teacher's memory, before anything changes
-        if (!h->colkl) HIP_TRY(hipMalloc((void **)&h->colkl, sizeof(float) * h->T));
+        if (!h->colkl) TRY(h->own.alloc(h->colkl, h->T, DeviceMem::kNoFill));
         if (int rc = ensure_kls(h, 1)) return rc;
         for (hipEvent_t &e : h->ev_soft)
             if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -1658,9 +1748,8 @@ int lstm_hip_set_text(lstm_hip_t *h, const uint8_t *text, size_t len) {
     CHECK(h);
     if (!text || len <= (size_t)h->cfg.S) return fail(LSTM_HIP_EINVAL, "set_text: need more than S=%d bytes (got %zu)", h->cfg.S, len);
     HIP_TRY(hipStreamSynchronize(h->st));
-    if (h->text) HIP_TRY(hipFree(h->text));
-    h->text = nullptr;
-    HIP_TRY(hipMalloc((void **)&h->text, len));
+    TRY(h->own.release(h->text));
+    TRY(h->own.alloc(h->text, len, DeviceMem::kNoFill));
     HIP_TRY(hipMemcpy(h->text, text, len, hipMemcpyHostToDevice));
     h->text_len = len;
     return 0;
@@ -1706,30 +1795,16 @@ int lstm_hip_set_loss_mode(lstm_hip_t *h, int32_t mode) {
 }
 
 // the window loops (lstm_hip_train_windows, the adaptive coder): room for `count` per-window losses
-static int ensure_kls(lstm_hip_ctx *h, int64_t count) { // (as ensure_norms)
-    if (count <= h->kls_cap) return 0;
-    const int64_t cap = count < 8192 ? 8192 : count;
-    HIP_TRY(hipStreamSynchronize(h->st));
-    if (h->d_kls) HIP_TRY(hipFree(h->d_kls));
-    h->d_kls = nullptr;
-    h->kls_cap = 0;
-    HIP_TRY(hipMalloc((void **)&h->d_kls, sizeof(double) * cap));
-    h->kls_cap = cap;
-    return 0;
+static int ensure_kls(lstm_hip_ctx *h, int64_t count) {
+    return h->own.grow(h->st, h->d_kls, h->kls_cap, count, FIGURES_FLOOR);
 }
-static int ensure_losses(lstm_hip_ctx *h, int64_t count) {
+static int ensure_losses(lstm_hip_ctx *h, int64_t count) { // the device array and its pinned twin grow together
     if (count <= h->losses_cap) return 0;
-    const int64_t cap = count < 8192 ? 8192 : count;
-    HIP_TRY(hipStreamSynchronize(h->st));
-    if (h->d_losses) HIP_TRY(hipFree(h->d_losses));
-    if (h->h_losses) HIP_TRY(hipHostFree(h->h_losses));
-    h->d_losses = nullptr;
-    h->h_losses = nullptr;
-    h->losses_cap = 0;
-    HIP_TRY(hipMalloc((void **)&h->d_losses, sizeof(double) * cap));
-    HIP_TRY(hipHostMalloc((void **)&h->h_losses, sizeof(double) * cap, hipHostMallocDefault));
-    h->losses_cap = cap;
-    return 0;
+    TRY(h->own.grow(h->st, h->d_losses, h->losses_cap, count, FIGURES_FLOOR));
+    TRY(h->own.release(h->h_losses));
+    const int rc = h->own.alloc_pinned(h->h_losses, (size_t)h->losses_cap);
+    if (rc) h->losses_cap = 0; // (no twin: the next call makes both again)
+    return rc;
 }
 // One window of a device-resident loop, before its forward pass: does its loss ride in the update launch (wherever the
 // gradient fold does, do_backward's defer_fold, but not under clipping -- the norm needs dby first -- nor in a profiling pass,
@@ -1866,14 +1941,8 @@ int lstm_hip_eval_bits(lstm_hip_t *h, const uint8_t *text, size_t len, double *b
     const int N = h->cfg.N;
     if (!h->plan.persistent()) {
         if (int rc = b1_lds_check(h, "eval_bits")) return rc;
-        uint8_t *d_text = nullptr;
-        struct Free {
-            uint8_t *&p;
-            ~Free() {
-                if (p) (void)hipFree(p);
-            }
-        } free_text{d_text};
-        HIP_TRY(hipMalloc((void **)&d_text, len));
+        DeviceTemp<uint8_t> d_text;
+        TRY(d_text.alloc(len));
         HIP_TRY(hipMemcpyAsync(d_text, text, len, hipMemcpyHostToDevice, h->st));
         // (one spelling per source: tests/test_hidden_widths_cpu.py pins the text of the launch from the parameters)
         const bool stable = (h->cfg.flags & LSTM_HIP_STABLE_SOFTMAX) != 0;
@@ -1895,7 +1964,8 @@ int lstm_hip_eval_bits(lstm_hip_t *h, const uint8_t *text, size_t len, double *b
     }
     lstm_hip_ctx *e = h->eval_h;
     HIP_TRY(hipMemcpy(e->P, infer_block(h), sizeof(float) * h->pl.total, hipMemcpyDeviceToDevice));
-    e->packed = false;
+    if (e->plan.bf16()) return fail(LSTM_HIP_ESTATE, "eval_bits: the internal handle is not fp32"); // (ensure_aux_handle: its only live flag is `packed`)
+    e->img.params_written();
     HIP_TRY(hipMemset(e->H, 0, sizeof(float) * N)); // h = c = 0 (reset_std = 0, lstm.cc:45,676-677)
     HIP_TRY(hipMemset(e->C, 0, sizeof(float) * N));
     std::vector<int32_t> xi(Se), ti(Se);
@@ -1934,28 +2004,18 @@ int lstm_hip_sample(lstm_hip_t *h, float *h0, float *c0, const double *u, int32_
         return lstm_hip_generate(h, 1, nullptr, nullptr, h0, c0, 1.0, u, count, out, nullptr, h0, c0);
     const int N = h->cfg.N;
     if (int rc = b1_lds_check(h, "sample")) return rc;
-    float *d_hc = nullptr;
-    double *d_u = nullptr;
-    uint8_t *d_out = nullptr;
-    struct Scratch { // released on every return path
-        float *&a;
-        double *&b;
-        uint8_t *&c;
-        ~Scratch() {
-            if (a) (void)hipFree(a);
-            if (b) (void)hipFree(b);
-            if (c) (void)hipFree(c);
-        }
-    } scratch{d_hc, d_u, d_out};
-    HIP_TRY(hipMalloc((void **)&d_hc, sizeof(float) * 2 * N));
-    HIP_TRY(hipMalloc((void **)&d_u, sizeof(double) * (count + 1)));
-    HIP_TRY(hipMalloc((void **)&d_out, (size_t)count + 1));
+    DeviceTemp<float> d_hc;
+    DeviceTemp<double> d_u;
+    DeviceTemp<uint8_t> d_out;
+    TRY(d_hc.alloc((size_t)2 * N));
+    TRY(d_u.alloc((size_t)count + 1));
+    TRY(d_out.alloc((size_t)count + 1));
     const PadMap hc_map = pad_map_rows(1, h->N_log, N, 2); // [h | c] as two columns
     if (h->padded()) {
         HIP_TRY(hipMemcpyAsync(h->stage, h0, sizeof(float) * h->N_log, hipMemcpyHostToDevice, h->st));
         HIP_TRY(hipMemcpyAsync(h->stage + h->N_log, c0, sizeof(float) * h->N_log, hipMemcpyHostToDevice, h->st));
         pad_copy(h->stage, d_hc, hc_map, true, h->st);
-        if (int rc = pad_status()) return rc;
+        if (int rc = untimed_status("pad_copy")) return rc;
     } else {
         HIP_TRY(hipMemcpyAsync(d_hc, h0, sizeof(float) * N, hipMemcpyHostToDevice, h->st));
         HIP_TRY(hipMemcpyAsync(d_hc + N, c0, sizeof(float) * N, hipMemcpyHostToDevice, h->st));
@@ -1967,7 +2027,7 @@ int lstm_hip_sample(lstm_hip_t *h, float *h0, float *c0, const double *u, int32_
         return rc;
     if (h->padded()) {
         pad_copy(d_hc, h->stage, hc_map, false, h->st);
-        if (int rc = pad_status()) return rc;
+        if (int rc = untimed_status("pad_copy")) return rc;
         HIP_TRY(hipMemcpyAsync(h0, h->stage, sizeof(float) * h->N_log, hipMemcpyDeviceToHost, h->st));
         HIP_TRY(hipMemcpyAsync(c0, h->stage + h->N_log, sizeof(float) * h->N_log, hipMemcpyDeviceToHost, h->st));
     } else {
@@ -1985,16 +2045,8 @@ int lstm_hip_sample(lstm_hip_t *h, float *h0, float *c0, const double *u, int32_
 namespace {
 
 // the generator's and the coder's working memory: one allocation on the handle, grown to the largest call
-int reserve_gen_scratch(lstm_hip_t *h, size_t bytes) {
-    if (bytes > h->gen_scratch_bytes) { // (kept between calls: hipFree waits for the whole device)
-        HIP_TRY(hipStreamSynchronize(h->st));
-        if (h->gen_scratch) HIP_TRY(hipFree(h->gen_scratch));
-        h->gen_scratch = nullptr;
-        h->gen_scratch_bytes = 0;
-        HIP_TRY(hipMalloc((void **)&h->gen_scratch, bytes));
-        h->gen_scratch_bytes = bytes;
-    }
-    return 0;
+int reserve_gen_scratch(lstm_hip_t *h, size_t bytes) { // (no floor: the first call's size)
+    return h->own.grow(h->st, h->gen_scratch, h->gen_scratch_bytes, bytes);
 }
 
 // A call's layout of that memory: 256-byte aligned pieces in the order they are named.  Each piece is named once: the pointer
@@ -2041,7 +2093,7 @@ int upload_states(lstm_hip_t *h, int N, int N_log, const float *h0, const float 
         else if (N_log != N) {
             HIP_TRY(hipMemcpyAsync(stage + k * nl, src, sizeof(float) * nl, hipMemcpyHostToDevice, h->st));
             pad_copy(stage + k * nl, dst, map, true, h->st);
-            if (int rc = pad_status()) return rc;
+            if (int rc = untimed_status("pad_copy")) return rc;
         } else
             HIP_TRY(hipMemcpyAsync(dst, src, sizeof(float) * n, hipMemcpyHostToDevice, h->st));
     }
@@ -2061,7 +2113,7 @@ int download_states(lstm_hip_t *h, int N, int N_log, float *h_out, float *c_out,
         if (!dst) continue;
         if (N_log != N) {
             pad_copy(src, stage + k * nl, map, false, h->st);
-            if (int rc = pad_status()) return rc;
+            if (int rc = untimed_status("pad_copy")) return rc;
             HIP_TRY(hipMemcpyAsync(dst, stage + k * nl, sizeof(float) * nl, hipMemcpyDeviceToHost, h->st));
         } else
             HIP_TRY(hipMemcpyAsync(dst, src, sizeof(float) * n, hipMemcpyDeviceToHost, h->st));
@@ -3060,11 +3112,6 @@ static int64_t checked_plan(const char *what, int32_t steps, int32_t lanes, int3
     if (int rc = check_offsets(what, "text_off", text_off, streams)) return rc;
     return text_plan(steps, lanes, streams, text_off, lane_of, first_window, slot);
 }
-static int eval_status(const char *which) { // (not among the window's timed kernels: no statistics row)
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(LSTM_HIP_EHIP, "launch of %s failed: %s", which, hipGetErrorString(e));
-    return 0;
-}
 
 // the cached internal handle of lstm_hip_eval_texts and lstm_hip_embed_texts: remade when `lanes` changes
 static int texts_handle(lstm_hip_t *h, int lanes) {
@@ -3153,7 +3200,8 @@ struct TextsRun {
     int upload(const float *h0, const float *c0, const uint64_t *skip, LaneArgs &a) {
         if (int rc = mem.commit(h)) return rc;
         HIP_TRY(hipMemcpyAsync(e->P, infer_block(h), sizeof(float) * h->pl.total, hipMemcpyDeviceToDevice, h->st));
-        e->packed = false;
+        if (e->plan.bf16()) return fail(LSTM_HIP_ESTATE, "the internal lane handle is not fp32"); // (texts_handle: its only live flag is `packed`)
+        e->img.params_written();
         if (int rc = upload_states(h, h0, c0, H0, C0, stage, streams)) return rc;
         HIP_TRY(hipMemcpyAsync(d_off, text_off, sizeof(uint64_t) * (streams + 1), hipMemcpyHostToDevice, h->st));
         if (skip) HIP_TRY(hipMemcpyAsync(d_skip, skip, sizeof(uint64_t) * streams, hipMemcpyHostToDevice, h->st));
@@ -3193,7 +3241,7 @@ struct TextsRun {
         if (elapsed_ms) HIP_TRY(hipEventRecord(e->evt0, e->st));
         for (int64_t w = 0; w < windows; w++) {
             lane_window(a, w, e->plan.n_cus, e->st);
-            if (int rc = eval_status("lane_window")) return rc;
+            if (int rc = untimed_status("lane_window")) return rc;
             if (int rc = do_forward(e)) return rc;
             if (int rc = fold(w)) return rc;
         }
@@ -3229,7 +3277,7 @@ int lstm_hip_eval_texts(lstm_hip_t *h, int32_t streams, const uint8_t *text, con
     a.Cout = c_out ? ho + n : nullptr;
     const auto fold = [&](int64_t w) {
         eval_fold(a, w, r.e->plan.n_cus, r.e->st);
-        return eval_status("eval_fold");
+        return untimed_status("eval_fold");
     };
     if (int rc = r.loop(a, fold, elapsed_ms)) return rc;
 
@@ -3321,7 +3369,7 @@ int lstm_hip_embed_texts(lstm_hip_t *h, int32_t streams, const uint8_t *text, co
     a.picks = d_picks;
     const auto fold = [&](int64_t w) {
         embed_fold(a, w, pick_at[w], pick_at[w + 1], r.e->plan.n_cus, r.e->st);
-        return eval_status("embed_fold");
+        return untimed_status("embed_fold");
     };
     if (int rc = r.loop(a, fold, elapsed_ms)) return rc;
 
@@ -3647,11 +3695,14 @@ int lstm_hip_decode_adaptive(lstm_hip_t *h, const uint8_t *code, const uint64_t 
 // unweighted set is the weighted one with weight = NULL.
 static int drop_train_texts(lstm_hip_ctx *h) {
     HIP_TRY(hipStreamSynchronize(h->st));
-    for (void *p : {(void *)h->tt_text, (void *)h->tt_off, (void *)h->tt_slot, (void *)h->tt_first, (void *)h->tt_bits,
-                    (void *)h->tt_weight, (void *)h->tt_wt})
-        if (p) HIP_TRY(hipFree(p));
-    h->tt_text = nullptr, h->tt_off = nullptr, h->tt_slot = nullptr, h->tt_first = nullptr, h->tt_bits = nullptr;
-    h->tt_weight = nullptr, h->tt_wt = nullptr;
+    DeviceMem &m = h->own;
+    TRY(m.release(h->tt_text));
+    TRY(m.release(h->tt_off));
+    TRY(m.release(h->tt_slot));
+    TRY(m.release(h->tt_first));
+    TRY(m.release(h->tt_bits));
+    TRY(m.release(h->tt_weight));
+    TRY(m.release(h->tt_wt));
     h->tt_streams = 0;
     h->tt_windows = h->tt_next = 0;
     return 0;
@@ -3677,21 +3728,20 @@ int lstm_hip_set_train_texts_weighted(lstm_hip_t *h, int32_t streams, const uint
                                 (unsigned long long)(i - text_off[s]), s, (double)weight[i]);
     if (int rc = drop_train_texts(h)) return rc;
     // (at least one element each, so that a set plan always has its five buffers)
-    HIP_TRY(hipMalloc((void **)&h->tt_text, total ? total : 1));
-    HIP_TRY(hipMalloc((void **)&h->tt_off, sizeof(uint64_t) * (streams + 1)));
-    HIP_TRY(hipMalloc((void **)&h->tt_slot, sizeof(int32_t) * (slot.empty() ? 1 : slot.size())));
-    HIP_TRY(hipMalloc((void **)&h->tt_first, sizeof(int64_t) * streams));
-    HIP_TRY(hipMalloc((void **)&h->tt_bits, sizeof(double) * streams));
+    DeviceMem &m = h->own;
+    TRY(m.alloc(h->tt_text, total ? total : 1, DeviceMem::kNoFill));
+    TRY(m.alloc(h->tt_off, (size_t)streams + 1, DeviceMem::kNoFill));
+    TRY(m.alloc(h->tt_slot, slot.empty() ? 1 : slot.size(), DeviceMem::kNoFill));
+    TRY(m.alloc(h->tt_first, streams, DeviceMem::kNoFill));
+    TRY(m.alloc(h->tt_bits, streams, 0));
     if (total) HIP_TRY(hipMemcpy(h->tt_text, text, total, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(h->tt_off, text_off, sizeof(uint64_t) * (streams + 1), hipMemcpyHostToDevice));
     if (!slot.empty()) HIP_TRY(hipMemcpy(h->tt_slot, slot.data(), sizeof(int32_t) * slot.size(), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(h->tt_first, first.data(), sizeof(int64_t) * streams, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(h->tt_bits, 0, sizeof(double) * streams));
     if (weight) {
-        HIP_TRY(hipMalloc((void **)&h->tt_weight, sizeof(float) * (total ? total : 1)));
-        HIP_TRY(hipMalloc((void **)&h->tt_wt, sizeof(float) * h->cfg.S * h->cfg.B));
+        TRY(m.alloc(h->tt_weight, total ? total : 1, DeviceMem::kNoFill));
+        TRY(m.alloc(h->tt_wt, (size_t)h->cfg.S * h->cfg.B, 0));
         if (total) HIP_TRY(hipMemcpy(h->tt_weight, weight, sizeof(float) * total, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemset(h->tt_wt, 0, sizeof(float) * h->cfg.S * h->cfg.B));
     }
     h->tt_streams = streams;
     h->tt_windows = windows;

@@ -3398,19 +3398,17 @@ template <class K> struct Rung {
     bool stamped; // a STAMP instantiation (LSTM_HIP_DEBUG_STAMPS); only these are handed the stamp buffer
 };
 template <class K> static Rung<K> rung(K kern, int threads, size_t lds = 0, bool stamped = false) { return {kern, threads, lds, stamped}; }
-// (asked for with every question and every launch: a process may hold handles on several devices)
-template <class K> static void request_lds(const Rung<K> &r) {
-    if (r.lds > 0) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(r.kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)r.lds);
-}
+// (request_lds, kernels.h, with every question and every launch: a process may hold handles on several devices; a refused
+// one shows as 0 per CU / a refused launch)
 struct Occupancy { // the callable of the questions: workgroups per CU of the rung (0: no rung, or the runtime refused)
     int per_cu = 0;
     template <class K> void operator()(const Rung<K> &r) {
-        request_lds(r);
+        if (r.lds > 0) (void)request_lds(r.kern, r.lds);
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, r.kern, r.threads, r.lds) != hipSuccess) per_cu = 0;
     }
 };
 template <class K, class... A> static void launch(const Rung<K> &r, dim3 grid, hipStream_t st, A... args) {
-    request_lds(r);
+    if (r.lds > 0) (void)request_lds(r.kern, r.lds);
     hipLaunchKernelGGL(r.kern, grid, dim3(r.threads), r.lds, st, args...);
 }
 template <class F> static bool with_flag(bool b, F &&f) { return b ? f(std::true_type{}) : f(std::false_type{}); }

@@ -94,7 +94,7 @@ def test_the_api_file_refuses_the_communicator_and_the_adaptive_coders():
     setter = _body(api, "int lstm_hip_set_grad_accumulation(lstm_hip_t *h, int32_t every, int32_t mean) {")
     assert 'if (every > 1 && h->comm)' in setter
     assert 'LSTM_HIP_ESTATE, "set_grad_accumulation: a handle with a communicator cannot accumulate gradients"' in setter
-    assert setter.index("h->comm") < setter.index("hipMalloc")  # refused before anything is allocated or changed
+    assert setter.index("h->comm") < setter.index("h->own.alloc(")  # refused before anything is allocated or changed
     comm = _body(api, "int lstm_hip_comm_init(lstm_hip_t *h, const uint8_t id[LSTM_HIP_UNIQUE_ID_BYTES], int32_t nranks, int32_t rank) {")
     assert ('LSTM_HIP_ESTATE, "comm_init: gradient accumulation is on (lstm_hip_set_grad_accumulation); it runs on one device"'
             in comm)

@@ -119,7 +119,7 @@ def test_the_mask_has_launches_of_its_own():
     names = api[api.index("kKernelNames[K_COUNT] = {"):api.index("};", api.index("kKernelNames[K_COUNT] = {"))]
     assert "drop" not in names
     launch = _body(api, "int weight_drop_launch(lstm_hip_ctx *h, const float *src, float *dst)")
-    assert "weight_drop_mask(src, dst, h->cfg.N, h->N_log," in launch and "return weight_drop_status();" in launch
+    assert "weight_drop_mask(src, dst, h->cfg.N, h->N_log," in launch and 'return untimed_status("weight_drop");' in launch
     assert "RUN(" not in launch and "Synchronize" not in launch and "Memcpy" not in launch and "st2" not in launch
     assert not re.search(r"RUN\([^;]*weight_drop", api)
     kernels_h = open(os.path.join(CSRC, "kernels.h")).read()
