@@ -42,93 +42,11 @@ __device__ __forceinline__ void rc_normalize(const CodeHeadArgs &a, int s, Coder
         c.range <<= 8;
     }
 }
-template <int SB>
-__global__ __launch_bounds__(256) void k_code_head(CodeHeadArgs a, long long t) {
-    HEAD_DYNAMIC_LDS(float, hs); // [N][SB]
-    __shared__ uint32_t tab[SB][260]; // the logits, then expf terms (as float), then cum_0 .. cum_256
-    __shared__ float s_zmax[SB], s_sum[SB];
-    __shared__ uint32_t s_wave[4][SB];
-    const int m = threadIdx.x, N = a.N, s0 = blockIdx.x * SB, lane = m & 63, wave = m >> 6;
-    bool act[SB]; // (the same in every thread)
-    bool need = false;
-#pragma unroll
-    for (int j = 0; j < SB; j++) {
-        const int s = s0 + j;
-        act[j] = s < a.streams && (unsigned long long)t < a.text_off[s + 1] - a.text_off[s];
-        need |= act[j];
-    }
-    if (need) { // (uniform)
-        float *ps = reinterpret_cast<float *>(&tab[0][0]);
-        for (int i = m; i < N * SB; i += 256) {
-            const int k = i / SB, j = i - k * SB;
-            hs[i] = s0 + j < a.streams ? a.H[(size_t)(s0 + j) * N + k] : 0.0f;
-        }
-        __syncthreads();
-        float y[SB];
-#pragma unroll
-        for (int j = 0; j < SB; j++) y[j] = 0.0f;
-        for (int k0 = 0; k0 < N; k0 += 16) { // as k_gen_head: 16 loads in flight, the additions in k order
-            float wv[16];
-#pragma unroll
-            for (int i = 0; i < 16; i++) wv[i] = a.Why[(size_t)(k0 + i) * 256 + m];
-#pragma unroll
-            for (int i = 0; i < 16; i++)
-#pragma unroll
-                for (int j = 0; j < SB; j++) y[j] += wv[i] * hs[(k0 + i) * SB + j];
-        }
-        const float bym = a.by[m];
-#pragma unroll
-        for (int j = 0; j < SB; j++) {
-            y[j] = y[j] + bym; // the logit z
-            ps[j * 260 + m] = y[j];
-        }
-        __syncthreads();
-        const bool own = m < SB && s0 + m < a.streams && (unsigned long long)t < a.text_off[s0 + m + 1] - a.text_off[s0 + m];
-        if (own) { // max z of stream m (every order gives the same max)
-            float best = ps[m * 260];
-            for (int i = 1; i < 256; i++)
-                if (ps[m * 260 + i] > best) best = ps[m * 260 + i];
-            s_zmax[m] = best;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < SB; j++)
-            if (act[j]) ps[j * 260 + m] = expf(y[j] - s_zmax[j]);
-        __syncthreads();
-        if (own) {
-            float s = 0.0f;
-            for (int i = 0; i < 256; i++) s += ps[m * 260 + i];
-            s_sum[m] = s;
-        }
-        __syncthreads();
-        // quantise; exclusive integer scan of q over the 256 threads (wave scan, then the wave totals through LDS)
-        uint32_t q[SB], incl[SB];
-#pragma unroll
-        for (int j = 0; j < SB; j++) {
-            const float v = ps[j * 260 + m] / s_sum[j] * 65024.0f; // p_m * 65024, in [0, 65024] (NaN: q = 1)
-            q[j] = act[j] ? 1u + (v >= 1.0f ? (uint32_t)v : 0u) : 1u;
-            int x = (int)q[j];
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const int o = __shfl_up(x, d, 64);
-                if (lane >= d) x += o;
-            }
-            incl[j] = (uint32_t)x;
-        }
-        if (lane == 63)
-#pragma unroll
-            for (int j = 0; j < SB; j++) s_wave[wave][j] = incl[j];
-        __syncthreads(); // (also: every read of the expf terms is done)
-#pragma unroll
-        for (int j = 0; j < SB; j++) {
-            uint32_t before = 0;
-            for (int w = 0; w < wave; w++) before += s_wave[w][j];
-            tab[j][m] = before + incl[j] - q[j];
-            if (m == 255) tab[j][256] = before + incl[j];
-        }
-        __syncthreads();
-    }
-    // one owner thread per stream, spread over the four waves
+// the coder step of one owner thread per stream, spread over the four waves (every other thread returns at once); PUBLISH:
+// the byte coded or decoded goes to x_out[j] as well, for the threads that wait behind the step
+template <int SB, bool PUBLISH>
+__device__ __forceinline__ void code_owner_step(const CodeHeadArgs &a, const uint32_t (*tab)[260], int s0, int lane, int wave, long long t,
+                                                uint32_t *x_out) {
     const int j = lane * 4 + wave;
     if (j >= SB || s0 + j >= a.streams) return;
     const int s = s0 + j;
@@ -188,4 +106,148 @@ __global__ __launch_bounds__(256) void k_code_head(CodeHeadArgs a, long long t) 
     }
     a.state[s] = c;
     a.x_next[s] = x;
+    if constexpr (PUBLISH) x_out[j] = (uint32_t)x;
+}
+// MIX (code_head_mixed; lstm_hip_encode_mixed / lstm_hip_decode_mixed, DESIGN.md section 3.25): the table is built on the mix
+//   z' = v_0 * z^0 + g,   g = v_1 * z^1, then g = g + v_k * z^k in index order (one multiply, one add, each rounded)
+// of the main model's logits z^0 and the guides' z^k (a.zk, written by k_guide_logits ahead of this launch) under the stream's
+// own weights v (a.v).  With rate != 0 the weights then take one step on the byte x just coded, from what both sides hold:
+//   d_m = (float)q_m / (float)T - (m == x ? 1.0f : 0.0f),   grad_k = sum_m d_m * z^k_m,   v_k = v_k - rate * grad_k
+// the sum sequential in m, every product rounded on its own.  Thread m stages its logit of every member behind hs
+// (zs: [SB][1 + G][257] floats, the odd stride keeps the summing threads on different banks), the owner lane publishes x
+// through s_wave, thread m then writes d_m over the dead table, and one thread per (stream, model) pair sums that pair.  No
+// thread returns before the last barrier: the owner's step is a call here, not the end of the kernel.
+template <int SB, bool MIX = false>
+__global__ __launch_bounds__(256) void k_code_head(CodeHeadArgs a, long long t) {
+    HEAD_DYNAMIC_LDS(float, hs); // [N][SB]; MIX: then zs
+    __shared__ uint32_t tab[SB][260]; // the logits, then expf terms (as float), then cum_0 .. cum_256
+    __shared__ float s_zmax[SB], s_sum[SB];
+    __shared__ uint32_t s_wave[4][SB];
+    const int m = threadIdx.x, N = a.N, s0 = blockIdx.x * SB, lane = m & 63, wave = m >> 6;
+    bool act[SB]; // (the same in every thread)
+    bool need = false;
+    [[maybe_unused]] uint32_t qm[SB]; // MIX: q_m of every stream, kept for the update
+#pragma unroll
+    for (int j = 0; j < SB; j++) {
+        const int s = s0 + j;
+        act[j] = s < a.streams && (unsigned long long)t < a.text_off[s + 1] - a.text_off[s];
+        need |= act[j];
+    }
+    if (need) { // (uniform)
+        float *ps = reinterpret_cast<float *>(&tab[0][0]);
+        for (int i = m; i < N * SB; i += 256) {
+            const int k = i / SB, j = i - k * SB;
+            hs[i] = s0 + j < a.streams ? a.H[(size_t)(s0 + j) * N + k] : 0.0f;
+        }
+        __syncthreads();
+        float y[SB];
+#pragma unroll
+        for (int j = 0; j < SB; j++) y[j] = 0.0f;
+        for (int k0 = 0; k0 < N; k0 += 16) { // as k_gen_head: 16 loads in flight, the additions in k order
+            float wv[16];
+#pragma unroll
+            for (int i = 0; i < 16; i++) wv[i] = a.Why[(size_t)(k0 + i) * 256 + m];
+#pragma unroll
+            for (int i = 0; i < 16; i++)
+#pragma unroll
+                for (int j = 0; j < SB; j++) y[j] += wv[i] * hs[(k0 + i) * SB + j];
+        }
+        const float bym = a.by[m];
+#pragma unroll
+        for (int j = 0; j < SB; j++) {
+            y[j] = y[j] + bym; // the logit z
+            if constexpr (MIX)
+                if (act[j]) { // the members to zs; z becomes the mix under the stream's weights
+                    const int G = a.nguides;
+                    const size_t s = (size_t)(s0 + j);
+                    const float *vj = a.v + s * (G + 1);
+                    float *zj = hs + (size_t)N * SB + (size_t)j * (G + 1) * 257;
+                    zj[m] = y[j];
+                    float g = 0.0f;
+                    for (int k = 1; k <= G; k++) {
+                        const float zk = a.zk[(s * G + (k - 1)) * 256 + m];
+                        zj[k * 257 + m] = zk;
+                        const float term = vj[k] * zk;
+                        g = k == 1 ? term : g + term;
+                    }
+                    y[j] = vj[0] * y[j] + g;
+                }
+            ps[j * 260 + m] = y[j];
+        }
+        __syncthreads();
+        const bool own = m < SB && s0 + m < a.streams && (unsigned long long)t < a.text_off[s0 + m + 1] - a.text_off[s0 + m];
+        if (own) { // max z of stream m (every order gives the same max)
+            float best = ps[m * 260];
+            for (int i = 1; i < 256; i++)
+                if (ps[m * 260 + i] > best) best = ps[m * 260 + i];
+            s_zmax[m] = best;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < SB; j++)
+            if (act[j]) ps[j * 260 + m] = expf(y[j] - s_zmax[j]);
+        __syncthreads();
+        if (own) {
+            float s = 0.0f;
+            for (int i = 0; i < 256; i++) s += ps[m * 260 + i];
+            s_sum[m] = s;
+        }
+        __syncthreads();
+        // quantise; exclusive integer scan of q over the 256 threads (wave scan, then the wave totals through LDS)
+        uint32_t q[SB], incl[SB];
+#pragma unroll
+        for (int j = 0; j < SB; j++) {
+            const float v = ps[j * 260 + m] / s_sum[j] * 65024.0f; // p_m * 65024, in [0, 65024] (NaN: q = 1)
+            q[j] = act[j] ? 1u + (v >= 1.0f ? (uint32_t)v : 0u) : 1u;
+            int x = (int)q[j];
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const int o = __shfl_up(x, d, 64);
+                if (lane >= d) x += o;
+            }
+            incl[j] = (uint32_t)x;
+        }
+        if (lane == 63)
+#pragma unroll
+            for (int j = 0; j < SB; j++) s_wave[wave][j] = incl[j];
+        __syncthreads(); // (also: every read of the expf terms is done)
+#pragma unroll
+        for (int j = 0; j < SB; j++) {
+            uint32_t before = 0;
+            for (int w = 0; w < wave; w++) before += s_wave[w][j];
+            tab[j][m] = before + incl[j] - q[j];
+            if (m == 255) tab[j][256] = before + incl[j];
+            if constexpr (MIX) qm[j] = q[j];
+        }
+        __syncthreads();
+    }
+    code_owner_step<SB, MIX>(a, tab, s0, lane, wave, t, &s_wave[0][0]);
+    if constexpr (MIX) {
+        if (!need) return; // (uniform)
+        __syncthreads(); // (also: every owner is done with the table)
+        const int G1 = a.nguides + 1;
+        float *ds = reinterpret_cast<float *>(&tab[0][0]);
+        if (a.rate != 0.0f) { // (uniform)
+#pragma unroll
+            for (int j = 0; j < SB; j++)
+                if (act[j]) {
+                    const float T = (float)tab[j][256]; // (entry 256 is not overwritten)
+                    ds[j * 260 + m] = (float)qm[j] / T - (m == (int)s_wave[0][j] ? 1.0f : 0.0f);
+                }
+            __syncthreads();
+        }
+        if (m < SB * G1) { // one thread per (stream, model) pair
+            const int j = m / G1, k = m - j * G1, s = s0 + j;
+            if (s < a.streams && (unsigned long long)t < a.text_off[s + 1] - a.text_off[s]) {
+                const float v = a.v[(size_t)s * G1 + k];
+                if (a.w_trace) a.w_trace[(size_t)(a.text_off[s] + t) * G1 + k] = v;
+                if (a.rate != 0.0f) {
+                    const float *zj = hs + (size_t)N * SB + (size_t)m * 257;
+                    float grad = 0.0f;
+                    for (int i = 0; i < 256; i++) grad += ds[j * 260 + i] * zj[i];
+                    a.v[(size_t)s * G1 + k] = v - a.rate * grad;
+                }
+            }
+        }
+    }
 }

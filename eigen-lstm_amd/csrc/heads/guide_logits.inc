@@ -19,6 +19,9 @@
 // At the step where the head copies the main model's state to h_out / c_out -- the state after the stream's last input:
 // t == prompt length + the bytes it draws (the stop byte included), or t == the text's length -- every guide's state of that
 // stream goes to its h_out / c_out.  Streams that need nothing at this step are not computed and their rows of gsum not written.
+// Coder mode (a.coder; lstm_hip_encode_mixed / lstm_hip_decode_mixed, DESIGN.md section 3.25): a stream is active iff t < its
+// length, no state is copied out, and instead of the weighted sum each guide's own logits go to a.zk[(s * nguides + k) * 256 + m]
+// (the coder's weights are per stream, and its update needs the members); rows of streams that have ended are not written.
 // ------------------------------------------------------------------------------------------------
 template <int SB>
 __global__ __launch_bounds__(256) void k_guide_logits(GuideLogitsArgs a, long long t) {
@@ -35,7 +38,8 @@ __global__ __launch_bounds__(256) void k_guide_logits(GuideLogitsArgs a, long lo
         const int s = s0 + j;
         act[j] = fin[j] = false;
         if (s >= a.streams) continue;
-        if (a.scorer) {
+        if (a.coder) act[j] = (unsigned long long)t < a.off[s + 1] - a.off[s]; // (no end-state copy: fin stays false)
+        else if (a.scorer) {
             const unsigned long long len = a.off[s + 1] - a.off[s];
             act[j] = (unsigned long long)t < len && (t >= 1 || a.first);
             fin[j] = (unsigned long long)t == len;
@@ -98,7 +102,12 @@ __global__ __launch_bounds__(256) void k_guide_logits(GuideLogitsArgs a, long lo
             if (g == 0) gs[j] = w * y[j];
             else gs[j] = gs[j] + w * y[j];
         }
+        if (a.coder) // (uniform) the members themselves: the coder's weights are per stream, and its update needs them
+#pragma unroll
+            for (int j = 0; j < SB; j++)
+                if (act[j]) a.zk[((size_t)(s0 + j) * a.nguides + g) * 256 + m] = y[j];
     }
+    if (a.coder) return; // (uniform)
 #pragma unroll
     for (int j = 0; j < SB; j++)
         if (act[j]) a.gsum[(size_t)(s0 + j) * 256 + m] = gs[j];

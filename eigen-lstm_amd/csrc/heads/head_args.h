@@ -72,6 +72,10 @@ struct GuideLogitsArgs {
     int32_t *end;               // generator: GenHeadArgs::end, only read (always set: a guided draw is a processed one)
     int count;                  // generator: GenHeadArgs::count
     int first;                  // scorer: ScoreHeadArgs::first
+    // the mixed coder (lstm_hip_encode_mixed / lstm_hip_decode_mixed): off is the coder's text_off, a
+    // stream is active at step t iff t < its length, no state is copied out and gsum is not written; all 0 / null otherwise
+    int coder;                  // 1: the coder's streams
+    float *zk;                  // coder: [streams][nguides][256] every guide's own, unweighted logits of this step
 };
 
 // ---- beam search (lstm_hip_beam_search): per step beam_head on the state after t inputs, then
@@ -124,6 +128,13 @@ struct CodeHeadArgs {
     int32_t *x_next;            // the next input of every stream (-1: none)
     uint32_t *err;              // OR of CODE_ERR_*
     int N, streams, decode;
+    // the mixed coder (lstm_hip_encode_mixed / lstm_hip_decode_mixed): read only by the MIX
+    // instantiation, which code_head_mixed launches; all null / 0 in the unmixed call
+    const float *zk;            // [streams][nguides][256] the guides' logits of this step, written by k_guide_logits
+    float *v;                   // [streams][1 + nguides] each stream's weights: the call's at the start, rewritten after every byte
+    float *w_trace;             // encoder: [total][1 + nguides] the weights each byte was coded under, in text order (null: not kept)
+    int nguides;                // 1 .. MAX_GUIDES
+    float rate;                 // (float)rate: 0 leaves v alone
 };
 
 // ---- per-byte scores (lstm_hip_score): per step score_head on the state after t inputs (byte t of

@@ -497,6 +497,9 @@ hipError_t beam_head(const BeamHeadArgs &a, long long t, hipStream_t st);
 void beam_backtrack(const uint8_t *trace_parent, const uint8_t *trace_byte, const int32_t *len, uint8_t *out, int streams,
                     int W, int count, hipStream_t st);
 void code_head(const CodeHeadArgs &a, long long t, hipStream_t st);
+// the MIX instantiation (a.zk, a.v, a.nguides, a.rate set), behind guide_logits in coder mode: the table on
+// the mixed logits, the coder step, the weights' update.  hipSuccess, or the HIP error of a refused LDS request
+hipError_t code_head_mixed(const CodeHeadArgs &a, long long t, hipStream_t st);
 hipError_t score_head(const ScoreHeadArgs &a, long long t, bool stable, hipStream_t st); // stable: LSTM_HIP_STABLE_SOFTMAX
 
 // ---- adaptive coding (lstm_hip_encode_adaptive / lstm_hip_decode_adaptive): the training window of

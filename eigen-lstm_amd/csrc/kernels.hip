@@ -2217,6 +2217,26 @@ void code_head(const CodeHeadArgs &a, long long t, hipStream_t st) {
     }
 #undef CODE_HEAD_CASE
 }
+// the MIX instantiation: behind h of the group, the members' logits ([SB][1 + G][257] floats: up to 80 KB at SB = 16, G = 4)
+hipError_t code_head_mixed(const CodeHeadArgs &a, long long t, hipStream_t st) {
+    const int sb = gen_head_group(a.N, a.streams);
+    const size_t lds = ((size_t)sb * a.N + (size_t)sb * (a.nguides + 1) * 257) * sizeof(float);
+    const dim3 grid((a.streams + sb - 1) / sb);
+#define CODE_HEAD_MIXED_CASE(SB)                                                                                            \
+    case SB:                                                                                                                \
+        if (const hipError_t e = grant_lds<k_code_head<SB, true>, 32768>(lds)) return e;                                    \
+        hipLaunchKernelGGL((k_code_head<SB, true>), grid, dim3(256), lds, st, a, t);                                       \
+        break;
+    switch (sb) {
+        CODE_HEAD_MIXED_CASE(1)
+        CODE_HEAD_MIXED_CASE(2)
+        CODE_HEAD_MIXED_CASE(4)
+        CODE_HEAD_MIXED_CASE(8)
+        CODE_HEAD_MIXED_CASE(16)
+    }
+#undef CODE_HEAD_MIXED_CASE
+    return hipSuccess;
+}
 #include "heads/score_head.inc"
 template <bool STABLE, bool DETAIL, bool CONSTRAIN> static hipError_t score_head_launch(const ScoreHeadArgs &a, long long t, hipStream_t st) {
     const int sb = gen_head_group(a.N, a.streams);

@@ -178,6 +178,8 @@ enum KernelId {
     K_GRAD_ACCUMULATE,             // gradient accumulation (lstm_hip_set_grad_accumulation): a window's gradient into the accumulator
     K_COUNT_MORE, // ... and the ids from here on in kKernelNamesLast
     K_GUIDE_LOGITS = K_COUNT_MORE, // one step of the guides of a guided call (lstm_hip_generate_guided / lstm_hip_score_guided)
+    K_COUNT_LAST, // ... and the ids from here on in kKernelNamesMixed
+    K_CODE_HEAD_MIXED = K_COUNT_LAST, // one step of the mixed range coder (lstm_hip_encode_mixed / lstm_hip_decode_mixed)
     K_COUNT
 };
 const char *const kKernelNames[K_COUNT] = { // (K_COUNT_BASE names; the rows behind them stay null)
@@ -186,9 +188,13 @@ const char *const kKernelNames[K_COUNT] = { // (K_COUNT_BASE names; the rows beh
     "gemm_dU_halves", "grad_sumsq", "grad_norm", "adam", "code_head", "block_window", "text_window", "text_fold",
     "softmax_loss_dy_text", "beam_head", "beam_backtrack", "score_head"};
 const char *const kKernelNamesMore[K_COUNT_MORE - K_COUNT_BASE] = {"softmax_soft", "softmax_loss_dy_weighted", "grad_accumulate"};
-const char *const kKernelNamesLast[K_COUNT - K_COUNT_MORE] = {"guide_logits"};
+const char *const kKernelNamesLast[K_COUNT - K_COUNT_MORE] = {"guide_logits"}; // (K_COUNT_LAST - K_COUNT_MORE names)
+const char *const kKernelNamesMixed[K_COUNT - K_COUNT_LAST] = {"code_head_mixed"};
 inline const char *kernel_name(int id) {
-    return id < K_COUNT_BASE ? kKernelNames[id] : id < K_COUNT_MORE ? kKernelNamesMore[id - K_COUNT_BASE] : kKernelNamesLast[id - K_COUNT_MORE];
+    return id < K_COUNT_BASE   ? kKernelNames[id]
+           : id < K_COUNT_MORE ? kKernelNamesMore[id - K_COUNT_BASE]
+           : id < K_COUNT_LAST ? kKernelNamesLast[id - K_COUNT_MORE]
+                               : kKernelNamesMixed[id - K_COUNT_LAST];
 }
 
 // ---- RCCL, loaded on first use so single-GPU users never touch it --------------------------
@@ -3394,6 +3400,10 @@ int lstm_hip_embed_texts(lstm_hip_t *h, int32_t streams, const uint8_t *text, co
 // `code` at `code_off` in, `text` out.  A run is begun once, stepped over ranges of t that together cover [0, max_len) in
 // order (the static calls: one range), and finished once; the coder state of every stream, x_next and the H / C ping-pong
 // live on the device or in the run between ranges, so a pause between two ranges changes no code.
+// The mixed calls (lstm_hip_encode_mixed / lstm_hip_decode_mixed) fill r.gs ahead of coder_begin: the
+// guides' pieces, their logits zk, the streams' weights and the weight trace are then carved behind every piece of the unmixed
+// run, and per step guide_logits (coder mode), code_head_mixed in code_head's place, and one k_fwd_step per guide behind the
+// main model's.  With r.gs.count == 0 nothing of that is carved, uploaded or launched.
 struct CoderRun {
     CodeHeadArgs a{};
     bool decode = false;
@@ -3406,9 +3416,15 @@ struct CoderRun {
     float *H = nullptr, *Cs = nullptr, *G = nullptr;
     double *bits_prev = nullptr, *block_bits = nullptr; // adaptive calls: per-stream bits at the last fold, per-block totals
     int cur = 0;
+    Guides gs;                  // mixed calls: the guides (count == 0: an unmixed run)
+    GuideLogitsArgs ga{};
+    float *zk = nullptr;        // [streams][guides][256]
+    float rate = 0.0f;
+    std::vector<float> v0;      // the call's weights, once per stream
 };
 static int coder_begin(lstm_hip_t *h, CoderRun &r, bool decode, int32_t streams, const uint64_t *text_off, const uint8_t *text_in,
-                       const uint8_t *code_in, const uint64_t *code_off_in, bool want_trace, int64_t n_block_bits) {
+                       const uint8_t *code_in, const uint64_t *code_off_in, bool want_trace, int64_t n_block_bits,
+                       const lstm_hip_guidance *gd = nullptr, bool want_w_trace = false) {
     const int N = h->cfg.N;
     r.decode = decode;
     r.streams = streams;
@@ -3433,6 +3449,10 @@ static int coder_begin(lstm_hip_t *h, CoderRun &r, bool decode, int32_t streams,
     mem.piece(a.state, streams).piece(a.code_len, streams).piece(d_bits, streams);
     mem.piece(d_trace, 3 * total, want_trace).piece(a.err, 1);
     mem.piece(r.bits_prev, streams, n_block_bits != 0).piece(r.block_bits, n_block_bits, n_block_bits != 0);
+    const int G = r.gs.count;
+    guide_pieces(mem, r.gs, gd, streams);
+    mem.piece(r.zk, (size_t)256 * G * streams, G > 0).piece(a.v, (size_t)(1 + G) * streams, G > 0);
+    mem.piece(a.w_trace, (size_t)(1 + G) * total, G > 0 && want_w_trace && !decode);
     if (int rc = mem.commit(h)) return rc;
     r.cur = 0;
     r.m = model_of(h);
@@ -3459,6 +3479,22 @@ static int coder_begin(lstm_hip_t *h, CoderRun &r, bool decode, int32_t streams,
         HIP_TRY(hipMemsetAsync(r.bits_prev, 0, sizeof(double) * streams, h->st));
         HIP_TRY(hipMemsetAsync(r.block_bits, 0, sizeof(double) * n_block_bits, h->st));
     }
+    if (G) { // every guide from h = c = 0, its image of U; every stream's weights the call's
+        r.ga = GuideLogitsArgs{};
+        if (int rc = guides_begin(h, r.gs, gd, streams, r.ga)) return rc;
+        r.ga.off = d_toff;
+        r.ga.coder = 1;
+        r.ga.zk = r.zk;
+        a.zk = r.zk;
+        a.nguides = G;
+        a.rate = r.rate;
+        r.v0.resize((size_t)(1 + G) * streams);
+        for (int s = 0; s < streams; s++) {
+            r.v0[(size_t)s * (1 + G)] = r.gs.wmain;
+            for (int k = 0; k < G; k++) r.v0[(size_t)s * (1 + G) + 1 + k] = r.gs.r[k].w;
+        }
+        HIP_TRY(hipMemcpyAsync(a.v, r.v0.data(), sizeof(float) * r.v0.size(), hipMemcpyHostToDevice, h->st));
+    }
     return 0;
 }
 // steps t0 .. t1-1 with the current P: the image of U is remade first, then per step code_head and (except behind the last
@@ -3469,17 +3505,25 @@ static int coder_steps(lstm_hip_t *h, CoderRun &r, uint64_t t0, uint64_t t1) {
     RUN(K_PACK_U, pack_U(r.m.U, r.Ufwd, nullptr, h->cfg.N, h->st));
     for (long long t = (long long)t0; t < (long long)t1; t++) {
         r.a.H = r.H + r.cur * n;
-        RUN(K_CODE_HEAD, code_head(r.a, t, h->st));
+        if (r.gs.count) {
+            const char *what = r.decode ? "decode" : "encode";
+            if (int rc = guides_logits(h, what, r.gs, r.ga, r.cur, t)) return rc;
+            hipError_t refused = hipSuccess;
+            RUN(K_CODE_HEAD_MIXED, refused = code_head_mixed(r.a, t, h->st));
+            if (refused != hipSuccess) return head_refused(what, "code_head_mixed", refused);
+        } else
+            RUN(K_CODE_HEAD, code_head(r.a, t, h->st));
         if (t + 1 == (long long)r.max_len) break;
         if (int rc = step_columns(h, r.m, r.Ufwd, r.a.H, r.Cs + r.cur * n, r.H + (r.cur ^ 1) * n, r.Cs + (r.cur ^ 1) * n, r.G,
                                   r.a.x_next, r.streams))
             return rc;
+        if (int rc = guides_step(h, r.gs, r.cur, r.a.x_next, r.streams)) return rc;
         r.cur ^= 1;
     }
     return 0;
 }
 static int coder_finish(lstm_hip_t *h, CoderRun &r, uint8_t *text_out, uint8_t *code_out, uint64_t *code_off_out, double *bits,
-                        uint32_t *trace, double *block_bits, int64_t n_block_bits) {
+                        uint32_t *trace, double *block_bits, int64_t n_block_bits, float *w_out = nullptr, float *w_trace = nullptr) {
     const bool decode = r.decode;
     const int32_t streams = r.streams;
     const uint64_t total = r.total, code_bytes = r.code_bytes;
@@ -3498,6 +3542,9 @@ static int coder_finish(lstm_hip_t *h, CoderRun &r, uint8_t *text_out, uint8_t *
         if (block_bits && n_block_bits)
             HIP_TRY(hipMemcpyAsync(block_bits, r.block_bits, sizeof(double) * n_block_bits, hipMemcpyDeviceToHost, h->st));
     }
+    if (w_out) HIP_TRY(hipMemcpyAsync(w_out, a.v, sizeof(float) * (1 + r.gs.count) * streams, hipMemcpyDeviceToHost, h->st));
+    if (w_trace && total)
+        HIP_TRY(hipMemcpyAsync(w_trace, a.w_trace, sizeof(float) * (1 + r.gs.count) * total, hipMemcpyDeviceToHost, h->st));
     HIP_TRY(hipStreamSynchronize(h->st));
     if (err & CODE_ERR_TOTAL) return fail(LSTM_HIP_EINVAL, "%s: a frequency total passed 2^16 (the quantisation bound)", what);
     if (err & CODE_ERR_BOUND) return fail(LSTM_HIP_EINVAL, "%s: a code passed lstm_hip_code_bound", what);
@@ -3511,17 +3558,52 @@ static int coder_finish(lstm_hip_t *h, CoderRun &r, uint8_t *text_out, uint8_t *
     }
     return 0;
 }
+// the refusals the mixed calls add to the coders' own (include/lstm_hip.h); on success r holds the guides and the rate
+static int mix_checks(lstm_hip_t *h, const char *what, const lstm_hip_guidance *gd, const lstm_hip_mix_coding *mx, const float *w_out,
+                      const float *w_trace, CoderRun &r) {
+    if (!gd) {
+        if (mx) return fail(LSTM_HIP_EINVAL, "%s: mix coding given without guidance", what);
+        if (w_out || w_trace) return fail(LSTM_HIP_EINVAL, "%s: w_out / w_trace given without guidance", what);
+        return 0;
+    }
+    if (int rc = check_guidance(what, h, gd, r.gs)) return rc;
+    for (int k = 0; k < gd->nguides; k++) {
+        const lstm_hip_guide &u = gd->guides[k];
+        if (u.h0 || u.c0 || u.h_out || u.c_out)
+            return fail(LSTM_HIP_EINVAL, "%s: guide %d: h0, c0, h_out and c_out must be null (the coders start every model from zero)", what, k);
+    }
+    if (mx) {
+        if (mx->size != sizeof(lstm_hip_mix_coding))
+            return fail(LSTM_HIP_EINVAL, "%s: mix coding of %u bytes, expected %zu", what, mx->size, sizeof(lstm_hip_mix_coding));
+        if (!std::isfinite(mx->rate) || mx->rate < 0.0) return fail(LSTM_HIP_EINVAL, "%s: rate must be finite and >= 0 (got %g)", what, mx->rate);
+        r.rate = (float)mx->rate;
+    }
+    return 0;
+}
 static int run_coder(lstm_hip_t *h, bool decode, int32_t streams, const uint64_t *text_off, const uint8_t *text_in,
                      uint8_t *text_out, const uint8_t *code_in, const uint64_t *code_off_in, uint8_t *code_out,
-                     uint64_t *code_off_out, double *bits, uint32_t *trace) {
+                     uint64_t *code_off_out, double *bits, uint32_t *trace, const lstm_hip_guidance *gd = nullptr,
+                     const lstm_hip_mix_coding *mx = nullptr, float *w_out = nullptr, float *w_trace = nullptr) {
     CoderRun r;
-    if (int rc = coder_begin(h, r, decode, streams, text_off, text_in, code_in, code_off_in, trace != nullptr, 0)) return rc;
+    if (int rc = mix_checks(h, decode ? "decode" : "encode", gd, mx, w_out, w_trace, r)) return rc;
+    if (int rc = coder_begin(h, r, decode, streams, text_off, text_in, code_in, code_off_in, trace != nullptr, 0, gd, w_trace != nullptr))
+        return rc;
     if (int rc = coder_steps(h, r, 0, r.max_len)) return rc;
-    return coder_finish(h, r, text_out, code_out, code_off_out, bits, trace, nullptr, 0);
+    return coder_finish(h, r, text_out, code_out, code_off_out, bits, trace, nullptr, 0, w_out, w_trace);
 }
 
 int lstm_hip_encode(lstm_hip_t *h, int32_t streams, const uint8_t *text, const uint64_t *text_off, uint8_t *code,
                     uint64_t code_cap, uint64_t *code_off, double *bits, uint32_t *trace) {
+    return lstm_hip_encode_mixed(h, streams, text, text_off, code, code_cap, code_off, bits, trace, nullptr, nullptr, nullptr, nullptr);
+}
+
+// The mixed coders.  The coders' own refusals first, then the guidance's and the mix coding's
+// (mix_checks); with gd NULL every offset, upload and launch is lstm_hip_encode's / lstm_hip_decode's.
+uint32_t lstm_hip_mix_coder_version(void) { return 1; }
+
+int lstm_hip_encode_mixed(lstm_hip_t *h, int32_t streams, const uint8_t *text, const uint64_t *text_off, uint8_t *code,
+                          uint64_t code_cap, uint64_t *code_off, double *bits, uint32_t *trace, const lstm_hip_guidance *gd,
+                          const lstm_hip_mix_coding *mx, float *w_out, float *w_trace) {
     CHECK(h);
     if (streams < 1 || streams > 4096) return fail(LSTM_HIP_EINVAL, "encode: streams must be in [1, 4096] (got %d)", streams);
     if (int rc = check_offsets("encode", "text_off", text_off, streams)) return rc;
@@ -3538,11 +3620,16 @@ int lstm_hip_encode(lstm_hip_t *h, int32_t streams, const uint8_t *text, const u
                     (unsigned long long)code_cap, (unsigned long long)need);
     if (need > 0 && !code) return fail(LSTM_HIP_EINVAL, "encode: null code");
     if (h->cfg.N > 16384) return fail(LSTM_HIP_EINVAL, "encode: hidden width %d above 16384", h->cfg.N);
-    return run_coder(h, false, streams, text_off, text, nullptr, nullptr, nullptr, code, code_off, bits, trace);
+    return run_coder(h, false, streams, text_off, text, nullptr, nullptr, nullptr, code, code_off, bits, trace, gd, mx, w_out, w_trace);
 }
 
 int lstm_hip_decode(lstm_hip_t *h, int32_t streams, const uint8_t *code, const uint64_t *code_off, const uint64_t *text_off,
                     uint8_t *text) {
+    return lstm_hip_decode_mixed(h, streams, code, code_off, text_off, text, nullptr, nullptr, nullptr);
+}
+
+int lstm_hip_decode_mixed(lstm_hip_t *h, int32_t streams, const uint8_t *code, const uint64_t *code_off, const uint64_t *text_off,
+                          uint8_t *text, const lstm_hip_guidance *gd, const lstm_hip_mix_coding *mx, float *w_out) {
     CHECK(h);
     if (streams < 1 || streams > 4096) return fail(LSTM_HIP_EINVAL, "decode: streams must be in [1, 4096] (got %d)", streams);
     if (int rc = check_offsets("decode", "code_off", code_off, streams)) return rc;
@@ -3550,7 +3637,7 @@ int lstm_hip_decode(lstm_hip_t *h, int32_t streams, const uint8_t *code, const u
     if (code_off[streams] > 0 && !code) return fail(LSTM_HIP_EINVAL, "decode: null code with %llu code bytes", (unsigned long long)code_off[streams]);
     if (text_off[streams] > 0 && !text) return fail(LSTM_HIP_EINVAL, "decode: null text with %llu bytes to decode", (unsigned long long)text_off[streams]);
     if (h->cfg.N > 16384) return fail(LSTM_HIP_EINVAL, "decode: hidden width %d above 16384", h->cfg.N);
-    return run_coder(h, true, streams, text_off, nullptr, text, code, code_off, nullptr, nullptr, nullptr, nullptr);
+    return run_coder(h, true, streams, text_off, nullptr, text, code, code_off, nullptr, nullptr, nullptr, nullptr, gd, mx, w_out, nullptr);
 }
 
 // ---- adaptive coding: the model trains on the bytes it has coded (include/lstm_hip.h)

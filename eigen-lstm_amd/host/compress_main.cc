@@ -17,6 +17,20 @@
 //   | u64 FNV-1a of the logical parameter block (its float32 bytes) | u64 original length | u32 K | u32 CRC32 of the original
 //   | K x u64 code lengths | the K codes back to back
 //
+//   lstm_compress --load PREFIX --guide PREFIX2 [--guide-weight B] [--main-weight A] [--mix-rate R] (-c|-d) IN OUT [...]
+//
+// --guide (up to four, each with its own --guide-weight behind it) codes on a log-linear mix of the --load model and the guides'
+// (lstm_hip_encode_mixed / lstm_hip_decode_mixed): logits mixed with the weights A (default 0.5) and B
+// (default 0.5 each), and with --mix-rate R > 0 (default 0: fixed weights) every stream learns its weights from the bytes it
+// has coded.  --fast-math then applies to every model.  -d takes the same --load / --guide order, reads weights and rate from
+// the container and names the model whose parameters differ.  Without --guide nothing changes: the container is LHAC.
+//
+// Mixed container, little-endian, G guides:
+//   u32 magic "LHAM" | u32 format version | u32 coder version | u32 mix coder version | u32 1 + G
+//   | (1 + G) x (u32 N | u32 flags (LSTM_HIP_FAST_MATH or 0) | u64 FNV-1a of the model's logical parameter block), main model first
+//   | (1 + G) x u32 weight (the float's bits), main model first | u32 rate (the float's bits)
+//   | u64 original length | u32 K | u32 CRC32 of the original | K x u64 code lengths | the K codes back to back
+//
 //   lstm_compress --adapt (-c|-d) IN OUT [--hidden N --seq S --streams B --lr X --seed K --optimizer adagrad|adam
 //                 --adam-betas B1,B2 --adam-eps E --weight-decay W --clip-norm X --stable-softmax --bf16 --fast-math
 //                 --load PREFIX --device D]
@@ -48,6 +62,9 @@
 namespace {
 
 const char *const kUsage = "usage: lstm_compress --load PREFIX (-c|-d) IN OUT [--streams K] [--fast-math] [--device D]\n"
+                            "       lstm_compress --load PREFIX --guide PREFIX2 [--guide-weight B] [--main-weight A] [--mix-rate R]\n"
+                            "                     (-c|-d) IN OUT [--streams K] [--fast-math] [--device D]   (up to 4 --guide;\n"
+                            "                     -d: the same --load / --guide order, weights and rate from the container)\n"
                             "       lstm_compress --adapt (-c|-d) IN OUT [--hidden N --seq S --streams B --lr X --seed K\n"
                             "                     --optimizer adagrad|adam --adam-betas B1,B2 --adam-eps E --weight-decay W\n"
                             "                     --clip-norm X --stable-softmax --bf16 --fast-math\n"
@@ -55,6 +72,8 @@ const char *const kUsage = "usage: lstm_compress --load PREFIX (-c|-d) IN OUT [-
 constexpr uint32_t kMagic = 0x4341484Cu; // "LHAC"
 constexpr uint32_t kFormat = 1;
 constexpr size_t kHeader = 44;
+constexpr uint32_t kMagicMixed = 0x4D41484Cu; // "LHAM"
+constexpr uint32_t kFormatMixed = 1;
 constexpr uint32_t kMagicAdaptive = 0x4441484Cu; // "LHAD"
 constexpr uint32_t kFormatAdaptive = 1;
 constexpr size_t kHeaderAdaptive = 312, kNameBytes = 64, kPlanBytes = 128;
@@ -99,6 +118,11 @@ struct Options {
     double lr = 0.05, beta1 = 0.9, beta2 = 0.999, adam_eps = 1e-8, weight_decay = 0.0, clip_norm = 0.0;
     bool adam = false;
     std::string adam_opt; // the last Adam option given (refused without --optimizer adam)
+    // --guide
+    std::vector<std::string> guides;
+    std::vector<double> guide_weights; // one per guide
+    double main_weight = 0.5, mix_rate = 0.0;
+    std::string mix_opt; // the last option given that only --guide -c takes
 };
 
 double parse_double(const std::string &opt, const std::string &v, double lo, bool lo_open, double hi, bool inf_ok) {
@@ -141,6 +165,16 @@ Options parse(int argc, char **argv) {
         else if (a == "--device") o.device = parse_int(a, val(), 0, 1 << 20);
         else if (a == "--fast-math") o.flags |= LSTM_HIP_FAST_MATH;
         else if (a == "--adapt") o.adapt = true;
+        else if (a == "--guide") {
+            if (o.guides.size() == LSTM_HIP_MAX_GUIDES) usage("at most " + std::to_string(LSTM_HIP_MAX_GUIDES) + " --guide");
+            o.guides.push_back(val());
+            o.guide_weights.push_back(0.5);
+        } else if (a == "--guide-weight") {
+            const double w = parse_double(o.mix_opt = a, val(), -INFINITY, false, INFINITY, false);
+            if (o.guides.empty()) usage("--guide-weight stands behind the --guide it belongs to");
+            o.guide_weights.back() = w;
+        } else if (a == "--main-weight") o.main_weight = parse_double(o.mix_opt = a, val(), -INFINITY, false, INFINITY, false);
+        else if (a == "--mix-rate") o.mix_rate = parse_double(o.mix_opt = a, val(), 0.0, false, INFINITY, false);
         else if (a == "--hidden") o.N = parse_int(o.model_opt = a, val(), 1, 16384);
         else if (a == "--seq") o.S = parse_int(o.model_opt = a, val(), 2, 1 << 16);
         else if (a == "--seed") o.seed = (uint32_t)parse_int(o.model_opt = a, val(), 0, 0xFFFFFFFFl);
@@ -171,6 +205,9 @@ Options parse(int argc, char **argv) {
         if (o.load.empty()) usage("--load PREFIX is required");
     }
     if (!o.mode) usage("nothing to do: give -c or -d");
+    if (o.adapt && !o.guides.empty()) usage("--guide needs --load without --adapt (the adaptive coders take no guides)");
+    if (o.guides.empty() && !o.mix_opt.empty()) usage(o.mix_opt + " needs --guide");
+    if (o.mode == 'd' && !o.mix_opt.empty()) usage(o.mix_opt + " is read from the container with -d");
     if (o.adapt && o.mode == 'd' && !o.model_opt.empty()) usage(o.model_opt + " is read from the container with -d");
     if (!o.adam_opt.empty() && !o.adam) usage(o.adam_opt + " needs --optimizer adam");
     if (o.mode == 'd' && o.streams) usage("--streams is read from the container with -d");
@@ -308,6 +345,8 @@ void decompress(const Options &o) {
     if (!read_file(o.in, in)) die("cannot read " + o.in);
     if (in.size() >= 4 && get32(&in[0]) == kMagicAdaptive)
         die(o.in + ": an adaptive lstm_compress file (LHAD): decode it with --adapt -d");
+    if (in.size() >= 4 && get32(&in[0]) == kMagicMixed)
+        die(o.in + ": a mixed lstm_compress file (LHAM): decode it with --load PREFIX --guide PREFIX2 -d");
     if (in.size() < kHeader) die(o.in + ": truncated header (" + std::to_string(in.size()) + " bytes)");
     if (get32(&in[0]) != kMagic) die(o.in + ": not an lstm_compress file (bad magic)");
     if (get32(&in[4]) != kFormat) die(o.in + ": container format " + std::to_string(get32(&in[4])) + ", this program reads " + std::to_string(kFormat));
@@ -338,6 +377,166 @@ void decompress(const Options &o) {
     lstm_hip_t *h = make_handle(Nc, P, flags, o.device);
     CK(lstm_hip_decode(h, (int32_t)K, in.data() + kHeader + 8ull * K, code_off.data(), text_off.data(), text.data()));
     CK(lstm_hip_destroy(h));
+    text.resize(len);
+    if (crc32(text) != crc) die(o.in + ": CRC32 of the decoded text differs; " + o.out + " not written");
+    write_file(o.out, text);
+}
+
+// ---- --guide -------------------------------------------------------------------------------------------------------------
+uint32_t fbits(float x) {
+    uint32_t u;
+    memcpy(&u, &x, 4);
+    return u;
+}
+float bits_to_float(uint32_t u) {
+    float x;
+    memcpy(&x, &u, 4);
+    return x;
+}
+struct MixedModels { // the --load model, then the guides in their order
+    std::vector<std::string> prefix;
+    std::vector<std::vector<float>> P;
+    std::vector<int> N;
+    std::vector<lstm_hip_t *> h;
+    std::vector<lstm_hip_guide> guide;
+    lstm_hip_guidance gd{};
+    lstm_hip_mix_coding mx{};
+};
+void load_mixed(const Options &o, MixedModels &m) {
+    m.prefix.push_back(o.load);
+    m.prefix.insert(m.prefix.end(), o.guides.begin(), o.guides.end());
+    m.P.resize(m.prefix.size());
+    for (size_t k = 0; k < m.prefix.size(); k++) m.N.push_back(load_model(m.prefix[k], m.P[k]));
+}
+// the handles and the two blocks of the call: weights[0] the main model's
+void open_mixed(MixedModels &m, unsigned flags, long device, const std::vector<float> &weights, float rate) {
+    for (size_t k = 0; k < m.prefix.size(); k++) m.h.push_back(make_handle(m.N[k], m.P[k], flags, device));
+    for (size_t k = 1; k < m.h.size(); k++) m.guide.push_back(lstm_hip_guide{m.h[k], (double)weights[k], nullptr, nullptr, nullptr, nullptr});
+    m.gd = lstm_hip_guidance{sizeof(lstm_hip_guidance), (double)weights[0], (int32_t)m.guide.size(), m.guide.data()};
+    m.mx = lstm_hip_mix_coding{sizeof(lstm_hip_mix_coding), (double)rate};
+}
+void close_mixed(MixedModels &m) {
+    for (lstm_hip_t *h : m.h) CK(lstm_hip_destroy(h));
+}
+
+void compress_mixed(const Options &o) {
+    std::vector<uint8_t> text;
+    if (!read_file(o.in, text)) die("cannot read " + o.in);
+    MixedModels m;
+    load_mixed(o, m);
+    const uint64_t len = text.size();
+    long K = o.streams;
+    if (K == 0) K = (long)std::min<uint64_t>(kDefaultMaxStreams, std::max<uint64_t>(1, len / kBytesPerStream));
+    std::vector<uint64_t> off(K + 1);
+    for (long s = 0; s <= K; s++) off[s] = (uint64_t)((unsigned __int128)s * len / (unsigned)K);
+    uint64_t cap = 0;
+    for (long s = 0; s < K; s++) cap += lstm_hip_code_bound(off[s + 1] - off[s]);
+    std::vector<uint8_t> code(cap ? cap : 1);
+    std::vector<uint64_t> code_off(K + 1);
+    std::vector<double> bits(K);
+    std::vector<float> weights{(float)o.main_weight}; // narrowed here, as the library narrows them: the container holds what was used
+    for (double w : o.guide_weights) weights.push_back((float)w);
+    const float rate = (float)o.mix_rate;
+    const size_t G1 = weights.size();
+    std::vector<float> w_out((size_t)K * G1);
+    open_mixed(m, o.flags, o.device, weights, rate);
+    CK(lstm_hip_encode_mixed(m.h[0], (int32_t)K, text.data(), off.data(), code.data(), cap, code_off.data(), bits.data(), nullptr, &m.gd,
+                             &m.mx, w_out.data(), nullptr));
+    close_mixed(m);
+
+    std::vector<uint8_t> out;
+    put32(out, kMagicMixed);
+    put32(out, kFormatMixed);
+    put32(out, lstm_hip_coder_version());
+    put32(out, lstm_hip_mix_coder_version());
+    put32(out, (uint32_t)G1);
+    for (size_t k = 0; k < G1; k++) {
+        put32(out, (uint32_t)m.N[k]);
+        put32(out, o.flags & LSTM_HIP_FAST_MATH);
+        put64(out, fnv1a(m.P[k]));
+    }
+    for (float w : weights) put32(out, fbits(w));
+    put32(out, fbits(rate));
+    put64(out, len);
+    put32(out, (uint32_t)K);
+    put32(out, crc32(text));
+    for (long s = 0; s < K; s++) put64(out, code_off[s + 1] - code_off[s]);
+    out.insert(out.end(), code.begin(), code.begin() + code_off[K]);
+    write_file(o.out, out);
+    double sum = 0.0;
+    for (double b : bits) sum += b;
+    const double n = len ? (double)len : 1.0;
+    printf("in %llu bytes, out %zu bytes, code %llu bytes in %ld streams, %zu models: %.5f bits/char (model %.5f bits/char)\n",
+           (unsigned long long)len, out.size(), (unsigned long long)code_off[K], K, G1, 8.0 * (double)code_off[K] / n, sum / n);
+    if (rate > 0.0f)
+        for (size_t k = 0; k < G1; k++) { // the range of the streams' final weights, per model
+            float lo = w_out[k], hi = w_out[k];
+            for (long s = 1; s < K; s++) lo = std::min(lo, w_out[s * G1 + k]), hi = std::max(hi, w_out[s * G1 + k]);
+            printf("model %zu: weight %g, final %g .. %g\n", k, (double)weights[k], (double)lo, (double)hi);
+        }
+}
+
+void decompress_mixed(const Options &o) {
+    std::vector<uint8_t> in;
+    if (!read_file(o.in, in)) die("cannot read " + o.in);
+    if (in.size() >= 4 && get32(&in[0]) == kMagic) die(o.in + ": a static lstm_compress file (LHAC), coded without guides: decode it without --guide");
+    if (in.size() >= 4 && get32(&in[0]) == kMagicAdaptive) die(o.in + ": an adaptive lstm_compress file (LHAD): decode it with --adapt -d");
+    if (in.size() < 20) die(o.in + ": truncated header (" + std::to_string(in.size()) + " bytes)");
+    if (get32(&in[0]) != kMagicMixed) die(o.in + ": not a mixed lstm_compress file (bad magic)");
+    if (get32(&in[4]) != kFormatMixed) die(o.in + ": container format " + std::to_string(get32(&in[4])) + ", this program reads " + std::to_string(kFormatMixed));
+    if (get32(&in[8]) != lstm_hip_coder_version())
+        die(o.in + ": coder version " + std::to_string(get32(&in[8])) + ", this library codes version " + std::to_string(lstm_hip_coder_version()));
+    if (get32(&in[12]) != lstm_hip_mix_coder_version())
+        die(o.in + ": mix coder version " + std::to_string(get32(&in[12])) + ", this library codes version " +
+            std::to_string(lstm_hip_mix_coder_version()));
+    const uint32_t G1 = get32(&in[16]);
+    if (G1 < 2 || G1 > 1 + LSTM_HIP_MAX_GUIDES) die(o.in + ": model count " + std::to_string(G1) + " outside [2, " + std::to_string(1 + LSTM_HIP_MAX_GUIDES) + "]");
+    if (G1 != 1 + o.guides.size())
+        die(o.in + ": coded with " + std::to_string(G1 - 1) + " guides, " + std::to_string(o.guides.size()) + " given with --guide");
+    const size_t header = 20 + 16ull * G1 + 4ull * G1 + 4 + 16;
+    if (in.size() < header) die(o.in + ": truncated header (" + std::to_string(in.size()) + " bytes)");
+    const uint8_t *at = &in[20 + 16ull * G1];
+    std::vector<float> weights;
+    for (uint32_t k = 0; k < G1; k++) weights.push_back(bits_to_float(get32(at + 4 * k)));
+    at += 4ull * G1;
+    const float rate = bits_to_float(get32(at));
+    const uint64_t len = get64(at + 4);
+    const uint32_t K = get32(at + 12), crc = get32(at + 16);
+    for (float w : weights)
+        if (!std::isfinite(w)) die(o.in + ": corrupt weight");
+    if (!std::isfinite(rate) || rate < 0.0f) die(o.in + ": corrupt mix rate");
+    if (K < 1 || K > 4096) die(o.in + ": stream count " + std::to_string(K) + " outside [1, 4096]");
+    if (in.size() < header + 8ull * K) die(o.in + ": truncated header (" + std::to_string(in.size()) + " bytes)");
+    std::vector<uint64_t> code_off(K + 1, 0), text_off(K + 1);
+    for (uint32_t s = 0; s < K; s++) {
+        const uint64_t n = get64(&in[header + 8 * s]);
+        if (n > in.size()) die(o.in + ": corrupt code length");
+        code_off[s + 1] = code_off[s] + n;
+    }
+    if (code_off[K] != in.size() - header - 8ull * K)
+        die(o.in + ": " + std::to_string(in.size() - header - 8ull * K) + " code bytes, the header says " + std::to_string(code_off[K]));
+    for (uint32_t s = 0; s <= K; s++) text_off[s] = (uint64_t)((unsigned __int128)s * len / K);
+
+    MixedModels m;
+    load_mixed(o, m);
+    uint32_t flags = 0;
+    for (uint32_t k = 0; k < G1; k++) { // every model against its record, before any handle is made
+        const uint8_t *rec = &in[20 + 16ull * k];
+        const std::string who = k == 0 ? "the --load model " + m.prefix[k] : "guide " + std::to_string(k) + " (" + m.prefix[k] + ")";
+        if (get32(rec + 4) & ~LSTM_HIP_FAST_MATH) die(o.in + ": unknown flags " + std::to_string(get32(rec + 4)));
+        if (k == 0) flags = get32(rec + 4);
+        else if (get32(rec + 4) != flags) die(o.in + ": the models' flags differ");
+        if (get32(rec) != (uint32_t)m.N[k])
+            die(o.in + ": model " + std::to_string(k) + " was coded with a hidden size of " + std::to_string(get32(rec)) + ", " + who + " has " +
+                std::to_string(m.N[k]));
+        if (get64(rec + 8) != fnv1a(m.P[k]))
+            die(o.in + ": model " + std::to_string(k) + " was coded with other parameters than " + who + " (parameter hash differs)");
+    }
+    std::vector<uint8_t> text(len ? len : 1);
+    open_mixed(m, flags, o.device, weights, rate);
+    CK(lstm_hip_decode_mixed(m.h[0], (int32_t)K, in.data() + header + 8ull * K, code_off.data(), text_off.data(), text.data(), &m.gd, &m.mx,
+                             nullptr));
+    close_mixed(m);
     text.resize(len);
     if (crc32(text) != crc) die(o.in + ": CRC32 of the decoded text differs; " + o.out + " not written");
     write_file(o.out, text);
@@ -454,6 +653,8 @@ void decompress_adaptive(const Options &o) {
     std::vector<uint8_t> in;
     if (!read_file(o.in, in)) die("cannot read " + o.in);
     if (in.size() >= 4 && get32(&in[0]) == kMagic) die(o.in + ": a static lstm_compress file (LHAC): decode it with --load PREFIX -d");
+    if (in.size() >= 4 && get32(&in[0]) == kMagicMixed)
+        die(o.in + ": a mixed lstm_compress file (LHAM): decode it with --load PREFIX --guide PREFIX2 -d");
     if (in.size() < kHeaderAdaptive) die(o.in + ": truncated header (" + std::to_string(in.size()) + " bytes)");
     if (get32(&in[0]) != kMagicAdaptive) die(o.in + ": not an adaptive lstm_compress file (bad magic)");
     if (get32(&in[4]) != kFormatAdaptive)
@@ -523,6 +724,11 @@ int main(int argc, char **argv) {
     if (o.adapt) {
         if (o.mode == 'c') compress_adaptive(o);
         else decompress_adaptive(o);
+        return 0;
+    }
+    if (!o.guides.empty()) {
+        if (o.mode == 'c') compress_mixed(o);
+        else decompress_mixed(o);
         return 0;
     }
     if (o.mode == 'c') compress(o);

@@ -71,6 +71,10 @@ class _Guidance(C.Structure):  # lstm_hip_guidance
     _fields_ = [("size", C.c_uint32), ("main_weight", C.c_double), ("nguides", C.c_int32), ("guides", C.POINTER(_Guide))]
 
 
+class _MixCoding(C.Structure):  # lstm_hip_mix_coding
+    _fields_ = [("size", C.c_uint32), ("rate", C.c_double)]
+
+
 class _Scoring(C.Structure):  # lstm_hip_scoring
     _fields_ = [("size", C.c_uint32), ("first", C.c_int32), ("top_n", C.c_int32), ("con", C.POINTER(_Constraint))]
 
@@ -131,6 +135,7 @@ SYMBOLS = [
     "lstm_hip_generate_processed",
     "lstm_hip_embed_texts",
     "lstm_hip_generate_guided", "lstm_hip_score_guided",
+    "lstm_hip_mix_coder_version", "lstm_hip_encode_mixed", "lstm_hip_decode_mixed",
 ]
 
 
@@ -162,6 +167,9 @@ def load_library():
         lib.lstm_hip_text_plan.restype = C.c_int64
         lib.lstm_hip_text_plan.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_int32),
                                            C.POINTER(C.c_int64)]
+    if hasattr(lib, "lstm_hip_mix_coder_version"):
+        lib.lstm_hip_mix_coder_version.restype = C.c_uint32
+        lib.lstm_hip_mix_coder_version.argtypes = []
     _lib = lib
     return lib
 
@@ -385,6 +393,20 @@ def _guidance(guides, main_weight, streams):
         arr[k] = _Guide(model._h.value, float(weight), _ptr(hh) if hh is not None else None, _ptr(cc) if cc is not None else None,
                         _ptr(gh[k]), _ptr(gc[k]))
     return _Guidance(C.sizeof(_Guidance), float(main_weight), len(items), arr), gh, gc, alive
+
+
+def _coder_guidance(guides, main_weight):
+    """the lstm_hip_guidance block of the mixed coders, guides = [(model, weight), ...]: no states in or out (every model
+    starts from zero).  (block, what has to stay alive until the call returns)"""
+    items = [tuple(g) for g in guides]
+    arr = (_Guide * max(len(items), 1))()
+    for k, (model, weight) in enumerate(items):
+        arr[k] = _Guide(model._h.value, float(weight), None, None, None, None)
+    return _Guidance(C.sizeof(_Guidance), float(main_weight), len(items), arr), arr
+
+
+def mix_coder_version():
+    return int(load_library().lstm_hip_mix_coder_version())
 
 
 def device_info(device=0):
@@ -1154,6 +1176,65 @@ class Lstm:
         _chk(self.lib.lstm_hip_decode(self._h, C.c_int32(streams), _ptr(data, C.c_uint8), _ptr(code_off, C.c_uint64),
                                       _ptr(text_off, C.c_uint64), _ptr(text, C.c_uint8)))
         return [text[int(text_off[s]):int(text_off[s + 1])].tobytes() for s in range(streams)]
+
+    def encode_mixed(self, texts, guides=None, main_weight=1.0, rate=0.0, trace=False, weights=False):
+        """lstm_hip_encode_mixed: lstm_hip_encode on the log-linear mix of this model (weight main_weight) and
+        guides = [(model, weight), ...]; with rate > 0 every stream learns its weights from the bytes it has coded.  Returns
+        (codes, bits), then with trace the uint32 [total, 3] table entries, then with weights the float32 [streams, 1 + G]
+        final weights and the float32 [total, 1 + G] weights each byte was coded under.  guides None: the call passes no
+        guidance and no mix coding, which is lstm_hip_encode exactly (weights is then refused by the library)."""
+        parts = _bytes_list(texts)
+        streams = len(parts)
+        data, off = _offsets(parts)
+        total = int(off[-1])
+        cap = sum(code_bound(q.size) for q in parts)
+        code = np.zeros(max(cap, 1), np.uint8)
+        code_off = np.zeros(streams + 1, np.uint64)
+        bits = np.zeros(streams, np.float64)
+        tr = np.zeros((max(total, 1), 3), np.uint32) if trace else None
+        G1 = 1 + (len(guides) if guides is not None else 0)
+        w_out = np.zeros((streams, G1), np.float32) if weights else None
+        w_tr = np.zeros((max(total, 1), G1), np.float32) if weights else None
+        gd = mx = alive = None
+        if guides is not None:
+            gd, alive = _coder_guidance(guides, main_weight)
+            mx = _MixCoding(C.sizeof(_MixCoding), float(rate))
+        _chk(self.lib.lstm_hip_encode_mixed(self._h, C.c_int32(streams), _ptr(data, C.c_uint8), _ptr(off, C.c_uint64),
+                                            _ptr(code, C.c_uint8), C.c_uint64(cap), _ptr(code_off, C.c_uint64),
+                                            _ptr(bits, C.c_double), _ptr(tr, C.c_uint32) if trace else None,
+                                            C.byref(gd) if gd is not None else None, C.byref(mx) if mx is not None else None,
+                                            _ptr(w_out) if weights else None, _ptr(w_tr) if weights else None))
+        del alive
+        res = ([code[int(code_off[s]):int(code_off[s + 1])].tobytes() for s in range(streams)], bits)
+        if trace:
+            res += (tr[:total],)
+        if weights:
+            res += (w_out, w_tr[:total])
+        return res
+
+    def decode_mixed(self, codes, lengths, guides=None, main_weight=1.0, rate=0.0, weights=False):
+        """lstm_hip_decode_mixed: stream s decodes `lengths[s]` bytes from codes[s] under the same models, weights and rate
+        as lstm_hip_encode_mixed.  Returns a list of bytes, and with weights the float32 [streams, 1 + G] final weights."""
+        parts = _bytes_list(codes)
+        streams = len(parts)
+        assert len(lengths) == streams, (len(lengths), streams)
+        data, code_off = _offsets(parts)
+        text_off = np.zeros(streams + 1, np.uint64)
+        text_off[1:] = np.cumsum([int(n) for n in lengths])
+        text = np.zeros(max(int(text_off[-1]), 1), np.uint8)
+        G1 = 1 + (len(guides) if guides is not None else 0)
+        w_out = np.zeros((streams, G1), np.float32) if weights else None
+        gd = mx = alive = None
+        if guides is not None:
+            gd, alive = _coder_guidance(guides, main_weight)
+            mx = _MixCoding(C.sizeof(_MixCoding), float(rate))
+        _chk(self.lib.lstm_hip_decode_mixed(self._h, C.c_int32(streams), _ptr(data, C.c_uint8), _ptr(code_off, C.c_uint64),
+                                            _ptr(text_off, C.c_uint64), _ptr(text, C.c_uint8),
+                                            C.byref(gd) if gd is not None else None, C.byref(mx) if mx is not None else None,
+                                            _ptr(w_out) if weights else None))
+        del alive
+        out = [text[int(text_off[s]):int(text_off[s + 1])].tobytes() for s in range(streams)]
+        return (out, w_out) if weights else out
 
     def encode_adaptive(self, texts, lr, trace=False):
         """lstm_hip_encode_adaptive: the handle's B streams coded block by block, the model trained on every block after it

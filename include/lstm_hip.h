@@ -771,7 +771,8 @@ int lstm_hip_generate_processed(lstm_hip_t *h, int32_t streams, const uint8_t *p
  *                   synchronised.  A guide may not be used by another host thread during the call.
  *        cost       per step one more launch for all guides together (their logits and the mix) and one recurrence step per guide;
  *                   the guides' images of U, states and the sum live in the MAIN handle's working memory.
- *      Beam search, the coders, lstm_hip_sample, lstm_hip_eval_texts and lstm_hip_embed_texts take no guides.
+ *      Beam search, the adaptive coders, lstm_hip_sample, lstm_hip_eval_texts and lstm_hip_embed_texts take no guides; the
+ *      static coders take them through lstm_hip_encode_mixed / lstm_hip_decode_mixed (below).
  *      LSTM_HIP_EINVAL (the handle stays usable, nothing is launched; the message names the guide's index), beside those of the
  *      unguided call, which come first: gd->size wrong; nguides outside 1..LSTM_HIP_MAX_GUIDES; guides NULL; main_weight or a
  *      weight NaN or infinite; a NULL model; a guide on another device; a guide whose internal width is above 16384.
@@ -1066,6 +1067,56 @@ int lstm_hip_encode(lstm_hip_t *h, int32_t streams, const uint8_t *text, const u
  * the container, not to the code) and where it goes in text.  A truncated code decodes to the requested length. */
 int lstm_hip_decode(lstm_hip_t *h, int32_t streams, const uint8_t *code, const uint64_t *code_off, const uint64_t *text_off,
                     uint8_t *text);
+
+/* ---- mixed coding: the static coder on a log-linear mix of several models' logits, the mixing
+ *      weights fixed or learned online, per stream, from the bytes already coded.  Models 0..G are the main handle (index 0)
+ *      and the G guides of gd in index order, G = 1..LSTM_HIP_MAX_GUIDES.  Everything lstm_hip_encode / lstm_hip_decode
+ *      document holds, except what follows.
+ *        states    every model starts every stream from h = c = 0 and is fed the coded bytes, each through its own W, U, b
+ *                  in the same steps, exactly as the guides of lstm_hip_score_guided are fed: the block a guide's
+ *                  lstm_hip_set_inference_source names is read, its LSTM_HIP_FAST_MATH applies to its recurrence, weight drop
+ *                  never applies.  Nothing of a guide is written; model == h is allowed.
+ *        logits    byte j of a stream is coded under z^k = Why_k*h_k + by_k of the states after inputs 0..j-1, each summed as
+ *                  every head sums it (sequentially in the hidden index, multiply and add separately rounded, by added last).
+ *        weights   a stream carries v[0..G], float, initialised to ((float)main_weight, (float)weight_1, .., (float)weight_G).
+ *        mix       g_m = v_1*z^1_m, then g_m = g_m + v_k*z^k_m for k = 2.. in index order, then z'_m = v_0*z^0_m + g_m.  Every
+ *                  multiply and every add is one fp32 operation, no contraction.
+ *        table     exactly lstm_hip_encode's, built on z': p_m = expf(z'_m - max z') / s with s summed in index order,
+ *                  q_m = 1 + (uint32)(p_m * 65024.0f), T = sum_m q_m, cum_m = sum_{k<m} q_k; the same coder, flush and
+ *                  lstm_hip_code_bound.  Weights that have become NaN or infinite give the flat table (every q = 1) on both
+ *                  sides, never a corrupt code.
+ *        learning  (rate > 0) after byte x of the stream has been coded or decoded, the stream's last byte included:
+ *                    d_m    = (float)q_m / (float)T - (m == x ? 1.0f : 0.0f)
+ *                    grad_k = SUM_m d_m * z^k_m      the sequential float sum in index order of separately rounded products
+ *                    v_k   <- v_k - (float)rate * grad_k              for k = 0..G, one multiply and one subtraction
+ *                  d is the gradient of the byte's code length (in nats) under the QUANTISED table with respect to z', so
+ *                  nothing transcendental enters the update and the decoder holds everything it needs when it needs it.
+ *                  rate == 0 skips the update: v stays the call's weights, and the call is a fixed log-linear mix.
+ *      gd == NULL: mx, w_out and w_trace must be NULL too, and the call is lstm_hip_encode / lstm_hip_decode exactly, with its
+ *      scratch offsets, launches and bytes (those two are thin callers of the functions below).  mx == NULL with gd: rate 0.
+ *      w_out (may be NULL): [streams][1+G], every stream's weights after its last byte (the call's weights for an empty
+ *      stream); the decoder's equal the encoder's bit for bit.  w_trace (encoder, may be NULL): [total][1+G], the weights each
+ *      byte was coded under, in text order; row 0 of a stream is the call's weights.  bits and trace are those of the mix.
+ *      A code decodes only with the same lstm_hip_coder_version AND lstm_hip_mix_coder_version (bumped whenever the mix, the
+ *      update or their order change a code), the same parameters and LSTM_HIP_FAST_MATH setting of every model in the same
+ *      order, the same weights and the same rate.  The adaptive coders take no guides.
+ *      LSTM_HIP_EINVAL (nothing is launched), after everything lstm_hip_encode / lstm_hip_decode refuse, in their words:
+ *      everything a guidance block is refused for (lstm_hip_score_guided); a guide with a non-NULL h0, c0, h_out or c_out (the
+ *      coders start every model from zero); mx->size wrong; rate negative, NaN or infinite; mx, w_out or w_trace without gd.
+ *      LSTM_HIP_EHIP: the device refused an LDS request of the guides' kernel or of the mixed head (nothing of that step is
+ *      launched). */
+typedef struct lstm_hip_mix_coding {
+    uint32_t size;              /* sizeof(lstm_hip_mix_coding); anything else: LSTM_HIP_EINVAL */
+    double rate;                /* >= 0, finite; 0: fixed weights */
+} lstm_hip_mix_coding;
+uint32_t lstm_hip_mix_coder_version(void);
+int lstm_hip_encode_mixed(lstm_hip_t *h, int32_t streams, const uint8_t *text, const uint64_t *text_off, uint8_t *code,
+                          uint64_t code_cap, uint64_t *code_off, double *bits, uint32_t *trace, const lstm_hip_guidance *gd,
+                          const lstm_hip_mix_coding *mx, float *w_out /* [streams][1+G], may be NULL */,
+                          float *w_trace /* [total][1+G], may be NULL */);
+int lstm_hip_decode_mixed(lstm_hip_t *h, int32_t streams, const uint8_t *code, const uint64_t *code_off, const uint64_t *text_off,
+                          uint8_t *text, const lstm_hip_guidance *gd, const lstm_hip_mix_coding *mx,
+                          float *w_out /* [streams][1+G], may be NULL */);
 
 /* ---- adaptive coding: no checkpoint, the model trains on the bytes it has coded.  The handle's B
  *      streams are the coder's streams: stream s is text[text_off[s] .. text_off[s+1]), s < cfg.B (at most 4096).  With
